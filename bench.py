@@ -16,11 +16,17 @@ broadcast through the C ABI (tts_hip_comm_unique_id + tts_hip_broadcast_weights_
 reference's per-worker load), further runners of a rank share their rank's arena (tts_load_options::share_with); afterwards utterances
 are independent, no data-path collective -> "scaling": "weak".
 
-Prints ONE JSON line on rank 0 (see the task contract): metric/value/unit + roofline + cpu_baseline, plus SURVEY §8(d)'s second metric
-(batch-1 ms per decode step at T ~ 128 / 512 / 1024 / 2580, a 1024-step utterance), `long_utterances` (1024 audio steps per utterance,
-uniform and ragged batches) and `secondary` (short runs of BASELINE configs 2-4).  The extra sections share a wall-clock budget
-(`--time-budget-s`, default 480 s for the whole run; `time_budget` in the line names what was skipped): with the driver's `--steps 20 --warmup 5`
-the 25 timed steps take ~280 s on their own, and the contract's part must never be lost to an extra.
+Prints ONE JSON line on rank 0: metric/value/unit, ms_per_step (wall milliseconds of one timed step) and the configuration.  A plain run
+does only that: set up, `--warmup` untimed steps, `--steps` timed steps, the line.  `--full` adds everything else the benchmark measures:
+the roofline (the live per-kernel-family HIP-event timing of the DAC launches in the timed region + one eager pass), the cpu_baseline,
+SURVEY §8(d)'s second metric (batch-1 ms per decode step at T ~ 128 / 512 / 1024 / 2580, a 1024-step utterance), `long_utterances` (1024
+audio steps per utterance, uniform and ragged batches) and `secondary` (short runs of BASELINE configs 2-4).  The extra sections of a
+`--full` run share a wall-clock budget (`--time-budget-s`, default 550 s for the whole run; `time_budget` in the line names what was
+skipped): with `--steps 20 --warmup 5` the 25 timed steps take ~220 s on their own, and the contract's part must never be lost to an extra.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed back to the caller (every utterance's PCM) as .npy
+files: a fixed, seeded sample of whole utterances (pcm_sample.npy) and per-utterance statistics of all of them (pcm_stats.npy).  The
+inputs (weights, sentences, sampler seeds) depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -278,10 +284,11 @@ def self_launch(n):
     have = torch.cuda.device_count()
     if os.environ.get("TTS_BENCH_FORCE_DEVICE") is None and have < n:
         raise SystemExit(f"bench.py --gpus {n}: this box has {have} GPU(s); refusing to report an n_gpus={n} line from fewer devices")
+    import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     log("bench.py: starting", n, "ranks:", " ".join(cmd))
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))   # a child process, not an exec: this process has already asked the HIP runtime for its devices
 
 
 def broadcast_arena_ctx(L, ctx, rank, world, local_rank, backend, dist, torch):
@@ -328,10 +335,24 @@ def load_runners(path, args, rank, world, local_rank, backend, dist, torch, gen_
     return runners, info
 
 
-def run_all(runners, texts, timings_=None, stream=False, reps=1):
+def generate_batch_kept(rn, texts):
+    """Runner.generate_batch_sizes (tts_c_generate_batch, nothing copied) that also returns the call's PCM: a function of the utterance index giving
+    a view of the runner-owned samples, valid until the runner's next generate call (tts_c.h)."""
+    n = len(texts)
+    arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
+    data = (C.POINTER(C.c_float) * n)()
+    ns = (C.c_size_t * n)()
+    if rn.L.tts_c_generate_batch(rn.h, arr, n, C.byref(rn.cfg), data, ns) != 0:
+        raise runner.RunnerError(rn.L.tts_c_last_error().decode("utf-8", "replace"))
+    sizes = [int(ns[i]) for i in range(n)]
+    return sizes, lambda j: np.ctypeslib.as_array(data[j], shape=(sizes[j],)) if sizes[j] else np.zeros(0, dtype=np.float32)
+
+
+def run_all(runners, texts, timings_=None, stream=False, reps=1, kept=None):
     """Every runner (a host thread each) makes `reps` generate calls back to back; returns when all are done.  reps > 1: the runners of a GPU are not
     joined between their calls — a runner that finishes a batch starts its next one at once, as the workers of a server do, so one runner's codec passes
-    keep falling on the others' decoder loops instead of all runners idling into a common tail after every batch."""
+    keep falling on the others' decoder loops instead of all runners idling into a common tail after every batch.  kept (a list, one slot per runner):
+    each runner's last call leaves (sizes, pcm) there (generate_batch_kept) for --dump-outputs."""
     res = [None] * len(runners)
 
     def work(i):
@@ -339,7 +360,13 @@ def run_all(runners, texts, timings_=None, stream=False, reps=1):
             n, dt = 0, 0.0
             for _ in range(reps):
                 t0 = time.perf_counter()
-                sizes = runners[i].generate_stream(texts[i], sizes_only=True) if stream else runners[i].generate_batch_sizes(texts[i])
+                if stream:
+                    sizes = runners[i].generate_stream(texts[i], sizes_only=True)
+                elif kept is not None:
+                    sizes, pcm = generate_batch_kept(runners[i], texts[i])
+                    kept[i] = (sizes, pcm)
+                else:
+                    sizes = runners[i].generate_batch_sizes(texts[i])
                 n += sum(sizes)
                 dt += time.perf_counter() - t0
             res[i] = (n, dt / reps)
@@ -360,6 +387,32 @@ def run_all(runners, texts, timings_=None, stream=False, reps=1):
     if timings_ is not None:
         timings_.append(float(np.mean([r[1] for r in res])))
     return sum(r[0] for r in res)
+
+
+DUMP_SAMPLE_BYTES = 48_000_000   # whole utterances of pcm_sample.npy; with pcm_stats.npy the dump stays under 64 MB
+
+
+def dump_outputs(out_dir, kept):
+    """--dump-outputs: what the last timed step returned to the caller, every runner's tts_c_generate_batch PCM (runner r, utterance j -> row
+    r * batch + j).  pcm_stats.npy (float64, one row per utterance: samples, sum, sum of squares, max |x|) covers all of them; pcm_sample.npy
+    (float32, zero-padded rows) holds whole utterances drawn by a fixed seed, their row numbers and lengths in pcm_sample_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = [(r, j) for r, (sizes, _) in enumerate(kept) for j in range(len(sizes))]
+    stats = np.zeros((len(rows), 4), dtype=np.float64)
+    for k, (r, j) in enumerate(rows):
+        x = kept[r][1](j).astype(np.float64)
+        stats[k] = (x.size, x.sum(), np.square(x).sum(), np.abs(x).max() if x.size else 0.0)
+    longest = max(int(stats[:, 0].max()), 1) if rows else 1
+    n_pick = min(len(rows), max(1, DUMP_SAMPLE_BYTES // (4 * longest)))
+    pick = np.sort(np.random.default_rng(0).choice(len(rows), size=n_pick, replace=False)) if rows else np.zeros(0, dtype=np.int64)
+    sample = np.zeros((len(pick), longest), dtype=np.float32)
+    for i, k in enumerate(pick):
+        x = kept[rows[k][0]][1](rows[k][1])
+        sample[i, :x.size] = x
+    np.save(os.path.join(out_dir, "pcm_stats.npy"), stats)
+    np.save(os.path.join(out_dir, "pcm_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "pcm_sample_rows.npy"), np.stack([pick.astype(np.float64), stats[pick, 0]], axis=1) if len(pick) else np.zeros((0, 2)))
+    log(f"bench.py: wrote {len(rows)} utterances' statistics and {len(pick)} whole utterances ({sample.nbytes / 1e6:.1f} MB) to {out_dir}")
 
 
 def profile_get(L, rn):
@@ -604,8 +657,13 @@ def long_utterances(args, mk, wt, local_rank, gen_cfg, torch, L, budget=None, mo
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1); ms_per_step = the timed region's wall time / steps")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, cpu_baseline, decode_step_batch1, generate_batch1_end_to_end, secondary, long_utterances "
+                         "(each can still be left out with its --no-* option); without it a run is set-up, warm-up, timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (PCM: a seeded sample of whole utterances + statistics of all) as DIR/*.npy")
     ap.add_argument("--join-steps", action="store_true", help="join all runners of the GPU after every batch (rounds 1-5); default: the runners make their K calls back to back")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("TTS_BENCH_BATCH", "1024")),
                     help="utterances per context decoded in lock-step (1024: every decoder GEMM is whole rounds of tiles over the 256 CUs; 3 x 384 was the round-2 default)")
@@ -635,6 +693,10 @@ def main():
     ap.add_argument("--wtype", choices=["f16", "f32", "q8_0", "q5_0", "q4_0"], default="f16",
                     help="GGUF type of the decoder matrices (headline: f16; q*: integer path with Q8_0 activations)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: only what the headline needs
+        args.no_roofline = args.no_cpu_baseline = args.no_step_sweep = args.no_long = args.no_e2e = args.no_secondary = True
     budget = TimeBudget(args.time_budget_s)
 
     if args.workload in ("orpheus", "kokoro") and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.gpus > 1):
@@ -718,7 +780,9 @@ def main():
     if dist is not None:
         dist.barrier()
 
+    t_set = time.perf_counter()
     all_texts = [make_sentences(runners[0], args.batch, args.prompt_len, 1000 + rank * 64 + i) for i in range(args.streams)]
+    log(f"[rank {rank}] {args.streams} x {args.batch} sentences in {time.perf_counter() - t_set:.1f}s; {time.perf_counter() - _T_START:.1f}s since start")
 
     def barrier():
         torch.cuda.synchronize()
@@ -731,27 +795,34 @@ def main():
             if L.tts_hip_profile(rn.device_context(), mode) != 0:
                 raise RuntimeError(L.tts_hip_last_error().decode())
 
+    kept = [None] * len(runners)   # every runner's last call: what --dump-outputs writes
+    t_set = time.perf_counter()
     for _ in range(args.warmup):
-        run_all(runners, all_texts)
+        run_all(runners, all_texts, kept=kept)
     barrier()
-    profile(2)   # HIP-event pairs around the (never graph-captured) DAC launches, live in the timed region
+    log(f"[rank {rank}] {args.warmup} warm-up step(s) in {time.perf_counter() - t_set:.1f}s")
+    if not args.no_roofline:
+        profile(2)   # HIP-event pairs around the (never graph-captured) DAC launches, live in the timed region
     timings = []
     t0 = time.perf_counter()
     n_samples = 0
     if args.join_steps:
         for _ in range(args.steps):
-            n_samples += run_all(runners, all_texts, timings)
+            n_samples += run_all(runners, all_texts, timings, kept=kept)
     else:   # K steps = every runner's K batches, free-running between the two barriers (round 6; --join-steps: all runners joined after every batch)
-        n_samples += run_all(runners, all_texts, timings, reps=args.steps)
+        n_samples += run_all(runners, all_texts, timings, reps=args.steps, kept=kept)
     barrier()
     elapsed = time.perf_counter() - t0
     live = {}
-    for rn in runners:
-        for k, v in profile_get(L, rn).items():
-            a = live.setdefault(k, dict(ms_total=0.0, launches=0, bytes_total=0.0, flops_total=0.0))
-            for f in a:
-                a[f] += v[f]
-    profile(0)
+    if not args.no_roofline:
+        for rn in runners:
+            for k, v in profile_get(L, rn).items():
+                a = live.setdefault(k, dict(ms_total=0.0, launches=0, bytes_total=0.0, flops_total=0.0))
+                for f in a:
+                    a[f] += v[f]
+        profile(0)
+    if args.dump_outputs and rank == 0:   # before anything else calls a runner: the PCM is the runners' until their next call
+        dump_outputs(args.dump_outputs, kept)
     if dist is not None:
         elapsed, n_samples = tdist.reduce_timing(elapsed, n_samples, device=f"cuda:{local_rank}")
 
@@ -879,7 +950,7 @@ def main():
                 out["long_utterances"] = long_utterances(args, mk, wt, local_rank, gen_cfg, torch, L, budget, model=model)
             except Exception as e:   # the headline must survive a failure of an extra section
                 out["long_utterances"] = {"error": str(e)[:300]}
-    if rank == 0:
+    if rank == 0 and args.full:
         out["time_budget"] = budget.report()
     if rank == 0:
         print(json.dumps(out), flush=True)

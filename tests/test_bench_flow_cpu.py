@@ -9,6 +9,7 @@ import os
 import sys
 import types
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,8 +42,11 @@ def bench(monkeypatch):
         kv = []
         def write_gguf(self, p): open(p, "w").close()
 
-    def run_all(runners, texts, timings_=None, stream=False, reps=1):   # reps: the timed region's runners make their K calls back to back (round 6)
+    def run_all(runners, texts, timings_=None, stream=False, reps=1, kept=None):   # reps: the timed region's runners make their K calls back to back (round 6)
         n = sum(len(t) for t in texts)
+        if kept is not None:   # each runner's last call: utterance j of runner i is 100 samples of value i * 1000 + j
+            for i, t in enumerate(texts):
+                kept[i] = ([100] * len(t), lambda j, i=i: np.full(100, i * 1000 + j, dtype=np.float32))
         warm = len(texts[0]) > 1 and texts[0][0] == texts[0][-1] and texts[0][0].startswith("w" * 40)   # the long section's 48-step warm-up
         clock[0] += reps * ((61.0 if n > 100 else 2.0) if stream else (11.8 if len(texts[0]) >= 1000 else 5.0 if warm else 33.0))
         if timings_ is not None:
@@ -85,6 +89,7 @@ def bench(monkeypatch):
         lines = [ln for ln in buf.getvalue().strip().split("\n") if ln.startswith("{")]
         assert len(lines) == 1                                  # ONE JSON line
         return json.loads(lines[0]), clock[0]
+    go.module = b
     return go
 
 
@@ -95,7 +100,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_driver_flags_keep_the_contract_and_stay_inside_the_budget(bench):
     """the driver's round-end flags with this round's measured costs (profiles/r05/bench_full_call3.json: time_budget.sections): every extra
     section fits the default budget — round 4's line dropped the two ragged parts of long_utterances — and the whole run stays under it"""
-    d, total = bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    d, total = bench(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"])
     assert all(k in d for k in CONTRACT) and d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1
     assert d["roofline"]["bound"] in ("hbm", "mfma") and "frac" in d["roofline"] and "traffic" in d["roofline"]
     assert total <= 550 and d["time_budget"]["skipped"] == [], (total, d["time_budget"])
@@ -105,16 +110,55 @@ def test_driver_flags_keep_the_contract_and_stay_inside_the_budget(bench):
     assert all("value" in v for v in d["secondary"].values()) and "decode_step_batch1" in d and "generate_batch1_end_to_end" in d
     assert set(d["time_budget"]["sections"]) >= {"decode_step_batch1", "cpu_baseline", "long_utterances.uniform", "long_utterances.ragged"}
     # a slow first `import torch` eats into the extras (last wanted first), never into the contract
-    d, total = bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], start=100.0)
+    d, total = bench(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"], start=100.0)
     assert all(k in d for k in CONTRACT) and total <= 550 + 10
     assert d["time_budget"]["skipped"] and d["time_budget"]["skipped"][-1] == "long_utterances.uniform_same_mix" and "audio_seconds_per_sec" in d["long_utterances"]["uniform"]
 
 
 def test_default_and_unlimited_runs(bench):
-    d, _ = bench([])
+    d, _ = bench(["--full"])
     assert all(k in d for k in CONTRACT) and d["steps"] == 3 and d["warmup"] == 1
     assert {"uniform", "ragged", "ragged_stream", "uniform_same_mix"} <= set(d["long_utterances"]) and "of_uniform" in d["long_utterances"]["ragged_stream"]
-    d, _ = bench(["--time-budget-s", "0", "--steps", "20", "--warmup", "5"])
+    d, _ = bench(["--full", "--time-budget-s", "0", "--steps", "20", "--warmup", "5"])
     assert d["time_budget"]["skipped"] == [] and "of_lockstep_ragged" in d["long_utterances"]["ragged_stream"]
-    d, _ = bench(["--no-long", "--no-secondary", "--no-e2e", "--no-step-sweep"])
+    d, _ = bench(["--full", "--no-long", "--no-secondary", "--no-e2e", "--no-step-sweep"])
     assert all(k in d for k in CONTRACT) and "long_utterances" not in d and "secondary" not in d
+
+
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+EXTRAS = ("roofline", "roofline_families", "kernel_classes", "cpu_baseline", "decode_step_batch1", "generate_batch1_end_to_end", "secondary",
+          "long_utterances", "time_budget")
+
+
+def test_plain_run_is_set_up_warm_up_timed_steps_and_the_line(bench):
+    """without --full nothing but the headline runs: the fake clock sees start-up, the 5 warm-up calls and the 20 timed calls (11.8 s each), and
+    ms_per_step is one timed call"""
+    d, total = bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert all(k in d for k in HEADLINE) and not any(k in d for k in EXTRAS), sorted(d)
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert total == pytest.approx(15.0 + 25 * 11.8)
+    assert d["ms_per_step"] == pytest.approx(11800.0)
+    d, total = bench(["--steps", "7", "--warmup", "0"])
+    assert d["steps"] == 7 and d["ms_per_step"] == pytest.approx(11800.0) and total == pytest.approx(15.0 + 7 * 11.8)
+    with pytest.raises(SystemExit):
+        bench(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_last_steps_pcm(bench, tmp_path):
+    """--dump-outputs: statistics of every utterance of the last timed step (row = runner * batch + utterance) and whole utterances of a seeded
+    sample, all float32 / float64 .npy, the same sample on every run"""
+    bench.module.DUMP_SAMPLE_BYTES = 10 * 100 * 4          # ten of the stand-in's 100-sample utterances
+    bench(["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    bench(["--steps", "3", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+    assert sorted(os.listdir(tmp_path / "a")) == ["pcm_sample.npy", "pcm_sample_rows.npy", "pcm_stats.npy"]
+    load = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("pcm_stats", "pcm_sample", "pcm_sample_rows")}
+    assert all(v.dtype in (np.float32, np.float64) for v in load.values())
+    v = np.array([r * 1000 + j for r in range(3) for j in range(1024)], dtype=np.float64)   # the stand-in's utterance (r, j): 100 x (r * 1000 + j)
+    stats = load["pcm_stats"]
+    assert stats.shape == (3 * 1024, 4) and (stats[:, 0] == 100).all()
+    assert np.allclose(stats[:, 1], 100 * v) and np.allclose(stats[:, 2], 100 * v * v) and np.allclose(stats[:, 3], v)
+    rows, sample = load["pcm_sample_rows"], load["pcm_sample"]
+    assert sample.shape == (10, 100) and rows.shape == (10, 2) and (np.diff(rows[:, 0]) > 0).all() and (rows[:, 1] == 100).all()
+    assert (sample == v[rows[:, 0].astype(int)][:, None]).all()
+    for k, a in load.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy")), k

@@ -443,7 +443,7 @@ def test_two_rank_bench_flow_on_one_gpu(tmp_path):
     env = dict(os.environ, TTS_BENCH_FORCE_DEVICE="0", TTS_BENCH_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--model", "small",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--model", "small",
            "--batch", "3", "--streams", "2", "--audio-steps", "40", "--prompt-len", "6", "--no-cpu-baseline", "--no-step-sweep"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -482,72 +482,82 @@ int main() {
     assert run.stdout.split() == ["220500", "44100", "dummy", "0"]
 
 
-REFERENCE = "/root/reference"
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")   # the reference's applications, built by build() (oracle/Makefile) through the compat/ overlay
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "examples", "cli")), reason="needs the reference checkout (absent on the GPU box)")
+def _ref_bin(name):
+    exe = os.path.join(REF_BIN, name)
+    if not os.path.exists(exe):
+        pytest.skip(f"oracle/_ref/{name} not built (the reference was absent when build() ran)")
+    return exe
+
+
+def test_overlay_links_the_applications_and_lays_our_headers_over_them(tmp_path):
+    """compat/make_overlay.py on a stand-in tree of the reference's layout: the application sources become links to where they lie (nothing is
+    copied), common.h / ggml.h / util.h / loaders.h resolve to compat/, and the server page becomes the header the reference's CMake generates."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "compat"))
+    from make_overlay import LINKS, OURS, make_overlay
+    ref = tmp_path / "ref"
+    page = b"<!doctype html><title>tts</title>\n"
+    for rel in ["examples/cli/cli.cpp", "examples/cli/vad.h", "examples/cli/README.md", "examples/perf_battery/perf_battery.cpp",
+                "examples/server/server.cpp", "examples/server/httplib.h", "src/args.cpp", "include/args.h", "include/audio_file.h"]:
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text(f"// {rel}\n")
+    (ref / "examples/server/public").mkdir()
+    (ref / "examples/server/public/index.html").write_bytes(page)
+    ovl = make_overlay(str(ref), str(tmp_path / "ovl"))
+    for rel in ["examples/cli/cli.cpp", "examples/cli/vad.h", "examples/perf_battery/perf_battery.cpp", "examples/server/server.cpp",
+                "examples/server/httplib.h", "src/args.cpp", "include/args.h", "include/audio_file.h"]:
+        assert os.path.islink(os.path.join(ovl, rel)) and os.path.realpath(os.path.join(ovl, rel)) == str(ref / rel), rel
+    assert not os.path.lexists(os.path.join(ovl, "examples/cli/README.md"))    # only sources are linked
+    for rel in OURS:
+        assert open(os.path.join(ovl, rel)).read() == f'#pragma once\n#include "{os.path.join(ROOT, "compat", rel)}"\n'
+        assert os.path.exists(os.path.join(ROOT, "compat", rel)), rel
+    hpp = open(os.path.join(ovl, "examples/server/index.html.hpp")).read()
+    assert hpp == "unsigned char index_html[] = {" + ",".join(f"0x{c:02x}" for c in page) + "};\nunsigned int index_html_len = %d;\n" % len(page)
+    assert set(LINKS) >= {"examples/cli", "examples/perf_battery", "examples/server", "src/args.cpp"}
+
+
 def test_reference_cli_and_perf_battery_build_unchanged_against_the_overlay(tmp_path):
     """The reference's OWN examples/cli/cli.cpp (+ playback / vad / write_file / src/args.cpp) and examples/perf_battery/perf_battery.cpp,
     compiled from where they lie with compat/'s three headers in place of include/common.h, src/models/loaders.h and ggml.h
-    (compat/make_overlay.py), link against libtts.so and run on the weightless backend (BASELINE configs[0])."""
+    (compat/make_overlay.py, built by build() into oracle/_ref/), link against libtts.so and run on the weightless backend
+    (BASELINE configs[0])."""
     import subprocess
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "compat"))
-    from make_overlay import make_overlay
-    ovl = make_overlay(REFERENCE, str(tmp_path / "ovl"))
-    # the application sources are links into the checkout, not copies
-    assert os.path.realpath(os.path.join(ovl, "examples/cli/cli.cpp")) == os.path.join(REFERENCE, "examples/cli/cli.cpp")
-    host = os.path.join(ROOT, "tts.cpp_amd", "host")
-    link = ["-L", host, "-ltts", "-L", os.path.join(ROOT, "tts.cpp_amd"), "-ltts_hip", f"-Wl,-rpath,{host}",
-            f"-Wl,-rpath,{os.path.join(ROOT, 'tts.cpp_amd')}", "-Wl,-rpath,/opt/rocm/lib"]
-    builds = {
-        "tts-cli": ["examples/cli/cli.cpp", "examples/cli/playback.cpp", "examples/cli/vad.cpp", "examples/cli/write_file.cpp", "src/args.cpp"],
-        "perf_battery": ["examples/perf_battery/perf_battery.cpp", "src/args.cpp"],
-    }
-    for exe, srcs in builds.items():
-        cc = subprocess.run(["g++", "-std=c++20", "-O1", "-I", "include", *srcs, "-o", exe, *link], cwd=ovl, capture_output=True, text=True, timeout=600)
-        assert cc.returncode == 0, cc.stderr[-4000:]
+    cli, battery = _ref_bin("tts-cli_ref"), _ref_bin("perf_battery_ref")
     wav = tmp_path / "out.wav"
-    run = subprocess.run(["./tts-cli", "--model-path", "test:dummy", "--prompt", "Hello", "--save-path", str(wav)], cwd=ovl, capture_output=True, text=True, timeout=120)
+    run = subprocess.run([cli, "--model-path", "test:dummy", "--prompt", "Hello", "--save-path", str(wav)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "total time" in run.stdout                       # cli.cpp:10-20 through compat/include/ggml.h
     assert wav.stat().st_size == 44 + 2 * 5 * 44100          # "Hello" -> 5 s of 16-bit mono at 44.1 kHz (test runner: 1 s per character)
-    run = subprocess.run(["./perf_battery", "--model-path", "test:dummy"], cwd=ovl, capture_output=True, text=True, timeout=300)
+    run = subprocess.run([battery, "--model-path", "test:dummy"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "Mean Stats for arch dummy" in run.stdout and "Generation Real Time Factor" in run.stdout
     # no ggml anywhere in what was linked
-    ldd = subprocess.run(["ldd", os.path.join(ovl, "tts-cli")], capture_output=True, text=True).stdout
-    assert "libtts.so" in ldd and "ggml" not in ldd
+    for exe in (cli, battery):
+        ldd = subprocess.run(["ldd", exe], capture_output=True, text=True).stdout
+        assert "libtts.so" in ldd and "ggml" not in ldd
 
 
 def test_reference_server_builds_unchanged_against_the_overlay_and_serves_a_wav(tmp_path):
     """north_star: "drops in under the existing CLI/server".  The reference's OWN examples/server/server.cpp (with its vendored httplib.h / json.hpp),
     compiled from where it lies against compat/ (common.h, loaders.h, ggml.h = timers + GGML_ASSERT, util.h = the string helpers server.cpp:809-821
-    uses) and the page header its CMake generates from public/index.html (make_overlay.py writes it the way cmake/xxd.cmake does), linked to libtts.so,
-    started on the weightless backend; POST /v1/audio/speech must come back as a RIFF / WAVE body."""
+    uses; compat/shims/format stands in for <format> only on a toolchain without it) and the page header its CMake generates from public/index.html
+    (make_overlay.py writes it the way cmake/xxd.cmake does), linked to libtts.so by build() (oracle/_ref/tts-server_ref), started on the weightless
+    backend; POST /v1/audio/speech must come back as a RIFF / WAVE body."""
+    import hashlib
     import json
     import socket
     import subprocess
-    import sys
     import time
     import urllib.request
-    sys.path.insert(0, os.path.join(ROOT, "compat"))
-    from make_overlay import make_overlay
-    ovl = make_overlay(REFERENCE, str(tmp_path / "ovl"))
-    assert os.path.realpath(os.path.join(ovl, "examples/server/server.cpp")) == os.path.join(REFERENCE, "examples/server/server.cpp")
-    host = os.path.join(ROOT, "tts.cpp_amd", "host")
-    link = ["-L", host, "-ltts", "-L", os.path.join(ROOT, "tts.cpp_amd"), "-ltts_hip", f"-Wl,-rpath,{host}",
-            f"-Wl,-rpath,{os.path.join(ROOT, 'tts.cpp_amd')}", "-Wl,-rpath,/opt/rocm/lib", "-lpthread"]
-    # server.cpp:5 includes the C++20 header <format>; g++ 11 has none: compat/shims/format stands in ONLY then (a toolchain with <format> never sees it)
-    probe = subprocess.run(["g++", "-std=c++20", "-x", "c++", "-fsyntax-only", "-"], input="#include <format>\nint main(){}\n", capture_output=True, text=True)
-    shim = [] if probe.returncode == 0 else ["-I", os.path.join(ROOT, "compat", "shims")]
-    cc = subprocess.run(["g++", "-std=c++20", "-O1", "-I", "include", "-I", "examples/server", *shim, "examples/server/server.cpp", "src/args.cpp", "-o", "tts-server", *link],
-                        cwd=ovl, capture_output=True, text=True, timeout=900)
-    assert cc.returncode == 0, cc.stderr[-4000:]
+    server = _ref_bin("tts-server_ref")
+    page_sha256 = open(_ref_bin("index_html.sha256")).read().strip()
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    srv = subprocess.Popen(["./tts-server", "--model-path", "test:dummy", "--port", str(port)], cwd=ovl, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    srv = subprocess.Popen([server, "--model-path", "test:dummy", "--port", str(port)], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     try:
         base = f"http://127.0.0.1:{port}"
         for _ in range(100):
@@ -566,14 +576,14 @@ def test_reference_server_builds_unchanged_against_the_overlay_and_serves_a_wav(
         models = json.loads(urllib.request.urlopen(base + "/v1/models", timeout=5).read())
         assert models["data"] and models["data"][0]["object"] == "model"
         page = urllib.request.urlopen(base + "/", timeout=5).read()
-        assert page == open(os.path.join(REFERENCE, "examples/server/public/index.html"), "rb").read()   # the generated page header round-trips
+        assert hashlib.sha256(page).hexdigest() == page_sha256   # the generated page header round-trips (digest of public/index.html at build time)
     finally:
         srv.terminate()
         try:
             srv.wait(timeout=10)
         except subprocess.TimeoutExpired:
             srv.kill()
-    ldd = subprocess.run(["ldd", os.path.join(ovl, "tts-server")], capture_output=True, text=True).stdout
+    ldd = subprocess.run(["ldd", server], capture_output=True, text=True).stdout
     assert "libtts.so" in ldd and "ggml" not in ldd
 
 
