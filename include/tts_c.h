@@ -50,6 +50,20 @@ int           tts_c_generate_batch(tts_c_runner *r, const char *const *texts, in
  * decode steps) instead of idling until the longest one is done.  Same outputs as n generate() calls; data[i] valid until the next call. */
 int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, const float **data,
                                     size_t *n_outputs);
+/* Extension: chunked audio (tts_generation_runner::generate_chunked).  fn receives the utterance's PCM in consecutive pieces of at most
+ * chunk_frames codec frames while the utterance is still generating (pcm valid during the call only; utterance = 0 here, the text's index in
+ * the batch form); their concatenation equals tts_c_generate's / tts_c_generate_batch's audio.  fn returning 0 stops the generation at the
+ * next look-in point.  Returns 0 when done, 1 when fn stopped it, another value with tts_c_last_error() on error (chunk_frames == 0 is one).
+ * Parler-TTS streams; the other architectures generate the whole utterance and hand it out as one chunk. */
+typedef int (*tts_c_chunk_fn)(void *user, int utterance, const float *pcm, size_t n);
+int           tts_c_generate_chunked(tts_c_runner *r, const char *text, const tts_c_config *cfg, uint32_t chunk_frames, tts_c_chunk_fn fn, void *user);
+int           tts_c_generate_batch_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,
+                                           tts_c_chunk_fn fn, void *user);
+/* Test hook: the Parler runner's un-delay rule (parler_undelay) on delayed tokens [n_steps][n_heads] — the codes of the kept frames that are
+ * final after n_steps steps (finished != 0: the generation is over, every frame is judged).  out [frames][n_heads] may be NULL to count;
+ * returns the number of frames. */
+int64_t       tts_c_parler_final_frames(const uint32_t *tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, int finished, uint32_t *out,
+                                        uint64_t cap_frames);
 /* Placement of the NEXT tts_c_runner_from_file on the calling thread (host/common.h tts_load_options): device (< 0: TTS_HIP_DEVICE or
  * 0), lock-step KV slots (0: TTS_HIP_MAX_SEQS or 1), declare_only != 0: lay the model out without uploading its bytes — the weights
  * then arrive in tts_hip_arena_ptr(tts_c_runner_device_context(r)) by a collective and tts_hip_arena_filled() marks them present. */

@@ -180,6 +180,22 @@ typedef struct tts_hip_sampling {
 int tts_hip_parler_generate_sampled(tts_hip_ctx *ctx, uint32_t n_seqs, const uint32_t *start_pos,
                                     uint32_t n_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sampling,
                                     const float *uniforms, uint32_t *tokens_out, uint32_t *steps_done);
+/* The same loop in pieces, so that the host can work while steps run (the runner's chunked audio decodes codec windows meanwhile):
+ *   gen_begin   stages n_seqs prefilled sequences as tts_hip_parler_generate_greedy / _sampled do (sampling == NULL: sampler::max;
+ *               else sampler::sample with uniforms [max_steps][n_seqs][n_output_heads])
+ *   gen_launch  enqueues up to n_steps more steps on the context's stream and returns at once (nothing once every sequence has stopped
+ *               or max_steps have run)
+ *   gen_wait    synchronises and looks in: steps_done [n_seqs] as in generate_greedy (0: still running), *ran = steps run so far, and —
+ *               when tokens_out != NULL — the tokens of the steps no earlier gen_wait handed out, written at their places in
+ *               tokens_out [max_steps][n_seqs][n_output_heads].  Finished rows are compacted out of the forward at a wait whose step
+ *               count is a multiple of 32, whatever the launch sizes: the tokens equal those of generate_greedy / _sampled.
+ * The generation is over when every steps_done is non-zero or *ran == max_steps.  While steps are in flight the context's codec may run
+ * (tts_hip_dac_decode*: its own stream, no buffer shared with the decoder); any other decoder call needs a gen_wait first
+ * (tts_hip_parler_reset waits for and drops an unfinished loop). */
+int tts_hip_parler_gen_begin(tts_hip_ctx *ctx, uint32_t n_seqs, const uint32_t *start_pos, uint32_t max_steps, uint32_t bos, uint32_t eos,
+                             const tts_hip_sampling *sampling, const float *uniforms);
+int tts_hip_parler_gen_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_parler_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint32_t *ran);
 /* The device sampler alone on caller-supplied logits [n_rows][n_output_heads][output_vocab_size]
  * (uniforms [n_rows][n_output_heads]) -> tokens_out [n_rows][n_output_heads]; for parity tests.
  * last_ids / rep_counts [n_rows][n_output_heads]: the repetition state, read and updated in place (may be NULL when
@@ -388,6 +404,16 @@ int tts_hip_dac_decode(tts_hip_ctx *ctx, const uint32_t *codes, uint32_t frames,
  * codes: the utterances' code frames concatenated [sum(frames)][n_output_heads]; frames[n]; pcm_out: the PCM of
  * the utterances concatenated (frames[i] * prod(strides) samples each).  Results are identical to n single calls. */
 int tts_hip_dac_decode_batch(tts_hip_ctx *ctx, const uint32_t *codes, const uint32_t *frames, uint32_t n, float *pcm_out);
+/* Halo of the codec in code frames: the samples of frame j depend only on the codes of frames [j - h, j + h].  A pure function of
+ * dac_n_blocks / dac_stride / dac_padding (no device); h = 10 for the DAC-44k layout (strides 8, 8, 4, 2).  -1 on a layout it does not
+ * describe (padding > stride). */
+int tts_hip_dac_halo_frames(const tts_hip_desc *desc);
+/* n windows of code frames decoded in one pass as separate utterances (tts_hip_dac_decode_batch), each cropped to the samples of its frames
+ * [keep0[i], keep1[i]).  codes: the windows' frames concatenated; pcm_out: (keep1[i] - keep0[i]) * prod(strides) samples per window,
+ * concatenated.  A window that reaches h frames past its kept frames on each side (or the utterance's edge) reproduces the samples of
+ * the whole utterance's decode.  Blocks until done. */
+int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1,
+                               uint32_t n, float *pcm_out);
 
 /* ---- introspection (tests, bench) -------------------------------------------------------- */
 /* Copy an internal buffer to the host.  what: "hidden" (final-normed hidden of the last forward,

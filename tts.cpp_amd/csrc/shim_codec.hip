@@ -611,7 +611,11 @@ static int dac_decode_batch(tts_hip_ctx *c, const uint32_t *codes, const uint32_
             if (!c->dac_stream) {
                 rc = dac_decode_batch_on(c, codes + code_off * c->d_ncb, frames + g0, m, pcm_out + pcm_off);
             } else {
-                // the decoder stream is idle here (every decoder entry point synchronises before it returns)
+                // The decoder stream may still be running steps here: tts_hip_parler_gen_launch returns with them in flight, and the runner's
+                // chunked audio decodes its windows in that time.  The two streams share no buffer: the pass reads the weight arena and the packed
+                // codec weights (read-only for both), writes the device's codec buffers (g_dac_buffers, under the pass mutex), c->d_frames and
+                // c->dac_dbg; the decoder writes its own staging, KV cache and token buffers.  Without a dac_stream the pass runs on c->stream,
+                // behind those steps (correct, no overlap).
                 hipStream_t ar = c->stream;
                 c->stream = c->dac_stream;
                 rc = dac_decode_batch_on(c, codes + code_off * c->d_ncb, frames + g0, m, pcm_out + pcm_off);
@@ -817,6 +821,67 @@ extern "C" int tts_hip_dac_decode(tts_hip_ctx *c, const uint32_t *codes, uint32_
 extern "C" int tts_hip_dac_decode_batch(tts_hip_ctx *c, const uint32_t *codes, const uint32_t *frames, uint32_t n, float *pcm_out) {
     if (n == 0) return 0;
     return dac_decode_batch(c, codes, frames, n, pcm_out);
+}
+
+// Halo of the DAC decoder in code frames: the output samples of frame j depend on the codes of frames [j - h, j + h] only.  Back from the
+// samples [0, U) of frame 0 through the layers (dac_decode_batch_on's order, reversed), as an interval of positions at each stage's rate:
+//   final conv k = 7 (padding 3)                          [lo, hi] -> [lo - 3, hi + 3]
+//   per block, last first: 3 residual units, dilation d = 9, 3, 1: k = 7 conv (padding 3d) + k = 1 conv  -> [lo - 3d, hi + 3d] each
+//                          transposed conv (stride s, kernel 2s, padding p): output t = i s - p + k, 0 <= k < 2s
+//                                                          -> [ceil((lo + p - 2s + 1) / s), floor((hi + p) / s)]
+//   initial conv k = 7 (padding 3)                        -> [lo - 3, hi + 3]
+//   quantizer / embedding: frame by frame
+// h = max(-lo, hi) at the codes.  DAC-44k (strides 8, 8, 4, 2, paddings 4, 4, 2, 1): [0, 511] -> [-3, 514] -> block 4 [-42, 553] ->
+// [-22, 277] -> block 3 [-61, 316] -> [-16, 79] -> block 2 [-55, 118] -> [-8, 15] -> block 1 [-47, 54] -> [-7, 7] -> [-10, 10]: h = 10.
+// A window of frames decoded as an utterance of its own therefore reproduces the full decode's samples of every frame at least h frames
+// from its cut edges: with p <= s each stage's interval lies inside the window's extent at that stage, so no sample the kept frames read
+// is one of the window's zero paddings (at a true utterance edge the full decode pads with the same zeros).  tests/test_chunked_cpu.py
+// measures h on the oracle and checks that h - 1 is not enough.
+static int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+extern "C" int tts_hip_dac_halo_frames(const tts_hip_desc *d) {
+    if (!d) return set_err("tts_hip_dac_halo_frames: null desc");
+    if (d->dac_n_blocks == 0 || d->dac_n_blocks > TTS_HIP_MAX_DAC_BLOCKS) return set_err("tts_hip_dac_halo_frames: %u codec blocks", d->dac_n_blocks);
+    int64_t up = 1;
+    for (uint32_t i = 0; i < d->dac_n_blocks; i++) {
+        if (d->dac_stride[i] == 0 || d->dac_padding[i] > d->dac_stride[i])
+            return set_err("tts_hip_dac_halo_frames: block %u has stride %u, padding %u (needs 0 <= padding <= stride >= 1)", i, d->dac_stride[i], d->dac_padding[i]);
+        up *= d->dac_stride[i];
+    }
+    int64_t lo = -3, hi = up - 1 + 3;   // the final conv
+    for (int bi = (int) d->dac_n_blocks - 1; bi >= 0; bi--) {
+        const int64_t s = d->dac_stride[bi], p = d->dac_padding[bi];
+        for (int dil = 1; dil <= 9; dil *= 3) { lo -= 3 * dil; hi += 3 * dil; }
+        lo = -floor_div(-(lo + p - 2 * s + 1), s);
+        hi = floor_div(hi + p, s);
+    }
+    lo -= 3; hi += 3;   // the initial conv
+    return (int) std::max(-lo, hi);
+}
+
+// n windows of code frames in one codec pass (dac_decode_batch: the same kernels, groups, pass mutex, buffers and stream), each cropped to
+// the samples of its frames [keep0, keep1) by an offset copy.
+extern "C" int tts_hip_dac_decode_windows(tts_hip_ctx *c, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1,
+                                          uint32_t n, float *pcm_out) {
+    if (n == 0) return 0;
+    if (!c || !codes || !frames || !keep0 || !keep1 || !pcm_out) return set_err("tts_hip_dac_decode_windows: null argument");
+    size_t tot = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (keep0[i] > keep1[i] || keep1[i] > frames[i]) return set_err("tts_hip_dac_decode_windows: window %u keeps frames [%u, %u) of %u", i, keep0[i], keep1[i], frames[i]);
+        tot += frames[i];
+    }
+    if (!c->finalized || !c->has_dac) return set_err("tts_hip_dac_decode: context has no finalized DAC");
+    const size_t U = (size_t) c->d_up;
+    c->win_pcm.resize(tot * U);
+    CHK(dac_decode_batch(c, codes, frames, n, c->win_pcm.data()));
+    size_t off = 0, o = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const size_t k = (size_t) (keep1[i] - keep0[i]) * U;
+        memcpy(pcm_out + o, c->win_pcm.data() + off + (size_t) keep0[i] * U, k * 4);
+        o += k;
+        off += (size_t) frames[i] * U;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

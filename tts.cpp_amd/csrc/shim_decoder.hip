@@ -1137,6 +1137,10 @@ int ready(tts_hip_ctx *c, const char *who) {
 
 extern "C" int tts_hip_parler_reset(tts_hip_ctx *c) {
     CHK(ready(c, "tts_hip_parler_reset"));
+    if (c->gl.active) {   // a generation left between gen_launch and its last gen_wait: let its steps finish, forget it
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->gl = tts_hip_ctx::GenLoop{};
+    }
     return 0;  // positions are caller-supplied; the cache is overwritten position by position like the reference's
 }
 
@@ -1311,18 +1315,25 @@ static void drop_gen_graphs(tts_hip_ctx *c) {
     }
 }
 
-// the device-resident generation loop; mode MODE_GEN (sampler::max) or MODE_GEN_SAMPLE (sample_kernel, c->smp / c->d_uniforms)
-static int generate_loop(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *start_pos, uint32_t n_steps,
-                         uint32_t bos, uint32_t eos, uint32_t *tokens_out, uint32_t *steps_done) {
-    if (!start_pos || !tokens_out) return set_err("generate_greedy: null argument");
-    if (n == 0 || (int) n > c->RMAX || n > c->d.max_seqs) return set_err("generate_greedy: n_seqs=%u out of range", n);
-    if (bos >= (uint32_t) c->EROWS || eos >= (uint32_t) c->EROWS) return set_err("generate_greedy: bos/eos outside the embedding table");
+// The device-resident generation loop, cut at the host's look-in points so that a caller can work between them (the runner's chunked
+// audio decodes codec windows while the next steps run):
+//   gen_begin    stages the rows (bos ids, start positions, cache slot = utterance index, step counters, EOS flags) and the sampler
+//   gen_launch   enqueues up to k more steps on the context's stream and returns at once
+//   gen_wait     synchronises, reads steps_done back (the look-in), compacts the rows every 32 steps, hands out the new steps' tokens
+// mode MODE_GEN (sampler::max) or MODE_GEN_SAMPLE (sample_kernel, c->smp / c->d_uniforms).  tts_hip_parler_generate_greedy / _sampled are
+// begin + (launch 32, wait) to the end.  Row compaction happens only at a wait whose step count is a multiple of 32, whatever the launch
+// sizes were: the rows of every forward, and hence every token, do not depend on how a caller splits the launches.
+static int gen_begin(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *start_pos, uint32_t n_steps, uint32_t bos, uint32_t eos) {
+    c->gl = tts_hip_ctx::GenLoop{};
+    if (!start_pos) return set_err("gen_begin: null argument");
+    if (n == 0 || (int) n > c->RMAX || n > c->d.max_seqs) return set_err("gen_begin: n_seqs=%u out of range", n);
+    if (bos >= (uint32_t) c->EROWS || eos >= (uint32_t) c->EROWS) return set_err("gen_begin: bos/eos outside the embedding table");
     c->host_pos.resize(n);
     for (uint32_t r = 0; r < n; r++) {
         // a row may be asked for more steps than its cache holds: it finishes when its position reaches the end of the cache
         // (steps_done says after how many steps) and idles there while the other rows go on
         if (start_pos[r] >= (uint32_t) c->KVPOS || start_pos[r] >= (uint32_t) c->NPOS)
-            return set_err("generate_greedy: sequence %u starts outside the cached positions (%u >= %d)", r, start_pos[r], c->KVPOS);
+            return set_err("gen_begin: sequence %u starts outside the cached positions (%u >= %d)", r, start_pos[r], c->KVPOS);
         for (int i = 0; i < c->NO; i++) c->h_ids[r * c->NO + i] = bos;  // model.cpp:781 with current_step == 0
         c->h_pos[r] = start_pos[r];
         c->h_seq[r] = r;
@@ -1355,60 +1366,99 @@ static int generate_loop(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *s
         c->gs_graphs = false;
     }
     c->gs = tts_hip_ctx::GenStream{};   // a batch generation ends any stream of this context
-    // Row compaction.  Every 32 steps the host looks at steps_done (one small D2H + sync) to see whether check_stopping() has fired for every
-    // utterance; utterances that have finished (EOS on every head, or their position reached max_generation) used to idle in the lock-step
-    // forward until the last one was done — a ragged batch paid for its longest row (165 against 323 audio-s/s at 1024 steps).  Now the
-    // finished rows are dropped from the forward: the live rows are gathered to the front (ids, position, cache slot, step counter; everything
-    // else is indexed by utterance) and the loop goes on with R' = the live count rounded up to a multiple of 128 (64 below 256) — finished
-    // rows fill the remainder, so that a forward keeps whole row tiles and only a handful of row counts are ever captured as graphs.
-    std::vector<uint32_t> row_utt(n);            // utterance of row r
-    for (uint32_t r = 0; r < n; r++) row_utt[r] = r;
-    uint32_t R = n, ran = 0;
-    for (uint32_t s = 0; s < n_steps; s++) {
-        for (uint32_t r = 0; r < R; r++) c->host_pos[r] = std::min<uint32_t>(start_pos[row_utt[r]] + s, (uint32_t) std::min(c->KVPOS, c->NPOS) - 1);
-        CHK(run_step(c, (int) R, mode, bos, eos));
-        ran = s + 1;
-        if ((ran % 32) == 0 && ran < n_steps) {
-            HIPCHK(hipMemcpyAsync(c->h_tok, c->d_steps_done, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            uint32_t live = 0;
-            for (uint32_t r = 0; r < R; r++) live += c->h_tok[row_utt[r]] == 0;
-            if (live == 0) break;
-            const uint32_t q = live >= 256 ? 128 : 64;
-            const uint32_t R2 = std::min(R, (live + q - 1) / q * q);
-            if (c->gen_compact && R2 < R) {
-                std::vector<uint32_t> map, fill;
-                for (uint32_t r = 0; r < R; r++) (c->h_tok[row_utt[r]] == 0 ? map : fill).push_back(r);
-                for (uint32_t i = 0; map.size() < R2; i++) map.push_back(fill[i]);
-                std::sort(map.begin(), map.end());   // keep the row order: rows only move towards lower indices
-                std::vector<uint32_t> utt2(R2);
-                for (uint32_t r = 0; r < R2; r++) utt2[r] = row_utt[map[r]];
-                GatherArgs ga{};
-                ga.map = c->d_gather; ga.R2 = (int) R2; ga.n_out = c->NO;
-                ga.ids = c->d_ids; ga.pos = c->d_pos; ga.seq = c->d_seq; ga.step = c->d_step;
-                ga.s_ids = c->d_gather + c->RMAX; ga.s_pos = ga.s_ids + (size_t) c->RMAX * c->NO; ga.s_seq = ga.s_pos + c->RMAX; ga.s_step = ga.s_seq + c->RMAX;
-                HIPCHK(hipMemcpyAsync(c->d_gather, map.data(), (size_t) R2 * 4, hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(R2), dim3(64), 0, c->stream, ga, 0);
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(R2), dim3(64), 0, c->stream, ga, 1);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(c->stream));   // map lives on the host stack
-                row_utt.swap(utt2);
-                R = R2;
-            }
+    auto &g = c->gl;
+    g.mode = mode; g.n = n; g.n_steps = n_steps; g.bos = bos; g.eos = eos; g.R = n;
+    g.start.assign(start_pos, start_pos + n);
+    g.row_utt.resize(n);
+    for (uint32_t r = 0; r < n; r++) g.row_utt[r] = r;   // utterance of row r
+    g.active = true;
+    g.done = n_steps == 0;
+    return 0;
+}
+
+static int gen_launch(tts_hip_ctx *c, uint32_t k) {
+    auto &g = c->gl;
+    if (!g.active) return set_err("gen_launch: no generation (tts_hip_parler_gen_begin)");
+    if (g.done) return 0;
+    const uint32_t end = std::min(g.n_steps, g.launched + k), max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS) - 1;
+    for (uint32_t s = g.launched; s < end; s++) {
+        for (uint32_t r = 0; r < g.R; r++) c->host_pos[r] = std::min<uint32_t>(g.start[g.row_utt[r]] + s, max_pos);
+        CHK(run_step(c, (int) g.R, g.mode, g.bos, g.eos));
+        g.launched = s + 1;
+    }
+    return 0;
+}
+
+// Row compaction.  At every look-in the host reads steps_done (one small D2H + sync) to see whether check_stopping() has fired for every
+// utterance; utterances that have finished (EOS on every head, or their position reached max_generation) used to idle in the lock-step
+// forward until the last one was done — a ragged batch paid for its longest row (165 against 323 audio-s/s at 1024 steps).  Now the
+// finished rows are dropped from the forward: the live rows are gathered to the front (ids, position, cache slot, step counter; everything
+// else is indexed by utterance) and the loop goes on with R' = the live count rounded up to a multiple of 128 (64 below 256) — finished
+// rows fill the remainder, so that a forward keeps whole row tiles and only a handful of row counts are ever captured as graphs.
+static int gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint32_t *ran_out) {
+    auto &g = c->gl;
+    if (!g.active) return set_err("gen_wait: no generation (tts_hip_parler_gen_begin)");
+    const uint32_t n = g.n, ran = g.launched;
+    HIPCHK(hipMemcpyAsync(c->h_tok, c->d_steps_done, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint32_t live = 0;
+    for (uint32_t r = 0; r < g.R; r++) live += c->h_tok[g.row_utt[r]] == 0;
+    if (live == 0 || ran >= g.n_steps) g.done = true;
+    if (!g.done && ran > 0 && (ran % 32) == 0) {
+        const uint32_t q = live >= 256 ? 128 : 64;
+        const uint32_t R2 = std::min(g.R, (live + q - 1) / q * q);
+        if (c->gen_compact && R2 < g.R) {
+            std::vector<uint32_t> map, fill;
+            for (uint32_t r = 0; r < g.R; r++) (c->h_tok[g.row_utt[r]] == 0 ? map : fill).push_back(r);
+            for (uint32_t i = 0; map.size() < R2; i++) map.push_back(fill[i]);
+            std::sort(map.begin(), map.end());   // keep the row order: rows only move towards lower indices
+            std::vector<uint32_t> utt2(R2);
+            for (uint32_t r = 0; r < R2; r++) utt2[r] = g.row_utt[map[r]];
+            GatherArgs ga{};
+            ga.map = c->d_gather; ga.R2 = (int) R2; ga.n_out = c->NO;
+            ga.ids = c->d_ids; ga.pos = c->d_pos; ga.seq = c->d_seq; ga.step = c->d_step;
+            ga.s_ids = c->d_gather + c->RMAX; ga.s_pos = ga.s_ids + (size_t) c->RMAX * c->NO; ga.s_seq = ga.s_pos + c->RMAX; ga.s_step = ga.s_seq + c->RMAX;
+            HIPCHK(hipMemcpyAsync(c->d_gather, map.data(), (size_t) R2 * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(R2), dim3(64), 0, c->stream, ga, 0);
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(R2), dim3(64), 0, c->stream, ga, 1);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(c->stream));   // map lives on the host stack
+            g.row_utt.swap(utt2);
+            g.R = R2;
         }
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(tokens_out, c->d_tokens_out, (size_t) ran * n * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+    if (steps_done) memcpy(steps_done, c->h_tok, (size_t) n * 4);
+    if (tokens_out && ran > g.copied) {   // only the steps no earlier wait handed out: [copied, ran) of tokens_out [n_steps][n][heads]
+        const size_t o = (size_t) g.copied * n * c->NO;
+        HIPCHK(hipMemcpyAsync(tokens_out + o, c->d_tokens_out + o, (size_t) (ran - g.copied) * n * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        g.copied = ran;
+    }
+    if (ran_out) *ran_out = ran;
+    return 0;
+}
+
+// begin + (launch 32, wait) until check_stopping() has fired for every utterance or the steps are spent; one copy of the tokens at the end
+static int generate_loop(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done) {
+    if (!tokens_out) return set_err("generate: null tokens_out");
+    const uint32_t n_steps = c->gl.n_steps, n = c->gl.n;
+    uint32_t ran = 0;
+    while (!c->gl.done) {
+        CHK(gen_launch(c, 32));
+        CHK(gen_wait(c, nullptr, nullptr, &ran));
+    }
+    CHK(gen_wait(c, tokens_out, steps_done, &ran));
     if (ran < n_steps) memset(tokens_out + (size_t) ran * n * c->NO, 0, (size_t) (n_steps - ran) * n * c->NO * 4);
-    if (steps_done) HIPCHK(hipMemcpyAsync(steps_done, c->d_steps_done, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    c->gl.active = false;
     return 0;
 }
 
 extern "C" int tts_hip_parler_generate_greedy(tts_hip_ctx *c, uint32_t n, const uint32_t *start_pos, uint32_t n_steps,
                                               uint32_t bos, uint32_t eos, uint32_t *tokens_out, uint32_t *steps_done) {
     CHK(ready(c, "tts_hip_parler_generate_greedy"));
-    return generate_loop(c, MODE_GEN, n, start_pos, n_steps, bos, eos, tokens_out, steps_done);
+    if (!tokens_out) return set_err("generate_greedy: null argument");
+    CHK(gen_begin(c, MODE_GEN, n, start_pos, n_steps, bos, eos));
+    return generate_loop(c, tokens_out, steps_done);
 }
 
 static int check_sampling(const tts_hip_ctx *c, const tts_hip_sampling *sp, const char *what) {
@@ -1450,13 +1500,11 @@ int stage_penalty(tts_hip_ctx *c, float penalty, int n) {
     return 0;
 }
 
-extern "C" int tts_hip_parler_generate_sampled(tts_hip_ctx *c, uint32_t n, const uint32_t *start_pos, uint32_t n_steps,
-                                               uint32_t bos, uint32_t eos, const tts_hip_sampling *sp, const float *uniforms,
-                                               uint32_t *tokens_out, uint32_t *steps_done) {
-    CHK(ready(c, "tts_hip_parler_generate_sampled"));
-    CHK(check_sampling(c, sp, "tts_hip_parler_generate_sampled"));
-    if (!uniforms) return set_err("tts_hip_parler_generate_sampled: null uniforms");
-    if (n == 0 || (int) n > c->RMAX || n > c->d.max_seqs) return set_err("generate_sampled: n_seqs=%u out of range", n);
+// the sampler's state for a sampled generation of n utterances: parameters, uniforms [n_steps][n][heads], penalty table, sampler::reset
+static int stage_sampler(tts_hip_ctx *c, uint32_t n, uint32_t n_steps, const tts_hip_sampling *sp, const float *uniforms, const char *what) {
+    CHK(check_sampling(c, sp, what));
+    if (!uniforms) return set_err("%s: null uniforms", what);
+    if (n == 0 || (int) n > c->RMAX || n > c->d.max_seqs) return set_err("%s: n_seqs=%u out of range", what, n);
     if (sp->top_k != c->smp.top_k || sp->top_p != c->smp.top_p || sp->temperature != c->smp.temperature ||
         (sp->repetition_penalty != 1.0f) != (c->smp.repetition_penalty != 1.0f)) {
         drop_gen_graphs(c);  // parameters are baked into the captured sample_kernel launch
@@ -1468,7 +1516,36 @@ extern "C" int tts_hip_parler_generate_sampled(tts_hip_ctx *c, uint32_t n, const
         HIPCHK(hipMemsetAsync(c->d_last, 0xFF, (size_t) n * c->NO * 4, c->stream));
         HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) n * c->NO * 4, c->stream));
     }
-    return generate_loop(c, MODE_GEN_SAMPLE, n, start_pos, n_steps, bos, eos, tokens_out, steps_done);
+    return 0;
+}
+
+extern "C" int tts_hip_parler_generate_sampled(tts_hip_ctx *c, uint32_t n, const uint32_t *start_pos, uint32_t n_steps,
+                                               uint32_t bos, uint32_t eos, const tts_hip_sampling *sp, const float *uniforms,
+                                               uint32_t *tokens_out, uint32_t *steps_done) {
+    CHK(ready(c, "tts_hip_parler_generate_sampled"));
+    CHK(stage_sampler(c, n, n_steps, sp, uniforms, "tts_hip_parler_generate_sampled"));
+    if (!tokens_out) return set_err("generate_sampled: null argument");
+    CHK(gen_begin(c, MODE_GEN_SAMPLE, n, start_pos, n_steps, bos, eos));
+    return generate_loop(c, tokens_out, steps_done);
+}
+
+// the loop in pieces (include/tts_hip.h)
+extern "C" int tts_hip_parler_gen_begin(tts_hip_ctx *c, uint32_t n, const uint32_t *start_pos, uint32_t max_steps, uint32_t bos, uint32_t eos,
+                                        const tts_hip_sampling *sp, const float *uniforms) {
+    CHK(ready(c, "tts_hip_parler_gen_begin"));
+    c->gl = tts_hip_ctx::GenLoop{};
+    if (sp) CHK(stage_sampler(c, n, max_steps, sp, uniforms, "tts_hip_parler_gen_begin"));
+    return gen_begin(c, sp ? MODE_GEN_SAMPLE : MODE_GEN, n, start_pos, max_steps, bos, eos);
+}
+
+extern "C" int tts_hip_parler_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    CHK(ready(c, "tts_hip_parler_gen_launch"));
+    return gen_launch(c, n_steps);
+}
+
+extern "C" int tts_hip_parler_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint32_t *ran) {
+    CHK(ready(c, "tts_hip_parler_gen_wait"));
+    return gen_wait(c, tokens_out, steps_done, ran);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -239,6 +239,16 @@ struct tts_hip_ctx {
     } gs;
     uint32_t gs_baked_steps = 0;    // ... and the step budget they carry
     bool gs_graphs = false;         // the captured generation graphs were made for a stream (feed_kernel's padding slot baked in)
+    // the generation loop between tts_hip_parler_gen_begin and its last gen_wait: launch enqueues steps, wait looks in
+    struct GenLoop {
+        bool active = false, done = false;
+        int mode = 0;
+        uint32_t n = 0, n_steps = 0, bos = 0, eos = 0;
+        uint32_t R = 0;          // rows of the forward (<= n after a compaction)
+        uint32_t launched = 0;   // steps enqueued so far
+        uint32_t copied = 0;     // steps whose tokens a gen_wait has handed out
+        std::vector<uint32_t> start, row_utt;   // start position per utterance; utterance of row r
+    } gl;
     int gen_total = 0;              // utterances of the generation loop under way (rows of the forward <= this after a compaction)
     bool gen_compact = true;        // TTS_HIP_GEN_COMPACT=0: finished utterances keep idling in the lock-step forward
     uint32_t *d_tokens_out = nullptr;
@@ -256,6 +266,7 @@ struct tts_hip_ctx {
     size_t d_frames_cap = 0;
     bool debug = false;
     std::map<int, std::vector<float>> dac_dbg;
+    std::vector<float> win_pcm;    // tts_hip_dac_decode_windows: the windows' whole PCM before the crop
     std::map<size_t, float *> packed;  // arena offset of a conv weight -> its MFMA-tile-packed copy
     std::set<size_t> packed_direct;    // ... of those, the k = 1 weights packed as [cin][cout] for conv1x1_direct_kernel
     std::map<size_t, _Float16 *> packed16;  // same, fp16 images (dac_f16)

@@ -87,6 +87,7 @@ EXPORTS = [
     "tts_hip_set_debug", "tts_hip_profile", "tts_hip_profile_get", "tts_hip_kclass_name", "tts_hip_stream",
     "tts_hip_synchronize", "tts_hip_dac_arith", "tts_hip_broadcast_weights", "tts_hip_comm_unique_id", "tts_hip_broadcast_weights_rank", "tts_hip_tune",
     "tts_hip_parler_stream_begin", "tts_hip_parler_stream_admit", "tts_hip_parler_stream_run", "tts_hip_parler_stream_collect", "tts_hip_parler_stream_end",
+    "tts_hip_parler_gen_begin", "tts_hip_parler_gen_launch", "tts_hip_parler_gen_wait", "tts_hip_dac_halo_frames", "tts_hip_dac_decode_windows",
 ]
 
 class Sampling(C.Structure):
@@ -181,8 +182,31 @@ def load_lib():
     L.tts_hip_parler_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
     L.tts_hip_parler_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
     L.tts_hip_parler_stream_end.argtypes = [vp]
+    L.tts_hip_parler_gen_begin.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Sampling), f32p]
+    L.tts_hip_parler_gen_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_parler_gen_wait.argtypes = [vp, u32p, u32p, u32p]
+    L.tts_hip_dac_halo_frames.argtypes = [C.POINTER(Desc)]
+    L.tts_hip_dac_decode_windows.argtypes = [vp, u32p, u32p, u32p, u32p, C.c_uint32, f32p]
     _lib = L
     return L
+
+
+def desc_for(cfg):
+    """the codec part of a tts_hip_desc for a synth config (what tts_hip_dac_halo_frames reads)"""
+    d = Desc()
+    d.struct_size = C.sizeof(Desc)
+    d.dac_n_blocks = len(cfg.strides)
+    for i, (s, p) in enumerate(zip(cfg.strides, cfg.paddings)):
+        d.dac_stride[i], d.dac_padding[i] = s, p
+    return d
+
+
+def dac_halo_frames(desc):
+    """tts_hip_dac_halo_frames: a pure function of the codec layout, no device needed"""
+    h = load_lib().tts_hip_dac_halo_frames(C.byref(desc))
+    if h < 0:
+        raise HipError(load_lib().tts_hip_last_error().decode("utf-8", "replace"))
+    return h
 
 
 def _u32(a):
@@ -397,6 +421,28 @@ class HipEngine:
         out = np.empty(frames * self.cfg.hop, dtype=np.float32)
         self._chk(self.L.tts_hip_dac_decode(self.ctx, ap, frames, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def dac_halo_frames(self):
+        return dac_halo_frames(self.desc)
+
+    def dac_decode_windows(self, windows):
+        """windows: list of (codes [frames][n_out], keep0, keep1) -> list of the PCM of frames [keep0, keep1) of each, one codec pass"""
+        codes = [np.asarray(c, dtype=np.uint32).reshape(-1, self.cfg.n_out) for c, _, _ in windows]
+        frames = np.array([len(c) for c in codes], dtype=np.uint32)
+        k0 = np.array([w[1] for w in windows], dtype=np.uint32)
+        k1 = np.array([w[2] for w in windows], dtype=np.uint32)
+        allc, cp = _u32(np.concatenate(codes) if codes else np.zeros(0))
+        out = np.empty(max(int((k1.astype(np.int64) - k0).sum()) * self.cfg.hop, 1), dtype=np.float32)
+        _, fp = _u32(frames)
+        _, k0p = _u32(k0)
+        _, k1p = _u32(k1)
+        self._chk(self.L.tts_hip_dac_decode_windows(self.ctx, cp, fp, k0p, k1p, len(windows), out.ctypes.data_as(C.POINTER(C.c_float))))
+        res, o = [], 0
+        for a, b in zip(k0, k1):
+            m = int(b - a) * self.cfg.hop
+            res.append(out[o:o + m].copy())
+            o += m
+        return res
 
     def dac_decode_batch(self, codes_list):
         """codes_list: list of [frames_i][n_out] arrays -> list of PCM arrays"""

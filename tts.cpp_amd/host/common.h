@@ -124,6 +124,18 @@ struct tts_generation_runner : tts_runner {
     void             generate_stream(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
                                      const generation_configuration & config);
 
+    // ---- extension: chunked audio — PCM handed out while the utterance is still generating ------------------------------------------
+    // on_chunk receives consecutive pieces of the utterance's audio, at most chunk_frames codec frames each (the last one may be shorter);
+    // their concatenation equals generate()'s PCM.  The pointer is valid during the call only.  on_chunk returning false stops the
+    // generation at the next look-in point; the runner stays usable.  chunk_frames == 0 is an error.  The default generates the whole
+    // utterance and hands it out as one chunk; parler_runner streams.
+    virtual void generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                                  const std::function<bool(const float *, size_t)> & on_chunk);
+    // the same for a batch: chunks of each utterance arrive in order, tagged with the utterance's index; their concatenation equals
+    // generate_batch()'s audio of that utterance
+    virtual void generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                        const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
+
   protected:
     std::vector<std::vector<float>> batch_store_;  // audio of the default generate_batch
 };

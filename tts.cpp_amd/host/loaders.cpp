@@ -61,6 +61,24 @@ void tts_generation_runner::generate_batch(const std::vector<std::string> & sent
     }
 }
 
+// chunked audio, the defaults: the whole utterance, then one chunk
+void tts_generation_runner::generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                                             const std::function<bool(const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_chunked: chunk_frames must be >= 1\n");
+    tts_response r;
+    generate(sentence, r, config);
+    if (r.n_outputs) (void) on_chunk(r.data, r.n_outputs);
+}
+
+void tts_generation_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                                   const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_batch_chunked: chunk_frames must be >= 1\n");
+    std::vector<tts_response> out;
+    generate_batch(sentences, out, config);
+    for (size_t i = 0; i < out.size(); i++)
+        if (out[i].n_outputs && !on_chunk((uint32_t) i, out[i].data, out[i].n_outputs)) break;
+}
+
 // continuous batching, the defaults: a runner without a session
 void tts_generation_runner::stream_begin(const generation_configuration &) { TTS_ABORT("stream_begin: this runner has no continuous batching (stream_capacity() == 0)\n"); }
 void tts_generation_runner::stream_submit(size_t, const std::string &) { TTS_ABORT("stream_submit: this runner has no continuous batching\n"); }

@@ -93,6 +93,7 @@ parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok
     // one utterance: the reference layout (max_ctx_length positions, model.cpp:368-369); lock-step batches keep only
     // the positions generation can reach (check_stopping stops at max_generation, model.cpp:720-722)
     d.kv_positions = max_seqs > 1 ? hp.max_generation_size : 0;
+    dac_halo = tts_hip_dac_halo_frames(&d);
     ctx = tts_hip_create(device, &d);
     if (!ctx) TTS_ABORT("tts_hip_create failed: %s\n", tts_hip_last_error());
     smp.n_output_heads = hp.n_output_heads;
@@ -167,21 +168,28 @@ void parler_runner::update_conditional_prompt(const char * file_path, const char
 
 // model.cpp:734-760, including the `next_index > size` bound (an index == size would read one past the
 // end in the reference; such a frame is dropped here, the only defined outcome).
-void parler_runner::adjust_output_tokens(const std::vector<uint32_t> & toks, std::vector<uint32_t> & filtered) const {
-    const size_t size = toks.size(), nh = hp.n_output_heads;
-    filtered.reserve(size);
-    for (size_t i = 0; i < size / nh; i++) {
+size_t parler_undelay(const uint32_t * toks, size_t steps, uint32_t nh, uint32_t audio_vocab, size_t next, bool finished, std::vector<uint32_t> & out) {
+    const size_t size = steps * nh, end = finished ? steps : (steps >= nh ? steps - nh + 1 : 0);
+    for (size_t i = next; i < end; i++) {
         bool remove = false;
         for (size_t ii = 0; ii < nh; ii++) {
             const size_t idx = i * nh + ii * nh + ii;
-            if (idx >= size || toks[idx] >= hp.audio_vocab_size) { remove = true; break; }
+            if (idx >= size || toks[idx] >= audio_vocab) { remove = true; break; }
         }
         if (remove) continue;
-        for (size_t ii = 0; ii < nh; ii++) filtered.push_back(toks[i * nh + ii * nh + ii]);
+        for (size_t ii = 0; ii < nh; ii++) out.push_back(toks[i * nh + ii * nh + ii]);
     }
+    return std::max(end, next);
 }
 
-void parler_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+void parler_runner::adjust_output_tokens(const std::vector<uint32_t> & toks, std::vector<uint32_t> & filtered) const {
+    filtered.reserve(toks.size());
+    parler_undelay(toks.data(), toks.size() / hp.n_output_heads, hp.n_output_heads, hp.audio_vocab_size, 0, true, filtered);
+}
+
+// generate() up to the prefill: the sampler's settings, batch_from_sentence (model.cpp:473-498), the prompt into cache slot 0.
+// false: the prompt leaves no room for generation (the response is empty).
+bool parler_runner::prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt) {
     smp.temperature = config.temperature;
     smp.repetition_penalty = config.repetition_penalty;
     smp.do_sample = config.sample;
@@ -194,24 +202,30 @@ void parler_runner::generate(const char * sentence, tts_response & output, const
                   "loads the encoder_attn tensors when it is set at load time, model.cpp:202-237)\n");
 
     // batch_from_sentence (model.cpp:473-498)
-    std::vector<uint32_t> prompt;
+    prompt.clear();
     tokenizer->tokenize(sentence, prompt);
     prompt.push_back(tokenizer->eos_token);
     last_prompt_tokens = prompt;
+    last_output_tokens.clear();
     smp.reset();
     hip_check(tts_hip_parler_reset(ctx), "tts_hip_parler_reset");
-    output.data = nullptr;
-    output.n_outputs = 0;
     if (prompt.size() >= hp.max_generation_size || prompt.size() >= hp.max_ctx_length) {
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", prompt.size());
-        return;
+        return false;
     }
     hip_check(tts_hip_parler_prefill(ctx, 0, prompt.data(), (uint32_t) prompt.size(), 0), "tts_hip_parler_prefill");
+    return true;
+}
+
+void parler_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+    std::vector<uint32_t> prompt;
+    output.data = nullptr;
+    output.n_outputs = 0;
+    if (!prepare_single(sentence, config, prompt)) return;
 
     const uint32_t nh = hp.n_output_heads;
     uint32_t       current_position = (uint32_t) prompt.size();
     std::vector<uint32_t> & out_tokens = last_output_tokens;
-    out_tokens.clear();
 
     // the sampler runs on the device (unless a head has more than 2048 logits).  Greedy never sees the repetition
     // penalty: sampler::max only reads last_token_ids, which stay -1 after reset() (sampler.cpp:71-80,185-204)
@@ -271,15 +285,18 @@ void parler_runner::generate(const char * sentence, tts_response & output, const
     output.n_outputs = pcm.size();
 }
 
-void parler_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
-                                   const generation_configuration & config) {
-    const uint32_t n_all = (uint32_t) sentences.size(), nh = hp.n_output_heads;
-    outputs.assign(n_all, tts_response{});
-    if (n_all == 0) return;
+// generate_batch() up to the prefill: the utterances that have room for generation as rows (row_of: the utterance of a row, start: its prompt
+// length), their prompts prefilled as one batch.  false: no row.
+bool parler_runner::prepare_batch(const std::vector<std::string> & sentences, const generation_configuration & config,
+                                  std::vector<uint32_t> & start, std::vector<uint32_t> & row_of) {
+    const uint32_t n_all = (uint32_t) sentences.size();
+    start.clear(); row_of.clear();
+    last_batch_tokens.assign(n_all, {});
+    if (n_all == 0) return false;
     if (n_all > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n_all, max_seqs);
     if (config.use_cross_attn != use_cross_attn) TTS_ABORT("generate_batch: use_cross_attn differs from load time\n");
     // batch_from_sentence per utterance; an utterance whose prompt leaves no room gets an empty response, exactly as generate() does
-    std::vector<uint32_t> ids, lens, start, row_of;
+    std::vector<uint32_t> ids, lens;
     for (uint32_t i = 0; i < n_all; i++) {
         std::vector<uint32_t> p;
         tokenizer->tokenize(sentences[i], p);
@@ -294,10 +311,19 @@ void parler_runner::generate_batch(const std::vector<std::string> & sentences, s
         ids.insert(ids.end(), p.begin(), p.end());
     }
     const uint32_t n = (uint32_t) row_of.size();
-    last_batch_tokens.assign(n_all, {});
-    if (n == 0) return;
+    if (n == 0) return false;
     hip_check(tts_hip_parler_reset(ctx), "tts_hip_parler_reset");
     hip_check(tts_hip_parler_prefill_batch(ctx, n, nullptr, ids.data(), lens.data(), nullptr), "tts_hip_parler_prefill_batch");
+    return true;
+}
+
+void parler_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
+                                   const generation_configuration & config) {
+    const uint32_t nh = hp.n_output_heads;
+    outputs.assign(sentences.size(), tts_response{});
+    std::vector<uint32_t> start, row_of;
+    if (!prepare_batch(sentences, config, start, row_of)) return;
+    const uint32_t n = (uint32_t) row_of.size();
     // every utterance gets the steps generate() would give it alone (max_generation - its own prompt): the loop runs as long as the
     // shortest prompt needs; the device marks a row finished when its position reaches max_generation and lets it idle there
     const uint32_t shortest = *std::min_element(start.begin(), start.end());
@@ -389,6 +415,185 @@ void parler_runner::generate_batch(const std::vector<std::string> & sentences, s
         outputs[row_of[i]].n_outputs = (size_t) frames[i] * hp.up_sampling_factor;
         off += outputs[row_of[i]].n_outputs;
     }
+}
+
+// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
+// The codec's output for frame j depends on the codes of frames [j - h, j + h] only (tts_hip_dac_halo_frames).  So once frames [e, f + h)
+// of an utterance are final, a window of frames [e - h, f + h) decoded as an utterance of its own yields the samples of frames [e, f)
+// exactly as the whole utterance's decode does (at the utterance's true edges the window is clipped and sees the same zero padding).
+// The loop: launch the next 32 steps -> decode the windows the last look-in made ready (one codec pass for every utterance, on the codec's
+// stream while the steps run) -> callbacks -> wait for the steps -> un-delay the frames that became final -> plan the next windows.
+static constexpr uint32_t CHUNK_LOOK_IN = 32;   // decode steps between two look-ins: generate_loop's, so rows are compacted at the same steps
+
+namespace {
+struct chunk_row {                    // one utterance of a chunked generation
+    std::vector<uint32_t> toks;       // delayed tokens so far [steps][heads]
+    std::vector<uint32_t> frames;     // codes of the kept frames that are final [frames][heads]
+    size_t   judged = 0;              // frames whose keep / drop is decided (parler_undelay's `next`)
+    uint32_t emitted = 0;             // kept frames handed out
+    bool     finished = false;
+};
+struct chunk_windows {                // the windows of one look-in: one tts_hip_dac_decode_windows pass
+    std::vector<uint32_t> codes, frames, keep0, keep1, row;
+};
+}
+
+void parler_runner::chunked_run(const std::vector<uint32_t> & start, const generation_configuration & config, uint32_t chunk_frames,
+                                const std::function<bool(uint32_t, const float *, size_t)> & on_chunk, std::vector<std::vector<uint32_t>> & row_tokens) {
+    const uint32_t n = (uint32_t) start.size(), nh = hp.n_output_heads, U = hp.up_sampling_factor;
+    const uint32_t max_steps = hp.max_generation_size - *std::min_element(start.begin(), start.end());
+    const uint32_t h = dac_halo >= 0 ? (uint32_t) dac_halo : hp.max_generation_size;   // unknown halo: whole utterances once they are done
+    std::vector<chunk_row> rows(n);
+    chunk_windows W;
+    bool go = true;
+
+    // the frames of each row that became final since the last call, then a window per row that has chunks ready: whole chunks whose
+    // right halo is final too, or everything left once the row is finished
+    auto plan = [&]() {
+        for (uint32_t i = 0; i < n; i++) {
+            chunk_row & r = rows[i];
+            r.judged = parler_undelay(r.toks.data(), r.toks.size() / nh, nh, hp.audio_vocab_size, r.judged, r.finished, r.frames);
+            const uint32_t have = (uint32_t) (r.frames.size() / nh);
+            uint32_t end = r.emitted;
+            if (r.finished) end = have;
+            else if (have >= r.emitted + h + chunk_frames) end = r.emitted + (have - h - r.emitted) / chunk_frames * chunk_frames;
+            if (end == r.emitted) continue;
+            const uint32_t w0 = r.emitted > h ? r.emitted - h : 0, w1 = std::min(end + h, have);
+            W.codes.insert(W.codes.end(), r.frames.begin() + (size_t) w0 * nh, r.frames.begin() + (size_t) w1 * nh);
+            W.frames.push_back(w1 - w0);
+            W.keep0.push_back(r.emitted - w0);
+            W.keep1.push_back(end - w0);
+            W.row.push_back(i);
+            r.emitted = end;
+        }
+    };
+    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
+    auto emit = [&]() {
+        if (W.row.empty()) return true;
+        size_t total = 0;
+        for (size_t w = 0; w < W.row.size(); w++) total += (size_t) (W.keep1[w] - W.keep0[w]) * U;
+        pcm.resize(total);
+        hip_check(tts_hip_dac_decode_windows(ctx, W.codes.data(), W.frames.data(), W.keep0.data(), W.keep1.data(), (uint32_t) W.row.size(), pcm.data()),
+                  "tts_hip_dac_decode_windows");
+        bool more = true;
+        size_t off = 0;
+        for (size_t w = 0; w < W.row.size() && more; w++) {
+            const uint32_t nf = W.keep1[w] - W.keep0[w];
+            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
+                more = on_chunk(W.row[w], pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
+            off += (size_t) nf * U;
+        }
+        W = chunk_windows{};
+        return more;
+    };
+
+    if (!getenv("TTS_HOST_LOOP") && (!config.sample || hp.output_vocab_size <= 2048)) {
+        // generate_batch's device loop, in look-in pieces
+        std::vector<float> u;
+        const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+        if (config.sample) {   // one sampler state per utterance, seeded as generate() seeds its own: uniforms [step][utterance][head]
+            u.resize((size_t) max_steps * n * nh);
+            for (uint32_t i = 0; i < n; i++) {
+                sampler si = smp;
+                si.seed = config.seed; si.n_calls = 0;
+                for (uint32_t s = 0; s < max_steps; s++) si.draw_uniforms(u.data() + ((size_t) s * n + i) * nh);
+            }
+        }
+        hip_check(tts_hip_parler_gen_begin(ctx, n, start.data(), max_steps, hp.bos_token_id, hp.eos_token_id, config.sample ? &sp : nullptr,
+                                           config.sample ? u.data() : nullptr), "tts_hip_parler_gen_begin");
+        std::vector<uint32_t> toks((size_t) max_steps * n * nh), done(n);
+        uint32_t ran = 0;
+        hip_check(tts_hip_parler_gen_launch(ctx, CHUNK_LOOK_IN), "tts_hip_parler_gen_launch");
+        for (;;) {
+            go = emit();   // the codec windows of the last look-in, while the steps run
+            hip_check(tts_hip_parler_gen_wait(ctx, toks.data(), done.data(), &ran), "tts_hip_parler_gen_wait");
+            bool all = true;
+            for (uint32_t i = 0; i < n; i++) {
+                // check_stopping per sequence, as generate_batch reads it: EOS on every head, or position == max_generation
+                const uint32_t cap = std::min(done[i] ? done[i] : max_steps, hp.max_generation_size - start[i]), have = std::min(ran, cap);
+                chunk_row & r = rows[i];
+                for (uint32_t s = (uint32_t) (r.toks.size() / nh); s < have; s++)
+                    r.toks.insert(r.toks.end(), toks.begin() + ((size_t) s * n + i) * nh, toks.begin() + ((size_t) s * n + i + 1) * nh);
+                r.finished = done[i] != 0 || ran >= max_steps || have >= cap;
+                all = all && r.finished;
+            }
+            if (all || !go) break;
+            hip_check(tts_hip_parler_gen_launch(ctx, CHUNK_LOOK_IN), "tts_hip_parler_gen_launch");
+            plan();
+        }
+    } else {
+        // generate_batch's host loop; the windows are planned and decoded at the same look-in points, without overlap
+        std::vector<sampler> smps(n, smp);
+        for (uint32_t i = 0; i < n; i++) {
+            smps[i].temperature = config.temperature; smps[i].repetition_penalty = config.repetition_penalty;
+            smps[i].do_sample = config.sample; smps[i].top_k = (uint32_t) config.top_k; smps[i].top_p = config.top_p;
+            smps[i].seed = config.seed; smps[i].n_calls = 0;
+            smps[i].reset();
+        }
+        std::vector<uint32_t> in_ids((size_t) n * nh, hp.bos_token_id), pos(start);
+        std::vector<std::vector<bool>> eos_seen(n, std::vector<bool>(nh, false));
+        std::vector<float> lg((size_t) n * nh * hp.output_vocab_size);
+        for (uint32_t step = 1; step <= max_steps && go; step++) {
+            bool all_done = true;
+            for (uint32_t i = 0; i < n; i++) {
+                chunk_row & r = rows[i];
+                if (r.finished) continue;
+                auto & t = r.toks;
+                if (!t.empty()) {
+                    if (pos[i] >= hp.max_generation_size) { r.finished = true; continue; }
+                    bool all = true;
+                    for (uint32_t k = 0; k < nh; k++) {
+                        eos_seen[i][k] = eos_seen[i][k] || t[t.size() - nh + k] == hp.eos_token_id;
+                        all = all && eos_seen[i][k];
+                    }
+                    if (all) { r.finished = true; continue; }
+                }
+                all_done = false;
+            }
+            if (all_done) break;
+            hip_check(tts_hip_parler_step(ctx, n, in_ids.data(), pos.data(), nullptr, lg.data()), "tts_hip_parler_step");
+            for (uint32_t i = 0; i < n; i++) {
+                if (pos[i] + 1 < hp.max_generation_size) pos[i] += 1;  // finished rows idle on their last position
+                if (rows[i].finished) continue;
+                auto & t = rows[i].toks;
+                smps[i].sample(lg.data() + (size_t) i * nh * hp.output_vocab_size, t);
+                const uint32_t * last = t.data() + t.size() - nh;
+                for (uint32_t k = 0; k < nh; k++)
+                    in_ids[(size_t) i * nh + k] = step > k ? (eos_seen[i][k] ? hp.eos_token_id : last[k]) : hp.bos_token_id;
+            }
+            if (step % CHUNK_LOOK_IN == 0) {
+                plan();
+                go = emit();
+            }
+        }
+        if (go) for (auto & r : rows) r.finished = true;   // the loop ran to its end: nothing more comes
+    }
+    if (go) {   // what is left once every utterance is done
+        plan();
+        (void) emit();
+    }
+    row_tokens.resize(n);
+    for (uint32_t i = 0; i < n; i++) row_tokens[i] = std::move(rows[i].toks);
+}
+
+void parler_runner::generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                                     const std::function<bool(const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_chunked: chunk_frames must be >= 1\n");
+    std::vector<uint32_t> prompt;
+    if (!prepare_single(sentence, config, prompt)) return;
+    std::vector<std::vector<uint32_t>> rt;
+    chunked_run({(uint32_t) prompt.size()}, config, chunk_frames, [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); }, rt);
+    last_output_tokens = std::move(rt[0]);
+}
+
+void parler_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                           const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_batch_chunked: chunk_frames must be >= 1\n");
+    std::vector<uint32_t> start, row_of;
+    if (!prepare_batch(sentences, config, start, row_of)) return;
+    std::vector<std::vector<uint32_t>> rt;
+    chunked_run(start, config, chunk_frames, [&](uint32_t row, const float * p, size_t k) { return on_chunk(row_of[row], p, k); }, rt);
+    for (size_t i = 0; i < row_of.size(); i++) last_batch_tokens[row_of[i]] = std::move(rt[i]);
 }
 
 // ---- continuous batching (common.h; tts_hip_parler_stream_* underneath) ----------------------------------------------------------------

@@ -29,6 +29,13 @@ struct parler_hparams {  // defaults = Parler TTS Mini v1 (model.h:66-83)
     uint32_t up_sampling_factor = 512;
 };
 
+// The delay pattern's per-frame rule (model.cpp:734-760): frame i takes head k's token from step i + k and is dropped when one of them lies
+// past the end of the tokens or is no audio code (>= audio_vocab).  Frame i is final once step i + nh - 1 exists, so whether it is kept
+// is known as soon as that step has run.  Judges frames [next, end) of tokens [steps][nh] — end = steps when the generation is over,
+// else the frames already final (steps - nh + 1) — appends the kept ones' codes to `out` and returns end.  adjust_output_tokens is
+// this with next = 0 and finished.
+size_t parler_undelay(const uint32_t * toks, size_t steps, uint32_t nh, uint32_t audio_vocab, size_t next, bool finished, std::vector<uint32_t> & out);
+
 struct parler_runner final : tts_generation_runner {
     parler_runner(const parler_hparams & hp, unigram_tokenizer * tok, int device, bool use_cross_attn);
     ~parler_runner() override;
@@ -55,6 +62,11 @@ struct parler_runner final : tts_generation_runner {
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
     void *   device_context() const override { return ctx; }
+    // chunked audio (common.h): codec windows of the frames that became final are decoded while the next steps run
+    void generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                          const std::function<bool(const float *, size_t)> & on_chunk) override;
+    void generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) override;
     bool          declare_only = false;   // tts_load_options at load time: no weight bytes uploaded by this runner
     tts_hip_ctx * share_ctx = nullptr;    // ... and whose arena it uses instead (same device)
     uint32_t max_seqs = 1;
@@ -76,6 +88,13 @@ struct parler_runner final : tts_generation_runner {
     std::vector<float>                 logits;
 
   private:
+    bool prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt);
+    bool prepare_batch(const std::vector<std::string> & sentences, const generation_configuration & config, std::vector<uint32_t> & start,
+                       std::vector<uint32_t> & row_of);
+    int  dac_halo = -1;   // tts_hip_dac_halo_frames of the codec layout (-1: unknown; chunked audio then decodes whole utterances)
+    // the generation loop of generate_chunked / generate_batch_chunked over n prefilled rows (row i starts at start[i]); tokens per row out
+    void chunked_run(const std::vector<uint32_t> & start, const generation_configuration & config, uint32_t chunk_frames,
+                     const std::function<bool(uint32_t, const float *, size_t)> & on_chunk, std::vector<std::vector<uint32_t>> & row_tokens);
     // session state of the continuous batching
     struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; };
     struct decoded { size_t ticket; std::vector<uint32_t> frames; };   // un-delayed codes waiting for a codec pass

@@ -98,6 +98,50 @@ int tts_c_generate_stream(tts_c_runner * r, const char * const * texts, int n, c
     }
 }
 
+int tts_c_generate_chunked(tts_c_runner * r, const char * text, const tts_c_config * cfg, uint32_t chunk_frames, tts_c_chunk_fn fn, void * user) {
+    g_tts_throw_on_abort = true;
+    try {
+        if (!fn) throw std::runtime_error("tts_c_generate_chunked: null callback");
+        bool stopped = false;
+        ((tts_generation_runner *) r)->generate_chunked(text, to_cfg(cfg), chunk_frames, [&](const float * pcm, size_t n) {
+            stopped = fn(user, 0, pcm, n) == 0;
+            return !stopped;
+        });
+        return stopped ? 1 : 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
+int tts_c_generate_batch_chunked(tts_c_runner * r, const char * const * texts, int n, const tts_c_config * cfg, uint32_t chunk_frames, tts_c_chunk_fn fn,
+                                 void * user) {
+    g_tts_throw_on_abort = true;
+    try {
+        if (!fn) throw std::runtime_error("tts_c_generate_batch_chunked: null callback");
+        bool stopped = false;
+        std::vector<std::string> s(texts, texts + n);
+        ((tts_generation_runner *) r)->generate_batch_chunked(s, to_cfg(cfg), chunk_frames, [&](uint32_t utt, const float * pcm, size_t k) {
+            stopped = fn(user, (int) utt, pcm, k) == 0;
+            return !stopped;
+        });
+        return stopped ? 1 : 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
+int64_t tts_c_parler_final_frames(const uint32_t * tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, int finished, uint32_t * out,
+                                  uint64_t cap_frames) {
+    if (n_heads == 0) { g_c_err = "tts_c_parler_final_frames: n_heads == 0"; return -1; }
+    std::vector<uint32_t> f;
+    parler_undelay(tokens, (size_t) n_steps, n_heads, audio_vocab, 0, finished != 0, f);
+    const uint64_t frames = f.size() / n_heads;
+    if (out) copy_u32(out, f.data(), (size_t) (frames < cap_frames ? frames : cap_frames) * n_heads);
+    return (int64_t) frames;
+}
+
 int tts_c_update_conditional_prompt(tts_c_runner * r, const char * text_encoder_path, const char * prompt) {
     g_tts_throw_on_abort = true;
     try {

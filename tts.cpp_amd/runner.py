@@ -30,7 +30,10 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_last_error", "tts_c_update_conditional_prompt", "tts_c_last_tokens", "tts_c_tokenize", "tts_c_sampler_sample", "tts_c_gguf_summary", "tts_c_gguf_tensor",
            "tts_c_pool_create", "tts_c_pool_set_text_encoder", "tts_c_pool_set_continuous", "tts_c_pool_set_continuous_yield_ms", "tts_c_pool_admitted_in_flight", "tts_c_pool_conditional_prompt", "tts_c_pool_submit", "tts_c_pool_wait", "tts_c_pool_release", "tts_c_pool_stats", "tts_c_pool_load_stats", "tts_c_pool_free", "tts_c_set_load_options", "tts_c_set_load_options_ex", "tts_c_runner_device_context", "tts_c_runner_tokenize",
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
-           "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform"]
+           "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
+           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames"]
+
+CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
 _lib = None
 
@@ -105,6 +108,10 @@ def load_lib():
         L.tts_c_runner_device_context.restype = C.c_void_p
         L.tts_c_runner_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]
         L.tts_c_pool_free.restype = None
+        L.tts_c_generate_chunked.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
+        L.tts_c_generate_batch_chunked.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
+        L.tts_c_parler_final_frames.restype = C.c_int64
+        L.tts_c_parler_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
         _lib = L
     return _lib
 
@@ -184,6 +191,39 @@ class Runner:
             return [int(ns[i]) for i in range(n)]
         return [np.ctypeslib.as_array(data[i], shape=(ns[i],)).copy() if ns[i] else np.zeros(0, dtype=np.float32) for i in range(n)]
 
+    def _chunked(self, call, on_chunk):
+        """runs `call(fn)` with a tts_c_chunk_fn that records (utterance, pcm copy, time.monotonic() at arrival) and asks on_chunk
+        whether to go on; sets self.stopped when the callback stopped the generation"""
+        import time
+        got = []
+
+        def fn(_user, utt, pcm, n):
+            a = np.ctypeslib.as_array(pcm, shape=(n,)).copy() if n else np.zeros(0, dtype=np.float32)
+            got.append((int(utt), a, time.monotonic()))
+            return 0 if on_chunk is not None and on_chunk(*got[-1]) is False else 1
+
+        cb = CHUNK_FN(fn)
+        rc = call(cb)
+        if rc not in (0, 1):
+            raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
+        self.stopped = rc == 1
+        return got
+
+    def generate_chunked(self, text, chunk_frames=32, on_chunk=None, **cfg):
+        """tts_c_generate_chunked: the audio in pieces of at most chunk_frames codec frames as they are decoded.  Returns [(pcm, arrival)]
+        with arrival = time.monotonic() when the piece came in; on_chunk(pcm, arrival) returning False stops the generation (self.stopped)."""
+        c = make_config(**cfg) if cfg else self.cfg
+        cb = None if on_chunk is None else (lambda utt, a, t: on_chunk(a, t))
+        got = self._chunked(lambda fn: self.L.tts_c_generate_chunked(self.h, text.encode("utf-8"), C.byref(c), chunk_frames, fn, None), cb)
+        return [(a, t) for _, a, t in got]
+
+    def generate_batch_chunked(self, texts, chunk_frames=32, on_chunk=None, **cfg):
+        """tts_c_generate_batch_chunked: [(utterance, pcm, arrival)] in arrival order; on_chunk(utterance, pcm, arrival) returning False stops"""
+        c = make_config(**cfg) if cfg else self.cfg
+        n = len(texts)
+        arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
+        return self._chunked(lambda fn: self.L.tts_c_generate_batch_chunked(self.h, arr, n, C.byref(c), chunk_frames, fn, None), on_chunk)
+
     def tokenize(self, text):
         n = self.L.tts_c_runner_tokenize(self.h, text.encode("utf-8"), None, 0)
         if n < 0:
@@ -224,6 +264,18 @@ def tokenize(gguf_path, text):
     if n < 0:
         raise RunnerError(L.tts_c_last_error().decode())
     return out[:n].copy()
+
+
+def parler_final_frames(tokens, audio_vocab, finished):
+    """the Parler runner's un-delay rule (parler_undelay) on delayed tokens [steps][heads]: the kept frames that are final after these steps"""
+    t = np.ascontiguousarray(tokens, dtype=np.uint32)
+    steps, nh = t.shape
+    L = load_lib()
+    tp = t.ctypes.data_as(C.POINTER(C.c_uint32))
+    n = L.tts_c_parler_final_frames(tp, steps, nh, audio_vocab, 1 if finished else 0, None, 0)
+    out = np.zeros((max(n, 1), nh), dtype=np.uint32)
+    L.tts_c_parler_final_frames(tp, steps, nh, audio_vocab, 1 if finished else 0, out.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+    return out[:n]
 
 
 def _vocab_array(vocab):
