@@ -54,7 +54,11 @@ int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, i
  * chunk_frames codec frames while the utterance is still generating (pcm valid during the call only; utterance = 0 here, the text's index in
  * the batch form); their concatenation equals tts_c_generate's / tts_c_generate_batch's audio.  fn returning 0 stops the generation at the
  * next look-in point.  Returns 0 when done, 1 when fn stopped it, another value with tts_c_last_error() on error (chunk_frames == 0 is one).
- * Parler-TTS streams; the other architectures generate the whole utterance and hand it out as one chunk. */
+ * Parler-TTS and Orpheus stream; the other architectures generate the whole utterance and hand it out as one chunk.
+ * Orpheus: chunk_frames counts SNAC frames (7 ids, 2048 samples at 24 kHz).  With TTS_SNAC_NO_NOISE the chunks concatenate to tts_c_generate's
+ * PCM.  With the noise block they are a different realisation of the same distribution: generate() draws the noise layer by layer over the
+ * whole utterance, chunked generation frame by frame (per frame, for layer l, 4 * prod(stride_0..l) normals) from the same engine, and the
+ * chunks equal the whole utterance's decode under that re-laid noise; a completed call consumes exactly the draws generate() would. */
 typedef int (*tts_c_chunk_fn)(void *user, int utterance, const float *pcm, size_t n);
 int           tts_c_generate_chunked(tts_c_runner *r, const char *text, const tts_c_config *cfg, uint32_t chunk_frames, tts_c_chunk_fn fn, void *user);
 int           tts_c_generate_batch_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,

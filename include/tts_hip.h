@@ -270,6 +270,21 @@ int tts_hip_orpheus_generate_sampled(tts_hip_ctx *ctx, const uint32_t *prompt, u
 int tts_hip_orpheus_step_batch(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *pos, float *logits_out, uint32_t *tokens_out);
 int tts_hip_orpheus_generate_batch(tts_hip_ctx *ctx, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
                                    const tts_hip_sampling *sampling, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out);
+/* The generation loops in pieces, for callers that work on the ids while the decoder is still running (chunked audio); the three
+ * generate_* calls above are built on them.  gen_begin: prompts / n_prompt / sampling / uniforms as for generate_batch (n_utt = 1: as for
+ * generate_greedy / generate_sampled, uniforms [max_new]); it runs the prompts and makes the first selection.  gen_launch enqueues up to n_steps
+ * more steps: for n_utt = 1 replays of the captured step, and the call returns while they run; for n_utt > 1 the host-driven lock-step
+ * loop, which returns after the steps ran.  gen_wait synchronises and hands out the ids no gen_wait handed out before: tokens_out
+ * [n_utt][max_new] receives utterance u's new ids at their places ([u * max_new + old n_out[u]] onwards), n_out[u] its count so far and
+ * done[u] whether it has ended (stopping token, max_new ids, or the end of the cache); done may be NULL.  The ids are those of the generate_*
+ * calls whatever the launch sizes; steps a launch ran past an utterance's stopping token are discarded.  One gen_launch per gen_wait.
+ * Between a gen_launch and its gen_wait the steps may still be running: every other tts_hip_orpheus_* call on the context (decode, step_batch,
+ * sample_logits, generate_*, gen_begin, gen_launch) is refused with an error until gen_wait has been called.  After a gen_wait, gen_begin
+ * or a generate_* call abandons the generation under way (its cache rows are overwritten from position 0). */
+int tts_hip_orpheus_gen_begin(tts_hip_ctx *ctx, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                              const tts_hip_sampling *sampling, const float *uniforms);
+int tts_hip_orpheus_gen_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_orpheus_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done);
 /* the device sampler alone on caller-supplied logits [vocab_size], for parity tests; last_id / rep_count: sampler::last_token_ids /
  * repetition_counts, read and updated in place (may be NULL when repetition_penalty == 1) */
 int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const tts_hip_sampling *sampling, float uniform, int32_t *last_id,
@@ -393,8 +408,27 @@ tts_hip_ctx *tts_hip_snac_create(int device, const tts_hip_snac_desc *desc);
 /* snac_runner::run (snac_model.cpp:180-208).  codes: level-major ids as set_inputs lays them out (:161-178): T/repeats[0]
  * of level 0, T/repeats[1] of level 1, ...; noise: per layer l, T * prod(stride_0..l) floats, concatenated (:131-137) —
  * the reference draws them from an unseeded normal generator (:177), here they are the caller's; NULL = no noise;
- * pcm_out: T * prod(strides) fp32 samples. */
+ * pcm_out: T * prod(strides) fp32 samples.  Every transposed conv must have 2 * padding == stride (each stage exactly `stride` times longer than
+ * the one before, as in every SNAC release: padding ceil(s / 2), even strides); another layout is refused with an error.  Not to be called
+ * between tts_hip_snac_decode_windows_begin and _end. */
 int tts_hip_snac_decode(tts_hip_ctx *ctx, const uint32_t *codes, uint32_t T, const float *noise, float *pcm_out);
+/* Chunked audio.  A SNAC frame is one group of 7 Orpheus ids = repeats[0] (4) finest-level tokens = 4 * prod(strides) samples.  The samples of
+ * frame j depend on the codes and the noise of frames [j - h, j + h] only; h follows from the layout alone (no device): 3 for snac_24khz
+ * (strides 8, 8, 4, 2), 5 for strides 4, 2.  -1 (tts_hip_last_error) for a layout the rule does not describe: other than three levels at
+ * repeats 4 / 2 / 1, or a transposed conv whose padding is not half its stride. */
+int tts_hip_snac_halo_frames(const tts_hip_snac_desc *desc);
+/* n windows decoded in one pass as separate utterances, each cropped to the samples of its frames [keep0[i], keep1[i]) (relative to the
+ * window); pcm_out receives the kept pieces back to back.  Per window the codes are level-major (T/4, T/2, T ids, T = 4 * frames[i]) and
+ * the noise layer-major (per layer l, T * prod(stride_0..l) floats) as for tts_hip_snac_decode; windows are concatenated; noise NULL = no
+ * noise block.  A window that reaches h frames beyond the kept ones on every side that is not an end of the utterance gives the kept
+ * frames the samples of the whole utterance's decode (under the same noise samples).
+ * _begin copies its inputs, enqueues the pass on the SNAC context's stream and returns; _end waits, after which pcm_out of _begin is
+ * valid.  Between the two no other call on this context.  tts_hip_snac_decode_windows = _begin + _end. */
+int tts_hip_snac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1, uint32_t n,
+                                const float *noise, float *pcm_out);
+int tts_hip_snac_decode_windows_begin(tts_hip_ctx *ctx, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1, uint32_t n,
+                                      const float *noise, float *pcm_out);
+int tts_hip_snac_decode_windows_end(tts_hip_ctx *ctx);
 
 /* ---- DAC codec --------------------------------------------------------------------------- */
 /* dac_runner::run (dac_model.cpp:172-212): codes [frames][n_output_heads] (frame-major),

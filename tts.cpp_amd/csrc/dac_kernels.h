@@ -380,25 +380,37 @@ static __global__ __launch_bounds__(256) void convt1d_kernel(ConvTArgs a) {
 //   dwconv7_kernel      snake_1d + ggml_conv_1d_dw (groups = channels) + bias [+ the next snake]  :141-142, gnac.cpp:135-145
 //   noise_fma_kernel    x + noise * conv1x1(x)   gnac.cpp:155-159 (the 1x1 conv is a conv1d launch)
 // ------------------------------------------------------------------------------------------------
+// One pass carries n utterances (grid.z), each a window of a longer one or a whole one: activations are [n][C][LS] with LS the longest
+// utterance of the pass at the stage's rate, and utterance z is valid on [0, tok[z] * mult).  A tap beyond that edge reads zero, as a
+// lone utterance's padding does, never the neighbour's samples.  The segment table SnacSeg holds, per utterance, its length in
+// finest-level tokens and where its codes and its noise start in the concatenated inputs.
+struct SnacSeg {
+    const uint32_t *tok;         // [n] finest-level tokens T_z
+    const uint32_t *code_base;   // [n] first id of the utterance in `codes`
+    const uint32_t *noise_base;  // [n] first float of the utterance in `noise`
+};
+
 struct SnacEmbedArgs {
-    const uint32_t *codes;   // level-major: T/rep[0] ids, then T/rep[1], ... (snac_runner::set_inputs :161-178)
+    const uint32_t *codes;   // per utterance level-major: T/rep[0] ids, then T/rep[1], ... (snac_runner::set_inputs :161-178)
     const float *codebook;   // [n_cb][cb_size][cb_dim]
     const float *proj_w;     // [n_cb][latent][cb_dim]
     const float *proj_b;     // [n_cb][latent]
-    int n_cb, cb_size, cb_dim, latent, T;
+    int n_cb, cb_size, cb_dim, latent, LS;
     int rep[4];
-    float *out;              // [latent][T]
+    SnacSeg seg;
+    float *out;              // [n][latent][LS]
 };
 
 static __global__ void snac_embed_kernel(SnacEmbedArgs a) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = blockIdx.y;
-    if (t >= a.T) return;
+    const int c = blockIdx.y, z = blockIdx.z;
+    const int T = (int) a.seg.tok[z];
+    if (t >= T) return;
     float total = 0.0f;
-    int off = 0;
+    int off = (int) a.seg.code_base[z];
     for (int i = 0; i < a.n_cb; i++) {
         const uint32_t code = a.codes[off + t / a.rep[i]];
-        off += a.T / a.rep[i];
+        off += T / a.rep[i];
         const float *cb = a.codebook + ((int64_t) i * a.cb_size + code) * a.cb_dim;
         const float *w = a.proj_w + ((int64_t) i * a.latent + c) * a.cb_dim;
         float acc = 0.0f;
@@ -406,16 +418,19 @@ static __global__ void snac_embed_kernel(SnacEmbedArgs a) {
         acc += a.proj_b[i * a.latent + c];
         total = (i == 0) ? acc : (total + acc);
     }
-    a.out[(int64_t) c * a.T + t] = total;
+    a.out[((int64_t) z * a.latent + c) * a.LS + t] = total;
 }
 
-// depthwise k = 7: one output per thread (memory-shaped: 1 read + 1 write per element, 7 taps from L1/L2)
+// depthwise k = 7: one output per thread (memory-shaped: 1 read + 1 write per element, 7 taps from L1/L2); one launch for every
+// utterance of the pass
 static __global__ __launch_bounds__(256) void dwconv7_kernel(const float *x, const float *w, const float *b, const float *alpha_in,
-                                                      const float *alpha_out, float *y, int C, int L, int pad, int dil) {
+                                                      const float *alpha_out, float *y, int C, int LS, int pad, int dil,
+                                                      const uint32_t *tok, int mult) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = blockIdx.y;
+    const int c = blockIdx.y, z = blockIdx.z;
+    const int L = (int) tok[z] * mult;
     if (t >= L) return;
-    const float *xr = x + (int64_t) c * L;
+    const float *xr = x + ((int64_t) z * C + c) * LS;
     const float al = alpha_in ? alpha_in[c] : 1.0f, ral = 1.0f / al;
     float acc = b ? b[c] : 0.0f;
 #pragma unroll
@@ -428,13 +443,25 @@ static __global__ __launch_bounds__(256) void dwconv7_kernel(const float *x, con
         }
     }
     if (alpha_out) { const float ao = alpha_out[c]; acc = snake_f(acc, ao, 1.0f / ao); }
-    y[(int64_t) c * L + t] = acc;
+    y[((int64_t) z * C + c) * LS + t] = acc;
 }
 
-static __global__ void noise_fma_kernel(float *x, const float *h, const float *noise, int C, int L) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t) C * L) return;
-    x[i] = x[i] + h[i] * noise[i % L];
+// x + noise * h: utterance z's noise of this layer starts at noise_base[z] + T_z * cum (cum = sum of the earlier layers' rates)
+static __global__ void noise_fma_kernel(float *x, const float *h, const float *noise, int C, int LS, SnacSeg seg, int mult, int cum) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y, z = blockIdx.z;
+    const int T = (int) seg.tok[z];
+    if (t >= T * mult) return;
+    const int64_t i = ((int64_t) z * C + c) * LS + t;
+    x[i] = x[i] + h[i] * noise[(int64_t) seg.noise_base[z] + (int64_t) T * cum + t];
+}
+
+// the samples [src0[z], src0[z] + len[z]) of utterance z's row -> dst[dst0[z] ...]: the kept pieces of all utterances back to back
+static __global__ void snac_crop_kernel(const float *src, int LS, const uint32_t *src0, const uint32_t *dst0, const uint32_t *len, float *dst) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int z = blockIdx.y;
+    if (t >= (int) len[z]) return;
+    dst[(int64_t) dst0[z] + t] = src[(int64_t) z * LS + src0[z] + t];
 }
 
 // ================================================================================================

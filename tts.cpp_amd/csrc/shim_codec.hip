@@ -1495,90 +1495,239 @@ static int ensure_packed_snac(tts_hip_ctx *c) {
     return 0;
 }
 
-extern "C" int tts_hip_snac_decode(tts_hip_ctx *c, const uint32_t *codes, uint32_t T_, const float *noise, float *pcm_out) {
-    if (!c || !c->has_snac) return set_err("tts_hip_snac_decode: not a SNAC context (tts_hip_snac_create)");
-    if (!c->finalized || !c->weights_present) return set_err("tts_hip_snac_decode: context not finalized");
-    if (!codes || !pcm_out) return set_err("tts_hip_snac_decode: null argument");
-    if (T_ == 0) return 0;
-    const tts_hip_snac_desc &sd = c->snac;
-    if (sd.max_frames && T_ > sd.max_frames) return set_err("tts_hip_snac_decode: %u tokens exceed snac.max_generation_size %u", T_, sd.max_frames);
-    size_t n_codes = 0;
-    for (uint32_t i = 0; i < sd.n_codebooks; i++) {
-        if (T_ % sd.repeats[i]) return set_err("tts_hip_snac_decode: T=%u is not a multiple of the level-%u repeat %u", T_, i, sd.repeats[i]);
-        n_codes += T_ / sd.repeats[i];
+// Halo of the SNAC decoder in frames (one frame = one group of 7 Orpheus ids = repeats[0] finest-level tokens): the samples of frame j
+// depend on the codes and the noise of frames [j - h, j + h] only.  tts_hip_dac_halo_frames' interval walk over snac_decode_pass' layers,
+// reversed, from the samples [0, 4 U) of frame 0:
+//   final conv k = 7                                                          [lo, hi] -> [lo - 3, hi + 3]
+//   per block, last first: 3 residual units = depthwise k = 7 at dilation 9, 3, 1 (+ pointwise)   -> [lo - 39, hi + 39]
+//                          noise block (pointwise, noise sample by sample)                        -> unchanged
+//                          transposed conv (stride s, kernel 2s, padding p)   -> [ceil((lo + p - 2s + 1) / s), floor((hi + p) / s)]
+//   `up` conv (pointwise), input depthwise k = 7                              -> [lo - 3, hi + 3]
+//   quantizers: token by token at the finest level, but a level-0 code spans a whole frame    -> frames [floor(lo / 4), floor(hi / 4)]
+// snac_24khz (strides 8, 8, 4, 2, paddings 4, 4, 2, 1): [0, 2047] -> [-3, 2050] -> [-22, 1045] -> [-16, 271] -> [-8, 39] -> [-7, 10] ->
+// tokens [-10, 13] -> frames [-3, 3]: h = 3.  synth.snac_tiny (strides 4, 2): [0, 31] -> [-3, 34] -> [-22, 37] -> [-16, 19] -> tokens
+// [-19, 22] -> frames [-5, 5]: h = 5.  The rule holds for the layouts a window pass can decode: three levels at repeats 4 / 2 / 1 and
+// transposed convs with 2 p = s (every stage exactly s times longer, so a window's zero padding coincides with an utterance's); -1 otherwise.
+// tests/test_orpheus_chunked_cpu.py measures h on the oracle and shows that h - 1 is not enough.
+extern "C" int tts_hip_snac_halo_frames(const tts_hip_snac_desc *sd) {
+    if (!sd || sd->struct_size != sizeof(tts_hip_snac_desc)) return set_err("tts_hip_snac_halo_frames: bad desc (struct_size mismatch)");
+    if (sd->n_blocks == 0 || sd->n_blocks > TTS_HIP_MAX_DAC_BLOCKS) return set_err("tts_hip_snac_halo_frames: %u codec blocks", sd->n_blocks);
+    if (sd->n_codebooks != 3 || sd->repeats[0] != 4 || sd->repeats[1] != 2 || (sd->repeats[2] != 1 && sd->repeats[2] != 0))
+        return set_err("tts_hip_snac_halo_frames: the rule covers three levels at repeats 4 / 2 / 1");
+    int64_t up = 1;
+    for (uint32_t i = 0; i < sd->n_blocks; i++) {
+        if (sd->stride[i] == 0 || 2 * sd->padding[i] != sd->stride[i])
+            return set_err("tts_hip_snac_halo_frames: block %u has stride %u, padding %u (needs 2 x padding == stride)", i, sd->stride[i], sd->padding[i]);
+        up *= sd->stride[i];
     }
-    for (size_t i = 0; i < n_codes; i++)
-        if (codes[i] >= (uint32_t) c->s_cbsize) return set_err("tts_hip_snac_decode: code %u >= codebook size %d", codes[i], c->s_cbsize);
+    const int64_t R = sd->repeats[0];
+    int64_t lo = -3, hi = R * up - 1 + 3;   // the final conv
+    for (int bi = (int) sd->n_blocks - 1; bi >= 0; bi--) {
+        const int64_t s = sd->stride[bi], p = sd->padding[bi];
+        for (int dil = 1; dil <= 9; dil *= 3) { lo -= 3 * dil; hi += 3 * dil; }
+        lo = -floor_div(-(lo + p - 2 * s + 1), s);
+        hi = floor_div(hi + p, s);
+    }
+    lo -= 3; hi += 3;   // the input depthwise conv
+    return (int) std::max(-floor_div(lo, R), floor_div(hi, R));
+}
+
+// snac_runner::run (snac_model.cpp:110-208) for n utterances in one pass (grid.z = utterance; see SnacSeg in dac_kernels.h), each cropped
+// to its samples [keep0, keep1) (in finest-level tokens): everything is enqueued on the context's stream, the kept pieces arrive back to
+// back in c->h_out.  tok[z] = finest-level tokens of utterance z.
+static int snac_decode_pass(tts_hip_ctx *c, const char *what, const uint32_t *codes, const uint32_t *tok, const uint32_t *keep0, const uint32_t *keep1, uint32_t n,
+                            const float *noise, bool whole_cap, size_t *n_pcm) {
+    const tts_hip_snac_desc &sd = c->snac;
     HIPCHK(hipSetDevice(c->device));
+    size_t up_sum = 0;
+    { size_t up = 1; for (auto &b : c->sblocks) { up *= b.stride; up_sum += up; } }
+    size_t n_codes = 0, n_noise = 0, n_keep = 0, Tmax = 0;
+    for (uint32_t z = 0; z < n; z++) {
+        if (sd.max_frames && tok[z] > sd.max_frames) return set_err("%s: %u tokens exceed snac.max_generation_size %u", what, tok[z], sd.max_frames);
+        for (uint32_t i = 0; i < sd.n_codebooks; i++) {
+            if (tok[z] % sd.repeats[i]) return set_err("%s: T=%u is not a multiple of the level-%u repeat %u", what, tok[z], i, sd.repeats[i]);
+            n_codes += tok[z] / sd.repeats[i];
+        }
+        n_noise += up_sum * tok[z];
+        n_keep += (size_t) (keep1[z] - keep0[z]) * c->s_up;
+        Tmax = std::max<size_t>(Tmax, tok[z]);
+    }
+    *n_pcm = n_keep;
+    if (Tmax == 0) return 0;
+    // every stage exactly `stride` times longer than the one before: the valid length of utterance z is tok[z] * mult throughout
+    for (auto &b : c->sblocks)
+        if (2 * b.padding != b.stride) return set_err("%s: transposed conv with stride %d, padding %d (needs 2 x padding == stride)", what, b.stride, b.padding);
+    if (!noise) n_noise = 0;
+    if (n_noise >= (1ull << 31) || (size_t) n * Tmax * c->s_up >= (1ull << 31)) return set_err("%s: pass too large", what);
+    for (size_t i = 0; i < n_codes; i++)
+        if (codes[i] >= (uint32_t) c->s_cbsize) return set_err("%s: code %u >= codebook size %d", what, codes[i], c->s_cbsize);
     CHK(ensure_packed_snac(c));
-    const int T = (int) T_;
-    // buffers sized for max_frames (or this call): largest activation = max over stages of C * L
-    const size_t Tcap = std::max<size_t>(sd.max_frames, T_);
+    // activation buffers: n rows of Tmax tokens (largest activation = max over stages of C * L); a whole-utterance decode reserves
+    // max_frames at once as before, a window pass what its windows need
+    const size_t Tcap = std::max<size_t>(whole_cap ? sd.max_frames : 0, (size_t) n * Tmax);
     if (!c->sbuf[0] || Tcap > c->dac_cap_frames) {
-        size_t mx = (size_t) std::max(c->s_latent, c->s_c0), up = 1, noise_len = 0;
-        for (auto &b : c->sblocks) { mx = std::max(mx, (size_t) b.cin * up); up *= b.stride; mx = std::max(mx, (size_t) b.cout * up); noise_len += up; }
+        size_t mx = (size_t) std::max(c->s_latent, c->s_c0), up = 1;
+        for (auto &b : c->sblocks) { mx = std::max(mx, (size_t) b.cin * up); up *= b.stride; mx = std::max(mx, (size_t) b.cout * up); }
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 3; i++) { free_dev(c->sbuf[i]); c->sbuf[i] = nullptr; HIPCHK(hipMalloc((void **) &c->sbuf[i], mx * Tcap * 4)); }
-        free_dev(c->s_noise); c->s_noise = nullptr;
-        HIPCHK(hipMalloc((void **) &c->s_noise, noise_len * Tcap * 4));
-        free_dev(c->s_codes); c->s_codes = nullptr;
-        HIPCHK(hipMalloc((void **) &c->s_codes, Tcap * sd.n_codebooks * 4));
+        c->dac_cap_frames = 0;
+        for (int i = 0; i < 3; i++) { free_dev(c->sbuf[i]); c->sbuf[i] = nullptr; }
+        for (int i = 0; i < 3; i++) HIPCHK(hipMalloc((void **) &c->sbuf[i], mx * Tcap * 4));
         c->dac_cap_frames = Tcap;
     }
+    const size_t n_in = (size_t) 6 * n + n_codes + n_noise;
+    if (n_in > c->s_in_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const size_t cap = std::max(n_in, whole_cap ? (size_t) 6 + (size_t) sd.max_frames * (sd.n_codebooks + up_sum) : 0);
+        c->s_in_cap = 0;
+        free_dev(c->s_in); c->s_in = nullptr;
+        if (c->h_in) { (void) hipHostFree(c->h_in); c->h_in = nullptr; }
+        HIPCHK(hipMalloc((void **) &c->s_in, cap * 4));
+        HIPCHK(hipHostMalloc((void **) &c->h_in, cap * 4));
+        c->s_in_cap = cap;
+    }
+    if (n_keep > c->s_out_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const size_t cap = std::max(n_keep, whole_cap ? (size_t) sd.max_frames * c->s_up : 0);
+        c->s_out_cap = 0;
+        free_dev(c->s_out); c->s_out = nullptr;
+        if (c->h_out) { (void) hipHostFree(c->h_out); c->h_out = nullptr; }
+        HIPCHK(hipMalloc((void **) &c->s_out, cap * 4));
+        HIPCHK(hipHostMalloc((void **) &c->h_out, cap * 4));
+        c->s_out_cap = cap;
+    }
+    // the input block: [tok | code_base | noise_base | crop src | crop dst | crop len][n], the codes, the noise
+    uint32_t *hs = c->h_in;
+    {
+        uint32_t cb = 0, nb = 0, dst = 0;
+        for (uint32_t z = 0; z < n; z++) {
+            hs[z] = tok[z]; hs[n + z] = cb; hs[2 * n + z] = nb;
+            hs[3 * n + z] = keep0[z] * (uint32_t) c->s_up; hs[4 * n + z] = dst; hs[5 * n + z] = (keep1[z] - keep0[z]) * (uint32_t) c->s_up;
+            for (uint32_t i = 0; i < sd.n_codebooks; i++) cb += tok[z] / sd.repeats[i];
+            if (noise) nb += (uint32_t) (up_sum * tok[z]);
+            dst += hs[5 * n + z];
+        }
+        memcpy(hs + 6 * n, codes, n_codes * 4);
+        if (noise) memcpy(hs + 6 * n + n_codes, noise, n_noise * 4);
+    }
+    HIPCHK(hipMemcpyAsync(c->s_in, c->h_in, n_in * 4, hipMemcpyHostToDevice, c->stream));
+    SnacSeg seg{c->s_in, c->s_in + n, c->s_in + 2 * n};
+    const uint32_t *d_codes = c->s_in + 6 * n;
+    const float *d_noise = (const float *) (c->s_in + 6 * n + n_codes);
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
-    HIPCHK(hipMemcpyAsync(c->s_codes, codes, n_codes * 4, hipMemcpyHostToDevice, c->stream));
-    size_t noise_len = 0;
-    { size_t up = 1; for (auto &b : c->sblocks) { up *= b.stride; noise_len += up * (size_t) T; } }
-    if (noise) HIPCHK(hipMemcpyAsync(c->s_noise, noise, noise_len * 4, hipMemcpyHostToDevice, c->stream));
 
     float *cur = c->sbuf[0], *t1 = c->sbuf[1], *t2 = c->sbuf[2];
-    int L = T;
+    int LS = (int) Tmax;   // row stride = the longest utterance at this stage
     SnacEmbedArgs ea{};
-    ea.codes = c->s_codes; ea.codebook = f32(c->s_codebook); ea.proj_w = f32(c->s_projw); ea.proj_b = f32(c->s_projb);
-    ea.n_cb = (int) sd.n_codebooks; ea.cb_size = c->s_cbsize; ea.cb_dim = c->s_cbdim; ea.latent = c->s_latent; ea.T = T; ea.out = cur;
+    ea.codes = d_codes; ea.codebook = f32(c->s_codebook); ea.proj_w = f32(c->s_projw); ea.proj_b = f32(c->s_projb);
+    ea.n_cb = (int) sd.n_codebooks; ea.cb_size = c->s_cbsize; ea.cb_dim = c->s_cbdim; ea.latent = c->s_latent; ea.LS = LS; ea.seg = seg; ea.out = cur;
     for (uint32_t i = 0; i < 4; i++) ea.rep[i] = i < sd.n_codebooks ? (int) sd.repeats[i] : 1;
-    hipLaunchKernelGGL(snac_embed_kernel, dim3((T + 63) / 64, c->s_latent), dim3(64), 0, c->stream, ea);
+    hipLaunchKernelGGL(snac_embed_kernel, dim3((LS + 63) / 64, c->s_latent, n), dim3(64), 0, c->stream, ea);
     HIPCHK(hipGetLastError());
-    auto dw = [&](const float *x, size_t w, size_t b, const float *ain, const float *aout, float *y, int C, int Ln, int pad, int dil) {
-        hipLaunchKernelGGL(dwconv7_kernel, dim3((Ln + 255) / 256, C), dim3(256), 0, c->stream, x, f32(w), f32(b), ain, aout, y, C, Ln, pad, dil);
+    DacBatch bt;
+    bt.n = (int) n; bt.frames = seg.tok; bt.mult = 1;
+    { double tot = 0; for (uint32_t z = 0; z < n; z++) tot += tok[z]; bt.tot_frames = tot; }
+    auto dw = [&](const float *x, size_t w, size_t b, const float *ain, const float *aout, float *y, int C, int Ls, int pad, int dil) {
+        hipLaunchKernelGGL(dwconv7_kernel, dim3((Ls + 255) / 256, C, n), dim3(256), 0, c->stream, x, f32(w), f32(b), ain, aout, y, C, Ls, pad, dil, seg.tok, bt.mult);
         return hipGetLastError() == hipSuccess ? 0 : set_err("dwconv7_kernel launch failed");
     };
-    DacBatch bt;
-    bt.n = 1; bt.frames = nullptr; bt.mult = 1; bt.tot_frames = (double) T;
-    CHK(dw(cur, c->s_inw, c->s_inb, nullptr, nullptr, t1, c->s_latent, L, 3, 1));                                 // :141-142
-    CHK(launch_conv(c, bt, t1, c->s_latent, L, c->s_upw, c->s_upb, 0, false, c->s_c0, 1, 0, 1, nullptr, false, cur));   // :143-144
-    int C = c->s_c0;
-    size_t noise_off = 0;
+    CHK(dw(cur, c->s_inw, c->s_inb, nullptr, nullptr, t1, c->s_latent, LS, 3, 1));                                 // :141-142
+    CHK(launch_conv(c, bt, t1, c->s_latent, LS, c->s_upw, c->s_upb, 0, false, c->s_c0, 1, 0, 1, nullptr, false, cur));   // :143-144
+    int C = c->s_c0, cum = 0;
     for (auto &b : c->sblocks) {                                                                                  // build_layer, gnac.cpp:151-164
         ConvTArgs ta{};
-        ta.x = cur; ta.w = f32(b.w); ta.b = f32(b.b); ta.alpha = f32(b.alpha); ta.y = t1; ta.cin = b.cin; ta.cout = b.cout; ta.L = L;
-        ta.Lout = (L - 1) * b.stride - 2 * b.padding + 2 * b.stride; ta.stride = b.stride; ta.pad = b.padding;
-        ta.frames = nullptr; ta.mult = 1;
-        CHK(prof_begin(c, TTS_HIP_K_DAC_CONVT, 0, 2.0 * b.cin * (double) b.cout * 2 * ta.Lout));
-        CHK(launch_convt(c, ta, b.w, 1));
+        ta.x = cur; ta.w = f32(b.w); ta.b = f32(b.b); ta.alpha = f32(b.alpha); ta.y = t1; ta.cin = b.cin; ta.cout = b.cout; ta.L = LS;
+        ta.Lout = (LS - 1) * b.stride - 2 * b.padding + 2 * b.stride; ta.stride = b.stride; ta.pad = b.padding;
+        ta.frames = seg.tok; ta.mult = bt.mult;
+        CHK(prof_begin(c, TTS_HIP_K_DAC_CONVT, 0, 2.0 * b.cin * (double) b.cout * 2 * bt.tot_frames * bt.mult * b.stride));
+        CHK(launch_convt(c, ta, b.w, (int) n));
         CHK(prof_end(c));
         std::swap(cur, t1);
-        L = ta.Lout; C = b.cout;
-        bt.tot_frames = (double) L;   // launch_conv's accounting: valid positions = tot_frames * mult
+        LS = ta.Lout; C = b.cout;
+        bt.mult *= b.stride;
         if (noise) {                                                                                              // gnac.cpp:155-159
-            CHK(launch_conv(c, bt, cur, C, L, b.noise_w, 0, 0, false, C, 1, 0, 1, nullptr, false, t1, 0, false, false));
-            hipLaunchKernelGGL(noise_fma_kernel, dim3((unsigned) (((size_t) C * L + 255) / 256)), dim3(256), 0, c->stream, cur, (const float *) t1,
-                               (const float *) (c->s_noise + noise_off), C, L);
+            CHK(launch_conv(c, bt, cur, C, LS, b.noise_w, 0, 0, false, C, 1, 0, 1, nullptr, false, t1, 0, false, false));
+            hipLaunchKernelGGL(noise_fma_kernel, dim3((LS + 255) / 256, C, n), dim3(256), 0, c->stream, cur, (const float *) t1, d_noise, C, LS, seg, bt.mult, cum);
             HIPCHK(hipGetLastError());
         }
-        noise_off += (size_t) L;
+        cum += bt.mult;
         for (int r = 0; r < 3; r++) {                                                                             // build_residual_unit, groups > 1
             int dil = 1;
             for (int e = 0; e < r; e++) dil *= 3;
             // snake(in_alpha) on the way in, depthwise k7, bias, and the pointwise conv's snake(out_alpha) on the way out
-            CHK(dw(cur, b.res[r].in_w, b.res[r].in_b, f32(b.res[r].in_alpha), f32(b.res[r].out_alpha), t1, C, L, 3 * dil, dil));
-            CHK(launch_conv(c, bt, t1, C, L, b.res[r].out_w, b.res[r].out_b, 0, false, C, 1, 0, 1, cur, false, t2));
+            CHK(dw(cur, b.res[r].in_w, b.res[r].in_b, f32(b.res[r].in_alpha), f32(b.res[r].out_alpha), t1, C, LS, 3 * dil, dil));
+            CHK(launch_conv(c, bt, t1, C, LS, b.res[r].out_w, b.res[r].out_b, 0, false, C, 1, 0, 1, cur, false, t2));
             std::swap(cur, t2);
         }
     }
-    CHK(launch_conv(c, bt, cur, C, L, c->s_fw, c->s_fb, c->s_falpha, true, 1, 7, 3, 1, nullptr, true, t1));        // :152-155
-    HIPCHK(hipMemcpyAsync(pcm_out, t1, (size_t) L * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(launch_conv(c, bt, cur, C, LS, c->s_fw, c->s_fb, c->s_falpha, true, 1, 7, 3, 1, nullptr, true, t1));        // :152-155
+    if (n_keep) {
+        size_t max_len = 0;
+        for (uint32_t z = 0; z < n; z++) max_len = std::max<size_t>(max_len, hs[5 * n + z]);
+        if (max_len) {
+            hipLaunchKernelGGL(snac_crop_kernel, dim3((unsigned) ((max_len + 255) / 256), n), dim3(256), 0, c->stream, (const float *) t1, LS, c->s_in + 3 * n, c->s_in + 4 * n,
+                               c->s_in + 5 * n, c->s_out);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(c->h_out, c->s_out, n_keep * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    return 0;
+}
+
+static int snac_ready(tts_hip_ctx *c, const char *what) {
+    if (!c || !c->has_snac) return set_err("%s: not a SNAC context (tts_hip_snac_create)", what);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
+    if (c->snac_pending.active) return set_err("%s: a window pass is under way (tts_hip_snac_decode_windows_end)", what);
+    return 0;
+}
+
+extern "C" int tts_hip_snac_decode_windows_end(tts_hip_ctx *c) {
+    if (!c || !c->has_snac) return set_err("tts_hip_snac_decode_windows_end: not a SNAC context (tts_hip_snac_create)");
+    if (!c->snac_pending.active) return set_err("tts_hip_snac_decode_windows_end: no pass under way (tts_hip_snac_decode_windows_begin)");
+    c->snac_pending.active = false;
+    HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->snac_pending.n) memcpy(c->snac_pending.pcm_out, c->h_out, c->snac_pending.n * 4);
+    return 0;
+}
+
+extern "C" int tts_hip_snac_decode_windows_begin(tts_hip_ctx *c, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1, uint32_t n,
+                                                 const float *noise, float *pcm_out) {
+    const char *what = "tts_hip_snac_decode_windows";
+    CHK(snac_ready(c, what));
+    if (n == 0) { c->snac_pending.active = true; c->snac_pending.pcm_out = pcm_out; c->snac_pending.n = 0; return 0; }
+    if (!codes || !frames || !keep0 || !keep1 || !pcm_out) return set_err("%s: null argument", what);
+    const uint32_t R = c->snac.repeats[0];
+    std::vector<uint32_t> tok(n), k0(n), k1(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (keep0[i] > keep1[i] || keep1[i] > frames[i]) return set_err("%s: window %u keeps frames [%u, %u) of %u", what, i, keep0[i], keep1[i], frames[i]);
+        if (frames[i] > 0x7FFFFFFFu / R) return set_err("%s: window %u of %u frames", what, i, frames[i]);
+        tok[i] = frames[i] * R; k0[i] = keep0[i] * R; k1[i] = keep1[i] * R;
+    }
+    size_t n_pcm = 0;
+    const int rc = snac_decode_pass(c, what, codes, tok.data(), k0.data(), k1.data(), n, noise, false, &n_pcm);
+    if (rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+    c->snac_pending.active = true; c->snac_pending.pcm_out = pcm_out; c->snac_pending.n = n_pcm;
+    return 0;
+}
+
+extern "C" int tts_hip_snac_decode_windows(tts_hip_ctx *c, const uint32_t *codes, const uint32_t *frames, const uint32_t *keep0, const uint32_t *keep1, uint32_t n,
+                                           const float *noise, float *pcm_out) {
+    CHK(tts_hip_snac_decode_windows_begin(c, codes, frames, keep0, keep1, n, noise, pcm_out));
+    return tts_hip_snac_decode_windows_end(c);
+}
+
+// one whole utterance: the pass with n = 1 that keeps everything
+extern "C" int tts_hip_snac_decode(tts_hip_ctx *c, const uint32_t *codes, uint32_t T_, const float *noise, float *pcm_out) {
+    CHK(snac_ready(c, "tts_hip_snac_decode"));
+    if (!codes || !pcm_out) return set_err("tts_hip_snac_decode: null argument");
+    if (T_ == 0) return 0;
+    const uint32_t zero = 0;
+    size_t n_pcm = 0;
+    const int rc = snac_decode_pass(c, "tts_hip_snac_decode", codes, &T_, &zero, &T_, 1, noise, true, &n_pcm);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    HIPCHK(e);
+    memcpy(pcm_out, c->h_out, n_pcm * 4);
     return 0;
 }
 

@@ -257,7 +257,10 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     for (uint32_t *p : {c->di_tok, c->di_epos, c->di_eseq, c->di_kbeg, c->di_kend, c->di_ids, c->di_pos, c->di_seq, c->di_cend, c->di_stok, c->di_loop, c->di_hist}) free_dev(p);
     free_dev(c->di_e16);
     for (int i = 0; i < 3; i++) free_dev(c->sbuf[i]);
-    free_dev(c->s_noise); free_dev(c->s_codes);
+    free_dev(c->s_in); free_dev(c->s_out);
+    if (c->h_in) (void) hipHostFree(c->h_in);
+    if (c->h_out) (void) hipHostFree(c->h_out);
+    if (c->h_hist) (void) hipHostFree(c->h_hist);
     free_dev(c->t5_bucket); free_dev(c->t5_x); free_dev(c->t5_qkv); free_dev(c->t5_att); free_dev(c->t5_ug); free_dev(c->t5_g); free_dev(c->t5_y); free_dev(c->t5_ids); free_dev(c->logits); free_dev(c->part); free_dev(c->attn_cnt); free_dev(c->b1_stamps); free_dev(c->dbg); free_dev(c->d_ids); free_dev(c->d_pos);
     free_dev(c->d_seq); free_dev(c->d_gather); free_dev(c->d_tok); free_dev(c->d_step); free_dev(c->d_steps_done); free_dev(c->d_tokens_out);
     free_dev(c->d_eos); free_dev(c->d_frames);

@@ -201,9 +201,26 @@ struct tts_hip_ctx {
     size_t s_codebook = 0, s_projw = 0, s_projb = 0, s_inw = 0, s_inb = 0, s_upw = 0, s_upb = 0, s_falpha = 0, s_fw = 0, s_fb = 0;
     int s_latent = 0, s_c0 = 0, s_cbdim = 0, s_cbsize = 0, s_up = 1, s_clast = 0;
     float *sbuf[3] = {nullptr, nullptr, nullptr};
-    float *s_noise = nullptr;
-    uint32_t *s_codes = nullptr;
     bool snac_packed = false;
+    // one pass (tts_hip_snac_decode / _decode_windows): segment table, codes and noise travel in one block, h_in (pinned) -> s_in; the
+    // cropped PCM comes back s_out -> h_out (pinned).  Capacities in 4-byte elements; sbuf holds dac_cap_frames tokens.
+    uint32_t *s_in = nullptr, *h_in = nullptr;
+    float *s_out = nullptr, *h_out = nullptr;
+    size_t s_in_cap = 0, s_out_cap = 0;
+    struct { bool active = false; float *pcm_out = nullptr; size_t n = 0; } snac_pending;   // between _decode_windows_begin and _end
+    // ---- Orpheus generation in pieces (tts_hip_orpheus_gen_begin / _launch / _wait) ----
+    struct LlamaGen {
+        bool active = false, lockstep = false, sampled = false;
+        uint32_t n_utt = 0, max_new = 0, stop_id = 0;
+        tts_hip_sampling sp{};
+        uint32_t pending = 0;                       // one sequence: steps enqueued by gen_launch that no gen_wait has read yet
+        std::vector<uint32_t> pos, cur, live;       // per utterance: next position, latest id; utterances still generating
+        std::vector<std::vector<uint32_t>> toks;    // ids so far
+        std::vector<uint32_t> handed;               // ... of which a gen_wait has handed out
+        std::vector<uint8_t> done;
+    } lg;
+    uint32_t *h_hist = nullptr;   // pinned: the ids of the steps of one gen_launch
+    size_t h_hist_cap = 0;
     // ---- T5 voice-prompt encoder context (tts_hip_t5_create) ----
     bool has_t5 = false;
     tts_hip_t5_desc t5{};

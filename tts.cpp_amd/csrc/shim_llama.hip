@@ -269,10 +269,17 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     return 0;
 }
 
+// between a tts_hip_orpheus_gen_launch and its gen_wait the steps may still be running on the stream: nothing else touches the context
+static int llama_gen_idle(const tts_hip_ctx *c, const char *what) {
+    if (c->lg.active && c->lg.pending) return set_err("%s: the steps of a tts_hip_orpheus_gen_launch are under way (tts_hip_orpheus_gen_wait first)", what);
+    return 0;
+}
+
 extern "C" int tts_hip_orpheus_decode(tts_hip_ctx *c, const uint32_t *ids, uint32_t n, uint32_t pos0, float *logits_out, uint32_t *token_out) {
     if (!c || !c->has_llama) return set_err("tts_hip_orpheus_decode: not an Orpheus context (tts_hip_orpheus_create)");
     if (!c->finalized || !c->weights_present) return set_err("tts_hip_orpheus_decode: context not finalized");
     if (!ids || n == 0) return set_err("tts_hip_orpheus_decode: no tokens");
+    CHK(llama_gen_idle(c, "tts_hip_orpheus_decode"));
     HIPCHK(hipSetDevice(c->device));
     uint32_t done = 0;
     while (done < n) {   // a long prompt goes through in pieces of RMAX rows (same cache semantics as one call)
@@ -345,18 +352,29 @@ static int check_llama_sampling(const tts_hip_ctx *c, const tts_hip_sampling *sp
     return 0;
 }
 
-// generate_from_batch (:378-392) with sampler::max (sp == NULL) or sampler::sample (sp, uniforms[max_new])
-static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp,
-                            const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
-    if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
-    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
-    if (!prompt || n_prompt == 0 || !tokens_out || !n_out) return set_err("%s: null argument", what);
-    *n_out = 0;
+// generate_from_batch (:378-392) with sampler::max (sp == NULL) or sampler::sample (sp, uniforms[max_new]), one sequence, in pieces:
+// begin = the prompt and the first selection, launch = up to n_steps replays of the captured step, wait = look at their ids.
+// An utterance ends once its last id is the stopping token, max_new ids exist or the cache is full.
+static void llama_gen_emit(tts_hip_ctx *c, uint32_t u, uint32_t tok) {
+    auto &g = c->lg;
+    g.toks[u].push_back(tok);
+    g.cur[u] = tok;
+    if (tok == g.stop_id || g.toks[u].size() >= g.max_new || g.pos[u] >= c->lm.n_ctx) g.done[u] = 1;
+}
+
+static int llama_gen_begin_one(tts_hip_ctx *c, const char *what, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp,
+                               const float *uniforms) {
+    auto &g = c->lg;
+    g.active = false;
+    if (!prompt || n_prompt == 0) return set_err("%s: null argument", what);
     HIPCHK(hipSetDevice(c->device));
+    g.lockstep = false; g.sampled = sp != nullptr; g.n_utt = 1; g.max_new = max_new; g.stop_id = stop_id; g.pending = 0;
+    if (sp) g.sp = *sp;
+    g.pos.assign(1, n_prompt); g.cur.assign(1, 0); g.toks.assign(1, {}); g.handed.assign(1, 0); g.done.assign(1, 0); g.live.clear();
+    if (max_new == 0) { g.done[0] = 1; g.active = true; return 0; }
     if (sp) {
         CHK(check_llama_sampling(c, sp, what));
         if (!uniforms) return set_err("%s: null uniforms", what);
-        if (max_new == 0) return 0;
         CHK(stage_uniforms(c, uniforms, (size_t) max_new));   // one sampler call per token, at most max_new tokens
         CHK(stage_penalty(c, sp->repetition_penalty, (int) max_new));
         const uint32_t init[3] = {0xFFFFFFFFu, 0u, 0u};   // sampler::reset (sampler.cpp:71-80): last token -1, count 0; call index 0
@@ -369,7 +387,7 @@ static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *pr
             c->l_smp_baked.uni = c->d_uniforms; c->l_smp_baked.pen = pen; c->l_smp_baked.k = sp->top_k; c->l_smp_baked.temp = sp->temperature; c->l_smp_baked.top_p = sp->top_p;
         }
     }
-    uint32_t tok = 0, pos = n_prompt;
+    uint32_t tok = 0;
     {   // the prompt (pieces of RMAX rows), then the first selection
         uint32_t done = 0;
         while (done < n_prompt) {
@@ -381,63 +399,133 @@ static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *pr
         HIPCHK(hipMemcpyAsync(&tok, c->l_tok, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    // stop once the last token is the stopping token or max_generation_size ids exist.  The token never leaves the device inside a
-    // chunk of LLAMA_GREEDY_CHUNK steps (the selection writes it back as the next input and bumps the position); the host looks at
-    // a chunk's tokens at once, so at most CHUNK-1 steps run past the stopping token (their cache rows are never read: the next
-    // call starts at position 0; the sampler draws they consume belong to no token).
-    uint32_t *hist = c->l_tok + 1 + 2 * ARGMAX_PARTS;
-    uint32_t host_hist[LLAMA_GREEDY_CHUNK];
-    while (*n_out < max_new) {
-        tokens_out[(*n_out)++] = tok;
-        if (tok == stop_id || *n_out >= max_new) break;
-        if (pos >= c->lm.n_ctx) break;
-        const uint32_t chunk = std::min<uint32_t>(std::min<uint32_t>(LLAMA_GREEDY_CHUNK, max_new - *n_out), c->lm.n_ctx - pos);
-        HIPCHK(hipMemcpyAsync(c->l_ids, &tok, 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->l_pos, &pos, 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));  // tok / pos are reused below
-        if (c->llama_graph && !c->prof) {
-            // one captured step (forward + selection + feedback) replayed `chunk` times; the history slot is a device counter
-            uint32_t *hist_idx = hist + LLAMA_GREEDY_CHUNK;
+    llama_gen_emit(c, 0, tok);
+    g.active = true;
+    return 0;
+}
+
+// The token never leaves the device between two steps (the selection writes it back as the next input and bumps the position).  The
+// history the captured step writes holds LLAMA_GREEDY_CHUNK ids: after that many replays it is copied to pinned host memory and its
+// counter reset, all on the stream, so a launch of any size returns at once.  Steps run past the stopping token are discarded by
+// gen_wait (their cache rows are never read: the next generation starts at position 0; the sampler draws they consume belong to no token).
+static int llama_gen_launch_one(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
+    auto &g = c->lg;
+    if (g.pending) return set_err("%s: the steps of the last gen_launch have not been looked at (gen_wait)", what);
+    if (g.done[0] || n_steps == 0) return 0;
+    const tts_hip_sampling *sp = g.sampled ? &g.sp : nullptr;
+    const uint32_t pos = g.pos[0];
+    const uint32_t steps = std::min<uint32_t>(std::min<uint32_t>(n_steps, g.max_new - (uint32_t) g.toks[0].size()), c->lm.n_ctx - pos);
+    if (steps > c->h_hist_cap) {
+        if (c->h_hist) { (void) hipHostFree(c->h_hist); c->h_hist = nullptr; c->h_hist_cap = 0; }
+        const size_t cap = std::max<size_t>(steps, 64);
+        HIPCHK(hipHostMalloc((void **) &c->h_hist, cap * 4));
+        c->h_hist_cap = cap;
+    }
+    uint32_t *hist = c->l_tok + 1 + 2 * ARGMAX_PARTS, *hist_idx = hist + LLAMA_GREEDY_CHUNK;
+    HIPCHK(hipMemcpyAsync(c->l_ids, &g.cur[0], 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->l_pos, &g.pos[0], 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const bool graph = c->llama_graph && !c->prof;
+    hipGraphExec_t exec = nullptr;
+    if (graph) {
+        // one captured step (forward + selection + feedback); the history slot is a device counter
+        const int key = sp ? 9000002 : 9000001;
+        auto it = c->graphs.find(key);
+        if (it == c->graphs.end()) {
+            // one eager pass first: per-kernel attributes are set outside the capture (it rewrites the cache row of `pos`
+            // with the values the first replay writes again, nothing else)
+            CHK(llama_forward(c, nullptr, 1, pos, (int) c->lm.n_ctx));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            hipGraph_t gr = nullptr;
+            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            int rc = llama_forward(c, nullptr, 1, 0, (int) c->lm.n_ctx);
+            if (rc == 0) rc = llama_select(c, sp, true, nullptr, true);
+            const hipError_t e = hipStreamEndCapture(c->stream, &gr);
+            if (rc != 0) { if (gr) (void) hipGraphDestroy(gr); return rc; }
+            if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
+            HIPCHK(hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0));
+            (void) hipGraphDestroy(gr);
+            it = c->graphs.emplace(key, exec).first;
+        }
+        exec = it->second;
+    }
+    for (uint32_t s0 = 0; s0 < steps; s0 += LLAMA_GREEDY_CHUNK) {
+        const uint32_t chunk = std::min<uint32_t>(LLAMA_GREEDY_CHUNK, steps - s0);
+        if (graph) {
             HIPCHK(hipMemsetAsync(hist_idx, 0, 4, c->stream));
-            if (pos + chunk > c->lm.n_ctx) return set_err("%s: positions exceed the cache", what);
-            const int key = sp ? 9000002 : 9000001;
-            auto it = c->graphs.find(key);
-            if (it == c->graphs.end()) {
-                // one eager pass first: per-kernel attributes are set outside the capture (it rewrites the cache row of `pos`
-                // with the values the first replay writes again, nothing else)
-                CHK(llama_forward(c, nullptr, 1, pos, (int) c->lm.n_ctx));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                hipGraph_t graph = nullptr;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                int rc = llama_forward(c, nullptr, 1, 0, (int) c->lm.n_ctx);
-                if (rc == 0) rc = llama_select(c, sp, true, nullptr, true);
-                const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-                if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-                if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void) hipGraphDestroy(graph);
-                it = c->graphs.emplace(key, exec).first;
-            }
-            for (uint32_t s = 0; s < chunk; s++) HIPCHK(hipGraphLaunch(it->second, c->stream));
+            for (uint32_t s = 0; s < chunk; s++) HIPCHK(hipGraphLaunch(exec, c->stream));
         } else {
             for (uint32_t s = 0; s < chunk; s++) {
-                CHK(llama_forward(c, nullptr, 1, pos + s));
+                CHK(llama_forward(c, nullptr, 1, pos + s0 + s));
                 CHK(llama_select(c, sp, false, hist + s, true));
             }
         }
-        HIPCHK(hipMemcpyAsync(host_hist, hist, (size_t) chunk * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        pos += chunk;
-        // all but the chunk's last token are final here; the last one goes through the loop head like any other
-        uint32_t s = 0;
-        for (; s + 1 < chunk; s++) {
-            tokens_out[(*n_out)++] = host_hist[s];
-            if (host_hist[s] == stop_id || *n_out >= max_new) return 0;
-        }
-        tok = host_hist[s];
+        HIPCHK(hipMemcpyAsync(c->h_hist + s0, hist, (size_t) chunk * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    g.pending = steps;
+    return 0;
+}
+
+static int llama_gen_wait_one(tts_hip_ctx *c) {
+    auto &g = c->lg;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t steps = g.pending;
+    g.pending = 0;
+    if (steps == 0) return 0;
+    g.pos[0] += steps;
+    for (uint32_t s = 0; s < steps && !g.done[0]; s++) {
+        // only the launch's last id meets the end of the cache: the ids before it were fed back inside the launch
+        g.toks[0].push_back(c->h_hist[s]);
+        g.cur[0] = c->h_hist[s];
+        if (c->h_hist[s] == g.stop_id || g.toks[0].size() >= g.max_new || (s + 1 == steps && g.pos[0] >= c->lm.n_ctx)) g.done[0] = 1;
     }
     return 0;
+}
+
+static int llama_gen_begin_rows(tts_hip_ctx *c, const char *what, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                const tts_hip_sampling *sp, const float *uniforms);
+static int llama_gen_launch_rows(tts_hip_ctx *c, const char *what, uint32_t n_steps);
+
+static int llama_gen_ready(tts_hip_ctx *c, const char *what, bool may_be_running = false) {
+    if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
+    return may_be_running ? 0 : llama_gen_idle(c, what);
+}
+
+static int llama_gen_wait(tts_hip_ctx *c, const char *what, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    auto &g = c->lg;
+    if (!g.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
+    if (!tokens_out || !n_out) return set_err("%s: null argument", what);
+    HIPCHK(hipSetDevice(c->device));
+    if (!g.lockstep) CHK(llama_gen_wait_one(c));
+    for (uint32_t u = 0; u < g.n_utt; u++) {
+        for (size_t i = g.handed[u]; i < g.toks[u].size(); i++) tokens_out[(size_t) u * g.max_new + i] = g.toks[u][i];
+        g.handed[u] = n_out[u] = (uint32_t) g.toks[u].size();
+        if (done) done[u] = g.done[u];
+    }
+    return 0;
+}
+
+static bool llama_gen_all_done(const tts_hip_ctx *c) {
+    for (uint8_t d : c->lg.done) if (!d) return false;
+    return true;
+}
+
+static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp,
+                            const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
+    CHK(llama_gen_ready(c, what));
+    if (!prompt || n_prompt == 0 || !tokens_out || !n_out) return set_err("%s: null argument", what);
+    *n_out = 0;
+    CHK(llama_gen_begin_one(c, what, prompt, n_prompt, max_new, stop_id, sp, uniforms));
+    // the host looks at LLAMA_GREEDY_CHUNK steps at once, so at most CHUNK-1 steps run past the stopping token
+    int rc = 0;
+    while (rc == 0 && !llama_gen_all_done(c)) {
+        rc = llama_gen_launch_one(c, what, LLAMA_GREEDY_CHUNK);
+        if (rc == 0) rc = llama_gen_wait_one(c);
+    }
+    if (rc == 0 && max_new) rc = llama_gen_wait(c, what, tokens_out, n_out, nullptr);
+    c->lg.active = false;
+    return rc;
 }
 
 extern "C" int tts_hip_orpheus_generate_greedy(tts_hip_ctx *c, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id,
@@ -456,6 +544,7 @@ extern "C" int tts_hip_orpheus_sample_logits(tts_hip_ctx *c, const float *logits
     if (!c || !c->has_llama) return set_err("tts_hip_orpheus_sample_logits: not an Orpheus context (tts_hip_orpheus_create)");
     if (!c->finalized) return set_err("tts_hip_orpheus_sample_logits: context not finalized");
     if (!logits || !token_out) return set_err("tts_hip_orpheus_sample_logits: null argument");
+    CHK(llama_gen_idle(c, "tts_hip_orpheus_sample_logits"));
     CHK(check_llama_sampling(c, sp, "tts_hip_orpheus_sample_logits"));
     HIPCHK(hipSetDevice(c->device));
     const bool rep = sp->repetition_penalty != 1.0f;
@@ -511,6 +600,7 @@ extern "C" int tts_hip_orpheus_step_batch(tts_hip_ctx *c, uint32_t n, const uint
     if (!c || !c->has_llama) return set_err("tts_hip_orpheus_step_batch: not an Orpheus context (tts_hip_orpheus_create)");
     if (!c->finalized || !c->weights_present) return set_err("tts_hip_orpheus_step_batch: context not finalized");
     if (!slots || !ids || !pos) return set_err("tts_hip_orpheus_step_batch: null argument");
+    CHK(llama_gen_idle(c, "tts_hip_orpheus_step_batch"));
     if (n > c->lm.max_seqs) return set_err("tts_hip_orpheus_step_batch: %u rows > max_seqs %u (one row per utterance)", n, c->lm.max_seqs);
     HIPCHK(hipSetDevice(c->device));
     uint32_t max_pos = 0;
@@ -544,16 +634,60 @@ static int llama_prefill_slot(tts_hip_ctx *c, const char *what, uint32_t slot, c
 
 // generate_from_batch (orpheus/model.cpp:378-392) for n_utt utterances in lock-step: every utterance gets exactly the tokens its own one-sequence
 // generation gets (sampler::max, or sampler::sample with its own uniforms and repetition state); finished utterances leave the step.
-extern "C" int tts_hip_orpheus_generate_batch(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
-                                              const tts_hip_sampling *sp, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
-    const char *what = "tts_hip_orpheus_generate_batch";
-    if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
-    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
-    if (!prompts || !n_prompt || !tokens_out || !n_out) return set_err("%s: null argument", what);
+// In pieces like the one-sequence loop: begin = prompts + first selection, launch = up to n_steps host-driven steps (each looks at its ids, so
+// nothing runs past a stopping token), wait = hand out.
+// select for logits row r on behalf of utterance utt[r] -> l_btok[r]
+static int llama_select_rows(tts_hip_ctx *c, const std::vector<uint32_t> &utt) {
+    auto &g = c->lg;
+    const int n = (int) utt.size();
+    if (!g.sampled) return llama_argmax_rows(c, n);
+    const tts_hip_sampling *sp = &g.sp;
+    const double *pen = sp->repetition_penalty != 1.0f ? c->d_pen : nullptr;
+    for (int r = 0; r < n; r++) {
+        const uint32_t u = utt[(size_t) r];
+        int32_t *last = (int32_t *) (c->l_bsmp + 3 * u);
+        uint32_t *repc = c->l_bsmp + 3 * u + 1, *call = c->l_bsmp + 3 * u + 2;
+        const float *lg = c->l_logits + (size_t) r * c->l_Vpad;
+        hipLaunchKernelGGL(topk_parts_kernel, dim3(TOPK_PARTS), dim3(512), 0, c->stream, lg, c->l_V, (int) sp->top_k, pen, c->pen_len, (const int32_t *) last, (const uint32_t *) repc, c->l_cand);
+        HIPCHK(hipGetLastError());
+        float *total = nullptr;
+        if (sp->top_p < 1.0f) {
+            total = (float *) (c->l_cand + (size_t) TOPK_PARTS * TOPK_MAXK);
+            hipLaunchKernelGGL(softmax_total_kernel, dim3(1), dim3(1024), 0, c->stream, lg, c->l_V, (const unsigned long long *) c->l_cand, sp->temperature, pen, c->pen_len,
+                               (const int32_t *) last, (const uint32_t *) repc, total);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(topk_sample_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long *) c->l_cand, (int) sp->top_k, sp->temperature,
+                           (const float *) c->d_uniforms + (size_t) u * g.max_new, call, pen, last, repc, c->l_btok + r, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr,
+                           (uint32_t *) nullptr, sp->top_p, (const float *) total);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// the head of orpheus_generate's loop, per live utterance: record the latest id; stop on the stopping token, at max_new ids or at the end of the cache
+static void llama_gen_emit_rows(tts_hip_ctx *c) {
+    auto &g = c->lg;
+    std::vector<uint32_t> next;
+    for (uint32_t u : g.live) {
+        llama_gen_emit(c, u, g.cur[u]);
+        if (!g.done[u]) next.push_back(u);
+    }
+    g.live.swap(next);   // utterances still generating, in utterance order (= the rows of the next step)
+}
+
+static int llama_gen_begin_rows(tts_hip_ctx *c, const char *what, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                const tts_hip_sampling *sp, const float *uniforms) {
+    auto &g = c->lg;
+    g.active = false;
+    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
     if (n_utt == 0 || n_utt > c->lm.max_seqs) return set_err("%s: %u utterances outside 1..max_seqs = %u", what, n_utt, c->lm.max_seqs);
     HIPCHK(hipSetDevice(c->device));
-    for (uint32_t u = 0; u < n_utt; u++) { n_out[u] = 0; if (n_prompt[u] == 0 || n_prompt[u] >= c->lm.n_ctx) return set_err("%s: utterance %u: prompt of %u ids", what, u, n_prompt[u]); }
-    if (max_new == 0) return 0;
+    for (uint32_t u = 0; u < n_utt; u++) if (n_prompt[u] == 0 || n_prompt[u] >= c->lm.n_ctx) return set_err("%s: utterance %u: prompt of %u ids", what, u, n_prompt[u]);
+    g.lockstep = true; g.sampled = sp != nullptr; g.n_utt = n_utt; g.max_new = max_new; g.stop_id = stop_id; g.pending = 0;
+    if (sp) g.sp = *sp;
+    g.pos.assign(n_utt, 0); g.cur.assign(n_utt, 0); g.toks.assign(n_utt, {}); g.handed.assign(n_utt, 0); g.done.assign(n_utt, 0); g.live.clear();
+    if (max_new == 0) { g.done.assign(n_utt, 1); g.active = true; return 0; }
     if (sp) {
         CHK(check_llama_sampling(c, sp, what));
         if (!uniforms) return set_err("%s: null uniforms", what);
@@ -564,70 +698,76 @@ extern "C" int tts_hip_orpheus_generate_batch(tts_hip_ctx *c, uint32_t n_utt, co
         HIPCHK(hipMemcpyAsync(c->l_bsmp, init.data(), init.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    // select for logits row r on behalf of utterance u -> l_btok[r]
-    auto select_rows = [&](const std::vector<uint32_t> &utt) -> int {
-        const int n = (int) utt.size();
-        if (!sp) return llama_argmax_rows(c, n);
-        const double *pen = sp->repetition_penalty != 1.0f ? c->d_pen : nullptr;
-        for (int r = 0; r < n; r++) {
-            const uint32_t u = utt[(size_t) r];
-            int32_t *last = (int32_t *) (c->l_bsmp + 3 * u);
-            uint32_t *repc = c->l_bsmp + 3 * u + 1, *call = c->l_bsmp + 3 * u + 2;
-            const float *lg = c->l_logits + (size_t) r * c->l_Vpad;
-            hipLaunchKernelGGL(topk_parts_kernel, dim3(TOPK_PARTS), dim3(512), 0, c->stream, lg, c->l_V, (int) sp->top_k, pen, c->pen_len, (const int32_t *) last, (const uint32_t *) repc, c->l_cand);
-            HIPCHK(hipGetLastError());
-            float *total = nullptr;
-            if (sp->top_p < 1.0f) {
-                total = (float *) (c->l_cand + (size_t) TOPK_PARTS * TOPK_MAXK);
-                hipLaunchKernelGGL(softmax_total_kernel, dim3(1), dim3(1024), 0, c->stream, lg, c->l_V, (const unsigned long long *) c->l_cand, sp->temperature, pen, c->pen_len,
-                                   (const int32_t *) last, (const uint32_t *) repc, total);
-                HIPCHK(hipGetLastError());
-            }
-            hipLaunchKernelGGL(topk_sample_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long *) c->l_cand, (int) sp->top_k, sp->temperature,
-                               (const float *) c->d_uniforms + (size_t) u * max_new, call, pen, last, repc, c->l_btok + r, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr,
-                               (uint32_t *) nullptr, sp->top_p, (const float *) total);
-            HIPCHK(hipGetLastError());
-        }
-        return 0;
-    };
     // prompts, then the first selection from every utterance's last prompt row (logits row u)
     size_t off = 0;
-    std::vector<uint32_t> utt(n_utt), pos(n_utt), tok(n_utt), slots, ids, ps;
     for (uint32_t u = 0; u < n_utt; u++) {
         CHK(llama_prefill_slot(c, what, u, prompts + off, n_prompt[u]));
         off += n_prompt[u];
-        utt[u] = u;
-        pos[u] = n_prompt[u];
+        g.live.push_back(u);
+        g.pos[u] = n_prompt[u];
     }
-    CHK(select_rows(utt));
-    HIPCHK(hipMemcpyAsync(tok.data(), c->l_btok, (size_t) n_utt * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(llama_select_rows(c, g.live));
+    HIPCHK(hipMemcpyAsync(g.cur.data(), c->l_btok, (size_t) n_utt * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    // the loop of orpheus_generate, per utterance: record the token; stop on the stopping token, at max_new ids or at the end of the cache
-    std::vector<uint32_t> live;   // utterances still generating, in utterance order (= the rows of the next step)
-    for (uint32_t u = 0; u < n_utt; u++) live.push_back(u);
-    std::vector<uint32_t> cur(n_utt);
-    for (uint32_t u = 0; u < n_utt; u++) cur[u] = tok[u];
-    while (!live.empty()) {
-        std::vector<uint32_t> next;
-        for (uint32_t u : live) {
-            tokens_out[(size_t) u * max_new + n_out[u]++] = cur[u];
-            if (cur[u] == stop_id || n_out[u] >= max_new || pos[u] >= c->lm.n_ctx) continue;
-            next.push_back(u);
-        }
-        live.swap(next);
-        if (live.empty()) break;
-        const uint32_t n = (uint32_t) live.size();
-        slots.resize(n); ids.resize(n); ps.resize(n);
-        for (uint32_t r = 0; r < n; r++) { slots[r] = live[r]; ids[r] = cur[live[r]]; ps[r] = pos[live[r]]; }
+    llama_gen_emit_rows(c);
+    g.active = true;
+    return 0;
+}
+
+static int llama_gen_launch_rows(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
+    auto &g = c->lg;
+    std::vector<uint32_t> slots, ids, ps, tok;
+    for (uint32_t s = 0; s < n_steps && !g.live.empty(); s++) {
+        const uint32_t n = (uint32_t) g.live.size();
+        slots.resize(n); ids.resize(n); ps.resize(n); tok.resize(n);
+        for (uint32_t r = 0; r < n; r++) { slots[r] = g.live[r]; ids[r] = g.cur[g.live[r]]; ps[r] = g.pos[g.live[r]]; }
         uint32_t max_pos = 0;
         CHK(llama_stage_rows(c, what, n, slots.data(), ids.data(), ps.data(), &max_pos));
         CHK(llama_forward(c, nullptr, (int) n, 0, (int) max_pos + 1, c->l_seq, -1));
-        CHK(select_rows(live));
+        CHK(llama_select_rows(c, g.live));
         HIPCHK(hipMemcpyAsync(tok.data(), c->l_btok, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t r = 0; r < n; r++) { cur[live[r]] = tok[r]; pos[live[r]]++; }
+        for (uint32_t r = 0; r < n; r++) { g.cur[g.live[r]] = tok[r]; g.pos[g.live[r]]++; }
+        llama_gen_emit_rows(c);
     }
     return 0;
+}
+
+extern "C" int tts_hip_orpheus_generate_batch(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                              const tts_hip_sampling *sp, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
+    const char *what = "tts_hip_orpheus_generate_batch";
+    CHK(llama_gen_ready(c, what));
+    if (!prompts || !n_prompt || !tokens_out || !n_out) return set_err("%s: null argument", what);
+    for (uint32_t u = 0; u < n_utt && u < c->lm.max_seqs; u++) n_out[u] = 0;
+    CHK(llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms));
+    int rc = 0;
+    while (rc == 0 && !c->lg.live.empty()) rc = llama_gen_launch_rows(c, what, 64);
+    if (rc == 0 && max_new) rc = llama_gen_wait(c, what, tokens_out, n_out, nullptr);
+    c->lg.active = false;
+    return rc;
+}
+
+extern "C" int tts_hip_orpheus_gen_begin(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                         const tts_hip_sampling *sp, const float *uniforms) {
+    const char *what = "tts_hip_orpheus_gen_begin";
+    CHK(llama_gen_ready(c, what));
+    c->lg.active = false;
+    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
+    if (n_utt == 1) return llama_gen_begin_one(c, what, prompts, n_prompt[0], max_new, stop_id, sp, uniforms);
+    return llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms);
+}
+
+extern "C" int tts_hip_orpheus_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    const char *what = "tts_hip_orpheus_gen_launch";
+    CHK(llama_gen_ready(c, what));
+    if (!c->lg.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
+    HIPCHK(hipSetDevice(c->device));
+    return c->lg.lockstep ? llama_gen_launch_rows(c, what, n_steps) : llama_gen_launch_one(c, what, n_steps);
+}
+
+extern "C" int tts_hip_orpheus_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    CHK(llama_gen_ready(c, "tts_hip_orpheus_gen_wait", true));
+    return llama_gen_wait(c, "tts_hip_orpheus_gen_wait", tokens_out, n_out, done);
 }
 
 extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *dd) {

@@ -88,6 +88,8 @@ EXPORTS = [
     "tts_hip_synchronize", "tts_hip_dac_arith", "tts_hip_broadcast_weights", "tts_hip_comm_unique_id", "tts_hip_broadcast_weights_rank", "tts_hip_tune",
     "tts_hip_parler_stream_begin", "tts_hip_parler_stream_admit", "tts_hip_parler_stream_run", "tts_hip_parler_stream_collect", "tts_hip_parler_stream_end",
     "tts_hip_parler_gen_begin", "tts_hip_parler_gen_launch", "tts_hip_parler_gen_wait", "tts_hip_dac_halo_frames", "tts_hip_dac_decode_windows",
+    "tts_hip_snac_halo_frames", "tts_hip_snac_decode_windows", "tts_hip_snac_decode_windows_begin", "tts_hip_snac_decode_windows_end",
+    "tts_hip_orpheus_gen_begin", "tts_hip_orpheus_gen_launch", "tts_hip_orpheus_gen_wait",
 ]
 
 class Sampling(C.Structure):
@@ -187,6 +189,13 @@ def load_lib():
     L.tts_hip_parler_gen_wait.argtypes = [vp, u32p, u32p, u32p]
     L.tts_hip_dac_halo_frames.argtypes = [C.POINTER(Desc)]
     L.tts_hip_dac_decode_windows.argtypes = [vp, u32p, u32p, u32p, u32p, C.c_uint32, f32p]
+    L.tts_hip_snac_halo_frames.argtypes = [C.POINTER(SnacDesc)]
+    L.tts_hip_snac_decode_windows.argtypes = [vp, u32p, u32p, u32p, u32p, C.c_uint32, f32p, f32p]
+    L.tts_hip_snac_decode_windows_begin.argtypes = [vp, u32p, u32p, u32p, u32p, C.c_uint32, f32p, f32p]
+    L.tts_hip_snac_decode_windows_end.argtypes = [vp]
+    L.tts_hip_orpheus_gen_begin.argtypes = [vp, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.POINTER(Sampling), f32p]
+    L.tts_hip_orpheus_gen_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_orpheus_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8)]
     _lib = L
     return L
 
@@ -204,6 +213,30 @@ def desc_for(cfg):
 def dac_halo_frames(desc):
     """tts_hip_dac_halo_frames: a pure function of the codec layout, no device needed"""
     h = load_lib().tts_hip_dac_halo_frames(C.byref(desc))
+    if h < 0:
+        raise HipError(load_lib().tts_hip_last_error().decode("utf-8", "replace"))
+    return h
+
+
+def snac_desc_for(cfg, flags=0):
+    """tts_hip_snac_desc of a synth.SnacConfig"""
+    d = SnacDesc()
+    d.struct_size = C.sizeof(SnacDesc)
+    d.n_blocks = len(cfg.strides)
+    c = cfg.c0
+    for i, (s, p) in enumerate(zip(cfg.strides, cfg.paddings)):
+        c //= 2
+        d.stride[i], d.padding[i], d.groups[i] = s, p, c
+    d.n_codebooks = len(cfg.repeats)
+    for i, r in enumerate(cfg.repeats):
+        d.repeats[i] = r
+    d.max_frames, d.flags = cfg.max_frames, flags
+    return d
+
+
+def snac_halo_frames(cfg):
+    """tts_hip_snac_halo_frames of a synth.SnacConfig: a pure function of the codec layout, no device needed"""
+    h = load_lib().tts_hip_snac_halo_frames(C.byref(snac_desc_for(cfg)))
     if h < 0:
         raise HipError(load_lib().tts_hip_last_error().decode("utf-8", "replace"))
     return h
@@ -552,17 +585,7 @@ class SnacEngine:
     def __init__(self, cfg, device=0, flags=0):
         self.L = load_lib()
         self.cfg = cfg
-        d = SnacDesc()
-        d.struct_size = C.sizeof(SnacDesc)
-        d.n_blocks = len(cfg.strides)
-        c = cfg.c0
-        for i, (s, p) in enumerate(zip(cfg.strides, cfg.paddings)):
-            c //= 2
-            d.stride[i], d.padding[i], d.groups[i] = s, p, c
-        d.n_codebooks = len(cfg.repeats)
-        for i, r in enumerate(cfg.repeats):
-            d.repeats[i] = r
-        d.max_frames, d.flags = cfg.max_frames, flags
+        d = snac_desc_for(cfg, flags)
         self.ctx = self.L.tts_hip_snac_create(device, C.byref(d))
         if not self.ctx:
             raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
@@ -585,6 +608,34 @@ class SnacEngine:
         self._chk(self.L.tts_hip_snac_decode(self.ctx, ap, T, None if nz is None else nz.ctypes.data_as(C.POINTER(C.c_float)),
                                              out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def halo_frames(self):
+        return snac_halo_frames(self.cfg)
+
+    def decode_windows(self, windows, split=False):
+        """tts_hip_snac_decode_windows: windows = [(codes of the window (level-major, 4 * frames finest tokens), frames, keep0, keep1, noise of the
+        window or None)] -> the kept PCM of each; noise on all windows or on none.  split: through _begin / _end."""
+        n = len(windows)
+        if n == 0:
+            return []
+        with_noise = windows[0][4] is not None
+        assert all((w[4] is not None) == with_noise for w in windows)
+        cat, cp = _u32(np.concatenate([np.asarray(w[0], dtype=np.uint32).reshape(-1) for w in windows]))
+        fr, fp = _u32([w[1] for w in windows])
+        k0, k0p = _u32([w[2] for w in windows])
+        k1, k1p = _u32([w[3] for w in windows])
+        nz = np.ascontiguousarray(np.concatenate([np.asarray(w[4], dtype=np.float32) for w in windows])) if with_noise else None
+        nzp = nz.ctypes.data_as(C.POINTER(C.c_float)) if with_noise else None
+        per = 4 * self.cfg.hop
+        out = np.empty(int((k1.astype(np.int64) - k0).sum()) * per, dtype=np.float32)
+        op = out.ctypes.data_as(C.POINTER(C.c_float))
+        if split:
+            self._chk(self.L.tts_hip_snac_decode_windows_begin(self.ctx, cp, fp, k0p, k1p, n, nzp, op))
+            self._chk(self.L.tts_hip_snac_decode_windows_end(self.ctx))
+        else:
+            self._chk(self.L.tts_hip_snac_decode_windows(self.ctx, cp, fp, k0p, k1p, n, nzp, op))
+        cuts = np.cumsum([(int(b) - int(a)) * per for a, b in zip(k0, k1)])[:-1]
+        return np.split(out, cuts)
 
     def close(self):
         if self.ctx:
@@ -690,6 +741,29 @@ class OrpheusEngine:
         self._chk(self.L.tts_hip_orpheus_generate_batch(self.ctx, n, cp, lp, max_new, stop_id, spp, up, out.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                         cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [out[i, :cnt[i]].copy() for i in range(n)]
+
+    def gen_begin(self, prompts, max_new, stop_id, uniforms=None, top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0):
+        """tts_hip_orpheus_gen_begin: prompts = one id list per utterance; uniforms [n_utt][max_new] selects sampler::sample, None = greedy"""
+        n = len(prompts)
+        cat, cp = _u32(np.concatenate([np.asarray(p, dtype=np.uint32) for p in prompts]))
+        lens, lp = _u32(np.array([len(p) for p in prompts], dtype=np.uint32))
+        spp, up = None, None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n, max_new)
+            sp_ = Sampling(top_k, top_p, temperature, repetition_penalty)
+            spp, up = C.byref(sp_), u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_orpheus_gen_begin(self.ctx, n, cp, lp, max_new, stop_id, spp, up))
+        self._gen = (np.zeros((n, max_new), dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8))   # a refused begin leaves the generation under way alone
+
+    def gen_launch(self, n_steps):
+        self._chk(self.L.tts_hip_orpheus_gen_launch(self.ctx, n_steps))
+
+    def gen_wait(self):
+        """-> (ids so far per utterance, ended per utterance)"""
+        out, cnt, done = self._gen
+        self._chk(self.L.tts_hip_orpheus_gen_wait(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), cnt.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  done.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return [out[i, :cnt[i]].copy() for i in range(len(cnt))], done.astype(bool).copy()
 
     def sample_logits(self, logits, uniform, top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0, last_id=-1, rep_count=0):
         """the device sampler on caller-supplied logits [vocab] -> (token, last_id, rep_count)"""

@@ -99,6 +99,7 @@ orpheus_runner::orpheus_runner(const orpheus_hparams & hp_, bpe_tokenizer * tok,
         lm = nullptr;
         TTS_ABORT("tts_hip_snac_create failed: %s\n", tts_hip_last_error());
     }
+    snac_halo = tts_hip_snac_halo_frames(&s);
     sampling_rate = 24000.0f;           // model.h:112
     supports_voices = true;
     smp.n_output_heads = 1;             // model.h:113-115
@@ -144,7 +145,13 @@ std::vector<std::vector<uint32_t>> orpheus_runner::prepare_output_tokens(const s
     return levels;
 }
 
-void orpheus_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+// what tts_hip_orpheus_generate_sampled's device sampler takes (top_k 1..64, any top_p > 0); TTS_HOST_LOOP forces the host sampler
+bool orpheus_runner::device_sampler(const generation_configuration & config) const {
+    return config.sample && !getenv("TTS_HOST_LOOP") && config.top_p > 0.0f && config.top_k >= 1 && config.top_k <= 64 && (uint32_t) config.top_k < hp.vocab_size;
+}
+
+// the sampler as a generate() call starts it: the call's parameters, n_calls = 0, reset
+void orpheus_runner::sampler_setup(const generation_configuration & config) {
     smp.temperature = config.temperature;
     smp.repetition_penalty = config.repetition_penalty;
     smp.do_sample = config.sample;
@@ -152,13 +159,23 @@ void orpheus_runner::generate(const char * sentence, tts_response & output, cons
     smp.top_p = config.top_p;
     smp.seed = config.seed;
     smp.n_calls = 0;
+    smp.reset();
+}
+
+// voice check, framing and tokenisation, length check; the prompt is remembered in last_prompt_tokens
+std::vector<uint32_t> orpheus_runner::checked_prompt(const std::string & sentence, const generation_configuration & config) {
     if (!config.voice.empty() && std::find(orpheus_voices.begin(), orpheus_voices.end(), config.voice) == orpheus_voices.end())
         TTS_ABORT("Voice '%s' is not a valid voice for Orpheus.\n", config.voice.c_str());
-    const std::vector<uint32_t> prompt = batch_from_sentence(sentence, config.voice);
-    last_prompt_tokens = prompt;
+    std::vector<uint32_t> prompt = batch_from_sentence(sentence, config.voice);
     if (prompt.size() > hp.max_context_length)
         TTS_ABORT("The prompt was too large for the default context window. Try splitting up or shortenning the prompt.\n");
-    smp.reset();
+    last_prompt_tokens = prompt;
+    return prompt;
+}
+
+void orpheus_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+    const std::vector<uint32_t> prompt = checked_prompt(sentence, config);
+    sampler_setup(config);
     output.data = nullptr;
     output.n_outputs = 0;
 
@@ -171,7 +188,7 @@ void orpheus_runner::generate(const char * sentence, tts_response & output, cons
         hip_check(tts_hip_orpheus_generate_greedy(lm, prompt.data(), (uint32_t) prompt.size(), hp.max_generation_size, hp.stopping_token_id, out.data(), &n),
                   "tts_hip_orpheus_generate_greedy");
         out.resize(n);
-    } else if (!getenv("TTS_HOST_LOOP") && config.top_p > 0.0f && config.top_k >= 1 && config.top_k <= 64 && (uint32_t) config.top_k < hp.vocab_size) {
+    } else if (device_sampler(config)) {
         // top_k in 1..64 (the default generation_configuration: top_k 50, top_p 1): sampler::sample runs on the device, two kernels pick the
         // top_k candidates out of the 156 940 logits (top_p < 1: a third accumulates the full-vocabulary softmax total in index order first,
         // round 5); the U[0,1) draws are made here, one generator per call as sampler.cpp:47-48
@@ -228,18 +245,14 @@ void orpheus_runner::decode_audio(const std::vector<uint32_t> & out, std::vector
 // and the codec then runs utterance by utterance in order (the noise engine is never reseeded: the draws follow the order of sequential calls).
 void orpheus_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs, const generation_configuration & config) {
     const uint32_t n = (uint32_t) sentences.size();
-    const bool dev_sample = config.sample && !getenv("TTS_HOST_LOOP") && config.top_p > 0.0f && config.top_k >= 1 && config.top_k <= 64 && (uint32_t) config.top_k < hp.vocab_size;
+    const bool dev_sample = device_sampler(config);
     if (n <= 1 || max_seqs <= 1 || (config.sample && !dev_sample)) { tts_generation_runner::generate_batch(sentences, outputs, config); return; }
     if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
-    if (!config.voice.empty() && std::find(orpheus_voices.begin(), orpheus_voices.end(), config.voice) == orpheus_voices.end())
-        TTS_ABORT("Voice '%s' is not a valid voice for Orpheus.\n", config.voice.c_str());
     std::vector<uint32_t> prompts, lens(n);
     for (uint32_t u = 0; u < n; u++) {
-        const std::vector<uint32_t> p = batch_from_sentence(sentences[u], config.voice);
-        if (p.size() > hp.max_context_length) TTS_ABORT("The prompt was too large for the default context window. Try splitting up or shortenning the prompt.\n");
+        const std::vector<uint32_t> p = checked_prompt(sentences[u], config);
         lens[u] = (uint32_t) p.size();
         prompts.insert(prompts.end(), p.begin(), p.end());
-        if (u + 1 == n) last_prompt_tokens = p;
     }
     const uint32_t M = hp.max_generation_size;
     std::vector<uint32_t> toks((size_t) n * M), cnt(n);
@@ -248,9 +261,7 @@ void orpheus_runner::generate_batch(const std::vector<std::string> & sentences, 
     if (dev_sample) {
         uni.resize((size_t) n * M);
         for (uint32_t u = 0; u < n; u++) {   // generate() per utterance: same parameters, n_calls = 0, reset, then one draw per sampler call
-            smp.temperature = config.temperature; smp.repetition_penalty = config.repetition_penalty; smp.do_sample = true;
-            smp.top_k = (uint32_t) config.top_k; smp.top_p = config.top_p; smp.seed = config.seed; smp.n_calls = 0;
-            smp.reset();
+            sampler_setup(config);
             for (uint32_t k = 0; k < M; k++) smp.draw_uniforms(&uni[(size_t) u * M + k]);
         }
     }
@@ -265,5 +276,208 @@ void orpheus_runner::generate_batch(const std::vector<std::string> & sentences, 
         outputs[u].data = batch_store_[u].empty() ? nullptr : batch_store_[u].data();
         outputs[u].n_outputs = batch_store_[u].size();
     }
+    last_output_tokens = last_batch_tokens[n - 1];
+}
+
+// ---- chunked audio -------------------------------------------------------------------------------------------------------------------
+// The windows the ids known now make ready: per utterance the whole chunks [next, f1) whose halo is complete (everything left once the utterance
+// has ended), as one window [next - h, f1 + h) clipped to the utterance.  Trailing ids that do not fill a group of 7 are dropped, as
+// prepare_output_tokens does.  Returns whether there is a window.
+bool orpheus_runner::chunk_collect(std::vector<chunk_state> & st, uint32_t chunk_frames, chunk_pass & P) {
+    P = chunk_pass{};
+    const uint32_t h = (uint32_t) snac_halo;
+    const bool with_noise = !getenv("TTS_SNAC_NO_NOISE");
+    std::vector<size_t> per_layer(hp.snac_layers);   // normals per frame and layer
+    size_t per_frame = 0;
+    { size_t up = 1; for (uint32_t l = 0; l < hp.snac_layers; l++) { up *= hp.snac_stride[l]; per_layer[l] = 4 * up; per_frame += 4 * up; } }
+    for (uint32_t u = 0; u < st.size(); u++) {
+        chunk_state & s = st[u];
+        const uint32_t F = (uint32_t) (s.ids.size() / 7);
+        uint32_t f1;
+        if (s.ended) f1 = F;
+        else {
+            const uint32_t avail = F > h ? F - h : 0;   // frames whose halo is complete
+            f1 = avail > s.next ? s.next + (avail - s.next) / chunk_frames * chunk_frames : s.next;
+        }
+        if (f1 <= s.next) continue;
+        const uint32_t w0 = s.next > h ? s.next - h : 0, w1 = std::min(F, f1 + h);
+        const std::vector<uint32_t> part(s.ids.begin() + (size_t) 7 * w0, s.ids.begin() + (size_t) 7 * w1);
+        for (auto & l : prepare_output_tokens(part)) P.codes.insert(P.codes.end(), l.begin(), l.end());
+        P.utt.push_back(u); P.frames.push_back(w1 - w0); P.keep0.push_back(s.next - w0); P.keep1.push_back(f1 - w0);
+        if (with_noise) {
+            while (s.noise0 + s.noise.size() < w1) {   // frames enter in increasing order, each drawn once
+                s.noise.emplace_back(per_frame);
+                for (auto & v : s.noise.back()) v = noise_dist(noise_engine);
+            }
+            size_t off = 0;
+            for (uint32_t l = 0; l < hp.snac_layers; l++) {   // the window's noise, layer-major
+                for (uint32_t f = w0; f < w1; f++) {
+                    const float * src = s.noise[f - s.noise0].data() + off;
+                    P.noise.insert(P.noise.end(), src, src + per_layer[l]);
+                }
+                off += per_layer[l];
+            }
+            const uint32_t keep_from = f1 > h ? f1 - h : 0;   // the next window starts here
+            if (keep_from > s.noise0) { s.noise.erase(s.noise.begin(), s.noise.begin() + (keep_from - s.noise0)); s.noise0 = keep_from; }
+        }
+        s.next = f1;
+    }
+    return !P.utt.empty();
+}
+
+static size_t chunk_samples(const std::vector<uint32_t> & keep0, const std::vector<uint32_t> & keep1, uint32_t up) {
+    size_t k = 0;
+    for (size_t i = 0; i < keep0.size(); i++) k += keep1[i] - keep0[i];
+    return std::max<size_t>(1, k * 4 * up);
+}
+
+// the pass' PCM (this->pcm) to the callback, chunk_frames at a time; false once the callback asks to stop
+bool orpheus_runner::chunk_deliver(const chunk_pass & P, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    const size_t per = (size_t) 4 * hp.snac_up;
+    size_t off = 0;
+    for (size_t i = 0; i < P.utt.size(); i++) {
+        uint32_t left = P.keep1[i] - P.keep0[i];
+        while (left) {
+            const uint32_t k = std::min(left, chunk_frames);
+            if (!on_chunk(P.utt[i], pcm.data() + off, k * per)) return false;
+            off += k * per;
+            left -= k;
+        }
+    }
+    return true;
+}
+
+// the look-in loop over a generation that tts_hip_orpheus_gen_begin has started.  One sequence: launch the next piece of decoder steps (the call
+// returns while they run), decode the windows the previous look-in made ready on the codec's stream, call back, then look at the piece's ids.
+// A lock-step launch returns only after its steps ran, so there the ready windows are decoded and handed out first: hiding a codec pass of a few
+// ms behind a piece of blocking steps would hold every chunk back by that piece (15 ms at chunk_frames 1, 120 ms at 16 for 8 rows of Orpheus-3B).
+void orpheus_runner::chunk_run(std::vector<chunk_state> & st, bool lockstep, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    const uint32_t n = (uint32_t) st.size(), M = hp.max_generation_size;
+    const uint32_t piece = 7 * std::min<uint32_t>(chunk_frames, 8);   // decoder steps per look-in: one chunk's ids, at most 8 frames'
+    std::vector<uint32_t> toks((size_t) n * M), cnt(n, 0);
+    std::vector<uint8_t> done(n, 0);
+    auto look = [&]() {
+        hip_check(tts_hip_orpheus_gen_wait(lm, toks.data(), cnt.data(), done.data()), "tts_hip_orpheus_gen_wait");
+        for (uint32_t u = 0; u < n; u++) {
+            st[u].ids.assign(toks.begin() + (size_t) u * M, toks.begin() + (size_t) u * M + cnt[u]);
+            st[u].ended = done[u] != 0;
+        }
+    };
+    look();
+    chunk_pass P;
+    bool go_on = true;
+    bool in_flight = false;   // a launch no look() has followed yet
+    try {
+    while (go_on) {
+        bool all_done = true;
+        for (auto & s : st) all_done = all_done && s.ended;
+        const bool have = chunk_collect(st, chunk_frames, P);
+        if (all_done && !have) break;
+        const bool launch = !all_done;
+        if (launch && !lockstep) { hip_check(tts_hip_orpheus_gen_launch(lm, piece), "tts_hip_orpheus_gen_launch"); in_flight = true; }
+        if (have) {
+            pcm.resize(chunk_samples(P.keep0, P.keep1, hp.snac_up));
+            hip_check(tts_hip_snac_decode_windows_begin(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), (uint32_t) P.utt.size(),
+                                                        P.noise.empty() ? nullptr : P.noise.data(), pcm.data()), "tts_hip_snac_decode_windows");
+            hip_check(tts_hip_snac_decode_windows_end(snac), "tts_hip_snac_decode_windows");
+            go_on = chunk_deliver(P, chunk_frames, on_chunk);
+        }
+        if (launch && lockstep && go_on) hip_check(tts_hip_orpheus_gen_launch(lm, piece), "tts_hip_orpheus_gen_launch");
+        if (launch) { in_flight = false; look(); }
+    }
+    } catch (...) {
+        // an error (the codec refusing an id) or a throwing callback: the steps under way are waited for, so the decoder context stays usable
+        if (in_flight) (void) tts_hip_orpheus_gen_wait(lm, toks.data(), cnt.data(), done.data());
+        throw;
+    }
+}
+
+void orpheus_runner::generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                                      const std::function<bool(const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_chunked: chunk_frames must be >= 1\n");
+    if (snac_halo < 0) { tts_generation_runner::generate_chunked(sentence, config, chunk_frames, on_chunk); return; }
+    const std::vector<uint32_t> prompt = checked_prompt(sentence, config);
+    sampler_setup(config);
+    const uint32_t M = hp.max_generation_size, n_prompt = (uint32_t) prompt.size();
+    std::vector<chunk_state> st(1);
+    const auto cb = [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); };
+    const bool dev_sample = device_sampler(config);
+    if (!config.sample || dev_sample) {
+        std::vector<float> u;
+        tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+        if (dev_sample) {
+            u.resize(M);
+            for (auto & v : u) smp.draw_uniforms(&v);
+        }
+        hip_check(tts_hip_orpheus_gen_begin(lm, 1, prompt.data(), &n_prompt, M, hp.stopping_token_id, dev_sample ? &sp : nullptr, dev_sample ? u.data() : nullptr),
+                  "tts_hip_orpheus_gen_begin");
+        chunk_run(st, false, chunk_frames, cb);
+    } else {
+        // the host sampler: logits come back at every step, so the windows are decoded between two steps (no overlap)
+        const uint32_t piece = 7 * std::min<uint32_t>(chunk_frames, 8);
+        std::vector<uint32_t> batch = prompt, & out = st[0].ids;
+        uint32_t pos = 0;
+        chunk_pass P;
+        bool go_on = true;
+        while (go_on) {
+            st[0].ended = !((out.empty() || out.back() != hp.stopping_token_id) && out.size() < M);
+            if (st[0].ended || out.size() % piece == 0) {
+                if (chunk_collect(st, chunk_frames, P)) {
+                    pcm.resize(chunk_samples(P.keep0, P.keep1, hp.snac_up));
+                    hip_check(tts_hip_snac_decode_windows(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), 1, P.noise.empty() ? nullptr : P.noise.data(), pcm.data()),
+                              "tts_hip_snac_decode_windows");
+                    go_on = chunk_deliver(P, chunk_frames, cb);
+                }
+            }
+            if (st[0].ended || !go_on) break;
+            hip_check(tts_hip_orpheus_decode(lm, batch.data(), (uint32_t) batch.size(), pos, logits.data(), nullptr), "tts_hip_orpheus_decode");
+            pos += (uint32_t) batch.size();
+            smp.sample(logits.data(), out);
+            batch.assign(1, out.back());
+        }
+    }
+    last_output_tokens = st[0].ids;
+    if (last_output_tokens.size() >= M)
+        fprintf(stdout, "Warning: generation hit its max default length. The generated audio may not contain the entire prompt.\n");
+}
+
+void orpheus_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                            const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_batch_chunked: chunk_frames must be >= 1\n");
+    const uint32_t n = (uint32_t) sentences.size();
+    const bool dev_sample = device_sampler(config);
+    if (snac_halo < 0) { tts_generation_runner::generate_batch_chunked(sentences, config, chunk_frames, on_chunk); return; }
+    if (n <= 1 || max_seqs <= 1 || (config.sample && !dev_sample)) {   // as generate_batch: one utterance after the other, each one streaming
+        last_batch_tokens.assign(n, {});
+        bool go_on = true;
+        for (uint32_t u = 0; u < n && go_on; u++) {
+            generate_chunked(sentences[u].c_str(), config, chunk_frames, [&](const float * p, size_t k) { return go_on = on_chunk(u, p, k); });
+            last_batch_tokens[u] = last_output_tokens;
+        }
+        return;
+    }
+    if (n > max_seqs) TTS_ABORT("generate_batch_chunked: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
+    std::vector<uint32_t> prompts, lens(n);
+    for (uint32_t u = 0; u < n; u++) {
+        const std::vector<uint32_t> p = checked_prompt(sentences[u], config);
+        lens[u] = (uint32_t) p.size();
+        prompts.insert(prompts.end(), p.begin(), p.end());
+    }
+    const uint32_t M = hp.max_generation_size;
+    std::vector<float> uni;
+    tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+    if (dev_sample) {
+        uni.resize((size_t) n * M);
+        for (uint32_t u = 0; u < n; u++) {   // generate() per utterance: same parameters, n_calls = 0, reset, then one draw per sampler call
+            sampler_setup(config);
+            for (uint32_t k = 0; k < M; k++) smp.draw_uniforms(&uni[(size_t) u * M + k]);
+        }
+    }
+    hip_check(tts_hip_orpheus_gen_begin(lm, n, prompts.data(), lens.data(), M, hp.stopping_token_id, dev_sample ? &sp : nullptr, dev_sample ? uni.data() : nullptr),
+              "tts_hip_orpheus_gen_begin");
+    std::vector<chunk_state> st(n);
+    chunk_run(st, true, chunk_frames, on_chunk);
+    last_batch_tokens.assign(n, {});
+    for (uint32_t u = 0; u < n; u++) last_batch_tokens[u] = st[u].ids;
     last_output_tokens = last_batch_tokens[n - 1];
 }

@@ -6,6 +6,7 @@
 // The ggml graphs inside decode() and snac_runner::run() are replaced by tts_hip_orpheus_* / tts_hip_snac_*.
 #pragma once
 #include <array>
+#include <functional>
 #include <memory>
 #include <random>
 #include <string>
@@ -49,6 +50,15 @@ struct orpheus_runner final : tts_generation_runner {
     // extension: lock-step utterances (tts_hip_orpheus_generate_batch): every utterance's audio is that of a generate() call of its own, made in order
     void     generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs, const generation_configuration & config) override;
     uint32_t batch_capacity() const override { return max_seqs; }
+    // extension: chunked audio.  chunk_frames counts SNAC frames (7 ids, 4 * snac_up samples).  The decoder runs in pieces
+    // (tts_hip_orpheus_gen_*); a chunk [f0, f1) is decoded once frames up to f1 + snac_halo exist or the utterance has ended, as the window
+    // [f0 - halo, f1 + halo) on the codec's stream (tts_hip_snac_decode_windows_begin / _end) while the next piece of steps runs (one sequence;
+    // a lock-step batch decodes and hands out its ready windows before the next piece, whose launch blocks).
+    // The noise block: see chunk_state below.
+    void     generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                              const std::function<bool(const float *, size_t)> & on_chunk) override;
+    void     generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) override;
     std::vector<std::string_view> list_voices() override;
 
     void decode_audio(const std::vector<uint32_t> & output_tokens, std::vector<float> & audio);   // prepare_output_tokens + SNAC
@@ -67,4 +77,28 @@ struct orpheus_runner final : tts_generation_runner {
     std::vector<float>             pcm, logits;
     std::default_random_engine     noise_engine;     // random_normal_gen's engine (util.cpp:74-80): default seed, never reseeded
     std::normal_distribution<float> noise_dist{0.0f, 1.0f};
+    int                            snac_halo = -1;   // tts_hip_snac_halo_frames of the codec layout (-1: unknown; chunked audio then decodes whole utterances)
+
+  private:
+    // One utterance of a chunked generation.  generate() draws the SNAC noise layer-major over the whole utterance, so where layer 1's noise starts
+    // depends on the final length, which is unknown while streaming.  Chunked generation draws frame-major from the same engine instead: frames in
+    // increasing order, each once, when it first enters a window (kept or halo), and kept until no later window needs it; per frame, for layer
+    // l = 0.., 4 * prod(stride_0..l) normals.  A completed call consumes exactly the draws generate() would.
+    struct chunk_state {
+        std::vector<uint32_t> ids;                 // the ids so far
+        bool                  ended = false;
+        uint32_t              next = 0;            // first frame not handed out yet
+        uint32_t              noise0 = 0;          // frame of noise.front()
+        std::vector<std::vector<float>> noise;     // frames [noise0, noise0 + size)
+    };
+    struct chunk_pass {                            // the windows of one look-in: one tts_hip_snac_decode_windows pass
+        std::vector<uint32_t> utt, codes, frames, keep0, keep1;
+        std::vector<float>    noise;
+    };
+    bool device_sampler(const generation_configuration & config) const;
+    void sampler_setup(const generation_configuration & config);
+    std::vector<uint32_t> checked_prompt(const std::string & sentence, const generation_configuration & config);
+    bool chunk_collect(std::vector<chunk_state> & st, uint32_t chunk_frames, chunk_pass & P);
+    bool chunk_deliver(const chunk_pass & P, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
+    void chunk_run(std::vector<chunk_state> & st, bool lockstep, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
 };
