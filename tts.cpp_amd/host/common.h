@@ -185,3 +185,9 @@ uint32_t tts_load_max_seqs();
 [[noreturn]] void tts_abort(const char * file, int line, const char * fmt, ...);
 #define TTS_ABORT(...) tts_abort(__FILE__, __LINE__, __VA_ARGS__)
 #define TTS_ASSERT(x) do { if (!(x)) TTS_ABORT("TTS_ASSERT(%s) failed\n", #x); } while (0)
+
+// a call into the C ABI (include/tts_hip.h) that must not fail: non-zero aborts with the shim's message
+extern "C" const char * tts_hip_last_error(void);
+inline void hip_check(int rc, const char * what) {
+    if (rc != 0) TTS_ABORT("%s failed: %s\n", what, tts_hip_last_error());
+}

@@ -5,10 +5,6 @@
 
 #include "gguf.h"
 
-static void hip_check(int rc, const char * what) {
-    if (rc != 0) TTS_ABORT("%s failed: %s\n", what, tts_hip_last_error());
-}
-
 dia_model_loader::dia_model_loader() : tts_model_loader{"dia"} {}
 const dia_model_loader dia_loader{};
 void dia_register() {}

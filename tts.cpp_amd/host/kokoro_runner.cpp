@@ -12,10 +12,6 @@
 
 #include "gguf.h"
 
-static void hip_check(int rc, const char * what) {
-    if (rc != 0) TTS_ABORT("%s failed: %s\n", what, tts_hip_last_error());
-}
-
 kokoro_model_loader::kokoro_model_loader() : tts_model_loader{"kokoro"} {}
 const kokoro_model_loader kokoro_loader{};
 void kokoro_register() {}

@@ -6,10 +6,6 @@
 
 #include "gguf.h"
 
-static void hip_check(int rc, const char * what) {
-    if (rc != 0) TTS_ABORT("%s failed: %s\n", what, tts_hip_last_error());
-}
-
 // model.cpp:7: the voices are not in the model configuration
 static constexpr std::array<const char *, 7> orpheus_voices{"zoe", "zac", "jess", "leo", "mia", "julia", "leah"};
 
@@ -173,6 +169,23 @@ std::vector<uint32_t> orpheus_runner::checked_prompt(const std::string & sentenc
     return prompt;
 }
 
+// a lock-step batch's inputs: the checked prompts concatenated, their lengths and, for the device sampler, the uniforms [utterance][step]
+void orpheus_runner::batch_inputs(const std::vector<std::string> & sentences, const generation_configuration & config, bool dev_sample,
+                                  std::vector<uint32_t> & prompts, std::vector<uint32_t> & lens, std::vector<float> & uni) {
+    const uint32_t n = (uint32_t) sentences.size(), M = hp.max_generation_size;
+    for (uint32_t u = 0; u < n; u++) {
+        const std::vector<uint32_t> p = checked_prompt(sentences[u], config);
+        lens.push_back((uint32_t) p.size());
+        prompts.insert(prompts.end(), p.begin(), p.end());
+    }
+    if (!dev_sample) return;
+    uni.resize((size_t) n * M);
+    for (uint32_t u = 0; u < n; u++) {   // generate() per utterance: same parameters, n_calls = 0, reset, then one draw per sampler call
+        sampler_setup(config);
+        for (uint32_t k = 0; k < M; k++) smp.draw_uniforms(&uni[(size_t) u * M + k]);
+    }
+}
+
 void orpheus_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
     const std::vector<uint32_t> prompt = checked_prompt(sentence, config);
     sampler_setup(config);
@@ -248,23 +261,12 @@ void orpheus_runner::generate_batch(const std::vector<std::string> & sentences, 
     const bool dev_sample = device_sampler(config);
     if (n <= 1 || max_seqs <= 1 || (config.sample && !dev_sample)) { tts_generation_runner::generate_batch(sentences, outputs, config); return; }
     if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
-    std::vector<uint32_t> prompts, lens(n);
-    for (uint32_t u = 0; u < n; u++) {
-        const std::vector<uint32_t> p = checked_prompt(sentences[u], config);
-        lens[u] = (uint32_t) p.size();
-        prompts.insert(prompts.end(), p.begin(), p.end());
-    }
+    std::vector<uint32_t> prompts, lens;
+    std::vector<float> uni;
+    batch_inputs(sentences, config, dev_sample, prompts, lens, uni);
     const uint32_t M = hp.max_generation_size;
     std::vector<uint32_t> toks((size_t) n * M), cnt(n);
-    std::vector<float> uni;
     tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-    if (dev_sample) {
-        uni.resize((size_t) n * M);
-        for (uint32_t u = 0; u < n; u++) {   // generate() per utterance: same parameters, n_calls = 0, reset, then one draw per sampler call
-            sampler_setup(config);
-            for (uint32_t k = 0; k < M; k++) smp.draw_uniforms(&uni[(size_t) u * M + k]);
-        }
-    }
     hip_check(tts_hip_orpheus_generate_batch(lm, n, prompts.data(), lens.data(), M, hp.stopping_token_id, dev_sample ? &sp : nullptr, dev_sample ? uni.data() : nullptr, toks.data(),
                                              cnt.data()), "tts_hip_orpheus_generate_batch");
     outputs.assign(n, tts_response{});
@@ -457,22 +459,11 @@ void orpheus_runner::generate_batch_chunked(const std::vector<std::string> & sen
         return;
     }
     if (n > max_seqs) TTS_ABORT("generate_batch_chunked: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
-    std::vector<uint32_t> prompts, lens(n);
-    for (uint32_t u = 0; u < n; u++) {
-        const std::vector<uint32_t> p = checked_prompt(sentences[u], config);
-        lens[u] = (uint32_t) p.size();
-        prompts.insert(prompts.end(), p.begin(), p.end());
-    }
-    const uint32_t M = hp.max_generation_size;
+    std::vector<uint32_t> prompts, lens;
     std::vector<float> uni;
+    batch_inputs(sentences, config, dev_sample, prompts, lens, uni);
+    const uint32_t M = hp.max_generation_size;
     tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-    if (dev_sample) {
-        uni.resize((size_t) n * M);
-        for (uint32_t u = 0; u < n; u++) {   // generate() per utterance: same parameters, n_calls = 0, reset, then one draw per sampler call
-            sampler_setup(config);
-            for (uint32_t k = 0; k < M; k++) smp.draw_uniforms(&uni[(size_t) u * M + k]);
-        }
-    }
     hip_check(tts_hip_orpheus_gen_begin(lm, n, prompts.data(), lens.data(), M, hp.stopping_token_id, dev_sample ? &sp : nullptr, dev_sample ? uni.data() : nullptr),
               "tts_hip_orpheus_gen_begin");
     std::vector<chunk_state> st(n);

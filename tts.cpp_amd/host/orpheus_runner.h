@@ -98,6 +98,8 @@ struct orpheus_runner final : tts_generation_runner {
     bool device_sampler(const generation_configuration & config) const;
     void sampler_setup(const generation_configuration & config);
     std::vector<uint32_t> checked_prompt(const std::string & sentence, const generation_configuration & config);
+    void batch_inputs(const std::vector<std::string> & sentences, const generation_configuration & config, bool dev_sample,
+                      std::vector<uint32_t> & prompts, std::vector<uint32_t> & lens, std::vector<float> & uni);
     bool chunk_collect(std::vector<chunk_state> & st, uint32_t chunk_frames, chunk_pass & P);
     bool chunk_deliver(const chunk_pass & P, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
     void chunk_run(std::vector<chunk_state> & st, bool lockstep, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);

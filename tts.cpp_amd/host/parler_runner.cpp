@@ -6,10 +6,6 @@
 
 #include "gguf.h"
 
-static void hip_check(int rc, const char * what) {
-    if (rc != 0) TTS_ABORT("%s failed: %s\n", what, tts_hip_last_error());
-}
-
 parler_model_loader::parler_model_loader() : tts_model_loader{"parler-tts"} {}
 const parler_model_loader parler_loader{};
 void parler_register() {}
@@ -119,7 +115,6 @@ void parler_runner::prepare_post_load() {
         hip_check(tts_hip_arena_filled(ctx), "tts_hip_arena_filled");
     } else
     hip_check(tts_hip_finalize(ctx, nullptr), "tts_hip_finalize");
-    logits.resize((size_t) hp.n_output_heads * hp.output_vocab_size);
     pcm.reserve((size_t) hp.max_generation_size * hp.up_sampling_factor);
 }
 
@@ -187,102 +182,50 @@ void parler_runner::adjust_output_tokens(const std::vector<uint32_t> & toks, std
     parler_undelay(toks.data(), toks.size() / hp.n_output_heads, hp.n_output_heads, hp.audio_vocab_size, 0, true, filtered);
 }
 
-// generate() up to the prefill: the sampler's settings, batch_from_sentence (model.cpp:473-498), the prompt into cache slot 0.
-// false: the prompt leaves no room for generation (the response is empty).
-bool parler_runner::prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt) {
-    smp.temperature = config.temperature;
-    smp.repetition_penalty = config.repetition_penalty;
-    smp.do_sample = config.sample;
-    smp.top_k = (uint32_t) config.top_k;
-    smp.top_p = config.top_p;
-    smp.seed = config.seed;
-    smp.n_calls = 0;
-    if (config.use_cross_attn != use_cross_attn)
-        TTS_ABORT("generate(): use_cross_attn differs from the value the model was loaded with (the reference only "
-                  "loads the encoder_attn tensors when it is set at load time, model.cpp:202-237)\n");
+// the sampler's settings as a generate() call starts it (n_calls = 0: a seeded sampler draws the sequence of a call of its own)
+static void sampler_setup(sampler & s, const generation_configuration & config) {
+    s.temperature = config.temperature;
+    s.repetition_penalty = config.repetition_penalty;
+    s.do_sample = config.sample;
+    s.top_k = (uint32_t) config.top_k;
+    s.top_p = config.top_p;
+    s.seed = config.seed;
+    s.n_calls = 0;
+}
 
-    // batch_from_sentence (model.cpp:473-498)
+// the U[0,1) draws sample() would make in `steps` calls (sampler.cpp:47-50) on one utterance's own sampler, seeded as a generate() call of
+// its own, drawn ahead for a device loop: step s at u + s * stride (stride = rows * heads in the [step][row][head] layout)
+static void draw_row_uniforms(sampler si, uint64_t seed, uint32_t steps, size_t stride, float * u) {
+    si.seed = seed;
+    si.n_calls = 0;
+    for (uint32_t s = 0; s < steps; s++) si.draw_uniforms(u + s * stride);
+}
+
+// batch_from_sentence (model.cpp:473-498): tokenise + EOS.  false: the prompt leaves no room for generation (the response is empty).
+bool parler_runner::tokenize_prompt(const std::string & sentence, std::vector<uint32_t> & prompt) const {
     prompt.clear();
     tokenizer->tokenize(sentence, prompt);
     prompt.push_back(tokenizer->eos_token);
+    return prompt.size() < hp.max_generation_size && prompt.size() < hp.max_ctx_length;
+}
+
+// generate() up to the prefill: the sampler's settings, the prompt into cache slot 0.  false: no room for generation.
+bool parler_runner::prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt) {
+    sampler_setup(smp, config);
+    if (config.use_cross_attn != use_cross_attn)
+        TTS_ABORT("generate(): use_cross_attn differs from the value the model was loaded with (the reference only "
+                  "loads the encoder_attn tensors when it is set at load time, model.cpp:202-237)\n");
+    const bool room = tokenize_prompt(sentence, prompt);
     last_prompt_tokens = prompt;
     last_output_tokens.clear();
     smp.reset();
     hip_check(tts_hip_parler_reset(ctx), "tts_hip_parler_reset");
-    if (prompt.size() >= hp.max_generation_size || prompt.size() >= hp.max_ctx_length) {
+    if (!room) {
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", prompt.size());
         return false;
     }
     hip_check(tts_hip_parler_prefill(ctx, 0, prompt.data(), (uint32_t) prompt.size(), 0), "tts_hip_parler_prefill");
     return true;
-}
-
-void parler_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
-    std::vector<uint32_t> prompt;
-    output.data = nullptr;
-    output.n_outputs = 0;
-    if (!prepare_single(sentence, config, prompt)) return;
-
-    const uint32_t nh = hp.n_output_heads;
-    uint32_t       current_position = (uint32_t) prompt.size();
-    std::vector<uint32_t> & out_tokens = last_output_tokens;
-
-    // the sampler runs on the device (unless a head has more than 2048 logits).  Greedy never sees the repetition
-    // penalty: sampler::max only reads last_token_ids, which stay -1 after reset() (sampler.cpp:71-80,185-204)
-    const bool device_loop = !getenv("TTS_HOST_LOOP") && (!config.sample || hp.output_vocab_size <= 2048);
-    if (device_loop) {
-        // sampler::max / sampler::sample, the delay-pattern feed and the EOS flags run on the device; the host
-        // synchronises in chunks only to learn whether check_stopping() would have fired.
-        const uint32_t max_steps = hp.max_generation_size - current_position;
-        std::vector<uint32_t> toks((size_t) max_steps * nh);
-        uint32_t start = current_position, done = 0;
-        if (config.sample) {
-            // the U[0,1) draws sample() would make, call by call (sampler.cpp:47-50), drawn ahead
-            std::vector<float> u((size_t) max_steps * nh);
-            for (uint32_t s = 0; s < max_steps; s++) smp.draw_uniforms(u.data() + (size_t) s * nh);
-            const tts_hip_sampling sp{smp.top_k, smp.top_p, smp.temperature, smp.repetition_penalty};
-            hip_check(tts_hip_parler_generate_sampled(ctx, 1, &start, max_steps, hp.bos_token_id, hp.eos_token_id, &sp, u.data(), toks.data(), &done),
-                      "tts_hip_parler_generate_sampled");
-        } else
-        hip_check(tts_hip_parler_generate_greedy(ctx, 1, &start, max_steps, hp.bos_token_id, hp.eos_token_id, toks.data(), &done),
-                  "tts_hip_parler_generate_greedy");
-        const uint32_t n = done ? done : max_steps;
-        out_tokens.assign(toks.begin(), toks.begin() + (size_t) n * nh);
-    } else {
-        // generate_from_batch (model.cpp:762-792) with host sampling
-        std::vector<uint32_t> ids(nh, hp.bos_token_id);
-        std::vector<bool>     eos_seen(nh, false);
-        int                   current_step = 0;  // batch.current_step of the decode that just ran
-        for (;;) {
-            // check_stopping (model.cpp:715-732)
-            if (!out_tokens.empty()) {
-                if (current_position >= hp.max_generation_size) break;
-                bool all = true;
-                for (uint32_t i = 0; i < nh; i++) {
-                    eos_seen[i] = eos_seen[i] || out_tokens[out_tokens.size() - nh + i] == hp.eos_token_id;
-                    all = all && eos_seen[i];
-                }
-                if (all) break;
-            } else if (current_position >= hp.max_generation_size) {
-                break;
-            }
-            current_step++;
-            hip_check(tts_hip_parler_step(ctx, 1, ids.data(), &current_position, nullptr, logits.data()), "tts_hip_parler_step");
-            smp.sample(logits.data(), out_tokens);
-            current_position += 1;
-            const uint32_t * last = out_tokens.data() + out_tokens.size() - nh;
-            for (uint32_t i = 0; i < nh; i++)
-                ids[i] = current_step > (int) i ? (eos_seen[i] ? hp.eos_token_id : last[i]) : hp.bos_token_id;
-        }
-    }
-
-    std::vector<uint32_t> filtered;
-    adjust_output_tokens(out_tokens, filtered);
-    const uint32_t frames = (uint32_t) (filtered.size() / nh);
-    pcm.assign((size_t) frames * hp.up_sampling_factor, 0.0f);
-    if (frames) hip_check(tts_hip_dac_decode(ctx, filtered.data(), frames, pcm.data()), "tts_hip_dac_decode");
-    output.data = pcm.data();
-    output.n_outputs = pcm.size();
 }
 
 // generate_batch() up to the prefill: the utterances that have room for generation as rows (row_of: the utterance of a row, start: its prompt
@@ -295,85 +238,160 @@ bool parler_runner::prepare_batch(const std::vector<std::string> & sentences, co
     if (n_all == 0) return false;
     if (n_all > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n_all, max_seqs);
     if (config.use_cross_attn != use_cross_attn) TTS_ABORT("generate_batch: use_cross_attn differs from load time\n");
-    // batch_from_sentence per utterance; an utterance whose prompt leaves no room gets an empty response, exactly as generate() does
-    std::vector<uint32_t> ids, lens;
+    // an utterance whose prompt leaves no room gets an empty response, exactly as generate() does
+    std::vector<uint32_t> ids, p;
     for (uint32_t i = 0; i < n_all; i++) {
-        std::vector<uint32_t> p;
-        tokenizer->tokenize(sentences[i], p);
-        p.push_back(tokenizer->eos_token);
-        if (p.size() >= hp.max_generation_size || p.size() >= hp.max_ctx_length) {
+        if (!tokenize_prompt(sentences[i], p)) {
             fprintf(stderr, "prompt %u of %zu tokens leaves no room for generation\n", i, p.size());
             continue;
         }
         row_of.push_back(i);
-        lens.push_back((uint32_t) p.size());
         start.push_back((uint32_t) p.size());
         ids.insert(ids.end(), p.begin(), p.end());
     }
     const uint32_t n = (uint32_t) row_of.size();
     if (n == 0) return false;
     hip_check(tts_hip_parler_reset(ctx), "tts_hip_parler_reset");
-    hip_check(tts_hip_parler_prefill_batch(ctx, n, nullptr, ids.data(), lens.data(), nullptr), "tts_hip_parler_prefill_batch");
+    hip_check(tts_hip_parler_prefill_batch(ctx, n, nullptr, ids.data(), start.data(), nullptr), "tts_hip_parler_prefill_batch");
     return true;
 }
 
-void parler_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
-                                   const generation_configuration & config) {
-    const uint32_t nh = hp.n_output_heads;
-    outputs.assign(sentences.size(), tts_response{});
-    std::vector<uint32_t> start, row_of;
-    if (!prepare_batch(sentences, config, start, row_of)) return;
-    const uint32_t n = (uint32_t) row_of.size();
-    // every utterance gets the steps generate() would give it alone (max_generation - its own prompt): the loop runs as long as the
-    // shortest prompt needs; the device marks a row finished when its position reaches max_generation and lets it idle there
-    const uint32_t shortest = *std::min_element(start.begin(), start.end());
-    const uint32_t max_steps = hp.max_generation_size - shortest;
-    std::vector<std::vector<uint32_t>> row_tokens(n);
+// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
+// The codec's output for frame j depends on the codes of frames [j - h, j + h] only (tts_hip_dac_halo_frames).  So once frames [e, f + h)
+// of an utterance are final, a window of frames [e - h, f + h) decoded as an utterance of its own yields the samples of frames [e, f)
+// exactly as the whole utterance's decode does (at the utterance's true edges the window is clipped and sees the same zero padding).
+// run_rows calls the hook at its look-ins: plan() un-delays the frames that became final and cuts the next windows, emit() decodes them
+// (one codec pass for every utterance, on the codec's stream while the device loop's next steps run) and hands the chunks out.
+static constexpr uint32_t LOOK_IN = 32;   // decode steps between two look-ins: the device compacts its rows at multiples of 32 steps
 
-    if (!getenv("TTS_HOST_LOOP") && (!config.sample || hp.output_vocab_size <= 2048)) {
-        std::vector<uint32_t> toks((size_t) max_steps * n * nh), done(n);
-        if (config.sample) {
-            // one sampler state per utterance, seeded like the host loop below: uniforms [step][utterance][head]
-            std::vector<float> u((size_t) max_steps * n * nh);
+struct parler_runner::chunker {
+    struct row {
+        std::vector<uint32_t> frames;     // codes of the kept frames that are final [frames][heads]
+        size_t   judged = 0;              // frames whose keep / drop is decided (parler_undelay's `next`)
+        uint32_t emitted = 0;             // kept frames handed out
+    };
+    parler_runner & r;
+    const uint32_t  chunk_frames;
+    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk;
+    std::vector<row>      rows;
+    std::vector<uint32_t> codes, frames, keep0, keep1, row_of;   // the planned windows: one tts_hip_dac_decode_windows pass
+    chunker(parler_runner & runner, uint32_t chunk_frames_, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk_)
+        : r(runner), chunk_frames(chunk_frames_), on_chunk(on_chunk_) {}
+
+    // the frames of each row that became final since the last call, then a window per row that has chunks ready: whole chunks whose
+    // right halo is final too, or everything left once the row is finished
+    void plan(const std::vector<std::vector<uint32_t>> & toks, const std::vector<bool> & finished) {
+        const uint32_t nh = r.hp.n_output_heads;
+        const uint32_t h = r.dac_halo >= 0 ? (uint32_t) r.dac_halo : r.hp.max_generation_size;   // unknown halo: whole utterances once they are done
+        rows.resize(toks.size());
+        for (uint32_t i = 0; i < toks.size(); i++) {
+            row & w = rows[i];
+            w.judged = parler_undelay(toks[i].data(), toks[i].size() / nh, nh, r.hp.audio_vocab_size, w.judged, finished[i], w.frames);
+            const uint32_t have = (uint32_t) (w.frames.size() / nh);
+            uint32_t end = w.emitted;
+            if (finished[i]) end = have;
+            else if (have >= w.emitted + h + chunk_frames) end = w.emitted + (have - h - w.emitted) / chunk_frames * chunk_frames;
+            if (end == w.emitted) continue;
+            const uint32_t w0 = w.emitted > h ? w.emitted - h : 0, w1 = std::min(end + h, have);
+            codes.insert(codes.end(), w.frames.begin() + (size_t) w0 * nh, w.frames.begin() + (size_t) w1 * nh);
+            frames.push_back(w1 - w0);
+            keep0.push_back(w.emitted - w0);
+            keep1.push_back(end - w0);
+            row_of.push_back(i);
+            w.emitted = end;
+        }
+    }
+    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
+    bool emit() {
+        if (row_of.empty()) return true;
+        const uint32_t U = r.hp.up_sampling_factor;
+        size_t total = 0;
+        for (size_t w = 0; w < row_of.size(); w++) total += (size_t) (keep1[w] - keep0[w]) * U;
+        r.pcm.resize(total);
+        hip_check(tts_hip_dac_decode_windows(r.ctx, codes.data(), frames.data(), keep0.data(), keep1.data(), (uint32_t) row_of.size(), r.pcm.data()),
+                  "tts_hip_dac_decode_windows");
+        bool more = true;
+        size_t off = 0;
+        for (size_t w = 0; w < row_of.size() && more; w++) {
+            const uint32_t nf = keep1[w] - keep0[w];
+            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
+                more = on_chunk(row_of[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
+            off += (size_t) nf * U;
+        }
+        codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear();
+        return more;
+    }
+};
+
+// generate_from_batch (model.cpp:762-792) over n prefilled rows (row i starts at position start[i]) -> the still-delayed tokens of each row.
+// Every row gets the steps generate() would give it alone (max_generation - its own prompt) and its own sampler, seeded as a generate() call
+// of its own; the loop runs as long as the shortest prompt needs.  With a hook, the look-ins every 32 steps hand out chunked audio.
+std::vector<std::vector<uint32_t>> parler_runner::run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook) {
+    const uint32_t n = (uint32_t) start.size(), nh = hp.n_output_heads, V = hp.output_vocab_size;
+    const uint32_t max_steps = hp.max_generation_size - *std::min_element(start.begin(), start.end());
+    std::vector<std::vector<uint32_t>> toks(n);
+    std::vector<bool> finished(n, false);
+    bool go = true;   // false: the hook's caller stopped the generation
+
+    // the sampler runs on the device (unless a head has more than 2048 logits).  Greedy never sees the repetition
+    // penalty: sampler::max only reads last_token_ids, which stay -1 after reset() (sampler.cpp:71-80,185-204)
+    if (!getenv("TTS_HOST_LOOP") && (!config.sample || V <= 2048)) {
+        // sampler::max / sampler::sample, the delay-pattern feed and the EOS flags run on the device; the host looks in every 32 steps to
+        // learn whether check_stopping() has fired, and fetches the tokens once at the end (with a hook: the new steps' at every look-in)
+        std::vector<float> u;
+        const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+        if (config.sample) {   // uniforms [step][row][head]
+            u.resize((size_t) max_steps * n * nh);
+            for (uint32_t i = 0; i < n; i++) draw_row_uniforms(smp, config.seed, max_steps, (size_t) n * nh, u.data() + (size_t) i * nh);
+        }
+        hip_check(tts_hip_parler_gen_begin(ctx, n, start.data(), max_steps, hp.bos_token_id, hp.eos_token_id, config.sample ? &sp : nullptr,
+                                           config.sample ? u.data() : nullptr), "tts_hip_parler_gen_begin");
+        std::vector<uint32_t> buf((size_t) max_steps * n * nh), done(n);
+        uint32_t ran = 0;
+        // check_stopping per row: EOS on every head (done), or position == max_generation
+        auto cap = [&](uint32_t i) { return std::min(done[i] ? done[i] : max_steps, hp.max_generation_size - start[i]); };
+        auto collect = [&]() {   // the steps of buf [step][row][head] that the rows do not hold yet
+            for (uint32_t i = 0; i < n; i++)
+                for (uint32_t s = (uint32_t) (toks[i].size() / nh), e = std::min(ran, cap(i)); s < e; s++)
+                    toks[i].insert(toks[i].end(), buf.begin() + ((size_t) s * n + i) * nh, buf.begin() + ((size_t) s * n + i + 1) * nh);
+        };
+        hip_check(tts_hip_parler_gen_launch(ctx, LOOK_IN), "tts_hip_parler_gen_launch");
+        for (;;) {
+            if (hook) go = hook->emit();   // the codec windows of the last look-in, while the steps run
+            hip_check(tts_hip_parler_gen_wait(ctx, hook ? buf.data() : nullptr, done.data(), &ran), "tts_hip_parler_gen_wait");
+            bool all = true;
             for (uint32_t i = 0; i < n; i++) {
-                sampler si = smp;
-                si.seed = config.seed; si.n_calls = 0;   // n separate generate() calls would each seed with config.seed
-                for (uint32_t s = 0; s < max_steps; s++) si.draw_uniforms(u.data() + ((size_t) s * n + i) * nh);
+                finished[i] = ran >= cap(i);
+                all = all && finished[i];
             }
-            const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-            hip_check(tts_hip_parler_generate_sampled(ctx, n, start.data(), max_steps, hp.bos_token_id, hp.eos_token_id, &sp, u.data(), toks.data(), done.data()),
-                      "tts_hip_parler_generate_sampled");
-        } else
-        hip_check(tts_hip_parler_generate_greedy(ctx, n, start.data(), max_steps, hp.bos_token_id, hp.eos_token_id, toks.data(), done.data()),
-                  "tts_hip_parler_generate_greedy");
-        for (uint32_t i = 0; i < n; i++) {
-            // check_stopping per sequence: EOS on every head, or position == max_generation
-            uint32_t steps = done[i] ? done[i] : max_steps;
-            steps = std::min(steps, hp.max_generation_size - start[i]);
-            for (uint32_t s = 0; s < steps; s++)
-                row_tokens[i].insert(row_tokens[i].end(), toks.begin() + ((size_t) s * n + i) * nh, toks.begin() + ((size_t) s * n + i + 1) * nh);
+            if (hook) collect();
+            if (all || !go) break;
+            hip_check(tts_hip_parler_gen_launch(ctx, LOOK_IN), "tts_hip_parler_gen_launch");
+            if (hook) hook->plan(toks, finished);
+        }
+        if (!hook) {   // one copy of all the tokens
+            hip_check(tts_hip_parler_gen_wait(ctx, buf.data(), done.data(), &ran), "tts_hip_parler_gen_wait");
+            collect();
         }
     } else {
-        // host sampling, one sampler state per utterance; finished sequences keep stepping on EOS inputs (their
-        // tokens are no longer recorded) until all are done
+        // host sampling, one sampler state per row; finished rows keep stepping on EOS inputs (their tokens are no longer recorded) until
+        // all are done.  A hook's windows are planned and decoded at the same look-in points, without overlap.
         std::vector<sampler> smps(n, smp);
-        for (uint32_t i = 0; i < n; i++) {
-            smps[i].temperature = config.temperature; smps[i].repetition_penalty = config.repetition_penalty;
-            smps[i].do_sample = config.sample; smps[i].top_k = (uint32_t) config.top_k; smps[i].top_p = config.top_p;
-            smps[i].seed = config.seed; smps[i].n_calls = 0;
-            smps[i].reset();
+        for (sampler & s : smps) {
+            sampler_setup(s, config);
+            s.reset();
         }
         std::vector<uint32_t> in_ids((size_t) n * nh, hp.bos_token_id), pos(start);
         std::vector<std::vector<bool>> eos_seen(n, std::vector<bool>(nh, false));
-        std::vector<bool> finished(n, false);
-        std::vector<float> lg((size_t) n * nh * hp.output_vocab_size);
-        for (uint32_t step = 1; step <= max_steps; step++) {
+        std::vector<float> lg((size_t) n * nh * V);
+        for (uint32_t step = 1; step <= max_steps && go; step++) {
             bool all_done = true;
             for (uint32_t i = 0; i < n; i++) {
+                // check_stopping (model.cpp:715-732)
                 if (finished[i]) continue;
-                auto & t = row_tokens[i];
+                auto & t = toks[i];
                 if (!t.empty()) {
-                    if (pos[i] >= hp.max_generation_size) { finished[i] = true; continue; }
+                    if (start[i] + t.size() / nh >= hp.max_generation_size) { finished[i] = true; continue; }
                     bool all = true;
                     for (uint32_t h = 0; h < nh; h++) {
                         eos_seen[i][h] = eos_seen[i][h] || t[t.size() - nh + h] == hp.eos_token_id;
@@ -388,192 +406,69 @@ void parler_runner::generate_batch(const std::vector<std::string> & sentences, s
             for (uint32_t i = 0; i < n; i++) {
                 if (pos[i] + 1 < hp.max_generation_size) pos[i] += 1;  // finished rows idle on their last position
                 if (finished[i]) continue;
-                auto & t = row_tokens[i];
-                smps[i].sample(lg.data() + (size_t) i * nh * hp.output_vocab_size, t);
+                auto & t = toks[i];
+                smps[i].sample(lg.data() + (size_t) i * nh * V, t);
                 const uint32_t * last = t.data() + t.size() - nh;
                 for (uint32_t h = 0; h < nh; h++)
                     in_ids[(size_t) i * nh + h] = step > h ? (eos_seen[i][h] ? hp.eos_token_id : last[h]) : hp.bos_token_id;
             }
+            if (hook && step % LOOK_IN == 0) {
+                hook->plan(toks, finished);
+                go = hook->emit();
+            }
         }
     }
-
-    std::vector<uint32_t> codes, frames(n);
-    for (uint32_t i = 0; i < n; i++) {
-        std::vector<uint32_t> f;
-        adjust_output_tokens(row_tokens[i], f);
-        frames[i] = (uint32_t) (f.size() / nh);
-        codes.insert(codes.end(), f.begin(), f.end());
-        last_batch_tokens[row_of[i]] = std::move(row_tokens[i]);
+    if (hook && go) {   // what is left once every row is done
+        finished.assign(n, true);
+        hook->plan(toks, finished);
+        (void) hook->emit();
     }
+    return toks;
+}
+
+// un-delayed codes of frames.size() utterances, concatenated, through the codec in one pass: the audio of each, pointing into `pcm`
+std::vector<tts_response> parler_runner::decode_frames(const std::vector<uint32_t> & codes, const std::vector<uint32_t> & frames) {
     size_t total = 0;
     for (uint32_t f : frames) total += (size_t) f * hp.up_sampling_factor;
     pcm.assign(total, 0.0f);
-    if (total) hip_check(tts_hip_dac_decode_batch(ctx, codes.data(), frames.data(), n, pcm.data()), "tts_hip_dac_decode_batch");
+    if (total) hip_check(tts_hip_dac_decode_batch(ctx, codes.data(), frames.data(), (uint32_t) frames.size(), pcm.data()), "tts_hip_dac_decode_batch");
+    std::vector<tts_response> audio(frames.size());
     size_t off = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        outputs[row_of[i]].data = pcm.data() + off;
-        outputs[row_of[i]].n_outputs = (size_t) frames[i] * hp.up_sampling_factor;
-        off += outputs[row_of[i]].n_outputs;
+    for (size_t i = 0; i < frames.size(); i++) {
+        audio[i].data = pcm.data() + off;
+        audio[i].n_outputs = (size_t) frames[i] * hp.up_sampling_factor;
+        off += audio[i].n_outputs;
     }
+    return audio;
 }
 
-// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
-// The codec's output for frame j depends on the codes of frames [j - h, j + h] only (tts_hip_dac_halo_frames).  So once frames [e, f + h)
-// of an utterance are final, a window of frames [e - h, f + h) decoded as an utterance of its own yields the samples of frames [e, f)
-// exactly as the whole utterance's decode does (at the utterance's true edges the window is clipped and sees the same zero padding).
-// The loop: launch the next 32 steps -> decode the windows the last look-in made ready (one codec pass for every utterance, on the codec's
-// stream while the steps run) -> callbacks -> wait for the steps -> un-delay the frames that became final -> plan the next windows.
-static constexpr uint32_t CHUNK_LOOK_IN = 32;   // decode steps between two look-ins: generate_loop's, so rows are compacted at the same steps
-
-namespace {
-struct chunk_row {                    // one utterance of a chunked generation
-    std::vector<uint32_t> toks;       // delayed tokens so far [steps][heads]
-    std::vector<uint32_t> frames;     // codes of the kept frames that are final [frames][heads]
-    size_t   judged = 0;              // frames whose keep / drop is decided (parler_undelay's `next`)
-    uint32_t emitted = 0;             // kept frames handed out
-    bool     finished = false;
-};
-struct chunk_windows {                // the windows of one look-in: one tts_hip_dac_decode_windows pass
-    std::vector<uint32_t> codes, frames, keep0, keep1, row;
-};
+void parler_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+    std::vector<uint32_t> prompt, codes;
+    output.data = nullptr;
+    output.n_outputs = 0;
+    if (!prepare_single(sentence, config, prompt)) return;
+    last_output_tokens = std::move(run_rows({(uint32_t) prompt.size()}, config, nullptr)[0]);
+    adjust_output_tokens(last_output_tokens, codes);
+    const tts_response audio = decode_frames(codes, {(uint32_t) (codes.size() / hp.n_output_heads)})[0];
+    output.data = audio.data;
+    output.n_outputs = audio.n_outputs;
 }
 
-void parler_runner::chunked_run(const std::vector<uint32_t> & start, const generation_configuration & config, uint32_t chunk_frames,
-                                const std::function<bool(uint32_t, const float *, size_t)> & on_chunk, std::vector<std::vector<uint32_t>> & row_tokens) {
-    const uint32_t n = (uint32_t) start.size(), nh = hp.n_output_heads, U = hp.up_sampling_factor;
-    const uint32_t max_steps = hp.max_generation_size - *std::min_element(start.begin(), start.end());
-    const uint32_t h = dac_halo >= 0 ? (uint32_t) dac_halo : hp.max_generation_size;   // unknown halo: whole utterances once they are done
-    std::vector<chunk_row> rows(n);
-    chunk_windows W;
-    bool go = true;
-
-    // the frames of each row that became final since the last call, then a window per row that has chunks ready: whole chunks whose
-    // right halo is final too, or everything left once the row is finished
-    auto plan = [&]() {
-        for (uint32_t i = 0; i < n; i++) {
-            chunk_row & r = rows[i];
-            r.judged = parler_undelay(r.toks.data(), r.toks.size() / nh, nh, hp.audio_vocab_size, r.judged, r.finished, r.frames);
-            const uint32_t have = (uint32_t) (r.frames.size() / nh);
-            uint32_t end = r.emitted;
-            if (r.finished) end = have;
-            else if (have >= r.emitted + h + chunk_frames) end = r.emitted + (have - h - r.emitted) / chunk_frames * chunk_frames;
-            if (end == r.emitted) continue;
-            const uint32_t w0 = r.emitted > h ? r.emitted - h : 0, w1 = std::min(end + h, have);
-            W.codes.insert(W.codes.end(), r.frames.begin() + (size_t) w0 * nh, r.frames.begin() + (size_t) w1 * nh);
-            W.frames.push_back(w1 - w0);
-            W.keep0.push_back(r.emitted - w0);
-            W.keep1.push_back(end - w0);
-            W.row.push_back(i);
-            r.emitted = end;
-        }
-    };
-    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
-    auto emit = [&]() {
-        if (W.row.empty()) return true;
-        size_t total = 0;
-        for (size_t w = 0; w < W.row.size(); w++) total += (size_t) (W.keep1[w] - W.keep0[w]) * U;
-        pcm.resize(total);
-        hip_check(tts_hip_dac_decode_windows(ctx, W.codes.data(), W.frames.data(), W.keep0.data(), W.keep1.data(), (uint32_t) W.row.size(), pcm.data()),
-                  "tts_hip_dac_decode_windows");
-        bool more = true;
-        size_t off = 0;
-        for (size_t w = 0; w < W.row.size() && more; w++) {
-            const uint32_t nf = W.keep1[w] - W.keep0[w];
-            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
-                more = on_chunk(W.row[w], pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
-            off += (size_t) nf * U;
-        }
-        W = chunk_windows{};
-        return more;
-    };
-
-    if (!getenv("TTS_HOST_LOOP") && (!config.sample || hp.output_vocab_size <= 2048)) {
-        // generate_batch's device loop, in look-in pieces
-        std::vector<float> u;
-        const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-        if (config.sample) {   // one sampler state per utterance, seeded as generate() seeds its own: uniforms [step][utterance][head]
-            u.resize((size_t) max_steps * n * nh);
-            for (uint32_t i = 0; i < n; i++) {
-                sampler si = smp;
-                si.seed = config.seed; si.n_calls = 0;
-                for (uint32_t s = 0; s < max_steps; s++) si.draw_uniforms(u.data() + ((size_t) s * n + i) * nh);
-            }
-        }
-        hip_check(tts_hip_parler_gen_begin(ctx, n, start.data(), max_steps, hp.bos_token_id, hp.eos_token_id, config.sample ? &sp : nullptr,
-                                           config.sample ? u.data() : nullptr), "tts_hip_parler_gen_begin");
-        std::vector<uint32_t> toks((size_t) max_steps * n * nh), done(n);
-        uint32_t ran = 0;
-        hip_check(tts_hip_parler_gen_launch(ctx, CHUNK_LOOK_IN), "tts_hip_parler_gen_launch");
-        for (;;) {
-            go = emit();   // the codec windows of the last look-in, while the steps run
-            hip_check(tts_hip_parler_gen_wait(ctx, toks.data(), done.data(), &ran), "tts_hip_parler_gen_wait");
-            bool all = true;
-            for (uint32_t i = 0; i < n; i++) {
-                // check_stopping per sequence, as generate_batch reads it: EOS on every head, or position == max_generation
-                const uint32_t cap = std::min(done[i] ? done[i] : max_steps, hp.max_generation_size - start[i]), have = std::min(ran, cap);
-                chunk_row & r = rows[i];
-                for (uint32_t s = (uint32_t) (r.toks.size() / nh); s < have; s++)
-                    r.toks.insert(r.toks.end(), toks.begin() + ((size_t) s * n + i) * nh, toks.begin() + ((size_t) s * n + i + 1) * nh);
-                r.finished = done[i] != 0 || ran >= max_steps || have >= cap;
-                all = all && r.finished;
-            }
-            if (all || !go) break;
-            hip_check(tts_hip_parler_gen_launch(ctx, CHUNK_LOOK_IN), "tts_hip_parler_gen_launch");
-            plan();
-        }
-    } else {
-        // generate_batch's host loop; the windows are planned and decoded at the same look-in points, without overlap
-        std::vector<sampler> smps(n, smp);
-        for (uint32_t i = 0; i < n; i++) {
-            smps[i].temperature = config.temperature; smps[i].repetition_penalty = config.repetition_penalty;
-            smps[i].do_sample = config.sample; smps[i].top_k = (uint32_t) config.top_k; smps[i].top_p = config.top_p;
-            smps[i].seed = config.seed; smps[i].n_calls = 0;
-            smps[i].reset();
-        }
-        std::vector<uint32_t> in_ids((size_t) n * nh, hp.bos_token_id), pos(start);
-        std::vector<std::vector<bool>> eos_seen(n, std::vector<bool>(nh, false));
-        std::vector<float> lg((size_t) n * nh * hp.output_vocab_size);
-        for (uint32_t step = 1; step <= max_steps && go; step++) {
-            bool all_done = true;
-            for (uint32_t i = 0; i < n; i++) {
-                chunk_row & r = rows[i];
-                if (r.finished) continue;
-                auto & t = r.toks;
-                if (!t.empty()) {
-                    if (pos[i] >= hp.max_generation_size) { r.finished = true; continue; }
-                    bool all = true;
-                    for (uint32_t k = 0; k < nh; k++) {
-                        eos_seen[i][k] = eos_seen[i][k] || t[t.size() - nh + k] == hp.eos_token_id;
-                        all = all && eos_seen[i][k];
-                    }
-                    if (all) { r.finished = true; continue; }
-                }
-                all_done = false;
-            }
-            if (all_done) break;
-            hip_check(tts_hip_parler_step(ctx, n, in_ids.data(), pos.data(), nullptr, lg.data()), "tts_hip_parler_step");
-            for (uint32_t i = 0; i < n; i++) {
-                if (pos[i] + 1 < hp.max_generation_size) pos[i] += 1;  // finished rows idle on their last position
-                if (rows[i].finished) continue;
-                auto & t = rows[i].toks;
-                smps[i].sample(lg.data() + (size_t) i * nh * hp.output_vocab_size, t);
-                const uint32_t * last = t.data() + t.size() - nh;
-                for (uint32_t k = 0; k < nh; k++)
-                    in_ids[(size_t) i * nh + k] = step > k ? (eos_seen[i][k] ? hp.eos_token_id : last[k]) : hp.bos_token_id;
-            }
-            if (step % CHUNK_LOOK_IN == 0) {
-                plan();
-                go = emit();
-            }
-        }
-        if (go) for (auto & r : rows) r.finished = true;   // the loop ran to its end: nothing more comes
+void parler_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
+                                   const generation_configuration & config) {
+    outputs.assign(sentences.size(), tts_response{});
+    std::vector<uint32_t> start, row_of;
+    if (!prepare_batch(sentences, config, start, row_of)) return;
+    std::vector<std::vector<uint32_t>> row_tokens = run_rows(start, config, nullptr);
+    std::vector<uint32_t> codes, frames;
+    for (size_t i = 0; i < row_of.size(); i++) {
+        const size_t before = codes.size();
+        adjust_output_tokens(row_tokens[i], codes);
+        frames.push_back((uint32_t) ((codes.size() - before) / hp.n_output_heads));
+        last_batch_tokens[row_of[i]] = std::move(row_tokens[i]);
     }
-    if (go) {   // what is left once every utterance is done
-        plan();
-        (void) emit();
-    }
-    row_tokens.resize(n);
-    for (uint32_t i = 0; i < n; i++) row_tokens[i] = std::move(rows[i].toks);
+    const std::vector<tts_response> audio = decode_frames(codes, frames);
+    for (size_t i = 0; i < row_of.size(); i++) outputs[row_of[i]] = audio[i];
 }
 
 void parler_runner::generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
@@ -581,9 +476,9 @@ void parler_runner::generate_chunked(const char * sentence, const generation_con
     if (chunk_frames == 0) TTS_ABORT("generate_chunked: chunk_frames must be >= 1\n");
     std::vector<uint32_t> prompt;
     if (!prepare_single(sentence, config, prompt)) return;
-    std::vector<std::vector<uint32_t>> rt;
-    chunked_run({(uint32_t) prompt.size()}, config, chunk_frames, [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); }, rt);
-    last_output_tokens = std::move(rt[0]);
+    const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); };
+    chunker hook{*this, chunk_frames, cb};
+    last_output_tokens = std::move(run_rows({(uint32_t) prompt.size()}, config, &hook)[0]);
 }
 
 void parler_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
@@ -591,9 +486,10 @@ void parler_runner::generate_batch_chunked(const std::vector<std::string> & sent
     if (chunk_frames == 0) TTS_ABORT("generate_batch_chunked: chunk_frames must be >= 1\n");
     std::vector<uint32_t> start, row_of;
     if (!prepare_batch(sentences, config, start, row_of)) return;
-    std::vector<std::vector<uint32_t>> rt;
-    chunked_run(start, config, chunk_frames, [&](uint32_t row, const float * p, size_t k) { return on_chunk(row_of[row], p, k); }, rt);
-    for (size_t i = 0; i < row_of.size(); i++) last_batch_tokens[row_of[i]] = std::move(rt[i]);
+    const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t row, const float * p, size_t k) { return on_chunk(row_of[row], p, k); };
+    chunker hook{*this, chunk_frames, cb};
+    std::vector<std::vector<uint32_t>> row_tokens = run_rows(start, config, &hook);
+    for (size_t i = 0; i < row_of.size(); i++) last_batch_tokens[row_of[i]] = std::move(row_tokens[i]);
 }
 
 // ---- continuous batching (common.h; tts_hip_parler_stream_* underneath) ----------------------------------------------------------------
@@ -625,9 +521,7 @@ void parler_runner::stream_submit(size_t ticket, const std::string & sentence) {
     if (st_free.empty()) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
     pending p;
     p.ticket = ticket;
-    tokenizer->tokenize(sentence, p.prompt);
-    p.prompt.push_back(tokenizer->eos_token);
-    if (p.prompt.size() >= hp.max_generation_size || p.prompt.size() >= hp.max_ctx_length) {
+    if (!tokenize_prompt(sentence, p.prompt)) {
         // generate() answers such a prompt with an empty response: the session does the same at its next step
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", p.prompt.size());
         st_codec.push_back(decoded{ticket, {}});
@@ -653,11 +547,9 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
             st_ticket[p.slot] = p.ticket;
             st_start[p.slot] = (uint32_t) p.prompt.size();
             if (st_cfg.sample) {   // the utterance's own sampler, seeded as a generate() call of its own would be
-                sampler si = smp;
-                si.seed = st_cfg.seed; si.n_calls = 0;
                 const size_t o = uni.size();
                 uni.resize(o + (size_t) st_max_steps * nh);
-                for (uint32_t s = 0; s < st_max_steps; s++) si.draw_uniforms(uni.data() + o + (size_t) s * nh);
+                draw_row_uniforms(smp, st_cfg.seed, st_max_steps, nh, uni.data() + o);
             }
         }
         hip_check(tts_hip_parler_stream_admit(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), st_cfg.sample ? uni.data() : nullptr),
@@ -688,21 +580,15 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
     st_codec_held = (take < st_codec.size()) ? (take ? 0 : st_codec_held + 1) : 0;
     if (take) {
         std::vector<uint32_t> codes, frames(take);
-        size_t total = 0;
         for (size_t i = 0; i < take; i++) {
             frames[i] = (uint32_t) (st_codec[i].frames.size() / nh);
             codes.insert(codes.end(), st_codec[i].frames.begin(), st_codec[i].frames.end());
-            total += (size_t) frames[i] * hp.up_sampling_factor;
         }
-        pcm.assign(total, 0.0f);
-        if (total) hip_check(tts_hip_dac_decode_batch(ctx, codes.data(), frames.data(), (uint32_t) take, pcm.data()), "tts_hip_dac_decode_batch");
-        size_t off = 0;
+        const std::vector<tts_response> audio = decode_frames(codes, frames);
         for (size_t i = 0; i < take; i++) {
             stream_result r;
             r.ticket = st_codec[i].ticket;
-            r.audio.data = pcm.data() + off;
-            r.audio.n_outputs = (size_t) frames[i] * hp.up_sampling_factor;
-            off += r.audio.n_outputs;
+            r.audio = audio[i];
             finished.push_back(r);
         }
         st_codec.erase(st_codec.begin(), st_codec.begin() + (std::ptrdiff_t) take);

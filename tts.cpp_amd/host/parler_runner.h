@@ -4,6 +4,10 @@
 // 704-858): tokenise -> text-prompt decode -> AR loop with the delay pattern, host sampling and EOS
 // tracking -> un-delay -> DAC.  The ggml graph build/compute inside decode() and dac_runner::run() is
 // replaced by calls into the C ABI; everything the reference keeps on the host stays on the host.
+//
+// generate, generate_batch and their chunked forms share one generation loop (run_rows) over the prefilled rows: the device loop
+// (tts_hip_parler_gen_begin / _launch / _wait, a look-in every 32 steps) or, under TTS_HOST_LOOP or with more than 2048 logits per head,
+// the host loop (tts_hip_parler_step + sampler::sample per step).  Chunked audio is a hook called at that loop's look-ins.
 #pragma once
 #include <memory>
 #include <string>
@@ -85,16 +89,17 @@ struct parler_runner final : tts_generation_runner {
     int                                device_id = 0;
     std::vector<uint32_t>              last_conditional_tokens;  // ids the voice prompt was encoded from (tests)
     std::vector<float>                 pcm;     // runner-owned output buffer (dctx->buf_output)
-    std::vector<float>                 logits;
 
   private:
+    bool tokenize_prompt(const std::string & sentence, std::vector<uint32_t> & prompt) const;
     bool prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt);
     bool prepare_batch(const std::vector<std::string> & sentences, const generation_configuration & config, std::vector<uint32_t> & start,
                        std::vector<uint32_t> & row_of);
     int  dac_halo = -1;   // tts_hip_dac_halo_frames of the codec layout (-1: unknown; chunked audio then decodes whole utterances)
-    // the generation loop of generate_chunked / generate_batch_chunked over n prefilled rows (row i starts at start[i]); tokens per row out
-    void chunked_run(const std::vector<uint32_t> & start, const generation_configuration & config, uint32_t chunk_frames,
-                     const std::function<bool(uint32_t, const float *, size_t)> & on_chunk, std::vector<std::vector<uint32_t>> & row_tokens);
+    struct chunker;       // the look-in hook of chunked audio: windows of the frames that became final -> codec -> callbacks
+    // the one generation loop, over n prefilled rows (row i starts at start[i]); hook: nullptr, or called at every look-in; tokens per row out
+    std::vector<std::vector<uint32_t>> run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook);
+    std::vector<tts_response> decode_frames(const std::vector<uint32_t> & codes, const std::vector<uint32_t> & frames);
     // session state of the continuous batching
     struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; };
     struct decoded { size_t ticket; std::vector<uint32_t> frames; };   // un-delayed codes waiting for a codec pass
