@@ -54,7 +54,8 @@ int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, i
  * chunk_frames codec frames while the utterance is still generating (pcm valid during the call only; utterance = 0 here, the text's index in
  * the batch form); their concatenation equals tts_c_generate's / tts_c_generate_batch's audio.  fn returning 0 stops the generation at the
  * next look-in point.  Returns 0 when done, 1 when fn stopped it, another value with tts_c_last_error() on error (chunk_frames == 0 is one).
- * Parler-TTS and Orpheus stream; the other architectures generate the whole utterance and hand it out as one chunk.
+ * Parler-TTS, Orpheus and Dia stream; Kokoro generates the whole utterance and hands it out as one chunk.
+ * Dia: chunk_frames counts the frames the codec sees, after the un-delay dropped those that hold EOS / PAD.
  * Orpheus: chunk_frames counts SNAC frames (7 ids, 2048 samples at 24 kHz).  With TTS_SNAC_NO_NOISE the chunks concatenate to tts_c_generate's
  * PCM.  With the noise block they are a different realisation of the same distribution: generate() draws the noise layer by layer over the
  * whole utterance, chunked generation frame by frame (per frame, for layer l, 4 * prod(stride_0..l) normals) from the same engine, and the
@@ -153,6 +154,11 @@ int tts_c_dia_check_stopping(uint32_t *ids, uint32_t eos, uint32_t pad, uint32_t
                              int *delay_steps);
 /* adjust_output_tokens :787-808: tokens[n_steps][9] -> filtered frames [..][9]; returns the number of ids written */
 int64_t tts_c_dia_adjust_output_tokens(const uint32_t *tokens, uint64_t n_ids, uint32_t audio_vocab, uint32_t max_delay, uint32_t *filtered);
+/* the runner's incremental form of that rule (dia_undelay) fed tokens[n_steps][9] in pieces of `piece` steps (0: all at once), each call
+ * continuing from the cursor the last one returned: the kept frames that are final after n_steps steps.  out [frames][9] may be NULL to
+ * count; returns the number of frames. */
+int64_t tts_c_dia_final_frames(const uint32_t *tokens, uint64_t n_steps, uint32_t audio_vocab, uint32_t max_delay, uint64_t piece, uint32_t *out,
+                               uint64_t cap_frames);
 
 /* ---- Kokoro host logic, callable without a device (host/kokoro_runner.h; reference src/tokenizer.cpp:159-177,
  * src/models/kokoro/model.cpp:1340-1388) ------------------------------------------------------------------------------

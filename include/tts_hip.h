@@ -348,6 +348,23 @@ typedef struct tts_hip_dia_codes {
 } tts_hip_dia_codes;
 int tts_hip_dia_generate(tts_hip_ctx *ctx, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sampling,
                          const float *uniforms, uint32_t *tokens_out, uint32_t *steps_out);
+/* The same loop in pieces, for callers that work on the ids while the decoder is still running (the runner's chunked audio un-delays
+ * frames and decodes codec windows meanwhile); tts_hip_dia_generate is built on them.
+ *   gen_begin   checks and stages what tts_hip_dia_generate does: uniforms, penalty table, loop state (ids = BOS, positions 0)
+ *   gen_launch  enqueues up to n_steps replays of the captured step (eager under TTS_HIP_FLAG_NO_GRAPH / profiling; the very first step
+ *               runs eagerly and is then captured) and returns without waiting.  Never more than the max_gen + 1 pre-steps
+ *               tts_hip_dia_generate allows; nothing once a gen_wait has seen every utterance done.
+ *   gen_wait    waits for the launched steps and looks in — one gather launch, one copy, one synchronisation whatever n_utt is:
+ *               steps_done [n_utt] = sampler calls made so far, done [n_utt] = the countdown has ended, *ran = pre-steps launched so far
+ *               (each may be NULL), and — when tokens_out != NULL — the tokens of the steps no earlier gen_wait handed out, written at
+ *               their places in tokens_out [n_utt][max_gen][n_output_heads] (NULL: they stay for a later gen_wait).
+ * The generation is over when every done flag is set or *ran == max_gen + 1.  The ids do not depend on the launch sizes.  While steps are
+ * in flight the codec context may run (its own context and stream); any other call on this context needs a gen_wait first, except that
+ * tts_hip_dia_encode* / tts_hip_dia_step* / gen_begin / tts_hip_dia_generate wait for an unfinished loop themselves and drop it. */
+int tts_hip_dia_gen_begin(tts_hip_ctx *ctx, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sampling,
+                          const float *uniforms);
+int tts_hip_dia_gen_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran);
 
 /* ---- Kokoro (src/models/kokoro/model.cpp) ----------------------------------------------------------------------------
  * Device side of kokoro_duration_runner::run (:1069-1123) and kokoro_runner::run (:1277-1325): create, tts_hip_upload every

@@ -103,3 +103,34 @@ static __global__ void dia_poststep_kernel(DiaLoopArgs a) {
     a.pos[2 * u + 1] = np;
     for (int i = 0; i < a.n_out; i++) a.ids[u * a.n_out + i] = np > (uint32_t) i ? a.tok[u * a.n_out + i] : a.bos;
 }
+
+// A look-in of the loop in pieces (tts_hip_dia_gen_wait): one workgroup per utterance packs {position, done flag, the history rows no
+// earlier look-in took} into its slot of one contiguous block, so that the host learns everything from one launch, one copy and one
+// synchronisation however many utterances there are.  take = 0: the header only (the rows stay for a later look-in).
+struct DiaLookArgs {
+    int n_utt, n_out;
+    uint32_t max_gen;
+    uint32_t cap;            // rows a slot holds: the steps enqueued since the last look-in that took rows
+    int take;
+    const uint32_t *pos;     // [2 * n_utt]
+    const uint32_t *done;    // [n_utt]
+    const uint32_t *hist;    // [n_utt][max_gen][n_out]
+    uint32_t *handed;        // [n_utt] history rows taken so far
+    uint32_t *block;         // [n_utt][2 + cap * n_out]
+};
+
+static __global__ __launch_bounds__(64) void dia_lookin_kernel(DiaLookArgs a) {
+    const int u = blockIdx.x;
+    if (u >= a.n_utt) return;
+    const uint32_t from = a.handed[u], to = min(a.pos[2 * u], a.max_gen);
+    const uint32_t rows = a.take && to > from ? min(to - from, a.cap) : 0u;
+    uint32_t *slot = a.block + (int64_t) u * (2 + (int64_t) a.cap * a.n_out);
+    const uint32_t *src = a.hist + ((int64_t) u * a.max_gen + from) * a.n_out;
+    for (uint32_t i = threadIdx.x; i < rows * (uint32_t) a.n_out; i += blockDim.x) slot[2 + i] = src[i];
+    __syncthreads();   // every thread has read handed[u]
+    if (threadIdx.x == 0) {
+        slot[0] = to;   // sampler calls made so far; the host derives `rows` from it as this kernel does
+        slot[1] = a.done[u];
+        a.handed[u] = from + rows;
+    }
+}

@@ -1050,7 +1050,9 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         CHK(dmalloc(&c->ad, (size_t) c->RMAX * maxK / 32 + 1));
         CHK(dmalloc(&c->di_tok, n)); CHK(dmalloc(&c->di_epos, n)); CHK(dmalloc(&c->di_eseq, n)); CHK(dmalloc(&c->di_kbeg, n)); CHK(dmalloc(&c->di_kend, n));
         CHK(dmalloc(&c->di_ids, (size_t) U * 16)); CHK(dmalloc(&c->di_pos, (size_t) R)); CHK(dmalloc(&c->di_seq, (size_t) R)); CHK(dmalloc(&c->di_cend, (size_t) R));
-        CHK(dmalloc(&c->di_stok, (size_t) U * 16)); CHK(dmalloc(&c->di_loop, (size_t) 3 * U)); CHK(dmalloc(&c->di_hist, (size_t) U * G * c->NO));
+        CHK(dmalloc(&c->di_stok, (size_t) U * 16)); CHK(dmalloc(&c->di_loop, (size_t) 4 * U)); CHK(dmalloc(&c->di_hist, (size_t) U * G * c->NO));
+        CHK(dmalloc(&c->di_look, (size_t) U * (2 + (size_t) G * c->NO)));
+        HIPCHK(hipHostMalloc((void **) &c->h_di_look, (size_t) U * (2 + (size_t) G * c->NO) * 4));
         CHK(dmalloc(&c->d_last, (size_t) U * c->NO)); CHK(dmalloc(&c->d_repc, (size_t) U * c->NO));
         HIPCHK(hipHostMalloc((void **) &c->h_di, ((size_t) U * 16 + 2 * (size_t) R) * 4));
         std::vector<uint32_t> cend((size_t) R, (uint32_t) S);

@@ -182,6 +182,19 @@ struct tts_hip_ctx {
     uint32_t *di_ids = nullptr, *di_pos = nullptr, *di_seq = nullptr, *di_cend = nullptr;
     // device-resident generation loop (tts_hip_dia_generate): sampled ids [U][NO], countdown [U] / done [U] / sampler call [U], history [U][G][NO]
     uint32_t *di_stok = nullptr, *di_loop = nullptr, *di_hist = nullptr;
+    // the loop in pieces (tts_hip_dia_gen_begin / _launch / _wait): di_loop carries a fourth array, history rows handed out [U]; a look-in
+    // packs per utterance {position, done, new history rows} into di_look, which travels to h_di_look (pinned) in one copy
+    uint32_t *di_look = nullptr, *h_di_look = nullptr;
+    struct DiaGen {
+        bool active = false, sampled = false, rep = false, all_done = false;
+        uint32_t n_utt = 0, max_gen = 0;
+        tts_hip_dia_codes codes{};
+        tts_hip_sampling sp{};
+        uint32_t launched = 0;   // pre-steps enqueued so far (at most max_gen + 1)
+        uint32_t pending = 0;    // ... of which no gen_wait has waited for yet
+        uint32_t unread = 0;     // steps enqueued since the last gen_wait that took tokens: bounds the rows a look-in can find
+        std::vector<uint32_t> handed;   // per utterance: history rows handed out (the host's copy of di_loop's fourth array)
+    } dg;
     _Float16 *di_e16 = nullptr;   // [2 * max_ctx][max(EH, A, EF)] the encoder activations rounded to fp16 for gemm_tile_kernel
     struct { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int mode = -1; uint32_t U = 0, max_gen = 0; tts_hip_dia_codes codes{}; } di_baked;
     int di_U = 1;                        // utterance slots (rows = 2 per slot)

@@ -846,6 +846,8 @@ static int dia_rms(tts_hip_ctx *c, size_t w_off, int rows, int H, float *x, floa
     return hipGetLastError() == hipSuccess ? 0 : set_err("rms_fold_rows_kernel launch failed");
 }
 
+static int dia_gen_drop(tts_hip_ctx *c);
+
 extern "C" int tts_hip_dia_encode_slot(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_encode: not a Dia context (tts_hip_dia_create)");
     if (slot >= (uint32_t) c->di_U) return set_err("tts_hip_dia_encode_slot: slot %u outside the %d utterance slots of this context (max_utterances)", slot, c->di_U);
@@ -854,6 +856,7 @@ extern "C" int tts_hip_dia_encode_slot(tts_hip_ctx *c, uint32_t slot, const uint
     const int S = (int) c->dia.max_ctx, EH = c->di_EH, EF = c->di_EF, A = c->di_A, HD = (int) c->dia.head_dim, ENH = (int) c->dia.enc_attn_heads;
     const int NH = c->NH, n = 2 * S;
     if (sentence_len == 0 || sentence_len > (uint32_t) S) return set_err("tts_hip_dia_encode: sentence length %u outside 1..%d", sentence_len, S);
+    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     std::vector<uint32_t> tok((size_t) n, 0u), epos((size_t) n), eseq((size_t) n), kbeg((size_t) n), kend((size_t) n);
     for (int t = 0; t < S; t++) {
         if (tokens[t] >= (uint32_t) c->di_evocab) return set_err("tts_hip_dia_encode: token %u >= encoder vocabulary %d", tokens[t], c->di_evocab);
@@ -1027,6 +1030,7 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
         h_seq[2 * u] = 2 * slot; h_seq[2 * u + 1] = 2 * slot + 1;
         max_pos = std::max(max_pos, pos[u]);
     }
+    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(c->di_ids, h_ids, (size_t) U * NO * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->di_pos, h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1040,33 +1044,84 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
     return 0;
 }
 
+// ---- the generation loop in pieces (include/tts_hip.h) ----------------------------------------------------------------------------------
 #define DIA_LOOP_CHUNK 16
-extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms,
-                                    uint32_t *tokens_out, uint32_t *steps_out) {
-    if (!c || !c->has_dia) return set_err("tts_hip_dia_generate: not a Dia context (tts_hip_dia_create)");
-    if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_generate: context not finalized");
-    if (!codes || !tokens_out || !steps_out) return set_err("tts_hip_dia_generate: null argument");
-    if (n_utt == 0 || n_utt > (uint32_t) c->di_U) return set_err("tts_hip_dia_generate: %u utterances outside 1..%d (max_utterances)", n_utt, c->di_U);
-    const int G = (int) c->dia.max_gen, NO = c->NO, V = c->di_V, U = (int) n_utt;
-    if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("tts_hip_dia_generate: max_gen %u outside 1..%d cached positions", max_gen, G);
-    if (codes->max_delay >= max_gen) return set_err("tts_hip_dia_generate: max_gen %u must exceed max_delay %u", max_gen, codes->max_delay);
-    if (codes->bos >= (uint32_t) V || codes->eos >= (uint32_t) V || codes->pad >= (uint32_t) V) return set_err("tts_hip_dia_generate: special ids outside the vocabulary %d", V);
-    for (int u = 0; u < U; u++)
-        if (!c->di_slot_encoded[(size_t) u]) return set_err("tts_hip_dia_generate: slot %d has not been encoded (tts_hip_dia_encode_slot)", u);
-    if (sp) {
-        if (V > SMP_VMAX) return set_err("tts_hip_dia_generate: output vocabulary %d > %d", V, SMP_VMAX);
-        if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f) || !(sp->repetition_penalty > 0.0f)) return set_err("tts_hip_dia_generate: temperature, top_p, repetition_penalty must be > 0");
-        if (!uniforms) return set_err("tts_hip_dia_generate: null uniforms");
+
+// an unfinished loop is waited for and dropped: encode / step / a new loop overwrite what its steps read
+static int dia_gen_drop(tts_hip_ctx *c) {
+    if (!c->dg.active) return 0;
+    if (c->dg.pending) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
+    c->dg = tts_hip_ctx::DiaGen{};
+    return 0;
+}
+
+static DiaLoopArgs dia_loop_args(tts_hip_ctx *c) {
+    const auto &g = c->dg;
+    DiaLoopArgs la{};
+    la.n_utt = (int) g.n_utt; la.n_out = c->NO;
+    la.bos = g.codes.bos; la.eos = g.codes.eos; la.pad = g.codes.pad; la.max_delay = g.codes.max_delay; la.max_gen = g.max_gen;
+    for (int i = 0; i < 16; i++) la.delay_pattern[i] = g.codes.delay_pattern[i];
+    la.ids = c->di_ids; la.pos = c->di_pos;
+    la.delay = (int32_t *) c->di_loop; la.done = c->di_loop + c->di_U; la.call = c->di_loop + 2 * c->di_U;
+    la.tok = c->di_stok; la.hist = c->di_hist;
+    return la;
+}
+
+// pre-step, forward, guidance, sampler, post-step: what one replay of the captured graph runs
+static int dia_loop_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
+    const auto &g = c->dg;
+    const int U = (int) g.n_utt, NO = c->NO, V = c->di_V;
+    hipLaunchKernelGGL(dia_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
+    HIPCHK(hipGetLastError());
+    CHK(dia_forward(c, U, (int) c->dia.max_gen, captured));
+    if (g.sampled) {
+        SampleArgs sa{};
+        sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
+        sa.top_k = g.sp.top_k; sa.top_p = g.sp.top_p; sa.temperature = g.sp.temperature;
+        sa.uniforms = c->d_uniforms; sa.row_step = la.call; sa.out = c->di_stok;
+        if (g.rep) { sa.pen_table = c->d_pen; sa.pen_len = c->pen_len; sa.last_ids = c->d_last; sa.rep_counts = c->d_repc; }
+        hipLaunchKernelGGL(sample_kernel, dim3(NO, U), dim3(256), 0, c->stream, sa);
+    } else {
+        hipLaunchKernelGGL(argmax_kernel, dim3(U * NO), dim3(256), 0, c->stream, (const float *) c->di_guided, V, c->di_stok);
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(dia_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static const int DIA_GRAPH_KEY = 9100001;
+
+static int dia_gen_begin(tts_hip_ctx *c, const char *what, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp,
+                         const float *uniforms) {
+    if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
+    if (!codes) return set_err("%s: null argument", what);
+    if (n_utt == 0 || n_utt > (uint32_t) c->di_U) return set_err("%s: %u utterances outside 1..%d (max_utterances)", what, n_utt, c->di_U);
+    const int G = (int) c->dia.max_gen, NO = c->NO, V = c->di_V, U = (int) n_utt;
+    if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("%s: max_gen %u outside 1..%d cached positions", what, max_gen, G);
+    if (codes->max_delay >= max_gen) return set_err("%s: max_gen %u must exceed max_delay %u", what, max_gen, codes->max_delay);
+    if (codes->bos >= (uint32_t) V || codes->eos >= (uint32_t) V || codes->pad >= (uint32_t) V) return set_err("%s: special ids outside the vocabulary %d", what, V);
+    for (int u = 0; u < U; u++)
+        if (!c->di_slot_encoded[(size_t) u]) return set_err("%s: slot %d has not been encoded (tts_hip_dia_encode_slot)", what, u);
+    if (sp) {
+        if (V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, V, SMP_VMAX);
+        if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f) || !(sp->repetition_penalty > 0.0f)) return set_err("%s: temperature, top_p, repetition_penalty must be > 0", what);
+        if (!uniforms) return set_err("%s: null uniforms", what);
+    }
+    CHK(dia_gen_drop(c));
     HIPCHK(hipSetDevice(c->device));
     const bool rep = sp && sp->repetition_penalty != 1.0f;
     if (sp) {
         CHK(stage_uniforms(c, uniforms, (size_t) max_gen * U * NO));
         CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
     }
-    // loop state: ids = BOS everywhere, positions 0, countdown -1, nothing done; sampler::reset (sampler.cpp:71-80)
+    // loop state: ids = BOS everywhere, positions 0, countdown -1, nothing done, nothing handed out; sampler::reset (sampler.cpp:71-80)
     {
-        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), zero((size_t) 3 * c->di_U, 0u), seq((size_t) 2 * U);
+        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), zero((size_t) 4 * c->di_U, 0u), seq((size_t) 2 * U);
         for (int u = 0; u < U; u++) { zero[(size_t) u] = 0xFFFFFFFFu; seq[(size_t) 2 * u] = 2 * u; seq[(size_t) 2 * u + 1] = 2 * u + 1; }
         HIPCHK(hipMemcpyAsync(c->di_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemsetAsync(c->di_pos, 0, (size_t) 2 * U * 4, c->stream));
@@ -1078,32 +1133,6 @@ extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals
     }
-    DiaLoopArgs la{};
-    la.n_utt = U; la.n_out = NO;
-    la.bos = codes->bos; la.eos = codes->eos; la.pad = codes->pad; la.max_delay = codes->max_delay; la.max_gen = max_gen;
-    for (int i = 0; i < 16; i++) la.delay_pattern[i] = codes->delay_pattern[i];
-    la.ids = c->di_ids; la.pos = c->di_pos;
-    la.delay = (int32_t *) c->di_loop; la.done = c->di_loop + c->di_U; la.call = c->di_loop + 2 * c->di_U;
-    la.tok = c->di_stok; la.hist = c->di_hist;
-    auto one_step = [&](bool captured) -> int {
-        hipLaunchKernelGGL(dia_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
-        HIPCHK(hipGetLastError());
-        CHK(dia_forward(c, U, G, captured));
-        if (sp) {
-            SampleArgs sa{};
-            sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
-            sa.top_k = sp->top_k; sa.top_p = sp->top_p; sa.temperature = sp->temperature;
-            sa.uniforms = c->d_uniforms; sa.row_step = la.call; sa.out = c->di_stok;
-            if (rep) { sa.pen_table = c->d_pen; sa.pen_len = c->pen_len; sa.last_ids = c->d_last; sa.rep_counts = c->d_repc; }
-            hipLaunchKernelGGL(sample_kernel, dim3(NO, U), dim3(256), 0, c->stream, sa);
-        } else {
-            hipLaunchKernelGGL(argmax_kernel, dim3(U * NO), dim3(256), 0, c->stream, (const float *) c->di_guided, V, c->di_stok);
-        }
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(dia_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
-        HIPCHK(hipGetLastError());
-        return 0;
-    };
     // everything the captured launches hold by value: a change drops the graph
     const int mode = sp ? 1 : 0;
     const void *pen = rep ? (const void *) c->d_pen : nullptr;
@@ -1111,53 +1140,117 @@ extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max
     auto &bk = c->di_baked;
     const bool same = bk.mode == mode && bk.U == n_utt && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
                       (!sp || (bk.uni == c->d_uniforms && bk.pen == pen && memcmp(&bk.sp, &spv, sizeof(spv)) == 0));
-    const int key = 9100001;
     if (!same) {
-        auto it = c->graphs.find(key);
+        auto it = c->graphs.find(DIA_GRAPH_KEY);
         if (it != c->graphs.end()) { (void) hipGraphExecDestroy(it->second); c->graphs.erase(it); }
         bk.mode = mode; bk.U = n_utt; bk.max_gen = max_gen; bk.codes = *codes; bk.uni = c->d_uniforms; bk.pen = pen; bk.sp = spv;
     }
+    auto &g = c->dg;
+    g.active = true; g.sampled = sp != nullptr; g.rep = rep;
+    g.n_utt = n_utt; g.max_gen = max_gen; g.codes = *codes; g.sp = spv;
+    g.handed.assign((size_t) U, 0u);
+    return 0;
+}
+
+// at most max_gen sampler calls, then one pre-step that ends the countdown: never more than max_gen + 1 pre-steps
+static int dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    auto &g = c->dg;
+    if (g.all_done || g.launched >= g.max_gen + 1) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t k = std::min<uint32_t>(n_steps, g.max_gen + 1 - g.launched);
     const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
-    std::vector<uint32_t> done((size_t) U);
-    uint32_t ran = 0;
-    while (ran < max_gen + 1) {   // at most max_gen sampler calls, then one pre-step that ends the countdown
-        const uint32_t chunk = std::min<uint32_t>(DIA_LOOP_CHUNK, max_gen + 1 - ran);
-        if (use_graph) {
-            auto it = c->graphs.find(key);
-            if (it == c->graphs.end()) {
+    const DiaLoopArgs la = dia_loop_args(c);
+    for (uint32_t s = 0; s < k; s++) {
+        if (!use_graph) {
+            CHK(dia_loop_step(c, la, false));
+        } else {
+            auto it = c->graphs.find(DIA_GRAPH_KEY);
+            if (it != c->graphs.end()) {
+                HIPCHK(hipGraphLaunch(it->second, c->stream));
+            } else {
                 // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
-                CHK(one_step(false));
+                CHK(dia_loop_step(c, la, false));
                 HIPCHK(hipStreamSynchronize(c->stream));
                 hipGraph_t graph = nullptr;
                 HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                const int rc = one_step(true);
+                const int rc = dia_loop_step(c, la, true);
                 const hipError_t e = hipStreamEndCapture(c->stream, &graph);
                 if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
                 if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
                 hipGraphExec_t exec = nullptr;
                 HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                 (void) hipGraphDestroy(graph);
-                it = c->graphs.emplace(key, exec).first;
-                for (uint32_t s = 1; s < chunk; s++) HIPCHK(hipGraphLaunch(it->second, c->stream));
-            } else {
-                for (uint32_t s = 0; s < chunk; s++) HIPCHK(hipGraphLaunch(it->second, c->stream));
+                c->graphs.emplace(DIA_GRAPH_KEY, exec);
             }
-        } else {
-            for (uint32_t s = 0; s < chunk; s++) CHK(one_step(false));
         }
-        ran += chunk;
-        HIPCHK(hipMemcpyAsync(done.data(), la.done, (size_t) U * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        bool all = true;
-        for (int u = 0; u < U; u++) all = all && done[(size_t) u] != 0;
-        if (all) break;
+        g.launched++; g.pending++; g.unread++;
     }
-    std::vector<uint32_t> pos((size_t) 2 * U);
-    HIPCHK(hipMemcpyAsync(pos.data(), c->di_pos, pos.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(tokens_out, c->di_hist, (size_t) U * max_gen * NO * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int u = 0; u < U; u++) steps_out[u] = pos[(size_t) 2 * u];
     return 0;
+}
+
+static int dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
+    auto &g = c->dg;
+    const int U = (int) g.n_utt, NO = c->NO;
+    HIPCHK(hipSetDevice(c->device));
+    DiaLookArgs a{};
+    a.n_utt = U; a.n_out = NO; a.max_gen = g.max_gen;
+    a.take = tokens_out ? 1 : 0;
+    a.cap = a.take ? g.unread : 0u;   // <= max_gen + 1 rows per slot; di_look holds max_generation_size rows and a slot never fills beyond max_gen - handed
+    a.cap = std::min(a.cap, g.max_gen);
+    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.hist = c->di_hist; a.handed = c->di_loop + 3 * c->di_U; a.block = c->di_look;
+    const size_t slot = 2 + (size_t) a.cap * NO;
+    hipLaunchKernelGGL(dia_lookin_kernel, dim3(U), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) U * slot * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    g.pending = 0;
+    bool all = true;
+    for (int u = 0; u < U; u++) {
+        const uint32_t *s = c->h_di_look + (size_t) u * slot;
+        const uint32_t from = g.handed[(size_t) u], to = s[0];
+        const uint32_t rows = a.take && to > from ? std::min(to - from, a.cap) : 0u;
+        if (rows) memcpy(tokens_out + ((size_t) u * g.max_gen + from) * NO, s + 2, (size_t) rows * NO * 4);
+        g.handed[(size_t) u] = from + rows;
+        if (steps_done) steps_done[u] = to;
+        if (done) done[u] = s[1] != 0;
+        all = all && s[1] != 0;
+    }
+    if (a.take) g.unread = 0;
+    g.all_done = all;
+    if (ran) *ran = g.launched;
+    return 0;
+}
+
+extern "C" int tts_hip_dia_gen_begin(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms) {
+    return dia_gen_begin(c, "tts_hip_dia_gen_begin", n_utt, max_gen, codes, sp, uniforms);
+}
+
+extern "C" int tts_hip_dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_launch: not a Dia context (tts_hip_dia_create)");
+    if (!c->dg.active) return set_err("tts_hip_dia_gen_launch: no generation (tts_hip_dia_gen_begin)");
+    return dia_gen_launch(c, n_steps);
+}
+
+extern "C" int tts_hip_dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
+    if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_wait: not a Dia context (tts_hip_dia_create)");
+    if (!c->dg.active) return set_err("tts_hip_dia_gen_wait: no generation (tts_hip_dia_gen_begin)");
+    return dia_gen_wait(c, tokens_out, steps_done, done, ran);
+}
+
+// begin + (launch 16, wait) until every utterance is done or the max_gen + 1 pre-steps are spent
+extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms,
+                                    uint32_t *tokens_out, uint32_t *steps_out) {
+    if (!c || !c->has_dia) return set_err("tts_hip_dia_generate: not a Dia context (tts_hip_dia_create)");
+    if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_generate: context not finalized");
+    if (!codes || !tokens_out || !steps_out) return set_err("tts_hip_dia_generate: null argument");
+    CHK(dia_gen_begin(c, "tts_hip_dia_generate", n_utt, max_gen, codes, sp, uniforms));
+    int rc = 0;
+    while (rc == 0 && !c->dg.all_done && c->dg.launched < max_gen + 1) {
+        rc = dia_gen_launch(c, DIA_LOOP_CHUNK);
+        if (rc == 0) rc = dia_gen_wait(c, tokens_out, steps_out, nullptr, nullptr);
+    }
+    (void) dia_gen_drop(c);
+    return rc;
 }
 
 extern "C" int tts_hip_dia_step(tts_hip_ctx *c, const uint32_t *ids, uint32_t pos, float *logits_out, float *raw_out) {

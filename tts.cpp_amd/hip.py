@@ -90,6 +90,7 @@ EXPORTS = [
     "tts_hip_parler_gen_begin", "tts_hip_parler_gen_launch", "tts_hip_parler_gen_wait", "tts_hip_dac_halo_frames", "tts_hip_dac_decode_windows",
     "tts_hip_snac_halo_frames", "tts_hip_snac_decode_windows", "tts_hip_snac_decode_windows_begin", "tts_hip_snac_decode_windows_end",
     "tts_hip_orpheus_gen_begin", "tts_hip_orpheus_gen_launch", "tts_hip_orpheus_gen_wait",
+    "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
 ]
 
 class Sampling(C.Structure):
@@ -196,6 +197,9 @@ def load_lib():
     L.tts_hip_orpheus_gen_begin.argtypes = [vp, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.POINTER(Sampling), f32p]
     L.tts_hip_orpheus_gen_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_orpheus_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8)]
+    L.tts_hip_dia_gen_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes), C.POINTER(Sampling), f32p]
+    L.tts_hip_dia_gen_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_dia_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p]
     _lib = L
     return L
 
@@ -867,6 +871,32 @@ class DiaEngine:
         self._chk(self.L.tts_hip_dia_generate(self.ctx, n_utt, max_gen, C.byref(codes), sp, up, out.ctypes.data_as(C.POINTER(C.c_uint32)),
                                               steps.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [out[u, :int(steps[u])].copy() for u in range(n_utt)]
+
+    def gen_begin(self, n_utt, max_gen, delay_pattern, bos, eos, pad, max_delay, uniforms=None, top_k=50, top_p=1.0, temperature=1.0, repetition_penalty=1.0):
+        """tts_hip_dia_gen_begin: the arguments of generate(); gen_launch / gen_wait run the loop"""
+        codes = DiaCodes(bos, eos, pad, max_delay)
+        for i, d in enumerate(delay_pattern):
+            codes.delay_pattern[i] = int(d)
+        sp, up = None, None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32)
+            assert u.size >= max_gen * n_utt * self.cfg.n_out
+            sp, up = C.byref(Sampling(top_k, top_p, temperature, repetition_penalty)), u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_dia_gen_begin(self.ctx, n_utt, max_gen, C.byref(codes), sp, up))
+        # cells no gen_wait has written hold a marker, so that a test can tell what each wait handed out
+        self._gen = (np.full((n_utt, max_gen, self.cfg.n_out), 0xFFFFFFFF, dtype=np.uint32), np.zeros(n_utt, dtype=np.uint32), np.zeros(n_utt, dtype=np.uint8))
+
+    def gen_launch(self, n_steps):
+        self._chk(self.L.tts_hip_dia_gen_launch(self.ctx, n_steps))
+
+    def gen_wait(self, take=True):
+        """-> (tokens [n_utt][max_gen][n_out] as handed out so far (a view), sampler calls per utterance, done per utterance, pre-steps run);
+        take=False looks in without taking tokens"""
+        out, steps, done = self._gen
+        ran = C.c_uint32()
+        self._chk(self.L.tts_hip_dia_gen_wait(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)) if take else None, steps.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              done.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(ran)))
+        return out, steps.copy(), done.astype(bool).copy(), ran.value
 
     def step(self, ids, pos, want_raw=False):
         a, ap = _u32(ids)

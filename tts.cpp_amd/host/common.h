@@ -128,7 +128,7 @@ struct tts_generation_runner : tts_runner {
     // on_chunk receives consecutive pieces of the utterance's audio, at most chunk_frames codec frames each (the last one may be shorter);
     // their concatenation equals generate()'s PCM.  The pointer is valid during the call only.  on_chunk returning false stops the
     // generation at the next look-in point; the runner stays usable.  chunk_frames == 0 is an error.  The default generates the whole
-    // utterance and hands it out as one chunk; parler_runner and orpheus_runner stream.  Orpheus' SNAC noise block: with TTS_SNAC_NO_NOISE
+    // utterance and hands it out as one chunk; parler_runner, orpheus_runner and dia_runner stream.  Orpheus' SNAC noise block: with TTS_SNAC_NO_NOISE
     // the chunks concatenate to generate()'s PCM; with noise they are the whole utterance's decode under the same engine's draws laid out
     // frame-major instead of layer-major (same distribution, another realisation; orpheus_runner.h), and a completed call consumes exactly
     // as many draws as generate() would, so later calls see the same engine state either way.

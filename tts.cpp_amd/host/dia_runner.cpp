@@ -1,5 +1,6 @@
 #include "dia_runner.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -80,6 +81,7 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : tts_generation_run
     a.dac_max_frames = hp.max_generation_size;
     a.max_seqs = 1;
     a.flags = TTS_HIP_FLAG_NO_PARLER;
+    dac_halo = tts_hip_dac_halo_frames(&a);
     dac = tts_hip_create(device, &a);
     if (!dac) {
         // the destructor does not run for a constructor that throws (TTS_ABORT under g_tts_throw_on_abort): release the model context
@@ -143,55 +145,100 @@ bool dia_check_stopping(const dia_hparams & hp, std::vector<uint32_t> & audio_to
     return delay_steps == 0;
 }
 
-void dia_adjust_output_tokens(const dia_hparams & hp, const std::vector<uint32_t> & output_tokens, std::vector<uint32_t> & filtered) {
-    const size_t size = output_tokens.size(), nh = hp.n_output_heads;
-    filtered.clear();
-    filtered.reserve(size);
-    for (int i = 0; i < (int) (size / nh) - (int) hp.max_delay; i++) {
+// adjust_output_tokens (model.cpp:787-808) from a cursor.  After `steps` steps the frames i < steps - max_delay can be judged, and judging
+// frame i reads tokens up to step i + max_delay only: what a prefix of the stream yields stays what the whole stream yields.  `judged`
+// frames have been judged by earlier calls; the kept ones of [judged, steps - max_delay) are appended to `kept`.  Returns the new cursor.
+size_t dia_undelay(const dia_hparams & hp, const uint32_t * toks, size_t steps, size_t judged, std::vector<uint32_t> & kept) {
+    const size_t nh = hp.n_output_heads, size = steps * nh;
+    const size_t end = steps > hp.max_delay ? steps - hp.max_delay : 0;
+    for (size_t i = judged; i < end; i++) {
         bool skip_step = false;
         for (size_t ii = 0; ii < nh; ii++) {
-            const size_t next_index = (size_t) i * nh + hp.delay_pattern[ii] * nh + ii;
-            if (next_index > size || output_tokens[next_index] >= hp.audio_vocab_size) { skip_step = true; break; }
+            const size_t next_index = i * nh + hp.delay_pattern[ii] * nh + ii;
+            if (next_index >= size || toks[next_index] >= hp.audio_vocab_size) { skip_step = true; break; }
         }
         if (skip_step) continue;
-        for (size_t ii = 0; ii < nh; ii++) filtered.push_back(output_tokens[(size_t) i * nh + hp.delay_pattern[ii] * nh + ii]);
+        for (size_t ii = 0; ii < nh; ii++) kept.push_back(toks[i * nh + hp.delay_pattern[ii] * nh + ii]);
     }
+    return std::max(end, judged);
 }
 
-// the generation loop on the device (tts_hip_dia_generate).  With a fixed seed every utterance gets the draws a separate generate()
-// call would make (each call seeds its own sampler the same way, so call k draws the same U[0,1) values for every utterance); with
-// seed == 0 (std::random_device per call, the reference's behaviour) separate calls are independently random, so every utterance of the
-// batch draws its own values — as the host loop's per-utterance samplers and the Parler batch path do
-static void dia_device_loop(tts_hip_ctx * lm, const dia_hparams & hp, sampler & proto, uint32_t n, uint32_t max_gen, const generation_configuration & config,
-                            std::vector<std::vector<uint32_t>> & tokens) {
-    const uint32_t nh = hp.n_output_heads;
-    tts_hip_dia_codes codes{};
-    codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
-    for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
-    std::vector<uint32_t> toks((size_t) n * max_gen * nh), steps(n);
-    std::vector<float> u;
-    tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-    if (config.sample) {
-        u.resize((size_t) max_gen * n * nh);
-        std::vector<float> draw(nh);
-        sampler s = proto;
-        s.seed = config.seed; s.n_calls = 0;
-        for (uint32_t k = 0; k < max_gen; k++) {
-            if (config.seed != 0) {
-                s.draw_uniforms(draw.data());
-                for (uint32_t i = 0; i < n; i++) std::copy(draw.begin(), draw.end(), u.begin() + ((size_t) k * n + i) * nh);
-            } else {
-                for (uint32_t i = 0; i < n; i++) s.draw_uniforms(u.data() + ((size_t) k * n + i) * nh);   // a fresh random_device draw per utterance
-            }
+void dia_adjust_output_tokens(const dia_hparams & hp, const std::vector<uint32_t> & output_tokens, std::vector<uint32_t> & filtered) {
+    filtered.clear();
+    filtered.reserve(output_tokens.size());
+    dia_undelay(hp, output_tokens.data(), output_tokens.size() / hp.n_output_heads, 0, filtered);
+}
+
+// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
+// As for Parler (parler_runner.cpp): the codec's samples of frame j depend on the codes of frames [j - h, j + h] only, so once the kept
+// frames [e, f + h) of an utterance are final, a window [e - h, f + h) decoded as an utterance of its own yields the samples of [e, f) that
+// the whole utterance's decode yields.  Frames are counted after the un-delay dropped those with EOS / PAD in them: that is the sequence
+// the codec sees.  run_utterances calls the hook at its look-ins: plan() un-delays what became final and cuts the next windows, emit()
+// decodes them — one codec pass for every utterance, on the codec context's stream while the decoder's next steps run — and hands out.
+static constexpr uint32_t LOOK_IN = 16;   // decode steps between two look-ins (what tts_hip_dia_generate uses)
+
+struct dia_runner::chunker {
+    struct row {
+        std::vector<uint32_t> frames;   // codes of the kept frames that are final [frames][heads]
+        size_t   judged = 0;            // dia_undelay's cursor
+        uint32_t emitted = 0;           // kept frames handed out
+    };
+    dia_runner &   r;
+    const uint32_t chunk_frames;
+    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk;
+    std::vector<row>      rows;
+    std::vector<uint32_t> codes, frames, keep0, keep1, row_of;   // the planned windows: one tts_hip_dac_decode_windows pass
+    chunker(dia_runner & runner, uint32_t chunk_frames_, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk_)
+        : r(runner), chunk_frames(chunk_frames_), on_chunk(on_chunk_) {}
+
+    // the frames of each utterance that became final since the last call, then a window per utterance that has chunks ready: whole chunks
+    // whose right halo is final too, or everything left once the utterance has finished
+    void plan(const std::vector<std::vector<uint32_t>> & toks, const std::vector<bool> & finished) {
+        const uint32_t nh = r.hp.n_output_heads;
+        const uint32_t h = r.dac_halo >= 0 ? (uint32_t) r.dac_halo : r.hp.max_generation_size;   // unknown halo: whole utterances once they are done
+        rows.resize(toks.size());
+        for (uint32_t i = 0; i < toks.size(); i++) {
+            row & w = rows[i];
+            w.judged = dia_undelay(r.hp, toks[i].data(), toks[i].size() / nh, w.judged, w.frames);
+            const uint32_t have = (uint32_t) (w.frames.size() / nh);
+            uint32_t end = w.emitted;
+            if (finished[i]) end = have;
+            else if (have >= w.emitted + h + chunk_frames) end = w.emitted + (have - h - w.emitted) / chunk_frames * chunk_frames;
+            if (end == w.emitted) continue;
+            const uint32_t w0 = w.emitted > h ? w.emitted - h : 0, w1 = std::min(end + h, have);
+            codes.insert(codes.end(), w.frames.begin() + (size_t) w0 * nh, w.frames.begin() + (size_t) w1 * nh);
+            frames.push_back(w1 - w0);
+            keep0.push_back(w.emitted - w0);
+            keep1.push_back(end - w0);
+            row_of.push_back(i);
+            w.emitted = end;
         }
     }
-    if (tts_hip_dia_generate(lm, n, max_gen, &codes, config.sample ? &sp : nullptr, config.sample ? u.data() : nullptr, toks.data(), steps.data()) != 0)
-        TTS_ABORT("tts_hip_dia_generate failed: %s\n", tts_hip_last_error());
-    tokens.assign(n, {});
-    for (uint32_t i = 0; i < n; i++) tokens[i].assign(toks.begin() + (size_t) i * max_gen * nh, toks.begin() + ((size_t) i * max_gen + steps[i]) * nh);
-}
+    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
+    bool emit() {
+        if (row_of.empty()) return true;
+        const uint32_t U = r.hp.up_sampling_factor;
+        size_t total = 0;
+        for (size_t w = 0; w < row_of.size(); w++) total += (size_t) (keep1[w] - keep0[w]) * U;
+        r.pcm.resize(total);
+        hip_check(tts_hip_dac_decode_windows(r.dac, codes.data(), frames.data(), keep0.data(), keep1.data(), (uint32_t) row_of.size(), r.pcm.data()),
+                  "tts_hip_dac_decode_windows");
+        bool more = true;
+        size_t off = 0;
+        for (size_t w = 0; w < row_of.size() && more; w++) {
+            const uint32_t nf = keep1[w] - keep0[w];
+            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
+                more = on_chunk(row_of[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
+            off += (size_t) nf * U;
+        }
+        codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear();
+        return more;
+    }
+};
 
-void dia_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+// what every form of generate() does before the loop: the sampler's settings (n_calls = 0: a seeded sampler draws the sequence of a call of
+// its own) and the step budget
+uint32_t dia_runner::begin_call(const generation_configuration & config) {
     if (!(config.max_tokens == 0 || config.max_tokens > (int) hp.max_delay)) TTS_ABORT("TTS_ASSERT(config.max_tokens == 0 || config.max_tokens > model->max_delay) failed\n");
     smp.temperature = config.temperature;
     smp.repetition_penalty = config.repetition_penalty;
@@ -201,41 +248,130 @@ void dia_runner::generate(const char * sentence, tts_response & output, const ge
     smp.seed = config.seed;
     smp.n_calls = 0;
     uint32_t max_gen = config.max_tokens > (int) hp.max_delay ? (uint32_t) config.max_tokens : hp.max_generation_size;
-    if (max_gen > hp.max_generation_size) max_gen = hp.max_generation_size;   // the self-attention cache holds max_generation_size positions (:300-301)
+    return std::min(max_gen, hp.max_generation_size);   // the self-attention cache holds max_generation_size positions (:300-301)
+}
+
+void dia_runner::encode_single(const char * sentence) {
+    const uint32_t sentence_length = dia_tokenize_sentence(hp, sentence, last_prompt_tokens);
+    last_output_tokens.clear();
+    hip_check(tts_hip_dia_encode(lm, last_prompt_tokens.data(), sentence_length, nullptr), "tts_hip_dia_encode");
+}
+
+void dia_runner::encode_batch(const std::vector<std::string> & sentences) {
+    const uint32_t n = (uint32_t) sentences.size();
+    if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
+    std::vector<uint32_t> prompt;
+    for (uint32_t u = 0; u < n; u++) {
+        const uint32_t len = dia_tokenize_sentence(hp, sentences[u], prompt);
+        hip_check(tts_hip_dia_encode_slot(lm, u, prompt.data(), len, nullptr), "tts_hip_dia_encode_slot");
+    }
+    last_batch_tokens.assign(n, {});
+}
+
+// generate_from_batch (model.cpp:806-870) for the utterances encoded in slots 0..n-1 -> the still-delayed tokens of each.  The device loop
+// (tts_hip_dia_gen_*: check_stopping, the step, the sampler and the delay-pattern feedback replay as one captured graph, the host looks in
+// every 16 steps), or under TTS_HOST_LOOP the reference's shape: logits back every step, sampler::sample and check_stopping here.  With a
+// hook, the look-ins hand out chunked audio.
+// Device loop and a fixed seed: every utterance gets the draws a separate generate() call would make (each call seeds its own sampler the
+// same way, so call k draws the same U[0,1) values for every utterance); with seed == 0 (std::random_device per call, the reference's
+// behaviour) separate calls are independently random, so every utterance of the batch draws its own values — as the host loop's
+// per-utterance samplers and the Parler batch path do.
+std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, chunker * hook) {
+    const uint32_t nh = hp.n_output_heads;
+    std::vector<std::vector<uint32_t>> toks(n);
+    std::vector<bool> finished(n, false);
+    bool go = true;   // false: the hook's caller stopped the generation
+    if (!getenv("TTS_HOST_LOOP")) {
+        tts_hip_dia_codes codes{};
+        codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
+        for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
+        std::vector<float> u;
+        const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+        if (config.sample) {   // uniforms [call][utterance][head]
+            u.resize((size_t) max_gen * n * nh);
+            std::vector<float> draw(nh);
+            sampler s = smp;
+            s.seed = config.seed; s.n_calls = 0;
+            for (uint32_t k = 0; k < max_gen; k++) {
+                if (config.seed != 0) {
+                    s.draw_uniforms(draw.data());
+                    for (uint32_t i = 0; i < n; i++) std::copy(draw.begin(), draw.end(), u.begin() + ((size_t) k * n + i) * nh);
+                } else {
+                    for (uint32_t i = 0; i < n; i++) s.draw_uniforms(u.data() + ((size_t) k * n + i) * nh);   // a fresh random_device draw per utterance
+                }
+            }
+        }
+        hip_check(tts_hip_dia_gen_begin(lm, n, max_gen, &codes, config.sample ? &sp : nullptr, config.sample ? u.data() : nullptr), "tts_hip_dia_gen_begin");
+        std::vector<uint32_t> buf((size_t) n * max_gen * nh), steps(n);
+        std::vector<uint8_t>  done(n);
+        uint32_t ran = 0;
+        hip_check(tts_hip_dia_gen_launch(lm, LOOK_IN), "tts_hip_dia_gen_launch");
+        for (;;) {
+            if (hook) go = hook->emit();   // the codec windows of the last look-in, while the steps run
+            hip_check(tts_hip_dia_gen_wait(lm, buf.data(), steps.data(), done.data(), &ran), "tts_hip_dia_gen_wait");
+            bool all = true;
+            for (uint32_t i = 0; i < n; i++) {
+                const uint32_t * b = buf.data() + (size_t) i * max_gen * nh;
+                toks[i].insert(toks[i].end(), b + toks[i].size(), b + (size_t) steps[i] * nh);
+                finished[i] = done[i] != 0;
+                all = all && finished[i];
+            }
+            if (all || ran >= max_gen + 1 || !go) break;
+            hip_check(tts_hip_dia_gen_launch(lm, LOOK_IN), "tts_hip_dia_gen_launch");
+            if (hook) hook->plan(toks, finished);
+        }
+    } else {
+        // per utterance: its own sampler state (n separate generate() calls would each reset and seed theirs), tokens, countdown.  A hook's
+        // windows are planned and decoded at the same look-in points, without overlap.
+        std::vector<sampler> smps(n, smp);
+        for (sampler & s : smps) s.reset();
+        std::vector<std::vector<uint32_t>> audio(n, std::vector<uint32_t>(nh, hp.bos_token_id));
+        std::vector<uint32_t> pos(n, 0), ids((size_t) n * nh);
+        std::vector<int>      delay(n, -1);
+        std::vector<float>    lg((size_t) n * nh * hp.output_vocab_size);
+        for (uint32_t step = 1; go; step++) {
+            // check_stopping (:767-785) per utterance before each decode, as generate_from_batch's while condition (:817)
+            bool any = false;
+            for (uint32_t u = 0; u < n; u++) {
+                if (!finished[u] && dia_check_stopping(hp, audio[u], pos[u], max_gen, delay[u])) finished[u] = true;
+                any = any || !finished[u];
+            }
+            if (!any) break;
+            for (uint32_t u = 0; u < n; u++) std::copy(audio[u].begin(), audio[u].end(), ids.begin() + (size_t) u * nh);
+            // a finished utterance keeps its rows in the step (lock-step shapes stay fixed); its logits are ignored and its position stays
+            hip_check(tts_hip_dia_step_batch(lm, n, nullptr, ids.data(), pos.data(), lg.data(), nullptr), "tts_hip_dia_step_batch");
+            for (uint32_t u = 0; u < n; u++) {
+                if (finished[u]) continue;
+                std::vector<uint32_t> & out = toks[u];
+                smps[u].sample(lg.data() + (size_t) u * nh * hp.output_vocab_size, out);
+                pos[u] += 1;
+                const uint32_t * last = out.data() + out.size() - nh;
+                for (uint32_t i = 0; i < nh; i++) audio[u][i] = pos[u] > i ? last[i] : hp.bos_token_id;
+            }
+            if (hook && step % LOOK_IN == 0) {
+                hook->plan(toks, finished);
+                go = hook->emit();
+            }
+        }
+    }
+    if (hook && go) {   // what is left once every utterance is done
+        finished.assign(n, true);
+        hook->plan(toks, finished);
+        (void) hook->emit();
+    }
+    return toks;
+}
+
+void dia_runner::generate(const char * sentence, tts_response & output, const generation_configuration & config) {
+    const uint32_t max_gen = begin_call(config);
     output.data = nullptr;
     output.n_outputs = 0;
-
-    const uint32_t sentence_length = dia_tokenize_sentence(hp, sentence, last_prompt_tokens);
-    smp.reset();
-    hip_check(tts_hip_dia_encode(lm, last_prompt_tokens.data(), sentence_length, nullptr), "tts_hip_dia_encode");
-
-    // generate_from_batch (:810-833)
-    const uint32_t nh = hp.n_output_heads;
-    std::vector<uint32_t> & out = last_output_tokens;
-    out.clear();
-    out.reserve((size_t) max_gen * nh);
-    std::vector<uint32_t> audio_tokens(nh, hp.bos_token_id);
-    uint32_t current_position = 0;
-    int      delay_steps = -1;
-    if (!getenv("TTS_HOST_LOOP")) {
-        // check_stopping, the step, the sampler and the delay-pattern feedback replay as one captured graph; the host loop below is
-        // the reference's shape (logits back every step, sampler::sample here) and stays for TTS_HOST_LOOP=1
-        std::vector<std::vector<uint32_t>> t;
-        dia_device_loop(lm, hp, smp, 1, max_gen, config, t);
-        out = t[0];
-        delay_steps = 0;
-    }
-    while (delay_steps != 0 && !dia_check_stopping(hp, audio_tokens, current_position, max_gen, delay_steps)) {
-        hip_check(tts_hip_dia_step(lm, audio_tokens.data(), current_position, logits.data(), nullptr), "tts_hip_dia_step");
-        smp.sample(logits.data(), out);
-        current_position += 1;
-        const uint32_t * last = out.data() + out.size() - nh;
-        for (uint32_t i = 0; i < nh; i++) audio_tokens[i] = current_position > i ? last[i] : hp.bos_token_id;
-    }
+    encode_single(sentence);
+    last_output_tokens = std::move(run_utterances(1, max_gen, config, nullptr)[0]);
 
     std::vector<uint32_t> filtered;
-    dia_adjust_output_tokens(hp, out, filtered);
-    const uint32_t frames = (uint32_t) (filtered.size() / nh);
+    dia_adjust_output_tokens(hp, last_output_tokens, filtered);
+    const uint32_t frames = (uint32_t) (filtered.size() / hp.n_output_heads);
     if (frames == 0) return;
     pcm.assign((size_t) frames * hp.up_sampling_factor, 0.0f);
     hip_check(tts_hip_dac_decode(dac, filtered.data(), frames, pcm.data()), "tts_hip_dac_decode");
@@ -248,49 +384,9 @@ void dia_runner::generate_batch(const std::vector<std::string> & sentences, std:
     outputs.assign(n, tts_response{});
     if (n == 0) return;
     if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
-    if (!(config.max_tokens == 0 || config.max_tokens > (int) hp.max_delay)) TTS_ABORT("TTS_ASSERT(config.max_tokens == 0 || config.max_tokens > model->max_delay) failed\n");
-    uint32_t max_gen = config.max_tokens > (int) hp.max_delay ? (uint32_t) config.max_tokens : hp.max_generation_size;
-    if (max_gen > hp.max_generation_size) max_gen = hp.max_generation_size;
-
-    // per utterance: its own sampler state (n separate generate() calls would each reset and seed theirs), tokens, countdown
-    std::vector<sampler> smps(n, smp);
-    std::vector<std::vector<uint32_t>> prompts(n);
-    for (uint32_t u = 0; u < n; u++) {
-        sampler & s = smps[u];
-        s.temperature = config.temperature; s.repetition_penalty = config.repetition_penalty; s.do_sample = config.sample;
-        s.top_k = (uint32_t) config.top_k; s.top_p = config.top_p; s.seed = config.seed; s.n_calls = 0;
-        s.reset();
-        const uint32_t len = dia_tokenize_sentence(hp, sentences[u], prompts[u]);
-        hip_check(tts_hip_dia_encode_slot(lm, u, prompts[u].data(), len, nullptr), "tts_hip_dia_encode_slot");
-    }
-    last_batch_tokens.assign(n, {});
-    std::vector<std::vector<uint32_t>> audio(n, std::vector<uint32_t>(nh, hp.bos_token_id));
-    std::vector<uint32_t> pos(n, 0), ids((size_t) n * nh);
-    std::vector<int>      delay(n, -1);
-    std::vector<bool>     done(n, false);
-    std::vector<float>    lg((size_t) n * nh * hp.output_vocab_size);
-    const bool device_loop = !getenv("TTS_HOST_LOOP");
-    if (device_loop) dia_device_loop(lm, hp, smp, n, max_gen, config, last_batch_tokens);
-    for (; !device_loop;) {
-        // check_stopping (:767-785) per utterance before each decode, as generate_from_batch's while condition (:817)
-        bool any = false;
-        for (uint32_t u = 0; u < n; u++) {
-            if (!done[u] && dia_check_stopping(hp, audio[u], pos[u], max_gen, delay[u])) done[u] = true;
-            any = any || !done[u];
-        }
-        if (!any) break;
-        for (uint32_t u = 0; u < n; u++) std::copy(audio[u].begin(), audio[u].end(), ids.begin() + (size_t) u * nh);
-        // a finished utterance keeps its rows in the step (lock-step shapes stay fixed); its logits are ignored and its position stays
-        hip_check(tts_hip_dia_step_batch(lm, n, nullptr, ids.data(), pos.data(), lg.data(), nullptr), "tts_hip_dia_step_batch");
-        for (uint32_t u = 0; u < n; u++) {
-            if (done[u]) continue;
-            std::vector<uint32_t> & out = last_batch_tokens[u];
-            smps[u].sample(lg.data() + (size_t) u * nh * hp.output_vocab_size, out);
-            pos[u] += 1;
-            const uint32_t * last = out.data() + out.size() - nh;
-            for (uint32_t i = 0; i < nh; i++) audio[u][i] = pos[u] > i ? last[i] : hp.bos_token_id;
-        }
-    }
+    const uint32_t max_gen = begin_call(config);
+    encode_batch(sentences);
+    last_batch_tokens = run_utterances(n, max_gen, config, nullptr);
 
     std::vector<uint32_t> codes, frames(n);
     for (uint32_t u = 0; u < n; u++) {
@@ -309,4 +405,26 @@ void dia_runner::generate_batch(const std::vector<std::string> & sentences, std:
         outputs[u].n_outputs = (size_t) frames[u] * hp.up_sampling_factor;
         off += outputs[u].n_outputs;
     }
+}
+
+void dia_runner::generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                                  const std::function<bool(const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_chunked: chunk_frames must be >= 1\n");
+    const uint32_t max_gen = begin_call(config);
+    encode_single(sentence);
+    const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); };
+    chunker hook{*this, chunk_frames, cb};
+    last_output_tokens = std::move(run_utterances(1, max_gen, config, &hook)[0]);
+}
+
+void dia_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                        const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_batch_chunked: chunk_frames must be >= 1\n");
+    const uint32_t n = (uint32_t) sentences.size();
+    if (n == 0) return;
+    if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
+    const uint32_t max_gen = begin_call(config);
+    encode_batch(sentences);
+    chunker hook{*this, chunk_frames, on_chunk};
+    last_batch_tokens = run_utterances(n, max_gen, config, &hook);
 }

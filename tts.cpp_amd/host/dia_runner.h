@@ -6,6 +6,7 @@
 // check_stopping, un-delay, DAC.  The ggml graphs inside decode() and dac_runner::run() are replaced by tts_hip_dia_* and
 // tts_hip_dac_decode; tokenisation, sampling and the stopping logic stay on the host as in the reference.
 #pragma once
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -37,6 +38,10 @@ uint32_t dia_tokenize_sentence(const dia_hparams & hp, std::string sentence, std
 bool     dia_check_stopping(const dia_hparams & hp, std::vector<uint32_t> & audio_tokens, uint32_t current_position, uint32_t max_generation_size,
                             int & delay_steps);                                                                                             // :767-785
 void     dia_adjust_output_tokens(const dia_hparams & hp, const std::vector<uint32_t> & output_tokens, std::vector<uint32_t> & filtered);   // :787-808
+// the same rule from a cursor: toks [steps][heads] is the stream so far, `judged` frames were judged by earlier calls; appends the kept
+// frames that became final (frame i is final once step i + max_delay exists) to `kept` and returns the new cursor.  A prefix of a stream
+// yields a prefix of the whole stream's frames; dia_adjust_output_tokens is this from zero over everything.
+size_t   dia_undelay(const dia_hparams & hp, const uint32_t * toks, size_t steps, size_t judged, std::vector<uint32_t> & kept);
 
 struct dia_runner final : tts_generation_runner {
     dia_runner(const dia_hparams & hp, int device);
@@ -50,6 +55,13 @@ struct dia_runner final : tts_generation_runner {
     // load time (tts_load_options / TTS_HIP_MAX_SEQS).  Greedy results equal n separate generate() calls.
     void generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
                         const generation_configuration & config) override;
+    // chunked audio (common.h): PCM in pieces of at most chunk_frames kept codec frames while the decoder is still running; the pieces
+    // concatenate to generate()'s / generate_batch()'s audio, last_output_tokens / last_batch_tokens hold what was generated (also after
+    // on_chunk stopped the call), and a fixed seed draws the uniforms of the one-call forms
+    void generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
+                          const std::function<bool(const float *, size_t)> & on_chunk) override;
+    void generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) override;
     uint32_t batch_capacity() const override { return max_seqs; }
     uint32_t max_seqs = 1;
     std::vector<std::vector<uint32_t>> last_batch_tokens;
@@ -61,4 +73,13 @@ struct dia_runner final : tts_generation_runner {
     tts_hip_ctx *      lm = nullptr;    // encoder + decoder context
     tts_hip_ctx *      dac = nullptr;   // codec context
     std::vector<float> pcm, logits;
+    int                dac_halo = -1;   // tts_hip_dac_halo_frames of the codec: frames of context a chunk's window needs on each side
+
+  private:
+    struct chunker;
+    uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
+    void     encode_single(const char * sentence);
+    void     encode_batch(const std::vector<std::string> & sentences);
+    // the one generation loop under generate, generate_batch and their chunked forms
+    std::vector<std::vector<uint32_t>> run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, chunker * hook);
 };

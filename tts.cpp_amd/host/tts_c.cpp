@@ -324,6 +324,22 @@ extern "C" int64_t tts_c_dia_adjust_output_tokens(const uint32_t * tokens, uint6
     return (int64_t) out.size();
 }
 
+extern "C" int64_t tts_c_dia_final_frames(const uint32_t * tokens, uint64_t n_steps, uint32_t audio_vocab, uint32_t max_delay, uint64_t piece, uint32_t * out,
+                                          uint64_t cap_frames) {
+    dia_hparams hp;
+    hp.audio_vocab_size = audio_vocab; hp.max_delay = max_delay;
+    std::vector<uint32_t> f;
+    size_t judged = 0;
+    if (piece == 0) piece = n_steps ? n_steps : 1;
+    for (uint64_t s = std::min<uint64_t>(piece, n_steps);; s = std::min<uint64_t>(s + piece, n_steps)) {
+        judged = dia_undelay(hp, tokens, (size_t) s, judged, f);
+        if (s >= n_steps) break;
+    }
+    const uint64_t frames = f.size() / hp.n_output_heads;
+    if (out) copy_u32(out, f.data(), (size_t) (frames < cap_frames ? frames : cap_frames) * hp.n_output_heads);
+    return (int64_t) frames;
+}
+
 // ---- Kokoro host logic (host/kokoro_runner.h) -------------------------------------------------------------------
 std::vector<std::vector<uint32_t>> kokoro_clause_chunks(const kokoro_hparams & hp, const single_pass_tokenizer & tok, const std::string & phonemes);
 

@@ -31,7 +31,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_pool_create", "tts_c_pool_set_text_encoder", "tts_c_pool_set_continuous", "tts_c_pool_set_continuous_yield_ms", "tts_c_pool_admitted_in_flight", "tts_c_pool_conditional_prompt", "tts_c_pool_submit", "tts_c_pool_wait", "tts_c_pool_release", "tts_c_pool_stats", "tts_c_pool_load_stats", "tts_c_pool_free", "tts_c_set_load_options", "tts_c_set_load_options_ex", "tts_c_runner_device_context", "tts_c_runner_tokenize",
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
-           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames"]
+           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -112,6 +112,8 @@ def load_lib():
         L.tts_c_generate_batch_chunked.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
         L.tts_c_parler_final_frames.restype = C.c_int64
         L.tts_c_parler_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
+        L.tts_c_dia_final_frames.restype = C.c_int64
+        L.tts_c_dia_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64]
         _lib = L
     return _lib
 
@@ -328,6 +330,19 @@ def dia_adjust_output_tokens(tokens, audio_vocab, max_delay):
     out = np.zeros(a.size, dtype=np.uint32)
     n = load_lib().tts_c_dia_adjust_output_tokens(a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, audio_vocab, max_delay, out.ctypes.data_as(C.POINTER(C.c_uint32)))
     return out[:n].reshape(-1, 9)
+
+
+def dia_final_frames(tokens, audio_vocab, max_delay, piece=0):
+    """the Dia runner's incremental un-delay (dia_undelay) on delayed tokens [steps][9], fed in pieces of `piece` steps (0: all at once):
+    the kept frames that are final after these steps"""
+    t = np.ascontiguousarray(tokens, dtype=np.uint32).reshape(-1, 9)
+    steps = t.shape[0]
+    L = load_lib()
+    tp = t.ctypes.data_as(C.POINTER(C.c_uint32))
+    n = L.tts_c_dia_final_frames(tp, steps, audio_vocab, max_delay, piece, None, 0)
+    out = np.zeros((max(n, 1), 9), dtype=np.uint32)
+    L.tts_c_dia_final_frames(tp, steps, audio_vocab, max_delay, piece, out.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+    return out[:n]
 
 
 def _qparams(qtype, n_threads=1, output_heads=False, text_embeddings=False, cross_attn_kv=False, dac_f16=False, non_quantizable_f16=False):
