@@ -45,9 +45,14 @@ int           tts_c_generate(tts_c_runner *r, const char *text, const tts_c_conf
  * must have been loaded with TTS_HIP_MAX_SEQS >= n in the environment. */
 int           tts_c_generate_batch(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, const float **data,
                                    size_t *n_outputs);
-/* Extension: any number of utterances through ONE continuous-batching session of the runner (tts_generation_runner::generate_stream): at most
- * max_seqs - 1 generate at a time, and a row freed by an utterance that finishes is refilled from texts[] at the next look-in point (every 32
- * decode steps) instead of idling until the longest one is done.  Same outputs as n generate() calls; data[i] valid until the next call. */
+/* Extension: any number of utterances through ONE continuous-batching session of the runner (tts_generation_runner::generate_stream): a row
+ * freed by an utterance that finishes is refilled from texts[] at the next look-in point instead of idling until the longest one is done.
+ * Parler-TTS and Orpheus have a session.  Parler-TTS: at most max_seqs - 1 utterances generate at a time (one cache slot pads the forward), a
+ * look-in every 32 decode steps.  Orpheus: max_seqs utterances, a look-in every 28 ids (four SNAC frames) of a device-driven loop; a sampled
+ * session needs the device sampler (top_k 1..64, top_p > 0) and is refused otherwise.  Dia and Kokoro have no session: their texts go through
+ * generate_batch in groups.  Same outputs as n generate() calls; data[i] valid until the next call.
+ * Orpheus' SNAC noise block: the codec runs when an utterance finishes, so the never-reseeded noise engine's draws follow the order in which
+ * utterances finish, not the order of texts[]; with TTS_SNAC_NO_NOISE every audio is bit for bit that of a tts_c_generate call of its own. */
 int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, const float **data,
                                     size_t *n_outputs);
 /* Extension: chunked audio (tts_generation_runner::generate_chunked).  fn receives the utterance's PCM in consecutive pieces of at most

@@ -289,6 +289,38 @@ int tts_hip_orpheus_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *n
  * repetition_counts, read and updated in place (may be NULL when repetition_penalty == 1) */
 int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const tts_hip_sampling *sampling, float uniform, int32_t *last_id,
                                   uint32_t *rep_count, uint32_t *token_out);
+/* Continuous session: a lock-step generation that admits utterances into free cache slots while the others are running, on a device-driven loop.
+ * The per-slot state (ids so far, finished flag, latest id and position, sampler state, uniforms) lives on the device; a run of k steps is
+ * k x (forward, row-batched selection, row advance) enqueued back to back with no copy and no synchronise in between.
+ *   begin    n_slots <= max_seqs cache slots, at most max_new ids per utterance, the stopping token, the sampler (sampling NULL: sampler::max; else the
+ *            limits of tts_hip_orpheus_generate_sampled; the repetition-penalty table is staged once)
+ *   admit    n utterances into free slots, between two runs: prompts back to back (n_prompt[i] ids each), uniforms [n][max_new] for a sampled session
+ *            (utterance i's k-th sampler call draws uniforms[i * max_new + k]), else NULL.  Each slot's sampler state and counts are reset, its
+ *            prompt runs, and the first id is selected from the prompt's last row, as gen_begin does.
+ *   run      stages the live rows once, enqueues n_steps steps, synchronises and reads the slots' counts and flags in one copy.  Slots that finished
+ *            (stopping token, max_new ids, or the end of the cache) — inside the run, or at their admission (max_new 0 or 1, a first id that stops) —
+ *            are reported with their id counts and leave the rows of the next run.  A row that finishes inside a run idles as padding until the run
+ *            ends: nothing it selects is emitted, its sampler state stands still.  With no live rows nothing is launched.
+ *   collect  the first `count` ids of a reported slot, before that slot is admitted again
+ *   end      ends the session
+ * An utterance's ids are those of tts_hip_orpheus_generate_batch for the same prompt, that is those of its own one-sequence generation
+ * (tests/test_gpu_orpheus_stream.py).  Key split: the attention of step i of a run is sized by max over the live rows of (position at the look-in)
+ * + i + 1, capped at n_ctx: the exact longest row as long as nobody finishes, an upper bound once someone has.  Below 256 keys that bound selects one
+ * key split, as in generate_batch; beyond, the split count follows the longest live row exactly as generate_batch does today, and the bound can
+ * select another count than generate_batch's exact length would for the same rows (another association of the same softmax).
+ * Between begin and end every other tts_hip_orpheus_* generation call on the context (decode, step_batch, sample_logits, generate_*, gen_begin,
+ * gen_launch) is refused with an error, as in the window between a gen_launch and its gen_wait; begin is refused in that window and while a
+ * gen_* generation has unfinished utterances.  Every misuse (a busy slot, a slot >= n_slots, collect on a slot that has not been reported or for
+ * more ids than it produced, n_slots > max_seqs, a prompt that does not fit) returns non-zero before anything is launched. */
+int tts_hip_orpheus_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sampling);
+int tts_hip_orpheus_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt, const float *uniforms);
+int tts_hip_orpheus_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts);
+int tts_hip_orpheus_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t count, uint32_t *tokens_out);
+int tts_hip_orpheus_stream_end(tts_hip_ctx *ctx);
+/* the session's row-batched selection alone on caller-supplied logits [n_rows][vocab_size] (n_rows <= max_seqs), for parity tests: per row the contract
+ * of tts_hip_orpheus_sample_logits with uniforms[r], last_id[r], rep_count[r]; sampling NULL: sampler::max per row (uniforms / state may be NULL) */
+int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *ctx, uint32_t n_rows, const float *logits, const tts_hip_sampling *sampling, const float *uniforms, int32_t *last_id,
+                                       uint32_t *rep_count, uint32_t *tokens_out);
 
 /* ---- Dia encoder + decoder step (src/models/dia/model.cpp) --------------------------------------------------------
  * Device side of dia_runner::decode (:730-757): create, tts_hip_upload every "dia.*" tensor (names

@@ -1,0 +1,181 @@
+"""Orpheus-3B Q4_0 (the synthetic shapes of secondary_bench.py): the host-driven lock-step loop against the continuous session.
+
+  per-step time   tts_hip_orpheus_gen_launch (host-driven: three copies, two synchronises and, when sampling, up to three launches per row in
+                  every step) against tts_hip_orpheus_stream_run (device-driven: forward, row-batched selection and row advance enqueued back
+                  to back) at 8 and 32 rows, greedy and sampled (top_k 50)
+  ragged mix      24 utterances at 8 slots whose lengths spread over 10:1 (RAGGED_LENGTHS): once as consecutive generate_batch groups of 8,
+                  once through one session with a look-in every 28 steps; tokens/s and the share of slot-steps that carried a live utterance.
+                  A pilot run looks for a stopping id whose first occurrences spread the lengths that way; when the greedy ids of the random
+                  weights offer none (they did not on the recorded runs), the lengths are set through the
+                  other stopping condition the two loops share, the end of the cache: a context of RAGGED_CTX positions and prompts of
+                  RAGGED_CTX + 1 - length ids.
+
+A build without the session (hip.OrpheusEngine has no stream_begin) runs the generate_batch / gen_launch legs only: that is how
+orpheus_stream_throughput_parent_before.json was made.  Usage: python profiles/orpheus_stream_bench.py [--out FILE] [--reps N]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+import tts_cpp_amd  # noqa: E402,F401
+from tts_cpp_amd import gguf, hip, synth  # noqa: E402
+import secondary_bench as sb  # noqa: E402
+
+NO_STOP = 0xFFFFFFFF
+SMP = dict(top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0)   # the default generation_configuration
+STEPS, WARM = 56, 8
+LOOK_IN = 28            # orpheus_runner's look-in interval
+N_RAGGED, SLOTS, CAP = 24, 8, 512
+RAGGED_CTX = 448
+RAGGED_LENGTHS = [40, 400, 120, 60, 280, 80, 200, 48, 360, 100, 160, 44, 240, 72, 320, 56, 140, 400, 90, 180, 52, 300, 64, 220]
+
+
+def med(v):
+    return float(np.median(v))
+
+
+def step_times(eng, B, prompts, uni, have_session, reps):
+    out = {}
+    for mode in ("greedy", "sampled"):
+        kw = dict(uniforms=uni[:, :WARM + STEPS + 1], **SMP) if mode == "sampled" else {}
+        host, dev = [], []
+        for _ in range(reps):
+            eng.gen_begin(prompts, WARM + STEPS + 1, NO_STOP, **kw)
+            eng.gen_launch(WARM)
+            eng.gen_wait()
+            t = time.perf_counter()
+            eng.gen_launch(STEPS)
+            eng.gen_wait()
+            host.append((time.perf_counter() - t) / STEPS * 1e3)
+            eng.gen_launch(1)
+            assert all(eng.gen_wait()[1])
+        out[mode] = {"host_driven_gen_launch_ms_per_step": round(med(host), 4), "host_driven_runs_ms": [round(x, 4) for x in host]}
+        if not have_session:
+            continue
+        for _ in range(reps):
+            eng.stream_begin(B, WARM + STEPS + 2, NO_STOP, sampled=mode == "sampled", **SMP)
+            eng.stream_admit(list(range(B)), prompts, uni if mode == "sampled" else None)
+            assert eng.stream_run(WARM) == []
+            t = time.perf_counter()
+            fin = eng.stream_run(STEPS)
+            dev.append((time.perf_counter() - t) / STEPS * 1e3)
+            assert fin == []
+            eng.stream_end()
+        out[mode].update({"device_driven_stream_run_ms_per_step": round(med(dev), 4), "device_driven_runs_ms": [round(x, 4) for x in dev],
+                          "device_over_host": round(med(dev) / med(host), 4)})
+    return out
+
+
+def pick_stop(pilot):
+    """the id whose first occurrences give lengths closest to a 10:1 spread (10th / 90th percentile) over all utterances"""
+    best, best_score = None, None
+    for tok in sorted({int(t) for ids in pilot for t in ids}):
+        lens = np.array([(list(ids).index(tok) + 1) if tok in ids else len(ids) for ids in pilot], dtype=np.float64)
+        if lens.min() < 8:
+            continue
+        ratio = np.percentile(lens, 90) / np.percentile(lens, 10)
+        score = abs(np.log(ratio / 10.0))
+        if best_score is None or score < best_score:
+            best, best_score = tok, score
+    return best
+
+
+def ragged(eng, prompts, stop, how, have_session, reps):
+    res = {"lengths_set_by": how, "stop_id": stop, "max_new": CAP, "utterances": N_RAGGED, "slots": SLOTS}
+    ts, got = [], None
+    for _ in range(reps):
+        t = time.perf_counter()
+        got = []
+        for g0 in range(0, N_RAGGED, SLOTS):
+            got += [ids.tolist() for ids in eng.generate_batch(prompts[g0:g0 + SLOTS], CAP, stop)]
+        ts.append(time.perf_counter() - t)
+    lens = [len(g) for g in got]
+    total = sum(lens)
+    # a group holds its 8 slots until its longest utterance ends; an utterance's first id comes with its prompt, the others take a step each
+    slot_steps = sum(SLOTS * (max(lens[g0:g0 + SLOTS]) - 1) for g0 in range(0, N_RAGGED, SLOTS))
+    res["lengths"] = lens
+    res["generate_batch_groups"] = {"seconds": round(med(ts), 4), "runs_s": [round(x, 4) for x in ts], "tokens_per_s": round(total / med(ts), 1),
+                                    "live_share_of_slot_steps": round((total - N_RAGGED) / slot_steps, 4)}
+    if not have_session:
+        return res
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        eng.stream_begin(SLOTS, CAP, stop)
+        free, slot_utt, out, nxt, runs = list(range(SLOTS)), {}, [None] * N_RAGGED, 0, 0
+        while nxt < N_RAGGED or slot_utt:
+            while nxt < N_RAGGED and free:
+                s = free.pop(0)
+                eng.stream_admit([s], [prompts[nxt]])
+                slot_utt[s] = nxt
+                nxt += 1
+            fin = eng.stream_run(LOOK_IN)
+            runs += 1
+            for s, cnt in fin:
+                out[slot_utt.pop(s)] = eng.stream_collect(s, cnt).tolist()
+                free.append(s)
+        eng.stream_end()
+        ts.append(time.perf_counter() - t)
+    slens = [len(o) for o in out]
+    res["session"] = {"seconds": round(med(ts), 4), "runs_s": [round(x, 4) for x in ts], "tokens_per_s": round(sum(slens) / med(ts), 1), "look_in_steps": LOOK_IN,
+                      "runs": runs, "live_share_of_slot_steps": round((sum(slens) - N_RAGGED) / (SLOTS * LOOK_IN * runs), 4),
+                      "utterances_with_generate_batch_ids": sum(a == b for a, b in zip(out, got)), "lengths": slens,
+                      "speedup_over_groups": round(res["generate_batch_groups"]["seconds"] / med(ts), 4)}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(HERE, "orpheus_stream_throughput.json"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--rows", default="8,32")
+    args = ap.parse_args()
+    have_session = hasattr(hip.OrpheusEngine, "stream_begin")
+    cfg = synth.orpheus_3b(ctx=1024, weight_type=gguf.Q4_0)
+    rng = np.random.default_rng(7)
+    tensors, _ = sb.orpheus_tensors(cfg, rng)
+    model = sb._Model(cfg, tensors)
+    out = {"setup": {"model": "synthetic Orpheus-3B (28 x 3072, 24 / 8 heads x 128, ffn 8192, 156 940 logits), Q4_0, n_ctx 1024", "prompt_ids": 32, "timed_steps": STEPS,
+                     "warm_steps": WARM, "reps": args.reps, "sampling": SMP, "session": have_session, "timing": "host wall clock around the blocking calls, median of reps"},
+           "per_step": {}, "ragged_mix": {}}
+    prng = np.random.default_rng(11)
+    for B in [int(x) for x in args.rows.split(",")]:
+        eng = hip.OrpheusEngine(cfg, max_seqs=B)
+        eng.load(model)
+        prompts = [prng.integers(0, cfg.vocab, 32).astype(np.uint32) for _ in range(B)]
+        uni = prng.random((B, WARM + STEPS + 2), dtype=np.float32)
+        eng.generate_batch(prompts, 4, NO_STOP)
+        out["per_step"][str(B)] = step_times(eng, B, prompts, uni, have_session, args.reps)
+        print(B, json.dumps(out["per_step"][str(B)]), flush=True)
+        if B == SLOTS:
+            rp = [prng.integers(0, cfg.vocab, 32).astype(np.uint32) for _ in range(N_RAGGED)]
+            pilot = []
+            for g0 in range(0, N_RAGGED, SLOTS):
+                pilot += [ids.tolist() for ids in eng.generate_batch(rp[g0:g0 + SLOTS], CAP, NO_STOP)]
+            stop = pick_stop(pilot)
+            if stop is not None:
+                out["ragged_mix"] = ragged(eng, rp, stop, "a stopping id chosen from the pilot run", have_session, args.reps)
+            else:
+                eng.close()
+                cfg2 = synth.orpheus_3b(ctx=RAGGED_CTX, weight_type=gguf.Q4_0)
+                eng = hip.OrpheusEngine(cfg2, max_seqs=B)
+                eng.load(sb._Model(cfg2, tensors))
+                rp = [prng.integers(0, cfg.vocab, RAGGED_CTX + 1 - n).astype(np.uint32) for n in RAGGED_LENGTHS]
+                out["ragged_mix"] = ragged(eng, rp, NO_STOP, "the end of a cache of %d positions (the pilot run found no usable stopping id)" % RAGGED_CTX, have_session, args.reps)
+                assert out["ragged_mix"]["lengths"] == RAGGED_LENGTHS
+            print("ragged", json.dumps(out["ragged_mix"]), flush=True)
+        eng.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -958,6 +958,229 @@ static __global__ __launch_bounds__(1024) void topk_sample_kernel(const unsigned
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The selection for the rows of a continuous session (tts_hip_orpheus_stream_*): the kernels above with the row as a grid dimension.
+// Row r stands for cache slot s = row_slot[r] (row_slot == NULL: slot0 + r) and reads that slot's sampler state smp[3 s ..] = {last id,
+// repetition count, call counter} and its stretch of the uniforms (uniforms + s * uni_stride).  slot_state (may be NULL) is the session's
+// per-slot record {count, finished, latest id, position}: a row whose slot is finished selects nothing and its state does not move.
+// Per row the operations and their order are those of the one-row kernels, statement for statement: the ids are bit-identical to n one-row
+// calls (tests/test_gpu_orpheus_stream.py).  cand: [rows][TOPK_PARTS][TOPK_MAXK], total: [rows], token: [rows].
+// ------------------------------------------------------------------------------------------------
+#define LLAMA_SLOT_STATE 4   // uint32 per slot: [0] ids so far, [1] finished, [2] latest id, [3] position of the latest forward row
+__device__ __forceinline__ uint32_t rows_slot(const uint32_t *row_slot, int slot0, int r) { return row_slot ? row_slot[r] : (uint32_t) (slot0 + r); }
+__device__ __forceinline__ bool rows_finished(const uint32_t *slot_state, uint32_t s) { return slot_state && slot_state[(size_t) s * LLAMA_SLOT_STATE + 1] != 0; }
+
+static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const uint32_t *row_slot, int slot0,
+                                                                 const uint32_t *slot_state) {
+    __shared__ float bv[4];
+    __shared__ uint32_t bi[4];
+    if (rows_finished(slot_state, rows_slot(row_slot, slot0, blockIdx.y))) return;
+    const float *lg = logits + (int64_t) blockIdx.y * ld;
+    const int chunk = (V + ARGMAX_PARTS - 1) / ARGMAX_PARTS;
+    const int i0 = blockIdx.x * chunk, i1 = min(V, i0 + chunk);
+    float best = -INFINITY;
+    uint32_t besti = 0xffffffffu;
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        const float v = lg[i];
+        if (v > best) { best = v; besti = (uint32_t) i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
+    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) argmax_merge(best, besti, bv[w], bi[w]);
+        pv[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = best;
+        pi[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = besti;
+    }
+}
+static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const uint32_t *row_slot, int slot0,
+                                                               const uint32_t *slot_state) {
+    const int r = blockIdx.x;
+    if (rows_finished(slot_state, rows_slot(row_slot, slot0, r))) return;
+    float best = -INFINITY;
+    uint32_t besti = 0xffffffffu;
+    for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[r * ARGMAX_PARTS + i], pi[r * ARGMAX_PARTS + i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
+    if (threadIdx.x == 0) token[r] = besti == 0xffffffffu ? 0u : besti;
+}
+
+// grid (TOPK_PARTS, rows)
+static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float *logits_base, int V, int ld, int k, const double *pen_table, int pen_len, const uint32_t *smp,
+                                                              unsigned long long *cand_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    __shared__ unsigned long long keys[TOPK_SLICE];
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    const float *logits = logits_base + (int64_t) r * ld;
+    const int32_t *last_id = (const int32_t *) (smp + (size_t) 3 * s);
+    const uint32_t *rep_count = smp + (size_t) 3 * s + 1;
+    unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
+    const int chunk = (V + TOPK_PARTS - 1) / TOPK_PARTS;
+    const int i0 = (int) blockIdx.x * chunk;
+    const int last = pen_table ? last_id[0] : -1;
+    for (int j = threadIdx.x; j < TOPK_SLICE; j += blockDim.x) {
+        const int i = i0 + j;
+        unsigned long long key = ~0ull;
+        if (j < chunk && i < V) {
+            float v = logits[i];
+            if (i == last) {
+                const uint32_t cnt = rep_count[0];
+                v = (float) ((double) v / pen_table[cnt < (uint32_t) pen_len ? cnt : (uint32_t) pen_len - 1]);
+            }
+            key = smp_key(v, i);
+        }
+        keys[j] = key;
+    }
+    __syncthreads();
+    bitonic_sort_keys(keys, TOPK_SLICE);
+    for (int j = threadIdx.x; j < k; j += blockDim.x) cand[(int) blockIdx.x * TOPK_MAXK + j] = keys[j];
+}
+
+// grid (1, rows)
+static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base, float temperature,
+                                                                  const double *pen_table, int pen_len, const uint32_t *smp, float *total_base, const uint32_t *row_slot,
+                                                                  int slot0, const uint32_t *slot_state) {
+    __shared__ __attribute__((aligned(16))) float ex[SOFTMAX_CHUNK];
+    __shared__ float s_top;
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    const float *logits = logits_base + (int64_t) r * ld;
+    const unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
+    const int32_t *last_id = (const int32_t *) (smp + (size_t) 3 * s);
+    const uint32_t *rep_count = smp + (size_t) 3 * s + 1;
+    const bool temp = temperature != 1.0f;
+    if (threadIdx.x == 0) {
+        unsigned long long best = ~0ull;
+        for (int p = 0; p < TOPK_PARTS; p++) best = cand[p * TOPK_MAXK] < best ? cand[p * TOPK_MAXK] : best;
+        float top = smp_key_value(best);
+        if (temp) top /= temperature;
+        s_top = top;
+    }
+    __syncthreads();
+    const float top = s_top;
+    const int last = pen_table ? last_id[0] : -1;
+    float total = 0.0f;
+    for (int c0 = 0; c0 < V; c0 += SOFTMAX_CHUNK) {
+        const int n = min(SOFTMAX_CHUNK, V - c0);
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const int i = c0 + j;
+            float v = logits[i];
+            if (i == last) {
+                const uint32_t cnt = rep_count[0];
+                v = (float) ((double) v / pen_table[cnt < (uint32_t) pen_len ? cnt : (uint32_t) pen_len - 1]);
+            }
+            if (temp) v /= temperature;
+            ex[j] = expf(v - top);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int j = 0;
+            for (; j + 64 <= n; j += 64) {
+                float4 e[16];
+#pragma unroll
+                for (int q = 0; q < 16; q++) e[q] = *(const float4 *) (ex + j + 4 * q);
+#pragma unroll
+                for (int q = 0; q < 16; q++) { total += e[q].x; total += e[q].y; total += e[q].z; total += e[q].w; }
+            }
+            for (; j < n; j++) total += ex[j];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) total_base[r] = total;
+}
+
+// grid (1, rows); the row's draw is uniforms[s * uni_stride + call counter of s], which advances
+static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const unsigned long long *cand_base, int k, float temperature, const float *uniforms, int64_t uni_stride,
+                                                                const double *pen_table, uint32_t *smp, uint32_t *token, float top_p, const float *total_base,
+                                                                const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    __shared__ unsigned long long keys[TOPK_PARTS * TOPK_MAXK];
+    __shared__ float prob[TOPK_MAXK];
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    const unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
+    int32_t *last_id = (int32_t *) (smp + (size_t) 3 * s);
+    uint32_t *rep_count = smp + (size_t) 3 * s + 1, *call = smp + (size_t) 3 * s + 2;
+    const int n = TOPK_PARTS * k;
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int j = threadIdx.x; j < P; j += blockDim.x) keys[j] = j < n ? cand[(j / k) * TOPK_MAXK + (j % k)] : ~0ull;
+    __syncthreads();
+    bitonic_sort_keys(keys, P);
+    const bool temp = temperature != 1.0f;
+    float top = smp_key_value(keys[0]);
+    if (temp) top /= temperature;
+    if ((int) threadIdx.x < k) {
+        float v = smp_key_value(keys[threadIdx.x]);
+        if (temp) v /= temperature;
+        prob[threadIdx.x] = keys[threadIdx.x] == ~0ull ? 0.0f : expf(v - top);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int m = k;
+        while (m > 1 && keys[m - 1] == ~0ull) m--;
+        float target = uniforms[(int64_t) s * uni_stride + call[0]];
+        call[0] += 1;
+        float cum = 0.0f;
+        int chosen;
+        if (total_base) {
+            const float total = total_base[r];
+            float mass = 0.0f;
+            int trim = -1;
+            for (int j = 0; j < m; j++) {
+                mass += prob[j] / total;
+                if (mass >= top_p) { trim = j + 1; break; }
+            }
+            if (trim > 0) m = trim;
+            target *= fminf(mass, top_p);
+            chosen = (int) (unsigned) keys[m - 1];
+            for (int j = 0; j < m; j++) {
+                cum += prob[j] / total;
+                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
+            }
+        } else {
+            float total = 0.0f;
+            for (int j = 0; j < m; j++) total += prob[j];
+            chosen = (int) (unsigned) keys[m - 1];
+            for (int j = 0; j < m; j++) {
+                cum += prob[j] / total;
+                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
+            }
+        }
+        if (pen_table) {
+            uint32_t cnt = rep_count[0];
+            if (last_id[0] != chosen) cnt = 0;
+            last_id[0] = chosen;
+            rep_count[0] = cnt + 1;
+        }
+        token[r] = (uint32_t) chosen;
+    }
+}
+
+// The row advance that makes the session's loop device-driven: one thread per row, after the selection.  A live row's selected id is appended to its
+// slot's ids (tokens [slots][max_new]) and counted; the slot is finished on the stopping token, at max_new ids or at the end of the cache (the
+// conditions of llama_gen_emit, in its order); otherwise the id and the next position become the row's input of the next step (next_id / next_pos:
+// l_ids / l_pos, NULL at admission, where no row is staged yet).  A finished row keeps its id and position: its forward is padding that rewrites
+// the last cache position of its own slot, and nothing it selects is emitted.
+static __global__ __launch_bounds__(64) void llama_advance_rows_kernel(int rows, const uint32_t *row_slot, int slot0, const uint32_t *token, uint32_t *slot_state, uint32_t *tokens,
+                                                                uint32_t max_new, uint32_t stop_id, uint32_t n_ctx, uint32_t *next_id, uint32_t *next_pos) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    uint32_t *st = slot_state + (size_t) s * LLAMA_SLOT_STATE;
+    if (st[1]) return;
+    const uint32_t id = token[r], cnt = st[0], pos = st[3] + 1;   // pos: where the id would be fed
+    if (cnt < max_new) tokens[(size_t) s * max_new + cnt] = id;
+    st[0] = cnt + 1;
+    st[2] = id;
+    if (id == stop_id || cnt + 1 >= max_new || pos >= n_ctx) { st[1] = 1; return; }
+    st[3] = pos;
+    if (next_id) { next_id[r] = id; next_pos[r] = pos; }
+}
+
 // gu [R][2F] (gate | up) -> g [R][F] = silu(gate) * up; aq / ad (optional, F % 32 == 0): g also as Q8_0 blocks for the down projection
 // n_parts > 1: gu holds n_parts fp32 slabs part_stride floats apart (gemv_stream_kernel), summed in slab order on the way in
 static __global__ void silu_mul_kernel(const float *gu, int F, int R, float *g, int8_t *aq, float *ad, int n_parts = 1, int64_t part_stride = 0) {

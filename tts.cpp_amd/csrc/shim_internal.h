@@ -232,6 +232,23 @@ struct tts_hip_ctx {
         std::vector<uint32_t> handed;               // ... of which a gen_wait has handed out
         std::vector<uint8_t> done;
     } lg;
+    // ---- Orpheus continuous session (tts_hip_orpheus_stream_*): per-slot state on the device, the host keeps the copy of the last look-in ----
+    struct LlamaStream {
+        bool active = false, sampled = false;
+        uint32_t n_slots = 0, max_new = 0, stop_id = 0;
+        tts_hip_sampling sp{};
+        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished at admission, the next stream_run reports it
+        std::vector<uint8_t> slot;                  // per slot, one of the above
+        std::vector<uint32_t> count, cur, pos;      // per slot at the last look-in: ids so far, latest id, its position
+        std::vector<uint32_t> rows;                 // live slots in slot order (= the rows of the next run)
+        uint32_t *state = nullptr;                  // device [n_slots][LLAMA_SLOT_STATE]
+        uint32_t *tokens = nullptr;                 // device [n_slots][max_new]
+        uint32_t *smp = nullptr;                    // device [n_slots][3] sampler state
+        float *uni = nullptr;                       // device [n_slots][max_new]
+        unsigned long long *cand = nullptr;         // device [n_slots][TOPK_PARTS][TOPK_MAXK]
+        float *total = nullptr;                     // device [n_slots]
+        uint32_t *h_state = nullptr;                // pinned [n_slots][LLAMA_SLOT_STATE]
+    } ls;
     uint32_t *h_hist = nullptr;   // pinned: the ids of the steps of one gen_launch
     size_t h_hist_cap = 0;
     // ---- T5 voice-prompt encoder context (tts_hip_t5_create) ----

@@ -271,6 +271,7 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
 
 // between a tts_hip_orpheus_gen_launch and its gen_wait the steps may still be running on the stream: nothing else touches the context
 static int llama_gen_idle(const tts_hip_ctx *c, const char *what) {
+    if (c->ls.active) return set_err("%s: a continuous session is open on this context (tts_hip_orpheus_stream_end first)", what);
     if (c->lg.active && c->lg.pending) return set_err("%s: the steps of a tts_hip_orpheus_gen_launch are under way (tts_hip_orpheus_gen_wait first)", what);
     return 0;
 }
@@ -768,6 +769,254 @@ extern "C" int tts_hip_orpheus_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
 extern "C" int tts_hip_orpheus_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
     CHK(llama_gen_ready(c, "tts_hip_orpheus_gen_wait", true));
     return llama_gen_wait(c, "tts_hip_orpheus_gen_wait", tokens_out, n_out, done);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Continuous session (tts_hip_orpheus_stream_*): cache slots are admitted and refilled while the others generate.  The state of a slot — ids so far,
+// finished flag, latest id and position, sampler state, uniforms — lives on the device, so a run of k steps is k x (forward, row-batched selection,
+// llama_advance_rows_kernel) enqueued back to back: no copy and no synchronise inside the run, against three copies, two synchronises and up to three
+// launches per row in every step of llama_gen_launch_rows.  Rows that finish inside a run idle as padding until its end.
+// ------------------------------------------------------------------------------------------------
+static int llama_stream_ready(tts_hip_ctx *c, const char *what, bool need_session = true) {
+    if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
+    if (need_session && !c->ls.active) return set_err("%s: no session (tts_hip_orpheus_stream_begin)", what);
+    return 0;
+}
+
+// the selection of `rows` logits rows (first at `logits`) for slots row_slot[r] (NULL: slot0 + r) -> l_btok[r]: two launches (arg-max, top-k) or three (top_p < 1)
+static int llama_select_slots(tts_hip_ctx *c, const tts_hip_sampling *sp, int rows, const float *logits, const uint32_t *row_slot, int slot0, const uint32_t *slot_state,
+                              uint32_t *smp, const float *uni, int64_t uni_stride, unsigned long long *cand, float *total) {
+    if (!sp) {
+        hipLaunchKernelGGL(argmax_slots_parts_kernel, dim3(ARGMAX_PARTS, rows), dim3(256), 0, c->stream, logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(argmax_slots_fold_kernel, dim3(rows), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    const double *pen = sp->repetition_penalty != 1.0f ? c->d_pen : nullptr;
+    hipLaunchKernelGGL(topk_parts_rows_kernel, dim3(TOPK_PARTS, rows), dim3(512), 0, c->stream, logits, c->l_V, c->l_Vpad, (int) sp->top_k, pen, c->pen_len, (const uint32_t *) smp, cand,
+                       row_slot, slot0, slot_state);
+    HIPCHK(hipGetLastError());
+    const bool nucleus = sp->top_p < 1.0f;
+    if (nucleus) {
+        hipLaunchKernelGGL(softmax_total_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, logits, c->l_V, c->l_Vpad, (const unsigned long long *) cand, sp->temperature, pen,
+                           c->pen_len, (const uint32_t *) smp, total, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(topk_sample_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, (const unsigned long long *) cand, (int) sp->top_k, sp->temperature, uni, uni_stride, pen, smp,
+                       c->l_btok, sp->top_p, nucleus ? (const float *) total : (const float *) nullptr, row_slot, slot0, slot_state);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+static int dmalloc(T **p, size_t n) {
+    HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
+    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
+    return 0;
+}
+
+static void llama_stream_free(tts_hip_ctx *c) {
+    auto &g = c->ls;
+    free_dev(g.state); free_dev(g.tokens); free_dev(g.smp); free_dev(g.uni); free_dev(g.cand); free_dev(g.total);
+    if (g.h_state) (void) hipHostFree(g.h_state);
+    g = tts_hip_ctx::LlamaStream{};
+}
+
+extern "C" int tts_hip_orpheus_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp) {
+    const char *what = "tts_hip_orpheus_stream_begin";
+    CHK(llama_stream_ready(c, what, false));
+    CHK(llama_gen_idle(c, what));   // an open session or the window between a gen_launch and its gen_wait
+    if (c->lg.active && !llama_gen_all_done(c)) return set_err("%s: a tts_hip_orpheus_gen_* generation is under way", what);
+    if (n_slots == 0 || n_slots > c->lm.max_seqs) return set_err("%s: %u slots outside 1..max_seqs = %u", what, n_slots, c->lm.max_seqs);
+    if (sp) CHK(check_llama_sampling(c, sp, what));
+    HIPCHK(hipSetDevice(c->device));
+    c->lg.active = false;
+    auto &g = c->ls;
+    g.sampled = sp != nullptr; g.n_slots = n_slots; g.max_new = max_new; g.stop_id = stop_id;
+    if (sp) g.sp = *sp;
+    const size_t S = n_slots, M = std::max<uint32_t>(max_new, 1);
+    int rc = dmalloc(&g.state, S * LLAMA_SLOT_STATE);
+    if (rc == 0) rc = dmalloc(&g.tokens, S * M);
+    if (rc == 0 && sp) rc = dmalloc(&g.smp, S * 3);
+    if (rc == 0 && sp) rc = dmalloc(&g.uni, S * M);
+    if (rc == 0 && sp) rc = dmalloc(&g.total, S);
+    if (rc == 0 && sp && hipMalloc((void **) &g.cand, S * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+    if (rc == 0 && hipHostMalloc((void **) &g.h_state, S * LLAMA_SLOT_STATE * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
+    if (rc == 0 && sp) rc = stage_penalty(c, sp->repetition_penalty, (int) max_new);   // once: every utterance of the session shares the table
+    if (rc != 0) { llama_stream_free(c); return rc; }
+    g.slot.assign(S, tts_hip_ctx::LlamaStream::FREE);
+    g.count.assign(S, 0); g.cur.assign(S, 0); g.pos.assign(S, 0);
+    g.rows.clear();
+    g.active = true;
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt, const float *uniforms) {
+    const char *what = "tts_hip_orpheus_stream_admit";
+    typedef tts_hip_ctx::LlamaStream LS;
+    CHK(llama_stream_ready(c, what));
+    auto &g = c->ls;
+    if (n == 0) return 0;
+    if (!slots || !prompts || !n_prompt) return set_err("%s: null argument", what);
+    if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_new]", what);
+    size_t off = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
+        if (g.slot[slots[i]] == LS::LIVE || g.slot[slots[i]] == LS::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
+        if (n_prompt[i] == 0 || n_prompt[i] >= c->lm.n_ctx) return set_err("%s: utterance %u: a prompt of %u ids does not fit %u cached positions", what, i, n_prompt[i], c->lm.n_ctx);
+        for (uint32_t j = 0; j < n_prompt[i]; j++)
+            if (prompts[off + j] >= (uint32_t) c->l_V) return set_err("%s: token id %u >= vocabulary %d", what, prompts[off + j], c->l_V);
+        off += n_prompt[i];
+    }
+    HIPCHK(hipSetDevice(c->device));
+    off = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t s = slots[i];
+        uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
+        g.count[s] = 0; g.cur[s] = 0; g.pos[s] = n_prompt[i] - 1;
+        if (g.max_new == 0) { g.slot[s] = LS::ENDED; off += n_prompt[i]; continue; }
+        // count 0, not finished, no id yet, position of the prompt's last row; sampler::reset and the utterance's own draws
+        const uint32_t init[LLAMA_SLOT_STATE] = {0u, 0u, 0u, n_prompt[i] - 1};
+        HIPCHK(hipMemcpyAsync(g.state + (size_t) s * LLAMA_SLOT_STATE, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+        if (g.sampled) {
+            const uint32_t reset[3] = {0xFFFFFFFFu, 0u, 0u};
+            HIPCHK(hipMemcpyAsync(g.smp + (size_t) s * 3, reset, sizeof(reset), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(g.uni + (size_t) s * g.max_new, uniforms + (size_t) i * g.max_new, (size_t) g.max_new * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));   // init / reset are locals
+        // the prompt into the slot's cache; its last row's logits land in l_logits row s; then the first selection, as gen_begin makes it
+        CHK(llama_prefill_slot(c, what, s, prompts + off, n_prompt[i]));
+        off += n_prompt[i];
+        CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+        hipLaunchKernelGGL(llama_advance_rows_kernel, dim3(1), dim3(64), 0, c->stream, 1, (const uint32_t *) nullptr, (int) s, (const uint32_t *) c->l_btok, g.state, g.tokens, g.max_new,
+                           g.stop_id, c->lm.n_ctx, (uint32_t *) nullptr, (uint32_t *) nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h, g.state + (size_t) s * LLAMA_SLOT_STATE, LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
+        g.slot[s] = h[1] ? LS::ENDED : LS::LIVE;
+    }
+    g.rows.clear();
+    for (uint32_t s = 0; s < g.n_slots; s++) if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
+    const char *what = "tts_hip_orpheus_stream_run";
+    typedef tts_hip_ctx::LlamaStream LS;
+    CHK(llama_stream_ready(c, what));
+    auto &g = c->ls;
+    if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    auto report = [&](uint32_t s) {
+        finished_slots[*n_finished] = s;
+        finished_counts[*n_finished] = g.count[s];
+        (*n_finished)++;
+        g.slot[s] = LS::REPORTED;
+    };
+    const uint32_t n = (uint32_t) g.rows.size();
+    if (n != 0 && n_steps != 0) {
+        HIPCHK(hipSetDevice(c->device));
+        std::vector<uint32_t> ids(n), ps(n);
+        for (uint32_t r = 0; r < n; r++) { ids[r] = g.cur[g.rows[r]]; ps[r] = g.pos[g.rows[r]]; }
+        uint32_t max_pos = 0;
+        CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
+        for (uint32_t i = 0; i < n_steps; i++) {
+            // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
+            const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
+            CHK(llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1));
+            CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, (int) n, c->l_logits, c->l_seq, 0, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+            hipLaunchKernelGGL(llama_advance_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (int) n, (const uint32_t *) c->l_seq, 0, (const uint32_t *) c->l_btok, g.state,
+                               g.tokens, g.max_new, g.stop_id, c->lm.n_ctx, c->l_ids, c->l_pos);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(g.h_state, g.state, (size_t) g.n_slots * LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t s : g.rows) {
+            const uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
+            g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
+            if (h[1]) g.slot[s] = LS::ENDED;
+        }
+    }
+    g.rows.clear();
+    for (uint32_t s = 0; s < g.n_slots; s++) {
+        if (g.slot[s] == LS::ENDED) report(s);
+        else if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
+    }
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t count, uint32_t *tokens_out) {
+    const char *what = "tts_hip_orpheus_stream_collect";
+    CHK(llama_stream_ready(c, what));
+    auto &g = c->ls;
+    if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
+    if (g.slot[slot] != tts_hip_ctx::LlamaStream::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_orpheus_stream_run reports it)", what, slot);
+    if (count > g.count[slot]) return set_err("%s: slot %u produced %u ids, %u asked for", what, slot, g.count[slot], count);
+    if (count == 0) return 0;
+    if (!tokens_out) return set_err("%s: null argument", what);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(tokens_out, g.tokens + (size_t) slot * g.max_new, (size_t) count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_stream_end(tts_hip_ctx *c) {
+    if (!c || !c->has_llama) return set_err("tts_hip_orpheus_stream_end: not an Orpheus context (tts_hip_orpheus_create)");
+    if (!c->ls.active) return 0;
+    (void) hipSetDevice(c->device);
+    (void) hipStreamSynchronize(c->stream);
+    llama_stream_free(c);
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *sp, const float *uniforms, int32_t *last_id,
+                                                  uint32_t *rep_count, uint32_t *tokens_out) {
+    const char *what = "tts_hip_orpheus_sample_logits_rows";
+    CHK(llama_stream_ready(c, what, false));
+    if (!logits || !tokens_out) return set_err("%s: null argument", what);
+    CHK(llama_gen_idle(c, what));
+    if (n_rows == 0 || n_rows > c->lm.max_seqs) return set_err("%s: %u rows outside 1..max_seqs = %u", what, n_rows, c->lm.max_seqs);
+    const bool rep = sp && sp->repetition_penalty != 1.0f;
+    if (sp) {
+        CHK(check_llama_sampling(c, sp, what));
+        if (!uniforms) return set_err("%s: null uniforms", what);
+        if (rep && (!last_id || !rep_count)) return set_err("%s: repetition penalty needs last_id and rep_count", what);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t *smp = nullptr;
+    float *uni = nullptr, *total = nullptr;
+    unsigned long long *cand = nullptr;
+    auto drop = [&](int rc) { free_dev(smp); free_dev(uni); free_dev(total); free_dev(cand); return rc; };
+    if (sp) {
+        uint32_t mx = 0;
+        std::vector<uint32_t> init((size_t) 3 * n_rows);
+        for (uint32_t r = 0; r < n_rows; r++) {
+            init[3 * r] = rep ? (uint32_t) last_id[r] : 0xFFFFFFFFu; init[3 * r + 1] = rep ? rep_count[r] : 0u; init[3 * r + 2] = 0u;
+            if (rep) mx = std::max(mx, rep_count[r]);
+        }
+        if (rep) CHK(stage_penalty(c, sp->repetition_penalty, (int) std::min<uint32_t>(mx + 2, 1u << 20)));
+        int rc = dmalloc(&smp, (size_t) 3 * n_rows);
+        if (rc == 0) rc = dmalloc(&uni, (size_t) n_rows);
+        if (rc == 0) rc = dmalloc(&total, (size_t) n_rows);
+        if (rc == 0 && hipMalloc((void **) &cand, (size_t) n_rows * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+        if (rc != 0) return drop(rc);
+        if (hipMemcpy(smp, init.data(), init.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(uni, uniforms, (size_t) n_rows * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return drop(set_err("%s: copy failed", what));
+    }
+    if (hipMemcpy2DAsync(c->l_logits, (size_t) c->l_Vpad * 4, logits, (size_t) c->l_V * 4, (size_t) c->l_V * 4, n_rows, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return drop(set_err("%s: copy failed", what));
+    if (llama_select_slots(c, sp, (int) n_rows, c->l_logits, nullptr, 0, nullptr, smp, uni, 1, cand, total) != 0) return drop(-1);
+    std::vector<uint32_t> back((size_t) 3 * n_rows);
+    bool ok = hipMemcpyAsync(tokens_out, c->l_btok, (size_t) n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    if (ok && sp) ok = hipMemcpyAsync(back.data(), smp, back.size() * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    ok = hipStreamSynchronize(c->stream) == hipSuccess && ok;
+    if (!ok) return drop(set_err("%s: copy failed", what));
+    if (rep) for (uint32_t r = 0; r < n_rows; r++) { last_id[r] = (int32_t) back[3 * r]; rep_count[r] = back[3 * r + 1]; }
+    return drop(0);
 }
 
 extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *dd) {

@@ -90,6 +90,8 @@ EXPORTS = [
     "tts_hip_parler_gen_begin", "tts_hip_parler_gen_launch", "tts_hip_parler_gen_wait", "tts_hip_dac_halo_frames", "tts_hip_dac_decode_windows",
     "tts_hip_snac_halo_frames", "tts_hip_snac_decode_windows", "tts_hip_snac_decode_windows_begin", "tts_hip_snac_decode_windows_end",
     "tts_hip_orpheus_gen_begin", "tts_hip_orpheus_gen_launch", "tts_hip_orpheus_gen_wait",
+    "tts_hip_orpheus_stream_begin", "tts_hip_orpheus_stream_admit", "tts_hip_orpheus_stream_run", "tts_hip_orpheus_stream_collect", "tts_hip_orpheus_stream_end",
+    "tts_hip_orpheus_sample_logits_rows",
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
 ]
 
@@ -197,6 +199,12 @@ def load_lib():
     L.tts_hip_orpheus_gen_begin.argtypes = [vp, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.POINTER(Sampling), f32p]
     L.tts_hip_orpheus_gen_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_orpheus_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8)]
+    L.tts_hip_orpheus_stream_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Sampling)]
+    L.tts_hip_orpheus_stream_admit.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, f32p]
+    L.tts_hip_orpheus_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
+    L.tts_hip_orpheus_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
+    L.tts_hip_orpheus_stream_end.argtypes = [vp]
+    L.tts_hip_orpheus_sample_logits_rows.argtypes = [vp, C.c_uint32, f32p, C.POINTER(Sampling), f32p, C.POINTER(C.c_int32), u32p, u32p]
     L.tts_hip_dia_gen_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes), C.POINTER(Sampling), f32p]
     L.tts_hip_dia_gen_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_dia_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p]
@@ -664,6 +672,7 @@ class OrpheusEngine:
         d.hidden_size, d.n_layers, d.n_attn_heads, d.n_kv_heads, d.head_dim = cfg.hidden, cfg.layers, cfg.heads, cfg.kv_heads, cfg.head_dim
         d.vocab_size, d.n_ctx, d.rope_base, d.flags = cfg.vocab, cfg.ctx, 0.0, flags
         d.max_seqs = max_seqs
+        self._stream = (max(1, max_seqs), 0)   # (slots, max_new) of the continuous session
         self.ctx = self.L.tts_hip_orpheus_create(device, C.byref(d))
         if not self.ctx:
             raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
@@ -777,6 +786,56 @@ class OrpheusEngine:
         li, rc, tok = C.c_int32(last_id), C.c_uint32(rep_count), C.c_uint32()
         self._chk(self.L.tts_hip_orpheus_sample_logits(self.ctx, lg.ctypes.data_as(C.POINTER(C.c_float)), C.byref(sp), uniform, C.byref(li), C.byref(rc), C.byref(tok)))
         return tok.value, li.value, rc.value
+
+    def sample_logits_rows(self, logits, uniforms=None, top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0, last_id=None, rep_count=None):
+        """tts_hip_orpheus_sample_logits_rows: the session's row-batched selection on logits [n][vocab]; uniforms [n] selects sampler::sample,
+        None = arg-max -> (tokens [n], last_id [n], rep_count [n])"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        n = lg.shape[0]
+        assert lg.shape == (n, self.cfg.vocab)
+        li = np.ascontiguousarray(np.full(n, -1) if last_id is None else last_id, dtype=np.int32).copy()
+        rc = np.ascontiguousarray(np.zeros(n) if rep_count is None else rep_count, dtype=np.uint32).copy()
+        tok = np.zeros(n, dtype=np.uint32)
+        spp, up = None, None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n)
+            sp_ = Sampling(top_k, top_p, temperature, repetition_penalty)
+            spp, up = C.byref(sp_), u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_orpheus_sample_logits_rows(self.ctx, n, lg.ctypes.data_as(C.POINTER(C.c_float)), spp, up, li.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            rc.ctypes.data_as(C.POINTER(C.c_uint32)), tok.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return tok, li, rc
+
+    # ---- continuous session (tts_hip_orpheus_stream_*) ----
+    def stream_begin(self, n_slots, max_new, stop_id, sampled=False, top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0):
+        sp = Sampling(top_k, top_p, temperature, repetition_penalty)
+        self._chk(self.L.tts_hip_orpheus_stream_begin(self.ctx, n_slots, max_new, stop_id, C.byref(sp) if sampled else None))
+        self._stream = (n_slots, max_new)
+
+    def stream_admit(self, slots, prompts, uniforms=None):
+        """prompts: one id list per slot; uniforms [n][max_new] for a sampled session"""
+        s, sp = _u32(slots)
+        cat, cp = _u32(np.concatenate([np.asarray(p, dtype=np.uint32) for p in prompts]))
+        lens, lp = _u32(np.array([len(p) for p in prompts], dtype=np.uint32))
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(len(prompts), self._stream[1])
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_orpheus_stream_admit(self.ctx, len(prompts), sp, cp, lp, up))
+
+    def stream_run(self, n_steps):
+        """-> [(slot, id count)] of the slots that finished"""
+        cap = self._stream[0]
+        fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
+        self._chk(self.L.tts_hip_orpheus_stream_run(self.ctx, n_steps, C.byref(n), fs.ctypes.data_as(C.POINTER(C.c_uint32)), fn.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_collect(self, slot, count):
+        out = np.zeros(max(count, 1), dtype=np.uint32)
+        self._chk(self.L.tts_hip_orpheus_stream_collect(self.ctx, slot, count, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:count].copy()
+
+    def stream_end(self):
+        self._chk(self.L.tts_hip_orpheus_stream_end(self.ctx))
 
     def close(self):
         if self.ctx:

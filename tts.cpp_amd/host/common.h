@@ -106,9 +106,12 @@ struct tts_generation_runner : tts_runner {
     // ---- extension: continuous batching — a session that takes utterances in while others are still generating ---------------------
     // The reference's server hands one task at a time to a worker that owns a whole model (examples/server/server.cpp:126-158, 236-271);
     // generate_batch widened that to "form a batch from the queue, run it to the end".  A session keeps the lock-step forward full instead:
-    // stream_submit() enters an utterance into a free row at the next look-in point (every 32 decode steps), stream_step() runs one such
-    // interval and hands back the utterances whose check_stopping() fired inside it, already decoded to audio.  An utterance's audio is that
-    // of a generate() call of its own.  A runner without the extension reports 0 capacity and the callers fall back to generate_batch.
+    // stream_submit() enters an utterance into a free row at the next look-in point (parler_runner: every 32 decode steps; orpheus_runner: every
+    // 28 ids, admitted at once into a free cache slot), stream_step() runs one such interval and hands back the utterances that ended inside
+    // it, already decoded to audio.  An utterance's audio is that of a generate() call of its own.  parler_runner and orpheus_runner have a
+    // session; a runner without the extension (dia_runner, kokoro_runner) reports 0 capacity and the callers fall back to generate_batch.
+    // Orpheus' SNAC noise block: a session decodes an utterance when it finishes, so the never-reseeded engine's draws follow the order in
+    // which utterances finish; with TTS_SNAC_NO_NOISE the audio is bit for bit generate()'s (see the chunked-audio note below).
     struct stream_result {
         size_t       ticket = 0;   // the caller's handle, as given to stream_submit
         tts_response audio;        // valid until the next stream_step / stream_end of this runner

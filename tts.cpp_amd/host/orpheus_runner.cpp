@@ -472,3 +472,81 @@ void orpheus_runner::generate_batch_chunked(const std::vector<std::string> & sen
     for (uint32_t u = 0; u < n; u++) last_batch_tokens[u] = st[u].ids;
     last_output_tokens = last_batch_tokens[n - 1];
 }
+
+// ---- continuous batching (common.h; tts_hip_orpheus_stream_* underneath) ---------------------------------------------------------------
+// Decoder steps between two look-ins.  A multiple of 7 ids, so an utterance admitted at a look-in is looked at on SNAC frame boundaries; four frames:
+// a finished row idles as padding for at most 27 steps (about 1 % of a 2100-id utterance, 14 steps on average) and a queued request waits at most
+// 28 steps (about 0.1 s at 8 rows of Orpheus-3B) for a free slot, while a look-in's staging copies, synchronise and state copy (tens of
+// microseconds) are spread over 28 forwards of a few milliseconds each.
+static constexpr uint32_t ORPHEUS_STREAM_STEPS = 28;
+
+void orpheus_runner::stream_begin(const generation_configuration & config) {
+    if (stream_capacity() == 0) TTS_ABORT("stream_begin: the runner was loaded with max_seqs=%u; a session needs >= 2 (TTS_HIP_MAX_SEQS)\n", max_seqs);
+    if (getenv("TTS_HOST_LOOP")) TTS_ABORT("stream_begin: TTS_HOST_LOOP asks for the host loop; a session runs on the device\n");
+    if (config.sample && !device_sampler(config))
+        TTS_ABORT("stream_begin: the device sampler takes top_k in 1..64 and top_p > 0 (got top_k %d, top_p %g); a session cannot sample on the host\n", config.top_k, config.top_p);
+    if (st_on) stream_end();
+    {   // a chunked generation that its callback stopped is abandoned here, as a generate() call would abandon it
+        const uint32_t one = 1, id = 0;
+        hip_check(tts_hip_orpheus_gen_begin(lm, 1, &id, &one, 0, hp.stopping_token_id, nullptr, nullptr), "tts_hip_orpheus_gen_begin");
+    }
+    const uint32_t slots = stream_capacity();
+    st_cfg = config;
+    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+    hip_check(tts_hip_orpheus_stream_begin(lm, slots, hp.max_generation_size, hp.stopping_token_id, config.sample ? &sp : nullptr), "tts_hip_orpheus_stream_begin");
+    st_free.clear();
+    for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
+    st_ticket.assign(slots, 0);
+    st_pcm.clear();
+    st_live = 0;
+    st_on = true;
+}
+
+void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence) {
+    if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
+    if (st_free.empty()) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
+    const std::vector<uint32_t> prompt = checked_prompt(sentence, st_cfg);
+    const uint32_t M = hp.max_generation_size, n_prompt = (uint32_t) prompt.size();
+    std::vector<float> uni;
+    if (st_cfg.sample) {   // as batch_inputs: the sampler as a generate() call of this utterance's own starts it, one draw per sampler call
+        uni.resize(M);
+        sampler_setup(st_cfg);
+        for (auto & v : uni) smp.draw_uniforms(&v);
+    }
+    const uint32_t slot = st_free.back();
+    hip_check(tts_hip_orpheus_stream_admit(lm, 1, &slot, prompt.data(), &n_prompt, st_cfg.sample ? uni.data() : nullptr), "tts_hip_orpheus_stream_admit");
+    st_free.pop_back();
+    st_ticket[slot] = ticket;
+    st_live++;
+}
+
+void orpheus_runner::stream_step(std::vector<stream_result> & finished) {
+    if (!st_on) TTS_ABORT("stream_step: no session (stream_begin)\n");
+    finished.clear();
+    std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());
+    uint32_t nf = 0;
+    hip_check(tts_hip_orpheus_stream_run(lm, ORPHEUS_STREAM_STEPS, &nf, fs.data(), fn.data()), "tts_hip_orpheus_stream_run");
+    st_pcm.assign(nf, {});
+    for (uint32_t i = 0; i < nf; i++) {   // in slot order; the codec runs utterance by utterance, as in generate_batch
+        const uint32_t slot = fs[i];
+        std::vector<uint32_t> ids(fn[i]);
+        hip_check(tts_hip_orpheus_stream_collect(lm, slot, fn[i], ids.data()), "tts_hip_orpheus_stream_collect");
+        st_free.push_back(slot);
+        st_live--;
+        decode_audio(ids, st_pcm[i]);   // ids the codec refuses abort here, as they do in generate()
+        last_output_tokens = std::move(ids);
+        stream_result r;
+        r.ticket = st_ticket[slot];
+        r.audio.data = st_pcm[i].empty() ? nullptr : st_pcm[i].data();
+        r.audio.n_outputs = st_pcm[i].size();
+        finished.push_back(r);
+    }
+}
+
+void orpheus_runner::stream_end() {
+    if (!st_on) return;
+    (void) tts_hip_orpheus_stream_end(lm);
+    st_on = false;
+    st_free.clear();
+    st_live = 0;
+}

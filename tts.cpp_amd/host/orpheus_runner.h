@@ -59,6 +59,17 @@ struct orpheus_runner final : tts_generation_runner {
                               const std::function<bool(const float *, size_t)> & on_chunk) override;
     void     generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
                                     const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) override;
+    // extension: continuous batching (common.h) on tts_hip_orpheus_stream_*: max_seqs slots, every one a row of the device-driven lock-step loop; a slot
+    // that frees up is refilled at the next look-in.  An utterance's ids are those of a generate() call of its own, and with TTS_SNAC_NO_NOISE so is
+    // its audio; with the noise block the engine's draws follow the order in which utterances finish.  A sampled session needs the device sampler
+    // (top_k 1..64): generate_batch falls back to the host loop for other configurations, a session cannot, and stream_begin aborts.
+    uint32_t stream_capacity() const override { return max_seqs > 1 ? max_seqs : 0; }
+    void     stream_begin(const generation_configuration & config) override;
+    uint32_t stream_free() const override { return (uint32_t) st_free.size(); }
+    uint32_t stream_live() const override { return st_live; }
+    void     stream_submit(size_t ticket, const std::string & sentence) override;
+    void     stream_step(std::vector<stream_result> & finished) override;
+    void     stream_end() override;
     std::vector<std::string_view> list_voices() override;
 
     void decode_audio(const std::vector<uint32_t> & output_tokens, std::vector<float> & audio);   // prepare_output_tokens + SNAC
@@ -95,6 +106,13 @@ struct orpheus_runner final : tts_generation_runner {
         std::vector<uint32_t> utt, codes, frames, keep0, keep1;
         std::vector<float>    noise;
     };
+    // session state of the continuous batching
+    bool                            st_on = false;
+    generation_configuration        st_cfg{};
+    uint32_t                        st_live = 0;
+    std::vector<uint32_t>           st_free;     // free cache slots
+    std::vector<size_t>             st_ticket;   // slot -> ticket
+    std::vector<std::vector<float>> st_pcm;      // audio handed out by the last stream_step
     bool device_sampler(const generation_configuration & config) const;
     void sampler_setup(const generation_configuration & config);
     std::vector<uint32_t> checked_prompt(const std::string & sentence, const generation_configuration & config);
