@@ -47,10 +47,12 @@ int           tts_c_generate_batch(tts_c_runner *r, const char *const *texts, in
                                    size_t *n_outputs);
 /* Extension: any number of utterances through ONE continuous-batching session of the runner (tts_generation_runner::generate_stream): a row
  * freed by an utterance that finishes is refilled from texts[] at the next look-in point instead of idling until the longest one is done.
- * Parler-TTS and Orpheus have a session.  Parler-TTS: at most max_seqs - 1 utterances generate at a time (one cache slot pads the forward), a
+ * Parler-TTS, Orpheus and Dia have a session.  Parler-TTS: at most max_seqs - 1 utterances generate at a time (one cache slot pads the forward), a
  * look-in every 32 decode steps.  Orpheus: max_seqs utterances, a look-in every 28 ids (four SNAC frames) of a device-driven loop; a sampled
- * session needs the device sampler (top_k 1..64, top_p > 0) and is refused otherwise.  Dia and Kokoro have no session: their texts go through
- * generate_batch in groups.  Same outputs as n generate() calls; data[i] valid until the next call.
+ * session needs the device sampler (top_k 1..64, top_p > 0) and is refused otherwise.  Dia: max_seqs utterances, a look-in every 16 steps; a slot
+ * that finished is parked on the device (one attention position per step) until the next look-in refills it, an admission runs the text encoder
+ * between two intervals, and the finished utterances of an interval share one codec pass (audio within 1e-5 of a tts_c_generate call's, ids
+ * identical).  Kokoro has no session: its texts go through generate_batch in groups.  Same outputs as n generate() calls; data[i] valid until the next call.
  * Orpheus' SNAC noise block: the codec runs when an utterance finishes, so the never-reseeded noise engine's draws follow the order in which
  * utterances finish, not the order of texts[]; with TTS_SNAC_NO_NOISE every audio is bit for bit that of a tts_c_generate call of its own. */
 int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, const float **data,
@@ -95,7 +97,8 @@ const char   *tts_c_last_error(void);
 
 /* ---- test hooks ---------------------------------------------------------------------------------- */
 /* which = 0: prompt ids of the last generate (tokenised + EOS); 1: sampled ids, still delayed
- * (pctx->output_tokens).  Returns the count (copies at most cap). */
+ * (pctx->output_tokens); Dia, 16 + i: the still-delayed ids of utterance i of the last generate_batch / generate_stream.
+ * Returns the count (copies at most cap). */
 int tts_c_last_tokens(tts_c_runner *r, int which, uint32_t *out, int cap);
 /* unigram tokenizer from the GGUF vocabulary + EOS, as batch_from_sentence builds it (model.cpp:473-498); a GGUF with
  * tokenizer.ggml.merges gets the byte-pair tokenizer instead (src/tokenizer.cpp:265-296; ids only, no framing) */

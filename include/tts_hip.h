@@ -397,6 +397,42 @@ int tts_hip_dia_gen_begin(tts_hip_ctx *ctx, uint32_t n_utt, uint32_t max_gen, co
                           const float *uniforms);
 int tts_hip_dia_gen_launch(tts_hip_ctx *ctx, uint32_t n_steps);
 int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran);
+/* Continuous session: the loop of tts_hip_dia_generate with utterances entering and leaving while the others keep going.
+ * Fixed shape: every step of a session steps all n_slots slots = 2 * n_slots rows through the decoder step tts_hip_dia_generate runs at
+ * n_utt == n_slots (kernel selection depends on the row count, so it never changes inside a session), as one captured graph per session
+ * configuration.  What belongs to a slot's occupant — its step budget, its uniforms, the parked flag — is device memory: an admission changes
+ * values, never the captured launches.
+ *   begin    n_slots <= max_utterances slots, every one parked; max_gen, codes and sampling as in tts_hip_dia_generate (sampling NULL:
+ *            sampler::max), with its limits.  An unfinished gen_* loop is waited for and dropped.  Slots no encoder pass has filled get the one
+ *            cross K/V position their parked rows attend over cleared.
+ *   admit    n utterances into free slots, between two runs: tokens [n][max_ctx] and sentence_len [n] as for tts_hip_dia_encode_slot, budget [n]
+ *            (NULL: max_gen) with max_delay < budget <= max_gen: the utterance runs as under tts_hip_dia_generate with max_gen = budget;
+ *            uniforms [n][max_gen][n_output_heads] for a sampled session (utterance i, sampler call k, head h), else NULL.  Per utterance the
+ *            encoder pass and cross K/V fill of its slot, then ONE launch for all n: ids = BOS, position 0, countdown not started, sampler::reset,
+ *            budget, the whole text context as cross extent, the uniforms into the slot's column of the sampler's [call][n_slots][head] block.
+ *   run      enqueues n_steps replays (no more than the live slots' budgets leave) with no copy and no synchronise in between, then one look-in
+ *            — one launch, one copy, one synchronise — that reads every slot's sampler calls and parked flag.  Slots whose countdown ended are
+ *            reported with their step counts.  (No budget ends at admission: budget = max_delay + 1 makes max_delay sampler calls and is reported
+ *            by the run that contains them, like any other.)  With no live slot nothing is launched.
+ *   collect  the first `steps` history rows [steps][n_output_heads] of a reported slot, before that slot is admitted again
+ *   end      ends the session; the slots stay encoded with their last occupants
+ * Parking: a slot is free when it has finished, was never admitted, or has been collected and not admitted again.  The pre-step that ends a
+ * slot's countdown parks it: both rows move to position 0 and their cross extent to one key, so from that step on its self-attention and its
+ * cross-attention read one position each, it records nothing and its sampler state stands still (a finished row of tts_hip_dia_generate keeps
+ * attending over its whole history until the batch is done).
+ * Equality: an utterance's ids and step count are those of tts_hip_dia_generate on a context with n_utt = n_slots, the utterance in the same
+ * slot, max_gen = its budget and its uniforms in that slot's column — the same forward at the same row count, whoever else is live, parked or
+ * admitted meanwhile (tests/test_gpu_dia_stream.py); greedy, they are also those of its one-utterance tts_hip_dia_generate at the test shapes.
+ * Between begin and end every other generation call on the context (tts_hip_dia_encode*, _step*, _generate, gen_begin / gen_launch / gen_wait)
+ * is refused with an error, and so is a second begin.  Every misuse (n_slots > max_utterances, a busy slot, a slot >= n_slots or named twice,
+ * collect on a slot that has not been reported or for more steps than it made, a budget outside (max_delay, max_gen], a sentence length outside
+ * 1..max_ctx, a sampled session without uniforms, sampler limits) returns non-zero before anything is launched; the context stays usable. */
+int tts_hip_dia_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sampling);
+int tts_hip_dia_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
+                             const float *uniforms);
+int tts_hip_dia_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps);
+int tts_hip_dia_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t steps, uint32_t *tokens_out);
+int tts_hip_dia_stream_end(tts_hip_ctx *ctx);
 
 /* ---- Kokoro (src/models/kokoro/model.cpp) ----------------------------------------------------------------------------
  * Device side of kokoro_duration_runner::run (:1069-1123) and kokoro_runner::run (:1277-1325): create, tts_hip_upload every

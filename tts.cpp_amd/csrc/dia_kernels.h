@@ -134,3 +134,102 @@ static __global__ __launch_bounds__(64) void dia_lookin_kernel(DiaLookArgs a) {
         a.handed[u] = from + rows;
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// continuous session (tts_hip_dia_stream_*): the loop above with a fixed number of slots that utterances enter and leave while the others
+// keep going.  What differs per slot and per occupant lives in device memory, so an admission never drops the captured graph:
+//   budget[u]   the occupant's max_gen (max_delay < budget <= max_gen of the session); the history stride stays the session's max_gen
+//   steps[u]    sampler calls the occupant made, written when the slot parks (its position does not survive parking)
+//   done[u]     the parked flag: set when the countdown ends, set for every slot by begin, cleared by an admission
+// Parking: the pre-step that ends a countdown moves both rows of the slot to position 0 and their cross extent to one key, so from that
+// step on the slot's self-attention and cross-attention read one position each (a finished row of the lock-step loop keeps attending
+// over its whole history); the post-step records nothing for it and sample_kernel leaves its state alone (SampleArgs::idle).
+//   dia_stream_prestep_kernel   dia_prestep_kernel with budget[u] for max_gen, plus parking
+//   dia_stream_admit_kernel     one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column
+//   dia_stream_clear_kernel     begin: zero cross K/V at position 0 of the slots no encoder pass has filled (what their parked rows attend over)
+//   dia_stream_look_kernel      the look-in: {sampler calls, parked flag} of every slot into one block
+// The post-step is dia_poststep_kernel unchanged.
+// ------------------------------------------------------------------------------------------------
+struct DiaStreamArgs {
+    const uint32_t *budget;   // [n_slots]
+    uint32_t *steps;          // [n_slots]
+    uint32_t *cend;           // [2 * n_slots] cross-attention extent of rows 2u, 2u+1
+};
+
+static __global__ void dia_stream_prestep_kernel(DiaLoopArgs a, DiaStreamArgs s) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.n_utt || a.done[u]) return;
+    uint32_t *aud = a.ids + u * a.n_out;
+    const uint32_t p = a.pos[2 * u];
+    int d = a.delay[u];
+    if (d == -1 && (aud[0] == a.eos || p >= s.budget[u] - a.max_delay)) d = (int) a.max_delay;
+    if (d > 0) {
+        const int after = (int) a.max_delay - d;
+        for (int i = 0; i < a.n_out; i++) {
+            if (after == (int) a.delay_pattern[i]) aud[i] = a.eos;
+            else if (after > (int) a.delay_pattern[i]) aud[i] = a.pad;
+        }
+        d -= 1;
+    }
+    a.delay[u] = d;
+    a.call[u] = p + 1;
+    if (d == 0) {   // park: this step's forward already reads one position per attention
+        a.done[u] = 1;
+        s.steps[u] = p;
+        a.pos[2 * u] = 0; a.pos[2 * u + 1] = 0;
+        s.cend[2 * u] = 1; s.cend[2 * u + 1] = 1;
+        a.call[u] = 1;
+    }
+}
+
+struct DiaAdmitArgs {
+    int n, n_slots, n_out;
+    uint32_t bos, max_gen, max_ctx;
+    const uint32_t *slots;    // [n]
+    const uint32_t *budgets;  // [n]
+    const float *uni_in;      // [n][max_gen][n_out] or NULL
+    float *uni;               // [max_gen][n_slots][n_out] what sample_kernel reads
+    int32_t *last;            // [n_slots][n_out] or NULL (no repetition penalty)
+    uint32_t *repc;
+    uint32_t *ids, *pos, *done, *call, *handed, *budget, *steps, *cend;
+    int32_t *delay;
+};
+
+// blockIdx.y = admitted utterance; thread 0 of block x == 0 resets the slot, all threads move its uniforms
+static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitArgs a) {
+    const int i = blockIdx.y;
+    if (i >= a.n) return;
+    const uint32_t u = a.slots[i];
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned) a.n_out) {
+        a.ids[u * a.n_out + threadIdx.x] = a.bos;
+        if (a.last) { a.last[u * a.n_out + threadIdx.x] = -1; a.repc[u * a.n_out + threadIdx.x] = 0; }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.pos[2 * u] = 0; a.pos[2 * u + 1] = 0;
+        a.cend[2 * u] = a.max_ctx; a.cend[2 * u + 1] = a.max_ctx;
+        a.delay[u] = -1; a.done[u] = 0; a.call[u] = 1; a.handed[u] = 0;
+        a.budget[u] = a.budgets[i]; a.steps[u] = 0;
+    }
+    if (!a.uni_in) return;
+    const int64_t total = (int64_t) a.max_gen * a.n_out;
+    for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
+        const int64_t k = e / a.n_out, h = e - k * a.n_out;
+        a.uni[(k * a.n_slots + u) * a.n_out + h] = a.uni_in[(int64_t) i * total + e];
+    }
+}
+
+// cross K/V [L][rows][S][A]: position 0 of rows 2u, 2u+1 of the flagged slots.  grid (ceil(A / 256), 2 * n_slots, L)
+static __global__ __launch_bounds__(256) void dia_stream_clear_kernel(float *ck, float *cv, uint64_t clear, int rows, int64_t S, int A) {
+    const int e = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, l = blockIdx.z;   // clear: bit u = slot u (a context has at most 64)
+    if (e >= A || !((clear >> (r >> 1)) & 1)) return;
+    const int64_t at = ((int64_t) l * rows + r) * S * A + e;
+    ck[at] = 0.0f;
+    cv[at] = 0.0f;
+}
+
+static __global__ void dia_stream_look_kernel(int n_slots, const uint32_t *pos, const uint32_t *done, const uint32_t *steps, uint32_t *block) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_slots) return;
+    block[2 * u] = done[u] ? steps[u] : pos[2 * u];
+    block[2 * u + 1] = done[u];
+}

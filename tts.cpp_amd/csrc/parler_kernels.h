@@ -1128,6 +1128,8 @@ struct SampleArgs {
     // indexed by utterance (NULL: row == utterance, R_total == R)
     const uint32_t *orig;
     int R_total;
+    // rows that sit out (a parked slot of a Dia session): idle[utterance] != 0 -> no id, no draw, the sampler state stands still (NULL: none)
+    const uint32_t *idle;
 };
 
 // Candidate order = descending value, equal values by ascending index: a total order, so a bitonic sort of the
@@ -1175,6 +1177,7 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
 
     // the token sampled last enters every comparison and the softmax with its penalised value
     const int ro = a.orig ? (int) a.orig[r] : r;   // utterance of this row
+    if (a.idle && a.idle[ro]) return;              // the whole workgroup: ro depends on the block alone
     const int last = a.pen_table ? a.last_ids[ro * a.n_out + h] : -1;
     float pen_v = 0.0f;
     if (last >= 0 && last < V) {

@@ -1052,6 +1052,7 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         CHK(dmalloc(&c->di_ids, (size_t) U * 16)); CHK(dmalloc(&c->di_pos, (size_t) R)); CHK(dmalloc(&c->di_seq, (size_t) R)); CHK(dmalloc(&c->di_cend, (size_t) R));
         CHK(dmalloc(&c->di_stok, (size_t) U * 16)); CHK(dmalloc(&c->di_loop, (size_t) 4 * U)); CHK(dmalloc(&c->di_hist, (size_t) U * G * c->NO));
         CHK(dmalloc(&c->di_look, (size_t) U * (2 + (size_t) G * c->NO)));
+        CHK(dmalloc(&c->di_sbud, (size_t) 2 * U)); CHK(dmalloc(&c->di_sadm, (size_t) 2 * U));
         HIPCHK(hipHostMalloc((void **) &c->h_di_look, (size_t) U * (2 + (size_t) G * c->NO) * 4));
         CHK(dmalloc(&c->d_last, (size_t) U * c->NO)); CHK(dmalloc(&c->d_repc, (size_t) U * c->NO));
         HIPCHK(hipHostMalloc((void **) &c->h_di, ((size_t) U * 16 + 2 * (size_t) R) * 4));

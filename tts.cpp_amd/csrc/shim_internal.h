@@ -198,6 +198,23 @@ struct tts_hip_ctx {
     _Float16 *di_e16 = nullptr;   // [2 * max_ctx][max(EH, A, EF)] the encoder activations rounded to fp16 for gemm_tile_kernel
     struct { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int mode = -1; uint32_t U = 0, max_gen = 0; tts_hip_dia_codes codes{}; } di_baked;
     int di_U = 1;                        // utterance slots (rows = 2 per slot)
+    // ---- Dia continuous session (tts_hip_dia_stream_*): the loop state of dg's arrays per slot, plus budget / steps [U] each in di_sbud ----
+    struct DiaStream {
+        bool active = false, sampled = false, rep = false;
+        uint32_t n_slots = 0, max_gen = 0;
+        tts_hip_dia_codes codes{};
+        tts_hip_sampling sp{};
+        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: seen parked by a look-in, not yet reported
+        std::vector<uint8_t> slot;       // per slot, one of the above
+        std::vector<uint32_t> steps;     // per slot at the last look-in: sampler calls made
+        std::vector<uint32_t> budget;    // per slot: the occupant's step budget
+    } ds;
+    uint32_t *di_sbud = nullptr;         // device [2][U]: budget, steps
+    uint32_t *di_sadm = nullptr;         // device [2][U]: slots, budgets of one admission
+    float *di_suni = nullptr;            // device: the admitted utterances' uniforms before they move into their columns
+    size_t di_suni_cap = 0;
+    bool di_park = false;                // the step being enqueued is a session step (launch_attn_gqa)
+    struct { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int mode = -1; uint32_t U = 0, max_gen = 0; tts_hip_dia_codes codes{}; } di_sbaked;
     std::vector<uint8_t> di_slot_encoded;   // tts_hip_dia_encode_slot has run for the slot
     uint32_t *h_di = nullptr;            // pinned staging: ids / pos / seq of a step
     // ---- Kokoro context (tts_hip_kokoro_create) ----

@@ -63,8 +63,12 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
     } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
         // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through 3 rolling register slots
-        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys,
-                           kend, row_seq, seq_stride, qp);
+        if (c->di_park)   // a session step: parked rows (kend[r] = 1) must not stream the context (attn_gqa_wave_kernel's CLAMP)
+            hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
+                               n_ctx_keys, kend, row_seq, seq_stride, qp);
+        else
+            hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys,
+                               kend, row_seq, seq_stride, qp);
     } else {
         hipLaunchKernelGGL(attn_gqa_split_kernel<128>, dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
                            kbeg, kend, row_seq, seq_stride, qp);
@@ -1096,21 +1100,33 @@ static int dia_rms(tts_hip_ctx *c, size_t w_off, int rows, int H, float *x, floa
 }
 
 static int dia_gen_drop(tts_hip_ctx *c);
+static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out);
+
+// between tts_hip_dia_stream_begin and _end the loop state, the cross extents and the slots belong to the session
+static int dia_no_session(const tts_hip_ctx *c, const char *what) {
+    return c->ds.active ? set_err("%s: a continuous session is open on this context (tts_hip_dia_stream_end)", what) : 0;
+}
 
 extern "C" int tts_hip_dia_encode_slot(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_encode: not a Dia context (tts_hip_dia_create)");
+    CHK(dia_no_session(c, "tts_hip_dia_encode"));
     if (slot >= (uint32_t) c->di_U) return set_err("tts_hip_dia_encode_slot: slot %u outside the %d utterance slots of this context (max_utterances)", slot, c->di_U);
     if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_encode: context not finalized");
     if (!tokens) return set_err("tts_hip_dia_encode: null argument");
+    const int S = (int) c->dia.max_ctx;
+    if (sentence_len == 0 || sentence_len > (uint32_t) S) return set_err("tts_hip_dia_encode: sentence length %u outside 1..%d", sentence_len, S);
+    for (int t = 0; t < S; t++)
+        if (tokens[t] >= (uint32_t) c->di_evocab) return set_err("tts_hip_dia_encode: token %u >= encoder vocabulary %d", tokens[t], c->di_evocab);
+    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
+    return dia_encode_into(c, slot, tokens, sentence_len, enc_out);
+}
+
+// the encoder pass and the cross K/V fill of one slot; the arguments have been checked (tts_hip_dia_encode_slot, tts_hip_dia_stream_admit)
+static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out) {
     const int S = (int) c->dia.max_ctx, EH = c->di_EH, EF = c->di_EF, A = c->di_A, HD = (int) c->dia.head_dim, ENH = (int) c->dia.enc_attn_heads;
     const int NH = c->NH, n = 2 * S;
-    if (sentence_len == 0 || sentence_len > (uint32_t) S) return set_err("tts_hip_dia_encode: sentence length %u outside 1..%d", sentence_len, S);
-    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     std::vector<uint32_t> tok((size_t) n, 0u), epos((size_t) n), eseq((size_t) n), kbeg((size_t) n), kend((size_t) n);
-    for (int t = 0; t < S; t++) {
-        if (tokens[t] >= (uint32_t) c->di_evocab) return set_err("tts_hip_dia_encode: token %u >= encoder vocabulary %d", tokens[t], c->di_evocab);
-        tok[(size_t) t] = tokens[t];
-    }
+    for (int t = 0; t < S; t++) tok[(size_t) t] = tokens[t];
     for (int t = 0; t < n; t++) {   // set_inputs :712-721: real positions see real positions, pad positions see pad positions
         const uint32_t p = (uint32_t) (t % S);
         epos[(size_t) t] = p; eseq[(size_t) t] = (uint32_t) (t / S);
@@ -1261,6 +1277,7 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
     if (!c || !c->has_dia) return set_err("tts_hip_dia_step: not a Dia context (tts_hip_dia_create)");
     if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_step: context not finalized");
     if (!ids || !pos || !logits_out) return set_err("tts_hip_dia_step: null argument");
+    CHK(dia_no_session(c, "tts_hip_dia_step"));
     if (n_utt == 0 || n_utt > (uint32_t) c->di_U) return set_err("tts_hip_dia_step_batch: %u utterances outside 1..%d (max_utterances)", n_utt, c->di_U);
     const int G = (int) c->dia.max_gen, NO = c->NO, V = c->di_V;
     const int U = (int) n_utt, R = 2 * U, RS = 2 * c->di_U;   // rows of this step, row slots of the caches
@@ -1349,6 +1366,7 @@ static int dia_gen_begin(tts_hip_ctx *c, const char *what, uint32_t n_utt, uint3
     if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
     if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
     if (!codes) return set_err("%s: null argument", what);
+    CHK(dia_no_session(c, what));
     if (n_utt == 0 || n_utt > (uint32_t) c->di_U) return set_err("%s: %u utterances outside 1..%d (max_utterances)", what, n_utt, c->di_U);
     const int G = (int) c->dia.max_gen, NO = c->NO, V = c->di_V, U = (int) n_utt;
     if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("%s: max_gen %u outside 1..%d cached positions", what, max_gen, G);
@@ -1476,12 +1494,14 @@ extern "C" int tts_hip_dia_gen_begin(tts_hip_ctx *c, uint32_t n_utt, uint32_t ma
 
 extern "C" int tts_hip_dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_launch: not a Dia context (tts_hip_dia_create)");
+    CHK(dia_no_session(c, "tts_hip_dia_gen_launch"));
     if (!c->dg.active) return set_err("tts_hip_dia_gen_launch: no generation (tts_hip_dia_gen_begin)");
     return dia_gen_launch(c, n_steps);
 }
 
 extern "C" int tts_hip_dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_wait: not a Dia context (tts_hip_dia_create)");
+    CHK(dia_no_session(c, "tts_hip_dia_gen_wait"));
     if (!c->dg.active) return set_err("tts_hip_dia_gen_wait: no generation (tts_hip_dia_gen_begin)");
     return dia_gen_wait(c, tokens_out, steps_done, done, ran);
 }
@@ -1500,6 +1520,276 @@ extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max
     }
     (void) dia_gen_drop(c);
     return rc;
+}
+
+// ---- continuous session (include/tts_hip.h; kernels in dia_kernels.h) ---------------------------------------------------------------------
+// The loop of tts_hip_dia_generate at a fixed n_utt == n_slots: every replay steps all 2 * n_slots rows through the same dia_forward, so what
+// a live slot computes does not depend on who else is live.  Budget, uniforms and the parked flag are device memory: an admission changes
+// values, never the captured launches.
+static const int DIA_STREAM_GRAPH_KEY = 9100002;
+
+static int dia_stream_ready(tts_hip_ctx *c, const char *what, bool need_session = true) {
+    if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
+    if (need_session && !c->ds.active) return set_err("%s: no session (tts_hip_dia_stream_begin)", what);
+    return 0;
+}
+
+static DiaLoopArgs dia_stream_loop_args(tts_hip_ctx *c) {
+    const auto &g = c->ds;
+    DiaLoopArgs la{};
+    la.n_utt = (int) g.n_slots; la.n_out = c->NO;
+    la.bos = g.codes.bos; la.eos = g.codes.eos; la.pad = g.codes.pad; la.max_delay = g.codes.max_delay; la.max_gen = g.max_gen;
+    for (int i = 0; i < 16; i++) la.delay_pattern[i] = g.codes.delay_pattern[i];
+    la.ids = c->di_ids; la.pos = c->di_pos;
+    la.delay = (int32_t *) c->di_loop; la.done = c->di_loop + c->di_U; la.call = c->di_loop + 2 * c->di_U;
+    la.tok = c->di_stok; la.hist = c->di_hist;
+    return la;
+}
+
+// session pre-step, the forward of dia_loop_step at U = n_slots, guidance, sampler (parked slots sit out), post-step
+static int dia_stream_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
+    const auto &g = c->ds;
+    const int U = (int) g.n_slots, NO = c->NO, V = c->di_V;
+    DiaStreamArgs st{};
+    st.budget = c->di_sbud; st.steps = c->di_sbud + c->di_U; st.cend = c->di_cend;
+    hipLaunchKernelGGL(dia_stream_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la, st);
+    HIPCHK(hipGetLastError());
+    c->di_park = true;
+    const int rc = dia_forward(c, U, (int) c->dia.max_gen, captured);
+    c->di_park = false;
+    CHK(rc);
+    if (g.sampled) {
+        SampleArgs sa{};
+        sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
+        sa.top_k = g.sp.top_k; sa.top_p = g.sp.top_p; sa.temperature = g.sp.temperature;
+        sa.uniforms = c->d_uniforms; sa.row_step = la.call; sa.out = c->di_stok; sa.idle = la.done;
+        if (g.rep) { sa.pen_table = c->d_pen; sa.pen_len = c->pen_len; sa.last_ids = c->d_last; sa.rep_counts = c->d_repc; }
+        hipLaunchKernelGGL(sample_kernel, dim3(NO, U), dim3(256), 0, c->stream, sa);
+    } else {
+        hipLaunchKernelGGL(argmax_kernel, dim3(U * NO), dim3(256), 0, c->stream, (const float *) c->di_guided, V, c->di_stok);
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(dia_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp) {
+    const char *what = "tts_hip_dia_stream_begin";
+    CHK(dia_stream_ready(c, what, false));
+    CHK(dia_no_session(c, what));
+    if (!codes) return set_err("%s: null argument", what);
+    if (n_slots == 0 || n_slots > (uint32_t) c->di_U) return set_err("%s: %u slots outside 1..%d (max_utterances)", what, n_slots, c->di_U);
+    const int G = (int) c->dia.max_gen, S = (int) c->dia.max_ctx, NO = c->NO, V = c->di_V, U = (int) n_slots;
+    if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("%s: max_gen %u outside 1..%d cached positions", what, max_gen, G);
+    if (codes->max_delay >= max_gen) return set_err("%s: max_gen %u must exceed max_delay %u", what, max_gen, codes->max_delay);
+    if (codes->bos >= (uint32_t) V || codes->eos >= (uint32_t) V || codes->pad >= (uint32_t) V) return set_err("%s: special ids outside the vocabulary %d", what, V);
+    if (sp) {
+        if (V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, V, SMP_VMAX);
+        if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f) || !(sp->repetition_penalty > 0.0f)) return set_err("%s: temperature, top_p, repetition_penalty must be > 0", what);
+    }
+    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
+    HIPCHK(hipSetDevice(c->device));
+    const bool rep = sp && sp->repetition_penalty != 1.0f;
+    if (sp) {
+        const std::vector<float> zero((size_t) max_gen * U * NO, 0.0f);   // sizes d_uniforms; the admissions fill the slots' columns
+        CHK(stage_uniforms(c, zero.data(), zero.size()));
+        CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
+    }
+    // every slot parked: ids BOS (the embedding reads them), position 0, one cross key, done; sampler::reset
+    {
+        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), loop((size_t) 4 * c->di_U, 0u), seq((size_t) 2 * U), one((size_t) 2 * U, 1u), bud((size_t) 2 * c->di_U, 0u);
+        for (int u = 0; u < U; u++) {
+            loop[(size_t) u] = 0xFFFFFFFFu; loop[(size_t) c->di_U + u] = 1u; loop[(size_t) 2 * c->di_U + u] = 1u;
+            seq[(size_t) 2 * u] = 2 * u; seq[(size_t) 2 * u + 1] = 2 * u + 1;
+            bud[(size_t) u] = max_gen;
+        }
+        HIPCHK(hipMemcpyAsync(c->di_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(c->di_pos, 0, (size_t) 2 * U * 4, c->stream));
+        HIPCHK(hipMemcpyAsync(c->di_seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->di_cend, one.data(), one.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->di_loop, loop.data(), loop.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->di_sbud, bud.data(), bud.size() * 4, hipMemcpyHostToDevice, c->stream));
+        if (rep) {
+            HIPCHK(hipMemsetAsync(c->d_last, 0xFF, (size_t) U * NO * 4, c->stream));
+            HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) U * NO * 4, c->stream));
+        }
+        // a slot no encoder pass has filled holds whatever its cross K/V held: the one position its parked rows attend over becomes zero
+        uint64_t clear = 0;
+        for (int u = 0; u < U; u++) if (!c->di_slot_encoded[(size_t) u]) clear |= 1ull << u;
+        if (clear) {
+            hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, c->di_ck, c->di_cv, clear, 2 * c->di_U, (int64_t) S,
+                               c->di_A);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals
+    }
+    // everything the captured launches hold by value: a change drops the session's graph
+    const int mode = sp ? 1 : 0;
+    const void *pen = rep ? (const void *) c->d_pen : nullptr;
+    const tts_hip_sampling spv = sp ? *sp : tts_hip_sampling{};
+    auto &bk = c->di_sbaked;
+    const bool same = bk.mode == mode && bk.U == n_slots && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
+                      (!sp || (bk.uni == c->d_uniforms && bk.pen == pen && memcmp(&bk.sp, &spv, sizeof(spv)) == 0));
+    if (!same) {
+        auto it = c->graphs.find(DIA_STREAM_GRAPH_KEY);
+        if (it != c->graphs.end()) { (void) hipGraphExecDestroy(it->second); c->graphs.erase(it); }
+        bk.mode = mode; bk.U = n_slots; bk.max_gen = max_gen; bk.codes = *codes; bk.uni = c->d_uniforms; bk.pen = pen; bk.sp = spv;
+    }
+    auto &g = c->ds;
+    g = tts_hip_ctx::DiaStream{};
+    g.active = true; g.sampled = sp != nullptr; g.rep = rep;
+    g.n_slots = n_slots; g.max_gen = max_gen; g.codes = *codes; g.sp = spv;
+    g.slot.assign((size_t) U, tts_hip_ctx::DiaStream::FREE);
+    g.steps.assign((size_t) U, 0u);
+    g.budget.assign((size_t) U, max_gen);
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
+                                        const float *uniforms) {
+    const char *what = "tts_hip_dia_stream_admit";
+    typedef tts_hip_ctx::DiaStream DS;
+    CHK(dia_stream_ready(c, what));
+    auto &g = c->ds;
+    if (n == 0) return 0;
+    if (!slots || !tokens || !sentence_len) return set_err("%s: null argument", what);
+    if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_gen][n_output_heads]", what);
+    const int S = (int) c->dia.max_ctx, NO = c->NO;
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
+        if (g.slot[slots[i]] == DS::LIVE || g.slot[slots[i]] == DS::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
+        if (sentence_len[i] == 0 || sentence_len[i] > (uint32_t) S) return set_err("%s: utterance %u: sentence length %u outside 1..%d", what, i, sentence_len[i], S);
+        if (budget && (budget[i] <= g.codes.max_delay || budget[i] > g.max_gen))
+            return set_err("%s: utterance %u: budget %u outside max_delay %u < budget <= max_gen %u", what, i, budget[i], g.codes.max_delay, g.max_gen);
+        for (int t = 0; t < S; t++)
+            if (tokens[(size_t) i * S + t] >= (uint32_t) c->di_evocab) return set_err("%s: token %u >= encoder vocabulary %d", what, tokens[(size_t) i * S + t], c->di_evocab);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t per = (size_t) g.max_gen * NO;
+    if (g.sampled && n * per > c->di_suni_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        free_dev(c->di_suni);
+        c->di_suni = nullptr; c->di_suni_cap = 0;
+        HIPCHK(hipMalloc((void **) &c->di_suni, n * per * 4));
+        c->di_suni_cap = n * per;
+    }
+    // the encoder and the cross K/V of each slot (stream order: the running slots' steps of the last run are behind us), then one launch for all
+    for (uint32_t i = 0; i < n; i++) {
+        CHK(dia_encode_into(c, slots[i], tokens + (size_t) i * S, sentence_len[i], nullptr));
+        c->di_slot_encoded[slots[i]] = 1;
+    }
+    std::vector<uint32_t> adm((size_t) 2 * n);
+    for (uint32_t i = 0; i < n; i++) { adm[i] = slots[i]; adm[(size_t) n + i] = budget ? budget[i] : g.max_gen; }
+    HIPCHK(hipMemcpyAsync(c->di_sadm, adm.data(), adm.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (g.sampled) HIPCHK(hipMemcpyAsync(c->di_suni, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
+    DiaAdmitArgs a{};
+    a.n = (int) n; a.n_slots = (int) g.n_slots; a.n_out = NO;
+    a.bos = g.codes.bos; a.max_gen = g.max_gen; a.max_ctx = (uint32_t) S;
+    a.slots = c->di_sadm; a.budgets = c->di_sadm + n;
+    a.uni_in = g.sampled ? c->di_suni : nullptr; a.uni = c->d_uniforms;
+    a.last = g.rep ? c->d_last : nullptr; a.repc = c->d_repc;
+    a.ids = c->di_ids; a.pos = c->di_pos; a.cend = c->di_cend;
+    a.delay = (int32_t *) c->di_loop; a.done = c->di_loop + c->di_U; a.call = c->di_loop + 2 * c->di_U; a.handed = c->di_loop + 3 * c->di_U;
+    a.budget = c->di_sbud; a.steps = c->di_sbud + c->di_U;
+    const unsigned bx = g.sampled ? (unsigned) std::min<size_t>((per + 255) / 256, 64) : 1u;
+    hipLaunchKernelGGL(dia_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));   // adm is a local, uniforms the caller's
+    for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DS::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; }
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
+    const char *what = "tts_hip_dia_stream_run";
+    typedef tts_hip_ctx::DiaStream DS;
+    CHK(dia_stream_ready(c, what));
+    auto &g = c->ds;
+    if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    // a live slot parks in the pre-step at position budget - 1 at the latest: no replay beyond the last one any live slot can need
+    uint32_t need = 0;
+    for (uint32_t s = 0; s < g.n_slots; s++)
+        if (g.slot[s] == DS::LIVE) need = std::max(need, g.budget[s] - std::min(g.steps[s], g.budget[s] - 1));
+    const uint32_t k = std::min(n_steps, need);
+    if (k != 0) {
+        HIPCHK(hipSetDevice(c->device));
+        const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
+        const DiaLoopArgs la = dia_stream_loop_args(c);
+        for (uint32_t i = 0; i < k; i++) {
+            if (!use_graph) {
+                CHK(dia_stream_step(c, la, false));
+                continue;
+            }
+            auto it = c->graphs.find(DIA_STREAM_GRAPH_KEY);
+            if (it != c->graphs.end()) {
+                HIPCHK(hipGraphLaunch(it->second, c->stream));
+                continue;
+            }
+            // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
+            CHK(dia_stream_step(c, la, false));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            hipGraph_t graph = nullptr;
+            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            const int rc = dia_stream_step(c, la, true);
+            const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+            if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
+            if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
+            hipGraphExec_t exec = nullptr;
+            HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            (void) hipGraphDestroy(graph);
+            c->graphs.emplace(DIA_STREAM_GRAPH_KEY, exec);
+        }
+        // the look-in: one launch, one copy, one synchronise
+        const int U = (int) g.n_slots;
+        hipLaunchKernelGGL(dia_stream_look_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, U, (const uint32_t *) c->di_pos, (const uint32_t *) (c->di_loop + c->di_U),
+                           (const uint32_t *) (c->di_sbud + c->di_U), c->di_look);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) 2 * U * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t s = 0; s < g.n_slots; s++) {
+            if (g.slot[s] != DS::LIVE) continue;
+            g.steps[s] = c->h_di_look[2 * s];
+            if (c->h_di_look[2 * s + 1]) g.slot[s] = DS::ENDED;
+        }
+    }
+    for (uint32_t s = 0; s < g.n_slots; s++) {
+        if (g.slot[s] != DS::ENDED) continue;
+        finished_slots[*n_finished] = s;
+        finished_steps[*n_finished] = g.steps[s];
+        (*n_finished)++;
+        g.slot[s] = DS::REPORTED;
+    }
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t steps, uint32_t *tokens_out) {
+    const char *what = "tts_hip_dia_stream_collect";
+    CHK(dia_stream_ready(c, what));
+    auto &g = c->ds;
+    if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
+    if (g.slot[slot] != tts_hip_ctx::DiaStream::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_dia_stream_run reports it)", what, slot);
+    if (steps > g.steps[slot]) return set_err("%s: slot %u made %u steps, %u asked for", what, slot, g.steps[slot], steps);
+    if (steps == 0) return 0;
+    if (!tokens_out) return set_err("%s: null argument", what);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(tokens_out, c->di_hist + (size_t) slot * g.max_gen * c->NO, (size_t) steps * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_end(tts_hip_ctx *c) {
+    if (!c || !c->has_dia) return set_err("tts_hip_dia_stream_end: not a Dia context (tts_hip_dia_create)");
+    if (!c->ds.active) return 0;
+    (void) hipSetDevice(c->device);
+    // the other entry points expect the cross extent of every row to be the whole text context
+    const std::vector<uint32_t> cend((size_t) 2 * c->di_U, c->dia.max_ctx);
+    (void) hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream);
+    (void) hipStreamSynchronize(c->stream);
+    c->ds = tts_hip_ctx::DiaStream{};
+    return 0;
 }
 
 extern "C" int tts_hip_dia_step(tts_hip_ctx *c, const uint32_t *ids, uint32_t pos, float *logits_out, float *raw_out) {

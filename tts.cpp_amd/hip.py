@@ -93,6 +93,7 @@ EXPORTS = [
     "tts_hip_orpheus_stream_begin", "tts_hip_orpheus_stream_admit", "tts_hip_orpheus_stream_run", "tts_hip_orpheus_stream_collect", "tts_hip_orpheus_stream_end",
     "tts_hip_orpheus_sample_logits_rows",
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
+    "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
 ]
 
 class Sampling(C.Structure):
@@ -208,6 +209,11 @@ def load_lib():
     L.tts_hip_dia_gen_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes), C.POINTER(Sampling), f32p]
     L.tts_hip_dia_gen_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_dia_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p]
+    L.tts_hip_dia_stream_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes), C.POINTER(Sampling)]
+    L.tts_hip_dia_stream_admit.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, f32p]
+    L.tts_hip_dia_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
+    L.tts_hip_dia_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
+    L.tts_hip_dia_stream_end.argtypes = [vp]
     _lib = L
     return L
 
@@ -867,6 +873,7 @@ class DiaEngine:
         d.dec_hidden_size, d.dec_layers, d.dec_attn_heads, d.dec_kv_heads = cfg.dec_hidden, cfg.dec_layers, cfg.dec_heads, cfg.dec_kv_heads
         d.head_dim, d.n_output_heads, d.output_vocab_size, d.max_ctx, d.max_gen = cfg.head_dim, cfg.n_out, cfg.out_vocab, cfg.max_ctx, cfg.max_gen
         d.cfg_scale, d.flags = cfg_scale, flags
+        self._stream = (max(1, max_utterances), cfg.max_gen)   # (slots, max_gen) of the continuous session
         self.ctx = self.L.tts_hip_dia_create(device, C.byref(d))
         if not self.ctx:
             raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
@@ -956,6 +963,48 @@ class DiaEngine:
         self._chk(self.L.tts_hip_dia_gen_wait(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)) if take else None, steps.ctypes.data_as(C.POINTER(C.c_uint32)),
                                               done.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(ran)))
         return out, steps.copy(), done.astype(bool).copy(), ran.value
+
+    # ---- continuous session (tts_hip_dia_stream_*) ----
+    def stream_begin(self, n_slots, max_gen, delay_pattern, bos, eos, pad, max_delay, sampled=False, top_k=50, top_p=1.0, temperature=1.0, repetition_penalty=1.0):
+        codes = DiaCodes(bos, eos, pad, max_delay)
+        for i, d in enumerate(delay_pattern):
+            codes.delay_pattern[i] = int(d)
+        sp = Sampling(top_k, top_p, temperature, repetition_penalty)
+        self._chk(self.L.tts_hip_dia_stream_begin(self.ctx, n_slots, max_gen, C.byref(codes), C.byref(sp) if sampled else None))
+        self._stream = (n_slots, max_gen)
+
+    def stream_admit(self, slots, tokens, sentence_lens, budgets=None, uniforms=None):
+        """tokens: one [max_ctx] id array per slot; budgets None: max_gen each; uniforms [n][max_gen][n_out] for a sampled session"""
+        s, sp = _u32(slots)
+        n = s.size
+        t, tp = _u32(np.asarray(tokens, dtype=np.uint32).reshape(-1))
+        assert t.size == n * self.cfg.max_ctx
+        ln, lp = _u32(sentence_lens)
+        bp = None
+        if budgets is not None:
+            b, bp = _u32(budgets)
+            assert b.size == n
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n, self._stream[1], self.cfg.n_out)
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_dia_stream_admit(self.ctx, n, sp, tp, lp, bp, up))
+
+    def stream_run(self, n_steps):
+        """-> [(slot, steps)] of the slots that finished"""
+        cap = self._stream[0]
+        fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
+        self._chk(self.L.tts_hip_dia_stream_run(self.ctx, n_steps, C.byref(n), fs.ctypes.data_as(C.POINTER(C.c_uint32)), fn.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_collect(self, slot, steps):
+        """-> [steps][n_out] ids in generation order (before adjust_output_tokens)"""
+        out = np.zeros((max(steps, 1), self.cfg.n_out), dtype=np.uint32)
+        self._chk(self.L.tts_hip_dia_stream_collect(self.ctx, slot, steps, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:steps].copy()
+
+    def stream_end(self):
+        self._chk(self.L.tts_hip_dia_stream_end(self.ctx))
 
     def step(self, ids, pos, want_raw=False):
         a, ap = _u32(ids)

@@ -107,9 +107,11 @@ struct tts_generation_runner : tts_runner {
     // The reference's server hands one task at a time to a worker that owns a whole model (examples/server/server.cpp:126-158, 236-271);
     // generate_batch widened that to "form a batch from the queue, run it to the end".  A session keeps the lock-step forward full instead:
     // stream_submit() enters an utterance into a free row at the next look-in point (parler_runner: every 32 decode steps; orpheus_runner: every
-    // 28 ids, admitted at once into a free cache slot), stream_step() runs one such interval and hands back the utterances that ended inside
-    // it, already decoded to audio.  An utterance's audio is that of a generate() call of its own.  parler_runner and orpheus_runner have a
-    // session; a runner without the extension (dia_runner, kokoro_runner) reports 0 capacity and the callers fall back to generate_batch.
+    // 28 ids, admitted at once into a free cache slot; dia_runner: every 16 steps, queued by stream_submit and admitted — text encoder included —
+    // at the start of the next stream_step), stream_step() runs one such interval and hands back the utterances that ended inside
+    // it, already decoded to audio.  An utterance's audio is that of a generate() call of its own (dia_runner: the same ids, the audio within
+    // 1e-5 because the finished utterances of an interval share one batched codec pass).  parler_runner, orpheus_runner and dia_runner have a
+    // session; a runner without the extension (kokoro_runner) reports 0 capacity and the callers fall back to generate_batch.
     // Orpheus' SNAC noise block: a session decodes an utterance when it finishes, so the never-reseeded engine's draws follow the order in
     // which utterances finish; with TTS_SNAC_NO_NOISE the audio is bit for bit generate()'s (see the chunked-audio note below).
     struct stream_result {

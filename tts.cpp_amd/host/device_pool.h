@@ -54,7 +54,7 @@ struct pool_options {
     std::string      text_encoder_path;    // T5 GGUF for CONDITIONAL_PROMPT tasks (server --text-encoder-path, :263-271)
     bool             share_weights = true; // parse + upload each model once: RCCL broadcast across devices, one arena per device
     // continuous batching: a worker keeps ONE generation session per run of compatible requests and admits queued requests into rows that
-    // free up while the others are still generating (tts_generation_runner::stream_*; parler_runner every 32 decode steps, orpheus_runner every 28 ids), instead of forming a batch from
+    // free up while the others are still generating (tts_generation_runner::stream_*; parler_runner every 32 decode steps, orpheus_runner every 28 ids, dia_runner every 16 steps), instead of forming a batch from
     // what is queued and running it to the end — a request that arrives one step late no longer waits a whole generation, and a ragged
     // batch refills instead of idling.  Runners without a session (stream_capacity() == 0) keep the batch path.
     bool             continuous = false;

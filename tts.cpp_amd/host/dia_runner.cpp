@@ -428,3 +428,104 @@ void dia_runner::generate_batch_chunked(const std::vector<std::string> & sentenc
     chunker hook{*this, chunk_frames, on_chunk};
     last_batch_tokens = run_utterances(n, max_gen, config, &hook);
 }
+
+// ---- continuous batching (common.h; tts_hip_dia_stream_* underneath) -------------------------------------------------------------------
+// Decoder steps between two look-ins: the distance tts_hip_dia_generate and run_utterances use.  A parked slot waits at most 15 steps for its
+// successor, a look-in (one launch, one small copy, one synchronise) is spread over 16 steps of about 2 ms.
+void dia_runner::stream_begin(const generation_configuration & config) {
+    if (stream_capacity() == 0) TTS_ABORT("stream_begin: the runner was loaded with max_seqs=%u; a session needs >= 2 (TTS_HIP_MAX_SEQS)\n", max_seqs);
+    if (getenv("TTS_HOST_LOOP")) TTS_ABORT("stream_begin: TTS_HOST_LOOP asks for the host loop; a session runs on the device\n");
+    if (st_on) stream_end();
+    st_max_gen = begin_call(config);
+    st_cfg = config;
+    tts_hip_dia_codes codes{};
+    codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
+    for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
+    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+    const uint32_t slots = stream_capacity();
+    hip_check(tts_hip_dia_stream_begin(lm, slots, st_max_gen, &codes, config.sample ? &sp : nullptr), "tts_hip_dia_stream_begin");
+    st_free.clear();
+    for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
+    st_ticket.assign(slots, 0);
+    st_wait.clear();
+    st_live = 0;
+    st_on = true;
+    last_batch_tokens.clear();
+}
+
+void dia_runner::stream_submit(size_t ticket, const std::string & sentence) {
+    if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
+    if (stream_free() == 0) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
+    waiting w;
+    w.ticket = ticket;
+    w.len = dia_tokenize_sentence(hp, sentence, w.prompt);
+    st_wait.push_back(std::move(w));
+}
+
+void dia_runner::stream_step(std::vector<stream_result> & finished) {
+    if (!st_on) TTS_ABORT("stream_step: no session (stream_begin)\n");
+    finished.clear();
+    const uint32_t nh = hp.n_output_heads, S = hp.max_encoder_context_length;
+    if (!st_wait.empty()) {   // everything queued, in one admission
+        const uint32_t n = (uint32_t) st_wait.size();
+        std::vector<uint32_t> slots(n), tokens((size_t) n * S, 0u), lens(n);
+        std::vector<float>    uni;
+        if (st_cfg.sample) uni.resize((size_t) n * st_max_gen * nh);
+        for (uint32_t i = 0; i < n; i++) {
+            slots[i] = st_free[st_free.size() - 1 - i];
+            lens[i] = st_wait[i].len;
+            std::copy(st_wait[i].prompt.begin(), st_wait[i].prompt.begin() + std::min<size_t>(S, st_wait[i].prompt.size()), tokens.begin() + (size_t) i * S);
+            if (st_cfg.sample) {   // the draws of a generate() call of this utterance's own (run_utterances with n = 1)
+                sampler s = smp;
+                s.seed = st_cfg.seed; s.n_calls = 0;
+                for (uint32_t k = 0; k < st_max_gen; k++) s.draw_uniforms(uni.data() + ((size_t) i * st_max_gen + k) * nh);
+            }
+        }
+        hip_check(tts_hip_dia_stream_admit(lm, n, slots.data(), tokens.data(), lens.data(), nullptr, st_cfg.sample ? uni.data() : nullptr), "tts_hip_dia_stream_admit");
+        for (uint32_t i = 0; i < n; i++) { st_ticket[slots[i]] = st_wait[i].ticket; st_free.pop_back(); }
+        st_live += n;
+        st_wait.clear();
+    }
+    std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());
+    uint32_t nf = 0;
+    hip_check(tts_hip_dia_stream_run(lm, LOOK_IN, &nf, fs.data(), fn.data()), "tts_hip_dia_stream_run");
+    if (nf == 0) return;
+    std::vector<uint32_t> codes, frames(nf);
+    for (uint32_t i = 0; i < nf; i++) {   // in slot order
+        std::vector<uint32_t> ids((size_t) fn[i] * nh), f;
+        hip_check(tts_hip_dia_stream_collect(lm, fs[i], fn[i], ids.data()), "tts_hip_dia_stream_collect");
+        st_free.push_back(fs[i]);
+        st_live--;
+        dia_adjust_output_tokens(hp, ids, f);
+        frames[i] = (uint32_t) (f.size() / nh);
+        codes.insert(codes.end(), f.begin(), f.end());
+        const size_t ticket = st_ticket[fs[i]];
+        if (ticket < 4096) {   // generate_stream's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
+            if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
+            last_batch_tokens[ticket] = ids;
+        }
+        last_output_tokens = std::move(ids);
+    }
+    size_t total = 0;
+    for (uint32_t f : frames) total += (size_t) f * hp.up_sampling_factor;
+    pcm.assign(total, 0.0f);
+    if (total) hip_check(tts_hip_dac_decode_batch(dac, codes.data(), frames.data(), nf, pcm.data()), "tts_hip_dac_decode_batch");   // one batched codec pass
+    size_t off = 0;
+    for (uint32_t i = 0; i < nf; i++) {
+        stream_result r;
+        r.ticket = st_ticket[fs[i]];
+        r.audio.data = frames[i] ? pcm.data() + off : nullptr;
+        r.audio.n_outputs = (size_t) frames[i] * hp.up_sampling_factor;
+        off += r.audio.n_outputs;
+        finished.push_back(r);
+    }
+}
+
+void dia_runner::stream_end() {
+    if (!st_on) return;
+    (void) tts_hip_dia_stream_end(lm);
+    st_on = false;
+    st_free.clear();
+    st_wait.clear();
+    st_live = 0;
+}

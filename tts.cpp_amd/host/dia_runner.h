@@ -62,6 +62,18 @@ struct dia_runner final : tts_generation_runner {
                           const std::function<bool(const float *, size_t)> & on_chunk) override;
     void generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
                                 const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) override;
+    // extension: continuous batching (common.h) on tts_hip_dia_stream_*: max_seqs utterance slots stepped as one fixed lock-step forward; a slot
+    // whose countdown ended is parked on the device and refilled at the next look-in (every 16 steps).  stream_submit tokenises and queues,
+    // stream_step admits everything queued in one call (the encoder passes run there), runs one interval, un-delays and decodes what finished
+    // in one batched codec pass.  An utterance's tokens are those of a generate() call of its own (a fixed seed draws that call's uniforms).
+    // The session runs on the device loop only: stream_begin aborts under TTS_HOST_LOOP instead of falling back.
+    uint32_t stream_capacity() const override { return max_seqs > 1 ? max_seqs : 0; }
+    void     stream_begin(const generation_configuration & config) override;
+    uint32_t stream_free() const override { return st_on ? (uint32_t) st_free.size() - (uint32_t) st_wait.size() : 0; }
+    uint32_t stream_live() const override { return st_live + (uint32_t) st_wait.size(); }
+    void     stream_submit(size_t ticket, const std::string & sentence) override;
+    void     stream_step(std::vector<stream_result> & finished) override;
+    void     stream_end() override;
     uint32_t batch_capacity() const override { return max_seqs; }
     uint32_t max_seqs = 1;
     std::vector<std::vector<uint32_t>> last_batch_tokens;
@@ -76,6 +88,14 @@ struct dia_runner final : tts_generation_runner {
     int                dac_halo = -1;   // tts_hip_dac_halo_frames of the codec: frames of context a chunk's window needs on each side
 
   private:
+    // session state of the continuous batching
+    struct waiting { size_t ticket = 0; std::vector<uint32_t> prompt; uint32_t len = 0; };
+    bool                     st_on = false;
+    generation_configuration st_cfg{};
+    uint32_t                 st_max_gen = 0, st_live = 0;
+    std::vector<uint32_t>    st_free;     // free utterance slots
+    std::vector<size_t>      st_ticket;   // slot -> ticket
+    std::vector<waiting>     st_wait;     // submitted, admitted by the next stream_step
     struct chunker;
     uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
     void     encode_single(const char * sentence);
