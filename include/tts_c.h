@@ -71,6 +71,15 @@ typedef int (*tts_c_chunk_fn)(void *user, int utterance, const float *pcm, size_
 int           tts_c_generate_chunked(tts_c_runner *r, const char *text, const tts_c_config *cfg, uint32_t chunk_frames, tts_c_chunk_fn fn, void *user);
 int           tts_c_generate_batch_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,
                                            tts_c_chunk_fn fn, void *user);
+/* Extension: chunked audio out of the continuous session (tts_generation_runner::generate_stream_chunked): tts_c_generate_stream's loop with
+ * every utterance's PCM handed to fn in consecutive pieces of at most chunk_frames codec frames; utterance = the text's index, the pieces of
+ * different utterances interleave, those of one utterance arrive in order and concatenate to its tts_c_generate_stream audio.  fn returning 0
+ * drops that utterance only; the others go on.  Returns 0 when done, 1 when fn dropped at least one utterance, another value with
+ * tts_c_last_error() on error (chunk_frames == 0 is one).  Dia's session chunks while its slots keep running: the codec pass of the windows
+ * that became final at one look-in runs under the next 16 decoder steps, and a dropped utterance's slot is parked at the next look-in.  The
+ * sessions of Parler-TTS and Orpheus, and Kokoro's groups, hand each finished utterance out as one chunk. */
+int           tts_c_generate_stream_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,
+                                            tts_c_chunk_fn fn, void *user);
 /* Test hook: the Parler runner's un-delay rule (parler_undelay) on delayed tokens [n_steps][n_heads] — the codes of the kept frames that are
  * final after n_steps steps (finished != 0: the generation is over, every frame is judged).  out [frames][n_heads] may be NULL to count;
  * returns the number of frames. */

@@ -414,8 +414,19 @@ int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps
  *            — one launch, one copy, one synchronise — that reads every slot's sampler calls and parked flag.  Slots whose countdown ended are
  *            reported with their step counts.  (No budget ends at admission: budget = max_delay + 1 makes max_delay sampler calls and is reported
  *            by the run that contains them, like any other.)  With no live slot nothing is launched.
- *   collect  the first `steps` history rows [steps][n_output_heads] of a reported slot, before that slot is admitted again
- *   end      ends the session; the slots stay encoded with their last occupants
+ *            run is launch followed by a wait that takes no rows.
+ *   launch   what run enqueues — the same cap from the live budgets, the eager first step and the capture, the same graph — and returns without
+ *            synchronising.  A launch must be followed by a wait.
+ *   wait     waits for the launched steps and looks in — one gather launch, one copy into pinned memory, one synchronise, whatever n_slots is:
+ *            steps_done [n_slots] = sampler calls each slot's occupant has made, done [n_slots] = the slot is parked (each may be NULL), the
+ *            slots whose countdown ended as run reports them, and — when tokens_out != NULL — the history rows of every slot that no earlier
+ *            wait handed out, written at their places in tokens_out [n_slots][max_gen][n_output_heads] (NULL: they stay for a later wait).
+ *            A slot's rows start at 0 again once it is admitted again.  With nothing launched a wait is a pure look-in.
+ *   drop     parks n live slots at once, between a wait and the next launch, in one launch: done, the step count, position 0, one cross key,
+ *            sampler call 1 — what the parking pre-step writes.  The slots are free again without being reported.
+ *   collect  the first `steps` history rows [steps][n_output_heads] of a reported slot, before that slot is admitted again; it works as before
+ *            after waits that took rows
+ *   end      ends the session (steps in flight are waited for and dropped); the slots stay encoded with their last occupants
  * Parking: a slot is free when it has finished, was never admitted, or has been collected and not admitted again.  The pre-step that ends a
  * slot's countdown parks it: both rows move to position 0 and their cross extent to one key, so from that step on its self-attention and its
  * cross-attention read one position each, it records nothing and its sampler state stands still (a finished row of tts_hip_dia_generate keeps
@@ -423,6 +434,11 @@ int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps
  * Equality: an utterance's ids and step count are those of tts_hip_dia_generate on a context with n_utt = n_slots, the utterance in the same
  * slot, max_gen = its budget and its uniforms in that slot's column — the same forward at the same row count, whoever else is live, parked or
  * admitted meanwhile (tests/test_gpu_dia_stream.py); greedy, they are also those of its one-utterance tts_hip_dia_generate at the test shapes.
+ * The rows the waits hand out for an occupant tile its history without gap or overlap; they are what collect returns and what the same session
+ * returns through run / collect, whatever the launch sizes are — hence the ids of tts_hip_dia_generate at n_utt = n_slots — and dropping a slot
+ * changes no other slot's ids (tests/test_gpu_dia_stream_chunked.py).
+ * Ordering: admit, collect, drop, run or a second launch while steps are in flight return non-zero before anything is launched and leave the
+ * session as it was; so does a drop of a slot that is not live, is >= n_slots or is named twice.
  * Between begin and end every other generation call on the context (tts_hip_dia_encode*, _step*, _generate, gen_begin / gen_launch / gen_wait)
  * is refused with an error, and so is a second begin.  Every misuse (n_slots > max_utterances, a busy slot, a slot >= n_slots or named twice,
  * collect on a slot that has not been reported or for more steps than it made, a budget outside (max_delay, max_gen], a sentence length outside
@@ -431,6 +447,10 @@ int tts_hip_dia_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_ge
 int tts_hip_dia_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
                              const float *uniforms);
 int tts_hip_dia_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps);
+int tts_hip_dia_stream_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_dia_stream_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                            uint32_t *finished_steps);
+int tts_hip_dia_stream_drop(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots);
 int tts_hip_dia_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t steps, uint32_t *tokens_out);
 int tts_hip_dia_stream_end(tts_hip_ctx *ctx);
 

@@ -147,7 +147,8 @@ static __global__ __launch_bounds__(64) void dia_lookin_kernel(DiaLookArgs a) {
 //   dia_stream_prestep_kernel   dia_prestep_kernel with budget[u] for max_gen, plus parking
 //   dia_stream_admit_kernel     one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column
 //   dia_stream_clear_kernel     begin: zero cross K/V at position 0 of the slots no encoder pass has filled (what their parked rows attend over)
-//   dia_stream_look_kernel      the look-in: {sampler calls, parked flag} of every slot into one block
+//   dia_stream_lookin_kernel    the look-in: {sampler calls, parked flag, the history rows no earlier look-in took} of every slot into one block
+//   dia_stream_drop_kernel      parks live slots at once, between a look-in and the next step (what the parking pre-step writes)
 // The post-step is dia_poststep_kernel unchanged.
 // ------------------------------------------------------------------------------------------------
 struct DiaStreamArgs {
@@ -227,9 +228,41 @@ static __global__ __launch_bounds__(256) void dia_stream_clear_kernel(float *ck,
     cv[at] = 0.0f;
 }
 
-static __global__ void dia_stream_look_kernel(int n_slots, const uint32_t *pos, const uint32_t *done, const uint32_t *steps, uint32_t *block) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_slots) return;
-    block[2 * u] = done[u] ? steps[u] : pos[2 * u];
-    block[2 * u + 1] = done[u];
+// dia_lookin_kernel under the session's rules: one workgroup per slot, and the count so far is steps[u] once the slot has parked (parking
+// moved its position to 0).  A slot's rows restart at 0 with every admission (dia_stream_admit_kernel resets handed[u]); the rows of a
+// parked slot stay in hist until then, so a look-in after the parking step still finds them.  take = 0: the header only.
+static __global__ __launch_bounds__(64) void dia_stream_lookin_kernel(DiaLookArgs a, const uint32_t *steps) {
+    const int u = blockIdx.x;
+    if (u >= a.n_utt) return;
+    const uint32_t parked = a.done[u];
+    const uint32_t from = a.handed[u], to = min(parked ? steps[u] : a.pos[2 * u], a.max_gen);
+    const uint32_t rows = a.take && to > from ? min(to - from, a.cap) : 0u;
+    uint32_t *slot = a.block + (int64_t) u * (2 + (int64_t) a.cap * a.n_out);
+    const uint32_t *src = a.hist + ((int64_t) u * a.max_gen + from) * a.n_out;
+    for (uint32_t i = threadIdx.x; i < rows * (uint32_t) a.n_out; i += blockDim.x) slot[2 + i] = src[i];
+    __syncthreads();   // every thread has read handed[u]
+    if (threadIdx.x == 0) {
+        slot[0] = to;   // sampler calls made so far; the host derives `rows` from it as this kernel does
+        slot[1] = parked;
+        a.handed[u] = from + rows;
+    }
+}
+
+struct DiaDropArgs {
+    int n;
+    const uint32_t *slots;   // [n] distinct live slots
+    uint32_t *pos, *done, *call, *steps, *cend;
+};
+
+// one thread per dropped slot: the values the parking pre-step writes.  The slot's history rows stay where they are.
+static __global__ void dia_stream_drop_kernel(DiaDropArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t u = a.slots[i];
+    if (a.done[u]) return;   // parked by the last step before the host saw it: steps[u] is already the occupant's
+    a.steps[u] = a.pos[2 * u];
+    a.done[u] = 1;
+    a.pos[2 * u] = 0; a.pos[2 * u + 1] = 0;
+    a.cend[2 * u] = 1; a.cend[2 * u + 1] = 1;
+    a.call[u] = 1;
 }

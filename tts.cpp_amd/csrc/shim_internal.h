@@ -208,6 +208,9 @@ struct tts_hip_ctx {
         std::vector<uint8_t> slot;       // per slot, one of the above
         std::vector<uint32_t> steps;     // per slot at the last look-in: sampler calls made
         std::vector<uint32_t> budget;    // per slot: the occupant's step budget
+        std::vector<uint32_t> handed;    // per slot: history rows of the occupant handed out by stream_wait (the host's copy of di_loop's fourth array)
+        uint32_t in_flight = 0;          // steps enqueued by stream_launch that no stream_wait has waited for
+        uint32_t unread = 0;             // steps enqueued since the last stream_wait that took rows: bounds the rows a look-in can find
     } ds;
     uint32_t *di_sbud = nullptr;         // device [2][U]: budget, steps
     uint32_t *di_sadm = nullptr;         // device [2][U]: slots, budgets of one admission

@@ -1535,6 +1535,11 @@ static int dia_stream_ready(tts_hip_ctx *c, const char *what, bool need_session 
     return 0;
 }
 
+// a launch must be followed by a wait: admit, collect, drop and a second launch find the state they read or write still moving
+static int dia_stream_idle(tts_hip_ctx *c, const char *what) {
+    return c->ds.in_flight ? set_err("%s: %u steps are in flight (tts_hip_dia_stream_wait first)", what, c->ds.in_flight) : 0;
+}
+
 static DiaLoopArgs dia_stream_loop_args(tts_hip_ctx *c) {
     const auto &g = c->ds;
     DiaLoopArgs la{};
@@ -1644,6 +1649,7 @@ extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32
     g.slot.assign((size_t) U, tts_hip_ctx::DiaStream::FREE);
     g.steps.assign((size_t) U, 0u);
     g.budget.assign((size_t) U, max_gen);
+    g.handed.assign((size_t) U, 0u);
     return 0;
 }
 
@@ -1652,6 +1658,7 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
     const char *what = "tts_hip_dia_stream_admit";
     typedef tts_hip_ctx::DiaStream DS;
     CHK(dia_stream_ready(c, what));
+    CHK(dia_stream_idle(c, what));
     auto &g = c->ds;
     if (n == 0) return 0;
     if (!slots || !tokens || !sentence_len) return set_err("%s: null argument", what);
@@ -1698,63 +1705,91 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
     hipLaunchKernelGGL(dia_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // adm is a local, uniforms the caller's
-    for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DS::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; }
+    for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DS::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; g.handed[slots[i]] = 0; }
     return 0;
 }
 
-extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
-    const char *what = "tts_hip_dia_stream_run";
+// enqueues min(n_steps, what the live budgets leave) replays; no copy, no synchronise after the graph exists
+static int dia_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
     typedef tts_hip_ctx::DiaStream DS;
-    CHK(dia_stream_ready(c, what));
     auto &g = c->ds;
-    if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
-    *n_finished = 0;
     // a live slot parks in the pre-step at position budget - 1 at the latest: no replay beyond the last one any live slot can need
     uint32_t need = 0;
     for (uint32_t s = 0; s < g.n_slots; s++)
         if (g.slot[s] == DS::LIVE) need = std::max(need, g.budget[s] - std::min(g.steps[s], g.budget[s] - 1));
     const uint32_t k = std::min(n_steps, need);
-    if (k != 0) {
-        HIPCHK(hipSetDevice(c->device));
-        const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
-        const DiaLoopArgs la = dia_stream_loop_args(c);
-        for (uint32_t i = 0; i < k; i++) {
-            if (!use_graph) {
-                CHK(dia_stream_step(c, la, false));
-                continue;
-            }
+    if (k == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
+    const DiaLoopArgs la = dia_stream_loop_args(c);
+    for (uint32_t i = 0; i < k; i++) {
+        if (!use_graph) {
+            CHK(dia_stream_step(c, la, false));
+        } else {
             auto it = c->graphs.find(DIA_STREAM_GRAPH_KEY);
             if (it != c->graphs.end()) {
                 HIPCHK(hipGraphLaunch(it->second, c->stream));
-                continue;
+            } else {
+                // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
+                CHK(dia_stream_step(c, la, false));
+                HIPCHK(hipStreamSynchronize(c->stream));
+                hipGraph_t graph = nullptr;
+                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+                const int rc = dia_stream_step(c, la, true);
+                const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+                if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
+                if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
+                hipGraphExec_t exec = nullptr;
+                HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+                (void) hipGraphDestroy(graph);
+                c->graphs.emplace(DIA_STREAM_GRAPH_KEY, exec);
             }
-            // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
-            CHK(dia_stream_step(c, la, false));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            hipGraph_t graph = nullptr;
-            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = dia_stream_step(c, la, true);
-            const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-            if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-            if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-            hipGraphExec_t exec = nullptr;
-            HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void) hipGraphDestroy(graph);
-            c->graphs.emplace(DIA_STREAM_GRAPH_KEY, exec);
         }
-        // the look-in: one launch, one copy, one synchronise
-        const int U = (int) g.n_slots;
-        hipLaunchKernelGGL(dia_stream_look_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, U, (const uint32_t *) c->di_pos, (const uint32_t *) (c->di_loop + c->di_U),
-                           (const uint32_t *) (c->di_sbud + c->di_U), c->di_look);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) 2 * U * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t s = 0; s < g.n_slots; s++) {
-            if (g.slot[s] != DS::LIVE) continue;
-            g.steps[s] = c->h_di_look[2 * s];
-            if (c->h_di_look[2 * s + 1]) g.slot[s] = DS::ENDED;
-        }
+        g.in_flight++; g.unread++;
     }
+    return 0;
+}
+
+// the look-in: one launch, one copy, one synchronise.  tokens_out != NULL takes the rows no earlier look-in took.
+static int dia_stream_look(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done) {
+    typedef tts_hip_ctx::DiaStream DS;
+    auto &g = c->ds;
+    const int U = (int) g.n_slots, NO = c->NO;
+    HIPCHK(hipSetDevice(c->device));
+    DiaLookArgs a{};
+    a.n_utt = U; a.n_out = NO; a.max_gen = g.max_gen;
+    a.take = tokens_out ? 1 : 0;
+    // a slot's un-taken rows were all recorded by steps enqueued since the last look-in that took rows (an admission starts at row 0), and
+    // di_look holds max_generation_size >= max_gen rows per slot
+    a.cap = a.take ? std::min(g.unread, g.max_gen) : 0u;
+    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.hist = c->di_hist; a.handed = c->di_loop + 3 * c->di_U; a.block = c->di_look;
+    const size_t slot = 2 + (size_t) a.cap * NO;
+    hipLaunchKernelGGL(dia_stream_lookin_kernel, dim3(U), dim3(64), 0, c->stream, a, (const uint32_t *) (c->di_sbud + c->di_U));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) U * slot * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    g.in_flight = 0;
+    for (int u = 0; u < U; u++) {
+        const uint32_t *s = c->h_di_look + (size_t) u * slot;
+        const uint32_t from = g.handed[(size_t) u], to = s[0];
+        const uint32_t rows = a.take && to > from ? std::min(to - from, a.cap) : 0u;
+        if (rows) memcpy(tokens_out + ((size_t) u * g.max_gen + from) * NO, s + 2, (size_t) rows * NO * 4);
+        g.handed[(size_t) u] = from + rows;
+        if (steps_done) steps_done[u] = to;
+        if (done) done[u] = s[1] != 0;
+        if (g.slot[(size_t) u] != DS::LIVE) continue;
+        g.steps[(size_t) u] = to;
+        if (s[1]) g.slot[(size_t) u] = DS::ENDED;
+    }
+    if (a.take) g.unread = 0;
+    return 0;
+}
+
+// slots a look-in saw parked and no call has reported yet, in slot order
+static void dia_stream_report(tts_hip_ctx *c, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
+    typedef tts_hip_ctx::DiaStream DS;
+    auto &g = c->ds;
+    *n_finished = 0;
     for (uint32_t s = 0; s < g.n_slots; s++) {
         if (g.slot[s] != DS::ENDED) continue;
         finished_slots[*n_finished] = s;
@@ -1762,12 +1797,68 @@ extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t
         (*n_finished)++;
         g.slot[s] = DS::REPORTED;
     }
+}
+
+extern "C" int tts_hip_dia_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    const char *what = "tts_hip_dia_stream_launch";
+    CHK(dia_stream_ready(c, what));
+    CHK(dia_stream_idle(c, what));
+    return dia_stream_launch(c, n_steps);
+}
+
+extern "C" int tts_hip_dia_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                                       uint32_t *finished_steps) {
+    const char *what = "tts_hip_dia_stream_wait";
+    CHK(dia_stream_ready(c, what));
+    if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    CHK(dia_stream_look(c, tokens_out, steps_done, done));
+    dia_stream_report(c, n_finished, finished_slots, finished_steps);
+    return 0;
+}
+
+// launch + a wait that takes no rows; with no live slot nothing is launched and nothing is looked at
+extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
+    const char *what = "tts_hip_dia_stream_run";
+    CHK(dia_stream_ready(c, what));
+    if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    CHK(dia_stream_idle(c, what));
+    CHK(dia_stream_launch(c, n_steps));
+    if (c->ds.in_flight) CHK(dia_stream_look(c, nullptr, nullptr, nullptr));
+    dia_stream_report(c, n_finished, finished_slots, finished_steps);
+    return 0;
+}
+
+extern "C" int tts_hip_dia_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
+    const char *what = "tts_hip_dia_stream_drop";
+    typedef tts_hip_ctx::DiaStream DS;
+    CHK(dia_stream_ready(c, what));
+    CHK(dia_stream_idle(c, what));
+    auto &g = c->ds;
+    if (n == 0) return 0;
+    if (!slots) return set_err("%s: null argument", what);
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
+        if (g.slot[slots[i]] != DS::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(c->di_sadm, slots, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));   // n <= n_slots <= max_utterances
+    DiaDropArgs a{};
+    a.n = (int) n; a.slots = c->di_sadm;
+    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.call = c->di_loop + 2 * c->di_U; a.steps = c->di_sbud + c->di_U; a.cend = c->di_cend;
+    hipLaunchKernelGGL(dia_stream_drop_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));   // slots is the caller's
+    for (uint32_t i = 0; i < n; i++) g.slot[slots[i]] = DS::FREE;
     return 0;
 }
 
 extern "C" int tts_hip_dia_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t steps, uint32_t *tokens_out) {
     const char *what = "tts_hip_dia_stream_collect";
     CHK(dia_stream_ready(c, what));
+    CHK(dia_stream_idle(c, what));
     auto &g = c->ds;
     if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
     if (g.slot[slot] != tts_hip_ctx::DiaStream::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_dia_stream_run reports it)", what, slot);
@@ -1784,6 +1875,7 @@ extern "C" int tts_hip_dia_stream_end(tts_hip_ctx *c) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_stream_end: not a Dia context (tts_hip_dia_create)");
     if (!c->ds.active) return 0;
     (void) hipSetDevice(c->device);
+    (void) hipStreamSynchronize(c->stream);   // steps in flight are waited for and dropped
     // the other entry points expect the cross extent of every row to be the whole text context
     const std::vector<uint32_t> cend((size_t) 2 * c->di_U, c->dia.max_ctx);
     (void) hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream);

@@ -94,6 +94,7 @@ EXPORTS = [
     "tts_hip_orpheus_sample_logits_rows",
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
     "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
+    "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
 ]
 
 class Sampling(C.Structure):
@@ -214,6 +215,9 @@ def load_lib():
     L.tts_hip_dia_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
     L.tts_hip_dia_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
     L.tts_hip_dia_stream_end.argtypes = [vp]
+    L.tts_hip_dia_stream_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_dia_stream_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p, u32p, u32p]
+    L.tts_hip_dia_stream_drop.argtypes = [vp, C.c_uint32, u32p]
     _lib = L
     return L
 
@@ -972,6 +976,8 @@ class DiaEngine:
         sp = Sampling(top_k, top_p, temperature, repetition_penalty)
         self._chk(self.L.tts_hip_dia_stream_begin(self.ctx, n_slots, max_gen, C.byref(codes), C.byref(sp) if sampled else None))
         self._stream = (n_slots, max_gen)
+        # cells no stream_wait has written hold a marker, so that a test can tell what each wait handed out
+        self._stream_out = (np.full((n_slots, max_gen, self.cfg.n_out), 0xFFFFFFFF, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint8))
 
     def stream_admit(self, slots, tokens, sentence_lens, budgets=None, uniforms=None):
         """tokens: one [max_ctx] id array per slot; budgets None: max_gen each; uniforms [n][max_gen][n_out] for a sampled session"""
@@ -996,6 +1002,26 @@ class DiaEngine:
         fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
         self._chk(self.L.tts_hip_dia_stream_run(self.ctx, n_steps, C.byref(n), fs.ctypes.data_as(C.POINTER(C.c_uint32)), fn.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_launch(self, n_steps):
+        """tts_hip_dia_stream_launch: what stream_run enqueues, without waiting; stream_wait must follow"""
+        self._chk(self.L.tts_hip_dia_stream_launch(self.ctx, n_steps))
+
+    def stream_wait(self, take=True):
+        """-> (tokens [n_slots][max_gen][n_out] as handed out so far (a view; a slot's rows start at 0 again with its next occupant), sampler calls
+        per slot, parked per slot, [(slot, steps)] of the slots that finished); take=False looks in without taking rows"""
+        out, steps, done = self._stream_out
+        cap = self._stream[0]
+        fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
+        u32 = C.POINTER(C.c_uint32)
+        self._chk(self.L.tts_hip_dia_stream_wait(self.ctx, out.ctypes.data_as(u32) if take else None, steps.ctypes.data_as(u32), done.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 C.byref(n), fs.ctypes.data_as(u32), fn.ctypes.data_as(u32)))
+        return out, steps.copy(), done.astype(bool).copy(), [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_drop(self, slots):
+        """tts_hip_dia_stream_drop: park live slots at once; they are free again without being reported"""
+        s, sp = _u32(slots)
+        self._chk(self.L.tts_hip_dia_stream_drop(self.ctx, s.size, sp))
 
     def stream_collect(self, slot, steps):
         """-> [steps][n_out] ids in generation order (before adjust_output_tokens)"""

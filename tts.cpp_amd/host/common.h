@@ -128,6 +128,16 @@ struct tts_generation_runner : tts_runner {
     // any number of sentences through one session (more than batch_capacity() is fine); outputs[i].data valid until the next call on this runner
     void             generate_stream(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
                                      const generation_configuration & config);
+    // chunked audio out of a session, asked for between stream_begin and the first stream_submit: from then on stream_step hands every
+    // utterance's PCM to on_chunk(ticket, pcm, n) in consecutive pieces of at most chunk_frames codec frames while the rows keep running; an
+    // utterance appears in `finished` — with empty audio — once its last piece is out, and stream_live() counts it until then.  on_chunk
+    // returning false drops that utterance only: it is reported in `finished` with what it got, the others go on.  The default returns false:
+    // this runner's session does not chunk (parler_runner, orpheus_runner); dia_runner's does.
+    virtual bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t ticket, const float *, size_t)> on_chunk);
+    // generate_stream's loop with on_chunk(utterance, pcm, n), utterance = the sentence's index.  Where the session does not chunk, or there is
+    // none (kokoro_runner), each finished utterance is handed out as one chunk, the default generate_chunked has.  chunk_frames == 0 is an error.
+    void             generate_stream_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                             const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
 
     // ---- extension: chunked audio — PCM handed out while the utterance is still generating ------------------------------------------
     // on_chunk receives consecutive pieces of the utterance's audio, at most chunk_frames codec frames each (the last one may be shorter);

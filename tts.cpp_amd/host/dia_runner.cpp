@@ -214,15 +214,21 @@ struct dia_runner::chunker {
             w.emitted = end;
         }
     }
-    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
-    bool emit() {
-        if (row_of.empty()) return true;
+    // the planned windows through the codec into r.pcm, window after window
+    void decode() {
         const uint32_t U = r.hp.up_sampling_factor;
         size_t total = 0;
         for (size_t w = 0; w < row_of.size(); w++) total += (size_t) (keep1[w] - keep0[w]) * U;
         r.pcm.resize(total);
         hip_check(tts_hip_dac_decode_windows(r.dac, codes.data(), frames.data(), keep0.data(), keep1.data(), (uint32_t) row_of.size(), r.pcm.data()),
                   "tts_hip_dac_decode_windows");
+    }
+    void clear() { codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear(); }
+    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
+    bool emit() {
+        if (row_of.empty()) return true;
+        const uint32_t U = r.hp.up_sampling_factor;
+        decode();
         bool more = true;
         size_t off = 0;
         for (size_t w = 0; w < row_of.size() && more; w++) {
@@ -231,8 +237,26 @@ struct dia_runner::chunker {
                 more = on_chunk(row_of[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
             off += (size_t) nf * U;
         }
-        codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear();
+        clear();
         return more;
+    }
+    // the session's form: window w belongs to the utterance tickets[w] (its slot may have a new occupant by now); a false from `to` ends
+    // that utterance only — its ticket goes into `stopped`, the rest of its window is skipped and the other windows go on
+    void emit_session(const std::vector<size_t> & tickets, const std::function<bool(size_t, const float *, size_t)> & to, std::vector<size_t> & stopped) {
+        if (row_of.empty()) return;
+        const uint32_t U = r.hp.up_sampling_factor;
+        decode();
+        size_t off = 0;
+        for (size_t w = 0; w < row_of.size(); w++) {
+            const uint32_t nf = keep1[w] - keep0[w];
+            bool more = std::find(stopped.begin(), stopped.end(), tickets[w]) == stopped.end();
+            for (uint32_t f = 0; f < nf && more; f += chunk_frames) {
+                more = to(tickets[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
+                if (!more) stopped.push_back(tickets[w]);
+            }
+            off += (size_t) nf * U;
+        }
+        clear();
     }
 };
 
@@ -450,7 +474,27 @@ void dia_runner::stream_begin(const generation_configuration & config) {
     st_wait.clear();
     st_live = 0;
     st_on = true;
+    st_hook.reset();
+    st_closing.clear();
+    st_stopped.clear();
     last_batch_tokens.clear();
+}
+
+// chunked audio out of the session (common.h): the chunker's rows are the slots
+static const std::function<bool(uint32_t, const float *, size_t)> no_row_chunks;
+
+bool dia_runner::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
+    if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
+    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
+    if (st_live != 0 || !st_wait.empty()) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
+    const uint32_t slots = stream_capacity();
+    st_on_chunk = std::move(on_chunk);
+    st_hook.reset(new chunker{*this, chunk_frames, no_row_chunks});
+    st_hook->rows.assign(slots, {});
+    st_toks.assign(slots, {});
+    st_gen.assign(slots, false);
+    st_buf.assign((size_t) slots * st_max_gen * hp.n_output_heads, 0u);
+    return true;
 }
 
 void dia_runner::stream_submit(size_t ticket, const std::string & sentence) {
@@ -462,30 +506,114 @@ void dia_runner::stream_submit(size_t ticket, const std::string & sentence) {
     st_wait.push_back(std::move(w));
 }
 
+// everything queued, in one admission
+void dia_runner::admit_waiting() {
+    const uint32_t nh = hp.n_output_heads, S = hp.max_encoder_context_length;
+    if (st_wait.empty()) return;
+    const uint32_t n = (uint32_t) st_wait.size();
+    std::vector<uint32_t> slots(n), tokens((size_t) n * S, 0u), lens(n);
+    std::vector<float>    uni;
+    if (st_cfg.sample) uni.resize((size_t) n * st_max_gen * nh);
+    for (uint32_t i = 0; i < n; i++) {
+        slots[i] = st_free[st_free.size() - 1 - i];
+        lens[i] = st_wait[i].len;
+        std::copy(st_wait[i].prompt.begin(), st_wait[i].prompt.begin() + std::min<size_t>(S, st_wait[i].prompt.size()), tokens.begin() + (size_t) i * S);
+        if (st_cfg.sample) {   // the draws of a generate() call of this utterance's own (run_utterances with n = 1)
+            sampler s = smp;
+            s.seed = st_cfg.seed; s.n_calls = 0;
+            for (uint32_t k = 0; k < st_max_gen; k++) s.draw_uniforms(uni.data() + ((size_t) i * st_max_gen + k) * nh);
+        }
+    }
+    hip_check(tts_hip_dia_stream_admit(lm, n, slots.data(), tokens.data(), lens.data(), nullptr, st_cfg.sample ? uni.data() : nullptr), "tts_hip_dia_stream_admit");
+    for (uint32_t i = 0; i < n; i++) {
+        st_ticket[slots[i]] = st_wait[i].ticket;
+        st_free.pop_back();
+        if (st_hook) {   // a new occupant: its rows and its chunker row start at zero
+            st_toks[slots[i]].clear();
+            st_hook->rows[slots[i]] = {};
+            st_gen[slots[i]] = true;
+        }
+    }
+    st_live += n;
+    st_wait.clear();
+}
+
+// the windows the last plan cut, through the codec and out; then the utterances that ended before that plan have had their last chunk
+void dia_runner::hand_out(std::vector<stream_result> & finished) {
+    st_hook->emit_session(st_win_ticket, st_on_chunk, st_stopped);
+    st_win_ticket.clear();
+    for (size_t ticket : st_closing) {
+        stream_result r;
+        r.ticket = ticket;   // no audio: everything went through the hook
+        finished.push_back(r);
+    }
+    st_closing.clear();
+}
+
+void dia_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & ids) {
+    if (ticket < 4096) {   // generate_stream's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
+        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
+        last_batch_tokens[ticket] = ids;
+    }
+    last_output_tokens = ids;
+}
+
+// stream_step with a hook: the codec pass of the windows cut at the last look-in runs on the codec context while this interval's steps run.
+// The rows are un-delayed and cut into windows right after the wait that brought them (host work on at most 16 rows per slot) rather than
+// under the next launch: a slot that finished is handed to the next occupant by the admission that precedes that launch, so its tail has to
+// be out of the slot's row by then.
+void dia_runner::stream_step_chunked(std::vector<stream_result> & finished) {
+    const uint32_t nh = hp.n_output_heads, slots = stream_capacity();
+    admit_waiting();
+    hip_check(tts_hip_dia_stream_launch(lm, LOOK_IN), "tts_hip_dia_stream_launch");
+    hand_out(finished);
+    std::vector<uint32_t> fs(slots), fn(slots), steps(slots);
+    uint32_t nf = 0;
+    hip_check(tts_hip_dia_stream_wait(lm, st_buf.data(), steps.data(), nullptr, &nf, fs.data(), fn.data()), "tts_hip_dia_stream_wait");
+    std::vector<bool> ended(slots, false);
+    for (uint32_t i = 0; i < nf; i++) ended[fs[i]] = true;
+    std::vector<uint32_t> drop;
+    for (uint32_t s = 0; s < slots; s++) {
+        if (!st_gen[s]) continue;
+        const uint32_t * b = st_buf.data() + (size_t) s * st_max_gen * nh;
+        st_toks[s].insert(st_toks[s].end(), b + st_toks[s].size(), b + (size_t) steps[s] * nh);
+        const bool stopped = std::find(st_stopped.begin(), st_stopped.end(), st_ticket[s]) != st_stopped.end();
+        if (!ended[s] && !stopped) continue;
+        // the occupant leaves: its rows are on the host, the slot is free for the next admission
+        remember_tokens(st_ticket[s], st_toks[s]);
+        st_gen[s] = false;
+        st_free.push_back(s);
+        st_live--;
+        if (stopped) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
+            if (!ended[s]) drop.push_back(s);
+            st_toks[s].clear();
+            st_hook->rows[s] = {};
+            stream_result r;
+            r.ticket = st_ticket[s];
+            finished.push_back(r);
+            ended[s] = false;
+        } else {
+            st_closing.push_back(st_ticket[s]);
+        }
+    }
+    st_stopped.clear();
+    if (!drop.empty()) hip_check(tts_hip_dia_stream_drop(lm, (uint32_t) drop.size(), drop.data()), "tts_hip_dia_stream_drop");
+    st_hook->plan(st_toks, ended);
+    for (uint32_t s : st_hook->row_of) st_win_ticket.push_back(st_ticket[s]);
+    for (uint32_t s = 0; s < slots; s++)
+        if (ended[s]) { st_toks[s].clear(); st_hook->rows[s] = {}; }   // its tail is in the windows
+    if (st_live == 0) {   // nothing to run the codec under: the tails now
+        hand_out(finished);
+        st_stopped.clear();   // only utterances that had ended could be stopped here
+    }
+}
+
 void dia_runner::stream_step(std::vector<stream_result> & finished) {
     if (!st_on) TTS_ABORT("stream_step: no session (stream_begin)\n");
     finished.clear();
-    const uint32_t nh = hp.n_output_heads, S = hp.max_encoder_context_length;
-    if (!st_wait.empty()) {   // everything queued, in one admission
-        const uint32_t n = (uint32_t) st_wait.size();
-        std::vector<uint32_t> slots(n), tokens((size_t) n * S, 0u), lens(n);
-        std::vector<float>    uni;
-        if (st_cfg.sample) uni.resize((size_t) n * st_max_gen * nh);
-        for (uint32_t i = 0; i < n; i++) {
-            slots[i] = st_free[st_free.size() - 1 - i];
-            lens[i] = st_wait[i].len;
-            std::copy(st_wait[i].prompt.begin(), st_wait[i].prompt.begin() + std::min<size_t>(S, st_wait[i].prompt.size()), tokens.begin() + (size_t) i * S);
-            if (st_cfg.sample) {   // the draws of a generate() call of this utterance's own (run_utterances with n = 1)
-                sampler s = smp;
-                s.seed = st_cfg.seed; s.n_calls = 0;
-                for (uint32_t k = 0; k < st_max_gen; k++) s.draw_uniforms(uni.data() + ((size_t) i * st_max_gen + k) * nh);
-            }
-        }
-        hip_check(tts_hip_dia_stream_admit(lm, n, slots.data(), tokens.data(), lens.data(), nullptr, st_cfg.sample ? uni.data() : nullptr), "tts_hip_dia_stream_admit");
-        for (uint32_t i = 0; i < n; i++) { st_ticket[slots[i]] = st_wait[i].ticket; st_free.pop_back(); }
-        st_live += n;
-        st_wait.clear();
-    }
+    if (st_hook) return stream_step_chunked(finished);
+    const uint32_t nh = hp.n_output_heads;
+    admit_waiting();
     std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());
     uint32_t nf = 0;
     hip_check(tts_hip_dia_stream_run(lm, LOOK_IN, &nf, fs.data(), fn.data()), "tts_hip_dia_stream_run");
@@ -499,12 +627,7 @@ void dia_runner::stream_step(std::vector<stream_result> & finished) {
         dia_adjust_output_tokens(hp, ids, f);
         frames[i] = (uint32_t) (f.size() / nh);
         codes.insert(codes.end(), f.begin(), f.end());
-        const size_t ticket = st_ticket[fs[i]];
-        if (ticket < 4096) {   // generate_stream's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
-            if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
-            last_batch_tokens[ticket] = ids;
-        }
-        last_output_tokens = std::move(ids);
+        remember_tokens(st_ticket[fs[i]], ids);
     }
     size_t total = 0;
     for (uint32_t f : frames) total += (size_t) f * hp.up_sampling_factor;
@@ -528,4 +651,9 @@ void dia_runner::stream_end() {
     st_free.clear();
     st_wait.clear();
     st_live = 0;
+    st_hook.reset();
+    st_on_chunk = nullptr;
+    st_closing.clear();
+    st_stopped.clear();
+    st_win_ticket.clear();
 }

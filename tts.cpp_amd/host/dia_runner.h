@@ -70,10 +70,15 @@ struct dia_runner final : tts_generation_runner {
     uint32_t stream_capacity() const override { return max_seqs > 1 ? max_seqs : 0; }
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return st_on ? (uint32_t) st_free.size() - (uint32_t) st_wait.size() : 0; }
-    uint32_t stream_live() const override { return st_live + (uint32_t) st_wait.size(); }
+    uint32_t stream_live() const override { return st_live + (uint32_t) st_wait.size() + (uint32_t) st_closing.size(); }
     void     stream_submit(size_t ticket, const std::string & sentence) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
+    // chunked audio out of the session: with a hook set, stream_step launches its 16 steps (tts_hip_dia_stream_launch), decodes the windows
+    // cut at the last look-in in one tts_hip_dac_decode_windows pass on the codec context while they run, hands the chunks to on_chunk, then
+    // waits and takes the new rows of every live slot (tts_hip_dia_stream_wait).  An utterance is reported in `finished` (no audio) once its
+    // last chunk is out; on_chunk returning false drops that utterance only (tts_hip_dia_stream_drop), reported with what it got.
+    bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) override;
     uint32_t batch_capacity() const override { return max_seqs; }
     uint32_t max_seqs = 1;
     std::vector<std::vector<uint32_t>> last_batch_tokens;
@@ -97,6 +102,19 @@ struct dia_runner final : tts_generation_runner {
     std::vector<size_t>      st_ticket;   // slot -> ticket
     std::vector<waiting>     st_wait;     // submitted, admitted by the next stream_step
     struct chunker;
+    // ... with stream_chunks: the chunker's rows are the slots
+    std::unique_ptr<chunker>                              st_hook;
+    std::function<bool(size_t, const float *, size_t)>    st_on_chunk;
+    std::vector<std::vector<uint32_t>> st_toks;        // slot -> the occupant's still-delayed ids so far
+    std::vector<bool>                  st_gen;         // slot -> its occupant is generating
+    std::vector<uint32_t>              st_buf;         // what tts_hip_dia_stream_wait writes: [slots][max_gen][heads]
+    std::vector<size_t>                st_win_ticket;  // planned window -> ticket
+    std::vector<size_t>                st_closing;     // ended, rows on the host, last chunk not handed out yet
+    std::vector<size_t>                st_stopped;     // on_chunk returned false for these
+    void admit_waiting();
+    void hand_out(std::vector<stream_result> & finished);
+    void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
+    void stream_step_chunked(std::vector<stream_result> & finished);
     uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
     void     encode_single(const char * sentence);
     void     encode_batch(const std::vector<std::string> & sentences);

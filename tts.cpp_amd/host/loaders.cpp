@@ -84,6 +84,7 @@ void tts_generation_runner::stream_begin(const generation_configuration &) { TTS
 void tts_generation_runner::stream_submit(size_t, const std::string &) { TTS_ABORT("stream_submit: this runner has no continuous batching\n"); }
 void tts_generation_runner::stream_step(std::vector<stream_result> &) { TTS_ABORT("stream_step: this runner has no continuous batching\n"); }
 void tts_generation_runner::stream_end() {}
+bool tts_generation_runner::stream_chunks(uint32_t, std::function<bool(size_t, const float *, size_t)>) { return false; }
 
 // any number of sentences through one session: rows freed by utterances that finish are refilled from the list at the next look-in point
 void tts_generation_runner::generate_stream(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
@@ -117,6 +118,32 @@ void tts_generation_runner::generate_stream(const std::vector<std::string> & sen
             outputs[f.ticket].data = batch_store_[f.ticket].data();
             outputs[f.ticket].n_outputs = f.audio.n_outputs;
         }
+    }
+    stream_end();
+}
+
+// generate_stream's loop with the audio handed out in chunks: by the session itself where it chunks (stream_chunks), else every finished
+// utterance as one chunk
+void tts_generation_runner::generate_stream_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
+                                                    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("generate_stream_chunked: chunk_frames must be >= 1\n");
+    if (stream_capacity() == 0) {   // no session: generate_stream's groups
+        std::vector<tts_response> out;
+        generate_stream(sentences, out, config);
+        for (size_t i = 0; i < out.size(); i++)
+            if (out[i].n_outputs) (void) on_chunk((uint32_t) i, out[i].data, out[i].n_outputs);
+        return;
+    }
+    stream_begin(config);
+    const bool chunks = stream_chunks(chunk_frames, [&](size_t ticket, const float * pcm, size_t n) { return on_chunk((uint32_t) ticket, pcm, n); });
+    size_t next = 0;
+    std::vector<stream_result> fin;
+    while (next < sentences.size() || stream_live() > 0) {
+        while (next < sentences.size() && stream_free() > 0) { stream_submit(next, sentences[next]); next++; }
+        stream_step(fin);
+        if (chunks) continue;   // everything went through the hook
+        for (auto & f : fin)
+            if (f.audio.n_outputs) (void) on_chunk((uint32_t) f.ticket, f.audio.data, f.audio.n_outputs);
     }
     stream_end();
 }

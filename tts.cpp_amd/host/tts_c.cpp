@@ -132,6 +132,26 @@ int tts_c_generate_batch_chunked(tts_c_runner * r, const char * const * texts, i
     }
 }
 
+int tts_c_generate_stream_chunked(tts_c_runner * r, const char * const * texts, int n, const tts_c_config * cfg, uint32_t chunk_frames, tts_c_chunk_fn fn,
+                                  void * user) {
+    g_tts_throw_on_abort = true;
+    try {
+        if (!r) throw std::runtime_error("tts_c_generate_stream_chunked: null runner");
+        if (!fn) throw std::runtime_error("tts_c_generate_stream_chunked: null callback");
+        bool dropped = false;
+        std::vector<std::string> s(texts, texts + n);
+        ((tts_generation_runner *) r)->generate_stream_chunked(s, to_cfg(cfg), chunk_frames, [&](uint32_t utt, const float * pcm, size_t k) {
+            const bool more = fn(user, (int) utt, pcm, k) != 0;
+            dropped = dropped || !more;
+            return more;
+        });
+        return dropped ? 1 : 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
 int64_t tts_c_parler_final_frames(const uint32_t * tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, int finished, uint32_t * out,
                                   uint64_t cap_frames) {
     if (n_heads == 0) { g_c_err = "tts_c_parler_final_frames: n_heads == 0"; return -1; }

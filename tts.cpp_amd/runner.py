@@ -31,7 +31,8 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_pool_create", "tts_c_pool_set_text_encoder", "tts_c_pool_set_continuous", "tts_c_pool_set_continuous_yield_ms", "tts_c_pool_admitted_in_flight", "tts_c_pool_conditional_prompt", "tts_c_pool_submit", "tts_c_pool_wait", "tts_c_pool_release", "tts_c_pool_stats", "tts_c_pool_load_stats", "tts_c_pool_free", "tts_c_set_load_options", "tts_c_set_load_options_ex", "tts_c_runner_device_context", "tts_c_runner_tokenize",
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
-           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames"]
+           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
+           "tts_c_generate_stream_chunked"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -110,6 +111,7 @@ def load_lib():
         L.tts_c_pool_free.restype = None
         L.tts_c_generate_chunked.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
         L.tts_c_generate_batch_chunked.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
+        L.tts_c_generate_stream_chunked.argtypes = L.tts_c_generate_batch_chunked.argtypes
         L.tts_c_parler_final_frames.restype = C.c_int64
         L.tts_c_parler_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
         L.tts_c_dia_final_frames.restype = C.c_int64
@@ -225,6 +227,14 @@ class Runner:
         n = len(texts)
         arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
         return self._chunked(lambda fn: self.L.tts_c_generate_batch_chunked(self.h, arr, n, C.byref(c), chunk_frames, fn, None), on_chunk)
+
+    def generate_stream_chunked(self, texts, chunk_frames=32, on_chunk=None, **cfg):
+        """tts_c_generate_stream_chunked: any number of utterances through one session, [(utterance, pcm, arrival)] in arrival order;
+        on_chunk(utterance, pcm, arrival) returning False drops that utterance only (self.stopped: at least one was dropped)"""
+        c = make_config(**cfg) if cfg else self.cfg
+        n = len(texts)
+        arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
+        return self._chunked(lambda fn: self.L.tts_c_generate_stream_chunked(self.h, arr, n, C.byref(c), chunk_frames, fn, None), on_chunk)
 
     def tokenize(self, text):
         n = self.L.tts_c_runner_tokenize(self.h, text.encode("utf-8"), None, 0)
