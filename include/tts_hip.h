@@ -370,7 +370,8 @@ int tts_hip_dia_step_batch(tts_hip_ctx *ctx, uint32_t n_utt, const uint32_t *slo
  * tts_hip_dia_encode_slot): per step check_stopping (:767-785: EOS on head 0 or position max_gen - max_delay starts the countdown that
  * forces EOS / PAD into the delayed heads), the decoder step, guidance, sampler::sample (sampling != NULL; sample_kernel, any top_k /
  * top_p / temperature / repetition penalty at this vocabulary) or sampler::max (NULL), and the delay-pattern feedback (:795-803) run
- * as one captured graph; the host looks at the done flags every few steps.  uniforms [max_gen][n_utt][n_output_heads]: the draw for
+ * as one captured graph; the host looks at the done flags every few steps.  An utterance whose countdown has ended is parked (see the
+ * session below: it is the same loop with every slot live from the first step) while the others go on.  uniforms [max_gen][n_utt][n_output_heads]: the draw for
  * head h of utterance u at its k-th sampler call (ignored for sampler::max).  tokens_out [n_utt][max_gen][n_output_heads]: the
  * sampled ids in generation order (the runner's output_tokens before adjust_output_tokens); steps_out [n_utt]: sampler calls made. */
 typedef struct tts_hip_dia_codes {
@@ -382,7 +383,8 @@ int tts_hip_dia_generate(tts_hip_ctx *ctx, uint32_t n_utt, uint32_t max_gen, con
                          const float *uniforms, uint32_t *tokens_out, uint32_t *steps_out);
 /* The same loop in pieces, for callers that work on the ids while the decoder is still running (the runner's chunked audio un-delays
  * frames and decodes codec windows meanwhile); tts_hip_dia_generate is built on them.
- *   gen_begin   checks and stages what tts_hip_dia_generate does: uniforms, penalty table, loop state (ids = BOS, positions 0)
+ *   gen_begin   checks and stages what tts_hip_dia_generate does: uniforms, penalty table, loop state (every slot 0..n_utt-1 live: ids = BOS,
+ *               position 0, budget max_gen, the whole text context as cross extent)
  *   gen_launch  enqueues up to n_steps replays of the captured step (eager under TTS_HIP_FLAG_NO_GRAPH / profiling; the very first step
  *               runs eagerly and is then captured) and returns without waiting.  Never more than the max_gen + 1 pre-steps
  *               tts_hip_dia_generate allows; nothing once a gen_wait has seen every utterance done.
@@ -397,10 +399,10 @@ int tts_hip_dia_gen_begin(tts_hip_ctx *ctx, uint32_t n_utt, uint32_t max_gen, co
                           const float *uniforms);
 int tts_hip_dia_gen_launch(tts_hip_ctx *ctx, uint32_t n_steps);
 int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran);
-/* Continuous session: the loop of tts_hip_dia_generate with utterances entering and leaving while the others keep going.
- * Fixed shape: every step of a session steps all n_slots slots = 2 * n_slots rows through the decoder step tts_hip_dia_generate runs at
- * n_utt == n_slots (kernel selection depends on the row count, so it never changes inside a session), as one captured graph per session
- * configuration.  What belongs to a slot's occupant — its step budget, its uniforms, the parked flag — is device memory: an admission changes
+/* Continuous session: the loop of tts_hip_dia_generate — the same kernels and host code, not a copy — with utterances entering and leaving
+ * while the others keep going.  Fixed shape: every step of a session steps all n_slots slots = 2 * n_slots rows through the decoder step
+ * tts_hip_dia_generate runs at n_utt == n_slots (kernel selection depends on the row count, so it never changes inside a session), as one
+ * captured graph per session configuration (kept beside the one of the gen_* calls: alternating the two recaptures neither).  What belongs to a slot's occupant — its step budget, its uniforms, the parked flag — is device memory: an admission changes
  * values, never the captured launches.
  *   begin    n_slots <= max_utterances slots, every one parked; max_gen, codes and sampling as in tts_hip_dia_generate (sampling NULL:
  *            sampler::max), with its limits.  An unfinished gen_* loop is waited for and dropped.  Slots no encoder pass has filled get the one
@@ -429,8 +431,8 @@ int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps
  *   end      ends the session (steps in flight are waited for and dropped); the slots stay encoded with their last occupants
  * Parking: a slot is free when it has finished, was never admitted, or has been collected and not admitted again.  The pre-step that ends a
  * slot's countdown parks it: both rows move to position 0 and their cross extent to one key, so from that step on its self-attention and its
- * cross-attention read one position each, it records nothing and its sampler state stands still (a finished row of tts_hip_dia_generate keeps
- * attending over its whole history until the batch is done).
+ * cross-attention read one position each, it records nothing and its sampler state stands still.  A finished utterance of tts_hip_dia_generate
+ * / gen_* is parked the same way.  Leaving the loop (end; for gen_*, the call that drops it) sets every cross extent back to the whole context.
  * Equality: an utterance's ids and step count are those of tts_hip_dia_generate on a context with n_utt = n_slots, the utterance in the same
  * slot, max_gen = its budget and its uniforms in that slot's column — the same forward at the same row count, whoever else is live, parked or
  * admitted meanwhile (tests/test_gpu_dia_stream.py); greedy, they are also those of its one-utterance tts_hip_dia_generate at the test shapes.

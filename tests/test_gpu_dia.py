@@ -330,3 +330,78 @@ def test_dia_captured_step_folds_slice_merge_and_silu_into_the_projections(shape
     assert len(outs[1]) == 3 and all(len(o) > 0 for o in outs[1])
     for a, b in zip(outs[1], outs[0]):
         assert a.shape == b.shape and np.array_equal(a, b)
+
+
+PARK_TEXTS = ["[S1] first one.", "[S1] stop early.", "[S2] the second is long."]
+PARK_SEEDS = (20, 14, 21)
+PARK_MAX_GEN, PARK_TOP_K, PARK_STEPS = 40, 16, (39, 18, 39)
+# seed 14 on "[S1] stop early." is tests/test_gpu_dia_stream.py's EOS_SEED (EOS on head 0 at step 3, 3 + max_delay = 18 steps).  The other two were
+# found on the CPU the same way: orc.DiaOracle(build_dia(dia_tiny(), suppress_special=False)).generate(text, max_tokens=40, pick=orc_sampler_sample with
+# top_k 16 and np.random.default_rng(seed).random((max_gen, n_out), float32)[call]) for seeds 20..31: every seed runs the 39 steps of the budget on
+# "[S2] the second is long.", every seed but 26 (26 steps) on "[S1] first one."; the first of each that no other slot uses was taken.
+
+
+def test_dia_loop_parks_a_finished_row_while_its_neighbours_go_on():
+    """The fixed batch on the device loop (gen_begin / gen_launch(16) / gen_wait), three utterances of which the middle one draws EOS at step 3
+    and parks after 18 steps — position 0, one cross key, no sampler call — while the other two run the 39 steps of their budget: two whole
+    look-ins later.  The anchor runs no loop kernel and parks nothing: step_batch with all three slots in every step, the oracle's sampler
+    (orc_sampler_sample) and stopping rule (orc_dia_check_stopping) on the host, a finished utterance keeping its last ids and position as
+    dia_runner::run_utterances does under TTS_HOST_LOOP.  Same row count, same forward: ids equal exactly, the bar
+    test_dia_device_loop_equals_the_per_step_host_loop sets for this pair of paths.  A step right after the loop must see the whole text
+    context again (leaving the loop restores the cross extents that parking moved to one key)."""
+    import ctypes as C
+    model = synth.build_dia(synth.dia_tiny(), suppress_special=False)
+    cfg = model.cfg
+    n, max_gen = 3, PARK_MAX_GEN
+    eng = hip.DiaEngine(cfg, max_utterances=n)
+    eng.load(model)
+    for u, t in enumerate(PARK_TEXTS):
+        eng.encode_slot(u, *orc.dia_tokenize(t, cfg.max_ctx))
+    uni = np.stack([np.random.default_rng(s).random((max_gen, cfg.n_out), dtype=np.float32) for s in PARK_SEEDS], axis=1)   # [call][utt][head]
+    # the anchor
+    o = orc.DiaOracle(model, act_mode=1)          # for its stopping rule only
+    smps = []
+    for _ in range(n):
+        s = orc.Sampler()
+        orc.lib().orc_sampler_init(C.byref(s), cfg.n_out, cfg.out_vocab)
+        s.top_k, s.temperature, s.top_p, s.repetition_penalty, s.do_sample = PARK_TOP_K, 1.0, 1.0, 1.0, 1
+        orc.lib().orc_sampler_reset(C.byref(s))
+        smps.append(s)
+    ids = np.full((n, cfg.n_out), cfg.bos, dtype=np.uint32)
+    pos, delay, fin, ref = np.zeros(n, dtype=np.uint32), [-1] * n, [False] * n, [[] for _ in range(n)]
+    first = None
+    while True:
+        for u in range(n):
+            if not fin[u]:
+                fin[u], ids[u], delay[u] = o.check_stopping(ids[u], int(pos[u]), max_gen, delay[u])
+        if all(fin):
+            break
+        lg = eng.step_batch(ids, pos)
+        if first is None:
+            first = (ids.copy(), lg.copy())
+        for u in range(n):
+            if fin[u]:
+                continue
+            new = np.zeros(cfg.n_out, dtype=np.uint32)
+            orc.lib().orc_sampler_sample(C.byref(smps[u]), orc.f32p(np.ascontiguousarray(lg[u])), orc.f32p(np.ascontiguousarray(uni[len(ref[u]), u])), orc.u32p(new))
+            ref[u].append(new)
+            pos[u] += 1
+            ids[u] = [new[i] if pos[u] > i else cfg.bos for i in range(cfg.n_out)]
+    assert tuple(len(r) for r in ref) == PARK_STEPS
+    # the device loop
+    eng.gen_begin(n, max_gen, uniforms=uni, top_k=PARK_TOP_K, delay_pattern=[0, 8, 9, 10, 11, 12, 13, 14, 15], bos=cfg.bos, eos=cfg.eos, pad=cfg.pad,
+                  max_delay=cfg.max_delay)
+    seen = []
+    for _ in range(3):
+        eng.gen_launch(16)
+        toks, steps, done, ran = eng.gen_wait()
+        seen.append(done.tolist())
+    print("steps", steps.tolist(), "ran", ran, "done at the look-ins", seen)
+    assert seen == [[False, False, False], [False, True, False], [True, True, True]]      # 18 < 32: parked for the whole third interval at least
+    assert tuple(steps.tolist()) == PARK_STEPS
+    for u in range(n):
+        assert np.array_equal(toks[u, :steps[u]], np.array(ref[u], dtype=np.uint32)), u
+    assert toks[1, PARK_STEPS[1] - cfg.max_delay, 0] == cfg.eos
+    again = eng.step_batch(first[0], np.zeros(n, dtype=np.uint32))
+    assert np.array_equal(again, first[1])
+    eng.close()

@@ -53,12 +53,25 @@ static __global__ __launch_bounds__(256) void rows_to_f16_kernel(const float *x,
 // device-resident generation loop (dia_runner::generate_from_batch, dia/model.cpp:806-870 with check_stopping :767-785 and the
 // delay-pattern feedback :795-803): one thread per utterance slot keeps what the host loop keeps — the n_out input ids, the position,
 // the countdown, the sampled history — so that a step (pre-step, forward, guidance, sampler, post-step) replays as one hipGraph and
-// neither logits nor ids cross PCIe inside the loop.
-//   dia_prestep_kernel   check_stopping before each decode: start the countdown when head 0 produced EOS or the position reaches
-//                        max_gen - max_delay; during it force EOS / PAD into the heads whose delay has passed; mark the utterance done
-//                        when the countdown reaches 0.  Also publishes the 1-based sampler call index of this step.
-//   dia_poststep_kernel  record the sampled ids, advance the position (both guidance rows), feed head i its id once pos > i, BOS before.
-// A finished utterance keeps its rows in the step (lock-step shapes stay fixed): its position stays, its ids stay, nothing is recorded.
+// neither logits nor ids cross PCIe inside the loop.  One loop serves the fixed batch (tts_hip_dia_gen_*, tts_hip_dia_generate: n
+// encoded slots, all live from the first step, each with the budget max_gen) and the continuous session (tts_hip_dia_stream_*: n slots
+// that utterances enter and leave while the others keep going).  What differs per slot and per occupant lives in device memory, so an
+// admission never drops the captured graph:
+//   budget[u]   the occupant's max_gen (max_delay < budget <= max_gen of the loop); the history stride stays the loop's max_gen
+//   steps[u]    sampler calls the occupant made, written when the slot parks (its position does not survive parking)
+//   done[u]     the parked flag: set when the countdown ends, set for every slot by a session's begin, cleared by an admission
+// Parking: the pre-step that ends a countdown moves both rows of the slot to position 0 and their cross extent to one key, so from that
+// step on the slot's self-attention and cross-attention read one position each while its rows stay in the step (lock-step shapes stay
+// fixed); the post-step records nothing for it and sample_kernel leaves its state alone (SampleArgs::idle).  Whoever leaves the loop
+// sets the cross extents back to the whole text context.
+//   dia_loop_prestep_kernel   check_stopping before each decode: start the countdown when head 0 produced EOS or the position reaches
+//                             budget - max_delay; during it force EOS / PAD into the heads whose delay has passed; park the slot when
+//                             the countdown reaches 0.  Also publishes the 1-based sampler call index of this step.
+//   dia_loop_poststep_kernel  record the sampled ids, advance the position (both guidance rows), feed head i its id once pos > i, BOS before.
+//   dia_loop_lookin_kernel    the look-in: {sampler calls, parked flag, the history rows no earlier look-in took} of every slot into one block
+//   dia_stream_admit_kernel   one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column
+//   dia_stream_clear_kernel   begin: zero cross K/V at position 0 of the slots no encoder pass has filled (what their parked rows attend over)
+//   dia_stream_drop_kernel    parks live slots at once, between a look-in and the next step (what the parking pre-step writes)
 // ------------------------------------------------------------------------------------------------
 struct DiaLoopArgs {
     int n_utt, n_out;
@@ -71,99 +84,18 @@ struct DiaLoopArgs {
     uint32_t *call;       // [n_utt] 1-based index of the sampler call this step makes (sample_kernel's row_step)
     const uint32_t *tok;  // [n_utt][n_out] ids the sampler produced this step
     uint32_t *hist;       // [n_utt][max_gen][n_out]
+    const uint32_t *budget;   // [n_utt]
+    uint32_t *steps;          // [n_utt]
+    uint32_t *cend;           // [2 * n_utt] cross-attention extent of rows 2u, 2u+1
 };
 
-static __global__ void dia_prestep_kernel(DiaLoopArgs a) {
+static __global__ void dia_loop_prestep_kernel(DiaLoopArgs a) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= a.n_utt || a.done[u]) return;
     uint32_t *aud = a.ids + u * a.n_out;
     const uint32_t p = a.pos[2 * u];
     int d = a.delay[u];
-    if (d == -1 && (aud[0] == a.eos || p >= a.max_gen - a.max_delay)) d = (int) a.max_delay;
-    if (d > 0) {
-        const int after = (int) a.max_delay - d;
-        for (int i = 0; i < a.n_out; i++) {
-            if (after == (int) a.delay_pattern[i]) aud[i] = a.eos;
-            else if (after > (int) a.delay_pattern[i]) aud[i] = a.pad;
-        }
-        d -= 1;
-    }
-    a.delay[u] = d;
-    if (d == 0) a.done[u] = 1;
-    a.call[u] = p + 1;
-}
-
-static __global__ void dia_poststep_kernel(DiaLoopArgs a) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= a.n_utt || a.done[u]) return;
-    const uint32_t p = a.pos[2 * u];
-    for (int i = 0; i < a.n_out; i++) a.hist[((int64_t) u * a.max_gen + p) * a.n_out + i] = a.tok[u * a.n_out + i];
-    const uint32_t np = p + 1;
-    a.pos[2 * u] = np;
-    a.pos[2 * u + 1] = np;
-    for (int i = 0; i < a.n_out; i++) a.ids[u * a.n_out + i] = np > (uint32_t) i ? a.tok[u * a.n_out + i] : a.bos;
-}
-
-// A look-in of the loop in pieces (tts_hip_dia_gen_wait): one workgroup per utterance packs {position, done flag, the history rows no
-// earlier look-in took} into its slot of one contiguous block, so that the host learns everything from one launch, one copy and one
-// synchronisation however many utterances there are.  take = 0: the header only (the rows stay for a later look-in).
-struct DiaLookArgs {
-    int n_utt, n_out;
-    uint32_t max_gen;
-    uint32_t cap;            // rows a slot holds: the steps enqueued since the last look-in that took rows
-    int take;
-    const uint32_t *pos;     // [2 * n_utt]
-    const uint32_t *done;    // [n_utt]
-    const uint32_t *hist;    // [n_utt][max_gen][n_out]
-    uint32_t *handed;        // [n_utt] history rows taken so far
-    uint32_t *block;         // [n_utt][2 + cap * n_out]
-};
-
-static __global__ __launch_bounds__(64) void dia_lookin_kernel(DiaLookArgs a) {
-    const int u = blockIdx.x;
-    if (u >= a.n_utt) return;
-    const uint32_t from = a.handed[u], to = min(a.pos[2 * u], a.max_gen);
-    const uint32_t rows = a.take && to > from ? min(to - from, a.cap) : 0u;
-    uint32_t *slot = a.block + (int64_t) u * (2 + (int64_t) a.cap * a.n_out);
-    const uint32_t *src = a.hist + ((int64_t) u * a.max_gen + from) * a.n_out;
-    for (uint32_t i = threadIdx.x; i < rows * (uint32_t) a.n_out; i += blockDim.x) slot[2 + i] = src[i];
-    __syncthreads();   // every thread has read handed[u]
-    if (threadIdx.x == 0) {
-        slot[0] = to;   // sampler calls made so far; the host derives `rows` from it as this kernel does
-        slot[1] = a.done[u];
-        a.handed[u] = from + rows;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// continuous session (tts_hip_dia_stream_*): the loop above with a fixed number of slots that utterances enter and leave while the others
-// keep going.  What differs per slot and per occupant lives in device memory, so an admission never drops the captured graph:
-//   budget[u]   the occupant's max_gen (max_delay < budget <= max_gen of the session); the history stride stays the session's max_gen
-//   steps[u]    sampler calls the occupant made, written when the slot parks (its position does not survive parking)
-//   done[u]     the parked flag: set when the countdown ends, set for every slot by begin, cleared by an admission
-// Parking: the pre-step that ends a countdown moves both rows of the slot to position 0 and their cross extent to one key, so from that
-// step on the slot's self-attention and cross-attention read one position each (a finished row of the lock-step loop keeps attending
-// over its whole history); the post-step records nothing for it and sample_kernel leaves its state alone (SampleArgs::idle).
-//   dia_stream_prestep_kernel   dia_prestep_kernel with budget[u] for max_gen, plus parking
-//   dia_stream_admit_kernel     one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column
-//   dia_stream_clear_kernel     begin: zero cross K/V at position 0 of the slots no encoder pass has filled (what their parked rows attend over)
-//   dia_stream_lookin_kernel    the look-in: {sampler calls, parked flag, the history rows no earlier look-in took} of every slot into one block
-//   dia_stream_drop_kernel      parks live slots at once, between a look-in and the next step (what the parking pre-step writes)
-// The post-step is dia_poststep_kernel unchanged.
-// ------------------------------------------------------------------------------------------------
-struct DiaStreamArgs {
-    const uint32_t *budget;   // [n_slots]
-    uint32_t *steps;          // [n_slots]
-    uint32_t *cend;           // [2 * n_slots] cross-attention extent of rows 2u, 2u+1
-};
-
-static __global__ void dia_stream_prestep_kernel(DiaLoopArgs a, DiaStreamArgs s) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= a.n_utt || a.done[u]) return;
-    uint32_t *aud = a.ids + u * a.n_out;
-    const uint32_t p = a.pos[2 * u];
-    int d = a.delay[u];
-    if (d == -1 && (aud[0] == a.eos || p >= s.budget[u] - a.max_delay)) d = (int) a.max_delay;
+    if (d == -1 && (aud[0] == a.eos || p >= a.budget[u] - a.max_delay)) d = (int) a.max_delay;
     if (d > 0) {
         const int after = (int) a.max_delay - d;
         for (int i = 0; i < a.n_out; i++) {
@@ -176,10 +108,56 @@ static __global__ void dia_stream_prestep_kernel(DiaLoopArgs a, DiaStreamArgs s)
     a.call[u] = p + 1;
     if (d == 0) {   // park: this step's forward already reads one position per attention
         a.done[u] = 1;
-        s.steps[u] = p;
+        a.steps[u] = p;
         a.pos[2 * u] = 0; a.pos[2 * u + 1] = 0;
-        s.cend[2 * u] = 1; s.cend[2 * u + 1] = 1;
+        a.cend[2 * u] = 1; a.cend[2 * u + 1] = 1;
         a.call[u] = 1;
+    }
+}
+
+static __global__ void dia_loop_poststep_kernel(DiaLoopArgs a) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.n_utt || a.done[u]) return;
+    const uint32_t p = a.pos[2 * u];
+    for (int i = 0; i < a.n_out; i++) a.hist[((int64_t) u * a.max_gen + p) * a.n_out + i] = a.tok[u * a.n_out + i];
+    const uint32_t np = p + 1;
+    a.pos[2 * u] = np;
+    a.pos[2 * u + 1] = np;
+    for (int i = 0; i < a.n_out; i++) a.ids[u * a.n_out + i] = np > (uint32_t) i ? a.tok[u * a.n_out + i] : a.bos;
+}
+
+// A look-in: one workgroup per slot packs {sampler calls so far, parked flag, the history rows no earlier look-in took} into its slot of
+// one contiguous block, so that the host learns everything from one launch, one copy and one synchronisation however many slots there
+// are.  The count so far is steps[u] once the slot has parked (parking moved its position to 0).  A session slot's rows restart at 0 with
+// every admission (dia_stream_admit_kernel resets handed[u]); the rows of a parked slot stay in hist until then, so a look-in after the
+// parking step still finds them.  take = 0: the header only (the rows stay for a later look-in).
+struct DiaLookArgs {
+    int n_utt, n_out;
+    uint32_t max_gen;
+    uint32_t cap;            // rows a slot holds: the steps enqueued since the last look-in that took rows
+    int take;
+    const uint32_t *pos;     // [2 * n_utt]
+    const uint32_t *done;    // [n_utt]
+    const uint32_t *steps;   // [n_utt]
+    const uint32_t *hist;    // [n_utt][max_gen][n_out]
+    uint32_t *handed;        // [n_utt] history rows taken so far
+    uint32_t *block;         // [n_utt][2 + cap * n_out]
+};
+
+static __global__ __launch_bounds__(64) void dia_loop_lookin_kernel(DiaLookArgs a) {
+    const int u = blockIdx.x;
+    if (u >= a.n_utt) return;
+    const uint32_t parked = a.done[u];
+    const uint32_t from = a.handed[u], to = min(parked ? a.steps[u] : a.pos[2 * u], a.max_gen);
+    const uint32_t rows = a.take && to > from ? min(to - from, a.cap) : 0u;
+    uint32_t *slot = a.block + (int64_t) u * (2 + (int64_t) a.cap * a.n_out);
+    const uint32_t *src = a.hist + ((int64_t) u * a.max_gen + from) * a.n_out;
+    for (uint32_t i = threadIdx.x; i < rows * (uint32_t) a.n_out; i += blockDim.x) slot[2 + i] = src[i];
+    __syncthreads();   // every thread has read handed[u]
+    if (threadIdx.x == 0) {
+        slot[0] = to;   // sampler calls made so far; the host derives `rows` from it as this kernel does
+        slot[1] = parked;
+        a.handed[u] = from + rows;
     }
 }
 
@@ -226,26 +204,6 @@ static __global__ __launch_bounds__(256) void dia_stream_clear_kernel(float *ck,
     const int64_t at = ((int64_t) l * rows + r) * S * A + e;
     ck[at] = 0.0f;
     cv[at] = 0.0f;
-}
-
-// dia_lookin_kernel under the session's rules: one workgroup per slot, and the count so far is steps[u] once the slot has parked (parking
-// moved its position to 0).  A slot's rows restart at 0 with every admission (dia_stream_admit_kernel resets handed[u]); the rows of a
-// parked slot stay in hist until then, so a look-in after the parking step still finds them.  take = 0: the header only.
-static __global__ __launch_bounds__(64) void dia_stream_lookin_kernel(DiaLookArgs a, const uint32_t *steps) {
-    const int u = blockIdx.x;
-    if (u >= a.n_utt) return;
-    const uint32_t parked = a.done[u];
-    const uint32_t from = a.handed[u], to = min(parked ? steps[u] : a.pos[2 * u], a.max_gen);
-    const uint32_t rows = a.take && to > from ? min(to - from, a.cap) : 0u;
-    uint32_t *slot = a.block + (int64_t) u * (2 + (int64_t) a.cap * a.n_out);
-    const uint32_t *src = a.hist + ((int64_t) u * a.max_gen + from) * a.n_out;
-    for (uint32_t i = threadIdx.x; i < rows * (uint32_t) a.n_out; i += blockDim.x) slot[2 + i] = src[i];
-    __syncthreads();   // every thread has read handed[u]
-    if (threadIdx.x == 0) {
-        slot[0] = to;   // sampler calls made so far; the host derives `rows` from it as this kernel does
-        slot[1] = parked;
-        a.handed[u] = from + rows;
-    }
 }
 
 struct DiaDropArgs {

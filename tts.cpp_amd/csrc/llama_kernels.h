@@ -500,10 +500,10 @@ __global__ __launch_bounds__(256) void attn_gqa_split_kernel(const float *qkv, i
 // EXT (Dia's cross-attention over the 1024 text positions, 8 rows x 16 heads x 8 slices of 128 keys = U = 8 passes): the keys end at kend[r], row r reads
 // the cache of sequence row_seq[r], and the query arrives as qp.n_parts K-slice slabs to be folded and rotated (QPre) — folded by the first 128
 // threads through LDS (one more barrier, under the rows in flight), rotated in the lanes (a lane holds both halves of its NEOX pairs).
-// CLAMP (the Dia session, whose parked slots have kend[r] = 1): the requests stop at the row's last key instead of the last key of the context, so a
-// row with one key asks for that one row of K and V over and over (cache hits) instead of streaming the whole context only to mask it; kend[r] is
-// loaded next to row_seq[r], one round trip for both.  A row with kend[r] = n_ctx issues the requests of the unclamped kernel.
-template <int HD, int U, bool EXT = false, bool CLAMP = false>
+// EXT requests stop at the row's last key instead of the last key of the context: a parked slot of Dia's loop has kend[r] = 1, and its rows ask for
+// that one row of K and V over and over (cache hits) instead of streaming the whole context only to mask it; kend[r] is loaded next to row_seq[r],
+// one round trip for both.  A row with kend[r] = n_ctx issues the requests an unclamped kernel would.
+template <int HD, int U, bool EXT = false>
 __global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, int ld, const uint32_t *pos, const float *kcache, const float *vcache, int NH, int NKV,
                                                             float scale, float *part, int n_ctx, const uint32_t *kend = nullptr, const uint32_t *row_seq = nullptr,
                                                             int64_t seq_stride = 0, QPre qp = QPre{}) {
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, in
     const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
     const int kvH = NKV * HD, kh = h / (NH / NKV);
-    const int lim = CLAMP && kend ? max(1, min((int) kend[r], n_ctx)) : n_ctx;
+    const int lim = EXT && kend ? max(1, min((int) kend[r], n_ctx)) : n_ctx;
     if (EXT && row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
     // wave-uniform bases + one 32-bit byte offset per row (a sequence's cache is far below 4 GB): K and V of a key share the offset register
     const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);

@@ -1273,19 +1273,9 @@ static int run_step(tts_hip_ctx *c, int R, int mode, uint32_t bos, uint32_t eos)
     if (!use_graph) return enqueue_step_body(c, R, mode, bos, eos);
     const int key = mode * GRAPH_KEY_ROWS + R;
     auto it = c->graphs.find(key);
-    if (it == c->graphs.end()) {
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_step_body(c, R, mode, bos, eos);
-        const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-        if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-        hipGraphExec_t exec = nullptr;
-        HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        (void) hipGraphDestroy(graph);
-        it = c->graphs.emplace(key, exec).first;
-    }
-    HIPCHK(hipGraphLaunch(it->second, c->stream));
+    hipGraphExec_t exec = it != c->graphs.end() ? it->second : nullptr;
+    if (!exec) CHK(capture_graph(c, key, [&] { return enqueue_step_body(c, R, mode, bos, eos); }, &exec));
+    HIPCHK(hipGraphLaunch(exec, c->stream));
     return 0;
 }
 

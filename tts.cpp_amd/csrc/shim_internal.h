@@ -180,44 +180,41 @@ struct tts_hip_ctx {
     float *di_logits = nullptr, *di_guided = nullptr;
     uint32_t *di_tok = nullptr, *di_epos = nullptr, *di_eseq = nullptr, *di_kbeg = nullptr, *di_kend = nullptr;
     uint32_t *di_ids = nullptr, *di_pos = nullptr, *di_seq = nullptr, *di_cend = nullptr;
-    // device-resident generation loop (tts_hip_dia_generate): sampled ids [U][NO], countdown [U] / done [U] / sampler call [U], history [U][G][NO]
+    // device-resident generation loop: sampled ids [U][NO], countdown [U] / parked [U] / sampler call [U] / history rows handed out [U] in di_loop,
+    // history [U][G][NO]; a look-in packs per slot {sampler calls, parked, new history rows} into di_look, which travels to h_di_look (pinned)
+    // in one copy
     uint32_t *di_stok = nullptr, *di_loop = nullptr, *di_hist = nullptr;
-    // the loop in pieces (tts_hip_dia_gen_begin / _launch / _wait): di_loop carries a fourth array, history rows handed out [U]; a look-in
-    // packs per utterance {position, done, new history rows} into di_look, which travels to h_di_look (pinned) in one copy
     uint32_t *di_look = nullptr, *h_di_look = nullptr;
-    struct DiaGen {
-        bool active = false, sampled = false, rep = false, all_done = false;
-        uint32_t n_utt = 0, max_gen = 0;
-        tts_hip_dia_codes codes{};
-        tts_hip_sampling sp{};
-        uint32_t launched = 0;   // pre-steps enqueued so far (at most max_gen + 1)
-        uint32_t pending = 0;    // ... of which no gen_wait has waited for yet
-        uint32_t unread = 0;     // steps enqueued since the last gen_wait that took tokens: bounds the rows a look-in can find
-        std::vector<uint32_t> handed;   // per utterance: history rows handed out (the host's copy of di_loop's fourth array)
-    } dg;
     _Float16 *di_e16 = nullptr;   // [2 * max_ctx][max(EH, A, EF)] the encoder activations rounded to fp16 for gemm_tile_kernel
-    struct { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int mode = -1; uint32_t U = 0, max_gen = 0; tts_hip_dia_codes codes{}; } di_baked;
     int di_U = 1;                        // utterance slots (rows = 2 per slot)
-    // ---- Dia continuous session (tts_hip_dia_stream_*): the loop state of dg's arrays per slot, plus budget / steps [U] each in di_sbud ----
-    struct DiaStream {
-        bool active = false, sampled = false, rep = false;
-        uint32_t n_slots = 0, max_gen = 0;
+    // One loop, two ways in.  BATCH (tts_hip_dia_gen_begin / _launch / _wait, tts_hip_dia_generate): n encoded slots, all live from the first
+    // step with the budget max_gen, until the last one has parked.  SESSION (tts_hip_dia_stream_*): n slots that begin parked; admissions
+    // make them live, reports and collections free them again.
+    struct DiaLoop {
+        enum Mode : uint8_t { NONE = 0, BATCH = 1, SESSION = 2 };
+        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: seen parked by a look-in, not yet reported
+        Mode mode = NONE;
+        bool sampled = false, rep = false;
+        bool all_done = false;           // the last look-in found no live slot
+        uint32_t n = 0, max_gen = 0;     // utterances (BATCH) or slots (SESSION)
         tts_hip_dia_codes codes{};
         tts_hip_sampling sp{};
-        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: seen parked by a look-in, not yet reported
         std::vector<uint8_t> slot;       // per slot, one of the above
         std::vector<uint32_t> steps;     // per slot at the last look-in: sampler calls made
         std::vector<uint32_t> budget;    // per slot: the occupant's step budget
-        std::vector<uint32_t> handed;    // per slot: history rows of the occupant handed out by stream_wait (the host's copy of di_loop's fourth array)
-        uint32_t in_flight = 0;          // steps enqueued by stream_launch that no stream_wait has waited for
-        uint32_t unread = 0;             // steps enqueued since the last stream_wait that took rows: bounds the rows a look-in can find
-    } ds;
+        std::vector<uint32_t> handed;    // per slot: history rows of the occupant handed out (the host's copy of di_loop's fourth array)
+        uint32_t launched = 0;           // steps enqueued so far (BATCH: at most max_gen + 1)
+        uint32_t in_flight = 0;          // ... of which no look-in has waited for yet
+        uint32_t unread = 0;             // steps enqueued since the last look-in that took rows: bounds the rows a look-in can find
+    } dl;
+    // what the captured step of a mode holds by value: a begin that changes any of it drops that mode's graph (and only that one, so a
+    // caller alternating tts_hip_dia_generate and a session keeps both)
+    struct DiaBaked { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int sampled = -1; uint32_t n = 0, max_gen = 0; tts_hip_dia_codes codes{}; };
+    DiaBaked di_baked[2];                // [0] BATCH, [1] SESSION
     uint32_t *di_sbud = nullptr;         // device [2][U]: budget, steps
     uint32_t *di_sadm = nullptr;         // device [2][U]: slots, budgets of one admission
     float *di_suni = nullptr;            // device: the admitted utterances' uniforms before they move into their columns
     size_t di_suni_cap = 0;
-    bool di_park = false;                // the step being enqueued is a session step (launch_attn_gqa)
-    struct { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int mode = -1; uint32_t U = 0, max_gen = 0; tts_hip_dia_codes codes{}; } di_sbaked;
     std::vector<uint8_t> di_slot_encoded;   // tts_hip_dia_encode_slot has run for the slot
     uint32_t *h_di = nullptr;            // pinned staging: ids / pos / seq of a step
     // ---- Kokoro context (tts_hip_kokoro_create) ----
@@ -412,6 +409,28 @@ struct tts_hip_ctx {
     bool attn_fused = true;          // tune("attn_fused")=0: split-T self-attention keeps its separate combine launch and small batches stay unsplit
     uint32_t *attn_cnt = nullptr;    // [RMAX][heads] arrival counters of the fused combine (attn_kernel)
 };
+
+// One captured graph: begin-capture on the context's stream, `enqueue` (a callable returning 0 or an error code), end-capture, instantiate.
+// The exec is kept in c->graphs under `key` and handed back.  What has to run outside a capture (an eager pass that sets per-kernel
+// attributes) is the caller's business.
+template <class F>
+static int capture_graph(tts_hip_ctx *c, int key, F enqueue, hipGraphExec_t *out) {
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+    if (rc != 0 || e != hipSuccess) {
+        if (graph) (void) hipGraphDestroy(graph);
+        return rc != 0 ? rc : set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
+    }
+    hipGraphExec_t exec = nullptr;
+    const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void) hipGraphDestroy(graph);
+    if (ei != hipSuccess) return set_err("hipGraphInstantiate: %s", hipGetErrorString(ei));
+    c->graphs.emplace(key, exec);
+    *out = exec;
+    return 0;
+}
 
 // ---- shim_core.hip
 void free_dev(void *p);

@@ -63,12 +63,9 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
     } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
         // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through 3 rolling register slots
-        if (c->di_park)   // a session step: parked rows (kend[r] = 1) must not stream the context (attn_gqa_wave_kernel's CLAMP)
-            hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
-                               n_ctx_keys, kend, row_seq, seq_stride, qp);
-        else
-            hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys,
-                               kend, row_seq, seq_stride, qp);
+        // (the parked rows of a loop step, kend[r] = 1, request that one key only)
+        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys,
+                           kend, row_seq, seq_stride, qp);
     } else {
         hipLaunchKernelGGL(attn_gqa_split_kernel<128>, dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
                            kbeg, kend, row_seq, seq_stride, qp);
@@ -441,18 +438,13 @@ static int llama_gen_launch_one(tts_hip_ctx *c, const char *what, uint32_t n_ste
             // with the values the first replay writes again, nothing else)
             CHK(llama_forward(c, nullptr, 1, pos, (int) c->lm.n_ctx));
             HIPCHK(hipStreamSynchronize(c->stream));
-            hipGraph_t gr = nullptr;
-            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            int rc = llama_forward(c, nullptr, 1, 0, (int) c->lm.n_ctx);
-            if (rc == 0) rc = llama_select(c, sp, true, nullptr, true);
-            const hipError_t e = hipStreamEndCapture(c->stream, &gr);
-            if (rc != 0) { if (gr) (void) hipGraphDestroy(gr); return rc; }
-            if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-            HIPCHK(hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0));
-            (void) hipGraphDestroy(gr);
-            it = c->graphs.emplace(key, exec).first;
+            CHK(capture_graph(c, key, [&] {
+                const int rc = llama_forward(c, nullptr, 1, 0, (int) c->lm.n_ctx);
+                return rc ? rc : llama_select(c, sp, true, nullptr, true);
+            }, &exec));
+        } else {
+            exec = it->second;
         }
-        exec = it->second;
     }
     for (uint32_t s0 = 0; s0 < steps; s0 += LLAMA_GREEDY_CHUNK) {
         const uint32_t chunk = std::min<uint32_t>(LLAMA_GREEDY_CHUNK, steps - s0);
@@ -1099,12 +1091,13 @@ static int dia_rms(tts_hip_ctx *c, size_t w_off, int rows, int H, float *x, floa
     return hipGetLastError() == hipSuccess ? 0 : set_err("rms_fold_rows_kernel launch failed");
 }
 
-static int dia_gen_drop(tts_hip_ctx *c);
+typedef tts_hip_ctx::DiaLoop DL;
+static int dia_loop_end(tts_hip_ctx *c);
 static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out);
 
 // between tts_hip_dia_stream_begin and _end the loop state, the cross extents and the slots belong to the session
 static int dia_no_session(const tts_hip_ctx *c, const char *what) {
-    return c->ds.active ? set_err("%s: a continuous session is open on this context (tts_hip_dia_stream_end)", what) : 0;
+    return c->dl.mode == DL::SESSION ? set_err("%s: a continuous session is open on this context (tts_hip_dia_stream_end)", what) : 0;
 }
 
 extern "C" int tts_hip_dia_encode_slot(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens, uint32_t sentence_len, float *enc_out) {
@@ -1117,7 +1110,7 @@ extern "C" int tts_hip_dia_encode_slot(tts_hip_ctx *c, uint32_t slot, const uint
     if (sentence_len == 0 || sentence_len > (uint32_t) S) return set_err("tts_hip_dia_encode: sentence length %u outside 1..%d", sentence_len, S);
     for (int t = 0; t < S; t++)
         if (tokens[t] >= (uint32_t) c->di_evocab) return set_err("tts_hip_dia_encode: token %u >= encoder vocabulary %d", tokens[t], c->di_evocab);
-    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
+    CHK(dia_loop_end(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     return dia_encode_into(c, slot, tokens, sentence_len, enc_out);
 }
 
@@ -1296,7 +1289,7 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
         h_seq[2 * u] = 2 * slot; h_seq[2 * u + 1] = 2 * slot + 1;
         max_pos = std::max(max_pos, pos[u]);
     }
-    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
+    CHK(dia_loop_end(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(c->di_ids, h_ids, (size_t) U * NO * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->di_pos, h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1310,260 +1303,58 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
     return 0;
 }
 
-// ---- the generation loop in pieces (include/tts_hip.h) ----------------------------------------------------------------------------------
+// ---- the device loop (include/tts_hip.h; kernels in dia_kernels.h) ------------------------------------------------------------------------
+// One loop under tts_hip_dia_gen_* / tts_hip_dia_generate (DiaLoop::BATCH) and tts_hip_dia_stream_* (DiaLoop::SESSION): every replay steps
+// all 2 * n rows through the same dia_forward, so what a live slot computes does not depend on who else is live.  Budget, uniforms and the
+// parked flag are device memory: an admission changes values, never the captured launches.  The modes differ in how slots become live
+// (all at begin / by admission), in how many replays a launch may enqueue, and in what a look-in reports.
 #define DIA_LOOP_CHUNK 16
+static const int DIA_GRAPH_KEY = 9100001;   // + 1 for the session's graph
 
-// an unfinished loop is waited for and dropped: encode / step / a new loop overwrite what its steps read
-static int dia_gen_drop(tts_hip_ctx *c) {
-    if (!c->dg.active) return 0;
-    if (c->dg.pending) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    c->dg = tts_hip_ctx::DiaGen{};
-    return 0;
-}
-
-static DiaLoopArgs dia_loop_args(tts_hip_ctx *c) {
-    const auto &g = c->dg;
-    DiaLoopArgs la{};
-    la.n_utt = (int) g.n_utt; la.n_out = c->NO;
-    la.bos = g.codes.bos; la.eos = g.codes.eos; la.pad = g.codes.pad; la.max_delay = g.codes.max_delay; la.max_gen = g.max_gen;
-    for (int i = 0; i < 16; i++) la.delay_pattern[i] = g.codes.delay_pattern[i];
-    la.ids = c->di_ids; la.pos = c->di_pos;
-    la.delay = (int32_t *) c->di_loop; la.done = c->di_loop + c->di_U; la.call = c->di_loop + 2 * c->di_U;
-    la.tok = c->di_stok; la.hist = c->di_hist;
-    return la;
-}
-
-// pre-step, forward, guidance, sampler, post-step: what one replay of the captured graph runs
-static int dia_loop_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
-    const auto &g = c->dg;
-    const int U = (int) g.n_utt, NO = c->NO, V = c->di_V;
-    hipLaunchKernelGGL(dia_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
-    HIPCHK(hipGetLastError());
-    CHK(dia_forward(c, U, (int) c->dia.max_gen, captured));
-    if (g.sampled) {
-        SampleArgs sa{};
-        sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
-        sa.top_k = g.sp.top_k; sa.top_p = g.sp.top_p; sa.temperature = g.sp.temperature;
-        sa.uniforms = c->d_uniforms; sa.row_step = la.call; sa.out = c->di_stok;
-        if (g.rep) { sa.pen_table = c->d_pen; sa.pen_len = c->pen_len; sa.last_ids = c->d_last; sa.rep_counts = c->d_repc; }
-        hipLaunchKernelGGL(sample_kernel, dim3(NO, U), dim3(256), 0, c->stream, sa);
-    } else {
-        hipLaunchKernelGGL(argmax_kernel, dim3(U * NO), dim3(256), 0, c->stream, (const float *) c->di_guided, V, c->di_stok);
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(dia_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static const int DIA_GRAPH_KEY = 9100001;
-
-static int dia_gen_begin(tts_hip_ctx *c, const char *what, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp,
-                         const float *uniforms) {
-    if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
-    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
-    if (!codes) return set_err("%s: null argument", what);
-    CHK(dia_no_session(c, what));
-    if (n_utt == 0 || n_utt > (uint32_t) c->di_U) return set_err("%s: %u utterances outside 1..%d (max_utterances)", what, n_utt, c->di_U);
-    const int G = (int) c->dia.max_gen, NO = c->NO, V = c->di_V, U = (int) n_utt;
-    if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("%s: max_gen %u outside 1..%d cached positions", what, max_gen, G);
-    if (codes->max_delay >= max_gen) return set_err("%s: max_gen %u must exceed max_delay %u", what, max_gen, codes->max_delay);
-    if (codes->bos >= (uint32_t) V || codes->eos >= (uint32_t) V || codes->pad >= (uint32_t) V) return set_err("%s: special ids outside the vocabulary %d", what, V);
-    for (int u = 0; u < U; u++)
-        if (!c->di_slot_encoded[(size_t) u]) return set_err("%s: slot %d has not been encoded (tts_hip_dia_encode_slot)", what, u);
-    if (sp) {
-        if (V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, V, SMP_VMAX);
-        if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f) || !(sp->repetition_penalty > 0.0f)) return set_err("%s: temperature, top_p, repetition_penalty must be > 0", what);
-        if (!uniforms) return set_err("%s: null uniforms", what);
-    }
-    CHK(dia_gen_drop(c));
+// leaving the loop, whichever mode: steps in flight are waited for and dropped (encode / step / a new loop overwrite what they read), and
+// the cross extent of every row is the whole text context again, as the other entry points expect (parking moved it to one key)
+static int dia_loop_end(tts_hip_ctx *c) {
+    if (c->dl.mode == DL::NONE) return 0;
     HIPCHK(hipSetDevice(c->device));
-    const bool rep = sp && sp->repetition_penalty != 1.0f;
-    if (sp) {
-        CHK(stage_uniforms(c, uniforms, (size_t) max_gen * U * NO));
-        CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
-    }
-    // loop state: ids = BOS everywhere, positions 0, countdown -1, nothing done, nothing handed out; sampler::reset (sampler.cpp:71-80)
-    {
-        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), zero((size_t) 4 * c->di_U, 0u), seq((size_t) 2 * U);
-        for (int u = 0; u < U; u++) { zero[(size_t) u] = 0xFFFFFFFFu; seq[(size_t) 2 * u] = 2 * u; seq[(size_t) 2 * u + 1] = 2 * u + 1; }
-        HIPCHK(hipMemcpyAsync(c->di_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemsetAsync(c->di_pos, 0, (size_t) 2 * U * 4, c->stream));
-        HIPCHK(hipMemcpyAsync(c->di_seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->di_loop, zero.data(), zero.size() * 4, hipMemcpyHostToDevice, c->stream));
-        if (rep) {
-            HIPCHK(hipMemsetAsync(c->d_last, 0xFF, (size_t) U * NO * 4, c->stream));
-            HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) U * NO * 4, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals
-    }
-    // everything the captured launches hold by value: a change drops the graph
-    const int mode = sp ? 1 : 0;
-    const void *pen = rep ? (const void *) c->d_pen : nullptr;
-    const tts_hip_sampling spv = sp ? *sp : tts_hip_sampling{};
-    auto &bk = c->di_baked;
-    const bool same = bk.mode == mode && bk.U == n_utt && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
-                      (!sp || (bk.uni == c->d_uniforms && bk.pen == pen && memcmp(&bk.sp, &spv, sizeof(spv)) == 0));
-    if (!same) {
-        auto it = c->graphs.find(DIA_GRAPH_KEY);
-        if (it != c->graphs.end()) { (void) hipGraphExecDestroy(it->second); c->graphs.erase(it); }
-        bk.mode = mode; bk.U = n_utt; bk.max_gen = max_gen; bk.codes = *codes; bk.uni = c->d_uniforms; bk.pen = pen; bk.sp = spv;
-    }
-    auto &g = c->dg;
-    g.active = true; g.sampled = sp != nullptr; g.rep = rep;
-    g.n_utt = n_utt; g.max_gen = max_gen; g.codes = *codes; g.sp = spv;
-    g.handed.assign((size_t) U, 0u);
-    return 0;
-}
-
-// at most max_gen sampler calls, then one pre-step that ends the countdown: never more than max_gen + 1 pre-steps
-static int dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
-    auto &g = c->dg;
-    if (g.all_done || g.launched >= g.max_gen + 1) return 0;
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t k = std::min<uint32_t>(n_steps, g.max_gen + 1 - g.launched);
-    const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
-    const DiaLoopArgs la = dia_loop_args(c);
-    for (uint32_t s = 0; s < k; s++) {
-        if (!use_graph) {
-            CHK(dia_loop_step(c, la, false));
-        } else {
-            auto it = c->graphs.find(DIA_GRAPH_KEY);
-            if (it != c->graphs.end()) {
-                HIPCHK(hipGraphLaunch(it->second, c->stream));
-            } else {
-                // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
-                CHK(dia_loop_step(c, la, false));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                hipGraph_t graph = nullptr;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                const int rc = dia_loop_step(c, la, true);
-                const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-                if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-                if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void) hipGraphDestroy(graph);
-                c->graphs.emplace(DIA_GRAPH_KEY, exec);
-            }
-        }
-        g.launched++; g.pending++; g.unread++;
-    }
-    return 0;
-}
-
-static int dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
-    auto &g = c->dg;
-    const int U = (int) g.n_utt, NO = c->NO;
-    HIPCHK(hipSetDevice(c->device));
-    DiaLookArgs a{};
-    a.n_utt = U; a.n_out = NO; a.max_gen = g.max_gen;
-    a.take = tokens_out ? 1 : 0;
-    a.cap = a.take ? g.unread : 0u;   // <= max_gen + 1 rows per slot; di_look holds max_generation_size rows and a slot never fills beyond max_gen - handed
-    a.cap = std::min(a.cap, g.max_gen);
-    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.hist = c->di_hist; a.handed = c->di_loop + 3 * c->di_U; a.block = c->di_look;
-    const size_t slot = 2 + (size_t) a.cap * NO;
-    hipLaunchKernelGGL(dia_lookin_kernel, dim3(U), dim3(64), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) U * slot * 4, hipMemcpyDeviceToHost, c->stream));
+    const std::vector<uint32_t> cend((size_t) 2 * c->di_U, c->dia.max_ctx);
+    HIPCHK(hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    g.pending = 0;
-    bool all = true;
-    for (int u = 0; u < U; u++) {
-        const uint32_t *s = c->h_di_look + (size_t) u * slot;
-        const uint32_t from = g.handed[(size_t) u], to = s[0];
-        const uint32_t rows = a.take && to > from ? std::min(to - from, a.cap) : 0u;
-        if (rows) memcpy(tokens_out + ((size_t) u * g.max_gen + from) * NO, s + 2, (size_t) rows * NO * 4);
-        g.handed[(size_t) u] = from + rows;
-        if (steps_done) steps_done[u] = to;
-        if (done) done[u] = s[1] != 0;
-        all = all && s[1] != 0;
-    }
-    if (a.take) g.unread = 0;
-    g.all_done = all;
-    if (ran) *ran = g.launched;
+    c->dl = DL{};
     return 0;
 }
-
-extern "C" int tts_hip_dia_gen_begin(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms) {
-    return dia_gen_begin(c, "tts_hip_dia_gen_begin", n_utt, max_gen, codes, sp, uniforms);
-}
-
-extern "C" int tts_hip_dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
-    if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_launch: not a Dia context (tts_hip_dia_create)");
-    CHK(dia_no_session(c, "tts_hip_dia_gen_launch"));
-    if (!c->dg.active) return set_err("tts_hip_dia_gen_launch: no generation (tts_hip_dia_gen_begin)");
-    return dia_gen_launch(c, n_steps);
-}
-
-extern "C" int tts_hip_dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
-    if (!c || !c->has_dia) return set_err("tts_hip_dia_gen_wait: not a Dia context (tts_hip_dia_create)");
-    CHK(dia_no_session(c, "tts_hip_dia_gen_wait"));
-    if (!c->dg.active) return set_err("tts_hip_dia_gen_wait: no generation (tts_hip_dia_gen_begin)");
-    return dia_gen_wait(c, tokens_out, steps_done, done, ran);
-}
-
-// begin + (launch 16, wait) until every utterance is done or the max_gen + 1 pre-steps are spent
-extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms,
-                                    uint32_t *tokens_out, uint32_t *steps_out) {
-    if (!c || !c->has_dia) return set_err("tts_hip_dia_generate: not a Dia context (tts_hip_dia_create)");
-    if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_generate: context not finalized");
-    if (!codes || !tokens_out || !steps_out) return set_err("tts_hip_dia_generate: null argument");
-    CHK(dia_gen_begin(c, "tts_hip_dia_generate", n_utt, max_gen, codes, sp, uniforms));
-    int rc = 0;
-    while (rc == 0 && !c->dg.all_done && c->dg.launched < max_gen + 1) {
-        rc = dia_gen_launch(c, DIA_LOOP_CHUNK);
-        if (rc == 0) rc = dia_gen_wait(c, tokens_out, steps_out, nullptr, nullptr);
-    }
-    (void) dia_gen_drop(c);
-    return rc;
-}
-
-// ---- continuous session (include/tts_hip.h; kernels in dia_kernels.h) ---------------------------------------------------------------------
-// The loop of tts_hip_dia_generate at a fixed n_utt == n_slots: every replay steps all 2 * n_slots rows through the same dia_forward, so what
-// a live slot computes does not depend on who else is live.  Budget, uniforms and the parked flag are device memory: an admission changes
-// values, never the captured launches.
-static const int DIA_STREAM_GRAPH_KEY = 9100002;
 
 static int dia_stream_ready(tts_hip_ctx *c, const char *what, bool need_session = true) {
     if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
     if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
-    if (need_session && !c->ds.active) return set_err("%s: no session (tts_hip_dia_stream_begin)", what);
+    if (need_session && c->dl.mode != DL::SESSION) return set_err("%s: no session (tts_hip_dia_stream_begin)", what);
     return 0;
 }
 
-// a launch must be followed by a wait: admit, collect, drop and a second launch find the state they read or write still moving
+// a session's launch must be followed by a wait: admit, collect, drop and a second launch find the state they read or write still moving
 static int dia_stream_idle(tts_hip_ctx *c, const char *what) {
-    return c->ds.in_flight ? set_err("%s: %u steps are in flight (tts_hip_dia_stream_wait first)", what, c->ds.in_flight) : 0;
+    return c->dl.in_flight ? set_err("%s: %u steps are in flight (tts_hip_dia_stream_wait first)", what, c->dl.in_flight) : 0;
 }
 
-static DiaLoopArgs dia_stream_loop_args(tts_hip_ctx *c) {
-    const auto &g = c->ds;
+static DiaLoopArgs dia_loop_args(tts_hip_ctx *c) {
+    const auto &g = c->dl;
     DiaLoopArgs la{};
-    la.n_utt = (int) g.n_slots; la.n_out = c->NO;
+    la.n_utt = (int) g.n; la.n_out = c->NO;
     la.bos = g.codes.bos; la.eos = g.codes.eos; la.pad = g.codes.pad; la.max_delay = g.codes.max_delay; la.max_gen = g.max_gen;
     for (int i = 0; i < 16; i++) la.delay_pattern[i] = g.codes.delay_pattern[i];
     la.ids = c->di_ids; la.pos = c->di_pos;
     la.delay = (int32_t *) c->di_loop; la.done = c->di_loop + c->di_U; la.call = c->di_loop + 2 * c->di_U;
     la.tok = c->di_stok; la.hist = c->di_hist;
+    la.budget = c->di_sbud; la.steps = c->di_sbud + c->di_U; la.cend = c->di_cend;
     return la;
 }
 
-// session pre-step, the forward of dia_loop_step at U = n_slots, guidance, sampler (parked slots sit out), post-step
-static int dia_stream_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
-    const auto &g = c->ds;
-    const int U = (int) g.n_slots, NO = c->NO, V = c->di_V;
-    DiaStreamArgs st{};
-    st.budget = c->di_sbud; st.steps = c->di_sbud + c->di_U; st.cend = c->di_cend;
-    hipLaunchKernelGGL(dia_stream_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la, st);
+// pre-step, forward, guidance, sampler (parked slots sit out), post-step: what one replay of the captured graph runs
+static int dia_loop_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
+    const auto &g = c->dl;
+    const int U = (int) g.n, NO = c->NO, V = c->di_V;
+    hipLaunchKernelGGL(dia_loop_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
     HIPCHK(hipGetLastError());
-    c->di_park = true;
-    const int rc = dia_forward(c, U, (int) c->dia.max_gen, captured);
-    c->di_park = false;
-    CHK(rc);
+    CHK(dia_forward(c, U, (int) c->dia.max_gen, captured));
     if (g.sampled) {
         SampleArgs sa{};
         sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
@@ -1575,18 +1366,18 @@ static int dia_stream_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured)
         hipLaunchKernelGGL(argmax_kernel, dim3(U * NO), dim3(256), 0, c->stream, (const float *) c->di_guided, V, c->di_stok);
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(dia_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
+    hipLaunchKernelGGL(dia_loop_poststep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp) {
-    const char *what = "tts_hip_dia_stream_begin";
+// what both begin calls ask of their arguments; `rows` names the n of the caller ("utterances", "slots")
+static int dia_loop_check(tts_hip_ctx *c, const char *what, const char *rows, uint32_t n, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp) {
     CHK(dia_stream_ready(c, what, false));
-    CHK(dia_no_session(c, what));
     if (!codes) return set_err("%s: null argument", what);
-    if (n_slots == 0 || n_slots > (uint32_t) c->di_U) return set_err("%s: %u slots outside 1..%d (max_utterances)", what, n_slots, c->di_U);
-    const int G = (int) c->dia.max_gen, S = (int) c->dia.max_ctx, NO = c->NO, V = c->di_V, U = (int) n_slots;
+    CHK(dia_no_session(c, what));
+    const int G = (int) c->dia.max_gen, V = c->di_V;
+    if (n == 0 || n > (uint32_t) c->di_U) return set_err("%s: %u %s outside 1..%d (max_utterances)", what, n, rows, c->di_U);
     if (max_gen == 0 || max_gen > (uint32_t) G) return set_err("%s: max_gen %u outside 1..%d cached positions", what, max_gen, G);
     if (codes->max_delay >= max_gen) return set_err("%s: max_gen %u must exceed max_delay %u", what, max_gen, codes->max_delay);
     if (codes->bos >= (uint32_t) V || codes->eos >= (uint32_t) V || codes->pad >= (uint32_t) V) return set_err("%s: special ids outside the vocabulary %d", what, V);
@@ -1594,79 +1385,210 @@ extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32
         if (V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, V, SMP_VMAX);
         if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f) || !(sp->repetition_penalty > 0.0f)) return set_err("%s: temperature, top_p, repetition_penalty must be > 0", what);
     }
-    CHK(dia_gen_drop(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
+    return 0;
+}
+
+// The loop over slots 0..n-1 from its first step; the arguments have been checked.  BATCH: every slot live, over the whole text context, with
+// the budget max_gen and the caller's uniforms [call][utt][head] (what an admission of all n slots leaves, without the encoder passes).
+// SESSION: every slot parked over one cross key until an admission; the admissions fill the slots' uniform columns.
+static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms) {
+    const int S = (int) c->dia.max_ctx, NO = c->NO, U = (int) n, DU = c->di_U;
+    const bool live = mode == DL::BATCH, rep = sp && sp->repetition_penalty != 1.0f;
+    CHK(dia_loop_end(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     HIPCHK(hipSetDevice(c->device));
-    const bool rep = sp && sp->repetition_penalty != 1.0f;
     if (sp) {
-        const std::vector<float> zero((size_t) max_gen * U * NO, 0.0f);   // sizes d_uniforms; the admissions fill the slots' columns
-        CHK(stage_uniforms(c, zero.data(), zero.size()));
+        const std::vector<float> zero(uniforms ? 0 : (size_t) max_gen * U * NO, 0.0f);   // sizes d_uniforms
+        CHK(stage_uniforms(c, uniforms ? uniforms : zero.data(), (size_t) max_gen * U * NO));
         CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
     }
-    // every slot parked: ids BOS (the embedding reads them), position 0, one cross key, done; sampler::reset
+    // ids BOS (the embedding reads them), position 0, countdown -1, sampler call 1, nothing handed out, budget max_gen; sampler::reset (sampler.cpp:71-80)
     {
-        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), loop((size_t) 4 * c->di_U, 0u), seq((size_t) 2 * U), one((size_t) 2 * U, 1u), bud((size_t) 2 * c->di_U, 0u);
+        std::vector<uint32_t> ids((size_t) U * NO, codes->bos), loop((size_t) 4 * DU, 0u), seq((size_t) 2 * U), cend((size_t) 2 * U, live ? (uint32_t) S : 1u), bud((size_t) 2 * DU, 0u);
         for (int u = 0; u < U; u++) {
-            loop[(size_t) u] = 0xFFFFFFFFu; loop[(size_t) c->di_U + u] = 1u; loop[(size_t) 2 * c->di_U + u] = 1u;
+            loop[(size_t) u] = 0xFFFFFFFFu; loop[(size_t) DU + u] = live ? 0u : 1u; loop[(size_t) 2 * DU + u] = 1u;
             seq[(size_t) 2 * u] = 2 * u; seq[(size_t) 2 * u + 1] = 2 * u + 1;
             bud[(size_t) u] = max_gen;
         }
         HIPCHK(hipMemcpyAsync(c->di_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemsetAsync(c->di_pos, 0, (size_t) 2 * U * 4, c->stream));
         HIPCHK(hipMemcpyAsync(c->di_seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->di_cend, one.data(), one.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->di_loop, loop.data(), loop.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->di_sbud, bud.data(), bud.size() * 4, hipMemcpyHostToDevice, c->stream));
         if (rep) {
             HIPCHK(hipMemsetAsync(c->d_last, 0xFF, (size_t) U * NO * 4, c->stream));
             HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) U * NO * 4, c->stream));
         }
-        // a slot no encoder pass has filled holds whatever its cross K/V held: the one position its parked rows attend over becomes zero
+        // a slot no encoder pass has filled (SESSION; BATCH refuses it) holds whatever its cross K/V held: the one position its parked rows attend over becomes zero
         uint64_t clear = 0;
         for (int u = 0; u < U; u++) if (!c->di_slot_encoded[(size_t) u]) clear |= 1ull << u;
         if (clear) {
-            hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, c->di_ck, c->di_cv, clear, 2 * c->di_U, (int64_t) S,
-                               c->di_A);
+            hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, c->di_ck, c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals
     }
-    // everything the captured launches hold by value: a change drops the session's graph
-    const int mode = sp ? 1 : 0;
-    const void *pen = rep ? (const void *) c->d_pen : nullptr;
-    const tts_hip_sampling spv = sp ? *sp : tts_hip_sampling{};
-    auto &bk = c->di_sbaked;
-    const bool same = bk.mode == mode && bk.U == n_slots && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
-                      (!sp || (bk.uni == c->d_uniforms && bk.pen == pen && memcmp(&bk.sp, &spv, sizeof(spv)) == 0));
+    // everything the captured launches hold by value: a change drops this mode's graph
+    tts_hip_ctx::DiaBaked now;
+    now.sampled = sp ? 1 : 0; now.n = n; now.max_gen = max_gen; now.codes = *codes;
+    if (sp) { now.uni = c->d_uniforms; now.pen = rep ? (const void *) c->d_pen : nullptr; now.sp = *sp; }
+    auto &bk = c->di_baked[mode == DL::SESSION];
+    const bool same = bk.sampled == now.sampled && bk.n == n && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
+                      (!sp || (bk.uni == now.uni && bk.pen == now.pen && memcmp(&bk.sp, &now.sp, sizeof(now.sp)) == 0));
     if (!same) {
-        auto it = c->graphs.find(DIA_STREAM_GRAPH_KEY);
+        auto it = c->graphs.find(DIA_GRAPH_KEY + (mode == DL::SESSION));
         if (it != c->graphs.end()) { (void) hipGraphExecDestroy(it->second); c->graphs.erase(it); }
-        bk.mode = mode; bk.U = n_slots; bk.max_gen = max_gen; bk.codes = *codes; bk.uni = c->d_uniforms; bk.pen = pen; bk.sp = spv;
+        bk = now;
     }
-    auto &g = c->ds;
-    g = tts_hip_ctx::DiaStream{};
-    g.active = true; g.sampled = sp != nullptr; g.rep = rep;
-    g.n_slots = n_slots; g.max_gen = max_gen; g.codes = *codes; g.sp = spv;
-    g.slot.assign((size_t) U, tts_hip_ctx::DiaStream::FREE);
+    auto &g = c->dl;
+    g.mode = mode; g.sampled = sp != nullptr; g.rep = rep;
+    g.n = n; g.max_gen = max_gen; g.codes = *codes; g.sp = now.sp;
+    g.slot.assign((size_t) U, live ? DL::LIVE : DL::FREE);
     g.steps.assign((size_t) U, 0u);
     g.budget.assign((size_t) U, max_gen);
     g.handed.assign((size_t) U, 0u);
     return 0;
 }
 
+// enqueues min(n_steps, what the mode allows) replays; no copy, no synchronise after the graph exists
+static int dia_loop_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    auto &g = c->dl;
+    uint32_t allowed = 0;
+    if (g.mode == DL::BATCH) {
+        // at most max_gen sampler calls, then one pre-step that ends the countdown: never more than max_gen + 1 pre-steps
+        if (!g.all_done && g.launched < g.max_gen + 1) allowed = g.max_gen + 1 - g.launched;
+    } else {
+        // a live slot parks in the pre-step at position budget - 1 at the latest: no replay beyond the last one any live slot can need
+        for (uint32_t s = 0; s < g.n; s++)
+            if (g.slot[s] == DL::LIVE) allowed = std::max(allowed, g.budget[s] - std::min(g.steps[s], g.budget[s] - 1));
+    }
+    const uint32_t k = std::min(n_steps, allowed);
+    if (k == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
+    const int key = DIA_GRAPH_KEY + (g.mode == DL::SESSION);
+    const DiaLoopArgs la = dia_loop_args(c);
+    for (uint32_t i = 0; i < k; i++) {
+        auto it = c->graphs.find(key);
+        if (use_graph && it != c->graphs.end()) {
+            HIPCHK(hipGraphLaunch(it->second, c->stream));
+        } else {
+            CHK(dia_loop_step(c, la, false));
+            if (use_graph) {
+                // that step ran eagerly (per-kernel attributes are set outside a capture); the capture for the next ones follows
+                HIPCHK(hipStreamSynchronize(c->stream));
+                hipGraphExec_t exec = nullptr;
+                CHK(capture_graph(c, key, [&] { return dia_loop_step(c, la, true); }, &exec));
+            }
+        }
+        g.launched++; g.in_flight++; g.unread++;
+    }
+    return 0;
+}
+
+// the look-in: one launch, one copy, one synchronise.  tokens_out != NULL takes the rows no earlier look-in took.
+static int dia_loop_look(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done) {
+    auto &g = c->dl;
+    const int U = (int) g.n, NO = c->NO;
+    HIPCHK(hipSetDevice(c->device));
+    DiaLookArgs a{};
+    a.n_utt = U; a.n_out = NO; a.max_gen = g.max_gen;
+    a.take = tokens_out ? 1 : 0;
+    // a slot's un-taken rows were all recorded by steps enqueued since the last look-in that took rows (an admission starts at row 0), and
+    // di_look holds max_generation_size >= max_gen rows per slot
+    a.cap = a.take ? std::min(g.unread, g.max_gen) : 0u;
+    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.steps = c->di_sbud + c->di_U; a.hist = c->di_hist; a.handed = c->di_loop + 3 * c->di_U; a.block = c->di_look;
+    const size_t slot = 2 + (size_t) a.cap * NO;
+    hipLaunchKernelGGL(dia_loop_lookin_kernel, dim3(U), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) U * slot * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    g.in_flight = 0;
+    g.all_done = true;
+    for (int u = 0; u < U; u++) {
+        const uint32_t *s = c->h_di_look + (size_t) u * slot;
+        const uint32_t from = g.handed[(size_t) u], to = s[0];
+        const uint32_t rows = a.take && to > from ? std::min(to - from, a.cap) : 0u;
+        if (rows) memcpy(tokens_out + ((size_t) u * g.max_gen + from) * NO, s + 2, (size_t) rows * NO * 4);
+        g.handed[(size_t) u] = from + rows;
+        if (steps_done) steps_done[u] = to;
+        if (done) done[u] = s[1] != 0;
+        if (g.slot[(size_t) u] != DL::LIVE) continue;
+        g.steps[(size_t) u] = to;
+        if (s[1]) g.slot[(size_t) u] = DL::ENDED;
+        else g.all_done = false;
+    }
+    if (a.take) g.unread = 0;
+    return 0;
+}
+
+// ---- the fixed batch ----
+static int dia_gen_begin(tts_hip_ctx *c, const char *what, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp,
+                         const float *uniforms) {
+    CHK(dia_loop_check(c, what, "utterances", n_utt, max_gen, codes, sp));
+    for (uint32_t u = 0; u < n_utt; u++)
+        if (!c->di_slot_encoded[u]) return set_err("%s: slot %u has not been encoded (tts_hip_dia_encode_slot)", what, u);
+    if (sp && !uniforms) return set_err("%s: null uniforms", what);
+    return dia_loop_begin(c, DL::BATCH, n_utt, max_gen, codes, sp, uniforms);
+}
+
+static int dia_gen_ready(tts_hip_ctx *c, const char *what) {
+    if (!c || !c->has_dia) return set_err("%s: not a Dia context (tts_hip_dia_create)", what);
+    CHK(dia_no_session(c, what));
+    return c->dl.mode == DL::BATCH ? 0 : set_err("%s: no generation (tts_hip_dia_gen_begin)", what);
+}
+
+extern "C" int tts_hip_dia_gen_begin(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms) {
+    return dia_gen_begin(c, "tts_hip_dia_gen_begin", n_utt, max_gen, codes, sp, uniforms);
+}
+
+extern "C" int tts_hip_dia_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    CHK(dia_gen_ready(c, "tts_hip_dia_gen_launch"));
+    return dia_loop_launch(c, n_steps);
+}
+
+extern "C" int tts_hip_dia_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *ran) {
+    CHK(dia_gen_ready(c, "tts_hip_dia_gen_wait"));
+    CHK(dia_loop_look(c, tokens_out, steps_done, done));
+    if (ran) *ran = c->dl.launched;
+    return 0;
+}
+
+// begin + (launch 16, wait) until every utterance is done or the max_gen + 1 pre-steps are spent
+extern "C" int tts_hip_dia_generate(tts_hip_ctx *c, uint32_t n_utt, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms,
+                                    uint32_t *tokens_out, uint32_t *steps_out) {
+    if (!c || !c->has_dia) return set_err("tts_hip_dia_generate: not a Dia context (tts_hip_dia_create)");
+    if (!c->finalized || !c->weights_present) return set_err("tts_hip_dia_generate: context not finalized");
+    if (!codes || !tokens_out || !steps_out) return set_err("tts_hip_dia_generate: null argument");
+    CHK(dia_gen_begin(c, "tts_hip_dia_generate", n_utt, max_gen, codes, sp, uniforms));
+    int rc = 0;
+    while (rc == 0 && !c->dl.all_done && c->dl.launched < max_gen + 1) {
+        rc = dia_loop_launch(c, DIA_LOOP_CHUNK);
+        if (rc == 0) rc = dia_loop_look(c, tokens_out, steps_out, nullptr);
+    }
+    (void) dia_loop_end(c);
+    return rc;
+}
+
+// ---- the continuous session ----
+extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp) {
+    CHK(dia_loop_check(c, "tts_hip_dia_stream_begin", "slots", n_slots, max_gen, codes, sp));
+    return dia_loop_begin(c, DL::SESSION, n_slots, max_gen, codes, sp, nullptr);
+}
+
 extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
                                         const float *uniforms) {
     const char *what = "tts_hip_dia_stream_admit";
-    typedef tts_hip_ctx::DiaStream DS;
     CHK(dia_stream_ready(c, what));
     CHK(dia_stream_idle(c, what));
-    auto &g = c->ds;
+    auto &g = c->dl;
     if (n == 0) return 0;
     if (!slots || !tokens || !sentence_len) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_gen][n_output_heads]", what);
     const int S = (int) c->dia.max_ctx, NO = c->NO;
     for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
-        if (g.slot[slots[i]] == DS::LIVE || g.slot[slots[i]] == DS::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
+        if (slots[i] >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n);
+        if (g.slot[slots[i]] == DL::LIVE || g.slot[slots[i]] == DL::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
         for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
         if (sentence_len[i] == 0 || sentence_len[i] > (uint32_t) S) return set_err("%s: utterance %u: sentence length %u outside 1..%d", what, i, sentence_len[i], S);
         if (budget && (budget[i] <= g.codes.max_delay || budget[i] > g.max_gen))
@@ -1693,7 +1615,7 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
     HIPCHK(hipMemcpyAsync(c->di_sadm, adm.data(), adm.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (g.sampled) HIPCHK(hipMemcpyAsync(c->di_suni, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
     DiaAdmitArgs a{};
-    a.n = (int) n; a.n_slots = (int) g.n_slots; a.n_out = NO;
+    a.n = (int) n; a.n_slots = (int) g.n; a.n_out = NO;
     a.bos = g.codes.bos; a.max_gen = g.max_gen; a.max_ctx = (uint32_t) S;
     a.slots = c->di_sadm; a.budgets = c->di_sadm + n;
     a.uni_in = g.sampled ? c->di_suni : nullptr; a.uni = c->d_uniforms;
@@ -1705,97 +1627,20 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
     hipLaunchKernelGGL(dia_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // adm is a local, uniforms the caller's
-    for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DS::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; g.handed[slots[i]] = 0; }
-    return 0;
-}
-
-// enqueues min(n_steps, what the live budgets leave) replays; no copy, no synchronise after the graph exists
-static int dia_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
-    typedef tts_hip_ctx::DiaStream DS;
-    auto &g = c->ds;
-    // a live slot parks in the pre-step at position budget - 1 at the latest: no replay beyond the last one any live slot can need
-    uint32_t need = 0;
-    for (uint32_t s = 0; s < g.n_slots; s++)
-        if (g.slot[s] == DS::LIVE) need = std::max(need, g.budget[s] - std::min(g.steps[s], g.budget[s] - 1));
-    const uint32_t k = std::min(n_steps, need);
-    if (k == 0) return 0;
-    HIPCHK(hipSetDevice(c->device));
-    const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
-    const DiaLoopArgs la = dia_stream_loop_args(c);
-    for (uint32_t i = 0; i < k; i++) {
-        if (!use_graph) {
-            CHK(dia_stream_step(c, la, false));
-        } else {
-            auto it = c->graphs.find(DIA_STREAM_GRAPH_KEY);
-            if (it != c->graphs.end()) {
-                HIPCHK(hipGraphLaunch(it->second, c->stream));
-            } else {
-                // the first step runs eagerly (per-kernel attributes are set outside a capture), the capture follows
-                CHK(dia_stream_step(c, la, false));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                hipGraph_t graph = nullptr;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                const int rc = dia_stream_step(c, la, true);
-                const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-                if (rc != 0) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-                if (e != hipSuccess) return set_err("hipStreamEndCapture: %s", hipGetErrorString(e));
-                hipGraphExec_t exec = nullptr;
-                HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void) hipGraphDestroy(graph);
-                c->graphs.emplace(DIA_STREAM_GRAPH_KEY, exec);
-            }
-        }
-        g.in_flight++; g.unread++;
-    }
-    return 0;
-}
-
-// the look-in: one launch, one copy, one synchronise.  tokens_out != NULL takes the rows no earlier look-in took.
-static int dia_stream_look(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done) {
-    typedef tts_hip_ctx::DiaStream DS;
-    auto &g = c->ds;
-    const int U = (int) g.n_slots, NO = c->NO;
-    HIPCHK(hipSetDevice(c->device));
-    DiaLookArgs a{};
-    a.n_utt = U; a.n_out = NO; a.max_gen = g.max_gen;
-    a.take = tokens_out ? 1 : 0;
-    // a slot's un-taken rows were all recorded by steps enqueued since the last look-in that took rows (an admission starts at row 0), and
-    // di_look holds max_generation_size >= max_gen rows per slot
-    a.cap = a.take ? std::min(g.unread, g.max_gen) : 0u;
-    a.pos = c->di_pos; a.done = c->di_loop + c->di_U; a.hist = c->di_hist; a.handed = c->di_loop + 3 * c->di_U; a.block = c->di_look;
-    const size_t slot = 2 + (size_t) a.cap * NO;
-    hipLaunchKernelGGL(dia_stream_lookin_kernel, dim3(U), dim3(64), 0, c->stream, a, (const uint32_t *) (c->di_sbud + c->di_U));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_di_look, c->di_look, (size_t) U * slot * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    g.in_flight = 0;
-    for (int u = 0; u < U; u++) {
-        const uint32_t *s = c->h_di_look + (size_t) u * slot;
-        const uint32_t from = g.handed[(size_t) u], to = s[0];
-        const uint32_t rows = a.take && to > from ? std::min(to - from, a.cap) : 0u;
-        if (rows) memcpy(tokens_out + ((size_t) u * g.max_gen + from) * NO, s + 2, (size_t) rows * NO * 4);
-        g.handed[(size_t) u] = from + rows;
-        if (steps_done) steps_done[u] = to;
-        if (done) done[u] = s[1] != 0;
-        if (g.slot[(size_t) u] != DS::LIVE) continue;
-        g.steps[(size_t) u] = to;
-        if (s[1]) g.slot[(size_t) u] = DS::ENDED;
-    }
-    if (a.take) g.unread = 0;
+    for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DL::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; g.handed[slots[i]] = 0; }
     return 0;
 }
 
 // slots a look-in saw parked and no call has reported yet, in slot order
 static void dia_stream_report(tts_hip_ctx *c, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
-    typedef tts_hip_ctx::DiaStream DS;
-    auto &g = c->ds;
+    auto &g = c->dl;
     *n_finished = 0;
-    for (uint32_t s = 0; s < g.n_slots; s++) {
-        if (g.slot[s] != DS::ENDED) continue;
+    for (uint32_t s = 0; s < g.n; s++) {
+        if (g.slot[s] != DL::ENDED) continue;
         finished_slots[*n_finished] = s;
         finished_steps[*n_finished] = g.steps[s];
         (*n_finished)++;
-        g.slot[s] = DS::REPORTED;
+        g.slot[s] = DL::REPORTED;
     }
 }
 
@@ -1803,7 +1648,7 @@ extern "C" int tts_hip_dia_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
     const char *what = "tts_hip_dia_stream_launch";
     CHK(dia_stream_ready(c, what));
     CHK(dia_stream_idle(c, what));
-    return dia_stream_launch(c, n_steps);
+    return dia_loop_launch(c, n_steps);
 }
 
 extern "C" int tts_hip_dia_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
@@ -1812,7 +1657,7 @@ extern "C" int tts_hip_dia_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uin
     CHK(dia_stream_ready(c, what));
     if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
     *n_finished = 0;
-    CHK(dia_stream_look(c, tokens_out, steps_done, done));
+    CHK(dia_loop_look(c, tokens_out, steps_done, done));
     dia_stream_report(c, n_finished, finished_slots, finished_steps);
     return 0;
 }
@@ -1824,23 +1669,22 @@ extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t
     if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
     *n_finished = 0;
     CHK(dia_stream_idle(c, what));
-    CHK(dia_stream_launch(c, n_steps));
-    if (c->ds.in_flight) CHK(dia_stream_look(c, nullptr, nullptr, nullptr));
+    CHK(dia_loop_launch(c, n_steps));
+    if (c->dl.in_flight) CHK(dia_loop_look(c, nullptr, nullptr, nullptr));
     dia_stream_report(c, n_finished, finished_slots, finished_steps);
     return 0;
 }
 
 extern "C" int tts_hip_dia_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
     const char *what = "tts_hip_dia_stream_drop";
-    typedef tts_hip_ctx::DiaStream DS;
     CHK(dia_stream_ready(c, what));
     CHK(dia_stream_idle(c, what));
-    auto &g = c->ds;
+    auto &g = c->dl;
     if (n == 0) return 0;
     if (!slots) return set_err("%s: null argument", what);
     for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
-        if (g.slot[slots[i]] != DS::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
+        if (slots[i] >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n);
+        if (g.slot[slots[i]] != DL::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
         for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
     }
     HIPCHK(hipSetDevice(c->device));
@@ -1851,7 +1695,7 @@ extern "C" int tts_hip_dia_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_
     hipLaunchKernelGGL(dia_stream_drop_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // slots is the caller's
-    for (uint32_t i = 0; i < n; i++) g.slot[slots[i]] = DS::FREE;
+    for (uint32_t i = 0; i < n; i++) g.slot[slots[i]] = DL::FREE;
     return 0;
 }
 
@@ -1859,9 +1703,9 @@ extern "C" int tts_hip_dia_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_
     const char *what = "tts_hip_dia_stream_collect";
     CHK(dia_stream_ready(c, what));
     CHK(dia_stream_idle(c, what));
-    auto &g = c->ds;
-    if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
-    if (g.slot[slot] != tts_hip_ctx::DiaStream::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_dia_stream_run reports it)", what, slot);
+    auto &g = c->dl;
+    if (slot >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n);
+    if (g.slot[slot] != DL::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_dia_stream_run reports it)", what, slot);
     if (steps > g.steps[slot]) return set_err("%s: slot %u made %u steps, %u asked for", what, slot, g.steps[slot], steps);
     if (steps == 0) return 0;
     if (!tokens_out) return set_err("%s: null argument", what);
@@ -1873,15 +1717,7 @@ extern "C" int tts_hip_dia_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_
 
 extern "C" int tts_hip_dia_stream_end(tts_hip_ctx *c) {
     if (!c || !c->has_dia) return set_err("tts_hip_dia_stream_end: not a Dia context (tts_hip_dia_create)");
-    if (!c->ds.active) return 0;
-    (void) hipSetDevice(c->device);
-    (void) hipStreamSynchronize(c->stream);   // steps in flight are waited for and dropped
-    // the other entry points expect the cross extent of every row to be the whole text context
-    const std::vector<uint32_t> cend((size_t) 2 * c->di_U, c->dia.max_ctx);
-    (void) hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream);
-    (void) hipStreamSynchronize(c->stream);
-    c->ds = tts_hip_ctx::DiaStream{};
-    return 0;
+    return c->dl.mode == DL::SESSION ? dia_loop_end(c) : 0;
 }
 
 extern "C" int tts_hip_dia_step(tts_hip_ctx *c, const uint32_t *ids, uint32_t pos, float *logits_out, float *raw_out) {

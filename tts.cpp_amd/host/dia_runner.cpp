@@ -224,39 +224,36 @@ struct dia_runner::chunker {
                   "tts_hip_dac_decode_windows");
     }
     void clear() { codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear(); }
-    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
-    bool emit() {
-        if (row_of.empty()) return true;
-        const uint32_t U = r.hp.up_sampling_factor;
-        decode();
-        bool more = true;
-        size_t off = 0;
-        for (size_t w = 0; w < row_of.size() && more; w++) {
-            const uint32_t nf = keep1[w] - keep0[w];
-            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
-                more = on_chunk(row_of[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
-            off += (size_t) nf * U;
-        }
-        clear();
-        return more;
-    }
-    // the session's form: window w belongs to the utterance tickets[w] (its slot may have a new occupant by now); a false from `to` ends
-    // that utterance only — its ticket goes into `stopped`, the rest of its window is skipped and the other windows go on
-    void emit_session(const std::vector<size_t> & tickets, const std::function<bool(size_t, const float *, size_t)> & to, std::vector<size_t> & stopped) {
+    // the planned windows through the codec, then window after window in chunks to `to(window, samples, count)`; a false skips the rest of
+    // that window
+    void emit(const std::function<bool(size_t, const float *, size_t)> & to) {
         if (row_of.empty()) return;
         const uint32_t U = r.hp.up_sampling_factor;
         decode();
         size_t off = 0;
         for (size_t w = 0; w < row_of.size(); w++) {
             const uint32_t nf = keep1[w] - keep0[w];
-            bool more = std::find(stopped.begin(), stopped.end(), tickets[w]) == stopped.end();
-            for (uint32_t f = 0; f < nf && more; f += chunk_frames) {
-                more = to(tickets[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
-                if (!more) stopped.push_back(tickets[w]);
-            }
+            bool more = true;
+            for (uint32_t f = 0; f < nf && more; f += chunk_frames) more = to(w, r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
             off += (size_t) nf * U;
         }
         clear();
+    }
+    // run_utterances' policy: a window's chunks go to its row; a false stops the generation, so nothing after it is handed out
+    bool emit_rows() {
+        bool go = true;
+        emit([&](size_t w, const float * p, size_t k) { return go = go && on_chunk(row_of[w], p, k); });
+        return go;
+    }
+    // the session's policy: window w belongs to the utterance tickets[w] (its slot may have a new occupant by now); a false from `to` ends
+    // that utterance only — its ticket goes into `stopped` and the other windows go on
+    void emit_session(const std::vector<size_t> & tickets, const std::function<bool(size_t, const float *, size_t)> & to, std::vector<size_t> & stopped) {
+        emit([&](size_t w, const float * p, size_t k) {
+            if (std::find(stopped.begin(), stopped.end(), tickets[w]) != stopped.end()) return false;
+            if (to(tickets[w], p, k)) return true;
+            stopped.push_back(tickets[w]);
+            return false;
+        });
     }
 };
 
@@ -273,6 +270,22 @@ uint32_t dia_runner::begin_call(const generation_configuration & config) {
     smp.n_calls = 0;
     uint32_t max_gen = config.max_tokens > (int) hp.max_delay ? (uint32_t) config.max_tokens : hp.max_generation_size;
     return std::min(max_gen, hp.max_generation_size);   // the self-attention cache holds max_generation_size positions (:300-301)
+}
+
+tts_hip_dia_codes dia_runner::loop_codes() const {
+    tts_hip_dia_codes codes{};
+    codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
+    for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
+    return codes;
+}
+
+// the U[0,1) values a generate() call of one utterance's own would draw in max_gen sampler calls, call k at out + k * stride.  Every call seeds
+// its sampler the same way, so under a fixed seed every utterance draws the same values; with seed == 0 (std::random_device per draw, the
+// reference's behaviour) every utterance draws its own.
+void dia_runner::draw_call_uniforms(uint64_t seed, uint32_t max_gen, float * out, size_t stride) const {
+    sampler s = smp;
+    s.seed = seed; s.n_calls = 0;
+    for (uint32_t k = 0; k < max_gen; k++) s.draw_uniforms(out + (size_t) k * stride);
 }
 
 void dia_runner::encode_single(const char * sentence) {
@@ -296,34 +309,20 @@ void dia_runner::encode_batch(const std::vector<std::string> & sentences) {
 // (tts_hip_dia_gen_*: check_stopping, the step, the sampler and the delay-pattern feedback replay as one captured graph, the host looks in
 // every 16 steps), or under TTS_HOST_LOOP the reference's shape: logits back every step, sampler::sample and check_stopping here.  With a
 // hook, the look-ins hand out chunked audio.
-// Device loop and a fixed seed: every utterance gets the draws a separate generate() call would make (each call seeds its own sampler the
-// same way, so call k draws the same U[0,1) values for every utterance); with seed == 0 (std::random_device per call, the reference's
-// behaviour) separate calls are independently random, so every utterance of the batch draws its own values — as the host loop's
-// per-utterance samplers and the Parler batch path do.
+// Device loop: every utterance gets the draws a separate generate() call would make (draw_call_uniforms), as the host loop's per-utterance
+// samplers and the Parler batch path do.
 std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, chunker * hook) {
     const uint32_t nh = hp.n_output_heads;
     std::vector<std::vector<uint32_t>> toks(n);
     std::vector<bool> finished(n, false);
     bool go = true;   // false: the hook's caller stopped the generation
     if (!getenv("TTS_HOST_LOOP")) {
-        tts_hip_dia_codes codes{};
-        codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
-        for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
+        const tts_hip_dia_codes codes = loop_codes();
         std::vector<float> u;
         const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
         if (config.sample) {   // uniforms [call][utterance][head]
             u.resize((size_t) max_gen * n * nh);
-            std::vector<float> draw(nh);
-            sampler s = smp;
-            s.seed = config.seed; s.n_calls = 0;
-            for (uint32_t k = 0; k < max_gen; k++) {
-                if (config.seed != 0) {
-                    s.draw_uniforms(draw.data());
-                    for (uint32_t i = 0; i < n; i++) std::copy(draw.begin(), draw.end(), u.begin() + ((size_t) k * n + i) * nh);
-                } else {
-                    for (uint32_t i = 0; i < n; i++) s.draw_uniforms(u.data() + ((size_t) k * n + i) * nh);   // a fresh random_device draw per utterance
-                }
-            }
+            for (uint32_t i = 0; i < n; i++) draw_call_uniforms(config.seed, max_gen, u.data() + (size_t) i * nh, (size_t) n * nh);
         }
         hip_check(tts_hip_dia_gen_begin(lm, n, max_gen, &codes, config.sample ? &sp : nullptr, config.sample ? u.data() : nullptr), "tts_hip_dia_gen_begin");
         std::vector<uint32_t> buf((size_t) n * max_gen * nh), steps(n);
@@ -331,7 +330,7 @@ std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32
         uint32_t ran = 0;
         hip_check(tts_hip_dia_gen_launch(lm, LOOK_IN), "tts_hip_dia_gen_launch");
         for (;;) {
-            if (hook) go = hook->emit();   // the codec windows of the last look-in, while the steps run
+            if (hook) go = hook->emit_rows();   // the codec windows of the last look-in, while the steps run
             hip_check(tts_hip_dia_gen_wait(lm, buf.data(), steps.data(), done.data(), &ran), "tts_hip_dia_gen_wait");
             bool all = true;
             for (uint32_t i = 0; i < n; i++) {
@@ -374,14 +373,14 @@ std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32
             }
             if (hook && step % LOOK_IN == 0) {
                 hook->plan(toks, finished);
-                go = hook->emit();
+                go = hook->emit_rows();
             }
         }
     }
     if (hook && go) {   // what is left once every utterance is done
         finished.assign(n, true);
         hook->plan(toks, finished);
-        (void) hook->emit();
+        (void) hook->emit_rows();
     }
     return toks;
 }
@@ -462,9 +461,7 @@ void dia_runner::stream_begin(const generation_configuration & config) {
     if (st_on) stream_end();
     st_max_gen = begin_call(config);
     st_cfg = config;
-    tts_hip_dia_codes codes{};
-    codes.bos = hp.bos_token_id; codes.eos = hp.eos_token_id; codes.pad = hp.pad_token_id; codes.max_delay = hp.max_delay;
-    for (size_t i = 0; i < hp.delay_pattern.size() && i < 16; i++) codes.delay_pattern[i] = hp.delay_pattern[i];
+    const tts_hip_dia_codes codes = loop_codes();
     const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
     const uint32_t slots = stream_capacity();
     hip_check(tts_hip_dia_stream_begin(lm, slots, st_max_gen, &codes, config.sample ? &sp : nullptr), "tts_hip_dia_stream_begin");
@@ -518,11 +515,7 @@ void dia_runner::admit_waiting() {
         slots[i] = st_free[st_free.size() - 1 - i];
         lens[i] = st_wait[i].len;
         std::copy(st_wait[i].prompt.begin(), st_wait[i].prompt.begin() + std::min<size_t>(S, st_wait[i].prompt.size()), tokens.begin() + (size_t) i * S);
-        if (st_cfg.sample) {   // the draws of a generate() call of this utterance's own (run_utterances with n = 1)
-            sampler s = smp;
-            s.seed = st_cfg.seed; s.n_calls = 0;
-            for (uint32_t k = 0; k < st_max_gen; k++) s.draw_uniforms(uni.data() + ((size_t) i * st_max_gen + k) * nh);
-        }
+        if (st_cfg.sample) draw_call_uniforms(st_cfg.seed, st_max_gen, uni.data() + (size_t) i * st_max_gen * nh, nh);
     }
     hip_check(tts_hip_dia_stream_admit(lm, n, slots.data(), tokens.data(), lens.data(), nullptr, st_cfg.sample ? uni.data() : nullptr), "tts_hip_dia_stream_admit");
     for (uint32_t i = 0; i < n; i++) {

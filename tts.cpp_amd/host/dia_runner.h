@@ -116,6 +116,8 @@ struct dia_runner final : tts_generation_runner {
     void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
     void stream_step_chunked(std::vector<stream_result> & finished);
     uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
+    tts_hip_dia_codes loop_codes() const;                           // the special ids and the delay pattern, as the device loop takes them
+    void     draw_call_uniforms(uint64_t seed, uint32_t max_gen, float * out, size_t stride) const;
     void     encode_single(const char * sentence);
     void     encode_batch(const std::vector<std::string> & sentences);
     // the one generation loop under generate, generate_batch and their chunked forms
