@@ -627,7 +627,14 @@ int tts_hip_parler_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t step
 int tts_hip_parler_stream_end(tts_hip_ctx *ctx);
 
 /* Tuning and fallback switches by name (profiles/ harnesses and the fallback parity test; call between tts_hip_create and the first
- * launch).  Unknown key: -1.  Not an environment variable on purpose: a deployment cannot flip a kernel path by accident. */
+ * launch).  Unknown key: -1.  Not an environment variable on purpose: a deployment cannot flip a kernel path by accident.
+ * Kokoro contexts (each 1 by default, 0 = the fallback; tests/test_gpu_kokoro.py runs every one against the oracle):
+ *   kokoro_mfma         0: every convolution, linear and instance norm through the plain one-thread-per-output kernels
+ *   kokoro_b3           0: the k = 3 / 5 / 7 / 11 same-convolutions on the exact-fp32 MFMA kernel instead of split products
+ *   kokoro_split        0: those split products as three bf16 planes (six products) instead of fp16 hi + lo (three)
+ *   kokoro_attn_lds     0: ALBERT's attention as one wave per (head, row) instead of keys staged through LDS
+ *   kokoro_lstm_split   0: each LSTM direction in one workgroup instead of hid / 16 workgroups exchanging their hidden state
+ *   kokoro_adain_split  0: instance-norm rows of 8192 positions and more in one workgroup per channel instead of slices over workgroups */
 int tts_hip_tune(tts_hip_ctx *ctx, const char *key, int value);
 
 /* stream / device handles for callers that need to order their own work (torch interop) */

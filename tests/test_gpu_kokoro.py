@@ -158,9 +158,12 @@ def test_kokoro_runner_generate_batch_equals_generate_calls_in_a_row(tmp_path):
     seq2.close()
 
 
-@pytest.mark.parametrize("tune", [{}, {"kokoro_split": 0}, {"kokoro_b3": 0}], ids=["fp16_hi_lo_convs", "bf16x3_convs", "exact_fp32_convs"])
+@pytest.mark.parametrize("tune", [{}, {"kokoro_split": 0}, {"kokoro_b3": 0}, {"kokoro_mfma": 0}, {"kokoro_lstm_split": 0}],
+                         ids=["fp16_hi_lo_convs", "bf16x3_convs", "exact_fp32_convs", "plain_kernels", "one_workgroup_lstm"])
 def test_kokoro_82m_shapes_match_oracle(tune):
-    """(default since round 6: the k = 3 / 5 / 7 / 11 same-convolutions as fp16 hi + lo split products, three MFMAs per product,
+    """(tune("kokoro_mfma") = 0: kk_conv1d_kernel, kk_convt1d_kernel, kk_linear_kernel and kk_adain_kernel for everything; tune("kokoro_lstm_split") = 0:
+    kk_lstm_kernel at hid 256 — the two fallbacks at these widths)
+    (default since round 6: the k = 3 / 5 / 7 / 11 same-convolutions as fp16 hi + lo split products, three MFMAs per product,
     conv1d_mfma_b3_kernel<.., KT, SplitH2>; tune("kokoro_split") = 0: three bf16 planes, six products; tune("kokoro_b3") = 0: the exact-fp32 MFMA kernel)
     BASELINE config 2's dimensions (hexgrad/Kokoro-82M: ALBERT 768 x 12 recurrences, predictor / text encoder 512, decoder 1024,
     generator 512 -> 256 -> 128, (10, 6) upsampling, n_fft 20 / hop 5) with seeded weights, 10 phoneme ids: durations identical,
@@ -217,3 +220,105 @@ def test_kokoro_82m_projections_over_a_long_sequence():
     print(f"kokoro-82m, 42 rows: duration states {relerr(hid, ref_hid):.2e}")
     assert np.array_equal(lens, ref_lens) and relerr(hid, ref_hid) < 2e-3     # fp16-table GELU on both sides (see the 82M test above)
     eng.close()
+
+
+@pytest.mark.parametrize("tune", [{"kokoro_mfma": 0}, {"kokoro_lstm_split": 0}], ids=["plain_kernels", "one_workgroup_lstm"])
+def test_kokoro_82m_fallbacks_over_a_long_sequence(tune):
+    """The 42 rows of test_kokoro_82m_projections_over_a_long_sequence through the two fallbacks: tune("kokoro_mfma") = 0 keeps kk_linear_kernel (one wave
+    per output) at 32 rows and more, tune("kokoro_lstm_split") = 0 runs kk_lstm_kernel at hid 256 over 42 steps — durations identical, duration states
+    against the oracle under the same bound (fp16-table GELU on both sides)"""
+    model = synth.build_kokoro(synth.kokoro_82m())
+    cfg = model.cfg
+    eng = hip.KokoroEngine(model, tune=tune)
+    rng = np.random.default_rng(40)
+    toks = np.concatenate([[0], rng.integers(1, cfg.vocab, 40), [0]]).astype(np.uint32)
+    lens, hid = eng.durations(toks, cfg.voices[0])
+    ref_lens, ref_hid = orc.KokoroOracle(model).durations(toks, cfg.voices[0])
+    print(f"kokoro-82m, 42 rows, {tune}: duration states {relerr(hid, ref_hid):.2e}")
+    assert np.array_equal(lens, ref_lens) and relerr(hid, ref_hid) < 2e-3
+    eng.close()
+
+
+def uneven_lens(n, total):
+    """n whole-number lengths in 1..50 that are not all equal and add up to `total` (a non-trivial alignment)"""
+    wt = 1.0 + (np.arange(n) * 5) % 7
+    lens = np.maximum(1, np.floor(wt * total / wt.sum())).astype(np.int64)
+    i = 0
+    while lens.sum() != total:
+        lens[i % n] += 1 if lens.sum() < total else -1
+        i += 1
+    assert lens.min() >= 1 and lens.max() <= 50 and len(set(lens.tolist())) > 1 and lens.sum() == total
+    return lens.astype(np.float32)
+
+
+def forced_generation(model, seed, n_ids, lens):
+    """the oracle's side of a generation from forced lengths: ids, oracle hidden states, noise, conditioning and audio"""
+    cfg = model.cfg
+    o = orc.KokoroOracle(model)
+    rng = np.random.default_rng(seed)
+    toks = np.concatenate([[0], rng.integers(1, cfg.vocab, n_ids - 2), [0]]).astype(np.uint32)
+    _, ref_hid = o.durations(toks, cfg.voices[0])
+    noise = rng.random(o.noise_len(int(lens.sum())), dtype=np.float32)
+    ref_pcm, _, _, ref_hs = o.generate(toks, lens, ref_hid, cfg.voices[0], noise, want_curves=True)
+    assert np.isfinite(ref_pcm).all()
+    return toks, ref_hid, noise, ref_hs, ref_pcm
+
+
+@pytest.mark.parametrize("kw, frames, sliced", [({}, 69, True), ({}, 84, True), ({}, 68, False), (dict(gen_channels=512, res_kernels=(3,)), 72, True)],
+                         ids=["tiny_L8281_S32", "tiny_L10081_S32", "tiny_L8161_below_the_threshold", "wide_L8641_S16"])
+def test_kokoro_long_rows_through_the_sliced_instance_norm(kw, frames, sliced):
+    """kk_adain_split_kernel (rows of 8192 positions and more: S = min(32, max(2, 2048 / C)) slices of 4-aligned chunks, the last one ragged, three phases)
+    against the oracle, and tune("kokoro_adain_split") = 0 (kk_adain_kernel, one workgroup per channel) as its fallback.  The generator's last stage has
+    L = 120 frames + 1 positions: 69 frames (8281, the first length past the threshold; chunk 260, last slice 221) and 84 frames (10081; chunk 316, last
+    slice 285) at 6 channels -> S = 32; 72 frames (8641; chunk 544, last slice 481, and a ragged 193-position tile of the split-product convolutions) with
+    gen_channels 512 -> 128 channels, S = 16 as in the 82M model; 68 frames (8161) stay below the threshold.  12 ids, forced lengths that are not all equal,
+    the oracle's hidden states and conditioning.  Both paths within the file's bound; on the long rows they differ in at least one sample (another
+    summation order over more than 8000 terms), which shows that the key switched the path.
+    The fp32 oracle itself against the float64 torch restatement of tests/golden/make_golden.py at these inputs (CPU): 2.3e-6 (69 frames), 6.6e-7 (84),
+    1.1e-6 (68), 3.0e-6 (wide, 72) — the bound of 2e-4 has two decades of room at 8000 to 10000 positions and stays as it is.
+    Device figures: not recorded yet — every case prints its own before it asserts (pytest -s)."""
+    model = synth.build_kokoro(synth.kokoro_tiny(**kw))
+    cfg = model.cfg
+    lens = uneven_lens(12, frames)
+    toks, ref_hid, noise, ref_hs, ref_pcm = forced_generation(model, 8192 + frames, 12, lens)
+    assert ((2 * frames * int(np.prod(cfg.up_rates)) + 1) >= 8192) == sliced
+    out = {}
+    for v in ((1, 0) if sliced else (1,)):
+        eng = hip.KokoroEngine(model, tune={"kokoro_adain_split": v})
+        out[v] = eng.generate(toks, lens, ref_hid, cfg.voices[0], noise, hsrc_in=ref_hs)
+        eng.close()
+        print(f"kokoro adain, {kw or 'tiny'}, {frames} frames, kokoro_adain_split={v}: audio {relerr(out[v], ref_pcm):.2e}")
+    for v, pcm in out.items():
+        assert pcm.shape == ref_pcm.shape and relerr(pcm, ref_pcm) < 2e-4, v
+    if sliced:
+        assert not np.array_equal(out[0], out[1])
+
+
+@pytest.mark.parametrize("D", [64, 128, 256])
+def test_kokoro_every_lstm_width_with_workgroups_that_exchange_their_state(D):
+    """kk_lstm_split_kernel<CP> for CP = 8, 16, 32: kokoro_tiny(dp_hidden = 64 / 128 / 256) gives hid 32 / 64 / 128, so 2 / 4 / 8 workgroups per direction
+    that hand each other their 16 hidden values at every step.  durations() on 30 ids (32 rows): lengths identical, hidden states under the tiny model's
+    bound.  generate() on 12 ids x 25 forced frames: the shared LSTM runs 300 steps, the step tag and the two-parity exchange buffer wrap 150 times.
+    Each with tune("kokoro_lstm_split") = 1 and 0 (kk_lstm_kernel): both within the bound, and not identical (4 partial sums of CP terms against one sum).
+    The fp32 oracle against the float64 torch restatement at these inputs (CPU): audio after 300 steps 1.9e-6 / 9.6e-7 / 5.2e-6 for dp_hidden 64 / 128 / 256;
+    duration states 3.4e-7 / 5.3e-7 / 8.0e-7 with an fp32 GELU (device and oracle both take ALBERT's GELU from the fp16 table) — the bound stays 2e-4.
+    Device figures: not recorded yet — every case prints its own before it asserts (pytest -s)."""
+    model = synth.build_kokoro(synth.kokoro_tiny(dp_hidden=D))
+    cfg = model.cfg
+    o = orc.KokoroOracle(model)
+    toks30 = np.concatenate([[0], np.random.default_rng(D).integers(1, cfg.vocab, 30), [0]]).astype(np.uint32)
+    ref_lens, ref_hid30 = o.durations(toks30, cfg.voices[0])
+    lens = np.full(12, 25.0, dtype=np.float32)
+    toks, ref_hid, noise, ref_hs, ref_pcm = forced_generation(model, 300 + D, 12, lens)
+    hid, pcm = {}, {}
+    for v in (1, 0):
+        eng = hip.KokoroEngine(model, tune={"kokoro_lstm_split": v})
+        got_lens, hid[v] = eng.durations(toks30, cfg.voices[0])
+        assert np.array_equal(got_lens, ref_lens), v
+        pcm[v] = eng.generate(toks, lens, ref_hid, cfg.voices[0], noise, hsrc_in=ref_hs)
+        eng.close()
+        print(f"kokoro lstm, dp_hidden {D}, kokoro_lstm_split={v}: duration states {relerr(hid[v], ref_hid30):.2e}, audio after 300 steps {relerr(pcm[v], ref_pcm):.2e}")
+    for v in (1, 0):
+        assert relerr(hid[v], ref_hid30) < 2e-4, v
+        assert pcm[v].shape == ref_pcm.shape and relerr(pcm[v], ref_pcm) < 2e-4, v
+    assert not np.array_equal(hid[0], hid[1]) and not np.array_equal(pcm[0], pcm[1])

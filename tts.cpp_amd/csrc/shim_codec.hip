@@ -1033,7 +1033,7 @@ struct KRun {
         linear(w(gw), w(gb), style, S, 1, S, C, gamma, C);
         linear(w(bw), w(bb), style, S, 1, S, C, beta, C);
         if (!err.empty() || !gamma || !beta) return;
-        if (c->kk_mfma && L >= 8192) {   // long rows: slices over workgroups, three phases (kk_adain_split_kernel)
+        if (c->kk_mfma && c->kk_adain_split && L >= 8192) {   // long rows: slices over workgroups, three phases (kk_adain_split_kernel; tune("kokoro_adain_split") = 0: the kernel below)
             const int S = (int) std::min<int64_t>(32, std::max<int64_t>(2, (int64_t) 2048 / C));
             float *part = s.f((size_t) 2 * C * S);
             if (!part) return;
@@ -1175,7 +1175,7 @@ static int kokoro_check_stuck(tts_hip_ctx *c, const char *who) {
     if (stuck) {
         (void) hipMemset(c->kk_stuck, 0, 4);
         return set_err("%s: the workgroups of a split LSTM recurrence never saw each other's hidden state (device oversubscribed?); "
-                       "TTS_HIP_KOKORO_LSTM_SPLIT=0 selects the single-workgroup kernel", who);
+                       "tune(\"kokoro_lstm_split\", 0) selects the single-workgroup kernel", who);
     }
     return 0;
 }

@@ -171,6 +171,7 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
         c->kk_split = v != 0;
     }
     else if (k == "kokoro_lstm_split") c->kk_lstm_split = v != 0;
+    else if (k == "kokoro_adain_split") c->kk_adain_split = v != 0;
     else if (k == "ln_fuse_max") c->ln_fuse_max = std::max(0, std::min(32, v));
     else if (k == "attn_short") c->attn_short = v != 0;
     else if (k == "attn_rows_min") c->attn_rows_min = std::max(0, v);

@@ -356,6 +356,7 @@ struct tts_hip_ctx {
     bool kk_b3 = true;          // tune("kokoro_b3") = 0: Kokoro's k = 3 / 5 / 7 / 11 same-convolutions stay on the exact-fp32 MFMA kernel instead of bf16 x 3 split products
     bool kk_attn_lds = true;    // tune("kokoro_attn_lds") = 0: ALBERT's attention as one wave per (head, row) walking the K rows from memory (kk_albert_attn_kernel)
     int kk_split = 1;           // tune("kokoro_split"): the operand split of those convolutions — 1 = fp16 hi + lo, three products (round 6), 0 = three bf16 planes, six products
+    bool kk_adain_split = true; // tune("kokoro_adain_split")=0: instance-norm rows of 8192 positions and more stay on one workgroup per channel (kk_adain_kernel) instead of the sliced kk_adain_split_kernel
     bool kk_mfma = true;        // tune("kokoro_mfma")=0: every Kokoro convolution through the one-thread-per-output kernel
     bool attn_short = true;     // tune("attn_short")=0: cross-attention through the general kernel
     int dac_group = 64;         // TTS_HIP_DAC_GROUP: utterances per codec pass (16: 451, 32: 458, 64: 461, 128: 460, 384: 462 audio-s/s at 3 x 384)
