@@ -560,6 +560,9 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
 /* Copy an internal buffer to the host.  what: "hidden" (final-normed hidden of the last forward,
  * [rows][H]), "k:<layer>:<seq>" / "v:<layer>:<seq>" (cache rows [n_pos][H] as fp32),
  * "dac:<stage>" (activation after DAC stage, see oracle stage numbering; requires
+ * tts_hip_set_debug(ctx,1) before the decode); SNAC contexts: "snac:<stage>" (utterance 0's valid region
+ * [C][tokens * rate] after the stage of the last pass, orc_snac_decode's numbering: 0 = the summed codebook levels, 1 = after
+ * the input depthwise conv and the `up` conv, 2 + i = the end of block i, 2 + n_blocks = the PCM before the crop; requires
  * tts_hip_set_debug(ctx,1) before the decode); Orpheus contexts: "l_logits" (the logits row the last
  * step left), "l_k:<layer>" / "l_v:<layer>" (cache slot 0 of a layer, [n_ctx][kv width]).
  * Returns number of floats written or <0. */

@@ -480,7 +480,7 @@ class SnacOracle:
 
     def __init__(self, model):
         self.L = lib()
-        self.L.orc_snac_decode.argtypes = [C.POINTER(SnacModel), C.POINTER(C.c_uint32), C.c_int, fp, fp]
+        self.L.orc_snac_decode.argtypes = [C.POINTER(SnacModel), C.POINTER(C.c_uint32), C.c_int, fp, fp, C.c_int, fp]
         self.L.orc_snac_decode.restype = C.c_int64
         cfg = model.cfg
         self.cfg = cfg
@@ -522,8 +522,24 @@ class SnacOracle:
             n += L
         return n
 
-    def decode(self, codes, T, noise=None):
-        """codes: level-major flat ids (T/4 + T/2 + T for repeats 4,2,1); noise: noise_len(T) floats or None"""
+    def n_stages(self):
+        return 3 + len(self.cfg.strides)
+
+    def stage_shape(self, stage, T):
+        """0: summed codebook levels, 1: after the input depthwise conv and `up`, 2 + i: end of block i, 2 + n_blocks: the PCM"""
+        cfg = self.cfg
+        if stage == 0:
+            return (cfg.latent, T)
+        if stage == 2 + len(cfg.strides):
+            return (1, T * cfg.hop)
+        c, L = cfg.c0, T
+        for s in cfg.strides[:stage - 1]:
+            c //= 2
+            L *= s
+        return (c, L)
+
+    def decode(self, codes, T, noise=None, stage=-1):
+        """codes: level-major flat ids (T/4 + T/2 + T for repeats 4,2,1); noise: noise_len(T) floats or None; stage >= 0: -> (pcm, that stage)"""
         codes = np.ascontiguousarray(codes, dtype=np.uint32)
         assert codes.size == sum(T // r for r in self.cfg.repeats)
         pcm = np.empty(T * self.cfg.hop, dtype=np.float32)
@@ -531,9 +547,27 @@ class SnacOracle:
         if noise is not None:
             nz = np.ascontiguousarray(noise, dtype=np.float32)
             assert nz.size == self.noise_len(T)
-        n = self.L.orc_snac_decode(C.byref(self.m), u32p(codes), T, f32p(nz) if nz is not None else None, f32p(pcm))
+        st = None
+        if stage >= 0:
+            st = np.empty(self.stage_shape(stage, T), dtype=np.float32)
+        n = self.L.orc_snac_decode(C.byref(self.m), u32p(codes), T, f32p(nz) if nz is not None else None, f32p(pcm), stage,
+                                   f32p(st) if st is not None else None)
         assert n == pcm.size
-        return pcm
+        return (pcm, st) if stage >= 0 else pcm
+
+    def decode_stages(self, codes, T, noise=None):
+        """-> (pcm, [every stage]) from one decode"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        assert codes.size == sum(T // r for r in self.cfg.repeats)
+        nz = None if noise is None else np.ascontiguousarray(noise, dtype=np.float32)
+        assert nz is None or nz.size == self.noise_len(T)
+        shapes = [self.stage_shape(st, T) for st in range(self.n_stages())]
+        pcm = np.empty(T * self.cfg.hop, dtype=np.float32)
+        buf = np.empty(sum(c * l for c, l in shapes), dtype=np.float32)
+        n = self.L.orc_snac_decode(C.byref(self.m), u32p(codes), T, f32p(nz) if nz is not None else None, f32p(pcm), -2, f32p(buf))
+        assert n == pcm.size
+        cuts = np.cumsum([c * l for c, l in shapes])[:-1]
+        return pcm, [a.reshape(sh) for a, sh in zip(np.split(buf, cuts), shapes)]
 
 
 class OrpheusOracle:

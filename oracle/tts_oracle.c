@@ -923,7 +923,15 @@ void orc_conv1d_dw(const float *x, int C, int64_t L, const float *w, const float
     }
 }
 
-int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, const float *noise, float *pcm_out) {
+/* stage k of orc_snac_decode: copied when it is the one asked for, or appended when every stage is (stage == -2) */
+static void snac_stage(int want, int k, float **out, const float *src, size_t n) {
+    if (!*out || (want != k && want != -2)) return;
+    memcpy(*out, src, n * 4);
+    if (want == -2) *out += n;
+}
+
+int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, const float *noise, float *pcm_out,
+                        int stage, float *stage_out) {
     int64_t L = T;
     int C = m->latent;
     float *cur = (float *) calloc((size_t) C * L, 4);
@@ -945,12 +953,14 @@ int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, c
         }
         off += (size_t) n;
     }
+    snac_stage(stage, 0, &stage_out, cur, (size_t) C * L);
     float *nxt = (float *) malloc((size_t) C * L * 4);
     orc_conv1d_dw(cur, C, L, m->in_w, m->in_b, 7, 3, 1, nxt);                         /* :141-142 */
     free(cur); cur = nxt;
     nxt = (float *) malloc((size_t) m->c0 * L * 4);
     orc_conv1d(cur, C, L, m->up_w, m->up_b, m->c0, 1, 0, 1, nxt);                     /* :143-144 */
     free(cur); cur = nxt; C = m->c0;
+    snac_stage(stage, 1, &stage_out, cur, (size_t) C * L);
     size_t noise_off = 0;
     for (int bi = 0; bi < m->n_blocks; bi++) {                                        /* build_layer, gnac.cpp:151-164 */
         const orc_snac_block *b = &m->blocks[bi];
@@ -977,11 +987,13 @@ int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, c
             for (size_t i = 0; i < (size_t) C * L; i++) cur[i] = t1[i] + cur[i];
         }
         free(t1); free(t2);
+        snac_stage(stage, 2 + bi, &stage_out, cur, (size_t) C * L);
     }
     orc_snake(cur, C, L, m->final_alpha);                                             /* :152-155 */
     float *pcm = (float *) malloc((size_t) L * 4);
     orc_conv1d(cur, C, L, m->final_w, m->final_b, 1, 7, 3, 1, pcm);
     for (int64_t t = 0; t < L; t++) pcm_out[t] = tanhf(pcm[t]);
+    snac_stage(stage, 2 + m->n_blocks, &stage_out, pcm_out, (size_t) L);
     free(pcm); free(cur);
     return L;
 }

@@ -291,8 +291,13 @@ typedef struct {
 } orc_snac_model;
 /* codes: level-major as snac_runner::set_inputs lays them out (:161-178): T/repeats[0] ids of level 0, then
  * T/repeats[1] of level 1, ...; noise: per layer l, L_l floats (L_l = T * prod(stride_0..l)), concatenated (:131-137),
- * or NULL for no noise; pcm_out: T * prod(strides). */
-int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, const float *noise, float *pcm_out);
+ * or NULL for no noise; pcm_out: T * prod(strides).
+ * stage_out (optional): if stage>=0 the activation after that stage is copied there:
+ *   stage 0 = summed codebook levels [latent][T], 1 = after the input depthwise conv and the `up` conv [c0][T],
+ *   2..1+n_blocks = after block i (its third residual unit), 2+n_blocks = the PCM [1][T * prod(strides)];
+ *   stage -2 = all of them back to back (one decode instead of one per stage). */
+int64_t orc_snac_decode(const orc_snac_model *m, const uint32_t *codes, int T, const float *noise, float *pcm_out,
+                        int stage, float *stage_out);
 void orc_conv1d_dw(const float *x, int C, int64_t L, const float *w, const float *b, int K, int pad, int dil, float *y);
 
 /* primitives exposed for unit tests */

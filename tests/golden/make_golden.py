@@ -163,9 +163,10 @@ def torch_t5(model, ids):
     return x
 
 
-def torch_snac(model, codes, T, noise):
+def torch_snac(model, codes, T, noise, stages=False):
     """SNAC decoder (src/decoder/snac_model.cpp:86-159) in float64 torch: repeat_interleave'd codebook levels, depthwise /
-    pointwise convs, ConvTranspose1d, noise block x + noise * conv1x1(x), snake, tanh."""
+    pointwise convs, ConvTranspose1d, noise block x + noise * conv1x1(x), snake, tanh.  stages: -> (pcm, [the summed levels, after `in` and
+    `up`, the end of every block, the PCM as [1][L]]), orc_snac_decode's stage numbering."""
     c = model.cfg
 
     def P(name):
@@ -185,8 +186,10 @@ def torch_snac(model, codes, T, noise):
         z = Fn.conv1d(z, P(f"quantizers.{i}.out_proj.weight"), P(f"quantizers.{i}.out_proj.bias"))
         z = torch.repeat_interleave(z, rep, dim=-1)
         x = z if x is None else x + z
+    outs = [x[0]]
     x = Fn.conv1d(x, P("in.weight"), P("in.bias"), padding=3, groups=c.latent)
     x = Fn.conv1d(x, P("up.weight"), P("up.bias"))
+    outs.append(x[0])
     noff = 0
     for li, (s, pd) in enumerate(zip(c.strides, c.paddings)):
         p = f"layers.{li}."
@@ -206,8 +209,11 @@ def torch_snac(model, codes, T, noise):
             y = snake(y, P(q + "final.alpha"))
             y = Fn.conv1d(y, P(q + "final.weight"), P(q + "final.bias"))
             x = x + y
+        outs.append(x[0])
     x = snake(x, P("alpha_out"))
-    return torch.tanh(Fn.conv1d(x, P("final.weight"), P("final.bias"), padding=3))[0, 0]
+    x = torch.tanh(Fn.conv1d(x, P("final.weight"), P("final.bias"), padding=3))
+    outs.append(x[0])
+    return (x[0, 0], outs) if stages else x[0, 0]
 
 
 def torch_orpheus(model, prompt, steps):

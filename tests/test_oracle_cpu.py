@@ -231,6 +231,68 @@ def test_snac_decoder_oracle_matches_torch_golden():
         assert np.abs(y - ref.numpy()).max() < 1e-5
 
 
+def _make_golden():
+    """tests/golden/make_golden.py as a module: the float64 torch restatements the golden vectors were made with"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(__file__), "golden", "make_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def snac_case(cfg, T):
+    """the codes and the noise of the SNAC stage tests (tests/test_gpu_snac.py decodes the same ones on the device)"""
+    rng = np.random.default_rng(T)
+    codes = np.concatenate([rng.integers(0, cfg.cb_size, T // r) for r in cfg.repeats]).astype(np.uint32)
+    n, L = 0, T
+    for s in cfg.strides:
+        L *= s
+        n += L
+    return codes, np.random.default_rng(T + 1).standard_normal(n).astype(np.float32)
+
+
+@pytest.mark.parametrize("with_noise", [True, False], ids=["noise", "clean"])
+@pytest.mark.parametrize("layout,T", [("snac_tiny", 80), ("snac_24khz", 76)])
+def test_snac_oracle_stages_match_float64(layout, T, with_noise):
+    """Every stage of orc_snac_decode (0 the summed codebook levels, 1 after `in` and `up`, 2 + i the end of block i, last the PCM) against
+    float64 torch_snac computed here, at lengths of many tiles: 2e-5 of max|f64| per stage, the bar of the other oracle stages.
+
+    d_ref[stage] = max|orc - f64| / max|f64| as measured (tests/test_gpu_snac.py holds the device to max(4 x d_ref, 1e-6)):
+
+        layout      noise   stage 0   1         2         3         4         5         6
+        snac_tiny   yes     1.14e-07  3.10e-07  4.70e-07  3.86e-07  5.03e-07
+        snac_tiny   no      1.14e-07  3.10e-07  4.55e-07  4.85e-07  4.21e-07
+        snac_24khz  yes     8.74e-08  1.44e-06  1.68e-06  1.38e-06  1.27e-06  1.23e-06  1.05e-06
+        snac_24khz  no      8.74e-08  1.44e-06  1.72e-06  1.42e-06  1.27e-06  1.12e-06  1.04e-06
+
+    The float64 PCM at snac_24khz, T = 76, with noise: max |x| 0.31, median 0.077, no sample above 0.99, 0.3 % below 1e-3 (not saturated: an
+    absolute bar on PCM means something).  The oracle takes 0.15 s / 0.5 s / 1.3 s for T = 8 / 28 / 76 at these dims."""
+    from tts_cpp_amd import synth as sy
+    model = sy.build_snac(getattr(sy, layout)(max_frames=128))
+    cfg = model.cfg
+    o = orc.SnacOracle(model)
+    codes, noise = snac_case(cfg, T)
+    if not with_noise:
+        noise = None
+    pcm64, st64 = _make_golden().torch_snac(model, codes, T, noise, stages=True)
+    pcm, st = o.decode_stages(codes, T, noise)
+    assert len(st) == len(st64) == 3 + len(cfg.strides)
+    d = []
+    for a, r in zip(st, st64):
+        assert a.shape == tuple(r.shape)
+        d.append(relerr(a, r.numpy()))
+    print(f"{layout} T={T} noise={with_noise}: d_ref per stage " + " ".join(f"{x:.2e}" for x in d))
+    assert max(d) < 2e-5, d
+    assert np.abs(pcm - pcm64.numpy()).max() < 2e-6
+    assert np.array_equal(st[-1][0], pcm)
+    # one stage at a time gives the same arrays, and a caller that asks for none the same PCM
+    assert np.array_equal(o.decode(codes, T, noise), pcm)
+    if layout == "snac_tiny":
+        for k in range(len(st)):
+            p2, a2 = o.decode(codes, T, noise, stage=k)
+            assert np.array_equal(p2, pcm) and np.array_equal(a2, st[k]), k
+
+
 def test_orpheus_decoder_oracle_matches_torch_golden():
     """orc_orpheus_decode (Llama-3 blocks, src/models/orpheus/model.cpp:186-325 restated with ggml's NEOX rope + frequency
     factors, iterated fp32 theta) against tests/golden/tiny_orpheus.npz (float64 torch with the HF rotary formulation):

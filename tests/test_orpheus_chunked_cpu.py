@@ -107,3 +107,25 @@ def test_windows_with_the_halo_stitch_to_the_full_decode():
         assert np.abs(stitched - full).max() <= 1e-6
         short = _stitch(o, cfg, levels, noise, K, h - 1, edges)
         assert np.abs(short - full).max() > 0, "h - 1 frames of halo must not be enough"
+
+
+def test_oracle_windows_with_halo_frames_match_the_full_decode_at_both_layouts():
+    """Windows of 2 kept frames with snac_halo_frames(cfg) frames either side, at the start, the end and two interior positions of a 24-frame
+    utterance: the oracle alone reproduces its own full decode within 1e-5 at snac_tiny and at snac_24khz (tests/test_gpu_snac.py decodes the
+    same windows on the device and holds them to the float64 decode of the whole utterance).  Measured on the oracle for these windows without
+    noise: at snac_tiny a 3-frame halo leaves 5.0e-4, a 4-frame halo 1.1e-5, the 5 frames of snac_halo_frames nothing; at snac_24khz a 2-frame
+    halo leaves 1.1e-4 and the 3 frames of snac_halo_frames nothing.  So the halo comes from snac_halo_frames, never from a constant."""
+    K = 24
+    for cfg, noises in ((synth.snac_tiny(max_frames=4096), (False, True)), (synth.snac_24khz(max_frames=4096), (False,))):
+        o = orc.SnacOracle(synth.build_snac(cfg))
+        h = hip.snac_halo_frames(cfg)
+        per = FRAME_TOKENS * cfg.hop
+        levels = _codes(cfg, K, 24)
+        for with_noise in noises:
+            noise = _noise_layers(cfg, K, 25) if with_noise else None
+            full = o.decode(_flat(levels), FRAME_TOKENS * K, None if noise is None else _noise_flat(cfg, noise, 0, K))
+            for f0 in (0, 9, 14, K - 2):
+                got = _stitch(o, cfg, levels, noise, K, h, [f0, f0 + 2])
+                err = float(np.abs(got - full[f0 * per:(f0 + 2) * per]).max())
+                print(f"latent {cfg.latent} noise={with_noise} frames [{f0}, {f0 + 2}) halo {h}: {err:.2e}")
+                assert err <= 1e-5, (cfg.latent, with_noise, f0, err)

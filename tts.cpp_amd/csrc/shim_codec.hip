@@ -1623,6 +1623,10 @@ static int snac_decode_pass(tts_hip_ctx *c, const char *what, const uint32_t *co
     for (uint32_t i = 0; i < 4; i++) ea.rep[i] = i < sd.n_codebooks ? (int) sd.repeats[i] : 1;
     hipLaunchKernelGGL(snac_embed_kernel, dim3((LS + 63) / 64, c->s_latent, n), dim3(64), 0, c->stream, ea);
     HIPCHK(hipGetLastError());
+    // tts_hip_set_debug: "snac:<stage>" = utterance 0's valid region [C][tok[0] * mult] after the stage (orc_snac_decode's numbering)
+    if (c->debug) c->dac_dbg.clear();
+    auto snap = [&](int stage, const float *dev, int ch, int mult, int ls) { return tok[0] ? dac_snapshot(c, stage, dev, ch, (size_t) tok[0] * mult, ls) : 0; };
+    CHK(snap(0, cur, c->s_latent, 1, LS));
     DacBatch bt;
     bt.n = (int) n; bt.frames = seg.tok; bt.mult = 1;
     { double tot = 0; for (uint32_t z = 0; z < n; z++) tot += tok[z]; bt.tot_frames = tot; }
@@ -1632,7 +1636,8 @@ static int snac_decode_pass(tts_hip_ctx *c, const char *what, const uint32_t *co
     };
     CHK(dw(cur, c->s_inw, c->s_inb, nullptr, nullptr, t1, c->s_latent, LS, 3, 1));                                 // :141-142
     CHK(launch_conv(c, bt, t1, c->s_latent, LS, c->s_upw, c->s_upb, 0, false, c->s_c0, 1, 0, 1, nullptr, false, cur));   // :143-144
-    int C = c->s_c0, cum = 0;
+    CHK(snap(1, cur, c->s_c0, 1, LS));
+    int C = c->s_c0, cum = 0, stage = 2;
     for (auto &b : c->sblocks) {                                                                                  // build_layer, gnac.cpp:151-164
         ConvTArgs ta{};
         ta.x = cur; ta.w = f32(b.w); ta.b = f32(b.b); ta.alpha = f32(b.alpha); ta.y = t1; ta.cin = b.cin; ta.cout = b.cout; ta.L = LS;
@@ -1658,8 +1663,10 @@ static int snac_decode_pass(tts_hip_ctx *c, const char *what, const uint32_t *co
             CHK(launch_conv(c, bt, t1, C, LS, b.res[r].out_w, b.res[r].out_b, 0, false, C, 1, 0, 1, cur, false, t2));
             std::swap(cur, t2);
         }
+        CHK(snap(stage++, cur, C, bt.mult, LS));
     }
     CHK(launch_conv(c, bt, cur, C, LS, c->s_fw, c->s_fb, c->s_falpha, true, 1, 7, 3, 1, nullptr, true, t1));        // :152-155
+    CHK(snap(stage, t1, 1, bt.mult, LS));
     if (n_keep) {
         size_t max_len = 0;
         for (uint32_t z = 0; z < n; z++) max_len = std::max<size_t>(max_len, hs[5 * n + z]);

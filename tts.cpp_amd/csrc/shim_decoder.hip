@@ -1945,8 +1945,8 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (hipMemcpy(out, c->cross_kv_ptr() + ((size_t) layer * 2 + kv) * c->ECAP * c->H * 4, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
-    if (starts_with(w, "dac:")) {
-        const int stage = atoi(w.c_str() + 4);
+    if (starts_with(w, "dac:") || (c->has_snac && starts_with(w, "snac:"))) {   // a SNAC context keeps its stages in the same table
+        const int stage = atoi(w.c_str() + (w[0] == 'd' ? 4 : 5));
         auto it = c->dac_dbg.find(stage);
         if (it == c->dac_dbg.end()) { set_err("debug_read(%s): no snapshot (enable tts_hip_set_debug before decode)", what); return -1; }
         if (it->second.size() > max_floats) { set_err("buffer too small"); return -1; }

@@ -631,6 +631,18 @@ class SnacEngine:
                                              out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def set_debug(self, on=True):
+        """keep utterance 0's activation after every stage of the next passes (debug_read 'snac:<stage>')"""
+        self._chk(self.L.tts_hip_set_debug(self.ctx, 1 if on else 0))
+
+    def debug_read(self, what, max_floats):
+        """'snac:<stage>': 0 the summed codebook levels, 1 after `in` and `up`, 2 + i the end of block i, 2 + n_blocks the PCM before the crop"""
+        out = np.empty(max_floats, dtype=np.float32)
+        n = self.L.tts_hip_debug_read(self.ctx, what.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), max_floats)
+        if n < 0:
+            raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
+        return out[:n].copy()
+
     def halo_frames(self):
         return snac_halo_frames(self.cfg)
 
