@@ -57,6 +57,13 @@ int           tts_c_generate_batch(tts_c_runner *r, const char *const *texts, in
  * utterances finish, not the order of texts[]; with TTS_SNAC_NO_NOISE every audio is bit for bit that of a tts_c_generate call of its own. */
 int           tts_c_generate_stream(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, const float **data,
                                     size_t *n_outputs);
+/* tts_c_generate_stream with one configuration per text, cfgs[n] (tts_generation_runner::generate_stream with configurations).  Orpheus takes them all
+ * into one session: the voice is a prompt prefix and every cache slot carries its own sampler, so texts that differ in voice, seed, sample, top_k,
+ * temperature, top_p or repetition_penalty share the forward (a sampled text needs the device sampler, top_k 1..64 and top_p > 0, and fails the call
+ * otherwise).  The other models run consecutive texts with equal configurations as one session each.  data[i] is the audio of
+ * tts_c_generate(texts[i], &cfgs[i]) (Orpheus' SNAC noise block: as for tts_c_generate_stream). */
+int           tts_c_generate_stream_configs(tts_c_runner *r, const char *const *texts, const tts_c_config *cfgs, int n, const float **data,
+                                            size_t *n_outputs);
 /* Extension: chunked audio (tts_generation_runner::generate_chunked).  fn receives the utterance's PCM in consecutive pieces of at most
  * chunk_frames codec frames while the utterance is still generating (pcm valid during the call only; utterance = 0 here, the text's index in
  * the batch form); their concatenation equals tts_c_generate's / tts_c_generate_batch's audio.  fn returning 0 stops the generation at the

@@ -311,9 +311,22 @@ int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const t
  * Between begin and end every other tts_hip_orpheus_* generation call on the context (decode, step_batch, sample_logits, generate_*, gen_begin,
  * gen_launch) is refused with an error, as in the window between a gen_launch and its gen_wait; begin is refused in that window and while a
  * gen_* generation has unfinished utterances.  Every misuse (a busy slot, a slot >= n_slots, collect on a slot that has not been reported or for
- * more ids than it produced, n_slots > max_seqs, a prompt that does not fit) returns non-zero before anything is launched. */
+ * more ids than it produced, n_slots > max_seqs, a prompt that does not fit) returns non-zero before anything is launched.
+ * Mixed session: begin_mixed opens a session whose slots carry their own sampler, so utterances that differ in top_k, temperature, top_p or
+ * repetition penalty, greedy ones among them, share one forward.  admit_mixed takes utterance i's sampler as sampling[i] (NULL: sampler::max; else
+ * the limits of tts_hip_orpheus_generate_sampled, checked for all n before anything is launched) and its draws as uniforms[i * max_new ..] (ignored for
+ * a greedy utterance; uniforms may be NULL when all n are greedy).  The slot's record {mode, top_k, temperature, top_p} and its own repetition-penalty
+ * table [max_new] are rewritten at every admission, so nothing of the slot's previous utterance stays.  run, collect and end are the calls above.  Per
+ * step a run enqueues the arg-max pair when a live row is greedy, the top-k kernels when one is sampled and the softmax total when a sampled one has
+ * top_p < 1 (known when the run's rows are staged); each kernel skips the rows of the other mode.  Per row the selection kernels are the uniform
+ * session's with the parameters read from the row's slot, so an utterance's ids are those of its own one-sequence generation with its own sampler
+ * (tests/test_gpu_orpheus_stream_mixed.py).  admit_mixed on a session opened by begin, and admit on one opened by begin_mixed, return non-zero
+ * with the session unchanged. */
 int tts_hip_orpheus_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sampling);
 int tts_hip_orpheus_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt, const float *uniforms);
+int tts_hip_orpheus_stream_begin_mixed(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_new, uint32_t stop_id);
+int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt,
+                                       const tts_hip_sampling *const *sampling, const float *uniforms);
 int tts_hip_orpheus_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts);
 int tts_hip_orpheus_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t count, uint32_t *tokens_out);
 int tts_hip_orpheus_stream_end(tts_hip_ctx *ctx);
@@ -321,6 +334,9 @@ int tts_hip_orpheus_stream_end(tts_hip_ctx *ctx);
  * of tts_hip_orpheus_sample_logits with uniforms[r], last_id[r], rep_count[r]; sampling NULL: sampler::max per row (uniforms / state may be NULL) */
 int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *ctx, uint32_t n_rows, const float *logits, const tts_hip_sampling *sampling, const float *uniforms, int32_t *last_id,
                                        uint32_t *rep_count, uint32_t *tokens_out);
+/* the mixed session's selection alone: row r with sampling[r] (NULL: sampler::max), per row the contract of tts_hip_orpheus_sample_logits */
+int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *ctx, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling, const float *uniforms,
+                                             int32_t *last_id, uint32_t *rep_count, uint32_t *tokens_out);
 
 /* ---- Dia encoder + decoder step (src/models/dia/model.cpp) --------------------------------------------------------
  * Device side of dia_runner::decode (:730-757): create, tts_hip_upload every "dia.*" tensor (names

@@ -10,6 +10,12 @@
                   other stopping condition the two loops share, the end of the cache: a context of RAGGED_CTX positions and prompts of
                   RAGGED_CTX + 1 - length ids.
 
+  --mixed         the mixed session (tts_hip_orpheus_stream_begin_mixed) at 8 and 32 slots, step time of tts_hip_orpheus_stream_run:
+                  (a) a uniform sampled session, (b) a mixed session whose slots all sample, each with its own setting (MIXED_SETTINGS in
+                  turn; the same number of launches as (a)), (c) a mixed session with every other slot greedy (two more launches per step, the
+                  arg-max pair).  The legs alternate within a repetition; five repetitions, median and spread (max - min).  A build without
+                  the mixed session runs (a) only: that is how orpheus_stream_mixed_parent_before.json was made.
+
 A build without the session (hip.OrpheusEngine has no stream_begin) runs the generate_batch / gen_launch legs only: that is how
 orpheus_stream_throughput_parent_before.json was made.  Usage: python profiles/orpheus_stream_bench.py [--out FILE] [--reps N]"""
 import argparse
@@ -70,6 +76,58 @@ def step_times(eng, B, prompts, uni, have_session, reps):
         out[mode].update({"device_driven_stream_run_ms_per_step": round(med(dev), 4), "device_driven_runs_ms": [round(x, 4) for x in dev],
                           "device_over_host": round(med(dev) / med(host), 4)})
     return out
+
+
+MIXED_SETTINGS = [dict(top_k=50, temperature=1.0), dict(top_k=40, temperature=0.6), dict(top_k=64, temperature=0.9), dict(top_k=20, temperature=1.2)]
+
+
+def mixed_step_times(eng, B, prompts, uni, have_mixed, reps):
+    """step time of stream_run for the legs (a), (b), (c), alternating within a repetition"""
+    legs = {"a_uniform_sampled": None}
+    if have_mixed:
+        legs["b_mixed_all_sampled"] = [dict(MIXED_SETTINGS[s % len(MIXED_SETTINGS)], repetition_penalty=1.0, top_p=1.0) for s in range(B)]
+        legs["c_mixed_half_greedy"] = [None if s % 2 else legs["b_mixed_all_sampled"][s] for s in range(B)]
+    runs = {k: [] for k in legs}
+    for _ in range(reps):
+        for name, settings in legs.items():
+            if settings is None:
+                eng.stream_begin(B, WARM + STEPS + 2, NO_STOP, sampled=True, **SMP)
+                eng.stream_admit(list(range(B)), prompts, uni)
+            else:
+                eng.stream_begin_mixed(B, WARM + STEPS + 2, NO_STOP)
+                eng.stream_admit_mixed(list(range(B)), prompts, settings, uni)
+            assert eng.stream_run(WARM) == []
+            t = time.perf_counter()
+            fin = eng.stream_run(STEPS)
+            runs[name].append((time.perf_counter() - t) / STEPS * 1e3)
+            assert fin == []
+            eng.stream_end()
+    return {k: {"stream_run_ms_per_step": round(med(v), 4), "spread_ms": round(max(v) - min(v), 4), "runs_ms": [round(x, 4) for x in v]} for k, v in runs.items()}
+
+
+def mixed_main(args):
+    have_mixed = hasattr(hip.OrpheusEngine, "stream_begin_mixed")
+    cfg = synth.orpheus_3b(ctx=1024, weight_type=gguf.Q4_0)
+    tensors, _ = sb.orpheus_tensors(cfg, np.random.default_rng(7))
+    model = sb._Model(cfg, tensors)
+    out = {"setup": {"model": "synthetic Orpheus-3B (28 x 3072, 24 / 8 heads x 128, ffn 8192, 156 940 logits), Q4_0, n_ctx 1024", "prompt_ids": 32, "timed_steps": STEPS,
+                     "warm_steps": WARM, "reps": args.reps, "uniform_sampling": SMP, "mixed_settings": MIXED_SETTINGS, "mixed_session": have_mixed,
+                     "timing": "host wall clock around the blocking tts_hip_orpheus_stream_run, median of reps, spread = max - min"},
+           "per_step": {}}
+    prng = np.random.default_rng(11)
+    for B in [int(x) for x in args.rows.split(",")]:
+        eng = hip.OrpheusEngine(cfg, max_seqs=B)
+        eng.load(model)
+        prompts = [prng.integers(0, cfg.vocab, 32).astype(np.uint32) for _ in range(B)]
+        uni = prng.random((B, WARM + STEPS + 2), dtype=np.float32)
+        eng.generate_batch(prompts, 4, NO_STOP)
+        out["per_step"][str(B)] = mixed_step_times(eng, B, prompts, uni, have_mixed, args.reps)
+        print(B, json.dumps(out["per_step"][str(B)]), flush=True)
+        eng.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
 
 
 def pick_stop(pilot):
@@ -135,7 +193,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(HERE, "orpheus_stream_throughput.json"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rows", default="8,32")
+    ap.add_argument("--mixed", action="store_true", help="the legs of the mixed session instead (--reps 5 for the recorded files)")
     args = ap.parse_args()
+    if args.mixed:
+        return mixed_main(args)
     have_session = hasattr(hip.OrpheusEngine, "stream_begin")
     cfg = synth.orpheus_3b(ctx=1024, weight_type=gguf.Q4_0)
     rng = np.random.default_rng(7)

@@ -974,11 +974,10 @@ static __global__ __launch_bounds__(1024) void topk_sample_kernel(const unsigned
 __device__ __forceinline__ uint32_t rows_slot(const uint32_t *row_slot, int slot0, int r) { return row_slot ? row_slot[r] : (uint32_t) (slot0 + r); }
 __device__ __forceinline__ bool rows_finished(const uint32_t *slot_state, uint32_t s) { return slot_state && slot_state[(size_t) s * LLAMA_SLOT_STATE + 1] != 0; }
 
-static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const uint32_t *row_slot, int slot0,
-                                                                 const uint32_t *slot_state) {
+// The bodies, shared by the uniform kernels (parameters are kernel arguments) and the mixed ones (parameters come from the row's slot, below).
+__device__ __forceinline__ void argmax_parts_row(const float *logits, int V, int ld, float *pv, uint32_t *pi) {
     __shared__ float bv[4];
     __shared__ uint32_t bi[4];
-    if (rows_finished(slot_state, rows_slot(row_slot, slot0, blockIdx.y))) return;
     const float *lg = logits + (int64_t) blockIdx.y * ld;
     const int chunk = (V + ARGMAX_PARTS - 1) / ARGMAX_PARTS;
     const int i0 = blockIdx.x * chunk, i1 = min(V, i0 + chunk);
@@ -998,10 +997,7 @@ static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const fl
         pi[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = besti;
     }
 }
-static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const uint32_t *row_slot, int slot0,
-                                                               const uint32_t *slot_state) {
-    const int r = blockIdx.x;
-    if (rows_finished(slot_state, rows_slot(row_slot, slot0, r))) return;
+__device__ __forceinline__ void argmax_fold_row(const float *pv, const uint32_t *pi, uint32_t *token, int r) {
     float best = -INFINITY;
     uint32_t besti = 0xffffffffu;
     for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[r * ARGMAX_PARTS + i], pi[r * ARGMAX_PARTS + i]);
@@ -1009,18 +1005,10 @@ static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const floa
     for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
     if (threadIdx.x == 0) token[r] = besti == 0xffffffffu ? 0u : besti;
 }
-
-// grid (TOPK_PARTS, rows)
-static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float *logits_base, int V, int ld, int k, const double *pen_table, int pen_len, const uint32_t *smp,
-                                                              unsigned long long *cand_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+// logits / cand: the row's; last_id / rep_count: the slot's
+__device__ __forceinline__ void topk_parts_row(const float *logits, int V, int k, const double *pen_table, int pen_len, const int32_t *last_id, const uint32_t *rep_count,
+                                               unsigned long long *cand) {
     __shared__ unsigned long long keys[TOPK_SLICE];
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    const float *logits = logits_base + (int64_t) r * ld;
-    const int32_t *last_id = (const int32_t *) (smp + (size_t) 3 * s);
-    const uint32_t *rep_count = smp + (size_t) 3 * s + 1;
-    unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
     const int chunk = (V + TOPK_PARTS - 1) / TOPK_PARTS;
     const int i0 = (int) blockIdx.x * chunk;
     const int last = pen_table ? last_id[0] : -1;
@@ -1041,20 +1029,10 @@ static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float
     bitonic_sort_keys(keys, TOPK_SLICE);
     for (int j = threadIdx.x; j < k; j += blockDim.x) cand[(int) blockIdx.x * TOPK_MAXK + j] = keys[j];
 }
-
-// grid (1, rows)
-static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base, float temperature,
-                                                                  const double *pen_table, int pen_len, const uint32_t *smp, float *total_base, const uint32_t *row_slot,
-                                                                  int slot0, const uint32_t *slot_state) {
+__device__ __forceinline__ void softmax_total_row(const float *logits, int V, const unsigned long long *cand, float temperature, const double *pen_table, int pen_len,
+                                                  const int32_t *last_id, const uint32_t *rep_count, float *total_out) {
     __shared__ __attribute__((aligned(16))) float ex[SOFTMAX_CHUNK];
     __shared__ float s_top;
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    const float *logits = logits_base + (int64_t) r * ld;
-    const unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
-    const int32_t *last_id = (const int32_t *) (smp + (size_t) 3 * s);
-    const uint32_t *rep_count = smp + (size_t) 3 * s + 1;
     const bool temp = temperature != 1.0f;
     if (threadIdx.x == 0) {
         unsigned long long best = ~0ull;
@@ -1093,21 +1071,13 @@ static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const f
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) total_base[r] = total;
+    if (threadIdx.x == 0) total_out[0] = total;
 }
-
-// grid (1, rows); the row's draw is uniforms[s * uni_stride + call counter of s], which advances
-static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const unsigned long long *cand_base, int k, float temperature, const float *uniforms, int64_t uni_stride,
-                                                                const double *pen_table, uint32_t *smp, uint32_t *token, float top_p, const float *total_base,
-                                                                const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+// uniforms: the slot's stretch; total_in (NULL: top_p >= 1): the row's softmax total; token: the row's
+__device__ __forceinline__ void topk_sample_row(const unsigned long long *cand, int k, float temperature, const float *uniforms, const double *pen_table, int32_t *last_id,
+                                                uint32_t *rep_count, uint32_t *call, uint32_t *token, float top_p, const float *total_in) {
     __shared__ unsigned long long keys[TOPK_PARTS * TOPK_MAXK];
     __shared__ float prob[TOPK_MAXK];
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    const unsigned long long *cand = cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK;
-    int32_t *last_id = (int32_t *) (smp + (size_t) 3 * s);
-    uint32_t *rep_count = smp + (size_t) 3 * s + 1, *call = smp + (size_t) 3 * s + 2;
     const int n = TOPK_PARTS * k;
     int P = 1;
     while (P < n) P <<= 1;
@@ -1126,12 +1096,12 @@ static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const uns
     if (threadIdx.x == 0) {
         int m = k;
         while (m > 1 && keys[m - 1] == ~0ull) m--;
-        float target = uniforms[(int64_t) s * uni_stride + call[0]];
+        float target = uniforms[call[0]];
         call[0] += 1;
         float cum = 0.0f;
         int chosen;
-        if (total_base) {
-            const float total = total_base[r];
+        if (total_in) {
+            const float total = total_in[0];
             float mass = 0.0f;
             int trim = -1;
             for (int j = 0; j < m; j++) {
@@ -1160,8 +1130,111 @@ static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const uns
             last_id[0] = chosen;
             rep_count[0] = cnt + 1;
         }
-        token[r] = (uint32_t) chosen;
+        token[0] = (uint32_t) chosen;
     }
+}
+
+static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const uint32_t *row_slot, int slot0,
+                                                                 const uint32_t *slot_state) {
+    if (rows_finished(slot_state, rows_slot(row_slot, slot0, blockIdx.y))) return;
+    argmax_parts_row(logits, V, ld, pv, pi);
+}
+static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const uint32_t *row_slot, int slot0,
+                                                               const uint32_t *slot_state) {
+    const int r = blockIdx.x;
+    if (rows_finished(slot_state, rows_slot(row_slot, slot0, r))) return;
+    argmax_fold_row(pv, pi, token, r);
+}
+
+// grid (TOPK_PARTS, rows)
+static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float *logits_base, int V, int ld, int k, const double *pen_table, int pen_len, const uint32_t *smp,
+                                                              unsigned long long *cand_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    topk_parts_row(logits_base + (int64_t) r * ld, V, k, pen_table, pen_len, (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1,
+                   cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK);
+}
+
+// grid (1, rows)
+static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base, float temperature,
+                                                                  const double *pen_table, int pen_len, const uint32_t *smp, float *total_base, const uint32_t *row_slot,
+                                                                  int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    softmax_total_row(logits_base + (int64_t) r * ld, V, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, temperature, pen_table, pen_len,
+                      (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, total_base + r);
+}
+
+// grid (1, rows); the row's draw is uniforms[s * uni_stride + call counter of s], which advances
+static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const unsigned long long *cand_base, int k, float temperature, const float *uniforms, int64_t uni_stride,
+                                                                const double *pen_table, uint32_t *smp, uint32_t *token, float top_p, const float *total_base,
+                                                                const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s)) return;
+    topk_sample_row(cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, k, temperature, uniforms + (int64_t) s * uni_stride, pen_table, (int32_t *) (smp + (size_t) 3 * s),
+                    smp + (size_t) 3 * s + 1, smp + (size_t) 3 * s + 2, token + r, top_p, total_base ? total_base + r : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The mixed session (tts_hip_orpheus_stream_begin_mixed): every slot carries its own sampler.  samp [n_slots] holds {mode, top_k, temperature, top_p}
+// (mode LLAMA_SLOT_MAX: sampler::max, LLAMA_SLOT_SAMPLE: sampler::sample) and pen_base [n_slots][pen_len] one stage_penalty table per slot; a stretch
+// whose first entry is 0 stands for penalty 1, i.e. the NULL table of the kernels above (pow(penalty, 0) is 1 in every built stretch).  Each kernel
+// is the uniform one with k, temperature, top_p and the table read from the row's slot: the same body, so the same ids.  A row of the other mode
+// returns at once like a finished one: the arg-max pair selects for the greedy rows, the top-k kernels for the sampled rows, the total only for
+// sampled rows with top_p < 1, all into the same token[rows].
+// ------------------------------------------------------------------------------------------------
+#define LLAMA_SLOT_MAX 0u
+#define LLAMA_SLOT_SAMPLE 1u
+struct llama_slot_sampler { uint32_t mode, top_k; float temperature, top_p; };
+__device__ __forceinline__ const double *slot_penalty(const double *pen_base, int pen_len, uint32_t s) {
+    const double *t = pen_base + (size_t) s * pen_len;
+    return t[0] != 0.0 ? t : nullptr;
+}
+
+static __global__ __launch_bounds__(256) void argmax_slots_parts_mixed_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const llama_slot_sampler *samp,
+                                                                       const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const uint32_t s = rows_slot(row_slot, slot0, blockIdx.y);
+    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_MAX) return;
+    argmax_parts_row(logits, V, ld, pv, pi);
+}
+static __global__ __launch_bounds__(64) void argmax_slots_fold_mixed_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const llama_slot_sampler *samp,
+                                                                     const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.x;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_MAX) return;
+    argmax_fold_row(pv, pi, token, r);
+}
+static __global__ __launch_bounds__(512) void topk_parts_rows_mixed_kernel(const float *logits_base, int V, int ld, const llama_slot_sampler *samp, const double *pen_base,
+                                                                    int pen_len, const uint32_t *smp, unsigned long long *cand_base, const uint32_t *row_slot, int slot0,
+                                                                    const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE) return;
+    topk_parts_row(logits_base + (int64_t) r * ld, V, (int) samp[s].top_k, slot_penalty(pen_base, pen_len, s), pen_len, (const int32_t *) (smp + (size_t) 3 * s),
+                   smp + (size_t) 3 * s + 1, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK);
+}
+static __global__ __launch_bounds__(1024) void softmax_total_rows_mixed_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base,
+                                                                        const llama_slot_sampler *samp, const double *pen_base, int pen_len, const uint32_t *smp,
+                                                                        float *total_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE || !(samp[s].top_p < 1.0f)) return;
+    softmax_total_row(logits_base + (int64_t) r * ld, V, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, samp[s].temperature, slot_penalty(pen_base, pen_len, s), pen_len,
+                      (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, total_base + r);
+}
+static __global__ __launch_bounds__(1024) void topk_sample_rows_mixed_kernel(const unsigned long long *cand_base, const llama_slot_sampler *samp, const float *uniforms,
+                                                                      int64_t uni_stride, const double *pen_base, int pen_len, uint32_t *smp, uint32_t *token,
+                                                                      const float *total_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    const uint32_t s = rows_slot(row_slot, slot0, r);
+    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE) return;
+    const float top_p = samp[s].top_p;
+    topk_sample_row(cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, (int) samp[s].top_k, samp[s].temperature, uniforms + (int64_t) s * uni_stride,
+                    slot_penalty(pen_base, pen_len, s), (int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, smp + (size_t) 3 * s + 2, token + r, top_p,
+                    top_p < 1.0f ? total_base + r : nullptr);
 }
 
 // The row advance that makes the session's loop device-driven: one thread per row, after the selection.  A live row's selected id is appended to its

@@ -252,6 +252,7 @@ struct tts_hip_ctx {
     // ---- Orpheus continuous session (tts_hip_orpheus_stream_*): per-slot state on the device, the host keeps the copy of the last look-in ----
     struct LlamaStream {
         bool active = false, sampled = false;
+        bool mixed = false;                         // begin_mixed: every slot carries its own sampler (samp / pen below), sp is unused
         uint32_t n_slots = 0, max_new = 0, stop_id = 0;
         tts_hip_sampling sp{};
         enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished at admission, the next stream_run reports it
@@ -265,6 +266,10 @@ struct tts_hip_ctx {
         unsigned long long *cand = nullptr;         // device [n_slots][TOPK_PARTS][TOPK_MAXK]
         float *total = nullptr;                     // device [n_slots]
         uint32_t *h_state = nullptr;                // pinned [n_slots][LLAMA_SLOT_STATE]
+        // mixed session: per slot, what its utterance samples with
+        std::vector<uint8_t> slot_sampled, slot_nucleus;   // sampler::sample / ... with top_p < 1
+        void *samp = nullptr;                       // device [n_slots] llama_slot_sampler
+        double *pen = nullptr;                      // device [n_slots][max_new] pow(penalty, count); first entry 0: penalty 1
     } ls;
     uint32_t *h_hist = nullptr;   // pinned: the ids of the steps of one gen_launch
     size_t h_hist_cap = 0;

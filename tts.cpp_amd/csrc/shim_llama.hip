@@ -806,6 +806,41 @@ static int llama_select_slots(tts_hip_ctx *c, const tts_hip_sampling *sp, int ro
     return 0;
 }
 
+// the same for slots that carry their own sampler (llama_slot_sampler samp[], tables pen[][pen_len]): the arg-max pair when a row is greedy, the top-k
+// kernels when one is sampled, the total when a sampled one has top_p < 1 — the caller knows which of its rows are
+static int llama_select_slots_mixed(tts_hip_ctx *c, bool any_max, bool any_sample, bool any_nucleus, int rows, const float *logits, const uint32_t *row_slot, int slot0,
+                                    const uint32_t *slot_state, const llama_slot_sampler *samp, const double *pen, int pen_len, uint32_t *smp, const float *uni,
+                                    int64_t uni_stride, unsigned long long *cand, float *total) {
+    if (any_max) {
+        hipLaunchKernelGGL(argmax_slots_parts_mixed_kernel, dim3(ARGMAX_PARTS, rows), dim3(256), 0, c->stream, logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi, samp, row_slot, slot0,
+                           slot_state);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(argmax_slots_fold_mixed_kernel, dim3(rows), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok, samp, row_slot, slot0,
+                           slot_state);
+        HIPCHK(hipGetLastError());
+    }
+    if (!any_sample) return 0;
+    hipLaunchKernelGGL(topk_parts_rows_mixed_kernel, dim3(TOPK_PARTS, rows), dim3(512), 0, c->stream, logits, c->l_V, c->l_Vpad, samp, pen, pen_len, (const uint32_t *) smp, cand, row_slot,
+                       slot0, slot_state);
+    HIPCHK(hipGetLastError());
+    if (any_nucleus) {
+        hipLaunchKernelGGL(softmax_total_rows_mixed_kernel, dim3(1, rows), dim3(1024), 0, c->stream, logits, c->l_V, c->l_Vpad, (const unsigned long long *) cand, samp, pen, pen_len,
+                           (const uint32_t *) smp, total, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(topk_sample_rows_mixed_kernel, dim3(1, rows), dim3(1024), 0, c->stream, (const unsigned long long *) cand, samp, uni, uni_stride, pen, pen_len, smp, c->l_btok,
+                       (const float *) total, row_slot, slot0, slot_state);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// one slot's record and table, as the mixed kernels read them: sp NULL is sampler::max; the table is stage_penalty's for sp's penalty, len entries
+static void llama_slot_sampler_host(const tts_hip_sampling *sp, int len, llama_slot_sampler *rec, double *table) {
+    *rec = sp ? llama_slot_sampler{LLAMA_SLOT_SAMPLE, sp->top_k, sp->temperature, sp->top_p} : llama_slot_sampler{LLAMA_SLOT_MAX, 0u, 1.0f, 1.0f};
+    const bool rep = sp && sp->repetition_penalty != 1.0f;
+    for (int i = 0; i < len; i++) table[i] = rep ? pow((double) sp->repetition_penalty, (double) i) : 0.0;
+}
+
 template <typename T>
 static int dmalloc(T **p, size_t n) {
     HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
@@ -815,13 +850,13 @@ static int dmalloc(T **p, size_t n) {
 
 static void llama_stream_free(tts_hip_ctx *c) {
     auto &g = c->ls;
-    free_dev(g.state); free_dev(g.tokens); free_dev(g.smp); free_dev(g.uni); free_dev(g.cand); free_dev(g.total);
+    free_dev(g.state); free_dev(g.tokens); free_dev(g.smp); free_dev(g.uni); free_dev(g.cand); free_dev(g.total); free_dev(g.samp); free_dev(g.pen);
     if (g.h_state) (void) hipHostFree(g.h_state);
     g = tts_hip_ctx::LlamaStream{};
 }
 
-extern "C" int tts_hip_orpheus_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp) {
-    const char *what = "tts_hip_orpheus_stream_begin";
+// mixed: every slot carries its own sampler (sp is NULL), so the sampler's buffers exist for every slot
+static int llama_stream_begin(tts_hip_ctx *c, const char *what, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp, bool mixed) {
     CHK(llama_stream_ready(c, what, false));
     CHK(llama_gen_idle(c, what));   // an open session or the window between a gen_launch and its gen_wait
     if (c->lg.active && !llama_gen_all_done(c)) return set_err("%s: a tts_hip_orpheus_gen_* generation is under way", what);
@@ -830,33 +865,55 @@ extern "C" int tts_hip_orpheus_stream_begin(tts_hip_ctx *c, uint32_t n_slots, ui
     HIPCHK(hipSetDevice(c->device));
     c->lg.active = false;
     auto &g = c->ls;
-    g.sampled = sp != nullptr; g.n_slots = n_slots; g.max_new = max_new; g.stop_id = stop_id;
+    g.sampled = sp != nullptr; g.mixed = mixed; g.n_slots = n_slots; g.max_new = max_new; g.stop_id = stop_id;
     if (sp) g.sp = *sp;
     const size_t S = n_slots, M = std::max<uint32_t>(max_new, 1);
+    const bool smp = sp || mixed;
     int rc = dmalloc(&g.state, S * LLAMA_SLOT_STATE);
     if (rc == 0) rc = dmalloc(&g.tokens, S * M);
-    if (rc == 0 && sp) rc = dmalloc(&g.smp, S * 3);
-    if (rc == 0 && sp) rc = dmalloc(&g.uni, S * M);
-    if (rc == 0 && sp) rc = dmalloc(&g.total, S);
-    if (rc == 0 && sp && hipMalloc((void **) &g.cand, S * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+    if (rc == 0 && smp) rc = dmalloc(&g.smp, S * 3);
+    if (rc == 0 && smp) rc = dmalloc(&g.uni, S * M);
+    if (rc == 0 && smp) rc = dmalloc(&g.total, S);
+    if (rc == 0 && smp && hipMalloc((void **) &g.cand, S * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+    if (rc == 0 && mixed) rc = dmalloc((llama_slot_sampler **) &g.samp, S);   // zeroed: sampler::max, no penalty
+    if (rc == 0 && mixed) rc = dmalloc(&g.pen, S * M);
     if (rc == 0 && hipHostMalloc((void **) &g.h_state, S * LLAMA_SLOT_STATE * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
     if (rc == 0 && sp) rc = stage_penalty(c, sp->repetition_penalty, (int) max_new);   // once: every utterance of the session shares the table
     if (rc != 0) { llama_stream_free(c); return rc; }
     g.slot.assign(S, tts_hip_ctx::LlamaStream::FREE);
     g.count.assign(S, 0); g.cur.assign(S, 0); g.pos.assign(S, 0);
+    g.slot_sampled.assign(S, 0); g.slot_nucleus.assign(S, 0);
     g.rows.clear();
     g.active = true;
     return 0;
 }
 
-extern "C" int tts_hip_orpheus_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt, const float *uniforms) {
-    const char *what = "tts_hip_orpheus_stream_admit";
+extern "C" int tts_hip_orpheus_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp) {
+    return llama_stream_begin(c, "tts_hip_orpheus_stream_begin", n_slots, max_new, stop_id, sp, false);
+}
+extern "C" int tts_hip_orpheus_stream_begin_mixed(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_new, uint32_t stop_id) {
+    return llama_stream_begin(c, "tts_hip_orpheus_stream_begin_mixed", n_slots, max_new, stop_id, nullptr, true);
+}
+
+// sampling (mixed session only): utterance i's sampler, NULL = sampler::max
+static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt,
+                              const tts_hip_sampling *const *sampling, const float *uniforms) {
     typedef tts_hip_ctx::LlamaStream LS;
     CHK(llama_stream_ready(c, what));
     auto &g = c->ls;
+    if (mixed != g.mixed)
+        return set_err(g.mixed ? "%s: the session carries a sampler per slot (tts_hip_orpheus_stream_admit_mixed)" : "%s: the session has one sampler (tts_hip_orpheus_stream_admit)", what);
     if (n == 0) return 0;
     if (!slots || !prompts || !n_prompt) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_new]", what);
+    if (mixed) {
+        if (!sampling) return set_err("%s: null argument", what);
+        for (uint32_t i = 0; i < n; i++) {
+            if (!sampling[i]) continue;
+            CHK(check_llama_sampling(c, sampling[i], what));
+            if (!uniforms) return set_err("%s: a sampled utterance needs the uniforms [n][max_new]", what);
+        }
+    }
     size_t off = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
@@ -877,16 +934,30 @@ extern "C" int tts_hip_orpheus_stream_admit(tts_hip_ctx *c, uint32_t n, const ui
         // count 0, not finished, no id yet, position of the prompt's last row; sampler::reset and the utterance's own draws
         const uint32_t init[LLAMA_SLOT_STATE] = {0u, 0u, 0u, n_prompt[i] - 1};
         HIPCHK(hipMemcpyAsync(g.state + (size_t) s * LLAMA_SLOT_STATE, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-        if (g.sampled) {
-            const uint32_t reset[3] = {0xFFFFFFFFu, 0u, 0u};
+        const tts_hip_sampling *sp = mixed ? sampling[i] : (g.sampled ? &g.sp : nullptr);
+        const uint32_t reset[3] = {0xFFFFFFFFu, 0u, 0u};
+        if (sp) {
             HIPCHK(hipMemcpyAsync(g.smp + (size_t) s * 3, reset, sizeof(reset), hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(g.uni + (size_t) s * g.max_new, uniforms + (size_t) i * g.max_new, (size_t) g.max_new * 4, hipMemcpyHostToDevice, c->stream));
         }
-        HIPCHK(hipStreamSynchronize(c->stream));   // init / reset are locals
+        llama_slot_sampler rec;
+        std::vector<double> table;
+        if (mixed) {   // the slot's own sampler: nothing of its predecessor's stays
+            table.resize(g.max_new);
+            llama_slot_sampler_host(sp, (int) g.max_new, &rec, table.data());
+            HIPCHK(hipMemcpyAsync((llama_slot_sampler *) g.samp + s, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(g.pen + (size_t) s * g.max_new, table.data(), table.size() * 8, hipMemcpyHostToDevice, c->stream));
+            g.slot_sampled[s] = sp != nullptr; g.slot_nucleus[s] = sp && sp->top_p < 1.0f;
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));   // init / reset / rec / table are locals
         // the prompt into the slot's cache; its last row's logits land in l_logits row s; then the first selection, as gen_begin makes it
         CHK(llama_prefill_slot(c, what, s, prompts + off, n_prompt[i]));
         off += n_prompt[i];
-        CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+        if (mixed)
+            CHK(llama_select_slots_mixed(c, !sp, sp != nullptr, g.slot_nucleus[s] != 0, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state,
+                                         (const llama_slot_sampler *) g.samp, g.pen, (int) g.max_new, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+        else
+            CHK(llama_select_slots(c, sp, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
         hipLaunchKernelGGL(llama_advance_rows_kernel, dim3(1), dim3(64), 0, c->stream, 1, (const uint32_t *) nullptr, (int) s, (const uint32_t *) c->l_btok, g.state, g.tokens, g.max_new,
                            g.stop_id, c->lm.n_ctx, (uint32_t *) nullptr, (uint32_t *) nullptr);
         HIPCHK(hipGetLastError());
@@ -898,6 +969,14 @@ extern "C" int tts_hip_orpheus_stream_admit(tts_hip_ctx *c, uint32_t n, const ui
     g.rows.clear();
     for (uint32_t s = 0; s < g.n_slots; s++) if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
     return 0;
+}
+
+extern "C" int tts_hip_orpheus_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt, const float *uniforms) {
+    return llama_stream_admit(c, "tts_hip_orpheus_stream_admit", false, n, slots, prompts, n_prompt, nullptr, uniforms);
+}
+extern "C" int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt,
+                                                  const tts_hip_sampling *const *sampling, const float *uniforms) {
+    return llama_stream_admit(c, "tts_hip_orpheus_stream_admit_mixed", true, n, slots, prompts, n_prompt, sampling, uniforms);
 }
 
 extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
@@ -920,11 +999,17 @@ extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint
         for (uint32_t r = 0; r < n; r++) { ids[r] = g.cur[g.rows[r]]; ps[r] = g.pos[g.rows[r]]; }
         uint32_t max_pos = 0;
         CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
+        bool any_max = false, any_sample = false, any_nucleus = false;   // mixed: which selection kernels this run's rows need
+        for (uint32_t s : g.rows) { any_max |= !g.slot_sampled[s]; any_sample |= g.slot_sampled[s] != 0; any_nucleus |= g.slot_nucleus[s] != 0; }
         for (uint32_t i = 0; i < n_steps; i++) {
             // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
             const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
             CHK(llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1));
-            CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, (int) n, c->l_logits, c->l_seq, 0, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+            if (g.mixed)
+                CHK(llama_select_slots_mixed(c, any_max, any_sample, any_nucleus, (int) n, c->l_logits, c->l_seq, 0, g.state, (const llama_slot_sampler *) g.samp, g.pen,
+                                             (int) g.max_new, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+            else
+                CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, (int) n, c->l_logits, c->l_seq, 0, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
             hipLaunchKernelGGL(llama_advance_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (int) n, (const uint32_t *) c->l_seq, 0, (const uint32_t *) c->l_btok, g.state,
                                g.tokens, g.max_new, g.stop_id, c->lm.n_ctx, c->l_ids, c->l_pos);
             HIPCHK(hipGetLastError());
@@ -1012,6 +1097,63 @@ extern "C" int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *c, uint32_t n_row
     ok = hipStreamSynchronize(c->stream) == hipSuccess && ok;
     if (!ok) return drop(set_err("%s: copy failed", what));
     if (rep) for (uint32_t r = 0; r < n_rows; r++) { last_id[r] = (int32_t) back[3 * r]; rep_count[r] = back[3 * r + 1]; }
+    return drop(0);
+}
+
+extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling, const float *uniforms,
+                                                        int32_t *last_id, uint32_t *rep_count, uint32_t *tokens_out) {
+    const char *what = "tts_hip_orpheus_sample_logits_rows_mixed";
+    CHK(llama_stream_ready(c, what, false));
+    if (!logits || !tokens_out || !sampling) return set_err("%s: null argument", what);
+    CHK(llama_gen_idle(c, what));
+    if (n_rows == 0 || n_rows > c->lm.max_seqs) return set_err("%s: %u rows outside 1..max_seqs = %u", what, n_rows, c->lm.max_seqs);
+    bool any_max = false, any_sample = false, any_nucleus = false;
+    uint32_t mx = 0;
+    auto rep = [&](uint32_t r) { return sampling[r] && sampling[r]->repetition_penalty != 1.0f; };
+    for (uint32_t r = 0; r < n_rows; r++) {
+        const tts_hip_sampling *sp = sampling[r];
+        if (!sp) { any_max = true; continue; }
+        CHK(check_llama_sampling(c, sp, what));
+        if (!uniforms) return set_err("%s: null uniforms", what);
+        if (rep(r) && (!last_id || !rep_count)) return set_err("%s: repetition penalty needs last_id and rep_count", what);
+        any_sample = true; any_nucleus |= sp->top_p < 1.0f;
+        if (rep(r)) mx = std::max(mx, rep_count[r]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const int len = (int) std::min<uint32_t>(mx + 2, 1u << 20) + 1;   // what stage_penalty builds for the one-row call
+    std::vector<llama_slot_sampler> rec(n_rows);
+    std::vector<double> table((size_t) n_rows * len);
+    std::vector<uint32_t> init((size_t) 3 * n_rows);
+    for (uint32_t r = 0; r < n_rows; r++) {
+        llama_slot_sampler_host(sampling[r], len, &rec[r], table.data() + (size_t) r * len);
+        init[3 * r] = rep(r) ? (uint32_t) last_id[r] : 0xFFFFFFFFu; init[3 * r + 1] = rep(r) ? rep_count[r] : 0u; init[3 * r + 2] = 0u;
+    }
+    uint32_t *smp = nullptr;
+    float *uni = nullptr, *total = nullptr;
+    unsigned long long *cand = nullptr;
+    llama_slot_sampler *samp = nullptr;
+    double *pen = nullptr;
+    auto drop = [&](int rc) { free_dev(smp); free_dev(uni); free_dev(total); free_dev(cand); free_dev(samp); free_dev(pen); return rc; };
+    int rc = dmalloc(&smp, (size_t) 3 * n_rows);
+    if (rc == 0) rc = dmalloc(&uni, (size_t) n_rows);
+    if (rc == 0) rc = dmalloc(&total, (size_t) n_rows);
+    if (rc == 0) rc = dmalloc(&samp, (size_t) n_rows);
+    if (rc == 0) rc = dmalloc(&pen, table.size());
+    if (rc == 0 && hipMalloc((void **) &cand, (size_t) n_rows * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+    if (rc != 0) return drop(rc);
+    if (hipMemcpy(smp, init.data(), init.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(samp, rec.data(), rec.size() * sizeof(rec[0]), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pen, table.data(), table.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (uniforms && hipMemcpy(uni, uniforms, (size_t) n_rows * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return drop(set_err("%s: copy failed", what));
+    if (hipMemcpy2DAsync(c->l_logits, (size_t) c->l_Vpad * 4, logits, (size_t) c->l_V * 4, (size_t) c->l_V * 4, n_rows, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return drop(set_err("%s: copy failed", what));
+    if (llama_select_slots_mixed(c, any_max, any_sample, any_nucleus, (int) n_rows, c->l_logits, nullptr, 0, nullptr, samp, pen, len, smp, uni, 1, cand, total) != 0) return drop(-1);
+    std::vector<uint32_t> back((size_t) 3 * n_rows);
+    bool ok = hipMemcpyAsync(tokens_out, c->l_btok, (size_t) n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(back.data(), smp, back.size() * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    ok = hipStreamSynchronize(c->stream) == hipSuccess && ok;
+    if (!ok) return drop(set_err("%s: copy failed", what));
+    for (uint32_t r = 0; r < n_rows; r++) if (rep(r)) { last_id[r] = (int32_t) back[3 * r]; rep_count[r] = back[3 * r + 1]; }
     return drop(0);
 }
 

@@ -92,6 +92,7 @@ EXPORTS = [
     "tts_hip_orpheus_gen_begin", "tts_hip_orpheus_gen_launch", "tts_hip_orpheus_gen_wait",
     "tts_hip_orpheus_stream_begin", "tts_hip_orpheus_stream_admit", "tts_hip_orpheus_stream_run", "tts_hip_orpheus_stream_collect", "tts_hip_orpheus_stream_end",
     "tts_hip_orpheus_sample_logits_rows",
+    "tts_hip_orpheus_stream_begin_mixed", "tts_hip_orpheus_stream_admit_mixed", "tts_hip_orpheus_sample_logits_rows_mixed",
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
     "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
@@ -207,6 +208,9 @@ def load_lib():
     L.tts_hip_orpheus_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
     L.tts_hip_orpheus_stream_end.argtypes = [vp]
     L.tts_hip_orpheus_sample_logits_rows.argtypes = [vp, C.c_uint32, f32p, C.POINTER(Sampling), f32p, C.POINTER(C.c_int32), u32p, u32p]
+    L.tts_hip_orpheus_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.tts_hip_orpheus_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
+    L.tts_hip_orpheus_sample_logits_rows_mixed.argtypes = [vp, C.c_uint32, f32p, C.POINTER(C.POINTER(Sampling)), f32p, C.POINTER(C.c_int32), u32p, u32p]
     L.tts_hip_dia_gen_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes), C.POINTER(Sampling), f32p]
     L.tts_hip_dia_gen_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_dia_gen_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p]
@@ -827,7 +831,50 @@ class OrpheusEngine:
                                                             rc.ctypes.data_as(C.POINTER(C.c_uint32)), tok.ctypes.data_as(C.POINTER(C.c_uint32))))
         return tok, li, rc
 
+    @staticmethod
+    def _sampling_rows(settings):
+        """settings: per row None (sampler::max) or a dict of top_k / temperature / repetition_penalty / top_p -> (Sampling *[n], the structs kept alive)"""
+        keep = [None if s is None else Sampling(s.get("top_k", 50), s.get("top_p", 1.0), s.get("temperature", 1.0), s.get("repetition_penalty", 1.0)) for s in settings]
+        arr = (C.POINTER(Sampling) * len(keep))(*[C.POINTER(Sampling)() if k is None else C.pointer(k) for k in keep])
+        return arr, keep
+
+    def sample_logits_rows_mixed(self, logits, settings, uniforms=None, last_id=None, rep_count=None):
+        """tts_hip_orpheus_sample_logits_rows_mixed: the mixed session's selection on logits [n][vocab], row r with settings[r] (None: arg-max)
+        -> (tokens [n], last_id [n], rep_count [n])"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        n = lg.shape[0]
+        assert lg.shape == (n, self.cfg.vocab) and len(settings) == n
+        li = np.ascontiguousarray(np.full(n, -1) if last_id is None else last_id, dtype=np.int32).copy()
+        rc = np.ascontiguousarray(np.zeros(n) if rep_count is None else rep_count, dtype=np.uint32).copy()
+        tok = np.zeros(n, dtype=np.uint32)
+        arr, keep = self._sampling_rows(settings)
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n)
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_orpheus_sample_logits_rows_mixed(self.ctx, n, lg.ctypes.data_as(C.POINTER(C.c_float)), arr, up, li.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                  rc.ctypes.data_as(C.POINTER(C.c_uint32)), tok.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return tok, li, rc
+
     # ---- continuous session (tts_hip_orpheus_stream_*) ----
+    def stream_begin_mixed(self, n_slots, max_new, stop_id):
+        """a session whose slots carry their own sampler (stream_admit_mixed); run / collect / end as for stream_begin"""
+        self._chk(self.L.tts_hip_orpheus_stream_begin_mixed(self.ctx, n_slots, max_new, stop_id))
+        self._stream = (n_slots, max_new)
+
+    def stream_admit_mixed(self, slots, prompts, settings, uniforms=None):
+        """settings: per utterance None (greedy) or a dict of top_k / temperature / repetition_penalty / top_p; uniforms [n][max_new] (a greedy
+        utterance's stretch is ignored; None when every utterance is greedy)"""
+        s, sp = _u32(slots)
+        cat, cp = _u32(np.concatenate([np.asarray(p, dtype=np.uint32) for p in prompts]))
+        lens, lp = _u32(np.array([len(p) for p in prompts], dtype=np.uint32))
+        arr, keep = self._sampling_rows(settings)
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(len(prompts), self._stream[1])
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_orpheus_stream_admit_mixed(self.ctx, len(prompts), sp, cp, lp, arr, up))
+
     def stream_begin(self, n_slots, max_new, stop_id, sampled=False, top_k=50, temperature=1.0, repetition_penalty=1.0, top_p=1.0):
         sp = Sampling(top_k, top_p, temperature, repetition_penalty)
         self._chk(self.L.tts_hip_orpheus_stream_begin(self.ctx, n_slots, max_new, stop_id, C.byref(sp) if sampled else None))

@@ -60,6 +60,9 @@ struct generation_configuration {
     uint64_t seed = 0;
 };
 
+// every field equal: two requests that any session can carry side by side
+bool same_generation_configuration(const generation_configuration & a, const generation_configuration & b);
+
 struct tts_runner {
     float sampling_rate   = 44100.0f;  // common.h:70
     bool  supports_voices = false;
@@ -125,9 +128,21 @@ struct tts_generation_runner : tts_runner {
     virtual void     stream_submit(size_t ticket, const std::string & sentence);
     virtual void     stream_step(std::vector<stream_result> & finished);
     virtual void     stream_end();
+    // per-request configurations: stream_accepts() says whether THIS open session can take a request with `config` although it differs from the one
+    // the session was opened with (orpheus_runner: the voice is a prompt prefix and every cache slot carries its own sampler; the default, and every
+    // other runner so far: no), and the three-argument stream_submit() enters such a request; its default ignores `config` — the caller has
+    // established that it equals the session's.  A request stream_accepts() would refuse makes stream_submit() fail like a bad prompt does
+    // (TTS_ABORT), with the session unchanged.
+    virtual bool     stream_accepts(const generation_configuration & config) const;
+    virtual void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config);
     // any number of sentences through one session (more than batch_capacity() is fine); outputs[i].data valid until the next call on this runner
     void             generate_stream(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs,
                                      const generation_configuration & config);
+    // one configuration per sentence: a session takes every following sentence whose configuration equals its first one's or that it accepts
+    // (stream_accepts), and is drained and reopened at the first one it cannot take — for a runner that accepts nothing, and for one without a
+    // session, consecutive runs of equal configurations.  Same outputs as n generate() calls with configs[i].
+    void             generate_stream(const std::vector<std::string> & sentences, const std::vector<generation_configuration> & configs,
+                                     std::vector<tts_response> & outputs);
     // chunked audio out of a session, asked for between stream_begin and the first stream_submit: from then on stream_step hands every
     // utterance's PCM to on_chunk(ticket, pcm, n) in consecutive pieces of at most chunk_frames codec frames while the rows keep running; an
     // utterance appears in `finished` — with empty audio — once its last piece is out, and stream_live() counts it until then.  on_chunk
@@ -156,6 +171,7 @@ struct tts_generation_runner : tts_runner {
 
   protected:
     std::vector<std::vector<float>> batch_store_;  // audio of the default generate_batch
+    std::vector<std::vector<float>> configs_store_;  // audio of generate_stream with per-sentence configurations
 };
 
 // loaders.h:8-20

@@ -10,11 +10,7 @@
 #include <atomic>
 extern std::atomic<bool> g_tts_throw_on_abort;
 
-bool pool_configs_compatible(const generation_configuration & a, const generation_configuration & b) {
-    return a.use_cross_attn == b.use_cross_attn && a.temperature == b.temperature && a.repetition_penalty == b.repetition_penalty &&
-           a.top_p == b.top_p && a.top_k == b.top_k && a.max_tokens == b.max_tokens && a.voice == b.voice && a.sample == b.sample &&
-           a.espeak_voice_id == b.espeak_voice_id && a.seed == b.seed;
-}
+bool pool_configs_compatible(const generation_configuration & a, const generation_configuration & b) { return same_generation_configuration(a, b); }
 
 struct device_pool::worker_state {
     std::map<std::string, std::unique_ptr<tts_generation_runner>> runners;  // worker::runners (:240)
@@ -267,7 +263,11 @@ void device_pool::worker_main(int w) {
 
 // queued TTS tasks compatible with `like`, up to cap, without waiting.  None while a control task addressed to this worker waits: the session
 // drains first (a CONDITIONAL_PROMPT changes the voice of everything generated after it).
-std::vector<std::shared_ptr<pool_task>> device_pool::poll_compatible(int w, const pool_task & like, size_t cap) {
+// `session`: the runner whose open session asks; it also takes a request of the same model whose configuration it accepts (stream_accepts)
+std::vector<std::shared_ptr<pool_task>> device_pool::poll_compatible(int w, const pool_task & like, size_t cap, const tts_generation_runner & session) {
+    auto fits = [&](const pool_task & t) {
+        return t.task == POOL_TTS && t.model == like.model && (pool_configs_compatible(t.gen_config, like.gen_config) || session.stream_accepts(t.gen_config));
+    };
     std::vector<std::shared_ptr<pool_task>> got;
     std::lock_guard<std::mutex> lock(q_mutex_);
     if (!running_ || !per_worker_[(size_t) w].empty()) return got;
@@ -277,12 +277,12 @@ std::vector<std::shared_ptr<pool_task>> device_pool::poll_compatible(int w, cons
     // idle: an idle worker takes the stale request through next_batch() itself, and with several workers on mixed models every session draining
     // at once for one request cost throughput.
     for (const auto & t : queue_) {
-        if (t->task == POOL_TTS && t->model == like.model && pool_configs_compatible(t->gen_config, like.gen_config)) continue;
+        if (fits(*t)) continue;
         if (idle_workers_ == 0 && t->waited_s() * 1e3 > opts_.continuous_yield_ms) return got;
         break;   // the oldest incompatible request is still young: requests behind it are younger
     }
     for (auto it = queue_.begin(); it != queue_.end() && got.size() < cap;) {
-        if ((*it)->task == POOL_TTS && (*it)->model == like.model && pool_configs_compatible((*it)->gen_config, like.gen_config)) {
+        if (fits(**it)) {
             got.push_back(*it);
             it = queue_.erase(it);
         } else ++it;
@@ -337,7 +337,7 @@ void device_pool::process_stream(int w, std::vector<std::shared_ptr<pool_task>> 
                 if (t->timed_out(opts_.task_timeout_s)) { t->message = "timed out in the queue"; expired++; done.push_back(t); continue; }
                 if (runner.stream_free() == 0) { overflow.push_back(t); continue; }
                 try {
-                    runner.stream_submit(ticket, t->prompt);   // host work only (tokenising, taking a row): a request it rejects fails alone
+                    runner.stream_submit(ticket, t->prompt, t->gen_config);   // host work only (tokenising, taking a row): a request it rejects fails alone
                 } catch (const std::exception & e) {
                     t->success = false; t->message = e.what(); served++; done.push_back(t);
                     continue;
@@ -374,7 +374,7 @@ void device_pool::process_stream(int w, std::vector<std::shared_ptr<pool_task>> 
                 admit(again, true);
             }
             if (runner.stream_free() > 0) {
-                auto more = poll_compatible(w, like, runner.stream_free());
+                auto more = poll_compatible(w, like, runner.stream_free(), runner);
                 if (!more.empty()) admit(more, true);
             }
         }

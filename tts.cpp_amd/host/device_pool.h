@@ -103,7 +103,7 @@ class device_pool {
     void worker_main(int w);
     void process(int w, std::vector<std::shared_ptr<pool_task>> & batch, worker_state & ws);
     void process_stream(int w, std::vector<std::shared_ptr<pool_task>> & first, worker_state & ws);
-    std::vector<std::shared_ptr<pool_task>> poll_compatible(int w, const pool_task & like, size_t cap);
+    std::vector<std::shared_ptr<pool_task>> poll_compatible(int w, const pool_task & like, size_t cap, const tts_generation_runner & session);
     std::vector<std::shared_ptr<pool_task>> next_batch(int w, int cap);
     void control(int w, pool_task & t, worker_state & ws);
     struct fanout { std::shared_ptr<pool_task> parent; int remaining = 0; bool ok = true; std::string message; };

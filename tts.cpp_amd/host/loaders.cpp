@@ -82,6 +82,8 @@ void tts_generation_runner::generate_batch_chunked(const std::vector<std::string
 // continuous batching, the defaults: a runner without a session
 void tts_generation_runner::stream_begin(const generation_configuration &) { TTS_ABORT("stream_begin: this runner has no continuous batching (stream_capacity() == 0)\n"); }
 void tts_generation_runner::stream_submit(size_t, const std::string &) { TTS_ABORT("stream_submit: this runner has no continuous batching\n"); }
+void tts_generation_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration &) { stream_submit(ticket, sentence); }
+bool tts_generation_runner::stream_accepts(const generation_configuration &) const { return false; }
 void tts_generation_runner::stream_step(std::vector<stream_result> &) { TTS_ABORT("stream_step: this runner has no continuous batching\n"); }
 void tts_generation_runner::stream_end() {}
 bool tts_generation_runner::stream_chunks(uint32_t, std::function<bool(size_t, const float *, size_t)>) { return false; }
@@ -120,6 +122,52 @@ void tts_generation_runner::generate_stream(const std::vector<std::string> & sen
         }
     }
     stream_end();
+}
+
+bool same_generation_configuration(const generation_configuration & a, const generation_configuration & b) {
+    return a.use_cross_attn == b.use_cross_attn && a.temperature == b.temperature && a.repetition_penalty == b.repetition_penalty &&
+           a.top_p == b.top_p && a.top_k == b.top_k && a.max_tokens == b.max_tokens && a.voice == b.voice && a.sample == b.sample &&
+           a.espeak_voice_id == b.espeak_voice_id && a.seed == b.seed;
+}
+
+void tts_generation_runner::generate_stream(const std::vector<std::string> & sentences, const std::vector<generation_configuration> & configs,
+                                            std::vector<tts_response> & outputs) {
+    if (configs.size() != sentences.size()) TTS_ABORT("generate_stream: %zu configurations for %zu sentences\n", configs.size(), sentences.size());
+    const size_t n = sentences.size();
+    configs_store_.assign(n, {});
+    auto keep = [&](size_t i, const tts_response & r) { configs_store_[i].assign(r.data, r.data + r.n_outputs); };
+    size_t next = 0;
+    while (next < n) {
+        const size_t first = next;
+        if (stream_capacity() == 0) {   // no session: the run of equal configurations through the one-configuration loop
+            while (next < n && same_generation_configuration(configs[next], configs[first])) next++;
+            std::vector<std::string> part(sentences.begin() + first, sentences.begin() + next);
+            std::vector<tts_response> out;
+            generate_stream(part, out, configs[first]);
+            for (size_t i = 0; i < part.size(); i++) keep(first + i, out[i]);
+            continue;
+        }
+        stream_begin(configs[first]);
+        bool more = true;   // the next sentence may still enter this session
+        std::vector<stream_result> fin;
+        try {
+            while (true) {
+                while (more && next < n && stream_free() > 0) {
+                    more = same_generation_configuration(configs[next], configs[first]) || stream_accepts(configs[next]);
+                    if (more) { stream_submit(next, sentences[next], configs[next]); next++; }
+                }
+                if (stream_live() == 0) break;
+                stream_step(fin);
+                for (auto & f : fin) keep(f.ticket, f.audio);
+            }
+        } catch (...) {   // a request the session refuses fails the call (where aborts throw), not the runner: the session does not stay open
+            stream_end();
+            throw;
+        }
+        stream_end();
+    }
+    outputs.assign(n, tts_response{});
+    for (size_t i = 0; i < n; i++) { outputs[i].data = configs_store_[i].empty() ? nullptr : configs_store_[i].data(); outputs[i].n_outputs = configs_store_[i].size(); }
 }
 
 // generate_stream's loop with the audio handed out in chunks: by the session itself where it chunks (stream_chunks), else every finished

@@ -492,8 +492,7 @@ void orpheus_runner::stream_begin(const generation_configuration & config) {
     }
     const uint32_t slots = stream_capacity();
     st_cfg = config;
-    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-    hip_check(tts_hip_orpheus_stream_begin(lm, slots, hp.max_generation_size, hp.stopping_token_id, config.sample ? &sp : nullptr), "tts_hip_orpheus_stream_begin");
+    hip_check(tts_hip_orpheus_stream_begin_mixed(lm, slots, hp.max_generation_size, hp.stopping_token_id), "tts_hip_orpheus_stream_begin_mixed");
     st_free.clear();
     for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
     st_ticket.assign(slots, 0);
@@ -502,19 +501,31 @@ void orpheus_runner::stream_begin(const generation_configuration & config) {
     st_on = true;
 }
 
-void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence) {
+bool orpheus_runner::stream_accepts(const generation_configuration & config) const {
+    if (!st_on) return false;
+    if (!config.voice.empty() && std::find(orpheus_voices.begin(), orpheus_voices.end(), config.voice) == orpheus_voices.end()) return false;
+    return !config.sample || device_sampler(config);
+}
+
+void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
+
+void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
     if (st_free.empty()) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
-    const std::vector<uint32_t> prompt = checked_prompt(sentence, st_cfg);
+    if (config.sample && !device_sampler(config))
+        TTS_ABORT("stream_submit: the device sampler takes top_k in 1..64 and top_p > 0 (got top_k %d, top_p %g); a session cannot sample on the host\n", config.top_k, config.top_p);
+    const std::vector<uint32_t> prompt = checked_prompt(sentence, config);
     const uint32_t M = hp.max_generation_size, n_prompt = (uint32_t) prompt.size();
     std::vector<float> uni;
-    if (st_cfg.sample) {   // as batch_inputs: the sampler as a generate() call of this utterance's own starts it, one draw per sampler call
+    if (config.sample) {   // as batch_inputs: the sampler as a generate() call of this utterance's own starts it, one draw per sampler call
         uni.resize(M);
-        sampler_setup(st_cfg);
+        sampler_setup(config);
         for (auto & v : uni) smp.draw_uniforms(&v);
     }
     const uint32_t slot = st_free.back();
-    hip_check(tts_hip_orpheus_stream_admit(lm, 1, &slot, prompt.data(), &n_prompt, st_cfg.sample ? uni.data() : nullptr), "tts_hip_orpheus_stream_admit");
+    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
+    const tts_hip_sampling * spp = config.sample ? &sp : nullptr;
+    hip_check(tts_hip_orpheus_stream_admit_mixed(lm, 1, &slot, prompt.data(), &n_prompt, &spp, config.sample ? uni.data() : nullptr), "tts_hip_orpheus_stream_admit_mixed");
     st_free.pop_back();
     st_ticket[slot] = ticket;
     st_live++;

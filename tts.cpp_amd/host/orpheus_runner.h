@@ -67,7 +67,12 @@ struct orpheus_runner final : tts_generation_runner {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return (uint32_t) st_free.size(); }
     uint32_t stream_live() const override { return st_live; }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;
+    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
+    // The session is a mixed one (tts_hip_orpheus_stream_begin_mixed): the voice is a prompt prefix and every slot carries its own sampler, so a
+    // request may differ from the session's configuration in voice, seed, sample, top_k, temperature, top_p and repetition penalty.  It is accepted
+    // when its voice is valid and it is greedy or within the device sampler's limits; its sampler is seeded as a generate() call of its own seeds it.
+    bool     stream_accepts(const generation_configuration & config) const override;
+    void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
     std::vector<std::string_view> list_voices() override;

@@ -98,6 +98,24 @@ int tts_c_generate_stream(tts_c_runner * r, const char * const * texts, int n, c
     }
 }
 
+int tts_c_generate_stream_configs(tts_c_runner * r, const char * const * texts, const tts_c_config * cfgs, int n, const float ** data, size_t * n_outputs) {
+    g_tts_throw_on_abort = true;
+    try {
+        if (!r || (n > 0 && (!texts || !cfgs))) throw std::runtime_error("tts_c_generate_stream_configs: null argument");
+        auto * p = (tts_generation_runner *) r;
+        std::vector<std::string> s(texts, texts + n);
+        std::vector<generation_configuration> c;
+        for (int i = 0; i < n; i++) c.push_back(to_cfg(cfgs + i));
+        std::vector<tts_response> out;
+        p->generate_stream(s, c, out);
+        for (int i = 0; i < n; i++) { data[i] = out[(size_t) i].data; n_outputs[i] = out[(size_t) i].n_outputs; }
+        return 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
 int tts_c_generate_chunked(tts_c_runner * r, const char * text, const tts_c_config * cfg, uint32_t chunk_frames, tts_c_chunk_fn fn, void * user) {
     g_tts_throw_on_abort = true;
     try {

@@ -32,7 +32,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
-           "tts_c_generate_stream_chunked"]
+           "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -57,6 +57,7 @@ def load_lib():
         L.tts_c_generate_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Config), C.POINTER(C.POINTER(C.c_float)),
                                            C.POINTER(C.c_size_t)]
         L.tts_c_generate_stream.argtypes = L.tts_c_generate_batch.argtypes
+        L.tts_c_generate_stream_configs.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(Config), C.c_int, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]
         L.tts_c_sampling_rate.restype = C.c_float
         L.tts_c_sampling_rate.argtypes = [C.c_void_p]
         L.tts_c_arch.restype = C.c_char_p
@@ -182,14 +183,22 @@ class Runner:
             raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
         return [int(ns[i]) for i in range(n)]
 
-    def generate_stream(self, texts, sizes_only=False, **cfg):
-        """tts_c_generate_stream: any number of utterances through one continuous-batching session (rows freed by finished utterances are refilled)"""
-        c = make_config(**cfg) if cfg else self.cfg
+    def generate_stream(self, texts, sizes_only=False, configs=None, **cfg):
+        """tts_c_generate_stream: any number of utterances through one continuous-batching session (rows freed by finished utterances are refilled).
+        configs: one dict of configuration fields per text (tts_c_generate_stream_configs) instead of one configuration for all"""
         n = len(texts)
         arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
         data = (C.POINTER(C.c_float) * n)()
         ns = (C.c_size_t * n)()
-        if self.L.tts_c_generate_stream(self.h, arr, n, C.byref(c), data, ns) != 0:
+        if configs is not None:
+            if cfg or len(configs) != n:
+                raise RunnerError("generate_stream: configs takes one dict per text and no other configuration fields")
+            each = [make_config(**k) for k in configs]   # kept alive: they own the voice strings
+            rc = self.L.tts_c_generate_stream_configs(self.h, arr, (Config * n)(*each), n, data, ns)
+        else:
+            c = make_config(**cfg) if cfg else self.cfg
+            rc = self.L.tts_c_generate_stream(self.h, arr, n, C.byref(c), data, ns)
+        if rc != 0:
             raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
         if sizes_only:
             return [int(ns[i]) for i in range(n)]
