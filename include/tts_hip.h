@@ -580,7 +580,16 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
  * [C][tokens * rate] after the stage of the last pass, orc_snac_decode's numbering: 0 = the summed codebook levels, 1 = after
  * the input depthwise conv and the `up` conv, 2 + i = the end of block i, 2 + n_blocks = the PCM before the crop; requires
  * tts_hip_set_debug(ctx,1) before the decode); Orpheus contexts: "l_logits" (the logits row the last
- * step left), "l_k:<layer>" / "l_v:<layer>" (cache slot 0 of a layer, [n_ctx][kv width]).
+ * step left), "l_k:<layer>[:<slot>]" / "l_v:<layer>[:<slot>]" (a cache slot of a layer, [n_ctx][kv width]; slot 0 by default), and of the
+ * last layer of the last forward — these buffers outlive it, a captured step included — "l_q" (the rotated queries the attention
+ * kernel read) and "l_att" (the rows it left), both [rows][heads * head_dim] with rows = max_floats / (heads * head_dim), "l_pos" (the
+ * rows' positions as floats; a captured step's selection has already advanced row 0 by one).
+ * Dia contexts: with tts_hip_set_debug(ctx,1) an eager tts_hip_dia_step_batch keeps, per layer and per kind, what its attention launch
+ * consumed and produced: "di_attn:<layer>:<self|cross>:q" (self: the rotated rows [R][ld]; cross: the raw query slabs, n_parts of them
+ * part_stride floats apart, which the kernel sums in slab order and rotates at the row's position), ":out" ([R][heads * head_dim]) and
+ * ":meta" (n_parts, part_stride, ld, R, then pos[R], kend[R], row_seq[R]).  "di_k:<layer>:<row slot>" / "di_v:..." are a row slot's
+ * self-attention cache [max_gen][kv width], "di_ck:..." / "di_cv:..." its cross K / V [max_ctx][heads * head_dim].  With debug off every
+ * forward launches exactly what it launches without these items; nothing is kept during a graph capture.
  * Returns number of floats written or <0. */
 int64_t tts_hip_debug_read(tts_hip_ctx *ctx, const char *what, float *out, size_t max_floats);
 int     tts_hip_set_debug(tts_hip_ctx *ctx, int on);

@@ -1,0 +1,95 @@
+"""Plain numpy float64 restatement of what one launch of the Llama / Dia attention kernels computes (csrc/llama_kernels.h): the reference of
+tests/test_gpu_llama_attention.py, pinned to torch by tests/test_attn_reference_cpu.py.  One query row, all heads; K / V are cache rows
+[keys][NKV * HD]."""
+import numpy as np
+
+HD = 128
+
+
+def kv_head(h, NH, NKV):
+    """the k/v head a query head reads (grouped-query attention)"""
+    return h // (NH // NKV)
+
+
+def _softmax_rows(Q, K, V, Ts, scale, NH, NKV, dtype):
+    """rows r with Ts[r] keys each of one cache: per head the probabilities [R][Tmax] (zero beyond a row's keys), the values [Tmax][HD] and the rows [R][HD]"""
+    Q = np.asarray(Q, dtype=dtype).reshape(-1, NH, HD)
+    Ts = np.asarray(Ts, dtype=np.int64).reshape(-1)
+    Tmax = int(Ts.max())
+    K = np.asarray(K[:Tmax], dtype=dtype).reshape(Tmax, NKV, HD)
+    V = np.asarray(V[:Tmax], dtype=dtype).reshape(Tmax, NKV, HD)
+    live = np.arange(Tmax)[None, :] < Ts[:, None]
+    P, Vh, O = [], [], []
+    for h in range(NH):
+        kh = kv_head(h, NH, NKV)
+        s = np.where(live, (Q[:, h, :] @ K[:, kh, :].T) * dtype(scale), dtype(-np.inf))
+        p = np.exp(s - s.max(axis=1, keepdims=True))
+        p = p / p.sum(axis=1, keepdims=True, dtype=dtype)
+        P.append(p); Vh.append(V[:, kh, :]); O.append(p @ V[:, kh, :])
+    return P, Vh, O
+
+
+def attention_rows(Q, K, V, Ts, scale, NH, NKV, dtype=np.float64):
+    """attention() for rows [R][NH * HD] that read the same cache, row r over keys [0, Ts[r]) -> [R][NH * HD]"""
+    _, _, O = _softmax_rows(Q, K, V, Ts, scale, NH, NKV, dtype)
+    return np.concatenate(O, axis=1)
+
+
+def attention(q, K, V, T, scale, NH, NKV, dtype=np.float64):
+    """softmax over keys [0, T) of q . K * scale, times V, query head h on k/v head kv_head(h) -> [NH * HD].
+    dtype=np.float32 evaluates the same formula in float32 (the yardstick of the tolerance, not a model of any kernel's summation order)."""
+    return attention_rows(np.asarray(q).reshape(1, -1), K, V, [T], scale, NH, NKV, dtype)[0]
+
+
+def drop_key(q, K, V, T, scale, NH, NKV, j):
+    """attention() without key j"""
+    keep = np.ones(T, dtype=bool)
+    keep[j] = False
+    return attention(q, np.asarray(K[:T])[keep], np.asarray(V[:T])[keep], T - 1, scale, NH, NKV)
+
+
+def drop_shifts(Q, K, V, Ts, scale, NH, NKV, keys_of):
+    """per row r: {j: max|attention - drop_key(j)| / max|attention|} for j in keys_of(r, Ts[r]), from one softmax: without key j the row is
+    (o - p_j v_j) / (1 - p_j), so it moves by p_j (o - v_j) / (1 - p_j).  Equal to drop_key() (test_attn_reference_cpu.py)."""
+    P, Vh, O = _softmax_rows(Q, K, V, Ts, scale, NH, NKV, np.float64)
+    ref = np.concatenate(O, axis=1)
+    out = []
+    for r, T in enumerate(np.asarray(Ts).reshape(-1)):
+        d = {}
+        for j in keys_of(r, int(T)):
+            d[j] = max(float(np.abs(P[h][r, j] * (O[h][r] - Vh[h][j]) / (1.0 - P[h][r, j])).max()) for h in range(NH)) / float(np.abs(ref[r]).max())
+        out.append(d)
+    return out
+
+
+def fold_slabs(buf, n_parts, part_stride, row, ld, width):
+    """the query row of a projection that left n_parts K-slice slabs part_stride floats apart: summed in slab order, in float32 as the kernels do"""
+    buf = np.asarray(buf, dtype=np.float32)
+    x = buf[row * ld: row * ld + width].copy()
+    for p in range(1, n_parts):
+        x += buf[p * part_stride + row * ld: p * part_stride + row * ld + width]
+    return x
+
+
+def rope_thetas(pos, theta_scale, n=HD // 2):
+    """ggml's angles: theta_0 = float32(pos), theta_{i+1} = theta_i * theta_scale, every product rounded to float32"""
+    t = np.empty(n, dtype=np.float32)
+    th, sc = np.float32(pos), np.float32(theta_scale)
+    for i in range(n):
+        t[i] = th
+        th = np.float32(th * sc)
+    return t
+
+
+def rope_neox(q, pos, theta_scale, NH):
+    """ggml_rope NEOX on every head of a row: pairs (i, i + HD/2); the angles iterated in float32 (rope_thetas), cos / sin and the rotation in float64"""
+    q = np.asarray(q, dtype=np.float64).reshape(NH, HD)
+    th = rope_thetas(pos, theta_scale).astype(np.float64)
+    cs, sn = np.cos(th), np.sin(th)
+    x0, x1 = q[:, :HD // 2], q[:, HD // 2:]
+    return np.concatenate([x0 * cs - x1 * sn, x0 * sn + x1 * cs], axis=1).reshape(NH * HD)
+
+
+def boundary_keys(T, Rd):
+    """the keys next to a batch, pass, round or chunk edge of a row of T keys (Rd: its round or chunk size)"""
+    return sorted({j for j in (0, 15, 16, 63, 64, Rd - 1, Rd, T - 1) if 0 <= j < T})

@@ -1900,11 +1900,51 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (hipMemcpy(out, c->l_logits, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
-    if (c->has_llama && w.size() > 4 && w[0] == 'l' && w[1] == '_' && (w[2] == 'k' || w[2] == 'v') && w[3] == ':') {   // "l_k:<layer>": slot 0's cache rows of a layer
-        const int layer = atoi(w.c_str() + 4);
-        if (layer < 0 || layer >= c->L) { set_err("debug_read(%s): bad layer", what); return -1; }
-        const size_t per = (size_t) c->lm.n_ctx * c->l_kvH, n = std::min(max_floats, per);
-        if (hipMemcpy(out, (w[2] == 'k' ? c->l_kc : c->l_vc) + (size_t) layer * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+    if (c->has_llama && w.size() > 4 && w[0] == 'l' && w[1] == '_' && (w[2] == 'k' || w[2] == 'v') && w[3] == ':') {   // "l_k:<layer>[:<slot>]": a slot's cache rows of a layer (slot 0 by default)
+        int layer = 0, slot = 0;
+        const int got = sscanf(w.c_str() + 4, "%d:%d", &layer, &slot);
+        if (got < 1 || layer < 0 || layer >= c->L || slot < 0 || slot >= (int) std::max<uint32_t>(1, c->lm.max_seqs)) { set_err("debug_read(%s): bad layer/slot", what); return -1; }
+        const size_t per = (size_t) c->lm.n_ctx * c->l_kvH, n = std::min(max_floats, per);   // the cache is [slot][layer][position][kv width]
+        if (hipMemcpy(out, (w[2] == 'k' ? c->l_kc : c->l_vc) + ((size_t) slot * c->L + layer) * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        return (int64_t) n;
+    }
+    if (c->has_llama && (w == "l_q" || w == "l_att")) {   // the last layer's attention of the last forward: the rotated queries it read / the rows it left, [rows][NH * head_dim]
+        const size_t A = (size_t) c->NH * c->lm.head_dim, QKV = A + 2 * (size_t) c->l_kvH, rows = std::min(max_floats / A, (size_t) c->RMAX);
+        if (rows == 0) { set_err("debug_read(%s): buffer too small", what); return -1; }
+        const hipError_t e = w == "l_q" ? hipMemcpy2D(out, A * 4, c->l_qkv, QKV * 4, A * 4, rows, hipMemcpyDeviceToHost) : hipMemcpy(out, c->l_att, rows * A * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { set_err("copy failed"); return -1; }
+        return (int64_t) (rows * A);
+    }
+    if (c->has_llama && w == "l_pos") {   // the rows' positions as the device holds them (a captured step's selection has already moved row 0 to the next position)
+        const size_t n = std::min(max_floats, (size_t) c->RMAX);
+        std::vector<uint32_t> p(n);
+        if (hipMemcpy(p.data(), c->l_pos, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        for (size_t i = 0; i < n; i++) out[i] = (float) p[i];
+        return (int64_t) n;
+    }
+    if (c->has_dia && starts_with(w, "di_attn:")) {   // "di_attn:<layer>:<self|cross>:<q|out|meta>": tts_hip_set_debug snapshots of the last tts_hip_dia_step_batch
+        int layer = 0;
+        char kind[8] = {0}, item[8] = {0};
+        if (sscanf(w.c_str() + 8, "%d:%7[a-z]:%7[a-z]", &layer, kind, item) != 3) { set_err("debug_read(%s): bad spec", what); return -1; }
+        const std::string k(kind), it(item);
+        auto f = c->dia_attn_dbg.find(layer * 2 + (k == "cross" ? 1 : 0));
+        if ((k != "self" && k != "cross") || f == c->dia_attn_dbg.end()) { set_err("debug_read(%s): no snapshot (tts_hip_set_debug before tts_hip_dia_step_batch)", what); return -1; }
+        const std::vector<float> *v = it == "q" ? &f->second.q : it == "out" ? &f->second.out : it == "meta" ? &f->second.meta : nullptr;
+        if (!v) { set_err("debug_read(%s): bad item", what); return -1; }
+        if (v->size() > max_floats) { set_err("buffer too small"); return -1; }
+        memcpy(out, v->data(), v->size() * 4);
+        return (int64_t) v->size();
+    }
+    if (c->has_dia && w.size() > 5 && w[0] == 'd' && w[1] == 'i' && w[2] == '_') {   // "di_k|di_v:<layer>:<row slot>" [max_gen][kv width], "di_ck|di_cv:<layer>:<row slot>" [max_ctx][A]
+        const bool cross = w[3] == 'c';
+        const char kv = w[cross ? 4 : 3];
+        int layer = 0, row = 0;
+        const size_t o = cross ? 5 : 4;
+        if ((kv != 'k' && kv != 'v') || w.size() <= o + 1 || w[o] != ':' || sscanf(w.c_str() + o + 1, "%d:%d", &layer, &row) != 2 || layer < 0 || layer >= c->L || row < 0 ||
+            row >= 2 * c->di_U) { set_err("debug_read(%s): bad item or layer/row slot", what); return -1; }
+        const size_t per = cross ? (size_t) c->dia.max_ctx * c->di_A : (size_t) c->dia.max_gen * c->di_kvH, n = std::min(max_floats, per);
+        const float *base = cross ? (kv == 'k' ? c->di_ck : c->di_cv) : (kv == 'k' ? c->di_k : c->di_v);
+        if (hipMemcpy(out, base + ((size_t) layer * 2 * c->di_U + row) * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
     if (w.size() > 2 && (w[0] == 'k' || w[0] == 'v') && w[1] == ':') {

@@ -335,6 +335,10 @@ struct tts_hip_ctx {
     size_t d_frames_cap = 0;
     bool debug = false;
     std::map<int, std::vector<float>> dac_dbg;
+    // Dia, tts_hip_set_debug: what every attention launch of the last eager tts_hip_dia_step_batch consumed and produced, key = layer * 2 + (cross ? 1 : 0)
+    // (self-attention writes di_att and cross-attention overwrites it, so the rows are copied out between the two)
+    struct DiaAttnSnap { std::vector<float> q, out, meta; };
+    std::map<int, DiaAttnSnap> dia_attn_dbg;
     std::vector<float> win_pcm;    // tts_hip_dac_decode_windows: the windows' whole PCM before the crop
     std::map<size_t, float *> packed;  // arena offset of a conv weight -> its MFMA-tile-packed copy
     std::set<size_t> packed_direct;    // ... of those, the k = 1 weights packed as [cin][cout] for conv1x1_direct_kernel

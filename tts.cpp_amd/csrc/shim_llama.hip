@@ -1325,10 +1325,30 @@ extern "C" int tts_hip_dia_encode(tts_hip_ctx *c, const uint32_t *tokens, uint32
     return tts_hip_dia_encode_slot(c, 0, tokens, sentence_len, enc_out);
 }
 
+// tts_hip_set_debug on an eager step: the query buffer an attention launch was handed (self: the rotated [R][ld] rows; cross: the raw slabs the kernel
+// folds and rotates itself), the rows it left in di_att, and the extents it read, copied to the host table tts_hip_debug_read serves
+// ("di_attn:<layer>:<self|cross>:<q|out|meta>").  meta: n_parts, part_stride, ld, R, then pos[R], kend[R], row_seq[R].
+static int dia_attn_snapshot(tts_hip_ctx *c, int layer, bool cross, const float *q, int ld, int n_parts, int64_t part_stride, int R, int A, const uint32_t *kend) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto &s = c->dia_attn_dbg[layer * 2 + (cross ? 1 : 0)];
+    s.q.resize((size_t) (n_parts - 1) * (size_t) part_stride + (size_t) R * ld);
+    s.out.resize((size_t) R * A);
+    std::vector<uint32_t> u((size_t) 3 * R);
+    HIPCHK(hipMemcpy(s.q.data(), q, s.q.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s.out.data(), c->di_att, s.out.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(u.data(), c->di_pos, (size_t) R * 4, hipMemcpyDeviceToHost));
+    if (kend) HIPCHK(hipMemcpy(u.data() + R, kend, (size_t) R * 4, hipMemcpyDeviceToHost));
+    else for (int r = 0; r < R; r++) u[(size_t) R + r] = u[(size_t) r] + 1;   // causal over the row's cache
+    HIPCHK(hipMemcpy(u.data() + 2 * R, c->di_seq, (size_t) R * 4, hipMemcpyDeviceToHost));
+    s.meta.assign({(float) n_parts, (float) part_stride, (float) ld, (float) R});
+    for (uint32_t v : u) s.meta.push_back((float) v);
+    return 0;
+}
+
 // the decoder step for the U utterances whose input ids / positions / cache rows are in di_ids / di_pos / di_seq; leaves the guided
 // logits in di_guided.  self_keys sizes the self-attention scratch; fixed_split: a captured step is replayed at every position, so the
 // key-split count must not depend on it (the kernels read the true extent from di_pos)
-static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split) {
+static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, bool snap = false) {
     const int S = (int) c->dia.max_ctx, G = (int) c->dia.max_gen, DH = c->H, DF = c->di_DF, A = c->di_A, kvH = c->di_kvH, HD = (int) c->dia.head_dim;
     const int NH = c->NH, NKV = (int) c->dia.dec_kv_heads, NO = c->NO, V = c->di_V, QKV = A + 2 * kvH;
     const int R = 2 * U, RS = 2 * c->di_U;
@@ -1362,6 +1382,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split) {
         CHK(launch_attn_gqa(c, NH, R, self_keys, (const float *) c->di_qkv, QKV, (const uint32_t *) c->di_pos, (const float *) kc, (const float *) vc, NKV, 1.0f,
                             c->di_att, nul, nul, (const uint32_t *) c->di_seq, (int64_t) G * kvH, fixed_split, false, QPre{},
                             A % 128 == 0 && stream_fold_ok(c, y.so, R, DIA_STREAM_SLABS) ? &slices : nullptr));
+        if (snap) CHK(dia_attn_snapshot(c, l, false, c->di_qkv, QKV, 1, 0, R, A, nullptr));
         CHK(dia_gemm_stream(c, y.so, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
         else CHK(dia_gemm(c, y.so, c->di_att, A, c->di_x, DH, R, EPI_RESID));
@@ -1374,6 +1395,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split) {
         CHK(launch_attn_gqa(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, ck, cv, NH, 1.0f, c->di_att, nul, (const uint32_t *) c->di_cend,
                             (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
                             A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S));
+        if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, qp.n_parts, qp.part_stride, R, A, c->di_cend));
         CHK(dia_gemm_stream(c, y.co, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
         else CHK(dia_gemm(c, y.co, c->di_att, A, c->di_x, DH, R, EPI_RESID));
@@ -1436,7 +1458,8 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
     HIPCHK(hipMemcpyAsync(c->di_ids, h_ids, (size_t) U * NO * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->di_pos, h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->di_seq, h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
-    CHK(dia_forward(c, U, (int) max_pos + 1, false));
+    if (c->debug) c->dia_attn_dbg.clear();
+    CHK(dia_forward(c, U, (int) max_pos + 1, false, c->debug));   // debug: the attention launches' inputs and outputs go to dia_attn_dbg (never under a capture: this step is eager)
     HIPCHK(hipMemcpyAsync(logits_out, c->di_guided, (size_t) U * NO * V * 4, hipMemcpyDeviceToHost, c->stream));
     if (raw_out)
         for (int b = 0; b < R; b++)

@@ -707,12 +707,18 @@ class OrpheusEngine:
         if rc != 0:
             raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
 
+    def set_debug(self, on=True):
+        """tts_hip_set_debug (an Orpheus forward launches the same with it on or off: every debug_read item survives the forward)"""
+        self._chk(self.L.tts_hip_set_debug(self.ctx, 1 if on else 0))
+
     def debug_read(self, what, max_floats):
-        """'l_logits': the logits row the last step left; 'l_k:<layer>' / 'l_v:<layer>': slot 0's cache rows (test / debugging aid)"""
+        """'l_logits': the logits row the last step left; 'l_k:<layer>[:<slot>]' / 'l_v:...': a cache slot's rows of a layer; last layer of the last
+        forward: 'l_q' the rotated queries the attention read and 'l_att' the rows it left ([rows][heads * 128], rows = max_floats // width), 'l_pos'
+        the rows' positions (after a captured step: already moved on by one) (test / debugging aid)"""
         out = np.empty(max_floats, dtype=np.float32)
         n = self.L.tts_hip_debug_read(self.ctx, what.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), max_floats)
         if n < 0:
-            raise HipError(self.err())
+            raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
         return out[:n].copy()
 
     def tune(self, key, value):
@@ -959,6 +965,20 @@ class DiaEngine:
 
     def synchronize(self):
         self._chk(self.L.tts_hip_synchronize(self.ctx))
+
+    def set_debug(self, on=True):
+        """keep, per layer, what the self- and the cross-attention launch of the next step_batch calls read and wrote (debug_read 'di_attn:...');
+        the slice merge then stays a launch of its own (attn_gqa_combine_kernel)"""
+        self._chk(self.L.tts_hip_set_debug(self.ctx, 1 if on else 0))
+
+    def debug_read(self, what, max_floats):
+        """'di_attn:<layer>:<self|cross>:<q|out|meta>' (set_debug before the step; meta = n_parts, part_stride, ld, rows, then pos / kend / row slot per
+        row), 'di_k|di_v:<layer>:<row slot>' [max_gen][kv width], 'di_ck|di_cv:<layer>:<row slot>' [max_ctx][heads * 128] (test / debugging aid)"""
+        out = np.empty(max_floats, dtype=np.float32)
+        n = self.L.tts_hip_debug_read(self.ctx, what.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), max_floats)
+        if n < 0:
+            raise HipError(self.L.tts_hip_last_error().decode("utf-8", "replace"))
+        return out[:n].copy()
 
     def encode(self, tokens, sentence_len, want_states=False):
         a, ap = _u32(tokens)
