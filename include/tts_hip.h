@@ -202,6 +202,12 @@ int tts_hip_parler_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *st
  * repetition_penalty == 1). */
 int tts_hip_sample_logits(tts_hip_ctx *ctx, uint32_t n_rows, const float *logits, const tts_hip_sampling *sampling,
                           const float *uniforms, int32_t *last_ids, uint32_t *rep_counts, uint32_t *tokens_out);
+/* The same selection with a sampler per row, as the slots of a mixed Dia session carry them (tts_hip_dia_stream_begin_mixed): row r runs with
+ * sampling[r], NULL meaning sampler::max (first maximum wins; no uniform read, its state untouched).  Per row the contract of
+ * tts_hip_sample_logits with that row's settings, and the same ids and state: uniforms may be NULL when every row is greedy, last_ids /
+ * rep_counts when no row has a repetition penalty; the state of a row without one is left as it is. */
+int tts_hip_sample_logits_rows_mixed(tts_hip_ctx *ctx, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling,
+                                     const float *uniforms, int32_t *last_ids, uint32_t *rep_counts, uint32_t *tokens_out);
 
 /* ---- T5 voice-prompt encoder (src/models/parler/t5/model.cpp) ---------------------------------
  * What parler_tts_runner::update_conditional_prompt runs (model.cpp:510-518): text_encoder_from_file ->
@@ -460,10 +466,29 @@ int tts_hip_dia_gen_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps
  * Between begin and end every other generation call on the context (tts_hip_dia_encode*, _step*, _generate, gen_begin / gen_launch / gen_wait)
  * is refused with an error, and so is a second begin.  Every misuse (n_slots > max_utterances, a busy slot, a slot >= n_slots or named twice,
  * collect on a slot that has not been reported or for more steps than it made, a budget outside (max_delay, max_gen], a sentence length outside
- * 1..max_ctx, a sampled session without uniforms, sampler limits) returns non-zero before anything is launched; the context stays usable. */
+ * 1..max_ctx, a sampled session without uniforms, sampler limits) returns non-zero before anything is launched; the context stays usable.
+ * Mixed session: begin_mixed is begin with every slot carrying its own sampler, so utterances that differ in top_k, top_p, temperature or
+ * repetition penalty, greedy ones among them, share one loop; its checks are begin's (output_vocab_size <= 2048 also when every occupant
+ * will be greedy).  The step is the session's — pre-step, forward, guidance, post-step — with ONE sample_kernel launch in place of the
+ * arg-max / sampler alternative: every row reads its slot's record {mode, top_k, top_p, temperature, its own repetition-penalty table}; a greedy
+ * row takes the kernel's first phase (sampler::max: first maximum wins, the id the arg-max kernel gives), reads no uniform and touches no sampler
+ * state; a parked slot sits out as before.  admit_mixed is admit with sampling[i] per utterance (sampling NULL or sampling[i] NULL: sampler::max;
+ * else the limits of tts_hip_dia_generate, checked for all n before anything is launched) and uniforms [n][max_gen][n_output_heads], where the
+ * block of a greedy utterance is ignored; uniforms may be NULL when all n are greedy and is refused with a sampled one.  The ONE admission launch
+ * also rewrites the slot's record, its own table [max_gen] (pow(penalty, count) in double, evaluated on the host) and its last_token_ids /
+ * repetition_counts (sampler::reset), so nothing of the previous occupant survives.  run, launch, wait, drop, collect and end are the calls above
+ * and work on either kind of session.  The mixed session has a captured graph of its own beside the fixed batch's and the uniform session's:
+ * alternating the three recaptures none, and no admission ever recaptures.  admit_mixed on a session opened by begin, and admit on one opened by
+ * begin_mixed, return non-zero with the session unchanged.
+ * Equality (mixed): an utterance's ids and step count are those of tts_hip_dia_generate on a context with n_utt = n_slots, the utterance in the
+ * same slot, max_gen = its budget, its own sampler (NULL for a greedy one) and its uniforms in that slot's column — whoever else is live, parked,
+ * greedy or sampled in the other slots, and whatever the launch sizes (tests/test_gpu_dia_stream_mixed.py). */
 int tts_hip_dia_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sampling);
 int tts_hip_dia_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
                              const float *uniforms);
+int tts_hip_dia_stream_begin_mixed(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes);
+int tts_hip_dia_stream_admit_mixed(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len,
+                                   const uint32_t *budget, const tts_hip_sampling *const *sampling, const float *uniforms);
 int tts_hip_dia_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps);
 int tts_hip_dia_stream_launch(tts_hip_ctx *ctx, uint32_t n_steps);
 int tts_hip_dia_stream_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "parler_kernels.h"   // SampleRow: the per-slot sampler record of a mixed session
+
 struct DiaEmbedArgs {
     const float *table[16];   // [V][H] fp32 each
     const uint32_t *ids;      // [n_utt][n_out]
@@ -69,7 +71,8 @@ static __global__ __launch_bounds__(256) void rows_to_f16_kernel(const float *x,
 //                             the countdown reaches 0.  Also publishes the 1-based sampler call index of this step.
 //   dia_loop_poststep_kernel  record the sampled ids, advance the position (both guidance rows), feed head i its id once pos > i, BOS before.
 //   dia_loop_lookin_kernel    the look-in: {sampler calls, parked flag, the history rows no earlier look-in took} of every slot into one block
-//   dia_stream_admit_kernel   one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column
+//   dia_stream_admit_kernel   one launch for all admitted slots: loop state and sampler state reset, uniforms into the slot's column; in a
+//                             mixed session also the occupant's sampler record and its own penalty table
 //   dia_stream_clear_kernel   begin: zero cross K/V at position 0 of the slots no encoder pass has filled (what their parked rows attend over)
 //   dia_stream_drop_kernel    parks live slots at once, between a look-in and the next step (what the parking pre-step writes)
 // ------------------------------------------------------------------------------------------------
@@ -172,9 +175,16 @@ struct DiaAdmitArgs {
     uint32_t *repc;
     uint32_t *ids, *pos, *done, *call, *handed, *budget, *steps, *cend;
     int32_t *delay;
+    // a mixed session (tts_hip_dia_stream_admit_mixed): the occupant's sampler record and its own penalty table move into the slot's places
+    // (rec_in NULL: a uniform session, the sampler is the launch's)
+    const SampleRow *rec_in;  // [n]; pen_table already points at the slot's table, or is NULL (penalty 1, or sampler::max)
+    SampleRow *rec;           // [n_slots] what sample_kernel reads
+    const double *pen_in;     // [n][pen_len]
+    double *pen;              // [n_slots][pen_len]
+    int pen_len;
 };
 
-// blockIdx.y = admitted utterance; thread 0 of block x == 0 resets the slot, all threads move its uniforms
+// blockIdx.y = admitted utterance; thread 0 of block x == 0 resets the slot, all threads move its penalty table and its uniforms
 static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitArgs a) {
     const int i = blockIdx.y;
     if (i >= a.n) return;
@@ -188,8 +198,15 @@ static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitAr
         a.cend[2 * u] = a.max_ctx; a.cend[2 * u + 1] = a.max_ctx;
         a.delay[u] = -1; a.done[u] = 0; a.call[u] = 1; a.handed[u] = 0;
         a.budget[u] = a.budgets[i]; a.steps[u] = 0;
+        if (a.rec_in) a.rec[u] = a.rec_in[i];
     }
-    if (!a.uni_in) return;
+    bool sampled = a.uni_in != nullptr;
+    if (a.rec_in) {
+        if (a.rec_in[i].pen_table)
+            for (int e = blockIdx.x * 256 + threadIdx.x; e < a.pen_len; e += gridDim.x * 256) a.pen[(int64_t) u * a.pen_len + e] = a.pen_in[(int64_t) i * a.pen_len + e];
+        sampled = sampled && a.rec_in[i].mode == SAMPLE_ROW_SAMPLE;   // a greedy utterance's block of uniforms is ignored
+    }
+    if (!sampled) return;
     const int64_t total = (int64_t) a.max_gen * a.n_out;
     for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
         const int64_t k = e / a.n_out, h = e - k * a.n_out;

@@ -1110,6 +1110,17 @@ static __global__ void argmax_kernel(const float *logits, int V, uint32_t *token
 // order of equal keys unspecified).  The uniform draws come from the host (std::minstd_rand, sampler.cpp:47-48).
 // ------------------------------------------------------------------------------------------------
 #define SMP_VMAX 2048
+// one utterance's sampler.  SAMPLE_ROW_MAX: sampler::max over the logits as they are — the id of argmax_kernel; no uniform is read and the
+// sampler state is neither read nor written.  SAMPLE_ROW_SAMPLE: sampler::sample with these settings; pen_table NULL means the penalty is 1,
+// and then no state is read or written for the row either.
+#define SAMPLE_ROW_MAX 0u
+#define SAMPLE_ROW_SAMPLE 1u
+struct SampleRow {
+    uint32_t mode, top_k;
+    float top_p, temperature;
+    const double *pen_table;   // this utterance's own pow(penalty, c) table
+    int pen_len, pad_;
+};
 struct SampleArgs {
     const float *logits;       // [R][n_out][V]
     int V, n_out, R;
@@ -1130,6 +1141,9 @@ struct SampleArgs {
     int R_total;
     // rows that sit out (a parked slot of a Dia session): idle[utterance] != 0 -> no id, no draw, the sampler state stands still (NULL: none)
     const uint32_t *idle;
+    // per-utterance settings (a mixed Dia session, tts_hip_sample_logits_rows_mixed): rows[utterance] replaces top_k / top_p / temperature /
+    // pen_table / pen_len above, which are then ignored (NULL: every row runs with the values above)
+    const SampleRow *rows;
 };
 
 // Candidate order = descending value, equal values by ascending index: a total order, so a bitonic sort of the
@@ -1171,18 +1185,26 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ int s_n;
     const int h = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, V = a.V;
     const float *row = a.logits + ((int64_t) r * a.n_out + h) * V;
-    const bool temp = a.temperature != 1.0f;
-    const bool use_topk = a.top_k > 0 && a.top_k < (uint32_t) V;
-    const bool use_topp = a.top_p < 1.0f;
-
-    // the token sampled last enters every comparison and the softmax with its penalised value
     const int ro = a.orig ? (int) a.orig[r] : r;   // utterance of this row
     if (a.idle && a.idle[ro]) return;              // the whole workgroup: ro depends on the block alone
-    const int last = a.pen_table ? a.last_ids[ro * a.n_out + h] : -1;
+    // the settings of this row: the launch's, or the utterance's own record.  Either way they depend on the block alone, so every branch on
+    // them below is taken by the whole workgroup
+    const SampleRow *rec = a.rows ? a.rows + ro : nullptr;
+    const bool greedy = rec && rec->mode == SAMPLE_ROW_MAX;
+    const uint32_t top_k = rec ? rec->top_k : a.top_k;
+    const float top_p = rec ? rec->top_p : a.top_p, temperature = rec ? rec->temperature : a.temperature;
+    const double *pen_table = greedy ? nullptr : rec ? rec->pen_table : a.pen_table;
+    const int pen_len = rec ? rec->pen_len : a.pen_len;
+    const bool temp = temperature != 1.0f;
+    const bool use_topk = top_k > 0 && top_k < (uint32_t) V;
+    const bool use_topp = top_p < 1.0f;
+
+    // the token sampled last enters every comparison and the softmax with its penalised value
+    const int last = pen_table ? a.last_ids[ro * a.n_out + h] : -1;
     float pen_v = 0.0f;
     if (last >= 0 && last < V) {
         const uint32_t cnt = a.rep_counts[ro * a.n_out + h];
-        pen_v = (float) ((double) row[last] / a.pen_table[cnt < (uint32_t) a.pen_len ? cnt : (uint32_t) a.pen_len - 1]);
+        pen_v = (float) ((double) row[last] / pen_table[cnt < (uint32_t) pen_len ? cnt : (uint32_t) pen_len - 1]);
     }
     // sampler::max (first maximum wins)
     float best = -INFINITY;
@@ -1204,9 +1226,11 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         for (int i = 1; i < 4; i++)
             if (bv[i] > best || (bv[i] == best && bi[i] < besti)) { best = bv[i]; besti = bi[i]; }
         float top = val[besti];
-        if (temp) top /= a.temperature;
+        if (temp) top /= temperature;
         s_top = top;
+        if (greedy) a.out[r * a.n_out + h] = besti;
     }
+    if (greedy) return;   // the whole workgroup, before the next barrier: sampler::max is the first phase alone
     __syncthreads();
     const float top = s_top;
     int n = V;
@@ -1215,7 +1239,7 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     if (use_topp) {  // softmax over the whole vocabulary first (sampler.cpp:20-23)
         for (int i = tid; i < V; i += 256) {
             float v = val[i];
-            if (temp) v /= a.temperature;
+            if (temp) v /= temperature;
             tmp[i] = expf(v - top);
         }
         __syncthreads();
@@ -1229,15 +1253,15 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         __syncthreads();
     }
     if (use_topk) {  // on logits, or on probabilities when the softmax already ran
-        smp_rank_select(val, V, (int) a.top_k, picks, keys);
-        n = (int) a.top_k;
+        smp_rank_select(val, V, (int) top_k, picks, keys);
+        n = (int) top_k;
         nucleus = true;
         __syncthreads();
     }
     if (!use_topp) {  // softmax over the candidates, in candidate order
         for (int j = tid; j < n; j += 256) {
             float v = val[nucleus ? picks[j] : j];
-            if (temp) v /= a.temperature;
+            if (temp) v /= temperature;
             tmp[j] = expf(v - top);
         }
         __syncthreads();
@@ -1260,9 +1284,9 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             int keep = -1;
             for (int j = 0; j < n; j++) {
                 mass += val[picks[j]];
-                if (mass >= a.top_p) { keep = j + 1; break; }
+                if (mass >= top_p) { keep = j + 1; break; }
             }
-            s_mhp = fminf(mass, a.top_p);
+            s_mhp = fminf(mass, top_p);
             s_n = keep > 0 ? keep : n;
         }
         __syncthreads();
@@ -1280,7 +1304,7 @@ static __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             if (target <= cum || j + 1 >= n) { chosen = i; break; }
         }
         a.out[r * a.n_out + h] = (uint32_t) chosen;
-        if (a.pen_table) {  // sampler.cpp:57-63
+        if (pen_table) {  // sampler.cpp:57-63
             uint32_t cnt = a.rep_counts[ro * a.n_out + h];
             if (last != chosen) cnt = 0;
             a.last_ids[ro * a.n_out + h] = chosen;

@@ -1771,6 +1771,77 @@ extern "C" int tts_hip_sample_logits(tts_hip_ctx *c, uint32_t n_rows, const floa
     return 0;
 }
 
+// sample_kernel with a record per row: row r runs with sampling[r] (NULL: sampler::max), every penalised row with a table of its own, as the
+// slots of a mixed Dia session do.  Per row what tts_hip_sample_logits does with that row's settings.
+extern "C" int tts_hip_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling,
+                                                const float *uniforms, int32_t *last_ids, uint32_t *rep_counts, uint32_t *tokens_out) {
+    const char *what = "tts_hip_sample_logits_rows_mixed";
+    CHK(ready(c, what));
+    if (!logits || !sampling || !tokens_out) return set_err("%s: null argument", what);
+    if (n_rows == 0 || (int) n_rows > c->RMAX) return set_err("%s: n_rows=%u outside 1..%d", what, n_rows, c->RMAX);
+    if (c->V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, c->V, SMP_VMAX);
+    bool any_sampled = false, any_rep = false;
+    uint32_t mx = 0;
+    for (uint32_t r = 0; r < n_rows; r++) {
+        if (!sampling[r]) continue;
+        CHK(check_sampling(c, sampling[r], what));
+        any_sampled = true;
+        if (sampling[r]->repetition_penalty == 1.0f) continue;
+        if (!last_ids || !rep_counts) return set_err("%s: repetition penalty needs last_ids and rep_counts", what);
+        any_rep = true;
+        for (int h = 0; h < c->NO; h++) mx = std::max(mx, rep_counts[(size_t) r * c->NO + h]);
+    }
+    if (any_sampled && !uniforms) return set_err("%s: a sampled row needs uniforms [n_rows][n_output_heads]", what);
+    const int len = (int) std::min<uint32_t>(mx + 2, 1u << 20) + 1;   // what stage_penalty builds for tts_hip_sample_logits
+    SampleRow *d_rec = nullptr;
+    double *d_tab = nullptr;
+    HIPCHK(hipMalloc((void **) &d_rec, (size_t) n_rows * sizeof(SampleRow)));
+    if (any_rep && hipMalloc((void **) &d_tab, (size_t) n_rows * len * 8) != hipSuccess) { free_dev(d_rec); return set_err("%s: out of device memory", what); }
+    std::vector<SampleRow> recs(n_rows);
+    std::vector<double> tabs(any_rep ? (size_t) n_rows * len : 0);
+    for (uint32_t r = 0; r < n_rows; r++) {
+        const tts_hip_sampling *sp = sampling[r];
+        SampleRow &rec = recs[r];
+        rec = SampleRow{};
+        rec.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
+        rec.top_k = sp ? sp->top_k : 0u; rec.top_p = sp ? sp->top_p : 1.0f; rec.temperature = sp ? sp->temperature : 1.0f;
+        rec.pen_len = len;
+        if (sp && sp->repetition_penalty != 1.0f) {
+            rec.pen_table = d_tab + (size_t) r * len;
+            for (int k = 0; k < len; k++) tabs[(size_t) r * len + k] = pow((double) sp->repetition_penalty, (double) k);
+        }
+    }
+    int rc = 0;
+    auto run = [&]() -> int {
+        if (any_sampled) CHK(stage_uniforms(c, uniforms, (size_t) n_rows * c->NO));
+        HIPCHK(hipMemcpyAsync(c->logits, logits, (size_t) n_rows * c->NO * c->V * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_rec, recs.data(), recs.size() * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+        SampleArgs sa{};
+        sa.logits = c->logits; sa.V = c->V; sa.n_out = c->NO; sa.R = (int) n_rows;
+        sa.uniforms = c->d_uniforms; sa.row_step = nullptr; sa.out = c->d_tok;
+        sa.rows = d_rec;
+        if (any_rep) {
+            HIPCHK(hipMemcpyAsync(d_tab, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->d_last, last_ids, (size_t) n_rows * c->NO * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->d_repc, rep_counts, (size_t) n_rows * c->NO * 4, hipMemcpyHostToDevice, c->stream));
+            sa.last_ids = c->d_last; sa.rep_counts = c->d_repc;
+        }
+        hipLaunchKernelGGL(sample_kernel, dim3(c->NO, n_rows), dim3(256), 0, c->stream, sa);
+        HIPCHK(hipGetLastError());
+        if (any_rep) {
+            HIPCHK(hipMemcpyAsync(last_ids, c->d_last, (size_t) n_rows * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(rep_counts, c->d_repc, (size_t) n_rows * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipMemcpyAsync(tokens_out, c->d_tok, (size_t) n_rows * c->NO * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return 0;
+    };
+    rc = run();
+    if (rc != 0) (void) hipStreamSynchronize(c->stream);
+    free_dev(d_rec); free_dev(d_tab);
+    return rc;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // T5 voice-prompt encoder (src/models/parler/t5/model.cpp:216-357)

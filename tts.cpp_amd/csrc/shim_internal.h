@@ -195,6 +195,7 @@ struct tts_hip_ctx {
         enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: seen parked by a look-in, not yet reported
         Mode mode = NONE;
         bool sampled = false, rep = false;
+        bool mixed = false;              // SESSION opened by tts_hip_dia_stream_begin_mixed: every slot carries its own sampler (di_srec)
         bool all_done = false;           // the last look-in found no live slot
         uint32_t n = 0, max_gen = 0;     // utterances (BATCH) or slots (SESSION)
         tts_hip_dia_codes codes{};
@@ -208,13 +209,20 @@ struct tts_hip_ctx {
         uint32_t unread = 0;             // steps enqueued since the last look-in that took rows: bounds the rows a look-in can find
     } dl;
     // what the captured step of a mode holds by value: a begin that changes any of it drops that mode's graph (and only that one, so a
-    // caller alternating tts_hip_dia_generate and a session keeps both)
+    // caller alternating tts_hip_dia_generate, a session and a mixed session keeps all three)
     struct DiaBaked { const void *uni = nullptr, *pen = nullptr; tts_hip_sampling sp{}; int sampled = -1; uint32_t n = 0, max_gen = 0; tts_hip_dia_codes codes{}; };
-    DiaBaked di_baked[2];                // [0] BATCH, [1] SESSION
+    DiaBaked di_baked[3];                // [0] BATCH, [1] SESSION, [2] mixed SESSION (sampled = 2, pen = di_srec)
     uint32_t *di_sbud = nullptr;         // device [2][U]: budget, steps
     uint32_t *di_sadm = nullptr;         // device [2][U]: slots, budgets of one admission
     float *di_suni = nullptr;            // device: the admitted utterances' uniforms before they move into their columns
     size_t di_suni_cap = 0;
+    // a mixed session: the slots' sampler records and penalty tables, and where one admission stages its utterances' before the admit launch
+    // moves them into the slots' places.  di_srec is allocated once (the captured sample_kernel launch holds it); the tables are reached
+    // through the records only, so they may move when a session asks for more
+    void *di_srec = nullptr, *di_srec_in = nullptr;   // device SampleRow [U] each
+    double *di_spen = nullptr, *di_spen_in = nullptr; // device [U][di_spen_len] each
+    size_t di_spen_cap = 0;                           // doubles either holds
+    int di_spen_len = 0;                              // entries per slot in the open mixed session (its max_gen)
     std::vector<uint8_t> di_slot_encoded;   // tts_hip_dia_encode_slot has run for the slot
     uint32_t *h_di = nullptr;            // pinned staging: ids / pos / seq of a step
     // ---- Kokoro context (tts_hip_kokoro_create) ----

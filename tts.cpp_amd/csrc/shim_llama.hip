@@ -1474,7 +1474,9 @@ extern "C" int tts_hip_dia_step_batch(tts_hip_ctx *c, uint32_t n_utt, const uint
 // parked flag are device memory: an admission changes values, never the captured launches.  The modes differ in how slots become live
 // (all at begin / by admission), in how many replays a launch may enqueue, and in what a look-in reports.
 #define DIA_LOOP_CHUNK 16
-static const int DIA_GRAPH_KEY = 9100001;   // + 1 for the session's graph
+static const int DIA_GRAPH_KEY = 9100001;   // + 1 for the session's graph, + 2 for the mixed session's
+// which captured step and which DiaBaked entry a loop uses: 0 BATCH, 1 SESSION, 2 mixed SESSION
+static int dia_graph_slot(const DL &g) { return g.mixed ? 2 : g.mode == DL::SESSION ? 1 : 0; }
 
 // leaving the loop, whichever mode: steps in flight are waited for and dropped (encode / step / a new loop overwrite what they read), and
 // the cross extent of every row is the whole text context again, as the other entry points expect (parking moved it to one key)
@@ -1520,7 +1522,14 @@ static int dia_loop_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
     hipLaunchKernelGGL(dia_loop_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
     HIPCHK(hipGetLastError());
     CHK(dia_forward(c, U, (int) c->dia.max_gen, captured));
-    if (g.sampled) {
+    if (g.mixed) {   // one launch whatever the slots hold: every row reads its slot's record, greedy rows leave after sampler::max
+        SampleArgs sa{};
+        sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
+        sa.uniforms = c->d_uniforms; sa.row_step = la.call; sa.out = c->di_stok; sa.idle = la.done;
+        sa.last_ids = c->d_last; sa.rep_counts = c->d_repc;
+        sa.rows = (const SampleRow *) c->di_srec;
+        hipLaunchKernelGGL(sample_kernel, dim3(NO, U), dim3(256), 0, c->stream, sa);
+    } else if (g.sampled) {
         SampleArgs sa{};
         sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;
         sa.top_k = g.sp.top_k; sa.top_p = g.sp.top_p; sa.temperature = g.sp.temperature;
@@ -1556,15 +1565,33 @@ static int dia_loop_check(tts_hip_ctx *c, const char *what, const char *rows, ui
 // The loop over slots 0..n-1 from its first step; the arguments have been checked.  BATCH: every slot live, over the whole text context, with
 // the budget max_gen and the caller's uniforms [call][utt][head] (what an admission of all n slots leaves, without the encoder passes).
 // SESSION: every slot parked over one cross key until an admission; the admissions fill the slots' uniform columns.
-static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms) {
+// mixed (SESSION with sp NULL): every slot carries its own sampler record and penalty table [max_gen], sampler::max until an admission
+// writes them; the uniforms block and the sampler state exist whatever the occupants turn out to be.
+static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t max_gen, const tts_hip_dia_codes *codes, const tts_hip_sampling *sp, const float *uniforms,
+                          bool mixed = false) {
     const int S = (int) c->dia.max_ctx, NO = c->NO, U = (int) n, DU = c->di_U;
     const bool live = mode == DL::BATCH, rep = sp && sp->repetition_penalty != 1.0f;
     CHK(dia_loop_end(c));   // an unfinished tts_hip_dia_gen_* loop is waited for and dropped
     HIPCHK(hipSetDevice(c->device));
-    if (sp) {
+    if (sp || mixed) {
         const std::vector<float> zero(uniforms ? 0 : (size_t) max_gen * U * NO, 0.0f);   // sizes d_uniforms
         CHK(stage_uniforms(c, uniforms ? uniforms : zero.data(), (size_t) max_gen * U * NO));
-        CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
+        if (sp) CHK(stage_penalty(c, sp->repetition_penalty, (int) max_gen));
+    }
+    if (mixed) {
+        if (!c->di_srec) {
+            HIPCHK(hipMalloc(&c->di_srec, (size_t) DU * sizeof(SampleRow)));
+            HIPCHK(hipMalloc(&c->di_srec_in, (size_t) DU * sizeof(SampleRow)));
+        }
+        if ((size_t) DU * max_gen > c->di_spen_cap) {   // nothing is in flight (dia_loop_end), and no captured launch holds these
+            free_dev(c->di_spen); free_dev(c->di_spen_in);
+            c->di_spen = c->di_spen_in = nullptr; c->di_spen_cap = 0;
+            HIPCHK(hipMalloc((void **) &c->di_spen, (size_t) DU * max_gen * 8));
+            HIPCHK(hipMalloc((void **) &c->di_spen_in, (size_t) DU * max_gen * 8));
+            c->di_spen_cap = (size_t) DU * max_gen;
+        }
+        c->di_spen_len = (int) max_gen;
+        HIPCHK(hipMemsetAsync(c->di_srec, 0, (size_t) DU * sizeof(SampleRow), c->stream));   // SAMPLE_ROW_MAX, no table
     }
     // ids BOS (the embedding reads them), position 0, countdown -1, sampler call 1, nothing handed out, budget max_gen; sampler::reset (sampler.cpp:71-80)
     {
@@ -1580,7 +1607,7 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
         HIPCHK(hipMemcpyAsync(c->di_cend, cend.data(), cend.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->di_loop, loop.data(), loop.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->di_sbud, bud.data(), bud.size() * 4, hipMemcpyHostToDevice, c->stream));
-        if (rep) {
+        if (rep || mixed) {
             HIPCHK(hipMemsetAsync(c->d_last, 0xFF, (size_t) U * NO * 4, c->stream));
             HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) U * NO * 4, c->stream));
         }
@@ -1595,18 +1622,22 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
     }
     // everything the captured launches hold by value: a change drops this mode's graph
     tts_hip_ctx::DiaBaked now;
-    now.sampled = sp ? 1 : 0; now.n = n; now.max_gen = max_gen; now.codes = *codes;
+    now.sampled = mixed ? 2 : sp ? 1 : 0; now.n = n; now.max_gen = max_gen; now.codes = *codes;
     if (sp) { now.uni = c->d_uniforms; now.pen = rep ? (const void *) c->d_pen : nullptr; now.sp = *sp; }
-    auto &bk = c->di_baked[mode == DL::SESSION];
+    if (mixed) { now.uni = c->d_uniforms; now.pen = c->di_srec; }   // the settings themselves are the records' contents
+    DL next;
+    next.mode = mode; next.mixed = mixed;
+    const int gs = dia_graph_slot(next);
+    auto &bk = c->di_baked[gs];
     const bool same = bk.sampled == now.sampled && bk.n == n && bk.max_gen == max_gen && memcmp(&bk.codes, codes, sizeof(*codes)) == 0 &&
-                      (!sp || (bk.uni == now.uni && bk.pen == now.pen && memcmp(&bk.sp, &now.sp, sizeof(now.sp)) == 0));
+                      (!(sp || mixed) || (bk.uni == now.uni && bk.pen == now.pen && memcmp(&bk.sp, &now.sp, sizeof(now.sp)) == 0));
     if (!same) {
-        auto it = c->graphs.find(DIA_GRAPH_KEY + (mode == DL::SESSION));
+        auto it = c->graphs.find(DIA_GRAPH_KEY + gs);
         if (it != c->graphs.end()) { (void) hipGraphExecDestroy(it->second); c->graphs.erase(it); }
         bk = now;
     }
     auto &g = c->dl;
-    g.mode = mode; g.sampled = sp != nullptr; g.rep = rep;
+    g.mode = mode; g.sampled = sp != nullptr; g.rep = rep; g.mixed = mixed;
     g.n = n; g.max_gen = max_gen; g.codes = *codes; g.sp = now.sp;
     g.slot.assign((size_t) U, live ? DL::LIVE : DL::FREE);
     g.steps.assign((size_t) U, 0u);
@@ -1631,7 +1662,7 @@ static int dia_loop_launch(tts_hip_ctx *c, uint32_t n_steps) {
     if (k == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
     const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
-    const int key = DIA_GRAPH_KEY + (g.mode == DL::SESSION);
+    const int key = DIA_GRAPH_KEY + dia_graph_slot(g);
     const DiaLoopArgs la = dia_loop_args(c);
     for (uint32_t i = 0; i < k; i++) {
         auto it = c->graphs.find(key);
@@ -1741,16 +1772,23 @@ extern "C" int tts_hip_dia_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32
     return dia_loop_begin(c, DL::SESSION, n_slots, max_gen, codes, sp, nullptr);
 }
 
-extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
-                                        const float *uniforms) {
-    const char *what = "tts_hip_dia_stream_admit";
+// one sampler's limits, as dia_loop_check asks them of a session's
+static bool dia_sampling_ok(const tts_hip_sampling *sp) { return sp->temperature > 0.0f && sp->top_p > 0.0f && sp->repetition_penalty > 0.0f; }
+
+// both admissions.  mixed: sampling [n] (NULL, or an entry NULL: sampler::max) and the slot's record, table and sampler state rewritten
+static int dia_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len,
+                            const uint32_t *budget, const tts_hip_sampling *const *sampling, const float *uniforms) {
     CHK(dia_stream_ready(c, what));
-    CHK(dia_stream_idle(c, what));
     auto &g = c->dl;
+    if (mixed != g.mixed)
+        return set_err(mixed ? "%s: the session was opened by tts_hip_dia_stream_begin (tts_hip_dia_stream_admit)"
+                             : "%s: the session was opened by tts_hip_dia_stream_begin_mixed (tts_hip_dia_stream_admit_mixed)", what);
+    CHK(dia_stream_idle(c, what));
     if (n == 0) return 0;
     if (!slots || !tokens || !sentence_len) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_gen][n_output_heads]", what);
     const int S = (int) c->dia.max_ctx, NO = c->NO;
+    bool any_sampled = g.sampled, any_rep = false;
     for (uint32_t i = 0; i < n; i++) {
         if (slots[i] >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n);
         if (g.slot[slots[i]] == DL::LIVE || g.slot[slots[i]] == DL::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
@@ -1760,10 +1798,16 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
             return set_err("%s: utterance %u: budget %u outside max_delay %u < budget <= max_gen %u", what, i, budget[i], g.codes.max_delay, g.max_gen);
         for (int t = 0; t < S; t++)
             if (tokens[(size_t) i * S + t] >= (uint32_t) c->di_evocab) return set_err("%s: token %u >= encoder vocabulary %d", what, tokens[(size_t) i * S + t], c->di_evocab);
+        const tts_hip_sampling *sp = mixed && sampling ? sampling[i] : nullptr;
+        if (!sp) continue;
+        if (!dia_sampling_ok(sp)) return set_err("%s: utterance %u: temperature, top_p, repetition_penalty must be > 0", what, i);
+        if (!uniforms) return set_err("%s: utterance %u is sampled: it needs uniforms [n][max_gen][n_output_heads]", what, i);
+        any_sampled = true;
+        any_rep = any_rep || sp->repetition_penalty != 1.0f;
     }
     HIPCHK(hipSetDevice(c->device));
     const size_t per = (size_t) g.max_gen * NO;
-    if (g.sampled && n * per > c->di_suni_cap) {
+    if (any_sampled && n * per > c->di_suni_cap) {
         HIPCHK(hipStreamSynchronize(c->stream));
         free_dev(c->di_suni);
         c->di_suni = nullptr; c->di_suni_cap = 0;
@@ -1778,22 +1822,60 @@ extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32
     std::vector<uint32_t> adm((size_t) 2 * n);
     for (uint32_t i = 0; i < n; i++) { adm[i] = slots[i]; adm[(size_t) n + i] = budget ? budget[i] : g.max_gen; }
     HIPCHK(hipMemcpyAsync(c->di_sadm, adm.data(), adm.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (g.sampled) HIPCHK(hipMemcpyAsync(c->di_suni, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
+    if (any_sampled) HIPCHK(hipMemcpyAsync(c->di_suni, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
+    // a mixed session: per utterance its record, and pow(penalty, count) in double as stage_penalty evaluates it, into the staging copies
+    const int len = c->di_spen_len;
+    std::vector<SampleRow> recs(mixed ? n : 0);
+    std::vector<double> tabs(mixed && any_rep ? (size_t) n * len : 0);
+    if (mixed) {
+        for (uint32_t i = 0; i < n; i++) {
+            const tts_hip_sampling *sp = sampling ? sampling[i] : nullptr;
+            SampleRow &r = recs[i];
+            r = SampleRow{};
+            r.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
+            r.top_k = sp ? sp->top_k : 0u; r.top_p = sp ? sp->top_p : 1.0f; r.temperature = sp ? sp->temperature : 1.0f;
+            r.pen_len = len;
+            if (sp && sp->repetition_penalty != 1.0f) {
+                r.pen_table = c->di_spen + (size_t) slots[i] * len;
+                for (int k = 0; k < len; k++) tabs[(size_t) i * len + k] = pow((double) sp->repetition_penalty, (double) k);
+            }
+        }
+        HIPCHK(hipMemcpyAsync(c->di_srec_in, recs.data(), recs.size() * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+        if (any_rep) HIPCHK(hipMemcpyAsync(c->di_spen_in, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
+    }
     DiaAdmitArgs a{};
     a.n = (int) n; a.n_slots = (int) g.n; a.n_out = NO;
     a.bos = g.codes.bos; a.max_gen = g.max_gen; a.max_ctx = (uint32_t) S;
     a.slots = c->di_sadm; a.budgets = c->di_sadm + n;
-    a.uni_in = g.sampled ? c->di_suni : nullptr; a.uni = c->d_uniforms;
-    a.last = g.rep ? c->d_last : nullptr; a.repc = c->d_repc;
+    a.uni_in = any_sampled ? c->di_suni : nullptr; a.uni = c->d_uniforms;
+    a.last = g.rep || mixed ? c->d_last : nullptr; a.repc = c->d_repc;
+    if (mixed) { a.rec_in = (const SampleRow *) c->di_srec_in; a.rec = (SampleRow *) c->di_srec; a.pen_in = c->di_spen_in; a.pen = c->di_spen; a.pen_len = len; }
     a.ids = c->di_ids; a.pos = c->di_pos; a.cend = c->di_cend;
     a.delay = (int32_t *) c->di_loop; a.done = c->di_loop + c->di_U; a.call = c->di_loop + 2 * c->di_U; a.handed = c->di_loop + 3 * c->di_U;
     a.budget = c->di_sbud; a.steps = c->di_sbud + c->di_U;
-    const unsigned bx = g.sampled ? (unsigned) std::min<size_t>((per + 255) / 256, 64) : 1u;
+    const unsigned bx = any_sampled || any_rep ? (unsigned) std::min<size_t>((per + 255) / 256, 64) : 1u;
     hipLaunchKernelGGL(dia_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));   // adm is a local, uniforms the caller's
+    HIPCHK(hipStreamSynchronize(c->stream));   // adm, recs and tabs are locals, uniforms the caller's
     for (uint32_t i = 0; i < n; i++) { g.slot[slots[i]] = DL::LIVE; g.steps[slots[i]] = 0; g.budget[slots[i]] = adm[(size_t) n + i]; g.handed[slots[i]] = 0; }
     return 0;
+}
+
+extern "C" int tts_hip_dia_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len, const uint32_t *budget,
+                                        const float *uniforms) {
+    return dia_stream_admit(c, "tts_hip_dia_stream_admit", false, n, slots, tokens, sentence_len, budget, nullptr, uniforms);
+}
+
+extern "C" int tts_hip_dia_stream_begin_mixed(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_gen, const tts_hip_dia_codes *codes) {
+    const char *what = "tts_hip_dia_stream_begin_mixed";
+    CHK(dia_loop_check(c, what, "slots", n_slots, max_gen, codes, nullptr));
+    if (c->di_V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, c->di_V, SMP_VMAX);   // every row goes through sample_kernel
+    return dia_loop_begin(c, DL::SESSION, n_slots, max_gen, codes, nullptr, nullptr, true);
+}
+
+extern "C" int tts_hip_dia_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *tokens, const uint32_t *sentence_len,
+                                              const uint32_t *budget, const tts_hip_sampling *const *sampling, const float *uniforms) {
+    return dia_stream_admit(c, "tts_hip_dia_stream_admit_mixed", true, n, slots, tokens, sentence_len, budget, sampling, uniforms);
 }
 
 // slots a look-in saw parked and no call has reported yet, in slot order

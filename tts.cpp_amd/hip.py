@@ -96,6 +96,7 @@ EXPORTS = [
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
     "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
+    "tts_hip_dia_stream_begin_mixed", "tts_hip_dia_stream_admit_mixed", "tts_hip_sample_logits_rows_mixed",
 ]
 
 class Sampling(C.Structure):
@@ -222,6 +223,9 @@ def load_lib():
     L.tts_hip_dia_stream_launch.argtypes = [vp, C.c_uint32]
     L.tts_hip_dia_stream_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p, u32p, u32p]
     L.tts_hip_dia_stream_drop.argtypes = [vp, C.c_uint32, u32p]
+    L.tts_hip_dia_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes)]
+    L.tts_hip_dia_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
+    L.tts_hip_sample_logits_rows_mixed.argtypes = [vp, C.c_uint32, f32p, C.POINTER(C.POINTER(Sampling)), f32p, C.POINTER(C.c_int32), u32p, u32p]
     _lib = L
     return L
 
@@ -266,6 +270,13 @@ def snac_halo_frames(cfg):
     if h < 0:
         raise HipError(load_lib().tts_hip_last_error().decode("utf-8", "replace"))
     return h
+
+
+def sampling_rows(settings):
+    """settings: per row None (sampler::max) or a dict of top_k / temperature / repetition_penalty / top_p -> (Sampling *[n], the structs kept alive)"""
+    keep = [None if s is None else Sampling(s.get("top_k", 50), s.get("top_p", 1.0), s.get("temperature", 1.0), s.get("repetition_penalty", 1.0)) for s in settings]
+    arr = (C.POINTER(Sampling) * len(keep))(*[C.POINTER(Sampling)() if k is None else C.pointer(k) for k in keep])
+    return arr, keep
 
 
 def _u32(a):
@@ -471,6 +482,23 @@ class HipEngine:
         cp = rep_counts.ctypes.data_as(C.POINTER(C.c_uint32)) if rep_counts is not None else None
         self._chk(self.L.tts_hip_sample_logits(self.ctx, lg.shape[0], lg.ctypes.data_as(C.POINTER(C.c_float)), C.byref(sp),
                                                 u.ctypes.data_as(C.POINTER(C.c_float)), lp, cp, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def sample_logits_rows_mixed(self, logits, settings, uniforms=None, last_ids=None, rep_counts=None):
+        """tts_hip_sample_logits_rows_mixed: logits [n][n_out][V], row r with settings[r] (None: sampler::max, else a dict of top_k / top_p /
+        temperature / repetition_penalty) -> ids [n][n_out]; last_ids / rep_counts [n][n_out] are updated in place for the penalised rows"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, self.cfg.n_out, self.cfg.out_vocab)
+        n = lg.shape[0]
+        assert len(settings) == n
+        arr, keep = sampling_rows(settings)
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n, self.cfg.n_out)
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        out = np.empty((n, self.cfg.n_out), dtype=np.uint32)
+        lp = last_ids.ctypes.data_as(C.POINTER(C.c_int32)) if last_ids is not None else None
+        cp = rep_counts.ctypes.data_as(C.POINTER(C.c_uint32)) if rep_counts is not None else None
+        self._chk(self.L.tts_hip_sample_logits_rows_mixed(self.ctx, n, lg.ctypes.data_as(C.POINTER(C.c_float)), arr, up, lp, cp, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
     # ---- dac ----------------------------------------------------------------------------------
@@ -837,13 +865,6 @@ class OrpheusEngine:
                                                             rc.ctypes.data_as(C.POINTER(C.c_uint32)), tok.ctypes.data_as(C.POINTER(C.c_uint32))))
         return tok, li, rc
 
-    @staticmethod
-    def _sampling_rows(settings):
-        """settings: per row None (sampler::max) or a dict of top_k / temperature / repetition_penalty / top_p -> (Sampling *[n], the structs kept alive)"""
-        keep = [None if s is None else Sampling(s.get("top_k", 50), s.get("top_p", 1.0), s.get("temperature", 1.0), s.get("repetition_penalty", 1.0)) for s in settings]
-        arr = (C.POINTER(Sampling) * len(keep))(*[C.POINTER(Sampling)() if k is None else C.pointer(k) for k in keep])
-        return arr, keep
-
     def sample_logits_rows_mixed(self, logits, settings, uniforms=None, last_id=None, rep_count=None):
         """tts_hip_orpheus_sample_logits_rows_mixed: the mixed session's selection on logits [n][vocab], row r with settings[r] (None: arg-max)
         -> (tokens [n], last_id [n], rep_count [n])"""
@@ -853,7 +874,7 @@ class OrpheusEngine:
         li = np.ascontiguousarray(np.full(n, -1) if last_id is None else last_id, dtype=np.int32).copy()
         rc = np.ascontiguousarray(np.zeros(n) if rep_count is None else rep_count, dtype=np.uint32).copy()
         tok = np.zeros(n, dtype=np.uint32)
-        arr, keep = self._sampling_rows(settings)
+        arr, keep = sampling_rows(settings)
         up = None
         if uniforms is not None:
             u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n)
@@ -874,7 +895,7 @@ class OrpheusEngine:
         s, sp = _u32(slots)
         cat, cp = _u32(np.concatenate([np.asarray(p, dtype=np.uint32) for p in prompts]))
         lens, lp = _u32(np.array([len(p) for p in prompts], dtype=np.uint32))
-        arr, keep = self._sampling_rows(settings)
+        arr, keep = sampling_rows(settings)
         up = None
         if uniforms is not None:
             u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(len(prompts), self._stream[1])
@@ -1074,6 +1095,34 @@ class DiaEngine:
             u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n, self._stream[1], self.cfg.n_out)
             up = u.ctypes.data_as(C.POINTER(C.c_float))
         self._chk(self.L.tts_hip_dia_stream_admit(self.ctx, n, sp, tp, lp, bp, up))
+
+    def stream_begin_mixed(self, n_slots, max_gen, delay_pattern, bos, eos, pad, max_delay):
+        """a session whose slots carry their own sampler (stream_admit_mixed); run / launch / wait / drop / collect / end as for stream_begin"""
+        codes = DiaCodes(bos, eos, pad, max_delay)
+        for i, d in enumerate(delay_pattern):
+            codes.delay_pattern[i] = int(d)
+        self._chk(self.L.tts_hip_dia_stream_begin_mixed(self.ctx, n_slots, max_gen, C.byref(codes)))
+        self._stream = (n_slots, max_gen)
+        self._stream_out = (np.full((n_slots, max_gen, self.cfg.n_out), 0xFFFFFFFF, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint8))
+
+    def stream_admit_mixed(self, slots, tokens, sentence_lens, settings, budgets=None, uniforms=None):
+        """stream_admit with settings per utterance: None (greedy) or a dict of top_k / top_p / temperature / repetition_penalty; uniforms
+        [n][max_gen][n_out] (a greedy utterance's block is ignored; None when every utterance is greedy)"""
+        s, sp = _u32(slots)
+        n = s.size
+        t, tp = _u32(np.asarray(tokens, dtype=np.uint32).reshape(-1))
+        assert t.size == n * self.cfg.max_ctx and len(settings) == n
+        ln, lp = _u32(sentence_lens)
+        bp = None
+        if budgets is not None:
+            b, bp = _u32(budgets)
+            assert b.size == n
+        arr, keep = sampling_rows(settings)
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(n, self._stream[1], self.cfg.n_out)
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_dia_stream_admit_mixed(self.ctx, n, sp, tp, lp, bp, arr, up))
 
     def stream_run(self, n_steps):
         """-> [(slot, steps)] of the slots that finished"""

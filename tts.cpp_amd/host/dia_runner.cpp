@@ -259,8 +259,19 @@ struct dia_runner::chunker {
 
 // what every form of generate() does before the loop: the sampler's settings (n_calls = 0: a seeded sampler draws the sequence of a call of
 // its own) and the step budget
+bool dia_runner::valid_max_tokens(const generation_configuration & config) const { return config.max_tokens == 0 || config.max_tokens > (int) hp.max_delay; }
+
+uint32_t dia_runner::resolved_max_gen(const generation_configuration & config) const {
+    const uint32_t max_gen = config.max_tokens > (int) hp.max_delay ? (uint32_t) config.max_tokens : hp.max_generation_size;
+    return std::min(max_gen, hp.max_generation_size);   // the self-attention cache holds max_generation_size positions (:300-301)
+}
+
+bool dia_runner::device_sampler(const generation_configuration & config) const {
+    return !config.sample || (config.temperature > 0.0f && config.top_p > 0.0f && config.repetition_penalty > 0.0f);
+}
+
 uint32_t dia_runner::begin_call(const generation_configuration & config) {
-    if (!(config.max_tokens == 0 || config.max_tokens > (int) hp.max_delay)) TTS_ABORT("TTS_ASSERT(config.max_tokens == 0 || config.max_tokens > model->max_delay) failed\n");
+    if (!valid_max_tokens(config)) TTS_ABORT("TTS_ASSERT(config.max_tokens == 0 || config.max_tokens > model->max_delay) failed\n");
     smp.temperature = config.temperature;
     smp.repetition_penalty = config.repetition_penalty;
     smp.do_sample = config.sample;
@@ -268,8 +279,7 @@ uint32_t dia_runner::begin_call(const generation_configuration & config) {
     smp.top_p = config.top_p;
     smp.seed = config.seed;
     smp.n_calls = 0;
-    uint32_t max_gen = config.max_tokens > (int) hp.max_delay ? (uint32_t) config.max_tokens : hp.max_generation_size;
-    return std::min(max_gen, hp.max_generation_size);   // the self-attention cache holds max_generation_size positions (:300-301)
+    return resolved_max_gen(config);
 }
 
 tts_hip_dia_codes dia_runner::loop_codes() const {
@@ -460,11 +470,12 @@ void dia_runner::stream_begin(const generation_configuration & config) {
     if (getenv("TTS_HOST_LOOP")) TTS_ABORT("stream_begin: TTS_HOST_LOOP asks for the host loop; a session runs on the device\n");
     if (st_on) stream_end();
     st_max_gen = begin_call(config);
+    if (!device_sampler(config)) TTS_ABORT("stream_begin: temperature, top_p and repetition_penalty must be > 0 for a sampled session\n");
     st_cfg = config;
+    // one path: the mixed session, whose slots carry their own sampler; a request with the opening configuration is one among the others
     const tts_hip_dia_codes codes = loop_codes();
-    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
     const uint32_t slots = stream_capacity();
-    hip_check(tts_hip_dia_stream_begin(lm, slots, st_max_gen, &codes, config.sample ? &sp : nullptr), "tts_hip_dia_stream_begin");
+    hip_check(tts_hip_dia_stream_begin_mixed(lm, slots, st_max_gen, &codes), "tts_hip_dia_stream_begin_mixed");
     st_free.clear();
     for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
     st_ticket.assign(slots, 0);
@@ -494,11 +505,22 @@ bool dia_runner::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t,
     return true;
 }
 
-void dia_runner::stream_submit(size_t ticket, const std::string & sentence) {
+bool dia_runner::stream_accepts(const generation_configuration & config) const {
+    return st_on && device_sampler(config) && valid_max_tokens(config) && resolved_max_gen(config) <= st_max_gen;
+}
+
+void dia_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
+
+void dia_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
     if (stream_free() == 0) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
+    if (!device_sampler(config)) TTS_ABORT("stream_submit: temperature, top_p and repetition_penalty must be > 0 (got %g, %g, %g)\n", config.temperature, config.top_p, config.repetition_penalty);
+    if (!valid_max_tokens(config)) TTS_ABORT("stream_submit: max_tokens %d must be 0 or exceed max_delay %u\n", config.max_tokens, hp.max_delay);
+    if (resolved_max_gen(config) > st_max_gen)
+        TTS_ABORT("stream_submit: the request generates up to %u steps, the session was opened for %u (max_tokens)\n", resolved_max_gen(config), st_max_gen);
     waiting w;
     w.ticket = ticket;
+    w.cfg = config;
     w.len = dia_tokenize_sentence(hp, sentence, w.prompt);
     st_wait.push_back(std::move(w));
 }
@@ -508,16 +530,26 @@ void dia_runner::admit_waiting() {
     const uint32_t nh = hp.n_output_heads, S = hp.max_encoder_context_length;
     if (st_wait.empty()) return;
     const uint32_t n = (uint32_t) st_wait.size();
-    std::vector<uint32_t> slots(n), tokens((size_t) n * S, 0u), lens(n);
+    std::vector<uint32_t> slots(n), tokens((size_t) n * S, 0u), lens(n), budgets(n);
+    std::vector<tts_hip_sampling>         sps(n);
+    std::vector<const tts_hip_sampling *> spp(n, nullptr);
     std::vector<float>    uni;
-    if (st_cfg.sample) uni.resize((size_t) n * st_max_gen * nh);
+    bool any_sampled = false;
+    for (const waiting & w : st_wait) any_sampled = any_sampled || w.cfg.sample;
+    if (any_sampled) uni.assign((size_t) n * st_max_gen * nh, 0.0f);
     for (uint32_t i = 0; i < n; i++) {
+        const generation_configuration & cfg = st_wait[i].cfg;
         slots[i] = st_free[st_free.size() - 1 - i];
         lens[i] = st_wait[i].len;
+        budgets[i] = resolved_max_gen(cfg);   // the utterance runs as under a generate() call of its own
         std::copy(st_wait[i].prompt.begin(), st_wait[i].prompt.begin() + std::min<size_t>(S, st_wait[i].prompt.size()), tokens.begin() + (size_t) i * S);
-        if (st_cfg.sample) draw_call_uniforms(st_cfg.seed, st_max_gen, uni.data() + (size_t) i * st_max_gen * nh, nh);
+        if (!cfg.sample) continue;
+        sps[i] = tts_hip_sampling{(uint32_t) cfg.top_k, cfg.top_p, cfg.temperature, cfg.repetition_penalty};
+        spp[i] = &sps[i];
+        draw_call_uniforms(cfg.seed, budgets[i], uni.data() + (size_t) i * st_max_gen * nh, nh);   // its own seed, the calls its budget allows
     }
-    hip_check(tts_hip_dia_stream_admit(lm, n, slots.data(), tokens.data(), lens.data(), nullptr, st_cfg.sample ? uni.data() : nullptr), "tts_hip_dia_stream_admit");
+    hip_check(tts_hip_dia_stream_admit_mixed(lm, n, slots.data(), tokens.data(), lens.data(), budgets.data(), spp.data(), any_sampled ? uni.data() : nullptr),
+              "tts_hip_dia_stream_admit_mixed");
     for (uint32_t i = 0; i < n; i++) {
         st_ticket[slots[i]] = st_wait[i].ticket;
         st_free.pop_back();

@@ -71,7 +71,13 @@ struct dia_runner final : tts_generation_runner {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return st_on ? (uint32_t) st_free.size() - (uint32_t) st_wait.size() : 0; }
     uint32_t stream_live() const override { return st_live + (uint32_t) st_wait.size() + (uint32_t) st_closing.size(); }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;
+    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
+    // The session is a mixed one (tts_hip_dia_stream_begin_mixed): every slot carries its own sampler record, penalty table and step budget, so
+    // a request may differ from the session's configuration in sample, seed, top_k, top_p, temperature, repetition_penalty and max_tokens.  It is
+    // accepted when it is greedy or within the device sampler's limits and its generation length is at most the session's (the opening
+    // configuration's); its uniforms are drawn from its own seed, as a generate() call of its own draws them.
+    bool     stream_accepts(const generation_configuration & config) const override;
+    void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
     // chunked audio out of the session: with a hook set, stream_step launches its 16 steps (tts_hip_dia_stream_launch), decodes the windows
@@ -94,7 +100,7 @@ struct dia_runner final : tts_generation_runner {
 
   private:
     // session state of the continuous batching
-    struct waiting { size_t ticket = 0; std::vector<uint32_t> prompt; uint32_t len = 0; };
+    struct waiting { size_t ticket = 0; std::vector<uint32_t> prompt; uint32_t len = 0; generation_configuration cfg{}; };
     bool                     st_on = false;
     generation_configuration st_cfg{};
     uint32_t                 st_max_gen = 0, st_live = 0;
@@ -116,6 +122,9 @@ struct dia_runner final : tts_generation_runner {
     void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
     void stream_step_chunked(std::vector<stream_result> & finished);
     uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
+    bool     valid_max_tokens(const generation_configuration & config) const;    // begin_call's assertion
+    uint32_t resolved_max_gen(const generation_configuration & config) const;    // the step budget begin_call returns
+    bool     device_sampler(const generation_configuration & config) const;      // greedy, or within the limits of tts_hip_dia_generate
     tts_hip_dia_codes loop_codes() const;                           // the special ids and the delay pattern, as the device loop takes them
     void     draw_call_uniforms(uint64_t seed, uint32_t max_gen, float * out, size_t stride) const;
     void     encode_single(const char * sentence);
