@@ -272,15 +272,18 @@ int tts_hip_orpheus_generate_sampled(tts_hip_ctx *ctx, const uint32_t *prompt, u
  * (sampler::max per row) may be NULL.  generate_batch: generate_from_batch (orpheus/model.cpp:378-392) for n_utt utterances at once — prompts are the
  * utterances' ids back to back (n_prompt[u] each), tokens_out [n_utt][max_new], n_out [n_utt]; sampling NULL = sampler::max, else sampler::sample with
  * uniforms [n_utt][max_new] (utterance u's k-th sampler call draws uniforms[u * max_new + k]) and one repetition state per utterance.  Every utterance
- * receives exactly the ids its own one-sequence generation produces; finished utterances leave the step. */
+ * receives exactly the ids its own one-sequence generation produces.  The loop is the continuous session's (below) with slots 0 .. n_utt-1 admitted
+ * at begin: runs of a fixed number of steps with no copy or synchronise inside; an utterance that finishes inside a run idles as padding until the
+ * run ends and then leaves the rows.  The loop's device buffers stay on the context from one call to the next. */
 int tts_hip_orpheus_step_batch(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *pos, float *logits_out, uint32_t *tokens_out);
 int tts_hip_orpheus_generate_batch(tts_hip_ctx *ctx, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
                                    const tts_hip_sampling *sampling, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out);
 /* The generation loops in pieces, for callers that work on the ids while the decoder is still running (chunked audio); the three
  * generate_* calls above are built on them.  gen_begin: prompts / n_prompt / sampling / uniforms as for generate_batch (n_utt = 1: as for
  * generate_greedy / generate_sampled, uniforms [max_new]); it runs the prompts and makes the first selection.  gen_launch enqueues up to n_steps
- * more steps: for n_utt = 1 replays of the captured step, and the call returns while they run; for n_utt > 1 the host-driven lock-step
- * loop, which returns after the steps ran.  gen_wait synchronises and hands out the ids no gen_wait handed out before: tokens_out
+ * more steps: for n_utt = 1 replays of the captured step, and the call returns while they run; for n_utt > 1 one run of the lock-step loop (what
+ * tts_hip_orpheus_stream_run enqueues: rows staged once, n_steps x (forward, selection, advance), one copy of the slots' state), which returns
+ * after the steps ran; rows that finished leave at this boundary.  gen_wait synchronises and hands out the ids no gen_wait handed out before: tokens_out
  * [n_utt][max_new] receives utterance u's new ids at their places ([u * max_new + old n_out[u]] onwards), n_out[u] its count so far and
  * done[u] whether it has ended (stopping token, max_new ids, or the end of the cache); done may be NULL.  The ids are those of the generate_*
  * calls whatever the launch sizes; steps a launch ran past an utterance's stopping token are discarded.  One gen_launch per gen_wait.
@@ -299,7 +302,7 @@ int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const t
  * The per-slot state (ids so far, finished flag, latest id and position, sampler state, uniforms) lives on the device; a run of k steps is
  * k x (forward, row-batched selection, row advance) enqueued back to back with no copy and no synchronise in between.
  *   begin    n_slots <= max_seqs cache slots, at most max_new ids per utterance, the stopping token, the sampler (sampling NULL: sampler::max; else the
- *            limits of tts_hip_orpheus_generate_sampled; the repetition-penalty table is staged once)
+ *            limits of tts_hip_orpheus_generate_sampled; every admission writes it into the slot's record and penalty table)
  *   admit    n utterances into free slots, between two runs: prompts back to back (n_prompt[i] ids each), uniforms [n][max_new] for a sampled session
  *            (utterance i's k-th sampler call draws uniforms[i * max_new + k]), else NULL.  Each slot's sampler state and counts are reset, its
  *            prompt runs, and the first id is selected from the prompt's last row, as gen_begin does.
@@ -308,12 +311,12 @@ int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const t
  *            are reported with their id counts and leave the rows of the next run.  A row that finishes inside a run idles as padding until the run
  *            ends: nothing it selects is emitted, its sampler state stands still.  With no live rows nothing is launched.
  *   collect  the first `count` ids of a reported slot, before that slot is admitted again
- *   end      ends the session
+ *   end      ends the session (its device buffers stay on the context for the next session or batch)
  * An utterance's ids are those of tts_hip_orpheus_generate_batch for the same prompt, that is those of its own one-sequence generation
  * (tests/test_gpu_orpheus_stream.py).  Key split: the attention of step i of a run is sized by max over the live rows of (position at the look-in)
  * + i + 1, capped at n_ctx: the exact longest row as long as nobody finishes, an upper bound once someone has.  Below 256 keys that bound selects one
- * key split, as in generate_batch; beyond, the split count follows the longest live row exactly as generate_batch does today, and the bound can
- * select another count than generate_batch's exact length would for the same rows (another association of the same softmax).
+ * key split; beyond, the split count follows the bound, which can select another count than the exact longest live row would (another association
+ * of the same softmax).  tts_hip_orpheus_generate_batch and gen_launch size their steps the same way.
  * Between begin and end every other tts_hip_orpheus_* generation call on the context (decode, step_batch, sample_logits, generate_*, gen_begin,
  * gen_launch) is refused with an error, as in the window between a gen_launch and its gen_wait; begin is refused in that window and while a
  * gen_* generation has unfinished utterances.  Every misuse (a busy slot, a slot >= n_slots, collect on a slot that has not been reported or for
@@ -324,8 +327,8 @@ int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const t
  * a greedy utterance; uniforms may be NULL when all n are greedy).  The slot's record {mode, top_k, temperature, top_p} and its own repetition-penalty
  * table [max_new] are rewritten at every admission, so nothing of the slot's previous utterance stays.  run, collect and end are the calls above.  Per
  * step a run enqueues the arg-max pair when a live row is greedy, the top-k kernels when one is sampled and the softmax total when a sampled one has
- * top_p < 1 (known when the run's rows are staged); each kernel skips the rows of the other mode.  Per row the selection kernels are the uniform
- * session's with the parameters read from the row's slot, so an utterance's ids are those of its own one-sequence generation with its own sampler
+ * top_p < 1 (known when the run's rows are staged); each kernel skips the rows of the other mode.  The uniform session runs the same kernels: its admissions write the
+ * session's one sampler into every slot's record.  So an utterance's ids are those of its own one-sequence generation with its own sampler
  * (tests/test_gpu_orpheus_stream_mixed.py).  admit_mixed on a session opened by begin, and admit on one opened by begin_mixed, return non-zero
  * with the session unchanged. */
 int tts_hip_orpheus_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sampling);

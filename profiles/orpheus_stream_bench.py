@@ -1,8 +1,10 @@
-"""Orpheus-3B Q4_0 (the synthetic shapes of secondary_bench.py): the host-driven lock-step loop against the continuous session.
+"""Orpheus-3B Q4_0 (the synthetic shapes of secondary_bench.py): the lock-step loop through its two ways in, the fixed batch and the continuous session.
 
-  per-step time   tts_hip_orpheus_gen_launch (host-driven: three copies, two synchronises and, when sampling, up to three launches per row in
-                  every step) against tts_hip_orpheus_stream_run (device-driven: forward, row-batched selection and row advance enqueued back
-                  to back) at 8 and 32 rows, greedy and sampled (top_k 50)
+  per-step time   tts_hip_orpheus_gen_launch (the fixed batch) against tts_hip_orpheus_stream_run (the session) at 8 and 32 rows, greedy and
+                  sampled (top_k 50).  Both are one run of the same loop (forward, row-batched selection and row advance enqueued back to back),
+                  so the two legs time the same thing; on commits before "one Orpheus lock-step loop" gen_launch was a host-driven loop of its
+                  own (three copies, two synchronises and, when sampling, up to three launches per row in every step), which is what the
+                  host_driven_* keys of the older recorded files hold
   ragged mix      24 utterances at 8 slots whose lengths spread over 10:1 (RAGGED_LENGTHS): once as consecutive generate_batch groups of 8,
                   once through one session with a look-in every 28 steps; tokens/s and the share of slot-steps that carried a live utterance.
                   A pilot run looks for a stopping id whose first occurrences spread the lengths that way; when the greedy ids of the random
@@ -50,7 +52,7 @@ def step_times(eng, B, prompts, uni, have_session, reps):
     out = {}
     for mode in ("greedy", "sampled"):
         kw = dict(uniforms=uni[:, :WARM + STEPS + 1], **SMP) if mode == "sampled" else {}
-        host, dev = [], []
+        batch, dev = [], []
         for _ in range(reps):
             eng.gen_begin(prompts, WARM + STEPS + 1, NO_STOP, **kw)
             eng.gen_launch(WARM)
@@ -58,10 +60,10 @@ def step_times(eng, B, prompts, uni, have_session, reps):
             t = time.perf_counter()
             eng.gen_launch(STEPS)
             eng.gen_wait()
-            host.append((time.perf_counter() - t) / STEPS * 1e3)
+            batch.append((time.perf_counter() - t) / STEPS * 1e3)
             eng.gen_launch(1)
             assert all(eng.gen_wait()[1])
-        out[mode] = {"host_driven_gen_launch_ms_per_step": round(med(host), 4), "host_driven_runs_ms": [round(x, 4) for x in host]}
+        out[mode] = {"gen_launch_ms_per_step": round(med(batch), 4), "gen_launch_runs_ms": [round(x, 4) for x in batch]}
         if not have_session:
             continue
         for _ in range(reps):
@@ -73,8 +75,8 @@ def step_times(eng, B, prompts, uni, have_session, reps):
             dev.append((time.perf_counter() - t) / STEPS * 1e3)
             assert fin == []
             eng.stream_end()
-        out[mode].update({"device_driven_stream_run_ms_per_step": round(med(dev), 4), "device_driven_runs_ms": [round(x, 4) for x in dev],
-                          "device_over_host": round(med(dev) / med(host), 4)})
+        out[mode].update({"stream_run_ms_per_step": round(med(dev), 4), "stream_run_runs_ms": [round(x, 4) for x in dev],
+                          "stream_run_over_gen_launch": round(med(dev) / med(batch), 4)})
     return out
 
 

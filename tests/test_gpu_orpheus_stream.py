@@ -135,7 +135,7 @@ def _run_session(eng, prompts, n_slots, n_steps, stop_id, uniforms=None, max_new
         assert run < 1000
     assert eng.stream_run(n_steps) == []          # no live rows: returns at once with nothing finished
     eng.stream_end()
-    return out, dict(mid_flight=mid_flight, slot_twice=max(uses) > 1, runs=len(set(end_run)))
+    return out, dict(mid_flight=mid_flight, slot_twice=max(uses) > 1, refilled=sum(u > 1 for u in uses), runs=len(set(end_run)))
 
 
 @pytest.mark.parametrize("wtype", [gguf.F16, gguf.Q4_0])
@@ -165,8 +165,9 @@ def test_session_equals_one_sequence_generations(n_slots, wtype):
     eng.close()
 
 
-def test_session_ends_where_the_one_sequence_generation_ends():
-    """max_new ids, the end of the cache (prompt + max_new > n_ctx) and max_new 0"""
+@functools.lru_cache(maxsize=None)
+def _cache_end_reference():
+    """a short prompt and one that leaves six positions of the cache, with the ids of the eager one-sequence engine"""
     model = synth.build_orpheus(synth.orpheus_tiny(weight_type=gguf.F16))
     cfg = model.cfg
     never = cfg.vocab + NEVER
@@ -177,6 +178,14 @@ def test_session_ends_where_the_one_sequence_generation_ends():
     ref_short, ref_long = single.generate_greedy(short, MAX_NEW, never).tolist(), single.generate_greedy(long_, MAX_NEW, never).tolist()
     ref_one = single.generate_greedy(short, 1, never).tolist()
     single.close()
+    return model, short, long_, ref_short, ref_long, ref_one
+
+
+def test_session_ends_where_the_one_sequence_generation_ends():
+    """max_new ids, the end of the cache (prompt + max_new > n_ctx) and max_new 0"""
+    model, short, long_, ref_short, ref_long, ref_one = _cache_end_reference()
+    cfg = model.cfg
+    never = cfg.vocab + NEVER
     assert len(ref_short) == MAX_NEW and 0 < len(ref_long) < MAX_NEW      # the second one runs into the end of the cache
     eng = hip.OrpheusEngine(cfg, max_seqs=2)
     eng.load(model)
@@ -190,6 +199,93 @@ def test_session_ends_where_the_one_sequence_generation_ends():
     assert eng.stream_run(7) == [(1, 0)]
     assert eng.stream_collect(1, 0).size == 0
     eng.stream_end()
+    eng.close()
+
+
+# ---- the fixed batch: the same loop with every slot admitted at begin ---------------------------------------------------------------------
+def _batch_in_pieces(eng, prompts, max_new, stop_id, k, ref, **kw):
+    """gen_begin, then launches of k steps; after the j-th launch (j = 0: the begin) an utterance whose one-sequence generation has L ids has
+    handed out min(L, 1 + j k) of them and is done exactly when those are all"""
+    eng.gen_begin(prompts, max_new, stop_id, **kw)
+    j = 0
+    while True:
+        ids, done = eng.gen_wait()
+        for u, r in enumerate(ref):
+            want = min(len(r), 1 + j * k)
+            assert ids[u].tolist() == r[:want], (k, j, u)
+            assert bool(done[u]) == (want == len(r)), (k, j, u)
+        if done.all():
+            return j
+        eng.gen_launch(k)
+        j += 1
+        assert j < 100
+
+
+def test_fixed_batch_rows_that_end_inside_a_launch():
+    """tts_hip_orpheus_gen_* at three utterances, launches of 1, 3 and 64 steps (64: more than is left of max_new 14), with the stopping id of
+    test_orpheus_lockstep_batch_equals_single_sequence_generations (some utterances meet it early, others never): the ids are the eager
+    one-sequence ids, nothing is counted after the stopping id, and an utterance is done at the wait of the launch in which it ended."""
+    model, prompts, uni, stop, greedy, stopped, sampled = _reference(3, gguf.F16)
+    cfg = model.cfg
+    never = cfg.vocab + NEVER
+    assert len({len(r) for r in stopped[:3]}) > 1 and max(len(r) for r in stopped[:3]) == MAX_NEW
+    eng = hip.OrpheusEngine(cfg, max_seqs=3)
+    eng.load(model)
+    for k in (1, 3, 64):
+        launches = _batch_in_pieces(eng, prompts[:3], MAX_NEW, stop, k, stopped[:3])
+        assert launches == -(-(MAX_NEW - 1) // k)
+        _batch_in_pieces(eng, prompts[:3], MAX_NEW, never, k, greedy[:3])
+        _batch_in_pieces(eng, prompts[:3], MAX_NEW, never, k, sampled[:3], uniforms=uni[:3], **SMP)
+    assert [g.tolist() for g in eng.generate_batch(prompts[:3], MAX_NEW, stop)] == stopped[:3]
+    eng.close()
+
+
+def test_fixed_batch_ends_where_the_one_sequence_generation_ends():
+    """the end of the cache inside a launch (prompt + max_new > n_ctx), max_new 1 and max_new 0 in a fixed batch"""
+    model, short, long_, ref_short, ref_long, ref_one = _cache_end_reference()
+    cfg = model.cfg
+    never = cfg.vocab + NEVER
+    assert len(ref_short) == MAX_NEW and 0 < len(ref_long) < MAX_NEW
+    eng = hip.OrpheusEngine(cfg, max_seqs=2)
+    eng.load(model)
+    assert [g.tolist() for g in eng.generate_batch([short, long_], MAX_NEW, never)] == [ref_short, ref_long]
+    for k in (1, 4, 64):
+        _batch_in_pieces(eng, [short, long_], MAX_NEW, never, k, [ref_short, ref_long])
+    assert [g.tolist() for g in eng.generate_batch([short, short], 1, never)] == [ref_one, ref_one]
+    assert [g.size for g in eng.generate_batch([short, long_], 0, never)] == [0, 0]
+    eng.gen_begin([short, long_], 0, never)
+    ids, done = eng.gen_wait()
+    assert [i.size for i in ids] == [0, 0] and done.all()
+    eng.close()
+
+
+def test_the_loops_buffers_are_reused_without_a_trace_of_the_last_loop():
+    """One context of seven slots: a sampled fixed batch of 3, a uniform greedy session over all 7 slots (15 utterances: slots are refilled), a
+    mixed session (every other utterance sampled), a greedy fixed batch of 7 with another max_new, and the first call again.  The loop's device
+    buffers stay on the context between them, so every admission has to overwrite what the slot's predecessor left — state, sampler state,
+    record, penalty table, uniforms, ids: every result equals its eager one-sequence reference, and the last equals the first."""
+    model, prompts, uni, stop, greedy, stopped, sampled = _reference(7, gguf.F16)
+    cfg = model.cfg
+    never = cfg.vocab + NEVER
+    eng = hip.OrpheusEngine(cfg, max_seqs=7)
+    eng.load(model)
+    first = [g.tolist() for g in eng.generate_batch(prompts[:3], MAX_NEW, never, uniforms=uni[:3], **SMP)]
+    assert first == sampled[:3]
+    got, facts = _run_session(eng, prompts, 7, 5, stop)
+    assert got == stopped and facts["refilled"] >= 2, facts
+    settings = [SMP if u % 2 == 0 else None for u in range(len(prompts))]
+    eng.stream_begin_mixed(7, MAX_NEW, never)
+    eng.stream_admit_mixed(list(range(7)), prompts[:7], settings[:7], uni[:7])
+    fin = eng.stream_run(64)
+    assert [s for s, _ in fin] == list(range(7))
+    assert [eng.stream_collect(s, c).tolist() for s, c in fin] == [sampled[u] if u % 2 == 0 else greedy[u] for u in range(7)]
+    eng.stream_admit_mixed([0, 1], prompts[7:9], settings[7:9], uni[7:9])      # utterance 7 is greedy in slot 0 after a sampled one, 8 the reverse
+    fin = eng.stream_run(64)
+    assert [eng.stream_collect(s, c).tolist() for s, c in fin] == [greedy[7], sampled[8]]
+    eng.stream_end()
+    assert [g.tolist() for g in eng.generate_batch(prompts[:7], 5, never)] == [r[:5] for r in greedy[:7]]   # greedy: max_new 5 gives the first 5 ids
+    again = [g.tolist() for g in eng.generate_batch(prompts[:3], MAX_NEW, never, uniforms=uni[:3], **SMP)]
+    assert again == first == sampled[:3]
     eng.close()
 
 

@@ -688,13 +688,53 @@ static __global__ __launch_bounds__(128) void attn_gqa_combine_kernel(const floa
     if (aq) q8_block_store(res, (int64_t) r * NH * 128 + h * 128 + t, aq, ad);   // the o projection's activation blocks
 }
 
-// arg-max over a large vocabulary (156 940 logits), sampler::max semantics (src/sampler.cpp:185-204: the first maximum
-// wins).  Stage 1: ARGMAX_PARTS workgroups over contiguous chunks; stage 2: one wave folds the partial results.
+// ------------------------------------------------------------------------------------------------
+// The selection of one token from one row of logits, one body per stage (the __device__ functions below).  Two kernel families call them:
+// the one-row kernels of the one-sequence step (their arguments are baked into its captured graph) and the rows kernels of the lock-step loop.
+//
+// sampler::max (src/sampler.cpp:185-204: the first maximum wins) over a large vocabulary (156 940 logits):
+//   argmax_parts_row    ARGMAX_PARTS workgroups over contiguous chunks;
+//   argmax_fold_row     one wave folds the partial results.
+// sampler::sample (orpheus/model.cpp:389-398, sampler.cpp:3-69 with topk :152-183 and softmax :82-116) for top_k in 1..TOPK_MAXK.  The reference
+// sorts all 156 940 indices by (penalised) value on the host at every step; only the first top_k of that order are ever read, so two stages find them:
+//   topk_parts_row      TOPK_PARTS workgroups, each sorts its slice of the vocabulary (bitonic, 64-bit keys = value descending, index
+//                       ascending — the total order of sample_kernel / smp_key) and keeps its first k keys;
+//   softmax_total_row   top_p < 1 only, see below;
+//   topk_sample_row     one workgroup sorts the TOPK_PARTS * k survivors, takes the first k (the reference's `picks`), and runs the
+//                       rest of sampler::sample exactly as sample_kernel does: softmax over the picks in pick order (sequential fp32
+//                       sum, exp(v / T - top) with top = the penalised maximum / T), inverse-CDF scan against the host-drawn uniform,
+//                       repetition state update (sampler.cpp:57-63).
+// The token sampled last takes part with v / pow(penalty, count) evaluated in double (sampler.cpp:89-90,172-175); pen_table[c] =
+// pow(penalty, c) comes from the host libm.
+// ------------------------------------------------------------------------------------------------
 #define ARGMAX_PARTS 128
+#define TOPK_PARTS 64
+#define TOPK_SLICE 4096   // keys one part sorts: vocabularies up to TOPK_PARTS * TOPK_SLICE = 262 144
+#define TOPK_MAXK 64
+
 __device__ __forceinline__ void argmax_merge(float &best, uint32_t &besti, float ov, uint32_t oi) {
     if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
 }
-static __global__ __launch_bounds__(256) void argmax_parts_kernel(const float *logits, int V, float *pv, uint32_t *pi) {
+__device__ __forceinline__ void bitonic_sort_keys(unsigned long long *keys, int P) {
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+                const int lo = ((t / stride) * (stride << 1)) + (t % stride), hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const unsigned long long a = keys[lo], b = keys[hi];
+                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+__device__ __forceinline__ float smp_key_value(unsigned long long key) {   // inverse of smp_key's value field
+    const unsigned u = ~(unsigned) (key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// logits / pv / pi: the row's (partials [ARGMAX_PARTS]); blockIdx.x is the part
+__device__ __forceinline__ void argmax_parts_row(const float *logits, int V, float *pv, uint32_t *pi) {
     __shared__ float bv[4];
     __shared__ uint32_t bi[4];
     const int chunk = (V + ARGMAX_PARTS - 1) / ARGMAX_PARTS;
@@ -715,110 +755,20 @@ static __global__ __launch_bounds__(256) void argmax_parts_kernel(const float *l
         pi[blockIdx.x] = besti;
     }
 }
-// hist / next_id / next_pos (optional): the device-resident greedy loop feeds the token straight back as the next input
-static __global__ __launch_bounds__(64) void argmax_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, uint32_t *hist, uint32_t *next_id,
-                                                         uint32_t *next_pos) {
+// one wave; thread 0 writes the token to token[0]; every lane returns it
+__device__ __forceinline__ uint32_t argmax_fold_row(const float *pv, const uint32_t *pi, uint32_t *token) {
     float best = -INFINITY;
     uint32_t besti = 0xffffffffu;
     for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[i], pi[i]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if (threadIdx.x == 0) {
-        const uint32_t t = besti == 0xffffffffu ? 0u : besti;   // all -inf / NaN: index 0 like sampler::max
-        token[0] = t;
-        if (hist) hist[0] = t;
-        if (next_id) { next_id[0] = t; next_pos[0] += 1; }
-    }
+    const uint32_t t = besti == 0xffffffffu ? 0u : besti;   // all -inf / NaN: index 0 like sampler::max
+    if (threadIdx.x == 0) token[0] = t;
+    return t;
 }
-
-// the two stages for R rows of logits (lock-step utterances): blockIdx.y = row, logits rows ld floats apart; partials [R][ARGMAX_PARTS]
-static __global__ __launch_bounds__(256) void argmax_rows_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi) {
-    __shared__ float bv[4];
-    __shared__ uint32_t bi[4];
-    const float *lg = logits + (int64_t) blockIdx.y * ld;
-    const int chunk = (V + ARGMAX_PARTS - 1) / ARGMAX_PARTS;
-    const int i0 = blockIdx.x * chunk, i1 = min(V, i0 + chunk);
-    float best = -INFINITY;
-    uint32_t besti = 0xffffffffu;
-    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
-        const float v = lg[i];
-        if (v > best) { best = v; besti = (uint32_t) i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_merge(best, besti, bv[w], bi[w]);
-        pv[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = best;
-        pi[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = besti;
-    }
-}
-static __global__ __launch_bounds__(64) void argmax_rows_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token) {
-    const int r = blockIdx.x;
-    float best = -INFINITY;
-    uint32_t besti = 0xffffffffu;
-    for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[r * ARGMAX_PARTS + i], pi[r * ARGMAX_PARTS + i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if (threadIdx.x == 0) token[r] = besti == 0xffffffffu ? 0u : besti;
-}
-
-// the same fold for a captured step (one graph replayed for every position): the history slot comes from a device counter
-static __global__ __launch_bounds__(64) void argmax_fold_graph_kernel(const float *pv, const uint32_t *pi, uint32_t *token, uint32_t *hist, uint32_t *hist_idx, uint32_t *next_id,
-                                                               uint32_t *next_pos) {
-    float best = -INFINITY;
-    uint32_t besti = 0xffffffffu;
-    for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[i], pi[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if (threadIdx.x == 0) {
-        const uint32_t t = besti == 0xffffffffu ? 0u : besti;
-        token[0] = t;
-        hist[hist_idx[0]] = t;
-        hist_idx[0] += 1;
-        next_id[0] = t;
-        next_pos[0] += 1;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// sampler::sample over the 156 940-logit vocabulary (orpheus/model.cpp:389-398, sampler.cpp:3-69 with topk :152-183 and softmax :82-116)
-// for top_k in 1..TOPK_MAXK (top_p < 1: + softmax_total_kernel, below).  The reference sorts all 156 940 indices by
-// (penalised) value on the host at every step; only the first top_k of that order are ever read, so two stages find them:
-//   topk_parts_kernel   TOPK_PARTS workgroups, each sorts its slice of the vocabulary (bitonic, 64-bit keys = value descending, index
-//                       ascending — the total order of sample_kernel / smp_key) and keeps its first k keys;
-//   topk_sample_kernel  one workgroup sorts the TOPK_PARTS * k survivors, takes the first k (the reference's `picks`), and runs the
-//                       rest of sampler::sample exactly as sample_kernel does: softmax over the picks in pick order (sequential fp32
-//                       sum, exp(v / T - top) with top = the penalised maximum / T), inverse-CDF scan against the host-drawn uniform,
-//                       repetition state update (sampler.cpp:57-63); it then feeds the token back like argmax_fold_*_kernel.
-// The token sampled last takes part with v / pow(penalty, count) evaluated in double (sampler.cpp:89-90,172-175); pen_table[c] =
-// pow(penalty, c) comes from the host libm.
-// ------------------------------------------------------------------------------------------------
-#define TOPK_PARTS 64
-#define TOPK_SLICE 4096   // keys one part sorts: vocabularies up to TOPK_PARTS * TOPK_SLICE = 262 144
-#define TOPK_MAXK 64
-
-__device__ __forceinline__ void bitonic_sort_keys(unsigned long long *keys, int P) {
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-                const int lo = ((t / stride) * (stride << 1)) + (t % stride), hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
-}
-__device__ __forceinline__ float smp_key_value(unsigned long long key) {   // inverse of smp_key's value field
-    const unsigned u = ~(unsigned) (key >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-static __global__ __launch_bounds__(512) void topk_parts_kernel(const float *logits, int V, int k, const double *pen_table, int pen_len, const int32_t *last_id,
-                                                         const uint32_t *rep_count, unsigned long long *cand) {
+// logits / cand: the row's; last_id / rep_count: the sequence's.  pen_table NULL: penalty 1.  The count indexes the table clamped at its last entry.
+__device__ __forceinline__ void topk_parts_row(const float *logits, int V, int k, const double *pen_table, int pen_len, const int32_t *last_id, const uint32_t *rep_count,
+                                               unsigned long long *cand) {
     __shared__ unsigned long long keys[TOPK_SLICE];
     const int chunk = (V + TOPK_PARTS - 1) / TOPK_PARTS;
     const int i0 = (int) blockIdx.x * chunk;
@@ -845,10 +795,10 @@ static __global__ __launch_bounds__(512) void topk_parts_kernel(const float *log
 // exp(v / T - top) / cumsum with cumsum accumulated over the 156 940 entries in index order, in fp32.  The order of an fp32 sum is part of its
 // value, so the total is accumulated here by ONE thread in that order (the exponentials are computed by the whole workgroup, a chunk at a time,
 // into LDS): ~0.4 ms per token — the price of drawing exactly the reference's nucleus on the device instead of shipping 628 KB of logits to
-// the host and sorting them there (~10 ms per token).  `top` is the penalised maximum / T, read off the part winners of topk_parts_kernel.
+// the host and sorting them there (~10 ms per token).  `top` is the penalised maximum / T, read off the part winners of topk_parts_row.
 #define SOFTMAX_CHUNK 8192
-static __global__ __launch_bounds__(1024) void softmax_total_kernel(const float *logits, int V, const unsigned long long *cand, float temperature, const double *pen_table,
-                                                             int pen_len, const int32_t *last_id, const uint32_t *rep_count, float *total_out) {
+__device__ __forceinline__ void softmax_total_row(const float *logits, int V, const unsigned long long *cand, float temperature, const double *pen_table, int pen_len,
+                                                  const int32_t *last_id, const uint32_t *rep_count, float *total_out) {
     __shared__ __attribute__((aligned(16))) float ex[SOFTMAX_CHUNK];
     __shared__ float s_top;
     const bool temp = temperature != 1.0f;
@@ -891,14 +841,11 @@ static __global__ __launch_bounds__(1024) void softmax_total_kernel(const float 
     }
     if (threadIdx.x == 0) total_out[0] = total;
 }
-
-// uniforms[call[0]] is this call's draw; call[0] advances.  hist_idx != NULL: captured step, the history slot is hist[hist_idx[0]++];
-// otherwise hist (may be NULL) is the slot itself.  next_id / next_pos (may be NULL): the token goes straight back as the next input.
-// total (NULL: top_p >= 1): the full-vocabulary softmax total of softmax_total_kernel; then the picks keep their full-vocabulary probabilities
-// exp(v - top) / total, topp() trims them at top_p (sampler.cpp:118-150) and the draw is scaled by the nucleus mass (sampler.cpp:47).
-static __global__ __launch_bounds__(1024) void topk_sample_kernel(const unsigned long long *cand, int k, float temperature, const float *uniforms, uint32_t *call,
-                                                           const double *pen_table, int32_t *last_id, uint32_t *rep_count, uint32_t *token, uint32_t *hist,
-                                                           uint32_t *hist_idx, uint32_t *next_id, uint32_t *next_pos, float top_p = 1.0f, const float *total_in = nullptr) {
+// uniforms[call[0]] is this call's draw; call[0] advances.  total_in (NULL: top_p >= 1): the full-vocabulary softmax total of softmax_total_row;
+// then the picks keep their full-vocabulary probabilities exp(v - top) / total, topp() trims them at top_p (sampler.cpp:118-150) and the draw is
+// scaled by the nucleus mass (sampler.cpp:47).  Thread 0 writes the token to token[0] and returns it (the other threads return 0).
+__device__ __forceinline__ uint32_t topk_sample_row(const unsigned long long *cand, int k, float temperature, const float *uniforms, const double *pen_table, int32_t *last_id,
+                                                    uint32_t *rep_count, uint32_t *call, uint32_t *token, float top_p, const float *total_in) {
     __shared__ unsigned long long keys[TOPK_PARTS * TOPK_MAXK];
     __shared__ float prob[TOPK_MAXK];
     const int n = TOPK_PARTS * k;
@@ -916,321 +863,147 @@ static __global__ __launch_bounds__(1024) void topk_sample_kernel(const unsigned
         prob[threadIdx.x] = keys[threadIdx.x] == ~0ull ? 0.0f : expf(v - top);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int m = k;                            // fewer than k real candidates only when the vocabulary is smaller than k
-        while (m > 1 && keys[m - 1] == ~0ull) m--;
-        float target = uniforms[call[0]];
-        call[0] += 1;
-        float cum = 0.0f;
-        int chosen;
-        if (total_in) {
-            // softmax ran over the whole vocabulary (prob / total_in are the reference's logits[] after it); topp(): the first prefix of the picks
-            // whose mass reaches top_p, the draw scaled by min(mass, top_p)
-            const float total = total_in[0];
-            float mass = 0.0f;
-            int trim = -1;
-            for (int j = 0; j < m; j++) {
-                mass += prob[j] / total;
-                if (mass >= top_p) { trim = j + 1; break; }
-            }
-            if (trim > 0) m = trim;
-            target *= fminf(mass, top_p);
-            chosen = (int) (unsigned) keys[m - 1];
-            for (int j = 0; j < m; j++) {
-                cum += prob[j] / total;
-                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
-            }
-        } else {
-            float total = 0.0f;
-            for (int j = 0; j < m; j++) total += prob[j];
-            chosen = (int) (unsigned) keys[m - 1];
-            for (int j = 0; j < m; j++) {
-                cum += prob[j] / total;
-                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
-            }
+    if (threadIdx.x != 0) return 0u;
+    int m = k;                            // fewer than k real candidates only when the vocabulary is smaller than k
+    while (m > 1 && keys[m - 1] == ~0ull) m--;
+    float target = uniforms[call[0]];
+    call[0] += 1;
+    float cum = 0.0f;
+    int chosen;
+    if (total_in) {
+        // softmax ran over the whole vocabulary (prob / total_in are the reference's logits[] after it); topp(): the first prefix of the picks
+        // whose mass reaches top_p, the draw scaled by min(mass, top_p)
+        const float total = total_in[0];
+        float mass = 0.0f;
+        int trim = -1;
+        for (int j = 0; j < m; j++) {
+            mass += prob[j] / total;
+            if (mass >= top_p) { trim = j + 1; break; }
         }
-        if (pen_table) {
-            uint32_t cnt = rep_count[0];
-            if (last_id[0] != chosen) cnt = 0;
-            last_id[0] = chosen;
-            rep_count[0] = cnt + 1;
+        if (trim > 0) m = trim;
+        target *= fminf(mass, top_p);
+        chosen = (int) (unsigned) keys[m - 1];
+        for (int j = 0; j < m; j++) {
+            cum += prob[j] / total;
+            if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
         }
-        token[0] = (uint32_t) chosen;
-        if (hist_idx) { hist[hist_idx[0]] = (uint32_t) chosen; hist_idx[0] += 1; }
-        else if (hist) hist[0] = (uint32_t) chosen;
-        if (next_id) { next_id[0] = (uint32_t) chosen; next_pos[0] += 1; }
+    } else {
+        float total = 0.0f;
+        for (int j = 0; j < m; j++) total += prob[j];
+        chosen = (int) (unsigned) keys[m - 1];
+        for (int j = 0; j < m; j++) {
+            cum += prob[j] / total;
+            if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
+        }
     }
+    if (pen_table) {
+        uint32_t cnt = rep_count[0];
+        if (last_id[0] != chosen) cnt = 0;
+        last_id[0] = chosen;
+        rep_count[0] = cnt + 1;
+    }
+    token[0] = (uint32_t) chosen;
+    return (uint32_t) chosen;
 }
 
 // ------------------------------------------------------------------------------------------------
-// The selection for the rows of a continuous session (tts_hip_orpheus_stream_*): the kernels above with the row as a grid dimension.
-// Row r stands for cache slot s = row_slot[r] (row_slot == NULL: slot0 + r) and reads that slot's sampler state smp[3 s ..] = {last id,
-// repetition count, call counter} and its stretch of the uniforms (uniforms + s * uni_stride).  slot_state (may be NULL) is the session's
-// per-slot record {count, finished, latest id, position}: a row whose slot is finished selects nothing and its state does not move.
-// Per row the operations and their order are those of the one-row kernels, statement for statement: the ids are bit-identical to n one-row
-// calls (tests/test_gpu_orpheus_stream.py).  cand: [rows][TOPK_PARTS][TOPK_MAXK], total: [rows], token: [rows].
+// The one-row kernels (tts_hip_orpheus_decode, the one-sequence generation and its captured step).  The last stage of either sampler feeds the
+// token back (one thread): hist_idx != NULL: captured step, the history slot is hist[hist_idx[0]++]; otherwise hist (may be NULL) is the slot
+// itself.  next_id / next_pos (may be NULL): the token goes straight back as the next input.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void select_feedback(uint32_t t, uint32_t *hist, uint32_t *hist_idx, uint32_t *next_id, uint32_t *next_pos) {
+    if (hist_idx) { hist[hist_idx[0]] = t; hist_idx[0] += 1; }
+    else if (hist) hist[0] = t;
+    if (next_id) { next_id[0] = t; next_pos[0] += 1; }
+}
+static __global__ __launch_bounds__(256) void argmax_parts_kernel(const float *logits, int V, float *pv, uint32_t *pi) { argmax_parts_row(logits, V, pv, pi); }
+static __global__ __launch_bounds__(64) void argmax_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, uint32_t *hist, uint32_t *hist_idx, uint32_t *next_id,
+                                                         uint32_t *next_pos) {
+    const uint32_t t = argmax_fold_row(pv, pi, token);
+    if (threadIdx.x == 0) select_feedback(t, hist, hist_idx, next_id, next_pos);
+}
+static __global__ __launch_bounds__(512) void topk_parts_kernel(const float *logits, int V, int k, const double *pen_table, int pen_len, const int32_t *last_id,
+                                                         const uint32_t *rep_count, unsigned long long *cand) {
+    topk_parts_row(logits, V, k, pen_table, pen_len, last_id, rep_count, cand);
+}
+static __global__ __launch_bounds__(1024) void softmax_total_kernel(const float *logits, int V, const unsigned long long *cand, float temperature, const double *pen_table,
+                                                             int pen_len, const int32_t *last_id, const uint32_t *rep_count, float *total_out) {
+    softmax_total_row(logits, V, cand, temperature, pen_table, pen_len, last_id, rep_count, total_out);
+}
+static __global__ __launch_bounds__(1024) void topk_sample_kernel(const unsigned long long *cand, int k, float temperature, const float *uniforms, uint32_t *call,
+                                                           const double *pen_table, int32_t *last_id, uint32_t *rep_count, uint32_t *token, uint32_t *hist,
+                                                           uint32_t *hist_idx, uint32_t *next_id, uint32_t *next_pos, float top_p = 1.0f, const float *total_in = nullptr) {
+    const uint32_t t = topk_sample_row(cand, k, temperature, uniforms, pen_table, last_id, rep_count, call, token, top_p, total_in);
+    if (threadIdx.x == 0) select_feedback(t, hist, hist_idx, next_id, next_pos);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The rows kernels (the lock-step loop, tts_hip_orpheus_step_batch, tts_hip_orpheus_sample_logits_rows*): the bodies above with the row as a
+// grid dimension.  Row r stands for cache slot s = row_slot[r] (row_slot == NULL: slot0 + r) and reads that slot's sampler state smp[3 s ..] =
+// {last id, repetition count, call counter}, its stretch of the uniforms (uniforms + s * uni_stride) and its sampler: samp [slots] holds
+// {mode, top_k, temperature, top_p} (mode LLAMA_SLOT_MAX: sampler::max, LLAMA_SLOT_SAMPLE: sampler::sample; samp == NULL: every row is
+// sampler::max) and pen_base [slots][pen_len] one table pow(penalty, count) per slot; a stretch whose first entry is 0 stands for penalty 1,
+// i.e. a NULL table (pow(penalty, 0) is 1 in every built stretch).  slot_state (may be NULL) is the loop's per-slot record {count, finished,
+// latest id, position}: a row whose slot is finished selects nothing and its state does not move.  A row of the other mode returns at once like
+// a finished one: the arg-max pair selects for the greedy rows, the top-k kernels for the sampled rows, the total only for sampled rows with
+// top_p < 1, all into the same token[rows].  cand: [rows][TOPK_PARTS][TOPK_MAXK], total: [rows], partials: [rows][ARGMAX_PARTS].
 // ------------------------------------------------------------------------------------------------
 #define LLAMA_SLOT_STATE 4   // uint32 per slot: [0] ids so far, [1] finished, [2] latest id, [3] position of the latest forward row
-__device__ __forceinline__ uint32_t rows_slot(const uint32_t *row_slot, int slot0, int r) { return row_slot ? row_slot[r] : (uint32_t) (slot0 + r); }
-__device__ __forceinline__ bool rows_finished(const uint32_t *slot_state, uint32_t s) { return slot_state && slot_state[(size_t) s * LLAMA_SLOT_STATE + 1] != 0; }
-
-// The bodies, shared by the uniform kernels (parameters are kernel arguments) and the mixed ones (parameters come from the row's slot, below).
-__device__ __forceinline__ void argmax_parts_row(const float *logits, int V, int ld, float *pv, uint32_t *pi) {
-    __shared__ float bv[4];
-    __shared__ uint32_t bi[4];
-    const float *lg = logits + (int64_t) blockIdx.y * ld;
-    const int chunk = (V + ARGMAX_PARTS - 1) / ARGMAX_PARTS;
-    const int i0 = blockIdx.x * chunk, i1 = min(V, i0 + chunk);
-    float best = -INFINITY;
-    uint32_t besti = 0xffffffffu;
-    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
-        const float v = lg[i];
-        if (v > best) { best = v; besti = (uint32_t) i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_merge(best, besti, bv[w], bi[w]);
-        pv[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = best;
-        pi[blockIdx.y * ARGMAX_PARTS + blockIdx.x] = besti;
-    }
-}
-__device__ __forceinline__ void argmax_fold_row(const float *pv, const uint32_t *pi, uint32_t *token, int r) {
-    float best = -INFINITY;
-    uint32_t besti = 0xffffffffu;
-    for (int i = threadIdx.x; i < ARGMAX_PARTS; i += 64) argmax_merge(best, besti, pv[r * ARGMAX_PARTS + i], pi[r * ARGMAX_PARTS + i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_merge(best, besti, __shfl_xor(best, o), __shfl_xor(besti, o));
-    if (threadIdx.x == 0) token[r] = besti == 0xffffffffu ? 0u : besti;
-}
-// logits / cand: the row's; last_id / rep_count: the slot's
-__device__ __forceinline__ void topk_parts_row(const float *logits, int V, int k, const double *pen_table, int pen_len, const int32_t *last_id, const uint32_t *rep_count,
-                                               unsigned long long *cand) {
-    __shared__ unsigned long long keys[TOPK_SLICE];
-    const int chunk = (V + TOPK_PARTS - 1) / TOPK_PARTS;
-    const int i0 = (int) blockIdx.x * chunk;
-    const int last = pen_table ? last_id[0] : -1;
-    for (int j = threadIdx.x; j < TOPK_SLICE; j += blockDim.x) {
-        const int i = i0 + j;
-        unsigned long long key = ~0ull;
-        if (j < chunk && i < V) {
-            float v = logits[i];
-            if (i == last) {
-                const uint32_t cnt = rep_count[0];
-                v = (float) ((double) v / pen_table[cnt < (uint32_t) pen_len ? cnt : (uint32_t) pen_len - 1]);
-            }
-            key = smp_key(v, i);
-        }
-        keys[j] = key;
-    }
-    __syncthreads();
-    bitonic_sort_keys(keys, TOPK_SLICE);
-    for (int j = threadIdx.x; j < k; j += blockDim.x) cand[(int) blockIdx.x * TOPK_MAXK + j] = keys[j];
-}
-__device__ __forceinline__ void softmax_total_row(const float *logits, int V, const unsigned long long *cand, float temperature, const double *pen_table, int pen_len,
-                                                  const int32_t *last_id, const uint32_t *rep_count, float *total_out) {
-    __shared__ __attribute__((aligned(16))) float ex[SOFTMAX_CHUNK];
-    __shared__ float s_top;
-    const bool temp = temperature != 1.0f;
-    if (threadIdx.x == 0) {
-        unsigned long long best = ~0ull;
-        for (int p = 0; p < TOPK_PARTS; p++) best = cand[p * TOPK_MAXK] < best ? cand[p * TOPK_MAXK] : best;
-        float top = smp_key_value(best);
-        if (temp) top /= temperature;
-        s_top = top;
-    }
-    __syncthreads();
-    const float top = s_top;
-    const int last = pen_table ? last_id[0] : -1;
-    float total = 0.0f;
-    for (int c0 = 0; c0 < V; c0 += SOFTMAX_CHUNK) {
-        const int n = min(SOFTMAX_CHUNK, V - c0);
-        for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            const int i = c0 + j;
-            float v = logits[i];
-            if (i == last) {
-                const uint32_t cnt = rep_count[0];
-                v = (float) ((double) v / pen_table[cnt < (uint32_t) pen_len ? cnt : (uint32_t) pen_len - 1]);
-            }
-            if (temp) v /= temperature;
-            ex[j] = expf(v - top);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int j = 0;
-            for (; j + 64 <= n; j += 64) {
-                float4 e[16];
-#pragma unroll
-                for (int q = 0; q < 16; q++) e[q] = *(const float4 *) (ex + j + 4 * q);
-#pragma unroll
-                for (int q = 0; q < 16; q++) { total += e[q].x; total += e[q].y; total += e[q].z; total += e[q].w; }
-            }
-            for (; j < n; j++) total += ex[j];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total_out[0] = total;
-}
-// uniforms: the slot's stretch; total_in (NULL: top_p >= 1): the row's softmax total; token: the row's
-__device__ __forceinline__ void topk_sample_row(const unsigned long long *cand, int k, float temperature, const float *uniforms, const double *pen_table, int32_t *last_id,
-                                                uint32_t *rep_count, uint32_t *call, uint32_t *token, float top_p, const float *total_in) {
-    __shared__ unsigned long long keys[TOPK_PARTS * TOPK_MAXK];
-    __shared__ float prob[TOPK_MAXK];
-    const int n = TOPK_PARTS * k;
-    int P = 1;
-    while (P < n) P <<= 1;
-    for (int j = threadIdx.x; j < P; j += blockDim.x) keys[j] = j < n ? cand[(j / k) * TOPK_MAXK + (j % k)] : ~0ull;
-    __syncthreads();
-    bitonic_sort_keys(keys, P);
-    const bool temp = temperature != 1.0f;
-    float top = smp_key_value(keys[0]);
-    if (temp) top /= temperature;
-    if ((int) threadIdx.x < k) {
-        float v = smp_key_value(keys[threadIdx.x]);
-        if (temp) v /= temperature;
-        prob[threadIdx.x] = keys[threadIdx.x] == ~0ull ? 0.0f : expf(v - top);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int m = k;
-        while (m > 1 && keys[m - 1] == ~0ull) m--;
-        float target = uniforms[call[0]];
-        call[0] += 1;
-        float cum = 0.0f;
-        int chosen;
-        if (total_in) {
-            const float total = total_in[0];
-            float mass = 0.0f;
-            int trim = -1;
-            for (int j = 0; j < m; j++) {
-                mass += prob[j] / total;
-                if (mass >= top_p) { trim = j + 1; break; }
-            }
-            if (trim > 0) m = trim;
-            target *= fminf(mass, top_p);
-            chosen = (int) (unsigned) keys[m - 1];
-            for (int j = 0; j < m; j++) {
-                cum += prob[j] / total;
-                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
-            }
-        } else {
-            float total = 0.0f;
-            for (int j = 0; j < m; j++) total += prob[j];
-            chosen = (int) (unsigned) keys[m - 1];
-            for (int j = 0; j < m; j++) {
-                cum += prob[j] / total;
-                if (target <= cum || j + 1 >= m) { chosen = (int) (unsigned) keys[j]; break; }
-            }
-        }
-        if (pen_table) {
-            uint32_t cnt = rep_count[0];
-            if (last_id[0] != chosen) cnt = 0;
-            last_id[0] = chosen;
-            rep_count[0] = cnt + 1;
-        }
-        token[0] = (uint32_t) chosen;
-    }
-}
-
-static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const uint32_t *row_slot, int slot0,
-                                                                 const uint32_t *slot_state) {
-    if (rows_finished(slot_state, rows_slot(row_slot, slot0, blockIdx.y))) return;
-    argmax_parts_row(logits, V, ld, pv, pi);
-}
-static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const uint32_t *row_slot, int slot0,
-                                                               const uint32_t *slot_state) {
-    const int r = blockIdx.x;
-    if (rows_finished(slot_state, rows_slot(row_slot, slot0, r))) return;
-    argmax_fold_row(pv, pi, token, r);
-}
-
-// grid (TOPK_PARTS, rows)
-static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float *logits_base, int V, int ld, int k, const double *pen_table, int pen_len, const uint32_t *smp,
-                                                              unsigned long long *cand_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    topk_parts_row(logits_base + (int64_t) r * ld, V, k, pen_table, pen_len, (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1,
-                   cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK);
-}
-
-// grid (1, rows)
-static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base, float temperature,
-                                                                  const double *pen_table, int pen_len, const uint32_t *smp, float *total_base, const uint32_t *row_slot,
-                                                                  int slot0, const uint32_t *slot_state) {
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    softmax_total_row(logits_base + (int64_t) r * ld, V, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, temperature, pen_table, pen_len,
-                      (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, total_base + r);
-}
-
-// grid (1, rows); the row's draw is uniforms[s * uni_stride + call counter of s], which advances
-static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const unsigned long long *cand_base, int k, float temperature, const float *uniforms, int64_t uni_stride,
-                                                                const double *pen_table, uint32_t *smp, uint32_t *token, float top_p, const float *total_base,
-                                                                const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
-    const int r = blockIdx.y;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s)) return;
-    topk_sample_row(cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, k, temperature, uniforms + (int64_t) s * uni_stride, pen_table, (int32_t *) (smp + (size_t) 3 * s),
-                    smp + (size_t) 3 * s + 1, smp + (size_t) 3 * s + 2, token + r, top_p, total_base ? total_base + r : nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The mixed session (tts_hip_orpheus_stream_begin_mixed): every slot carries its own sampler.  samp [n_slots] holds {mode, top_k, temperature, top_p}
-// (mode LLAMA_SLOT_MAX: sampler::max, LLAMA_SLOT_SAMPLE: sampler::sample) and pen_base [n_slots][pen_len] one stage_penalty table per slot; a stretch
-// whose first entry is 0 stands for penalty 1, i.e. the NULL table of the kernels above (pow(penalty, 0) is 1 in every built stretch).  Each kernel
-// is the uniform one with k, temperature, top_p and the table read from the row's slot: the same body, so the same ids.  A row of the other mode
-// returns at once like a finished one: the arg-max pair selects for the greedy rows, the top-k kernels for the sampled rows, the total only for
-// sampled rows with top_p < 1, all into the same token[rows].
-// ------------------------------------------------------------------------------------------------
 #define LLAMA_SLOT_MAX 0u
 #define LLAMA_SLOT_SAMPLE 1u
 struct llama_slot_sampler { uint32_t mode, top_k; float temperature, top_p; };
+__device__ __forceinline__ uint32_t rows_slot(const uint32_t *row_slot, int slot0, int r) { return row_slot ? row_slot[r] : (uint32_t) (slot0 + r); }
+// the row of slot s has nothing to select in a kernel of `mode`
+__device__ __forceinline__ bool rows_idle(const uint32_t *slot_state, const llama_slot_sampler *samp, uint32_t s, uint32_t mode) {
+    if (slot_state && slot_state[(size_t) s * LLAMA_SLOT_STATE + 1] != 0) return true;
+    return (samp ? samp[s].mode : LLAMA_SLOT_MAX) != mode;
+}
 __device__ __forceinline__ const double *slot_penalty(const double *pen_base, int pen_len, uint32_t s) {
     const double *t = pen_base + (size_t) s * pen_len;
     return t[0] != 0.0 ? t : nullptr;
 }
 
-static __global__ __launch_bounds__(256) void argmax_slots_parts_mixed_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const llama_slot_sampler *samp,
-                                                                       const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
-    const uint32_t s = rows_slot(row_slot, slot0, blockIdx.y);
-    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_MAX) return;
-    argmax_parts_row(logits, V, ld, pv, pi);
+// grid (ARGMAX_PARTS, rows); logits rows ld floats apart
+static __global__ __launch_bounds__(256) void argmax_slots_parts_kernel(const float *logits, int V, int ld, float *pv, uint32_t *pi, const llama_slot_sampler *samp,
+                                                                 const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+    const int r = blockIdx.y;
+    if (rows_idle(slot_state, samp, rows_slot(row_slot, slot0, r), LLAMA_SLOT_MAX)) return;
+    argmax_parts_row(logits + (int64_t) r * ld, V, pv + r * ARGMAX_PARTS, pi + r * ARGMAX_PARTS);
 }
-static __global__ __launch_bounds__(64) void argmax_slots_fold_mixed_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const llama_slot_sampler *samp,
-                                                                     const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+// grid (rows)
+static __global__ __launch_bounds__(64) void argmax_slots_fold_kernel(const float *pv, const uint32_t *pi, uint32_t *token, const llama_slot_sampler *samp,
+                                                               const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
     const int r = blockIdx.x;
-    const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_MAX) return;
-    argmax_fold_row(pv, pi, token, r);
+    if (rows_idle(slot_state, samp, rows_slot(row_slot, slot0, r), LLAMA_SLOT_MAX)) return;
+    argmax_fold_row(pv + r * ARGMAX_PARTS, pi + r * ARGMAX_PARTS, token + r);
 }
-static __global__ __launch_bounds__(512) void topk_parts_rows_mixed_kernel(const float *logits_base, int V, int ld, const llama_slot_sampler *samp, const double *pen_base,
-                                                                    int pen_len, const uint32_t *smp, unsigned long long *cand_base, const uint32_t *row_slot, int slot0,
-                                                                    const uint32_t *slot_state) {
+// grid (TOPK_PARTS, rows)
+static __global__ __launch_bounds__(512) void topk_parts_rows_kernel(const float *logits_base, int V, int ld, const llama_slot_sampler *samp, const double *pen_base, int pen_len,
+                                                              const uint32_t *smp, unsigned long long *cand_base, const uint32_t *row_slot, int slot0,
+                                                              const uint32_t *slot_state) {
     const int r = blockIdx.y;
     const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE) return;
+    if (rows_idle(slot_state, samp, s, LLAMA_SLOT_SAMPLE)) return;
     topk_parts_row(logits_base + (int64_t) r * ld, V, (int) samp[s].top_k, slot_penalty(pen_base, pen_len, s), pen_len, (const int32_t *) (smp + (size_t) 3 * s),
                    smp + (size_t) 3 * s + 1, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK);
 }
-static __global__ __launch_bounds__(1024) void softmax_total_rows_mixed_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base,
-                                                                        const llama_slot_sampler *samp, const double *pen_base, int pen_len, const uint32_t *smp,
-                                                                        float *total_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+// grid (1, rows)
+static __global__ __launch_bounds__(1024) void softmax_total_rows_kernel(const float *logits_base, int V, int ld, const unsigned long long *cand_base, const llama_slot_sampler *samp,
+                                                                  const double *pen_base, int pen_len, const uint32_t *smp, float *total_base, const uint32_t *row_slot,
+                                                                  int slot0, const uint32_t *slot_state) {
     const int r = blockIdx.y;
     const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE || !(samp[s].top_p < 1.0f)) return;
+    if (rows_idle(slot_state, samp, s, LLAMA_SLOT_SAMPLE) || !(samp[s].top_p < 1.0f)) return;
     softmax_total_row(logits_base + (int64_t) r * ld, V, cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, samp[s].temperature, slot_penalty(pen_base, pen_len, s), pen_len,
                       (const int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, total_base + r);
 }
-static __global__ __launch_bounds__(1024) void topk_sample_rows_mixed_kernel(const unsigned long long *cand_base, const llama_slot_sampler *samp, const float *uniforms,
-                                                                      int64_t uni_stride, const double *pen_base, int pen_len, uint32_t *smp, uint32_t *token,
-                                                                      const float *total_base, const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
+// grid (1, rows); the row's draw is uniforms[s * uni_stride + call counter of s], which advances
+static __global__ __launch_bounds__(1024) void topk_sample_rows_kernel(const unsigned long long *cand_base, const llama_slot_sampler *samp, const float *uniforms, int64_t uni_stride,
+                                                                const double *pen_base, int pen_len, uint32_t *smp, uint32_t *token, const float *total_base,
+                                                                const uint32_t *row_slot, int slot0, const uint32_t *slot_state) {
     const int r = blockIdx.y;
     const uint32_t s = rows_slot(row_slot, slot0, r);
-    if (rows_finished(slot_state, s) || samp[s].mode != LLAMA_SLOT_SAMPLE) return;
+    if (rows_idle(slot_state, samp, s, LLAMA_SLOT_SAMPLE)) return;
     const float top_p = samp[s].top_p;
     topk_sample_row(cand_base + (size_t) r * TOPK_PARTS * TOPK_MAXK, (int) samp[s].top_k, samp[s].temperature, uniforms + (int64_t) s * uni_stride,
                     slot_penalty(pen_base, pen_len, s), (int32_t *) (smp + (size_t) 3 * s), smp + (size_t) 3 * s + 1, smp + (size_t) 3 * s + 2, token + r, top_p,

@@ -177,6 +177,7 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "attn_rows_min") c->attn_rows_min = std::max(0, v);
     else if (k == "attn_fused") c->attn_fused = v != 0;
     else if (k == "attn_split") c->attn_split_max = std::max(1, std::min(16, v));
+    else if (k == "orpheus_batch_run") c->l_batch_run = (uint32_t) std::max(1, std::min(1024, v));
     else if (k == "attn_fold") c->attn_fold = v != 0;
     else if (k == "attn_wave") c->attn_wave = v != 0;
     else if (k == "cross_fold") c->cross_fold = v != 0;
@@ -250,7 +251,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     free_dev(c->l_x); free_dev(c->l_xn); free_dev(c->l_qkv); free_dev(c->l_att); free_dev(c->l_gu); free_dev(c->l_g); free_dev(c->l_logits); free_dev(c->l_parts);
     free_dev(c->attn_part); free_dev(c->kk_stuck); free_dev(c->kk_pool);
     free_dev(c->l_kc); free_dev(c->l_vc); free_dev(c->l_ids); free_dev(c->l_pos); free_dev(c->l_tok);
-    free_dev(c->l_seq); free_dev(c->l_btok); free_dev(c->l_bpi); free_dev(c->l_bsmp); free_dev(c->l_bpv);
+    free_dev(c->l_seq); free_dev(c->l_btok); free_dev(c->l_bpi); free_dev(c->l_bpv);
     for (void *p : c->q4_bufs) free_dev(p);
     for (float *p : {c->di_ex, c->di_exn, c->di_eqkv, c->di_eatt, c->di_egu, c->di_eg, c->di_ek, c->di_ev, c->di_ckv, c->di_ck, c->di_cv, c->di_k, c->di_v, c->di_x,
                      c->di_xn, c->di_qkv, c->di_q, c->di_att, c->di_gu, c->di_g, c->di_parts, c->di_logits, c->di_guided})
@@ -264,7 +265,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     if (c->h_in) (void) hipHostFree(c->h_in);
     if (c->h_out) (void) hipHostFree(c->h_out);
     if (c->h_hist) (void) hipHostFree(c->h_hist);
-    free_dev(c->ls.state); free_dev(c->ls.tokens); free_dev(c->ls.smp); free_dev(c->ls.uni); free_dev(c->ls.cand); free_dev(c->ls.total);
+    free_dev(c->ls.state); free_dev(c->ls.tokens); free_dev(c->ls.smp); free_dev(c->ls.uni); free_dev(c->ls.cand); free_dev(c->ls.total); free_dev(c->ls.samp); free_dev(c->ls.pen);
     if (c->ls.h_state) (void) hipHostFree(c->ls.h_state);
     free_dev(c->t5_bucket); free_dev(c->t5_x); free_dev(c->t5_qkv); free_dev(c->t5_att); free_dev(c->t5_ug); free_dev(c->t5_g); free_dev(c->t5_y); free_dev(c->t5_ids); free_dev(c->logits); free_dev(c->part); free_dev(c->attn_cnt); free_dev(c->b1_stamps); free_dev(c->dbg); free_dev(c->d_ids); free_dev(c->d_pos);
     free_dev(c->d_seq); free_dev(c->d_gather); free_dev(c->d_tok); free_dev(c->d_step); free_dev(c->d_steps_done); free_dev(c->d_tokens_out);

@@ -1005,7 +1005,6 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         CHK(dmalloc(&c->l_btok, S));
         CHK(dmalloc(&c->l_bpv, S * ARGMAX_PARTS));
         CHK(dmalloc(&c->l_bpi, S * ARGMAX_PARTS));
-        CHK(dmalloc(&c->l_bsmp, S * 3));
         CHK(dmalloc(&c->dbg, (size_t) R * std::max(H, F)));
         CHK(dmalloc(&c->aq, (size_t) R * std::max(std::max(H, F), c->NH * (int) c->lm.head_dim)));
         CHK(dmalloc(&c->ad, (size_t) R * std::max(std::max(H, F), c->NH * (int) c->lm.head_dim) / 32 + 1));

@@ -160,7 +160,7 @@ struct tts_hip_ctx {
     float *l_x = nullptr, *l_xn = nullptr, *l_qkv = nullptr, *l_att = nullptr, *l_gu = nullptr, *l_g = nullptr, *l_logits = nullptr, *l_parts = nullptr;
     float *l_kc = nullptr, *l_vc = nullptr;
     uint32_t *l_ids = nullptr, *l_pos = nullptr, *l_tok = nullptr;
-    uint32_t *l_seq = nullptr, *l_btok = nullptr, *l_bpi = nullptr, *l_bsmp = nullptr;   // lock-step utterances: row -> cache slot, selected tokens [rows], arg-max partials, sampler state [utterance][3]
+    uint32_t *l_seq = nullptr, *l_btok = nullptr, *l_bpi = nullptr;   // lock-step utterances: row -> cache slot, selected tokens [rows], arg-max partials
     float *l_bpv = nullptr;
     int l_pending = 0;
     int64_t l_pstride = 0;   // floats between the pending slabs (0: RMAX * H)
@@ -246,39 +246,45 @@ struct tts_hip_ctx {
     float *s_out = nullptr, *h_out = nullptr;
     size_t s_in_cap = 0, s_out_cap = 0;
     struct { bool active = false; float *pcm_out = nullptr; size_t n = 0; } snac_pending;   // between _decode_windows_begin and _end
-    // ---- Orpheus generation in pieces (tts_hip_orpheus_gen_begin / _launch / _wait) ----
+    // ---- Orpheus generation in pieces (tts_hip_orpheus_gen_begin / _launch / _wait), one sequence: the captured step; several utterances are ls in BATCH mode ----
     struct LlamaGen {
-        bool active = false, lockstep = false, sampled = false;
-        uint32_t n_utt = 0, max_new = 0, stop_id = 0;
+        bool active = false, sampled = false, done = false;
+        uint32_t max_new = 0, stop_id = 0;
         tts_hip_sampling sp{};
-        uint32_t pending = 0;                       // one sequence: steps enqueued by gen_launch that no gen_wait has read yet
-        std::vector<uint32_t> pos, cur, live;       // per utterance: next position, latest id; utterances still generating
-        std::vector<std::vector<uint32_t>> toks;    // ids so far
-        std::vector<uint32_t> handed;               // ... of which a gen_wait has handed out
-        std::vector<uint8_t> done;
+        uint32_t pending = 0;                       // steps enqueued by gen_launch that no gen_wait has read yet
+        uint32_t pos = 0, cur = 0;                  // next position, latest id
+        std::vector<uint32_t> toks;                 // ids so far
+        uint32_t handed = 0;                        // ... of which a gen_wait has handed out
     } lg;
-    // ---- Orpheus continuous session (tts_hip_orpheus_stream_*): per-slot state on the device, the host keeps the copy of the last look-in ----
+    // ---- The Orpheus lock-step loop: per-slot state on the device, the host keeps the copy of the last look-in.  One loop, two ways in.  BATCH
+    // (tts_hip_orpheus_gen_begin / _launch / _wait at n_utt > 1, tts_hip_orpheus_generate_batch): slots 0 .. n-1, all admitted at begin.  SESSION
+    // (tts_hip_orpheus_stream_*): admissions fill the slots, reports and collections free them again.  The device buffers stay on the context from
+    // one loop to the next (cap_slots x cap_new) and grow when a begin asks for more ----
     struct LlamaStream {
-        bool active = false, sampled = false;
-        bool mixed = false;                         // begin_mixed: every slot carries its own sampler (samp / pen below), sp is unused
+        enum Mode : uint8_t { NONE = 0, BATCH = 1, SESSION = 2 };
+        Mode mode = NONE;
+        bool sampled = false;
+        bool mixed = false;                         // begin_mixed: the admissions bring a sampler per utterance; otherwise every admission takes sp (sampled) or sampler::max
         uint32_t n_slots = 0, max_new = 0, stop_id = 0;
         tts_hip_sampling sp{};
-        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished at admission, the next stream_run reports it
+        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished, not yet reported (SESSION) / done (BATCH)
         std::vector<uint8_t> slot;                  // per slot, one of the above
         std::vector<uint32_t> count, cur, pos;      // per slot at the last look-in: ids so far, latest id, its position
+        std::vector<uint32_t> handed;               // BATCH: ids of the slot a gen_wait has handed out
         std::vector<uint32_t> rows;                 // live slots in slot order (= the rows of the next run)
-        uint32_t *state = nullptr;                  // device [n_slots][LLAMA_SLOT_STATE]
-        uint32_t *tokens = nullptr;                 // device [n_slots][max_new]
-        uint32_t *smp = nullptr;                    // device [n_slots][3] sampler state
-        float *uni = nullptr;                       // device [n_slots][max_new]
-        unsigned long long *cand = nullptr;         // device [n_slots][TOPK_PARTS][TOPK_MAXK]
-        float *total = nullptr;                     // device [n_slots]
-        uint32_t *h_state = nullptr;                // pinned [n_slots][LLAMA_SLOT_STATE]
-        // mixed session: per slot, what its utterance samples with
-        std::vector<uint8_t> slot_sampled, slot_nucleus;   // sampler::sample / ... with top_p < 1
-        void *samp = nullptr;                       // device [n_slots] llama_slot_sampler
-        double *pen = nullptr;                      // device [n_slots][max_new] pow(penalty, count); first entry 0: penalty 1
+        std::vector<uint8_t> slot_sampled, slot_nucleus;   // per slot, what its occupant selects with: sampler::sample / ... with top_p < 1
+        size_t cap_slots = 0, cap_new = 0;          // what the buffers below hold
+        uint32_t *state = nullptr;                  // device [slots][LLAMA_SLOT_STATE]
+        uint32_t *tokens = nullptr;                 // device [slots][max_new]
+        uint32_t *smp = nullptr;                    // device [slots][3] sampler state
+        float *uni = nullptr;                       // device [slots][max_new]
+        unsigned long long *cand = nullptr;         // device [slots][TOPK_PARTS][TOPK_MAXK]
+        float *total = nullptr;                     // device [slots]
+        uint32_t *h_state = nullptr;                // pinned [slots][LLAMA_SLOT_STATE]
+        void *samp = nullptr;                       // device [slots] llama_slot_sampler
+        double *pen = nullptr;                      // device [slots][max_new] pow(penalty, count); first entry 0: penalty 1
     } ls;
+    uint32_t l_batch_run = 7;     // tune("orpheus_batch_run"): steps per launch of tts_hip_orpheus_generate_batch: padding rows against look-ins, 7 / 14 / 28 / 56 measured (DESIGN)
     uint32_t *h_hist = nullptr;   // pinned: the ids of the steps of one gen_launch
     size_t h_hist_cap = 0;
     // ---- T5 voice-prompt encoder context (tts_hip_t5_create) ----

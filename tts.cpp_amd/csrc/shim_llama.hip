@@ -272,7 +272,7 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
 
 // between a tts_hip_orpheus_gen_launch and its gen_wait the steps may still be running on the stream: nothing else touches the context
 static int llama_gen_idle(const tts_hip_ctx *c, const char *what) {
-    if (c->ls.active) return set_err("%s: a continuous session is open on this context (tts_hip_orpheus_stream_end first)", what);
+    if (c->ls.mode == tts_hip_ctx::LlamaStream::SESSION) return set_err("%s: a continuous session is open on this context (tts_hip_orpheus_stream_end first)", what);
     if (c->lg.active && c->lg.pending) return set_err("%s: the steps of a tts_hip_orpheus_gen_launch are under way (tts_hip_orpheus_gen_wait first)", what);
     return 0;
 }
@@ -296,7 +296,7 @@ extern "C" int tts_hip_orpheus_decode(tts_hip_ctx *c, const uint32_t *ids, uint3
         hipLaunchKernelGGL(argmax_parts_kernel, dim3(ARGMAX_PARTS), dim3(256), 0, c->stream, (const float *) c->l_logits, c->l_V, pv, pi);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(argmax_fold_kernel, dim3(1), dim3(64), 0, c->stream, (const float *) pv, (const uint32_t *) pi, c->l_tok, (uint32_t *) nullptr,
-                           (uint32_t *) nullptr, (uint32_t *) nullptr);
+                           (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(token_out, c->l_tok, 4, hipMemcpyDeviceToHost, c->stream));
     }
@@ -313,11 +313,8 @@ static int llama_select(tts_hip_ctx *c, const tts_hip_sampling *sp, bool capture
     if (!sp) {
         hipLaunchKernelGGL(argmax_parts_kernel, dim3(ARGMAX_PARTS), dim3(256), 0, c->stream, (const float *) c->l_logits, c->l_V, pv, pi);
         HIPCHK(hipGetLastError());
-        if (captured)
-            hipLaunchKernelGGL(argmax_fold_graph_kernel, dim3(1), dim3(64), 0, c->stream, (const float *) pv, (const uint32_t *) pi, c->l_tok, hist, hist_idx, c->l_ids, c->l_pos);
-        else
-            hipLaunchKernelGGL(argmax_fold_kernel, dim3(1), dim3(64), 0, c->stream, (const float *) pv, (const uint32_t *) pi, c->l_tok, hist_slot,
-                               feed ? c->l_ids : (uint32_t *) nullptr, feed ? c->l_pos : (uint32_t *) nullptr);
+        hipLaunchKernelGGL(argmax_fold_kernel, dim3(1), dim3(64), 0, c->stream, (const float *) pv, (const uint32_t *) pi, c->l_tok, captured ? hist : hist_slot,
+                           captured ? hist_idx : (uint32_t *) nullptr, (captured || feed) ? c->l_ids : (uint32_t *) nullptr, (captured || feed) ? c->l_pos : (uint32_t *) nullptr);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -357,11 +354,11 @@ static int check_llama_sampling(const tts_hip_ctx *c, const tts_hip_sampling *sp
 // generate_from_batch (:378-392) with sampler::max (sp == NULL) or sampler::sample (sp, uniforms[max_new]), one sequence, in pieces:
 // begin = the prompt and the first selection, launch = up to n_steps replays of the captured step, wait = look at their ids.
 // An utterance ends once its last id is the stopping token, max_new ids exist or the cache is full.
-static void llama_gen_emit(tts_hip_ctx *c, uint32_t u, uint32_t tok) {
+static void llama_gen_emit(tts_hip_ctx *c, uint32_t tok) {
     auto &g = c->lg;
-    g.toks[u].push_back(tok);
-    g.cur[u] = tok;
-    if (tok == g.stop_id || g.toks[u].size() >= g.max_new || g.pos[u] >= c->lm.n_ctx) g.done[u] = 1;
+    g.toks.push_back(tok);
+    g.cur = tok;
+    if (tok == g.stop_id || g.toks.size() >= g.max_new || g.pos >= c->lm.n_ctx) g.done = true;
 }
 
 static int llama_gen_begin_one(tts_hip_ctx *c, const char *what, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp,
@@ -370,10 +367,10 @@ static int llama_gen_begin_one(tts_hip_ctx *c, const char *what, const uint32_t 
     g.active = false;
     if (!prompt || n_prompt == 0) return set_err("%s: null argument", what);
     HIPCHK(hipSetDevice(c->device));
-    g.lockstep = false; g.sampled = sp != nullptr; g.n_utt = 1; g.max_new = max_new; g.stop_id = stop_id; g.pending = 0;
+    g.sampled = sp != nullptr; g.max_new = max_new; g.stop_id = stop_id; g.pending = 0;
     if (sp) g.sp = *sp;
-    g.pos.assign(1, n_prompt); g.cur.assign(1, 0); g.toks.assign(1, {}); g.handed.assign(1, 0); g.done.assign(1, 0); g.live.clear();
-    if (max_new == 0) { g.done[0] = 1; g.active = true; return 0; }
+    g.pos = n_prompt; g.cur = 0; g.toks.clear(); g.handed = 0; g.done = false;
+    if (max_new == 0) { g.done = true; g.active = true; return 0; }
     if (sp) {
         CHK(check_llama_sampling(c, sp, what));
         if (!uniforms) return set_err("%s: null uniforms", what);
@@ -401,7 +398,7 @@ static int llama_gen_begin_one(tts_hip_ctx *c, const char *what, const uint32_t 
         HIPCHK(hipMemcpyAsync(&tok, c->l_tok, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    llama_gen_emit(c, 0, tok);
+    llama_gen_emit(c, tok);
     g.active = true;
     return 0;
 }
@@ -413,10 +410,10 @@ static int llama_gen_begin_one(tts_hip_ctx *c, const char *what, const uint32_t 
 static int llama_gen_launch_one(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
     auto &g = c->lg;
     if (g.pending) return set_err("%s: the steps of the last gen_launch have not been looked at (gen_wait)", what);
-    if (g.done[0] || n_steps == 0) return 0;
+    if (g.done || n_steps == 0) return 0;
     const tts_hip_sampling *sp = g.sampled ? &g.sp : nullptr;
-    const uint32_t pos = g.pos[0];
-    const uint32_t steps = std::min<uint32_t>(std::min<uint32_t>(n_steps, g.max_new - (uint32_t) g.toks[0].size()), c->lm.n_ctx - pos);
+    const uint32_t pos = g.pos;
+    const uint32_t steps = std::min<uint32_t>(std::min<uint32_t>(n_steps, g.max_new - (uint32_t) g.toks.size()), c->lm.n_ctx - pos);
     if (steps > c->h_hist_cap) {
         if (c->h_hist) { (void) hipHostFree(c->h_hist); c->h_hist = nullptr; c->h_hist_cap = 0; }
         const size_t cap = std::max<size_t>(steps, 64);
@@ -424,8 +421,8 @@ static int llama_gen_launch_one(tts_hip_ctx *c, const char *what, uint32_t n_ste
         c->h_hist_cap = cap;
     }
     uint32_t *hist = c->l_tok + 1 + 2 * ARGMAX_PARTS, *hist_idx = hist + LLAMA_GREEDY_CHUNK;
-    HIPCHK(hipMemcpyAsync(c->l_ids, &g.cur[0], 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->l_pos, &g.pos[0], 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->l_ids, &g.cur, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->l_pos, &g.pos, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     const bool graph = c->llama_graph && !c->prof;
     hipGraphExec_t exec = nullptr;
@@ -469,19 +466,23 @@ static int llama_gen_wait_one(tts_hip_ctx *c) {
     const uint32_t steps = g.pending;
     g.pending = 0;
     if (steps == 0) return 0;
-    g.pos[0] += steps;
-    for (uint32_t s = 0; s < steps && !g.done[0]; s++) {
+    g.pos += steps;
+    for (uint32_t s = 0; s < steps && !g.done; s++) {
         // only the launch's last id meets the end of the cache: the ids before it were fed back inside the launch
-        g.toks[0].push_back(c->h_hist[s]);
-        g.cur[0] = c->h_hist[s];
-        if (c->h_hist[s] == g.stop_id || g.toks[0].size() >= g.max_new || (s + 1 == steps && g.pos[0] >= c->lm.n_ctx)) g.done[0] = 1;
+        g.toks.push_back(c->h_hist[s]);
+        g.cur = c->h_hist[s];
+        if (c->h_hist[s] == g.stop_id || g.toks.size() >= g.max_new || (s + 1 == steps && g.pos >= c->lm.n_ctx)) g.done = true;
     }
     return 0;
 }
 
-static int llama_gen_begin_rows(tts_hip_ctx *c, const char *what, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
-                                const tts_hip_sampling *sp, const float *uniforms);
-static int llama_gen_launch_rows(tts_hip_ctx *c, const char *what, uint32_t n_steps);
+// the ids no gen_wait has handed out yet -> tokens_out [max_new]
+static void llama_gen_hand_one(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    auto &g = c->lg;
+    for (size_t i = g.handed; i < g.toks.size(); i++) tokens_out[i] = g.toks[i];
+    g.handed = n_out[0] = (uint32_t) g.toks.size();
+    if (done) done[0] = g.done;
+}
 
 static int llama_gen_ready(tts_hip_ctx *c, const char *what, bool may_be_running = false) {
     if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
@@ -489,23 +490,9 @@ static int llama_gen_ready(tts_hip_ctx *c, const char *what, bool may_be_running
     return may_be_running ? 0 : llama_gen_idle(c, what);
 }
 
-static int llama_gen_wait(tts_hip_ctx *c, const char *what, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
-    auto &g = c->lg;
-    if (!g.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
-    if (!tokens_out || !n_out) return set_err("%s: null argument", what);
-    HIPCHK(hipSetDevice(c->device));
-    if (!g.lockstep) CHK(llama_gen_wait_one(c));
-    for (uint32_t u = 0; u < g.n_utt; u++) {
-        for (size_t i = g.handed[u]; i < g.toks[u].size(); i++) tokens_out[(size_t) u * g.max_new + i] = g.toks[u][i];
-        g.handed[u] = n_out[u] = (uint32_t) g.toks[u].size();
-        if (done) done[u] = g.done[u];
-    }
-    return 0;
-}
-
-static bool llama_gen_all_done(const tts_hip_ctx *c) {
-    for (uint8_t d : c->lg.done) if (!d) return false;
-    return true;
+// a one-sequence generation takes the context: a fixed batch that was under way is dropped
+static void llama_batch_drop(tts_hip_ctx *c) {
+    if (c->ls.mode == tts_hip_ctx::LlamaStream::BATCH) c->ls.mode = tts_hip_ctx::LlamaStream::NONE;
 }
 
 static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *prompt, uint32_t n_prompt, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp,
@@ -513,14 +500,15 @@ static int orpheus_generate(tts_hip_ctx *c, const char *what, const uint32_t *pr
     CHK(llama_gen_ready(c, what));
     if (!prompt || n_prompt == 0 || !tokens_out || !n_out) return set_err("%s: null argument", what);
     *n_out = 0;
+    llama_batch_drop(c);
     CHK(llama_gen_begin_one(c, what, prompt, n_prompt, max_new, stop_id, sp, uniforms));
     // the host looks at LLAMA_GREEDY_CHUNK steps at once, so at most CHUNK-1 steps run past the stopping token
     int rc = 0;
-    while (rc == 0 && !llama_gen_all_done(c)) {
+    while (rc == 0 && !c->lg.done) {
         rc = llama_gen_launch_one(c, what, LLAMA_GREEDY_CHUNK);
         if (rc == 0) rc = llama_gen_wait_one(c);
     }
-    if (rc == 0 && max_new) rc = llama_gen_wait(c, what, tokens_out, n_out, nullptr);
+    if (rc == 0 && max_new) llama_gen_hand_one(c, tokens_out, n_out, nullptr);
     c->lg.active = false;
     return rc;
 }
@@ -561,9 +549,6 @@ extern "C" int tts_hip_orpheus_sample_logits(tts_hip_ctx *c, const float *logits
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dia (src/models/dia/model.cpp:383-659)
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
 // Lock-step utterances ("within a GPU, B utterances batched in lock-step"; the reference's only concurrency is N independent
 // workers, each with its own model copy, examples/server/server.cpp:225-321).  The cache holds lm.max_seqs slots; a step carries one row per
 // live utterance, every row with its own slot and position.
@@ -584,11 +569,30 @@ static int llama_stage_rows(tts_hip_ctx *c, const char *what, uint32_t n, const 
     return 0;
 }
 
-// sampler::max of the logits of rows 0 .. n-1 -> l_btok[r]
-static int llama_argmax_rows(tts_hip_ctx *c, int n) {
-    hipLaunchKernelGGL(argmax_rows_parts_kernel, dim3(ARGMAX_PARTS, n), dim3(256), 0, c->stream, (const float *) c->l_logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi);
+// The selection of `rows` logits rows (first at `logits`) for slots row_slot[r] (NULL: slot0 + r) -> l_btok[r], every row with its slot's sampler
+// (samp[], tables pen[][pen_len]; samp NULL: sampler::max for all): the arg-max pair when a row is greedy, the top-k kernels when one is sampled,
+// the total when a sampled one has top_p < 1 — the caller knows which of its rows are.
+static int llama_select_slots(tts_hip_ctx *c, bool any_max, bool any_sample, bool any_nucleus, int rows, const float *logits, const uint32_t *row_slot, int slot0,
+                              const uint32_t *slot_state, const llama_slot_sampler *samp, const double *pen, int pen_len, uint32_t *smp, const float *uni, int64_t uni_stride,
+                              unsigned long long *cand, float *total) {
+    if (!any_sample) samp = nullptr;   // every row is sampler::max: the arg-max pair need not read the records
+    if (any_max) {
+        hipLaunchKernelGGL(argmax_slots_parts_kernel, dim3(ARGMAX_PARTS, rows), dim3(256), 0, c->stream, logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi, samp, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(argmax_slots_fold_kernel, dim3(rows), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok, samp, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+    }
+    if (!any_sample) return 0;
+    hipLaunchKernelGGL(topk_parts_rows_kernel, dim3(TOPK_PARTS, rows), dim3(512), 0, c->stream, logits, c->l_V, c->l_Vpad, samp, pen, pen_len, (const uint32_t *) smp, cand, row_slot, slot0,
+                       slot_state);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(argmax_rows_fold_kernel, dim3(n), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok);
+    if (any_nucleus) {
+        hipLaunchKernelGGL(softmax_total_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, logits, c->l_V, c->l_Vpad, (const unsigned long long *) cand, samp, pen, pen_len,
+                           (const uint32_t *) smp, total, row_slot, slot0, slot_state);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(topk_sample_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, (const unsigned long long *) cand, samp, uni, uni_stride, pen, pen_len, smp, c->l_btok,
+                       (const float *) total, row_slot, slot0, slot_state);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -603,8 +607,8 @@ extern "C" int tts_hip_orpheus_step_batch(tts_hip_ctx *c, uint32_t n, const uint
     uint32_t max_pos = 0;
     CHK(llama_stage_rows(c, "tts_hip_orpheus_step_batch", n, slots, ids, pos, &max_pos));
     CHK(llama_forward(c, nullptr, (int) n, 0, (int) max_pos + 1, c->l_seq, -1));
-    if (tokens_out) {
-        CHK(llama_argmax_rows(c, (int) n));
+    if (tokens_out) {   // sampler::max of every row: no records
+        CHK(llama_select_slots(c, true, false, false, (int) n, c->l_logits, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr));
         HIPCHK(hipMemcpyAsync(tokens_out, c->l_btok, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
     }
     if (logits_out) HIPCHK(hipMemcpy2DAsync(logits_out, (size_t) c->l_V * 4, c->l_logits, (size_t) c->l_Vpad * 4, (size_t) c->l_V * 4, n, hipMemcpyDeviceToHost, c->stream));
@@ -629,212 +633,25 @@ static int llama_prefill_slot(tts_hip_ctx *c, const char *what, uint32_t slot, c
     return 0;
 }
 
-// generate_from_batch (orpheus/model.cpp:378-392) for n_utt utterances in lock-step: every utterance gets exactly the tokens its own one-sequence
-// generation gets (sampler::max, or sampler::sample with its own uniforms and repetition state); finished utterances leave the step.
-// In pieces like the one-sequence loop: begin = prompts + first selection, launch = up to n_steps host-driven steps (each looks at its ids, so
-// nothing runs past a stopping token), wait = hand out.
-// select for logits row r on behalf of utterance utt[r] -> l_btok[r]
-static int llama_select_rows(tts_hip_ctx *c, const std::vector<uint32_t> &utt) {
-    auto &g = c->lg;
-    const int n = (int) utt.size();
-    if (!g.sampled) return llama_argmax_rows(c, n);
-    const tts_hip_sampling *sp = &g.sp;
-    const double *pen = sp->repetition_penalty != 1.0f ? c->d_pen : nullptr;
-    for (int r = 0; r < n; r++) {
-        const uint32_t u = utt[(size_t) r];
-        int32_t *last = (int32_t *) (c->l_bsmp + 3 * u);
-        uint32_t *repc = c->l_bsmp + 3 * u + 1, *call = c->l_bsmp + 3 * u + 2;
-        const float *lg = c->l_logits + (size_t) r * c->l_Vpad;
-        hipLaunchKernelGGL(topk_parts_kernel, dim3(TOPK_PARTS), dim3(512), 0, c->stream, lg, c->l_V, (int) sp->top_k, pen, c->pen_len, (const int32_t *) last, (const uint32_t *) repc, c->l_cand);
-        HIPCHK(hipGetLastError());
-        float *total = nullptr;
-        if (sp->top_p < 1.0f) {
-            total = (float *) (c->l_cand + (size_t) TOPK_PARTS * TOPK_MAXK);
-            hipLaunchKernelGGL(softmax_total_kernel, dim3(1), dim3(1024), 0, c->stream, lg, c->l_V, (const unsigned long long *) c->l_cand, sp->temperature, pen, c->pen_len,
-                               (const int32_t *) last, (const uint32_t *) repc, total);
-            HIPCHK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(topk_sample_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long *) c->l_cand, (int) sp->top_k, sp->temperature,
-                           (const float *) c->d_uniforms + (size_t) u * g.max_new, call, pen, last, repc, c->l_btok + r, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr,
-                           (uint32_t *) nullptr, sp->top_p, (const float *) total);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
-}
-
-// the head of orpheus_generate's loop, per live utterance: record the latest id; stop on the stopping token, at max_new ids or at the end of the cache
-static void llama_gen_emit_rows(tts_hip_ctx *c) {
-    auto &g = c->lg;
-    std::vector<uint32_t> next;
-    for (uint32_t u : g.live) {
-        llama_gen_emit(c, u, g.cur[u]);
-        if (!g.done[u]) next.push_back(u);
-    }
-    g.live.swap(next);   // utterances still generating, in utterance order (= the rows of the next step)
-}
-
-static int llama_gen_begin_rows(tts_hip_ctx *c, const char *what, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
-                                const tts_hip_sampling *sp, const float *uniforms) {
-    auto &g = c->lg;
-    g.active = false;
-    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
-    if (n_utt == 0 || n_utt > c->lm.max_seqs) return set_err("%s: %u utterances outside 1..max_seqs = %u", what, n_utt, c->lm.max_seqs);
-    HIPCHK(hipSetDevice(c->device));
-    for (uint32_t u = 0; u < n_utt; u++) if (n_prompt[u] == 0 || n_prompt[u] >= c->lm.n_ctx) return set_err("%s: utterance %u: prompt of %u ids", what, u, n_prompt[u]);
-    g.lockstep = true; g.sampled = sp != nullptr; g.n_utt = n_utt; g.max_new = max_new; g.stop_id = stop_id; g.pending = 0;
-    if (sp) g.sp = *sp;
-    g.pos.assign(n_utt, 0); g.cur.assign(n_utt, 0); g.toks.assign(n_utt, {}); g.handed.assign(n_utt, 0); g.done.assign(n_utt, 0); g.live.clear();
-    if (max_new == 0) { g.done.assign(n_utt, 1); g.active = true; return 0; }
-    if (sp) {
-        CHK(check_llama_sampling(c, sp, what));
-        if (!uniforms) return set_err("%s: null uniforms", what);
-        CHK(stage_uniforms(c, uniforms, (size_t) n_utt * max_new));   // utterance u draws uniforms[u * max_new + call]
-        CHK(stage_penalty(c, sp->repetition_penalty, (int) max_new));
-        std::vector<uint32_t> init((size_t) 3 * n_utt);
-        for (uint32_t u = 0; u < n_utt; u++) { init[3 * u] = 0xFFFFFFFFu; init[3 * u + 1] = 0; init[3 * u + 2] = 0; }   // sampler::reset per utterance
-        HIPCHK(hipMemcpyAsync(c->l_bsmp, init.data(), init.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    // prompts, then the first selection from every utterance's last prompt row (logits row u)
-    size_t off = 0;
-    for (uint32_t u = 0; u < n_utt; u++) {
-        CHK(llama_prefill_slot(c, what, u, prompts + off, n_prompt[u]));
-        off += n_prompt[u];
-        g.live.push_back(u);
-        g.pos[u] = n_prompt[u];
-    }
-    CHK(llama_select_rows(c, g.live));
-    HIPCHK(hipMemcpyAsync(g.cur.data(), c->l_btok, (size_t) n_utt * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    llama_gen_emit_rows(c);
-    g.active = true;
-    return 0;
-}
-
-static int llama_gen_launch_rows(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
-    auto &g = c->lg;
-    std::vector<uint32_t> slots, ids, ps, tok;
-    for (uint32_t s = 0; s < n_steps && !g.live.empty(); s++) {
-        const uint32_t n = (uint32_t) g.live.size();
-        slots.resize(n); ids.resize(n); ps.resize(n); tok.resize(n);
-        for (uint32_t r = 0; r < n; r++) { slots[r] = g.live[r]; ids[r] = g.cur[g.live[r]]; ps[r] = g.pos[g.live[r]]; }
-        uint32_t max_pos = 0;
-        CHK(llama_stage_rows(c, what, n, slots.data(), ids.data(), ps.data(), &max_pos));
-        CHK(llama_forward(c, nullptr, (int) n, 0, (int) max_pos + 1, c->l_seq, -1));
-        CHK(llama_select_rows(c, g.live));
-        HIPCHK(hipMemcpyAsync(tok.data(), c->l_btok, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t r = 0; r < n; r++) { g.cur[g.live[r]] = tok[r]; g.pos[g.live[r]]++; }
-        llama_gen_emit_rows(c);
-    }
-    return 0;
-}
-
-extern "C" int tts_hip_orpheus_generate_batch(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
-                                              const tts_hip_sampling *sp, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
-    const char *what = "tts_hip_orpheus_generate_batch";
-    CHK(llama_gen_ready(c, what));
-    if (!prompts || !n_prompt || !tokens_out || !n_out) return set_err("%s: null argument", what);
-    for (uint32_t u = 0; u < n_utt && u < c->lm.max_seqs; u++) n_out[u] = 0;
-    CHK(llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms));
-    int rc = 0;
-    while (rc == 0 && !c->lg.live.empty()) rc = llama_gen_launch_rows(c, what, 64);
-    if (rc == 0 && max_new) rc = llama_gen_wait(c, what, tokens_out, n_out, nullptr);
-    c->lg.active = false;
-    return rc;
-}
-
-extern "C" int tts_hip_orpheus_gen_begin(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
-                                         const tts_hip_sampling *sp, const float *uniforms) {
-    const char *what = "tts_hip_orpheus_gen_begin";
-    CHK(llama_gen_ready(c, what));
-    c->lg.active = false;
-    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
-    if (n_utt == 1) return llama_gen_begin_one(c, what, prompts, n_prompt[0], max_new, stop_id, sp, uniforms);
-    return llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms);
-}
-
-extern "C" int tts_hip_orpheus_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
-    const char *what = "tts_hip_orpheus_gen_launch";
-    CHK(llama_gen_ready(c, what));
-    if (!c->lg.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
-    HIPCHK(hipSetDevice(c->device));
-    return c->lg.lockstep ? llama_gen_launch_rows(c, what, n_steps) : llama_gen_launch_one(c, what, n_steps);
-}
-
-extern "C" int tts_hip_orpheus_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
-    CHK(llama_gen_ready(c, "tts_hip_orpheus_gen_wait", true));
-    return llama_gen_wait(c, "tts_hip_orpheus_gen_wait", tokens_out, n_out, done);
-}
-
 // ------------------------------------------------------------------------------------------------
-// Continuous session (tts_hip_orpheus_stream_*): cache slots are admitted and refilled while the others generate.  The state of a slot — ids so far,
-// finished flag, latest id and position, sampler state, uniforms — lives on the device, so a run of k steps is k x (forward, row-batched selection,
-// llama_advance_rows_kernel) enqueued back to back: no copy and no synchronise inside the run, against three copies, two synchronises and up to three
-// launches per row in every step of llama_gen_launch_rows.  Rows that finish inside a run idle as padding until its end.
+// The lock-step loop (tts_hip_ctx::LlamaStream): generate_from_batch (orpheus/model.cpp:378-392) for the utterances in the cache slots, every one
+// with exactly the tokens its own one-sequence generation gets (sampler::max, or sampler::sample with its own uniforms and repetition state).
+// The state of a slot — ids so far, finished flag, latest id and position, sampler record and state, penalty table, uniforms — lives on the
+// device, so a run of k steps is k x (forward, row-batched selection, llama_advance_rows_kernel) enqueued back to back: no copy and no
+// synchronise inside the run.  Rows that finish inside a run idle as padding until its end.  The fixed batch (tts_hip_orpheus_gen_* at
+// n_utt > 1, tts_hip_orpheus_generate_batch) admits slots 0 .. n-1 at begin; the continuous session (tts_hip_orpheus_stream_*) admits and
+// refills slots while the others generate.
 // ------------------------------------------------------------------------------------------------
+typedef tts_hip_ctx::LlamaStream LS;
+
 static int llama_stream_ready(tts_hip_ctx *c, const char *what, bool need_session = true) {
     if (!c || !c->has_llama) return set_err("%s: not an Orpheus context (tts_hip_orpheus_create)", what);
     if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", what);
-    if (need_session && !c->ls.active) return set_err("%s: no session (tts_hip_orpheus_stream_begin)", what);
+    if (need_session && c->ls.mode != LS::SESSION) return set_err("%s: no session (tts_hip_orpheus_stream_begin)", what);
     return 0;
 }
 
-// the selection of `rows` logits rows (first at `logits`) for slots row_slot[r] (NULL: slot0 + r) -> l_btok[r]: two launches (arg-max, top-k) or three (top_p < 1)
-static int llama_select_slots(tts_hip_ctx *c, const tts_hip_sampling *sp, int rows, const float *logits, const uint32_t *row_slot, int slot0, const uint32_t *slot_state,
-                              uint32_t *smp, const float *uni, int64_t uni_stride, unsigned long long *cand, float *total) {
-    if (!sp) {
-        hipLaunchKernelGGL(argmax_slots_parts_kernel, dim3(ARGMAX_PARTS, rows), dim3(256), 0, c->stream, logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi, row_slot, slot0, slot_state);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(argmax_slots_fold_kernel, dim3(rows), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok, row_slot, slot0, slot_state);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    const double *pen = sp->repetition_penalty != 1.0f ? c->d_pen : nullptr;
-    hipLaunchKernelGGL(topk_parts_rows_kernel, dim3(TOPK_PARTS, rows), dim3(512), 0, c->stream, logits, c->l_V, c->l_Vpad, (int) sp->top_k, pen, c->pen_len, (const uint32_t *) smp, cand,
-                       row_slot, slot0, slot_state);
-    HIPCHK(hipGetLastError());
-    const bool nucleus = sp->top_p < 1.0f;
-    if (nucleus) {
-        hipLaunchKernelGGL(softmax_total_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, logits, c->l_V, c->l_Vpad, (const unsigned long long *) cand, sp->temperature, pen,
-                           c->pen_len, (const uint32_t *) smp, total, row_slot, slot0, slot_state);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(topk_sample_rows_kernel, dim3(1, rows), dim3(1024), 0, c->stream, (const unsigned long long *) cand, (int) sp->top_k, sp->temperature, uni, uni_stride, pen, smp,
-                       c->l_btok, sp->top_p, nucleus ? (const float *) total : (const float *) nullptr, row_slot, slot0, slot_state);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// the same for slots that carry their own sampler (llama_slot_sampler samp[], tables pen[][pen_len]): the arg-max pair when a row is greedy, the top-k
-// kernels when one is sampled, the total when a sampled one has top_p < 1 — the caller knows which of its rows are
-static int llama_select_slots_mixed(tts_hip_ctx *c, bool any_max, bool any_sample, bool any_nucleus, int rows, const float *logits, const uint32_t *row_slot, int slot0,
-                                    const uint32_t *slot_state, const llama_slot_sampler *samp, const double *pen, int pen_len, uint32_t *smp, const float *uni,
-                                    int64_t uni_stride, unsigned long long *cand, float *total) {
-    if (any_max) {
-        hipLaunchKernelGGL(argmax_slots_parts_mixed_kernel, dim3(ARGMAX_PARTS, rows), dim3(256), 0, c->stream, logits, c->l_V, c->l_Vpad, c->l_bpv, c->l_bpi, samp, row_slot, slot0,
-                           slot_state);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(argmax_slots_fold_mixed_kernel, dim3(rows), dim3(64), 0, c->stream, (const float *) c->l_bpv, (const uint32_t *) c->l_bpi, c->l_btok, samp, row_slot, slot0,
-                           slot_state);
-        HIPCHK(hipGetLastError());
-    }
-    if (!any_sample) return 0;
-    hipLaunchKernelGGL(topk_parts_rows_mixed_kernel, dim3(TOPK_PARTS, rows), dim3(512), 0, c->stream, logits, c->l_V, c->l_Vpad, samp, pen, pen_len, (const uint32_t *) smp, cand, row_slot,
-                       slot0, slot_state);
-    HIPCHK(hipGetLastError());
-    if (any_nucleus) {
-        hipLaunchKernelGGL(softmax_total_rows_mixed_kernel, dim3(1, rows), dim3(1024), 0, c->stream, logits, c->l_V, c->l_Vpad, (const unsigned long long *) cand, samp, pen, pen_len,
-                           (const uint32_t *) smp, total, row_slot, slot0, slot_state);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(topk_sample_rows_mixed_kernel, dim3(1, rows), dim3(1024), 0, c->stream, (const unsigned long long *) cand, samp, uni, uni_stride, pen, pen_len, smp, c->l_btok,
-                       (const float *) total, row_slot, slot0, slot_state);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// one slot's record and table, as the mixed kernels read them: sp NULL is sampler::max; the table is stage_penalty's for sp's penalty, len entries
+// one slot's record and table, as the rows kernels read them: sp NULL is sampler::max; the table is stage_penalty's for sp's penalty, len entries
 static void llama_slot_sampler_host(const tts_hip_sampling *sp, int len, llama_slot_sampler *rec, double *table) {
     *rec = sp ? llama_slot_sampler{LLAMA_SLOT_SAMPLE, sp->top_k, sp->temperature, sp->top_p} : llama_slot_sampler{LLAMA_SLOT_MAX, 0u, 1.0f, 1.0f};
     const bool rep = sp && sp->repetition_penalty != 1.0f;
@@ -848,44 +665,225 @@ static int dmalloc(T **p, size_t n) {
     return 0;
 }
 
-static void llama_stream_free(tts_hip_ctx *c) {
+static void llama_loop_free(tts_hip_ctx *c) {
     auto &g = c->ls;
     free_dev(g.state); free_dev(g.tokens); free_dev(g.smp); free_dev(g.uni); free_dev(g.cand); free_dev(g.total); free_dev(g.samp); free_dev(g.pen);
     if (g.h_state) (void) hipHostFree(g.h_state);
-    g = tts_hip_ctx::LlamaStream{};
+    g = LS{};
 }
 
-// mixed: every slot carries its own sampler (sp is NULL), so the sampler's buffers exist for every slot
+// Enter the loop.  The buffers stay on the context from one loop to the next while (n_slots, max_new) fits and grow when it does not (tts_hip_destroy
+// frees them); whatever an earlier loop left in them is overwritten slot by slot by the admissions.  sp: what every admission of a loop that is
+// not mixed selects with (NULL: sampler::max).
+static int llama_loop_begin(tts_hip_ctx *c, const char *what, LS::Mode mode, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp, bool mixed) {
+    auto &g = c->ls;
+    const size_t S = n_slots, M = std::max<uint32_t>(max_new, 1);
+    if (S > g.cap_slots || M > g.cap_new) {
+        const size_t CS = std::max(S, g.cap_slots), CM = std::max(M, g.cap_new);
+        (void) hipStreamSynchronize(c->stream);
+        llama_loop_free(c);
+        int rc = dmalloc(&g.state, CS * LLAMA_SLOT_STATE);
+        if (rc == 0) rc = dmalloc(&g.tokens, CS * CM);
+        if (rc == 0) rc = dmalloc(&g.smp, CS * 3);
+        if (rc == 0) rc = dmalloc(&g.uni, CS * CM);
+        if (rc == 0) rc = dmalloc(&g.total, CS);
+        if (rc == 0 && hipMalloc((void **) &g.cand, CS * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
+        if (rc == 0) rc = dmalloc((llama_slot_sampler **) &g.samp, CS);
+        if (rc == 0) rc = dmalloc(&g.pen, CS * CM);
+        if (rc == 0 && hipHostMalloc((void **) &g.h_state, CS * LLAMA_SLOT_STATE * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
+        if (rc != 0) { llama_loop_free(c); return rc; }
+        g.cap_slots = CS; g.cap_new = CM;
+    }
+    g.sampled = sp != nullptr; g.mixed = mixed; g.n_slots = n_slots; g.max_new = max_new; g.stop_id = stop_id;
+    if (sp) g.sp = *sp;
+    g.slot.assign(S, LS::FREE);
+    g.count.assign(S, 0); g.cur.assign(S, 0); g.pos.assign(S, 0); g.handed.assign(S, 0);
+    g.slot_sampled.assign(S, 0); g.slot_nucleus.assign(S, 0);
+    g.rows.clear();
+    g.mode = mode;
+    return 0;
+}
+
+// One utterance into slot s (the arguments have been checked): everything the slot's predecessor left is overwritten — state, sampler state,
+// record, table and the uniforms a sampled utterance draws from ([max_new]) — then the prompt goes into the slot's cache, its last row's logits
+// land in l_logits row s, and the first selection and advance follow.
+static int llama_loop_admit(tts_hip_ctx *c, const char *what, uint32_t s, const uint32_t *prompt, uint32_t n_prompt, const tts_hip_sampling *sp, const float *uniforms) {
+    auto &g = c->ls;
+    uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
+    g.count[s] = 0; g.cur[s] = 0; g.pos[s] = n_prompt - 1; g.handed[s] = 0;
+    if (g.max_new == 0) { g.slot[s] = LS::ENDED; return 0; }
+    // count 0, not finished, no id yet, position of the prompt's last row; sampler::reset and the utterance's own draws
+    const uint32_t init[LLAMA_SLOT_STATE] = {0u, 0u, 0u, n_prompt - 1};
+    const uint32_t reset[3] = {0xFFFFFFFFu, 0u, 0u};
+    // max_new entries, read at index min(count, max_new - 1).  The clamp never binds: a count goes up by at most one per selection, so the i-th
+    // selection of an utterance (i = 1 .. max_new) reads a count of at most i - 1 <= max_new - 1.
+    llama_slot_sampler rec;
+    std::vector<double> table(g.max_new);
+    llama_slot_sampler_host(sp, (int) g.max_new, &rec, table.data());
+    HIPCHK(hipMemcpyAsync(g.state + (size_t) s * LLAMA_SLOT_STATE, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g.smp + (size_t) s * 3, reset, sizeof(reset), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync((llama_slot_sampler *) g.samp + s, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g.pen + (size_t) s * g.max_new, table.data(), table.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (sp) HIPCHK(hipMemcpyAsync(g.uni + (size_t) s * g.max_new, uniforms, (size_t) g.max_new * 4, hipMemcpyHostToDevice, c->stream));
+    g.slot_sampled[s] = sp != nullptr; g.slot_nucleus[s] = sp && sp->top_p < 1.0f;
+    HIPCHK(hipStreamSynchronize(c->stream));   // init / reset / rec / table are locals
+    CHK(llama_prefill_slot(c, what, s, prompt, n_prompt));
+    CHK(llama_select_slots(c, !sp, sp != nullptr, g.slot_nucleus[s] != 0, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state, (const llama_slot_sampler *) g.samp, g.pen,
+                           (int) g.max_new, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
+    hipLaunchKernelGGL(llama_advance_rows_kernel, dim3(1), dim3(64), 0, c->stream, 1, (const uint32_t *) nullptr, (int) s, (const uint32_t *) c->l_btok, g.state, g.tokens, g.max_new,
+                       g.stop_id, c->lm.n_ctx, (uint32_t *) nullptr, (uint32_t *) nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, g.state + (size_t) s * LLAMA_SLOT_STATE, LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
+    g.slot[s] = h[1] ? LS::ENDED : LS::LIVE;
+    return 0;
+}
+
+static void llama_loop_live_rows(tts_hip_ctx *c) {
+    auto &g = c->ls;
+    g.rows.clear();
+    for (uint32_t s = 0; s < g.n_slots; s++) if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
+}
+
+// A run: the live rows staged once, up to n_steps x (forward, selection, advance), one copy of the slots' state and one synchronise.  The run is
+// over once no row can still be live: a row with `count` ids at position `pos` ends after min(max_new - count, n_ctx - pos) steps at the latest.
+// Slots that finished are ENDED afterwards and have left the rows of the next run.
+static int llama_loop_run(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
+    auto &g = c->ls;
+    const uint32_t n = (uint32_t) g.rows.size();
+    if (n != 0 && n_steps != 0) {
+        HIPCHK(hipSetDevice(c->device));
+        std::vector<uint32_t> ids(n), ps(n);
+        uint32_t left = 0;
+        for (uint32_t r = 0; r < n; r++) {
+            const uint32_t s = g.rows[r];
+            ids[r] = g.cur[s]; ps[r] = g.pos[s];
+            left = std::max(left, std::min(g.max_new - g.count[s], c->lm.n_ctx - g.pos[s]));
+        }
+        uint32_t max_pos = 0;
+        CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
+        bool any_max = false, any_sample = false, any_nucleus = false;   // which selection kernels this run's rows need
+        for (uint32_t s : g.rows) { any_max |= !g.slot_sampled[s]; any_sample |= g.slot_sampled[s] != 0; any_nucleus |= g.slot_nucleus[s] != 0; }
+        for (uint32_t i = 0; i < std::min(n_steps, left); i++) {
+            // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
+            const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
+            CHK(llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1));
+            CHK(llama_select_slots(c, any_max, any_sample, any_nucleus, (int) n, c->l_logits, c->l_seq, 0, g.state, (const llama_slot_sampler *) g.samp, g.pen, (int) g.max_new, g.smp,
+                                   g.uni, (int64_t) g.max_new, g.cand, g.total));
+            hipLaunchKernelGGL(llama_advance_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (int) n, (const uint32_t *) c->l_seq, 0, (const uint32_t *) c->l_btok, g.state,
+                               g.tokens, g.max_new, g.stop_id, c->lm.n_ctx, c->l_ids, c->l_pos);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(g.h_state, g.state, (size_t) g.n_slots * LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t s : g.rows) {
+            const uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
+            g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
+            if (h[1]) g.slot[s] = LS::ENDED;
+        }
+    }
+    llama_loop_live_rows(c);
+    return 0;
+}
+
+// ---- the fixed batch: slots 0 .. n_utt-1, all admitted at begin; every utterance takes sp (NULL: sampler::max) and its row of uniforms [n_utt][max_new] ----
+static int llama_gen_begin_rows(tts_hip_ctx *c, const char *what, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                const tts_hip_sampling *sp, const float *uniforms) {
+    auto &g = c->ls;
+    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
+    if (n_utt == 0 || n_utt > c->lm.max_seqs) return set_err("%s: %u utterances outside 1..max_seqs = %u", what, n_utt, c->lm.max_seqs);
+    HIPCHK(hipSetDevice(c->device));
+    for (uint32_t u = 0; u < n_utt; u++) if (n_prompt[u] == 0 || n_prompt[u] >= c->lm.n_ctx) return set_err("%s: utterance %u: prompt of %u ids", what, u, n_prompt[u]);
+    if (max_new != 0 && sp) {
+        CHK(check_llama_sampling(c, sp, what));
+        if (!uniforms) return set_err("%s: null uniforms", what);
+    }
+    CHK(llama_loop_begin(c, what, LS::BATCH, n_utt, max_new, stop_id, sp, false));
+    size_t off = 0;
+    for (uint32_t u = 0; u < n_utt; u++) {
+        if (llama_loop_admit(c, what, u, prompts + off, n_prompt[u], sp, sp ? uniforms + (size_t) u * max_new : nullptr) != 0) { g.mode = LS::NONE; return -1; }
+        off += n_prompt[u];
+    }
+    llama_loop_live_rows(c);
+    return 0;
+}
+
+// each utterance's ids since the last wait, from the device token buffer -> tokens_out [n_utt][max_new]
+static int llama_gen_wait_rows(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    auto &g = c->ls;
+    for (uint32_t u = 0; u < g.n_slots; u++) {
+        const size_t at = (size_t) u * g.max_new + g.handed[u];
+        if (g.count[u] > g.handed[u]) HIPCHK(hipMemcpyAsync(tokens_out + at, g.tokens + at, (size_t) (g.count[u] - g.handed[u]) * 4, hipMemcpyDeviceToHost, c->stream));
+        g.handed[u] = n_out[u] = g.count[u];
+        if (done) done[u] = g.slot[u] != LS::LIVE;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int tts_hip_orpheus_generate_batch(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                              const tts_hip_sampling *sp, const float *uniforms, uint32_t *tokens_out, uint32_t *n_out) {
+    const char *what = "tts_hip_orpheus_generate_batch";
+    CHK(llama_gen_ready(c, what));
+    if (!prompts || !n_prompt || !tokens_out || !n_out) return set_err("%s: null argument", what);
+    for (uint32_t u = 0; u < n_utt && u < c->lm.max_seqs; u++) n_out[u] = 0;
+    c->lg.active = false;
+    llama_batch_drop(c);
+    CHK(llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms));
+    int rc = 0;
+    while (rc == 0 && !c->ls.rows.empty()) rc = llama_loop_run(c, what, c->l_batch_run);
+    if (rc == 0 && max_new) rc = llama_gen_wait_rows(c, tokens_out, n_out, nullptr);
+    c->ls.mode = LS::NONE;
+    return rc;
+}
+
+extern "C" int tts_hip_orpheus_gen_begin(tts_hip_ctx *c, uint32_t n_utt, const uint32_t *prompts, const uint32_t *n_prompt, uint32_t max_new, uint32_t stop_id,
+                                         const tts_hip_sampling *sp, const float *uniforms) {
+    const char *what = "tts_hip_orpheus_gen_begin";
+    CHK(llama_gen_ready(c, what));
+    c->lg.active = false;
+    llama_batch_drop(c);
+    if (!prompts || !n_prompt) return set_err("%s: null argument", what);
+    if (n_utt == 1) return llama_gen_begin_one(c, what, prompts, n_prompt[0], max_new, stop_id, sp, uniforms);
+    return llama_gen_begin_rows(c, what, n_utt, prompts, n_prompt, max_new, stop_id, sp, uniforms);
+}
+
+// blocking for a batch (the run ends with its look-in), asynchronous for one sequence
+extern "C" int tts_hip_orpheus_gen_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    const char *what = "tts_hip_orpheus_gen_launch";
+    CHK(llama_gen_ready(c, what));
+    if (c->ls.mode == LS::BATCH) return llama_loop_run(c, what, n_steps);
+    if (!c->lg.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
+    HIPCHK(hipSetDevice(c->device));
+    return llama_gen_launch_one(c, what, n_steps);
+}
+
+extern "C" int tts_hip_orpheus_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    const char *what = "tts_hip_orpheus_gen_wait";
+    CHK(llama_gen_ready(c, what, true));
+    const bool batch = c->ls.mode == LS::BATCH;
+    if (!batch && !c->lg.active) return set_err("%s: no generation (tts_hip_orpheus_gen_begin)", what);
+    if (!tokens_out || !n_out) return set_err("%s: null argument", what);
+    HIPCHK(hipSetDevice(c->device));
+    if (batch) return llama_gen_wait_rows(c, tokens_out, n_out, done);
+    CHK(llama_gen_wait_one(c));
+    llama_gen_hand_one(c, tokens_out, n_out, done);
+    return 0;
+}
+
+// ---- the continuous session ----
+// mixed: every admission brings its utterances' samplers (sp is NULL); otherwise every admission takes sp
 static int llama_stream_begin(tts_hip_ctx *c, const char *what, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp, bool mixed) {
     CHK(llama_stream_ready(c, what, false));
     CHK(llama_gen_idle(c, what));   // an open session or the window between a gen_launch and its gen_wait
-    if (c->lg.active && !llama_gen_all_done(c)) return set_err("%s: a tts_hip_orpheus_gen_* generation is under way", what);
+    if ((c->lg.active && !c->lg.done) || (c->ls.mode == LS::BATCH && !c->ls.rows.empty())) return set_err("%s: a tts_hip_orpheus_gen_* generation is under way", what);
     if (n_slots == 0 || n_slots > c->lm.max_seqs) return set_err("%s: %u slots outside 1..max_seqs = %u", what, n_slots, c->lm.max_seqs);
     if (sp) CHK(check_llama_sampling(c, sp, what));
     HIPCHK(hipSetDevice(c->device));
     c->lg.active = false;
-    auto &g = c->ls;
-    g.sampled = sp != nullptr; g.mixed = mixed; g.n_slots = n_slots; g.max_new = max_new; g.stop_id = stop_id;
-    if (sp) g.sp = *sp;
-    const size_t S = n_slots, M = std::max<uint32_t>(max_new, 1);
-    const bool smp = sp || mixed;
-    int rc = dmalloc(&g.state, S * LLAMA_SLOT_STATE);
-    if (rc == 0) rc = dmalloc(&g.tokens, S * M);
-    if (rc == 0 && smp) rc = dmalloc(&g.smp, S * 3);
-    if (rc == 0 && smp) rc = dmalloc(&g.uni, S * M);
-    if (rc == 0 && smp) rc = dmalloc(&g.total, S);
-    if (rc == 0 && smp && hipMalloc((void **) &g.cand, S * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
-    if (rc == 0 && mixed) rc = dmalloc((llama_slot_sampler **) &g.samp, S);   // zeroed: sampler::max, no penalty
-    if (rc == 0 && mixed) rc = dmalloc(&g.pen, S * M);
-    if (rc == 0 && hipHostMalloc((void **) &g.h_state, S * LLAMA_SLOT_STATE * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
-    if (rc == 0 && sp) rc = stage_penalty(c, sp->repetition_penalty, (int) max_new);   // once: every utterance of the session shares the table
-    if (rc != 0) { llama_stream_free(c); return rc; }
-    g.slot.assign(S, tts_hip_ctx::LlamaStream::FREE);
-    g.count.assign(S, 0); g.cur.assign(S, 0); g.pos.assign(S, 0);
-    g.slot_sampled.assign(S, 0); g.slot_nucleus.assign(S, 0);
-    g.rows.clear();
-    g.active = true;
-    return 0;
+    c->ls.mode = LS::NONE;
+    return llama_loop_begin(c, what, LS::SESSION, n_slots, max_new, stop_id, sp, mixed);
 }
 
 extern "C" int tts_hip_orpheus_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_new, uint32_t stop_id, const tts_hip_sampling *sp) {
@@ -898,7 +896,6 @@ extern "C" int tts_hip_orpheus_stream_begin_mixed(tts_hip_ctx *c, uint32_t n_slo
 // sampling (mixed session only): utterance i's sampler, NULL = sampler::max
 static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt,
                               const tts_hip_sampling *const *sampling, const float *uniforms) {
-    typedef tts_hip_ctx::LlamaStream LS;
     CHK(llama_stream_ready(c, what));
     auto &g = c->ls;
     if (mixed != g.mixed)
@@ -927,47 +924,11 @@ static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint
     HIPCHK(hipSetDevice(c->device));
     off = 0;
     for (uint32_t i = 0; i < n; i++) {
-        const uint32_t s = slots[i];
-        uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
-        g.count[s] = 0; g.cur[s] = 0; g.pos[s] = n_prompt[i] - 1;
-        if (g.max_new == 0) { g.slot[s] = LS::ENDED; off += n_prompt[i]; continue; }
-        // count 0, not finished, no id yet, position of the prompt's last row; sampler::reset and the utterance's own draws
-        const uint32_t init[LLAMA_SLOT_STATE] = {0u, 0u, 0u, n_prompt[i] - 1};
-        HIPCHK(hipMemcpyAsync(g.state + (size_t) s * LLAMA_SLOT_STATE, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-        const tts_hip_sampling *sp = mixed ? sampling[i] : (g.sampled ? &g.sp : nullptr);
-        const uint32_t reset[3] = {0xFFFFFFFFu, 0u, 0u};
-        if (sp) {
-            HIPCHK(hipMemcpyAsync(g.smp + (size_t) s * 3, reset, sizeof(reset), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(g.uni + (size_t) s * g.max_new, uniforms + (size_t) i * g.max_new, (size_t) g.max_new * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        llama_slot_sampler rec;
-        std::vector<double> table;
-        if (mixed) {   // the slot's own sampler: nothing of its predecessor's stays
-            table.resize(g.max_new);
-            llama_slot_sampler_host(sp, (int) g.max_new, &rec, table.data());
-            HIPCHK(hipMemcpyAsync((llama_slot_sampler *) g.samp + s, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(g.pen + (size_t) s * g.max_new, table.data(), table.size() * 8, hipMemcpyHostToDevice, c->stream));
-            g.slot_sampled[s] = sp != nullptr; g.slot_nucleus[s] = sp && sp->top_p < 1.0f;
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));   // init / reset / rec / table are locals
-        // the prompt into the slot's cache; its last row's logits land in l_logits row s; then the first selection, as gen_begin makes it
-        CHK(llama_prefill_slot(c, what, s, prompts + off, n_prompt[i]));
+        const tts_hip_sampling *sp = sampling ? sampling[i] : (g.sampled ? &g.sp : nullptr);   // the one sampler of a session that is not mixed, in every slot's record
+        CHK(llama_loop_admit(c, what, slots[i], prompts + off, n_prompt[i], sp, sp ? uniforms + (size_t) i * g.max_new : nullptr));
         off += n_prompt[i];
-        if (mixed)
-            CHK(llama_select_slots_mixed(c, !sp, sp != nullptr, g.slot_nucleus[s] != 0, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state,
-                                         (const llama_slot_sampler *) g.samp, g.pen, (int) g.max_new, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
-        else
-            CHK(llama_select_slots(c, sp, 1, c->l_logits + (size_t) s * c->l_Vpad, nullptr, (int) s, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
-        hipLaunchKernelGGL(llama_advance_rows_kernel, dim3(1), dim3(64), 0, c->stream, 1, (const uint32_t *) nullptr, (int) s, (const uint32_t *) c->l_btok, g.state, g.tokens, g.max_new,
-                           g.stop_id, c->lm.n_ctx, (uint32_t *) nullptr, (uint32_t *) nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h, g.state + (size_t) s * LLAMA_SLOT_STATE, LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
-        g.slot[s] = h[1] ? LS::ENDED : LS::LIVE;
     }
-    g.rows.clear();
-    for (uint32_t s = 0; s < g.n_slots; s++) if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
+    llama_loop_live_rows(c);
     return 0;
 }
 
@@ -981,51 +942,17 @@ extern "C" int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, co
 
 extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
     const char *what = "tts_hip_orpheus_stream_run";
-    typedef tts_hip_ctx::LlamaStream LS;
     CHK(llama_stream_ready(c, what));
     auto &g = c->ls;
     if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
     *n_finished = 0;
-    auto report = [&](uint32_t s) {
+    CHK(llama_loop_run(c, what, n_steps));
+    for (uint32_t s = 0; s < g.n_slots; s++) {
+        if (g.slot[s] != LS::ENDED) continue;
         finished_slots[*n_finished] = s;
         finished_counts[*n_finished] = g.count[s];
         (*n_finished)++;
         g.slot[s] = LS::REPORTED;
-    };
-    const uint32_t n = (uint32_t) g.rows.size();
-    if (n != 0 && n_steps != 0) {
-        HIPCHK(hipSetDevice(c->device));
-        std::vector<uint32_t> ids(n), ps(n);
-        for (uint32_t r = 0; r < n; r++) { ids[r] = g.cur[g.rows[r]]; ps[r] = g.pos[g.rows[r]]; }
-        uint32_t max_pos = 0;
-        CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
-        bool any_max = false, any_sample = false, any_nucleus = false;   // mixed: which selection kernels this run's rows need
-        for (uint32_t s : g.rows) { any_max |= !g.slot_sampled[s]; any_sample |= g.slot_sampled[s] != 0; any_nucleus |= g.slot_nucleus[s] != 0; }
-        for (uint32_t i = 0; i < n_steps; i++) {
-            // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
-            const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
-            CHK(llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1));
-            if (g.mixed)
-                CHK(llama_select_slots_mixed(c, any_max, any_sample, any_nucleus, (int) n, c->l_logits, c->l_seq, 0, g.state, (const llama_slot_sampler *) g.samp, g.pen,
-                                             (int) g.max_new, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
-            else
-                CHK(llama_select_slots(c, g.sampled ? &g.sp : nullptr, (int) n, c->l_logits, c->l_seq, 0, g.state, g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total));
-            hipLaunchKernelGGL(llama_advance_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (int) n, (const uint32_t *) c->l_seq, 0, (const uint32_t *) c->l_btok, g.state,
-                               g.tokens, g.max_new, g.stop_id, c->lm.n_ctx, c->l_ids, c->l_pos);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(g.h_state, g.state, (size_t) g.n_slots * LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t s : g.rows) {
-            const uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
-            g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
-            if (h[1]) g.slot[s] = LS::ENDED;
-        }
-    }
-    g.rows.clear();
-    for (uint32_t s = 0; s < g.n_slots; s++) {
-        if (g.slot[s] == LS::ENDED) report(s);
-        else if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
     }
     return 0;
 }
@@ -1035,7 +962,7 @@ extern "C" int tts_hip_orpheus_stream_collect(tts_hip_ctx *c, uint32_t slot, uin
     CHK(llama_stream_ready(c, what));
     auto &g = c->ls;
     if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
-    if (g.slot[slot] != tts_hip_ctx::LlamaStream::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_orpheus_stream_run reports it)", what, slot);
+    if (g.slot[slot] != LS::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_orpheus_stream_run reports it)", what, slot);
     if (count > g.count[slot]) return set_err("%s: slot %u produced %u ids, %u asked for", what, slot, g.count[slot], count);
     if (count == 0) return 0;
     if (!tokens_out) return set_err("%s: null argument", what);
@@ -1045,73 +972,27 @@ extern "C" int tts_hip_orpheus_stream_collect(tts_hip_ctx *c, uint32_t slot, uin
     return 0;
 }
 
+// leaves the loop; its buffers stay for the next one
 extern "C" int tts_hip_orpheus_stream_end(tts_hip_ctx *c) {
     if (!c || !c->has_llama) return set_err("tts_hip_orpheus_stream_end: not an Orpheus context (tts_hip_orpheus_create)");
-    if (!c->ls.active) return 0;
+    if (c->ls.mode != LS::SESSION) return 0;
     (void) hipSetDevice(c->device);
     (void) hipStreamSynchronize(c->stream);
-    llama_stream_free(c);
+    c->ls.mode = LS::NONE;
     return 0;
 }
 
-extern "C" int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *sp, const float *uniforms, int32_t *last_id,
-                                                  uint32_t *rep_count, uint32_t *tokens_out) {
-    const char *what = "tts_hip_orpheus_sample_logits_rows";
-    CHK(llama_stream_ready(c, what, false));
-    if (!logits || !tokens_out) return set_err("%s: null argument", what);
-    CHK(llama_gen_idle(c, what));
-    if (n_rows == 0 || n_rows > c->lm.max_seqs) return set_err("%s: %u rows outside 1..max_seqs = %u", what, n_rows, c->lm.max_seqs);
-    const bool rep = sp && sp->repetition_penalty != 1.0f;
-    if (sp) {
-        CHK(check_llama_sampling(c, sp, what));
-        if (!uniforms) return set_err("%s: null uniforms", what);
-        if (rep && (!last_id || !rep_count)) return set_err("%s: repetition penalty needs last_id and rep_count", what);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    uint32_t *smp = nullptr;
-    float *uni = nullptr, *total = nullptr;
-    unsigned long long *cand = nullptr;
-    auto drop = [&](int rc) { free_dev(smp); free_dev(uni); free_dev(total); free_dev(cand); return rc; };
-    if (sp) {
-        uint32_t mx = 0;
-        std::vector<uint32_t> init((size_t) 3 * n_rows);
-        for (uint32_t r = 0; r < n_rows; r++) {
-            init[3 * r] = rep ? (uint32_t) last_id[r] : 0xFFFFFFFFu; init[3 * r + 1] = rep ? rep_count[r] : 0u; init[3 * r + 2] = 0u;
-            if (rep) mx = std::max(mx, rep_count[r]);
-        }
-        if (rep) CHK(stage_penalty(c, sp->repetition_penalty, (int) std::min<uint32_t>(mx + 2, 1u << 20)));
-        int rc = dmalloc(&smp, (size_t) 3 * n_rows);
-        if (rc == 0) rc = dmalloc(&uni, (size_t) n_rows);
-        if (rc == 0) rc = dmalloc(&total, (size_t) n_rows);
-        if (rc == 0 && hipMalloc((void **) &cand, (size_t) n_rows * TOPK_PARTS * TOPK_MAXK * 8) != hipSuccess) rc = set_err("%s: out of device memory", what);
-        if (rc != 0) return drop(rc);
-        if (hipMemcpy(smp, init.data(), init.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(uni, uniforms, (size_t) n_rows * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return drop(set_err("%s: copy failed", what));
-    }
-    if (hipMemcpy2DAsync(c->l_logits, (size_t) c->l_Vpad * 4, logits, (size_t) c->l_V * 4, (size_t) c->l_V * 4, n_rows, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return drop(set_err("%s: copy failed", what));
-    if (llama_select_slots(c, sp, (int) n_rows, c->l_logits, nullptr, 0, nullptr, smp, uni, 1, cand, total) != 0) return drop(-1);
-    std::vector<uint32_t> back((size_t) 3 * n_rows);
-    bool ok = hipMemcpyAsync(tokens_out, c->l_btok, (size_t) n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-    if (ok && sp) ok = hipMemcpyAsync(back.data(), smp, back.size() * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
-    ok = hipStreamSynchronize(c->stream) == hipSuccess && ok;
-    if (!ok) return drop(set_err("%s: copy failed", what));
-    if (rep) for (uint32_t r = 0; r < n_rows; r++) { last_id[r] = (int32_t) back[3 * r]; rep_count[r] = back[3 * r + 1]; }
-    return drop(0);
-}
-
-extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling, const float *uniforms,
-                                                        int32_t *last_id, uint32_t *rep_count, uint32_t *tokens_out) {
-    const char *what = "tts_hip_orpheus_sample_logits_rows_mixed";
-    CHK(llama_stream_ready(c, what, false));
-    if (!logits || !tokens_out || !sampling) return set_err("%s: null argument", what);
+// the selection of the rows kernels on n_rows rows of caller-supplied logits; row r selects with at(r) (NULL: sampler::max)
+template <typename At>
+static int llama_sample_rows(tts_hip_ctx *c, const char *what, uint32_t n_rows, const float *logits, At at, const float *uniforms, int32_t *last_id, uint32_t *rep_count,
+                             uint32_t *tokens_out) {
     CHK(llama_gen_idle(c, what));
     if (n_rows == 0 || n_rows > c->lm.max_seqs) return set_err("%s: %u rows outside 1..max_seqs = %u", what, n_rows, c->lm.max_seqs);
     bool any_max = false, any_sample = false, any_nucleus = false;
     uint32_t mx = 0;
-    auto rep = [&](uint32_t r) { return sampling[r] && sampling[r]->repetition_penalty != 1.0f; };
+    auto rep = [&](uint32_t r) { return at(r) && at(r)->repetition_penalty != 1.0f; };
     for (uint32_t r = 0; r < n_rows; r++) {
-        const tts_hip_sampling *sp = sampling[r];
+        const tts_hip_sampling *sp = at(r);
         if (!sp) { any_max = true; continue; }
         CHK(check_llama_sampling(c, sp, what));
         if (!uniforms) return set_err("%s: null uniforms", what);
@@ -1125,7 +1006,7 @@ extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t
     std::vector<double> table((size_t) n_rows * len);
     std::vector<uint32_t> init((size_t) 3 * n_rows);
     for (uint32_t r = 0; r < n_rows; r++) {
-        llama_slot_sampler_host(sampling[r], len, &rec[r], table.data() + (size_t) r * len);
+        llama_slot_sampler_host(at(r), len, &rec[r], table.data() + (size_t) r * len);
         init[3 * r] = rep(r) ? (uint32_t) last_id[r] : 0xFFFFFFFFu; init[3 * r + 1] = rep(r) ? rep_count[r] : 0u; init[3 * r + 2] = 0u;
     }
     uint32_t *smp = nullptr;
@@ -1147,7 +1028,7 @@ extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t
         return drop(set_err("%s: copy failed", what));
     if (hipMemcpy2DAsync(c->l_logits, (size_t) c->l_Vpad * 4, logits, (size_t) c->l_V * 4, (size_t) c->l_V * 4, n_rows, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return drop(set_err("%s: copy failed", what));
-    if (llama_select_slots_mixed(c, any_max, any_sample, any_nucleus, (int) n_rows, c->l_logits, nullptr, 0, nullptr, samp, pen, len, smp, uni, 1, cand, total) != 0) return drop(-1);
+    if (llama_select_slots(c, any_max, any_sample, any_nucleus, (int) n_rows, c->l_logits, nullptr, 0, nullptr, samp, pen, len, smp, uni, 1, cand, total) != 0) return drop(-1);
     std::vector<uint32_t> back((size_t) 3 * n_rows);
     bool ok = hipMemcpyAsync(tokens_out, c->l_btok, (size_t) n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
     ok = ok && hipMemcpyAsync(back.data(), smp, back.size() * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
@@ -1156,6 +1037,27 @@ extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t
     for (uint32_t r = 0; r < n_rows; r++) if (rep(r)) { last_id[r] = (int32_t) back[3 * r]; rep_count[r] = back[3 * r + 1]; }
     return drop(0);
 }
+
+// one setting for all rows: the per-row entry with sp repeated
+extern "C" int tts_hip_orpheus_sample_logits_rows(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *sp, const float *uniforms, int32_t *last_id,
+                                                  uint32_t *rep_count, uint32_t *tokens_out) {
+    const char *what = "tts_hip_orpheus_sample_logits_rows";
+    CHK(llama_stream_ready(c, what, false));
+    if (!logits || !tokens_out) return set_err("%s: null argument", what);
+    return llama_sample_rows(c, what, n_rows, logits, [&](uint32_t) { return sp; }, uniforms, last_id, rep_count, tokens_out);
+}
+
+extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows, const float *logits, const tts_hip_sampling *const *sampling, const float *uniforms,
+                                                        int32_t *last_id, uint32_t *rep_count, uint32_t *tokens_out) {
+    const char *what = "tts_hip_orpheus_sample_logits_rows_mixed";
+    CHK(llama_stream_ready(c, what, false));
+    if (!logits || !tokens_out || !sampling) return set_err("%s: null argument", what);
+    return llama_sample_rows(c, what, n_rows, logits, [&](uint32_t r) { return sampling[r]; }, uniforms, last_id, rep_count, tokens_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dia (src/models/dia/model.cpp:383-659)
+// ------------------------------------------------------------------------------------------------
 
 extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *dd) {
     if (!dd || dd->struct_size != sizeof(tts_hip_dia_desc)) { set_err("tts_hip_dia_create: bad desc (struct_size mismatch)"); return nullptr; }
