@@ -675,9 +675,33 @@ const char *tts_hip_kclass_name(int kclass);
  *   run     n_steps lock-step decode steps over the live utterances; then *n_finished slots whose check_stopping() fired (EOS on every head,
  *           position == the cached positions, or max_steps reached) are reported with their step counts and become free
  *   collect the tokens [steps][heads] of a finished slot (before the slot is admitted again)
- * An utterance's tokens are those of a solo tts_hip_parler_generate_* run of the same prompt (tests/test_gpu_runner.py). */
+ * An utterance's tokens are those of a solo tts_hip_parler_generate_* run of the same prompt (tests/test_gpu_runner.py).
+ * Mixed session: begin_mixed is begin with every slot carrying its own sampler, so utterances that differ in top_k, top_p, temperature or
+ * repetition penalty, greedy ones among them, share one lock-step forward.  Its checks are begin's, and output_vocab_size <= 2048 also when every
+ * occupant will be greedy.  It sizes, once, the uniforms [max_steps + 1][n_slots + 1][heads], a sampler record per slot {mode, top_k, top_p,
+ * temperature, its own repetition-penalty table} — the padding slot's record is sampler::max for good — and the tables [n_slots][max_steps]; they
+ * stay on the context from one session to the next, and no admission reallocates or recaptures.
+ *   admit_mixed   admit with sampling[i] per utterance: sampling NULL or sampling[i] NULL means sampler::max, else the limits of
+ *           tts_hip_parler_generate_sampled (temperature, top_p, repetition_penalty > 0).  uniforms is [n][max_steps][heads]; the block of a
+ *           greedy utterance is ignored; uniforms may be NULL when all n are greedy and is refused with a sampled one.  Every check (admit's,
+ *           the sampler limits, the uniforms) runs for all n before anything is launched: a refusal returns non-zero, the session unchanged.
+ *           After the prompts' side batch ONE launch clears the slots' EOS flags and steps_done, resets last_token_ids /
+ *           repetition_counts (sampler::reset), writes each slot's record and its own table (pow(penalty, count) in double, evaluated on the
+ *           host) and scatters the draws into the slot's column, so nothing of the previous occupant survives.
+ * run, collect and end are the calls above and serve either kind of session.  A run whose live slots are all greedy replays the captured step of
+ * a uniform greedy session (the arg-max launch); any other run replays the mixed step, where ONE sample_kernel launch reads every row's record
+ * through its cache slot: a greedy row takes the kernel's first phase (sampler::max: first maximum wins, the id the arg-max kernel gives), reads
+ * no uniform and touches no sampler state.  Both graphs stay cached per row count: alternating between them recaptures nothing, and no
+ * admission recaptures.  admit_mixed on a session opened by begin, and admit on one opened by begin_mixed, return non-zero, the session unchanged.
+ * Equality (mixed): an utterance's tokens and step count are those of tts_hip_parler_generate_greedy / tts_hip_parler_generate_sampled for the
+ * same prompt with its own sampler and uniforms — whoever else is live, greedy or sampled, and whenever it entered
+ * (tests/test_gpu_parler_stream_mixed.py).  As for the uniform session this holds where the row count does not select another GEMM tile shape,
+ * that is another fp32 summation order: the row-count rounding pins it for the decode steps, the tests pin it for the reference run. */
 int tts_hip_parler_stream_begin(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sp);
 int tts_hip_parler_stream_admit(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens, const float *uniforms);
+int tts_hip_parler_stream_begin_mixed(tts_hip_ctx *ctx, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos);
+int tts_hip_parler_stream_admit_mixed(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens,
+                                      const tts_hip_sampling *const *sampling, const float *uniforms);
 int tts_hip_parler_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps);
 int tts_hip_parler_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t steps, uint32_t *tokens_out);
 int tts_hip_parler_stream_end(tts_hip_ctx *ctx);

@@ -1388,6 +1388,50 @@ static __global__ void feed_kernel(FeedArgs a) {
     }
 }
 
+// The admission of a mixed continuous session (tts_hip_parler_stream_admit_mixed): ONE launch for all admitted slots.  Everything here is
+// indexed by cache slot, as sample_kernel and feed_kernel read it through orig = the rows' cache slots.
+struct ParlerAdmitArgs {
+    int n, n_total, n_out;    // admitted utterances; slots + the padding slot (the stride of uni); heads
+    uint32_t max_steps;
+    const uint32_t *slots;    // [n] distinct, < n_total - 1
+    const float *uni_in;      // [n][max_steps][n_out] or NULL (every admitted utterance is greedy)
+    float *uni;               // [max_steps + 1][n_total][n_out] what sample_kernel reads
+    uint8_t *eos_seen;        // [n_total][n_out]
+    uint32_t *steps_done;     // [n_total]
+    int32_t *last;            // [n_total][n_out] sampler::last_token_ids
+    uint32_t *repc;           // [n_total][n_out] sampler::repetition_counts
+    const SampleRow *rec_in;  // [n]; pen_table already points at the slot's own table, or is NULL (penalty 1, or sampler::max)
+    SampleRow *rec;           // [n_total] what sample_kernel reads
+    const double *pen_in;     // [n][pen_len]
+    double *pen;              // [n_total - 1][pen_len]
+    int pen_len;
+};
+
+// blockIdx.y = admitted utterance; block x == 0 resets the slot (EOS flags, steps_done, sampler::reset, the record), all blocks move its penalty
+// table and its draws.  A greedy utterance's block of uni_in is ignored.
+static __global__ __launch_bounds__(256) void parler_stream_admit_kernel(ParlerAdmitArgs a) {
+    const int i = blockIdx.y;
+    if (i >= a.n) return;
+    const uint32_t u = a.slots[i];
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned) a.n_out) {
+        a.eos_seen[u * a.n_out + threadIdx.x] = 0;
+        a.last[u * a.n_out + threadIdx.x] = -1;
+        a.repc[u * a.n_out + threadIdx.x] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.steps_done[u] = 0;
+        a.rec[u] = a.rec_in[i];
+    }
+    if (a.rec_in[i].pen_table)
+        for (int e = blockIdx.x * 256 + threadIdx.x; e < a.pen_len; e += gridDim.x * 256) a.pen[(int64_t) u * a.pen_len + e] = a.pen_in[(int64_t) i * a.pen_len + e];
+    if (!a.uni_in || a.rec_in[i].mode != SAMPLE_ROW_SAMPLE) return;
+    const int64_t total = (int64_t) a.max_steps * a.n_out;
+    for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
+        const int64_t k = e / a.n_out, h = e - k * a.n_out;
+        a.uni[(k * a.n_total + u) * a.n_out + h] = a.uni_in[(int64_t) i * total + e];
+    }
+}
+
 // ================================================================================================
 // Quantised weights (GGUF Q4_0 / Q5_0 / Q8_0) with ggml's CPU semantics (upstream ggml knowledge, SURVEY.md
 // A.3): ggml_compute_forward_mul_mat converts the activation row to Q8_0 blocks (d = max|x|/127 per 32

@@ -259,6 +259,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     for (uint32_t *p : {c->di_tok, c->di_epos, c->di_eseq, c->di_kbeg, c->di_kend, c->di_ids, c->di_pos, c->di_seq, c->di_cend, c->di_stok, c->di_loop, c->di_hist, c->di_look, c->di_sbud, c->di_sadm}) free_dev(p);
     free_dev(c->di_suni);
     free_dev(c->di_srec); free_dev(c->di_srec_in); free_dev(c->di_spen); free_dev(c->di_spen_in);
+    free_dev(c->gs_rec); free_dev(c->gs_rec_in); free_dev(c->gs_pen); free_dev(c->gs_pen_in); free_dev(c->gs_adm); free_dev(c->gs_uni_in);
     free_dev(c->di_e16);
     for (int i = 0; i < 3; i++) free_dev(c->sbuf[i]);
     free_dev(c->s_in); free_dev(c->s_out);

@@ -1202,7 +1202,8 @@ extern "C" int tts_hip_parler_prefill_batch(tts_hip_ctx *c, uint32_t n, const ui
     return 0;
 }
 
-enum { MODE_LOGITS = 0, MODE_GREEDY = 1, MODE_GEN = 2, MODE_GEN_SAMPLE = 3 };
+enum { MODE_LOGITS = 0, MODE_GREEDY = 1, MODE_GEN = 2, MODE_GEN_SAMPLE = 3, MODE_GEN_MIXED = 4 };   // MODE_GEN_MIXED: sample_kernel over the slots' own records (c->gs_rec)
+static bool gen_mode(int mode) { return mode == MODE_GEN || mode == MODE_GEN_SAMPLE || mode == MODE_GEN_MIXED; }
 // captured steps are keyed mode * GRAPH_KEY_ROWS + rows (rows <= TTS_HIP_MAX_ROWS, 1024 by default); drop_gen_graphs() recovers the mode from the
 // key — with the two sites out of step (keys in units of 8192, the drop in units of 1000) the generation graphs were never dropped and a
 // replay used whatever sampling parameters / tokens_out pointer its capture had baked in
@@ -1229,7 +1230,7 @@ static int stage_step_inputs(tts_hip_ctx *c, uint32_t n, const uint32_t *ids, co
 
 // enqueue (or replay) one audio step for R rows in the given mode
 static int enqueue_step_body(tts_hip_ctx *c, int R, int mode, uint32_t bos, uint32_t eos) {
-    if (mode != MODE_GEN && mode != MODE_GEN_SAMPLE) {
+    if (!gen_mode(mode)) {
         HIPCHK(hipMemcpyAsync(c->d_ids, c->h_ids, (size_t) R * c->NO * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_seq, c->h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1248,11 +1249,19 @@ static int enqueue_step_body(tts_hip_ctx *c, int R, int mode, uint32_t bos, uint
             sa.last_ids = c->d_last; sa.rep_counts = c->d_repc;
             sa.orig = c->d_seq; sa.R_total = c->gen_total;   // the loop's rows sit in cache slot = utterance index
             hipLaunchKernelGGL(sample_kernel, dim3(c->NO, R), dim3(256), 0, c->stream, sa);
+        } else if (mode == MODE_GEN_MIXED) {   // every row with the record of its cache slot: settings, its own penalty table, or sampler::max
+            SampleArgs sa{};
+            sa.logits = c->logits; sa.V = c->V; sa.n_out = c->NO; sa.R = R;
+            sa.uniforms = c->d_uniforms; sa.row_step = c->d_step; sa.out = c->d_tok;
+            sa.last_ids = c->d_last; sa.rep_counts = c->d_repc;
+            sa.orig = c->d_seq; sa.R_total = c->gen_total;
+            sa.rows = (const SampleRow *) c->gs_rec;
+            hipLaunchKernelGGL(sample_kernel, dim3(c->NO, R), dim3(256), 0, c->stream, sa);
         } else {
             hipLaunchKernelGGL(argmax_kernel, dim3(R * c->NO), dim3(256), 0, c->stream, (const float *) c->logits, c->V, c->d_tok);
         }
         HIPCHK(hipGetLastError());
-        if (mode == MODE_GEN || mode == MODE_GEN_SAMPLE) {
+        if (gen_mode(mode)) {
             FeedArgs f{};
             f.tokens = c->d_tok; f.ids = c->d_ids; f.row_pos = c->d_pos; f.row_step = c->d_step; f.eos_seen = c->d_eos;
             f.steps_done = c->d_steps_done; f.tokens_out = c->d_tokens_out; f.R = R; f.n_out = c->NO; f.bos = bos; f.eos = eos;
@@ -1303,7 +1312,7 @@ extern "C" int tts_hip_parler_step_greedy(tts_hip_ctx *c, uint32_t n, const uint
 static void drop_gen_graphs(tts_hip_ctx *c) {
     for (auto g = c->graphs.begin(); g != c->graphs.end();) {
         const int mode = g->first / GRAPH_KEY_ROWS;   // run_step's key
-        if (mode == MODE_GEN || mode == MODE_GEN_SAMPLE) { (void) hipGraphExecDestroy(g->second); g = c->graphs.erase(g); } else ++g;
+        if (gen_mode(mode)) { (void) hipGraphExecDestroy(g->second); g = c->graphs.erase(g); } else ++g;
     }
 }
 
@@ -1557,15 +1566,50 @@ extern "C" int tts_hip_parler_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uin
 // An utterance's tokens do not depend on when it was admitted or on its neighbours: every kernel of the forward works row by row, and the
 // GEMM tile a row count selects is pinned by the row-count rounding (tests/test_gpu_runner.py: admitted mid-flight == solo run).
 // ------------------------------------------------------------------------------------------------
-extern "C" int tts_hip_parler_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sp) {
-    CHK(ready(c, "tts_hip_parler_stream_begin"));
+// both begin calls.  mixed (sp NULL): every slot carries its own sampler record and penalty table [max_steps], sampler::max until an admission
+// writes them; the uniforms block and the sampler state exist whatever the occupants turn out to be.
+static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sp) {
+    CHK(ready(c, what));
     if (n_slots == 0 || n_slots + 1 > c->d.max_seqs || (int) n_slots > c->RMAX) return set_err("stream_begin: %u slots need a context with max_seqs >= %u (have %u) and <= %d rows", n_slots, n_slots + 1, c->d.max_seqs, c->RMAX);
     if (max_steps == 0) return set_err("stream_begin: max_steps == 0");
     if (bos >= (uint32_t) c->EROWS || eos >= (uint32_t) c->EROWS) return set_err("stream_begin: bos/eos outside the embedding table");
+    if (mixed && c->V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, c->V, SMP_VMAX);   // every row of a mixed step goes through sample_kernel
     auto &g = c->gs;
     g = tts_hip_ctx::GenStream{};
     g.n_slots = n_slots; g.max_steps = max_steps; g.bos = bos; g.eos = eos; g.sampled = sp != nullptr;
     const uint32_t RT = n_slots + 1;
+    if (mixed) {
+        // everything an admission writes into is sized here, once: no admission reallocates what a captured launch holds
+        const size_t count = (size_t) (max_steps + 1) * RT * c->NO;
+        if (count > c->uniforms_cap) {
+            free_dev(c->d_uniforms); c->d_uniforms = nullptr; c->uniforms_cap = 0;
+            HIPCHK(hipMalloc((void **) &c->d_uniforms, count * 4));
+            c->uniforms_cap = count;
+            drop_gen_graphs(c);
+            // once: an admission writes a sampled slot's whole column; the plane after the last is read by a row that spent its budget inside a
+            // chunk, whose id is recorded nowhere
+            HIPCHK(hipMemsetAsync(c->d_uniforms, 0, count * 4, c->stream));
+        }
+        if ((size_t) RT > c->gs_rec_cap) {
+            free_dev(c->gs_rec); free_dev(c->gs_rec_in); free_dev(c->gs_adm);
+            c->gs_rec = c->gs_rec_in = nullptr; c->gs_adm = nullptr; c->gs_rec_cap = 0;
+            HIPCHK(hipMalloc(&c->gs_rec, (size_t) RT * sizeof(SampleRow)));
+            HIPCHK(hipMalloc(&c->gs_rec_in, (size_t) RT * sizeof(SampleRow)));
+            HIPCHK(hipMalloc((void **) &c->gs_adm, (size_t) RT * 4));
+            c->gs_rec_cap = RT;
+            drop_gen_graphs(c);   // the captured MODE_GEN_MIXED launch holds gs_rec
+        }
+        if ((size_t) n_slots * max_steps > c->gs_pen_cap) {   // reached through the records alone: no captured launch holds it
+            free_dev(c->gs_pen);
+            c->gs_pen = nullptr; c->gs_pen_cap = 0;
+            HIPCHK(hipMalloc((void **) &c->gs_pen, (size_t) n_slots * max_steps * 8));
+            c->gs_pen_cap = (size_t) n_slots * max_steps;
+        }
+        c->gs_pen_len = (int) max_steps;
+        HIPCHK(hipMemsetAsync(c->gs_rec, 0, c->gs_rec_cap * sizeof(SampleRow), c->stream));   // SAMPLE_ROW_MAX, no table: the padding slot's for good
+        g.mixed = true;
+        g.slot_sampled.assign(n_slots, 0);
+    }
     if (sp) {
         CHK(check_sampling(c, sp, "tts_hip_parler_stream_begin"));
         if (sp->top_k != c->smp.top_k || sp->top_p != c->smp.top_p || sp->temperature != c->smp.temperature ||
@@ -1599,19 +1643,62 @@ extern "C" int tts_hip_parler_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uin
     return 0;
 }
 
-extern "C" int tts_hip_parler_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens, const float *uniforms) {
-    CHK(ready(c, "tts_hip_parler_stream_admit"));
+extern "C" int tts_hip_parler_stream_begin(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sp) {
+    return parler_stream_begin(c, "tts_hip_parler_stream_begin", false, n_slots, max_steps, bos, eos, sp);
+}
+
+extern "C" int tts_hip_parler_stream_begin_mixed(tts_hip_ctx *c, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos) {
+    return parler_stream_begin(c, "tts_hip_parler_stream_begin_mixed", true, n_slots, max_steps, bos, eos, nullptr);
+}
+
+// both admissions.  mixed: sampling [n] (NULL, or an entry NULL: sampler::max); one parler_stream_admit_kernel launch rewrites the slots' records,
+// tables, sampler state, EOS flags, steps_done and uniform columns.  Every check runs for all n before anything is launched.
+static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens,
+                               const tts_hip_sampling *const *sampling, const float *uniforms) {
+    CHK(ready(c, what));
     auto &g = c->gs;
     if (!g.active) return set_err("stream_admit: no stream (tts_hip_parler_stream_begin)");
+    if (mixed != g.mixed)
+        return set_err(mixed ? "%s: the session was opened by tts_hip_parler_stream_begin (tts_hip_parler_stream_admit)"
+                             : "%s: the session was opened by tts_hip_parler_stream_begin_mixed (tts_hip_parler_stream_admit_mixed)", what);
     if (n == 0) return 0;
     if (!slots || !ids || !lens) return set_err("stream_admit: null argument");
     if (g.sampled && !uniforms) return set_err("stream_admit: a sampled stream needs the utterances' uniforms [n][max_steps][heads]");
     const uint32_t RT = g.n_slots + 1, max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS);
-    for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("stream_admit: slot %u >= %u", slots[i], g.n_slots);
-        if (g.slot_live[slots[i]]) return set_err("stream_admit: slot %u is still generating", slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("stream_admit: slot %u named twice", slots[i]);
-        if (lens[i] == 0 || lens[i] >= max_pos) return set_err("stream_admit: prompt of %u ids leaves no room in %u cached positions", lens[i], max_pos);
+    bool any_sampled = false, any_rep = false;
+    {
+        size_t off = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (slots[i] >= g.n_slots) return set_err("stream_admit: slot %u >= %u", slots[i], g.n_slots);
+            if (g.slot_live[slots[i]]) return set_err("stream_admit: slot %u is still generating", slots[i]);
+            for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("stream_admit: slot %u named twice", slots[i]);
+            if (lens[i] == 0 || lens[i] >= max_pos) return set_err("stream_admit: prompt of %u ids leaves no room in %u cached positions", lens[i], max_pos);
+            for (uint32_t j = 0; j < lens[i]; j++)
+                if (ids[off + j] >= (uint32_t) c->PV) return set_err("stream_admit: text id %u >= prompt vocab %d", ids[off + j], c->PV);
+            off += lens[i];
+            const tts_hip_sampling *sp = mixed && sampling ? sampling[i] : nullptr;
+            if (!sp) continue;
+            CHK(check_sampling(c, sp, what));
+            if (!uniforms) return set_err("%s: utterance %u is sampled: it needs uniforms [n][max_steps][heads]", what, i);
+            any_sampled = true;
+            any_rep = any_rep || sp->repetition_penalty != 1.0f;
+        }
+    }
+    const size_t per = (size_t) g.max_steps * c->NO;
+    if (mixed) {   // the staging copies grow before anything is launched; no captured launch holds them
+        const int len = c->gs_pen_len;
+        if (any_sampled && n * per > c->gs_uni_in_cap) {
+            free_dev(c->gs_uni_in);
+            c->gs_uni_in = nullptr; c->gs_uni_in_cap = 0;
+            HIPCHK(hipMalloc((void **) &c->gs_uni_in, n * per * 4));
+            c->gs_uni_in_cap = n * per;
+        }
+        if (any_rep && (size_t) n * len > c->gs_pen_in_cap) {
+            free_dev(c->gs_pen_in);
+            c->gs_pen_in = nullptr; c->gs_pen_in_cap = 0;
+            HIPCHK(hipMalloc((void **) &c->gs_pen_in, (size_t) n * len * 8));
+            c->gs_pen_in_cap = (size_t) n * len;
+        }
     }
     {   // The newcomers' prompts as one side batch (prefill_batch's rows), padded with rows of the padding slot to the row counts the decode steps
         // use (multiples of 64): a lone 5-id prompt would otherwise run through the small-batch GEMM kernels (other summation order than the
@@ -1619,10 +1706,7 @@ extern "C" int tts_hip_parler_stream_admit(tts_hip_ctx *c, uint32_t n, const uin
         std::vector<uint32_t> rs, rp, ri;
         size_t off = 0;
         for (uint32_t i = 0; i < n; i++) {
-            for (uint32_t j = 0; j < lens[i]; j++) {
-                if (ids[off + j] >= (uint32_t) c->PV) return set_err("stream_admit: text id %u >= prompt vocab %d", ids[off + j], c->PV);
-                rs.push_back(slots[i]); rp.push_back(j); ri.push_back(ids[off + j]);
-            }
+            for (uint32_t j = 0; j < lens[i]; j++) { rs.push_back(slots[i]); rp.push_back(j); ri.push_back(ids[off + j]); }
             off += lens[i];
         }
         for (size_t o = 0; o < rs.size(); o += (size_t) c->RMAX) {
@@ -1643,8 +1727,49 @@ extern "C" int tts_hip_parler_stream_admit(tts_hip_ctx *c, uint32_t n, const uin
             HIPCHK(hipStreamSynchronize(c->stream));
         }
     }
+    // a mixed session: per utterance its record, and pow(penalty, count) in double as stage_penalty evaluates it, through the staging copies
+    std::vector<SampleRow> recs(mixed ? n : 0);
+    std::vector<double> tabs;
+    if (mixed) {
+        const int len = c->gs_pen_len;
+        tabs.resize(any_rep ? (size_t) n * len : 0);
+        for (uint32_t i = 0; i < n; i++) {
+            const tts_hip_sampling *sp = sampling ? sampling[i] : nullptr;
+            SampleRow &r = recs[i];
+            r = SampleRow{};
+            r.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
+            r.top_k = sp ? sp->top_k : 0u; r.top_p = sp ? sp->top_p : 1.0f; r.temperature = sp ? sp->temperature : 1.0f;
+            r.pen_len = len;
+            if (sp && sp->repetition_penalty != 1.0f) {
+                r.pen_table = c->gs_pen + (size_t) slots[i] * len;
+                for (int k = 0; k < len; k++) tabs[(size_t) i * len + k] = pow((double) sp->repetition_penalty, (double) k);
+            }
+        }
+        HIPCHK(hipMemcpyAsync(c->gs_adm, slots, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->gs_rec_in, recs.data(), recs.size() * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
+        if (any_rep) HIPCHK(hipMemcpyAsync(c->gs_pen_in, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
+        if (any_sampled) HIPCHK(hipMemcpyAsync(c->gs_uni_in, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
+        ParlerAdmitArgs a{};
+        a.n = (int) n; a.n_total = (int) RT; a.n_out = c->NO; a.max_steps = g.max_steps;
+        a.slots = c->gs_adm;
+        a.uni_in = any_sampled ? c->gs_uni_in : nullptr; a.uni = c->d_uniforms;
+        a.eos_seen = c->d_eos; a.steps_done = c->d_steps_done; a.last = c->d_last; a.repc = c->d_repc;
+        a.rec_in = (const SampleRow *) c->gs_rec_in; a.rec = (SampleRow *) c->gs_rec; a.pen_in = c->gs_pen_in; a.pen = c->gs_pen; a.pen_len = len;
+        const unsigned bx = any_sampled || any_rep ? (unsigned) std::min<size_t>((std::max(per, (size_t) len) + 255) / 256, 64) : 1u;
+        hipLaunchKernelGGL(parler_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t s = slots[i];
+        if (mixed) {
+            g.slot_sampled[s] = sampling && sampling[i];
+            g.slot_live[s] = 1;
+            g.row_slot.push_back(s);
+            g.pos.push_back(lens[i]);
+            g.step.push_back(1);
+            for (int h = 0; h < c->NO; h++) g.ids.push_back(g.bos);
+            continue;
+        }
         HIPCHK(hipMemsetAsync(c->d_eos + (size_t) s * c->NO, 0, (size_t) c->NO, c->stream));
         HIPCHK(hipMemsetAsync(c->d_steps_done + s, 0, 4, c->stream));
         if (g.sampled) {
@@ -1662,8 +1787,17 @@ extern "C" int tts_hip_parler_stream_admit(tts_hip_ctx *c, uint32_t n, const uin
         g.step.push_back(1);
         for (int h = 0; h < c->NO; h++) g.ids.push_back(g.bos);
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // recs and tabs are locals, slots and uniforms the caller's
     return 0;
+}
+
+extern "C" int tts_hip_parler_stream_admit(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens, const float *uniforms) {
+    return parler_stream_admit(c, "tts_hip_parler_stream_admit", false, n, slots, ids, lens, nullptr, uniforms);
+}
+
+extern "C" int tts_hip_parler_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens,
+                                                 const tts_hip_sampling *const *sampling, const float *uniforms) {
+    return parler_stream_admit(c, "tts_hip_parler_stream_admit_mixed", true, n, slots, ids, lens, sampling, uniforms);
 }
 
 extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
@@ -1688,7 +1822,11 @@ extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint3
     HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_seq, c->h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_step, c->h_tok, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
-    const int mode = g.sampled ? MODE_GEN_SAMPLE : MODE_GEN;
+    // a mixed session whose live slots are all greedy replays the arg-max graph of a uniform greedy session, launch for launch; both graphs stay
+    // cached per row count, so alternating between them captures nothing
+    int mode = g.sampled ? MODE_GEN_SAMPLE : MODE_GEN;
+    if (g.mixed)
+        for (uint32_t r = 0; r < live; r++) if (g.slot_sampled[g.row_slot[r]]) { mode = MODE_GEN_MIXED; break; }
     c->host_pos.resize(R);
     const uint32_t max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS);
     for (uint32_t s = 0; s < n_steps; s++) {

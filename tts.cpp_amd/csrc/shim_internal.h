@@ -316,10 +316,23 @@ struct tts_hip_ctx {
     // continuous batching (tts_hip_parler_stream_*): the rows' state between two stream_run calls lives on the host
     struct GenStream {
         bool active = false, sampled = false;
+        bool mixed = false;              // opened by tts_hip_parler_stream_begin_mixed: every slot carries its own sampler (gs_rec)
         uint32_t n_slots = 0, max_steps = 0, bos = 0, eos = 0;
         std::vector<uint8_t> slot_live;
+        std::vector<uint8_t> slot_sampled;   // mixed: the slot's occupant is sampled (a run whose live slots are all greedy replays MODE_GEN)
         std::vector<uint32_t> row_slot, pos, step, ids;   // live rows: cache slot, next position, step counter, next input ids [rows][heads]
     } gs;
+    // a mixed session's sampler records and penalty tables, kept from one session to the next.  gs_rec [slots + 1] is what the captured
+    // MODE_GEN_MIXED sample_kernel launch holds (the padding slot's record stays SAMPLE_ROW_MAX); the tables [slots][gs_pen_len] are reached
+    // through the records' pointers.  The *_in copies and gs_adm / gs_uni_in stage one admission for parler_stream_admit_kernel.
+    void *gs_rec = nullptr, *gs_rec_in = nullptr;
+    size_t gs_rec_cap = 0;               // records either holds
+    double *gs_pen = nullptr, *gs_pen_in = nullptr;
+    size_t gs_pen_cap = 0, gs_pen_in_cap = 0;   // doubles
+    int gs_pen_len = 0;                  // entries per slot in the open mixed session (its max_steps)
+    uint32_t *gs_adm = nullptr;          // device [gs_rec_cap]: the slots of one admission
+    float *gs_uni_in = nullptr;          // device: the admitted utterances' uniforms before they move into their columns
+    size_t gs_uni_in_cap = 0;
     uint32_t gs_baked_steps = 0;    // ... and the step budget they carry
     bool gs_graphs = false;         // the captured generation graphs were made for a stream (feed_kernel's padding slot baked in)
     // the generation loop between tts_hip_parler_gen_begin and its last gen_wait: launch enqueues steps, wait looks in

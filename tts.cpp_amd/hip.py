@@ -97,6 +97,7 @@ EXPORTS = [
     "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
     "tts_hip_dia_stream_begin_mixed", "tts_hip_dia_stream_admit_mixed", "tts_hip_sample_logits_rows_mixed",
+    "tts_hip_parler_stream_begin_mixed", "tts_hip_parler_stream_admit_mixed",
 ]
 
 class Sampling(C.Structure):
@@ -226,6 +227,8 @@ def load_lib():
     L.tts_hip_dia_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DiaCodes)]
     L.tts_hip_dia_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
     L.tts_hip_sample_logits_rows_mixed.argtypes = [vp, C.c_uint32, f32p, C.POINTER(C.POINTER(Sampling)), f32p, C.POINTER(C.c_int32), u32p, u32p]
+    L.tts_hip_parler_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.tts_hip_parler_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
     _lib = L
     return L
 
@@ -440,6 +443,26 @@ class HipEngine:
             u = np.ascontiguousarray(uniforms, dtype=np.float32)
             up = u.ctypes.data_as(C.POINTER(C.c_float))
         self._chk(self.L.tts_hip_parler_stream_admit(self.ctx, len(s), sp, cp, lp, up))
+
+    def stream_begin_mixed(self, n_slots, max_steps, bos=None, eos=None):
+        """a session whose slots carry their own sampler (stream_admit_mixed); run / collect / end as for stream_begin"""
+        self._chk(self.L.tts_hip_parler_stream_begin_mixed(self.ctx, n_slots, max_steps, self.cfg.bos if bos is None else bos, self.cfg.eos if eos is None else eos))
+        self._stream_slots = n_slots
+
+    def stream_admit_mixed(self, slots, prompts, settings, uniforms=None):
+        """stream_admit with settings per utterance: None (greedy) or a dict of top_k / top_p / temperature / repetition_penalty; uniforms
+        [n][max_steps][n_out] (a greedy utterance's block is ignored; None when every utterance is greedy)"""
+        s, sp = _u32(slots)
+        assert len(prompts) == s.size and len(settings) == s.size
+        lens, lp = _u32([len(p) for p in prompts])
+        cat, cp = _u32(np.concatenate([np.asarray(p, dtype=np.uint32) for p in prompts]))
+        arr, keep = sampling_rows(settings)
+        up = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32)
+            assert u.size % (s.size * self.cfg.n_out) == 0
+            up = u.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self.L.tts_hip_parler_stream_admit_mixed(self.ctx, len(s), sp, cp, lp, arr, up))
 
     def stream_run(self, n_steps):
         """-> [(slot, steps)] of the utterances that finished inside these steps"""

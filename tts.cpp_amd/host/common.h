@@ -130,7 +130,8 @@ struct tts_generation_runner : tts_runner {
     virtual void     stream_end();
     // per-request configurations: stream_accepts() says whether THIS open session can take a request with `config` although it differs from the one
     // the session was opened with (orpheus_runner: the voice is a prompt prefix and every cache slot carries its own sampler; dia_runner: every slot
-    // carries its own sampler, seed and step budget, up to the length the session was opened for; the default, and every other runner so far: no),
+    // carries its own sampler, seed and step budget, up to the length the session was opened for; parler_runner: every slot carries its own sampler
+    // and seed where a head has at most 2048 logits, the voice description stays the session's; the default, and every other runner so far: no),
     // and the three-argument stream_submit() enters such a request; its default ignores `config` — the caller has established that it equals
     // the session's.  A request stream_accepts() would refuse makes stream_submit() fail like a bad prompt does
     // (TTS_ABORT), with the session unchanged.

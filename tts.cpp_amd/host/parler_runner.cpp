@@ -496,6 +496,11 @@ void parler_runner::generate_batch_chunked(const std::vector<std::string> & sent
 static constexpr uint32_t STREAM_CHUNK = 32;     // decode steps between two look-in points (what generate_loop's compaction uses)
 static constexpr size_t   STREAM_CODEC_GROUP = 64;   // finished utterances per codec pass (the device's pass size); flushed when the session drains
 
+// the limits of the device sampler (tts_hip_parler_stream_admit_mixed); a greedy request never reads them
+static bool device_sampler(const generation_configuration & config) {
+    return !config.sample || (config.temperature > 0.0f && config.top_p > 0.0f && config.repetition_penalty > 0.0f);
+}
+
 void parler_runner::stream_begin(const generation_configuration & config) {
     if (stream_capacity() == 0) TTS_ABORT("stream_begin: the runner was loaded with max_seqs=%u; a session needs >= 2 (TTS_HIP_MAX_SEQS)\n", max_seqs);
     if (config.use_cross_attn != use_cross_attn) TTS_ABORT("stream_begin: use_cross_attn differs from load time\n");
@@ -504,8 +509,14 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     const uint32_t slots = stream_capacity();
     st_cfg = config;
     st_max_steps = hp.max_generation_size - 1;   // an utterance ends at position max_generation (check_stopping): at most this many steps after a 1-id prompt
-    const tts_hip_sampling sp{(uint32_t) config.top_k, config.top_p, config.temperature, config.repetition_penalty};
-    hip_check(tts_hip_parler_stream_begin(ctx, slots, st_max_steps, hp.bos_token_id, hp.eos_token_id, config.sample ? &sp : nullptr), "tts_hip_parler_stream_begin");
+    // the device sampler's vocabulary: every slot carries its own sampler record (stream_accepts); above it the session is greedy with one setting
+    st_mixed = hp.output_vocab_size <= 2048;
+    if (st_mixed) {
+        if (!device_sampler(config)) TTS_ABORT("stream_begin: temperature, top_p and repetition_penalty must be > 0 (got %g, %g, %g)\n", config.temperature, config.top_p, config.repetition_penalty);
+        hip_check(tts_hip_parler_stream_begin_mixed(ctx, slots, st_max_steps, hp.bos_token_id, hp.eos_token_id), "tts_hip_parler_stream_begin_mixed");
+    } else {
+        hip_check(tts_hip_parler_stream_begin(ctx, slots, st_max_steps, hp.bos_token_id, hp.eos_token_id, nullptr), "tts_hip_parler_stream_begin");
+    }
     st_free.clear();
     for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
     st_ticket.assign(slots, 0);
@@ -516,11 +527,21 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     st_on = true;
 }
 
-void parler_runner::stream_submit(size_t ticket, const std::string & sentence) {
+bool parler_runner::stream_accepts(const generation_configuration & config) const {
+    return st_on && st_mixed && config.use_cross_attn == use_cross_attn && device_sampler(config);
+}
+
+void parler_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
+
+void parler_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
     if (st_free.empty()) TTS_ABORT("stream_submit: no free row (stream_free() == 0)\n");
+    if (config.use_cross_attn != use_cross_attn) TTS_ABORT("stream_submit: use_cross_attn differs from load time\n");
+    if (st_mixed && !device_sampler(config))
+        TTS_ABORT("stream_submit: temperature, top_p and repetition_penalty must be > 0 (got %g, %g, %g)\n", config.temperature, config.top_p, config.repetition_penalty);
     pending p;
     p.ticket = ticket;
+    p.cfg = st_mixed ? config : st_cfg;   // a session without per-slot samplers runs everything with the configuration it was opened with
     if (!tokenize_prompt(sentence, p.prompt)) {
         // generate() answers such a prompt with an empty response: the session does the same at its next step
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", p.prompt.size());
@@ -540,20 +561,29 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
     if (!st_wait.empty()) {   // the newcomers: one prefill side batch, then rows of the lock-step forward
         std::vector<uint32_t> slots, ids, lens;
         std::vector<float> uni;
-        for (auto & p : st_wait) {
+        std::vector<tts_hip_sampling> sps(st_wait.size());
+        std::vector<const tts_hip_sampling *> spp(st_wait.size(), nullptr);
+        bool any_sampled = false;
+        for (const auto & p : st_wait) any_sampled = any_sampled || p.cfg.sample;
+        if (st_mixed && any_sampled) uni.assign(st_wait.size() * (size_t) st_max_steps * nh, 0.0f);   // [n][max_steps][heads]; a greedy utterance's block is ignored
+        for (size_t i = 0; i < st_wait.size(); i++) {
+            const pending & p = st_wait[i];
             slots.push_back(p.slot);
             lens.push_back((uint32_t) p.prompt.size());
             ids.insert(ids.end(), p.prompt.begin(), p.prompt.end());
             st_ticket[p.slot] = p.ticket;
             st_start[p.slot] = (uint32_t) p.prompt.size();
-            if (st_cfg.sample) {   // the utterance's own sampler, seeded as a generate() call of its own would be
-                const size_t o = uni.size();
-                uni.resize(o + (size_t) st_max_steps * nh);
-                draw_row_uniforms(smp, st_cfg.seed, st_max_steps, nh, uni.data() + o);
-            }
+            if (!st_mixed || !p.cfg.sample) continue;
+            // the utterance's own sampler and draws, seeded as a generate() call of its own would be
+            sps[i] = tts_hip_sampling{(uint32_t) p.cfg.top_k, p.cfg.top_p, p.cfg.temperature, p.cfg.repetition_penalty};
+            spp[i] = &sps[i];
+            draw_row_uniforms(smp, p.cfg.seed, st_max_steps, nh, uni.data() + i * (size_t) st_max_steps * nh);
         }
-        hip_check(tts_hip_parler_stream_admit(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), st_cfg.sample ? uni.data() : nullptr),
-                  "tts_hip_parler_stream_admit");
+        if (st_mixed)
+            hip_check(tts_hip_parler_stream_admit_mixed(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), spp.data(), any_sampled ? uni.data() : nullptr),
+                      "tts_hip_parler_stream_admit_mixed");
+        else
+            hip_check(tts_hip_parler_stream_admit(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), nullptr), "tts_hip_parler_stream_admit");
         st_wait.clear();
     }
     std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());

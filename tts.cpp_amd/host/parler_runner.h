@@ -62,7 +62,13 @@ struct parler_runner final : tts_generation_runner {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return (uint32_t) st_free.size(); }
     uint32_t stream_live() const override { return st_live + (uint32_t) st_codec.size(); }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;
+    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
+    // With at most 2048 logits per head the session is a mixed one (tts_hip_parler_stream_begin_mixed): every slot carries its own sampler record
+    // and penalty table, so a request may differ from the session's configuration in sample, seed, top_k, top_p, temperature and
+    // repetition_penalty.  It is accepted when use_cross_attn is the load-time value and it is greedy or within the device sampler's limits; its
+    // uniforms are drawn from its own seed, as a generate() call of its own draws them.  The voice description stays the session's.
+    bool     stream_accepts(const generation_configuration & config) const override;
+    void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
     void *   device_context() const override { return ctx; }
@@ -101,9 +107,10 @@ struct parler_runner final : tts_generation_runner {
     std::vector<std::vector<uint32_t>> run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook);
     std::vector<tts_response> decode_frames(const std::vector<uint32_t> & codes, const std::vector<uint32_t> & frames);
     // session state of the continuous batching
-    struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; };
+    struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; generation_configuration cfg; };
     struct decoded { size_t ticket; std::vector<uint32_t> frames; };   // un-delayed codes waiting for a codec pass
     bool                        st_on = false;
+    bool                        st_mixed = false;    // the open session carries a sampler per slot
     generation_configuration    st_cfg{};
     uint32_t                    st_live = 0, st_max_steps = 0;
     uint32_t                    st_codec_hold = 1;   // tts_load_options::stream_codec_hold at load time
