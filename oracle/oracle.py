@@ -474,6 +474,18 @@ class DacOracle:
         assert n == pcm.size
         return (pcm, st) if stage >= 0 else pcm
 
+    def decode_stages(self, codes):
+        """-> (pcm, [every stage]) from one decode"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32).reshape(-1, self.cfg.n_out)
+        frames = codes.shape[0]
+        shapes = [self.stage_shape(st, frames) for st in range(2 + len(self.cfg.strides))]
+        pcm = np.empty(frames * self.cfg.hop, dtype=np.float32)
+        buf = np.empty(sum(c * l for c, l in shapes), dtype=np.float32)
+        n = self.L.orc_dac_decode(C.byref(self.m), u32p(codes), frames, f32p(pcm), -2, f32p(buf))
+        assert n == pcm.size
+        cuts = np.cumsum([c * l for c, l in shapes])[:-1]
+        return pcm, [a.reshape(sh) for a, sh in zip(np.split(buf, cuts), shapes)]
+
 
 class SnacOracle:
     """Oracle twin of a tts_cpp_amd.synth.SynthSnac (src/decoder/snac_model.cpp restated in tts_oracle.c)."""

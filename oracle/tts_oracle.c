@@ -831,6 +831,13 @@ static void round_buf_f16(float *x, size_t n) {
     for (int64_t i = 0; i < (int64_t) n; i++) x[i] = orc_h2f(orc_f2h(x[i]));
 }
 
+/* stage k of orc_dac_decode: copied when it is the one asked for, or appended when every stage is (stage == -2) */
+static void dac_stage(int want, int k, float **out, const float *src, size_t n) {
+    if (!*out || (want != k && want != -2)) return;
+    memcpy(*out, src, n * 4);
+    if (want == -2) *out += n;
+}
+
 int64_t orc_dac_decode(const orc_dac_model *m, const uint32_t *codes, int frames, float *pcm_out,
                        int stage, float *stage_out) {
     int64_t L = frames;
@@ -859,14 +866,14 @@ int64_t orc_dac_decode(const orc_dac_model *m, const uint32_t *codes, int frames
             }
         }
     }
-    if (stage == 0 && stage_out) memcpy(stage_out, cur, (size_t) C * L * 4);
+    dac_stage(stage, 0, &stage_out, cur, (size_t) C * L);
 
     /* initial conv k7 pad 3 (dac_model.cpp:158-159) */
     float *nxt = (float *) malloc((size_t) m->c0 * L * 4);
     if (h) round_buf_f16(cur, (size_t) C * L);
     orc_conv1d(cur, C, L, m->init_w, m->init_b, m->c0, 7, 3, 1, nxt);
     free(cur); cur = nxt; C = m->c0;
-    if (stage == 1 && stage_out) memcpy(stage_out, cur, (size_t) C * L * 4);
+    dac_stage(stage, 1, &stage_out, cur, (size_t) C * L);
 
     for (int bi = 0; bi < m->n_blocks; bi++) { /* build_layer (general_neural_audio_codec.cpp:151-164) */
         const orc_dac_block *b = &m->blocks[bi];
@@ -892,7 +899,7 @@ int64_t orc_dac_decode(const orc_dac_model *m, const uint32_t *codes, int frames
             for (size_t i = 0; i < (size_t) C * L; i++) cur[i] = t1[i] + cur[i];
         }
         free(t1); free(t2);
-        if (stage == 2 + bi && stage_out) memcpy(stage_out, cur, (size_t) C * L * 4);
+        dac_stage(stage, 2 + bi, &stage_out, cur, (size_t) C * L);
     }
     /* final snake, conv k7 -> 1 channel, tanh (dac_model.cpp:163-166) */
     orc_snake(cur, C, L, m->final_alpha);

@@ -180,7 +180,8 @@ typedef struct {
 
 /* codes: frame-major [frames][n_codebooks] (dac_model.cpp:112); pcm_out: frames*prod(strides).
  * stage_out (optional): if stage>=0 the activation after that stage is copied there:
- *   stage 0 = quantizer sum [latent][T], 1 = after initial conv, 2..1+n_blocks = after block i. */
+ *   stage 0 = quantizer sum [latent][T], 1 = after initial conv, 2..1+n_blocks = after block i;
+ *   stage -2 = all of them back to back (one decode instead of one per stage). */
 int64_t orc_dac_decode(const orc_dac_model *m, const uint32_t *codes, int frames, float *pcm_out,
                        int stage, float *stage_out);
 

@@ -88,8 +88,9 @@ def snake(x, alpha):
     return x + torch.sin(a * x) ** 2 / a
 
 
-def torch_dac(model, codes, stages=False):
-    """DAC decoder (src/decoder/dac_model.cpp:146-170) in float64 torch. codes [frames][n_out]."""
+def torch_dac(model, codes, stages=False, last_stage=None):
+    """DAC decoder (src/decoder/dac_model.cpp:146-170) in float64 torch. codes [frames][n_out].
+    last_stage = k: the list of stages 0..k alone (0 the quantizer sum, 1 the first conv, 2 + i the end of block i), nothing beyond is computed."""
     c = model.cfg
     codes = torch.as_tensor(np.asarray(codes, dtype=np.int64)).reshape(-1, c.n_out)
     x = 0
@@ -98,9 +99,13 @@ def torch_dac(model, codes, stages=False):
         e = T(model, p + "codebook.weight")[codes[:, i]].t()[None]  # [1][dim][T]
         x = x + Fn.conv1d(e, T(model, p + "out_proj.weight"), T(model, p + "out_proj.bias"))
     outs = [x[0]]
+    if last_stage == 0:
+        return outs
     x = Fn.conv1d(x, T(model, "audio_encoder.initial.weight"), T(model, "audio_encoder.initial.bias"), padding=3)
     outs.append(x[0])
     for bi, (s, pd) in enumerate(zip(c.strides, c.paddings)):
+        if last_stage is not None and last_stage < 2 + bi:
+            return outs
         p = f"audio_encoder.decoder_block.{bi + 1}."
         x = snake(x[0], T(model, p + "final.alpha"))[None]
         x = Fn.conv_transpose1d(x, T(model, p + "final.weight"), T(model, p + "final.bias"), stride=s, padding=pd)
@@ -113,6 +118,8 @@ def torch_dac(model, codes, stages=False):
             y = Fn.conv1d(y, T(model, q + "final.weight"), T(model, q + "final.bias"))
             x = x + y
         outs.append(x[0])
+    if last_stage is not None and last_stage < 2 + len(c.strides):
+        return outs
     x = snake(x[0], T(model, "audio_encoder.final.alpha"))[None]
     x = torch.tanh(Fn.conv1d(x, T(model, "audio_encoder.final.weight"), T(model, "audio_encoder.final.bias"), padding=3))
     return (x[0, 0], outs) if stages else x[0, 0]

@@ -197,12 +197,16 @@ ARITH_CASES = [
     ("bf16x3", {}, {"dac_split": 0}, 1 | 2 | 4 | 32),                 # rounds 3 - 5: bf16 x 3 split products (six per product)
     ("bf16x3_by_env", {"TTS_HIP_DAC_SPLIT": "0"}, {}, 1 | 2 | 4 | 32),
     ("exact_fp32", {"TTS_HIP_DAC_BF16X3": "0"}, {}, 0),              # the exact-fp32 MFMA pipe the default is held against
-    ("units_unfused", {}, {"dac_fuse": 0}, 1 | 4 | 32 | 64),          # residual units at 96 / 192 channels as two launches
+    ("exact_fp32_by_key", {}, {"dac_exact_fp32": 1}, 0),
+    ("units_unfused", {}, {"dac_fuse": 0}, 1 | 4 | 32 | 64),         # residual units at 96 / 192 channels as two launches
     ("convt_fp32", {}, {"dac_convt_b3": 0}, 1 | 2 | 32 | 64),         # transposed convs on the exact-fp32 kernel
     ("no_planes", {}, {"dac_planes": 0}, 1 | 2 | 4 | 64),             # wide classes keep fp32 activations (conv1d_mfma_b3_kernel + fp32 k = 1)
     ("tap_pairs", {}, {"dac_tap7": 0}, 1 | 2 | 4 | 32 | 64),          # k = 7 convs with tap-pair k-steps (8 slots for 7 taps); the tap-pair unit kernel stays bf16 x 3
     ("convt_fp32_input", {}, {"dac_convt_planes": 0}, 1 | 2 | 4 | 32 | 64),  # the split transposed convs stage fp32 input themselves instead of the producer's planes
+    ("units_weights_by_registers", {}, {"dac_wdma": 0}, 1 | 2 | 4 | 32 | 64),  # the fused units of round 5: weight stages through registers, the k = 1 operand rebuilt per pass
+    ("units_unfused_conv1_mfma", {}, {"dac_conv1_direct": 0, "dac_fuse": 0}, 1 | 4 | 32 | 64),  # ... two launches, the k = 1 conv on conv1d_mfma_kernel<1, ...> instead of conv1x1_direct_kernel
 ]
+# (tests/test_gpu_dac_stages.py runs every row, and the switches of F16 codec tensors — dac_f16_planes, FLAG_DAC_F32 —, at lengths of several position tiles against float64)
 
 
 @pytest.mark.parametrize("case", ARITH_CASES, ids=[c[0] for c in ARITH_CASES])

@@ -293,6 +293,71 @@ def test_snac_oracle_stages_match_float64(layout, T, with_noise):
             assert np.array_equal(p2, pcm) and np.array_equal(a2, st[k]), k
 
 
+F16_DAC_TOL = 1e-3   # the fp16-im2col noise floor (tests/test_gpu_dac.py)
+DAC_STAGE_ROWS = [
+    # (id, F16 codec tensors, DacOracle f16_conv, bar per stage and for the PCM, of max|f64|)
+    ("f32", False, None, 2e-5),
+    ("f16_im2col", True, None, F16_DAC_TOL),
+    ("f16_exact", True, 0, 2e-5),
+]
+
+
+@pytest.mark.parametrize("row", DAC_STAGE_ROWS, ids=[r[0] for r in DAC_STAGE_ROWS])
+def test_dac_oracle_stages_match_float64(row):
+    """Every stage of orc_dac_decode (0 the quantizer sum, 1 the first conv, 2 + i the end of block i) and its PCM against float64 torch_dac
+    computed here, at the DAC-44k dims and 70 frames (stage lengths 70, 70, 560, 4480, 17920, 35840: many position tiles of every device
+    kernel), codes np.random.default_rng(70): F32 tensors and F16 tensors read exactly (f16_conv = 0) at 2e-5 of max|f64|, the bar of the other
+    oracle stages; F16 tensors with ggml's fp16 im2col (the default for them) at the fp16-im2col floor F16_DAC_TOL.  The float64 reference of
+    an F16 model reads the same fp16-rounded kernels and keeps its activations in float64.
+
+    d_ref[stage] = max|orc - f64| / max|f64| as measured, PCM absolute (tests/test_gpu_dac_stages.py derives the device's bars from this table):
+
+        tensors              stage 0   1         2         3         4         5         PCM
+        F32                  1.53e-07  4.19e-06  2.58e-06  2.64e-06  2.54e-06  2.24e-06  1.66e-06
+        F16, fp16 im2col     1.34e-07  2.39e-04  3.46e-04  4.25e-04  5.06e-04  4.81e-04  3.61e-04
+        F16, f16_conv = 0    1.34e-07  2.67e-06  2.32e-06  2.64e-06  2.76e-06  2.32e-06  1.74e-06
+
+    The float64 PCM (F32 tensors): max |x| 0.65, median 0.105, nothing near saturation, so an absolute bar on the PCM means something."""
+    from tts_cpp_amd import synth as sy
+    name, dac_f16, f16_conv, bar = row
+    frames = 70
+    model = sy.build(sy.parler_mini(layers=1, prompt_vocab=64, ctx=64, dac_f16=dac_f16))
+    cfg = model.cfg
+    codes = np.random.default_rng(frames).integers(0, cfg.cb_size, (frames, cfg.n_out)).astype(np.uint32)
+    pcm64, st64 = _make_golden().torch_dac(model, codes, stages=True)
+    o = orc.DacOracle(model, f16_conv=f16_conv)
+    assert o.m.f16_conv == (0 if f16_conv == 0 or not dac_f16 else 1)
+    pcm, st = o.decode_stages(codes)
+    assert len(st) == len(st64) == 2 + len(cfg.strides)
+    assert [a.shape[1] for a in st] == [70, 70, 560, 4480, 17920, 35840]
+    d = []
+    for a, r in zip(st, st64):
+        assert a.shape == tuple(r.shape)
+        d.append(relerr(a, r.numpy()))
+    d_pcm = float(np.abs(pcm - pcm64.numpy()).max())
+    print(f"DAC-44k {name} F={frames}: d_ref per stage " + " ".join(f"{x:.2e}" for x in d) + f"  PCM {d_pcm:.2e} (max|pcm64| {np.abs(pcm64.numpy()).max():.3f}, "
+          f"median {np.median(np.abs(pcm64.numpy())):.3f})")
+    assert max(d) < bar, d
+    assert d_pcm < bar * np.abs(pcm64.numpy()).max()
+
+
+def test_dac_oracle_every_stage_in_one_decode(tiny_f32):
+    """decode_stages (stage -2) gives the arrays of one decode per stage, and the same PCM; torch_dac's last_stage the leading stages of a whole decode"""
+    g = np.load(GOLD)
+    d = orc.DacOracle(tiny_f32)
+    pcm, st = d.decode_stages(g["codes"])
+    assert np.array_equal(pcm, d.decode(g["codes"])) and len(st) == 2 + len(tiny_f32.cfg.strides)
+    for k, a in enumerate(st):
+        p2, a2 = d.decode(g["codes"], stage=k)
+        assert np.array_equal(p2, pcm) and np.array_equal(a2, a), k
+    mg = _make_golden()
+    pcm64, st64 = mg.torch_dac(tiny_f32, g["codes"], stages=True)
+    assert torch.equal(mg.torch_dac(tiny_f32, g["codes"]), pcm64)
+    for k in range(len(st64)):
+        part = mg.torch_dac(tiny_f32, g["codes"], last_stage=k)
+        assert len(part) == k + 1 and all(torch.equal(a, b) for a, b in zip(part, st64)), k
+
+
 def test_orpheus_decoder_oracle_matches_torch_golden():
     """orc_orpheus_decode (Llama-3 blocks, src/models/orpheus/model.cpp:186-325 restated with ggml's NEOX rope + frequency
     factors, iterated fp32 theta) against tests/golden/tiny_orpheus.npz (float64 torch with the HF rotary formulation):

@@ -135,7 +135,7 @@ extern "C" tts_hip_ctx *tts_hip_create(int device, const tts_hip_desc *desc) {
     // tts_hip_tune() key: a harness under profiles/ can still flip it, a deployment cannot flip it by accident.
     if (const char *e = getenv("TTS_HIP_ATTN_NSPLIT")) c->attn_nsplit_override = atoi(e);
     if (const char *e = getenv("TTS_HIP_ATTN_ROWS")) c->attn_rows_min = std::max(0, atoi(e));                                                 // bench.py A/B, test_gpu_parler.py: row-major self-attention from this many rows (0: never)
-    if (const char *e = getenv("TTS_HIP_DAC_GROUP")) c->dac_group = std::max(1, atoi(e));                       // test_gpu_dac.py, bench.py: utterances per codec pass
+    if (const char *e = getenv("TTS_HIP_DAC_GROUP")) c->dac_group = std::max(1, atoi(e));                       // test_gpu_dac_stages.py, bench.py: utterances per codec pass
     if (const char *e = getenv("TTS_HIP_DAC_BF16X3")) (void) tts_hip_tune(c, "dac_exact_fp32", atoi(e) == 0);  // test_gpu_dac.py: 0 = the exact-fp32 MFMA codec
     if (const char *e = getenv("TTS_HIP_DAC_SPLIT")) c->dac_split = atoi(e) != 0;                               // test_gpu_dac.py: 0 = bf16 x 3 products, 1 = fp16 hi + lo
     if (const char *e = getenv("TTS_HIP_GEN_COMPACT")) c->gen_compact = atoi(e) != 0;                           // test_gpu_runner.py: row compaction of the generation loop
