@@ -603,6 +603,12 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
 /* ---- introspection (tests, bench) -------------------------------------------------------- */
 /* Copy an internal buffer to the host.  what: "hidden" (final-normed hidden of the last forward,
  * [rows][H]), "k:<layer>:<seq>" / "v:<layer>:<seq>" (cache rows [n_pos][H] as fp32),
+ * and, of the last attention launch of the last forward (these buffers outlive it, a graph replay included; without cross-attention it is
+ * the last layer's self-attention, with cross-attention and fp32 matrices the last layer's cross-attention; reading them changes no
+ * dispatch decision, unlike tts_hip_set_debug): "q" (the query rows it read) and "att" / "att16" (the fp32 / fp16 rows it left, the fp16
+ * ones widened exactly), all [rows][H] with rows = max_floats / H; "pos" / "seq" (the rows' positions and cache slots as the device holds
+ * them, as floats); "part:<nz>" (the key-slice partials of a launch with nz slices: [rows][heads][nz][66] = the slice's maximum (-inf:
+ * an empty slice), its sum and its 64 unnormalised channels, rows = max_floats / (heads * nz * 66));
  * "dac:<stage>" (activation after DAC stage, see oracle stage numbering; requires
  * tts_hip_set_debug(ctx,1) before the decode); SNAC contexts: "snac:<stage>" (utterance 0's valid region
  * [C][tokens * rate] after the stage of the last pass, orc_snac_decode's numbering: 0 = the summed codebook levels, 1 = after

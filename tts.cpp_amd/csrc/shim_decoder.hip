@@ -2155,6 +2155,39 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (hipMemcpy(out, base + ((size_t) layer * 2 * c->di_U + row) * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
+    // Parler: the rows of the last forward's last attention launch.  Nothing after it writes these buffers (enqueue_forward: the FFN and the heads use
+    // x / u32 / u16 / logits), so they outlive the forward, a graph replay included.  Without cross-attention that launch is the last layer's
+    // self-attention; with it, q and att hold the last layer's cross-attention query and rows.
+    if (c->has_parler && (w == "q" || w == "att" || w == "att16")) {   // [rows][H], rows = max_floats / H
+        const size_t rows = std::min(max_floats / (size_t) c->H, (size_t) c->RMAX), n = rows * c->H;
+        if (rows == 0) { set_err("debug_read(%s): buffer too small", what); return -1; }
+        if (w == "att16") {   // widened exactly
+            std::vector<_Float16> h(n);
+            if (hipMemcpy(h.data(), c->att16, n * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = (float) h[i];
+        } else if (hipMemcpy(out, w == "q" ? c->q : c->att, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        return (int64_t) n;
+    }
+    if (c->has_parler && (w == "pos" || w == "seq")) {   // the rows' positions / cache slots as the device holds them, as floats
+        const size_t n = std::min(max_floats, (size_t) c->RMAX);
+        std::vector<uint32_t> p(n);
+        if (hipMemcpy(p.data(), w == "pos" ? c->d_pos : c->d_seq, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        for (size_t i = 0; i < n; i++) out[i] = (float) p[i];
+        return (int64_t) n;
+    }
+    if (c->has_parler && starts_with(w, "part:")) {   // "part:<nz>": the key-slice partials of a launch with nz slices, [rows][heads][nz][2 + 64] = max, sum, the 64 unnormalised channels
+        const int nz = atoi(w.c_str() + 5);
+        if (nz < 1 || nz > 16) { set_err("debug_read(%s): 1 <= nz <= 16", what); return -1; }
+        const size_t per = (size_t) c->NH * nz, rows = std::min(max_floats / (per * 66), (size_t) c->RMAX);
+        if (rows == 0) { set_err("debug_read(%s): buffer too small", what); return -1; }
+        std::vector<float> p(rows * per * ATT_PS);
+        if (hipMemcpy(p.data(), c->part, p.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        for (size_t i = 0; i < rows * per; i++) {
+            out[i * 66] = p[i * ATT_PS]; out[i * 66 + 1] = p[i * ATT_PS + 1];
+            memcpy(out + i * 66 + 2, p.data() + i * ATT_PS + ATT_PO, 64 * 4);
+        }
+        return (int64_t) (rows * per * 66);
+    }
     if (w.size() > 2 && (w[0] == 'k' || w[0] == 'v') && w[1] == ':') {
         int layer = 0, seq = 0;
         if (sscanf(w.c_str() + 2, "%d:%d", &layer, &seq) != 2 || layer < 0 || layer >= c->L || seq < 0 || seq >= (int) c->d.max_seqs) {
