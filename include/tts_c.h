@@ -135,6 +135,14 @@ int tts_c_sampler_sample(const tts_c_sampler_cfg *cfg, const int32_t *last_ids, 
  * tts_c_last_tokens returns the ids it was encoded from. */
 int tts_c_update_conditional_prompt(tts_c_runner *r, const char *text_encoder_path, const char *prompt);
 
+/* tts_generation_runner::add_voice (an extension; Parler): encode `description` with the T5 encoder GGUF at text_encoder_path and keep it as the
+ * voice `name` beside the runner's own description.  tts_c_config::voice == name then selects it per request — in tts_c_generate, the batch, the
+ * chunked forms and the sessions, where requests with different voices share one lock-step forward; an unknown name fails the request and the
+ * message lists the known ones.  At most 32 tokens and 64 voices; a known name is replaced.  A runner without voice descriptions refuses.
+ * tts_c_list_voices writes the names, comma-separated, into out[0..cap) and returns the length of the whole list (< 0 on error). */
+int tts_c_add_voice(tts_c_runner *r, const char *name, const char *text_encoder_path, const char *description);
+int tts_c_list_voices(tts_c_runner *r, char *out, int cap);
+
 /* ---- device pool: the server's worker pool (examples/server/server.cpp:126-330,885-895) with one worker per device
  * and dynamic lock-step batching of the queued requests (tts.cpp_amd/host/device_pool.h).  No HTTP. -------------- */
 typedef struct tts_c_pool tts_c_pool;
@@ -157,6 +165,8 @@ int  tts_c_pool_submit(tts_c_pool *pool, const char *text, const tts_c_config *c
 /* CONDITIONAL_PROMPT task (server.cpp:263-271) fanned out to every worker; wait on the id like any task (no audio:
  * tts_c_pool_wait returns 0 with n_outputs == 0 on success, 1 + tts_c_last_error() otherwise) */
 int  tts_c_pool_conditional_prompt(tts_c_pool *pool, const char *prompt);
+/* add_voice on every worker's runner, with the path given to tts_c_pool_set_text_encoder; fanned out and waited for like CONDITIONAL_PROMPT */
+int  tts_c_pool_add_voice(tts_c_pool *pool, const char *name, const char *description);
 /* blocks until the task is done (timeout_ms < 0: forever).  0 = audio in data[0..n_outputs), valid until
  * tts_c_pool_release(id); 1 = finished without audio (tts_c_last_error says why); -1 = not finished */
 int  tts_c_pool_wait(tts_c_pool *pool, int id, int timeout_ms, const float **data, size_t *n_outputs, int *batch_size, int *worker);

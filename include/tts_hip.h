@@ -712,6 +712,41 @@ int tts_hip_parler_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_fi
 int tts_hip_parler_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t steps, uint32_t *tokens_out);
 int tts_hip_parler_stream_end(tts_hip_ctx *ctx);
 
+/* ---- per-request voice descriptions: rows of ONE lock-step forward attending over different descriptions -----------------------------
+ * A context holds its own description (the arena's, or tts_hip_parler_set_text_encoding's): voice 0.  A voice bank adds voices 1 .. n_voices,
+ * and every cache slot carries the voice its utterance attends over, so two requests with different voices share a prefill, a step, a
+ * generation or a session run.
+ *   voice_bank(n_voices)      room for voices 1 .. n_voices (1 .. 256): per voice [L][2][32][H] fp32 cross K / V and a length (Parler-Mini:
+ *           6.3 MB), the device table of the slots' voices [max_seqs + padding slot] (all 0) and its host mirror.  Once per context (captured
+ *           steps hold the addresses); a context on a shared arena has a bank of its own; tts_hip_destroy frees it.  Out of memory is
+ *           reported with the context unchanged.
+ *   voice_set(voice, enc, n)  the entry's K / V from the T5 output enc [n][H], by the launches that compute the context's own cross K / V
+ *           (bit for bit what tts_hip_parler_set_text_encoding(enc, n) leaves in "cross:").  Refused: n outside 1..32 — a bank entry holds
+ *           32 positions, what the short cross-attention body covers; voice 0 or a voice beyond the bank; a voice some live cache slot uses;
+ *           steps in flight (between tts_hip_parler_gen_launch and its tts_hip_parler_gen_wait).
+ *   seq_voices(n, seqs, voices)  the voice of n cache slots.  Allowed with no generation open, and inside a session between two runs for
+ *           slots that are not live: a voice enters BEFORE tts_hip_parler_stream_admit*, whose prefill already attends.  Refused: a live
+ *           slot (a session's live slot, a row of an open generation); a voice never set or beyond the bank; steps in flight; a session's
+ *           padding slot (it stays at voice 0); a non-zero voice while the context's own description has more than 32 positions (voice 0
+ *           then cannot join a mixed forward; tts_hip_parler_set_text_encoding refuses the other order).
+ * Every misuse returns non-zero before anything is launched and leaves the context usable.
+ * The forward: whether a prefill / step / generation / session run is "mixed" is decided on the host when its rows are staged — it is when
+ * any slot involved carries a non-zero voice — and never inside a run (a generation keeps its choice through row compactions).  When none
+ * does, the forward is the one-description forward, launch for launch.  A mixed forward runs the cross-q projection with a plain store,
+ * tries neither cross-attention fold, and runs attn_short_voices_kernel where the unfolded chain runs the cross-attention: per row the
+ * statements of attn_short_kernel, on the K / V base and length of the row's voice (voice 0: the context's own).  The out projection reads
+ * the attended rows as the unfolded chain does, quantised matrices included.  No existing kernel is changed.
+ * Equality: the logits (and so the tokens) of a row with voice v are bit for bit those of a context whose own description is v's encoding,
+ * run with tune("cross_fold") = 0 over the same rows, ids and positions (tests/test_gpu_parler_voices.py).  Against the folded
+ * one-description forward the project's tolerances hold (another summation order).
+ * Captured steps: the mixed step has graph keys of its own beside the one-description step's.  The slots' voices, the lengths and the
+ * bank are read through device pointers, so a call of seq_voices or voice_set never recaptures, and alternating one-voice and mixed runs recaptures
+ * nothing after the first of each.
+ * tts_hip_debug_read("voice:<v>:<layer>:<0|1>") returns an entry's K or V [len][H], like "cross:"; "graphs" the number of captured steps. */
+int tts_hip_parler_voice_bank(tts_hip_ctx *ctx, uint32_t n_voices);
+int tts_hip_parler_voice_set(tts_hip_ctx *ctx, uint32_t voice, const float *enc, uint32_t n_tokens);
+int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs, const uint32_t *voices);
+
 /* Tuning and fallback switches by name (profiles/ harnesses and the fallback parity test; call between tts_hip_create and the first
  * launch).  Unknown key: -1.  Not an environment variable on purpose: a deployment cannot flip a kernel path by accident.
  * Kokoro contexts (each 1 by default, 0 = the fallback; tests/test_gpu_kokoro.py runs every one against the oracle):

@@ -1035,6 +1035,42 @@ static __global__ __launch_bounds__(256) void attn_short_kernel(AttnArgs a) {
     B1_STAMP(a.stamps, 3);
 }
 
+// Per-request voice descriptions (tts_hip_parler_voice_bank, include/tts_hip.h): attn_short_kernel with the K / V base and the prompt length of
+// the ROW's voice.  Row r sits on cache slot row_seq[r], the slot carries voice seq_voice[slot]; voice 0 is the launch's own AttnArgs (the context's
+// description, T_fixed positions), voice v >= 1 is bank entry v - 1 ([L][2][32][H] fp32, this launch's layer at k_off / v_off) with voice_len[v]
+// positions.  Same grid; the body is attn_short_body, called on a local AttnArgs: per row the statements attn_short_kernel runs on a context whose
+// own description is that voice.  All three tables are read through device pointers, so a captured launch follows tts_hip_parler_seq_voices and
+// tts_hip_parler_voice_set without a recapture.
+struct VoiceArgs {
+    const uint32_t *row_seq;     // [R] cache slot of a row
+    const uint32_t *seq_voice;   // [max_seqs + 1] voice of a cache slot (the padding slot stays at 0)
+    const int *voice_len;        // [n_voices + 1] positions of a voice, 0 = never set ([0] unused)
+    const float *bank;           // [n_voices][voice_stride]
+    int64_t voice_stride;        // floats per entry: L * 2 * 32 * H
+    int64_t k_off, v_off;        // this layer's K / V inside an entry, in floats
+    int n_voices;
+};
+static __global__ __launch_bounds__(256) void attn_short_voices_kernel(AttnArgs a, VoiceArgs va) {
+    const int lane = threadIdx.x & 63;
+    const int h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), r = blockIdx.y;
+    if (h >= a.n_heads) return;
+    B1_STAMP(a.stamps, 0);
+    const uint32_t v = va.seq_voice[va.row_seq[r]];
+    int T = a.T_fixed;
+    if (v != 0) {
+        if (v > (uint32_t) va.n_voices) return;   // (the host refuses such a table entry: never taken)
+        const float *e = va.bank + (int64_t) (v - 1) * va.voice_stride;
+        a.kc = e + va.k_off;
+        a.vc = e + va.v_off;
+        T = va.voice_len[v];
+    }
+    if (T < 1 || T > 32) return;                  // (likewise: a voice is set before a slot may name it, the context's own description is checked)
+    if (T <= 8) attn_short_body<8>(a, r, h, lane, T);
+    else if (T <= 16) attn_short_body<16>(a, r, h, lane, T);
+    else attn_short_body<32>(a, r, h, lane, T);
+    B1_STAMP(a.stamps, 3);
+}
+
 // (A second lane layout — key = lane / 4, a quarter of the head's channels per lane: all scores from 16 FMAs and two quad steps, 14 cross-lane steps
 // per row instead of six per key — measured 14.8 us per launch at 1024 rows against 13.7 for this kernel with its compile-time prompt bound:
 // the launch is bound by the latency of its loads, not by the reductions; profiles/r03/attn_short16_rejected.txt.)

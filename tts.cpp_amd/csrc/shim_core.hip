@@ -276,6 +276,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     for (auto &pw : c->packed16) free_dev(pw.second);
     for (auto &pw : c->packed_b3) free_dev(pw.second);
     free_dev(c->cond_text_enc); free_dev(c->cond_cross_kv);
+    free_dev(c->vb_kv); free_dev(c->vb_enc); free_dev(c->vb_len); free_dev(c->vb_seq);   // the voice bank
     for (auto &pw : c->packed_ru) free_dev(pw.second);
     for (auto &pw : c->packed_ct) free_dev(pw.second);
     for (auto &pw : c->packed_p) free_dev(pw.second);

@@ -706,14 +706,32 @@ static int attn_nsplit(const tts_hip_ctx *c, int R, bool same_seq) {
     return 1;  // 1024-thread workgroups for few pairs (run_attn); split-T stays available via TTS_HIP_ATTN_NSPLIT
 }
 
+// cross-attention of the "voices" variant: every row over the description of its cache slot's voice (attn_short_voices_kernel); `a` is what the
+// unfolded chain hands run_attn (the context's own K / V of this layer and c->E: voice 0)
+static int run_attn_voices(tts_hip_ctx *c, AttnArgs a, int R, int layer) {
+    if (!c->vb_kv || c->E < 1 || c->E > tts_hip_ctx::VOICE_POS) return set_err("voices forward: no voice bank, or the context's own description has %d positions (1..%d)", c->E, (int) tts_hip_ctx::VOICE_POS);
+    VoiceArgs va{};
+    va.row_seq = c->d_seq; va.seq_voice = c->vb_seq; va.voice_len = c->vb_len; va.bank = c->vb_kv;
+    va.voice_stride = (int64_t) c->voice_stride(); va.n_voices = c->vb_n;
+    va.k_off = ((int64_t) layer * 2 + 0) * tts_hip_ctx::VOICE_POS * c->H;
+    va.v_off = ((int64_t) layer * 2 + 1) * tts_hip_ctx::VOICE_POS * c->H;
+    CHK(prof_begin(c, TTS_HIP_K_ATTN_CROSS, 2.0 * tts_hip_ctx::VOICE_POS * c->H * 4 + 2.0 * R * c->H * 4, 0));
+    hipLaunchKernelGGL(attn_short_voices_kernel, dim3((c->NH + 3) / 4, R), dim3(256), 0, c->stream, a, va);
+    HIPCHK(hipGetLastError());
+    return prof_end(c);
+}
+
 // ------------------------------------------------------------------------------------------------
 // the decoder forward over R rows (ids / positions / cache slots already in d_ids / d_pos / d_seq)
+// c->fwd_voices (set where the rows are staged): the "voices" variant — the cross-q GEMM stores q, neither fold is tried, attn_short_voices_kernel
+// runs where the unfolded chain runs the cross-attention, the out projection reads att / att16 as that chain does.  Everything else is unchanged.
 // ------------------------------------------------------------------------------------------------
 static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, bool same_seq) {
     const int H = c->H;
     const int64_t seq_stride = (int64_t) c->KVPOS * H;
     const size_t kv_esz = c->d.kv_type == TTS_HIP_F16 ? 2 : 4;
     const size_t layer_kv_bytes = (size_t) c->d.max_seqs * seq_stride * kv_esz;
+    const bool voices = c->fwd_voices;
 
     c->pending_parts = 0;
     EmbedArgs ea{};
@@ -790,7 +808,7 @@ static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, 
             gq.stamps = stamp_slot();
             const bool co_half_ = y.co.type == TTS_HIP_F16 && !valu_mode && (H % 256 == 0);
             // many rows: the attention over the voice prompt inside the q projection's 64 x 64 tiles (gemm_tile_kernel<.., EPI_CROSS>), no launch of its own
-            const bool try_fold = c->cross_fold && c->attn_short && c->E >= 1 && c->E <= 32 && H == c->NH * 64 && !c->debug;
+            const bool try_fold = !voices && c->cross_fold && c->attn_short && c->E >= 1 && c->E <= 32 && H == c->NH * 64 && !c->debug;
             if (try_fold) {
                 gq.cross_k = (const float *) (c->cross_kv_ptr() + ((size_t) l * 2 + 0) * c->ECAP * H * 4);
                 gq.cross_v = (const float *) (c->cross_kv_ptr() + ((size_t) l * 2 + 1) * c->ECAP * H * 4);
@@ -811,9 +829,10 @@ static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, 
             ac.H = H; ac.n_heads = c->NH; ac.scale = at.scale; ac.out = c->att; ac.out16 = co_half ? c->att16 : nullptr; ac.part = c->part;
             ac.stamps = stamp_slot();
             // one-sequence chain: the attention inside the out projection's prologue (gemm16_kernel<.., PRO_CROSS, ..>), no launch of its own
-            const bool b1_fold = !folded && c->cross_fold && c->attn_short && R <= 4 && co_half && c->E >= 1 && c->E <= 32 && H == c->NH * 64 && H <= 2048 &&
+            const bool b1_fold = !voices && !folded && c->cross_fold && c->attn_short && R <= 4 && co_half && c->E >= 1 && c->E <= 32 && H == c->NH * 64 && H <= 2048 &&
                                  (int) y.co.K == H && !c->gemv_rows && !c->debug && !c->prof;
-            if (!folded && !b1_fold) CHK(run_attn(c, TTS_HIP_K_ATTN_CROSS, ac, R, 1, 2.0 * c->E * H * 4));
+            if (voices) CHK(run_attn_voices(c, ac, R, l));
+            else if (!folded && !b1_fold) CHK(run_attn(c, TTS_HIP_K_ATTN_CROSS, ac, R, 1, 2.0 * c->E * H * 4));
             GemmArgs gc = go;
             gc.stamps = stamp_slot();
             gc.A = co_half ? (const void *) c->att16 : (const void *) c->att;
@@ -853,16 +872,16 @@ static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, 
 }
 
 // prep_cross_key_values (model.cpp:110-173): K_c / V_c = W_k / W_v · text_encoding, per layer
-static int compute_cross_kv(tts_hip_ctx *c) {
-    if (!c->has_parler || !c->d.use_cross_attn) return 0;
+// enc [E][H] (device) -> dst [L][2][cap][H]: the context's own description (cap = ECAP) or a voice-bank entry (cap = VOICE_POS), the same launches
+static int cross_kv_into(tts_hip_ctx *c, const float *enc, int E, float *dst, int cap) {
     const int H = c->H, step = 32;
     for (int l = 0; l < c->L; l++) {
         for (int kv = 0; kv < 2; kv++) {
-            for (int e0 = 0; e0 < c->E; e0 += step) {
+            for (int e0 = 0; e0 < E; e0 += step) {
                 GemmArgs g{};
-                g.R = std::min(step, c->E - e0); g.H = H;
-                g.A = (const float *) c->text_enc_ptr() + (size_t) e0 * H; g.lda = H;
-                g.out = (float *) (c->cross_kv_ptr() + ((size_t) l * 2 + kv) * c->ECAP * H * 4) + (size_t) e0 * H;
+                g.R = std::min(step, E - e0); g.H = H;
+                g.A = enc + (size_t) e0 * H; g.lda = H;
+                g.out = dst + ((size_t) l * 2 + kv) * cap * H + (size_t) e0 * H;
                 g.ldo = H;
                 CHK(run_gemm(c, TTS_HIP_K_GEMM_OTHER, kv == 0 ? c->layers[l].ck : c->layers[l].cv, g, PRO_F32, EPI_STORE));
             }
@@ -870,6 +889,10 @@ static int compute_cross_kv(tts_hip_ctx *c) {
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
+}
+static int compute_cross_kv(tts_hip_ctx *c) {
+    if (!c->has_parler || !c->d.use_cross_attn) return 0;
+    return cross_kv_into(c, (const float *) c->text_enc_ptr(), c->E, (float *) c->cross_kv_ptr(), c->ECAP);
 }
 
 // the block scales of the Parler decoder's quantised matrices once more, transposed, for qgemm_tile_kernel (arena space reserved by the planner)
@@ -1108,6 +1131,8 @@ extern "C" int tts_hip_parler_set_text_encoding(tts_hip_ctx *c, const float *enc
     if (!c || !c->finalized || !c->has_parler) return set_err("set_text_encoding: context not ready");
     if (!c->d.use_cross_attn) return set_err("set_text_encoding: cross attention disabled");
     if ((int) n_tokens > c->ECAP || n_tokens == 0) return set_err("set_text_encoding: %u tokens outside 1..%d", n_tokens, c->ECAP);
+    if ((int) n_tokens > tts_hip_ctx::VOICE_POS)   // voice 0 could not join a mixed forward (tts_hip_parler_seq_voices refuses the other order)
+        for (uint32_t v : c->vb_seq_h) if (v) return set_err("set_text_encoding: %u positions while a cache slot carries a non-zero voice (at most %d then)", n_tokens, (int) tts_hip_ctx::VOICE_POS);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     // (stream copies, not hipMemcpy: the legacy stream may not be used while another context captures a graph)
@@ -1146,6 +1171,101 @@ extern "C" int tts_hip_parler_reset(tts_hip_ctx *c) {
     return 0;  // positions are caller-supplied; the cache is overwritten position by position like the reference's
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-request voice descriptions (include/tts_hip.h): the bank, an entry's K / V, the slots' voices
+// ------------------------------------------------------------------------------------------------
+// a cache slot whose utterance is generating: a row of the generation between gen_begin and its end, a live slot of the session
+static bool slot_is_live(const tts_hip_ctx *c, uint32_t s) {
+    if (c->gl.active && !c->gl.done && s < c->gl.n) return true;
+    return c->gs.active && s < c->gs.slot_live.size() && c->gs.slot_live[s];
+}
+static int voices_ready(tts_hip_ctx *c, const char *who) {
+    CHK(ready(c, who));
+    if (!c->d.use_cross_attn) return set_err("%s: cross attention disabled", who);
+    if (c->gl.active && c->gl.unwaited) return set_err("%s: steps in flight (between tts_hip_parler_gen_launch and its tts_hip_parler_gen_wait)", who);
+    return 0;
+}
+
+extern "C" int tts_hip_parler_voice_bank(tts_hip_ctx *c, uint32_t n_voices) {
+    const char *who = "tts_hip_parler_voice_bank";
+    CHK(voices_ready(c, who));
+    if (n_voices == 0 || n_voices > (uint32_t) tts_hip_ctx::VOICE_MAX) return set_err("%s: %u voices outside 1..%d", who, n_voices, (int) tts_hip_ctx::VOICE_MAX);
+    if (c->vb_kv) return set_err("%s: the context has a bank of %d voices already (captured steps hold its address)", who, c->vb_n);
+    if (c->H != c->NH * 64) return set_err("%s: attn_short_body wants 64-wide heads (hidden %d, %d heads)", who, c->H, c->NH);
+    float *kv = nullptr, *enc = nullptr;
+    int *len = nullptr;
+    uint32_t *seq = nullptr;
+    const size_t kvb = (size_t) n_voices * c->voice_stride() * 4, encb = (size_t) tts_hip_ctx::VOICE_POS * c->H * 4;
+    const size_t lenb = ((size_t) n_voices + 1) * 4, seqb = ((size_t) c->d.max_seqs + 1) * 4;
+    auto all = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = hipMalloc((void **) &kv, kvb)) != hipSuccess) return e;
+        if ((e = hipMalloc((void **) &enc, encb)) != hipSuccess) return e;
+        if ((e = hipMalloc((void **) &len, lenb)) != hipSuccess) return e;
+        if ((e = hipMalloc((void **) &seq, seqb)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(kv, 0, kvb, c->stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(enc, 0, encb, c->stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(len, 0, lenb, c->stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(seq, 0, seqb, c->stream)) != hipSuccess) return e;
+        return hipStreamSynchronize(c->stream);
+    };
+    const hipError_t e = all();
+    if (e != hipSuccess) {   // nothing of the context has changed yet
+        (void) hipGetLastError();
+        free_dev(kv); free_dev(enc); free_dev(len); free_dev(seq);
+        return set_err("%s: %u voices of %zu bytes: %s", who, n_voices, c->voice_stride() * 4, hipGetErrorString(e));
+    }
+    c->vb_kv = kv; c->vb_enc = enc; c->vb_len = len; c->vb_seq = seq;
+    c->vb_n = (int) n_voices;
+    c->vb_len_h.assign((size_t) n_voices + 1, 0);
+    c->vb_seq_h.assign((size_t) c->d.max_seqs + 1, 0u);
+    return 0;
+}
+
+extern "C" int tts_hip_parler_voice_set(tts_hip_ctx *c, uint32_t voice, const float *enc, uint32_t n_tokens) {
+    const char *who = "tts_hip_parler_voice_set";
+    CHK(voices_ready(c, who));
+    if (!enc) return set_err("%s: null argument", who);
+    if (!c->vb_kv) return set_err("%s: no voice bank (tts_hip_parler_voice_bank)", who);
+    if (voice == 0) return set_err("%s: voice 0 is the context's own description (tts_hip_parler_set_text_encoding)", who);
+    if (voice > (uint32_t) c->vb_n) return set_err("%s: voice %u beyond the bank of %d", who, voice, c->vb_n);
+    if (n_tokens == 0 || n_tokens > (uint32_t) tts_hip_ctx::VOICE_POS) return set_err("%s: %u tokens outside 1..%d (a bank entry holds 32 positions)", who, n_tokens, (int) tts_hip_ctx::VOICE_POS);
+    for (uint32_t s = 0; s < (uint32_t) c->vb_seq_h.size(); s++)
+        if (c->vb_seq_h[s] == voice && slot_is_live(c, s)) return set_err("%s: voice %u is in use by live cache slot %u", who, voice, s);
+    HIPCHK(hipMemcpyAsync(c->vb_enc, enc, (size_t) n_tokens * c->H * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(cross_kv_into(c, c->vb_enc, (int) n_tokens, c->vb_kv + (size_t) (voice - 1) * c->voice_stride(), tts_hip_ctx::VOICE_POS));
+    c->vb_len_h[voice] = (int) n_tokens;
+    HIPCHK(hipMemcpyAsync(c->vb_len + voice, &c->vb_len_h[voice], 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int tts_hip_parler_seq_voices(tts_hip_ctx *c, uint32_t n, const uint32_t *seqs, const uint32_t *voices) {
+    const char *who = "tts_hip_parler_seq_voices";
+    CHK(voices_ready(c, who));
+    if (n == 0) return 0;
+    if (!seqs || !voices) return set_err("%s: null argument", who);
+    bool any = false;
+    for (uint32_t i = 0; i < n; i++) {
+        if (seqs[i] >= c->d.max_seqs) return set_err("%s: seq %u >= max_seqs %u", who, seqs[i], c->d.max_seqs);
+        if (slot_is_live(c, seqs[i])) return set_err("%s: cache slot %u is live", who, seqs[i]);
+        if (voices[i] == 0) continue;
+        any = true;
+        if (!c->vb_kv) return set_err("%s: no voice bank (tts_hip_parler_voice_bank)", who);
+        if (voices[i] > (uint32_t) c->vb_n) return set_err("%s: voice %u beyond the bank of %d", who, voices[i], c->vb_n);
+        if (c->vb_len_h[voices[i]] == 0) return set_err("%s: voice %u was never set (tts_hip_parler_voice_set)", who, voices[i]);
+        if (c->gs.active && seqs[i] == c->gs.n_slots) return set_err("%s: cache slot %u pads the session's forward and stays at voice 0", who, seqs[i]);
+    }
+    if (any && (c->E < 1 || c->E > tts_hip_ctx::VOICE_POS))
+        return set_err("%s: the context's own description has %d positions: voice 0 cannot join a mixed forward (at most %d)", who, c->E, (int) tts_hip_ctx::VOICE_POS);
+    if (!c->vb_kv) return 0;   // all zero, and no table to hold them: every slot is at voice 0 as it is
+    for (uint32_t i = 0; i < n; i++) c->vb_seq_h[seqs[i]] = voices[i];
+    HIPCHK(hipMemcpyAsync(c->vb_seq, c->vb_seq_h.data(), c->vb_seq_h.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 extern "C" int tts_hip_parler_prefill(tts_hip_ctx *c, uint32_t seq, const uint32_t *ids, uint32_t n, uint32_t pos0) {
     CHK(ready(c, "tts_hip_parler_prefill"));
     if (seq >= c->d.max_seqs) return set_err("prefill: seq %u >= max_seqs %u", seq, c->d.max_seqs);
@@ -1160,6 +1280,7 @@ extern "C" int tts_hip_parler_prefill(tts_hip_ctx *c, uint32_t seq, const uint32
             c->h_seq[r] = seq;
             c->host_pos[r] = pos0 + o + r;
         }
+        c->fwd_voices = c->slot_voiced(seq);
         HIPCHK(hipMemcpyAsync(c->d_ids, c->h_ids, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_seq, c->h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1193,6 +1314,8 @@ extern "C" int tts_hip_parler_prefill_batch(tts_hip_ctx *c, uint32_t n, const ui
         for (int r = 0; r < R; r++) {
             c->h_ids[r] = ri[o + r]; c->h_pos[r] = rp[o + r]; c->h_seq[r] = rs[o + r]; c->host_pos[r] = rp[o + r];
         }
+        c->fwd_voices = false;
+        for (uint32_t s : rs) c->fwd_voices = c->fwd_voices || c->slot_voiced(s);   // of the whole call: its forwards agree
         HIPCHK(hipMemcpyAsync(c->d_ids, c->h_ids, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_seq, c->h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1203,7 +1326,8 @@ extern "C" int tts_hip_parler_prefill_batch(tts_hip_ctx *c, uint32_t n, const ui
 }
 
 enum { MODE_LOGITS = 0, MODE_GREEDY = 1, MODE_GEN = 2, MODE_GEN_SAMPLE = 3, MODE_GEN_MIXED = 4 };   // MODE_GEN_MIXED: sample_kernel over the slots' own records (c->gs_rec)
-static bool gen_mode(int mode) { return mode == MODE_GEN || mode == MODE_GEN_SAMPLE || mode == MODE_GEN_MIXED; }
+enum { MODE_VOICES = 8 };   // added to a mode in the graph key alone: the captured step of the "voices" forward (enqueue_forward), cached beside the one-description step
+static bool gen_mode(int mode) { mode &= MODE_VOICES - 1; return mode == MODE_GEN || mode == MODE_GEN_SAMPLE || mode == MODE_GEN_MIXED; }
 // captured steps are keyed mode * GRAPH_KEY_ROWS + rows (rows <= TTS_HIP_MAX_ROWS, 1024 by default); drop_gen_graphs() recovers the mode from the
 // key — with the two sites out of step (keys in units of 8192, the drop in units of 1000) the generation graphs were never dropped and a
 // replay used whatever sampling parameters / tokens_out pointer its capture had baked in
@@ -1212,9 +1336,11 @@ static bool gen_mode(int mode) { return mode == MODE_GEN || mode == MODE_GEN_SAM
 static int stage_step_inputs(tts_hip_ctx *c, uint32_t n, const uint32_t *ids, const uint32_t *pos, const uint32_t *seqs) {
     if (n == 0 || (int) n > c->RMAX || n > c->d.max_seqs) return set_err("step: n_seqs=%u outside 1..%u", n, std::min<uint32_t>(c->RMAX, c->d.max_seqs));
     c->host_pos.resize(n);
+    c->fwd_voices = false;
     for (uint32_t r = 0; r < n; r++) {
         const uint32_t s = seqs ? seqs[r] : r;
         if (s >= c->d.max_seqs) return set_err("step: seq %u >= max_seqs %u", s, c->d.max_seqs);
+        c->fwd_voices = c->fwd_voices || c->slot_voiced(s);
         if (pos[r] >= (uint32_t) c->KVPOS || pos[r] >= (uint32_t) c->NPOS) return set_err("step: position %u exceeds the %d cached positions", pos[r], c->KVPOS);
         for (int i = 0; i < c->NO; i++) {
             const uint32_t id = ids[r * c->NO + i];
@@ -1279,7 +1405,7 @@ static int enqueue_step_body(tts_hip_ctx *c, int R, int mode, uint32_t bos, uint
 static int run_step(tts_hip_ctx *c, int R, int mode, uint32_t bos, uint32_t eos) {
     const bool use_graph = !(c->d.flags & TTS_HIP_FLAG_NO_GRAPH) && !c->prof;
     if (!use_graph) return enqueue_step_body(c, R, mode, bos, eos);
-    const int key = mode * GRAPH_KEY_ROWS + R;
+    const int key = (mode + (c->fwd_voices ? (int) MODE_VOICES : 0)) * GRAPH_KEY_ROWS + R;
     auto it = c->graphs.find(key);
     hipGraphExec_t exec = it != c->graphs.end() ? it->second : nullptr;
     if (!exec) CHK(capture_graph(c, key, [&] { return enqueue_step_body(c, R, mode, bos, eos); }, &exec));
@@ -1369,6 +1495,7 @@ static int gen_begin(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *start
     c->gs = tts_hip_ctx::GenStream{};   // a batch generation ends any stream of this context
     auto &g = c->gl;
     g.mode = mode; g.n = n; g.n_steps = n_steps; g.bos = bos; g.eos = eos; g.R = n;
+    for (uint32_t r = 0; r < n; r++) g.voices = g.voices || c->slot_voiced(r);   // fixed here for the whole generation, compactions included
     g.start.assign(start_pos, start_pos + n);
     g.row_utt.resize(n);
     for (uint32_t r = 0; r < n; r++) g.row_utt[r] = r;   // utterance of row r
@@ -1384,6 +1511,8 @@ static int gen_launch(tts_hip_ctx *c, uint32_t k) {
     const uint32_t end = std::min(g.n_steps, g.launched + k), max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS) - 1;
     for (uint32_t s = g.launched; s < end; s++) {
         for (uint32_t r = 0; r < g.R; r++) c->host_pos[r] = std::min<uint32_t>(g.start[g.row_utt[r]] + s, max_pos);
+        c->fwd_voices = g.voices;
+        g.unwaited = true;
         CHK(run_step(c, (int) g.R, g.mode, g.bos, g.eos));
         g.launched = s + 1;
     }
@@ -1402,6 +1531,7 @@ static int gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, 
     const uint32_t n = g.n, ran = g.launched;
     HIPCHK(hipMemcpyAsync(c->h_tok, c->d_steps_done, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    g.unwaited = false;
     uint32_t live = 0;
     for (uint32_t r = 0; r < g.R; r++) live += c->h_tok[g.row_utt[r]] == 0;
     if (live == 0 || ran >= g.n_steps) g.done = true;
@@ -1637,6 +1767,10 @@ static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uin
     if (c->gen_total != (int) RT || !c->gs_graphs || c->gs_baked_steps != max_steps) { drop_gen_graphs(c); c->gen_total = (int) RT; c->gs_graphs = true; c->gs_baked_steps = max_steps; }   // feed_kernel's padding slot is baked in too
     HIPCHK(hipMemsetAsync(c->d_eos, 0, (size_t) RT * c->NO, c->stream));
     HIPCHK(hipMemsetAsync(c->d_steps_done, 0, (size_t) RT * 4, c->stream));
+    if (c->slot_voiced(n_slots)) {   // the padding slot attends over the context's own description
+        c->vb_seq_h[n_slots] = 0;
+        HIPCHK(hipMemsetAsync(c->vb_seq + n_slots, 0, 4, c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     g.slot_live.assign(n_slots, 0);
     g.active = true;
@@ -1720,6 +1854,8 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
                 c->h_seq[r] = pad ? g.n_slots : rs[o + r];
                 c->host_pos[r] = c->h_pos[r];
             }
+            c->fwd_voices = false;
+            for (uint32_t i = 0; i < n; i++) c->fwd_voices = c->fwd_voices || c->slot_voiced(slots[i]);   // the newcomers' own voices (tts_hip_parler_seq_voices before the admission)
             HIPCHK(hipMemcpyAsync(c->d_ids, c->h_ids, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(c->d_seq, c->h_seq, (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
@@ -1828,6 +1964,8 @@ extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint3
     if (g.mixed)
         for (uint32_t r = 0; r < live; r++) if (g.slot_sampled[g.row_slot[r]]) { mode = MODE_GEN_MIXED; break; }
     c->host_pos.resize(R);
+    c->fwd_voices = false;   // of this run: chosen here, from the live slots, for all its steps
+    for (uint32_t r = 0; r < live; r++) c->fwd_voices = c->fwd_voices || c->slot_voiced(g.row_slot[r]);
     const uint32_t max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS);
     for (uint32_t s = 0; s < n_steps; s++) {
         for (uint32_t r = 0; r < R; r++) c->host_pos[r] = r < live ? std::min(g.pos[r] + s, max_pos - 1) : 0;
@@ -2216,6 +2354,19 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         const size_t n = (size_t) 16 * c->b1_stamp_slot * 2;
         if (n > max_floats) { set_err("buffer too small"); return -1; }
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, c->b1_stamps, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        return (int64_t) n;
+    }
+    if (c->has_parler && w == "graphs") {   // how many captured steps the context holds (the tests' "nothing was recaptured")
+        if (max_floats < 1) { set_err("buffer too small"); return -1; }
+        out[0] = (float) c->graphs.size();
+        return 1;
+    }
+    if (c->has_parler && starts_with(w, "voice:")) {  // voice:<v>:<layer>:<0|1>  -> [len][H] of bank entry v
+        int v = 0, layer = 0, kv = 0;
+        if (sscanf(w.c_str() + 6, "%d:%d:%d", &v, &layer, &kv) != 3 || v < 1 || v > c->vb_n || layer < 0 || layer >= c->L || kv < 0 || kv > 1) { set_err("debug_read(%s): bad voice spec", what); return -1; }
+        const size_t n = (size_t) c->vb_len_h[v] * c->H;
+        if (n > max_floats) { set_err("buffer too small"); return -1; }
+        if (n && hipMemcpy(out, c->vb_kv + (size_t) (v - 1) * c->voice_stride() + ((size_t) layer * 2 + kv) * tts_hip_ctx::VOICE_POS * c->H, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
     if (starts_with(w, "cross:")) {  // cross:<layer>:<0|1>  -> [E][H]

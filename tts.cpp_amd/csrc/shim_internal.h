@@ -121,6 +121,18 @@ struct tts_hip_ctx {
     char *text_enc_ptr() const { return cond_text_enc ? cond_text_enc : arena + text_enc; }
     char *cross_kv_ptr() const { return cond_cross_kv ? cond_cross_kv : arena + cross_kv; }
     std::vector<PLayer> layers;
+    // Per-request voice descriptions (tts_hip_parler_voice_bank): voices 1 .. vb_n, each [L][2][VOICE_POS][H] fp32 cross K / V plus a length; voice 0 is the
+    // description above.  The context's own, also on a shared arena.  Captured launches hold vb_kv / vb_len / vb_seq by pointer: none is ever reallocated.
+    enum { VOICE_POS = 32, VOICE_MAX = 256 };   // 32: what attn_short_body<32> covers
+    int vb_n = 0;
+    float *vb_kv = nullptr, *vb_enc = nullptr;   // the bank; staging for one description's T5 output [VOICE_POS][H]
+    int *vb_len = nullptr;                       // device [vb_n + 1]
+    uint32_t *vb_seq = nullptr;                  // device [max_seqs + 1]: voice of a cache slot
+    std::vector<int> vb_len_h;                   // host mirrors
+    std::vector<uint32_t> vb_seq_h;
+    bool fwd_voices = false;                     // the forward being staged has a row whose slot carries a non-zero voice: enqueue_forward's "voices" variant
+    size_t voice_stride() const { return (size_t) L * 2 * VOICE_POS * H; }
+    bool slot_voiced(uint32_t s) const { return s < vb_seq_h.size() && vb_seq_h[s] != 0; }
 
     // dac model
     int d_ncb = 0, d_cbsize = 0, d_cbdim = 0, d_latent = 0, d_c0 = 0, d_clast = 0, d_up = 1;
@@ -338,6 +350,8 @@ struct tts_hip_ctx {
     // the generation loop between tts_hip_parler_gen_begin and its last gen_wait: launch enqueues steps, wait looks in
     struct GenLoop {
         bool active = false, done = false;
+        bool voices = false;     // some utterance's slot carried a non-zero voice at gen_begin: every step is the "voices" variant
+        bool unwaited = false;   // a gen_launch has enqueued steps that no gen_wait has waited for
         int mode = 0;
         uint32_t n = 0, n_steps = 0, bos = 0, eos = 0;
         uint32_t R = 0;          // rows of the forward (<= n after a compaction)

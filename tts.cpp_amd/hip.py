@@ -98,6 +98,7 @@ EXPORTS = [
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
     "tts_hip_dia_stream_begin_mixed", "tts_hip_dia_stream_admit_mixed", "tts_hip_sample_logits_rows_mixed",
     "tts_hip_parler_stream_begin_mixed", "tts_hip_parler_stream_admit_mixed",
+    "tts_hip_parler_voice_bank", "tts_hip_parler_voice_set", "tts_hip_parler_seq_voices",
 ]
 
 class Sampling(C.Structure):
@@ -229,6 +230,9 @@ def load_lib():
     L.tts_hip_sample_logits_rows_mixed.argtypes = [vp, C.c_uint32, f32p, C.POINTER(C.POINTER(Sampling)), f32p, C.POINTER(C.c_int32), u32p, u32p]
     L.tts_hip_parler_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     L.tts_hip_parler_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
+    L.tts_hip_parler_voice_bank.argtypes = [vp, C.c_uint32]
+    L.tts_hip_parler_voice_set.argtypes = [vp, C.c_uint32, f32p, C.c_uint32]
+    L.tts_hip_parler_seq_voices.argtypes = [vp, C.c_uint32, u32p, u32p]
     _lib = L
     return L
 
@@ -376,6 +380,23 @@ class HipEngine:
     def set_text_encoding(self, enc):
         enc = np.ascontiguousarray(enc, dtype=np.float32)
         self._chk(self.L.tts_hip_parler_set_text_encoding(self.ctx, enc.ctypes.data_as(C.POINTER(C.c_float)), enc.shape[0]))
+
+    # ---- per-request voice descriptions (tts_hip_parler_voice_*) ----
+    def voice_bank(self, n_voices):
+        """room for voices 1 .. n_voices; voice 0 is the context's own description"""
+        self._chk(self.L.tts_hip_parler_voice_bank(self.ctx, n_voices))
+
+    def voice_set(self, voice, enc):
+        """enc [n_tokens][hidden]: the T5 output of the description, at most 32 positions"""
+        enc = np.ascontiguousarray(enc, dtype=np.float32)
+        self._chk(self.L.tts_hip_parler_voice_set(self.ctx, voice, enc.ctypes.data_as(C.POINTER(C.c_float)), enc.shape[0]))
+
+    def seq_voices(self, seqs, voices):
+        """the voice of each named cache slot (before its prefill / admission)"""
+        s, sp = _u32(seqs)
+        v, vp = _u32(voices)
+        assert s.size == v.size
+        self._chk(self.L.tts_hip_parler_seq_voices(self.ctx, s.size, sp, vp))
 
     # ---- parler -------------------------------------------------------------------------------
     def reset(self):

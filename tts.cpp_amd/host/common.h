@@ -131,7 +131,7 @@ struct tts_generation_runner : tts_runner {
     // per-request configurations: stream_accepts() says whether THIS open session can take a request with `config` although it differs from the one
     // the session was opened with (orpheus_runner: the voice is a prompt prefix and every cache slot carries its own sampler; dia_runner: every slot
     // carries its own sampler, seed and step budget, up to the length the session was opened for; parler_runner: every slot carries its own sampler
-    // and seed where a head has at most 2048 logits, the voice description stays the session's; the default, and every other runner so far: no),
+    // and seed where a head has at most 2048 logits, and the voice description it names — empty, or one entered by add_voice; the default, and every other runner so far: no),
     // and the three-argument stream_submit() enters such a request; its default ignores `config` — the caller has established that it equals
     // the session's.  A request stream_accepts() would refuse makes stream_submit() fail like a bad prompt does
     // (TTS_ABORT), with the session unchanged.
@@ -170,6 +170,14 @@ struct tts_generation_runner : tts_runner {
     // generate_batch()'s audio of that utterance
     virtual void generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
                                         const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
+
+    // ---- extension: a named voice description beside the runner's own (parler_runner: T5-encoded like update_conditional_prompt's, at most 32
+    // tokens, kept in the device's voice bank).  generation_configuration::voice == name then selects it per request, in generate, generate_batch,
+    // the chunked forms and the session — requests with different voices share one lock-step forward.  A known name is replaced (refused while a
+    // session slot uses it); list_voices() returns the names.  The default aborts: "this runner has no voice descriptions".
+    // Declared after every other virtual on purpose: a new virtual goes at the END of this class, so that an application compiled against an earlier
+    // common.h (the reference's cli / perf_battery / server through compat/) keeps calling the functions it means.
+    virtual void add_voice(const char * name, const char * text_encoder_path, const char * description);
 
   protected:
     std::vector<std::vector<float>> batch_store_;  // audio of the default generate_batch

@@ -153,6 +153,23 @@ int device_pool::submit_conditional_prompt(const std::string & model, const std:
     return parent->id;
 }
 
+int device_pool::submit_add_voice(const std::string & model, const std::string & name, const std::string & description) {
+    auto parent = std::make_shared<pool_task>();
+    parent->task = POOL_ADD_VOICE;
+    parent->id = next_id_.fetch_add(1);
+    parent->model = model;
+    parent->prompt = description;
+    parent->voice_name = name;
+    {
+        std::lock_guard<std::mutex> lock(q_mutex_);
+        if (!running_) return -1;
+        fanouts_[parent->id] = fanout{parent, opts_.n_workers, true, ""};
+        for (int w = 0; w < opts_.n_workers; w++) per_worker_[(size_t) w].push_back(std::make_shared<pool_task>(*parent));   // same id, as above
+    }
+    q_cv_.notify_all();
+    return parent->id;
+}
+
 int device_pool::submit_voices() {
     auto t = std::make_shared<pool_task>();
     t->task = POOL_VOICES;
@@ -230,7 +247,7 @@ void device_pool::worker_main(int w) {
         if (batch.empty()) break;
         if (batch[0]->task != POOL_TTS) {
             control(w, *batch[0], ws);
-            if (batch[0]->task == POOL_CONDITIONAL_PROMPT) {
+            if (batch[0]->task == POOL_CONDITIONAL_PROMPT || batch[0]->task == POOL_ADD_VOICE) {
                 std::shared_ptr<pool_task> done;
                 {
                     std::lock_guard<std::mutex> lock(q_mutex_);
@@ -401,14 +418,15 @@ void device_pool::process_stream(int w, std::vector<std::shared_ptr<pool_task>> 
 void device_pool::control(int w, pool_task & t, worker_state & ws) {
     t.worker = w;
     try {
-        if (t.task == POOL_CONDITIONAL_PROMPT) {
+        if (t.task == POOL_CONDITIONAL_PROMPT || t.task == POOL_ADD_VOICE) {
             if (opts_.text_encoder_path.empty()) {
                 t.message = "A text encoder path must be specified on server initialization in order to support conditional prompting.";  // :264-266
                 return;
             }
             auto found = ws.runners.find(t.model);
             if (found == ws.runners.end() || !found->second) { t.message = "unknown model '" + t.model + "'"; return; }
-            found->second->update_conditional_prompt(opts_.text_encoder_path.c_str(), t.prompt.c_str());
+            if (t.task == POOL_ADD_VOICE) found->second->add_voice(t.voice_name.c_str(), opts_.text_encoder_path.c_str(), t.prompt.c_str());
+            else found->second->update_conditional_prompt(opts_.text_encoder_path.c_str(), t.prompt.c_str());
             t.success = true;
         } else {  // VOICES
             for (const auto & [id, runner] : ws.runners) {

@@ -25,13 +25,14 @@
 
 #include "common.h"
 
-enum pool_task_type { POOL_TTS = 0, POOL_CONDITIONAL_PROMPT = 1, POOL_VOICES = 2 };  // task_type (server.cpp:94-98)
+enum pool_task_type { POOL_TTS = 0, POOL_CONDITIONAL_PROMPT = 1, POOL_VOICES = 2, POOL_ADD_VOICE = 3 };  // task_type (server.cpp:94-98); ADD_VOICE: an extension
 
 struct pool_task {  // simple_server_task (:100-123); the audio is copied out of the runner-owned buffer
     pool_task_type           task = POOL_TTS;
     int                      id = 0;
     std::string              model;
     std::string              prompt;
+    std::string              voice_name;   // ADD_VOICE: the name `prompt` (the description) is kept under
     generation_configuration gen_config;
     std::vector<float>       audio;
     float                    sample_rate = 44100.0f;
@@ -89,6 +90,8 @@ class device_pool {
     // the last worker has applied it).  VOICES (:272-306): "model/voice,voice;model/..." in pool_task::message.
     int submit_conditional_prompt(const std::string & model, const std::string & prompt);
     int submit_voices();
+    // tts_generation_runner::add_voice(name, text_encoder_path, description) on every worker's runner of `model`, fanned out like CONDITIONAL_PROMPT
+    int submit_add_voice(const std::string & model, const std::string & name, const std::string & description);
     // block until task `id` is finished (simple_response_map::get :203-218); nullptr after terminate()/timeout
     std::shared_ptr<pool_task> wait(int id, int timeout_ms = -1);
     void       release(int id);  // drop a finished task from the response map (the reference's cleanup thread, :168-189)

@@ -44,6 +44,9 @@ uint32_t tts_load_max_seqs() {
 std::vector<std::string_view> tts_generation_runner::list_voices() {
     TTS_ABORT("The architecture '%s' does not support #list_voices.\n", loader.get().arch);
 }
+void tts_generation_runner::add_voice(const char *, const char *, const char *) {
+    TTS_ABORT("The architecture '%s' cannot add a voice: this runner has no voice descriptions.\n", loader.get().arch);
+}
 void tts_generation_runner::update_conditional_prompt(const char *, const char *) {
     TTS_ABORT("The architecture '%s' does not support update_conditional_prompt.\n", loader.get().arch);
 }

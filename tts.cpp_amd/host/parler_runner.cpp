@@ -121,7 +121,7 @@ void parler_runner::prepare_post_load() {
 // model.cpp:510-518: text_encoder_from_file (t5/model.cpp:365-402) with THIS runner's tokenizer, t5_runner::generate
 // (:359-364: tokenize + EOS, run), then prep_cross_key_values with the response.  The encoder lives in its own device
 // context for the duration of the call, as the reference builds and deletes a t5_runner per call.
-void parler_runner::update_conditional_prompt(const char * file_path, const char * prompt) {
+std::vector<float> parler_runner::encode_description(const char * file_path, const char * prompt, const char * what, std::vector<uint32_t> & tokens) {
     std::string err;
     std::shared_ptr<gguf_file> meta = gguf_file::open(file_path, err);
     if (!meta) TTS_ABORT("text_encoder_from_file failed for file %s: %s\n", file_path, err.c_str());
@@ -139,7 +139,7 @@ void parler_runner::update_conditional_prompt(const char * file_path, const char
     meta->get_u32({"t5encoder.output_size"}, td.output_size);
     td.gelu_mode = 1;
     if (td.output_size != hp.hidden_size)
-        TTS_ABORT("update_conditional_prompt: the encoder's output size %u differs from the decoder's hidden size %u\n", td.output_size, hp.hidden_size);
+        TTS_ABORT("%s: the encoder's output size %u differs from the decoder's hidden size %u\n", what, td.output_size, hp.hidden_size);
 
     tts_hip_ctx * t5 = tts_hip_t5_create(device_id, &td);
     if (!t5) TTS_ABORT("tts_hip_t5_create failed: %s\n", tts_hip_last_error());
@@ -150,15 +150,76 @@ void parler_runner::update_conditional_prompt(const char * file_path, const char
     }
     hip_check(tts_hip_finalize(t5, nullptr), "tts_hip_finalize(t5)");
 
-    std::vector<uint32_t> tokens;
+    tokens.clear();
     tokenizer->tokenize(prompt, tokens);
     tokens.push_back(eos);
     if (tokens.size() > td.max_ctx_length || tokens.size() > 512)   // max_encode_length, model.h:69
-        TTS_ABORT("update_conditional_prompt: %zu prompt tokens exceed the encoder context %u\n", tokens.size(), td.max_ctx_length);
+        TTS_ABORT("%s: %zu prompt tokens exceed the encoder context %u\n", what, tokens.size(), td.max_ctx_length);
     std::vector<float> enc(tokens.size() * (size_t) td.output_size);
     hip_check(tts_hip_t5_encode(t5, tokens.data(), (uint32_t) tokens.size(), enc.data()), "tts_hip_t5_encode");
+    return enc;
+}
+
+void parler_runner::update_conditional_prompt(const char * file_path, const char * prompt) {
+    std::vector<uint32_t> tokens;
+    const std::vector<float> enc = encode_description(file_path, prompt, "update_conditional_prompt", tokens);
     hip_check(tts_hip_parler_set_text_encoding(ctx, enc.data(), (uint32_t) tokens.size()), "tts_hip_parler_set_text_encoding");
     last_conditional_tokens = tokens;
+}
+
+void parler_runner::add_voice(const char * name, const char * text_encoder_path, const char * description) {
+    if (!name || !*name) TTS_ABORT("add_voice: a voice needs a name (the empty name is the runner's own description)\n");
+    if (!use_cross_attn) TTS_ABORT("add_voice: the model was loaded without cross attention\n");
+    size_t idx = 0;
+    while (idx < voice_names.size() && voice_names[idx] != name) idx++;
+    if (idx == VOICE_BANK) TTS_ABORT("add_voice: the bank holds %u voices\n", VOICE_BANK);
+    if (st_on && idx < voice_names.size()) {
+        for (const pending & p : st_wait)
+            if (p.voice == idx + 1) TTS_ABORT("add_voice: voice '%s' is in use by a request waiting for its admission\n", name);
+        for (uint32_t s = 0; s < (uint32_t) st_voice.size(); s++) {
+            bool free_slot = false;
+            for (uint32_t f : st_free) free_slot = free_slot || f == s;
+            if (!free_slot && st_voice[s] == idx + 1) TTS_ABORT("add_voice: voice '%s' is in use by a session slot\n", name);
+        }
+    }
+    std::vector<uint32_t> tokens;
+    const std::vector<float> enc = encode_description(text_encoder_path, description, "add_voice", tokens);
+    if (tokens.size() > VOICE_TOKENS)
+        TTS_ABORT("add_voice: the description of '%s' has %zu tokens; a voice holds at most %u\n", name, tokens.size(), VOICE_TOKENS);
+    if (!voice_bank_made) {
+        hip_check(tts_hip_parler_voice_bank(ctx, VOICE_BANK), "tts_hip_parler_voice_bank");
+        voice_bank_made = true;
+        voice_names.reserve(VOICE_BANK);   // list_voices hands out views
+    }
+    hip_check(tts_hip_parler_voice_set(ctx, (uint32_t) idx + 1, enc.data(), (uint32_t) tokens.size()), "tts_hip_parler_voice_set");
+    if (idx == voice_names.size()) voice_names.emplace_back(name);
+    last_conditional_tokens = tokens;
+}
+
+std::vector<std::string_view> parler_runner::list_voices() {
+    return std::vector<std::string_view>(voice_names.begin(), voice_names.end());
+}
+
+bool parler_runner::voice_known(const std::string & voice) const {
+    if (voice.empty()) return true;
+    for (const std::string & v : voice_names) if (v == voice) return true;
+    return false;
+}
+
+uint32_t parler_runner::voice_index(const std::string & voice, const char * what) const {
+    if (voice.empty()) return 0;
+    std::string known;
+    for (size_t i = 0; i < voice_names.size(); i++) {
+        if (voice_names[i] == voice) return (uint32_t) i + 1;
+        known += (i ? ", " : "") + voice_names[i];
+    }
+    TTS_ABORT("%s: unknown voice '%s' (known: %s)\n", what, voice.c_str(), known.empty() ? "none; add_voice enters one" : known.c_str());
+}
+
+// a runner without added voices never calls into the bank: every slot is at voice 0 as it always was
+void parler_runner::set_slot_voices(const std::vector<uint32_t> & slots, const std::vector<uint32_t> & voices, const char * what) {
+    if (voice_names.empty() || slots.empty()) return;
+    hip_check(tts_hip_parler_seq_voices(ctx, (uint32_t) slots.size(), slots.data(), voices.data()), what);
 }
 
 // model.cpp:734-760, including the `next_index > size` bound (an index == size would read one past the
@@ -215,6 +276,7 @@ bool parler_runner::prepare_single(const char * sentence, const generation_confi
     if (config.use_cross_attn != use_cross_attn)
         TTS_ABORT("generate(): use_cross_attn differs from the value the model was loaded with (the reference only "
                   "loads the encoder_attn tensors when it is set at load time, model.cpp:202-237)\n");
+    const uint32_t voice = voice_index(config.voice, "generate()");
     const bool room = tokenize_prompt(sentence, prompt);
     last_prompt_tokens = prompt;
     last_output_tokens.clear();
@@ -224,6 +286,7 @@ bool parler_runner::prepare_single(const char * sentence, const generation_confi
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", prompt.size());
         return false;
     }
+    set_slot_voices({0}, {voice}, "tts_hip_parler_seq_voices");
     hip_check(tts_hip_parler_prefill(ctx, 0, prompt.data(), (uint32_t) prompt.size(), 0), "tts_hip_parler_prefill");
     return true;
 }
@@ -238,6 +301,7 @@ bool parler_runner::prepare_batch(const std::vector<std::string> & sentences, co
     if (n_all == 0) return false;
     if (n_all > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n_all, max_seqs);
     if (config.use_cross_attn != use_cross_attn) TTS_ABORT("generate_batch: use_cross_attn differs from load time\n");
+    const uint32_t voice = voice_index(config.voice, "generate_batch");
     // an utterance whose prompt leaves no room gets an empty response, exactly as generate() does
     std::vector<uint32_t> ids, p;
     for (uint32_t i = 0; i < n_all; i++) {
@@ -252,6 +316,11 @@ bool parler_runner::prepare_batch(const std::vector<std::string> & sentences, co
     const uint32_t n = (uint32_t) row_of.size();
     if (n == 0) return false;
     hip_check(tts_hip_parler_reset(ctx), "tts_hip_parler_reset");
+    {
+        std::vector<uint32_t> rows(n);
+        for (uint32_t i = 0; i < n; i++) rows[i] = i;
+        set_slot_voices(rows, std::vector<uint32_t>(n, voice), "tts_hip_parler_seq_voices");
+    }
     hip_check(tts_hip_parler_prefill_batch(ctx, n, nullptr, ids.data(), start.data(), nullptr), "tts_hip_parler_prefill_batch");
     return true;
 }
@@ -505,6 +574,7 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     if (stream_capacity() == 0) TTS_ABORT("stream_begin: the runner was loaded with max_seqs=%u; a session needs >= 2 (TTS_HIP_MAX_SEQS)\n", max_seqs);
     if (config.use_cross_attn != use_cross_attn) TTS_ABORT("stream_begin: use_cross_attn differs from load time\n");
     if (config.sample && hp.output_vocab_size > 2048) TTS_ABORT("stream_begin: sampling over %u logits per head is host-only\n", hp.output_vocab_size);
+    (void) voice_index(config.voice, "stream_begin");
     if (st_on) stream_end();
     const uint32_t slots = stream_capacity();
     st_cfg = config;
@@ -521,6 +591,7 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
     st_ticket.assign(slots, 0);
     st_start.assign(slots, 0);
+    st_voice.assign(slots, 0);
     st_wait.clear(); st_codec.clear(); st_pcm.clear();
     st_live = 0;
     st_codec_held = 0;
@@ -528,7 +599,7 @@ void parler_runner::stream_begin(const generation_configuration & config) {
 }
 
 bool parler_runner::stream_accepts(const generation_configuration & config) const {
-    return st_on && st_mixed && config.use_cross_attn == use_cross_attn && device_sampler(config);
+    return st_on && st_mixed && config.use_cross_attn == use_cross_attn && device_sampler(config) && voice_known(config.voice);
 }
 
 void parler_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
@@ -542,6 +613,7 @@ void parler_runner::stream_submit(size_t ticket, const std::string & sentence, c
     pending p;
     p.ticket = ticket;
     p.cfg = st_mixed ? config : st_cfg;   // a session without per-slot samplers runs everything with the configuration it was opened with
+    p.voice = voice_index(p.cfg.voice, "stream_submit");
     if (!tokenize_prompt(sentence, p.prompt)) {
         // generate() answers such a prompt with an empty response: the session does the same at its next step
         fprintf(stderr, "prompt of %zu tokens leaves no room for generation\n", p.prompt.size());
@@ -559,7 +631,7 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
     finished.clear();
     const uint32_t nh = hp.n_output_heads;
     if (!st_wait.empty()) {   // the newcomers: one prefill side batch, then rows of the lock-step forward
-        std::vector<uint32_t> slots, ids, lens;
+        std::vector<uint32_t> slots, ids, lens, voices;
         std::vector<float> uni;
         std::vector<tts_hip_sampling> sps(st_wait.size());
         std::vector<const tts_hip_sampling *> spp(st_wait.size(), nullptr);
@@ -569,6 +641,8 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
         for (size_t i = 0; i < st_wait.size(); i++) {
             const pending & p = st_wait[i];
             slots.push_back(p.slot);
+            voices.push_back(p.voice);
+            st_voice[p.slot] = p.voice;
             lens.push_back((uint32_t) p.prompt.size());
             ids.insert(ids.end(), p.prompt.begin(), p.prompt.end());
             st_ticket[p.slot] = p.ticket;
@@ -579,6 +653,7 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
             spp[i] = &sps[i];
             draw_row_uniforms(smp, p.cfg.seed, st_max_steps, nh, uni.data() + i * (size_t) st_max_steps * nh);
         }
+        set_slot_voices(slots, voices, "tts_hip_parler_seq_voices");   // before the admission: its prefill already attends
         if (st_mixed)
             hip_check(tts_hip_parler_stream_admit_mixed(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), spp.data(), any_sampled ? uni.data() : nullptr),
                       "tts_hip_parler_stream_admit_mixed");

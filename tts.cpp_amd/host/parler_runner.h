@@ -48,6 +48,10 @@ struct parler_runner final : tts_generation_runner {
     void prepare_post_load() override;
     void generate(const char * sentence, tts_response & output, const generation_configuration & config) override;
     void update_conditional_prompt(const char * file_path, const char * prompt) override;
+    // named voice descriptions (common.h): each lives in the device's voice bank (tts_hip_parler_voice_bank, created on first use with 64 entries)
+    // and is selected per request by generation_configuration::voice; "" is the runner's own description.  More than 32 tokens abort.
+    void add_voice(const char * name, const char * text_encoder_path, const char * description) override;
+    std::vector<std::string_view> list_voices() override;
 
     // Extension (the reference generates one utterance per call; its only multi-utterance construct is the
     // server's pool of full replicas, examples/server/server.cpp:885-895): n utterances decoded in lock-step on
@@ -66,7 +70,9 @@ struct parler_runner final : tts_generation_runner {
     // With at most 2048 logits per head the session is a mixed one (tts_hip_parler_stream_begin_mixed): every slot carries its own sampler record
     // and penalty table, so a request may differ from the session's configuration in sample, seed, top_k, top_p, temperature and
     // repetition_penalty.  It is accepted when use_cross_attn is the load-time value and it is greedy or within the device sampler's limits; its
-    // uniforms are drawn from its own seed, as a generate() call of its own draws them.  The voice description stays the session's.
+    // uniforms are drawn from its own seed, as a generate() call of its own draws them.  Its voice is empty (the runner's own description) or a name
+    // add_voice has entered: the slot's voice is set before its admission (tts_hip_parler_seq_voices), so requests with different voices share
+    // the session's forward; an unknown name is refused.
     bool     stream_accepts(const generation_configuration & config) const override;
     void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
@@ -97,6 +103,15 @@ struct parler_runner final : tts_generation_runner {
     std::vector<float>                 pcm;     // runner-owned output buffer (dctx->buf_output)
 
   private:
+    static constexpr uint32_t VOICE_BANK = 64, VOICE_TOKENS = 32;   // bank entries; positions an entry holds
+    std::vector<std::string> voice_names;   // voice i + 1 of the device's bank
+    bool                     voice_bank_made = false;
+    std::vector<uint32_t>    st_voice;      // slot -> voice of its occupant (session)
+    // T5-encode a description with this runner's tokenizer: the ids (+ EOS) and the encoder's output [ids][hidden]
+    std::vector<float> encode_description(const char * file_path, const char * prompt, const char * what, std::vector<uint32_t> & tokens);
+    bool     voice_known(const std::string & voice) const;
+    uint32_t voice_index(const std::string & voice, const char * what) const;   // "" -> 0; unknown: TTS_ABORT listing the names
+    void     set_slot_voices(const std::vector<uint32_t> & slots, const std::vector<uint32_t> & voices, const char * what);
     bool tokenize_prompt(const std::string & sentence, std::vector<uint32_t> & prompt) const;
     bool prepare_single(const char * sentence, const generation_configuration & config, std::vector<uint32_t> & prompt);
     bool prepare_batch(const std::vector<std::string> & sentences, const generation_configuration & config, std::vector<uint32_t> & start,
@@ -107,7 +122,7 @@ struct parler_runner final : tts_generation_runner {
     std::vector<std::vector<uint32_t>> run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook);
     std::vector<tts_response> decode_frames(const std::vector<uint32_t> & codes, const std::vector<uint32_t> & frames);
     // session state of the continuous batching
-    struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; generation_configuration cfg; };
+    struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; generation_configuration cfg; uint32_t voice = 0; };
     struct decoded { size_t ticket; std::vector<uint32_t> frames; };   // un-delayed codes waiting for a codec pass
     bool                        st_on = false;
     bool                        st_mixed = false;    // the open session carries a sampler per slot

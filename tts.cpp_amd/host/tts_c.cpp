@@ -191,6 +191,39 @@ int tts_c_update_conditional_prompt(tts_c_runner * r, const char * text_encoder_
     }
 }
 
+int tts_c_add_voice(tts_c_runner * r, const char * name, const char * text_encoder_path, const char * description) {
+    if (!r || !name || !text_encoder_path || !description) { g_c_err = "tts_c_add_voice: null argument"; return -1; }
+    g_tts_throw_on_abort = true;
+    try {
+        ((tts_generation_runner *) r)->add_voice(name, text_encoder_path, description);
+        return 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
+int tts_c_list_voices(tts_c_runner * r, char * out, int cap) {
+    if (!r) { g_c_err = "tts_c_list_voices: null runner"; return -1; }
+    g_tts_throw_on_abort = true;
+    try {
+        std::string all;
+        for (const std::string_view v : ((tts_generation_runner *) r)->list_voices()) {
+            if (!all.empty()) all += ",";
+            all += v;
+        }
+        if (out && cap > 0) {
+            const size_t n = std::min(all.size(), (size_t) cap - 1);
+            memcpy(out, all.data(), n);
+            out[n] = 0;
+        }
+        return (int) all.size();
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
 void tts_c_set_load_options(int device, int max_seqs, int declare_only) {
     tts_load_options & o = tts_thread_load_options();
     o = tts_load_options{};
@@ -473,6 +506,13 @@ void tts_c_pool_set_continuous(int on) { g_pool_continuous = on != 0; }
 static thread_local int g_pool_yield_ms = 2000;
 void tts_c_pool_set_continuous_yield_ms(int ms) { g_pool_yield_ms = ms < 0 ? 0 : ms; }
 uint64_t tts_c_pool_admitted_in_flight(tts_c_pool * p) { return p->pool->stats().admitted_in_flight; }
+
+int tts_c_pool_add_voice(tts_c_pool * p, const char * name, const char * description) {
+    if (!p || !name || !description) { g_c_err = "tts_c_pool_add_voice: null argument"; return -1; }
+    const int id = p->pool->submit_add_voice("default", name, description);
+    if (id < 0) g_c_err = "pool is terminated";
+    return id;
+}
 
 int tts_c_pool_conditional_prompt(tts_c_pool * p, const char * prompt) {
     const int id = p->pool->submit_conditional_prompt("default", prompt);

@@ -32,7 +32,8 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
-           "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs"]
+           "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs",
+           "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -72,6 +73,9 @@ def load_lib():
         L.tts_c_gguf_summary.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_int]
         L.tts_c_gguf_tensor.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
         L.tts_c_update_conditional_prompt.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.tts_c_add_voice.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
+        L.tts_c_list_voices.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.tts_c_pool_add_voice.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.tts_c_single_pass_tokenize.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]
         L.tts_c_kokoro_chunks.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]
         L.tts_c_dia_tokenize.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -125,7 +129,7 @@ def make_config(**kw):
     c = Config()
     load_lib().tts_c_default_config(C.byref(c))
     for k, v in kw.items():
-        setattr(c, k, v)
+        setattr(c, k, v.encode("utf-8") if isinstance(v, str) else v)   # voice: a C string
     return c
 
 
@@ -259,6 +263,19 @@ class Runner:
     def update_conditional_prompt(self, text_encoder_path, prompt):
         if self.L.tts_c_update_conditional_prompt(self.h, text_encoder_path.encode(), prompt.encode("utf-8")) != 0:
             raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
+
+    def add_voice(self, name, text_encoder_path, description):
+        """a named voice description beside the runner's own; generate(..., voice=name) and the sessions select it per request"""
+        if self.L.tts_c_add_voice(self.h, name.encode("utf-8"), text_encoder_path.encode(), description.encode("utf-8")) != 0:
+            raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
+
+    def list_voices(self):
+        n = self.L.tts_c_list_voices(self.h, None, 0)
+        if n < 0:
+            raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
+        buf = C.create_string_buffer(n + 1)
+        self.L.tts_c_list_voices(self.h, buf, n + 1)
+        return [v for v in buf.value.decode("utf-8").split(",") if v]
 
     def last_tokens(self, which):
         n = self.L.tts_c_last_tokens(self.h, which, None, 0)
@@ -416,6 +433,13 @@ class Pool:
     def submit(self, text, **cfg):
         c = make_config(**cfg) if cfg else self.cfg
         i = self.L.tts_c_pool_submit(self.h, text.encode("utf-8"), C.byref(c))
+        if i < 0:
+            raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
+        return i
+
+    def add_voice(self, name, description):
+        """add_voice on every worker (the pool's text encoder); wait on the returned id like any task"""
+        i = self.L.tts_c_pool_add_voice(self.h, name.encode("utf-8"), description.encode("utf-8"))
         if i < 0:
             raise RunnerError(self.L.tts_c_last_error().decode("utf-8", "replace"))
         return i
