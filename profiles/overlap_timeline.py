@@ -12,7 +12,7 @@ rows = []
 for r in csv.DictReader(open(sys.argv[1])):
     n = r["Kernel_Name"]
     cls = "codec" if any(k in n for k in CODEC) else "attn" if ("attn_kernel" in n or "attn_walk" in n or "attn_rows" in n) else "gemm" if "gemm" in n else "other"
-    rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), cls, r.get("Queue_Id", "?"), r.get("Stream_Id", r.get("Queue_Id", "?"))))
+    rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), cls, r.get("Queue_Id", "?"), r.get("Stream_Id", r.get("Queue_Id", "?")), n))
 rows.sort()
 t0, t1 = rows[0][0], rows[-1][1]
 lo, hi = t0 + (t1 - t0) * 0.35, t0 + (t1 - t0) * 0.95      # skip loading / warm-up
@@ -49,7 +49,7 @@ def inter(a, b):
 
 
 by = defaultdict(list)
-for s, e, c, q, st in rows:
+for s, e, c, q, st, _n in rows:
     by[c].append((s, e))
 span = rows[-1][1] - rows[0][0]
 print(f"window {span / 1e9:.3f} s, {len(rows)} dispatches on {len(set(r[3] for r in rows))} hardware queues")
@@ -73,3 +73,13 @@ for s, e in by.get("attn", []):
     (ov if hit else free).append(e - s)
 if ov and free:
     print(f"  self-attention launches: {len(free)} outside codec time, mean {sum(free) / len(free) / 1e3:.1f} us; {len(ov)} overlapping a codec kernel, mean {sum(ov) / len(ov) / 1e3:.1f} us")
+# per codec kernel family: the share of its running time during which a self-attention kernel (of another runner: a runner's own decoder loop and codec
+# passes follow each other) is running too — the register budget of DESIGN.md §4.1 decides which families an attention wave fits beside
+FAMILIES = (("resunit_t7_kernel<6", "resunit_t7 192 ch"), ("resunit_t7_kernel<3", "resunit_t7 96 ch"), ("conv_b3p_kernel<7", "conv_b3p<7>"), ("convt_b3_kernel", "convt_b3"))
+rows_attn = U.get("attn", [])
+for key, label in FAMILIES:
+    iv = [(s, e) for s, e, c, q, st, n in rows if key in n]
+    if iv:
+        u = union(iv)
+        print(f"  {label:18s} {len(iv):6d} launches, running {length(u) / 1e9:7.3f} s; with a self-attention kernel also running {length(inter(u, rows_attn)) / 1e9:7.3f} s = "
+              f"{100 * length(inter(u, rows_attn)) / max(1, length(u)):5.1f} %")

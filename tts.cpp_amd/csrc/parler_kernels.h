@@ -910,7 +910,7 @@ static __global__ __launch_bounds__(1024) void attn_kernel(AttnArgs a) {   // U 
 }
 
 // Self-attention of a many-row forward, one workgroup per ROW: 16 lanes per head, all heads of the row side by side (threads = 16 n_heads), the
-// keys of the row one after the other with the rows of eight keys in flight per lane.  A wave-instruction of the workgroup then reads ONE key's
+// keys of the row one after the other with the rows of U keys in flight per lane (U = 2, 4, 8: run_attn).  A wave-instruction of the workgroup then reads ONE key's
 // whole K (or V) row — 4 KB contiguous for Parler-Mini — where attn_kernel's one-head workgroups read 256-byte pieces 4 KB apart and leave it to
 // the dispatcher to run the 16 heads of a row close enough in time for the DRAM pages to be shared (5.7 TB/s; a plain streaming read reaches
 // 7.1 TB/s on this chip, profiles/r04/overlap_bench_synthetic.txt).  Every 16-lane group owns its head from the first key to the last: one running

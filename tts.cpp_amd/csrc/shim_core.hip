@@ -135,6 +135,7 @@ extern "C" tts_hip_ctx *tts_hip_create(int device, const tts_hip_desc *desc) {
     // tts_hip_tune() key: a harness under profiles/ can still flip it, a deployment cannot flip it by accident.
     if (const char *e = getenv("TTS_HIP_ATTN_NSPLIT")) c->attn_nsplit_override = atoi(e);
     if (const char *e = getenv("TTS_HIP_ATTN_ROWS")) c->attn_rows_min = std::max(0, atoi(e));                                                 // bench.py A/B, test_gpu_parler.py: row-major self-attention from this many rows (0: never)
+    if (const char *e = getenv("TTS_HIP_ATTN_ROWS_U")) (void) tts_hip_tune(c, "attn_rows_u", atoi(e));                                         // bench.py A/B, test_gpu_attn_rows_u.py: keys in flight per lane of that kernel (2 / 4 / 8)
     if (const char *e = getenv("TTS_HIP_DAC_GROUP")) c->dac_group = std::max(1, atoi(e));                       // test_gpu_dac_stages.py, bench.py: utterances per codec pass
     if (const char *e = getenv("TTS_HIP_DAC_BF16X3")) (void) tts_hip_tune(c, "dac_exact_fp32", atoi(e) == 0);  // test_gpu_dac.py: 0 = the exact-fp32 MFMA codec
     if (const char *e = getenv("TTS_HIP_DAC_SPLIT")) c->dac_split = atoi(e) != 0;                               // test_gpu_dac.py: 0 = bf16 x 3 products, 1 = fp16 hi + lo
@@ -175,6 +176,10 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "ln_fuse_max") c->ln_fuse_max = std::max(0, std::min(32, v));
     else if (k == "attn_short") c->attn_short = v != 0;
     else if (k == "attn_rows_min") c->attn_rows_min = std::max(0, v);
+    else if (k == "attn_rows_u") {   // the instantiations run_attn holds
+        if (v != 2 && v != 4 && v != 8) return set_err("tts_hip_tune: attn_rows_u is 2, 4 or 8 (got %d)", v);
+        c->attn_rows_u = v;
+    }
     else if (k == "attn_fused") c->attn_fused = v != 0;
     else if (k == "attn_split") c->attn_split_max = std::max(1, std::min(16, v));
     else if (k == "orpheus_batch_run") c->l_batch_run = (uint32_t) std::max(1, std::min(1024, v));

@@ -676,8 +676,14 @@ static int run_attn(tts_hip_ctx *c, int kclass, AttnArgs a, int R, int nsplit, d
         // are compacted from 384 to 256 keeps its summation order
         const int nzr = R >= 1024 ? 1 : 4;
         a.part = c->part;
-        // eight keys in flight per lane: 4 / 8 / 12 / 16 measured 5.19 / 5.25 / 5.28 / 5.67 ms per 1024-row step (profiles/r04/attn_rows_u_call22.txt)
-        hipLaunchKernelGGL(attn_rows_kernel<8>, dim3(R, nzr), dim3(c->NH * 16), 0, c->stream, a);
+        // keys in flight per lane (tune("attn_rows_u"), default 2): the instantiation belongs to the context, since a captured step graph is replayed while
+        // the history grows, and an in-kernel switch would cost every variant the registers of the largest.  Round 4 swept 4 / 8 / 12 / 16 at short
+        // histories (5.19 / 5.25 / 5.28 / 5.67 ms per 1024-row step, one run each, profiles/r04/attn_rows_u_call22.txt) and 8 stayed:
+        // 1 % between single runs decided nothing, and what 80 registers cost beside the codec had not been asked.  They keep the wave
+        // off every SIMD that another context's fused residual units occupy; 2 keys = 32 registers fit beside every codec kernel and
+        // are also the fastest alone, at short and at long histories (profiles/attn_beside_codec.txt)
+        auto *rows_kernel = c->attn_rows_u == 2 ? attn_rows_kernel<2> : c->attn_rows_u == 4 ? attn_rows_kernel<4> : attn_rows_kernel<8>;
+        hipLaunchKernelGGL(rows_kernel, dim3(R, nzr), dim3(c->NH * 16), 0, c->stream, a);
         HIPCHK(hipGetLastError());
         if (nzr > 1) {
             hipLaunchKernelGGL(attn_combine_kernel, dim3(c->NH, R), dim3(64), 0, c->stream, (const float *) a.part, nzr, c->H, c->NH, a.out, a.out16, a.out_q, a.out_dT, a.ldr);

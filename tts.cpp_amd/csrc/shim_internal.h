@@ -412,6 +412,7 @@ struct tts_hip_ctx {
     int dac_group = 64;         // TTS_HIP_DAC_GROUP: utterances per codec pass (16: 451, 32: 458, 64: 461, 128: 460, 384: 462 audio-s/s at 3 x 384)
     bool dac_conv1_direct = true;   // tune("dac_conv1_direct")=0: the 96- / 192-channel k=1 convs stay on conv1d_mfma_kernel<1,...>
     int attn_rows_min = 256;    // tune("attn_rows_min") / TTS_HIP_ATTN_ROWS: forwards with at least this many rows run the self-attention one workgroup per ROW (attn_rows_kernel); 0 = never
+    int attn_rows_u = 2;        // tune("attn_rows_u") / TTS_HIP_ATTN_ROWS_U: keys in flight per lane of attn_rows_kernel, 2 / 4 / 8 = 32 / 48 / 80 VGPRs; same arithmetic in the same key order.  2: a wave fits beside every codec kernel of another context (measured in profiles/attn_beside_codec.txt)
     int tile_min_rows = 33;     // forwards with at least this many rows take the LDS-tiled GEMM (gemm_tile_kernels.h); 0 = never
     int tile_force = -1;        // TTS_HIP_TILE_FORCE: tile shape index for every tiled GEMM (tuning)
     int tile_force_ks = 0;      // TTS_HIP_TILE_KS: k slices for the residual GEMMs (tuning)
