@@ -80,6 +80,16 @@ typedef struct tts_hip_desc {
                                        fp16 im2col x fp16 kernel semantics */
 #define TTS_HIP_FLAG_DEQUANT_Q  16u /* decode Q4_0/Q5_0/Q8_0 matrices to fp32 at upload (fp32 activations) instead of
                                        the integer path with Q8_0-quantised activations (ggml's CPU semantics) */
+#define TTS_HIP_FLAG_KV_F16     64u /* tts_hip_orpheus_create only (extension; the reference keeps fp32 K/V, orpheus/model.cpp:176-181):
+                                       the K/V cache is [slot][layer][position][kv width] in fp16 — half the cache memory and half
+                                       the bytes every attention launch reads.  Rotated K and V are rounded once, to nearest-even,
+                                       when they are appended (a plain fp32 -> fp16 conversion, as in Parler's fp16 cache,
+                                       tts_hip_desc::kv_type): a magnitude above 65504 becomes inf, one below 6.1e-5 keeps
+                                       fewer bits (fp16 subnormals).  All arithmetic stays fp32: query, scores, softmax and the
+                                       P.V sums run on the cache rows widened exactly.  Fixed at create for every path of the
+                                       context (decode, the captured step, step_batch / generate_batch, gen_*, stream_*).
+                                       tts_hip_create, tts_hip_t5_create, tts_hip_snac_create and tts_hip_dia_create refuse it
+                                       with an error that names the flag and the call. */
 
 typedef struct tts_hip_ctx tts_hip_ctx;
 
@@ -246,7 +256,7 @@ typedef struct tts_hip_orpheus_desc {
     uint32_t vocab_size;       /* orpheus.vocab_size (156940)  */
     uint32_t n_ctx;            /* KV positions: max_context_length + max_generation_size (1024 + 2100, :176-177) */
     float    rope_base;        /* 500000 (:190,250); 0 = that  */
-    uint32_t flags;            /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q */
+    uint32_t flags;            /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_KV_F16 (fp16 K/V cache, see the flag) */
     uint32_t max_seqs;         /* KV-cache slots for lock-step utterances (tts_hip_orpheus_generate_batch); 0 / 1: one sequence, as the reference's runner */
 } tts_hip_orpheus_desc;
 tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus_desc *desc);

@@ -5,6 +5,8 @@
 //                          the preceding down_proj into the residual stream, ggml_add :283)
 //   llama_rope_kv_kernel   ggml_rope_ext(NEOX, frequency factors) on q and k, K/V cache append :186-221,248-251
 //   attn_gqa_kernel        mul_mat(k, q) -> soft_max_ext(causal, 1/sqrt(d)) -> mul_mat(kq, v), kv head = q head / rep :228-259
+//   *_f16_kernel           the writers and readers of the cache over fp16 K/V (TTS_HIP_FLAG_KV_F16, extension): llama_rope_kv_f16_kernel,
+//                          attn_gqa_f16_kernel<HD, SPLIT>, attn_gqa_wave_f16_kernel; the fp32 kernels are untouched by the option
 //   silu_mul_kernel        silu(gate x) * (up x) :279
 //   argmax_parts/fold      sampler::max over the 156 940-logit vocabulary, two stages
 #pragma once
@@ -229,6 +231,90 @@ static __global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, co
                     if (q < n_parts) t += tp[q - 1];
                 for (int q = 8; q < n_parts; q++) t += vsrc[q * part_stride + i];
                 vdst[i] = t;
+            }
+        }
+    }
+}
+// llama_rope_kv_kernel appending to an fp16 cache (TTS_HIP_FLAG_KV_F16, Orpheus contexts): the same slab folds, theta chain and rotation in fp32; the rotated key
+// and the value are rounded once, to nearest-even, as they are stored (q stays fp32 in slab 0).  A kernel of its own, so that the fp32 kernel above — Dia's
+// too — is the code it was before the option.  seq_stride counts cache elements.
+static __global__ __launch_bounds__(64) void llama_rope_kv_f16_kernel(float *qkv, const uint32_t *pos, const float *ff, float theta_scale, int NH, int NKV, int HD,
+                                                               _Float16 *kcache, _Float16 *vcache, const uint32_t *row_seq, int64_t seq_stride, int n_parts = 1,
+                                                               int64_t part_stride = 0) {
+    const int r = blockIdx.x, h = blockIdx.y;
+    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
+    const int half = HD >> 1;
+    const int ld = (NH + 2 * NKV) * HD, kvH = NKV * HD;
+    float *row = qkv + (int64_t) r * ld;
+    float *v = row + (int64_t) h * HD;      // heads NH.. are the k heads (they follow q in the row)
+    const bool kw = h >= NH;
+    const float *vsrc = row + (int64_t) (NH + NKV) * HD + (int64_t) (h - NH) * HD;
+    auto slabs2 = [&](const float *b, int i, int j, float &a0, float &a1, float (&t0)[7], float (&t1)[7]) __attribute__((always_inline)) {
+        a0 = b[i]; a1 = b[j];
+#pragma unroll
+        for (int q = 1; q < 8; q++) {   // straight-line, as in llama_rope_kv_kernel
+            const int64_t qo = (int64_t) min(q, n_parts - 1) * part_stride;
+            t0[q - 1] = b[qo + i]; t1[q - 1] = b[qo + j];
+        }
+    };
+    auto fold2 = [&](const float *b, int i, int j, float &a0, float &a1, const float (&t0)[7], const float (&t1)[7]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 1; q < 8; q++)
+            if (q < n_parts) { a0 += t0[q - 1]; a1 += t1[q - 1]; }
+        for (int q = 8; q < n_parts; q++) { a0 += b[q * part_stride + i]; a1 += b[q * part_stride + j]; }
+    };
+    const uint32_t p = pos[r];   // first in the queue: the theta chain needs nothing else
+    const int i0 = min((int) threadIdx.x, half - 1);
+    const float ff0 = ff ? ff[i0] : 1.0f;
+    float fx0, fx1, ft0[7], ft1[7], vx0 = 0.0f, vx1 = 0.0f, vt0[7], vt1[7];
+    slabs2(v, i0, i0 + half, fx0, fx1, ft0, ft1);
+    const int vi0 = min((int) threadIdx.x, HD - 1), vi1 = min((int) threadIdx.x + 64, HD - 1);
+    if (kw) slabs2(vsrc, vi0, vi1, vx0, vx1, vt0, vt1);
+    __builtin_amdgcn_sched_barrier(0);
+    auto angle = [&](int i, float fi, float &cs, float &sn) __attribute__((always_inline)) {
+        float theta = (float) p;
+        for (int j = 0; j < i; j++) theta *= theta_scale;
+        const float ang = theta / fi;
+        cs = cosf(ang); sn = sinf(ang);
+    };
+    auto rotate = [&](int i, float x0, float x1, float cs, float sn) __attribute__((always_inline)) {
+        const float y0 = x0 * cs - x1 * sn, y1 = x0 * sn + x1 * cs;
+        if (h < NH) { v[i] = y0; v[i + half] = y1; }
+        else {
+            _Float16 *kc = kcache + (int64_t) p * kvH + (h - NH) * HD;
+            kc[i] = (_Float16) y0; kc[i + half] = (_Float16) y1;
+        }
+    };
+    {   // the wave's first pair: its loads are in flight while the angle is computed
+        float cs, sn;
+        angle(i0, ff0, cs, sn);
+        __builtin_amdgcn_sched_barrier(0);
+        fold2(v, i0, i0 + half, fx0, fx1, ft0, ft1);
+        if ((int) threadIdx.x < half) rotate(i0, fx0, fx1, cs, sn);
+    }
+    for (int i = threadIdx.x + 64; i < half; i += 64) {   // HD > 128: the later pairs
+        float cs, sn, x0, x1, t0[7], t1[7];
+        slabs2(v, i, i + half, x0, x1, t0, t1);
+        angle(i, ff ? ff[i] : 1.0f, cs, sn);
+        fold2(v, i, i + half, x0, x1, t0, t1);
+        rotate(i, x0, x1, cs, sn);
+    }
+    if (kw) {
+        _Float16 *vdst = vcache + (int64_t) p * kvH + (h - NH) * HD;
+        if (HD <= 128) {
+            fold2(vsrc, vi0, vi1, vx0, vx1, vt0, vt1);
+            if ((int) threadIdx.x < HD) vdst[threadIdx.x] = (_Float16) vx0;
+            if ((int) threadIdx.x + 64 < HD) vdst[threadIdx.x + 64] = (_Float16) vx1;
+        } else {
+            for (int i = threadIdx.x; i < HD; i += 64) {
+                float t = vsrc[i], tp[7];
+#pragma unroll
+                for (int q = 1; q < 8; q++) tp[q - 1] = vsrc[(int64_t) min(q, n_parts - 1) * part_stride + i];
+#pragma unroll
+                for (int q = 1; q < 8; q++)
+                    if (q < n_parts) t += tp[q - 1];
+                for (int q = 8; q < n_parts; q++) t += vsrc[q * part_stride + i];
+                vdst[i] = (_Float16) t;
             }
         }
     }
@@ -686,6 +772,233 @@ static __global__ __launch_bounds__(128) void attn_gqa_combine_kernel(const floa
     const float res = o / l;
     out[(int64_t) r * NH * 128 + h * 128 + t] = res;
     if (aq) q8_block_store(res, (int64_t) r * NH * 128 + h * 128 + t, aq, ad);   // the o projection's activation blocks
+}
+
+// ------------------------------------------------------------------------------------------------
+// The three readers over an fp16 cache (TTS_HIP_FLAG_KV_F16, Orpheus contexts).  A key row of one kv head is 256 contiguous bytes instead of 512.
+// Lane -> dims, key -> lane group and the order of every sum are those of the fp32 kernels above, applied to the rows widened to fp32 (exact): a lane's
+// two 4-dim pieces (scores: dims 4 sub .. + 3 and 64 + 4 sub .. + 3; P.V: dims 4 e4 .. + 3) are 8-byte loads, kept as fp16 while they are in flight — the
+// rows in flight take half the registers — and widened where they are consumed.  Query, scores, softmax and accumulators are fp32; the partials have
+// the fp32 kernels' meaning, attn_gqa_combine_kernel follows unchanged.
+// ------------------------------------------------------------------------------------------------
+typedef _Float16 half4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 widen4(half4v h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); }
+
+template <int HD>
+__device__ __forceinline__ void attn_v_batch_f16(half4v (&v)[8], const _Float16 *vbase, int kvH, int T, int j0, int tid) {
+    const int grp = tid >> 5, e4 = tid & 31;
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+        const int j = max(0, min(j0 + grp + 8 * u, T - 1));
+        v[u] = *(const half4v *) (vbase + (int64_t) j * kvH + e4 * 4);
+    }
+}
+struct KBatchF16 {   // the rows of a lane's 4 keys of a 64-key batch (its 2 x 8 bytes of each)
+    half4v a[4], b[4];
+};
+template <int HD>
+__device__ __forceinline__ void attn_k_request_f16(KBatchF16 &kb, const _Float16 *kbase, int kvH, int T, int j0, int tid) {
+    const int g = tid >> 4, sub = tid & 15;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int j = max(0, min(j0 + g + 16 * u, T - 1));
+        const half4v *kr = (const half4v *) (kbase + (int64_t) j * kvH);
+        kb.a[u] = kr[sub]; kb.b[u] = kr[16 + sub];
+    }
+}
+template <int HD>
+__device__ __forceinline__ void attn_scores_batched_f16(KBatchF16 &kpre, const _Float16 *kbase, int kvH, int T, const float *qs, float scale, float *ps, int tid) {
+    const int g = tid >> 4, sub = tid & 15;
+    const float4 q0 = *(const float4 *) (qs + sub * 4), q1 = *(const float4 *) (qs + 64 + sub * 4);
+    auto scores = [&](const KBatchF16 &kb, int j0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int j = j0 + g + 16 * u;
+            const float4 a = widen4(kb.a[u]), b = widen4(kb.b[u]);
+            float d = (a.x * q0.x + a.y * q0.y + a.z * q0.z + a.w * q0.w) + (b.x * q1.x + b.y * q1.y + b.z * q1.z + b.w * q1.w);
+            d = row16_sum(d);
+            if (sub == 0 && j < T) ps[j] = d * scale;
+        }
+    };
+    scores(kpre, 0);
+    for (int j0 = 64; j0 < T; j0 += 64) {
+        KBatchF16 kb;
+        attn_k_request_f16<HD>(kb, kbase, kvH, T, j0, tid);
+        scores(kb, j0);
+    }
+}
+template <int HD>
+__device__ __forceinline__ float4 attn_pv_batched_f16(half4v (&v)[8], const _Float16 *vbase, int kvH, int T, const float *ps, int tid) {   // v: the first batch, already requested
+    const int grp = tid >> 5;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int j0 = 0; j0 < T; j0 += 64) {
+        if (j0) attn_v_batch_f16<HD>(v, vbase, kvH, T, j0, tid);
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int j = j0 + grp + 8 * u;
+            if (j < T) {
+                const float p = ps[j];
+                const float4 w = widen4(v[u]);
+                acc.x += p * w.x; acc.y += p * w.y; acc.z += p * w.z; acc.w += p * w.w;
+            }
+        }
+    }
+    return acc;
+}
+
+// attn_gqa_kernel (SPLIT false: grid (head, row), dst = out [R][NH * HD], aq / ad as there) and attn_gqa_split_kernel (SPLIT true: grid (slice, row, head),
+// dst = the partials) over an fp16 cache: one body, the two differ in the keys a workgroup owns and in what it leaves.
+template <int HD, bool SPLIT>
+__global__ __launch_bounds__(256) void attn_gqa_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH, int NKV,
+                                                           float scale, float *dst, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq,
+                                                           int64_t seq_stride, QPre qp = QPre{}, int8_t *aq = nullptr, float *ad = nullptr) {
+    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
+    __shared__ float red[8];
+    __shared__ float4 accs[8][HD / 4];
+    float *qs = attn_gqa_sm, *ps = attn_gqa_sm + HD;   // [HD] q, then [T] scores -> probabilities
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.y, h = SPLIT ? blockIdx.z : blockIdx.x, z = SPLIT ? blockIdx.x : 0, nz = SPLIT ? gridDim.x : 1;
+    const int kb = kbeg ? (int) kbeg[r] : 0;
+    const int Tall = (kend ? (int) kend[r] : (int) pos[r] + 1) - kb;
+    const int chunk = (Tall + nz - 1) / nz;
+    const int k0 = kb + z * chunk;
+    const int T = SPLIT ? max(0, min(chunk, Tall - z * chunk)) : Tall;
+    float *pz = dst + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;   // SPLIT only
+    if (SPLIT && T <= 0) {
+        if (tid == 0) { pz[0] = -INFINITY; pz[1] = 0.0f; }
+        return;
+    }
+    const int kvH = NKV * HD, kh = h / (NH / NKV);
+    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
+    kcache += (int64_t) k0 * kvH + kh * HD;
+    vcache += (int64_t) k0 * kvH + kh * HD;
+    // requests in the order of their use, as in the fp32 kernels: the query, the K rows of the first 64 keys, the V rows of the first 64
+    QRaw qr;
+    attn_q_request<HD>(qr, qkv + (int64_t) r * ld + h * HD, r, qp, tid);
+    KBatchF16 kpre;
+    attn_k_request_f16<HD>(kpre, kcache, kvH, T, 0, tid);
+    half4v vfirst[8];
+    attn_v_batch_f16<HD>(vfirst, vcache, kvH, T, 0, tid);
+    __builtin_amdgcn_sched_barrier(0);
+    attn_q_finish<HD>(qs, qr, qkv + (int64_t) r * ld + h * HD, qp, tid);
+    attn_scores_batched_f16<HD>(kpre, kcache, kvH, T, qs, scale, ps, tid);
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int j = tid; j < T; j += 256) mx = fmaxf(mx, ps[j]);
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float sum = 0.0f;
+    for (int j = tid; j < T; j += 256) {
+        const float p = expf(ps[j] - mx);
+        ps[j] = p;
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) red[4 + wave] = sum;
+    __syncthreads();   // probabilities and the four partial sums are in LDS
+    const float total = (red[4] + red[5]) + (red[6] + red[7]);
+    accs[tid >> 5][tid & 31] = attn_pv_batched_f16<HD>(vfirst, vcache, kvH, T, ps, tid);
+    __syncthreads();
+    if (tid < HD) {
+        const float *a = (const float *) &accs[0][0];
+        float o = 0.0f;
+#pragma unroll
+        for (int g = 0; g < 8; g++) o += a[g * HD + tid];
+        if (SPLIT) pz[2 + tid] = o;
+        else {
+            const float res = o * (1.0f / total);
+            dst[(int64_t) r * NH * HD + h * HD + tid] = res;
+            if (aq) q8_block_store(res, (int64_t) r * NH * HD + h * HD + tid, aq, ad);
+        }
+    }
+    if (SPLIT && tid == 0) { pz[0] = mx; pz[1] = total; }
+}
+
+// attn_gqa_wave_kernel<HD, U> (the captured one-row step of Orpheus; its EXT form is Dia's and stays fp32) over an fp16 cache: the same keys per
+// (slice, wave, 16-lane group), the same running max / sum / output, the same merges.  K and V of a key share a 32-bit byte offset of 2 bytes per element.
+template <int HD, int U>
+__global__ __launch_bounds__(256) void attn_gqa_wave_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH, int NKV,
+                                                                float scale, float *part, int n_ctx) {
+    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
+    __shared__ float s_m[4], s_l[4];
+    __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
+    const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
+    const int kvH = NKV * HD, kh = h / (NH / NKV);
+    const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);
+    auto key_of = [&](int p) { return 16 * (nz * p + z) + gi; };
+    half4v ka[U], kb[U], va[U], vb[U];
+    auto request = [&](int p0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t off = ((uint32_t) min(key_of(p0 + u), n_ctx - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * 2u;
+            ka[u] = *(const half4v *) (kp + off); kb[u] = *(const half4v *) (kp + off + 128);
+            va[u] = *(const half4v *) (vp + off); vb[u] = *(const half4v *) (vp + off + 128);
+        }
+    };
+    // the small inputs first (vmcnt retires in issue order: the position and q are usable while the rows below are still in flight)
+    const float *qr = qkv + (int64_t) r * ld + h * HD + sub * 4;
+    const float4 q0 = *(const float4 *) qr, q1 = *(const float4 *) (qr + 64);
+    const int T = (int) pos[r] + 1;
+    __builtin_amdgcn_sched_barrier(0);
+    request(0);
+    __builtin_amdgcn_sched_barrier(0);
+    float m = -INFINITY, l = 0.0f;
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+    auto consume = [&](int u, int pass) __attribute__((always_inline)) {
+        if (key_of(pass) < T) {
+            const float4 k0 = widen4(ka[u]), k1 = widen4(kb[u]), v0 = widen4(va[u]), v1 = widen4(vb[u]);
+            float d = (k0.x * q0.x + k0.y * q0.y + k0.z * q0.z + k0.w * q0.w) + (k1.x * q1.x + k1.y * q1.y + k1.z * q1.z + k1.w * q1.w);
+            d = row16_sum(d) * scale;
+            const float mn = fmaxf(m, d);
+            const float f = expf(m - mn);   // 0 on the group's first key (m = -inf)
+            const float pr = expf(d - mn);
+            l = l * f + pr;
+            a0.x = a0.x * f + pr * v0.x; a0.y = a0.y * f + pr * v0.y; a0.z = a0.z * f + pr * v0.z; a0.w = a0.w * f + pr * v0.w;
+            a1.x = a1.x * f + pr * v1.x; a1.y = a1.y * f + pr * v1.y; a1.z = a1.z * f + pr * v1.z; a1.w = a1.w * f + pr * v1.w;
+            m = mn;
+        }
+    };
+    for (int p0 = 0; 16 * nz * p0 < T; p0 += U) {
+        if (p0) request(p0);
+#pragma unroll
+        for (int u = 0; u < U; u++) consume(u, p0 + u);
+    }
+    // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
+    auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
+                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
+    auto x32 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
+    float mw;
+    { float2 t = x16(m); mw = fmaxf(t.x, t.y); t = x32(mw); mw = fmaxf(t.x, t.y); }
+    const float fg = m == -INFINITY ? 0.0f : expf(m - mw);
+    float vals[9] = {l * fg, a0.x * fg, a0.y * fg, a0.z * fg, a0.w * fg, a1.x * fg, a1.y * fg, a1.z * fg, a1.w * fg};
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        float2 t = x16(vals[i]); float v = t.x + t.y;
+        t = x32(v); vals[i] = t.x + t.y;
+    }
+    if (g == 0) {
+        *(float4 *) (&s_acc[wave][sub * 4]) = make_float4(vals[1], vals[2], vals[3], vals[4]);
+        *(float4 *) (&s_acc[wave][64 + sub * 4]) = make_float4(vals[5], vals[6], vals[7], vals[8]);
+        if (sub == 0) { s_m[wave] = mw; s_l[wave] = vals[0]; }
+    }
+    __syncthreads();
+    if (tid < HD) {
+        const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+        float o = 0.0f, L = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const float f = s_m[w] == -INFINITY ? 0.0f : expf(s_m[w] - M);
+            o += f * s_acc[w][tid];
+            L += f * s_l[w];
+        }
+        float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
+        pz[2 + tid] = o;
+        if (tid == 0) { pz[0] = M; pz[1] = L; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1465,6 +1465,7 @@ extern "C" int tts_hip_kokoro_generate(tts_hip_ctx *c, const uint32_t *tokens, u
 // ------------------------------------------------------------------------------------------------
 extern "C" tts_hip_ctx *tts_hip_snac_create(int device, const tts_hip_snac_desc *sd) {
     if (!sd || sd->struct_size != sizeof(tts_hip_snac_desc)) { set_err("tts_hip_snac_create: bad desc (struct_size mismatch)"); return nullptr; }
+    if (refuse_kv_f16(sd->flags, "tts_hip_snac_create")) return nullptr;
     if (sd->n_blocks == 0 || sd->n_blocks > TTS_HIP_MAX_DAC_BLOCKS || sd->n_codebooks == 0 || sd->n_codebooks > 4) { set_err("tts_hip_snac_create: n_blocks / n_codebooks out of range"); return nullptr; }
     tts_hip_desc d{};
     d.struct_size = sizeof(d);

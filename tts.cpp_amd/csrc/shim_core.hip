@@ -110,6 +110,7 @@ extern "C" int tts_hip_device_count(void) {
 extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v);
 extern "C" tts_hip_ctx *tts_hip_create(int device, const tts_hip_desc *desc) {
     if (!desc || desc->struct_size != sizeof(tts_hip_desc)) { set_err("tts_hip_create: bad desc (struct_size mismatch)"); return nullptr; }
+    if (refuse_kv_f16(desc->flags, "tts_hip_create")) return nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_err("tts_hip_create: no HIP device available; this library has no CPU fallback"); return nullptr; }
     if (device < 0 || device >= n) { set_err("tts_hip_create: device %d out of range (%d devices)", device, n); return nullptr; }

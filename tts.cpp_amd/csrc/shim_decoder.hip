@@ -1015,12 +1015,12 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         while (F / c->l_ksplit > 4096 || (F % c->l_ksplit)) c->l_ksplit++;
         if ((F / c->l_ksplit) % 256) c->l_ksplit = 1;
         const size_t S = std::max<uint32_t>(1, c->lm.max_seqs);                 // cache slots of lock-step utterances; [slot][layer][position][kv width]
-        const size_t kvb = S * c->L * NCTX * c->l_kvH;
+        const size_t kvb = S * c->L * NCTX * c->l_kvH * (size_t) c->l_kv_esz;   // bytes: half of them under TTS_HIP_FLAG_KV_F16
         c->attn_part_cap = (size_t) 4 * c->NH * 16;   // up to 4 rows x heads x 16 splits (more rows take the unsplit kernel)
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
         CHK(dmalloc(&c->attn_cnt, (size_t) 256 + c->NH));   // arrival counters of the split attention's in-kernel merge (rows x heads <= 256)
-        CHK(dmalloc(&c->l_kc, kvb));   // ggml_backend_buffer_clear(buf, 0), orpheus/model.cpp:181
-        CHK(dmalloc(&c->l_vc, kvb));
+        CHK(dmalloc((char **) &c->l_kc, kvb));   // ggml_backend_buffer_clear(buf, 0), orpheus/model.cpp:181
+        CHK(dmalloc((char **) &c->l_vc, kvb));
         const int R = c->RMAX;
         CHK(dmalloc(&c->l_x, (size_t) R * H));
         CHK(dmalloc(&c->l_xn, (size_t) R * H));
@@ -2129,6 +2129,7 @@ extern "C" int tts_hip_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows,
 // ------------------------------------------------------------------------------------------------
 extern "C" tts_hip_ctx *tts_hip_t5_create(int device, const tts_hip_t5_desc *td) {
     if (!td || td->struct_size != sizeof(tts_hip_t5_desc)) { set_err("tts_hip_t5_create: bad desc (struct_size mismatch)"); return nullptr; }
+    if (refuse_kv_f16(td->flags, "tts_hip_t5_create")) return nullptr;
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = td->hidden_size; d.n_layers = td->n_layers; d.n_attn_heads = td->n_attn_heads; d.max_ctx_length = td->max_ctx_length;
@@ -2257,8 +2258,20 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         const int got = sscanf(w.c_str() + 4, "%d:%d", &layer, &slot);
         if (got < 1 || layer < 0 || layer >= c->L || slot < 0 || slot >= (int) std::max<uint32_t>(1, c->lm.max_seqs)) { set_err("debug_read(%s): bad layer/slot", what); return -1; }
         const size_t per = (size_t) c->lm.n_ctx * c->l_kvH, n = std::min(max_floats, per);   // the cache is [slot][layer][position][kv width]
-        if (hipMemcpy(out, (w[2] == 'k' ? c->l_kc : c->l_vc) + ((size_t) slot * c->L + layer) * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        const char *src = (const char *) (w[2] == 'k' ? c->l_kc : c->l_vc) + ((size_t) slot * c->L + layer) * per * (size_t) c->l_kv_esz;
+        if (c->l_kv_esz == 2) {   // the fp16 cache: the rows widened to fp32 (exact)
+            std::vector<_Float16> h(n);
+            if (hipMemcpy(h.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = (float) h[i];
+            return (int64_t) n;
+        }
+        if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
+    }
+    if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, or 2 under TTS_HIP_FLAG_KV_F16
+        if (max_floats < 1) { set_err("debug_read(l_kv_elem): buffer too small"); return -1; }
+        out[0] = (float) c->l_kv_esz;
+        return 1;
     }
     if (c->has_llama && (w == "l_q" || w == "l_att")) {   // the last layer's attention of the last forward: the rotated queries it read / the rows it left, [rows][NH * head_dim]
         const size_t A = (size_t) c->NH * c->lm.head_dim, QKV = A + 2 * (size_t) c->l_kvH, rows = std::min(max_floats / A, (size_t) c->RMAX);

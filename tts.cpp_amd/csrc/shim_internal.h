@@ -22,6 +22,12 @@
 #define LLAMA_GREEDY_CHUNK 8
 
 int set_err(const char *fmt, ...);   // shim_core.hip: thread-local message behind tts_hip_last_error()
+// TTS_HIP_FLAG_KV_F16 is tts_hip_orpheus_create's alone: every other create call refuses it by name (true: refused, the message is set)
+static inline bool refuse_kv_f16(uint32_t flags, const char *call) {
+    if (!(flags & TTS_HIP_FLAG_KV_F16)) return false;
+    set_err("%s: TTS_HIP_FLAG_KV_F16 is not accepted here: it selects the fp16 K/V cache of tts_hip_orpheus_create (Parler's is tts_hip_desc::kv_type)", call);
+    return true;
+}
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
@@ -170,7 +176,8 @@ struct tts_hip_ctx {
     W l_head;
     int l_V = 0, l_Vpad = 0, l_kvH = 0, l_ksplit = 1;
     float *l_x = nullptr, *l_xn = nullptr, *l_qkv = nullptr, *l_att = nullptr, *l_gu = nullptr, *l_g = nullptr, *l_logits = nullptr, *l_parts = nullptr;
-    float *l_kc = nullptr, *l_vc = nullptr;
+    void *l_kc = nullptr, *l_vc = nullptr;   // [slot][layer][position][kv width] of l_kv_esz bytes per element
+    int l_kv_esz = 4;                        // 2 under TTS_HIP_FLAG_KV_F16 (fixed at create: the captured graphs never see it change)
     uint32_t *l_ids = nullptr, *l_pos = nullptr, *l_tok = nullptr;
     uint32_t *l_seq = nullptr, *l_btok = nullptr, *l_bpi = nullptr;   // lock-step utterances: row -> cache slot, selected tokens [rows], arg-max partials
     float *l_bpv = nullptr;

@@ -22,6 +22,7 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
     if (!c) return nullptr;
     c->has_llama = true;
     c->lm = *ld;
+    if (ld->flags & TTS_HIP_FLAG_KV_F16) c->l_kv_esz = 2;
     if (c->lm.max_seqs == 0) c->lm.max_seqs = 1;
     if (c->lm.max_seqs > 64) { set_err("tts_hip_orpheus_create: max_seqs %u > 64", c->lm.max_seqs); tts_hip_destroy(c); return nullptr; }
     // measured on MI355X at the orpheus-3b Q4_0 shapes (profiles/r02/first_call_orpheus_*.log): 3.84 ms/step through the
@@ -41,7 +42,9 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
 // plus a combine launch (attn_gqa_split_kernel).  max_keys bounds the LDS score buffer.
 static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const float *kc, const float *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
-                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0) {
+                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0, int kv_esz = 4) {
+    // kv_esz 2: kc / vc are an Orpheus context's fp16 cache (TTS_HIP_FLAG_KV_F16) and the fp16 forms of the three kernels read it; seq_stride stays in elements
+    const _Float16 *kc16 = (const _Float16 *) kc, *vc16 = (const _Float16 *) vc;
     int nz = 1;
     if (deferred) *deferred = 0;
     if (c->attn_split_max > 1 && NHq * rows <= 256) {
@@ -50,15 +53,27 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         while (nz > 1 && (size_t) rows * NHq * nz > c->attn_part_cap) nz--;
     }
     if (nz <= 1) {
-        hipLaunchKernelGGL(attn_gqa_kernel<128>, dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
-                           row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
+        if (kv_esz == 2) {
+            hipLaunchKernelGGL((attn_gqa_f16_kernel<128, false>), dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, out, kbeg, kend,
+                               row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
+        } else {
+            hipLaunchKernelGGL(attn_gqa_kernel<128>, dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
+                               row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
+        }
         HIPCHK(hipGetLastError());
         if (q_out) c->aq_src = out;
         return 0;
     }
     const int chunk = (max_keys + nz - 1) / nz;
-    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * 4 < (1ull << 32);   // attn_gqa_wave_kernel addresses a sequence's rows with 32-bit byte offsets
-    if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
+    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * (uint64_t) kv_esz < (1ull << 32);   // attn_gqa_wave_kernel addresses a sequence's rows with 32-bit byte offsets
+    if (kv_esz == 2) {
+        if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
+            hipLaunchKernelGGL((attn_gqa_wave_f16_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part, n_ctx_keys);
+        } else {
+            hipLaunchKernelGGL((attn_gqa_f16_kernel<128, true>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part,
+                               kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
+        }
+    } else if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
         // the captured one-row step (Orpheus): every key row requested at kernel start, online softmax per 16-lane group, one barrier (attn_gqa_wave_kernel)
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
     } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
@@ -159,7 +174,11 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     };
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->l_layers[l];
-        float *kc = c->l_kc + (size_t) l * NCTX * c->l_kvH, *vc = c->l_vc + (size_t) l * NCTX * c->l_kvH;
+        // this layer of slot 0; under TTS_HIP_FLAG_KV_F16 the same rows as fp16 (kc16 / vc16) and the fp16 forms of the writers and readers
+        const bool kv16 = c->l_kv_esz == 2;
+        const size_t layer_off = (size_t) l * NCTX * c->l_kvH * (size_t) c->l_kv_esz;
+        float *kc = (float *) ((char *) c->l_kc + layer_off), *vc = (float *) ((char *) c->l_vc + layer_off);
+        _Float16 *kc16 = (_Float16 *) kc, *vc16 = (_Float16 *) vc;
         const size_t qkv_lds = (size_t) n * H + (size_t) n * (H / 32) * 4;
         const bool qkv_fused = !row_seq && n <= 4 && c->q4_rope && c->q4_lds && y.qkv.q4 && q_for(y.qkv, n, QS_QKV) && HD == 128 && H % 512 == 0 && qkv_lds <= 64 * 1024 && !c->prof;
         // the rms norm inside the consuming projection's staging (stage_rms_q8): no slabs may be pending, the row is held in registers
@@ -169,8 +188,10 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
             qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
             qa.wd = (const _Float16 *) (c->arena + y.qkv.soff);
             RopeEpi re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
+            RopeEpiF16 re16{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc16, vc16};
             RmsSrc rs{c->l_x, f32(y.in_norm), 1e-5f};
-            hipLaunchKernelGGL((gemv_q4_qkv_rope_kernel<4, 2>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re, rs);
+            if (kv16) hipLaunchKernelGGL((gemv_q4_qkv_rope_f16_kernel<4, 2>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re16, rs);
+            else hipLaunchKernelGGL((gemv_q4_qkv_rope_kernel<4, 2>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re, rs);
             HIPCHK(hipGetLastError());
             c->aq_src = nullptr;
         } else if (qkv_fused) {
@@ -180,7 +201,9 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
             qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
             qa.wd = (const _Float16 *) (c->arena + y.qkv.soff); qa.aq = c->aq; qa.ad = c->ad;
             RopeEpi re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
-            hipLaunchKernelGGL(gemv_q4_qkv_rope_kernel<4>, dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re);
+            RopeEpiF16 re16{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc16, vc16};
+            if (kv16) hipLaunchKernelGGL(gemv_q4_qkv_rope_f16_kernel<4>, dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re16, RmsSrc{});
+            else hipLaunchKernelGGL(gemv_q4_qkv_rope_kernel<4>, dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re);
             HIPCHK(hipGetLastError());
             c->aq_src = nullptr;
         } else {
@@ -188,13 +211,21 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
             const int sl = qstream(y.qkv, QS_QKV, c->l_xn, H, c->l_qkv, QKV, (int64_t) srows * QKV, smax);   // slabs of srows rows inside l_qkv ([RMAX][QKV])
             if (sl < 0) return -1;
             if (!sl) CHK(llama_gemm(c, y.qkv, c->l_xn, H, c->l_qkv, QKV, n, EPI_STORE));
-            hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc, vc,
-                               row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
+            if (kv16)
+                hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc16, vc16,
+                                   row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
+            else
+                hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc, vc,
+                                   row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
             HIPCHK(hipGetLastError());
         }
-        CHK(launch_attn_gqa(c, NH, n, (int) (attn_positions ? (uint32_t) attn_positions : pos0 + n), (const float *) c->l_qkv, QKV, (const uint32_t *) c->l_pos,
+        // tts_hip_profile: the attention launches of the step as TTS_HIP_K_ATTN_SELF (bytes: K and V rows up to the bound on the rows' keys)
+        const int max_keys = (int) (attn_positions ? (uint32_t) attn_positions : pos0 + n);
+        CHK(prof_begin(c, TTS_HIP_K_ATTN_SELF, 2.0 * n * max_keys * c->l_kvH * c->l_kv_esz, 0.0));
+        CHK(launch_attn_gqa(c, NH, n, max_keys, (const float *) c->l_qkv, QKV, (const uint32_t *) c->l_pos,
                             (const float *) kc, (const float *) vc, NKV, 1.0f / sqrtf((float) HD), c->l_att, nullptr, nullptr, row_seq, row_seq ? seq_stride : (int64_t) 0,
-                            attn_positions != 0 && !row_seq, q_for(y.o, n, QS_O), QPre{}, nullptr, NCTX));
+                            attn_positions != 0 && !row_seq, q_for(y.o, n, QS_O), QPre{}, nullptr, NCTX, c->l_kv_esz));
+        CHK(prof_end(c));
         {
             const int sl = qstream(y.o, QS_O, c->l_att, NH * HD, c->l_parts, H, (int64_t) srows * H, pmax);   // slabs of srows rows inside l_parts ([8][RMAX][H]), folded into the residual stream by the next rms norm
             if (sl < 0) return -1;
@@ -1061,6 +1092,7 @@ extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t
 
 extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *dd) {
     if (!dd || dd->struct_size != sizeof(tts_hip_dia_desc)) { set_err("tts_hip_dia_create: bad desc (struct_size mismatch)"); return nullptr; }
+    if (refuse_kv_f16(dd->flags, "tts_hip_dia_create")) return nullptr;
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = dd->dec_hidden_size; d.n_layers = dd->dec_layers; d.n_attn_heads = dd->dec_attn_heads; d.max_ctx_length = dd->max_gen;

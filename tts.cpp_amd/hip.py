@@ -14,6 +14,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 MAX_DAC_BLOCKS = 8
 
 FLAG_NO_GRAPH, FLAG_VALU_GEMM, FLAG_NO_DAC, FLAG_NO_PARLER, FLAG_DEQUANT_Q, FLAG_DAC_F32 = 1, 2, 4, 8, 16, 32
+FLAG_KV_F16 = 64   # OrpheusEngine(flags=...) only: fp16 K/V cache (TTS_HIP_FLAG_KV_F16); every other engine refuses it
 KCLASSES = ["embed", "ln", "gemm_qkv", "attn_self", "gemm_attn_out", "gemm_cross_q", "attn_cross", "gemm_cross_out", "gemm_fc1",
             "gemm_fc2", "gemm_heads", "sample", "gemm_other", "dac_embed", "dac_conv7", "dac_conv1", "dac_convt", "dac_final", "dac_resunit", "kokoro_conv_mfma"]
 
@@ -784,7 +785,8 @@ class OrpheusEngine:
         self._chk(self.L.tts_hip_set_debug(self.ctx, 1 if on else 0))
 
     def debug_read(self, what, max_floats):
-        """'l_logits': the logits row the last step left; 'l_k:<layer>[:<slot>]' / 'l_v:...': a cache slot's rows of a layer; last layer of the last
+        """'l_logits': the logits row the last step left; 'l_k:<layer>[:<slot>]' / 'l_v:...': a cache slot's rows of a layer (an fp16 cache widened
+        exactly); 'l_kv_elem': the cache element size in bytes (4, or 2 under FLAG_KV_F16); last layer of the last
         forward: 'l_q' the rotated queries the attention read and 'l_att' the rows it left ([rows][heads * 128], rows = max_floats // width), 'l_pos'
         the rows' positions (after a captured step: already moved on by one) (test / debugging aid)"""
         out = np.empty(max_floats, dtype=np.float32)
@@ -803,6 +805,12 @@ class OrpheusEngine:
             raw = np.frombuffer(bytes(t.raw()), dtype=np.uint8)
             self._chk(self.L.tts_hip_upload(self.ctx, t.name.encode(), t.type, len(t.ne), ne, raw.ctypes.data_as(C.c_void_p)))
         self._chk(self.L.tts_hip_finalize(self.ctx, None))
+
+    def profile(self, enable):
+        """tts_hip_profile: True: every launch timed, the steps run eagerly and unfused; the attention launches count as 'attn_self'"""
+        self._chk(self.L.tts_hip_profile(self.ctx, int(enable)))
+
+    profile_get = HipEngine.profile_get
 
     def decode(self, ids, pos0):
         """-> (logits [vocab] of the last token, its arg-max)"""

@@ -79,6 +79,7 @@ orpheus_runner::orpheus_runner(const orpheus_hparams & hp_, bpe_tokenizer * tok,
     d.n_ctx = hp.max_context_length + hp.max_generation_size;   // orpheus_kv_cache_init, model.cpp:176-177
     max_seqs = std::min<uint32_t>(std::max<uint32_t>(1, tts_load_max_seqs()), 64);
     d.max_seqs = max_seqs;
+    if (getenv("TTS_HIP_KV_F16")) d.flags |= TTS_HIP_FLAG_KV_F16;   // the switch Parler's runner reads: fp16 K/V cache (extension, include/tts_hip.h)
     lm = tts_hip_orpheus_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_orpheus_create failed: %s\n", tts_hip_last_error());
     tts_hip_snac_desc s{};
@@ -139,6 +140,11 @@ std::vector<std::vector<uint32_t>> orpheus_runner::prepare_output_tokens(const s
         for (size_t ii = 0; ii < 7; ii++)
             levels[hp.heads[ii]].push_back(out[i * 7 + ii] - hp.audio_token_offset - (uint32_t) (ii % 7) * hp.audio_token_stride);
     return levels;
+}
+
+uint32_t orpheus_runner::kv_element_bytes() const {
+    float v = 0.0f;
+    return tts_hip_debug_read(lm, "l_kv_elem", &v, 1) == 1 ? (uint32_t) v : 0;
 }
 
 // what tts_hip_orpheus_generate_sampled's device sampler takes (top_k 1..64, any top_p > 0); TTS_HOST_LOOP forces the host sampler

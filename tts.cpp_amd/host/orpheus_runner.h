@@ -50,6 +50,7 @@ struct orpheus_runner final : tts_generation_runner {
     // extension: lock-step utterances (tts_hip_orpheus_generate_batch): every utterance's audio is that of a generate() call of its own, made in order
     void     generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs, const generation_configuration & config) override;
     uint32_t batch_capacity() const override { return max_seqs; }
+    uint32_t kv_element_bytes() const override;
     // extension: chunked audio.  chunk_frames counts SNAC frames (7 ids, 4 * snac_up samples).  The decoder runs in pieces
     // (tts_hip_orpheus_gen_*); a chunk [f0, f1) is decoded once frames up to f1 + snac_halo exist or the utterance has ended, as the window
     // [f0 - halo, f1 + halo) on the codec's stream (tts_hip_snac_decode_windows_begin / _end) while the next piece of steps runs (one sequence;
