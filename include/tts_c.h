@@ -104,8 +104,8 @@ void          tts_c_set_load_options(int device, int max_seqs, int declare_only)
 void          tts_c_set_load_options_ex(int device, int max_seqs, int declare_only, tts_c_runner *share_with);
 /* the runner's tts_hip_ctx* (include/tts_hip.h: arena, profiling), or NULL when the architecture keeps several contexts */
 void         *tts_c_runner_device_context(tts_c_runner *r);
-/* bytes per element of the decoder's K/V cache as the device context reports them (Orpheus: 4, or 2 when TTS_HIP_KV_F16 was in the
- * environment at load, TTS_HIP_FLAG_KV_F16); 0 when the architecture does not report it */
+/* bytes per element of the decoder's K/V cache as the device context reports them (Orpheus and Dia: 4, or 2 when TTS_HIP_KV_F16 was in the
+ * environment at load, TTS_HIP_FLAG_KV_F16 / tts_hip_dia_desc::kv_type); 0 when the architecture does not report it */
 uint32_t      tts_c_runner_kv_element_bytes(tts_c_runner *r);
 /* the loaded runner's own tokenizer (Parler: unigram ids + EOS as batch_from_sentence builds them); returns the id count */
 int           tts_c_runner_tokenize(tts_c_runner *r, const char *text, uint32_t *out, int cap);

@@ -89,7 +89,8 @@ typedef struct tts_hip_desc {
                                        P.V sums run on the cache rows widened exactly.  Fixed at create for every path of the
                                        context (decode, the captured step, step_batch / generate_batch, gen_*, stream_*).
                                        tts_hip_create, tts_hip_t5_create, tts_hip_snac_create and tts_hip_dia_create refuse it
-                                       with an error that names the flag and the call. */
+                                       with an error that names the flag and the call; a Dia context selects its fp16 caches
+                                       through tts_hip_dia_desc::kv_type. */
 
 typedef struct tts_hip_ctx tts_hip_ctx;
 
@@ -378,9 +379,23 @@ typedef struct tts_hip_dia_desc {
     uint32_t max_ctx;           /* dia.encoder.max_context_length (1024): the encoder always runs all of it */
     uint32_t max_gen;           /* dia.decoder.max_generation_size (3072) self-attention cache positions  */
     float    cfg_scale;         /* dia.cfg_scale (3.0, model.h:82); 0 = that                             */
-    uint32_t flags;             /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q */
+    uint32_t flags;             /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_NO_GRAPH (the device loop's steps run
+                                   eagerly instead of as replays of one captured graph; the same launches once max_gen reaches
+                                   128 x the self-attention's key splits, 1024 by default) */
     uint32_t max_utterances;    /* extension: utterances decoded in lock-step (each is the reference's batch of 2 guidance streams,
                                    dia/model.cpp:330-341); 0 = 1.  Rows of a step = 2 x utterances */
+    uint32_t kv_type;           /* extension (the reference keeps fp32 K/V, dia/model.cpp:329): TTS_HIP_F32 (0, so a zeroed desc) or
+                                   TTS_HIP_F16: the self cache [layer][row slot][max_gen][kv width] and the cross cache
+                                   [layer][row slot][max_ctx][heads * head_dim] are kept in fp16 — half the cache memory
+                                   (Dia-1.6B: 1.06 GB -> 0.53 GB per utterance slot) and half the bytes both attention launches of a
+                                   step read.  Rotated K and V are rounded once, to nearest-even, as they are stored (a plain
+                                   fp32 -> fp16 conversion, as under TTS_HIP_FLAG_KV_F16): a magnitude above 65504 becomes inf, one
+                                   below 6.1e-5 keeps fewer bits (fp16 subnormals).  All arithmetic stays fp32: query, scores,
+                                   softmax and the P.V sums run on the cache rows widened exactly; the encoder's own K/V
+                                   scratch stays fp32.  Fixed at create for every call of the context: tts_hip_dia_encode /
+                                   _encode_slot (cross K/V), tts_hip_dia_step / _step_batch, tts_hip_dia_generate, gen_* and
+                                   stream_* (self K/V appended, both caches read).  Any other value is refused with an error that
+                                   names tts_hip_dia_create and kv_type. */
 } tts_hip_dia_desc;
 tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *desc);
 /* tokens [max_ctx]: the sentence bytes then zeros; the all-zero second stream is added here (:700-703).  Fills the cross
@@ -632,7 +647,8 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
  * consumed and produced: "di_attn:<layer>:<self|cross>:q" (self: the rotated rows [R][ld]; cross: the raw query slabs, n_parts of them
  * part_stride floats apart, which the kernel sums in slab order and rotates at the row's position), ":out" ([R][heads * head_dim]) and
  * ":meta" (n_parts, part_stride, ld, R, then pos[R], kend[R], row_seq[R]).  "di_k:<layer>:<row slot>" / "di_v:..." are a row slot's
- * self-attention cache [max_gen][kv width], "di_ck:..." / "di_cv:..." its cross K / V [max_ctx][heads * head_dim].  With debug off every
+ * self-attention cache [max_gen][kv width], "di_ck:..." / "di_cv:..." its cross K / V [max_ctx][heads * head_dim] (fp16 caches, kv_type =
+ * TTS_HIP_F16: the rows widened exactly); "di_kv_elem" is the caches' element size in bytes (4 or 2).  With debug off every
  * forward launches exactly what it launches without these items; nothing is kept during a graph capture.
  * Returns number of floats written or <0. */
 int64_t tts_hip_debug_read(tts_hip_ctx *ctx, const char *what, float *out, size_t max_floats);

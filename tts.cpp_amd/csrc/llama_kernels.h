@@ -6,7 +6,8 @@
 //   llama_rope_kv_kernel   ggml_rope_ext(NEOX, frequency factors) on q and k, K/V cache append :186-221,248-251
 //   attn_gqa_kernel        mul_mat(k, q) -> soft_max_ext(causal, 1/sqrt(d)) -> mul_mat(kq, v), kv head = q head / rep :228-259
 //   *_f16_kernel           the writers and readers of the cache over fp16 K/V (TTS_HIP_FLAG_KV_F16, extension): llama_rope_kv_f16_kernel,
-//                          attn_gqa_f16_kernel<HD, SPLIT>, attn_gqa_wave_f16_kernel; the fp32 kernels are untouched by the option
+//                          attn_gqa_f16_kernel<HD, SPLIT>, attn_gqa_wave_f16_kernel, and for Dia's fp16 caches (tts_hip_dia_desc::kv_type)
+//                          attn_gqa_wave_ext_f16_kernel; the fp32 kernels are untouched by the option
 //   silu_mul_kernel        silu(gate x) * (up x) :279
 //   argmax_parts/fold      sampler::max over the 156 940-logit vocabulary, two stages
 #pragma once
@@ -916,7 +917,7 @@ __global__ __launch_bounds__(256) void attn_gqa_f16_kernel(const float *qkv, int
     if (SPLIT && tid == 0) { pz[0] = mx; pz[1] = total; }
 }
 
-// attn_gqa_wave_kernel<HD, U> (the captured one-row step of Orpheus; its EXT form is Dia's and stays fp32) over an fp16 cache: the same keys per
+// attn_gqa_wave_kernel<HD, U> (the captured one-row step of Orpheus; its EXT form, Dia's, has attn_gqa_wave_ext_f16_kernel below) over an fp16 cache: the same keys per
 // (slice, wave, 16-lane group), the same running max / sum / output, the same merges.  K and V of a key share a 32-bit byte offset of 2 bytes per element.
 template <int HD, int U>
 __global__ __launch_bounds__(256) void attn_gqa_wave_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH, int NKV,
@@ -965,6 +966,144 @@ __global__ __launch_bounds__(256) void attn_gqa_wave_f16_kernel(const float *qkv
         if (p0) request(p0);
 #pragma unroll
         for (int u = 0; u < U; u++) consume(u, p0 + u);
+    }
+    // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
+    auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
+                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
+    auto x32 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
+    float mw;
+    { float2 t = x16(m); mw = fmaxf(t.x, t.y); t = x32(mw); mw = fmaxf(t.x, t.y); }
+    const float fg = m == -INFINITY ? 0.0f : expf(m - mw);
+    float vals[9] = {l * fg, a0.x * fg, a0.y * fg, a0.z * fg, a0.w * fg, a1.x * fg, a1.y * fg, a1.z * fg, a1.w * fg};
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        float2 t = x16(vals[i]); float v = t.x + t.y;
+        t = x32(v); vals[i] = t.x + t.y;
+    }
+    if (g == 0) {
+        *(float4 *) (&s_acc[wave][sub * 4]) = make_float4(vals[1], vals[2], vals[3], vals[4]);
+        *(float4 *) (&s_acc[wave][64 + sub * 4]) = make_float4(vals[5], vals[6], vals[7], vals[8]);
+        if (sub == 0) { s_m[wave] = mw; s_l[wave] = vals[0]; }
+    }
+    __syncthreads();
+    if (tid < HD) {
+        const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+        float o = 0.0f, L = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const float f = s_m[w] == -INFINITY ? 0.0f : expf(s_m[w] - M);
+            o += f * s_acc[w][tid];
+            L += f * s_l[w];
+        }
+        float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
+        pz[2 + tid] = o;
+        if (tid == 0) { pz[0] = M; pz[1] = L; }
+    }
+}
+
+// attn_gqa_wave_kernel<HD, U, true> (Dia's cross-attention, the EXT form above) over an fp16 cache (tts_hip_dia_desc::kv_type = TTS_HIP_F16): the same
+// key -> (slice, wave, 16-lane group, pass), requests clamped at kend[r] (a parked row asks for its one key only), row_seq and the sequence stride, the query
+// folded from its QPre slabs through LDS and rotated in the lanes, non-temporal loads, the same running max / sum / output and the same merges.  A lane's
+// two 4-dim pieces of a row are 8-byte loads kept as fp16 while in flight and widened where they are consumed, so the dot product and every fold associate
+// as in the fp32 kernel: the results differ from it only through the rounding of the stored rows.  A pass costs 8 registers instead of 16.  Measured on
+// the Dia-1.6B step at 8 rows (profiles/dia_kv_f16_u.json; fp32 cache 1.735 / 2.086 ms at positions 100 / 2000): U = 4 slots (98 registers, four
+// workgroups per CU, under the fp32 form's 112) 1.596 / 1.858 ms, all eight passes requested at once (U = 8: 132 registers, three workgroups per CU)
+// 1.648 / 1.919 — so the host launches <128, 4> and holds no other instantiation.  U only moves requests, never a sum: the result bits do not depend on it.
+template <int HD, int U>
+__global__ __launch_bounds__(256) void attn_gqa_wave_ext_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH,
+                                                                    int NKV, float scale, float *part, int n_ctx, const uint32_t *kend, const uint32_t *row_seq,
+                                                                    int64_t seq_stride, QPre qp) {
+    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
+    static_assert(U >= 1 && U <= 8, "eight passes through U register slots");
+    __shared__ float s_m[4], s_l[4];
+    __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
+    __shared__ __attribute__((aligned(16))) float s_q[HD];
+    const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
+    const int kvH = NKV * HD, kh = h / (NH / NKV);
+    const int lim = kend ? max(1, min((int) kend[r], n_ctx)) : n_ctx;
+    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
+    // wave-uniform bases + one 32-bit byte offset per row (2 bytes per element): K and V of a key share the offset register
+    const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);
+    auto key_of = [&](int p) { return 16 * (nz * p + z) + gi; };
+    half4v ka[U], kb[U], va[U], vb[U];
+    auto request_one = [&](int u, int pass) __attribute__((always_inline)) {
+        const uint32_t off = ((uint32_t) min(key_of(pass), lim - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * 2u;
+        auto ntl = [](const char *a) __attribute__((always_inline)) { return __builtin_nontemporal_load((const half4v *) a); };   // met once per step, as in the fp32 form
+        ka[u] = ntl(kp + off); kb[u] = ntl(kp + off + 128);
+        va[u] = ntl(vp + off); vb[u] = ntl(vp + off + 128);
+    };
+    // the small inputs first (vmcnt retires in issue order): threads 0-127 hold slabs 0-3 of query element tid, threads 128-255 slabs 4-7 of element tid - 128
+    float tq[4];
+    uint32_t rp = 0;
+    {
+        const float *qe = qkv + (int64_t) r * ld + h * HD + (tid & (HD - 1));
+#pragma unroll
+        for (int p = 0; p < 4; p++) tq[p] = qe[(int64_t) min((tid >> 7) * 4 + p, qp.n_parts - 1) * qp.part_stride];
+        if (qp.rope_pos) rp = qp.rope_pos[r];
+    }
+    const int T = kend ? (int) kend[r] : (int) pos[r] + 1;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; u++) request_one(u, u);
+    __builtin_amdgcn_sched_barrier(0);
+    // attn_q_finish's arithmetic, as in the fp32 form: slabs in slab order (the upper half of the workgroup continues the lower half's sum), then ggml_rope
+    // NEOX with the iterated theta (pair i, i + 64: both in this lane)
+    if (tid < HD) {
+        float x = tq[0];
+#pragma unroll
+        for (int p = 1; p < 4; p++)
+            if (p < qp.n_parts) x += tq[p];
+        s_q[tid] = x;
+    }
+    __syncthreads();
+    if (tid >= HD) {
+        float x = s_q[tid - HD];
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            if (4 + p < qp.n_parts) x += tq[p];   // (the host sends at most 8 slabs here)
+        s_q[tid - HD] = x;
+    }
+    __syncthreads();
+    float4 q0 = *(const float4 *) (s_q + sub * 4), q1 = *(const float4 *) (s_q + 64 + sub * 4);
+    if (qp.rope_pos) {
+        float theta = (float) rp;
+        for (int j = 0; j < sub * 4; j++) theta *= qp.theta_scale;
+        float *a = (float *) &q0, *b = (float *) &q1;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float cs = cosf(theta), sn = sinf(theta);
+            const float x0 = a[e], x1 = b[e];
+            a[e] = x0 * cs - x1 * sn; b[e] = x0 * sn + x1 * cs;
+            theta *= qp.theta_scale;
+        }
+    }
+    float m = -INFINITY, l = 0.0f;
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+    auto consume = [&](int u, int pass) __attribute__((always_inline)) {
+        if (key_of(pass) < T) {
+            const float4 k0 = widen4(ka[u]), k1 = widen4(kb[u]), v0 = widen4(va[u]), v1 = widen4(vb[u]);
+            float d = (k0.x * q0.x + k0.y * q0.y + k0.z * q0.z + k0.w * q0.w) + (k1.x * q1.x + k1.y * q1.y + k1.z * q1.z + k1.w * q1.w);
+            d = row16_sum(d) * scale;
+            const float mn = fmaxf(m, d);
+            const float f = expf(m - mn);   // 0 on the group's first key (m = -inf)
+            const float pr = expf(d - mn);
+            l = l * f + pr;
+            a0.x = a0.x * f + pr * v0.x; a0.y = a0.y * f + pr * v0.y; a0.z = a0.z * f + pr * v0.z; a0.w = a0.w * f + pr * v0.w;
+            a1.x = a1.x * f + pr * v1.x; a1.y = a1.y * f + pr * v1.y; a1.z = a1.z * f + pr * v1.z; a1.w = a1.w * f + pr * v1.w;
+            m = mn;
+        }
+    };
+    // eight passes (the host checks: at most 16 nz 8 keys) through U register slots: a slot is requested again for pass p + U once pass p has been consumed
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        consume(p % U, p);
+        if (p + U < 8) {
+            __builtin_amdgcn_sched_barrier(0);   // the slot's registers are free only now
+            request_one(p % U, p + U);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
     auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);

@@ -259,9 +259,10 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     free_dev(c->l_kc); free_dev(c->l_vc); free_dev(c->l_ids); free_dev(c->l_pos); free_dev(c->l_tok);
     free_dev(c->l_seq); free_dev(c->l_btok); free_dev(c->l_bpi); free_dev(c->l_bpv);
     for (void *p : c->q4_bufs) free_dev(p);
-    for (float *p : {c->di_ex, c->di_exn, c->di_eqkv, c->di_eatt, c->di_egu, c->di_eg, c->di_ek, c->di_ev, c->di_ckv, c->di_ck, c->di_cv, c->di_k, c->di_v, c->di_x,
+    for (float *p : {c->di_ex, c->di_exn, c->di_eqkv, c->di_eatt, c->di_egu, c->di_eg, c->di_ek, c->di_ev, c->di_ckv, c->di_x,
                      c->di_xn, c->di_qkv, c->di_q, c->di_att, c->di_gu, c->di_g, c->di_parts, c->di_logits, c->di_guided})
         free_dev(p);
+    free_dev(c->di_ck); free_dev(c->di_cv); free_dev(c->di_k); free_dev(c->di_v);   // fp32 or fp16 (di_kv_esz)
     for (uint32_t *p : {c->di_tok, c->di_epos, c->di_eseq, c->di_kbeg, c->di_kend, c->di_ids, c->di_pos, c->di_seq, c->di_cend, c->di_stok, c->di_loop, c->di_hist, c->di_look, c->di_sbud, c->di_sadm}) free_dev(p);
     free_dev(c->di_suni);
     free_dev(c->di_srec); free_dev(c->di_srec_in); free_dev(c->di_spen); free_dev(c->di_spen_in);

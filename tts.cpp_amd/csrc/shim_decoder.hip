@@ -1061,10 +1061,11 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         c->di_slot_encoded.assign((size_t) U, 0);
         c->attn_part_cap = (size_t) R * c->NH * 16;
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
-        CHK(dmalloc(&c->di_ck, (size_t) c->L * U * n * A));   // [L][2U][S][A], zero like the reference's cleared cache (dia/model.cpp:329)
-        CHK(dmalloc(&c->di_cv, (size_t) c->L * U * n * A));
-        CHK(dmalloc(&c->di_k, (size_t) c->L * R * G * kvH));  // [L][2U][G][kvH]
-        CHK(dmalloc(&c->di_v, (size_t) c->L * R * G * kvH));
+        const size_t kve = (size_t) c->di_kv_esz;   // bytes per cache element: half of them under tts_hip_dia_desc::kv_type = TTS_HIP_F16
+        CHK(dmalloc((char **) &c->di_ck, (size_t) c->L * U * n * A * kve));   // [L][2U][S][A], zero like the reference's cleared cache (dia/model.cpp:329)
+        CHK(dmalloc((char **) &c->di_cv, (size_t) c->L * U * n * A * kve));
+        CHK(dmalloc((char **) &c->di_k, (size_t) c->L * R * G * kvH * kve));  // [L][2U][G][kvH]
+        CHK(dmalloc((char **) &c->di_v, (size_t) c->L * R * G * kvH * kve));
         CHK(dmalloc(&c->di_x, (size_t) R * DH)); CHK(dmalloc(&c->di_xn, (size_t) R * DH)); 
         // the projections of a step with <= 16 rows may arrive as up to DIA_STREAM_SLABS K-slice slabs of 16 rows (gemv_stream_kernels.h)
         const size_t RSL = std::max((size_t) R, (size_t) DIA_STREAM_SLABS * 16);
@@ -2300,6 +2301,11 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         memcpy(out, v->data(), v->size() * 4);
         return (int64_t) v->size();
     }
+    if (c->has_dia && w == "di_kv_elem") {   // the element size of the four caches in bytes: 4, or 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16
+        if (max_floats < 1) { set_err("debug_read(di_kv_elem): buffer too small"); return -1; }
+        out[0] = (float) c->di_kv_esz;
+        return 1;
+    }
     if (c->has_dia && w.size() > 5 && w[0] == 'd' && w[1] == 'i' && w[2] == '_') {   // "di_k|di_v:<layer>:<row slot>" [max_gen][kv width], "di_ck|di_cv:<layer>:<row slot>" [max_ctx][A]
         const bool cross = w[3] == 'c';
         const char kv = w[cross ? 4 : 3];
@@ -2308,8 +2314,15 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if ((kv != 'k' && kv != 'v') || w.size() <= o + 1 || w[o] != ':' || sscanf(w.c_str() + o + 1, "%d:%d", &layer, &row) != 2 || layer < 0 || layer >= c->L || row < 0 ||
             row >= 2 * c->di_U) { set_err("debug_read(%s): bad item or layer/row slot", what); return -1; }
         const size_t per = cross ? (size_t) c->dia.max_ctx * c->di_A : (size_t) c->dia.max_gen * c->di_kvH, n = std::min(max_floats, per);
-        const float *base = cross ? (kv == 'k' ? c->di_ck : c->di_cv) : (kv == 'k' ? c->di_k : c->di_v);
-        if (hipMemcpy(out, base + ((size_t) layer * 2 * c->di_U + row) * per, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        const void *base = cross ? (kv == 'k' ? c->di_ck : c->di_cv) : (kv == 'k' ? c->di_k : c->di_v);
+        const char *src = (const char *) base + ((size_t) layer * 2 * c->di_U + row) * per * (size_t) c->di_kv_esz;
+        if (c->di_kv_esz == 2) {   // the fp16 caches: the rows widened to fp32 (exact)
+            std::vector<_Float16> h(n);
+            if (hipMemcpy(h.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = (float) h[i];
+            return (int64_t) n;
+        }
+        if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
     // Parler: the rows of the last forward's last attention launch.  Nothing after it writes these buffers (enqueue_forward: the FFN and the heads use

@@ -194,7 +194,9 @@ struct tts_hip_ctx {
     W di_heads;
     int di_EH = 0, di_EF = 0, di_DF = 0, di_A = 0, di_kvH = 0, di_V = 0, di_Vpad = 0, di_ksplit = 1, di_pending = 0, di_evocab = 0;
     float *di_ex = nullptr, *di_exn = nullptr, *di_eqkv = nullptr, *di_eatt = nullptr, *di_egu = nullptr, *di_eg = nullptr, *di_ek = nullptr, *di_ev = nullptr;
-    float *di_ckv = nullptr, *di_ck = nullptr, *di_cv = nullptr, *di_k = nullptr, *di_v = nullptr;
+    float *di_ckv = nullptr;
+    void *di_ck = nullptr, *di_cv = nullptr, *di_k = nullptr, *di_v = nullptr;   // cross [L][2U][max_ctx][A] and self [L][2U][max_gen][kv width] of di_kv_esz bytes per element
+    int di_kv_esz = 4;   // 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16 (fixed at create: the captured graphs never see it change)
     float *di_x = nullptr, *di_xn = nullptr, *di_qkv = nullptr, *di_q = nullptr, *di_att = nullptr, *di_gu = nullptr, *di_g = nullptr, *di_parts = nullptr;
     float *di_logits = nullptr, *di_guided = nullptr;
     uint32_t *di_tok = nullptr, *di_epos = nullptr, *di_eseq = nullptr, *di_kbeg = nullptr, *di_kend = nullptr;

@@ -43,7 +43,7 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
 static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const float *kc, const float *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
                            QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0, int kv_esz = 4) {
-    // kv_esz 2: kc / vc are an Orpheus context's fp16 cache (TTS_HIP_FLAG_KV_F16) and the fp16 forms of the three kernels read it; seq_stride stays in elements
+    // kv_esz 2: kc / vc are an fp16 cache (Orpheus: TTS_HIP_FLAG_KV_F16; Dia: tts_hip_dia_desc::kv_type) and the fp16 forms of the kernels read it; seq_stride stays in elements
     const _Float16 *kc16 = (const _Float16 *) kc, *vc16 = (const _Float16 *) vc;
     int nz = 1;
     if (deferred) *deferred = 0;
@@ -69,6 +69,10 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
     if (kv_esz == 2) {
         if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
             hipLaunchKernelGGL((attn_gqa_wave_f16_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part, n_ctx_keys);
+        } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
+            // Dia's cross-attention over an fp16 cache (tts_hip_dia_desc::kv_type): the conditions of the fp32 EXT form below, 8 passes through 4 rolling register slots
+            hipLaunchKernelGGL((attn_gqa_wave_ext_f16_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part, n_ctx_keys,
+                               kend, row_seq, seq_stride, qp);
         } else {
             hipLaunchKernelGGL((attn_gqa_f16_kernel<128, true>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part,
                                kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
@@ -1093,15 +1097,21 @@ extern "C" int tts_hip_orpheus_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t
 extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *dd) {
     if (!dd || dd->struct_size != sizeof(tts_hip_dia_desc)) { set_err("tts_hip_dia_create: bad desc (struct_size mismatch)"); return nullptr; }
     if (refuse_kv_f16(dd->flags, "tts_hip_dia_create")) return nullptr;
+    if (dd->kv_type != TTS_HIP_F32 && dd->kv_type != TTS_HIP_F16) {
+        set_err("tts_hip_dia_create: kv_type %u is neither TTS_HIP_F32 (0) nor TTS_HIP_F16 (1)", dd->kv_type);
+        return nullptr;
+    }
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = dd->dec_hidden_size; d.n_layers = dd->dec_layers; d.n_attn_heads = dd->dec_attn_heads; d.max_ctx_length = dd->max_gen;
     d.max_seqs = 1;
-    d.flags = (dd->flags & (TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q)) | TTS_HIP_FLAG_NO_PARLER | TTS_HIP_FLAG_NO_DAC;
+    // TTS_HIP_FLAG_NO_GRAPH reaches dia_loop_launch: the loop's steps then run eagerly instead of as replays of one captured graph
+    d.flags = (dd->flags & (TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_NO_GRAPH)) | TTS_HIP_FLAG_NO_PARLER | TTS_HIP_FLAG_NO_DAC;
     tts_hip_ctx *c = tts_hip_create(device, &d);
     if (!c) return nullptr;
     c->has_dia = true;
     c->dia = *dd;
+    if (dd->kv_type == TTS_HIP_F16) c->di_kv_esz = 2;
     if (c->dia.cfg_scale == 0.0f) c->dia.cfg_scale = 3.0f;
     return c;
 }
@@ -1240,14 +1250,20 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
     // positions) only for the sentence; the other K rows are zero as in the freshly cleared cache
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->di_dec[(size_t) l];
-        float *ck = c->di_ck + ((size_t) l * c->di_U + slot) * n * A, *cv = c->di_cv + ((size_t) l * c->di_U + slot) * n * A;   // rows 2*slot, 2*slot+1
+        const size_t esz = (size_t) c->di_kv_esz, slot_off = ((size_t) l * c->di_U + slot) * n * A * esz;   // rows 2*slot, 2*slot+1
+        char *ck = (char *) c->di_ck + slot_off, *cv = (char *) c->di_cv + slot_off;
         CHK(dia_gemm_rows(c, y.ckv, c->di_exn, EH, c->di_ckv, 2 * A, n, EPI_STORE));
-        hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale, 0, NH,
-                           HD, ck, cv, (const uint32_t *) c->di_eseq, (int64_t) S * A);
+        if (esz == 2) {   // the fp16 cache: the same rotation, K and V rounded once as they are stored
+            hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale, 0, NH,
+                               HD, (_Float16 *) ck, (_Float16 *) cv, (const uint32_t *) c->di_eseq, (int64_t) S * A);
+        } else {
+            hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale, 0, NH,
+                               HD, (float *) ck, (float *) cv, (const uint32_t *) c->di_eseq, (int64_t) S * A);
+        }
         HIPCHK(hipGetLastError());
         if ((int) sentence_len < S)
             for (int b = 0; b < 2; b++)
-                HIPCHK(hipMemsetAsync(ck + ((size_t) b * S + sentence_len) * A, 0, (size_t) (S - (int) sentence_len) * A * 4, c->stream));
+                HIPCHK(hipMemsetAsync(ck + ((size_t) b * S + sentence_len) * A * esz, 0, (size_t) (S - (int) sentence_len) * A * esz, c->stream));
     }
     if (enc_out) HIPCHK(hipMemcpyAsync(enc_out, c->di_exn, (size_t) n * EH * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1285,12 +1301,14 @@ static int dia_attn_snapshot(tts_hip_ctx *c, int layer, bool cross, const float 
 static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, bool snap = false) {
     const int S = (int) c->dia.max_ctx, G = (int) c->dia.max_gen, DH = c->H, DF = c->di_DF, A = c->di_A, kvH = c->di_kvH, HD = (int) c->dia.head_dim;
     const int NH = c->NH, NKV = (int) c->dia.dec_kv_heads, NO = c->NO, V = c->di_V, QKV = A + 2 * kvH;
-    const int R = 2 * U, RS = 2 * c->di_U;
+    const int R = 2 * U, RS = 2 * c->di_U, kv_esz = c->di_kv_esz;
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
     const float theta_scale = powf(10000.0f, -2.0f / (float) HD);
-    static std::atomic<uint64_t> attr{0};
+    static std::atomic<uint64_t> attr{0}, attr16{0};
     if ((size_t) (128 + std::max(S, G)) * 4 > 48 * 1024 && attr_needed(attr, c->device))
         HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
+    if (kv_esz == 2 && (size_t) (128 + std::max(S, G)) * 4 > 48 * 1024 && attr_needed(attr16, c->device))
+        HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_f16_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
     DiaEmbedArgs ea{};
     for (int i = 0; i < NO; i++) ea.table[i] = f32(c->di_embd[i]);
     ea.ids = c->di_ids; ea.n_out = NO; ea.H = DH; ea.x = c->di_x;
@@ -1300,8 +1318,9 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     const uint32_t *nul = nullptr;
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->di_dec[(size_t) l];
-        float *kc = c->di_k + (size_t) l * RS * G * kvH, *vc = c->di_v + (size_t) l * RS * G * kvH;
-        const float *ck = c->di_ck + (size_t) l * RS * S * A, *cv = c->di_cv + (size_t) l * RS * S * A;
+        const size_t self_off = (size_t) l * RS * G * kvH * (size_t) kv_esz, cross_off = (size_t) l * RS * S * A * (size_t) kv_esz;
+        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off;
+        const float *ck = (const float *) ((const char *) c->di_ck + cross_off), *cv = (const float *) ((const char *) c->di_cv + cross_off);   // fp16 rows under kv_esz 2 (launch_attn_gqa)
         // every projection: gemv_stream_kernel slabs folded by its consumer when the step has <= 16 rows and fp16 matrices
         // (sl = slabs written, 0 = shape does not qualify -> gemm16_kernel as before)
         int sl = 0;
@@ -1309,13 +1328,18 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         CHK(dia_rms(c, y.sa_norm, R, DH, c->di_x, c->di_xn, true));
         CHK(dia_gemm_stream(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, DIA_STREAM_SLABS, st16 * QKV, &sl));
         if (!sl) CHK(dia_gemm(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, EPI_STORE));
-        hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
-                           NKV, HD, kc, vc, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
+        if (kv_esz == 2) {   // the fp16 cache: the same slab fold and rotation, K and V rounded once as they are appended
+            hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
+                               NKV, HD, (_Float16 *) kc, (_Float16 *) vc, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
+        } else {
+            hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
+                               NKV, HD, (float *) kc, (float *) vc, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
+        }
         HIPCHK(hipGetLastError());
         int slices = 0;   // key slices the attention left unmerged for the projection's staging prologue (0: di_att holds the rows)
         CHK(launch_attn_gqa(c, NH, R, self_keys, (const float *) c->di_qkv, QKV, (const uint32_t *) c->di_pos, (const float *) kc, (const float *) vc, NKV, 1.0f,
                             c->di_att, nul, nul, (const uint32_t *) c->di_seq, (int64_t) G * kvH, fixed_split, false, QPre{},
-                            A % 128 == 0 && stream_fold_ok(c, y.so, R, DIA_STREAM_SLABS) ? &slices : nullptr));
+                            A % 128 == 0 && stream_fold_ok(c, y.so, R, DIA_STREAM_SLABS) ? &slices : nullptr, 0, kv_esz));
         if (snap) CHK(dia_attn_snapshot(c, l, false, c->di_qkv, QKV, 1, 0, R, A, nullptr));
         CHK(dia_gemm_stream(c, y.so, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
@@ -1328,7 +1352,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         slices = 0;
         CHK(launch_attn_gqa(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, ck, cv, NH, 1.0f, c->di_att, nul, (const uint32_t *) c->di_cend,
                             (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
-                            A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S));
+                            A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S, kv_esz));
         if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, qp.n_parts, qp.part_stride, R, A, c->di_cend));
         CHK(dia_gemm_stream(c, y.co, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
@@ -1549,7 +1573,10 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
         uint64_t clear = 0;
         for (int u = 0; u < U; u++) if (!c->di_slot_encoded[(size_t) u]) clear |= 1ull << u;
         if (clear) {
-            hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, c->di_ck, c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
+            if (c->di_kv_esz == 2)
+                hipLaunchKernelGGL(dia_stream_clear_f16_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, (_Float16 *) c->di_ck, (_Float16 *) c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
+            else
+                hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, (float *) c->di_ck, (float *) c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals

@@ -62,7 +62,7 @@ class DiaDesc(C.Structure):
     """tts_hip_dia_desc (include/tts_hip.h)"""
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "enc_hidden_size", "enc_layers", "enc_attn_heads", "dec_hidden_size", "dec_layers", "dec_attn_heads",
                                           "dec_kv_heads", "head_dim", "n_output_heads", "output_vocab_size", "max_ctx", "max_gen")] + [
-        ("cfg_scale", C.c_float), ("flags", C.c_uint32), ("max_utterances", C.c_uint32)]
+        ("cfg_scale", C.c_float), ("flags", C.c_uint32), ("max_utterances", C.c_uint32), ("kv_type", C.c_uint32)]
 
 
 class KokoroDesc(C.Structure):
@@ -1005,11 +1005,13 @@ class DiaCodes(C.Structure):
 class DiaEngine:
     """A Dia context (tts_hip_dia_create): encoder + cross K/V once per sentence, then one decoder step per call."""
 
-    def __init__(self, cfg, device=0, flags=0, cfg_scale=0.0, max_utterances=1):
+    def __init__(self, cfg, device=0, flags=0, cfg_scale=0.0, max_utterances=1, kv_type=gguf.F32):
+        """kv_type: gguf.F32 (the reference's caches) or gguf.F16 (tts_hip_dia_desc::kv_type: the self and cross K/V caches in fp16, rounded once as they are stored)"""
         self.L = load_lib()
         self.cfg = cfg
         d = DiaDesc()
         d.max_utterances = max_utterances
+        d.kv_type = kv_type
         d.struct_size = C.sizeof(DiaDesc)
         d.enc_hidden_size, d.enc_layers, d.enc_attn_heads = cfg.enc_hidden, cfg.enc_layers, cfg.enc_heads
         d.dec_hidden_size, d.dec_layers, d.dec_attn_heads, d.dec_kv_heads = cfg.dec_hidden, cfg.dec_layers, cfg.dec_heads, cfg.dec_kv_heads
@@ -1046,7 +1048,8 @@ class DiaEngine:
 
     def debug_read(self, what, max_floats):
         """'di_attn:<layer>:<self|cross>:<q|out|meta>' (set_debug before the step; meta = n_parts, part_stride, ld, rows, then pos / kend / row slot per
-        row), 'di_k|di_v:<layer>:<row slot>' [max_gen][kv width], 'di_ck|di_cv:<layer>:<row slot>' [max_ctx][heads * 128] (test / debugging aid)"""
+        row), 'di_k|di_v:<layer>:<row slot>' [max_gen][kv width], 'di_ck|di_cv:<layer>:<row slot>' [max_ctx][heads * 128] (fp16 caches widened exactly), 'di_kv_elem': the
+        cache element size in bytes (4, or 2 with kv_type=gguf.F16) (test / debugging aid)"""
         out = np.empty(max_floats, dtype=np.float32)
         n = self.L.tts_hip_debug_read(self.ctx, what.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), max_floats)
         if n < 0:

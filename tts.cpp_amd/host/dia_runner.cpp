@@ -72,6 +72,7 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : tts_generation_run
     d.max_ctx = hp.max_encoder_context_length; d.max_gen = hp.max_generation_size; d.cfg_scale = hp.cfg_scale;
     max_seqs = tts_load_max_seqs();
     d.max_utterances = max_seqs;
+    if (getenv("TTS_HIP_KV_F16")) d.kv_type = TTS_HIP_F16;   // the switch the Parler and Orpheus runners read: fp16 self and cross K/V caches (extension, include/tts_hip.h)
     lm = tts_hip_dia_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_dia_create failed: %s\n", tts_hip_last_error());
     tts_hip_desc a{};
@@ -98,6 +99,11 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : tts_generation_run
 dia_runner::~dia_runner() {
     tts_hip_destroy(lm);
     tts_hip_destroy(dac);
+}
+
+uint32_t dia_runner::kv_element_bytes() const {
+    float v = 0.0f;
+    return tts_hip_debug_read(lm, "di_kv_elem", &v, 1) == 1 ? (uint32_t) v : 0;
 }
 
 void dia_runner::assign_weight(const char * name, const gguf_tensor_view & t) {

@@ -86,6 +86,7 @@ struct dia_runner final : tts_generation_runner {
     // last chunk is out; on_chunk returning false drops that utterance only (tts_hip_dia_stream_drop), reported with what it got.
     bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) override;
     uint32_t batch_capacity() const override { return max_seqs; }
+    uint32_t kv_element_bytes() const override;   // 4, or 2 when TTS_HIP_KV_F16 was in the environment at load (tts_hip_dia_desc::kv_type)
     uint32_t max_seqs = 1;
     std::vector<std::vector<uint32_t>> last_batch_tokens;
 
