@@ -83,8 +83,11 @@ int           tts_c_generate_batch_chunked(tts_c_runner *r, const char *const *t
  * different utterances interleave, those of one utterance arrive in order and concatenate to its tts_c_generate_stream audio.  fn returning 0
  * drops that utterance only; the others go on.  Returns 0 when done, 1 when fn dropped at least one utterance, another value with
  * tts_c_last_error() on error (chunk_frames == 0 is one).  Dia's session chunks while its slots keep running: the codec pass of the windows
- * that became final at one look-in runs under the next 16 decoder steps, and a dropped utterance's slot is parked at the next look-in.  The
- * sessions of Parler-TTS and Orpheus, and Kokoro's groups, hand each finished utterance out as one chunk. */
+ * that became final at one look-in runs under the next 16 decoder steps, and a dropped utterance's slot is parked at the next look-in.
+ * Orpheus' session chunks the same way: chunk_frames counts SNAC frames, the windows of all slots go through one SNAC window pass under the next
+ * 28 decoder steps, and a dropped utterance's slot is freed at the next look-in; the SNAC noise block is drawn as for tts_c_generate_chunked
+ * (frame by frame; across utterances in slot order within a look-in), so with TTS_SNAC_NO_NOISE the pieces concatenate to tts_c_generate's PCM.
+ * Parler-TTS' session, and Kokoro's groups, hand each finished utterance out as one chunk. */
 int           tts_c_generate_stream_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,
                                             tts_c_chunk_fn fn, void *user);
 /* Test hook: the Parler runner's un-delay rule (parler_undelay) on delayed tokens [n_steps][n_heads] — the codes of the kept frames that are
@@ -116,7 +119,8 @@ const char   *tts_c_last_error(void);
 
 /* ---- test hooks ---------------------------------------------------------------------------------- */
 /* which = 0: prompt ids of the last generate (tokenised + EOS); 1: sampled ids, still delayed
- * (pctx->output_tokens); Dia, 16 + i: the still-delayed ids of utterance i of the last generate_batch / generate_stream.
+ * (pctx->output_tokens); Dia, 16 + i: the still-delayed ids of utterance i of the last generate_batch / generate_stream; Orpheus, 16 + i: the ids
+ * of utterance i of the last generate_batch, or of the last generate_stream_chunked whose session chunked (i below 4096).
  * Returns the count (copies at most cap). */
 int tts_c_last_tokens(tts_c_runner *r, int which, uint32_t *out, int cap);
 /* unigram tokenizer from the GGUF vocabulary + EOS, as batch_from_sentence builds it (model.cpp:473-498); a GGUF with

@@ -321,8 +321,23 @@ int tts_hip_orpheus_sample_logits(tts_hip_ctx *ctx, const float *logits, const t
  *            (stopping token, max_new ids, or the end of the cache) — inside the run, or at their admission (max_new 0 or 1, a first id that stops) —
  *            are reported with their id counts and leave the rows of the next run.  A row that finishes inside a run idles as padding until the run
  *            ends: nothing it selects is emitted, its sampler state stands still.  With no live rows nothing is launched.
+ *   launch   the enqueue half of run: the live rows staged once, min(n_steps, what the longest live row can still need) steps enqueued, and the call
+ *            returns while they run, with no copy and no synchronise.  The session is in flight until a wait.  With no live rows nothing is launched.
+ *   wait     the look-in: one launch (llama_loop_lookin_kernel, one workgroup per slot), one copy into pinned memory and one synchronise, whatever
+ *            the slot count.  tokens_out [n_slots][max_new] receives each slot's ids that no earlier wait handed out, at their places (the contract
+ *            of gen_wait); n_out[s] is the occupant's count so far (0 for a slot nobody occupies) and done[s] whether it has ended (both may be
+ *            NULL).  Slots that ended are reported exactly as run reports them.  tokens_out NULL takes nothing: only the slots' headers are copied
+ *            (they are the state array itself, so no kernel is launched: what run has always copied) and the handed-out marks stand still, so
+ *            the next taking wait still delivers everything.  A wait with nothing in flight is a pure look-in.
+ *   drop     frees n live slots without reporting them, between a wait and the next launch.  Nothing is launched: the rows of a run are staged from
+ *            the host's state, so the slot has left the next run's rows, and the next admission rewrites its device state.  It is admissible at once.
  *   collect  the first `count` ids of a reported slot, before that slot is admitted again
- *   end      ends the session (its device buffers stay on the context for the next session or batch)
+ *   end      ends the session (its device buffers stay on the context for the next session or batch); with steps in flight it synchronises first
+ * run is launch, a wait that takes nothing, and the report: one loop under both.  The ids the waits hand out tile each occupant's sequence
+ * without gap or overlap whatever the launch sizes; they equal what run and collect return; a drop changes no other slot's ids
+ * (tests/test_gpu_orpheus_stream_chunked.py).  While steps are in flight (between a launch and its wait), admit, collect, drop, run and a second
+ * launch return non-zero before anything is launched and leave the session as it was; so does a drop of a slot that is not live, is >= n_slots
+ * or is named twice.
  * An utterance's ids are those of tts_hip_orpheus_generate_batch for the same prompt, that is those of its own one-sequence generation
  * (tests/test_gpu_orpheus_stream.py).  Key split: the attention of step i of a run is sized by max over the live rows of (position at the look-in)
  * + i + 1, capped at n_ctx: the exact longest row as long as nobody finishes, an upper bound once someone has.  Below 256 keys that bound selects one
@@ -348,6 +363,10 @@ int tts_hip_orpheus_stream_begin_mixed(tts_hip_ctx *ctx, uint32_t n_slots, uint3
 int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *prompts, const uint32_t *n_prompt,
                                        const tts_hip_sampling *const *sampling, const float *uniforms);
 int tts_hip_orpheus_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts);
+int tts_hip_orpheus_stream_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_orpheus_stream_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                                uint32_t *finished_counts);
+int tts_hip_orpheus_stream_drop(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots);
 int tts_hip_orpheus_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t count, uint32_t *tokens_out);
 int tts_hip_orpheus_stream_end(tts_hip_ctx *ctx);
 /* the session's row-batched selection alone on caller-supplied logits [n_rows][vocab_size] (n_rows <= max_seqs), for parity tests: per row the contract

@@ -1483,6 +1483,26 @@ static __global__ __launch_bounds__(64) void llama_advance_rows_kernel(int rows,
     if (next_id) { next_id[r] = id; next_pos[r] = pos; }
 }
 
+// A look-in: one workgroup per slot packs {the slot's state, the ids no earlier look-in took} into its stretch of one contiguous block
+// [n_slots][LLAMA_SLOT_STATE + cap], so that the host learns everything from one launch, one copy and one synchronisation however many slots there
+// are.  The header is the whole state record: the host stages the next run's rows from it.  handed [n_slots] counts the ids of the occupant that
+// look-ins have taken (an admission resets it); cap bounds what one slot can hold un-taken: the steps enqueued since the last look-in that took
+// ids, plus the id an admission selects.  take = 0: the headers only, handed stands still.  Latency-bound: plain loads and stores, 64 lanes.
+static __global__ __launch_bounds__(64) void llama_loop_lookin_kernel(int n_slots, int take, uint32_t cap, uint32_t max_new, const uint32_t *slot_state, const uint32_t *tokens,
+                                                               uint32_t *handed, uint32_t *block) {
+    const int s = blockIdx.x;
+    if (s >= n_slots) return;
+    const uint32_t *st = slot_state + (size_t) s * LLAMA_SLOT_STATE;
+    const uint32_t from = handed[s], to = min(st[0], max_new);
+    const uint32_t n = take && to > from ? min(to - from, cap) : 0u;
+    uint32_t *out = block + (size_t) s * (LLAMA_SLOT_STATE + cap);
+    const uint32_t *src = tokens + (size_t) s * max_new + from;
+    if (threadIdx.x < LLAMA_SLOT_STATE) out[threadIdx.x] = st[threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[LLAMA_SLOT_STATE + i] = src[i];
+    __syncthreads();   // every thread has read handed[s]
+    if (threadIdx.x == 0 && n) handed[s] = from + n;
+}
+
 // gu [R][2F] (gate | up) -> g [R][F] = silu(gate) * up; aq / ad (optional, F % 32 == 0): g also as Q8_0 blocks for the down projection
 // n_parts > 1: gu holds n_parts fp32 slabs part_stride floats apart (gemv_stream_kernel), summed in slab order on the way in
 static __global__ void silu_mul_kernel(const float *gu, int F, int R, float *g, int8_t *aq, float *ad, int n_parts = 1, int64_t part_stride = 0) {

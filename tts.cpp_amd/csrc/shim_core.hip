@@ -274,7 +274,9 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     if (c->h_out) (void) hipHostFree(c->h_out);
     if (c->h_hist) (void) hipHostFree(c->h_hist);
     free_dev(c->ls.state); free_dev(c->ls.tokens); free_dev(c->ls.smp); free_dev(c->ls.uni); free_dev(c->ls.cand); free_dev(c->ls.total); free_dev(c->ls.samp); free_dev(c->ls.pen);
+    free_dev(c->ls.d_handed); free_dev(c->ls.look);
     if (c->ls.h_state) (void) hipHostFree(c->ls.h_state);
+    if (c->ls.h_look) (void) hipHostFree(c->ls.h_look);
     free_dev(c->t5_bucket); free_dev(c->t5_x); free_dev(c->t5_qkv); free_dev(c->t5_att); free_dev(c->t5_ug); free_dev(c->t5_g); free_dev(c->t5_y); free_dev(c->t5_ids); free_dev(c->logits); free_dev(c->part); free_dev(c->attn_cnt); free_dev(c->b1_stamps); free_dev(c->dbg); free_dev(c->d_ids); free_dev(c->d_pos);
     free_dev(c->d_seq); free_dev(c->d_gather); free_dev(c->d_tok); free_dev(c->d_step); free_dev(c->d_steps_done); free_dev(c->d_tokens_out);
     free_dev(c->d_eos); free_dev(c->d_frames);

@@ -291,8 +291,10 @@ struct tts_hip_ctx {
         enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished, not yet reported (SESSION) / done (BATCH)
         std::vector<uint8_t> slot;                  // per slot, one of the above
         std::vector<uint32_t> count, cur, pos;      // per slot at the last look-in: ids so far, latest id, its position
-        std::vector<uint32_t> handed;               // BATCH: ids of the slot a gen_wait has handed out
+        std::vector<uint32_t> handed;               // ids of the occupant that a gen_wait (BATCH) or a stream_wait (SESSION, mirrored in d_handed) has handed out
         std::vector<uint32_t> rows;                 // live slots in slot order (= the rows of the next run)
+        uint32_t in_flight = 0;                     // steps enqueued by a launch that no look-in has waited for
+        uint32_t unread = 0;                        // steps enqueued since the last look-in that took ids
         std::vector<uint8_t> slot_sampled, slot_nucleus;   // per slot, what its occupant selects with: sampler::sample / ... with top_p < 1
         size_t cap_slots = 0, cap_new = 0;          // what the buffers below hold
         uint32_t *state = nullptr;                  // device [slots][LLAMA_SLOT_STATE]
@@ -301,7 +303,9 @@ struct tts_hip_ctx {
         float *uni = nullptr;                       // device [slots][max_new]
         unsigned long long *cand = nullptr;         // device [slots][TOPK_PARTS][TOPK_MAXK]
         float *total = nullptr;                     // device [slots]
-        uint32_t *h_state = nullptr;                // pinned [slots][LLAMA_SLOT_STATE]
+        uint32_t *h_state = nullptr;                // pinned [slots][LLAMA_SLOT_STATE]: an admission's look at its slot
+        uint32_t *d_handed = nullptr;               // device [slots] ids llama_loop_lookin_kernel has taken from the occupant
+        uint32_t *look = nullptr, *h_look = nullptr;   // device / pinned [slots][LLAMA_SLOT_STATE + max_new] the look-in's block
         void *samp = nullptr;                       // device [slots] llama_slot_sampler
         double *pen = nullptr;                      // device [slots][max_new] pow(penalty, count); first entry 0: penalty 1
     } ls;

@@ -686,6 +686,11 @@ static int llama_stream_ready(tts_hip_ctx *c, const char *what, bool need_sessio
     return 0;
 }
 
+// between a tts_hip_orpheus_stream_launch and its stream_wait the steps may still be running: nothing else touches the session
+static int llama_stream_idle(const tts_hip_ctx *c, const char *what) {
+    return c->ls.in_flight ? set_err("%s: %u steps are in flight (tts_hip_orpheus_stream_wait first)", what, c->ls.in_flight) : 0;
+}
+
 // one slot's record and table, as the rows kernels read them: sp NULL is sampler::max; the table is stage_penalty's for sp's penalty, len entries
 static void llama_slot_sampler_host(const tts_hip_sampling *sp, int len, llama_slot_sampler *rec, double *table) {
     *rec = sp ? llama_slot_sampler{LLAMA_SLOT_SAMPLE, sp->top_k, sp->temperature, sp->top_p} : llama_slot_sampler{LLAMA_SLOT_MAX, 0u, 1.0f, 1.0f};
@@ -703,7 +708,9 @@ static int dmalloc(T **p, size_t n) {
 static void llama_loop_free(tts_hip_ctx *c) {
     auto &g = c->ls;
     free_dev(g.state); free_dev(g.tokens); free_dev(g.smp); free_dev(g.uni); free_dev(g.cand); free_dev(g.total); free_dev(g.samp); free_dev(g.pen);
+    free_dev(g.d_handed); free_dev(g.look);
     if (g.h_state) (void) hipHostFree(g.h_state);
+    if (g.h_look) (void) hipHostFree(g.h_look);
     g = LS{};
 }
 
@@ -726,6 +733,9 @@ static int llama_loop_begin(tts_hip_ctx *c, const char *what, LS::Mode mode, uin
         if (rc == 0) rc = dmalloc((llama_slot_sampler **) &g.samp, CS);
         if (rc == 0) rc = dmalloc(&g.pen, CS * CM);
         if (rc == 0 && hipHostMalloc((void **) &g.h_state, CS * LLAMA_SLOT_STATE * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
+        if (rc == 0) rc = dmalloc(&g.d_handed, CS);
+        if (rc == 0) rc = dmalloc(&g.look, CS * (LLAMA_SLOT_STATE + CM));
+        if (rc == 0 && hipHostMalloc((void **) &g.h_look, CS * (LLAMA_SLOT_STATE + CM) * 4) != hipSuccess) rc = set_err("%s: out of pinned memory", what);
         if (rc != 0) { llama_loop_free(c); return rc; }
         g.cap_slots = CS; g.cap_new = CM;
     }
@@ -735,6 +745,7 @@ static int llama_loop_begin(tts_hip_ctx *c, const char *what, LS::Mode mode, uin
     g.count.assign(S, 0); g.cur.assign(S, 0); g.pos.assign(S, 0); g.handed.assign(S, 0);
     g.slot_sampled.assign(S, 0); g.slot_nucleus.assign(S, 0);
     g.rows.clear();
+    g.in_flight = 0; g.unread = 0;
     g.mode = mode;
     return 0;
 }
@@ -757,6 +768,7 @@ static int llama_loop_admit(tts_hip_ctx *c, const char *what, uint32_t s, const 
     llama_slot_sampler_host(sp, (int) g.max_new, &rec, table.data());
     HIPCHK(hipMemcpyAsync(g.state + (size_t) s * LLAMA_SLOT_STATE, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(g.smp + (size_t) s * 3, reset, sizeof(reset), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(g.d_handed + s, 0, 4, c->stream));   // the look-ins start at the occupant's first id
     HIPCHK(hipMemcpyAsync((llama_slot_sampler *) g.samp + s, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(g.pen + (size_t) s * g.max_new, table.data(), table.size() * 8, hipMemcpyHostToDevice, c->stream));
     if (sp) HIPCHK(hipMemcpyAsync(g.uni + (size_t) s * g.max_new, uniforms, (size_t) g.max_new * 4, hipMemcpyHostToDevice, c->stream));
@@ -781,45 +793,94 @@ static void llama_loop_live_rows(tts_hip_ctx *c) {
     for (uint32_t s = 0; s < g.n_slots; s++) if (g.slot[s] == LS::LIVE) g.rows.push_back(s);
 }
 
-// A run: the live rows staged once, up to n_steps x (forward, selection, advance), one copy of the slots' state and one synchronise.  The run is
-// over once no row can still be live: a row with `count` ids at position `pos` ends after min(max_new - count, n_ctx - pos) steps at the latest.
-// Slots that finished are ENDED afterwards and have left the rows of the next run.
-static int llama_loop_run(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
+// The enqueue half of a run: the live rows staged once, then up to n_steps x (forward, selection, advance), no copy and no synchronise behind them.
+// The run is over once no row can still be live: a row with `count` ids at position `pos` ends after min(max_new - count, n_ctx - pos) steps at
+// the latest.  With no live row nothing is launched.
+static int llama_loop_launch(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
     auto &g = c->ls;
     const uint32_t n = (uint32_t) g.rows.size();
-    if (n != 0 && n_steps != 0) {
-        HIPCHK(hipSetDevice(c->device));
-        std::vector<uint32_t> ids(n), ps(n);
-        uint32_t left = 0;
-        for (uint32_t r = 0; r < n; r++) {
-            const uint32_t s = g.rows[r];
-            ids[r] = g.cur[s]; ps[r] = g.pos[s];
-            left = std::max(left, std::min(g.max_new - g.count[s], c->lm.n_ctx - g.pos[s]));
-        }
-        uint32_t max_pos = 0;
-        CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
-        bool any_max = false, any_sample = false, any_nucleus = false;   // which selection kernels this run's rows need
-        for (uint32_t s : g.rows) { any_max |= !g.slot_sampled[s]; any_sample |= g.slot_sampled[s] != 0; any_nucleus |= g.slot_nucleus[s] != 0; }
-        for (uint32_t i = 0; i < std::min(n_steps, left); i++) {
-            // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
-            const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
-            CHK(llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1));
-            CHK(llama_select_slots(c, any_max, any_sample, any_nucleus, (int) n, c->l_logits, c->l_seq, 0, g.state, (const llama_slot_sampler *) g.samp, g.pen, (int) g.max_new, g.smp,
-                                   g.uni, (int64_t) g.max_new, g.cand, g.total));
+    if (n == 0 || n_steps == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint32_t> ids(n), ps(n);
+    uint32_t left = 0;
+    for (uint32_t r = 0; r < n; r++) {
+        const uint32_t s = g.rows[r];
+        ids[r] = g.cur[s]; ps[r] = g.pos[s];
+        left = std::max(left, std::min(g.max_new - g.count[s], c->lm.n_ctx - g.pos[s]));
+    }
+    uint32_t max_pos = 0;
+    CHK(llama_stage_rows(c, what, n, g.rows.data(), ids.data(), ps.data(), &max_pos));   // the live rows, once per run
+    bool any_max = false, any_sample = false, any_nucleus = false;   // which selection kernels this run's rows need
+    for (uint32_t s : g.rows) { any_max |= !g.slot_sampled[s]; any_sample |= g.slot_sampled[s] != 0; any_nucleus |= g.slot_nucleus[s] != 0; }
+    const uint32_t steps = std::min(n_steps, left);
+    for (uint32_t i = 0; i < steps; i++) {
+        // the longest row as long as nobody finishes, an upper bound once someone has (a finished row's position stands still)
+        const uint32_t keys = std::min(max_pos + i + 1, c->lm.n_ctx);
+        int rc = llama_forward(c, nullptr, (int) n, 0, (int) keys, c->l_seq, -1);
+        if (rc == 0) rc = llama_select_slots(c, any_max, any_sample, any_nucleus, (int) n, c->l_logits, c->l_seq, 0, g.state, (const llama_slot_sampler *) g.samp, g.pen, (int) g.max_new,
+                                             g.smp, g.uni, (int64_t) g.max_new, g.cand, g.total);
+        if (rc == 0) {
             hipLaunchKernelGGL(llama_advance_rows_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (int) n, (const uint32_t *) c->l_seq, 0, (const uint32_t *) c->l_btok, g.state,
                                g.tokens, g.max_new, g.stop_id, c->lm.n_ctx, c->l_ids, c->l_pos);
-            HIPCHK(hipGetLastError());
+            if (hipGetLastError() != hipSuccess) rc = set_err("%s: llama_advance_rows_kernel did not launch", what);
         }
-        HIPCHK(hipMemcpyAsync(g.h_state, g.state, (size_t) g.n_slots * LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t s : g.rows) {
-            const uint32_t *h = g.h_state + (size_t) s * LLAMA_SLOT_STATE;
+        g.in_flight = i + 1; g.unread += 1;   // also when the step was enqueued in part: the look-in that follows waits for it
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+// The look-in half: one llama_loop_lookin_kernel launch (none when nothing is taken), one copy into pinned memory, one synchronise, whatever the slot count.  The slots' state
+// becomes the host's; slots that finished are ENDED afterwards and have left the rows of the next run.  tokens_out != NULL ([n_slots][max_new])
+// takes each occupant's ids that no earlier look-in took, at their places; n_out / done (may be NULL): ids so far / no longer live.
+static int llama_loop_look(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done) {
+    auto &g = c->ls;
+    HIPCHK(hipSetDevice(c->device));
+    const int take = tokens_out ? 1 : 0;
+    // an occupant's un-taken ids: one per step enqueued since the last look-in that took ids, plus the one its admission selected
+    const uint32_t cap = take ? std::min(g.unread + 1, g.max_new) : 0u;
+    const size_t stride = LLAMA_SLOT_STATE + (size_t) cap;
+    if (take) {
+        hipLaunchKernelGGL(llama_loop_lookin_kernel, dim3(g.n_slots), dim3(64), 0, c->stream, (int) g.n_slots, take, cap, g.max_new, (const uint32_t *) g.state,
+                           (const uint32_t *) g.tokens, g.d_handed, g.look);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(g.h_look, g.look, (size_t) g.n_slots * stride * 4, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        // nothing to gather: a block of headers alone is the state array itself, copied as a run has always copied it
+        HIPCHK(hipMemcpyAsync(g.h_look, g.state, (size_t) g.n_slots * LLAMA_SLOT_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    g.in_flight = 0;
+    for (uint32_t s = 0; s < g.n_slots; s++) {
+        const uint32_t *h = g.h_look + (size_t) s * stride;
+        if (g.slot[s] == LS::LIVE) {
             g.count[s] = h[0]; g.cur[s] = h[2]; g.pos[s] = h[3];
             if (h[1]) g.slot[s] = LS::ENDED;
         }
+        const bool occupied = g.slot[s] != LS::FREE && g.max_new != 0;   // a free slot's block holds what its last occupant left
+        if (take && occupied) {
+            const uint32_t from = g.handed[s], to = std::min(g.count[s], g.max_new);
+            const uint32_t ids = to > from ? std::min(to - from, cap) : 0u;   // as the kernel counts them
+            if (ids) memcpy(tokens_out + (size_t) s * g.max_new + from, h + LLAMA_SLOT_STATE, (size_t) ids * 4);
+            g.handed[s] = from + ids;
+        }
+        if (n_out) n_out[s] = occupied ? g.count[s] : 0u;
+        if (done) done[s] = g.slot[s] != LS::LIVE;
     }
+    if (take) g.unread = 0;
     llama_loop_live_rows(c);
     return 0;
+}
+
+// A run: launch, then a look-in that takes nothing.  With no live row nothing is launched and nothing is looked at.
+static int llama_loop_run(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
+    const int rc = llama_loop_launch(c, what, n_steps);
+    if (c->ls.in_flight) {
+        const int rl = llama_loop_look(c, nullptr, nullptr, nullptr);
+        return rc ? rc : rl;
+    }
+    llama_loop_live_rows(c);
+    return rc;
 }
 
 // ---- the fixed batch: slots 0 .. n_utt-1, all admitted at begin; every utterance takes sp (NULL: sampler::max) and its row of uniforms [n_utt][max_new] ----
@@ -935,6 +996,7 @@ static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint
     auto &g = c->ls;
     if (mixed != g.mixed)
         return set_err(g.mixed ? "%s: the session carries a sampler per slot (tts_hip_orpheus_stream_admit_mixed)" : "%s: the session has one sampler (tts_hip_orpheus_stream_admit)", what);
+    CHK(llama_stream_idle(c, what));
     if (n == 0) return 0;
     if (!slots || !prompts || !n_prompt) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_new]", what);
@@ -975,13 +1037,10 @@ extern "C" int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, co
     return llama_stream_admit(c, "tts_hip_orpheus_stream_admit_mixed", true, n, slots, prompts, n_prompt, sampling, uniforms);
 }
 
-extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
-    const char *what = "tts_hip_orpheus_stream_run";
-    CHK(llama_stream_ready(c, what));
+// slots a look-in saw finished and no call has reported yet, in slot order
+static void llama_stream_report(tts_hip_ctx *c, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
     auto &g = c->ls;
-    if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
     *n_finished = 0;
-    CHK(llama_loop_run(c, what, n_steps));
     for (uint32_t s = 0; s < g.n_slots; s++) {
         if (g.slot[s] != LS::ENDED) continue;
         finished_slots[*n_finished] = s;
@@ -989,12 +1048,61 @@ extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint
         (*n_finished)++;
         g.slot[s] = LS::REPORTED;
     }
+}
+
+extern "C" int tts_hip_orpheus_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    const char *what = "tts_hip_orpheus_stream_launch";
+    CHK(llama_stream_ready(c, what));
+    CHK(llama_stream_idle(c, what));
+    return llama_loop_launch(c, what, n_steps);
+}
+
+extern "C" int tts_hip_orpheus_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                                           uint32_t *finished_counts) {
+    const char *what = "tts_hip_orpheus_stream_wait";
+    CHK(llama_stream_ready(c, what));
+    if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    CHK(llama_loop_look(c, tokens_out, n_out, done));
+    llama_stream_report(c, n_finished, finished_slots, finished_counts);
+    return 0;
+}
+
+// launch + a wait that takes nothing + the report
+extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
+    const char *what = "tts_hip_orpheus_stream_run";
+    CHK(llama_stream_ready(c, what));
+    if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    CHK(llama_stream_idle(c, what));
+    CHK(llama_loop_run(c, what, n_steps));
+    llama_stream_report(c, n_finished, finished_slots, finished_counts);
+    return 0;
+}
+
+// Live slots leave the session without a report.  The rows of a run are staged from the host's state, so nothing is launched: the slot is gone from
+// the next run's rows, and what it left on the device is rewritten by the next admission.
+extern "C" int tts_hip_orpheus_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
+    const char *what = "tts_hip_orpheus_stream_drop";
+    CHK(llama_stream_ready(c, what));
+    CHK(llama_stream_idle(c, what));
+    auto &g = c->ls;
+    if (n == 0) return 0;
+    if (!slots) return set_err("%s: null argument", what);
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
+        if (g.slot[slots[i]] != LS::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
+    }
+    for (uint32_t i = 0; i < n; i++) g.slot[slots[i]] = LS::FREE;
+    llama_loop_live_rows(c);
     return 0;
 }
 
 extern "C" int tts_hip_orpheus_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t count, uint32_t *tokens_out) {
     const char *what = "tts_hip_orpheus_stream_collect";
     CHK(llama_stream_ready(c, what));
+    CHK(llama_stream_idle(c, what));
     auto &g = c->ls;
     if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
     if (g.slot[slot] != LS::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_orpheus_stream_run reports it)", what, slot);
@@ -1012,7 +1120,8 @@ extern "C" int tts_hip_orpheus_stream_end(tts_hip_ctx *c) {
     if (!c || !c->has_llama) return set_err("tts_hip_orpheus_stream_end: not an Orpheus context (tts_hip_orpheus_create)");
     if (c->ls.mode != LS::SESSION) return 0;
     (void) hipSetDevice(c->device);
-    (void) hipStreamSynchronize(c->stream);
+    (void) hipStreamSynchronize(c->stream);   // also the steps of a launch nobody waited for
+    c->ls.in_flight = 0;
     c->ls.mode = LS::NONE;
     return 0;
 }

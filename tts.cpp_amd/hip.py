@@ -94,6 +94,7 @@ EXPORTS = [
     "tts_hip_orpheus_stream_begin", "tts_hip_orpheus_stream_admit", "tts_hip_orpheus_stream_run", "tts_hip_orpheus_stream_collect", "tts_hip_orpheus_stream_end",
     "tts_hip_orpheus_sample_logits_rows",
     "tts_hip_orpheus_stream_begin_mixed", "tts_hip_orpheus_stream_admit_mixed", "tts_hip_orpheus_sample_logits_rows_mixed",
+    "tts_hip_orpheus_stream_launch", "tts_hip_orpheus_stream_wait", "tts_hip_orpheus_stream_drop",
     "tts_hip_dia_gen_begin", "tts_hip_dia_gen_launch", "tts_hip_dia_gen_wait",
     "tts_hip_dia_stream_begin", "tts_hip_dia_stream_admit", "tts_hip_dia_stream_run", "tts_hip_dia_stream_collect", "tts_hip_dia_stream_end",
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
@@ -211,6 +212,9 @@ def load_lib():
     L.tts_hip_orpheus_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
     L.tts_hip_orpheus_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
     L.tts_hip_orpheus_stream_end.argtypes = [vp]
+    L.tts_hip_orpheus_stream_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_orpheus_stream_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p, u32p, u32p]
+    L.tts_hip_orpheus_stream_drop.argtypes = [vp, C.c_uint32, u32p]
     L.tts_hip_orpheus_sample_logits_rows.argtypes = [vp, C.c_uint32, f32p, C.POINTER(Sampling), f32p, C.POINTER(C.c_int32), u32p, u32p]
     L.tts_hip_orpheus_stream_begin_mixed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
     L.tts_hip_orpheus_stream_admit_mixed.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.POINTER(Sampling)), f32p]
@@ -940,6 +944,7 @@ class OrpheusEngine:
         """a session whose slots carry their own sampler (stream_admit_mixed); run / collect / end as for stream_begin"""
         self._chk(self.L.tts_hip_orpheus_stream_begin_mixed(self.ctx, n_slots, max_new, stop_id))
         self._stream = (n_slots, max_new)
+        self._stream_out = None
 
     def stream_admit_mixed(self, slots, prompts, settings, uniforms=None):
         """settings: per utterance None (greedy) or a dict of top_k / temperature / repetition_penalty / top_p; uniforms [n][max_new] (a greedy
@@ -958,6 +963,7 @@ class OrpheusEngine:
         sp = Sampling(top_k, top_p, temperature, repetition_penalty)
         self._chk(self.L.tts_hip_orpheus_stream_begin(self.ctx, n_slots, max_new, stop_id, C.byref(sp) if sampled else None))
         self._stream = (n_slots, max_new)
+        self._stream_out = None
 
     def stream_admit(self, slots, prompts, uniforms=None):
         """prompts: one id list per slot; uniforms [n][max_new] for a sampled session"""
@@ -981,6 +987,32 @@ class OrpheusEngine:
         out = np.zeros(max(count, 1), dtype=np.uint32)
         self._chk(self.L.tts_hip_orpheus_stream_collect(self.ctx, slot, count, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out[:count].copy()
+
+    def stream_launch(self, n_steps):
+        """tts_hip_orpheus_stream_launch: what stream_run enqueues, without waiting; stream_wait must follow"""
+        self._chk(self.L.tts_hip_orpheus_stream_launch(self.ctx, n_steps))
+
+    def stream_wait(self, take=True, out=None):
+        """-> (tokens [n_slots][max_new] as handed out so far (a view; a slot's ids start at 0 again with its next occupant), id count per slot,
+        ended per slot, [(slot, id count)] of the slots that finished); take=False looks in without taking ids.  out: the caller's uint32
+        array [n_slots][max(max_new, 1)] to write the ids into (default: one the engine keeps for the session)"""
+        cap, max_new = self._stream
+        if out is None:
+            if self._stream_out is None:
+                self._stream_out = np.zeros((cap, max(max_new, 1)), dtype=np.uint32)
+            out = self._stream_out
+        assert out.dtype == np.uint32 and out.shape == (cap, max(max_new, 1)) and out.flags.c_contiguous
+        cnt, done = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint8)
+        fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
+        u32 = C.POINTER(C.c_uint32)
+        self._chk(self.L.tts_hip_orpheus_stream_wait(self.ctx, out.ctypes.data_as(u32) if take else None, cnt.ctypes.data_as(u32), done.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                     C.byref(n), fs.ctypes.data_as(u32), fn.ctypes.data_as(u32)))
+        return out, cnt, done.astype(bool), [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_drop(self, slots):
+        """tts_hip_orpheus_stream_drop: live slots leave the session at once; they are free again without being reported"""
+        s, sp = _u32(slots)
+        self._chk(self.L.tts_hip_orpheus_stream_drop(self.ctx, s.size, sp))
 
     def stream_end(self):
         self._chk(self.L.tts_hip_orpheus_stream_end(self.ctx))

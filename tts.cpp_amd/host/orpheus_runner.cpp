@@ -71,7 +71,7 @@ std::unique_ptr<tts_generation_runner> orpheus_model_loader::from_file(gguf_file
 }
 
 orpheus_runner::orpheus_runner(const orpheus_hparams & hp_, bpe_tokenizer * tok, int device)
-    : tts_generation_runner{orpheus_loader}, hp(hp_), tokenizer(tok) {
+    : orpheus_session{orpheus_loader}, hp(hp_), tokenizer(tok) {
     tts_hip_orpheus_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = hp.hidden_size; d.n_layers = hp.n_layers; d.n_attn_heads = hp.n_attn_heads; d.n_kv_heads = hp.n_kv_attn_heads;
@@ -505,6 +505,33 @@ void orpheus_runner::stream_begin(const generation_configuration & config) {
     st_pcm.clear();
     st_live = 0;
     st_on = true;
+    st_chunk_frames = 0;
+    st_on_chunk = nullptr;
+}
+
+// chunked audio out of the session (common.h; the override is declared in orpheus_session.h)
+bool orpheus_session::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
+    if (!session_chunks_ready(chunk_frames)) return false;
+    st_chunk_frames = chunk_frames;
+    st_on_chunk = std::move(on_chunk);
+    return true;
+}
+
+bool orpheus_runner::session_chunks_ready(uint32_t) {
+    if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
+    if (st_live != 0) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
+    if (snac_halo < 0) return false;   // no window pass for this codec layout: whole utterances, as without the hook
+    const uint32_t slots = stream_capacity();
+    st_rows.assign(slots, {});
+    st_gen.assign(slots, 0);
+    st_buf.assign((size_t) slots * hp.max_generation_size, 0u);
+    st_pass = chunk_pass{};
+    st_pass_ticket.clear();
+    st_closing.clear();
+    st_stopped.clear();
+    last_batch_tokens.clear();
+    return true;
 }
 
 bool orpheus_runner::stream_accepts(const generation_configuration & config) const {
@@ -535,11 +562,115 @@ void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence, 
     st_free.pop_back();
     st_ticket[slot] = ticket;
     st_live++;
+    if (st_chunk_frames) {   // a new occupant: its ids and its chunker row start at zero
+        st_rows[slot] = {};
+        st_gen[slot] = 1;
+    }
+}
+
+void orpheus_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & ids) {
+    if (ticket < TOKEN_RECORD_TICKETS) {   // generate_stream_chunked's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
+        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
+        last_batch_tokens[ticket] = ids;
+    }
+    last_output_tokens = ids;
+    if (ids.size() >= hp.max_generation_size)
+        fprintf(stdout, "Warning: generation hit its max default length. The generated audio may not contain the entire prompt.\n");
+}
+
+// the windows the last look-in cut, through the codec in one pass and out chunk by chunk, each under the ticket it was cut for; then the utterances
+// that had ended at that look-in have had their last chunk.  An utterance whose callback returns false gets nothing more.
+void orpheus_runner::session_hand_out(std::vector<stream_result> & finished) {
+    const chunk_pass & P = st_pass;
+    if (!P.utt.empty()) {
+        pcm.resize(chunk_samples(P.keep0, P.keep1, hp.snac_up));
+        hip_check(tts_hip_snac_decode_windows_begin(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), (uint32_t) P.utt.size(),
+                                                    P.noise.empty() ? nullptr : P.noise.data(), pcm.data()), "tts_hip_snac_decode_windows");
+        hip_check(tts_hip_snac_decode_windows_end(snac), "tts_hip_snac_decode_windows");
+        const size_t per = (size_t) 4 * hp.snac_up;
+        size_t off = 0;
+        for (size_t i = 0; i < P.utt.size(); i++) {
+            const size_t ticket = st_pass_ticket[i];
+            uint32_t left = P.keep1[i] - P.keep0[i];
+            bool go_on = std::find(st_stopped.begin(), st_stopped.end(), ticket) == st_stopped.end();
+            while (left) {
+                const uint32_t k = std::min(left, st_chunk_frames);
+                if (go_on && !st_on_chunk(ticket, pcm.data() + off, k * per)) { go_on = false; st_stopped.push_back(ticket); }
+                off += k * per;
+                left -= k;
+            }
+        }
+    }
+    st_pass = chunk_pass{};
+    st_pass_ticket.clear();
+    for (size_t ticket : st_closing) {
+        stream_result r;
+        r.ticket = ticket;   // no audio: everything went through the hook
+        finished.push_back(r);
+        st_live--;
+    }
+    st_closing.clear();
+}
+
+// stream_step with the hook (orpheus_runner.h): the codec pass of the windows cut at the last look-in runs on the codec context while this
+// interval's decoder steps run on the decoder's.
+void orpheus_runner::stream_step_chunked(std::vector<stream_result> & finished) {
+    const uint32_t slots = stream_capacity(), M = hp.max_generation_size;
+    std::vector<uint32_t> fs(slots), fn(slots), cnt(slots);
+    std::vector<uint8_t> done(slots);
+    uint32_t nf = 0;
+    hip_check(tts_hip_orpheus_stream_launch(lm, ORPHEUS_STREAM_STEPS), "tts_hip_orpheus_stream_launch");
+    try {
+        session_hand_out(finished);
+    } catch (...) {
+        // an error (the codec refusing an id) or a throwing callback: the steps under way are waited for, so the decoder context stays usable
+        (void) tts_hip_orpheus_stream_wait(lm, nullptr, nullptr, nullptr, &nf, fs.data(), fn.data());
+        throw;
+    }
+    hip_check(tts_hip_orpheus_stream_wait(lm, st_buf.data(), cnt.data(), done.data(), &nf, fs.data(), fn.data()), "tts_hip_orpheus_stream_wait");
+    std::vector<uint32_t> drop;
+    std::vector<uint8_t> ended(slots, 0);
+    bool generating = false;
+    for (uint32_t s = 0; s < slots; s++) {
+        if (!st_gen[s]) continue;
+        chunk_state & row = st_rows[s];
+        const uint32_t * b = st_buf.data() + (size_t) s * M;
+        row.ids.insert(row.ids.end(), b + row.ids.size(), b + cnt[s]);
+        const bool stopped = std::find(st_stopped.begin(), st_stopped.end(), st_ticket[s]) != st_stopped.end();
+        if (!done[s] && !stopped) { generating = true; continue; }
+        // the occupant leaves: its ids are on the host, the slot is free for the next admission
+        remember_tokens(st_ticket[s], row.ids);
+        st_gen[s] = 0;
+        st_free.push_back(s);
+        if (stopped) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
+            if (!done[s]) drop.push_back(s);
+            row = {};
+            stream_result r;
+            r.ticket = st_ticket[s];
+            finished.push_back(r);
+            st_live--;
+        } else {
+            row.ended = true;
+            ended[s] = 1;
+            st_closing.push_back(st_ticket[s]);
+        }
+    }
+    st_stopped.clear();
+    if (!drop.empty()) hip_check(tts_hip_orpheus_stream_drop(lm, (uint32_t) drop.size(), drop.data()), "tts_hip_orpheus_stream_drop");
+    chunk_collect(st_rows, st_chunk_frames, st_pass);   // the noise draws: slot order, frames increasing
+    for (uint32_t s : st_pass.utt) st_pass_ticket.push_back(st_ticket[s]);
+    for (uint32_t s = 0; s < slots; s++)
+        if (ended[s]) st_rows[s] = {};   // its tail is in the windows
+    if (!generating) {   // nothing to run the codec under: the tails now
+        session_hand_out(finished);
+        st_stopped.clear();   // only utterances that had ended could be stopped here
+    }
 }
 
 void orpheus_runner::stream_step(std::vector<stream_result> & finished) {
     if (!st_on) TTS_ABORT("stream_step: no session (stream_begin)\n");
     finished.clear();
+    if (st_chunk_frames) return stream_step_chunked(finished);
     std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());
     uint32_t nf = 0;
     hip_check(tts_hip_orpheus_stream_run(lm, ORPHEUS_STREAM_STEPS, &nf, fs.data(), fn.data()), "tts_hip_orpheus_stream_run");
@@ -566,4 +697,10 @@ void orpheus_runner::stream_end() {
     st_on = false;
     st_free.clear();
     st_live = 0;
+    st_chunk_frames = 0;
+    st_on_chunk = nullptr;
+    st_pass = chunk_pass{};
+    st_pass_ticket.clear();
+    st_closing.clear();
+    st_stopped.clear();
 }

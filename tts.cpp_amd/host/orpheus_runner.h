@@ -14,6 +14,7 @@
 
 #include "../../include/tts_hip.h"
 #include "common.h"
+#include "orpheus_session.h"
 #include "sampler.h"
 #include "tokenizer.h"
 
@@ -40,7 +41,7 @@ struct orpheus_hparams {  // defaults = canopylabs/orpheus-3b (orpheus/model.h:2
     uint32_t snac_repeats[3] = {4, 2, 1};
 };
 
-struct orpheus_runner final : tts_generation_runner {
+struct orpheus_runner final : orpheus_session {
     orpheus_runner(const orpheus_hparams & hp, bpe_tokenizer * tok, int device);
     ~orpheus_runner() override;
 
@@ -76,6 +77,20 @@ struct orpheus_runner final : tts_generation_runner {
     void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
+    // extension: chunked audio out of the session (the hook is declared in orpheus_session.h).  With the hook set, a stream_step launches its 28
+    // decoder steps (tts_hip_orpheus_stream_launch), decodes the windows cut at the previous look-in in one tts_hip_snac_decode_windows_begin / _end
+    // pass on the codec context while they run (the windows of all slots in one pass), hands the chunks to on_chunk(ticket, ...), and then waits
+    // taking the new ids (tts_hip_orpheus_stream_wait).  Right after the wait the ids go to the slots' chunk_state and the next windows are cut, with
+    // slots as chunk_collect's rows: a slot whose occupant ended is free for the admission that precedes the next launch (stream_free() counts it
+    // from here on), so its tail has to be in the windows by then; the windows carry the ticket they were cut for.  An utterance appears in
+    // `finished`, with empty audio, once its last chunk is out, and stream_live() counts it until then.  When nothing generates after a wait, the
+    // tails are decoded in the same stream_step.  on_chunk returning false ends that utterance only: its slot is dropped after the next wait
+    // (tts_hip_orpheus_stream_drop) and it is reported with what it got.  last_output_tokens follows the utterances as they finish, and
+    // last_batch_tokens[ticket] keeps an utterance's ids for tickets below TOKEN_RECORD_TICKETS.
+    // The noise block: as in generate_chunked every frame is drawn once, frame-major, when it first enters a window.  The order of the draws across
+    // utterances is the order of chunk_collect: slot order within a look-in, frames increasing.  With TTS_SNAC_NO_NOISE the chunks concatenate to
+    // generate()'s PCM; a completed utterance consumes as many draws as its generate() would.
+    bool     session_chunks_ready(uint32_t chunk_frames) override;
     std::vector<std::string_view> list_voices() override;
 
     void decode_audio(const std::vector<uint32_t> & output_tokens, std::vector<float> & audio);   // prepare_output_tokens + SNAC
@@ -84,6 +99,10 @@ struct orpheus_runner final : tts_generation_runner {
     std::vector<std::vector<uint32_t>> prepare_output_tokens(const std::vector<uint32_t> & output_tokens) const;           // :358-376
     std::vector<uint32_t> last_prompt_tokens, last_output_tokens;
     std::vector<std::vector<uint32_t>> last_batch_tokens;   // generate_batch: the ids of every utterance
+    // The chunked session keeps an utterance's ids in last_batch_tokens[ticket] (a record for tests, read through tts_c_last_tokens(16 + ticket)) only
+    // for tickets below this bound.  A ticket is the caller's handle: generate_stream_chunked numbers its sentences from 0, which the record is for;
+    // a host with its own queue may use any size_t (a request id, a pointer), and the vector must not grow to it.  Other tickets keep no record.
+    static constexpr size_t TOKEN_RECORD_TICKETS = 4096;
 
     orpheus_hparams                hp;
     std::unique_ptr<bpe_tokenizer> tokenizer;
@@ -119,6 +138,17 @@ struct orpheus_runner final : tts_generation_runner {
     std::vector<uint32_t>           st_free;     // free cache slots
     std::vector<size_t>             st_ticket;   // slot -> ticket
     std::vector<std::vector<float>> st_pcm;      // audio handed out by the last stream_step
+    // ... with the chunk hook: the chunker's rows are the slots
+    std::vector<chunk_state>        st_rows;     // slot -> its occupant's ids and noise
+    std::vector<uint8_t>            st_gen;      // slot -> its occupant is still generating
+    std::vector<uint32_t>           st_buf;      // [slots][max_generation_size]: what the waits hand out
+    chunk_pass                      st_pass;     // the windows cut at the last look-in ...
+    std::vector<size_t>             st_pass_ticket;   // ... and the ticket each was cut for
+    std::vector<size_t>             st_closing;  // utterances that ended at the last look-in: their tails are in st_pass
+    std::vector<size_t>             st_stopped;  // utterances whose on_chunk returned false since the last look-in
+    void stream_step_chunked(std::vector<stream_result> & finished);
+    void session_hand_out(std::vector<stream_result> & finished);
+    void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
     bool device_sampler(const generation_configuration & config) const;
     void sampler_setup(const generation_configuration & config);
     std::vector<uint32_t> checked_prompt(const std::string & sentence, const generation_configuration & config);

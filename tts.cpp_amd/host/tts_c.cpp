@@ -263,7 +263,9 @@ int tts_c_last_tokens(tts_c_runner * r, int which, uint32_t * out, int cap) {
     if (auto * p = dynamic_cast<parler_runner *>((tts_generation_runner *) r))
         vp = which == 0 ? &p->last_prompt_tokens : (which == 2 ? &p->last_conditional_tokens : &p->last_output_tokens);
     else if (auto * o = dynamic_cast<orpheus_runner *>((tts_generation_runner *) r))
-        vp = which == 0 ? &o->last_prompt_tokens : (which == 1 ? &o->last_output_tokens : &none);
+        vp = which == 0 ? &o->last_prompt_tokens
+           : which == 1 ? &o->last_output_tokens
+           : which >= 16 && (size_t) (which - 16) < o->last_batch_tokens.size() ? &o->last_batch_tokens[(size_t) (which - 16)] : &none;
     else if (auto * d = dynamic_cast<dia_runner *>((tts_generation_runner *) r))
         vp = which == 0 ? &d->last_prompt_tokens
            : which == 1 ? &d->last_output_tokens
