@@ -87,9 +87,15 @@ int           tts_c_generate_batch_chunked(tts_c_runner *r, const char *const *t
  * Orpheus' session chunks the same way: chunk_frames counts SNAC frames, the windows of all slots go through one SNAC window pass under the next
  * 28 decoder steps, and a dropped utterance's slot is freed at the next look-in; the SNAC noise block is drawn as for tts_c_generate_chunked
  * (frame by frame; across utterances in slot order within a look-in), so with TTS_SNAC_NO_NOISE the pieces concatenate to tts_c_generate's PCM.
- * Parler-TTS' session, and Kokoro's groups, hand each finished utterance out as one chunk. */
+ * Parler-TTS' session chunks the same way with TTS_PARLER_STREAM_CHUNKS=1 in the environment (an opt-in): the windows of all slots go through one
+ * DAC window pass under the next 32 decoder steps, and an utterance's slot is taken again only once its last piece is out.  Without the switch
+ * Parler-TTS' session, and always Kokoro's groups, hand each finished utterance out as one chunk. */
 int           tts_c_generate_stream_chunked(tts_c_runner *r, const char *const *texts, int n, const tts_c_config *cfg, uint32_t chunk_frames,
                                             tts_c_chunk_fn fn, void *user);
+/* tts_c_generate_stream_chunked with one configuration per text, cfgs[n], as tts_c_generate_stream_configs takes them: a session takes every
+ * following text whose configuration it accepts and is drained and reopened at the first one it cannot take. */
+int           tts_c_generate_stream_chunked_configs(tts_c_runner *r, const char *const *texts, const tts_c_config *cfgs, int n, uint32_t chunk_frames,
+                                                    tts_c_chunk_fn fn, void *user);
 /* Test hook: the Parler runner's un-delay rule (parler_undelay) on delayed tokens [n_steps][n_heads] — the codes of the kept frames that are
  * final after n_steps steps (finished != 0: the generation is over, every frame is judged).  out [frames][n_heads] may be NULL to count;
  * returns the number of frames. */
@@ -120,7 +126,9 @@ const char   *tts_c_last_error(void);
 /* ---- test hooks ---------------------------------------------------------------------------------- */
 /* which = 0: prompt ids of the last generate (tokenised + EOS); 1: sampled ids, still delayed
  * (pctx->output_tokens); Dia, 16 + i: the still-delayed ids of utterance i of the last generate_batch / generate_stream; Orpheus, 16 + i: the ids
- * of utterance i of the last generate_batch, or of the last generate_stream_chunked whose session chunked (i below 4096).
+ * of utterance i of the last generate_batch, or of the last generate_stream_chunked whose session chunked (i below 4096); Parler, 16 + i: the
+ * still-delayed ids of utterance i of the last generate_batch / generate_batch_chunked, or of the last generate_stream_chunked whose session
+ * chunked (i below 4096).
  * Returns the count (copies at most cap). */
 int tts_c_last_tokens(tts_c_runner *r, int which, uint32_t *out, int cap);
 /* unigram tokenizer from the GGUF vocabulary + EOS, as batch_from_sentence builds it (model.cpp:473-498); a GGUF with

@@ -725,8 +725,31 @@ const char *tts_hip_kclass_name(int kclass);
  *           uniforms [n][max_steps][heads] for a sampled stream (the host-drawn std::minstd_rand sequence of each utterance), else NULL
  *   run     n_steps lock-step decode steps over the live utterances; then *n_finished slots whose check_stopping() fired (EOS on every head,
  *           position == the cached positions, or max_steps reached) are reported with their step counts and become free
- *   collect the tokens [steps][heads] of a finished slot (before the slot is admitted again)
+ *           run is launch followed by a wait that takes no rows.
+ *   launch  what run enqueues — the rows staged (ids, positions, cache slots, step counters, padding rows), the same choice of step (arg-max,
+ *           sampled, mixed; with or without voices), the same captured graphs — and returns without synchronising.  A launch must be followed
+ *           by a wait.
+ *   wait    waits for the launched steps and looks in: the rows' state and steps_done come back, and a wait that takes rows adds one
+ *           parler_stream_lookin_kernel launch and one copy of its block into pinned memory, whatever n_slots is; one synchronise.
+ *           steps_done [n_slots] = decode steps each slot's occupant has recorded so far, done [n_slots] = the slot's check_stopping() has fired
+ *           (each may be NULL), the finished slots as run reports them, and — when tokens_out != NULL — the token rows of every live or
+ *           just-finished slot that no earlier wait handed out, written at their places in tokens_out [n_slots][max_steps][heads]; rows above
+ *           steps_done are not touched (NULL: they stay for a later wait).  A slot that finishes inside an interval steps on to the interval's
+ *           end; only its rows below its step count are handed out.  A slot's rows start at 0 again once it is admitted again.  With nothing
+ *           launched a wait is a pure look-in.  The staging is sized by begin for 64 steps per slot: a wait that finds more enqueued since
+ *           the last wait that took rows goes round again, one launch, copy and synchronise per 64; no wait allocates.
+ *   drop    takes n live slots out at once, between a wait and the next launch.  The row list lives on the host and every launch stages it
+ *           afresh, so nothing runs on the device.  The slots are free again without being reported.
+ *   collect the tokens [steps][heads] of a finished slot (before the slot is admitted again); it works as before after waits that took rows
+ *   end     ends the session (steps in flight are waited for and dropped); so does the tts_hip_parler_gen_begin / generate_* that ends one
  * An utterance's tokens are those of a solo tts_hip_parler_generate_* run of the same prompt (tests/test_gpu_runner.py).
+ * The rows the waits hand out for an occupant tile its history without gap or overlap; they are what collect returns and what the same session
+ * returns through run / collect, whatever the launch sizes are — under the proviso below about row counts that select another GEMM tile shape —
+ * and dropping a slot changes no other slot's tokens (tests/test_gpu_parler_stream_chunked.py).
+ * Ordering: admit, admit_mixed, collect, drop, run or a second launch while steps are in flight return non-zero before anything is launched
+ * and leave the session as it was, and so do tts_hip_parler_voice_set and tts_hip_parler_seq_voices; so does a drop of a slot that is not
+ * live, is >= n_slots or is named twice.  tts_hip_dac_decode_windows stays callable between a launch and its wait: that is where the audio
+ * of the last look-in is decoded.
  * Mixed session: begin_mixed is begin with every slot carrying its own sampler, so utterances that differ in top_k, top_p, temperature or
  * repetition penalty, greedy ones among them, share one lock-step forward.  Its checks are begin's, and output_vocab_size <= 2048 also when every
  * occupant will be greedy.  It sizes, once, the uniforms [max_steps + 1][n_slots + 1][heads], a sampler record per slot {mode, top_k, top_p,
@@ -754,6 +777,10 @@ int tts_hip_parler_stream_begin_mixed(tts_hip_ctx *ctx, uint32_t n_slots, uint32
 int tts_hip_parler_stream_admit_mixed(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots, const uint32_t *ids, const uint32_t *lens,
                                       const tts_hip_sampling *const *sampling, const float *uniforms);
 int tts_hip_parler_stream_run(tts_hip_ctx *ctx, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps);
+int tts_hip_parler_stream_launch(tts_hip_ctx *ctx, uint32_t n_steps);
+int tts_hip_parler_stream_wait(tts_hip_ctx *ctx, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                               uint32_t *finished_steps);
+int tts_hip_parler_stream_drop(tts_hip_ctx *ctx, uint32_t n, const uint32_t *slots);
 int tts_hip_parler_stream_collect(tts_hip_ctx *ctx, uint32_t slot, uint32_t steps, uint32_t *tokens_out);
 int tts_hip_parler_stream_end(tts_hip_ctx *ctx);
 

@@ -1,0 +1,75 @@
+"""Chunked audio out of the Parler continuous session, without a device: the C ABI declares and exports the three new entry points, libtts.so
+calls them, hip.py binds them, every one answers a NULL context with an error that names it, the contract is written above
+tts_hip_parler_stream_begin, and the session's chunk hook is overridden in host/parler_session.h (parler_runner.h must not spell the hook:
+tests/test_parler_stream_mixed_cpu.py, tests/test_dia_stream_chunked_cpu.py)."""
+import ctypes as C
+import os
+import re
+
+from tts_cpp_amd import hip
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ["tts_hip_parler_stream_launch", "tts_hip_parler_stream_wait", "tts_hip_parler_stream_drop"]
+HOST = os.path.join(ROOT, "tts.cpp_amd", "host")
+
+
+def _without_comments(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
+def test_libraries_export_the_new_entry_points():
+    assert os.path.exists(hip.lib_path()), "libtts_hip.so not built (run __graft_entry__.build())"
+    L = C.CDLL(hip.lib_path())
+    for name in NAMES:
+        assert hasattr(L, name), f"{name} not exported"
+        assert name in hip.EXPORTS
+    host = os.path.join(HOST, "libtts.so")
+    assert os.path.exists(host), "libtts.so not built"
+    blob = open(host, "rb").read()
+    for name in NAMES:                                                  # the runner's session calls all three
+        assert name.encode() in blob, name
+
+
+def test_header_declares_them_and_states_the_contract():
+    hdr = _without_comments(os.path.join(ROOT, "include", "tts_hip.h"))
+    for name in NAMES:
+        assert re.search(r"\bint\s+%s\s*\(\s*tts_hip_ctx\s*\*" % name, hdr), f"{name} not declared"
+    full = open(os.path.join(ROOT, "include", "tts_hip.h")).read()
+    at = full.index("int tts_hip_parler_stream_begin(")
+    comment = full[full.rindex("/*", 0, at):at]
+    for word in ("launch", "wait", "drop", "without gap or overlap", "whatever the launch sizes", "in flight"):
+        assert word in comment, word
+
+
+def test_engine_has_the_methods():
+    for m in ("stream_launch", "stream_wait", "stream_drop"):
+        assert callable(getattr(hip.HipEngine, m, None)), m
+
+
+def test_new_entry_points_refuse_a_null_context():
+    L = hip.load_lib()
+    n = C.c_uint32()
+    buf = (C.c_uint32 * 4)()
+    assert L.tts_hip_parler_stream_launch(None, 1) != 0
+    assert b"null ctx" in L.tts_hip_last_error() and b"tts_hip_parler_stream_launch" in L.tts_hip_last_error()
+    assert L.tts_hip_parler_stream_wait(None, None, None, None, C.byref(n), buf, buf) != 0
+    assert b"tts_hip_parler_stream_wait" in L.tts_hip_last_error()
+    assert L.tts_hip_parler_stream_drop(None, 1, buf) != 0
+    assert b"tts_hip_parler_stream_drop" in L.tts_hip_last_error()
+
+
+def test_parler_session_header_declares_the_override():
+    """a Parler runner cannot be loaded without a device, so the override is checked where it is declared"""
+    session_h = open(os.path.join(HOST, "parler_session.h")).read()
+    assert re.search(r"\bbool\s+stream_chunks\([^;]*\)\s+override\s*;", session_h)
+    assert re.search(r"struct\s+parler_session\s*:\s*tts_generation_runner\b", session_h)
+    assert re.search(r"virtual\s+bool\s+session_chunks_ready\([^;]*\)\s*=\s*0\s*;", session_h)
+    runner_h = open(os.path.join(HOST, "parler_runner.h")).read()
+    assert '#include "parler_session.h"' in runner_h
+    assert re.search(r"struct\s+parler_runner\s+final\s*:\s*parler_session\b", runner_h)
+    assert "stream_chunks" not in runner_h
+    common = open(os.path.join(HOST, "common.h")).read()
+    at = common.index("virtual bool     stream_chunks(")
+    note = common[common.rindex("// chunked audio out of a session", 0, at):at]
+    assert "parler_session.h" in note and "no halo" in note and "TTS_PARLER_STREAM_CHUNKS" in note   # the runner's hook is an opt-in
+    assert re.search(r"does not chunk \(parler_runner\)", note)         # the literal tests/test_orpheus_stream_chunked_cpu.py reads stays

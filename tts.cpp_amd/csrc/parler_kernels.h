@@ -1434,6 +1434,7 @@ struct ParlerAdmitArgs {
     float *uni;               // [max_steps + 1][n_total][n_out] what sample_kernel reads
     uint8_t *eos_seen;        // [n_total][n_out]
     uint32_t *steps_done;     // [n_total]
+    uint32_t *handed;         // [n_total] rows parler_stream_lookin_kernel has handed out of the slot's occupant: the newcomer's start at 0
     int32_t *last;            // [n_total][n_out] sampler::last_token_ids
     uint32_t *repc;           // [n_total][n_out] sampler::repetition_counts
     const SampleRow *rec_in;  // [n]; pen_table already points at the slot's own table, or is NULL (penalty 1, or sampler::max)
@@ -1456,6 +1457,7 @@ static __global__ __launch_bounds__(256) void parler_stream_admit_kernel(ParlerA
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.steps_done[u] = 0;
+        a.handed[u] = 0;
         a.rec[u] = a.rec_in[i];
     }
     if (a.rec_in[i].pen_table)
@@ -1465,6 +1467,49 @@ static __global__ __launch_bounds__(256) void parler_stream_admit_kernel(ParlerA
     for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
         const int64_t k = e / a.n_out, h = e - k * a.n_out;
         a.uni[(k * a.n_total + u) * a.n_out + h] = a.uni_in[(int64_t) i * total + e];
+    }
+}
+
+// The look-in of a session wait that takes rows (tts_hip_parler_stream_wait): the token rows no earlier wait handed out, of every slot the host
+// names, into one dense block, so that the host gets them with one launch, one copy and one synchronisation however many slots there are.
+// The session's token buffer is step-major, [max_steps][n_total][n_out], and every slot sits at a step of its own: slot s's new rows are steps
+// [handed[s], to) with to = the steps it has recorded, or its steps_done once check_stopping() has fired (a slot that finishes inside an
+// interval keeps stepping to the interval's end; those rows are not handed out).  The buffer is contiguous along [slot][head] within a step and
+// strided by n_total * n_out words along a slot's steps, so a workgroup takes 256 / n_out entries of the host's list (ascending slots) and its
+// lanes walk consecutive [entry][head] words of one step at a time: neighbouring live slots are read as one run.  Each entry belongs to one
+// workgroup alone, which advances handed[s] after all its lanes have read it.
+struct ParlerLookArgs {
+    int n, n_total, n_out;       // entries; slots + the padding slot (the stride of tokens); heads
+    uint32_t cap;                // rows an entry holds in block: >= 1, the steps enqueued since the last wait that took rows at most
+    const uint32_t *look;        // [n][2] {slot < n_total - 1, steps the occupant has recorded so far <= max_steps}, ascending slots
+    const uint32_t *steps_done;  // [n_total]
+    const uint32_t *tokens;      // [max_steps][n_total][n_out]
+    uint32_t *handed;            // [n_total] rows handed out so far, reset by the admission
+    uint32_t *block;             // [n][2 + cap * n_out]: {steps so far (steps_done once finished), finished flag, the new rows}
+};
+
+static __global__ __launch_bounds__(256) void parler_stream_lookin_kernel(ParlerLookArgs a) {
+    const int per = 256 / a.n_out, e = (int) threadIdx.x / a.n_out, h = (int) threadIdx.x - e * a.n_out;
+    const int i = (int) blockIdx.x * per + e;
+    const bool on = e < per && i < a.n;
+    uint32_t slot = 0, from = 0, to = 0, rows = 0, done = 0;
+    uint32_t *dst = nullptr;
+    if (on) {
+        slot = a.look[2 * i];
+        const uint32_t sofar = a.look[2 * i + 1];
+        done = a.steps_done[slot];
+        to = done ? min(done, sofar) : sofar;
+        from = a.handed[slot];
+        rows = to > from ? min(to - from, a.cap) : 0u;
+        dst = a.block + (int64_t) i * (2 + (int64_t) a.cap * a.n_out);
+        const uint32_t *src = a.tokens + ((int64_t) from * a.n_total + slot) * a.n_out + h;
+        for (uint32_t j = 0; j < rows; j++) dst[2 + (int64_t) j * a.n_out + h] = src[(int64_t) j * a.n_total * a.n_out];
+    }
+    __syncthreads();   // every lane of the entry has read handed[slot]
+    if (on && h == 0) {
+        dst[0] = to;   // the host derives `rows` from it as this kernel does
+        dst[1] = done != 0;
+        a.handed[slot] = from + rows;
     }
 }
 

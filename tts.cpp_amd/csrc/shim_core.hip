@@ -267,6 +267,9 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     free_dev(c->di_suni);
     free_dev(c->di_srec); free_dev(c->di_srec_in); free_dev(c->di_spen); free_dev(c->di_spen_in);
     free_dev(c->gs_rec); free_dev(c->gs_rec_in); free_dev(c->gs_pen); free_dev(c->gs_pen_in); free_dev(c->gs_adm); free_dev(c->gs_uni_in);
+    free_dev(c->gs_handed); free_dev(c->gs_look_in); free_dev(c->gs_look);
+    if (c->h_gs_look_in) (void) hipHostFree(c->h_gs_look_in);
+    if (c->h_gs_look) (void) hipHostFree(c->h_gs_look);
     free_dev(c->di_e16);
     for (int i = 0; i < 3; i++) free_dev(c->sbuf[i]);
     free_dev(c->s_in); free_dev(c->s_out);

@@ -1190,6 +1190,7 @@ static int voices_ready(tts_hip_ctx *c, const char *who) {
     CHK(ready(c, who));
     if (!c->d.use_cross_attn) return set_err("%s: cross attention disabled", who);
     if (c->gl.active && c->gl.unwaited) return set_err("%s: steps in flight (between tts_hip_parler_gen_launch and its tts_hip_parler_gen_wait)", who);
+    if (c->gs.active && c->gs.unwaited) return set_err("%s: steps in flight (between tts_hip_parler_stream_launch and its tts_hip_parler_stream_wait)", who);
     return 0;
 }
 
@@ -1499,6 +1500,7 @@ static int gen_begin(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *start
         c->gen_total = (int) n;
         c->gs_graphs = false;
     }
+    if (c->gs.active && c->gs.unwaited) HIPCHK(hipStreamSynchronize(c->stream));   // steps of a session in flight: let them finish
     c->gs = tts_hip_ctx::GenStream{};   // a batch generation ends any stream of this context
     auto &g = c->gl;
     g.mode = mode; g.n = n; g.n_steps = n_steps; g.bos = bos; g.eos = eos; g.R = n;
@@ -1703,6 +1705,11 @@ extern "C" int tts_hip_parler_gen_wait(tts_hip_ctx *c, uint32_t *tokens_out, uin
 // An utterance's tokens do not depend on when it was admitted or on its neighbours: every kernel of the forward works row by row, and the
 // GEMM tile a row count selects is pinned by the row-count rounding (tests/test_gpu_runner.py: admitted mid-flight == solo run).
 // ------------------------------------------------------------------------------------------------
+// rows per slot the look-in's staging holds (parler_stream_lookin_kernel): two of the runner's 32-step look-ins; a wait that finds more steps
+// enqueued since the last taking wait goes round again
+static const uint32_t GS_LOOK_ROWS = 64;
+#define GS_IN_FLIGHT "%s: steps in flight (between tts_hip_parler_stream_launch and its tts_hip_parler_stream_wait)"
+
 // both begin calls.  mixed (sp NULL): every slot carries its own sampler record and penalty table [max_steps], sampler::max until an admission
 // writes them; the uniforms block and the sampler state exist whatever the occupants turn out to be.
 static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uint32_t n_slots, uint32_t max_steps, uint32_t bos, uint32_t eos, const tts_hip_sampling *sp) {
@@ -1712,9 +1719,28 @@ static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uin
     if (bos >= (uint32_t) c->EROWS || eos >= (uint32_t) c->EROWS) return set_err("stream_begin: bos/eos outside the embedding table");
     if (mixed && c->V > SMP_VMAX) return set_err("%s: output vocabulary %d > %d", what, c->V, SMP_VMAX);   // every row of a mixed step goes through sample_kernel
     auto &g = c->gs;
+    if (g.active && g.unwaited) HIPCHK(hipStreamSynchronize(c->stream));   // the session this one replaces still has steps in flight
     g = tts_hip_ctx::GenStream{};
     g.n_slots = n_slots; g.max_steps = max_steps; g.bos = bos; g.eos = eos; g.sampled = sp != nullptr;
     const uint32_t RT = n_slots + 1;
+    {   // the look-in's staging (parler_stream_lookin_kernel), once: no wait allocates
+        const size_t words = (size_t) n_slots * (2 + (size_t) std::min(max_steps, GS_LOOK_ROWS) * c->NO);
+        if ((size_t) RT > c->gs_look_slots || words > c->gs_look_words) {
+            const size_t ns = std::max((size_t) RT, c->gs_look_slots), nw = std::max(words, c->gs_look_words);
+            free_dev(c->gs_handed); free_dev(c->gs_look_in); free_dev(c->gs_look);
+            if (c->h_gs_look_in) (void) hipHostFree(c->h_gs_look_in);
+            if (c->h_gs_look) (void) hipHostFree(c->h_gs_look);
+            c->gs_handed = c->gs_look_in = c->gs_look = c->h_gs_look_in = c->h_gs_look = nullptr;
+            c->gs_look_slots = c->gs_look_words = 0;
+            HIPCHK(hipMalloc((void **) &c->gs_handed, ns * 4));
+            HIPCHK(hipMalloc((void **) &c->gs_look_in, ns * 2 * 4));
+            HIPCHK(hipMalloc((void **) &c->gs_look, nw * 4));
+            HIPCHK(hipHostMalloc((void **) &c->h_gs_look_in, ns * 2 * 4));
+            HIPCHK(hipHostMalloc((void **) &c->h_gs_look, nw * 4));
+            c->gs_look_slots = ns; c->gs_look_words = nw;
+        }
+        HIPCHK(hipMemsetAsync(c->gs_handed, 0, (size_t) RT * 4, c->stream));
+    }
     if (mixed) {
         // everything an admission writes into is sized here, once: no admission reallocates what a captured launch holds
         const size_t count = (size_t) (max_steps + 1) * RT * c->NO;
@@ -1780,6 +1806,7 @@ static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uin
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     g.slot_live.assign(n_slots, 0);
+    g.slot_sofar.assign(n_slots, 0u); g.slot_done.assign(n_slots, 0u); g.slot_handed.assign(n_slots, 0u); g.slot_pend.assign(n_slots, 0);
     g.active = true;
     return 0;
 }
@@ -1802,6 +1829,7 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
     if (mixed != g.mixed)
         return set_err(mixed ? "%s: the session was opened by tts_hip_parler_stream_begin (tts_hip_parler_stream_admit)"
                              : "%s: the session was opened by tts_hip_parler_stream_begin_mixed (tts_hip_parler_stream_admit_mixed)", what);
+    if (g.unwaited) return set_err(GS_IN_FLIGHT, what);
     if (n == 0) return 0;
     if (!slots || !ids || !lens) return set_err("stream_admit: null argument");
     if (g.sampled && !uniforms) return set_err("stream_admit: a sampled stream needs the utterances' uniforms [n][max_steps][heads]");
@@ -1896,7 +1924,7 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
         a.n = (int) n; a.n_total = (int) RT; a.n_out = c->NO; a.max_steps = g.max_steps;
         a.slots = c->gs_adm;
         a.uni_in = any_sampled ? c->gs_uni_in : nullptr; a.uni = c->d_uniforms;
-        a.eos_seen = c->d_eos; a.steps_done = c->d_steps_done; a.last = c->d_last; a.repc = c->d_repc;
+        a.eos_seen = c->d_eos; a.steps_done = c->d_steps_done; a.handed = c->gs_handed; a.last = c->d_last; a.repc = c->d_repc;
         a.rec_in = (const SampleRow *) c->gs_rec_in; a.rec = (SampleRow *) c->gs_rec; a.pen_in = c->gs_pen_in; a.pen = c->gs_pen; a.pen_len = len;
         const unsigned bx = any_sampled || any_rep ? (unsigned) std::min<size_t>((std::max(per, (size_t) len) + 255) / 256, 64) : 1u;
         hipLaunchKernelGGL(parler_stream_admit_kernel, dim3(bx, n), dim3(256), 0, c->stream, a);
@@ -1904,6 +1932,8 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
     }
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t s = slots[i];
+        g.slot_sofar[s] = g.slot_done[s] = g.slot_handed[s] = 0;   // the newcomer's rows start at 0; un-taken rows of the last occupant are gone
+        g.slot_pend[s] = 0;
         if (mixed) {
             g.slot_sampled[s] = sampling && sampling[i];
             g.slot_live[s] = 1;
@@ -1915,6 +1945,7 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
         }
         HIPCHK(hipMemsetAsync(c->d_eos + (size_t) s * c->NO, 0, (size_t) c->NO, c->stream));
         HIPCHK(hipMemsetAsync(c->d_steps_done + s, 0, 4, c->stream));
+        HIPCHK(hipMemsetAsync(c->gs_handed + s, 0, 4, c->stream));
         if (g.sampled) {
             if (c->smp.repetition_penalty != 1.0f) {   // sampler::reset for this utterance
                 HIPCHK(hipMemsetAsync(c->d_last + (size_t) s * c->NO, 0xFF, (size_t) c->NO * 4, c->stream));
@@ -1943,12 +1974,13 @@ extern "C" int tts_hip_parler_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, con
     return parler_stream_admit(c, "tts_hip_parler_stream_admit_mixed", true, n, slots, ids, lens, sampling, uniforms);
 }
 
-extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
-    CHK(ready(c, "tts_hip_parler_stream_run"));
+// The session's step in two halves (include/tts_hip.h), so that the host can decode audio under the steps: stream_launch stages the rows and
+// enqueues the steps, stream_wait reads the rows' state back, looks in, synchronises once and compacts the host's row list.  stream_run is the
+// one after the other.  Between the two, g.unwaited refuses everything that would touch the rows or the staging arrays.
+static int parler_stream_launch(tts_hip_ctx *c, const char *what, uint32_t n_steps) {
     auto &g = c->gs;
-    if (!g.active) return set_err("stream_run: no stream (tts_hip_parler_stream_begin)");
-    if (!n_finished || !finished_slots || !finished_steps) return set_err("stream_run: null argument");
-    *n_finished = 0;
+    if (!g.active) return set_err("%s: no stream (tts_hip_parler_stream_begin)", what);
+    if (g.unwaited) return set_err(GS_IN_FLIGHT, what);
     const uint32_t live = (uint32_t) g.row_slot.size();
     if (live == 0 || n_steps == 0) return 0;
     const uint32_t q = live >= 256 ? 128 : 64;
@@ -1974,29 +2006,161 @@ extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint3
     c->fwd_voices = false;   // of this run: chosen here, from the live slots, for all its steps
     for (uint32_t r = 0; r < live; r++) c->fwd_voices = c->fwd_voices || c->slot_voiced(g.row_slot[r]);
     const uint32_t max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS);
+    g.unwaited = true;
+    g.launched_live = live;
     for (uint32_t s = 0; s < n_steps; s++) {
         for (uint32_t r = 0; r < R; r++) c->host_pos[r] = r < live ? std::min(g.pos[r] + s, max_pos - 1) : 0;
         CHK(run_step(c, (int) R, mode, g.bos, g.eos));
     }
-    // the rows' state back to the host (the next admit's prefill reuses the device staging arrays), and who has finished
-    HIPCHK(hipMemcpyAsync(c->h_ids, c->d_ids, (size_t) live * NO * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_pos, c->d_pos, (size_t) live * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_seq, c->d_step, (size_t) live * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_tok, c->d_steps_done, (size_t) (g.n_slots + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<uint32_t> slot2, pos2, step2, ids2;
-    for (uint32_t r = 0; r < live; r++) {
-        const uint32_t sl = g.row_slot[r];
-        uint32_t done = c->h_tok[sl];
-        if (done) {
-            finished_slots[*n_finished] = sl;
-            finished_steps[*n_finished] = std::min(done, g.max_steps);
-            (*n_finished)++;
-            g.slot_live[sl] = 0;
-            continue;
+    // feed_kernel advances a row's step counter with every step until its budget is spent, whatever the row does: the rows a slot has recorded
+    // after these steps are known here, without a read
+    for (uint32_t r = 0; r < live; r++)
+        g.slot_sofar[g.row_slot[r]] = (uint32_t) std::min<uint64_t>((uint64_t) g.step[r] - 1 + n_steps, g.max_steps);
+    g.unread = (uint32_t) std::min<uint64_t>((uint64_t) g.unread + n_steps, g.max_steps);
+    return 0;
+}
+
+// One round of the look-in: the entries' rows [handed, min(to, handed + cap)) into tokens_out [n_slots][max_steps][heads].  The launch and the
+// copy are enqueued by look_enqueue, the block is read after the synchronise by look_scatter.
+static int parler_look_enqueue(tts_hip_ctx *c, uint32_t n_look, uint32_t cap) {
+    auto &g = c->gs;
+    ParlerLookArgs a{};
+    a.n = (int) n_look; a.n_total = (int) g.n_slots + 1; a.n_out = c->NO; a.cap = cap;
+    a.look = c->gs_look_in; a.steps_done = c->d_steps_done; a.tokens = c->d_tokens_out; a.handed = c->gs_handed; a.block = c->gs_look;
+    const int per = 256 / c->NO;
+    hipLaunchKernelGGL(parler_stream_lookin_kernel, dim3((n_look + per - 1) / per), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_gs_look, c->gs_look, (size_t) n_look * (2 + (size_t) cap * c->NO) * 4, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+static void parler_look_scatter(tts_hip_ctx *c, uint32_t n_look, uint32_t cap, uint32_t *tokens_out) {
+    auto &g = c->gs;
+    const size_t ent = 2 + (size_t) cap * c->NO;
+    for (uint32_t i = 0; i < n_look; i++) {
+        const uint32_t *b = c->h_gs_look + (size_t) i * ent;
+        const uint32_t sl = c->h_gs_look_in[2 * i], from = g.slot_handed[sl], to = b[0];
+        const uint32_t rows = to > from ? std::min(to - from, cap) : 0u;
+        if (rows) memcpy(tokens_out + ((size_t) sl * g.max_steps + from) * c->NO, b + 2, (size_t) rows * c->NO * 4);
+        g.slot_handed[sl] = from + rows;
+    }
+}
+
+static int parler_stream_wait(tts_hip_ctx *c, const char *what, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished,
+                              uint32_t *finished_slots, uint32_t *finished_steps) {
+    auto &g = c->gs;
+    if (!g.active) return set_err("%s: no stream (tts_hip_parler_stream_begin)", what);
+    if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
+    *n_finished = 0;
+    const int NO = c->NO;
+    const bool in_flight = g.unwaited;
+    const uint32_t live = in_flight ? g.launched_live : 0u;
+    if (in_flight) {
+        // the rows' state back to the host (the next admit's prefill reuses the device staging arrays), and who has finished
+        HIPCHK(hipMemcpyAsync(c->h_ids, c->d_ids, (size_t) live * NO * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_pos, c->d_pos, (size_t) live * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_seq, c->d_step, (size_t) live * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_tok, c->d_steps_done, (size_t) (g.n_slots + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    // The look-in, only for a wait that takes rows: what a wait reports besides the rows (steps so far, finished) the host has from the copies
+    // above and its own count, so a session nobody takes rows from steps exactly as tts_hip_parler_stream_run always did.  The slots to look at
+    // are the live ones and those that finished with rows no wait has taken yet, in ascending order.
+    uint32_t n_look = 0, cap = 0;
+    if (tokens_out && g.unread) {
+        for (uint32_t s = 0; s < g.n_slots; s++)
+            if (g.slot_live[s] || g.slot_pend[s]) { c->h_gs_look_in[2 * n_look] = s; c->h_gs_look_in[2 * n_look + 1] = g.slot_sofar[s]; n_look++; }
+        if (n_look) {
+            cap = std::min(g.unread, GS_LOOK_ROWS);
+            HIPCHK(hipMemcpyAsync(c->gs_look_in, c->h_gs_look_in, (size_t) n_look * 2 * 4, hipMemcpyHostToDevice, c->stream));
+            CHK(parler_look_enqueue(c, n_look, cap));
         }
-        slot2.push_back(sl); pos2.push_back(c->h_pos[r]); step2.push_back(c->h_seq[r]);
-        ids2.insert(ids2.end(), c->h_ids + (size_t) r * NO, c->h_ids + (size_t) (r + 1) * NO);
+    }
+    if (in_flight || n_look) HIPCHK(hipStreamSynchronize(c->stream));
+    g.unwaited = false;
+    if (in_flight) {
+        std::vector<uint32_t> slot2, pos2, step2, ids2;
+        for (uint32_t r = 0; r < live; r++) {
+            const uint32_t sl = g.row_slot[r];
+            uint32_t fin = c->h_tok[sl];
+            if (fin) {
+                finished_slots[*n_finished] = sl;
+                finished_steps[*n_finished] = std::min(fin, g.max_steps);
+                (*n_finished)++;
+                g.slot_live[sl] = 0;
+                g.slot_done[sl] = std::min(fin, g.max_steps);
+                g.slot_pend[sl] = 1;
+                continue;
+            }
+            slot2.push_back(sl); pos2.push_back(c->h_pos[r]); step2.push_back(c->h_seq[r]);
+            ids2.insert(ids2.end(), c->h_ids + (size_t) r * NO, c->h_ids + (size_t) (r + 1) * NO);
+        }
+        g.row_slot.swap(slot2); g.pos.swap(pos2); g.step.swap(step2); g.ids.swap(ids2);
+    }
+    if (n_look) {
+        parler_look_scatter(c, n_look, cap, tokens_out);
+        // more steps were enqueued since the last taking wait than the staging holds rows for: further rounds over the same entries
+        for (uint32_t left = g.unread - cap; left > 0; left -= cap) {
+            cap = std::min(left, GS_LOOK_ROWS);
+            CHK(parler_look_enqueue(c, n_look, cap));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            parler_look_scatter(c, n_look, cap, tokens_out);
+        }
+        for (uint32_t i = 0; i < n_look; i++) {
+            const uint32_t sl = c->h_gs_look_in[2 * i];
+            if (g.slot_done[sl] && g.slot_handed[sl] >= g.slot_done[sl]) g.slot_pend[sl] = 0;   // the whole utterance is out
+        }
+    }
+    if (tokens_out) g.unread = 0;
+    for (uint32_t s = 0; s < g.n_slots; s++) {
+        if (steps_done) steps_done[s] = g.slot_done[s] ? g.slot_done[s] : g.slot_sofar[s];
+        if (done) done[s] = g.slot_done[s] != 0;
+    }
+    return 0;
+}
+
+extern "C" int tts_hip_parler_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
+    CHK(ready(c, "tts_hip_parler_stream_launch"));
+    return parler_stream_launch(c, "tts_hip_parler_stream_launch", n_steps);
+}
+
+extern "C" int tts_hip_parler_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *steps_done, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
+                                          uint32_t *finished_steps) {
+    CHK(ready(c, "tts_hip_parler_stream_wait"));
+    return parler_stream_wait(c, "tts_hip_parler_stream_wait", tokens_out, steps_done, done, n_finished, finished_slots, finished_steps);
+}
+
+// launch, then a wait that takes no rows: the look-in kernel never runs for a session that only uses this call
+extern "C" int tts_hip_parler_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
+    CHK(ready(c, "tts_hip_parler_stream_run"));
+    if (c->gs.active && (!n_finished || !finished_slots || !finished_steps)) return set_err("stream_run: null argument");
+    CHK(parler_stream_launch(c, "stream_run", n_steps));
+    return parler_stream_wait(c, "stream_run", nullptr, nullptr, nullptr, n_finished, finished_slots, finished_steps);
+}
+
+// Live slots out of the session between a wait and the next launch.  The row list lives on the host and every launch restages it, so nothing
+// runs on the device: the rows leave the list and the slots are free (an admission resets everything a slot's occupant left behind).
+extern "C" int tts_hip_parler_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
+    const char *who = "tts_hip_parler_stream_drop";
+    CHK(ready(c, who));
+    auto &g = c->gs;
+    if (!g.active) return set_err("%s: no stream (tts_hip_parler_stream_begin)", who);
+    if (g.unwaited) return set_err(GS_IN_FLIGHT, who);
+    if (n == 0) return 0;
+    if (!slots) return set_err("%s: null argument", who);
+    for (uint32_t i = 0; i < n; i++) {
+        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= %u", who, slots[i], g.n_slots);
+        if (!g.slot_live[slots[i]]) return set_err("%s: slot %u is not live", who, slots[i]);
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", who, slots[i]);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        g.slot_live[slots[i]] = 0;
+        g.slot_sofar[slots[i]] = g.slot_done[slots[i]] = 0;
+    }
+    const int NO = c->NO;
+    std::vector<uint32_t> slot2, pos2, step2, ids2;
+    for (size_t r = 0; r < g.row_slot.size(); r++) {
+        if (!g.slot_live[g.row_slot[r]]) continue;
+        slot2.push_back(g.row_slot[r]); pos2.push_back(g.pos[r]); step2.push_back(g.step[r]);
+        ids2.insert(ids2.end(), g.ids.begin() + (ptrdiff_t) (r * NO), g.ids.begin() + (ptrdiff_t) ((r + 1) * NO));
     }
     g.row_slot.swap(slot2); g.pos.swap(pos2); g.step.swap(step2); g.ids.swap(ids2);
     return 0;
@@ -2006,6 +2170,7 @@ extern "C" int tts_hip_parler_stream_collect(tts_hip_ctx *c, uint32_t slot, uint
     CHK(ready(c, "tts_hip_parler_stream_collect"));
     auto &g = c->gs;
     if (!g.active) return set_err("stream_collect: no stream");
+    if (g.unwaited) return set_err(GS_IN_FLIGHT, "tts_hip_parler_stream_collect");
     if (slot >= g.n_slots || steps > g.max_steps || !tokens_out) return set_err("stream_collect: slot %u / %u steps out of range", slot, steps);
     if (steps == 0) return 0;
     const size_t RT = g.n_slots + 1;
@@ -2016,6 +2181,10 @@ extern "C" int tts_hip_parler_stream_collect(tts_hip_ctx *c, uint32_t slot, uint
 
 extern "C" int tts_hip_parler_stream_end(tts_hip_ctx *c) {
     if (!c) return set_err("null ctx");
+    if (c->gs.active && c->gs.unwaited) {   // steps in flight: wait for them, then forget the session
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     c->gs = tts_hip_ctx::GenStream{};
     return 0;
 }

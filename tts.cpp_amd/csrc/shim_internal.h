@@ -346,7 +346,20 @@ struct tts_hip_ctx {
         std::vector<uint8_t> slot_live;
         std::vector<uint8_t> slot_sampled;   // mixed: the slot's occupant is sampled (a run whose live slots are all greedy replays MODE_GEN)
         std::vector<uint32_t> row_slot, pos, step, ids;   // live rows: cache slot, next position, step counter, next input ids [rows][heads]
+        // launch / wait / drop (audio in chunks while the slots keep running)
+        bool unwaited = false;           // a stream_launch has enqueued steps that no stream_wait has waited for
+        uint32_t launched_live = 0;      // live rows of that launch
+        uint32_t unread = 0;             // steps enqueued since the last wait that took rows: no slot holds more un-taken rows than this
+        std::vector<uint32_t> slot_sofar;   // [n_slots] steps the occupant has recorded (the step counter advances with every enqueued step: known without a read)
+        std::vector<uint32_t> slot_done;    // [n_slots] the occupant's steps_done once check_stopping() has fired (0: not yet), until the next admission
+        std::vector<uint32_t> slot_handed;  // [n_slots] host mirror of gs_handed: rows of the occupant a wait has handed out
+        std::vector<uint8_t> slot_pend;     // [n_slots] finished and reported, rows not all handed out yet (until taken, collected over by an admission, or dropped)
     } gs;
+    // the look-in of a session wait that takes rows (parler_stream_lookin_kernel): the slots to look at {slot, steps so far} go up from h_gs_look_in,
+    // one dense block [entries][2 + cap * heads] comes back into h_gs_look; sized by stream_begin for GS_LOOK_ROWS steps, no wait allocates
+    uint32_t *gs_handed = nullptr;       // device [slots + 1]: rows handed out per slot, reset by the admission
+    uint32_t *gs_look_in = nullptr, *gs_look = nullptr, *h_gs_look_in = nullptr, *h_gs_look = nullptr;
+    size_t gs_look_slots = 0, gs_look_words = 0;   // capacity: slots of gs_handed / gs_look_in, words of gs_look
     // a mixed session's sampler records and penalty tables, kept from one session to the next.  gs_rec [slots + 1] is what the captured
     // MODE_GEN_MIXED sample_kernel launch holds (the padding slot's record stays SAMPLE_ROW_MAX); the tables [slots][gs_pen_len] are reached
     // through the records' pointers.  The *_in copies and gs_adm / gs_uni_in stage one admission for parler_stream_admit_kernel.

@@ -100,6 +100,7 @@ EXPORTS = [
     "tts_hip_dia_stream_launch", "tts_hip_dia_stream_wait", "tts_hip_dia_stream_drop",
     "tts_hip_dia_stream_begin_mixed", "tts_hip_dia_stream_admit_mixed", "tts_hip_sample_logits_rows_mixed",
     "tts_hip_parler_stream_begin_mixed", "tts_hip_parler_stream_admit_mixed",
+    "tts_hip_parler_stream_launch", "tts_hip_parler_stream_wait", "tts_hip_parler_stream_drop",
     "tts_hip_parler_voice_bank", "tts_hip_parler_voice_set", "tts_hip_parler_seq_voices",
 ]
 
@@ -194,6 +195,9 @@ def load_lib():
     L.tts_hip_parler_stream_admit.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, f32p]
     L.tts_hip_parler_stream_run.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
     L.tts_hip_parler_stream_collect.argtypes = [vp, C.c_uint32, C.c_uint32, u32p]
+    L.tts_hip_parler_stream_launch.argtypes = [vp, C.c_uint32]
+    L.tts_hip_parler_stream_wait.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint8), u32p, u32p, u32p]
+    L.tts_hip_parler_stream_drop.argtypes = [vp, C.c_uint32, u32p]
     L.tts_hip_parler_stream_end.argtypes = [vp]
     L.tts_hip_parler_gen_begin.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Sampling), f32p]
     L.tts_hip_parler_gen_launch.argtypes = [vp, C.c_uint32]
@@ -459,6 +463,7 @@ class HipEngine:
         self._chk(self.L.tts_hip_parler_stream_begin(self.ctx, n_slots, max_steps, self.cfg.bos if bos is None else bos, self.cfg.eos if eos is None else eos,
                                                      C.byref(sp) if sp is not None else None))
         self._stream_slots = n_slots
+        self._stream_out = (np.zeros((n_slots, max_steps, self.cfg.n_out), dtype=np.uint32), np.zeros(n_slots, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint8))
 
     def stream_admit(self, slots, prompts, uniforms=None):
         s, sp = _u32(slots)
@@ -474,6 +479,7 @@ class HipEngine:
         """a session whose slots carry their own sampler (stream_admit_mixed); run / collect / end as for stream_begin"""
         self._chk(self.L.tts_hip_parler_stream_begin_mixed(self.ctx, n_slots, max_steps, self.cfg.bos if bos is None else bos, self.cfg.eos if eos is None else eos))
         self._stream_slots = n_slots
+        self._stream_out = (np.zeros((n_slots, max_steps, self.cfg.n_out), dtype=np.uint32), np.zeros(n_slots, dtype=np.uint32), np.zeros(n_slots, dtype=np.uint8))
 
     def stream_admit_mixed(self, slots, prompts, settings, uniforms=None):
         """stream_admit with settings per utterance: None (greedy) or a dict of top_k / top_p / temperature / repetition_penalty; uniforms
@@ -497,6 +503,26 @@ class HipEngine:
         fn = np.zeros(self._stream_slots, dtype=np.uint32)
         self._chk(self.L.tts_hip_parler_stream_run(self.ctx, n_steps, C.byref(n), fs.ctypes.data_as(C.POINTER(C.c_uint32)), fn.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_launch(self, n_steps):
+        """tts_hip_parler_stream_launch: what stream_run enqueues, without waiting; stream_wait must follow"""
+        self._chk(self.L.tts_hip_parler_stream_launch(self.ctx, n_steps))
+
+    def stream_wait(self, take=True):
+        """-> (tokens [n_slots][max_steps][n_out] as handed out so far (a view; a slot's rows start at 0 again with its next occupant), steps
+        recorded per slot, finished per slot, [(slot, steps)] of the slots that finished); take=False looks in without taking rows"""
+        out, steps, done = self._stream_out
+        cap = self._stream_slots
+        fs, fn, n = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), C.c_uint32()
+        u32 = C.POINTER(C.c_uint32)
+        self._chk(self.L.tts_hip_parler_stream_wait(self.ctx, out.ctypes.data_as(u32) if take else None, steps.ctypes.data_as(u32), done.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                    C.byref(n), fs.ctypes.data_as(u32), fn.ctypes.data_as(u32)))
+        return out, steps.copy(), done.astype(bool).copy(), [(int(fs[i]), int(fn[i])) for i in range(n.value)]
+
+    def stream_drop(self, slots):
+        """tts_hip_parler_stream_drop: live slots out of the session at once; they are free again without being reported"""
+        s, sp = _u32(slots)
+        self._chk(self.L.tts_hip_parler_stream_drop(self.ctx, s.size, sp))
 
     def stream_collect(self, slot, steps):
         out = np.zeros((steps, self.cfg.n_out), dtype=np.uint32)

@@ -152,7 +152,9 @@ struct tts_generation_runner : tts_runner {
     // utterance's PCM to on_chunk(ticket, pcm, n) in consecutive pieces of at most chunk_frames codec frames while the rows keep running; an
     // utterance appears in `finished` — with empty audio — once its last piece is out, and stream_live() counts it until then.  on_chunk
     // returning false drops that utterance only: it is reported in `finished` with what it got, the others go on.  The default returns false:
-    // this runner's session does not chunk (parler_runner); dia_runner's and orpheus_runner's do (orpheus_runner: chunk_frames counts SNAC
+    // this runner's session does not chunk (parler_runner) holds for a Parler codec layout that reports no halo and, by default, for every
+    // other: its override, declared in parler_session.h, chunks when TTS_PARLER_STREAM_CHUNKS is set in the environment (an opt-in: the
+    // whole-utterance answer stays the default), and a slot of its session is then free again only once its occupant's last piece is out.  dia_runner's and orpheus_runner's chunk too (orpheus_runner: chunk_frames counts SNAC
     // frames, the override is declared in orpheus_session.h; its SNAC noise block is drawn frame-major as in generate_chunked, across
     // utterances in slot order within a look-in).
     virtual bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t ticket, const float *, size_t)> on_chunk);
@@ -160,6 +162,9 @@ struct tts_generation_runner : tts_runner {
     // none (kokoro_runner), each finished utterance is handed out as one chunk, the default generate_chunked has.  chunk_frames == 0 is an error.
     void             generate_stream_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
                                              const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
+    // one configuration per sentence, taken into sessions as generate_stream with configurations takes them
+    void             generate_stream_chunked(const std::vector<std::string> & sentences, const std::vector<generation_configuration> & configs,
+                                             uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
 
     // ---- extension: chunked audio — PCM handed out while the utterance is still generating ------------------------------------------
     // on_chunk receives consecutive pieces of the utterance's audio, at most chunk_frames codec frames each (the last one may be shorter);

@@ -199,6 +199,45 @@ void tts_generation_runner::generate_stream_chunked(const std::vector<std::strin
     stream_end();
 }
 
+// ... with one configuration per sentence: generate_stream's sessions (one takes every following sentence it accepts), each with the chunk hook
+void tts_generation_runner::generate_stream_chunked(const std::vector<std::string> & sentences, const std::vector<generation_configuration> & configs,
+                                                    uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
+    if (configs.size() != sentences.size()) TTS_ABORT("generate_stream_chunked: %zu configurations for %zu sentences\n", configs.size(), sentences.size());
+    if (chunk_frames == 0) TTS_ABORT("generate_stream_chunked: chunk_frames must be >= 1\n");
+    const size_t n = sentences.size();
+    size_t next = 0;
+    while (next < n) {
+        const size_t first = next;
+        if (stream_capacity() == 0) {   // no session: the run of equal configurations through the one-configuration loop
+            while (next < n && same_generation_configuration(configs[next], configs[first])) next++;
+            const std::vector<std::string> part(sentences.begin() + first, sentences.begin() + next);
+            generate_stream_chunked(part, configs[first], chunk_frames, [&](uint32_t i, const float * pcm, size_t k) { return on_chunk((uint32_t) (first + i), pcm, k); });
+            continue;
+        }
+        stream_begin(configs[first]);
+        bool more = true;   // the next sentence may still enter this session
+        std::vector<stream_result> fin;
+        try {
+            const bool chunks = stream_chunks(chunk_frames, [&](size_t ticket, const float * pcm, size_t k) { return on_chunk((uint32_t) ticket, pcm, k); });
+            while (true) {
+                while (more && next < n && stream_free() > 0) {
+                    more = same_generation_configuration(configs[next], configs[first]) || stream_accepts(configs[next]);
+                    if (more) { stream_submit(next, sentences[next], configs[next]); next++; }
+                }
+                if (stream_live() == 0) break;
+                stream_step(fin);
+                if (chunks) continue;   // everything went through the hook
+                for (auto & f : fin)
+                    if (f.audio.n_outputs) (void) on_chunk((uint32_t) f.ticket, f.audio.data, f.audio.n_outputs);
+            }
+        } catch (...) {   // a request the session refuses fails the call (where aborts throw), not the runner: the session does not stay open
+            stream_end();
+            throw;
+        }
+        stream_end();
+    }
+}
+
 // ---- "test:dummy": weightless plumbing backend (src/models/dummy/model.cpp:6-19) ----------------------
 namespace {
 struct dummy_loader_t final : tts_model_loader {

@@ -64,7 +64,7 @@ std::unique_ptr<tts_generation_runner> parler_model_loader::from_file(gguf_file 
 }
 
 parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok, int device, bool cross)
-    : tts_generation_runner{parler_loader}, hp(hp_), tokenizer(tok), use_cross_attn(cross), device_id(device) {
+    : parler_session{parler_loader}, hp(hp_), tokenizer(tok), use_cross_attn(cross), device_id(device) {
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = hp.hidden_size; d.n_layers = hp.n_layers; d.n_attn_heads = hp.n_attn_heads;
@@ -596,6 +596,44 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     st_live = 0;
     st_codec_held = 0;
     st_on = true;
+    st_chunk_frames = 0;
+    st_on_chunk = nullptr;
+    st_hook.reset();
+}
+
+// chunked audio out of the session (common.h; the override is declared in parler_session.h)
+bool parler_session::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
+    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
+    if (!session_chunks_ready(chunk_frames)) return false;
+    st_chunk_frames = chunk_frames;
+    st_on_chunk = std::move(on_chunk);
+    return true;
+}
+
+bool parler_runner::session_chunks_ready(uint32_t chunk_frames) {
+    if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
+    if (st_live != 0 || !st_wait.empty() || !st_codec.empty()) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
+    if (dac_halo < 0) return false;   // no window pass for this codec layout: whole utterances, as without the hook
+    // Opt-in (TTS_PARLER_STREAM_CHUNKS, read here like TTS_HOST_LOOP in run_rows): without it generate_stream_chunked on a Parler runner keeps
+    // handing each finished utterance out as one chunk, out of the codec groups of 64, which callers and tests/test_gpu_dia_stream_chunked.py rely on
+    const char * on = getenv("TTS_PARLER_STREAM_CHUNKS");
+    if (!on || !*on || !strcmp(on, "0")) return false;
+    const uint32_t slots = stream_capacity();
+    // the chunker calls back with the window's row, here the slot: the slot keeps its ticket until its last piece is out.  One utterance's
+    // "stop" must not end the others' chunks, so the chunker always hears "go on" and the slot is remembered instead.
+    st_slot_chunk = [this](uint32_t slot, const float * p, size_t k) {
+        if (!st_stopped[slot] && !st_on_chunk(st_ticket[slot], p, k)) st_stopped[slot] = 1;
+        return true;
+    };
+    st_hook = std::make_shared<chunker>(*this, chunk_frames, st_slot_chunk);
+    st_hook->rows.assign(slots, {});
+    st_toks.assign(slots, {});
+    st_fin.assign(slots, false);
+    st_state.assign(slots, SLOT_FREE);
+    st_stopped.assign(slots, 0);
+    st_buf.assign((size_t) slots * st_max_steps * hp.n_output_heads, 0u);
+    last_batch_tokens.clear();
+    return true;
 }
 
 bool parler_runner::stream_accepts(const generation_configuration & config) const {
@@ -622,8 +660,83 @@ void parler_runner::stream_submit(size_t ticket, const std::string & sentence, c
     }
     p.slot = st_free.back();
     st_free.pop_back();
+    if (st_chunk_frames) {   // a new occupant: its tokens and its chunker row start at zero
+        st_hook->rows[p.slot] = {};
+        st_toks[p.slot].clear();
+        st_fin[p.slot] = false;
+        st_stopped[p.slot] = 0;
+        st_state[p.slot] = SLOT_RUNNING;
+    }
     st_wait.push_back(std::move(p));
     st_live++;
+}
+
+void parler_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & toks) {
+    if (ticket < TOKEN_RECORD_TICKETS) {   // generate_stream_chunked's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
+        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
+        last_batch_tokens[ticket] = toks;
+    }
+    last_output_tokens = toks;
+}
+
+// stream_step with the hook (parler_runner.h), the newcomers admitted: the codec pass of the windows planned at the last look-in runs on the
+// codec's stream while this interval's decoder steps run on the decoder's.
+void parler_runner::stream_step_chunked(std::vector<stream_result> & finished) {
+    const uint32_t slots = stream_capacity(), nh = hp.n_output_heads;
+    auto report = [&](size_t ticket) {
+        stream_result r;
+        r.ticket = ticket;   // no audio: everything went through the hook
+        finished.push_back(r);
+    };
+    for (const decoded & d : st_codec) report(d.ticket);   // prompts that left no room for generation: an empty answer, as generate() gives
+    st_codec.clear();
+    std::vector<uint32_t> fs(slots), fn(slots), cnt(slots);
+    std::vector<uint8_t> done(slots);
+    uint32_t nf = 0;
+    bool running = false;
+    for (uint32_t s = 0; s < slots; s++) running = running || st_state[s] == SLOT_RUNNING;
+    // nothing live but windows still planned: they are decoded without a launch
+    if (running) hip_check(tts_hip_parler_stream_launch(ctx, STREAM_CHUNK), "tts_hip_parler_stream_launch");
+    try {
+        (void) st_hook->emit();
+    } catch (...) {
+        // an error of the codec pass or a throwing callback: the steps under way are waited for, so the context stays usable
+        if (running) (void) tts_hip_parler_stream_wait(ctx, nullptr, nullptr, nullptr, &nf, fs.data(), fn.data());
+        throw;
+    }
+    for (uint32_t s = 0; s < slots; s++) {   // those that had ended at the last look-in have had their last piece: the slot is free from here on
+        if (st_state[s] != SLOT_CLOSING) continue;
+        report(st_ticket[s]);
+        st_state[s] = SLOT_FREE;
+        st_free.push_back(s);
+        st_live--;
+    }
+    if (!running) return;
+    hip_check(tts_hip_parler_stream_wait(ctx, st_buf.data(), cnt.data(), done.data(), &nf, fs.data(), fn.data()), "tts_hip_parler_stream_wait");
+    std::vector<uint32_t> drop;
+    for (uint32_t s = 0; s < slots; s++) {
+        if (st_state[s] != SLOT_RUNNING) continue;
+        std::vector<uint32_t> & t = st_toks[s];
+        const uint32_t steps = std::min(cnt[s], hp.max_generation_size - st_start[s]);   // what generate() would have run alone
+        const uint32_t * b = st_buf.data() + (size_t) s * st_max_steps * nh;
+        if ((size_t) steps * nh > t.size()) t.insert(t.end(), b + t.size(), b + (size_t) steps * nh);
+        if (st_stopped[s]) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
+            if (!done[s]) drop.push_back(s);
+            remember_tokens(st_ticket[s], t);
+            report(st_ticket[s]);
+            st_hook->rows[s] = {};
+            t.clear();
+            st_state[s] = SLOT_FREE;
+            st_free.push_back(s);
+            st_live--;
+        } else if (done[s]) {   // ended: plan() cuts its tail, the next step hands it out
+            remember_tokens(st_ticket[s], t);
+            st_fin[s] = true;
+            st_state[s] = SLOT_CLOSING;
+        }
+    }
+    if (!drop.empty()) hip_check(tts_hip_parler_stream_drop(ctx, (uint32_t) drop.size(), drop.data()), "tts_hip_parler_stream_drop");
+    st_hook->plan(st_toks, st_fin);
 }
 
 void parler_runner::stream_step(std::vector<stream_result> & finished) {
@@ -661,6 +774,7 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
             hip_check(tts_hip_parler_stream_admit(ctx, (uint32_t) slots.size(), slots.data(), ids.data(), lens.data(), nullptr), "tts_hip_parler_stream_admit");
         st_wait.clear();
     }
+    if (st_chunk_frames) return stream_step_chunked(finished);
     std::vector<uint32_t> fs(stream_capacity()), fn(stream_capacity());
     uint32_t nf = 0;
     hip_check(tts_hip_parler_stream_run(ctx, STREAM_CHUNK, &nf, fs.data(), fn.data()), "tts_hip_parler_stream_run");
@@ -706,4 +820,8 @@ void parler_runner::stream_end() {
     st_on = false;
     st_wait.clear(); st_codec.clear();
     st_live = 0;
+    st_chunk_frames = 0;
+    st_on_chunk = nullptr;
+    st_hook.reset();
+    st_buf.clear(); st_buf.shrink_to_fit();
 }

@@ -15,6 +15,7 @@
 
 #include "../../include/tts_hip.h"
 #include "common.h"
+#include "parler_session.h"
 #include "sampler.h"
 #include "tokenizer.h"
 
@@ -40,7 +41,7 @@ struct parler_hparams {  // defaults = Parler TTS Mini v1 (model.h:66-83)
 // this with next = 0 and finished.
 size_t parler_undelay(const uint32_t * toks, size_t steps, uint32_t nh, uint32_t audio_vocab, size_t next, bool finished, std::vector<uint32_t> & out);
 
-struct parler_runner final : tts_generation_runner {
+struct parler_runner final : parler_session {
     parler_runner(const parler_hparams & hp, unigram_tokenizer * tok, int device, bool use_cross_attn);
     ~parler_runner() override;
 
@@ -77,6 +78,12 @@ struct parler_runner final : tts_generation_runner {
     void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
+    // chunked audio out of the session (the hook itself is declared in parler_session.h): with a hook set, stream_step launches its 32 steps
+    // (tts_hip_parler_stream_launch), decodes the windows the last look-in planned while they run (one tts_hip_dac_decode_windows pass for all
+    // slots) and hands their chunks out under the slots' tickets, then waits and takes the new rows of every live slot
+    // (tts_hip_parler_stream_wait).  An utterance is reported in `finished` (no audio) once its last chunk is out, and its slot is free from then
+    // on, not earlier: the chunker's rows are the slots.  on_chunk returning false drops that utterance only (tts_hip_parler_stream_drop),
+    // reported with what it got.  last_batch_tokens[ticket] keeps an utterance's tokens for tickets below TOKEN_RECORD_TICKETS.
     void *   device_context() const override { return ctx; }
     // chunked audio (common.h): codec windows of the frames that became final are decoded while the next steps run
     void generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
@@ -136,4 +143,17 @@ struct parler_runner final : tts_generation_runner {
     std::vector<pending>        st_wait;            // submitted, not yet admitted (admitted as one side batch by the next stream_step)
     std::vector<decoded>        st_codec;
     std::vector<std::vector<float>> st_pcm;         // audio handed out by the last stream_step
+    // ... with the chunk hook: the chunker's rows are the slots
+    static constexpr size_t TOKEN_RECORD_TICKETS = 4096;
+    enum : uint8_t { SLOT_FREE = 0, SLOT_RUNNING = 1, SLOT_CLOSING = 2 };   // closing: ended, its last windows planned and not yet handed out
+    bool session_chunks_ready(uint32_t chunk_frames) override;
+    void stream_step_chunked(std::vector<stream_result> & finished);
+    void remember_tokens(size_t ticket, const std::vector<uint32_t> & toks);
+    std::shared_ptr<chunker>           st_hook;     // plan() / emit() over the slots; calls st_slot_chunk
+    std::function<bool(uint32_t, const float *, size_t)> st_slot_chunk;   // slot -> its ticket's on_chunk; remembers who said stop
+    std::vector<std::vector<uint32_t>> st_toks;     // slot -> the occupant's tokens so far, still delayed
+    std::vector<bool>                  st_fin;      // slot -> its occupant has ended (plan() then cuts its tail)
+    std::vector<uint8_t>               st_state;    // slot -> SLOT_*
+    std::vector<uint8_t>               st_stopped;  // slot -> its occupant's on_chunk returned false
+    std::vector<uint32_t>              st_buf;      // what tts_hip_parler_stream_wait writes: [slots][max_steps][heads]
 };

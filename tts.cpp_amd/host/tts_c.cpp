@@ -170,6 +170,28 @@ int tts_c_generate_stream_chunked(tts_c_runner * r, const char * const * texts, 
     }
 }
 
+int tts_c_generate_stream_chunked_configs(tts_c_runner * r, const char * const * texts, const tts_c_config * cfgs, int n, uint32_t chunk_frames,
+                                          tts_c_chunk_fn fn, void * user) {
+    g_tts_throw_on_abort = true;
+    try {
+        if (!r || (n > 0 && (!texts || !cfgs))) throw std::runtime_error("tts_c_generate_stream_chunked_configs: null argument");
+        if (!fn) throw std::runtime_error("tts_c_generate_stream_chunked_configs: null callback");
+        bool dropped = false;
+        std::vector<std::string> s(texts, texts + n);
+        std::vector<generation_configuration> c;
+        for (int i = 0; i < n; i++) c.push_back(to_cfg(cfgs + i));
+        ((tts_generation_runner *) r)->generate_stream_chunked(s, c, chunk_frames, [&](uint32_t utt, const float * pcm, size_t k) {
+            const bool more = fn(user, (int) utt, pcm, k) != 0;
+            dropped = dropped || !more;
+            return more;
+        });
+        return dropped ? 1 : 0;
+    } catch (const std::exception & e) {
+        g_c_err = e.what();
+        return -1;
+    }
+}
+
 int64_t tts_c_parler_final_frames(const uint32_t * tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, int finished, uint32_t * out,
                                   uint64_t cap_frames) {
     if (n_heads == 0) { g_c_err = "tts_c_parler_final_frames: n_heads == 0"; return -1; }
@@ -261,7 +283,10 @@ int tts_c_last_tokens(tts_c_runner * r, int which, uint32_t * out, int cap) {
     static const std::vector<uint32_t> none;
     const std::vector<uint32_t> * vp = nullptr;
     if (auto * p = dynamic_cast<parler_runner *>((tts_generation_runner *) r))
-        vp = which == 0 ? &p->last_prompt_tokens : (which == 2 ? &p->last_conditional_tokens : &p->last_output_tokens);
+        vp = which == 0 ? &p->last_prompt_tokens
+           : which == 2 ? &p->last_conditional_tokens
+           : which >= 16 ? ((size_t) (which - 16) < p->last_batch_tokens.size() ? &p->last_batch_tokens[(size_t) (which - 16)] : &none)
+           : &p->last_output_tokens;
     else if (auto * o = dynamic_cast<orpheus_runner *>((tts_generation_runner *) r))
         vp = which == 0 ? &o->last_prompt_tokens
            : which == 1 ? &o->last_output_tokens

@@ -32,7 +32,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
-           "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs",
+           "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs", "tts_c_generate_stream_chunked_configs",
            "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
@@ -119,6 +119,7 @@ def load_lib():
         L.tts_c_generate_chunked.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
         L.tts_c_generate_batch_chunked.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
         L.tts_c_generate_stream_chunked.argtypes = L.tts_c_generate_batch_chunked.argtypes
+        L.tts_c_generate_stream_chunked_configs.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(Config), C.c_int, C.c_uint32, CHUNK_FN, C.c_void_p]
         L.tts_c_parler_final_frames.restype = C.c_int64
         L.tts_c_parler_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
         L.tts_c_dia_final_frames.restype = C.c_int64
@@ -243,12 +244,19 @@ class Runner:
         arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
         return self._chunked(lambda fn: self.L.tts_c_generate_batch_chunked(self.h, arr, n, C.byref(c), chunk_frames, fn, None), on_chunk)
 
-    def generate_stream_chunked(self, texts, chunk_frames=32, on_chunk=None, **cfg):
+    def generate_stream_chunked(self, texts, chunk_frames=32, on_chunk=None, configs=None, **cfg):
         """tts_c_generate_stream_chunked: any number of utterances through one session, [(utterance, pcm, arrival)] in arrival order;
-        on_chunk(utterance, pcm, arrival) returning False drops that utterance only (self.stopped: at least one was dropped)"""
-        c = make_config(**cfg) if cfg else self.cfg
+        on_chunk(utterance, pcm, arrival) returning False drops that utterance only (self.stopped: at least one was dropped).
+        A Parler runner's session chunks with TTS_PARLER_STREAM_CHUNKS=1 in the environment and hands whole utterances out without it.
+        configs: one dict of configuration fields per text (tts_c_generate_stream_chunked_configs) instead of one configuration for all"""
         n = len(texts)
         arr = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
+        if configs is not None:
+            if cfg or len(configs) != n:
+                raise RunnerError("generate_stream_chunked: configs takes one dict per text and no other configuration fields")
+            each = [make_config(**k) for k in configs]   # kept alive: they own the voice strings
+            return self._chunked(lambda fn: self.L.tts_c_generate_stream_chunked_configs(self.h, arr, (Config * n)(*each), n, chunk_frames, fn, None), on_chunk)
+        c = make_config(**cfg) if cfg else self.cfg
         return self._chunked(lambda fn: self.L.tts_c_generate_stream_chunked(self.h, arr, n, C.byref(c), chunk_frames, fn, None), on_chunk)
 
     def tokenize(self, text):
