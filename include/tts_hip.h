@@ -669,9 +669,18 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
  * self-attention cache [max_gen][kv width], "di_ck:..." / "di_cv:..." its cross K / V [max_ctx][heads * head_dim] (fp16 caches, kv_type =
  * TTS_HIP_F16: the rows widened exactly); "di_kv_elem" is the caches' element size in bytes (4 or 2).  With debug off every
  * forward launches exactly what it launches without these items; nothing is kept during a graph capture.
+ * Any context: "tile_pair" (two values: the tune key "tile_pair" as the tiled GEMM launches read it, i.e. what the default came to at the context's
+ * first tiled launch, -1 before it; and the most LDS in bytes that a tiled GEMM launch of the context has asked for since the key was last set).
  * Returns number of floats written or <0. */
 int64_t tts_hip_debug_read(tts_hip_ctx *ctx, const char *what, float *out, size_t max_floats);
 int     tts_hip_set_debug(tts_hip_ctx *ctx, int on);
+/* Test entry: one LDS-tiled GEMM y = W · a on the caller's fp16 operands (W [N][K], a [R][K], K a multiple of 128 and >= 256, N of 16), launched as a
+ * decoder forward launches it, i.e. under the context's tile keys (tune "tile_force", "tile_deep", "tile_pair"), without a K split.  The context need not
+ * be finalized.  epi: 0 store (out [R][N]); 1 q | k | v with cache append (N = 3 H: out = q [R][H], out2 = K | V caches [2][R][3][H] fp32, row r is
+ * sequence r at position r % 3); 2 residual (out [R][N], read and written); 3 GELU (out [R][N], out2 the same rows as fp16, [R][N] uint16); 4 the
+ * cross-attention inside the 64 x 64 tiles (N = H a multiple of 64, aux = K_c | V_c [2][E][H] fp32, E <= 32; out = the attended rows [R][H]; needs
+ * tile_force = 3).  Returns 0 or -1 (tts_hip_last_error). */
+int     tts_hip_debug_tile_gemm(tts_hip_ctx *ctx, int epi, int R, int N, int K, int H, int E, const void *W16, const void *A16, const float *aux, float *out, void *out2);
 
 /* Per-kernel-class timing with HIP events on the context's stream.  While enabled, forwards are
  * launched eagerly and every launch of every class is bracketed by an event pair. */

@@ -3,23 +3,38 @@
 make progress under a codec pass?  Parler-Mini fp16, fp32 KV, lock-step rows; everything through the C ABI, contexts on their own streams,
 one Python thread per context (ctypes releases the GIL).  Prints ms per decoder step of 1024 rows for: one context, two contexts side by
 side, and one context with a codec pass (64 x 248 frames, its own context) looping beside it.
-usage: dec_overlap.py [rows=1024] [steps=96]"""
-import os, sys, threading, time
+usage: dec_overlap.py [rows=1024] [steps=96] [--tune key=value,...] [--only-pair] [--sweep key=value,... [--sweep ...]]
+--tune: tts_hip_tune keys of every decoder context (tile_deep=0, tile_pair=1, ...); --only-pair: stop after the two side-by-side contexts;
+--sweep: after that, the one-context and side-by-side figures once more under each further set of keys (fresh contexts, same process), then stop.
+Under the default tile_pair the first context runs alone before the second attaches, so it keeps the tiles of a context alone: set the key."""
+import argparse, os, sys, threading, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tts_cpp_amd  # noqa: F401
 from tts_cpp_amd import gguf, hip, synth
 
-R = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 96
+
+def tune_keys(text):
+    """'tile_pair=1,tile_deep=0' -> {'tile_pair': 1, 'tile_deep': 0}"""
+    return {k: int(v) for k, v in (kv.split("=") for kv in text.split(",") if kv)}
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("rows", nargs="?", type=int, default=1024)
+ap.add_argument("steps", nargs="?", type=int, default=96)
+ap.add_argument("--tune", type=tune_keys, default={})
+ap.add_argument("--only-pair", action="store_true")
+ap.add_argument("--sweep", type=tune_keys, action="append", default=[])
+args = ap.parse_args()
+R, STEPS = args.rows, args.steps
 cfg = synth.parler_mini(weight_type=gguf.F16, max_gen=16 + 272)
 model = synth.build(cfg)
 rng = np.random.default_rng(3)
 
 
-def mk(rows, share=None):
-    e = hip.HipEngine(cfg, max_seqs=rows, kv_positions=16 + 272)
+def mk(rows, share=None, tune=args.tune):
+    e = hip.HipEngine(cfg, max_seqs=rows, kv_positions=16 + 272, tune=tune)
     if share is None:
         e.load(model)
     else:
@@ -63,13 +78,24 @@ def run(engines, rows, extra=None):
 a = mk(R)
 o, wall = run([a], R)
 base = o["d0"]
-print(f"one context, {R} rows: {base:.3f} ms/step")
+print(f"tune {args.tune}: one context, {R} rows: {base:.3f} ms/step")
 if os.environ.get("DEC_OVERLAP_ONE"):
     sys.exit(0)
 b = mk(R, share=a)
 o, wall = run([a, b], R)
 print(f"two contexts x {R} rows side by side: {o['d0']:.3f} / {o['d1']:.3f} ms/step each, wall {wall / STEPS:.3f} ms per step pair = {wall / STEPS / 2:.3f} per {R} rows  ({2 * base / (wall / STEPS):.2f}x of serial)")
 b.close()
+for keys in args.sweep:
+    a.close()
+    a = mk(R, tune=keys)
+    o, wall = run([a], R)
+    base = o["d0"]
+    b = mk(R, share=a, tune=keys)
+    o, wall = run([a, b], R)
+    print(f"tune {keys}: one context {base:.3f} ms/step; two side by side {o['d0']:.3f} / {o['d1']:.3f} each, wall {wall / STEPS:.3f} ms per step pair ({2 * base / (wall / STEPS):.2f}x of serial)")
+    b.close()
+if args.only_pair or args.sweep:
+    sys.exit(0)
 if R >= 512:
     h1, h2 = mk(R // 2, share=a), mk(R // 2, share=a)
     o, wall = run([h1, h2], R // 2)

@@ -143,6 +143,9 @@ extern "C" tts_hip_ctx *tts_hip_create(int device, const tts_hip_desc *desc) {
     if (const char *e = getenv("TTS_HIP_GEN_COMPACT")) c->gen_compact = atoi(e) != 0;                           // test_gpu_runner.py: row compaction of the generation loop
     if (const char *e = getenv("TTS_HIP_TILE_FORCE")) c->tile_force = atoi(e);                                  // test_gpu_parler.py: every tile shape of the tiled GEMM
     if (const char *e = getenv("TTS_HIP_TILE_KS")) c->tile_force_ks = atoi(e);
+    if (const char *e = getenv("TTS_HIP_TILE_PAIR")) {                                                          // bench.py A/B (profiles/gemm_two_per_cu.txt): GEMM tile forms of which two fit one CU
+        if (tts_hip_tune(c, "tile_pair", atoi(e)) != 0) { tts_hip_destroy(c); return nullptr; }                 // a value no kernel was built for: no context, not a silent default
+    }
     if (const char *e = getenv("TTS_HIP_GEMV_ROWS")) c->gemv_rows = atoi(e) != 0;                               // test_gpu_gemv_rows.py, test_gpu_orpheus.py
     if (const char *e = getenv("TTS_HIP_LLAMA_GRAPH")) c->llama_graph = atoi(e) != 0;
     if (const char *e = getenv("TTS_HIP_Q4_NATIVE")) c->q4_native = atoi(e) != 0;
@@ -189,6 +192,13 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "cross_fold") c->cross_fold = v != 0;
     else if (k == "tile_min_rows") c->tile_min_rows = std::max(0, v);
     else if (k == "tile_deep") c->tile_deep = v;
+    else if (k == "tile_force") c->tile_force = v;               // as TTS_HIP_TILE_FORCE: tile shape index of every tiled GEMM, -1 = the cost model's
+    else if (k == "tile_pair") {   // the forms launch_tile_shape holds
+        if (v < -1 || v > 2) return set_err("tts_hip_tune: tile_pair is -1 (by arena sharing), 0, 1 or 2 (got %d)", v);
+        c->tile_pair = v;
+        c->tile_pair_auto = -1;
+        c->tile_lds_max = 0;
+    }
     else if (k == "qtile_min_rows") c->qtile_min_rows = std::max(0, v);   // 0: quantised matrices stay on the 16-feature kernel (<= 256 rows per forward)
     else if (k == "qtile_shape") c->qtile_shape = v;
     else if (k == "qtile_big") c->qtile_big = std::max(0, std::min(3, v));
@@ -235,6 +245,11 @@ void arena_share(tts_hip_ctx *c) {
     auto it = g_arena_refs.find(c->arena);
     c->arena_counted = it != g_arena_refs.end();
     if (c->arena_counted) it->second++;
+}
+int arena_sharers(tts_hip_ctx *c) {
+    std::lock_guard<std::mutex> l(g_arena_mutex);
+    auto it = g_arena_refs.find(c->arena);
+    return it == g_arena_refs.end() ? 1 : it->second;
 }
 void arena_release(tts_hip_ctx *c) {
     if (!c->arena) return;

@@ -176,33 +176,49 @@ struct TileShape { int BM, BN, threads; };
 static const TileShape TILE_SHAPES[] = {{32, 32, 128}, {32, 64, 256}, {64, 32, 256}, {64, 64, 512}, {128, 64, 512}, {128, 128, 512}};
 enum { N_TILE_SHAPES = 6 };
 
+template <int BM, int BN, int WM, int WN, int BK, int S, int EPI>
+static int launch_tile_form(tts_hip_ctx *c, const GemmArgs &a, const TileMap &tm) {
+    const int total = tm.m_tiles * tm.n_tiles * tm.k_slices;
+    const int grid = (total + 7) / 8 * 8;
+    const size_t lds = (size_t) S * (BM + BN) * BK * 2;
+    c->tile_lds_max = std::max(c->tile_lds_max, (int) lds);
+    static std::atomic<uint64_t> attr{0};
+    if (attr_needed(attr, c->device))
+        HIPCHK(hipFuncSetAttribute((const void *) gemm_tile_kernel<BM, BN, WM, WN, BK, S, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, WM, WN, BK, S, EPI>), dim3(grid), dim3(WM * WN * 64), lds, c->stream, a, tm);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// tile_pair as the launches read it.  -1 (the default) is settled at the context's first tiled launch and then kept, so that the eager pass, the captured
+// steps and every later forward of a context run the same kernels: 1 when another context holds a reference on this context's weight arena (the runners
+// of one device), 0 for a context alone, which keeps the deeper pipelines (3 % faster alone, profiles/gemm_two_per_cu.txt).  tune("tile_pair") asks again.
+static int tile_pair_of(tts_hip_ctx *c) {
+    if (c->tile_pair >= 0) return c->tile_pair;
+    if (c->tile_pair_auto < 0) c->tile_pair_auto = arena_sharers(c) > 1 ? 1 : 0;
+    return c->tile_pair_auto;
+}
+
 template <int BM, int BN, int WM, int WN, int EPI>
 static int launch_tile_shape(tts_hip_ctx *c, const GemmArgs &a, const TileMap &tm, bool deep) {
     // deep: 128-wide k-tiles, 3 LDS buffers — fewer barriers for a single wave of workgroups; otherwise 64-wide k-tiles,
     // 4 buffers (half the LDS: two workgroups per CU when the grid exceeds the CU count)
     constexpr bool can_deep = (BM + BN) * 256 * 3 <= 160 * 1024;
-    const int total = tm.m_tiles * tm.n_tiles * tm.k_slices;
-    const int grid = (total + 7) / 8 * 8;
+    // tune("tile_pair"): every form at most 72 KB, so that two workgroups share a CU's 160 KB whatever launches they belong to.  The tiles of 192 and
+    // 256 rows | features give up buffers for that: 3 x 24 KB and 2 x 32 KB (one k-tile in flight under the MFMAs of the current one)
+    constexpr int PAIR_S = (BM + BN) * 128 * 4 <= 72 * 1024 ? 4 : (BM + BN) * 128 * 3 <= 72 * 1024 ? 3 : 2;
     const int kc = a.kchunk ? a.kchunk : a.K;
-    if (can_deep && deep && kc % 128 == 0) {
-        const size_t lds = (size_t) 3 * (BM + BN) * 256;
-        static std::atomic<uint64_t> attr{0};
-        if (attr_needed(attr, c->device))
-            HIPCHK(hipFuncSetAttribute((const void *) gemm_tile_kernel<BM, BN, WM, WN, 128, 3, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, WM, WN, 128, 3, EPI>), dim3(grid), dim3(WM * WN * 64), lds, c->stream, a, tm);
-    } else {
-        const size_t lds = (size_t) 4 * (BM + BN) * 128;
-        static std::atomic<uint64_t> attr{0};
-        if (attr_needed(attr, c->device))
-            HIPCHK(hipFuncSetAttribute((const void *) gemm_tile_kernel<BM, BN, WM, WN, 64, 4, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, WM, WN, 64, 4, EPI>), dim3(grid), dim3(WM * WN * 64), lds, c->stream, a, tm);
+    const bool pair = tile_pair_of(c) != 0;
+    if constexpr (PAIR_S < 4) {
+        if (pair) return launch_tile_form<BM, BN, WM, WN, 64, PAIR_S, EPI>(c, a, tm);
     }
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (can_deep && deep && !pair && kc % 128 == 0) return launch_tile_form<BM, BN, WM, WN, 128, 3, EPI>(c, a, tm);
+    return launch_tile_form<BM, BN, WM, WN, 64, 4, EPI>(c, a, tm);
 }
 
 template <int EPI>
 static int launch_tile(tts_hip_ctx *c, const GemmArgs &a, int shape, int ks) {
+    if (tile_pair_of(c) == 2 && shape == 5) shape = 4;   // 128 x 64 tiles, three buffers, instead of 128 x 128 with two
     const TileShape &t = TILE_SHAPES[shape];
     TileMap tm{(a.R + t.BM - 1) / t.BM, (a.N + t.BN - 1) / t.BN, ks};
     const bool deep = c->tile_deep && tm.m_tiles * tm.n_tiles * tm.k_slices <= 320;
@@ -238,6 +254,74 @@ static void choose_tile(const tts_hip_ctx *c, int R, int N, int K, bool may_spli
     if (c->tile_force_ks > 0 && may_split && K % (c->tile_force_ks * 128) == 0) bk = c->tile_force_ks;
     *shape_out = bs;
     *ks_out = bk;
+}
+
+// the tiled launch of an epilogue; want_cross: the cross-attention inside the 64 x 64 tiles where the shape allows (c->cross_folded says whether)
+static int launch_tile_epi(tts_hip_ctx *c, const GemmArgs &a, int epi, bool want_cross, int shape, int ks) {
+    if (want_cross && shape == 3 && ks == 1 && a.cross_E >= 1 && a.cross_E <= 32 && a.N == a.H && a.H % 64 == 0) {
+        TileMap tm{(a.R + 63) / 64, a.N / 64, 1};
+        const int rc = launch_tile_shape<64, 64, 2, 4, EPI_CROSS>(c, a, tm, c->tile_deep && tm.m_tiles * tm.n_tiles <= 320);
+        c->cross_folded = rc == 0;
+        return rc;
+    }
+    if (epi == EPI_STORE) return launch_tile<EPI_STORE>(c, a, shape, ks);
+    if (epi == EPI_QKV) return launch_tile<EPI_QKV>(c, a, shape, ks);
+    if (epi == EPI_RESID) return launch_tile<EPI_RESID>(c, a, shape, ks);
+    return launch_tile<EPI_GELU>(c, a, shape, ks);
+}
+
+// Test entry (tests/test_gpu_gemm_two_per_cu.py): ONE tiled GEMM on the caller's fp16 operands, through choose_tile and launch_tile_epi, that is under the
+// context's tile keys (tile_force, tile_deep, tile_pair), with no K split.  W [N][K], A [R][K] (fp16 bits); by epilogue:
+//   EPI_STORE  out [R][N]                       EPI_GELU  out [R][N], out2 = the same rows as fp16 bits ([R][N] uint16)
+//   EPI_RESID  out [R][N] in and out            EPI_CROSS N = H: aux = K_c | V_c, [2][E][H] fp32; out = the attended rows [R][H]
+//   EPI_QKV    N = 3 H: out = q [R][H], out2 = K | V caches [2][R][3][H] fp32 (row r is sequence r at position r % 3; untouched positions stay 0)
+extern "C" int tts_hip_debug_tile_gemm(tts_hip_ctx *c, int epi, int R, int N, int K, int H, int E, const void *W16, const void *A16, const float *aux, float *out, void *out2) {
+    if (!c || !W16 || !A16 || !out) return set_err("tts_hip_debug_tile_gemm: null argument");
+    if (epi < EPI_STORE || epi > EPI_CROSS || R < 1 || N < 16 || N % 16 || K < 256 || K % 128 || H < 4 || H % 4) return set_err("tts_hip_debug_tile_gemm: bad shape");
+    if ((epi == EPI_QKV && (N != 3 * H || !out2)) || (epi == EPI_GELU && !out2) || (epi == EPI_CROSS && (N != H || H % 64 || E < 1 || E > 32 || !aux)))
+        return set_err("tts_hip_debug_tile_gemm: bad arguments for epilogue %d", epi);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t wb = (size_t) N * K * 2, ab = (size_t) R * K * 2, ob = (size_t) R * (epi == EPI_QKV || epi == EPI_CROSS ? H : N) * 4;
+    const size_t o2b = epi == EPI_QKV ? (size_t) 2 * R * 3 * H * 4 : epi == EPI_GELU ? (size_t) R * N * 2 : 0;
+    const size_t xb = epi == EPI_CROSS ? (size_t) 2 * E * H * 4 : 0, ib = (size_t) 2 * R * 4;
+    char *d = nullptr;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t) 255; };
+    HIPCHK(hipMalloc((void **) &d, up(wb) + up(ab) + up(ob) + up(o2b) + up(xb) + up(ib)));
+    char *dW = d, *dA = dW + up(wb), *dO = dA + up(ab), *dO2 = dO + up(ob), *dX = dO2 + up(o2b), *dI = dX + up(xb);
+    std::vector<uint32_t> idx((size_t) 2 * R);
+    for (int r = 0; r < R; r++) { idx[r] = (uint32_t) r; idx[R + r] = (uint32_t) (r % 3); }
+    int rc = 0;
+    auto ok = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = set_err("tts_hip_debug_tile_gemm: %s", hipGetErrorString(e)); return e == hipSuccess; };
+    (void) (ok(hipMemcpy(dW, W16, wb, hipMemcpyHostToDevice)) && ok(hipMemcpy(dA, A16, ab, hipMemcpyHostToDevice)) && ok(hipMemcpy(dI, idx.data(), ib, hipMemcpyHostToDevice)) &&
+            ok(epi == EPI_RESID ? hipMemcpy(dO, out, ob, hipMemcpyHostToDevice) : hipMemsetAsync(dO, 0, ob, c->stream)) && (!o2b || ok(hipMemsetAsync(dO2, 0, o2b, c->stream))) &&
+            (!xb || ok(hipMemcpy(dX, aux, xb, hipMemcpyHostToDevice))));
+    if (!rc) {
+        GemmArgs a{};
+        a.W = dW; a.K = K; a.N = N; a.R = R; a.A = dA; a.lda = K; a.H = H; a.gelu_mode = (int) c->d.gelu_mode;
+        a.out = (float *) dO; a.ldo = N;
+        if (epi == EPI_GELU) a.out16 = nullptr;
+        if (epi == EPI_QKV) {
+            a.q = (float *) dO; a.kc = dO2; a.vc = dO2 + (size_t) R * 3 * H * 4; a.kv_f16 = 0; a.seq_stride = (int64_t) 3 * H;
+            a.row_seq = (const uint32_t *) dI; a.row_pos = (const uint32_t *) dI + R;
+        }
+        if (epi == EPI_CROSS) {
+            a.cross_k = (const float *) dX; a.cross_v = (const float *) dX + (size_t) E * H; a.cross_E = E; a.cross_scale = 0.125f;
+            a.cross_out = (float *) dO; a.cross_out16 = nullptr;
+        }
+        int shape = 0, ks = 1;
+        choose_tile(c, R, N, K, false, &shape, &ks);
+        c->cross_folded = false;
+        rc = launch_tile_epi(c, a, epi == EPI_CROSS ? (int) EPI_STORE : epi, epi == EPI_CROSS, shape, 1);
+        if (!rc && epi == EPI_CROSS && !c->cross_folded) rc = set_err("tts_hip_debug_tile_gemm: the cross-attention fold needs the 64 x 64 tile (tile_force = 3)");
+        if (!rc && epi == EPI_GELU) {   // once more with the fp16 output an fp16 fc2 reads
+            a.out16 = (_Float16 *) dO2;
+            rc = launch_tile_epi(c, a, epi, false, shape, 1);
+        }
+        if (!rc) (void) (ok(hipStreamSynchronize(c->stream)) && ok(hipMemcpy(out, dO, ob, hipMemcpyDeviceToHost)) && (!o2b || ok(hipMemcpy(out2, dO2, o2b, hipMemcpyDeviceToHost))));
+    }
+    (void) hipStreamSynchronize(c->stream);
+    free_dev(d);
+    return rc;
 }
 
 // GGUF-quantised matrix: LayerNorm (if any) -> Q8_0-quantise the activation rows -> integer block GEMM
@@ -601,17 +685,7 @@ int run_gemm(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int pro, int ep
             c->pending_parts = ks;
         }
         CHK(prof_begin(c, kclass, bytes, flops));
-        int rc;
-        if (want_cross && shape == 3 && ks == 1 && a.cross_E >= 1 && a.cross_E <= 32 && a.N == a.H && a.H % 64 == 0) {
-            TileMap tm{(a.R + 63) / 64, a.N / 64, 1};
-            rc = launch_tile_shape<64, 64, 2, 4, EPI_CROSS>(c, a, tm, c->tile_deep && tm.m_tiles * tm.n_tiles <= 320);
-            c->cross_folded = rc == 0;
-        } else
-        if (epi == EPI_STORE) rc = launch_tile<EPI_STORE>(c, a, shape, ks);
-        else if (epi == EPI_QKV) rc = launch_tile<EPI_QKV>(c, a, shape, ks);
-        else if (epi == EPI_RESID) rc = launch_tile<EPI_RESID>(c, a, shape, ks);
-        else rc = launch_tile<EPI_GELU>(c, a, shape, ks);
-        CHK(rc);
+        CHK(launch_tile_epi(c, a, epi, want_cross, shape, ks));
         return prof_end(c);
     }
     if (epi == EPI_RESID && a.R > c->ln_fuse_max && a.H <= 2048 && a.N == a.H && a.out == c->x && pro != PRO_CROSS && pro != PRO_ATTN) {   // (the staging prologues of the one-sequence chain have no K-slice form)
@@ -2561,6 +2635,12 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (max_floats < 1) { set_err("buffer too small"); return -1; }
         out[0] = (float) c->graphs.size();
         return 1;
+    }
+    if (w == "tile_pair") {   // [0] the tile_pair the tiled GEMM launches run under (-1: the default, no tiled launch yet); [1] the most LDS in bytes a tiled launch of this context asked for since tune("tile_pair")
+        if (max_floats < 2) { set_err("buffer too small"); return -1; }
+        out[0] = (float) (c->tile_pair >= 0 ? c->tile_pair : c->tile_pair_auto);
+        out[1] = (float) c->tile_lds_max;
+        return 2;
     }
     if (c->has_parler && starts_with(w, "voice:")) {  // voice:<v>:<layer>:<0|1>  -> [len][H] of bank entry v
         int v = 0, layer = 0, kv = 0;

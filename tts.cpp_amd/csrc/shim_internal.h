@@ -465,6 +465,13 @@ struct tts_hip_ctx {
     float *attn_part = nullptr; // [rows][heads][splits][130] partial softmax results
     size_t attn_part_cap = 0;   // in (row, head, split) triples
     int tile_deep = 1;          // tune("tile_deep")=0: always the 64-wide k-tiles / 4 buffers form (half the LDS per workgroup)
+    int tile_pair = -1;         // tune("tile_pair") / TTS_HIP_TILE_PAIR: tile forms of at most 72 KB of LDS and 80 VGPRs, so that a GEMM workgroup fits a CU beside another one (of this
+                                // context's launch or of another context's) or beside a codec workgroup.  0 = off; 1 = 128 x 128 tiles with two 64-wide buffers (64 KB), 128 x 64 with
+                                // three (72 KB), the smaller shapes as under tile_deep = 0; 2 = as 1, a 128 x 128 choice takes 128 x 64 tiles instead.  Same k order per output element:
+                                // the same bits.  -1 (default): 1 when another context reads this context's weight arena (the runners of one device), else 0, decided at the first
+                                // tiled launch (tile_pair_of, shim_decoder.hip): a captured step keeps its kernels.  Measured in profiles/gemm_two_per_cu.txt
+    int tile_pair_auto = -1;    // what the default came to: -1 until the first tiled launch, then 0 or 1; tune("tile_pair") resets it
+    int tile_lds_max = 0;       // the most LDS in bytes a tiled GEMM launch asked for since tune("tile_pair") (debug_read "tile_pair": the tests' "which forms ran")
     bool dac_f16 = false;      // every codec conv kernel arrived as F16: fp16 im2col x fp16 kernel, fp32 accumulate (ggml)
     bool dac_packed = false;
 
@@ -514,6 +521,7 @@ static int capture_graph(tts_hip_ctx *c, int key, F enqueue, hipGraphExec_t *out
 void free_dev(void *p);
 void arena_own(tts_hip_ctx *c);
 void arena_share(tts_hip_ctx *c);
+int arena_sharers(tts_hip_ctx *c);   // contexts that hold a reference on c's arena (1: c alone)
 void arena_release(tts_hip_ctx *c);
 bool starts_with(const std::string &s, const char *pre);
 int plan(tts_hip_ctx *c);

@@ -85,7 +85,7 @@ EXPORTS = [
     "tts_hip_parler_set_text_encoding", "tts_hip_parler_reset", "tts_hip_parler_prefill", "tts_hip_parler_prefill_batch", "tts_hip_parler_step",
     "tts_hip_parler_step_greedy", "tts_hip_parler_generate_greedy", "tts_hip_parler_generate_sampled", "tts_hip_sample_logits",
     "tts_hip_t5_create", "tts_hip_t5_encode", "tts_hip_t5_output_size", "tts_hip_snac_create", "tts_hip_snac_decode", "tts_hip_orpheus_create", "tts_hip_orpheus_decode", "tts_hip_orpheus_step_batch", "tts_hip_orpheus_generate_batch", "tts_hip_orpheus_generate_greedy", "tts_hip_orpheus_generate_sampled", "tts_hip_orpheus_sample_logits", "tts_hip_dia_create", "tts_hip_dia_encode", "tts_hip_dia_step", "tts_hip_dia_encode_slot", "tts_hip_dia_step_batch", "tts_hip_dia_generate", "tts_hip_kokoro_create", "tts_hip_kokoro_durations", "tts_hip_kokoro_generate", "tts_hip_dac_decode", "tts_hip_dac_decode_batch", "tts_hip_debug_read",
-    "tts_hip_set_debug", "tts_hip_profile", "tts_hip_profile_get", "tts_hip_kclass_name", "tts_hip_stream",
+    "tts_hip_set_debug", "tts_hip_debug_tile_gemm", "tts_hip_profile", "tts_hip_profile_get", "tts_hip_kclass_name", "tts_hip_stream",
     "tts_hip_synchronize", "tts_hip_dac_arith", "tts_hip_broadcast_weights", "tts_hip_comm_unique_id", "tts_hip_broadcast_weights_rank", "tts_hip_tune",
     "tts_hip_parler_stream_begin", "tts_hip_parler_stream_admit", "tts_hip_parler_stream_run", "tts_hip_parler_stream_collect", "tts_hip_parler_stream_end",
     "tts_hip_parler_gen_begin", "tts_hip_parler_gen_launch", "tts_hip_parler_gen_wait", "tts_hip_dac_halo_frames", "tts_hip_dac_decode_windows",
@@ -183,6 +183,7 @@ def load_lib():
     L.tts_hip_debug_read.argtypes = [vp, C.c_char_p, f32p, C.c_size_t]
     L.tts_hip_debug_read.restype = C.c_int64
     L.tts_hip_set_debug.argtypes = [vp, C.c_int]
+    L.tts_hip_debug_tile_gemm.argtypes = [vp] + [C.c_int] * 6 + [vp, vp, f32p, f32p, vp]
     L.tts_hip_profile.argtypes = [vp, C.c_int]
     L.tts_hip_profile_get.argtypes = [vp, C.c_int, C.POINTER(KStat)]
     L.tts_hip_kclass_name.argtypes = [C.c_int]
@@ -629,6 +630,22 @@ class HipEngine:
         if n < 0:
             raise HipError(self.err())
         return out[:n].copy()
+
+    def debug_tile_gemm(self, epi, W, A, H, resid=None, cross_kv=None):
+        """tts_hip_debug_tile_gemm: one tiled GEMM under the context's tile keys.  W [N][K], A [R][K] float16; epi 0 store, 1 qkv, 2 residual (resid
+        [R][N]), 3 GELU, 4 cross fold (cross_kv [2][E][H] float32).  -> (out, out2): see include/tts_hip.h"""
+        W, A = np.ascontiguousarray(W, dtype=np.float16), np.ascontiguousarray(A, dtype=np.float16)
+        (N, K), R = W.shape, A.shape[0]
+        assert A.shape[1] == K
+        out = np.array(resid, dtype=np.float32, order="C") if epi == 2 else np.zeros((R, H if epi in (1, 4) else N), dtype=np.float32)
+        assert out.shape == (R, H if epi in (1, 4) else N)
+        out2 = np.zeros((2, R, 3, H), dtype=np.float32) if epi == 1 else np.zeros((R, N), dtype=np.uint16) if epi == 3 else None
+        aux = None if cross_kv is None else np.ascontiguousarray(cross_kv, dtype=np.float32)
+        E = 0 if aux is None else aux.shape[1]
+        f32p = C.POINTER(C.c_float)
+        self._chk(self.L.tts_hip_debug_tile_gemm(self.ctx, epi, R, N, K, H, E, W.ctypes.data, A.ctypes.data, None if aux is None else aux.ctypes.data_as(f32p),
+                                                 out.ctypes.data_as(f32p), None if out2 is None else out2.ctypes.data))
+        return out, out2
 
     def profile(self, enable):
         """True/1: every launch (eager forwards); 2: DAC launches only (usable inside a timed region); False/0: off"""
