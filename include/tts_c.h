@@ -116,6 +116,9 @@ void         *tts_c_runner_device_context(tts_c_runner *r);
 /* bytes per element of the decoder's K/V cache as the device context reports them (Orpheus and Dia: 4, or 2 when TTS_HIP_KV_F16 was in the
  * environment at load, TTS_HIP_FLAG_KV_F16 / tts_hip_dia_desc::kv_type); 0 when the architecture does not report it */
 uint32_t      tts_c_runner_kv_element_bytes(tts_c_runner *r);
+/* utterances a continuous session of the runner holds at once (tts_generation_runner::stream_capacity: an Orpheus runner's max_seqs, at most 256;
+ * 0: the runner has no session) */
+uint32_t      tts_c_runner_stream_capacity(tts_c_runner *r);
 /* the loaded runner's own tokenizer (Parler: unigram ids + EOS as batch_from_sentence builds them); returns the id count */
 int           tts_c_runner_tokenize(tts_c_runner *r, const char *text, uint32_t *out, int cap);
 float         tts_c_sampling_rate(tts_c_runner *r);

@@ -258,7 +258,13 @@ typedef struct tts_hip_orpheus_desc {
     uint32_t n_ctx;            /* KV positions: max_context_length + max_generation_size (1024 + 2100, :176-177) */
     float    rope_base;        /* 500000 (:190,250); 0 = that  */
     uint32_t flags;            /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_KV_F16 (fp16 K/V cache, see the flag) */
-    uint32_t max_seqs;         /* KV-cache slots for lock-step utterances (tts_hip_orpheus_generate_batch); 0 / 1: one sequence, as the reference's runner */
+    uint32_t max_seqs;         /* KV-cache slots for lock-step utterances (tts_hip_orpheus_generate_batch); 0 / 1: one sequence, as the reference's runner.
+                                * At most 256 (= the rows one decoder forward carries); tts_hip_orpheus_step_batch, generate_batch, gen_* and stream_begin[_mixed] take
+                                * up to max_seqs rows / slots.  Contexts of at most 64 slots are unchanged: same arena, same kernels.  A context of 65 .. 256
+                                * slots also plans the transposed block scales of its GGUF-quantised matrices into the arena (share_with / broadcast carry them),
+                                * and its forwards of more than 64 rows run those matrices on the LDS-tiled integer GEMM (F32 / F16 matrices: the 16-feature
+                                * kernels, correct but slow).  A slot costs n_layers * n_ctx * n_kv_heads * head_dim * 2 cache elements: 0.72 GB at 3B shapes,
+                                * 0.36 GB under TTS_HIP_FLAG_KV_F16; tts_hip_finalize fails with the slot count and the bytes it asked for when they do not fit. */
 } tts_hip_orpheus_desc;
 tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus_desc *desc);
 /* n tokens at positions pos0 .. pos0+n-1 (KV cache appended); logits_out [vocab_size] of the LAST token (:287-290).

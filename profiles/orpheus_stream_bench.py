@@ -18,6 +18,12 @@
                   arg-max pair).  The legs alternate within a repetition; five repetitions, median and spread (max - min).  A build without
                   the mixed session runs (a) only: that is how orpheus_stream_mixed_parent_before.json was made.
 
+  --many-rows     the session's step time and tokens/s at --rows slots (64,128,256 for the recorded files; 64 alone on a build whose contexts stop at
+                  64 slots: orpheus_many_rows_parent_before.json), greedy, every utterance behind a prompt of --prompt ids (480: positions around
+                  512 inside the timed window), --kv f16 for the fp16 cache (256 fp32 slots of 1024 positions would be 60 GB).  Five repetitions,
+                  median and spread (max - min).  At the largest row count one profiled step (tts_hip_profile: eager, every launch timed) gives the
+                  split between the GEMM classes and self-attention.
+
 A build without the session (hip.OrpheusEngine has no stream_begin) runs the generate_batch / gen_launch legs only: that is how
 orpheus_stream_throughput_parent_before.json was made.  Usage: python profiles/orpheus_stream_bench.py [--out FILE] [--reps N]"""
 import argparse
@@ -132,6 +138,56 @@ def mixed_main(args):
         f.write("\n")
 
 
+def many_rows_main(args):
+    flags = hip.FLAG_KV_F16 if args.kv == "f16" else 0
+    cfg = synth.orpheus_3b(ctx=1024, weight_type=gguf.Q4_0)
+    tensors, _ = sb.orpheus_tensors(cfg, np.random.default_rng(7))
+    model = sb._Model(cfg, tensors)
+    rows = [int(x) for x in args.rows.split(",")]
+    out = {"setup": {"model": "synthetic Orpheus-3B (28 x 3072, 24 / 8 heads x 128, ffn 8192, 156 940 logits), Q4_0, n_ctx 1024", "kv_cache": args.kv, "prompt_ids": args.prompt,
+                     "timed_steps": STEPS, "warm_steps": WARM, "reps": args.reps, "selection": "greedy",
+                     "timing": "host wall clock around the blocking tts_hip_orpheus_stream_run, median of reps, spread = max - min; one context of max_seqs = rows per leg"},
+           "per_step": {}}
+    prng = np.random.default_rng(11)
+    for B in rows:
+        eng = hip.OrpheusEngine(cfg, max_seqs=B, flags=flags)
+        eng.load(model)
+        prompts = [prng.integers(0, cfg.vocab, args.prompt).astype(np.uint32) for _ in range(B)]
+        runs = []
+        for _ in range(args.reps):
+            eng.stream_begin(B, WARM + STEPS + 2, NO_STOP)
+            eng.stream_admit(list(range(B)), prompts)
+            assert eng.stream_run(WARM) == []
+            t = time.perf_counter()
+            fin = eng.stream_run(STEPS)
+            runs.append((time.perf_counter() - t) / STEPS * 1e3)
+            assert fin == []
+            eng.stream_end()
+        res = {"stream_run_ms_per_step": round(med(runs), 4), "spread_ms": round(max(runs) - min(runs), 4), "runs_ms": [round(x, 4) for x in runs],
+               "tokens_per_s": round(B / med(runs) * 1e3, 1), "tokens_per_s_spread": round(B / min(runs) * 1e3 - B / max(runs) * 1e3, 1)}
+        if B == max(rows):
+            # one eager step with every launch timed: the classes' shares of the device time (the step itself is slower than the timed ones above)
+            eng.stream_begin(B, 8, NO_STOP)
+            eng.stream_admit(list(range(B)), prompts)
+            eng.stream_run(2)
+            eng.profile(True)
+            eng.stream_run(1)
+            prof = {k: v for k, v in eng.profile_get().items() if v["launches"]}
+            eng.profile(False)
+            eng.stream_end()
+            total = sum(v["ms_total"] for v in prof.values())
+            res["profiled_step"] = {"rows": B, "ms_total_of_timed_launches": round(total, 4),
+                                    "classes": {k: {"ms": round(v["ms_total"], 4), "launches": v["launches"], "share": round(v["ms_total"] / total, 4)} for k, v in prof.items()},
+                                    "note": "launches outside the profiled classes (rms norm, rope, silu, quantisation, selection) are not in the total"}
+        out["per_step"][str(B)] = res
+        print(B, json.dumps(res), flush=True)
+        eng.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def pick_stop(pilot):
     """the id whose first occurrences give lengths closest to a 10:1 spread (10th / 90th percentile) over all utterances"""
     best, best_score = None, None
@@ -196,9 +252,14 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rows", default="8,32")
     ap.add_argument("--mixed", action="store_true", help="the legs of the mixed session instead (--reps 5 for the recorded files)")
+    ap.add_argument("--many-rows", action="store_true", help="session step time and tokens/s at --rows slots (--reps 5, --kv f16 for the recorded files)")
+    ap.add_argument("--kv", default="f32", choices=["f32", "f16"], help="K/V cache element type of the --many-rows legs")
+    ap.add_argument("--prompt", type=int, default=480, help="prompt ids per utterance of the --many-rows legs")
     args = ap.parse_args()
     if args.mixed:
         return mixed_main(args)
+    if args.many_rows:
+        return many_rows_main(args)
     have_session = hasattr(hip.OrpheusEngine, "stream_begin")
     cfg = synth.orpheus_3b(ctx=1024, weight_type=gguf.Q4_0)
     rng = np.random.default_rng(7)

@@ -2,6 +2,9 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o qgemm_bench profiles/qgemm_bench.hip && ./qgemm_bench [rows ...]
 // Every (shape, rows, tile, k-slices) combination is checked against a per-element device reference (block dots in integers, the block
 // terms added in k order in double) and timed over launches that cycle through NBUF weight copies, as gemm_bench.hip does.
+//   QGEMM_BENCH_MODEL=orpheus: the five Orpheus-3B shapes (K x N: 3072 x 5120, 3072 x 3072, 3072 x 16384, 8192 x 3072, 3072 x 156944) with 128 and 256
+//   rows, the five tile shapes the shim launches (shim_qtile.hip: QTILE_SHAPES) and 1 / 2 / 4 / 8 K slices on the two residual GEMMs; the weight copies
+//   fill 2 GB, so every launch streams its matrix from HBM as a decoder step does (profiles/orpheus_tile_shapes.txt).
 #include "../tts.cpp_amd/csrc/qgemm_tile_kernels.h"
 #include <cstdio>
 #include <cstdlib>
@@ -63,46 +66,55 @@ static Cfg cfgs[] = {
     CFG(64, 64, 2, 2, 2, 4, false), CFG(64, 64, 2, 2, 3, 3, true), CFG(64, 64, 2, 2, 4, 2, true), CFG(128, 64, 4, 2, 2, 4, false), CFG(128, 128, 4, 4, 2, 4, true), CFG(128, 128, 2, 4, 2, 3, true),
     CFG(128, 128, 2, 4, 3, 2, true), CFG(128, 128, 2, 4, 4, 2, true), CFG(256, 128, 4, 4, 2, 2, true),
     CFGK(64, 64, 2, 2, 2, 4, 2), CFGK(64, 64, 2, 2, 2, 4, 4), CFGK(128, 128, 2, 4, 2, 4, 2),
+    CFGK(128, 128, 2, 4, 2, 4, 1), CFGK(128, 64, 4, 2, 2, 4, 1), CFGK(64, 128, 2, 4, 2, 4, 1),   // shapes 1 - 3 of QTILE_SHAPES (0: the first entry, 4: 64x64 kg2)
 };
+static const char *shim_shapes[] = {"64x64/2x2/s2w4pfalse", "128x128/2x4/s2w4kg1", "128x64/4x2/s2w4kg1", "64x128/2x4/s2w4kg1", "64x64/2x2/s2w4kg2"};
 
 
 
 
 int main(int argc, char **argv) {
+    const bool orpheus = getenv("QGEMM_BENCH_MODEL") && !strcmp(getenv("QGEMM_BENCH_MODEL"), "orpheus");
     const int NBUF = getenv("GEMM_BENCH_NBUF") ? atoi(getenv("GEMM_BENCH_NBUF")) : 40;
-    struct Shape { const char *name; int N, K; bool splitk; } shapes[] = {
-        {"qkv", 3072, 1024, false}, {"proj", 1024, 1024, true}, {"fc1", 4096, 1024, false}, {"fc2", 1024, 4096, true}, {"heads", 9792, 1024, false}};
+    struct Shape { const char *name; int N, K; bool splitk; };
+    std::vector<Shape> shapes = {{"qkv", 3072, 1024, false}, {"proj", 1024, 1024, true}, {"fc1", 4096, 1024, false}, {"fc2", 1024, 4096, true}, {"heads", 9792, 1024, false}};
+    if (orpheus) shapes = {{"qkv", 5120, 3072, false}, {"o", 3072, 3072, true}, {"gu", 16384, 3072, false}, {"down", 3072, 8192, true}, {"head", 156944, 3072, false}};
     std::vector<int> Rs = {1024};
+    if (orpheus) Rs = {128, 256};
     if (argc > 1) { Rs.clear(); for (int i = 1; i < argc; i++) Rs.push_back(atoi(argv[i])); }
-    const int RMAXB = 1024, LDR = 1024;
-    const size_t wmax = (size_t) 9792 * 1024;
+    const int RMAXB = orpheus ? 256 : 1024, LDR = RMAXB, NMAX = orpheus ? 156944 : 9792;
+    // orpheus: every shape gets as many weight copies as fill 2 GB (nbuf below, at least one); wmax * NBUF is those 2 GB in bytes
+    const size_t wmax = orpheus ? ((size_t) 2 << 30) / NBUF : (size_t) 9792 * 1024;
     const int ldw_max = 9984;
     int8_t *W, *aq; _Float16 *wd; float *wdT, *adT, *X, *out, *ref, *fold;
     CK(hipMalloc(&W, wmax * NBUF));
     CK(hipMalloc(&wd, wmax / 32 * 2 * NBUF));
-    CK(hipMalloc(&wdT, (size_t) ldw_max * 128 * 4 * NBUF));
-    CK(hipMalloc(&X, (size_t) RMAXB * 4096 * 4));
-    CK(hipMalloc(&aq, (size_t) RMAXB * 4096));
-    CK(hipMalloc(&adT, (size_t) LDR * 128 * 4));
-    CK(hipMalloc(&out, (size_t) 8 * RMAXB * 9792 * 4));
-    CK(hipMalloc(&ref, (size_t) RMAXB * 9792 * 4));
-    CK(hipMalloc(&fold, (size_t) RMAXB * 9792 * 4));
+    // orpheus: a shape's copies hold at most 2 GB of codes = 2 GB / 32 scales of 4 bytes, plus the head's pad columns
+    CK(hipMalloc(&wdT, orpheus ? ((size_t) 2 << 30) / 8 + ((size_t) 64 << 20) : (size_t) ldw_max * 128 * 4 * NBUF));
+    const int KMAX = orpheus ? 8192 : 4096;
+    CK(hipMalloc(&X, (size_t) RMAXB * KMAX * 4));
+    CK(hipMalloc(&aq, (size_t) RMAXB * KMAX));
+    CK(hipMalloc(&adT, (size_t) LDR * (KMAX / 32) * 4));
+    CK(hipMalloc(&out, (size_t) (orpheus ? 1 : 8) * RMAXB * NMAX * 4));   // orpheus: 8 slabs of the N = 3072 GEMMs are smaller than the head's one
+    CK(hipMalloc(&ref, (size_t) RMAXB * NMAX * 4));
+    CK(hipMalloc(&fold, (size_t) RMAXB * NMAX * 4));
     fill_i8_kernel<<<(wmax * NBUF + 255) / 256, 256>>>(W, wmax * NBUF, 12345u, -127, 127);
     fill_h_kernel<<<(wmax / 32 * NBUF + 255) / 256, 256>>>(wd, wmax / 32 * NBUF, 99u, 0.01f);
-    fill_f_kernel<<<((size_t) RMAXB * 4096 + 255) / 256, 256>>>(X, (size_t) RMAXB * 4096, 777u, 3.0f);
-    CK(hipMemset(adT, 0, (size_t) LDR * 128 * 4));
+    fill_f_kernel<<<((size_t) RMAXB * KMAX + 255) / 256, 256>>>(X, (size_t) RMAXB * KMAX, 777u, 3.0f);
+    CK(hipMemset(adT, 0, (size_t) LDR * (KMAX / 32) * 4));
     CK(hipDeviceSynchronize());
     for (auto &c : cfgs) CK(hipFuncSetAttribute((const void *) c.k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     long long *stamps; CK(hipMalloc(&stamps, 8192 * 4 * 8)); std::vector<long long> h_st(8192 * 4);
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    std::vector<float> h_out((size_t) RMAXB * 9792), h_ref((size_t) RMAXB * 9792);
+    std::vector<float> h_out((size_t) RMAXB * NMAX), h_ref((size_t) RMAXB * NMAX);
     const char *only = getenv("QGEMM_BENCH_ONLY");
 
     for (auto &sh : shapes) {
         if (getenv("QGEMM_BENCH_SHAPE") && strcmp(getenv("QGEMM_BENCH_SHAPE"), sh.name)) continue;
         const int nb = sh.K / 32, ldw = (sh.N + 255) & ~255;
-        for (int i = 0; i < NBUF; i++)
+        const int nbuf = orpheus ? (int) std::max<size_t>(1, std::min<size_t>(40, ((size_t) 2 << 30) / ((size_t) sh.N * sh.K))) : NBUF;   // weight copies of this shape
+        for (int i = 0; i < nbuf; i++)
             transpose_scales_kernel<<<dim3((ldw + 255) / 256, nb), 256>>>(wd + (size_t) i * sh.N * nb, wdT + (size_t) i * ldw * nb, sh.N, nb, ldw);
         for (int R : Rs) {
             quant_rows_q8t_kernel<<<dim3((sh.K / 256 + 3) / 4, R), 256>>>(X, sh.K, sh.K, aq, adT, LDR, R);
@@ -114,11 +126,13 @@ int main(int argc, char **argv) {
             double best = 1e9; char bestname[64] = "";
             for (auto &c : cfgs) {
                 if (only && !strstr(only, c.name)) continue;
+                if (orpheus && std::none_of(std::begin(shim_shapes), std::end(shim_shapes), [&](const char *n) { return !strcmp(n, c.name); })) continue;
                 if (c.lds > 160 * 1024) continue;
-                for (int ks : {1, 2, 4}) {
+                for (int ks : {1, 2, 4, 8}) {
                     if (ks > 1 && !sh.splitk) continue;
-                    if (sh.K % (ks * 256)) continue;
-                    if (sh.K / ks > 1024 && !getenv("QGEMM_BENCH_LONGK") && sh.splitk && ks < 4 && sh.K > 1024) continue;
+                    if (ks == 8 && !orpheus) continue;
+                    if (sh.K % (ks * (orpheus ? 128 : 256))) continue;
+                    if (!orpheus && sh.K / ks > 1024 && !getenv("QGEMM_BENCH_LONGK") && sh.splitk && ks < 4 && sh.K > 1024) continue;
                     QTileArgs qa{};
                     qa.g.K = sh.K; qa.g.N = sh.N; qa.g.R = R; qa.g.out = out; qa.g.ldo = sh.N; qa.g.H = 1024;
                     qa.g.kchunk = ks > 1 ? sh.K / ks : 0; qa.g.slab_stride = (int64_t) R * sh.N;
@@ -126,8 +140,8 @@ int main(int argc, char **argv) {
                     TileMap tm{(R + c.BM - 1) / c.BM, (sh.N + c.BN - 1) / c.BN, ks};
                     const int total = tm.m_tiles * tm.n_tiles * ks, grid = (total + 7) / 8 * 8;
                     auto launch = [&](int i) {
-                        qa.g.W = W + (size_t) (i % NBUF) * sh.N * sh.K;
-                        qa.wdT = wdT + (size_t) (i % NBUF) * ldw * nb;
+                        qa.g.W = W + (size_t) (i % nbuf) * sh.N * sh.K;
+                        qa.wdT = wdT + (size_t) (i % nbuf) * ldw * nb;
                         hipLaunchKernelGGL(c.k, dim3(grid), dim3(c.threads), c.lds, 0, qa, tm);
                     };
                     CK(hipMemset(out, 0xFF, (size_t) ks * R * sh.N * 4));

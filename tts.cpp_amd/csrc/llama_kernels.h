@@ -25,6 +25,15 @@ __device__ __forceinline__ void q8_block_store(float v, int64_t idx, int8_t *aq,
     if ((idx & 31) == 0) ad[idx >> 5] = (float) (_Float16) dd;
 }
 
+// the same block for the tiled integer GEMM (qgemm_tile_kernels.h): codes [R][K] row-major, the scale into the transposed table float [K/32][ldr]
+__device__ __forceinline__ void q8t_block_store(float v, int r, int col, int K, int8_t *aq, float *adT, int ldr) {
+    const float amax = lanes32_max(fabsf(v));
+    const float dd = amax / 127.0f;
+    const float id = dd ? 1.0f / dd : 0.0f;
+    aq[(int64_t) r * K + col] = (int8_t) roundf(v * id);
+    if ((col & 31) == 0) adT[(int64_t) (col >> 5) * ldr + r] = (float) (_Float16) dd;
+}
+
 // one workgroup (4 waves) per row; the row (H <= 4096) is held in registers: every load of the row, the slabs and the weight is in
 // flight at once (the first version walked the row twice with dependent loads: 9.4 us for one 3072-wide row).
 // aq / ad (optional): the normalised row is also written as Q8_0 blocks (aq int8 [R][H], ad [R][H/32]) for an integer GEMV that
@@ -143,6 +152,66 @@ static __global__ __launch_bounds__(256) void rms_fold_rows_kernel(float *x, int
         const float o = xr[i] * scale * w[i];   // xr[i] was written by this thread
         y[(int64_t) r * H + i] = o;
         if (aq) q8_block_store(o, (int64_t) r * H + i, aq, ad);
+    }
+}
+
+// The same norm for a consumer on the tiled integer GEMM (forwards of 65 .. 256 rows, qgemm_tile_kernels.h): the pending slabs are folded into x as above, the
+// normalised row leaves as Q8_0 codes (aq int8 [R][H]) and TRANSPOSED block scales (adT float [H/32][ldr]) only — nobody reads the fp32 row.  H <= 4096 and
+// H % 32 == 0 (the host checks).  Loads as above: straight-line with clamped indices, none under `i < H`; a 3072-wide row takes eight slabs per round trip.
+static __global__ __launch_bounds__(256) void rms_fold_rows_q8t_kernel(float *x, int H, const float *w, int R, float eps, const float *parts, int n_parts, int64_t slab_stride,
+                                                                int8_t *aq, float *adT, int ldr) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    float *xr = x + (int64_t) r * H;
+    float v[16], wv[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const int i = min(tid + k * 256, H - 1);
+        v[k] = xr[i]; wv[k] = w[i];
+    }
+    if (parts) {
+        int p = 0;
+        if (H <= 3072) {
+            for (; p < n_parts; p += 8) {   // a slab beyond n_parts re-reads the last one and is never added; slab order kept
+                float t[8][12];
+#pragma unroll
+                for (int q = 0; q < 8; q++)
+#pragma unroll
+                    for (int k = 0; k < 12; k++) t[q][k] = parts[min(p + q, n_parts - 1) * slab_stride + (int64_t) r * H + min(tid + k * 256, H - 1)];
+#pragma unroll
+                for (int q = 0; q < 8; q++)
+#pragma unroll
+                    for (int k = 0; k < 12; k++)
+                        if (p + q < n_parts && tid + k * 256 < H) v[k] += t[q][k];
+            }
+        }
+        for (; p < n_parts; p++) {
+            float t[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) t[k] = parts[p * slab_stride + (int64_t) r * H + min(tid + k * 256, H - 1)];
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                if (tid + k * 256 < H) v[k] += t[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const int i = tid + k * 256;
+            if (i < H) xr[i] = v[k];
+        }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        if (tid + k * 256 < H) s += v[k] * v[k];
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    s = (red[0] + red[1]) + (red[2] + red[3]);
+    const float scale = 1.0f / sqrtf(s / (float) H + eps);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const int i = tid + k * 256;
+        if (i < H) q8t_block_store(v[k] * scale * wv[k], r, i, H, aq, adT, ldr);   // a wave's 32-lane halves are whole blocks
     }
 }
 
@@ -1525,4 +1594,20 @@ static __global__ void silu_mul_kernel(const float *gu, int F, int R, float *g, 
     const float o = (x / (1.0f + expf(-x))) * u;
     g[i] = o;
     if (aq) q8_block_store(o, i, aq, ad);
+}
+
+// the same product for a down projection on the tiled integer GEMM (65 .. 256 rows): gu is that GEMM's plain [R][2F] output (no slabs), the result
+// leaves as Q8_0 codes [R][F] and transposed block scales float [F/32][ldr] only.  grid (F / 1024, R); a lane holds 4 consecutive values, 8 neighbouring
+// lanes a block (quant4_q8: the arithmetic of quant_rows_q8t_kernel); F % 32 == 0, so a block's lanes pass the column bound together.
+static __global__ __launch_bounds__(256) void silu_mul_q8t_kernel(const float *gu, int F, int8_t *aq, float *adT, int ldr) {
+    const int r = blockIdx.y, c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= F) return;
+    const float4v x = *(const float4v *) (gu + (int64_t) r * 2 * F + c), u = *(const float4v *) (gu + (int64_t) r * 2 * F + F + c);
+    float4v o;
+#pragma unroll
+    for (int e = 0; e < 4; e++) o[e] = (x[e] / (1.0f + expf(-x[e]))) * u[e];
+    float dd;
+    const unsigned qq = quant4_q8(o, dd);
+    *(unsigned *) (aq + (int64_t) r * F + c) = qq;
+    if ((threadIdx.x & 7) == 0) adT[(int64_t) (c >> 5) * ldr + r] = dd;
 }

@@ -516,9 +516,10 @@ struct Planner {
             cur += (size_t) n_pad * (w.K / 32) * 2;
         }
         w.N += n_pad;
-        if (w.type == TTS_HIP_Q8I && c->has_parler && w.K % 128 == 0) {
+        if (w.type == TTS_HIP_Q8I && (c->has_parler || llama_many_rows(c)) && w.K % 128 == 0) {
             // the same scales transposed for the many-row kernel (qgemm_tile_kernels.h), written by tts_hip_finalize: part of the arena, so that
-            // contexts sharing it and ranks receiving it by broadcast hold them too
+            // contexts sharing it and ranks receiving it by broadcast hold them too.  Orpheus: only contexts of more than 64 slots (forwards of
+            // 65 .. 256 rows); a context of at most 64 slots plans the arena it always has
             w.ldw = (int) ((w.N + 255) & ~(int64_t) 255);
             w.stoff = alloc((size_t) (w.K / 32) * w.ldw * 4);
         }

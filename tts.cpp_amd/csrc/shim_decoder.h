@@ -11,3 +11,6 @@ int qstream_slab_rows(int R);
 int qstream_slices(const tts_hip_ctx *c, const W &w, int R, int max_slabs);
 int launch_qstream(tts_hip_ctx *c, int kclass, const W &w, int R, float *out, int ldo, int64_t slab_stride, int ks);
 int run_gemm(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int pro, int epi);
+// an Orpheus forward of 65 .. 256 rows on qgemm_tile_kernel: shape / k slices of a GEMM, and its launch on the codes in c->aq / c->adT
+void choose_llama_qtile(const tts_hip_ctx *c, int R, int N, int K, bool residual, int max_slabs, int *shape_out, int *ks_out);
+int run_qtile_rows(tts_hip_ctx *c, int kclass, const W &w, int R, float *out, int ldo, int epi, int shape, int ks, int64_t slab_stride);

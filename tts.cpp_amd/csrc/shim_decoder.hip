@@ -409,6 +409,7 @@ static int launch_stream(tts_hip_ctx *c, const GemmArgs &a, int pro, int epi) {
 // LayerNorm launch (ln_rows_q8t_kernel) or from quant_rows_q8t_kernel.
 // ------------------------------------------------------------------------------------------------
 static bool qtile_ok(const tts_hip_ctx *c, const W &w, const GemmArgs &a, int pro) {
+    if (c->has_llama) return false;   // an Orpheus forward routes its 65 .. 256 rows itself (llama_forward: run_qtile_rows)
     return c->qtile_min_rows > 0 && a.R >= c->qtile_min_rows && w.stoff && c->adT && w.K % 128 == 0 && w.N % 16 == 0 && pro != PRO_F16 && pro != PRO_ATTN && pro != PRO_CROSS &&
            a.R <= c->ldr && !a.kchunk && !a.n_parts && (pro != PRO_LN || (a.K <= 2048 && a.K % 32 == 0));
 }
@@ -479,6 +480,42 @@ static int run_qtile(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int pro
     if (q_out) { qa.q_out = qo.q; qa.d_out = qo.dT; qa.ldq = qo.ldq; }
     CHK(launch_qtile(c, qa, epi, shape, ks));
     if (q_out) { c->aqt_src = qo.stands_for; c->aqt_set = qo.q == c->aq2 ? 1 : 0; }
+    return prof_end(c);
+}
+
+// The tiled GEMMs of an Orpheus forward of 65 .. 256 rows (llama_forward).  Tile shape and k slices per GEMM class, from profiles/qgemm_bench.hip at the
+// five Orpheus-3B shapes with 128 and 256 rows (profiles/orpheus_tile_shapes.txt).  residual: the GEMM may leave split-K slabs (o / down projection,
+// folded by the next rms_fold_rows_q8t_kernel); max_slabs: what the slab buffer holds.
+void choose_llama_qtile(const tts_hip_ctx *c, int R, int N, int K, bool residual, int max_slabs, int *shape_out, int *ks_out) {
+    const int tiles = ((R + 63) / 64) * ((N + 63) / 64);
+    // the head (4906 / 9812 tiles of 64 x 64 at 128 / 256 rows): 128 x 128 tiles, 243 / 420 us against 268 / 464; gate | up at 256 rows (1024 tiles): 64 x 128,
+    // 54.5 us against 57.9; below that (qkv: 160 / 320 tiles, gate | up at 128 rows: 512) two k groups in a 64 x 64 workgroup, 21.5 / 28.2 us against 26.8 / 30.6
+    int shape = tiles >= 2048 ? 1 : tiles >= 768 ? 3 : 4, ks = 1;
+    if (residual) {
+        // N = hidden size: 96 / 192 tiles on 256 CUs.  Plain 64 x 64 tiles and K slices until about 768 workgroups exist: o 25.7 -> 11.4 us (4 slices, 128 rows) and
+        // 26.1 -> 15.4 (4 slices, 256 rows), down 62.7 -> 18.5 (8 slices, 128 rows) and 62.9 -> 29.4 (4 slices, 256 rows)
+        shape = 0;
+        while (ks * 2 <= max_slabs && tiles * ks < 768 && K % (ks * 2 * 128) == 0) ks *= 2;
+    }
+    if (c->qtile_shape >= 0 && c->qtile_shape < N_QTILE_SHAPES) shape = c->qtile_shape;
+    if (c->qtile_ks > 0 && residual) {   // tune("qtile_ks"): clamped to the slab budget and to what K allows
+        ks = std::min(c->qtile_ks, max_slabs);
+        while (ks > 1 && K % (ks * 128)) ks--;
+    }
+    *shape_out = shape;
+    *ks_out = ks;
+}
+// activations: the Q8_0 codes in c->aq and the transposed scales in c->adT (written by the producing kernel); ks > 1: slab kz of `out` (slab_stride floats
+// apart) receives the partial products of K slice kz and epi is EPI_STORE
+int run_qtile_rows(tts_hip_ctx *c, int kclass, const W &w, int R, float *out, int ldo, int epi, int shape, int ks, int64_t slab_stride) {
+    QTileArgs qa{};
+    qa.g.W = c->arena + w.off; qa.g.K = (int) w.K; qa.g.N = (int) w.N; qa.g.R = R; qa.g.H = c->H; qa.g.out = out; qa.g.ldo = ldo;
+    if (ks > 1) { qa.g.kchunk = (int) w.K / ks; qa.g.slab_stride = slab_stride; }
+    qa.wdT = (const float *) (c->arena + w.stoff);
+    qa.ldw = w.ldw;
+    qa.aq = c->aq; qa.adT = c->adT; qa.ldr = c->ldr;
+    CHK(prof_begin(c, kclass, (double) w.K * w.N * (1.0 + 2.0 / 32) + (double) R * w.K * 1.125 + (double) ks * R * w.N * 4, 2.0 * R * (double) w.K * w.N));
+    CHK(launch_qtile(c, qa, epi, shape, ks));
     return prof_end(c);
 }
 
@@ -977,6 +1014,13 @@ static int compute_cross_kv(tts_hip_ctx *c) {
 
 // the block scales of the Parler decoder's quantised matrices once more, transposed, for qgemm_tile_kernel (arena space reserved by the planner)
 static int derive_scale_tables(tts_hip_ctx *c) {
+    if (llama_many_rows(c)) {   // an Orpheus context of more than 64 slots: qkv, o, gate | up, down and the LM head
+        HIPCHK(hipSetDevice(c->device));
+        for (const auto &y : c->l_layers)
+            for (const W *w : {&y.qkv, &y.o, &y.gu, &y.down}) CHK(qtile_transpose_scales(c, *w));
+        CHK(qtile_transpose_scales(c, c->l_head));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     if (!c->has_parler) return 0;
     HIPCHK(hipSetDevice(c->device));
     for (const PLayer &y : c->layers)
@@ -1093,8 +1137,14 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         c->attn_part_cap = (size_t) 4 * c->NH * 16;   // up to 4 rows x heads x 16 splits (more rows take the unsplit kernel)
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
         CHK(dmalloc(&c->attn_cnt, (size_t) 256 + c->NH));   // arrival counters of the split attention's in-kernel merge (rows x heads <= 256)
-        CHK(dmalloc((char **) &c->l_kc, kvb));   // ggml_backend_buffer_clear(buf, 0), orpheus/model.cpp:181
-        CHK(dmalloc((char **) &c->l_vc, kvb));
+        // ggml_backend_buffer_clear(buf, 0), orpheus/model.cpp:181
+        if (hipMalloc((void **) &c->l_kc, kvb) != hipSuccess || hipMalloc((void **) &c->l_vc, kvb) != hipSuccess) {
+            (void) hipGetLastError();
+            return set_err("tts_hip_finalize: the K/V cache of %zu slots does not fit: 2 x %zu bytes asked for (%s; fewer slots, or TTS_HIP_KV_F16 halves it)", S, kvb,
+                           c->l_kv_esz == 2 ? "fp16 cache" : "fp32 cache");
+        }
+        HIPCHK(hipMemset(c->l_kc, 0, kvb));
+        HIPCHK(hipMemset(c->l_vc, 0, kvb));
         const int R = c->RMAX;
         CHK(dmalloc(&c->l_x, (size_t) R * H));
         CHK(dmalloc(&c->l_xn, (size_t) R * H));
@@ -1111,6 +1161,11 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         CHK(dmalloc(&c->dbg, (size_t) R * std::max(H, F)));
         CHK(dmalloc(&c->aq, (size_t) R * std::max(std::max(H, F), c->NH * (int) c->lm.head_dim)));
         CHK(dmalloc(&c->ad, (size_t) R * std::max(std::max(H, F), c->NH * (int) c->lm.head_dim) / 32 + 1));
+        if (llama_many_rows(c) && c->l_head.stoff + (c->l_layers.empty() ? 0 : c->l_layers[0].qkv.stoff + c->l_layers[0].o.stoff + c->l_layers[0].gu.stoff + c->l_layers[0].down.stoff)) {
+            // forwards of 65 .. 256 rows on the tiled integer GEMM: the activation scales transposed, float [K / 32][ldr]; the codes share aq ([RMAX][widest K])
+            c->ldr = R;
+            CHK(dmalloc(&c->adT, (size_t) c->ldr * (std::max(std::max(H, F), c->NH * (int) c->lm.head_dim) / 32)));
+        }
         CHK(dmalloc(&c->l_ids, (size_t) R));
         CHK(dmalloc(&c->l_pos, (size_t) R));
         CHK(dmalloc(&c->l_tok, (size_t) 1 + 2 * ARGMAX_PARTS + LLAMA_GREEDY_CHUNK + 1));
@@ -2515,6 +2570,14 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
     if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, or 2 under TTS_HIP_FLAG_KV_F16
         if (max_floats < 1) { set_err("debug_read(l_kv_elem): buffer too small"); return -1; }
         out[0] = (float) c->l_kv_esz;
+        return 1;
+    }
+    if (c->has_llama && w == "l_tile_tables") {   // how many matrices hold a transposed scale table for qgemm_tile_kernel (0 in a context of at most 64 slots)
+        if (max_floats < 1) { set_err("debug_read(l_tile_tables): buffer too small"); return -1; }
+        int n = c->l_head.stoff ? 1 : 0;
+        for (const auto &y : c->l_layers)
+            for (const W *m : {&y.qkv, &y.o, &y.gu, &y.down}) n += m->stoff ? 1 : 0;
+        out[0] = (float) n;
         return 1;
     }
     if (c->has_llama && (w == "l_q" || w == "l_att")) {   // the last layer's attention of the last forward: the rotated queries it read / the rows it left, [rows][NH * head_dim]

@@ -62,7 +62,7 @@ struct W {  // a matrix living in the arena
     int64_t K = 0, N = 0;
     bool src_q4 = false;            // every stacked source tensor was Q4_0 in the GGUF
     const uint8_t *q4 = nullptr;    // TTS_HIP_Q4_NATIVE: the 4-bit codes repacked next to the int8 expansion (gemv_q4_rows_kernel)
-    size_t stoff = 0;               // TTS_HIP_Q8I matrices of the Parler decoder: the block scales once more, transposed (float [K/32][ldw]) for qgemm_tile_kernel
+    size_t stoff = 0;               // TTS_HIP_Q8I matrices of the Parler decoder and of Orpheus contexts of more than 64 slots: the block scales once more, transposed (float [K/32][ldw]) for qgemm_tile_kernel
     int ldw = 0;
 };
 
@@ -517,6 +517,11 @@ static int capture_graph(tts_hip_ctx *c, int key, F enqueue, hipGraphExec_t *out
     return 0;
 }
 
+// Orpheus contexts of more than LLAMA_STREAM_ROWS slots carry forwards of 65 .. LLAMA_MAX_SEQS rows: their quantised matrices get the transposed scale
+// tables and the forward routes those rows to qgemm_tile_kernel.  Contexts of at most 64 slots plan, allocate and launch what they always have.
+enum { LLAMA_STREAM_ROWS = 64, LLAMA_MAX_SEQS = 256 };
+static inline bool llama_many_rows(const tts_hip_ctx *c) { return c->has_llama && c->lm.max_seqs > LLAMA_STREAM_ROWS; }
+
 // ---- shim_core.hip
 void free_dev(void *p);
 void arena_own(tts_hip_ctx *c);
@@ -534,6 +539,7 @@ int stage_uniforms(tts_hip_ctx *c, const float *uniforms, size_t count);
 int stage_penalty(tts_hip_ctx *c, float penalty, int n);
 // ---- shim_qtile.hip (the tiled integer GEMM: its own unit, built without SLP vectorisation and with MFMA results in VGPRs)
 int qtile_transpose_scales(tts_hip_ctx *c, const W &w);
+int qtile_quant_rows(tts_hip_ctx *c, const float *x, int lda, int K, int R);   // fp32 rows -> Q8_0 blocks in c->aq / c->adT
 // ---- shim_codec.hip
 int dac_row_stride(const tts_hip_ctx *c, int L);
 

@@ -24,7 +24,9 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
     c->lm = *ld;
     if (ld->flags & TTS_HIP_FLAG_KV_F16) c->l_kv_esz = 2;
     if (c->lm.max_seqs == 0) c->lm.max_seqs = 1;
-    if (c->lm.max_seqs > 64) { set_err("tts_hip_orpheus_create: max_seqs %u > 64", c->lm.max_seqs); tts_hip_destroy(c); return nullptr; }
+    // up to 64 slots: the streaming kernels carry every step.  65 .. 256 (= RMAX, the rows of one forward): the steps of more than 64 rows run on the
+    // LDS-tiled integer GEMM (llama_forward); such a context plans the transposed scale tables into its arena
+    if (c->lm.max_seqs > LLAMA_MAX_SEQS) { set_err("tts_hip_orpheus_create: max_seqs %u > %d", c->lm.max_seqs, (int) LLAMA_MAX_SEQS); tts_hip_destroy(c); return nullptr; }
     // measured on MI355X at the orpheus-3b Q4_0 shapes (profiles/r02/first_call_orpheus_*.log): 3.84 ms/step through the
     // lock-step workgroups, 2.98 with the streaming 1-4 row kernels, 2.84 reading the Q4_0 codes themselves, 2.80 with the
     // step captured in one hipGraph -> all three are the default here; TTS_HIP_GEMV_ROWS / _Q4_NATIVE / _LLAMA_GRAPH=0 turn them off
@@ -127,7 +129,8 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     const int H = c->H, F = c->F, NH = c->NH, NKV = (int) c->lm.n_kv_heads, HD = (int) c->lm.head_dim;
     const int QKV = (NH + 2 * NKV) * HD, NCTX = (int) c->lm.n_ctx;
     if (n < 1 || n > c->RMAX) return set_err("tts_hip_orpheus_decode: %d tokens per call outside 1..%d", n, c->RMAX);
-    if (pos0 + (uint32_t) n > (uint32_t) NCTX) return set_err("tts_hip_orpheus_decode: positions up to %u exceed the %d cached positions", pos0 + n, NCTX);
+    // (lock-step rows carry their own positions, checked by llama_stage_rows: more rows than cached positions is fine there)
+    if (!row_seq && pos0 + (uint32_t) n > (uint32_t) NCTX) return set_err("tts_hip_orpheus_decode: positions up to %u exceed the %d cached positions", pos0 + n, NCTX);
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
     if (ids) {
         std::vector<uint32_t> hp((size_t) n);
@@ -167,7 +170,38 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
         if (launch_qstream(c, TTS_HIP_K_GEMM_OTHER, w, n, out, ldo, slab_stride, ks) != 0) return -1;
         return ks;
     };
+    // 65 .. 256 rows of a context of more than 64 slots on a quantised matrix: one qgemm_tile_kernel launch over all rows (65 is where qgemv_stream_kernel
+    // ends).  Its operands are Q8_0 codes [n][K] in aq and TRANSPOSED block scales in adT, written by the producer: rms_fold_rows_q8t_kernel (qkv, gate | up,
+    // the head), silu_mul_q8t_kernel (down), quant_rows_q8t_kernel on the attention's rows (o).  tune("qtile_min_rows") = 0: the 16-feature kernel as before.
+    auto tiled = [&](const W &w) {
+        return c->adT && w.stoff && H <= 4096 && n > LLAMA_STREAM_ROWS && c->qtile_min_rows > 0 && n >= c->qtile_min_rows && !(c->d.flags & (TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q));
+    };
+    // o / down projection: K slices as slabs in l_parts ([8][RMAX][H]) that the next rms norm folds, or the residual add in the epilogue
+    auto tile_resid = [&](const W &w) {
+        int shape, ks;
+        choose_llama_qtile(c, n, (int) w.N, (int) w.K, true, 8, &shape, &ks);
+        if (ks > 1) {
+            CHK(run_qtile_rows(c, TTS_HIP_K_GEMM_OTHER, w, n, c->l_parts, H, EPI_STORE, shape, ks, (int64_t) c->RMAX * H));
+            c->l_pending = ks; c->l_pstride = (int64_t) c->RMAX * H;
+            return 0;
+        }
+        return run_qtile_rows(c, TTS_HIP_K_GEMM_OTHER, w, n, c->l_x, H, EPI_RESID, shape, 1, 0);
+    };
+    auto tile_store = [&](int kclass, const W &w, float *out, int ldo) {
+        int shape, ks;
+        choose_llama_qtile(c, n, (int) w.N, (int) w.K, false, 1, &shape, &ks);
+        return run_qtile_rows(c, kclass, w, n, out, ldo, EPI_STORE, shape, 1, 0);
+    };
     auto rms = [&](size_t w_off, int rows, float *x, float *y, const W *next, int bit = 0) {
+        if (next && rows == n && tiled(*next)) {
+            // y (l_xn) is not written on this path: the consumer reads the codes, and no debug_read item reads l_xn
+            hipLaunchKernelGGL(rms_fold_rows_q8t_kernel, dim3(rows), dim3(256), 0, c->stream, x, H, f32(w_off), rows, 1e-5f,
+                               c->l_pending ? (const float *) c->l_parts : (const float *) nullptr, c->l_pending, c->l_pstride ? c->l_pstride : (int64_t) c->RMAX * H,
+                               c->aq, c->adT, c->ldr);
+            c->l_pending = 0; c->l_pstride = 0;
+            c->aq_src = nullptr;
+            return hipGetLastError() == hipSuccess ? 0 : set_err("rms_fold_rows_q8t_kernel launch failed");
+        }
         const bool q = next && q_for(*next, rows, bit);
         hipLaunchKernelGGL(rms_fold_rows_kernel, dim3(rows), dim3(256), 0, c->stream, x, H, f32(w_off), y, rows, 1e-5f,
                            c->l_pending ? (const float *) c->l_parts : (const float *) nullptr, c->l_pending, c->l_pstride ? c->l_pstride : (int64_t) c->RMAX * H,
@@ -214,7 +248,10 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
             CHK(rms(y.in_norm, n, c->l_x, c->l_xn, &y.qkv, QS_QKV));
             const int sl = qstream(y.qkv, QS_QKV, c->l_xn, H, c->l_qkv, QKV, (int64_t) srows * QKV, smax);   // slabs of srows rows inside l_qkv ([RMAX][QKV])
             if (sl < 0) return -1;
-            if (!sl) CHK(llama_gemm(c, y.qkv, c->l_xn, H, c->l_qkv, QKV, n, EPI_STORE));
+            if (!sl) {
+                if (tiled(y.qkv)) CHK(tile_store(TTS_HIP_K_GEMM_OTHER, y.qkv, c->l_qkv, QKV));
+                else CHK(llama_gemm(c, y.qkv, c->l_xn, H, c->l_qkv, QKV, n, EPI_STORE));
+            }
             if (kv16)
                 hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc16, vc16,
                                    row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
@@ -234,6 +271,10 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
             const int sl = qstream(y.o, QS_O, c->l_att, NH * HD, c->l_parts, H, (int64_t) srows * H, pmax);   // slabs of srows rows inside l_parts ([8][RMAX][H]), folded into the residual stream by the next rms norm
             if (sl < 0) return -1;
             if (sl) { c->l_pending = sl; c->l_pstride = (int64_t) srows * H; }
+            else if (tiled(y.o)) {
+                CHK(qtile_quant_rows(c, c->l_att, NH * HD, NH * HD, n));   // the attention's rows -> codes and transposed scales, a launch of its own
+                CHK(tile_resid(y.o));
+            }
             else CHK(llama_gemm(c, y.o, c->l_att, NH * HD, c->l_x, H, n, EPI_RESID));
         }
         const size_t gu_lds = (size_t) n * H + (size_t) n * (H / 32) * 4, dn_lds = (size_t) n * F + (size_t) n * (F / 32) * 4;
@@ -270,7 +311,17 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
         }
         const int slg = qstream(y.gu, QS_GU, c->l_xn, H, c->l_gu, 2 * F, (int64_t) srows * 2 * F, smax);   // slabs of srows rows inside l_gu; silu_mul_kernel folds them
         if (slg < 0) return -1;
-        if (!slg) CHK(llama_gemm(c, y.gu, c->l_xn, H, c->l_gu, 2 * F, n, EPI_STORE));
+        if (!slg) {
+            if (tiled(y.gu)) CHK(tile_store(TTS_HIP_K_GEMM_OTHER, y.gu, c->l_gu, 2 * F));
+            else CHK(llama_gemm(c, y.gu, c->l_xn, H, c->l_gu, 2 * F, n, EPI_STORE));
+        }
+        if (tiled(y.down) && F % 32 == 0) {
+            hipLaunchKernelGGL(silu_mul_q8t_kernel, dim3((F + 1023) / 1024, n), dim3(256), 0, c->stream, (const float *) c->l_gu, F, c->aq, c->adT, c->ldr);
+            HIPCHK(hipGetLastError());
+            c->aq_src = nullptr;
+            CHK(tile_resid(y.down));
+            continue;
+        }
         const bool down_stream = slices(y.down, QS_DOWN, n, pmax) != 0;
         const int ks = ((c->gemv_rows && n <= 4) || down_stream) ? 1 : c->l_ksplit;   // the streaming kernels walk all of K themselves
         const bool qd = ks == 1 && q_for(y.down, n, QS_DOWN);
@@ -291,7 +342,9 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     }
     // lm_head on the last token only (:287-290) — or, for lock-step utterances, on every row (each row is an utterance's last token)
     const bool head_stream = logits_row < 0 && slices(c->l_head, QS_HEAD, n, 1) != 0;
-    CHK(rms(c->l_out_norm, n, c->l_x, c->l_xn, head_stream ? &c->l_head : nullptr, QS_HEAD));
+    const bool head_tiled = logits_row < 0 && tiled(c->l_head);   // every row's logits: N = Vpad is no multiple of the tile width, the last tile's stores stop at Vpad
+    CHK(rms(c->l_out_norm, n, c->l_x, c->l_xn, (head_stream || head_tiled) ? &c->l_head : nullptr, QS_HEAD));
+    if (head_tiled) return tile_store(TTS_HIP_K_GEMM_HEADS, c->l_head, c->l_logits, c->l_Vpad);
     if (head_stream) {   // lock-step utterances, 5 .. 16 of them: the head streams once, whole K per wave (no slabs)
         const int sl = qstream(c->l_head, QS_HEAD, c->l_xn, H, c->l_logits, c->l_Vpad, 0, 1);
         if (sl < 0) return -1;

@@ -70,7 +70,8 @@ int qtile_transpose_scales(tts_hip_ctx *c, const W &w) {
 }
 
 int qtile_quant_rows(tts_hip_ctx *c, const float *x, int lda, int K, int R) {
-    hipLaunchKernelGGL(quant_rows_q8t_kernel, dim3((K / 256 + 3) / 4, R), dim3(256), 0, c->stream, x, lda, K, c->aq, c->adT, c->ldr, R);
+    // a workgroup covers 1024 columns (today every caller's K is a multiple of 256: the upload keeps integer codes for such matrices only)
+    hipLaunchKernelGGL(quant_rows_q8t_kernel, dim3((K + 1023) / 1024, R), dim3(256), 0, c->stream, x, lda, K, c->aq, c->adT, c->ldr, R);
     HIPCHK(hipGetLastError());
     return 0;
 }

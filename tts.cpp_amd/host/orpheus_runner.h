@@ -107,7 +107,7 @@ struct orpheus_runner final : orpheus_session {
     orpheus_hparams                hp;
     std::unique_ptr<bpe_tokenizer> tokenizer;
     sampler                        smp;
-    uint32_t                       max_seqs = 1;     // cache slots of the decoder context (tts_load_options::max_seqs, at most 64)
+    uint32_t                       max_seqs = 1;     // cache slots of the decoder context (tts_load_options::max_seqs, at most 256)
     tts_hip_ctx *                  lm = nullptr;     // Llama-3 decoder context
     tts_hip_ctx *                  snac = nullptr;   // SNAC codec context
     std::vector<float>             pcm, logits;

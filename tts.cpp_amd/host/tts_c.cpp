@@ -259,6 +259,7 @@ void tts_c_set_load_options_ex(int device, int max_seqs, int declare_only, tts_c
 }
 void * tts_c_runner_device_context(tts_c_runner * r) { return r ? ((tts_generation_runner *) r)->device_context() : nullptr; }
 uint32_t tts_c_runner_kv_element_bytes(tts_c_runner * r) { return r ? ((tts_generation_runner *) r)->kv_element_bytes() : 0; }
+uint32_t tts_c_runner_stream_capacity(tts_c_runner * r) { return r ? ((tts_generation_runner *) r)->stream_capacity() : 0; }
 int tts_c_runner_tokenize(tts_c_runner * r, const char * text, uint32_t * out, int cap) {
     g_tts_throw_on_abort = true;
     try {

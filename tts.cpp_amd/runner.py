@@ -33,7 +33,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
            "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs", "tts_c_generate_stream_chunked_configs",
-           "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes"]
+           "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes", "tts_c_runner_stream_capacity"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -114,6 +114,8 @@ def load_lib():
         L.tts_c_runner_device_context.restype = C.c_void_p
         L.tts_c_runner_kv_element_bytes.argtypes = [C.c_void_p]
         L.tts_c_runner_kv_element_bytes.restype = C.c_uint32
+        L.tts_c_runner_stream_capacity.argtypes = [C.c_void_p]
+        L.tts_c_runner_stream_capacity.restype = C.c_uint32
         L.tts_c_runner_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]
         L.tts_c_pool_free.restype = None
         L.tts_c_generate_chunked.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Config), C.c_uint32, CHUNK_FN, C.c_void_p]
@@ -273,6 +275,10 @@ class Runner:
     def kv_element_bytes(self):
         """bytes per element of the decoder's K/V cache (Orpheus: 4, or 2 with TTS_HIP_KV_F16 in the environment at load); 0: not reported"""
         return int(self.L.tts_c_runner_kv_element_bytes(self.h))
+
+    def stream_capacity(self):
+        """utterances a continuous session of this runner holds at once (0: no session)"""
+        return int(self.L.tts_c_runner_stream_capacity(self.h))
 
     def update_conditional_prompt(self, text_encoder_path, prompt):
         if self.L.tts_c_update_conditional_prompt(self.h, text_encoder_path.encode(), prompt.encode("utf-8")) != 0:
