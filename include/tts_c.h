@@ -212,6 +212,18 @@ int64_t tts_c_dia_adjust_output_tokens(const uint32_t *tokens, uint64_t n_ids, u
 int64_t tts_c_dia_final_frames(const uint32_t *tokens, uint64_t n_steps, uint32_t audio_vocab, uint32_t max_delay, uint64_t piece, uint32_t *out,
                                uint64_t cap_frames);
 
+/* ---- chunked audio, host logic callable without a device: the planner the Parler and Dia runners cut their codec windows with
+ * (host/chunk_windows.h).  rule 0: Parler's un-delay over tokens[n_steps][n_heads] (audio_vocab; max_delay unused), 1: Dia's over
+ * tokens[n_steps][9] (audio_vocab, max_delay; n_heads unused) — the arguments of the two *_final_frames calls.  The stream is fed to the planner
+ * in pieces of `piece` steps (0: all at once), each a look-in of a generation that is still running, then once more marked finished.  Every
+ * window cut, in order: windows[i] = (w0, w1, keep0, keep1) — the codec decodes frames [w0, w1) of the kept-frame sequence and keeps
+ * [w0 + keep0, w0 + keep1) of them, as tts_hip_dac_decode_windows takes it; cut_at[i] = (steps fed when it was cut, 1 if that was the finished
+ * call); codes = the kept frames' codes of all windows back to back, [*n_kept][heads].  windows, cut_at and codes may be NULL; at most
+ * cap_windows windows and cap_frames frames are written.  Returns the number of windows, -1 on a bad argument. */
+int64_t tts_c_chunk_windows(int rule, const uint32_t *tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, uint32_t max_delay, uint32_t halo,
+                            uint32_t chunk_frames, uint64_t piece, uint32_t *windows, uint32_t *cut_at, uint64_t cap_windows, uint32_t *codes,
+                            uint64_t cap_frames, uint64_t *n_kept);
+
 /* ---- Kokoro host logic, callable without a device (host/kokoro_runner.h; reference src/tokenizer.cpp:159-177,
  * src/models/kokoro/model.cpp:1340-1388) ------------------------------------------------------------------------------
  * single_pass_tokenizer::tokenize over the given vocabulary; returns the number of ids (out may be NULL to count) */

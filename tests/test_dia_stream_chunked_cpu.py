@@ -68,8 +68,26 @@ def test_new_entry_points_refuse_a_null_context():
 
 
 def test_dia_runner_overrides_the_chunk_hook():
-    """a Dia runner cannot be loaded without a device, so the override is checked where it is declared"""
-    runner_h = open(os.path.join(ROOT, "tts.cpp_amd", "host", "dia_runner.h")).read()
-    assert re.search(r"\bbool\s+stream_chunks\([^;]*\)\s+override\s*;", runner_h)
-    for other in ("parler_runner.h", "orpheus_runner.h"):               # their sessions hand out whole utterances
-        assert "stream_chunks" not in open(os.path.join(ROOT, "tts.cpp_amd", "host", other)).read(), other
+    """a runner cannot be loaded without a device, so the override is checked where it is declared: once, in the base the three session runners
+    share (host/stream_session.h), with each runner's part behind the pure session_chunks_ready.  Parler's part is an opt-in: that its session
+    hands out whole utterances without TTS_PARLER_STREAM_CHUNKS is held on the device by
+    tests/test_gpu_dia_stream_chunked.py::test_sessions_that_do_not_chunk_hand_out_whole_utterances; here the switch is checked to be in place."""
+    host = os.path.join(ROOT, "tts.cpp_amd", "host")
+    session_h = open(os.path.join(host, "stream_session.h")).read()
+    assert len(re.findall(r"\bbool\s+stream_chunks\([^;]*\)\s+override\s*;", session_h)) == 1
+    assert re.search(r"struct\s+stream_session\s*:\s*tts_generation_runner\b", session_h)
+    assert re.search(r"virtual\s+bool\s+session_chunks_ready\([^;]*\)\s*=\s*0\s*;", session_h)
+    for name in ("dia", "parler", "orpheus"):
+        runner_h = open(os.path.join(host, name + "_runner.h")).read()
+        assert '#include "stream_session.h"' in runner_h, name
+        assert re.search(r"struct\s+%s_runner\s+final\s*:\s*stream_session\b" % name, runner_h), name
+        assert re.search(r"\bbool\s+session_chunks_ready\([^;]*\)\s+override\s*;", runner_h), name
+        assert not re.search(r"\bstream_chunks\s*\(", open(os.path.join(host, name + "_runner.cpp")).read()), name   # no hook of its own
+    parler_cpp = open(os.path.join(host, "parler_runner.cpp")).read()
+    ready = parler_cpp[parler_cpp.index("bool parler_runner::session_chunks_ready("):]
+    ready = ready[:ready.index("\n}\n")]
+    assert 'getenv("TTS_PARLER_STREAM_CHUNKS")' in ready and "return false" in ready
+    common = open(os.path.join(host, "common.h")).read()
+    at = common.index("virtual bool     stream_chunks(")
+    note = common[common.rindex("// chunked audio out of a session", 0, at):at]
+    assert "TTS_PARLER_STREAM_CHUNKS" in note and "opt-in" in note and "no halo" in note

@@ -1,6 +1,6 @@
 """Chunked audio out of the Orpheus continuous session, without a device: the C ABI declares and exports the three new entry points, libtts.so
-calls them, hip.py binds them, every one answers a NULL context with an error that names it, and the session's chunk hook is overridden in
-host/orpheus_session.h (orpheus_runner.h must not spell the hook: tests/test_dia_stream_chunked_cpu.py)."""
+calls them, hip.py binds them, every one answers a NULL context with an error that names it, and the session's chunk hook is overridden once,
+in host/stream_session.h, the base the three session runners share; orpheus_runner supplies its part, session_chunks_ready."""
 import ctypes as C
 import os
 import re
@@ -60,13 +60,15 @@ def test_new_entry_points_refuse_a_null_context():
 
 def test_orpheus_session_header_declares_the_override():
     """an Orpheus runner cannot be loaded without a device, so the override is checked where it is declared"""
-    session_h = open(os.path.join(HOST, "orpheus_session.h")).read()
-    assert re.search(r"\bbool\s+stream_chunks\([^;]*\)\s+override\s*;", session_h)
-    assert re.search(r"struct\s+orpheus_session\s*:\s*tts_generation_runner\b", session_h)
+    session_h = open(os.path.join(HOST, "stream_session.h")).read()
+    assert len(re.findall(r"\bbool\s+stream_chunks\([^;]*\)\s+override\s*;", session_h)) == 1
+    assert re.search(r"struct\s+stream_session\s*:\s*tts_generation_runner\b", session_h)
+    assert re.search(r"virtual\s+bool\s+session_chunks_ready\([^;]*\)\s*=\s*0\s*;", session_h)
     runner_h = open(os.path.join(HOST, "orpheus_runner.h")).read()
-    assert '#include "orpheus_session.h"' in runner_h
-    assert re.search(r"struct\s+orpheus_runner\s+final\s*:\s*orpheus_session\b", runner_h)
-    assert "stream_chunks" not in runner_h
+    assert '#include "stream_session.h"' in runner_h
+    assert re.search(r"struct\s+orpheus_runner\s+final\s*:\s*stream_session\b", runner_h)
+    assert re.search(r"\bbool\s+session_chunks_ready\([^;]*\)\s+override\s*;", runner_h)
+    assert not re.search(r"\bstream_chunks\s*\(", open(os.path.join(HOST, "orpheus_runner.cpp")).read())   # no hook of its own beside the base's
     common = open(os.path.join(HOST, "common.h")).read()
     at = common.index("virtual bool     stream_chunks(")
     note = common[common.rindex("// chunked audio out of a session", 0, at):at]

@@ -64,7 +64,16 @@ def test_engine_binds_the_two_calls():
 
 
 def test_parler_runner_overrides_the_per_request_virtuals():
+    """... and its session hands out whole utterances unless chunks are opted into: the behaviour is held on the device by
+    tests/test_gpu_dia_stream_chunked.py::test_sessions_that_do_not_chunk_hand_out_whole_utterances (Parler without TTS_PARLER_STREAM_CHUNKS);
+    here common.h's note and the runner are checked to carry the switch"""
     text = _read("tts.cpp_amd", "host", "parler_runner.h")
     assert re.search(r"bool\s+stream_accepts\(const generation_configuration &\s*\w*\)\s*const\s+override;", text)
     assert re.search(r"void\s+stream_submit\(size_t \w+, const std::string &\s*\w+, const generation_configuration &\s*\w*\)\s*override;", text)
-    assert "stream_chunks" not in text   # the session hands out whole utterances, as before
+    common = _read("tts.cpp_amd", "host", "common.h")
+    at = common.index("virtual bool     stream_chunks(")
+    note = common[common.rindex("// chunked audio out of a session", 0, at):at]
+    assert "TTS_PARLER_STREAM_CHUNKS" in note and "opt-in" in note and "does not chunk (parler_runner)" in note
+    source = _read("tts.cpp_amd", "host", "parler_runner.cpp")
+    ready = source[source.index("bool parler_runner::session_chunks_ready("):]
+    assert re.search(r'getenv\("TTS_PARLER_STREAM_CHUNKS"\);\s*if \(!on \|\| !\*on \|\| !strcmp\(on, "0"\)\) return false;', ready[:ready.index("\n}\n")])

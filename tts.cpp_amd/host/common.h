@@ -152,11 +152,13 @@ struct tts_generation_runner : tts_runner {
     // utterance's PCM to on_chunk(ticket, pcm, n) in consecutive pieces of at most chunk_frames codec frames while the rows keep running; an
     // utterance appears in `finished` — with empty audio — once its last piece is out, and stream_live() counts it until then.  on_chunk
     // returning false drops that utterance only: it is reported in `finished` with what it got, the others go on.  The default returns false:
-    // this runner's session does not chunk (parler_runner) holds for a Parler codec layout that reports no halo and, by default, for every
-    // other: its override, declared in parler_session.h, chunks when TTS_PARLER_STREAM_CHUNKS is set in the environment (an opt-in: the
-    // whole-utterance answer stays the default), and a slot of its session is then free again only once its occupant's last piece is out.  dia_runner's and orpheus_runner's chunk too (orpheus_runner: chunk_frames counts SNAC
-    // frames, the override is declared in orpheus_session.h; its SNAC noise block is drawn frame-major as in generate_chunked, across
-    // utterances in slot order within a look-in).
+    // this runner's session does not chunk.  The three session runners share one override, declared in stream_session.h, which asks the
+    // runner whether its session can cut windows; the windows themselves are cut by chunk_windows.h.  dia_runner's and orpheus_runner's
+    // sessions chunk (orpheus_runner: chunk_frames counts SNAC frames; its SNAC noise block is drawn frame-major as in generate_chunked, across
+    // utterances in slot order within a look-in; a SNAC layout with no halo does not chunk.  dia_runner: a DAC layout with no halo sends whole
+    // utterances through the hook).  The answer "does not chunk (parler_runner)" holds for a Parler codec layout that reports no halo and,
+    // by default, for every other: its session chunks when TTS_PARLER_STREAM_CHUNKS is set in the environment (an opt-in: the
+    // whole-utterance answer stays the default), and a slot of its session is then free again only once its occupant's last piece is out.
     virtual bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t ticket, const float *, size_t)> on_chunk);
     // generate_stream's loop with on_chunk(utterance, pcm, n), utterance = the sentence's index.  Where the session does not chunk, or there is
     // none (kokoro_runner), each finished utterance is handed out as one chunk, the default generate_chunked has.  chunk_frames == 0 is an error.

@@ -62,7 +62,7 @@ std::unique_ptr<tts_generation_runner> dia_model_loader::from_file(gguf_file * m
     return std::make_unique<dia_runner>(hp, device);
 }
 
-dia_runner::dia_runner(const dia_hparams & hp_, int device) : tts_generation_runner{dia_loader}, hp(hp_) {
+dia_runner::dia_runner(const dia_hparams & hp_, int device) : stream_session{dia_loader}, hp(hp_) {
     tts_hip_dia_desc d{};
     d.struct_size = sizeof(d);
     d.enc_hidden_size = hp.encoder_hidden_size; d.enc_layers = hp.n_encoder_layers; d.enc_attn_heads = hp.encoder_attn_heads;
@@ -175,93 +175,16 @@ void dia_adjust_output_tokens(const dia_hparams & hp, const std::vector<uint32_t
     dia_undelay(hp, output_tokens.data(), output_tokens.size() / hp.n_output_heads, 0, filtered);
 }
 
-// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
-// As for Parler (parler_runner.cpp): the codec's samples of frame j depend on the codes of frames [j - h, j + h] only, so once the kept
-// frames [e, f + h) of an utterance are final, a window [e - h, f + h) decoded as an utterance of its own yields the samples of [e, f) that
-// the whole utterance's decode yields.  Frames are counted after the un-delay dropped those with EOS / PAD in them: that is the sequence
-// the codec sees.  run_utterances calls the hook at its look-ins: plan() un-delays what became final and cuts the next windows, emit()
-// decodes them — one codec pass for every utterance, on the codec context's stream while the decoder's next steps run — and hands out.
+// ---- chunked audio (common.h; the windows and the chunker: chunk_windows.h) ------------------------------------------------------------------
+// Frames are counted after the un-delay dropped those with EOS / PAD in them: that is the sequence the codec sees.  run_utterances calls the
+// hook at its look-ins: plan() un-delays what became final and cuts the next windows, emit_rows() decodes them — one codec pass for every
+// utterance, on the codec context's stream while the decoder's next steps run — and hands out.
 static constexpr uint32_t LOOK_IN = 16;   // decode steps between two look-ins (what tts_hip_dia_generate uses)
 
-struct dia_runner::chunker {
-    struct row {
-        std::vector<uint32_t> frames;   // codes of the kept frames that are final [frames][heads]
-        size_t   judged = 0;            // dia_undelay's cursor
-        uint32_t emitted = 0;           // kept frames handed out
-    };
-    dia_runner &   r;
-    const uint32_t chunk_frames;
-    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk;
-    std::vector<row>      rows;
-    std::vector<uint32_t> codes, frames, keep0, keep1, row_of;   // the planned windows: one tts_hip_dac_decode_windows pass
-    chunker(dia_runner & runner, uint32_t chunk_frames_, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk_)
-        : r(runner), chunk_frames(chunk_frames_), on_chunk(on_chunk_) {}
-
-    // the frames of each utterance that became final since the last call, then a window per utterance that has chunks ready: whole chunks
-    // whose right halo is final too, or everything left once the utterance has finished
-    void plan(const std::vector<std::vector<uint32_t>> & toks, const std::vector<bool> & finished) {
-        const uint32_t nh = r.hp.n_output_heads;
-        const uint32_t h = r.dac_halo >= 0 ? (uint32_t) r.dac_halo : r.hp.max_generation_size;   // unknown halo: whole utterances once they are done
-        rows.resize(toks.size());
-        for (uint32_t i = 0; i < toks.size(); i++) {
-            row & w = rows[i];
-            w.judged = dia_undelay(r.hp, toks[i].data(), toks[i].size() / nh, w.judged, w.frames);
-            const uint32_t have = (uint32_t) (w.frames.size() / nh);
-            uint32_t end = w.emitted;
-            if (finished[i]) end = have;
-            else if (have >= w.emitted + h + chunk_frames) end = w.emitted + (have - h - w.emitted) / chunk_frames * chunk_frames;
-            if (end == w.emitted) continue;
-            const uint32_t w0 = w.emitted > h ? w.emitted - h : 0, w1 = std::min(end + h, have);
-            codes.insert(codes.end(), w.frames.begin() + (size_t) w0 * nh, w.frames.begin() + (size_t) w1 * nh);
-            frames.push_back(w1 - w0);
-            keep0.push_back(w.emitted - w0);
-            keep1.push_back(end - w0);
-            row_of.push_back(i);
-            w.emitted = end;
-        }
-    }
-    // the planned windows through the codec into r.pcm, window after window
-    void decode() {
-        const uint32_t U = r.hp.up_sampling_factor;
-        size_t total = 0;
-        for (size_t w = 0; w < row_of.size(); w++) total += (size_t) (keep1[w] - keep0[w]) * U;
-        r.pcm.resize(total);
-        hip_check(tts_hip_dac_decode_windows(r.dac, codes.data(), frames.data(), keep0.data(), keep1.data(), (uint32_t) row_of.size(), r.pcm.data()),
-                  "tts_hip_dac_decode_windows");
-    }
-    void clear() { codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear(); }
-    // the planned windows through the codec, then window after window in chunks to `to(window, samples, count)`; a false skips the rest of
-    // that window
-    void emit(const std::function<bool(size_t, const float *, size_t)> & to) {
-        if (row_of.empty()) return;
-        const uint32_t U = r.hp.up_sampling_factor;
-        decode();
-        size_t off = 0;
-        for (size_t w = 0; w < row_of.size(); w++) {
-            const uint32_t nf = keep1[w] - keep0[w];
-            bool more = true;
-            for (uint32_t f = 0; f < nf && more; f += chunk_frames) more = to(w, r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
-            off += (size_t) nf * U;
-        }
-        clear();
-    }
-    // run_utterances' policy: a window's chunks go to its row; a false stops the generation, so nothing after it is handed out
-    bool emit_rows() {
-        bool go = true;
-        emit([&](size_t w, const float * p, size_t k) { return go = go && on_chunk(row_of[w], p, k); });
-        return go;
-    }
-    // the session's policy: window w belongs to the utterance tickets[w] (its slot may have a new occupant by now); a false from `to` ends
-    // that utterance only — its ticket goes into `stopped` and the other windows go on
-    void emit_session(const std::vector<size_t> & tickets, const std::function<bool(size_t, const float *, size_t)> & to, std::vector<size_t> & stopped) {
-        emit([&](size_t w, const float * p, size_t k) {
-            if (std::find(stopped.begin(), stopped.end(), tickets[w]) != stopped.end()) return false;
-            if (to(tickets[w], p, k)) return true;
-            stopped.push_back(tickets[w]);
-            return false;
-        });
-    }
-};
+dac_chunker dia_runner::make_chunker(uint32_t chunk_frames) {
+    return dac_chunker{[this](const uint32_t * toks, size_t steps, size_t judged, bool, std::vector<uint32_t> & kept) { return dia_undelay(hp, toks, steps, judged, kept); },
+                       hp.n_output_heads, hp.up_sampling_factor, dac_halo >= 0 ? (uint32_t) dac_halo : hp.max_generation_size, chunk_frames, dac, pcm};
+}
 
 // what every form of generate() does before the loop: the sampler's settings (n_calls = 0: a seeded sampler draws the sequence of a call of
 // its own) and the step budget
@@ -327,7 +250,8 @@ void dia_runner::encode_batch(const std::vector<std::string> & sentences) {
 // hook, the look-ins hand out chunked audio.
 // Device loop: every utterance gets the draws a separate generate() call would make (draw_call_uniforms), as the host loop's per-utterance
 // samplers and the Parler batch path do.
-std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, chunker * hook) {
+std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, dac_chunker * hook,
+                                                              const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
     const uint32_t nh = hp.n_output_heads;
     std::vector<std::vector<uint32_t>> toks(n);
     std::vector<bool> finished(n, false);
@@ -346,7 +270,7 @@ std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32
         uint32_t ran = 0;
         hip_check(tts_hip_dia_gen_launch(lm, LOOK_IN), "tts_hip_dia_gen_launch");
         for (;;) {
-            if (hook) go = hook->emit_rows();   // the codec windows of the last look-in, while the steps run
+            if (hook) go = hook->emit_rows(on_chunk);   // the codec windows of the last look-in, while the steps run
             hip_check(tts_hip_dia_gen_wait(lm, buf.data(), steps.data(), done.data(), &ran), "tts_hip_dia_gen_wait");
             bool all = true;
             for (uint32_t i = 0; i < n; i++) {
@@ -389,14 +313,14 @@ std::vector<std::vector<uint32_t>> dia_runner::run_utterances(uint32_t n, uint32
             }
             if (hook && step % LOOK_IN == 0) {
                 hook->plan(toks, finished);
-                go = hook->emit_rows();
+                go = hook->emit_rows(on_chunk);
             }
         }
     }
     if (hook && go) {   // what is left once every utterance is done
         finished.assign(n, true);
         hook->plan(toks, finished);
-        (void) hook->emit_rows();
+        (void) hook->emit_rows(on_chunk);
     }
     return toks;
 }
@@ -452,8 +376,8 @@ void dia_runner::generate_chunked(const char * sentence, const generation_config
     const uint32_t max_gen = begin_call(config);
     encode_single(sentence);
     const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); };
-    chunker hook{*this, chunk_frames, cb};
-    last_output_tokens = std::move(run_utterances(1, max_gen, config, &hook)[0]);
+    dac_chunker hook = make_chunker(chunk_frames);
+    last_output_tokens = std::move(run_utterances(1, max_gen, config, &hook, cb)[0]);
 }
 
 void dia_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
@@ -464,8 +388,8 @@ void dia_runner::generate_batch_chunked(const std::vector<std::string> & sentenc
     if (n > max_seqs) TTS_ABORT("generate_batch: %u utterances but the runner was loaded with max_seqs=%u (TTS_HIP_MAX_SEQS)\n", n, max_seqs);
     const uint32_t max_gen = begin_call(config);
     encode_batch(sentences);
-    chunker hook{*this, chunk_frames, on_chunk};
-    last_batch_tokens = run_utterances(n, max_gen, config, &hook);
+    dac_chunker hook = make_chunker(chunk_frames);
+    last_batch_tokens = run_utterances(n, max_gen, config, &hook, on_chunk);
 }
 
 // ---- continuous batching (common.h; tts_hip_dia_stream_* underneath) -------------------------------------------------------------------
@@ -477,33 +401,25 @@ void dia_runner::stream_begin(const generation_configuration & config) {
     if (st_on) stream_end();
     st_max_gen = begin_call(config);
     if (!device_sampler(config)) TTS_ABORT("stream_begin: temperature, top_p and repetition_penalty must be > 0 for a sampled session\n");
-    st_cfg = config;
     // one path: the mixed session, whose slots carry their own sampler; a request with the opening configuration is one among the others
     const tts_hip_dia_codes codes = loop_codes();
     const uint32_t slots = stream_capacity();
     hip_check(tts_hip_dia_stream_begin_mixed(lm, slots, st_max_gen, &codes), "tts_hip_dia_stream_begin_mixed");
-    st_free.clear();
-    for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
-    st_ticket.assign(slots, 0);
+    session_open(config, slots);
     st_wait.clear();
-    st_live = 0;
-    st_on = true;
     st_hook.reset();
     st_closing.clear();
     st_stopped.clear();
     last_batch_tokens.clear();
 }
 
-// chunked audio out of the session (common.h): the chunker's rows are the slots
-static const std::function<bool(uint32_t, const float *, size_t)> no_row_chunks;
-
-bool dia_runner::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
+// chunked audio out of the session (common.h), this runner's part of stream_session's hook: the chunker's rows are the slots.  An unknown halo
+// is no refusal: the chunker then cuts one window per utterance once it has ended, and the whole utterance goes out through the hook.
+bool dia_runner::session_chunks_ready(uint32_t chunk_frames) {
     if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
-    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
     if (st_live != 0 || !st_wait.empty()) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
     const uint32_t slots = stream_capacity();
-    st_on_chunk = std::move(on_chunk);
-    st_hook.reset(new chunker{*this, chunk_frames, no_row_chunks});
+    st_hook = std::make_unique<dac_chunker>(make_chunker(chunk_frames));
     st_hook->rows.assign(slots, {});
     st_toks.assign(slots, {});
     st_gen.assign(slots, false);
@@ -514,8 +430,6 @@ bool dia_runner::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t,
 bool dia_runner::stream_accepts(const generation_configuration & config) const {
     return st_on && device_sampler(config) && valid_max_tokens(config) && resolved_max_gen(config) <= st_max_gen;
 }
-
-void dia_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
 
 void dia_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
@@ -573,20 +487,8 @@ void dia_runner::admit_waiting() {
 void dia_runner::hand_out(std::vector<stream_result> & finished) {
     st_hook->emit_session(st_win_ticket, st_on_chunk, st_stopped);
     st_win_ticket.clear();
-    for (size_t ticket : st_closing) {
-        stream_result r;
-        r.ticket = ticket;   // no audio: everything went through the hook
-        finished.push_back(r);
-    }
+    for (size_t ticket : st_closing) report_no_audio(finished, ticket);
     st_closing.clear();
-}
-
-void dia_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & ids) {
-    if (ticket < 4096) {   // generate_stream's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
-        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
-        last_batch_tokens[ticket] = ids;
-    }
-    last_output_tokens = ids;
 }
 
 // stream_step with a hook: the codec pass of the windows cut at the last look-in runs on the codec context while this interval's steps run.
@@ -619,9 +521,7 @@ void dia_runner::stream_step_chunked(std::vector<stream_result> & finished) {
             if (!ended[s]) drop.push_back(s);
             st_toks[s].clear();
             st_hook->rows[s] = {};
-            stream_result r;
-            r.ticket = st_ticket[s];
-            finished.push_back(r);
+            report_no_audio(finished, st_ticket[s]);
             ended[s] = false;
         } else {
             st_closing.push_back(st_ticket[s]);
@@ -678,12 +578,9 @@ void dia_runner::stream_step(std::vector<stream_result> & finished) {
 void dia_runner::stream_end() {
     if (!st_on) return;
     (void) tts_hip_dia_stream_end(lm);
-    st_on = false;
-    st_free.clear();
+    session_close();
     st_wait.clear();
-    st_live = 0;
     st_hook.reset();
-    st_on_chunk = nullptr;
     st_closing.clear();
     st_stopped.clear();
     st_win_ticket.clear();

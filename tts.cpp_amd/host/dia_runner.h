@@ -5,6 +5,9 @@
 // loop over nine delayed codebook heads with classifier-free guidance inside every step, the end-of-sequence countdown of
 // check_stopping, un-delay, DAC.  The ggml graphs inside decode() and dac_runner::run() are replaced by tts_hip_dia_* and
 // tts_hip_dac_decode; tokenisation, sampling and the stopping logic stay on the host as in the reference.
+//
+// Chunked audio is the shared DAC chunker (chunk_windows.h) with dia_undelay as its rule; the session's bookkeeping and its chunk hook come
+// from stream_session.h.
 #pragma once
 #include <functional>
 #include <memory>
@@ -12,8 +15,10 @@
 #include <vector>
 
 #include "../../include/tts_hip.h"
+#include "chunk_windows.h"
 #include "common.h"
 #include "sampler.h"
+#include "stream_session.h"
 
 extern const struct dia_model_loader final : tts_model_loader {
     explicit dia_model_loader();
@@ -43,7 +48,7 @@ void     dia_adjust_output_tokens(const dia_hparams & hp, const std::vector<uint
 // yields a prefix of the whole stream's frames; dia_adjust_output_tokens is this from zero over everything.
 size_t   dia_undelay(const dia_hparams & hp, const uint32_t * toks, size_t steps, size_t judged, std::vector<uint32_t> & kept);
 
-struct dia_runner final : tts_generation_runner {
+struct dia_runner final : stream_session {
     dia_runner(const dia_hparams & hp, int device);
     ~dia_runner() override;
 
@@ -71,7 +76,6 @@ struct dia_runner final : tts_generation_runner {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return st_on ? (uint32_t) st_free.size() - (uint32_t) st_wait.size() : 0; }
     uint32_t stream_live() const override { return st_live + (uint32_t) st_wait.size() + (uint32_t) st_closing.size(); }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
     // The session is a mixed one (tts_hip_dia_stream_begin_mixed): every slot carries its own sampler record, penalty table and step budget, so
     // a request may differ from the session's configuration in sample, seed, top_k, top_p, temperature, repetition_penalty and max_tokens.  It is
     // accepted when it is greedy or within the device sampler's limits and its generation length is at most the session's (the opening
@@ -83,14 +87,12 @@ struct dia_runner final : tts_generation_runner {
     // chunked audio out of the session: with a hook set, stream_step launches its 16 steps (tts_hip_dia_stream_launch), decodes the windows
     // cut at the last look-in in one tts_hip_dac_decode_windows pass on the codec context while they run, hands the chunks to on_chunk, then
     // waits and takes the new rows of every live slot (tts_hip_dia_stream_wait).  An utterance is reported in `finished` (no audio) once its
-    // last chunk is out; on_chunk returning false drops that utterance only (tts_hip_dia_stream_drop), reported with what it got.
-    bool     stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) override;
+    // last chunk is out; on_chunk returning false drops that utterance only (tts_hip_dia_stream_drop), reported with what it got.  The hook
+    // itself is stream_session's; this runner's part always says yes: with an unknown halo its chunker hands whole utterances out through the hook.
+    bool     session_chunks_ready(uint32_t chunk_frames) override;
     uint32_t batch_capacity() const override { return max_seqs; }
     uint32_t kv_element_bytes() const override;   // 4, or 2 when TTS_HIP_KV_F16 was in the environment at load (tts_hip_dia_desc::kv_type)
     uint32_t max_seqs = 1;
-    std::vector<std::vector<uint32_t>> last_batch_tokens;
-
-    std::vector<uint32_t> last_prompt_tokens, last_output_tokens;
 
     dia_hparams        hp;
     sampler            smp;
@@ -102,16 +104,10 @@ struct dia_runner final : tts_generation_runner {
   private:
     // session state of the continuous batching
     struct waiting { size_t ticket = 0; std::vector<uint32_t> prompt; uint32_t len = 0; generation_configuration cfg{}; };
-    bool                     st_on = false;
-    generation_configuration st_cfg{};
-    uint32_t                 st_max_gen = 0, st_live = 0;
-    std::vector<uint32_t>    st_free;     // free utterance slots
-    std::vector<size_t>      st_ticket;   // slot -> ticket
+    uint32_t                 st_max_gen = 0;
     std::vector<waiting>     st_wait;     // submitted, admitted by the next stream_step
-    struct chunker;
-    // ... with stream_chunks: the chunker's rows are the slots
-    std::unique_ptr<chunker>                              st_hook;
-    std::function<bool(size_t, const float *, size_t)>    st_on_chunk;
+    // ... with the chunk hook: the chunker's rows are the slots
+    std::unique_ptr<dac_chunker>       st_hook;
     std::vector<std::vector<uint32_t>> st_toks;        // slot -> the occupant's still-delayed ids so far
     std::vector<bool>                  st_gen;         // slot -> its occupant is generating
     std::vector<uint32_t>              st_buf;         // what tts_hip_dia_stream_wait writes: [slots][max_gen][heads]
@@ -120,7 +116,6 @@ struct dia_runner final : tts_generation_runner {
     std::vector<size_t>                st_stopped;     // on_chunk returned false for these
     void admit_waiting();
     void hand_out(std::vector<stream_result> & finished);
-    void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
     void stream_step_chunked(std::vector<stream_result> & finished);
     uint32_t begin_call(const generation_configuration & config);   // sampler settings; -> the step budget (max_gen)
     bool     valid_max_tokens(const generation_configuration & config) const;    // begin_call's assertion
@@ -131,5 +126,7 @@ struct dia_runner final : tts_generation_runner {
     void     encode_single(const char * sentence);
     void     encode_batch(const std::vector<std::string> & sentences);
     // the one generation loop under generate, generate_batch and their chunked forms
-    std::vector<std::vector<uint32_t>> run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, chunker * hook);
+    dac_chunker make_chunker(uint32_t chunk_frames);
+    std::vector<std::vector<uint32_t>> run_utterances(uint32_t n, uint32_t max_gen, const generation_configuration & config, dac_chunker * hook,
+                                                      const std::function<bool(uint32_t, const float *, size_t)> & on_chunk = {});
 };

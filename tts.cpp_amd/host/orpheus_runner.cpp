@@ -71,7 +71,7 @@ std::unique_ptr<tts_generation_runner> orpheus_model_loader::from_file(gguf_file
 }
 
 orpheus_runner::orpheus_runner(const orpheus_hparams & hp_, bpe_tokenizer * tok, int device)
-    : orpheus_session{orpheus_loader}, hp(hp_), tokenizer(tok) {
+    : stream_session{orpheus_loader}, hp(hp_), tokenizer(tok) {
     tts_hip_orpheus_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = hp.hidden_size; d.n_layers = hp.n_layers; d.n_attn_heads = hp.n_attn_heads; d.n_kv_heads = hp.n_kv_attn_heads;
@@ -291,8 +291,7 @@ void orpheus_runner::generate_batch(const std::vector<std::string> & sentences, 
 }
 
 // ---- chunked audio -------------------------------------------------------------------------------------------------------------------
-// The windows the ids known now make ready: per utterance the whole chunks [next, f1) whose halo is complete (everything left once the utterance
-// has ended), as one window [next - h, f1 + h) clipped to the utterance.  Trailing ids that do not fill a group of 7 are dropped, as
+// The windows the ids known now make ready: per utterance one cut of chunk_windows.h over its whole frames.  Trailing ids that do not fill a group of 7 are dropped, as
 // prepare_output_tokens does.  Returns whether there is a window.
 bool orpheus_runner::chunk_collect(std::vector<chunk_state> & st, uint32_t chunk_frames, chunk_pass & P) {
     P = chunk_pass{};
@@ -304,17 +303,12 @@ bool orpheus_runner::chunk_collect(std::vector<chunk_state> & st, uint32_t chunk
     for (uint32_t u = 0; u < st.size(); u++) {
         chunk_state & s = st[u];
         const uint32_t F = (uint32_t) (s.ids.size() / 7);
-        uint32_t f1;
-        if (s.ended) f1 = F;
-        else {
-            const uint32_t avail = F > h ? F - h : 0;   // frames whose halo is complete
-            f1 = avail > s.next ? s.next + (avail - s.next) / chunk_frames * chunk_frames : s.next;
-        }
-        if (f1 <= s.next) continue;
-        const uint32_t w0 = s.next > h ? s.next - h : 0, w1 = std::min(F, f1 + h);
+        const chunk_window c = cut_chunk_window(s.next, F, h, chunk_frames, s.ended);
+        if (c.end == s.next) continue;
+        const uint32_t f1 = c.end, w0 = c.w0, w1 = c.w1;
         const std::vector<uint32_t> part(s.ids.begin() + (size_t) 7 * w0, s.ids.begin() + (size_t) 7 * w1);
         for (auto & l : prepare_output_tokens(part)) P.codes.insert(P.codes.end(), l.begin(), l.end());
-        P.utt.push_back(u); P.frames.push_back(w1 - w0); P.keep0.push_back(s.next - w0); P.keep1.push_back(f1 - w0);
+        P.utt.push_back(u); P.frames.push_back(w1 - w0); P.keep0.push_back(c.keep0); P.keep1.push_back(c.keep1);
         if (with_noise) {
             while (s.noise0 + s.noise.size() < w1) {   // frames enter in increasing order, each drawn once
                 s.noise.emplace_back(per_frame);
@@ -340,22 +334,6 @@ static size_t chunk_samples(const std::vector<uint32_t> & keep0, const std::vect
     size_t k = 0;
     for (size_t i = 0; i < keep0.size(); i++) k += keep1[i] - keep0[i];
     return std::max<size_t>(1, k * 4 * up);
-}
-
-// the pass' PCM (this->pcm) to the callback, chunk_frames at a time; false once the callback asks to stop
-bool orpheus_runner::chunk_deliver(const chunk_pass & P, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
-    const size_t per = (size_t) 4 * hp.snac_up;
-    size_t off = 0;
-    for (size_t i = 0; i < P.utt.size(); i++) {
-        uint32_t left = P.keep1[i] - P.keep0[i];
-        while (left) {
-            const uint32_t k = std::min(left, chunk_frames);
-            if (!on_chunk(P.utt[i], pcm.data() + off, k * per)) return false;
-            off += k * per;
-            left -= k;
-        }
-    }
-    return true;
 }
 
 // the look-in loop over a generation that tts_hip_orpheus_gen_begin has started.  One sequence: launch the next piece of decoder steps (the call
@@ -391,7 +369,7 @@ void orpheus_runner::chunk_run(std::vector<chunk_state> & st, bool lockstep, uin
             hip_check(tts_hip_snac_decode_windows_begin(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), (uint32_t) P.utt.size(),
                                                         P.noise.empty() ? nullptr : P.noise.data(), pcm.data()), "tts_hip_snac_decode_windows");
             hip_check(tts_hip_snac_decode_windows_end(snac), "tts_hip_snac_decode_windows");
-            go_on = chunk_deliver(P, chunk_frames, on_chunk);
+            go_on = hand_out_rows(P.keep0, P.keep1, P.utt, chunk_frames, (size_t) 4 * hp.snac_up, pcm.data(), on_chunk);
         }
         if (launch && lockstep && go_on) hip_check(tts_hip_orpheus_gen_launch(lm, piece), "tts_hip_orpheus_gen_launch");
         if (launch) { in_flight = false; look(); }
@@ -437,7 +415,7 @@ void orpheus_runner::generate_chunked(const char * sentence, const generation_co
                     pcm.resize(chunk_samples(P.keep0, P.keep1, hp.snac_up));
                     hip_check(tts_hip_snac_decode_windows(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), 1, P.noise.empty() ? nullptr : P.noise.data(), pcm.data()),
                               "tts_hip_snac_decode_windows");
-                    go_on = chunk_deliver(P, chunk_frames, cb);
+                    go_on = hand_out_rows(P.keep0, P.keep1, P.utt, chunk_frames, (size_t) 4 * hp.snac_up, pcm.data(), cb);
                 }
             }
             if (st[0].ended || !go_on) break;
@@ -500,27 +478,12 @@ void orpheus_runner::stream_begin(const generation_configuration & config) {
         hip_check(tts_hip_orpheus_gen_begin(lm, 1, &id, &one, 0, hp.stopping_token_id, nullptr, nullptr), "tts_hip_orpheus_gen_begin");
     }
     const uint32_t slots = stream_capacity();
-    st_cfg = config;
     hip_check(tts_hip_orpheus_stream_begin_mixed(lm, slots, hp.max_generation_size, hp.stopping_token_id), "tts_hip_orpheus_stream_begin_mixed");
-    st_free.clear();
-    for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
-    st_ticket.assign(slots, 0);
+    session_open(config, slots);
     st_pcm.clear();
-    st_live = 0;
-    st_on = true;
-    st_chunk_frames = 0;
-    st_on_chunk = nullptr;
 }
 
-// chunked audio out of the session (common.h; the override is declared in orpheus_session.h)
-bool orpheus_session::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
-    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
-    if (!session_chunks_ready(chunk_frames)) return false;
-    st_chunk_frames = chunk_frames;
-    st_on_chunk = std::move(on_chunk);
-    return true;
-}
-
+// chunked audio out of the session (common.h): this runner's part of stream_session's hook
 bool orpheus_runner::session_chunks_ready(uint32_t) {
     if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
     if (st_live != 0) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
@@ -542,8 +505,6 @@ bool orpheus_runner::stream_accepts(const generation_configuration & config) con
     if (!config.voice.empty() && std::find(orpheus_voices.begin(), orpheus_voices.end(), config.voice) == orpheus_voices.end()) return false;
     return !config.sample || device_sampler(config);
 }
-
-void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
 
 void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
@@ -571,16 +532,6 @@ void orpheus_runner::stream_submit(size_t ticket, const std::string & sentence, 
     }
 }
 
-void orpheus_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & ids) {
-    if (ticket < TOKEN_RECORD_TICKETS) {   // generate_stream_chunked's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
-        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
-        last_batch_tokens[ticket] = ids;
-    }
-    last_output_tokens = ids;
-    if (ids.size() >= hp.max_generation_size)
-        fprintf(stdout, "Warning: generation hit its max default length. The generated audio may not contain the entire prompt.\n");
-}
-
 // the windows the last look-in cut, through the codec in one pass and out chunk by chunk, each under the ticket it was cut for; then the utterances
 // that had ended at that look-in have had their last chunk.  An utterance whose callback returns false gets nothing more.
 void orpheus_runner::session_hand_out(std::vector<stream_result> & finished) {
@@ -590,26 +541,12 @@ void orpheus_runner::session_hand_out(std::vector<stream_result> & finished) {
         hip_check(tts_hip_snac_decode_windows_begin(snac, P.codes.data(), P.frames.data(), P.keep0.data(), P.keep1.data(), (uint32_t) P.utt.size(),
                                                     P.noise.empty() ? nullptr : P.noise.data(), pcm.data()), "tts_hip_snac_decode_windows");
         hip_check(tts_hip_snac_decode_windows_end(snac), "tts_hip_snac_decode_windows");
-        const size_t per = (size_t) 4 * hp.snac_up;
-        size_t off = 0;
-        for (size_t i = 0; i < P.utt.size(); i++) {
-            const size_t ticket = st_pass_ticket[i];
-            uint32_t left = P.keep1[i] - P.keep0[i];
-            bool go_on = std::find(st_stopped.begin(), st_stopped.end(), ticket) == st_stopped.end();
-            while (left) {
-                const uint32_t k = std::min(left, st_chunk_frames);
-                if (go_on && !st_on_chunk(ticket, pcm.data() + off, k * per)) { go_on = false; st_stopped.push_back(ticket); }
-                off += k * per;
-                left -= k;
-            }
-        }
+        hand_out_session(P.keep0, P.keep1, st_pass_ticket, st_chunk_frames, (size_t) 4 * hp.snac_up, pcm.data(), st_on_chunk, st_stopped);
     }
     st_pass = chunk_pass{};
     st_pass_ticket.clear();
     for (size_t ticket : st_closing) {
-        stream_result r;
-        r.ticket = ticket;   // no audio: everything went through the hook
-        finished.push_back(r);
+        report_no_audio(finished, ticket);
         st_live--;
     }
     st_closing.clear();
@@ -643,14 +580,13 @@ void orpheus_runner::stream_step_chunked(std::vector<stream_result> & finished) 
         if (!done[s] && !stopped) { generating = true; continue; }
         // the occupant leaves: its ids are on the host, the slot is free for the next admission
         remember_tokens(st_ticket[s], row.ids);
+        if (row.ids.size() >= M) fprintf(stdout, "Warning: generation hit its max default length. The generated audio may not contain the entire prompt.\n");
         st_gen[s] = 0;
         st_free.push_back(s);
         if (stopped) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
             if (!done[s]) drop.push_back(s);
             row = {};
-            stream_result r;
-            r.ticket = st_ticket[s];
-            finished.push_back(r);
+            report_no_audio(finished, st_ticket[s]);
             st_live--;
         } else {
             row.ended = true;
@@ -697,11 +633,7 @@ void orpheus_runner::stream_step(std::vector<stream_result> & finished) {
 void orpheus_runner::stream_end() {
     if (!st_on) return;
     (void) tts_hip_orpheus_stream_end(lm);
-    st_on = false;
-    st_free.clear();
-    st_live = 0;
-    st_chunk_frames = 0;
-    st_on_chunk = nullptr;
+    session_close();
     st_pass = chunk_pass{};
     st_pass_ticket.clear();
     st_closing.clear();

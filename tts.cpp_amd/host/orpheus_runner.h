@@ -4,6 +4,9 @@
 // (fixed leading / trailing ids, optional "voice: " prefix), byte-pair tokenise, autoregress one token at a time through
 // the Llama-3 decoder until the stopping token, regroup every 7 ids into the three SNAC levels, decode with SNAC.
 // The ggml graphs inside decode() and snac_runner::run() are replaced by tts_hip_orpheus_* / tts_hip_snac_*.
+//
+// Chunked audio cuts its windows and hands its chunks out with chunk_windows.h; the id regrouping and the frame-major noise block around them
+// are this runner's.  The session's bookkeeping and its chunk hook come from stream_session.h.
 #pragma once
 #include <array>
 #include <functional>
@@ -13,9 +16,10 @@
 #include <vector>
 
 #include "../../include/tts_hip.h"
+#include "chunk_windows.h"
 #include "common.h"
-#include "orpheus_session.h"
 #include "sampler.h"
+#include "stream_session.h"
 #include "tokenizer.h"
 
 extern const struct orpheus_model_loader final : tts_model_loader {
@@ -41,7 +45,7 @@ struct orpheus_hparams {  // defaults = canopylabs/orpheus-3b (orpheus/model.h:2
     uint32_t snac_repeats[3] = {4, 2, 1};
 };
 
-struct orpheus_runner final : orpheus_session {
+struct orpheus_runner final : stream_session {
     orpheus_runner(const orpheus_hparams & hp, bpe_tokenizer * tok, int device);
     ~orpheus_runner() override;
 
@@ -69,7 +73,6 @@ struct orpheus_runner final : orpheus_session {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return (uint32_t) st_free.size(); }
     uint32_t stream_live() const override { return st_live; }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
     // The session is a mixed one (tts_hip_orpheus_stream_begin_mixed): the voice is a prompt prefix and every slot carries its own sampler, so a
     // request may differ from the session's configuration in voice, seed, sample, top_k, temperature, top_p and repetition penalty.  It is accepted
     // when its voice is valid and it is greedy or within the device sampler's limits; its sampler is seeded as a generate() call of its own seeds it.
@@ -77,7 +80,7 @@ struct orpheus_runner final : orpheus_session {
     void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
-    // extension: chunked audio out of the session (the hook is declared in orpheus_session.h).  With the hook set, a stream_step launches its 28
+    // extension: chunked audio out of the session (the hook itself is stream_session's).  With the hook set, a stream_step launches its 28
     // decoder steps (tts_hip_orpheus_stream_launch), decodes the windows cut at the previous look-in in one tts_hip_snac_decode_windows_begin / _end
     // pass on the codec context while they run (the windows of all slots in one pass), hands the chunks to on_chunk(ticket, ...), and then waits
     // taking the new ids (tts_hip_orpheus_stream_wait).  Right after the wait the ids go to the slots' chunk_state and the next windows are cut, with
@@ -97,12 +100,7 @@ struct orpheus_runner final : orpheus_session {
     // pieces exposed for tests
     std::vector<uint32_t>              batch_from_sentence(const std::string & sentence, const std::string & voice) const;  // model.cpp:341-356
     std::vector<std::vector<uint32_t>> prepare_output_tokens(const std::vector<uint32_t> & output_tokens) const;           // :358-376
-    std::vector<uint32_t> last_prompt_tokens, last_output_tokens;
-    std::vector<std::vector<uint32_t>> last_batch_tokens;   // generate_batch: the ids of every utterance
-    // The chunked session keeps an utterance's ids in last_batch_tokens[ticket] (a record for tests, read through tts_c_last_tokens(16 + ticket)) only
-    // for tickets below this bound.  A ticket is the caller's handle: generate_stream_chunked numbers its sentences from 0, which the record is for;
-    // a host with its own queue may use any size_t (a request id, a pointer), and the vector must not grow to it.  Other tickets keep no record.
-    static constexpr size_t TOKEN_RECORD_TICKETS = 4096;
+    // stream_session's records: last_batch_tokens holds the ids of every utterance of the last generate_batch, or of the chunked session
 
     orpheus_hparams                hp;
     std::unique_ptr<bpe_tokenizer> tokenizer;
@@ -132,11 +130,6 @@ struct orpheus_runner final : orpheus_session {
         std::vector<float>    noise;
     };
     // session state of the continuous batching
-    bool                            st_on = false;
-    generation_configuration        st_cfg{};
-    uint32_t                        st_live = 0;
-    std::vector<uint32_t>           st_free;     // free cache slots
-    std::vector<size_t>             st_ticket;   // slot -> ticket
     std::vector<std::vector<float>> st_pcm;      // audio handed out by the last stream_step
     // ... with the chunk hook: the chunker's rows are the slots
     std::vector<chunk_state>        st_rows;     // slot -> its occupant's ids and noise
@@ -148,13 +141,11 @@ struct orpheus_runner final : orpheus_session {
     std::vector<size_t>             st_stopped;  // utterances whose on_chunk returned false since the last look-in
     void stream_step_chunked(std::vector<stream_result> & finished);
     void session_hand_out(std::vector<stream_result> & finished);
-    void remember_tokens(size_t ticket, const std::vector<uint32_t> & ids);
     bool device_sampler(const generation_configuration & config) const;
     void sampler_setup(const generation_configuration & config);
     std::vector<uint32_t> checked_prompt(const std::string & sentence, const generation_configuration & config);
     void batch_inputs(const std::vector<std::string> & sentences, const generation_configuration & config, bool dev_sample,
                       std::vector<uint32_t> & prompts, std::vector<uint32_t> & lens, std::vector<float> & uni);
     bool chunk_collect(std::vector<chunk_state> & st, uint32_t chunk_frames, chunk_pass & P);
-    bool chunk_deliver(const chunk_pass & P, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
     void chunk_run(std::vector<chunk_state> & st, bool lockstep, uint32_t chunk_frames, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk);
 };

@@ -64,7 +64,7 @@ std::unique_ptr<tts_generation_runner> parler_model_loader::from_file(gguf_file 
 }
 
 parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok, int device, bool cross)
-    : parler_session{parler_loader}, hp(hp_), tokenizer(tok), use_cross_attn(cross), device_id(device) {
+    : stream_session{parler_loader}, hp(hp_), tokenizer(tok), use_cross_attn(cross), device_id(device) {
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = hp.hidden_size; d.n_layers = hp.n_layers; d.n_attn_heads = hp.n_attn_heads;
@@ -325,77 +325,24 @@ bool parler_runner::prepare_batch(const std::vector<std::string> & sentences, co
     return true;
 }
 
-// ---- chunked audio (common.h) -------------------------------------------------------------------------------------------------------------
-// The codec's output for frame j depends on the codes of frames [j - h, j + h] only (tts_hip_dac_halo_frames).  So once frames [e, f + h)
-// of an utterance are final, a window of frames [e - h, f + h) decoded as an utterance of its own yields the samples of frames [e, f)
-// exactly as the whole utterance's decode does (at the utterance's true edges the window is clipped and sees the same zero padding).
-// run_rows calls the hook at its look-ins: plan() un-delays the frames that became final and cuts the next windows, emit() decodes them
+// ---- chunked audio (common.h; the windows and the chunker: chunk_windows.h) ------------------------------------------------------------------
+// run_rows calls the hook at its look-ins: plan() un-delays the frames that became final and cuts the next windows, emit_rows() decodes them
 // (one codec pass for every utterance, on the codec's stream while the device loop's next steps run) and hands the chunks out.
 static constexpr uint32_t LOOK_IN = 32;   // decode steps between two look-ins: the device compacts its rows at multiples of 32 steps
 
-struct parler_runner::chunker {
-    struct row {
-        std::vector<uint32_t> frames;     // codes of the kept frames that are final [frames][heads]
-        size_t   judged = 0;              // frames whose keep / drop is decided (parler_undelay's `next`)
-        uint32_t emitted = 0;             // kept frames handed out
-    };
-    parler_runner & r;
-    const uint32_t  chunk_frames;
-    const std::function<bool(uint32_t, const float *, size_t)> & on_chunk;
-    std::vector<row>      rows;
-    std::vector<uint32_t> codes, frames, keep0, keep1, row_of;   // the planned windows: one tts_hip_dac_decode_windows pass
-    chunker(parler_runner & runner, uint32_t chunk_frames_, const std::function<bool(uint32_t, const float *, size_t)> & on_chunk_)
-        : r(runner), chunk_frames(chunk_frames_), on_chunk(on_chunk_) {}
-
-    // the frames of each row that became final since the last call, then a window per row that has chunks ready: whole chunks whose
-    // right halo is final too, or everything left once the row is finished
-    void plan(const std::vector<std::vector<uint32_t>> & toks, const std::vector<bool> & finished) {
-        const uint32_t nh = r.hp.n_output_heads;
-        const uint32_t h = r.dac_halo >= 0 ? (uint32_t) r.dac_halo : r.hp.max_generation_size;   // unknown halo: whole utterances once they are done
-        rows.resize(toks.size());
-        for (uint32_t i = 0; i < toks.size(); i++) {
-            row & w = rows[i];
-            w.judged = parler_undelay(toks[i].data(), toks[i].size() / nh, nh, r.hp.audio_vocab_size, w.judged, finished[i], w.frames);
-            const uint32_t have = (uint32_t) (w.frames.size() / nh);
-            uint32_t end = w.emitted;
-            if (finished[i]) end = have;
-            else if (have >= w.emitted + h + chunk_frames) end = w.emitted + (have - h - w.emitted) / chunk_frames * chunk_frames;
-            if (end == w.emitted) continue;
-            const uint32_t w0 = w.emitted > h ? w.emitted - h : 0, w1 = std::min(end + h, have);
-            codes.insert(codes.end(), w.frames.begin() + (size_t) w0 * nh, w.frames.begin() + (size_t) w1 * nh);
-            frames.push_back(w1 - w0);
-            keep0.push_back(w.emitted - w0);
-            keep1.push_back(end - w0);
-            row_of.push_back(i);
-            w.emitted = end;
-        }
-    }
-    // the planned windows through the codec, then their chunks to the caller (false: the caller stopped the generation)
-    bool emit() {
-        if (row_of.empty()) return true;
-        const uint32_t U = r.hp.up_sampling_factor;
-        size_t total = 0;
-        for (size_t w = 0; w < row_of.size(); w++) total += (size_t) (keep1[w] - keep0[w]) * U;
-        r.pcm.resize(total);
-        hip_check(tts_hip_dac_decode_windows(r.ctx, codes.data(), frames.data(), keep0.data(), keep1.data(), (uint32_t) row_of.size(), r.pcm.data()),
-                  "tts_hip_dac_decode_windows");
-        bool more = true;
-        size_t off = 0;
-        for (size_t w = 0; w < row_of.size() && more; w++) {
-            const uint32_t nf = keep1[w] - keep0[w];
-            for (uint32_t f = 0; f < nf && more; f += chunk_frames)
-                more = on_chunk(row_of[w], r.pcm.data() + off + (size_t) f * U, (size_t) std::min(chunk_frames, nf - f) * U);
-            off += (size_t) nf * U;
-        }
-        codes.clear(); frames.clear(); keep0.clear(); keep1.clear(); row_of.clear();
-        return more;
-    }
-};
+dac_chunker parler_runner::make_chunker(uint32_t chunk_frames) {
+    const uint32_t nh = hp.n_output_heads, av = hp.audio_vocab_size;
+    return dac_chunker{[nh, av](const uint32_t * toks, size_t steps, size_t judged, bool finished, std::vector<uint32_t> & kept) {
+                           return parler_undelay(toks, steps, nh, av, judged, finished, kept);
+                       },
+                       nh, hp.up_sampling_factor, dac_halo >= 0 ? (uint32_t) dac_halo : hp.max_generation_size, chunk_frames, ctx, pcm};
+}
 
 // generate_from_batch (model.cpp:762-792) over n prefilled rows (row i starts at position start[i]) -> the still-delayed tokens of each row.
 // Every row gets the steps generate() would give it alone (max_generation - its own prompt) and its own sampler, seeded as a generate() call
 // of its own; the loop runs as long as the shortest prompt needs.  With a hook, the look-ins every 32 steps hand out chunked audio.
-std::vector<std::vector<uint32_t>> parler_runner::run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook) {
+std::vector<std::vector<uint32_t>> parler_runner::run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, dac_chunker * hook,
+                                                           const std::function<bool(uint32_t, const float *, size_t)> & on_chunk) {
     const uint32_t n = (uint32_t) start.size(), nh = hp.n_output_heads, V = hp.output_vocab_size;
     const uint32_t max_steps = hp.max_generation_size - *std::min_element(start.begin(), start.end());
     std::vector<std::vector<uint32_t>> toks(n);
@@ -426,7 +373,7 @@ std::vector<std::vector<uint32_t>> parler_runner::run_rows(const std::vector<uin
         };
         hip_check(tts_hip_parler_gen_launch(ctx, LOOK_IN), "tts_hip_parler_gen_launch");
         for (;;) {
-            if (hook) go = hook->emit();   // the codec windows of the last look-in, while the steps run
+            if (hook) go = hook->emit_rows(on_chunk);   // the codec windows of the last look-in, while the steps run
             hip_check(tts_hip_parler_gen_wait(ctx, hook ? buf.data() : nullptr, done.data(), &ran), "tts_hip_parler_gen_wait");
             bool all = true;
             for (uint32_t i = 0; i < n; i++) {
@@ -483,14 +430,14 @@ std::vector<std::vector<uint32_t>> parler_runner::run_rows(const std::vector<uin
             }
             if (hook && step % LOOK_IN == 0) {
                 hook->plan(toks, finished);
-                go = hook->emit();
+                go = hook->emit_rows(on_chunk);
             }
         }
     }
     if (hook && go) {   // what is left once every row is done
         finished.assign(n, true);
         hook->plan(toks, finished);
-        (void) hook->emit();
+        (void) hook->emit_rows(on_chunk);
     }
     return toks;
 }
@@ -546,8 +493,8 @@ void parler_runner::generate_chunked(const char * sentence, const generation_con
     std::vector<uint32_t> prompt;
     if (!prepare_single(sentence, config, prompt)) return;
     const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t, const float * p, size_t k) { return on_chunk(p, k); };
-    chunker hook{*this, chunk_frames, cb};
-    last_output_tokens = std::move(run_rows({(uint32_t) prompt.size()}, config, &hook)[0]);
+    dac_chunker hook = make_chunker(chunk_frames);
+    last_output_tokens = std::move(run_rows({(uint32_t) prompt.size()}, config, &hook, cb)[0]);
 }
 
 void parler_runner::generate_batch_chunked(const std::vector<std::string> & sentences, const generation_configuration & config, uint32_t chunk_frames,
@@ -556,8 +503,8 @@ void parler_runner::generate_batch_chunked(const std::vector<std::string> & sent
     std::vector<uint32_t> start, row_of;
     if (!prepare_batch(sentences, config, start, row_of)) return;
     const std::function<bool(uint32_t, const float *, size_t)> cb = [&](uint32_t row, const float * p, size_t k) { return on_chunk(row_of[row], p, k); };
-    chunker hook{*this, chunk_frames, cb};
-    std::vector<std::vector<uint32_t>> row_tokens = run_rows(start, config, &hook);
+    dac_chunker hook = make_chunker(chunk_frames);
+    std::vector<std::vector<uint32_t>> row_tokens = run_rows(start, config, &hook, cb);
     for (size_t i = 0; i < row_of.size(); i++) last_batch_tokens[row_of[i]] = std::move(row_tokens[i]);
 }
 
@@ -577,7 +524,6 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     (void) voice_index(config.voice, "stream_begin");
     if (st_on) stream_end();
     const uint32_t slots = stream_capacity();
-    st_cfg = config;
     st_max_steps = hp.max_generation_size - 1;   // an utterance ends at position max_generation (check_stopping): at most this many steps after a 1-id prompt
     // the device sampler's vocabulary: every slot carries its own sampler record (stream_accepts); above it the session is greedy with one setting
     st_mixed = hp.output_vocab_size <= 2048;
@@ -587,29 +533,15 @@ void parler_runner::stream_begin(const generation_configuration & config) {
     } else {
         hip_check(tts_hip_parler_stream_begin(ctx, slots, st_max_steps, hp.bos_token_id, hp.eos_token_id, nullptr), "tts_hip_parler_stream_begin");
     }
-    st_free.clear();
-    for (uint32_t s = slots; s-- > 0;) st_free.push_back(s);   // pop_back hands out slot 0 first
-    st_ticket.assign(slots, 0);
+    session_open(config, slots);
     st_start.assign(slots, 0);
     st_voice.assign(slots, 0);
     st_wait.clear(); st_codec.clear(); st_pcm.clear();
-    st_live = 0;
     st_codec_held = 0;
-    st_on = true;
-    st_chunk_frames = 0;
-    st_on_chunk = nullptr;
     st_hook.reset();
 }
 
-// chunked audio out of the session (common.h; the override is declared in parler_session.h)
-bool parler_session::stream_chunks(uint32_t chunk_frames, std::function<bool(size_t, const float *, size_t)> on_chunk) {
-    if (chunk_frames == 0) TTS_ABORT("stream_chunks: chunk_frames must be >= 1\n");
-    if (!session_chunks_ready(chunk_frames)) return false;
-    st_chunk_frames = chunk_frames;
-    st_on_chunk = std::move(on_chunk);
-    return true;
-}
-
+// chunked audio out of the session (common.h): this runner's part of stream_session's hook
 bool parler_runner::session_chunks_ready(uint32_t chunk_frames) {
     if (!st_on) TTS_ABORT("stream_chunks: no session (stream_begin)\n");
     if (st_live != 0 || !st_wait.empty() || !st_codec.empty()) TTS_ABORT("stream_chunks: after stream_begin and before the first stream_submit\n");
@@ -619,18 +551,12 @@ bool parler_runner::session_chunks_ready(uint32_t chunk_frames) {
     const char * on = getenv("TTS_PARLER_STREAM_CHUNKS");
     if (!on || !*on || !strcmp(on, "0")) return false;
     const uint32_t slots = stream_capacity();
-    // the chunker calls back with the window's row, here the slot: the slot keeps its ticket until its last piece is out.  One utterance's
-    // "stop" must not end the others' chunks, so the chunker always hears "go on" and the slot is remembered instead.
-    st_slot_chunk = [this](uint32_t slot, const float * p, size_t k) {
-        if (!st_stopped[slot] && !st_on_chunk(st_ticket[slot], p, k)) st_stopped[slot] = 1;
-        return true;
-    };
-    st_hook = std::make_shared<chunker>(*this, chunk_frames, st_slot_chunk);
+    st_hook = std::make_unique<dac_chunker>(make_chunker(chunk_frames));
     st_hook->rows.assign(slots, {});
     st_toks.assign(slots, {});
     st_fin.assign(slots, false);
     st_state.assign(slots, SLOT_FREE);
-    st_stopped.assign(slots, 0);
+    st_stopped.clear();
     st_buf.assign((size_t) slots * st_max_steps * hp.n_output_heads, 0u);
     last_batch_tokens.clear();
     return true;
@@ -639,8 +565,6 @@ bool parler_runner::session_chunks_ready(uint32_t chunk_frames) {
 bool parler_runner::stream_accepts(const generation_configuration & config) const {
     return st_on && st_mixed && config.use_cross_attn == use_cross_attn && device_sampler(config) && voice_known(config.voice);
 }
-
-void parler_runner::stream_submit(size_t ticket, const std::string & sentence) { stream_submit(ticket, sentence, st_cfg); }
 
 void parler_runner::stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) {
     if (!st_on) TTS_ABORT("stream_submit: no session (stream_begin)\n");
@@ -664,31 +588,18 @@ void parler_runner::stream_submit(size_t ticket, const std::string & sentence, c
         st_hook->rows[p.slot] = {};
         st_toks[p.slot].clear();
         st_fin[p.slot] = false;
-        st_stopped[p.slot] = 0;
+        std::erase(st_stopped, (size_t) p.slot);
         st_state[p.slot] = SLOT_RUNNING;
     }
     st_wait.push_back(std::move(p));
     st_live++;
 }
 
-void parler_runner::remember_tokens(size_t ticket, const std::vector<uint32_t> & toks) {
-    if (ticket < TOKEN_RECORD_TICKETS) {   // generate_stream_chunked's tickets are the sentence indices: last_batch_tokens[i] as after generate_batch
-        if (last_batch_tokens.size() <= ticket) last_batch_tokens.resize(ticket + 1);
-        last_batch_tokens[ticket] = toks;
-    }
-    last_output_tokens = toks;
-}
-
 // stream_step with the hook (parler_runner.h), the newcomers admitted: the codec pass of the windows planned at the last look-in runs on the
 // codec's stream while this interval's decoder steps run on the decoder's.
 void parler_runner::stream_step_chunked(std::vector<stream_result> & finished) {
     const uint32_t slots = stream_capacity(), nh = hp.n_output_heads;
-    auto report = [&](size_t ticket) {
-        stream_result r;
-        r.ticket = ticket;   // no audio: everything went through the hook
-        finished.push_back(r);
-    };
-    for (const decoded & d : st_codec) report(d.ticket);   // prompts that left no room for generation: an empty answer, as generate() gives
+    for (const decoded & d : st_codec) report_no_audio(finished, d.ticket);   // prompts that left no room for generation: an empty answer, as generate() gives
     st_codec.clear();
     std::vector<uint32_t> fs(slots), fn(slots), cnt(slots);
     std::vector<uint8_t> done(slots);
@@ -698,7 +609,9 @@ void parler_runner::stream_step_chunked(std::vector<stream_result> & finished) {
     // nothing live but windows still planned: they are decoded without a launch
     if (running) hip_check(tts_hip_parler_stream_launch(ctx, STREAM_CHUNK), "tts_hip_parler_stream_launch");
     try {
-        (void) st_hook->emit();
+        // a window's key is its row, here the slot: the slot keeps its ticket until its last piece is out
+        st_hook->emit_session(std::vector<size_t>(st_hook->row_of.begin(), st_hook->row_of.end()),
+                              [this](size_t slot, const float * p, size_t k) { return st_on_chunk(st_ticket[slot], p, k); }, st_stopped);
     } catch (...) {
         // an error of the codec pass or a throwing callback: the steps under way are waited for, so the context stays usable
         if (running) (void) tts_hip_parler_stream_wait(ctx, nullptr, nullptr, nullptr, &nf, fs.data(), fn.data());
@@ -706,7 +619,7 @@ void parler_runner::stream_step_chunked(std::vector<stream_result> & finished) {
     }
     for (uint32_t s = 0; s < slots; s++) {   // those that had ended at the last look-in have had their last piece: the slot is free from here on
         if (st_state[s] != SLOT_CLOSING) continue;
-        report(st_ticket[s]);
+        report_no_audio(finished, st_ticket[s]);
         st_state[s] = SLOT_FREE;
         st_free.push_back(s);
         st_live--;
@@ -720,10 +633,10 @@ void parler_runner::stream_step_chunked(std::vector<stream_result> & finished) {
         const uint32_t steps = std::min(cnt[s], hp.max_generation_size - st_start[s]);   // what generate() would have run alone
         const uint32_t * b = st_buf.data() + (size_t) s * st_max_steps * nh;
         if ((size_t) steps * nh > t.size()) t.insert(t.end(), b + t.size(), b + (size_t) steps * nh);
-        if (st_stopped[s]) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
+        if (std::find(st_stopped.begin(), st_stopped.end(), s) != st_stopped.end()) {   // on_chunk ended it: reported with what it got, nothing more is decoded for it
             if (!done[s]) drop.push_back(s);
             remember_tokens(st_ticket[s], t);
-            report(st_ticket[s]);
+            report_no_audio(finished, st_ticket[s]);
             st_hook->rows[s] = {};
             t.clear();
             st_state[s] = SLOT_FREE;
@@ -817,11 +730,8 @@ void parler_runner::stream_step(std::vector<stream_result> & finished) {
 void parler_runner::stream_end() {
     if (!st_on) return;
     (void) tts_hip_parler_stream_end(ctx);
-    st_on = false;
+    session_close();
     st_wait.clear(); st_codec.clear();
-    st_live = 0;
-    st_chunk_frames = 0;
-    st_on_chunk = nullptr;
     st_hook.reset();
     st_buf.clear(); st_buf.shrink_to_fit();
 }

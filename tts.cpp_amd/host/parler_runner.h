@@ -7,16 +7,18 @@
 //
 // generate, generate_batch and their chunked forms share one generation loop (run_rows) over the prefilled rows: the device loop
 // (tts_hip_parler_gen_begin / _launch / _wait, a look-in every 32 steps) or, under TTS_HOST_LOOP or with more than 2048 logits per head,
-// the host loop (tts_hip_parler_step + sampler::sample per step).  Chunked audio is a hook called at that loop's look-ins.
+// the host loop (tts_hip_parler_step + sampler::sample per step).  Chunked audio is a hook called at that loop's look-ins: the shared DAC
+// chunker (chunk_windows.h) with parler_undelay as its rule.  The session's bookkeeping and its chunk hook come from stream_session.h.
 #pragma once
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/tts_hip.h"
+#include "chunk_windows.h"
 #include "common.h"
-#include "parler_session.h"
 #include "sampler.h"
+#include "stream_session.h"
 #include "tokenizer.h"
 
 extern const struct parler_model_loader final : tts_model_loader {
@@ -41,7 +43,7 @@ struct parler_hparams {  // defaults = Parler TTS Mini v1 (model.h:66-83)
 // this with next = 0 and finished.
 size_t parler_undelay(const uint32_t * toks, size_t steps, uint32_t nh, uint32_t audio_vocab, size_t next, bool finished, std::vector<uint32_t> & out);
 
-struct parler_runner final : parler_session {
+struct parler_runner final : stream_session {
     parler_runner(const parler_hparams & hp, unigram_tokenizer * tok, int device, bool use_cross_attn);
     ~parler_runner() override;
 
@@ -67,7 +69,6 @@ struct parler_runner final : parler_session {
     void     stream_begin(const generation_configuration & config) override;
     uint32_t stream_free() const override { return (uint32_t) st_free.size(); }
     uint32_t stream_live() const override { return st_live + (uint32_t) st_codec.size(); }
-    void     stream_submit(size_t ticket, const std::string & sentence) override;   // with the configuration the session was opened with
     // With at most 2048 logits per head the session is a mixed one (tts_hip_parler_stream_begin_mixed): every slot carries its own sampler record
     // and penalty table, so a request may differ from the session's configuration in sample, seed, top_k, top_p, temperature and
     // repetition_penalty.  It is accepted when use_cross_attn is the load-time value and it is greedy or within the device sampler's limits; its
@@ -78,7 +79,7 @@ struct parler_runner final : parler_session {
     void     stream_submit(size_t ticket, const std::string & sentence, const generation_configuration & config) override;
     void     stream_step(std::vector<stream_result> & finished) override;
     void     stream_end() override;
-    // chunked audio out of the session (the hook itself is declared in parler_session.h): with a hook set, stream_step launches its 32 steps
+    // chunked audio out of the session (the hook itself is stream_session's): with a hook set, stream_step launches its 32 steps
     // (tts_hip_parler_stream_launch), decodes the windows the last look-in planned while they run (one tts_hip_dac_decode_windows pass for all
     // slots) and hands their chunks out under the slots' tickets, then waits and takes the new rows of every live slot
     // (tts_hip_parler_stream_wait).  An utterance is reported in `finished` (no audio) once its last chunk is out, and its slot is free from then
@@ -93,12 +94,10 @@ struct parler_runner final : parler_session {
     bool          declare_only = false;   // tts_load_options at load time: no weight bytes uploaded by this runner
     tts_hip_ctx * share_ctx = nullptr;    // ... and whose arena it uses instead (same device)
     uint32_t max_seqs = 1;
-    std::vector<std::vector<uint32_t>> last_batch_tokens;  // per utterance, still delayed
 
     // pieces exposed for tests
     void                 adjust_output_tokens(const std::vector<uint32_t> & output_tokens, std::vector<uint32_t> & filtered) const;
-    std::vector<uint32_t> last_output_tokens;  // pctx->output_tokens of the last generate (still delayed)
-    std::vector<uint32_t> last_prompt_tokens;
+    // stream_session's records: last_output_tokens is pctx->output_tokens of the last generate, last_batch_tokens per utterance, both still delayed
 
     parler_hparams                     hp;
     std::unique_ptr<unigram_tokenizer> tokenizer;
@@ -124,36 +123,31 @@ struct parler_runner final : parler_session {
     bool prepare_batch(const std::vector<std::string> & sentences, const generation_configuration & config, std::vector<uint32_t> & start,
                        std::vector<uint32_t> & row_of);
     int  dac_halo = -1;   // tts_hip_dac_halo_frames of the codec layout (-1: unknown; chunked audio then decodes whole utterances)
-    struct chunker;       // the look-in hook of chunked audio: windows of the frames that became final -> codec -> callbacks
-    // the one generation loop, over n prefilled rows (row i starts at start[i]); hook: nullptr, or called at every look-in; tokens per row out
-    std::vector<std::vector<uint32_t>> run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, chunker * hook);
+    dac_chunker make_chunker(uint32_t chunk_frames);   // the look-in hook of chunked audio: windows of the frames that became final -> codec -> callbacks
+    // the one generation loop, over n prefilled rows (row i starts at start[i]); hook: nullptr, or planned and handed to on_chunk(row, ...) at every
+    // look-in; tokens per row out
+    std::vector<std::vector<uint32_t>> run_rows(const std::vector<uint32_t> & start, const generation_configuration & config, dac_chunker * hook,
+                                                const std::function<bool(uint32_t, const float *, size_t)> & on_chunk = {});
     std::vector<tts_response> decode_frames(const std::vector<uint32_t> & codes, const std::vector<uint32_t> & frames);
     // session state of the continuous batching
     struct pending { size_t ticket; uint32_t slot; std::vector<uint32_t> prompt; generation_configuration cfg; uint32_t voice = 0; };
     struct decoded { size_t ticket; std::vector<uint32_t> frames; };   // un-delayed codes waiting for a codec pass
-    bool                        st_on = false;
     bool                        st_mixed = false;    // the open session carries a sampler per slot
-    generation_configuration    st_cfg{};
-    uint32_t                    st_live = 0, st_max_steps = 0;
+    uint32_t                    st_max_steps = 0;
     uint32_t                    st_codec_hold = 1;   // tts_load_options::stream_codec_hold at load time
     uint32_t                    st_codec_held = 0;   // stream_step calls the oldest undecoded finished utterance has waited for a codec group to fill
-    std::vector<uint32_t>       st_free;            // free cache slots
-    std::vector<size_t>         st_ticket;          // slot -> ticket
     std::vector<uint32_t>       st_start;           // slot -> prompt length
     std::vector<pending>        st_wait;            // submitted, not yet admitted (admitted as one side batch by the next stream_step)
     std::vector<decoded>        st_codec;
     std::vector<std::vector<float>> st_pcm;         // audio handed out by the last stream_step
     // ... with the chunk hook: the chunker's rows are the slots
-    static constexpr size_t TOKEN_RECORD_TICKETS = 4096;
     enum : uint8_t { SLOT_FREE = 0, SLOT_RUNNING = 1, SLOT_CLOSING = 2 };   // closing: ended, its last windows planned and not yet handed out
     bool session_chunks_ready(uint32_t chunk_frames) override;
     void stream_step_chunked(std::vector<stream_result> & finished);
-    void remember_tokens(size_t ticket, const std::vector<uint32_t> & toks);
-    std::shared_ptr<chunker>           st_hook;     // plan() / emit() over the slots; calls st_slot_chunk
-    std::function<bool(uint32_t, const float *, size_t)> st_slot_chunk;   // slot -> its ticket's on_chunk; remembers who said stop
+    std::unique_ptr<dac_chunker>       st_hook;     // plan() / emit_session() over the slots
     std::vector<std::vector<uint32_t>> st_toks;     // slot -> the occupant's tokens so far, still delayed
     std::vector<bool>                  st_fin;      // slot -> its occupant has ended (plan() then cuts its tail)
     std::vector<uint8_t>               st_state;    // slot -> SLOT_*
-    std::vector<uint8_t>               st_stopped;  // slot -> its occupant's on_chunk returned false
+    std::vector<size_t>                st_stopped;  // the slots whose occupant's on_chunk returned false
     std::vector<uint32_t>              st_buf;      // what tts_hip_parler_stream_wait writes: [slots][max_steps][heads]
 };

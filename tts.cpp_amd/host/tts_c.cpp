@@ -283,20 +283,14 @@ void         tts_c_free(tts_c_runner * r) { delete (tts_generation_runner *) r; 
 int tts_c_last_tokens(tts_c_runner * r, int which, uint32_t * out, int cap) {
     static const std::vector<uint32_t> none;
     const std::vector<uint32_t> * vp = nullptr;
-    if (auto * p = dynamic_cast<parler_runner *>((tts_generation_runner *) r))
-        vp = which == 0 ? &p->last_prompt_tokens
-           : which == 2 ? &p->last_conditional_tokens
-           : which >= 16 ? ((size_t) (which - 16) < p->last_batch_tokens.size() ? &p->last_batch_tokens[(size_t) (which - 16)] : &none)
-           : &p->last_output_tokens;
-    else if (auto * o = dynamic_cast<orpheus_runner *>((tts_generation_runner *) r))
-        vp = which == 0 ? &o->last_prompt_tokens
-           : which == 1 ? &o->last_output_tokens
-           : which >= 16 && (size_t) (which - 16) < o->last_batch_tokens.size() ? &o->last_batch_tokens[(size_t) (which - 16)] : &none;
-    else if (auto * d = dynamic_cast<dia_runner *>((tts_generation_runner *) r))
-        vp = which == 0 ? &d->last_prompt_tokens
-           : which == 1 ? &d->last_output_tokens
-           : which >= 16 && (size_t) (which - 16) < d->last_batch_tokens.size() ? &d->last_batch_tokens[(size_t) (which - 16)] : &none;
-    else if (auto * k = dynamic_cast<kokoro_runner *>((tts_generation_runner *) r))
+    if (auto * s = dynamic_cast<stream_session *>((tts_generation_runner *) r)) {
+        // Parler numbers its records its own way: 2 is the conditional prompt and every other value below 16 the output
+        auto * p = dynamic_cast<parler_runner *>(s);
+        vp = which >= 16 ? ((size_t) (which - 16) < s->last_batch_tokens.size() ? &s->last_batch_tokens[(size_t) (which - 16)] : &none)
+           : which == 0 ? &s->last_prompt_tokens
+           : p && which == 2 ? &p->last_conditional_tokens
+           : p || which == 1 ? &s->last_output_tokens : &none;
+    } else if (auto * k = dynamic_cast<kokoro_runner *>((tts_generation_runner *) r))
         vp = which == 0 ? &k->last_prompt_tokens : &none;
     if (!vp) { g_c_err = "runner keeps no token record"; return -1; }
     const std::vector<uint32_t> & v = *vp;
@@ -440,6 +434,49 @@ extern "C" int64_t tts_c_dia_final_frames(const uint32_t * tokens, uint64_t n_st
     const uint64_t frames = f.size() / hp.n_output_heads;
     if (out) copy_u32(out, f.data(), (size_t) (frames < cap_frames ? frames : cap_frames) * hp.n_output_heads);
     return (int64_t) frames;
+}
+
+// ---- the chunk-window planner (host/chunk_windows.h) -----------------------------------------------------------
+extern "C" int64_t tts_c_chunk_windows(int rule, const uint32_t * tokens, uint64_t n_steps, uint32_t n_heads, uint32_t audio_vocab, uint32_t max_delay, uint32_t halo,
+                                       uint32_t chunk_frames, uint64_t piece, uint32_t * windows, uint32_t * cut_at, uint64_t cap_windows, uint32_t * codes,
+                                       uint64_t cap_frames, uint64_t * n_kept) {
+    dia_hparams hp;
+    hp.audio_vocab_size = audio_vocab; hp.max_delay = max_delay;
+    if (rule == 1) n_heads = hp.n_output_heads;
+    if ((rule != 0 && rule != 1) || n_heads == 0 || chunk_frames == 0) { g_c_err = "tts_c_chunk_windows: rule must be 0 or 1, n_heads and chunk_frames >= 1"; return -1; }
+    std::vector<float> no_pcm;
+    dac_chunker ck{rule == 1 ? dac_chunker::undelay_fn([&](const uint32_t * t, size_t steps, size_t judged, bool, std::vector<uint32_t> & kept) {
+                                   return dia_undelay(hp, t, steps, judged, kept);
+                               })
+                             : dac_chunker::undelay_fn([&](const uint32_t * t, size_t steps, size_t judged, bool finished, std::vector<uint32_t> & kept) {
+                                   return parler_undelay(t, steps, n_heads, audio_vocab, judged, finished, kept);
+                               }),
+                   n_heads, 1, halo, chunk_frames, nullptr, no_pcm};
+    std::vector<std::vector<uint32_t>> toks(1);
+    uint64_t n_windows = 0, kept = 0;
+    auto feed = [&](uint64_t steps, bool finished) {   // one look-in: the stream so far to plan(), which cuts at most one window of the one row
+        toks[0].insert(toks[0].end(), tokens + toks[0].size(), tokens + steps * n_heads);
+        const uint32_t emitted = ck.rows.empty() ? 0 : ck.rows[0].emitted;
+        ck.plan(toks, {finished});
+        if (ck.row_of.empty()) return;
+        const uint32_t w0 = emitted - ck.keep0[0], k = ck.keep1[0] - ck.keep0[0];
+        if (n_windows < cap_windows) {
+            if (windows) { uint32_t * w = windows + 4 * n_windows; w[0] = w0; w[1] = w0 + ck.frames[0]; w[2] = ck.keep0[0]; w[3] = ck.keep1[0]; }
+            if (cut_at) { cut_at[2 * n_windows] = (uint32_t) steps; cut_at[2 * n_windows + 1] = finished ? 1 : 0; }
+        }
+        if (codes && kept < cap_frames) copy_u32(codes + kept * n_heads, ck.codes.data() + (size_t) ck.keep0[0] * n_heads, (size_t) std::min<uint64_t>(k, cap_frames - kept) * n_heads);
+        n_windows++;
+        kept += k;
+        ck.clear();
+    };
+    if (piece == 0) piece = n_steps ? n_steps : 1;
+    for (uint64_t s = std::min<uint64_t>(piece, n_steps);; s = std::min<uint64_t>(s + piece, n_steps)) {
+        feed(s, false);
+        if (s >= n_steps) break;
+    }
+    feed(n_steps, true);
+    if (n_kept) *n_kept = kept;
+    return (int64_t) n_windows;
 }
 
 // ---- Kokoro host logic (host/kokoro_runner.h) -------------------------------------------------------------------

@@ -31,7 +31,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_pool_create", "tts_c_pool_set_text_encoder", "tts_c_pool_set_continuous", "tts_c_pool_set_continuous_yield_ms", "tts_c_pool_admitted_in_flight", "tts_c_pool_conditional_prompt", "tts_c_pool_submit", "tts_c_pool_wait", "tts_c_pool_release", "tts_c_pool_stats", "tts_c_pool_load_stats", "tts_c_pool_free", "tts_c_set_load_options", "tts_c_set_load_options_ex", "tts_c_runner_device_context", "tts_c_runner_tokenize",
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
-           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames",
+           "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames", "tts_c_chunk_windows",
            "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs", "tts_c_generate_stream_chunked_configs",
            "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes", "tts_c_runner_stream_capacity"]
 
@@ -126,6 +126,9 @@ def load_lib():
         L.tts_c_parler_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
         L.tts_c_dia_final_frames.restype = C.c_int64
         L.tts_c_dia_final_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64]
+        L.tts_c_chunk_windows.restype = C.c_int64
+        L.tts_c_chunk_windows.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -399,6 +402,29 @@ def dia_final_frames(tokens, audio_vocab, max_delay, piece=0):
     out = np.zeros((max(n, 1), 9), dtype=np.uint32)
     L.tts_c_dia_final_frames(tp, steps, audio_vocab, max_delay, piece, out.ctypes.data_as(C.POINTER(C.c_uint32)), n)
     return out[:n]
+
+
+def chunk_windows(rule, tokens, audio_vocab, halo, chunk_frames, piece=0, max_delay=0):
+    """tts_c_chunk_windows: the runners' chunk-window planner (host/chunk_windows.h) over delayed tokens [steps][heads], fed in pieces of `piece`
+    steps (0: all at once) and then once more marked finished.  rule "parler" or "dia" (its nine heads, max_delay).  Returns (windows [n][4] =
+    w0, w1, keep0, keep1 with the kept range relative to w0; cut_at [n][2] = steps fed when the window was cut, 1 if the stream was marked
+    finished; codes [kept frames][heads] = the kept frames of all windows back to back)"""
+    dia = {"parler": 0, "dia": 1}[rule] == 1
+    t = np.ascontiguousarray(tokens, dtype=np.uint32)
+    t = t.reshape(-1, 9) if dia else t
+    steps, nh = t.shape
+    L = load_lib()
+    tp = t.ctypes.data_as(C.POINTER(C.c_uint32))
+    kept = C.c_uint64()
+    args = (1 if dia else 0, tp, steps, nh, audio_vocab, max_delay, halo, chunk_frames, piece)
+    n = L.tts_c_chunk_windows(*args, None, None, 0, None, 0, C.byref(kept))
+    if n < 0:
+        raise RunnerError(L.tts_c_last_error().decode("utf-8", "replace"))
+    win, cut = np.zeros((max(n, 1), 4), dtype=np.uint32), np.zeros((max(n, 1), 2), dtype=np.uint32)
+    codes = np.zeros((max(kept.value, 1), nh), dtype=np.uint32)
+    u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+    L.tts_c_chunk_windows(*args, u32(win), u32(cut), n, u32(codes), kept.value, None)
+    return win[:n], cut[:n], codes[:kept.value]
 
 
 def _qparams(qtype, n_threads=1, output_heads=False, text_embeddings=False, cross_attn_kv=False, dac_f16=False, non_quantizable_f16=False):
