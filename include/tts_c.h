@@ -234,6 +234,12 @@ int tts_c_kokoro_chunks(const char *const *vocab, int n_vocab, const char *phone
 /* the state of the reference's noise engine (random_uniform_gen, src/util.cpp:65-71: std::default_random_engine = minstd_rand0) after k more draws:
  * kokoro_runner::generate_batch hands every clause its stretch of the one stream this way (host/kokoro_runner.h) */
 uint32_t tts_c_minstd0_jump(uint32_t state, uint64_t k);
+/* generate_batch's plan for the duration passes (TTS_KOKORO_ROWS): the pieces sorted by non-increasing token count (stable), in consecutive groups of at most
+ * max_per_group.  out receives, per group, its size followed by its piece indices; returns the number of uint32 written (or needed, when larger than cap) */
+int tts_c_kokoro_duration_groups(const uint32_t *lengths, int n, int max_per_group, uint32_t *out, int cap);
+/* starts_out[i] = the noise engine's state at the first draw of piece i, which draws frames[i] * per_frame values (pieces in clause order); returns the state
+ * after the last piece */
+uint32_t tts_c_kokoro_noise_starts(uint32_t state, const uint64_t *frames, int n, uint64_t per_frame, uint32_t *starts_out);
 /* n draws of that engine through std::uniform_real_distribution<float>(0, 1) from `state`, drawn as `threads` parallel stretches (what the runner does for a
  * clause's source noise); returns the state afterwards */
 uint32_t tts_c_minstd0_uniform(uint32_t state, uint64_t n, float *out, uint32_t threads);

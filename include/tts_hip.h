@@ -584,6 +584,14 @@ tts_hip_ctx *tts_hip_kokoro_create(int device, const tts_hip_kokoro_desc *desc);
 /* tokens [n] (bos, phoneme ids, eos); voice: the name after "kokoro.voice_tensors."; lens_out [n] = clamp(round(sum of the
  * duration sigmoids), 1, 50) (:1035-1037); hidden_out [n][duration hidden + style half] (:1029-1031) */
 int tts_hip_kokoro_durations(tts_hip_ctx *ctx, const uint32_t *tokens, uint32_t n, const char *voice, float *lens_out, float *hidden_out);
+#define TTS_HIP_KOKORO_ROWS_MAX 8
+/* B clauses in one pass. tokens: the clauses' ids back to back; n[b] in 3..max_ctx; voices[b]: name after "kokoro.voice_tensors.".
+ * lens_out [sum n], hidden_out [sum n][duration hidden + style half] (may be NULL), both in the caller's clause order.
+ * Every clause's lens / hidden are bit for bit what tts_hip_kokoro_durations gives for that clause alone under the same tune keys.
+ * Inside, the clauses are worked on sorted by non-increasing length (stable); the recurrences of all clauses advance in lock-step
+ * (kk_lstm_rows_kernel, csrc/kokoro_kernels.h), so similar lengths waste the fewest steps. */
+int tts_hip_kokoro_durations_batch(tts_hip_ctx *ctx, const uint32_t *tokens, const uint32_t *n, uint32_t B,
+                                   const char *const *voices, float *lens_out, float *hidden_out);
 /* lens [n]: whole numbers (the predicted ones, or forced); hidden [n][duration hidden + style half] from the call above;
  * noise [(harmonic_num + 1) * total * up_sampling_factor] uniform draws, total = sum(lens); pcm_out [total * up_sampling_factor].
  * hsrc_out / hsrc_in (may be NULL) [2 * (n_fft / 2 + 1)][2 * total * upsample_scale / hop + 1]: the STFT conditioning read out /

@@ -308,6 +308,243 @@ __global__ __launch_bounds__(256) void kk_lstm_split_kernel(LstmArgs a) {
     }
 }
 
+// ---- several clauses in one pass (tts_hip_kokoro_durations_batch) ------------------------------------------------------------------
+// The clauses' rows lie back to back, sorted by non-increasing length; clause b owns rows off .. off + len - 1.  Everything that works on
+// a row alone (projections, norms, gelu, adds) runs over all R rows as it is; the kernels below are the ones that need to know the clause.
+#define KK_ROWS_MAX 8
+struct KkClause {
+    int off, len;               // first row, rows
+    const float *style;         // the clause's style row (voice tensor row len - 3, second half)
+};
+
+// kk_albert_embed_kernel with the position counted inside the row's clause
+static __global__ void kk_albert_embed_rows_kernel(const float *tok_embd, const float *pos_embd, const float *type_embd, const uint32_t *tok, int n, int E, float *x,
+                                                   const KkClause *cl, const int *row_clause) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t) n * E) return;
+    const int t = (int) (i / E), e = (int) (i - (int64_t) t * E);
+    const int pos = t - cl[row_clause[t]].off;
+    x[i] = (tok_embd[(int64_t) tok[t] * E + e] + pos_embd[(int64_t) pos * E + e]) + type_embd[e];
+}
+
+// sty[b][s] = the style row of clause b (the gamma / beta projections read one row per clause)
+static __global__ void kk_gather_style_kernel(const KkClause *cl, int B, int S, float *sty) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * S) return;
+    sty[i] = cl[i / S].style[i % S];
+}
+
+// kk_fill_cols_kernel with the style row of the row's clause
+static __global__ void kk_fill_cols_rows_kernel(float *x, int n, int ld, int off, const KkClause *cl, const int *row_clause, int S) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t) n * S) return;
+    const int t = (int) (i / S), s = (int) (i - (int64_t) t * S);
+    x[(int64_t) t * ld + off + s] = cl[row_clause[t]].style[s];
+}
+
+// kk_norm_rows_kernel mode 1 (AdaLayerNorm) with gamma / beta [B][H] of the row's clause
+static __global__ __launch_bounds__(64) void kk_norm_rows_clause_kernel(const float *x, int ldx, int H, float eps, const float *gamma, const float *beta, const int *row_clause, float *y,
+                                                                        int ldy) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const float *xr = x + (int64_t) r * ldx;
+    const float *w = gamma + (int64_t) row_clause[r] * H, *b = beta + (int64_t) row_clause[r] * H;
+    float s = 0.0f;
+    for (int i = lane; i < H; i += 64) s += xr[i];
+    const float mean = wave_sum(s) / (float) H;
+    float v2 = 0.0f;
+    for (int i = lane; i < H; i += 64) { const float d = xr[i] - mean; v2 += d * d; }
+    const float scale = 1.0f / sqrtf(wave_sum(v2) / (float) H + eps);
+    for (int i = lane; i < H; i += 64) {
+        const float n = (xr[i] - mean) * scale;
+        const float o = (n + n * w[i]) + b[i];
+        y[(int64_t) r * ldy + i] = o;
+    }
+}
+
+// kk_albert_attn_kernel for clause c0 + blockIdx.z: a row attends to its own clause's keys.  grid (heads, longest clause, clauses), dynamic LDS for the longest
+static __global__ __launch_bounds__(64) void kk_albert_attn_rows_kernel(const float *q, const float *k, const float *v, const KkClause *cl, int c0, int H, int hs, float scale, float *out) {
+    extern __shared__ float kk_sc[];
+    const KkClause me = cl[c0 + blockIdx.z];
+    const int n = me.len, h = blockIdx.x, t = blockIdx.y, lane = threadIdx.x;
+    if (t >= n) return;
+    q += (int64_t) me.off * H; k += (int64_t) me.off * H; v += (int64_t) me.off * H; out += (int64_t) me.off * H;
+    const float *qr = q + (int64_t) t * H + h * hs;
+    float mx = -INFINITY;
+    for (int j = lane; j < n; j += 64) {
+        const float *kr = k + (int64_t) j * H + h * hs;
+        float d = 0.0f;
+        for (int e = 0; e < hs; e++) d += qr[e] * kr[e];
+        d *= scale;
+        kk_sc[j] = d;
+        mx = fmaxf(mx, d);
+    }
+    mx = wave_max(mx);
+    float sum = 0.0f;
+    for (int j = lane; j < n; j += 64) { const float p = expf(kk_sc[j] - mx); kk_sc[j] = p; sum += p; }
+    sum = wave_sum(sum);
+    __syncthreads();
+    const float inv = 1.0f / sum;
+    for (int e = lane; e < hs; e += 64) {
+        float a = 0.0f;
+        for (int j = 0; j < n; j++) a += (kk_sc[j] * inv) * v[(int64_t) j * H + h * hs + e];
+        out[(int64_t) t * H + h * hs + e] = a;
+    }
+}
+
+// kk_albert_attn64_kernel for clause c0 + blockIdx.z; grid (heads, ceil(longest clause / 4), clauses), dynamic LDS for the longest
+static __global__ __launch_bounds__(256) void kk_albert_attn64_rows_kernel(const float *q, const float *k, const float *v, const KkClause *cl, int c0, int H, float scale, float *out) {
+    extern __shared__ float kk_sm[];
+    constexpr int HS = 64, LD = 65;
+    const KkClause me = cl[c0 + blockIdx.z];
+    const int n = me.len;
+    if ((int) blockIdx.y * 4 >= n) return;    // the whole workgroup lies past this clause's rows (uniform: no barrier is missed)
+    q += (int64_t) me.off * H; k += (int64_t) me.off * H; v += (int64_t) me.off * H; out += (int64_t) me.off * H;
+    float *ks = kk_sm;                        // [64][65] the chunk's keys
+    float *qs = ks + 64 * LD;                 // [4][64] the rows' queries
+    float *sc = qs + 4 * HS;                  // [4][n] scores -> probabilities
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = blockIdx.y * 4 + wave;
+    const bool live = t < n;
+    qs[wave * HS + lane] = live ? q[(int64_t) t * H + h * HS + lane] : 0.0f;
+    float *scw = sc + (size_t) wave * n;
+    float mx = -INFINITY;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int idx = tid + i * 256, key = idx >> 6, e = idx & 63;
+            ks[key * LD + e] = k[(int64_t) min(j0 + key, n - 1) * H + h * HS + e];
+        }
+        __syncthreads();
+        if (live && j0 + lane < n) {
+            const float *qr = qs + wave * HS, *kr = ks + lane * LD;
+            float d = 0.0f;
+            for (int e = 0; e < HS; e++) d = __builtin_fmaf(qr[e], kr[e], d);
+            d *= scale;
+            scw[j0 + lane] = d;
+            mx = fmaxf(mx, d);
+        }
+    }
+    if (!live) return;                        // (no barrier below)
+    mx = wave_max(mx);
+    float sum = 0.0f;
+    for (int j = lane; j < n; j += 64) { const float p = expf(scw[j] - mx); scw[j] = p; sum += p; }
+    sum = wave_sum(sum);
+    const float inv = 1.0f / sum;
+    float a = 0.0f;
+    for (int j = 0; j < n; j++) a = __builtin_fmaf(scw[j] * inv, v[(int64_t) j * H + h * HS + lane], a);
+    out[(int64_t) t * H + h * HS + lane] = a;
+}
+
+// kk_lstm_split_kernel for up to KK_ROWS_MAX sequences advanced in lock-step: a recurrence step is one granule hand-off (~1 us) around a CP-term dot
+// product per thread, so a second ... eighth sequence reuses the recurrent weights the thread holds in registers and rides the same hand-off.
+// Same grid and thread mapping (hid / 16 workgroups per direction, thread = (unit, gate, part)).  At step idx the live sequences are the prefix
+// {b : idx < len[b]} (non-increasing lengths); forward reads row off + idx, reversed off + len - 1 - idx; a finished sequence loads, computes and
+// stores nothing.  Hidden states [B][hid] in LDS; granules [2 dirs][2 parities][B][hid], one device-scope store each.  A thread issues the polls of
+// all its live sequences before it tests the first tag.  The parity buffer is safe as in the single kernel: a workgroup writes step idx only after
+// it has seen every peer's step idx - 1 of the longest sequence, and a peer publishes a step after it has read all live sequences of the step before.
+// Per sequence the arithmetic is kk_lstm_split_kernel's, term for term: the same bits as that kernel on the sequence alone.  The gate math of
+// sequence b is done by lane b of the unit's 16 (the single kernel: lane 0), which keeps that sequence's cell state.
+struct LstmRowsArgs {
+    const float *pre[2];        // [4][R][hid] input pre-activations per direction
+    const float *whh[2][4];     // [hid][hid] per gate (i, f, g, o)
+    const float *bhh[2][4];     // [hid]
+    unsigned long long *xch;    // [2 dirs][2 parities][B][hid] granules, zeroed before the launch
+    float *out;                 // [R][out_stride]
+    const KkClause *cl;         // [B] in non-increasing length
+    int R, B, hid, out_stride;
+    int *stuck;
+};
+
+template <int CP>
+__global__ __launch_bounds__(256) void kk_lstm_rows_kernel(LstmRowsArgs a) {
+    extern __shared__ float kk_h[];   // [B][hid] previous hidden states
+    const int tid = threadIdx.x, dir = blockIdx.y;
+    const int u = tid >> 4, g = (tid >> 2) & 3, p = tid & 3, me = tid & 15;
+    const int unit = blockIdx.x * 16 + u, hid = a.hid, B = a.B;
+    float w[CP];
+    {
+        const float *wr = a.whh[dir][g] + (int64_t) unit * hid + p * CP;
+#pragma unroll
+        for (int j = 0; j < CP; j++) w[j] = wr[j];
+    }
+    const float bias = a.bhh[dir][g][unit];
+    const float *pre = a.pre[dir] + (int64_t) g * a.R * hid + unit;
+    unsigned long long *xch = a.xch + (int64_t) dir * 2 * B * hid;
+    int off[KK_ROWS_MAX], len[KK_ROWS_MAX];
+#pragma unroll
+    for (int b = 0; b < KK_ROWS_MAX; b++) {
+        off[b] = b < B ? a.cl[b].off : 0;
+        len[b] = b < B ? a.cl[b].len : 0;
+    }
+    const int my_off = me < B ? a.cl[me].off : 0, my_len = me < B ? a.cl[me].len : 0;
+    float c = 0.0f;
+    const int L = len[0];
+    for (int idx = 0; idx < L; idx++) {
+        int nl = 0;
+#pragma unroll
+        for (int b = 0; b < KK_ROWS_MAX; b++) nl += idx < len[b] ? 1 : 0;
+        float pv[KK_ROWS_MAX];
+#pragma unroll
+        for (int b = 0; b < KK_ROWS_MAX; b++) {
+            pv[b] = 0.0f;
+            if (b < nl) pv[b] = pre[(int64_t) (dir ? off[b] + len[b] - 1 - idx : off[b] + idx) * hid];   // issued before the wait
+        }
+        if (idx == 0) {
+            for (int j = tid; j < B * hid; j += 256) kk_h[j] = 0.0f;
+        } else {
+            const unsigned long long *slot = xch + (int64_t) ((idx - 1) & 1) * B * hid;
+            for (int j = tid; j < hid; j += 256) {
+                unsigned long long v[KK_ROWS_MAX];
+#pragma unroll
+                for (int b = 0; b < KK_ROWS_MAX; b++)
+                    if (b < nl) v[b] = __hip_atomic_load(slot + b * hid + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                for (int b = 0; b < KK_ROWS_MAX; b++) {
+                    if (b >= nl) continue;
+                    int spins = 0;
+                    while ((unsigned) (v[b] >> 32) != (unsigned) idx) {
+                        // as in kk_lstm_split_kernel: give up once, for the whole launch
+                        if (++spins > (1 << 22)) { __hip_atomic_store(a.stuck, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                        if ((spins & 1023) == 0 && __hip_atomic_load(a.stuck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                        __builtin_amdgcn_s_sleep(1);
+                        v[b] = __hip_atomic_load(slot + b * hid + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    kk_h[b * hid + j] = __uint_as_float((unsigned) v[b]);
+                }
+            }
+        }
+        if (idx > 0 && __syncthreads_or(__hip_atomic_load(a.stuck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) return;   // fail fast (the host reports kk_stuck)
+        __syncthreads();
+        float gi = 0.0f, gf = 0.0f, gg_ = 0.0f, go = 0.0f;   // the gates of sequence `me`
+        const int base = (tid & 63) & ~15;                    // lane of (u, gate 0, part 0) inside the wave
+#pragma unroll
+        for (int b = 0; b < KK_ROWS_MAX; b++) {
+            if (b >= nl) continue;
+            const float *hb = kk_h + b * hid + p * CP;
+            float acc = 0.0f;
+#pragma unroll
+            for (int j = 0; j < CP; j++) acc += w[j] * hb[j];
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);                        // the four parts of row (g, unit)
+            const float gate = pv[b] + (acc + bias);
+            const float bi = __shfl(gate, base), bf = __shfl(gate, base + 4), bg = __shfl(gate, base + 8), bo = __shfl(gate, base + 12);
+            if (me == b) { gi = bi; gf = bf; gg_ = bg; go = bo; }
+        }
+        if (idx < my_len) {
+            const float ig = 1.0f / (1.0f + expf(-gi)), fg = 1.0f / (1.0f + expf(-gf)), gg = tanhf(gg_), og = 1.0f / (1.0f + expf(-go));
+            c = fg * c + ig * gg;
+            const float h = tanhf(c) * og;
+            const int t = dir ? my_off + my_len - 1 - idx : my_off + idx;
+            a.out[(int64_t) t * a.out_stride + dir * hid + unit] = h;
+            if (idx + 1 < my_len)
+                __hip_atomic_store(xch + (int64_t) (idx & 1) * B * hid + me * hid + unit, ((unsigned long long) (unsigned) (idx + 1) << 32) | __float_as_uint(h), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();   // kk_h is rewritten by the next step
+    }
+}
+
 static __global__ __launch_bounds__(1024) void kk_lstm_kernel(const float *pre, const float *whh0, const float *whh1, const float *whh2, const float *whh3, const float *bhh0,
                                                        const float *bhh1, const float *bhh2, const float *bhh3, int L, int hid, int reversed, float *out, int out_stride,
                                                        int out_off) {

@@ -1026,6 +1026,56 @@ struct KRun {
                                L, hid, dir, out, 2 * hid, dir * hid);
         }
     }
+    // ---- several clauses in one pass (tts_hip_kokoro_durations_batch): R rows of clauses sorted by non-increasing length ----
+    // A row takes the projection kernel its clause alone would take (the two sum in different orders): the clauses of >= 32 rows are a
+    // prefix of Rm rows and go through the matrix-pipe kernel, the rest through the wave-per-output kernel; both compute a row independently of its neighbours.
+    void linear_rows(const float *W, const float *b, const float *x, int ldx, int R, int Rm, int K, int N, float *y, int ldy) {
+        if (!W || !x || !y) return;
+        int r0 = 0;
+        if (c->kk_mfma && Rm > 0 && K % 16 == 0 && ldx % 4 == 0 && ((uintptr_t) W & 15) == 0 && ((uintptr_t) x & 15) == 0) {
+            hipLaunchKernelGGL(kk_linear_mfma_kernel, dim3((unsigned) ((N + 63) / 64), (unsigned) ((Rm + 63) / 64)), dim3(256), 0, st, W, b, x, ldx, Rm, K, N, y, ldy, 0);
+            r0 = Rm;
+        }
+        if (R > r0)
+            hipLaunchKernelGGL(kk_linear_kernel, dim3((unsigned) (((int64_t) (R - r0) * N + 3) / 4)), dim3(256), 0, st, W, b, x + (size_t) r0 * ldx, ldx, R - r0, K, N,
+                               y + (size_t) r0 * ldy, ldy, 0);
+    }
+    // bilstm over the clauses: one lock-step launch (kk_lstm_rows_kernel) where bilstm would split, else bilstm per clause
+    void bilstm_rows(const std::string &base, const float *x, int R, int Rm, int in, int hid, float *out, const KkClause *d_cl, const KkClause *h_cl, int B) {
+        const int cp = hid / 4;
+        const bool split = c->kk_lstm_split && hid % 16 == 0 && (cp == 4 || cp == 8 || cp == 16 || cp == 32 || cp == 64 || cp == 128);
+        if (!split) {
+            for (int b = 0; b < B; b++) bilstm(base, x + (size_t) h_cl[b].off * in, h_cl[b].len, in, hid, out + (size_t) h_cl[b].off * 2 * hid);
+            return;
+        }
+        float *pre = s.f((size_t) 8 * R * hid);   // [dir][4][R][hid]
+        LstmRowsArgs la{};
+        for (int dir = 0; dir < 2; dir++) {
+            const std::string wn = dir ? ".0.reverse_weights." : ".0.weights.", bn = dir ? ".0.reverse_biases." : ".0.biases.";
+            float *pd = pre ? pre + (size_t) dir * 4 * R * hid : nullptr;
+            for (int g = 0; g < 4; g++) {
+                linear_rows(w(base + wn + std::to_string(2 * g)), w(base + bn + std::to_string(2 * g)), x, in, R, Rm, in, hid, pd ? pd + (size_t) g * R * hid : nullptr, hid);
+                la.whh[dir][g] = w(base + wn + std::to_string(2 * g + 1));
+                la.bhh[dir][g] = w(base + bn + std::to_string(2 * g + 1));
+            }
+            la.pre[dir] = pd;
+        }
+        float *xch = s.f((size_t) 2 * 2 * B * hid * 2);   // 8-byte granules
+        if (!err.empty() || !pre || !xch) return;
+        (void) hipMemsetAsync(xch, 0, (size_t) 2 * 2 * B * hid * 8, st);
+        (void) hipMemsetAsync(c->kk_stuck, 0, 4, st);
+        la.xch = (unsigned long long *) xch; la.out = out; la.cl = d_cl; la.R = R; la.B = B; la.hid = hid; la.out_stride = 2 * hid; la.stuck = c->kk_stuck;
+        const dim3 grid(hid / 16, 2);   // as kk_lstm_split_kernel: the exchange assumes no more workgroups than that
+        const size_t lds = (size_t) B * hid * 4;
+        switch (cp) {
+            case 4: hipLaunchKernelGGL(kk_lstm_rows_kernel<4>, grid, dim3(256), lds, st, la); break;
+            case 8: hipLaunchKernelGGL(kk_lstm_rows_kernel<8>, grid, dim3(256), lds, st, la); break;
+            case 16: hipLaunchKernelGGL(kk_lstm_rows_kernel<16>, grid, dim3(256), lds, st, la); break;
+            case 32: hipLaunchKernelGGL(kk_lstm_rows_kernel<32>, grid, dim3(256), lds, st, la); break;
+            case 64: hipLaunchKernelGGL(kk_lstm_rows_kernel<64>, grid, dim3(256), lds, st, la); break;
+            default: hipLaunchKernelGGL(kk_lstm_rows_kernel<128>, grid, dim3(256), lds, st, la); break;
+        }
+    }
     // gamma / beta = W style + b, then the fused instance norm (:93-101)
     void adain(float *x, int C, int64_t L, const float *style, int S, const std::string &gw, const std::string &gb, const std::string &bw, const std::string &bb, int act,
                float slope, const float *alpha) {
@@ -1255,6 +1305,130 @@ extern "C" int tts_hip_kokoro_durations(tts_hip_ctx *c, const uint32_t *tokens, 
     HIPCHK(hipMemcpyAsync(lens_out, lens, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return kokoro_check_stuck(c, "tts_hip_kokoro_durations");
+}
+
+// tts_hip_kokoro_durations for B clauses in one pass: the clauses' rows back to back (sorted by non-increasing length, stable), the row-wise
+// kernels over all rows, the clause-aware ones through the clause table (kokoro_kernels.h), the recurrences in lock-step.
+extern "C" int tts_hip_kokoro_durations_batch(tts_hip_ctx *c, const uint32_t *tokens, const uint32_t *n, uint32_t B, const char *const *voices, float *lens_out, float *hidden_out) {
+    static const char *const who = "tts_hip_kokoro_durations_batch";
+    if (!c || !c->has_kokoro) return set_err("%s: not a Kokoro context (tts_hip_kokoro_create)", who);
+    if (!c->finalized || !c->weights_present) return set_err("%s: context not finalized", who);
+    if (!tokens || !n || !voices || !lens_out) return set_err("%s: null argument", who);
+    if (B < 1 || B > TTS_HIP_KOKORO_ROWS_MAX) return set_err("%s: %u clauses outside 1..%d", who, B, TTS_HIP_KOKORO_ROWS_MAX);
+    static_assert(TTS_HIP_KOKORO_ROWS_MAX == KK_ROWS_MAX, "the header's clause limit is the kernels'");
+    int R = 0;
+    int coff[KK_ROWS_MAX];   // first row of clause b in the caller's order
+    for (uint32_t b = 0; b < B; b++) {
+        if (n[b] < 3 || n[b] > c->ko.max_ctx) return set_err("%s: clause %u has %u tokens, outside 3..%u", who, b, n[b], c->ko.max_ctx);
+        coff[b] = R;
+        R += (int) n[b];
+    }
+    HIPCHK(hipSetDevice(c->device));
+    KScratch s(c);
+    KRun k(c, s);
+    int64_t ne[4];
+    const float *tok_embd = k.w("albert.token_embd", ne);
+    if (!tok_embd) return set_err("%s: %s", who, k.err.c_str());
+    const int E = (int) ne[0], vocab = (int) ne[1];
+    for (int i = 0; i < R; i++)
+        if (tokens[i] >= (uint32_t) vocab) return set_err("%s: token %u >= vocabulary %d", who, tokens[i], vocab);
+    const float *embd = k.w("albert.embd", ne);
+    const int H = embd ? (int) ne[1] : 0, NH = (int) c->ko.n_attn_heads, hs = NH ? H / NH : 0;
+    const float *ffn_w = k.w("albert.layer.0.ffn", ne);
+    const int F = ffn_w ? (int) ne[1] : 0;
+    int D = 0, S = 0;
+    if (kokoro_dims(c, k, D, S) != 0 || !embd || !ffn_w || NH == 0 || H % NH) return set_err("%s: %s", who, k.err.empty() ? "bad ALBERT shapes" : k.err.c_str());
+    // the working order: non-increasing length, equal lengths in the caller's order
+    int ord[KK_ROWS_MAX];
+    for (uint32_t b = 0; b < B; b++) ord[b] = (int) b;
+    std::stable_sort(ord, ord + B, [&](int x, int y) { return n[x] > n[y]; });
+    KkClause h_cl[KK_ROWS_MAX] = {};
+    std::vector<uint32_t> h_tok((size_t) R);
+    std::vector<int> h_rc((size_t) R);
+    int Rm = 0, Nmax = (int) n[ord[0]];
+    for (int i = 0, at = 0; i < (int) B; i++) {
+        const int b = ord[i], len = (int) n[b];
+        const float *style = kokoro_voice(c, k, voices[b], n[b], S, true);
+        if (!style) return set_err("%s: clause %d: %s", who, b, k.err.c_str());
+        h_cl[i].off = at; h_cl[i].len = len; h_cl[i].style = style;
+        memcpy(h_tok.data() + at, tokens + coff[b], (size_t) len * 4);
+        for (int t = 0; t < len; t++) h_rc[(size_t) at + t] = i;
+        at += len;
+        if (len >= 32) Rm = at;   // the clauses a lone call sends to the matrix-pipe projection (KRun::linear)
+    }
+    const int Wd = D + S;
+    uint32_t *d_tok = (uint32_t *) s.f((size_t) R);
+    int *d_rc = (int *) s.f((size_t) R);
+    KkClause *d_cl = (KkClause *) s.f(sizeof(h_cl) / 4);
+    float *x0 = s.f((size_t) R * E), *x = s.f((size_t) R * H), *q = s.f((size_t) R * H), *kk = s.f((size_t) R * H), *v = s.f((size_t) R * H), *att = s.f((size_t) R * H);
+    float *o = s.f((size_t) R * H), *ff = s.f((size_t) R * F), *cur = s.f((size_t) R * Wd), *ls = s.f((size_t) R * D);
+    float *gamma = s.f((size_t) B * D), *beta = s.f((size_t) B * D), *sty = s.f((size_t) B * S);
+    if (s.failed) return set_err("%s: device scratch allocation failed", who);
+    // the host copies of the three tables live to the end of the call; a failure past this point waits for the stream first
+    auto fail = [&](const char *what) { (void) hipStreamSynchronize(c->stream); return set_err("%s: %s", who, what); };
+    HIPCHK(hipMemcpyAsync(d_tok, h_tok.data(), (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_rc, h_rc.data(), (size_t) R * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_cl, h_cl, sizeof(h_cl), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(kk_albert_embed_rows_kernel, kgrid((int64_t) R * E), dim3(256), 0, c->stream, tok_embd, k.w("albert.position_embd"), k.w("albert.token_type_embd"),
+                       (const uint32_t *) d_tok, R, E, x0, (const KkClause *) d_cl, (const int *) d_rc);
+    k.norm_rows(x0, E, R, E, 1e-12f, k.w("albert.norm"), k.w("albert.norm_bias"), 0, x0, E);
+    k.linear_rows(embd, k.w("albert.embd_bias"), x0, E, R, Rm, E, H, x, H);
+    // the attention form a clause alone would take: the LDS form while its scores fit (the longer clauses come first)
+    auto lds64 = [](int len) { return (size_t) (64 * 65 + 4 * 64 + 4 * len) * 4; };
+    int b64 = (int) B;   // clauses b64 .. B - 1 take kk_albert_attn64_rows_kernel
+    if (hs == 64 && c->kk_attn_lds)
+        for (b64 = 0; b64 < (int) B && lds64(h_cl[b64].len) > 64 * 1024; b64++) {}
+    const std::string L0 = "albert.layer.0.";
+    for (uint32_t r = 0; r < c->ko.n_recurrence; r++) {
+        k.linear_rows(k.w(L0 + "q"), k.w(L0 + "q_bias"), x, H, R, Rm, H, H, q, H);
+        k.linear_rows(k.w(L0 + "k"), k.w(L0 + "k_bias"), x, H, R, Rm, H, H, kk, H);
+        k.linear_rows(k.w(L0 + "v"), k.w(L0 + "v_bias"), x, H, R, Rm, H, H, v, H);
+        if (b64 < (int) B)
+            hipLaunchKernelGGL(kk_albert_attn64_rows_kernel, dim3(NH, (h_cl[b64].len + 3) / 4, B - b64), dim3(256), lds64(h_cl[b64].len), c->stream, (const float *) q, (const float *) kk,
+                               (const float *) v, (const KkClause *) d_cl, b64, H, c->ko.attn_scale, att);
+        if (b64 > 0)
+            hipLaunchKernelGGL(kk_albert_attn_rows_kernel, dim3(NH, Nmax, b64), dim3(64), (size_t) Nmax * 4, c->stream, (const float *) q, (const float *) kk, (const float *) v,
+                               (const KkClause *) d_cl, 0, H, hs, c->ko.attn_scale, att);
+        k.linear_rows(k.w(L0 + "o"), k.w(L0 + "o_bias"), att, H, R, Rm, H, H, o, H);
+        hipLaunchKernelGGL(kk_add_kernel, kgrid((int64_t) R * H), dim3(256), 0, c->stream, (const float *) o, (const float *) x, o, (int64_t) R * H, 1.0f);
+        k.norm_rows(o, H, R, H, 1e-12f, k.w(L0 + "ffn_norm"), k.w(L0 + "ffn_norm_bias"), 0, x, H);
+        k.linear_rows(ffn_w, k.w(L0 + "ffn_bias"), x, H, R, Rm, H, F, ff, F);
+        hipLaunchKernelGGL(kk_gelu_kernel, kgrid((int64_t) R * F), dim3(256), 0, c->stream, ff, (int64_t) R * F);
+        k.linear_rows(k.w(L0 + "ffn_out"), k.w(L0 + "ffn_out_bias"), ff, F, R, Rm, F, H, o, H);
+        hipLaunchKernelGGL(kk_add_kernel, kgrid((int64_t) R * H), dim3(256), 0, c->stream, (const float *) o, (const float *) x, o, (int64_t) R * H, 1.0f);
+        k.norm_rows(o, H, R, H, 1e-12f, k.w(L0 + "attn_norm"), k.w(L0 + "attn_norm_bias"), 0, x, H);
+        if (!k.ok()) return fail(k.err.c_str());
+    }
+    const std::string dp = "duration_predictor.";
+    k.linear_rows(k.w(dp + "encode"), k.w(dp + "encode_bias"), x, H, R, Rm, H, D, cur, Wd);
+    hipLaunchKernelGGL(kk_fill_cols_rows_kernel, kgrid((int64_t) R * S), dim3(256), 0, c->stream, cur, R, Wd, D, (const KkClause *) d_cl, (const int *) d_rc, S);
+    hipLaunchKernelGGL(kk_gather_style_kernel, kgrid((int64_t) B * S), dim3(256), 0, c->stream, (const KkClause *) d_cl, (int) B, S, sty);
+    auto style_proj = [&](const float *W, const float *b, float *y) {   // one row per clause: the wave-per-output kernel whatever B is, as a lone call's single row
+        if (W) hipLaunchKernelGGL(kk_linear_kernel, dim3((unsigned) (((int64_t) B * D + 3) / 4)), dim3(256), 0, c->stream, W, b, (const float *) sty, S, (int) B, S, D, y, D, 0);
+    };
+    for (uint32_t l = 0; l < c->ko.n_dp_layers; l++) {
+        const std::string lb = dp + "layers." + std::to_string(2 * l + 1) + ".";
+        k.bilstm_rows(dp + "layers." + std::to_string(2 * l) + ".lstm", cur, R, Rm, Wd, D / 2, ls, d_cl, h_cl, (int) B);
+        style_proj(k.w(lb + "gamma_weight"), k.w(lb + "gamma_bias"), gamma);
+        style_proj(k.w(lb + "beta_weight"), k.w(lb + "beta_bias"), beta);
+        hipLaunchKernelGGL(kk_norm_rows_clause_kernel, dim3(R), dim3(64), 0, c->stream, (const float *) ls, D, D, 1e-5f, (const float *) gamma, (const float *) beta, (const int *) d_rc,
+                           cur, Wd);   // the style columns of cur stay in place
+        if (!k.ok()) return fail(k.err.c_str());
+    }
+    if (hidden_out)
+        for (int i = 0; i < (int) B; i++)
+            HIPCHK(hipMemcpyAsync(hidden_out + (size_t) coff[ord[i]] * Wd, cur + (size_t) h_cl[i].off * Wd, (size_t) h_cl[i].len * Wd * 4, hipMemcpyDeviceToHost, c->stream));
+    k.bilstm_rows(dp + "duration_lstm", cur, R, Rm, Wd, D / 2, ls, d_cl, h_cl, (int) B);
+    const float *dpw = k.w(dp + "duration_proj", ne);
+    const int ND = dpw ? (int) ne[1] : 0;
+    float *dur = s.f((size_t) R * ND), *lens = s.f((size_t) R);
+    k.linear_rows(dpw, k.w(dp + "duration_proj_bias"), ls, D, R, Rm, D, ND, dur, ND);
+    if (dur && lens) hipLaunchKernelGGL(kk_duration_kernel, kgrid(R, 64), dim3(64), 0, c->stream, (const float *) dur, R, ND, lens);
+    if (!k.ok()) return fail(k.err.c_str());
+    for (int i = 0; i < (int) B; i++)
+        HIPCHK(hipMemcpyAsync(lens_out + coff[ord[i]], lens + h_cl[i].off, (size_t) h_cl[i].len * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return kokoro_check_stuck(c, who);
 }
 
 extern "C" int tts_hip_kokoro_generate(tts_hip_ctx *c, const uint32_t *tokens, uint32_t n, const float *lens, const float *hidden, const char *voice, const float *noise,

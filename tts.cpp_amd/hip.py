@@ -84,7 +84,7 @@ EXPORTS = [
     "tts_hip_upload", "tts_hip_arena_bytes", "tts_hip_finalize", "tts_hip_arena_ptr", "tts_hip_arena_filled",
     "tts_hip_parler_set_text_encoding", "tts_hip_parler_reset", "tts_hip_parler_prefill", "tts_hip_parler_prefill_batch", "tts_hip_parler_step",
     "tts_hip_parler_step_greedy", "tts_hip_parler_generate_greedy", "tts_hip_parler_generate_sampled", "tts_hip_sample_logits",
-    "tts_hip_t5_create", "tts_hip_t5_encode", "tts_hip_t5_output_size", "tts_hip_snac_create", "tts_hip_snac_decode", "tts_hip_orpheus_create", "tts_hip_orpheus_decode", "tts_hip_orpheus_step_batch", "tts_hip_orpheus_generate_batch", "tts_hip_orpheus_generate_greedy", "tts_hip_orpheus_generate_sampled", "tts_hip_orpheus_sample_logits", "tts_hip_dia_create", "tts_hip_dia_encode", "tts_hip_dia_step", "tts_hip_dia_encode_slot", "tts_hip_dia_step_batch", "tts_hip_dia_generate", "tts_hip_kokoro_create", "tts_hip_kokoro_durations", "tts_hip_kokoro_generate", "tts_hip_dac_decode", "tts_hip_dac_decode_batch", "tts_hip_debug_read",
+    "tts_hip_t5_create", "tts_hip_t5_encode", "tts_hip_t5_output_size", "tts_hip_snac_create", "tts_hip_snac_decode", "tts_hip_orpheus_create", "tts_hip_orpheus_decode", "tts_hip_orpheus_step_batch", "tts_hip_orpheus_generate_batch", "tts_hip_orpheus_generate_greedy", "tts_hip_orpheus_generate_sampled", "tts_hip_orpheus_sample_logits", "tts_hip_dia_create", "tts_hip_dia_encode", "tts_hip_dia_step", "tts_hip_dia_encode_slot", "tts_hip_dia_step_batch", "tts_hip_dia_generate", "tts_hip_kokoro_create", "tts_hip_kokoro_durations", "tts_hip_kokoro_durations_batch", "tts_hip_kokoro_generate", "tts_hip_dac_decode", "tts_hip_dac_decode_batch", "tts_hip_debug_read",
     "tts_hip_set_debug", "tts_hip_debug_tile_gemm", "tts_hip_profile", "tts_hip_profile_get", "tts_hip_kclass_name", "tts_hip_stream",
     "tts_hip_synchronize", "tts_hip_dac_arith", "tts_hip_broadcast_weights", "tts_hip_comm_unique_id", "tts_hip_broadcast_weights_rank", "tts_hip_tune",
     "tts_hip_parler_stream_begin", "tts_hip_parler_stream_admit", "tts_hip_parler_stream_run", "tts_hip_parler_stream_collect", "tts_hip_parler_stream_end",
@@ -163,6 +163,7 @@ def load_lib():
     L.tts_hip_kokoro_create.restype = vp
     L.tts_hip_kokoro_create.argtypes = [C.c_int, C.POINTER(KokoroDesc)]
     L.tts_hip_kokoro_durations.argtypes = [vp, u32p, C.c_uint32, C.c_char_p, f32p, f32p]
+    L.tts_hip_kokoro_durations_batch.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(C.c_char_p), f32p, f32p]
     L.tts_hip_kokoro_generate.argtypes = [vp, u32p, C.c_uint32, f32p, f32p, C.c_char_p, f32p, f32p, f32p, f32p]
     L.tts_hip_dia_create.restype = vp
     L.tts_hip_dia_create.argtypes = [C.c_int, C.POINTER(DiaDesc)]
@@ -1359,6 +1360,22 @@ class KokoroEngine:
         fpt = C.POINTER(C.c_float)
         self._chk(self.L.tts_hip_kokoro_durations(self.ctx, ap, a.size, voice.encode(), lens.ctypes.data_as(fpt), hid.ctypes.data_as(fpt)))
         return lens, hid
+
+    def durations_batch(self, tokens, voices):
+        """up to 8 clauses in one pass (tts_hip_kokoro_durations_batch) -> [(lens, hidden), ...] in the order given"""
+        arrs = [np.ascontiguousarray(t, dtype=np.uint32).reshape(-1) for t in tokens]
+        if len(arrs) != len(voices):
+            raise ValueError("durations_batch: one voice per clause")
+        flat, fp = _u32(np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32))
+        n, npt = _u32([a.size for a in arrs])
+        names = (C.c_char_p * max(1, len(voices)))(*[v.encode() for v in voices])
+        width = self.cfg.dp_hidden + self.cfg.style_half
+        lens = np.empty(flat.size, dtype=np.float32)
+        hid = np.empty((flat.size, width), dtype=np.float32)
+        fpt = C.POINTER(C.c_float)
+        self._chk(self.L.tts_hip_kokoro_durations_batch(self.ctx, fp, npt, len(arrs), names, lens.ctypes.data_as(fpt), hid.ctypes.data_as(fpt)))
+        at = np.concatenate([[0], np.cumsum([a.size for a in arrs])]).astype(int)
+        return [(lens[at[b]:at[b + 1]].copy(), hid[at[b]:at[b + 1]].copy()) for b in range(len(arrs))]
 
     def generate(self, tokens, lens, hidden, voice, noise, hsrc_in=None, want_hsrc=False):
         a, ap = _u32(tokens)

@@ -5,6 +5,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <chrono>
 #include <thread>
@@ -170,6 +171,7 @@ kokoro_runner::kokoro_runner(const kokoro_hparams & hp_, single_pass_tokenizer *
         declare_only = lo.declare_only || share_ctx != nullptr;
         if (lo.max_seqs > 0 || getenv("TTS_HIP_MAX_SEQS")) lanes_max = std::min<uint32_t>(tts_load_max_seqs(), 16);   // an explicit 1: one context, as the reference
         if (const char * e = getenv("TTS_KOKORO_LANES")) lanes_max = (uint32_t) std::clamp(atoi(e), 1, 16);
+        if (const char * e = getenv("TTS_KOKORO_ROWS")) rows_max = (uint32_t) std::clamp(atoi(e), 0, TTS_HIP_KOKORO_ROWS_MAX);
     }
     tts_hip_kokoro_desc & d = desc;
     d.struct_size = sizeof(d);
@@ -358,9 +360,32 @@ void kokoro_runner::generate(const char * prompt, tts_response & output, const g
 
 // ---- generate_batch: clauses of n utterances through `lanes_max` contexts on one weight arena -------------------------------------
 
+// the duration groups of generate_batch: the pieces sorted by non-increasing token count (equal counts keep their order), cut into consecutive
+// runs of at most max_per_group, so that a group's members are close in length and the lock-step recurrence wastes few steps
+std::vector<std::vector<size_t>> kokoro_duration_groups(const std::vector<uint32_t> & lengths, size_t max_per_group) {
+    std::vector<size_t> order(lengths.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return lengths[a] > lengths[b]; });
+    max_per_group = std::max<size_t>(1, max_per_group);
+    std::vector<std::vector<size_t>> groups;
+    for (size_t at = 0; at < order.size(); at += max_per_group)
+        groups.emplace_back(order.begin() + (long) at, order.begin() + (long) std::min(order.size(), at + max_per_group));
+    return groups;
+}
+
+// starts[i] = the noise engine's state at clause i's first draw (clause i draws frames[i] * per_frame values); returns the state after the last clause
+uint32_t kokoro_noise_starts(uint32_t state, const std::vector<uint64_t> & frames, uint64_t per_frame, std::vector<uint32_t> & starts) {
+    starts.resize(frames.size());
+    for (size_t i = 0; i < frames.size(); i++) {
+        starts[i] = state;
+        state = minstd0_jump(state, frames[i] * per_frame);
+    }
+    return state;
+}
+
 void kokoro_runner::generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs, const generation_configuration & config) {
     const size_t n = sentences.size();
-    if (n <= 1 || lanes_max <= 1) { tts_generation_runner::generate_batch(sentences, outputs, config); return; }
+    if (n <= 1 || (lanes_max <= 1 && rows_max == 0)) { tts_generation_runner::generate_batch(sentences, outputs, config); return; }   // (one lane still gains from duration groups)
     voice = config.voice.empty() ? std::string("af_heart") : config.voice;
     if (!uploaded_voices.count(voice)) TTS_ABORT("Failed to find Kokoro voice '%s' aborting.\n", voice.c_str());
     if (!phoneme_notice_given && !getenv("TTS_KOKORO_INPUT_IS_PHONEMES")) {
@@ -437,11 +462,82 @@ void kokoro_runner::generate_batch(const std::vector<std::string> & sentences, s
             }
         }
     };
-    std::vector<std::thread> threads;
-    for (size_t li = 1; li < n_lanes; li++) threads.emplace_back(worker, li);
-    worker(0);
-    for (auto & t : threads) t.join();
-    if (failed) TTS_ABORT("%s\n", error.c_str());
+    auto on_lanes = [&](size_t count, const std::function<void(size_t)> & fn) {
+        std::vector<std::thread> threads;
+        for (size_t li = 1; li < count; li++) threads.emplace_back(fn, li);
+        fn(0);
+        for (auto & t : threads) t.join();
+        if (failed) TTS_ABORT("%s\n", error.c_str());
+    };
+    if (rows_max == 0) on_lanes(n_lanes, worker);
+    else {
+        // phase 1: the durations of up to rows_max clauses of similar length per device call; the lanes take groups from a shared counter
+        std::vector<uint32_t> lengths;
+        for (const auto & w : work) lengths.push_back((uint32_t) w.tokens.size());
+        const auto groups = kokoro_duration_groups(lengths, rows_max);
+        const size_t width = duration_hidden + style_half;
+        auto duration_worker = [&](size_t li) {
+            tts_hip_ctx * c = lanes[li];
+            std::vector<uint32_t> ids, ns;
+            std::vector<float>    lens, hidden;
+            std::vector<const char *> voices;
+            for (;;) {
+                const size_t gi = next.fetch_add(1);
+                if (gi >= groups.size() || failed) return;
+                ids.clear(); ns.clear();
+                for (size_t i : groups[gi]) { ids.insert(ids.end(), work[i].tokens.begin(), work[i].tokens.end()); ns.push_back((uint32_t) work[i].tokens.size()); }
+                voices.assign(ns.size(), voice.c_str());
+                lens.resize(ids.size());
+                hidden.resize(ids.size() * width);
+                const double t0 = now();
+                if (tts_hip_kokoro_durations_batch(c, ids.data(), ns.data(), (uint32_t) ns.size(), voices.data(), lens.data(), hidden.data())) {
+                    std::lock_guard<std::mutex> lk(mu);
+                    if (!failed.exchange(true)) error = std::string("tts_hip_kokoro_durations_batch failed: ") + tts_hip_last_error();
+                    return;
+                }
+                if (trace) fprintf(stderr, "kokoro batch: group %zu (%zu clauses, %zu rows) lane %zu  start %.1f  durations %.1f ms\n", gi, ns.size(), ids.size(), li, t0 - t_begin, now() - t0);
+                size_t at = 0;
+                for (size_t i : groups[gi]) {
+                    piece & w = work[i];
+                    const size_t nt = w.tokens.size();
+                    w.lens.assign(lens.begin() + (long) at, lens.begin() + (long) (at + nt));
+                    w.hidden.assign(hidden.begin() + (long) (at * width), hidden.begin() + (long) ((at + nt) * width));
+                    for (float l : w.lens) w.frames += (size_t) l;
+                    at += nt;
+                }
+            }
+        };
+        on_lanes(std::min<size_t>(n_lanes, groups.size()), duration_worker);
+        // every length is known: clause i's stretch of the noise stream starts where clause i - 1's ends
+        std::vector<uint64_t> frames;
+        for (const auto & w : work) frames.push_back(w.frames);
+        std::vector<uint32_t> starts;
+        state = kokoro_noise_starts(state, frames, per_frame, starts);
+        // phase 2: noise draw + generation graph per clause, nobody waits for anybody
+        next = 0;
+        auto generate_worker = [&](size_t li) {
+            tts_hip_ctx * c = lanes[li];
+            std::vector<float> noise;
+            for (;;) {
+                const size_t i = next.fetch_add(1);
+                if (i >= work.size() || failed) return;
+                piece & w = work[i];
+                const double t0 = now();
+                noise.resize(w.frames * per_frame);
+                minstd0_draw_uniform(starts[i], noise.size(), noise.data(), n_noise_threads);
+                w.pcm.resize(w.frames * hp.up_sampling_factor);
+                const double t1 = now();
+                const int rc = tts_hip_kokoro_generate(c, w.tokens.data(), (uint32_t) w.tokens.size(), w.lens.data(), w.hidden.data(), voice.c_str(), noise.data(), w.pcm.data(), nullptr, nullptr);
+                if (trace) fprintf(stderr, "kokoro batch: clause %zu lane %zu  start %.1f  noise %.1f  generate %.1f ms\n", i, li, t0 - t_begin, t1 - t0, now() - t1);
+                if (rc) {
+                    std::lock_guard<std::mutex> lk(mu);
+                    if (!failed.exchange(true)) error = std::string("tts_hip_kokoro_generate failed: ") + tts_hip_last_error();
+                    return;
+                }
+            }
+        };
+        on_lanes(n_lanes, generate_worker);
+    }
     noise_engine.seed(state);                               // as after the same utterances through generate()
     batch_store_.assign(n, {});
     outputs.assign(n, tts_response{});

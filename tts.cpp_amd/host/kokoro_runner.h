@@ -67,7 +67,11 @@ struct kokoro_runner final : tts_generation_runner {
     // follows clause i - 1's (the engine is jumped ahead, x -> a^k x mod m, once the earlier clauses' durations are known).
     void     generate_batch(const std::vector<std::string> & sentences, std::vector<tts_response> & outputs, const generation_configuration & config) override;
     void *   device_context() const override { return ctx; }
-    uint32_t lanes_max = 4;   // tts_load_options::max_seqs / TTS_HIP_MAX_SEQS when given, TTS_KOKORO_LANES; 1: generate_batch = generate in a loop
+    uint32_t lanes_max = 4;   // tts_load_options::max_seqs / TTS_HIP_MAX_SEQS when given, TTS_KOKORO_LANES; 1 with rows_max 0: generate_batch = generate in a loop
+    // TTS_KOKORO_ROWS: clauses per duration pass of generate_batch (tts_hip_kokoro_durations_batch, 1..8): first every clause's durations in groups of
+    // similar length, then the generation graphs with every noise stretch known up front.  0: durations per clause, the lanes wait for their turn.
+    // 8 by the measurement in profiles/kokoro_rows.json: four lanes 1612 audio-s/s against the parent's 1448.
+    uint32_t rows_max = 8;
 
     std::vector<uint32_t> last_prompt_tokens;   // every clause's ids of the last generate, concatenated
     std::vector<float>    last_lengths;
@@ -94,6 +98,9 @@ struct kokoro_runner final : tts_generation_runner {
     void run(const std::vector<uint32_t> & tokens);
 };
 
+// generate_batch's plan for the duration passes and the noise stretches (pure functions, exported for the tests as tts_c_kokoro_*)
+std::vector<std::vector<size_t>> kokoro_duration_groups(const std::vector<uint32_t> & lengths, size_t max_per_group);
+uint32_t kokoro_noise_starts(uint32_t state, const std::vector<uint64_t> & frames, uint64_t per_frame, std::vector<uint32_t> & starts);
 // the state of std::minstd_rand0 after k more draws (x -> 16807^k x mod 2^31 - 1)
 uint32_t minstd0_jump(uint32_t state, uint64_t k);
 // out[0 .. n) = the draws an engine in `state` gives through uniform_real_distribution<float>(0, 1), drawn as `threads` parallel stretches

@@ -505,6 +505,22 @@ extern "C" int tts_c_kokoro_chunks(const char * const * vocab, int n_vocab, cons
 }
 
 extern "C" uint32_t tts_c_minstd0_jump(uint32_t state, uint64_t k) { return minstd0_jump(state, k); }
+extern "C" int tts_c_kokoro_duration_groups(const uint32_t * lengths, int n, int max_per_group, uint32_t * out, int cap) {
+    if (n < 0 || max_per_group < 1 || (n > 0 && !lengths)) { g_c_err = "tts_c_kokoro_duration_groups: bad arguments"; return -1; }
+    std::vector<uint32_t> flat;
+    for (const auto & g : kokoro_duration_groups(std::vector<uint32_t>(lengths, lengths + n), (size_t) max_per_group)) {
+        flat.push_back((uint32_t) g.size());
+        for (size_t i : g) flat.push_back((uint32_t) i);
+    }
+    if (out && (int) flat.size() <= cap) memcpy(out, flat.data(), flat.size() * sizeof(uint32_t));
+    return (int) flat.size();
+}
+extern "C" uint32_t tts_c_kokoro_noise_starts(uint32_t state, const uint64_t * frames, int n, uint64_t per_frame, uint32_t * starts_out) {
+    std::vector<uint32_t> starts;
+    state = kokoro_noise_starts(state, std::vector<uint64_t>(frames, frames + std::max(0, n)), per_frame, starts);
+    if (starts_out && n > 0) memcpy(starts_out, starts.data(), starts.size() * sizeof(uint32_t));
+    return state;
+}
 extern "C" uint32_t tts_c_minstd0_uniform(uint32_t state, uint64_t n, float * out, uint32_t threads) {
     minstd0_draw_uniform(state, (size_t) n, out, threads);
     return minstd0_jump(state, n);

@@ -31,6 +31,7 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_pool_create", "tts_c_pool_set_text_encoder", "tts_c_pool_set_continuous", "tts_c_pool_set_continuous_yield_ms", "tts_c_pool_admitted_in_flight", "tts_c_pool_conditional_prompt", "tts_c_pool_submit", "tts_c_pool_wait", "tts_c_pool_release", "tts_c_pool_stats", "tts_c_pool_load_stats", "tts_c_pool_free", "tts_c_set_load_options", "tts_c_set_load_options_ex", "tts_c_runner_device_context", "tts_c_runner_tokenize",
            "tts_c_quantize_gguf", "tts_c_quantize_decision", "tts_c_quantize_rows",
            "tts_c_dia_tokenize", "tts_c_dia_check_stopping", "tts_c_dia_adjust_output_tokens", "tts_c_single_pass_tokenize", "tts_c_kokoro_chunks", "tts_c_minstd0_jump", "tts_c_minstd0_uniform",
+           "tts_c_kokoro_duration_groups", "tts_c_kokoro_noise_starts",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames", "tts_c_chunk_windows",
            "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs", "tts_c_generate_stream_chunked_configs",
            "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes", "tts_c_runner_stream_capacity"]
@@ -78,6 +79,9 @@ def load_lib():
         L.tts_c_pool_add_voice.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.tts_c_single_pass_tokenize.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]
         L.tts_c_kokoro_chunks.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]
+        L.tts_c_kokoro_duration_groups.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int]
+        L.tts_c_kokoro_noise_starts.restype = C.c_uint32
+        L.tts_c_kokoro_noise_starts.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.POINTER(C.c_uint32)]
         L.tts_c_dia_tokenize.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.tts_c_dia_check_stopping.argtypes = [C.POINTER(C.c_uint32)] + [C.c_uint32] * 5 + [C.POINTER(C.c_int)]
         L.tts_c_dia_adjust_output_tokens.restype = C.c_int64
@@ -366,6 +370,33 @@ def kokoro_chunks(vocab, phonemes, max_ctx, space_token_id=16):
         out.append(flat[i + 1:i + 1 + k].tolist())
         i += 1 + k
     return out
+
+
+def kokoro_duration_groups(lengths, max_per_group):
+    """generate_batch's duration groups (TTS_KOKORO_ROWS): lists of piece indices"""
+    L = load_lib()
+    a = np.ascontiguousarray(lengths, dtype=np.uint32).reshape(-1)
+    ap = a.ctypes.data_as(C.POINTER(C.c_uint32))
+    n = L.tts_c_kokoro_duration_groups(ap, a.size, max_per_group, None, 0)
+    if n < 0:
+        raise RunnerError(L.tts_c_last_error().decode("utf-8", "replace"))
+    flat = np.zeros(max(n, 1), dtype=np.uint32)
+    L.tts_c_kokoro_duration_groups(ap, a.size, max_per_group, flat.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+    out, i = [], 0
+    while i < n:
+        k = int(flat[i])
+        out.append(flat[i + 1:i + 1 + k].tolist())
+        i += 1 + k
+    return out
+
+
+def kokoro_noise_starts(state, frames, per_frame):
+    """-> (the noise engine's state at each piece's first draw, the state after the last piece)"""
+    L = load_lib()
+    f = np.ascontiguousarray(frames, dtype=np.uint64).reshape(-1)
+    starts = np.zeros(max(f.size, 1), dtype=np.uint32)
+    end = L.tts_c_kokoro_noise_starts(state, f.ctypes.data_as(C.POINTER(C.c_uint64)), f.size, per_frame, starts.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return starts[:f.size], int(end)
 
 
 def dia_tokenize(sentence, max_ctx):
