@@ -13,7 +13,7 @@ runs to position 84, then 16 steps of warm-up, then 128 timed steps at positions
 step from a host clock around gen_launch + gen_wait (which ends in a device synchronise; one look-in per 128 steps is inside).  To alternate two trees
 process by process, run both with --reps 1 in turn and join the files: python THIS_FILE --merge OUT.json PART1.json PART2.json ...
 
-profiles/dia_kv_f16_u.json holds a run of this script on a build that also held attn_gqa_wave_ext_f16_kernel<128, 8> ("f16": all eight passes requested at
+profiles/dia_kv_f16_u.json holds a run of this script on a build that also held the fp16 EXT kernel (now attn_gqa_wave_kernel<128, U, true, _Float16>) at U = 8 ("f16": all eight passes requested at
 once, "f16_u4": the four rolling slots that stayed), 4 slots, two processes each, 48 timed steps at positions 100..147 and 2000..2047.
 Every figure is the list of its repetitions; the report prints min / median / max."""
 import argparse

@@ -186,7 +186,7 @@ def run_dia(args, ranks=None):
         "x_real_time_per_gpu": round(U / (step_ms * 1e-3) / 86.13, 2),
         "roofline": {"bound": "hbm", "achieved": round(tot / (step_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(tot / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": _pmc("dia_1_6b_lockstep4_step"),
-                     "kernel": "whole decoder step (18 layers x 12 launches: gemv_stream_kernel, attn_gqa_split_kernel<128> (self) / attn_gqa_wave_kernel<128, 3, EXT> (cross), rms_fold_rows_kernel, llama_rope_kv_kernel, ... + sample_kernel)",
+                     "kernel": "whole decoder step (18 layers x 12 launches: gemv_stream_kernel, attn_gqa_kernel<128, true, float> (self) / attn_gqa_wave_kernel<128, 3, true, float> (cross), rms_fold_rows_kernel, llama_rope_kv_kernel<float>, ... + sample_kernel)",
                      "algorithmic_bytes_per_launch": tot, "note": f"fp16 matrices {w_bytes / 1e9:.3f} GB + {U} x (fp32 cross K/V {ckv_bytes / 1e9:.3f} GB + self-attention K/V at the mean position {skv_bytes / 1e9:.3f} GB) per step"},
     }
     eng.close()
@@ -304,7 +304,7 @@ def run_orpheus(args):
         "snac_share_of_step": round(float(np.mean(tc)) / (float(np.mean(ts)) + float(np.mean(tc))), 4),
         "x_real_time_per_gpu": round(audio_s / elapsed, 2),
         "roofline": {"bound": "hbm", "achieved": round(q4_bytes / step / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(q4_bytes / step / 1e9 / HBM_PEAK_GBS, 4),
-                     "traffic": _pmc("orpheus_3b_q4_0_step"), "kernel": "whole decoder step (28 layers x 6 launches: gemv_q4_qkv_rope_kernel, attn_gqa_wave_kernel<128> + attn_gqa_combine_kernel, gemv_q4_rows_lds_kernel, gemv_q4_gateup_silu_kernel; lm_head over 156 940 logits, arg-max)",
+                     "traffic": _pmc("orpheus_3b_q4_0_step"), "kernel": "whole decoder step (28 layers x 6 launches: gemv_q4_qkv_rope_kernel<4, 2, 2, float>, attn_gqa_wave_kernel<128, 4, false, float> + attn_gqa_combine_kernel, gemv_q4_rows_lds_kernel, gemv_q4_gateup_silu_kernel; lm_head over 156 940 logits, arg-max)",
                      "algorithmic_bytes_per_launch": q4_bytes, "note": "Q4_0 bytes of every matrix one step reads (lm_head included, one embedding row excluded); "
                      "the decoder steps are the dominant part of the timed region (snac_share_of_step is the codec's)"},
     }

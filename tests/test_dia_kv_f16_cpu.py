@@ -1,9 +1,11 @@
 """The fp16 self and cross K/V caches of a Dia context (tts_hip_dia_desc::kv_type), checked without a GPU: the field and its documentation, what the
-libraries and the Python layer expose, and a gfx950 cross-compile of the new cross-attention kernel next to the fp32 kernel it restates.
+libraries and the Python layer expose, and a gfx950 cross-compile of the cross-attention kernel's two instantiations, attn_gqa_wave_kernel<128, U, EXT, KV>
+at KV = _Float16 next to KV = float (U = KVRow<KV>::EXT_SLOTS: 4 and 3).
 
-The register condition is derived, not measured: attn_gqa_wave_ext_f16_kernel keeps a pass in flight in 8 registers where the fp32 EXT kernel needs 16, and
-adds nothing that lives as long; with 4 slots against the fp32 kernel's 3 it holds 32 row registers against 48 — so it may not need more vector registers
-than the fp32 kernel of the same compile, neither may spill, and the static LDS (partials of four waves, the folded query) is the same."""
+The register condition is derived, not measured: the fp16 instantiation keeps a pass in flight in 8 registers where the fp32 one needs 16, and
+adds nothing that lives as long; with 4 slots against 3 it holds 32 row registers against 48 — so it may not need more vector registers
+than the fp32 instantiation of the same compile, neither may spill, and the static LDS (partials of four waves, the folded query) is the same.  Both stay
+within 128 VGPRs + AGPRs, the line of four 256-thread workgroups per CU (512 registers per lane and SIMD / 4) that their slot counts were chosen for."""
 import inspect
 import os
 import re
@@ -25,9 +27,9 @@ TU = """
 #include "{root}/tts.cpp_amd/csrc/gemv_kernels.h"
 #include "{root}/tts.cpp_amd/csrc/dia_kernels.h"
 #define ATTN_ARGS(KV) const float *, int, const uint32_t *, const KV *, const KV *, int, int, float, float *
-template __global__ void attn_gqa_wave_kernel<128, 3, true>(ATTN_ARGS(float), int, const uint32_t *, const uint32_t *, int64_t, QPre);
-template __global__ void attn_gqa_wave_ext_f16_kernel<128, 4>(ATTN_ARGS(_Float16), int, const uint32_t *, const uint32_t *, int64_t, QPre);
-const void *use_clear_f16() {{ return (const void *) dia_stream_clear_f16_kernel; }}   // a static kernel: referenced from host code so that it is emitted
+#define EXT(KV) template __global__ void attn_gqa_wave_kernel<128, KVRow<KV>::EXT_SLOTS, true, KV>(ATTN_ARGS(KV), int, const uint32_t *, const uint32_t *, int64_t, QPre);
+EXT(float) EXT(_Float16)
+template __global__ void dia_stream_clear_kernel<_Float16>(_Float16 *, _Float16 *, uint64_t, int, int64_t, int);
 """
 
 
@@ -96,15 +98,17 @@ def _one(usage, mangled_part):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_ext_f16_kernel_fits_in_the_budget_of_the_fp32_ext_kernel(usage):
-    v32, a32, s32, l32 = _one(usage, "20attn_gqa_wave_kernelILi128ELi3ELb1EE")
-    v16, a16, s16, l16 = _one(usage, "28attn_gqa_wave_ext_f16_kernelILi128ELi4EE")
+    v32, a32, s32, l32 = _one(usage, "20attn_gqa_wave_kernelILi128ELi3ELb1EfE")
+    v16, a16, s16, l16 = _one(usage, "20attn_gqa_wave_kernelILi128ELi4ELb1EDF16_E")
     print(f"fp32 EXT <128, 3>: {v32} VGPRs + {a32} AGPRs, scratch {s32}, LDS {l32};  fp16 EXT <128, 4>: {v16} + {a16}, scratch {s16}, LDS {l16}")
     assert s16 == 0 and s32 == 0
     assert l16 == l32
     assert v16 + a16 <= v32 + a32
+    assert v32 + a32 <= 128      # four workgroups of 256 threads per CU
+    assert v16 + a16 <= 128
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_clear_kernel_compiles_for_gfx950_without_scratch(usage):
-    v, a, scratch, lds = _one(usage, "27dia_stream_clear_f16_kernel")
+    v, a, scratch, lds = _one(usage, "23dia_stream_clear_kernelIDF16_E")
     assert scratch == 0 and lds == 0

@@ -278,7 +278,7 @@ def test_dia_1_6b_layer_shapes():
 def test_dia_cross_attention_in_rolling_passes_matches_the_split_kernel():
     """Round 5: the cross-attention of a Dia-1.6B step (16 heads x 2 rows x 8 slices of 128 text positions) runs as attn_gqa_wave_kernel<128, 3, EXT>:
     keys of a slice interleaved 16 by 16, a running softmax per 16-lane group, eight passes through three register slots, the query's slabs folded
-    and rotated under the first rows.  Another association of the same softmax than attn_gqa_split_kernel (tune("attn_wave") = 0): guided logits
+    and rotated under the first rows.  Another association of the same softmax than attn_gqa_kernel<128, true, KV> (tune("attn_wave") = 0): guided logits
     of three steps agree inside the fp16-matrix bar (2e-3 of the largest logit), and both stay inside the oracle's bar (test_dia_1_6b_layer_shapes runs the default)."""
     model = synth.build_dia(synth.dia_1_6b(enc_layers=1, dec_layers=2, max_gen=32, weight_type=gguf.F16))
     cfg = model.cfg

@@ -1,10 +1,10 @@
 """GPU: the opt-in fp16 self and cross K/V caches of a Dia context (tts_hip_dia_desc::kv_type = TTS_HIP_F16, include/tts_hip.h).
 
-1. the writers: what llama_rope_kv_f16_kernel stores into the cross cache (tts_hip_dia_encode_slot, NH = 0) and into the self cache (dia_forward) is
-   np.float16 of what the fp32 kernel stores, bit for bit, the zero K rows behind the sentence and the V rows there included;
+1. the writers: what llama_rope_kv_kernel<_Float16> stores into the cross cache (tts_hip_dia_encode_slot, NH = 0) and into the self cache (dia_forward) is
+   np.float16 of what llama_rope_kv_kernel<float> stores, bit for bit, the zero K rows behind the sentence and the V rows there included;
 2. re-encoding a slot touches that slot alone (the memset behind the sentence counts elements of the cache's size), and a session's begin clears position 0
-   of a never-encoded slot without reaching the encoded one (dia_stream_clear_f16_kernel);
-3. the readers — attn_gqa_wave_ext_f16_kernel<128, 4> (new), attn_gqa_f16_kernel<128, false / true> — against the float64 softmax . V of what the launch
+   of a never-encoded slot without reaching the encoded one (dia_stream_clear_kernel<_Float16>);
+3. the readers — attn_gqa_wave_kernel<128, 4, true, _Float16> (EXT), attn_gqa_kernel<128, false / true, _Float16> — against the float64 softmax . V of what the launch
    itself read (tests/attn_reference.py), with the scheme, the positions and the bar of test_gpu_llama_attention's Dia cases restated here: BAR =
    min(4 x 1.61e-6, 1e-5) of max|ref|.  The cache rows come back widened exactly, so the cache's rounding is on both sides and the arithmetic between the two
    numbers is fp32 on the values the reference sees: no wider bar is due.  Sharpness as there: removing a boundary key moves the reference by >= 10 x BAR on
@@ -174,7 +174,7 @@ def _args(cfg):
 
 
 def test_session_begin_clears_position_0_of_a_slot_never_encoded():
-    """slot 1 never encoded: dia_stream_clear_f16_kernel zeroes position 0 of its rows (what its parked rows attend over) and nothing of slot 0.  Offsets
+    """slot 1 never encoded: dia_stream_clear_kernel<_Float16> zeroes position 0 of its rows (what its parked rows attend over) and nothing of slot 0.  Offsets
     counted in 4-byte elements would land in slot 0's rows of the next layer."""
     model = _model(gguf.F16)
     cfg = model.cfg
@@ -321,7 +321,7 @@ CASE_IDS = ["ctx256-f16", "ctx256-f32", "ctx384-f32", "ctx320-f32", "ctx1024-f32
 
 @pytest.mark.parametrize("max_ctx,wtype,wave", CASES[:2], ids=CASE_IDS[:2])
 def test_f16_cache_self_attention(max_ctx, wtype, wave):
-    """rows of up to 301 and 71 keys in one launch (row_seq, the slot stride in elements): attn_gqa_f16_kernel<128, false> up to 255 keys, <128, true> + combine from 256"""
+    """rows of up to 301 and 71 keys in one launch (row_seq, the slot stride in elements): attn_gqa_kernel<128, false, _Float16> up to 255 keys, <128, true, _Float16> + combine from 256"""
     self_log, _, failures = _run(max_ctx, wtype, wave)
     by_pos = {e["tag"].split("pos ")[1]: (e["kernel"], e["nz"]) for e in self_log}
     assert by_pos == {"0/0": ("unsplit", 1), "127/70": ("unsplit", 1), "128/70": ("unsplit", 1), "255/70": ("split", 2), "256/70": ("split", 2), "300/70": ("split", 2)}
@@ -332,8 +332,8 @@ def test_f16_cache_self_attention(max_ctx, wtype, wave):
 
 @pytest.mark.parametrize("max_ctx,wtype,wave", CASES, ids=CASE_IDS)
 def test_f16_cache_cross_attention(max_ctx, wtype, wave):
-    """256: attn_gqa_wave_ext_f16_kernel at nz = 2 (F16 matrices: the query folded from its slabs); 384: nz = 3; 1024: nz = 8; 320: 2 x 128 < 320,
-    attn_gqa_f16_kernel<128, true> with the fold and the rope; wave=0: that kernel at 256"""
+    """256: attn_gqa_wave_kernel<128, 4, true, _Float16> at nz = 2 (F16 matrices: the query folded from its slabs); 384: nz = 3; 1024: nz = 8; 320: 2 x 128 < 320,
+    attn_gqa_kernel<128, true, _Float16> with the fold and the rope; wave=0: that kernel at 256"""
     _, cross_log, failures = _run(max_ctx, wtype, wave)
     want = {(256, 1): ("ext", 2), (384, 1): ("ext", 3), (320, 1): ("split", 2), (1024, 1): ("ext", 8), (256, 0): ("split", 2)}[(max_ctx, wave)]
     bad = [f for f in failures if " cross " in f]

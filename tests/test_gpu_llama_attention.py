@@ -1,5 +1,5 @@
-"""GPU: the five attention kernels of the Orpheus / Dia steps (csrc/llama_kernels.h: attn_gqa_kernel, attn_gqa_split_kernel,
-attn_gqa_wave_kernel<128,4>, attn_gqa_wave_kernel<128,3,EXT>, attn_gqa_combine_kernel) past their first batch of 64 keys, their first round of
+"""GPU: the five attention kernels of the Orpheus / Dia steps (csrc/llama_kernels.h: attn_gqa_kernel<128, SPLIT, float> unsplit and split,
+attn_gqa_wave_kernel<128, 4, false, float>, its EXT form attn_gqa_wave_kernel<128, 3, true, float>, attn_gqa_combine_kernel) past their first batch of 64 keys, their first round of
 64 * nz keys and up to the last cache row, against a float64 softmax . V (tests/attn_reference.py) of what the launch itself read: the rotated query,
 the cache rows and the output rows are fetched back from the device (tts_hip_debug_read), so nothing but the attention is between the two numbers.
 
@@ -168,9 +168,9 @@ def _entry(log, p0, n):
 
 @pytest.mark.parametrize("wave", [1, 0])
 def test_orpheus_eager_decode_ascending_through_the_cache(wave):
-    """cases 1 and 2.  wave=1: one-row / 3-row / 20-row calls take attn_gqa_wave_kernel<128,4> + the combine (two full rounds at T = 256, 512, 1024; one key in a
+    """cases 1 and 2.  wave=1: one-row / 3-row / 20-row calls take attn_gqa_wave_kernel<128, 4, false, float> + the combine (two full rounds at T = 256, 512, 1024; one key in a
     third round at 257 and 1025; five slices at 641; the last cache row at 1061; nz = 3 from the partials cap at 20 rows); the pieces — the 100 rows at
-    500 with T = 501..600, every T mod 64 — take the unsplit attn_gqa_kernel.  wave=0: the same calls through attn_gqa_split_kernel."""
+    500 with T = 501..600, every T mod 64 — take the unsplit attn_gqa_kernel<128, false, float>.  wave=0: the same calls through its split form <128, true, float>."""
     log, _, failures = _orpheus_sequence(wave)
     assert len(log) == len(ORPHEUS_CALLS)
     want = "wave" if wave else "split"
@@ -203,7 +203,7 @@ def test_orpheus_eager_decode_logits_match_the_oracle_at_high_positions():
 @pytest.mark.parametrize("split", [8, 3])
 @pytest.mark.parametrize("n_prompt,max_new,T", [(3, 2, 4), (509, 5, 513), (600, 3, 602)])
 def test_orpheus_captured_step(n_prompt, max_new, T, split):
-    """case 3: generate_greedy, then the last replay of the captured step read back (attn_gqa_wave_kernel<128,4> at a split count fixed for every position: 8, or 3 —
+    """case 3: generate_greedy, then the last replay of the captured step read back (attn_gqa_wave_kernel<128, 4, false, float> at a split count fixed for every position: 8, or 3 —
     no power of two).  3 ids: all keys in slice 0, the other slices leave -inf partials for the combine; 509 ids + 4 replays: position 512, at 8 slices a
     single key in round two; 600 ids: a ragged second round.  T comes from the position read back (the step's selection has already advanced it by one)."""
     model, ids = _orpheus_model(), _orpheus_ids()
@@ -221,7 +221,7 @@ def test_orpheus_captured_step(n_prompt, max_new, T, split):
 
 
 def test_orpheus_lockstep_rows_with_their_own_slots():
-    """case 4: four utterances of 2, 70, 333 and 600 prompt ids, one lock-step step: attn_gqa_split_kernel with row_seq and the slot stride, nz = 4 from the
+    """case 4: four utterances of 2, 70, 333 and 600 prompt ids, one lock-step step: attn_gqa_kernel<128, true, float> with row_seq and the slot stride, nz = 4 from the
     longest row; the row with 3 keys has chunks of one key and an empty fourth slice; K / V are read per slot"""
     model = _orpheus_model()
     rng = np.random.default_rng(0x10C)
@@ -335,8 +335,8 @@ DIA_IDS = ["ctx256-f16", "ctx256-f32", "ctx384-f32", "ctx320-f32", "ctx1024-f32"
 
 @pytest.mark.parametrize("max_ctx,wtype,wave", DIA_CASES[:2], ids=DIA_IDS[:2])
 def test_dia_self_attention(max_ctx, wtype, wave):
-    """case 6: rows of 301 and 71 keys in one launch (row_seq, a slot stride); nz = 1 up to 255 keys (attn_gqa_kernel, batches two and three of 64 keys), nz = 2 from 256
-    (attn_gqa_split_kernel + combine: chunks of two full batches at 256, two full batches and one key at 257)"""
+    """case 6: rows of 301 and 71 keys in one launch (row_seq, a slot stride); nz = 1 up to 255 keys (attn_gqa_kernel<128, false, float>, batches two and three of 64 keys), nz = 2 from 256
+    (its split form <128, true, float> + combine: chunks of two full batches at 256, two full batches and one key at 257)"""
     self_log, _, failures = _dia_run(max_ctx, wtype, wave)
     by_pos = {e["tag"].split("pos ")[1]: (e["kernel"], e["nz"]) for e in self_log}
     assert by_pos == {"0/0": ("unsplit", 1), "127/70": ("unsplit", 1), "128/70": ("unsplit", 1), "255/70": ("split", 2), "256/70": ("split", 2), "300/70": ("split", 2)}
@@ -348,8 +348,8 @@ def test_dia_self_attention(max_ctx, wtype, wave):
 @pytest.mark.parametrize("max_ctx,wtype,wave", DIA_CASES, ids=DIA_IDS)
 def test_dia_cross_attention(max_ctx, wtype, wave):
     """case 7: the cross-attention of the same steps over all max_ctx text positions (the K rows beyond the sentence are zero and take part), the query folded from its
-    slabs and rotated by the kernel itself — restated here from the raw slabs; position 0 has no rotation, 300 a large theta.  256: attn_gqa_wave_kernel<128,3,EXT>
-    at nz = 2, all 8 passes; 384: nz = 3; 320: 2 x 128 < 320, attn_gqa_split_kernel with the fold and the rope; 1024: nz = 8; wave=0: the split kernel at 256"""
+    slabs and rotated by the kernel itself — restated here from the raw slabs; position 0 has no rotation, 300 a large theta.  256: attn_gqa_wave_kernel<128, 3, true, float> (EXT)
+    at nz = 2, all 8 passes; 384: nz = 3; 320: 2 x 128 < 320, attn_gqa_kernel<128, true, float> with the fold and the rope; 1024: nz = 8; wave=0: the split kernel at 256"""
     _, cross_log, failures = _dia_run(max_ctx, wtype, wave)
     want = {(256, 1): ("ext", 2), (384, 1): ("ext", 3), (320, 1): ("split", 2), (1024, 1): ("ext", 8), (256, 0): ("split", 2)}[(max_ctx, wave)]
     bad = [f for f in failures if " cross " in f]

@@ -150,7 +150,7 @@ def test_orpheus_3b_shapes_5_to_64_rows_take_the_weight_streaming_integer_gemm(w
 
 
 def test_orpheus_3b_shapes_captured_step_with_split_attention():
-    """The captured greedy step at the 3B widths (Q4_0) cuts the keys of every (row, head) into eight slices (attn_gqa_split_kernel; at these
+    """The captured greedy step at the 3B widths (Q4_0) cuts the keys of every (row, head) into eight slices (attn_gqa_kernel<128, true, KV>; at these
     positions most of them are empty) and attn_gqa_combine_kernel merges them with every slice requested at once (round 4 kept two more places
     for the merge as switches — measured equal, removed in round 5).  A second generation on the same context repeats the first; four slices
     instead of eight give the same ids wherever the oracle's margin allows; every id must be the oracle's arg-max up to the Q8_0

@@ -1,7 +1,7 @@
 """GPU: the opt-in fp16 K/V cache of an Orpheus context (TTS_HIP_FLAG_KV_F16, include/tts_hip.h).
 
-1. the writers: what llama_rope_kv_f16_kernel and gemv_q4_qkv_rope_f16_kernel<4> / <4, 2> store is np.float16 of what the fp32 kernels store, bit for bit;
-2. the readers: attn_gqa_f16_kernel<128, false / true> and attn_gqa_wave_f16_kernel<128, 4> against the float64 softmax . V of what the launch itself read, with
+1. the writers: what llama_rope_kv_kernel<_Float16> and gemv_q4_qkv_rope_kernel<4, 0 / 2, 2, _Float16> store is np.float16 of what their float instantiations store, bit for bit;
+2. the readers: attn_gqa_kernel<128, false / true, _Float16> and attn_gqa_wave_kernel<128, 4, false, _Float16> against the float64 softmax . V of what the launch itself read, with
    the checker, the call tables and the bar of test_gpu_llama_attention (BAR = 6.44e-6 of max|ref|; the cache rows come back widened exactly, so the rounding
    of the cache is on both sides and nothing but the attention lies between the two numbers);
 3. prompt + eight steps against the oracle, which keeps fp32 K/V, at the bar of the fp16-cache extension (1e-2, tests/test_gpu_parler.py);
@@ -66,7 +66,7 @@ def _pair(model, tune=None, **kw):
 
 # ---- 1. the writers ---------------------------------------------------------------------------------------------------------------------
 def test_rope_kv_kernel_stores_the_fp32_rows_rounded_once():
-    """F16 matrices: a 255-row piece and two one-row steps, all through llama_rope_kv_kernel / llama_rope_kv_f16_kernel"""
+    """F16 matrices: a 255-row piece and two one-row steps, all through llama_rope_kv_kernel<float> / <_Float16>"""
     model, ids = _tiny(gguf.F16), ta._orpheus_ids()
     e32, e16 = _pair(model)
     for p0, n in ((0, 255), (255, 1), (256, 1)):
@@ -78,7 +78,7 @@ def test_rope_kv_kernel_stores_the_fp32_rows_rounded_once():
 
 @pytest.mark.parametrize("q4_rms", [1, 0])
 def test_fused_q4_projection_stores_the_fp32_rows_rounded_once(q4_rms):
-    """Q4_0 matrices, calls of 3, 1, 1 and 3 rows: gemv_q4_qkv_rope_kernel<4, 2> (the rms norm in its staging) and <4> (q4_rms off) against their fp16 forms"""
+    """Q4_0 matrices, calls of 3, 1, 1 and 3 rows: gemv_q4_qkv_rope_kernel<4, 2, 2, KV> (the rms norm in its staging) and <4, 0, 2, KV> (q4_rms off), KV = float against _Float16"""
     model, ids = _tiny(gguf.Q4_0), ta._orpheus_ids()
     e32, e16 = _pair(model, tune={"q4_rms": q4_rms})
     for p0, n in ((0, 3), (3, 1), (4, 1), (5, 3)):
@@ -138,8 +138,8 @@ def _sequence(wave):
 
 @pytest.mark.parametrize("wave", [1, 0])
 def test_f16_cache_eager_decode_ascending_through_the_cache(wave):
-    """ORPHEUS_CALLS up to position 1060.  The multi-row pieces take attn_gqa_f16_kernel<128, false>; the one-row, 3-row and 20-row calls take
-    attn_gqa_wave_f16_kernel<128, 4> (wave=1) or attn_gqa_f16_kernel<128, true> (wave=0) at the nz of ONE_ROW_NZ, then attn_gqa_combine_kernel"""
+    """ORPHEUS_CALLS up to position 1060.  The multi-row pieces take attn_gqa_kernel<128, false, _Float16>; the one-row, 3-row and 20-row calls take
+    attn_gqa_wave_kernel<128, 4, false, _Float16> (wave=1) or attn_gqa_kernel<128, true, _Float16> (wave=0) at the nz of ONE_ROW_NZ, then attn_gqa_combine_kernel"""
     log, failures = _sequence(wave)
     assert len(log) == len(ta.ORPHEUS_CALLS)
     want = "wave" if wave else "split"
@@ -155,7 +155,7 @@ def test_f16_cache_eager_decode_ascending_through_the_cache(wave):
 @pytest.mark.parametrize("split", [8, 3])
 @pytest.mark.parametrize("n_prompt,max_new,T", [(3, 2, 4), (509, 5, 513), (600, 3, 602)])
 def test_f16_cache_captured_step(n_prompt, max_new, T, split):
-    """the last replay of the captured step (attn_gqa_wave_f16_kernel<128, 4> at a fixed split count), as test_orpheus_captured_step reads it"""
+    """the last replay of the captured step (attn_gqa_wave_kernel<128, 4, false, _Float16> at a fixed split count), as test_orpheus_captured_step reads it"""
     model, ids = ta._orpheus_model(), ta._orpheus_ids()
     eng = _engine(model)
     eng.tune("attn_split", split)
@@ -170,7 +170,7 @@ def test_f16_cache_captured_step(n_prompt, max_new, T, split):
 
 
 def test_f16_cache_lockstep_rows_with_their_own_slots():
-    """four utterances of 2, 70, 333 and 600 prompt ids, one lock-step step: attn_gqa_f16_kernel<128, true> with row_seq and the slot stride, nz = 4"""
+    """four utterances of 2, 70, 333 and 600 prompt ids, one lock-step step: attn_gqa_kernel<128, true, _Float16> with row_seq and the slot stride, nz = 4"""
     model = ta._orpheus_model()
     rng = np.random.default_rng(0x10C)
     lens = [2, 70, 333, 600]

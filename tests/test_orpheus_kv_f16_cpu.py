@@ -1,8 +1,11 @@
 """The fp16 K/V cache of the Orpheus decoder (TTS_HIP_FLAG_KV_F16), checked without a GPU: the flag's value and documentation, and a gfx950 cross-compile
-of the six fp16 forms whose resource usage is read the way test_isa_budget_cpu.py reads it.
+of the six _Float16 instantiations of the cache's writers and readers (one body per kernel, the element type KV a template parameter) whose resource usage
+is read the way test_isa_budget_cpu.py reads it.
 
 The register condition is derived, not measured: an fp16 reader keeps the same rows in flight as its fp32 counterpart in half the registers and adds
-nothing that lives as long, so it may not need more vector registers; neither form may spill, and the fp16 form's LDS may not be larger."""
+nothing that lives as long, so it may not need more vector registers; neither form may spill, and the fp16 form's LDS may not be larger.  Every reader,
+fp32 or fp16, stays within 128 VGPRs + AGPRs: a workgroup of 256 threads is one wave per SIMD, a SIMD has 512 registers per lane, and the kernels'
+request depths were chosen for four workgroups per CU (512 / 4)."""
 import os
 import re
 import shutil
@@ -22,15 +25,13 @@ TU = """
 #include <cmath>
 #include "{root}/tts.cpp_amd/csrc/gemv_kernels.h"
 #define ATTN_ARGS(KV) const float *, int, const uint32_t *, const KV *, const KV *, int, int, float, float *
-template __global__ void attn_gqa_kernel<128>(ATTN_ARGS(float), const uint32_t *, const uint32_t *, const uint32_t *, int64_t, QPre, int8_t *, float *);
-template __global__ void attn_gqa_split_kernel<128>(ATTN_ARGS(float), const uint32_t *, const uint32_t *, const uint32_t *, int64_t, QPre);
-template __global__ void attn_gqa_wave_kernel<128, 4>(ATTN_ARGS(float), int, const uint32_t *, const uint32_t *, int64_t, QPre);
-template __global__ void attn_gqa_f16_kernel<128, false>(ATTN_ARGS(_Float16), const uint32_t *, const uint32_t *, const uint32_t *, int64_t, QPre, int8_t *, float *);
-template __global__ void attn_gqa_f16_kernel<128, true>(ATTN_ARGS(_Float16), const uint32_t *, const uint32_t *, const uint32_t *, int64_t, QPre, int8_t *, float *);
-template __global__ void attn_gqa_wave_f16_kernel<128, 4>(ATTN_ARGS(_Float16), int);
-template __global__ void gemv_q4_qkv_rope_f16_kernel<4, 0, 2>(QGemmArgs, const uint8_t *, RopeEpiF16, RmsSrc);
-template __global__ void gemv_q4_qkv_rope_f16_kernel<4, 2, 2>(QGemmArgs, const uint8_t *, RopeEpiF16, RmsSrc);
-const void *use_rope_f16() {{ return (const void *) llama_rope_kv_f16_kernel; }}   // a static kernel: referenced from host code so that it is emitted
+#define GQA(SPLIT, KV) template __global__ void attn_gqa_kernel<128, SPLIT, KV>(ATTN_ARGS(KV), const uint32_t *, const uint32_t *, const uint32_t *, int64_t, QPre, int8_t *, float *);
+#define WAVE(KV) template __global__ void attn_gqa_wave_kernel<128, 4, false, KV>(ATTN_ARGS(KV), int, const uint32_t *, const uint32_t *, int64_t, QPre);
+GQA(false, float) GQA(true, float) WAVE(float)
+GQA(false, _Float16) GQA(true, _Float16) WAVE(_Float16)
+template __global__ void gemv_q4_qkv_rope_kernel<4, 0, 2, _Float16>(QGemmArgs, const uint8_t *, RopeEpi<_Float16>, RmsSrc);
+template __global__ void gemv_q4_qkv_rope_kernel<4, 2, 2, _Float16>(QGemmArgs, const uint8_t *, RopeEpi<_Float16>, RmsSrc);
+template __global__ void llama_rope_kv_kernel<_Float16>(float *, const uint32_t *, const float *, float, int, int, int, _Float16 *, _Float16 *, const uint32_t *, int64_t, int, int64_t);
 """
 
 
@@ -74,9 +75,9 @@ def _one(usage, mangled_part):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("f32,f16", [("15attn_gqa_kernelILi128EE", "19attn_gqa_f16_kernelILi128ELb0EE"),
-                                     ("21attn_gqa_split_kernelILi128EE", "19attn_gqa_f16_kernelILi128ELb1EE"),
-                                     ("20attn_gqa_wave_kernelILi128ELi4ELb0EE", "24attn_gqa_wave_f16_kernelILi128ELi4EE")],
+@pytest.mark.parametrize("f32,f16", [("15attn_gqa_kernelILi128ELb0EfE", "15attn_gqa_kernelILi128ELb0EDF16_E"),
+                                     ("15attn_gqa_kernelILi128ELb1EfE", "15attn_gqa_kernelILi128ELb1EDF16_E"),
+                                     ("20attn_gqa_wave_kernelILi128ELi4ELb0EfE", "20attn_gqa_wave_kernelILi128ELi4ELb0EDF16_E")],
                          ids=["unsplit", "split", "wave"])
 def test_f16_readers_fit_in_the_budget_of_their_fp32_counterparts(usage, f32, f16):
     (v32, a32, s32, l32), (v16, a16, s16, l16) = _one(usage, f32), _one(usage, f16)
@@ -84,11 +85,13 @@ def test_f16_readers_fit_in_the_budget_of_their_fp32_counterparts(usage, f32, f1
     assert s16 == 0 and s32 == 0
     assert v16 + a16 <= v32 + a32
     assert l16 <= l32
+    assert v32 + a32 <= 128, f32      # four workgroups of 256 threads per CU
+    assert v16 + a16 <= 128, f16
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_f16_writers_compile_for_gfx950_without_scratch(usage):
-    for part in ("27gemv_q4_qkv_rope_f16_kernelILi4ELi0ELi2EE", "27gemv_q4_qkv_rope_f16_kernelILi4ELi2ELi2EE", "24llama_rope_kv_f16_kernel"):
+    for part in ("23gemv_q4_qkv_rope_kernelILi4ELi0ELi2EDF16_E", "23gemv_q4_qkv_rope_kernelILi4ELi2ELi2EDF16_E", "20llama_rope_kv_kernelIDF16_E"):
         v, a, scratch, _ = _one(usage, part)
         print(f"{part}: {v} VGPRs + {a} AGPRs, scratch {scratch}")
         assert scratch == 0, part

@@ -214,22 +214,15 @@ static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitAr
     }
 }
 
-// cross K/V [L][rows][S][A]: position 0 of rows 2u, 2u+1 of the flagged slots.  grid (ceil(A / 256), 2 * n_slots, L)
-static __global__ __launch_bounds__(256) void dia_stream_clear_kernel(float *ck, float *cv, uint64_t clear, int rows, int64_t S, int A) {
+// cross K/V [L][rows][S][A] of KV = float or _Float16 elements (tts_hip_dia_desc::kv_type): position 0 of rows 2u, 2u+1 of the flagged slots.
+// grid (ceil(A / 256), 2 * n_slots, L)
+template <typename KV>
+__global__ __launch_bounds__(256) void dia_stream_clear_kernel(KV *ck, KV *cv, uint64_t clear, int rows, int64_t S, int A) {
     const int e = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, l = blockIdx.z;   // clear: bit u = slot u (a context has at most 64)
     if (e >= A || !((clear >> (r >> 1)) & 1)) return;
     const int64_t at = ((int64_t) l * rows + r) * S * A + e;
-    ck[at] = 0.0f;
-    cv[at] = 0.0f;
-}
-
-// the same over the fp16 caches (tts_hip_dia_desc::kv_type = TTS_HIP_F16): the offsets count 2-byte elements
-static __global__ __launch_bounds__(256) void dia_stream_clear_f16_kernel(_Float16 *ck, _Float16 *cv, uint64_t clear, int rows, int64_t S, int A) {
-    const int e = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, l = blockIdx.z;
-    if (e >= A || !((clear >> (r >> 1)) & 1)) return;
-    const int64_t at = ((int64_t) l * rows + r) * S * A + e;
-    ck[at] = (_Float16) 0.0f;
-    cv[at] = (_Float16) 0.0f;
+    ck[at] = (KV) 0.0f;
+    cv[at] = (KV) 0.0f;
 }
 
 struct DiaDropArgs {

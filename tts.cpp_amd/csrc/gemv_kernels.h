@@ -407,15 +407,18 @@ __device__ __forceinline__ void stage_rms_q8(RmsRow &first, const RmsSrc &rs, in
     }
 }
 
+// KV: the cache element type (llama_kernels.h).  Over an fp16 cache lane 0 rounds the rotated key and the value once, to nearest-even, as it stores them
+// (q stays fp32).
+template <typename KV>
 struct RopeEpi {
     const uint32_t *pos;   // [R]
     const float *ff;       // [64] frequency factors or NULL
     float theta_scale;
     int NH, NKV;
-    float *kcache, *vcache;   // this layer: [n_ctx][NKV * 128]
+    KV *kcache, *vcache;   // this layer: [n_ctx][NKV * 128]
 };
-template <int NR, int QSRC = 0, int NP = 2>
-__global__ __launch_bounds__(256) void gemv_q4_qkv_rope_kernel(QGemmArgs qa, const uint8_t *w4, RopeEpi re, RmsSrc rs = RmsSrc{}) {
+template <int NR, int QSRC, int NP, typename KV>
+__global__ __launch_bounds__(256) void gemv_q4_qkv_rope_kernel(QGemmArgs qa, const uint8_t *w4, RopeEpi<KV> re, RmsSrc rs = RmsSrc{}) {
     extern __shared__ __attribute__((aligned(16))) char gq_sm[];
     const GemmArgs &a = qa.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -480,99 +483,12 @@ __global__ __launch_bounds__(256) void gemv_q4_qkv_rope_kernel(QGemmArgs qa, con
                         float *o = a.out + (int64_t) r * a.ldo + nf[0];
                         o[0] = y0; o[64] = y1;
                     } else {
-                        float *kc = re.kcache + (int64_t) ps[r] * kvH + (head - re.NH) * 128 + i;
-                        kc[0] = y0; kc[64] = y1;
+                        KV *kc = re.kcache + (int64_t) ps[r] * kvH + (head - re.NH) * 128 + i;
+                        kc[0] = (KV) y0; kc[64] = (KV) y1;
                     }
                 } else {
-                    float *vd = re.vcache + (int64_t) ps[r] * kvH + (head - re.NH - re.NKV) * 128 + i;
-                    vd[0] = x0; vd[64] = x1;
-                }
-            }
-        }
-    }
-}
-
-// gemv_q4_qkv_rope_kernel over an fp16 cache (TTS_HIP_FLAG_KV_F16): the same staging, dot products and rotation; lane 0 rounds the rotated key and the
-// value once, to nearest-even, as it stores them (q stays fp32).  A kernel of its own, so that the fp32 kernel above is the code it was before the option.
-struct RopeEpiF16 {
-    const uint32_t *pos;   // [R]
-    const float *ff;       // [64] frequency factors or NULL
-    float theta_scale;
-    int NH, NKV;
-    _Float16 *kcache, *vcache;   // this layer: [n_ctx][NKV * 128]
-};
-template <int NR, int QSRC = 0, int NP = 2>
-__global__ __launch_bounds__(256) void gemv_q4_qkv_rope_f16_kernel(QGemmArgs qa, const uint8_t *w4, RopeEpiF16 re, RmsSrc rs = RmsSrc{}) {
-    extern __shared__ __attribute__((aligned(16))) char gq_sm[];
-    const GemmArgs &a = qa.g;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, nb = K >> 5, R = a.R;
-    // rotation pair p = features i and i + 64 of one head
-    const int p = (int) blockIdx.x * 4 + wave;
-    const bool active = p * 2 < a.N;
-    const int pc = active ? p : 0;
-    const int head = pc >> 6, i = pc & 63;
-    const int nf[2] = {head * 128 + i, head * 128 + i + 64};
-    // requests in the order their consumers run (vmcnt retires in issue order, see gemv_q4_rows_lds_kernel): the staging inputs and what the
-    // epilogue needs (positions, frequency factor: they were a round trip of their own after the wave sums) first, the weights behind them
-    RmsRow row;
-    StageQ8 s8;
-    if (QSRC == 2) rms_row_load(row, rs, 0, K, tid);
-    else stage_q8_load(s8, qa, R, K, nb, tid);
-    uint32_t ps[NR];
-#pragma unroll
-    for (int r = 0; r < NR; r++) ps[r] = re.pos[min(r, R - 1)];
-    const float ffi = re.ff ? re.ff[i] : 1.0f;
-    __builtin_amdgcn_sched_barrier(0);
-    Q4Frag<2, NP> fr;
-    q4_frag_load<2, NP>(fr, w4, qa.wd, nf, K, nb, 0, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    int8_t *sx = (int8_t *) gq_sm;
-    float *sd = (float *) (gq_sm + (size_t) R * K);
-    if (QSRC == 2) stage_rms_q8(row, rs, R, K, sx, sd, sd + (size_t) R * nb);
-    else stage_q8_store(s8, qa, R, K, nb, tid, sx, sd);
-    // the rotation of this wave's pair (llama_rope_kv_kernel's arithmetic: iterated theta, cosf / sinf), computed while the weights are in flight
-    float cs[NR], sn[NR];
-    if (head < re.NH + re.NKV) {
-#pragma unroll
-        for (int r = 0; r < NR; r++) {
-            if (r < R) {
-                float theta = (float) ps[r];
-                for (int j = 0; j < i; j++) theta *= re.theta_scale;
-                const float ang = theta / ffi;
-                cs[r] = cosf(ang); sn[r] = sinf(ang);
-            }
-        }
-    }
-    float acc[2][NR];
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-        for (int r = 0; r < NR; r++) acc[f][r] = 0.0f;
-    q4_frag_dot<2, NP, NR>(fr, sx, sd, R, K, nb, 0, lane, acc);
-    for (int b0 = 64 * NP; b0 < nb; b0 += 64 * NP) {
-        q4_frag_load<2, NP>(fr, w4, qa.wd, nf, K, nb, b0, lane);
-        q4_frag_dot<2, NP, NR>(fr, sx, sd, R, K, nb, b0, lane, acc);
-    }
-    if (!active) return;
-    const int kvH = re.NKV * 128;
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-        if (r < R) {
-            const float x0 = wave_sum(acc[0][r]), x1 = wave_sum(acc[1][r]);
-            if (lane == 0) {
-                if (head < re.NH + re.NKV) {
-                    const float y0 = x0 * cs[r] - x1 * sn[r], y1 = x0 * sn[r] + x1 * cs[r];
-                    if (head < re.NH) {
-                        float *o = a.out + (int64_t) r * a.ldo + nf[0];
-                        o[0] = y0; o[64] = y1;
-                    } else {
-                        _Float16 *kc = re.kcache + (int64_t) ps[r] * kvH + (head - re.NH) * 128 + i;
-                        kc[0] = (_Float16) y0; kc[64] = (_Float16) y1;
-                    }
-                } else {
-                    _Float16 *vd = re.vcache + (int64_t) ps[r] * kvH + (head - re.NH - re.NKV) * 128 + i;
-                    vd[0] = (_Float16) x0; vd[64] = (_Float16) x1;
+                    KV *vd = re.vcache + (int64_t) ps[r] * kvH + (head - re.NH - re.NKV) * 128 + i;
+                    vd[0] = (KV) x0; vd[64] = (KV) x1;
                 }
             }
         }

@@ -5,9 +5,9 @@
 //                          the preceding down_proj into the residual stream, ggml_add :283)
 //   llama_rope_kv_kernel   ggml_rope_ext(NEOX, frequency factors) on q and k, K/V cache append :186-221,248-251
 //   attn_gqa_kernel        mul_mat(k, q) -> soft_max_ext(causal, 1/sqrt(d)) -> mul_mat(kq, v), kv head = q head / rep :228-259
-//   *_f16_kernel           the writers and readers of the cache over fp16 K/V (TTS_HIP_FLAG_KV_F16, extension): llama_rope_kv_f16_kernel,
-//                          attn_gqa_f16_kernel<HD, SPLIT>, attn_gqa_wave_f16_kernel, and for Dia's fp16 caches (tts_hip_dia_desc::kv_type)
-//                          attn_gqa_wave_ext_f16_kernel; the fp32 kernels are untouched by the option
+//   KV                     the cache element type, float or _Float16 (extension: TTS_HIP_FLAG_KV_F16 for Orpheus, tts_hip_dia_desc::kv_type for Dia), is a
+//                          template parameter of the cache's writer and readers: llama_rope_kv_kernel<KV>, attn_gqa_kernel<HD, SPLIT, KV>,
+//                          attn_gqa_wave_kernel<HD, U, EXT, KV>.  KVRow<KV> holds what depends on it (row vector, loads, widening, EXT slot count)
 //   silu_mul_kernel        silu(gate x) * (up x) :279
 //   argmax_parts/fold      sampler::max over the 156 940-logit vocabulary, two stages
 #pragma once
@@ -219,11 +219,14 @@ static __global__ __launch_bounds__(256) void rms_fold_rows_q8t_kernel(float *x,
 // theta walks pos, pos*s, (pos*s)*s, ... in fp32 exactly like ggml_rope_cache_init (theta *= theta_scale), theta_scale =
 // powf(base, -2/HD) from the host; angle = theta / freq_factor[i]; NEOX pairing (i, i + HD/2).  The k-head waves write the
 // rotated key into the cache and copy their head's slice of v next to it.
-// row_seq (optional): row r appends to the cache of sequence row_seq[r], seq_stride floats apart (Dia's two streams).
+// row_seq (optional): row r appends to the cache of sequence row_seq[r], seq_stride cache elements apart (Dia's two streams).
 // n_parts > 1: qkv holds n_parts fp32 slabs (part_stride floats apart, K slices of the projection written by gemv_stream_kernel); they are
 // summed in slab order on the way in and the rotated q lands in slab 0, where the attention kernels read it.
-static __global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, const uint32_t *pos, const float *ff, float theta_scale, int NH, int NKV, int HD,
-                                                           float *kcache, float *vcache, const uint32_t *row_seq, int64_t seq_stride, int n_parts = 1,
+// KV = _Float16 (an fp16 cache): the slab folds, theta chain and rotation stay fp32; the rotated key and the value are rounded once, to nearest-even, as
+// they are stored (q stays fp32 in slab 0).
+template <typename KV>
+__global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, const uint32_t *pos, const float *ff, float theta_scale, int NH, int NKV, int HD,
+                                                           KV *kcache, KV *vcache, const uint32_t *row_seq, int64_t seq_stride, int n_parts = 1,
                                                            int64_t part_stride = 0) {
     const int r = blockIdx.x, h = blockIdx.y;
     if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
@@ -267,8 +270,8 @@ static __global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, co
         const float y0 = x0 * cs - x1 * sn, y1 = x0 * sn + x1 * cs;
         if (h < NH) { v[i] = y0; v[i + half] = y1; }
         else {
-            float *kc = kcache + (int64_t) p * kvH + (h - NH) * HD;
-            kc[i] = y0; kc[i + half] = y1;
+            KV *kc = kcache + (int64_t) p * kvH + (h - NH) * HD;
+            kc[i] = (KV) y0; kc[i + half] = (KV) y1;
         }
     };
     {   // the wave's first pair: its loads are in flight while the angle is computed
@@ -286,11 +289,11 @@ static __global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, co
         rotate(i, x0, x1, cs, sn);
     }
     if (kw) {
-        float *vdst = vcache + (int64_t) p * kvH + (h - NH) * HD;
+        KV *vdst = vcache + (int64_t) p * kvH + (h - NH) * HD;
         if (HD <= 128) {
             fold2(vsrc, vi0, vi1, vx0, vx1, vt0, vt1);
-            if ((int) threadIdx.x < HD) vdst[threadIdx.x] = vx0;
-            if ((int) threadIdx.x + 64 < HD) vdst[threadIdx.x + 64] = vx1;
+            if ((int) threadIdx.x < HD) vdst[threadIdx.x] = (KV) vx0;
+            if ((int) threadIdx.x + 64 < HD) vdst[threadIdx.x + 64] = (KV) vx1;
         } else {
             for (int i = threadIdx.x; i < HD; i += 64) {
                 float t = vsrc[i], tp[7];
@@ -300,91 +303,7 @@ static __global__ __launch_bounds__(64) void llama_rope_kv_kernel(float *qkv, co
                 for (int q = 1; q < 8; q++)
                     if (q < n_parts) t += tp[q - 1];
                 for (int q = 8; q < n_parts; q++) t += vsrc[q * part_stride + i];
-                vdst[i] = t;
-            }
-        }
-    }
-}
-// llama_rope_kv_kernel appending to an fp16 cache (TTS_HIP_FLAG_KV_F16, Orpheus contexts): the same slab folds, theta chain and rotation in fp32; the rotated key
-// and the value are rounded once, to nearest-even, as they are stored (q stays fp32 in slab 0).  A kernel of its own, so that the fp32 kernel above — Dia's
-// too — is the code it was before the option.  seq_stride counts cache elements.
-static __global__ __launch_bounds__(64) void llama_rope_kv_f16_kernel(float *qkv, const uint32_t *pos, const float *ff, float theta_scale, int NH, int NKV, int HD,
-                                                               _Float16 *kcache, _Float16 *vcache, const uint32_t *row_seq, int64_t seq_stride, int n_parts = 1,
-                                                               int64_t part_stride = 0) {
-    const int r = blockIdx.x, h = blockIdx.y;
-    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
-    const int half = HD >> 1;
-    const int ld = (NH + 2 * NKV) * HD, kvH = NKV * HD;
-    float *row = qkv + (int64_t) r * ld;
-    float *v = row + (int64_t) h * HD;      // heads NH.. are the k heads (they follow q in the row)
-    const bool kw = h >= NH;
-    const float *vsrc = row + (int64_t) (NH + NKV) * HD + (int64_t) (h - NH) * HD;
-    auto slabs2 = [&](const float *b, int i, int j, float &a0, float &a1, float (&t0)[7], float (&t1)[7]) __attribute__((always_inline)) {
-        a0 = b[i]; a1 = b[j];
-#pragma unroll
-        for (int q = 1; q < 8; q++) {   // straight-line, as in llama_rope_kv_kernel
-            const int64_t qo = (int64_t) min(q, n_parts - 1) * part_stride;
-            t0[q - 1] = b[qo + i]; t1[q - 1] = b[qo + j];
-        }
-    };
-    auto fold2 = [&](const float *b, int i, int j, float &a0, float &a1, const float (&t0)[7], const float (&t1)[7]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 1; q < 8; q++)
-            if (q < n_parts) { a0 += t0[q - 1]; a1 += t1[q - 1]; }
-        for (int q = 8; q < n_parts; q++) { a0 += b[q * part_stride + i]; a1 += b[q * part_stride + j]; }
-    };
-    const uint32_t p = pos[r];   // first in the queue: the theta chain needs nothing else
-    const int i0 = min((int) threadIdx.x, half - 1);
-    const float ff0 = ff ? ff[i0] : 1.0f;
-    float fx0, fx1, ft0[7], ft1[7], vx0 = 0.0f, vx1 = 0.0f, vt0[7], vt1[7];
-    slabs2(v, i0, i0 + half, fx0, fx1, ft0, ft1);
-    const int vi0 = min((int) threadIdx.x, HD - 1), vi1 = min((int) threadIdx.x + 64, HD - 1);
-    if (kw) slabs2(vsrc, vi0, vi1, vx0, vx1, vt0, vt1);
-    __builtin_amdgcn_sched_barrier(0);
-    auto angle = [&](int i, float fi, float &cs, float &sn) __attribute__((always_inline)) {
-        float theta = (float) p;
-        for (int j = 0; j < i; j++) theta *= theta_scale;
-        const float ang = theta / fi;
-        cs = cosf(ang); sn = sinf(ang);
-    };
-    auto rotate = [&](int i, float x0, float x1, float cs, float sn) __attribute__((always_inline)) {
-        const float y0 = x0 * cs - x1 * sn, y1 = x0 * sn + x1 * cs;
-        if (h < NH) { v[i] = y0; v[i + half] = y1; }
-        else {
-            _Float16 *kc = kcache + (int64_t) p * kvH + (h - NH) * HD;
-            kc[i] = (_Float16) y0; kc[i + half] = (_Float16) y1;
-        }
-    };
-    {   // the wave's first pair: its loads are in flight while the angle is computed
-        float cs, sn;
-        angle(i0, ff0, cs, sn);
-        __builtin_amdgcn_sched_barrier(0);
-        fold2(v, i0, i0 + half, fx0, fx1, ft0, ft1);
-        if ((int) threadIdx.x < half) rotate(i0, fx0, fx1, cs, sn);
-    }
-    for (int i = threadIdx.x + 64; i < half; i += 64) {   // HD > 128: the later pairs
-        float cs, sn, x0, x1, t0[7], t1[7];
-        slabs2(v, i, i + half, x0, x1, t0, t1);
-        angle(i, ff ? ff[i] : 1.0f, cs, sn);
-        fold2(v, i, i + half, x0, x1, t0, t1);
-        rotate(i, x0, x1, cs, sn);
-    }
-    if (kw) {
-        _Float16 *vdst = vcache + (int64_t) p * kvH + (h - NH) * HD;
-        if (HD <= 128) {
-            fold2(vsrc, vi0, vi1, vx0, vx1, vt0, vt1);
-            if ((int) threadIdx.x < HD) vdst[threadIdx.x] = (_Float16) vx0;
-            if ((int) threadIdx.x + 64 < HD) vdst[threadIdx.x + 64] = (_Float16) vx1;
-        } else {
-            for (int i = threadIdx.x; i < HD; i += 64) {
-                float t = vsrc[i], tp[7];
-#pragma unroll
-                for (int q = 1; q < 8; q++) tp[q - 1] = vsrc[(int64_t) min(q, n_parts - 1) * part_stride + i];
-#pragma unroll
-                for (int q = 1; q < 8; q++)
-                    if (q < n_parts) t += tp[q - 1];
-                for (int q = 8; q < n_parts; q++) t += vsrc[q * part_stride + i];
-                vdst[i] = (_Float16) t;
+                vdst[i] = (KV) t;
             }
         }
     }
@@ -448,53 +367,82 @@ __device__ __forceinline__ void attn_q_finish(float *qs, const QRaw &qr, const f
 // instead of one per 16 (scores) / 8 (P.V) keys: a 40-key slice of a split took 3 + 5 round trips (15-18 us per launch at the Orpheus-3B shapes,
 // profiles/r04/kernel_stats_orpheus_baseline.csv).  Key -> lane group and the order of every sum are the ones of round 3 (key j: group j % 16 of
 // the score pass, group j % 8 of the P.V pass, keys ascending inside a group; row16_sum reproduces the xor butterfly), so results are unchanged.
-template <int HD>
-__device__ __forceinline__ void attn_v_batch(float4 (&v)[8], const float *vbase, int kvH, int T, int j0, int tid) {
+//
+// The cache element type KV is float or _Float16; KVRow<KV> holds everything that depends on it.  Over an fp16 cache a key row of one kv head is 256
+// contiguous bytes instead of 512; lane -> dims, key -> lane group and the order of every sum are the same for both types, applied to the rows widened
+// to fp32 (exact): a lane's 4-dim pieces are 8-byte loads, kept as fp16 while they are in flight — the rows in flight take half the registers — and
+// widened where they are consumed.  Query, scores, softmax, accumulators and the partials are fp32 either way.
+typedef _Float16 half4v __attribute__((ext_vector_type(4)));
+template <typename KV> struct KVRow;
+template <> struct KVRow<float> {
+    typedef float4 vec4;   // 4 consecutive elements of a row
+    // rolling register slots of attn_gqa_wave_kernel's EXT form, measured on Dia's cross-attention (134 MB per launch; a pure read of the same bytes: 23 us,
+    // profiles/r05/stride_read_bench_call19.txt): all eight passes requested at once (198 registers, two workgroups per CU) 30.3 us, four slots (130
+    // registers, three per CU) 27.7, three slots (112, four per CU) 26.9, the split kernel's three phases 28.1-28.9
+    // (profiles/r05/dia_cross_attention_forms.txt, dia_step_kernels_call21.txt).
+    static constexpr int EXT_SLOTS = 3;
+    static __device__ __forceinline__ vec4 load(const void *a) { return *(const float4 *) a; }
+    static __device__ __forceinline__ vec4 load_nt(const void *a) { return __builtin_bit_cast(float4, __builtin_nontemporal_load((const float4v *) a)); }
+    static __device__ __forceinline__ const float4 &widen(const vec4 &v) { return v; }   // the identity, without a copy (attn_gqa_wave_kernel's consume)
+};
+template <> struct KVRow<_Float16> {
+    typedef half4v vec4;
+    // a pass costs 8 registers instead of 16.  Measured on the Dia-1.6B step at 8 rows (profiles/dia_kv_f16_u.json; fp32 cache 1.735 / 2.086 ms at positions
+    // 100 / 2000): 4 slots (98 registers, four workgroups per CU, under the fp32 form's 112) 1.596 / 1.858 ms, all eight passes requested at once (132
+    // registers, three workgroups per CU) 1.648 / 1.919.  The slot count only moves requests, never a sum: the result bits do not depend on it.
+    static constexpr int EXT_SLOTS = 4;
+    static __device__ __forceinline__ vec4 load(const void *a) { return *(const half4v *) a; }
+    static __device__ __forceinline__ vec4 load_nt(const void *a) { return __builtin_nontemporal_load((const half4v *) a); }
+    static __device__ __forceinline__ float4 widen(vec4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); }
+};
+
+template <int HD, typename KV>
+__device__ __forceinline__ void attn_v_batch(typename KVRow<KV>::vec4 (&v)[8], const KV *vbase, int kvH, int T, int j0, int tid) {
     const int grp = tid >> 5, e4 = tid & 31;
 #pragma unroll
     for (int u = 0; u < 8; u++) {
         const int j = max(0, min(j0 + grp + 8 * u, T - 1));
-        v[u] = *(const float4 *) (vbase + (int64_t) j * kvH + e4 * 4);
+        v[u] = KVRow<KV>::load(vbase + (int64_t) j * kvH + e4 * 4);
     }
 }
-struct KBatch {   // the rows of a lane's 4 keys of a 64-key batch (its 2 x 16 bytes of each)
-    float4 a[4], b[4];
+template <typename KV>
+struct KBatch {   // the rows of a lane's 4 keys of a 64-key batch (its 2 x 4 elements of each)
+    typename KVRow<KV>::vec4 a[4], b[4];
 };
-template <int HD>
-__device__ __forceinline__ void attn_k_request(KBatch &kb, const float *kbase, int kvH, int T, int j0, int tid) {
+template <int HD, typename KV>
+__device__ __forceinline__ void attn_k_request(KBatch<KV> &kb, const KV *kbase, int kvH, int T, int j0, int tid) {
     const int g = tid >> 4, sub = tid & 15;
 #pragma unroll
     for (int u = 0; u < 4; u++) {
         const int j = max(0, min(j0 + g + 16 * u, T - 1));
-        const float4 *kr = (const float4 *) (kbase + (int64_t) j * kvH);
-        kb.a[u] = kr[sub]; kb.b[u] = kr[16 + sub];
+        const KV *kr = kbase + (int64_t) j * kvH;
+        kb.a[u] = KVRow<KV>::load(kr + sub * 4); kb.b[u] = KVRow<KV>::load(kr + 64 + sub * 4);
     }
 }
-// kpre: the first NPRE batches, requested by the caller before the query was ready
-template <int HD, int NPRE>
-__device__ __forceinline__ void attn_scores_batched(KBatch (&kpre)[NPRE], const float *kbase, int kvH, int T, const float *qs, float scale, float *ps, int tid) {
+// kpre: the first batch, requested by the caller before the query was ready
+template <int HD, typename KV>
+__device__ __forceinline__ void attn_scores_batched(KBatch<KV> &kpre, const KV *kbase, int kvH, int T, const float *qs, float scale, float *ps, int tid) {
     const int g = tid >> 4, sub = tid & 15;
     const float4 q0 = *(const float4 *) (qs + sub * 4), q1 = *(const float4 *) (qs + 64 + sub * 4);
-    auto scores = [&](const KBatch &kb, int j0) __attribute__((always_inline)) {
+    auto scores = [&](const KBatch<KV> &kb, int j0) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int j = j0 + g + 16 * u;
-            float d = (kb.a[u].x * q0.x + kb.a[u].y * q0.y + kb.a[u].z * q0.z + kb.a[u].w * q0.w) + (kb.b[u].x * q1.x + kb.b[u].y * q1.y + kb.b[u].z * q1.z + kb.b[u].w * q1.w);
+            const float4 a = KVRow<KV>::widen(kb.a[u]), b = KVRow<KV>::widen(kb.b[u]);
+            float d = (a.x * q0.x + a.y * q0.y + a.z * q0.z + a.w * q0.w) + (b.x * q1.x + b.y * q1.y + b.z * q1.z + b.w * q1.w);
             d = row16_sum(d);
             if (sub == 0 && j < T) ps[j] = d * scale;
         }
     };
-#pragma unroll
-    for (int b = 0; b < NPRE; b++)
-        if (b * 64 < T) scores(kpre[b], b * 64);
-    for (int j0 = NPRE * 64; j0 < T; j0 += 64) {
-        KBatch kb;
+    scores(kpre, 0);
+    for (int j0 = 64; j0 < T; j0 += 64) {
+        KBatch<KV> kb;
         attn_k_request<HD>(kb, kbase, kvH, T, j0, tid);
         scores(kb, j0);
     }
 }
-template <int HD>
-__device__ __forceinline__ float4 attn_pv_batched(float4 (&v)[8], const float *vbase, int kvH, int T, const float *ps, int tid) {   // v: the first batch, already requested
+template <int HD, typename KV>
+__device__ __forceinline__ float4 attn_pv_batched(typename KVRow<KV>::vec4 (&v)[8], const KV *vbase, int kvH, int T, const float *ps, int tid) {   // v: the first batch, already requested
     const int grp = tid >> 5;
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (int j0 = 0; j0 < T; j0 += 64) {
@@ -504,7 +452,8 @@ __device__ __forceinline__ float4 attn_pv_batched(float4 (&v)[8], const float *v
             const int j = j0 + grp + 8 * u;
             if (j < T) {
                 const float p = ps[j];
-                acc.x += p * v[u].x; acc.y += p * v[u].y; acc.z += p * v[u].z; acc.w += p * v[u].w;
+                const float4 w = KVRow<KV>::widen(v[u]);
+                acc.x += p * w.x; acc.y += p * w.y; acc.z += p * w.z; acc.w += p * w.w;
             }
         }
     }
@@ -512,32 +461,53 @@ __device__ __forceinline__ float4 attn_pv_batched(float4 (&v)[8], const float *v
 }
 
 // Keys [kbeg[r], kend[r]) of the row's sequence (defaults: 0 and pos[r] + 1 = causal over the cache); row_seq / seq_stride as above.
-template <int HD>
-__global__ __launch_bounds__(256) void attn_gqa_kernel(const float *qkv, int ld, const uint32_t *pos, const float *kcache, const float *vcache, int NH, int NKV,
-                                                       float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq,
+// SPLIT false: grid (head, row), one workgroup reads all keys of its row; dst = out [R][NH * HD], aq / ad (optional) the o projection's Q8_0 blocks.
+// SPLIT true (grid (slice, row, head), dst = the partials; aq / ad unused): the decode-time form for few (head, row) pairs and many keys: one workgroup can
+// pull only ~1/256 of the HBM bandwidth (a CU's load path), so 24 workgroups reading 0.5 MB each take 20 us whatever the chip could do.  The keys of a row are
+// split over gridDim.x workgroups; each leaves (max, sum, unnormalised out[128]) and attn_gqa_combine_kernel merges them — the same
+// softmax, associated differently.  An empty split (short sequences under a graph captured for long ones) leaves max = -inf.
+// ATTN_PART (parler_kernels.h) floats per partial: max, sum, out[128]
+// One body: the two differ in the keys a workgroup owns and in what it leaves.
+template <int HD, bool SPLIT, typename KV>
+__global__ __launch_bounds__(256) void attn_gqa_kernel(const float *qkv, int ld, const uint32_t *pos, const KV *kcache, const KV *vcache, int NH, int NKV,
+                                                       float scale, float *dst, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq,
                                                        int64_t seq_stride, QPre qp = QPre{}, int8_t *aq = nullptr, float *ad = nullptr) {
     static_assert(HD == 128, "lane mapping below is written for head_dim 128 (orpheus/model.h:28)");
     __shared__ float red[8];
     __shared__ float4 accs[8][HD / 4];
     float *qs = attn_gqa_sm, *ps = attn_gqa_sm + HD;   // [HD] q, then [T] scores -> probabilities
-    const int h = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int k0 = kbeg ? (int) kbeg[r] : 0;
-    const int T = (kend ? (int) kend[r] : (int) pos[r] + 1) - k0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // SPLIT: blockIdx.x = key slice: workgroups go to the XCDs round-robin by their linear index, so with 8 slices an XCD owns ONE slice of every head and row —
+    // whole contiguous K / V rows per XCD.  With the head in x (until round 5) an XCD saw heads x and x + 8 only: two 512-byte pieces of every 8 KB row.
+    // (Measured equal on Dia's cross-attention, 134 MB per launch: 28.9 us = 4.6 TB/s either way, as is the request order below: that launch is
+    // neither latency- nor channel-bound, profiles/r05/dia_step_kernels_call18.txt.)
+    const int r = blockIdx.y, h = SPLIT ? blockIdx.z : blockIdx.x, z = SPLIT ? blockIdx.x : 0, nz = SPLIT ? gridDim.x : 1;
+    const int kb = kbeg ? (int) kbeg[r] : 0;
+    const int Tall = (kend ? (int) kend[r] : (int) pos[r] + 1) - kb;
+    const int chunk = (Tall + nz - 1) / nz;
+    const int k0 = kb + z * chunk;
+    const int T = SPLIT ? max(0, min(chunk, Tall - z * chunk)) : Tall;
+    float *pz = dst + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;   // SPLIT only
+    if (SPLIT && T <= 0) {
+        if (tid == 0) { pz[0] = -INFINITY; pz[1] = 0.0f; }
+        return;
+    }
     const int kvH = NKV * HD, kh = h / (NH / NKV);
     if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
-    kcache += (int64_t) k0 * kvH;
-    vcache += (int64_t) k0 * kvH;
-    // requests in the order of their use: the query (slabs, rope position), the K rows of the first 64 keys (two batches would be 140 registers: three workgroups per CU instead of four), the V rows of the first 64 (they do
-    // not depend on the scores); the query is folded and rotated under the K / V rows
+    kcache += (int64_t) k0 * kvH + kh * HD;
+    vcache += (int64_t) k0 * kvH + kh * HD;
+    // requests in the order of their use: the query (slabs, rope position), the K rows of the first 64 keys (two batches would be 140 registers over an fp32
+    // cache: three workgroups per CU instead of four), the V rows of the first 64 (they do not depend on the scores); the query is folded and rotated under
+    // the K / V rows
     QRaw qr;
     attn_q_request<HD>(qr, qkv + (int64_t) r * ld + h * HD, r, qp, tid);
-    KBatch kpre[1];
-    attn_k_request<HD>(kpre[0], kcache + kh * HD, kvH, T, 0, tid);
-    float4 vfirst[8];
-    attn_v_batch<HD>(vfirst, vcache + kh * HD, kvH, T, 0, tid);
+    KBatch<KV> kpre;
+    attn_k_request<HD>(kpre, kcache, kvH, T, 0, tid);
+    typename KVRow<KV>::vec4 vfirst[8];
+    attn_v_batch<HD>(vfirst, vcache, kvH, T, 0, tid);
     __builtin_amdgcn_sched_barrier(0);
     attn_q_finish<HD>(qs, qr, qkv + (int64_t) r * ld + h * HD, qp, tid);
-    attn_scores_batched<HD, 1>(kpre, kcache + kh * HD, kvH, T, qs, scale, ps, tid);
+    attn_scores_batched<HD>(kpre, kcache, kvH, T, qs, scale, ps, tid);
     __syncthreads();
     float mx = -INFINITY;
     for (int j = tid; j < T; j += 256) mx = fmaxf(mx, ps[j]);
@@ -554,93 +524,26 @@ __global__ __launch_bounds__(256) void attn_gqa_kernel(const float *qkv, int ld,
     sum = wave_sum(sum);
     if (lane == 0) red[4 + wave] = sum;
     __syncthreads();   // probabilities and the four partial sums are in LDS
-    const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
-    accs[tid >> 5][tid & 31] = attn_pv_batched<HD>(vfirst, vcache + kh * HD, kvH, T, ps, tid);
+    const float total = (red[4] + red[5]) + (red[6] + red[7]);
+    accs[tid >> 5][tid & 31] = attn_pv_batched<HD>(vfirst, vcache, kvH, T, ps, tid);
     __syncthreads();
     if (tid < HD) {
         const float *a = (const float *) &accs[0][0];
         float o = 0.0f;
 #pragma unroll
         for (int g = 0; g < 8; g++) o += a[g * HD + tid];
-        const float res = o * inv;
-        out[(int64_t) r * NH * HD + h * HD + tid] = res;
-        // the o projection's activation blocks (a head is four Q8_0 blocks; waves 0 and 1 are whole here): saves its quant_rows_q8_kernel launch
-        if (aq) q8_block_store(res, (int64_t) r * NH * HD + h * HD + tid, aq, ad);
+        if (SPLIT) pz[2 + tid] = o;
+        else {
+            const float res = o * (1.0f / total);
+            dst[(int64_t) r * NH * HD + h * HD + tid] = res;
+            // the o projection's activation blocks (a head is four Q8_0 blocks; waves 0 and 1 are whole here): saves its quant_rows_q8_kernel launch
+            if (aq) q8_block_store(res, (int64_t) r * NH * HD + h * HD + tid, aq, ad);
+        }
     }
+    if (SPLIT && tid == 0) { pz[0] = mx; pz[1] = total; }
 }
 
-// Decode-time form of attn_gqa_kernel for few (head, row) pairs and many keys: one workgroup can pull only ~1/256 of the HBM
-// bandwidth (a CU's load path), so 24 workgroups reading 0.5 MB each take 20 us whatever the chip could do.  The keys of a row are
-// split over gridDim.z workgroups; each leaves (max, sum, unnormalised out[128]) and attn_gqa_combine_kernel merges them — the same
-// softmax, associated differently.  An empty split (short sequences under a graph captured for long ones) leaves max = -inf.
-// ATTN_PART (parler_kernels.h) floats per partial: max, sum, out[128]
-template <int HD>
-__global__ __launch_bounds__(256) void attn_gqa_split_kernel(const float *qkv, int ld, const uint32_t *pos, const float *kcache, const float *vcache, int NH, int NKV,
-                                                             float scale, float *part, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq,
-                                                             int64_t seq_stride, QPre qp = QPre{}) {
-    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
-    __shared__ float red[8];
-    __shared__ float4 accs[8][HD / 4];
-    float *qs = attn_gqa_sm, *ps = attn_gqa_sm + HD;
-    // blockIdx.x = key slice: workgroups go to the XCDs round-robin by their linear index, so with 8 slices an XCD owns ONE slice of every head and row —
-    // whole contiguous K / V rows per XCD.  With the head in x (until round 5) an XCD saw heads x and x + 8 only: two 512-byte pieces of every 8 KB row.
-    // (Measured equal on Dia's cross-attention, 134 MB per launch: 28.9 us = 4.6 TB/s either way, as is the request order below: that launch is
-    // neither latency- nor channel-bound, profiles/r05/dia_step_kernels_call18.txt.)
-    const int z = blockIdx.x, r = blockIdx.y, h = blockIdx.z, nz = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kb = kbeg ? (int) kbeg[r] : 0;
-    const int Tall = (kend ? (int) kend[r] : (int) pos[r] + 1) - kb;
-    const int chunk = (Tall + nz - 1) / nz;
-    const int k0 = kb + z * chunk;
-    const int T = max(0, min(chunk, Tall - z * chunk));
-    float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
-    if (T <= 0) {
-        if (tid == 0) { pz[0] = -INFINITY; pz[1] = 0.0f; }
-        return;
-    }
-    const int kvH = NKV * HD, kh = h / (NH / NKV);
-    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
-    kcache += (int64_t) k0 * kvH;
-    vcache += (int64_t) k0 * kvH;
-    // requests in the order of their use: the query (slabs, rope position), the K rows of the first 64 keys (two batches would be 140 registers: three workgroups per CU instead of four), the V rows of the first 64 (they do
-    // not depend on the scores); the query is folded and rotated under the K / V rows
-    QRaw qr;
-    attn_q_request<HD>(qr, qkv + (int64_t) r * ld + h * HD, r, qp, tid);
-    KBatch kpre[1];
-    attn_k_request<HD>(kpre[0], kcache + kh * HD, kvH, T, 0, tid);
-    float4 vfirst[8];
-    attn_v_batch<HD>(vfirst, vcache + kh * HD, kvH, T, 0, tid);
-    __builtin_amdgcn_sched_barrier(0);
-    attn_q_finish<HD>(qs, qr, qkv + (int64_t) r * ld + h * HD, qp, tid);
-    attn_scores_batched<HD, 1>(kpre, kcache + kh * HD, kvH, T, qs, scale, ps, tid);
-    __syncthreads();
-    float mx = -INFINITY;
-    for (int j = tid; j < T; j += 256) mx = fmaxf(mx, ps[j]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.0f;
-    for (int j = tid; j < T; j += 256) {
-        const float p = expf(ps[j] - mx);
-        ps[j] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();
-    accs[tid >> 5][tid & 31] = attn_pv_batched<HD>(vfirst, vcache + kh * HD, kvH, T, ps, tid);
-    __syncthreads();
-    if (tid < HD) {
-        const float *a = (const float *) &accs[0][0];
-        float o = 0.0f;
-#pragma unroll
-        for (int g = 0; g < 8; g++) o += a[g * HD + tid];
-        pz[2 + tid] = o;
-    }
-    if (tid == 0) { pz[0] = mx; pz[1] = (red[4] + red[5]) + (red[6] + red[7]); }
-}
-
-// attn_gqa_split_kernel's job for the captured one-row step of a Llama decoder, restructured so that the launch is ONE memory round trip with
+// The job of attn_gqa_kernel's SPLIT form for the captured one-row step of a Llama decoder, restructured so that the launch is ONE memory round trip with
 // one workgroup barrier (round 5; the split kernel above is a chain of seven: position -> q -> K batch -> scores -> max -> exp / sum -> V -> merge,
 // 8.5 us per launch for 2.4 MB of cache at the Orpheus-3B shapes, profiles/r05/kernel_stats_orpheus_call1.csv):
 //   * the keys a (slice, wave, 16-lane group) reads do not depend on the position: key j belongs to slice (j / 16) % nz, inside the slice to group
@@ -651,7 +554,7 @@ __global__ __launch_bounds__(256) void attn_gqa_split_kernel(const float *qkv, i
 //     does for Parler): no score buffer, no barrier inside the key loop;
 //   * the 4 groups of a wave merge by permlane swaps, the 4 waves through LDS with the only barrier of the kernel.
 // A lane holds dims 4 sub .. + 3 and 64 + 4 sub .. + 3 of the 128-wide head (sub = lane % 16): a K or V row is read as 512 contiguous bytes.
-// The partials have attn_gqa_split_kernel's meaning (max, sum, unnormalised out[128] of the slice's keys; an empty slice leaves -inf, 0), so
+// The partials have the meaning of attn_gqa_kernel's SPLIT form (max, sum, unnormalised out[128] of the slice's keys; an empty slice leaves -inf, 0), so
 // attn_gqa_combine_kernel follows unchanged.  Another association of the same softmax than the kernel above: results agree to rounding.
 // EXT (Dia's cross-attention over the 1024 text positions, 8 rows x 16 heads x 8 slices of 128 keys = U = 8 passes): the keys end at kend[r], row r reads
 // the cache of sequence row_seq[r], and the query arrives as qp.n_parts K-slice slabs to be folded and rotated (QPre) — folded by the first 128
@@ -659,11 +562,14 @@ __global__ __launch_bounds__(256) void attn_gqa_split_kernel(const float *qkv, i
 // EXT requests stop at the row's last key instead of the last key of the context: a parked slot of Dia's loop has kend[r] = 1, and its rows ask for
 // that one row of K and V over and over (cache hits) instead of streaming the whole context only to mask it; kend[r] is loaded next to row_seq[r],
 // one round trip for both.  A row with kend[r] = n_ctx issues the requests an unclamped kernel would.
-template <int HD, int U, bool EXT = false>
-__global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, int ld, const uint32_t *pos, const float *kcache, const float *vcache, int NH, int NKV,
+// EXT runs its eight passes through U = KVRow<KV>::EXT_SLOTS rolling register slots (the host holds no other instantiation).
+template <int HD, int U, bool EXT, typename KV>
+__global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, int ld, const uint32_t *pos, const KV *kcache, const KV *vcache, int NH, int NKV,
                                                             float scale, float *part, int n_ctx, const uint32_t *kend = nullptr, const uint32_t *row_seq = nullptr,
                                                             int64_t seq_stride = 0, QPre qp = QPre{}) {
     static_assert(HD == 128, "lane mapping below is written for head_dim 128");
+    static_assert(U >= 1 && U <= 8, "EXT: eight passes through U register slots");
+    typedef KVRow<KV> Row;
     __shared__ float s_m[4], s_l[4];
     __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
     __shared__ __attribute__((aligned(16))) float s_q[EXT ? HD : 4];
@@ -675,19 +581,19 @@ __global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, in
     // wave-uniform bases + one 32-bit byte offset per row (a sequence's cache is far below 4 GB): K and V of a key share the offset register
     const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);
     auto key_of = [&](int p) { return 16 * (nz * p + z) + gi; };
-    float4 ka[U], kb[U], va[U], vb[U];
+    constexpr uint32_t ESZ = sizeof(KV), HALF = 64 * sizeof(KV);   // bytes per element, and between a lane's two 4-dim pieces of a row
+    typename Row::vec4 ka[U], kb[U], va[U], vb[U];
     auto request_one = [&](int u, int pass) __attribute__((always_inline)) {
-        const uint32_t off = ((uint32_t) min(key_of(pass), lim - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * 4u;
+        const uint32_t off = ((uint32_t) min(key_of(pass), lim - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * ESZ;
         if (EXT) {
-            // non-temporal: 2.4 GB of cross K / V per Dia step, nothing of it is met again before it has left every cache — and with plain loads the
+            // non-temporal: 2.4 GB of cross K / V per Dia step (fp32), nothing of it is met again before it has left every cache — and with plain loads the
             // 134 MB of a launch pushed the step's small hot set (rows, slabs, partials) out of L2 / the memory-side cache: the launch itself gains
             // 0.8 us, the step 5 % (1.90 -> 1.80 ms, same box, profiles/r05/dia_step_kernels_call21.txt)
-            auto ntl = [](const char *a) __attribute__((always_inline)) { return __builtin_bit_cast(float4, __builtin_nontemporal_load((const float4v *) a)); };
-            ka[u] = ntl(kp + off); kb[u] = ntl(kp + off + 256);
-            va[u] = ntl(vp + off); vb[u] = ntl(vp + off + 256);
+            ka[u] = Row::load_nt(kp + off); kb[u] = Row::load_nt(kp + off + HALF);
+            va[u] = Row::load_nt(vp + off); vb[u] = Row::load_nt(vp + off + HALF);
         } else {
-            ka[u] = *(const float4 *) (kp + off); kb[u] = *(const float4 *) (kp + off + 256);
-            va[u] = *(const float4 *) (vp + off); vb[u] = *(const float4 *) (vp + off + 256);
+            ka[u] = Row::load(kp + off); kb[u] = Row::load(kp + off + HALF);
+            va[u] = Row::load(vp + off); vb[u] = Row::load(vp + off + HALF);
         }
     };
     auto request = [&](int p0) __attribute__((always_inline)) {
@@ -746,23 +652,24 @@ __global__ __launch_bounds__(256) void attn_gqa_wave_kernel(const float *qkv, in
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
     auto consume = [&](int u, int pass) __attribute__((always_inline)) {
         if (key_of(pass) < T) {
-            float d = (ka[u].x * q0.x + ka[u].y * q0.y + ka[u].z * q0.z + ka[u].w * q0.w) + (kb[u].x * q1.x + kb[u].y * q1.y + kb[u].z * q1.z + kb[u].w * q1.w);
+            // fp32: references to the slot's registers, not copies — with copies the compiler contracted the other product of a * f + pr * v into the fma
+            // (the tree builds with -ffp-contract=fast) and the partials moved by a few units in the last place
+            decltype(auto) k0 = Row::widen(ka[u]); decltype(auto) k1 = Row::widen(kb[u]); decltype(auto) v0 = Row::widen(va[u]); decltype(auto) v1 = Row::widen(vb[u]);
+            float d = (k0.x * q0.x + k0.y * q0.y + k0.z * q0.z + k0.w * q0.w) + (k1.x * q1.x + k1.y * q1.y + k1.z * q1.z + k1.w * q1.w);
             d = row16_sum(d) * scale;
             const float mn = fmaxf(m, d);
             const float f = expf(m - mn);   // 0 on the group's first key (m = -inf)
             const float pr = expf(d - mn);
             l = l * f + pr;
-            a0.x = a0.x * f + pr * va[u].x; a0.y = a0.y * f + pr * va[u].y; a0.z = a0.z * f + pr * va[u].z; a0.w = a0.w * f + pr * va[u].w;
-            a1.x = a1.x * f + pr * vb[u].x; a1.y = a1.y * f + pr * vb[u].y; a1.z = a1.z * f + pr * vb[u].z; a1.w = a1.w * f + pr * vb[u].w;
+            a0.x = a0.x * f + pr * v0.x; a0.y = a0.y * f + pr * v0.y; a0.z = a0.z * f + pr * v0.z; a0.w = a0.w * f + pr * v0.w;
+            a1.x = a1.x * f + pr * v1.x; a1.y = a1.y * f + pr * v1.y; a1.z = a1.z * f + pr * v1.z; a1.w = a1.w * f + pr * v1.w;
             m = mn;
         }
     };
     if (EXT) {
         // eight passes (the host checks: at most 16 nz 8 keys), U register slots: a slot is requested again for pass p + U the moment pass p has been
-        // consumed, so every workgroup keeps U passes in flight from its first instruction to its last key.  Measured on Dia's cross-attention (134 MB
-        // per launch; a pure read of the same bytes: 23 us, profiles/r05/stride_read_bench_call19.txt): all eight passes requested at once (198
-        // registers, two workgroups per CU) 30.3 us, four slots (130 registers, three per CU) 27.7, three slots (112, four per CU) 26.9, the split
-        // kernel's three phases 28.1-28.9 (profiles/r05/dia_cross_attention_forms.txt, dia_step_kernels_call21.txt).
+        // consumed, so every workgroup keeps U passes in flight from its first instruction to its last key (the slot counts and what was measured for
+        // them: KVRow<KV>::EXT_SLOTS).
 #pragma unroll
         for (int p = 0; p < 8; p++) {
             consume(p % U, p);
@@ -842,371 +749,6 @@ static __global__ __launch_bounds__(128) void attn_gqa_combine_kernel(const floa
     const float res = o / l;
     out[(int64_t) r * NH * 128 + h * 128 + t] = res;
     if (aq) q8_block_store(res, (int64_t) r * NH * 128 + h * 128 + t, aq, ad);   // the o projection's activation blocks
-}
-
-// ------------------------------------------------------------------------------------------------
-// The three readers over an fp16 cache (TTS_HIP_FLAG_KV_F16, Orpheus contexts).  A key row of one kv head is 256 contiguous bytes instead of 512.
-// Lane -> dims, key -> lane group and the order of every sum are those of the fp32 kernels above, applied to the rows widened to fp32 (exact): a lane's
-// two 4-dim pieces (scores: dims 4 sub .. + 3 and 64 + 4 sub .. + 3; P.V: dims 4 e4 .. + 3) are 8-byte loads, kept as fp16 while they are in flight — the
-// rows in flight take half the registers — and widened where they are consumed.  Query, scores, softmax and accumulators are fp32; the partials have
-// the fp32 kernels' meaning, attn_gqa_combine_kernel follows unchanged.
-// ------------------------------------------------------------------------------------------------
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 widen4(half4v h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); }
-
-template <int HD>
-__device__ __forceinline__ void attn_v_batch_f16(half4v (&v)[8], const _Float16 *vbase, int kvH, int T, int j0, int tid) {
-    const int grp = tid >> 5, e4 = tid & 31;
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int j = max(0, min(j0 + grp + 8 * u, T - 1));
-        v[u] = *(const half4v *) (vbase + (int64_t) j * kvH + e4 * 4);
-    }
-}
-struct KBatchF16 {   // the rows of a lane's 4 keys of a 64-key batch (its 2 x 8 bytes of each)
-    half4v a[4], b[4];
-};
-template <int HD>
-__device__ __forceinline__ void attn_k_request_f16(KBatchF16 &kb, const _Float16 *kbase, int kvH, int T, int j0, int tid) {
-    const int g = tid >> 4, sub = tid & 15;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int j = max(0, min(j0 + g + 16 * u, T - 1));
-        const half4v *kr = (const half4v *) (kbase + (int64_t) j * kvH);
-        kb.a[u] = kr[sub]; kb.b[u] = kr[16 + sub];
-    }
-}
-template <int HD>
-__device__ __forceinline__ void attn_scores_batched_f16(KBatchF16 &kpre, const _Float16 *kbase, int kvH, int T, const float *qs, float scale, float *ps, int tid) {
-    const int g = tid >> 4, sub = tid & 15;
-    const float4 q0 = *(const float4 *) (qs + sub * 4), q1 = *(const float4 *) (qs + 64 + sub * 4);
-    auto scores = [&](const KBatchF16 &kb, int j0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + g + 16 * u;
-            const float4 a = widen4(kb.a[u]), b = widen4(kb.b[u]);
-            float d = (a.x * q0.x + a.y * q0.y + a.z * q0.z + a.w * q0.w) + (b.x * q1.x + b.y * q1.y + b.z * q1.z + b.w * q1.w);
-            d = row16_sum(d);
-            if (sub == 0 && j < T) ps[j] = d * scale;
-        }
-    };
-    scores(kpre, 0);
-    for (int j0 = 64; j0 < T; j0 += 64) {
-        KBatchF16 kb;
-        attn_k_request_f16<HD>(kb, kbase, kvH, T, j0, tid);
-        scores(kb, j0);
-    }
-}
-template <int HD>
-__device__ __forceinline__ float4 attn_pv_batched_f16(half4v (&v)[8], const _Float16 *vbase, int kvH, int T, const float *ps, int tid) {   // v: the first batch, already requested
-    const int grp = tid >> 5;
-    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int j0 = 0; j0 < T; j0 += 64) {
-        if (j0) attn_v_batch_f16<HD>(v, vbase, kvH, T, j0, tid);
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int j = j0 + grp + 8 * u;
-            if (j < T) {
-                const float p = ps[j];
-                const float4 w = widen4(v[u]);
-                acc.x += p * w.x; acc.y += p * w.y; acc.z += p * w.z; acc.w += p * w.w;
-            }
-        }
-    }
-    return acc;
-}
-
-// attn_gqa_kernel (SPLIT false: grid (head, row), dst = out [R][NH * HD], aq / ad as there) and attn_gqa_split_kernel (SPLIT true: grid (slice, row, head),
-// dst = the partials) over an fp16 cache: one body, the two differ in the keys a workgroup owns and in what it leaves.
-template <int HD, bool SPLIT>
-__global__ __launch_bounds__(256) void attn_gqa_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH, int NKV,
-                                                           float scale, float *dst, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq,
-                                                           int64_t seq_stride, QPre qp = QPre{}, int8_t *aq = nullptr, float *ad = nullptr) {
-    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
-    __shared__ float red[8];
-    __shared__ float4 accs[8][HD / 4];
-    float *qs = attn_gqa_sm, *ps = attn_gqa_sm + HD;   // [HD] q, then [T] scores -> probabilities
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = blockIdx.y, h = SPLIT ? blockIdx.z : blockIdx.x, z = SPLIT ? blockIdx.x : 0, nz = SPLIT ? gridDim.x : 1;
-    const int kb = kbeg ? (int) kbeg[r] : 0;
-    const int Tall = (kend ? (int) kend[r] : (int) pos[r] + 1) - kb;
-    const int chunk = (Tall + nz - 1) / nz;
-    const int k0 = kb + z * chunk;
-    const int T = SPLIT ? max(0, min(chunk, Tall - z * chunk)) : Tall;
-    float *pz = dst + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;   // SPLIT only
-    if (SPLIT && T <= 0) {
-        if (tid == 0) { pz[0] = -INFINITY; pz[1] = 0.0f; }
-        return;
-    }
-    const int kvH = NKV * HD, kh = h / (NH / NKV);
-    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
-    kcache += (int64_t) k0 * kvH + kh * HD;
-    vcache += (int64_t) k0 * kvH + kh * HD;
-    // requests in the order of their use, as in the fp32 kernels: the query, the K rows of the first 64 keys, the V rows of the first 64
-    QRaw qr;
-    attn_q_request<HD>(qr, qkv + (int64_t) r * ld + h * HD, r, qp, tid);
-    KBatchF16 kpre;
-    attn_k_request_f16<HD>(kpre, kcache, kvH, T, 0, tid);
-    half4v vfirst[8];
-    attn_v_batch_f16<HD>(vfirst, vcache, kvH, T, 0, tid);
-    __builtin_amdgcn_sched_barrier(0);
-    attn_q_finish<HD>(qs, qr, qkv + (int64_t) r * ld + h * HD, qp, tid);
-    attn_scores_batched_f16<HD>(kpre, kcache, kvH, T, qs, scale, ps, tid);
-    __syncthreads();
-    float mx = -INFINITY;
-    for (int j = tid; j < T; j += 256) mx = fmaxf(mx, ps[j]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.0f;
-    for (int j = tid; j < T; j += 256) {
-        const float p = expf(ps[j] - mx);
-        ps[j] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();   // probabilities and the four partial sums are in LDS
-    const float total = (red[4] + red[5]) + (red[6] + red[7]);
-    accs[tid >> 5][tid & 31] = attn_pv_batched_f16<HD>(vfirst, vcache, kvH, T, ps, tid);
-    __syncthreads();
-    if (tid < HD) {
-        const float *a = (const float *) &accs[0][0];
-        float o = 0.0f;
-#pragma unroll
-        for (int g = 0; g < 8; g++) o += a[g * HD + tid];
-        if (SPLIT) pz[2 + tid] = o;
-        else {
-            const float res = o * (1.0f / total);
-            dst[(int64_t) r * NH * HD + h * HD + tid] = res;
-            if (aq) q8_block_store(res, (int64_t) r * NH * HD + h * HD + tid, aq, ad);
-        }
-    }
-    if (SPLIT && tid == 0) { pz[0] = mx; pz[1] = total; }
-}
-
-// attn_gqa_wave_kernel<HD, U> (the captured one-row step of Orpheus; its EXT form, Dia's, has attn_gqa_wave_ext_f16_kernel below) over an fp16 cache: the same keys per
-// (slice, wave, 16-lane group), the same running max / sum / output, the same merges.  K and V of a key share a 32-bit byte offset of 2 bytes per element.
-template <int HD, int U>
-__global__ __launch_bounds__(256) void attn_gqa_wave_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH, int NKV,
-                                                                float scale, float *part, int n_ctx) {
-    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
-    __shared__ float s_m[4], s_l[4];
-    __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
-    const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
-    const int kvH = NKV * HD, kh = h / (NH / NKV);
-    const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);
-    auto key_of = [&](int p) { return 16 * (nz * p + z) + gi; };
-    half4v ka[U], kb[U], va[U], vb[U];
-    auto request = [&](int p0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t off = ((uint32_t) min(key_of(p0 + u), n_ctx - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * 2u;
-            ka[u] = *(const half4v *) (kp + off); kb[u] = *(const half4v *) (kp + off + 128);
-            va[u] = *(const half4v *) (vp + off); vb[u] = *(const half4v *) (vp + off + 128);
-        }
-    };
-    // the small inputs first (vmcnt retires in issue order: the position and q are usable while the rows below are still in flight)
-    const float *qr = qkv + (int64_t) r * ld + h * HD + sub * 4;
-    const float4 q0 = *(const float4 *) qr, q1 = *(const float4 *) (qr + 64);
-    const int T = (int) pos[r] + 1;
-    __builtin_amdgcn_sched_barrier(0);
-    request(0);
-    __builtin_amdgcn_sched_barrier(0);
-    float m = -INFINITY, l = 0.0f;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    auto consume = [&](int u, int pass) __attribute__((always_inline)) {
-        if (key_of(pass) < T) {
-            const float4 k0 = widen4(ka[u]), k1 = widen4(kb[u]), v0 = widen4(va[u]), v1 = widen4(vb[u]);
-            float d = (k0.x * q0.x + k0.y * q0.y + k0.z * q0.z + k0.w * q0.w) + (k1.x * q1.x + k1.y * q1.y + k1.z * q1.z + k1.w * q1.w);
-            d = row16_sum(d) * scale;
-            const float mn = fmaxf(m, d);
-            const float f = expf(m - mn);   // 0 on the group's first key (m = -inf)
-            const float pr = expf(d - mn);
-            l = l * f + pr;
-            a0.x = a0.x * f + pr * v0.x; a0.y = a0.y * f + pr * v0.y; a0.z = a0.z * f + pr * v0.z; a0.w = a0.w * f + pr * v0.w;
-            a1.x = a1.x * f + pr * v1.x; a1.y = a1.y * f + pr * v1.y; a1.z = a1.z * f + pr * v1.z; a1.w = a1.w * f + pr * v1.w;
-            m = mn;
-        }
-    };
-    for (int p0 = 0; 16 * nz * p0 < T; p0 += U) {
-        if (p0) request(p0);
-#pragma unroll
-        for (int u = 0; u < U; u++) consume(u, p0 + u);
-    }
-    // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
-    auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
-                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
-    auto x32 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
-    float mw;
-    { float2 t = x16(m); mw = fmaxf(t.x, t.y); t = x32(mw); mw = fmaxf(t.x, t.y); }
-    const float fg = m == -INFINITY ? 0.0f : expf(m - mw);
-    float vals[9] = {l * fg, a0.x * fg, a0.y * fg, a0.z * fg, a0.w * fg, a1.x * fg, a1.y * fg, a1.z * fg, a1.w * fg};
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        float2 t = x16(vals[i]); float v = t.x + t.y;
-        t = x32(v); vals[i] = t.x + t.y;
-    }
-    if (g == 0) {
-        *(float4 *) (&s_acc[wave][sub * 4]) = make_float4(vals[1], vals[2], vals[3], vals[4]);
-        *(float4 *) (&s_acc[wave][64 + sub * 4]) = make_float4(vals[5], vals[6], vals[7], vals[8]);
-        if (sub == 0) { s_m[wave] = mw; s_l[wave] = vals[0]; }
-    }
-    __syncthreads();
-    if (tid < HD) {
-        const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float o = 0.0f, L = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const float f = s_m[w] == -INFINITY ? 0.0f : expf(s_m[w] - M);
-            o += f * s_acc[w][tid];
-            L += f * s_l[w];
-        }
-        float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
-        pz[2 + tid] = o;
-        if (tid == 0) { pz[0] = M; pz[1] = L; }
-    }
-}
-
-// attn_gqa_wave_kernel<HD, U, true> (Dia's cross-attention, the EXT form above) over an fp16 cache (tts_hip_dia_desc::kv_type = TTS_HIP_F16): the same
-// key -> (slice, wave, 16-lane group, pass), requests clamped at kend[r] (a parked row asks for its one key only), row_seq and the sequence stride, the query
-// folded from its QPre slabs through LDS and rotated in the lanes, non-temporal loads, the same running max / sum / output and the same merges.  A lane's
-// two 4-dim pieces of a row are 8-byte loads kept as fp16 while in flight and widened where they are consumed, so the dot product and every fold associate
-// as in the fp32 kernel: the results differ from it only through the rounding of the stored rows.  A pass costs 8 registers instead of 16.  Measured on
-// the Dia-1.6B step at 8 rows (profiles/dia_kv_f16_u.json; fp32 cache 1.735 / 2.086 ms at positions 100 / 2000): U = 4 slots (98 registers, four
-// workgroups per CU, under the fp32 form's 112) 1.596 / 1.858 ms, all eight passes requested at once (U = 8: 132 registers, three workgroups per CU)
-// 1.648 / 1.919 — so the host launches <128, 4> and holds no other instantiation.  U only moves requests, never a sum: the result bits do not depend on it.
-template <int HD, int U>
-__global__ __launch_bounds__(256) void attn_gqa_wave_ext_f16_kernel(const float *qkv, int ld, const uint32_t *pos, const _Float16 *kcache, const _Float16 *vcache, int NH,
-                                                                    int NKV, float scale, float *part, int n_ctx, const uint32_t *kend, const uint32_t *row_seq,
-                                                                    int64_t seq_stride, QPre qp) {
-    static_assert(HD == 128, "lane mapping below is written for head_dim 128");
-    static_assert(U >= 1 && U <= 8, "eight passes through U register slots");
-    __shared__ float s_m[4], s_l[4];
-    __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
-    __shared__ __attribute__((aligned(16))) float s_q[HD];
-    const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
-    const int kvH = NKV * HD, kh = h / (NH / NKV);
-    const int lim = kend ? max(1, min((int) kend[r], n_ctx)) : n_ctx;
-    if (row_seq) { kcache += (int64_t) row_seq[r] * seq_stride; vcache += (int64_t) row_seq[r] * seq_stride; }
-    // wave-uniform bases + one 32-bit byte offset per row (2 bytes per element): K and V of a key share the offset register
-    const char *kp = (const char *) (kcache + kh * HD), *vp = (const char *) (vcache + kh * HD);
-    auto key_of = [&](int p) { return 16 * (nz * p + z) + gi; };
-    half4v ka[U], kb[U], va[U], vb[U];
-    auto request_one = [&](int u, int pass) __attribute__((always_inline)) {
-        const uint32_t off = ((uint32_t) min(key_of(pass), lim - 1) * (uint32_t) kvH + (uint32_t) sub * 4u) * 2u;
-        auto ntl = [](const char *a) __attribute__((always_inline)) { return __builtin_nontemporal_load((const half4v *) a); };   // met once per step, as in the fp32 form
-        ka[u] = ntl(kp + off); kb[u] = ntl(kp + off + 128);
-        va[u] = ntl(vp + off); vb[u] = ntl(vp + off + 128);
-    };
-    // the small inputs first (vmcnt retires in issue order): threads 0-127 hold slabs 0-3 of query element tid, threads 128-255 slabs 4-7 of element tid - 128
-    float tq[4];
-    uint32_t rp = 0;
-    {
-        const float *qe = qkv + (int64_t) r * ld + h * HD + (tid & (HD - 1));
-#pragma unroll
-        for (int p = 0; p < 4; p++) tq[p] = qe[(int64_t) min((tid >> 7) * 4 + p, qp.n_parts - 1) * qp.part_stride];
-        if (qp.rope_pos) rp = qp.rope_pos[r];
-    }
-    const int T = kend ? (int) kend[r] : (int) pos[r] + 1;
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; u++) request_one(u, u);
-    __builtin_amdgcn_sched_barrier(0);
-    // attn_q_finish's arithmetic, as in the fp32 form: slabs in slab order (the upper half of the workgroup continues the lower half's sum), then ggml_rope
-    // NEOX with the iterated theta (pair i, i + 64: both in this lane)
-    if (tid < HD) {
-        float x = tq[0];
-#pragma unroll
-        for (int p = 1; p < 4; p++)
-            if (p < qp.n_parts) x += tq[p];
-        s_q[tid] = x;
-    }
-    __syncthreads();
-    if (tid >= HD) {
-        float x = s_q[tid - HD];
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-            if (4 + p < qp.n_parts) x += tq[p];   // (the host sends at most 8 slabs here)
-        s_q[tid - HD] = x;
-    }
-    __syncthreads();
-    float4 q0 = *(const float4 *) (s_q + sub * 4), q1 = *(const float4 *) (s_q + 64 + sub * 4);
-    if (qp.rope_pos) {
-        float theta = (float) rp;
-        for (int j = 0; j < sub * 4; j++) theta *= qp.theta_scale;
-        float *a = (float *) &q0, *b = (float *) &q1;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float cs = cosf(theta), sn = sinf(theta);
-            const float x0 = a[e], x1 = b[e];
-            a[e] = x0 * cs - x1 * sn; b[e] = x0 * sn + x1 * cs;
-            theta *= qp.theta_scale;
-        }
-    }
-    float m = -INFINITY, l = 0.0f;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    auto consume = [&](int u, int pass) __attribute__((always_inline)) {
-        if (key_of(pass) < T) {
-            const float4 k0 = widen4(ka[u]), k1 = widen4(kb[u]), v0 = widen4(va[u]), v1 = widen4(vb[u]);
-            float d = (k0.x * q0.x + k0.y * q0.y + k0.z * q0.z + k0.w * q0.w) + (k1.x * q1.x + k1.y * q1.y + k1.z * q1.z + k1.w * q1.w);
-            d = row16_sum(d) * scale;
-            const float mn = fmaxf(m, d);
-            const float f = expf(m - mn);   // 0 on the group's first key (m = -inf)
-            const float pr = expf(d - mn);
-            l = l * f + pr;
-            a0.x = a0.x * f + pr * v0.x; a0.y = a0.y * f + pr * v0.y; a0.z = a0.z * f + pr * v0.z; a0.w = a0.w * f + pr * v0.w;
-            a1.x = a1.x * f + pr * v1.x; a1.y = a1.y * f + pr * v1.y; a1.z = a1.z * f + pr * v1.z; a1.w = a1.w * f + pr * v1.w;
-            m = mn;
-        }
-    };
-    // eight passes (the host checks: at most 16 nz 8 keys) through U register slots: a slot is requested again for pass p + U once pass p has been consumed
-#pragma unroll
-    for (int p = 0; p < 8; p++) {
-        consume(p % U, p);
-        if (p + U < 8) {
-            __builtin_amdgcn_sched_barrier(0);   // the slot's registers are free only now
-            request_one(p % U, p + U);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
-    auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
-                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
-    auto x32 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-                             return make_float2(__builtin_bit_cast(float, (unsigned) b[0]), __builtin_bit_cast(float, (unsigned) b[1])); };
-    float mw;
-    { float2 t = x16(m); mw = fmaxf(t.x, t.y); t = x32(mw); mw = fmaxf(t.x, t.y); }
-    const float fg = m == -INFINITY ? 0.0f : expf(m - mw);
-    float vals[9] = {l * fg, a0.x * fg, a0.y * fg, a0.z * fg, a0.w * fg, a1.x * fg, a1.y * fg, a1.z * fg, a1.w * fg};
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        float2 t = x16(vals[i]); float v = t.x + t.y;
-        t = x32(v); vals[i] = t.x + t.y;
-    }
-    if (g == 0) {
-        *(float4 *) (&s_acc[wave][sub * 4]) = make_float4(vals[1], vals[2], vals[3], vals[4]);
-        *(float4 *) (&s_acc[wave][64 + sub * 4]) = make_float4(vals[5], vals[6], vals[7], vals[8]);
-        if (sub == 0) { s_m[wave] = mw; s_l[wave] = vals[0]; }
-    }
-    __syncthreads();
-    if (tid < HD) {
-        const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float o = 0.0f, L = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const float f = s_m[w] == -INFINITY ? 0.0f : expf(s_m[w] - M);
-            o += f * s_acc[w][tid];
-            L += f * s_l[w];
-        }
-        float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
-        pz[2 + tid] = o;
-        if (tid == 0) { pz[0] = M; pz[1] = L; }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------

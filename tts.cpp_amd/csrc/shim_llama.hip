@@ -40,13 +40,29 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
     return c;
 }
 
+// The one dispatch on a K/V cache's element size (4: fp32; 2: fp16 — Orpheus TTS_HIP_FLAG_KV_F16, Dia tts_hip_dia_desc::kv_type): f(kc, vc) runs with the two
+// pointers typed float * or _Float16 *, and the writers and readers it launches are the instantiations for that type (kv_of<decltype(kc)>).
+template <typename P> using kv_of = std::remove_pointer_t<P>;
+template <typename F>
+static int with_kv(int kv_esz, void *kc, void *vc, F &&f) {
+    return kv_esz == 2 ? f((_Float16 *) kc, (_Float16 *) vc) : f((float *) kc, (float *) vc);
+}
+
+// attn_gqa_kernel<128, false, KV> with more than 48 KB of scores: the attribute once per instantiation and device
+template <typename KV>
+static int attn_gqa_allow_lds(tts_hip_ctx *c, size_t lds) {
+    static std::atomic<uint64_t> attr{0};
+    if (lds > 48 * 1024 && attr_needed(attr, c->device))
+        HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_kernel<128, false, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
+    return 0;
+}
+
 // attention of the Llama / Dia steps: one workgroup per (head, row), or — few rows, many keys — the keys split over `nz` workgroups
-// plus a combine launch (attn_gqa_split_kernel).  max_keys bounds the LDS score buffer.
-static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const float *kc, const float *vc, int NKV,
+// plus a combine launch (attn_gqa_kernel<128, true, KV>).  max_keys bounds the LDS score buffer.  seq_stride counts cache elements.
+template <typename KV>
+static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const KV *kc, const KV *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
-                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0, int kv_esz = 4) {
-    // kv_esz 2: kc / vc are an fp16 cache (Orpheus: TTS_HIP_FLAG_KV_F16; Dia: tts_hip_dia_desc::kv_type) and the fp16 forms of the kernels read it; seq_stride stays in elements
-    const _Float16 *kc16 = (const _Float16 *) kc, *vc16 = (const _Float16 *) vc;
+                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0) {
     int nz = 1;
     if (deferred) *deferred = 0;
     if (c->attn_split_max > 1 && NHq * rows <= 256) {
@@ -55,41 +71,25 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         while (nz > 1 && (size_t) rows * NHq * nz > c->attn_part_cap) nz--;
     }
     if (nz <= 1) {
-        if (kv_esz == 2) {
-            hipLaunchKernelGGL((attn_gqa_f16_kernel<128, false>), dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, out, kbeg, kend,
-                               row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
-        } else {
-            hipLaunchKernelGGL(attn_gqa_kernel<128>, dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
-                               row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
-        }
+        hipLaunchKernelGGL((attn_gqa_kernel<128, false, KV>), dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
+                           row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
         HIPCHK(hipGetLastError());
         if (q_out) c->aq_src = out;
         return 0;
     }
     const int chunk = (max_keys + nz - 1) / nz;
-    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * (uint64_t) kv_esz < (1ull << 32);   // attn_gqa_wave_kernel addresses a sequence's rows with 32-bit byte offsets
-    if (kv_esz == 2) {
-        if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
-            hipLaunchKernelGGL((attn_gqa_wave_f16_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part, n_ctx_keys);
-        } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
-            // Dia's cross-attention over an fp16 cache (tts_hip_dia_desc::kv_type): the conditions of the fp32 EXT form below, 8 passes through 4 rolling register slots
-            hipLaunchKernelGGL((attn_gqa_wave_ext_f16_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part, n_ctx_keys,
-                               kend, row_seq, seq_stride, qp);
-        } else {
-            hipLaunchKernelGGL((attn_gqa_f16_kernel<128, true>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc16, vc16, NHq, NKV, scale, c->attn_part,
-                               kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
-        }
-    } else if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
+    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * sizeof(KV) < (1ull << 32);   // attn_gqa_wave_kernel addresses a sequence's rows with 32-bit byte offsets
+    if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
         // the captured one-row step (Orpheus): every key row requested at kernel start, online softmax per 16-lane group, one barrier (attn_gqa_wave_kernel)
-        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
+        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4, false, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
     } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
-        // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through 3 rolling register slots
-        // (the parked rows of a loop step, kend[r] = 1, request that one key only)
-        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 3, true>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys,
-                           kend, row_seq, seq_stride, qp);
+        // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through KVRow<KV>::EXT_SLOTS
+        // rolling register slots (the parked rows of a loop step, kend[r] = 1, request that one key only)
+        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, KVRow<KV>::EXT_SLOTS, true, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
+                           n_ctx_keys, kend, row_seq, seq_stride, qp);
     } else {
-        hipLaunchKernelGGL(attn_gqa_split_kernel<128>, dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
-                           kbeg, kend, row_seq, seq_stride, qp);
+        hipLaunchKernelGGL((attn_gqa_kernel<128, true, KV>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
+                           kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
     }
     HIPCHK(hipGetLastError());
     if (deferred && c->attn_fold && nz == ATTN_FOLD_NZ && !c->prof && !c->debug) {
@@ -212,61 +212,51 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     };
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->l_layers[l];
-        // this layer of slot 0; under TTS_HIP_FLAG_KV_F16 the same rows as fp16 (kc16 / vc16) and the fp16 forms of the writers and readers
-        const bool kv16 = c->l_kv_esz == 2;
+        // this layer of slot 0: fp32 rows, or fp16 rows under TTS_HIP_FLAG_KV_F16 (with_kv: the cache's writer and readers below are launched for that type)
         const size_t layer_off = (size_t) l * NCTX * c->l_kvH * (size_t) c->l_kv_esz;
-        float *kc = (float *) ((char *) c->l_kc + layer_off), *vc = (float *) ((char *) c->l_vc + layer_off);
-        _Float16 *kc16 = (_Float16 *) kc, *vc16 = (_Float16 *) vc;
         const size_t qkv_lds = (size_t) n * H + (size_t) n * (H / 32) * 4;
         const bool qkv_fused = !row_seq && n <= 4 && c->q4_rope && c->q4_lds && y.qkv.q4 && q_for(y.qkv, n, QS_QKV) && HD == 128 && H % 512 == 0 && qkv_lds <= 64 * 1024 && !c->prof;
         // the rms norm inside the consuming projection's staging (stage_rms_q8): no slabs may be pending, the row is held in registers
         const bool rms_fused = c->q4_rms && !c->l_pending && H <= 4096;
-        if (qkv_fused && rms_fused) {
-            QGemmArgs qa{};
-            qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
-            qa.wd = (const _Float16 *) (c->arena + y.qkv.soff);
-            RopeEpi re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
-            RopeEpiF16 re16{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc16, vc16};
-            RmsSrc rs{c->l_x, f32(y.in_norm), 1e-5f};
-            if (kv16) hipLaunchKernelGGL((gemv_q4_qkv_rope_f16_kernel<4, 2>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re16, rs);
-            else hipLaunchKernelGGL((gemv_q4_qkv_rope_kernel<4, 2>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re, rs);
-            HIPCHK(hipGetLastError());
-            c->aq_src = nullptr;
-        } else if (qkv_fused) {
-            CHK(rms(y.in_norm, n, c->l_x, c->l_xn, &y.qkv, QS_QKV));
-            // the projection, the rope of q and k and the cache append in one launch (gemv_q4_qkv_rope_kernel)
-            QGemmArgs qa{};
-            qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
-            qa.wd = (const _Float16 *) (c->arena + y.qkv.soff); qa.aq = c->aq; qa.ad = c->ad;
-            RopeEpi re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
-            RopeEpiF16 re16{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc16, vc16};
-            if (kv16) hipLaunchKernelGGL(gemv_q4_qkv_rope_f16_kernel<4>, dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re16, RmsSrc{});
-            else hipLaunchKernelGGL(gemv_q4_qkv_rope_kernel<4>, dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re);
-            HIPCHK(hipGetLastError());
-            c->aq_src = nullptr;
-        } else {
-            CHK(rms(y.in_norm, n, c->l_x, c->l_xn, &y.qkv, QS_QKV));
-            const int sl = qstream(y.qkv, QS_QKV, c->l_xn, H, c->l_qkv, QKV, (int64_t) srows * QKV, smax);   // slabs of srows rows inside l_qkv ([RMAX][QKV])
-            if (sl < 0) return -1;
-            if (!sl) {
-                if (tiled(y.qkv)) CHK(tile_store(TTS_HIP_K_GEMM_OTHER, y.qkv, c->l_qkv, QKV));
-                else CHK(llama_gemm(c, y.qkv, c->l_xn, H, c->l_qkv, QKV, n, EPI_STORE));
+        CHK(with_kv(c->l_kv_esz, (char *) c->l_kc + layer_off, (char *) c->l_vc + layer_off, [&](auto *kc, auto *vc) -> int {
+            typedef kv_of<decltype(kc)> KV;
+            const RopeEpi<KV> re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
+            if (qkv_fused && rms_fused) {
+                QGemmArgs qa{};
+                qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
+                qa.wd = (const _Float16 *) (c->arena + y.qkv.soff);
+                RmsSrc rs{c->l_x, f32(y.in_norm), 1e-5f};
+                hipLaunchKernelGGL((gemv_q4_qkv_rope_kernel<4, 2, 2, KV>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds + 16, c->stream, qa, y.qkv.q4, re, rs);
+                HIPCHK(hipGetLastError());
+                c->aq_src = nullptr;
+            } else if (qkv_fused) {
+                CHK(rms(y.in_norm, n, c->l_x, c->l_xn, &y.qkv, QS_QKV));
+                // the projection, the rope of q and k and the cache append in one launch (gemv_q4_qkv_rope_kernel)
+                QGemmArgs qa{};
+                qa.g.W = c->arena + y.qkv.off; qa.g.K = H; qa.g.N = QKV; qa.g.R = n; qa.g.out = c->l_qkv; qa.g.ldo = QKV;
+                qa.wd = (const _Float16 *) (c->arena + y.qkv.soff); qa.aq = c->aq; qa.ad = c->ad;
+                hipLaunchKernelGGL((gemv_q4_qkv_rope_kernel<4, 0, 2, KV>), dim3((QKV / 2 + 3) / 4), dim3(256), qkv_lds, c->stream, qa, y.qkv.q4, re, RmsSrc{});
+                HIPCHK(hipGetLastError());
+                c->aq_src = nullptr;
+            } else {
+                CHK(rms(y.in_norm, n, c->l_x, c->l_xn, &y.qkv, QS_QKV));
+                const int sl = qstream(y.qkv, QS_QKV, c->l_xn, H, c->l_qkv, QKV, (int64_t) srows * QKV, smax);   // slabs of srows rows inside l_qkv ([RMAX][QKV])
+                if (sl < 0) return -1;
+                if (!sl) {
+                    if (tiled(y.qkv)) CHK(tile_store(TTS_HIP_K_GEMM_OTHER, y.qkv, c->l_qkv, QKV));
+                    else CHK(llama_gemm(c, y.qkv, c->l_xn, H, c->l_qkv, QKV, n, EPI_STORE));
+                }
+                hipLaunchKernelGGL(llama_rope_kv_kernel<KV>, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc, vc,
+                                   row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
+                HIPCHK(hipGetLastError());
             }
-            if (kv16)
-                hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc16, vc16,
-                                   row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
-            else
-                hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH + NKV), dim3(64), 0, c->stream, c->l_qkv, (const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, HD, kc, vc,
-                                   row_seq, row_seq ? seq_stride : (int64_t) 0, std::max(sl, 1), (int64_t) srows * QKV);
-            HIPCHK(hipGetLastError());
-        }
-        // tts_hip_profile: the attention launches of the step as TTS_HIP_K_ATTN_SELF (bytes: K and V rows up to the bound on the rows' keys)
-        const int max_keys = (int) (attn_positions ? (uint32_t) attn_positions : pos0 + n);
-        CHK(prof_begin(c, TTS_HIP_K_ATTN_SELF, 2.0 * n * max_keys * c->l_kvH * c->l_kv_esz, 0.0));
-        CHK(launch_attn_gqa(c, NH, n, max_keys, (const float *) c->l_qkv, QKV, (const uint32_t *) c->l_pos,
-                            (const float *) kc, (const float *) vc, NKV, 1.0f / sqrtf((float) HD), c->l_att, nullptr, nullptr, row_seq, row_seq ? seq_stride : (int64_t) 0,
-                            attn_positions != 0 && !row_seq, q_for(y.o, n, QS_O), QPre{}, nullptr, NCTX, c->l_kv_esz));
-        CHK(prof_end(c));
+            // tts_hip_profile: the attention launches of the step as TTS_HIP_K_ATTN_SELF (bytes: K and V rows up to the bound on the rows' keys)
+            const int max_keys = (int) (attn_positions ? (uint32_t) attn_positions : pos0 + n);
+            CHK(prof_begin(c, TTS_HIP_K_ATTN_SELF, 2.0 * n * max_keys * c->l_kvH * c->l_kv_esz, 0.0));
+            CHK(launch_attn_gqa<KV>(c, NH, n, max_keys, (const float *) c->l_qkv, QKV, (const uint32_t *) c->l_pos, kc, vc, NKV, 1.0f / sqrtf((float) HD), c->l_att, nullptr, nullptr,
+                                    row_seq, row_seq ? seq_stride : (int64_t) 0, attn_positions != 0 && !row_seq, q_for(y.o, n, QS_O), QPre{}, nullptr, NCTX));
+            return prof_end(c);
+        }));
         {
             const int sl = qstream(y.o, QS_O, c->l_att, NH * HD, c->l_parts, H, (int64_t) srows * H, pmax);   // slabs of srows rows inside l_parts ([8][RMAX][H]), folded into the residual stream by the next rms norm
             if (sl < 0) return -1;
@@ -1385,18 +1375,16 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
     const float theta_scale = powf(10000.0f, -2.0f / (float) HD);   // ggml_rope(..., head_size, 2): default base
     const size_t attn_lds = (size_t) (128 + S) * 4;
-    static std::atomic<uint64_t> attr{0};
-    if (attn_lds > 48 * 1024 && attr_needed(attr, c->device))
-        HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
+    CHK(attn_gqa_allow_lds<float>(c, attn_lds));   // the encoder's own K/V scratch is fp32
     hipLaunchKernelGGL(t5_embed_kernel, dim3(n), dim3(256), 0, c->stream, f32(c->di_enc_embd), (const uint32_t *) c->di_tok, EH, c->di_ex);
     HIPCHK(hipGetLastError());
     for (const auto &y : c->di_enc) {
         CHK(dia_rms(c, y.sa_norm, n, EH, c->di_ex, c->di_exn, false));
         CHK(dia_gemm_rows(c, y.qkv, c->di_exn, EH, c->di_eqkv, 3 * A, n, EPI_STORE));
-        hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, 2 * ENH), dim3(64), 0, c->stream, c->di_eqkv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale,
+        hipLaunchKernelGGL(llama_rope_kv_kernel<float>, dim3(n, 2 * ENH), dim3(64), 0, c->stream, c->di_eqkv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale,
                            ENH, ENH, HD, c->di_ek, c->di_ev, (const uint32_t *) c->di_eseq, (int64_t) S * A);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(attn_gqa_kernel<128>, dim3(ENH, n), dim3(256), attn_lds, c->stream, (const float *) c->di_eqkv, 3 * A, (const uint32_t *) c->di_epos,
+        hipLaunchKernelGGL((attn_gqa_kernel<128, false, float>), dim3(ENH, n), dim3(256), attn_lds, c->stream, (const float *) c->di_eqkv, 3 * A, (const uint32_t *) c->di_epos,
                            (const float *) c->di_ek, (const float *) c->di_ev, ENH, ENH, 1.0f, c->di_eatt, (const uint32_t *) c->di_kbeg, (const uint32_t *) c->di_kend,
                            (const uint32_t *) c->di_eseq, (int64_t) S * A);
         HIPCHK(hipGetLastError());
@@ -1415,14 +1403,12 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
         const size_t esz = (size_t) c->di_kv_esz, slot_off = ((size_t) l * c->di_U + slot) * n * A * esz;   // rows 2*slot, 2*slot+1
         char *ck = (char *) c->di_ck + slot_off, *cv = (char *) c->di_cv + slot_off;
         CHK(dia_gemm_rows(c, y.ckv, c->di_exn, EH, c->di_ckv, 2 * A, n, EPI_STORE));
-        if (esz == 2) {   // the fp16 cache: the same rotation, K and V rounded once as they are stored
-            hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale, 0, NH,
-                               HD, (_Float16 *) ck, (_Float16 *) cv, (const uint32_t *) c->di_eseq, (int64_t) S * A);
-        } else {
-            hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos, (const float *) nullptr, theta_scale, 0, NH,
-                               HD, (float *) ck, (float *) cv, (const uint32_t *) c->di_eseq, (int64_t) S * A);
-        }
-        HIPCHK(hipGetLastError());
+        CHK(with_kv(c->di_kv_esz, ck, cv, [&](auto *k, auto *v) -> int {   // an fp16 cache: the same rotation, K and V rounded once as they are stored
+            hipLaunchKernelGGL(llama_rope_kv_kernel<kv_of<decltype(k)>>, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos,
+                               (const float *) nullptr, theta_scale, 0, NH, HD, k, v, (const uint32_t *) c->di_eseq, (int64_t) S * A);
+            HIPCHK(hipGetLastError());
+            return 0;
+        }));
         if ((int) sentence_len < S)
             for (int b = 0; b < 2; b++)
                 HIPCHK(hipMemsetAsync(ck + ((size_t) b * S + sentence_len) * A * esz, 0, (size_t) (S - (int) sentence_len) * A * esz, c->stream));
@@ -1466,11 +1452,8 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     const int R = 2 * U, RS = 2 * c->di_U, kv_esz = c->di_kv_esz;
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
     const float theta_scale = powf(10000.0f, -2.0f / (float) HD);
-    static std::atomic<uint64_t> attr{0}, attr16{0};
-    if ((size_t) (128 + std::max(S, G)) * 4 > 48 * 1024 && attr_needed(attr, c->device))
-        HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
-    if (kv_esz == 2 && (size_t) (128 + std::max(S, G)) * 4 > 48 * 1024 && attr_needed(attr16, c->device))
-        HIPCHK(hipFuncSetAttribute((const void *) attn_gqa_f16_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192));
+    const size_t attn_lds = (size_t) (128 + std::max(S, G)) * 4;
+    CHK(kv_esz == 2 ? attn_gqa_allow_lds<_Float16>(c, attn_lds) : attn_gqa_allow_lds<float>(c, attn_lds));
     DiaEmbedArgs ea{};
     for (int i = 0; i < NO; i++) ea.table[i] = f32(c->di_embd[i]);
     ea.ids = c->di_ids; ea.n_out = NO; ea.H = DH; ea.x = c->di_x;
@@ -1481,8 +1464,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->di_dec[(size_t) l];
         const size_t self_off = (size_t) l * RS * G * kvH * (size_t) kv_esz, cross_off = (size_t) l * RS * S * A * (size_t) kv_esz;
-        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off;
-        const float *ck = (const float *) ((const char *) c->di_ck + cross_off), *cv = (const float *) ((const char *) c->di_cv + cross_off);   // fp16 rows under kv_esz 2 (launch_attn_gqa)
+        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off, *ck = (char *) c->di_ck + cross_off, *cv = (char *) c->di_cv + cross_off;   // fp32 or fp16 rows (with_kv)
         // every projection: gemv_stream_kernel slabs folded by its consumer when the step has <= 16 rows and fp16 matrices
         // (sl = slabs written, 0 = shape does not qualify -> gemm16_kernel as before)
         int sl = 0;
@@ -1490,18 +1472,16 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         CHK(dia_rms(c, y.sa_norm, R, DH, c->di_x, c->di_xn, true));
         CHK(dia_gemm_stream(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, DIA_STREAM_SLABS, st16 * QKV, &sl));
         if (!sl) CHK(dia_gemm(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, EPI_STORE));
-        if (kv_esz == 2) {   // the fp16 cache: the same slab fold and rotation, K and V rounded once as they are appended
-            hipLaunchKernelGGL(llama_rope_kv_f16_kernel, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
-                               NKV, HD, (_Float16 *) kc, (_Float16 *) vc, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
-        } else {
-            hipLaunchKernelGGL(llama_rope_kv_kernel, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
-                               NKV, HD, (float *) kc, (float *) vc, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
-        }
-        HIPCHK(hipGetLastError());
         int slices = 0;   // key slices the attention left unmerged for the projection's staging prologue (0: di_att holds the rows)
-        CHK(launch_attn_gqa(c, NH, R, self_keys, (const float *) c->di_qkv, QKV, (const uint32_t *) c->di_pos, (const float *) kc, (const float *) vc, NKV, 1.0f,
-                            c->di_att, nul, nul, (const uint32_t *) c->di_seq, (int64_t) G * kvH, fixed_split, false, QPre{},
-                            A % 128 == 0 && stream_fold_ok(c, y.so, R, DIA_STREAM_SLABS) ? &slices : nullptr, 0, kv_esz));
+        CHK(with_kv(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {   // an fp16 cache: the same slab fold and rotation, K and V rounded once as they are appended
+            typedef kv_of<decltype(k)> KV;
+            hipLaunchKernelGGL(llama_rope_kv_kernel<KV>, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
+                               NKV, HD, k, v, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
+            HIPCHK(hipGetLastError());
+            return launch_attn_gqa<KV>(c, NH, R, self_keys, (const float *) c->di_qkv, QKV, (const uint32_t *) c->di_pos, k, v, NKV, 1.0f,
+                                       c->di_att, nul, nul, (const uint32_t *) c->di_seq, (int64_t) G * kvH, fixed_split, false, QPre{},
+                                       A % 128 == 0 && stream_fold_ok(c, y.so, R, DIA_STREAM_SLABS) ? &slices : nullptr, 0);
+        }));
         if (snap) CHK(dia_attn_snapshot(c, l, false, c->di_qkv, QKV, 1, 0, R, A, nullptr));
         CHK(dia_gemm_stream(c, y.so, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
@@ -1512,9 +1492,11 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         QPre qp;   // slab fold + rope of the cross-attention query happen as the attention workgroups load it
         qp.n_parts = std::max(sl, 1); qp.part_stride = st16 * A; qp.rope_pos = c->di_pos; qp.theta_scale = theta_scale;
         slices = 0;
-        CHK(launch_attn_gqa(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, ck, cv, NH, 1.0f, c->di_att, nul, (const uint32_t *) c->di_cend,
-                            (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
-                            A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S, kv_esz));
+        CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
+            return launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
+                                                                       (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
+                                                                       A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S);
+        }));
         if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, qp.n_parts, qp.part_stride, R, A, c->di_cend));
         CHK(dia_gemm_stream(c, y.co, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
         if (sl) c->di_pending = sl;
@@ -1735,11 +1717,11 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
         uint64_t clear = 0;
         for (int u = 0; u < U; u++) if (!c->di_slot_encoded[(size_t) u]) clear |= 1ull << u;
         if (clear) {
-            if (c->di_kv_esz == 2)
-                hipLaunchKernelGGL(dia_stream_clear_f16_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, (_Float16 *) c->di_ck, (_Float16 *) c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
-            else
-                hipLaunchKernelGGL(dia_stream_clear_kernel, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, (float *) c->di_ck, (float *) c->di_cv, clear, 2 * DU, (int64_t) S, c->di_A);
-            HIPCHK(hipGetLastError());
+            CHK(with_kv(c->di_kv_esz, c->di_ck, c->di_cv, [&](auto *ck, auto *cv) -> int {
+                hipLaunchKernelGGL(dia_stream_clear_kernel<kv_of<decltype(ck)>>, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, ck, cv, clear, 2 * DU, (int64_t) S, c->di_A);
+                HIPCHK(hipGetLastError());
+                return 0;
+            }));
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the vectors are locals
     }
