@@ -114,7 +114,8 @@ void          tts_c_set_load_options_ex(int device, int max_seqs, int declare_on
 /* the runner's tts_hip_ctx* (include/tts_hip.h: arena, profiling), or NULL when the architecture keeps several contexts */
 void         *tts_c_runner_device_context(tts_c_runner *r);
 /* bytes per element of the decoder's K/V cache as the device context reports them (Orpheus and Dia: 4, or 2 when TTS_HIP_KV_F16 was in the
- * environment at load, TTS_HIP_FLAG_KV_F16 / tts_hip_dia_desc::kv_type); 0 when the architecture does not report it */
+ * environment at load, TTS_HIP_FLAG_KV_F16 / tts_hip_dia_desc::kv_type; Orpheus alone: 1 when TTS_HIP_KV_F8 was, the e4m3 cache of
+ * tts_hip_orpheus_desc::kv_type - with both variables set the load fails, and a Parler or Dia load fails under TTS_HIP_KV_F8); 0 when the architecture does not report it */
 uint32_t      tts_c_runner_kv_element_bytes(tts_c_runner *r);
 /* utterances a continuous session of the runner holds at once (tts_generation_runner::stream_capacity: an Orpheus runner's max_seqs, at most 256;
  * 0: the runner has no session) */

@@ -91,6 +91,8 @@ typedef struct tts_hip_desc {
                                        tts_hip_create, tts_hip_t5_create, tts_hip_snac_create and tts_hip_dia_create refuse it
                                        with an error that names the flag and the call; a Dia context selects its fp16 caches
                                        through tts_hip_dia_desc::kv_type. */
+/* A value of tts_hip_orpheus_desc::kv_type (see there): the one-byte OCP e4m3fn K/V cache.  Not a ggml tensor type id, so not in enum tts_hip_type. */
+#define TTS_HIP_KV_F8_E4M3 256u
 
 typedef struct tts_hip_ctx tts_hip_ctx;
 
@@ -257,14 +259,26 @@ typedef struct tts_hip_orpheus_desc {
     uint32_t vocab_size;       /* orpheus.vocab_size (156940)  */
     uint32_t n_ctx;            /* KV positions: max_context_length + max_generation_size (1024 + 2100, :176-177) */
     float    rope_base;        /* 500000 (:190,250); 0 = that  */
-    uint32_t flags;            /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_KV_F16 (fp16 K/V cache, see the flag) */
+    uint32_t flags;            /* TTS_HIP_FLAG_VALU_GEMM | TTS_HIP_FLAG_DEQUANT_Q | TTS_HIP_FLAG_KV_F16 (fp16 K/V cache, see the flag; the e4m3 cache: kv_type below) */
     uint32_t max_seqs;         /* KV-cache slots for lock-step utterances (tts_hip_orpheus_generate_batch); 0 / 1: one sequence, as the reference's runner.
                                 * At most 256 (= the rows one decoder forward carries); tts_hip_orpheus_step_batch, generate_batch, gen_* and stream_begin[_mixed] take
                                 * up to max_seqs rows / slots.  Contexts of at most 64 slots are unchanged: same arena, same kernels.  A context of 65 .. 256
                                 * slots also plans the transposed block scales of its GGUF-quantised matrices into the arena (share_with / broadcast carry them),
                                 * and its forwards of more than 64 rows run those matrices on the LDS-tiled integer GEMM (F32 / F16 matrices: the 16-feature
                                 * kernels, correct but slow).  A slot costs n_layers * n_ctx * n_kv_heads * head_dim * 2 cache elements: 0.72 GB at 3B shapes,
-                                * 0.36 GB under TTS_HIP_FLAG_KV_F16; tts_hip_finalize fails with the slot count and the bytes it asked for when they do not fit. */
+                                * 0.36 GB under TTS_HIP_FLAG_KV_F16, 0.18 GB under kv_type = TTS_HIP_KV_F8_E4M3; tts_hip_finalize fails with the slot count and the bytes
+                                * it asked for when they do not fit. */
+    uint32_t kv_type;          /* the cache element type (extension; appended last: a desc of the size before this field is accepted and reads as 0).
+                                * 0: the flags decide, fp32 or fp16 under TTS_HIP_FLAG_KV_F16.  TTS_HIP_F16: the same as TTS_HIP_FLAG_KV_F16.
+                                * TTS_HIP_KV_F8_E4M3: the cache is [slot][layer][position][kv width] with one byte per element, OCP e4m3fn (1 sign, 4 exponent,
+                                * 3 mantissa bits, no inf) - a quarter of the fp32 cache memory and of the bytes every attention launch reads.  Rotated K and V
+                                * are rounded once, to nearest-even, when they are appended; saturation at +-448: a larger magnitude is stored as +-448;
+                                * subnormals below 2^-6 (steps of 2^-9), flush to zero below 2^-10.  All arithmetic stays fp32: query, scores, softmax and the
+                                * P.V sums run on the cache rows widened exactly.  This costs accuracy fp16 does not (three mantissa bits: DESIGN.md has the
+                                * measured logits distance); it is opt-in.  Fixed at create for every path of the context: decode, the captured step,
+                                * step_batch / generate_batch, gen_*, stream_*, and the 65 .. 256-row forwards.  Any other value is refused by name, as is
+                                * TTS_HIP_KV_F8_E4M3 together with TTS_HIP_FLAG_KV_F16.  Dia and Parler contexts have no fp8 cache: tts_hip_dia_create refuses
+                                * every kv_type but TTS_HIP_F32 / TTS_HIP_F16, tts_hip_create reads anything but TTS_HIP_F16 as fp32. */
 } tts_hip_orpheus_desc;
 tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus_desc *desc);
 /* n tokens at positions pos0 .. pos0+n-1 (KV cache appended); logits_out [vocab_size] of the LAST token (:287-290).
@@ -672,7 +686,8 @@ int tts_hip_dac_decode_windows(tts_hip_ctx *ctx, const uint32_t *codes, const ui
  * [C][tokens * rate] after the stage of the last pass, orc_snac_decode's numbering: 0 = the summed codebook levels, 1 = after
  * the input depthwise conv and the `up` conv, 2 + i = the end of block i, 2 + n_blocks = the PCM before the crop; requires
  * tts_hip_set_debug(ctx,1) before the decode); Orpheus contexts: "l_logits" (the logits row the last
- * step left), "l_k:<layer>[:<slot>]" / "l_v:<layer>[:<slot>]" (a cache slot of a layer, [n_ctx][kv width]; slot 0 by default), and of the
+ * step left), "l_k:<layer>[:<slot>]" / "l_v:<layer>[:<slot>]" (a cache slot of a layer, [n_ctx][kv width]; slot 0 by default; an fp16 or e4m3 cache
+ * comes back widened to fp32, exact), "l_kv_elem" (the cache element size in bytes: 4, 2 or 1), and of the
  * last layer of the last forward — these buffers outlive it, a captured step included — "l_q" (the rotated queries the attention
  * kernel read) and "l_att" (the rows it left), both [rows][heads * head_dim] with rows = max_floats / (heads * head_dim), "l_pos" (the
  * rows' positions as floats; a captured step's selection has already advanced row 0 by one).

@@ -408,7 +408,7 @@ __device__ __forceinline__ void stage_rms_q8(RmsRow &first, const RmsSrc &rs, in
 }
 
 // KV: the cache element type (llama_kernels.h).  Over an fp16 cache lane 0 rounds the rotated key and the value once, to nearest-even, as it stores them
-// (q stays fp32).
+// (q stays fp32); over an e4m3 cache (kv_f8) it clamps to +-448 and rounds once the same way, a byte store.
 template <typename KV>
 struct RopeEpi {
     const uint32_t *pos;   // [R]

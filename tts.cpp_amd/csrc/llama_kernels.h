@@ -7,7 +7,8 @@
 //   attn_gqa_kernel        mul_mat(k, q) -> soft_max_ext(causal, 1/sqrt(d)) -> mul_mat(kq, v), kv head = q head / rep :228-259
 //   KV                     the cache element type, float or _Float16 (extension: TTS_HIP_FLAG_KV_F16 for Orpheus, tts_hip_dia_desc::kv_type for Dia), is a
 //                          template parameter of the cache's writer and readers: llama_rope_kv_kernel<KV>, attn_gqa_kernel<HD, SPLIT, KV>,
-//                          attn_gqa_wave_kernel<HD, U, EXT, KV>.  KVRow<KV> holds what depends on it (row vector, loads, widening, EXT slot count)
+//                          attn_gqa_wave_kernel<HD, U, EXT, KV>.  KVRow<KV> holds what depends on it (row vector, loads, widening, EXT slot count).
+//                          kv_f8 (OCP e4m3fn, one byte; tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3) is the Llama decoder's alone: no EXT form
 //   silu_mul_kernel        silu(gate x) * (up x) :279
 //   argmax_parts/fold      sampler::max over the 156 940-logit vocabulary, two stages
 #pragma once
@@ -215,6 +216,19 @@ static __global__ __launch_bounds__(256) void rms_fold_rows_q8t_kernel(float *x,
     }
 }
 
+// One-byte cache element: OCP e4m3fn (1 sign, 4 exponent, 3 mantissa bits, bias 7: largest finite 448, subnormals below 2^-6 in steps of 2^-9, no inf).
+// The writers convert with `(KV) y`, as they do for _Float16: clamped to +-448 here (what v_cvt_pk_fp8_f32 does above 448 depends on a mode bit the
+// kernels do not own), then rounded to nearest-even by the hardware conversion.  Readers widen exactly (KVRow<kv_f8>).
+struct kv_f8 {
+    uint8_t b;
+    kv_f8() = default;
+    explicit __device__ __forceinline__ kv_f8(float x) {
+        const float c = fminf(fmaxf(x, -448.0f), 448.0f);
+        b = (uint8_t) __builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false);
+    }
+};
+static_assert(sizeof(kv_f8) == 1, "a cache row of kv_f8 is one byte per element");
+
 // qkv [R][(NH + 2 NKV) * HD] (q | k | v).  One wave per (row, q or k head); lane = pair i (and i + 64, ... for HD > 128).
 // theta walks pos, pos*s, (pos*s)*s, ... in fp32 exactly like ggml_rope_cache_init (theta *= theta_scale), theta_scale =
 // powf(base, -2/HD) from the host; angle = theta / freq_factor[i]; NEOX pairing (i, i + HD/2).  The k-head waves write the
@@ -371,7 +385,8 @@ __device__ __forceinline__ void attn_q_finish(float *qs, const QRaw &qr, const f
 // The cache element type KV is float or _Float16; KVRow<KV> holds everything that depends on it.  Over an fp16 cache a key row of one kv head is 256
 // contiguous bytes instead of 512; lane -> dims, key -> lane group and the order of every sum are the same for both types, applied to the rows widened
 // to fp32 (exact): a lane's 4-dim pieces are 8-byte loads, kept as fp16 while they are in flight — the rows in flight take half the registers — and
-// widened where they are consumed.  Query, scores, softmax, accumulators and the partials are fp32 either way.
+// widened where they are consumed.  Query, scores, softmax, accumulators and the partials are fp32 either way.  kv_f8 (e4m3, Orpheus only) is the third
+// type under the same mapping and sums: 128 bytes per key row, 4-byte loads.
 typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 template <typename KV> struct KVRow;
 template <> struct KVRow<float> {
@@ -394,6 +409,18 @@ template <> struct KVRow<_Float16> {
     static __device__ __forceinline__ vec4 load(const void *a) { return *(const half4v *) a; }
     static __device__ __forceinline__ vec4 load_nt(const void *a) { return __builtin_nontemporal_load((const half4v *) a); }
     static __device__ __forceinline__ float4 widen(vec4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); }
+};
+// e4m3 rows (the Llama decoder's cache only): a key row of one kv head is 128 contiguous bytes, a lane's 4-dim piece one 4-byte load, kept packed while it
+// is in flight (a quarter of the fp32 form's registers) and widened by two v_cvt_pk_f32_fp8 (bytes 0-1, bytes 2-3; exact) where it is consumed.
+template <> struct KVRow<kv_f8> {
+    typedef uint32_t vec4;
+    static constexpr int EXT_SLOTS = 0;   // no EXT form over this type (Dia has no fp8 cache): the host never names one
+    static __device__ __forceinline__ vec4 load(const void *a) { return *(const uint32_t *) a; }
+    static __device__ __forceinline__ vec4 load_nt(const void *a) { return __builtin_nontemporal_load((const uint32_t *) a); }
+    static __device__ __forceinline__ float4 widen(vec4 w) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int) w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int) w, true);
+        return make_float4(lo[0], lo[1], hi[0], hi[1]);
+    }
 };
 
 template <int HD, typename KV>

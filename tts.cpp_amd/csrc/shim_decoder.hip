@@ -1133,7 +1133,7 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         while (F / c->l_ksplit > 4096 || (F % c->l_ksplit)) c->l_ksplit++;
         if ((F / c->l_ksplit) % 256) c->l_ksplit = 1;
         const size_t S = std::max<uint32_t>(1, c->lm.max_seqs);                 // cache slots of lock-step utterances; [slot][layer][position][kv width]
-        const size_t kvb = S * c->L * NCTX * c->l_kvH * (size_t) c->l_kv_esz;   // bytes: half of them under TTS_HIP_FLAG_KV_F16
+        const size_t kvb = S * c->L * NCTX * c->l_kvH * (size_t) c->l_kv_esz;   // bytes: half of them under TTS_HIP_FLAG_KV_F16, a quarter under TTS_HIP_KV_F8_E4M3
         c->attn_part_cap = (size_t) 4 * c->NH * 16;   // up to 4 rows x heads x 16 splits (more rows take the unsplit kernel)
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
         CHK(dmalloc(&c->attn_cnt, (size_t) 256 + c->NH));   // arrival counters of the split attention's in-kernel merge (rows x heads <= 256)
@@ -1141,7 +1141,7 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         if (hipMalloc((void **) &c->l_kc, kvb) != hipSuccess || hipMalloc((void **) &c->l_vc, kvb) != hipSuccess) {
             (void) hipGetLastError();
             return set_err("tts_hip_finalize: the K/V cache of %zu slots does not fit: 2 x %zu bytes asked for (%s; fewer slots, or TTS_HIP_KV_F16 halves it)", S, kvb,
-                           c->l_kv_esz == 2 ? "fp16 cache" : "fp32 cache");
+                           c->l_kv_esz == 1 ? "fp8 e4m3 cache" : c->l_kv_esz == 2 ? "fp16 cache" : "fp32 cache");
         }
         HIPCHK(hipMemset(c->l_kc, 0, kvb));
         HIPCHK(hipMemset(c->l_vc, 0, kvb));
@@ -2564,10 +2564,20 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
             for (size_t i = 0; i < n; i++) out[i] = (float) h[i];
             return (int64_t) n;
         }
+        if (c->l_kv_esz == 1) {   // the e4m3 cache: the bytes decoded on the host (exact: every finite e4m3 number is an fp32 number)
+            std::vector<uint8_t> h(n);
+            if (hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) {
+                const int e = (h[i] >> 3) & 15, m = h[i] & 7;
+                const float mag = e == 15 && m == 7 ? NAN : e ? ldexpf((float) (8 + m), e - 10) : ldexpf((float) m, -9);   // bias 7, 3 mantissa bits; subnormals m * 2^-9
+                out[i] = (h[i] & 128) ? -mag : mag;
+            }
+            return (int64_t) n;
+        }
         if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
-    if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, or 2 under TTS_HIP_FLAG_KV_F16
+    if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, 2 under TTS_HIP_FLAG_KV_F16, 1 under TTS_HIP_KV_F8_E4M3
         if (max_floats < 1) { set_err("debug_read(l_kv_elem): buffer too small"); return -1; }
         out[0] = (float) c->l_kv_esz;
         return 1;

@@ -177,7 +177,7 @@ struct tts_hip_ctx {
     int l_V = 0, l_Vpad = 0, l_kvH = 0, l_ksplit = 1;
     float *l_x = nullptr, *l_xn = nullptr, *l_qkv = nullptr, *l_att = nullptr, *l_gu = nullptr, *l_g = nullptr, *l_logits = nullptr, *l_parts = nullptr;
     void *l_kc = nullptr, *l_vc = nullptr;   // [slot][layer][position][kv width] of l_kv_esz bytes per element
-    int l_kv_esz = 4;                        // 2 under TTS_HIP_FLAG_KV_F16 (fixed at create: the captured graphs never see it change)
+    int l_kv_esz = 4;                        // 2 under TTS_HIP_FLAG_KV_F16, 1 under kv_type = TTS_HIP_KV_F8_E4M3 (fixed at create: the captured graphs never see it change)
     uint32_t *l_ids = nullptr, *l_pos = nullptr, *l_tok = nullptr;
     uint32_t *l_seq = nullptr, *l_btok = nullptr, *l_bpi = nullptr;   // lock-step utterances: row -> cache slot, selected tokens [rows], arg-max partials
     float *l_bpv = nullptr;

@@ -11,8 +11,25 @@
 
 // Orpheus decoder (src/models/orpheus/model.cpp:186-325)
 // ------------------------------------------------------------------------------------------------
-extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus_desc *ld) {
-    if (!ld || ld->struct_size != sizeof(tts_hip_orpheus_desc)) { set_err("tts_hip_orpheus_create: bad desc (struct_size mismatch)"); return nullptr; }
+extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus_desc *ld_in) {
+    // a desc of the size before kv_type was appended (callers built against that header) reads as kv_type = 0; every other size is refused
+    constexpr size_t size_before_kv_type = offsetof(tts_hip_orpheus_desc, kv_type);
+    if (!ld_in || (ld_in->struct_size != sizeof(tts_hip_orpheus_desc) && ld_in->struct_size != size_before_kv_type)) {
+        set_err("tts_hip_orpheus_create: bad desc (struct_size mismatch)");
+        return nullptr;
+    }
+    tts_hip_orpheus_desc full{};
+    memcpy(&full, ld_in, ld_in->struct_size);
+    full.struct_size = sizeof(full);
+    const tts_hip_orpheus_desc *ld = &full;
+    if (ld->kv_type != 0 && ld->kv_type != TTS_HIP_F16 && ld->kv_type != TTS_HIP_KV_F8_E4M3) {
+        set_err("tts_hip_orpheus_create: kv_type %u is none of 0 (the flags decide), TTS_HIP_F16 (1) and TTS_HIP_KV_F8_E4M3 (256)", ld->kv_type);
+        return nullptr;
+    }
+    if (ld->kv_type == TTS_HIP_KV_F8_E4M3 && (ld->flags & TTS_HIP_FLAG_KV_F16)) {
+        set_err("tts_hip_orpheus_create: kv_type TTS_HIP_KV_F8_E4M3 together with TTS_HIP_FLAG_KV_F16: one cache element type per context");
+        return nullptr;
+    }
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = ld->hidden_size; d.n_layers = ld->n_layers; d.n_attn_heads = ld->n_attn_heads; d.max_ctx_length = ld->n_ctx;
@@ -22,7 +39,8 @@ extern "C" tts_hip_ctx *tts_hip_orpheus_create(int device, const tts_hip_orpheus
     if (!c) return nullptr;
     c->has_llama = true;
     c->lm = *ld;
-    if (ld->flags & TTS_HIP_FLAG_KV_F16) c->l_kv_esz = 2;
+    if ((ld->flags & TTS_HIP_FLAG_KV_F16) || ld->kv_type == TTS_HIP_F16) c->l_kv_esz = 2;
+    if (ld->kv_type == TTS_HIP_KV_F8_E4M3) c->l_kv_esz = 1;
     if (c->lm.max_seqs == 0) c->lm.max_seqs = 1;
     // up to 64 slots: the streaming kernels carry every step.  65 .. 256 (= RMAX, the rows of one forward): the steps of more than 64 rows run on the
     // LDS-tiled integer GEMM (llama_forward); such a context plans the transposed scale tables into its arena
@@ -46,6 +64,12 @@ template <typename P> using kv_of = std::remove_pointer_t<P>;
 template <typename F>
 static int with_kv(int kv_esz, void *kc, void *vc, F &&f) {
     return kv_esz == 2 ? f((_Float16 *) kc, (_Float16 *) vc) : f((float *) kc, (float *) vc);
+}
+// The Llama forward's dispatch: the same, plus 1: e4m3 (tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3).  Dia's call sites stay on with_kv: no Dia writer
+// and no EXT reader is built for kv_f8.
+template <typename F>
+static int with_kv_llama(int kv_esz, void *kc, void *vc, F &&f) {
+    return kv_esz == 1 ? f((kv_f8 *) kc, (kv_f8 *) vc) : with_kv(kv_esz, kc, vc, f);
 }
 
 // attn_gqa_kernel<128, false, KV> with more than 48 KB of scores: the attribute once per instantiation and device
@@ -82,14 +106,21 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
     if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
         // the captured one-row step (Orpheus): every key row requested at kernel start, online softmax per 16-lane group, one barrier (attn_gqa_wave_kernel)
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4, false, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
-    } else if (c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8) {
-        // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through KVRow<KV>::EXT_SLOTS
-        // rolling register slots (the parked rows of a loop step, kend[r] = 1, request that one key only)
-        hipLaunchKernelGGL((attn_gqa_wave_kernel<128, KVRow<KV>::EXT_SLOTS, true, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
-                           n_ctx_keys, kend, row_seq, seq_stride, qp);
     } else {
-        hipLaunchKernelGGL((attn_gqa_kernel<128, true, KV>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part,
-                           kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
+        bool ext = false;
+        if constexpr (KVRow<KV>::EXT_SLOTS > 0) {   // (kv_f8, the Llama decoder's alone, has no EXT form: nothing of it is built)
+            ext = c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8;
+            // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through KVRow<KV>::EXT_SLOTS
+            // rolling register slots (the parked rows of a loop step, kend[r] = 1, request that one key only)
+            if (ext) {
+                hipLaunchKernelGGL((attn_gqa_wave_kernel<128, KVRow<KV>::EXT_SLOTS, true, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale,
+                                   c->attn_part, n_ctx_keys, kend, row_seq, seq_stride, qp);
+            }
+        }
+        if (!ext) {
+            hipLaunchKernelGGL((attn_gqa_kernel<128, true, KV>), dim3(nz, rows, NHq), dim3(256), (size_t) (128 + chunk + 1) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale,
+                               c->attn_part, kbeg, kend, row_seq, seq_stride, qp, (int8_t *) nullptr, (float *) nullptr);
+        }
     }
     HIPCHK(hipGetLastError());
     if (deferred && c->attn_fold && nz == ATTN_FOLD_NZ && !c->prof && !c->debug) {
@@ -212,13 +243,14 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     };
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->l_layers[l];
-        // this layer of slot 0: fp32 rows, or fp16 rows under TTS_HIP_FLAG_KV_F16 (with_kv: the cache's writer and readers below are launched for that type)
+        // this layer of slot 0: fp32 rows, fp16 rows under TTS_HIP_FLAG_KV_F16 or e4m3 bytes under kv_type = TTS_HIP_KV_F8_E4M3 (with_kv_llama: the cache's writer and
+        // readers below are launched for that type)
         const size_t layer_off = (size_t) l * NCTX * c->l_kvH * (size_t) c->l_kv_esz;
         const size_t qkv_lds = (size_t) n * H + (size_t) n * (H / 32) * 4;
         const bool qkv_fused = !row_seq && n <= 4 && c->q4_rope && c->q4_lds && y.qkv.q4 && q_for(y.qkv, n, QS_QKV) && HD == 128 && H % 512 == 0 && qkv_lds <= 64 * 1024 && !c->prof;
         // the rms norm inside the consuming projection's staging (stage_rms_q8): no slabs may be pending, the row is held in registers
         const bool rms_fused = c->q4_rms && !c->l_pending && H <= 4096;
-        CHK(with_kv(c->l_kv_esz, (char *) c->l_kc + layer_off, (char *) c->l_vc + layer_off, [&](auto *kc, auto *vc) -> int {
+        CHK(with_kv_llama(c->l_kv_esz, (char *) c->l_kc + layer_off, (char *) c->l_vc + layer_off, [&](auto *kc, auto *vc) -> int {
             typedef kv_of<decltype(kc)> KV;
             const RopeEpi<KV> re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
             if (qkv_fused && rms_fused) {

@@ -15,6 +15,7 @@ MAX_DAC_BLOCKS = 8
 
 FLAG_NO_GRAPH, FLAG_VALU_GEMM, FLAG_NO_DAC, FLAG_NO_PARLER, FLAG_DEQUANT_Q, FLAG_DAC_F32 = 1, 2, 4, 8, 16, 32
 FLAG_KV_F16 = 64   # OrpheusEngine(flags=...) only: fp16 K/V cache (TTS_HIP_FLAG_KV_F16); every other engine refuses it
+KV_F8_E4M3 = 256   # OrpheusEngine(kv_type=...) only: one-byte OCP e4m3fn K/V cache (TTS_HIP_KV_F8_E4M3, tts_hip_orpheus_desc::kv_type)
 KCLASSES = ["embed", "ln", "gemm_qkv", "attn_self", "gemm_attn_out", "gemm_cross_q", "attn_cross", "gemm_cross_out", "gemm_fc1",
             "gemm_fc2", "gemm_heads", "sample", "gemm_other", "dac_embed", "dac_conv7", "dac_conv1", "dac_convt", "dac_final", "dac_resunit", "kokoro_conv_mfma"]
 
@@ -55,7 +56,7 @@ class OrpheusDesc(C.Structure):
     """tts_hip_orpheus_desc (include/tts_hip.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("hidden_size", C.c_uint32), ("n_layers", C.c_uint32), ("n_attn_heads", C.c_uint32),
                 ("n_kv_heads", C.c_uint32), ("head_dim", C.c_uint32), ("vocab_size", C.c_uint32), ("n_ctx", C.c_uint32),
-                ("rope_base", C.c_float), ("flags", C.c_uint32), ("max_seqs", C.c_uint32)]
+                ("rope_base", C.c_float), ("flags", C.c_uint32), ("max_seqs", C.c_uint32), ("kv_type", C.c_uint32)]
 
 
 class DiaDesc(C.Structure):
@@ -811,14 +812,16 @@ class SnacEngine:
 class OrpheusEngine:
     """An Orpheus decoder context (tts_hip_orpheus_create): Llama-3 blocks, one sequence or max_seqs lock-step utterances."""
 
-    def __init__(self, cfg, device=0, flags=0, max_seqs=1):
+    def __init__(self, cfg, device=0, flags=0, max_seqs=1, kv_type=0):
+        """kv_type (tts_hip_orpheus_desc::kv_type): 0 = the flags decide (fp32, or fp16 under FLAG_KV_F16), gguf.F16 = the same as FLAG_KV_F16,
+        KV_F8_E4M3 = the one-byte e4m3 cache (rounded once as appended, saturating at +-448; a quarter of the fp32 cache's memory)"""
         self.L = load_lib()
         self.cfg = cfg
         d = OrpheusDesc()
         d.struct_size = C.sizeof(OrpheusDesc)
         d.hidden_size, d.n_layers, d.n_attn_heads, d.n_kv_heads, d.head_dim = cfg.hidden, cfg.layers, cfg.heads, cfg.kv_heads, cfg.head_dim
         d.vocab_size, d.n_ctx, d.rope_base, d.flags = cfg.vocab, cfg.ctx, 0.0, flags
-        d.max_seqs = max_seqs
+        d.max_seqs, d.kv_type = max_seqs, kv_type
         self._stream = (max(1, max_seqs), 0)   # (slots, max_new) of the continuous session
         self.ctx = self.L.tts_hip_orpheus_create(device, C.byref(d))
         if not self.ctx:
@@ -833,8 +836,8 @@ class OrpheusEngine:
         self._chk(self.L.tts_hip_set_debug(self.ctx, 1 if on else 0))
 
     def debug_read(self, what, max_floats):
-        """'l_logits': the logits row the last step left; 'l_k:<layer>[:<slot>]' / 'l_v:...': a cache slot's rows of a layer (an fp16 cache widened
-        exactly); 'l_kv_elem': the cache element size in bytes (4, or 2 under FLAG_KV_F16); last layer of the last
+        """'l_logits': the logits row the last step left; 'l_k:<layer>[:<slot>]' / 'l_v:...': a cache slot's rows of a layer (an fp16 or
+        e4m3 cache widened exactly); 'l_kv_elem': the cache element size in bytes (4, 2 under FLAG_KV_F16, 1 under kv_type=KV_F8_E4M3); last layer of the last
         forward: 'l_q' the rotated queries the attention read and 'l_att' the rows it left ([rows][heads * 128], rows = max_floats // width), 'l_pos'
         the rows' positions (after a captured step: already moved on by one) (test / debugging aid)"""
         out = np.empty(max_floats, dtype=np.float32)

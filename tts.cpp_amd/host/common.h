@@ -105,7 +105,7 @@ struct tts_generation_runner : tts_runner {
     // the device context (tts_hip_ctx*) that holds this runner's weight arena, or nullptr when the runner cannot hand its weights to
     // another runner (tts_load_options::share_with / tts_hip_broadcast_weights)
     virtual void *   device_context() const { return nullptr; }
-    // bytes per element of the decoder's K/V cache as its device context reports them (orpheus_runner: 4, or 2 when TTS_HIP_KV_F16 was set at load);
+    // bytes per element of the decoder's K/V cache as its device context reports them (orpheus_runner: 4, 2 when TTS_HIP_KV_F16 or 1 when TTS_HIP_KV_F8 was set at load);
     // 0: the runner does not report it
     virtual uint32_t kv_element_bytes() const { return 0; }
 

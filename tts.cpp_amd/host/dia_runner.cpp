@@ -72,6 +72,8 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : stream_session{dia
     d.max_ctx = hp.max_encoder_context_length; d.max_gen = hp.max_generation_size; d.cfg_scale = hp.cfg_scale;
     max_seqs = tts_load_max_seqs();
     d.max_utterances = max_seqs;
+    // the fp8 cache is the Orpheus decoder's alone: a silent fp32 cache here would be worse than a failed load
+    if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("dia: TTS_HIP_KV_F8 is set, and a Dia decoder has no fp8 K/V caches (TTS_HIP_KV_F16 selects its fp16 ones)\n");
     if (getenv("TTS_HIP_KV_F16")) d.kv_type = TTS_HIP_F16;   // the switch the Parler and Orpheus runners read: fp16 self and cross K/V caches (extension, include/tts_hip.h)
     lm = tts_hip_dia_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_dia_create failed: %s\n", tts_hip_last_error());

@@ -77,12 +77,15 @@ orpheus_runner::orpheus_runner(const orpheus_hparams & hp_, bpe_tokenizer * tok,
     d.hidden_size = hp.hidden_size; d.n_layers = hp.n_layers; d.n_attn_heads = hp.n_attn_heads; d.n_kv_heads = hp.n_kv_attn_heads;
     d.head_dim = hp.head_size; d.vocab_size = hp.vocab_size;
     d.n_ctx = hp.max_context_length + hp.max_generation_size;   // orpheus_kv_cache_init, model.cpp:176-177
-    // up to 256 slots = the rows one decoder forward carries (tts_hip_orpheus_create); at 3B shapes a slot of the cache is 0.72 GB, 0.36 GB under TTS_HIP_KV_F16
+    // up to 256 slots = the rows one decoder forward carries (tts_hip_orpheus_create); at 3B shapes a slot of the cache is 0.72 GB, 0.36 GB under TTS_HIP_KV_F16, 0.18 GB under TTS_HIP_KV_F8
     const uint32_t asked = std::max<uint32_t>(1, tts_load_max_seqs());
     max_seqs = std::min<uint32_t>(asked, 256);
     if (max_seqs != asked) fprintf(stderr, "orpheus: max_seqs %u exceeds what one decoder forward carries: loading with %u slots\n", asked, max_seqs);
     d.max_seqs = max_seqs;
+    // both read once, here: the cache element type is fixed at create
+    if (getenv("TTS_HIP_KV_F16") && getenv("TTS_HIP_KV_F8")) TTS_ABORT("orpheus: TTS_HIP_KV_F16 and TTS_HIP_KV_F8 are both set: one K/V cache element type per runner\n");
     if (getenv("TTS_HIP_KV_F16")) d.flags |= TTS_HIP_FLAG_KV_F16;   // the switch Parler's runner reads: fp16 K/V cache (extension, include/tts_hip.h)
+    if (getenv("TTS_HIP_KV_F8")) d.kv_type = TTS_HIP_KV_F8_E4M3;    // one-byte e4m3 K/V cache (extension, tts_hip_orpheus_desc::kv_type)
     lm = tts_hip_orpheus_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_orpheus_create failed: %s\n", tts_hip_last_error());
     tts_hip_snac_desc s{};

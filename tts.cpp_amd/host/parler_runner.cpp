@@ -84,6 +84,8 @@ parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok
         }
         declare_only = lo.declare_only || share_ctx != nullptr;
     }
+    // the fp8 cache is the Orpheus decoder's alone: a silent fp32 cache here would be worse than a failed load
+    if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("parler: TTS_HIP_KV_F8 is set, and a Parler decoder has no fp8 K/V cache (TTS_HIP_KV_F16 selects its fp16 one)\n");
     d.kv_type = getenv("TTS_HIP_KV_F16") ? TTS_HIP_F16 : TTS_HIP_F32;
     d.gelu_mode = 1;
     // one utterance: the reference layout (max_ctx_length positions, model.cpp:368-369); lock-step batches keep only

@@ -280,7 +280,8 @@ class Runner:
         return self.L.tts_c_runner_device_context(self.h)
 
     def kv_element_bytes(self):
-        """bytes per element of the decoder's K/V cache (Orpheus: 4, or 2 with TTS_HIP_KV_F16 in the environment at load); 0: not reported"""
+        """bytes per element of the decoder's K/V cache (Orpheus: 4, 2 with TTS_HIP_KV_F16 or 1 with TTS_HIP_KV_F8 (the e4m3 cache) in the environment
+        at load; both set: the load fails); 0: not reported"""
         return int(self.L.tts_c_runner_kv_element_bytes(self.h))
 
     def stream_capacity(self):

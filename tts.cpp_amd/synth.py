@@ -561,6 +561,8 @@ class OrpheusConfig:
     ctx: int = 96             # max_context_length + max_generation_size positions of KV cache
     weight_type: int = gguf.F32
     seed: int = 0x0A9
+    kv_gain: float = 1.0      # factor on layer 0's k_proj / v_proj (1: the tensors as they always were, bit for bit); large values drive K and V past
+                              # the range of a narrow cache element type (the e4m3 cache saturates at 448)
 
 
 def orpheus_tiny(**kw):
@@ -630,11 +632,17 @@ class SynthOrpheus:
                 self.tensors.append(gguf.Tensor.from_array("orpheus." + name, arr, ttype))
 
         add("embed_tokens", normal((cfg.vocab, H), 1.0))
+        def gained(m, g):   # the same draws, scaled
+            if g == 1.0:
+                return m
+            return _Lazy(m.shape, m.std * g) if isinstance(m, _Lazy) else m * np.float32(g)
+
         for l in range(cfg.layers):
             p = f"layers.{l}."
+            g = cfg.kv_gain if l == 0 else 1.0
             add(p + "self_attn.q_proj", normal((cfg.heads * cfg.head_dim, H), 1.0 / math.sqrt(H)))
-            add(p + "self_attn.k_proj", normal((kvH, H), 1.0 / math.sqrt(H)))
-            add(p + "self_attn.v_proj", normal((kvH, H), 1.0 / math.sqrt(H)))
+            add(p + "self_attn.k_proj", gained(normal((kvH, H), 1.0 / math.sqrt(H)), g))
+            add(p + "self_attn.v_proj", gained(normal((kvH, H), 1.0 / math.sqrt(H)), g))
             add(p + "self_attn.o_proj", normal((H, cfg.heads * cfg.head_dim), 1.0 / math.sqrt(H)))
             add(p + "mlp.gate_proj", normal((F, H), 1.0 / math.sqrt(H)))
             add(p + "mlp.up_proj", normal((F, H), 1.0 / math.sqrt(H)))
