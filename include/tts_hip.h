@@ -422,7 +422,13 @@ typedef struct tts_hip_dia_desc {
                                    eagerly instead of as replays of one captured graph; the same launches once max_gen reaches
                                    128 x the self-attention's key splits, 1024 by default) */
     uint32_t max_utterances;    /* extension: utterances decoded in lock-step (each is the reference's batch of 2 guidance streams,
-                                   dia/model.cpp:330-341); 0 = 1.  Rows of a step = 2 x utterances */
+                                   dia/model.cpp:330-341); 0 = 1.  Rows of a step = 2 x utterances.  At most 128 (one decoder forward
+                                   carries 256 rows): tts_hip_dia_create refuses more with an error that names it and max_utterances.
+                                   Up to 64 slots every step launches the streaming kernels (<= 16 rows) or the 16-feature GEMM;
+                                   on a context of 65 .. 128 slots a step of more than 16 rows runs fp16 matrices (K % 128 == 0,
+                                   N % 16 == 0, no TTS_HIP_FLAG_VALU_GEMM) on the LDS-tiled MFMA GEMM — tts_hip_tune
+                                   "dia_tile_min_rows" below.  One slot of Dia-1.6B is 1.06 GB of caches (0.53 GB with kv_type =
+                                   TTS_HIP_F16); caches that do not fit fail tts_hip_finalize with the slot count and the bytes */
     uint32_t kv_type;           /* extension (the reference keeps fp32 K/V, dia/model.cpp:329): TTS_HIP_F32 (0, so a zeroed desc) or
                                    TTS_HIP_F16: the self cache [layer][row slot][max_gen][kv width] and the cross cache
                                    [layer][row slot][max_ctx][heads * head_dim] are kept in fp16 — half the cache memory
@@ -865,7 +871,17 @@ int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs
  *   kokoro_split        0: those split products as three bf16 planes (six products) instead of fp16 hi + lo (three)
  *   kokoro_attn_lds     0: ALBERT's attention as one wave per (head, row) instead of keys staged through LDS
  *   kokoro_lstm_split   0: each LSTM direction in one workgroup instead of hid / 16 workgroups exchanging their hidden state
- *   kokoro_adain_split  0: instance-norm rows of 8192 positions and more in one workgroup per channel instead of slices over workgroups */
+ *   kokoro_adain_split  0: instance-norm rows of 8192 positions and more in one workgroup per channel instead of slices over workgroups
+ * Dia contexts:
+ *   dia_tile_min_rows   decoder steps of at least this many rows, and more than 16, run fp16 matrices on the LDS-tiled MFMA GEMM (every
+ *                       matrix and the heads F16 with K % 128 == 0 and N % 16 == 0, no TTS_HIP_FLAG_VALU_GEMM); 0 = never.  Default 0 on a
+ *                       context of at most 64 utterance slots, 17 on a larger one.  tts_hip_debug_read("di_tiled") returns the tiled GEMM
+ *                       launches of the last forward (0 on the other routes), "di_pending_max" the most K-slice slabs one GEMM left.
+ *                       Like every key it is read when a step is issued: a loop graph captured before the call keeps replaying the route
+ *                       it was captured with (set it before the first tts_hip_dia_generate / gen_* / stream_* of the context); the same
+ *                       holds for tile_force and tile_ks.  The decoder must be at most 2048 wide for the route
+ *   tile_force, tile_ks tile shape index (0..5, -1 = the cost model's) and K slices of the residual GEMMs (0 = the cost model's) of every
+ *                       tiled GEMM: tests and tuning */
 int tts_hip_tune(tts_hip_ctx *ctx, const char *key, int value);
 
 /* stream / device handles for callers that need to order their own work (torch interop) */

@@ -16,7 +16,7 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-UNITS = ["shim_core", "shim_decoder", "shim_codec", "shim_llama", "shim_qtile"]
+UNITS = ["shim_core", "shim_decoder", "shim_codec", "shim_llama", "shim_qtile", "shim_dia_rows"]
 # per-unit code-generation switches (the reasons are in the unit's header comment)
 UNIT_FLAGS = {"shim_qtile": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 

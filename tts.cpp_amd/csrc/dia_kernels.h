@@ -218,7 +218,7 @@ static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitAr
 // grid (ceil(A / 256), 2 * n_slots, L)
 template <typename KV>
 __global__ __launch_bounds__(256) void dia_stream_clear_kernel(KV *ck, KV *cv, uint64_t clear, int rows, int64_t S, int A) {
-    const int e = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, l = blockIdx.z;   // clear: bit u = slot u (a context has at most 64)
+    const int e = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, l = blockIdx.z;   // clear: bit u = slot u of the launch's group of 64 (ck / cv start at the group's first row)
     if (e >= A || !((clear >> (r >> 1)) & 1)) return;
     const int64_t at = ((int64_t) l * rows + r) * S * A + e;
     ck[at] = (KV) 0.0f;

@@ -191,8 +191,10 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "attn_wave") c->attn_wave = v != 0;
     else if (k == "cross_fold") c->cross_fold = v != 0;
     else if (k == "tile_min_rows") c->tile_min_rows = std::max(0, v);
+    else if (k == "dia_tile_min_rows") { c->dia_tile_min_rows = std::max(0, v); if (c->finalized) CHK(dia_tiled_buffers(c)); }   // Dia decoder steps of at least this many rows (and more than 16) on gemm_tile_kernel; 0: never
     else if (k == "tile_deep") c->tile_deep = v;
     else if (k == "tile_force") c->tile_force = v;               // as TTS_HIP_TILE_FORCE: tile shape index of every tiled GEMM, -1 = the cost model's
+    else if (k == "tile_ks") c->tile_force_ks = std::max(0, std::min(8, v));   // as TTS_HIP_TILE_KS: k slices of the residual tiled GEMMs where K allows them (the slab buffers hold 8), 0 = the cost model's
     else if (k == "tile_pair") {   // the forms launch_tile_shape holds
         if (v < -1 || v > 2) return set_err("tts_hip_tune: tile_pair is -1 (by arena sharing), 0, 1 or 2 (got %d)", v);
         c->tile_pair = v;
@@ -278,6 +280,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
                      c->di_xn, c->di_qkv, c->di_q, c->di_att, c->di_gu, c->di_g, c->di_parts, c->di_logits, c->di_guided})
         free_dev(p);
     free_dev(c->di_ck); free_dev(c->di_cv); free_dev(c->di_k); free_dev(c->di_v);   // fp32 or fp16 (di_kv_esz)
+    free_dev(c->di_h16);
     for (uint32_t *p : {c->di_tok, c->di_epos, c->di_eseq, c->di_kbeg, c->di_kend, c->di_ids, c->di_pos, c->di_seq, c->di_cend, c->di_stok, c->di_loop, c->di_hist, c->di_look, c->di_sbud, c->di_sadm}) free_dev(p);
     free_dev(c->di_suni);
     free_dev(c->di_srec); free_dev(c->di_srec_in); free_dev(c->di_spen); free_dev(c->di_spen_in);

@@ -187,6 +187,7 @@ static int launch_tile_form(tts_hip_ctx *c, const GemmArgs &a, const TileMap &tm
         HIPCHK(hipFuncSetAttribute((const void *) gemm_tile_kernel<BM, BN, WM, WN, BK, S, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, WM, WN, BK, S, EPI>), dim3(grid), dim3(WM * WN * 64), lds, c->stream, a, tm);
     HIPCHK(hipGetLastError());
+    c->tile_launches++;
     return 0;
 }
 
@@ -652,6 +653,34 @@ static bool chain_all_f16(const tts_hip_ctx *c) {
     return c->heads.type == TTS_HIP_F16;
 }
 
+// many rows: LDS-tiled MFMA GEMM on fp16 rows; a residual GEMM onto x may split K into fp32 slabs in `parts` that the next folding norm adds to x
+// (*pending = their count).  x / parts / pending: a Parler forward's c->x, c->partials, c->pending_parts; a Dia step's di_x, di_parts, di_pending
+static int run_tile(tts_hip_ctx *c, int kclass, GemmArgs a, int epi, bool want_cross, const float *x, float *parts, int *pending, double bytes, double flops) {
+    const bool may_split = epi == EPI_RESID && a.H <= 2048 && a.N == a.H && a.out == x;
+    int shape = 0, ks = 1;
+    choose_tile(c, a.R, a.N, a.K, may_split, &shape, &ks);
+    if (ks > 1) {
+        a.kchunk = a.K / ks;
+        a.slab_stride = (int64_t) c->RMAX * c->H;
+        a.out = parts;
+        epi = EPI_STORE;
+        *pending = ks;
+    }
+    CHK(prof_begin(c, kclass, bytes, flops));
+    CHK(launch_tile_epi(c, a, epi, want_cross, shape, ks));
+    return prof_end(c);
+}
+
+int run_gemm_tile_f16(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int epi, float *parts, int *pending) {
+    if (w.type != TTS_HIP_F16 || w.K % 128 || w.N % 16 || a.R > c->RMAX) return set_err("run_gemm_tile_f16: not a shape of gemm_tile_kernel (type %d, K %lld, N %lld, %d rows)", w.type, (long long) w.K, (long long) w.N, a.R);
+    a.W = c->arena + w.off;
+    a.K = (int) w.K;
+    a.N = (int) w.N;
+    c->qtile_out = QTileOut{};
+    const double bytes = (double) w.K * w.N * 2 + (double) a.R * a.K * 2 + (double) a.R * a.N * 4;
+    return run_tile(c, kclass, a, epi, false, parts ? a.out : nullptr, parts, pending, bytes, 2.0 * a.R * (double) w.K * w.N);
+}
+
 int run_gemm(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int pro, int epi) {
     a.W = c->arena + w.off;
     a.K = (int) w.K;
@@ -709,22 +738,8 @@ int run_gemm(tts_hip_ctx *c, int kclass, const W &w, GemmArgs a, int pro, int ep
         a.lda = a.K;
         pro = h16 ? PRO_F16 : PRO_F32;
     }
-    if (w.type == TTS_HIP_F16 && pro == PRO_F16 && c->tile_min_rows > 0 && a.R >= c->tile_min_rows && a.K % 128 == 0 && a.N % 16 == 0) {
-        // many rows: LDS-tiled MFMA GEMM; a residual GEMM may split K into fp32 slabs that the next LayerNorm folds into x
-        const bool may_split = epi == EPI_RESID && a.H <= 2048 && a.N == a.H && a.out == c->x;
-        int shape = 0, ks = 1;
-        choose_tile(c, a.R, a.N, a.K, may_split, &shape, &ks);
-        if (ks > 1) {
-            a.kchunk = a.K / ks;
-            a.slab_stride = (int64_t) c->RMAX * c->H;
-            a.out = c->partials;
-            epi = EPI_STORE;
-            c->pending_parts = ks;
-        }
-        CHK(prof_begin(c, kclass, bytes, flops));
-        CHK(launch_tile_epi(c, a, epi, want_cross, shape, ks));
-        return prof_end(c);
-    }
+    if (w.type == TTS_HIP_F16 && pro == PRO_F16 && c->tile_min_rows > 0 && a.R >= c->tile_min_rows && a.K % 128 == 0 && a.N % 16 == 0)
+        return run_tile(c, kclass, a, epi, want_cross, c->x, c->partials, &c->pending_parts, bytes, flops);
     if (epi == EPI_RESID && a.R > c->ln_fuse_max && a.H <= 2048 && a.N == a.H && a.out == c->x && pro != PRO_CROSS && pro != PRO_ATTN) {   // (the staging prologues of the one-sequence chain have no K-slice form)
         // many rows: spread K over 4-8x more workgroups; the partial slabs are folded into x by the next LayerNorm
         const int ks = 4;
@@ -1040,6 +1055,15 @@ static int dmalloc(T **p, size_t n) {
     return 0;
 }
 
+// di_h16, the fp16 rows of Dia's tiled route: allocated once the context can take the route (tune("dia_tile_min_rows") above 0: the default of more than 64
+// slots), by finalize or by the tts_hip_tune call that turns the key on afterwards.  Contexts that keep the key at 0 never hold it.
+int dia_tiled_buffers(tts_hip_ctx *c) {
+    if (!c->has_dia || c->di_h16 || c->dia_tile_min_rows <= 0 || c->di_U < 1 || !c->di_x) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMalloc((void **) &c->di_h16, (size_t) 2 * c->di_U * std::max(std::max(c->H, c->di_DF), c->di_A) * 2));
+    return 0;
+}
+
 extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
     if (!c) return set_err("null ctx");
     if (c->finalized) return set_err("tts_hip_finalize: already finalized");
@@ -1185,17 +1209,20 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         CHK(dmalloc(&c->di_egu, n * 2 * EF)); CHK(dmalloc(&c->di_eg, n * EF)); CHK(dmalloc(&c->di_ek, n * A)); CHK(dmalloc(&c->di_ev, n * A));
         CHK(dmalloc(&c->di_ckv, n * 2 * A));
         HIPCHK(hipMalloc((void **) &c->di_e16, n * (size_t) std::max(std::max(EH, EF), A) * 2));
-        const int U = std::max(1, std::min((int) dd.max_utterances, 64)), R = 2 * U;
+        const int U = std::max(1, (int) dd.max_utterances), R = 2 * U;   // at most DIA_MAX_UTTERANCES (tts_hip_dia_create refuses more): R <= RMAX
         c->di_U = U;
         c->di_slot_encoded.assign((size_t) U, 0);
         c->attn_part_cap = (size_t) R * c->NH * 16;
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
         const size_t kve = (size_t) c->di_kv_esz;   // bytes per cache element: half of them under tts_hip_dia_desc::kv_type = TTS_HIP_F16
-        CHK(dmalloc((char **) &c->di_ck, (size_t) c->L * U * n * A * kve));   // [L][2U][S][A], zero like the reference's cleared cache (dia/model.cpp:329)
-        CHK(dmalloc((char **) &c->di_cv, (size_t) c->L * U * n * A * kve));
-        CHK(dmalloc((char **) &c->di_k, (size_t) c->L * R * G * kvH * kve));  // [L][2U][G][kvH]
-        CHK(dmalloc((char **) &c->di_v, (size_t) c->L * R * G * kvH * kve));
-        CHK(dmalloc(&c->di_x, (size_t) R * DH)); CHK(dmalloc(&c->di_xn, (size_t) R * DH)); 
+        const size_t crossb = (size_t) c->L * U * n * A * kve, selfb = (size_t) c->L * R * G * kvH * kve;
+        if (dmalloc((char **) &c->di_ck, crossb) || dmalloc((char **) &c->di_cv, crossb) ||   // [L][2U][S][A], zero like the reference's cleared cache (dia/model.cpp:329)
+            dmalloc((char **) &c->di_k, selfb) || dmalloc((char **) &c->di_v, selfb)) {       // [L][2U][G][kvH]
+            (void) hipGetLastError();
+            return set_err("tts_hip_finalize: the K/V caches of %d utterance slots do not fit: 2 x %zu (cross) + 2 x %zu (self) bytes asked for (%s; fewer slots, or TTS_HIP_KV_F16 halves it)", U,
+                           crossb, selfb, kve == 2 ? "fp16 caches" : "fp32 caches");
+        }
+        CHK(dmalloc(&c->di_x, (size_t) R * DH)); CHK(dmalloc(&c->di_xn, (size_t) R * DH));
         // the projections of a step with <= 16 rows may arrive as up to DIA_STREAM_SLABS K-slice slabs of 16 rows (gemv_stream_kernels.h)
         const size_t RSL = std::max((size_t) R, (size_t) DIA_STREAM_SLABS * 16);
         CHK(dmalloc(&c->di_qkv, RSL * (A + 2 * kvH)));
@@ -1216,6 +1243,7 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         HIPCHK(hipHostMalloc((void **) &c->h_di, ((size_t) U * 16 + 2 * (size_t) R) * 4));
         std::vector<uint32_t> cend((size_t) R, (uint32_t) S);
         HIPCHK(hipMemcpy(c->di_cend, cend.data(), (size_t) R * 4, hipMemcpyHostToDevice));
+        CHK(dia_tiled_buffers(c));   // after everything else, and only where the tiled route can be taken: a context with the key at 0 allocates what it always allocated
     }
     if (c->has_t5) {
         const int H = c->H, F = c->F, S = (int) c->t5.max_ctx_length;
@@ -2620,6 +2648,11 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
     if (c->has_dia && w == "di_kv_elem") {   // the element size of the four caches in bytes: 4, or 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16
         if (max_floats < 1) { set_err("debug_read(di_kv_elem): buffer too small"); return -1; }
         out[0] = (float) c->di_kv_esz;
+        return 1;
+    }
+    if (c->has_dia && (w == "di_tiled" || w == "di_pending_max")) {   // of the last decoder forward issued (a captured step replays what its capture counted): gemm_tile_kernel launches, 0 on the streaming / 16-feature routes; the most K-slice slabs a GEMM left for the next rms norm
+        if (max_floats < 1) { set_err("debug_read(%s): buffer too small", what); return -1; }
+        out[0] = (float) (w == "di_tiled" ? c->di_tiled : c->di_pending_max);
         return 1;
     }
     if (c->has_dia && w.size() > 5 && w[0] == 'd' && w[1] == 'i' && w[2] == '_') {   // "di_k|di_v:<layer>:<row slot>" [max_gen][kv width], "di_ck|di_cv:<layer>:<row slot>" [max_ctx][A]

@@ -207,6 +207,11 @@ struct tts_hip_ctx {
     uint32_t *di_stok = nullptr, *di_loop = nullptr, *di_hist = nullptr;
     uint32_t *di_look = nullptr, *h_di_look = nullptr;
     _Float16 *di_e16 = nullptr;   // [2 * max_ctx][max(EH, A, EF)] the encoder activations rounded to fp16 for gemm_tile_kernel
+    // the tiled route (decoder steps of more than 16 rows on gemm_tile_kernel, shim_llama.hip: dia_forward_tiled)
+    _Float16 *di_h16 = nullptr;   // [2 * di_U][max(DH, A, DF)] the fp16 rows the next tiled GEMM reads (one producer, one consumer, stream order); NULL while the key is 0 (dia_tiled_buffers)
+    int dia_tile_min_rows = 0;    // tune("dia_tile_min_rows"): steps of at least this many rows (and more than 16) take the route; 0 = never.  0 up to 64 slots, 17 above
+    int di_tiled = 0;             // gemm_tile_kernel launches of the last dia_forward (debug_read "di_tiled")
+    int di_pending_max = 0;       // most K-slice slabs one GEMM of the last dia_forward left in di_parts (debug_read "di_pending_max")
     int di_U = 1;                        // utterance slots (rows = 2 per slot)
     // One loop, two ways in.  BATCH (tts_hip_dia_gen_begin / _launch / _wait, tts_hip_dia_generate): n encoded slots, all live from the first
     // step with the budget max_gen, until the last one has parked.  SESSION (tts_hip_dia_stream_*): n slots that begin parked; admissions
@@ -442,6 +447,7 @@ struct tts_hip_ctx {
     int tile_min_rows = 33;     // forwards with at least this many rows take the LDS-tiled GEMM (gemm_tile_kernels.h); 0 = never
     int tile_force = -1;        // TTS_HIP_TILE_FORCE: tile shape index for every tiled GEMM (tuning)
     int tile_force_ks = 0;      // TTS_HIP_TILE_KS: k slices for the residual GEMMs (tuning)
+    uint64_t tile_launches = 0; // gemm_tile_kernel launches of this context so far (launch_tile_form)
     const void *aq_src = nullptr;  // activation rows whose Q8_0 blocks already sit in aq / ad (written by the producing kernel)
     // many rows on quantised matrices (qgemm_tile_kernels.h): activation block scales transposed, float [max(H, F) / 32][ldr]
     float *adT = nullptr;
@@ -534,6 +540,7 @@ int plan(tts_hip_ctx *c);
 bool attr_needed(std::atomic<uint64_t> &done, int device);
 int prof_begin(tts_hip_ctx *c, int kclass, double bytes, double flops);
 int prof_end(tts_hip_ctx *c);
+int dia_tiled_buffers(tts_hip_ctx *c);   // di_h16 once tune("dia_tile_min_rows") is above 0 (finalize, or the tune call after it)
 int ready(tts_hip_ctx *c, const char *who);
 int stage_uniforms(tts_hip_ctx *c, const float *uniforms, size_t count);
 int stage_penalty(tts_hip_ctx *c, float penalty, int n);

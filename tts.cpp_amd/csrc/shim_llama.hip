@@ -8,6 +8,7 @@
 #include "dia_kernels.h"
 #include "gemv_kernels.h"
 #include "shim_decoder.h"
+#include "shim_dia_rows.h"
 
 // Orpheus decoder (src/models/orpheus/model.cpp:186-325)
 // ------------------------------------------------------------------------------------------------
@@ -1285,6 +1286,11 @@ extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *d
         set_err("tts_hip_dia_create: kv_type %u is neither TTS_HIP_F32 (0) nor TTS_HIP_F16 (1)", dd->kv_type);
         return nullptr;
     }
+    // two guidance rows per utterance, RMAX = 256 rows per forward
+    if (dd->max_utterances > (uint32_t) DIA_MAX_UTTERANCES) {
+        set_err("tts_hip_dia_create: max_utterances %u > %d (one decoder forward carries %d rows, two per utterance)", dd->max_utterances, (int) DIA_MAX_UTTERANCES, 2 * (int) DIA_MAX_UTTERANCES);
+        return nullptr;
+    }
     tts_hip_desc d{};
     d.struct_size = sizeof(d);
     d.hidden_size = dd->dec_hidden_size; d.n_layers = dd->dec_layers; d.n_attn_heads = dd->dec_attn_heads; d.max_ctx_length = dd->max_gen;
@@ -1297,6 +1303,9 @@ extern "C" tts_hip_ctx *tts_hip_dia_create(int device, const tts_hip_dia_desc *d
     c->dia = *dd;
     if (dd->kv_type == TTS_HIP_F16) c->di_kv_esz = 2;
     if (c->dia.cfg_scale == 0.0f) c->dia.cfg_scale = 3.0f;
+    // up to 64 slots: every step launches what it always launched.  65 .. 128: the steps of more than 16 rows run fp16 matrices on gemm_tile_kernel
+    // (dia_forward_tiled); tune("dia_tile_min_rows") moves either default
+    c->dia_tile_min_rows = dd->max_utterances > 64 ? 17 : 0;
     return c;
 }
 
@@ -1355,6 +1364,7 @@ static int dia_gemm_stream(tts_hip_ctx *c, const W &w, const float *A, int lda, 
 
 static int dia_rms(tts_hip_ctx *c, size_t w_off, int rows, int H, float *x, float *y, bool fold) {
     const int pend = fold ? c->di_pending : 0;
+    c->di_pending_max = std::max(c->di_pending_max, pend);
     hipLaunchKernelGGL(rms_fold_rows_kernel, dim3(rows), dim3(256), 0, c->stream, x, H, (const float *) (c->arena + w_off), y, rows, 1e-5f,
                        pend ? (const float *) c->di_parts : (const float *) nullptr, pend, (int64_t) c->RMAX * H, (int8_t *) nullptr, (float *) nullptr);
     if (fold) c->di_pending = 0;
@@ -1475,6 +1485,109 @@ static int dia_attn_snapshot(tts_hip_ctx *c, int layer, bool cross, const float 
     return 0;
 }
 
+// ---- the tiled route: a decoder step of more than 16 rows with every matrix on gemm_tile_kernel -----------------------------------------------
+// Whether a step of R rows takes it: fp16 matrices of tile shapes throughout, no TTS_HIP_FLAG_VALU_GEMM, and tune("dia_tile_min_rows") non-zero and at
+// most R (0 on contexts of at most 64 slots, so those launch what they always launched; 17 on larger ones).  The rms producer holds a row of at most
+// 2048 values in registers (Dia-1.6B's width; run_tile splits K up to that width too).
+static bool dia_step_tiled(const tts_hip_ctx *c, int R) {
+    if (R <= 16 || c->dia_tile_min_rows <= 0 || R < c->dia_tile_min_rows || (c->d.flags & TTS_HIP_FLAG_VALU_GEMM) || !c->di_h16 || c->H > 2048) return false;
+    auto ok = [](const W &w) { return w.type == TTS_HIP_F16 && w.K % 128 == 0 && w.N % 16 == 0; };
+    for (const auto &y : c->di_dec)
+        for (const W *w : {&y.sqkv, &y.so, &y.cq, &y.co, &y.gu, &y.out})
+            if (!ok(*w)) return false;
+    return ok(c->di_heads);
+}
+
+// rms norm of the R rows of di_x, the pending slabs of di_parts folded in first, as the fp16 rows the next tiled GEMM reads (di_h16)
+static int dia_rms_f16(tts_hip_ctx *c, size_t w_off, int R, int H) {
+    const int pend = c->di_pending;
+    c->di_pending_max = std::max(c->di_pending_max, pend);
+    CHK(prof_begin(c, TTS_HIP_K_LN, (double) R * H * (6 + 4 * pend), 0));
+    const float *w = (const float *) (c->arena + w_off), *parts = pend ? (const float *) c->di_parts : (const float *) nullptr;
+    if (!dia_rows_rms_fold_f16(c->stream, c->di_x, H, w, c->di_h16, R, 1e-5f, parts, pend, (int64_t) c->RMAX * H)) return set_err("rms_fold_rows_f16_kernel launch failed");   // H <= 2048 (dia_step_tiled)
+    c->di_pending = 0;
+    return prof_end(c);
+}
+
+// one matrix over the fp16 rows in di_h16, all R rows in one launch; resid: onto di_x, K slices as slabs in di_parts where the cost model (or tile_ks) splits
+static int dia_gemm_tile(tts_hip_ctx *c, int kclass, const W &w, float *out, int ldo, int R, bool resid) {
+    GemmArgs g{};
+    g.R = R; g.H = c->H;
+    g.A = c->di_h16; g.lda = (int) w.K;
+    g.out = out; g.ldo = ldo;
+    return run_gemm_tile_f16(c, kclass, w, g, resid ? EPI_RESID : EPI_STORE, resid ? c->di_parts : (float *) nullptr, &c->di_pending);
+}
+
+// the attended rows (di_att, fp32) rounded to fp16 for the out projections
+static int dia_att_f16(tts_hip_ctx *c, int R, int A) {
+    const int64_t n8 = (int64_t) R * (A / 8);
+    CHK(prof_begin(c, TTS_HIP_K_LN, (double) R * A * 6, 0));
+    hipLaunchKernelGGL(rows_to_f16_kernel, dim3((unsigned) ((n8 + 255) / 256)), dim3(256), 0, c->stream, (const float *) c->di_att, A, A, n8, c->di_h16);
+    HIPCHK(hipGetLastError());
+    return prof_end(c);
+}
+
+// The layers, the final norm and the heads of dia_forward for a step dia_step_tiled() accepts (di_x holds the embedded rows).  Per layer: rms -> fp16,
+// sqkv, rope + cache append, self attention, rows -> fp16, so (+ residual), rms -> fp16, cq, cross attention (the query arrives as one part and is
+// rotated inside the kernel, as on the streaming route), rows -> fp16, co, rms -> fp16, gate|up, silu * up -> fp16, out.  so / co / out add into di_x
+// in their epilogue or leave K-slice slabs in di_parts for the next rms (di_pending), the contract dia_rms has with the streaming route.  Both attention
+// launches are launch_attn_gqa's, with nothing deferred.  Profiling classes: the GEMMs under their Parler names (qkv, attn_out, cross_q, cross_out,
+// fc1 = gate|up, fc2 = out, heads), attn_self, attn_cross, and the row producers (rms, rows -> fp16, silu, rope) under "ln".
+static int dia_forward_tiled(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, bool snap) {
+    const int S = (int) c->dia.max_ctx, G = (int) c->dia.max_gen, DH = c->H, DF = c->di_DF, A = c->di_A, kvH = c->di_kvH, HD = (int) c->dia.head_dim;
+    const int NH = c->NH, NKV = (int) c->dia.dec_kv_heads, NO = c->NO, V = c->di_V, QKV = A + 2 * kvH;
+    const int R = 2 * U, RS = 2 * c->di_U, kv_esz = c->di_kv_esz;
+    const float theta_scale = powf(10000.0f, -2.0f / (float) HD);
+    const uint32_t *nul = nullptr;
+    const double kvb = (double) kv_esz;
+    for (int l = 0; l < c->L; l++) {
+        const auto &y = c->di_dec[(size_t) l];
+        const size_t self_off = (size_t) l * RS * G * kvH * (size_t) kv_esz, cross_off = (size_t) l * RS * S * A * (size_t) kv_esz;
+        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off, *ck = (char *) c->di_ck + cross_off, *cv = (char *) c->di_cv + cross_off;
+        CHK(dia_rms_f16(c, y.sa_norm, R, DH));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_QKV, y.sqkv, c->di_qkv, QKV, R, false));
+        CHK(with_kv(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {
+            typedef kv_of<decltype(k)> KV;
+            CHK(prof_begin(c, TTS_HIP_K_LN, (double) R * QKV * 8, 0));
+            hipLaunchKernelGGL(llama_rope_kv_kernel<KV>, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
+                               NKV, HD, k, v, (const uint32_t *) c->di_seq, (int64_t) G * kvH, 1, (int64_t) 0);
+            HIPCHK(hipGetLastError());
+            CHK(prof_end(c));
+            CHK(prof_begin(c, TTS_HIP_K_ATTN_SELF, (double) R * self_keys * 2 * kvH * kvb, 0));
+            CHK(launch_attn_gqa<KV>(c, NH, R, self_keys, (const float *) c->di_qkv, QKV, (const uint32_t *) c->di_pos, k, v, NKV, 1.0f, c->di_att, nul, nul,
+                                    (const uint32_t *) c->di_seq, (int64_t) G * kvH, fixed_split, false, QPre{}, nullptr, 0));
+            return prof_end(c);
+        }));
+        if (snap) CHK(dia_attn_snapshot(c, l, false, c->di_qkv, QKV, 1, 0, R, A, nullptr));
+        CHK(dia_att_f16(c, R, A));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_ATTN_OUT, y.so, c->di_x, DH, R, true));
+        CHK(dia_rms_f16(c, y.ca_norm, R, DH));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_CROSS_Q, y.cq, c->di_q, A, R, false));
+        QPre qp;   // one part; the rope of the cross-attention query happens as the attention workgroups load it
+        qp.n_parts = 1; qp.part_stride = 0; qp.rope_pos = c->di_pos; qp.theta_scale = theta_scale;
+        CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
+            CHK(prof_begin(c, TTS_HIP_K_ATTN_CROSS, (double) R * S * 2 * A * kvb, 0));
+            CHK(launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
+                                                    (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp, nullptr, S));
+            return prof_end(c);
+        }));
+        if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, 1, 0, R, A, c->di_cend));
+        CHK(dia_att_f16(c, R, A));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_CROSS_OUT, y.co, c->di_x, DH, R, true));
+        CHK(dia_rms_f16(c, y.mlp_norm, R, DH));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_FC1, y.gu, c->di_gu, 2 * DF, R, false));
+        CHK(prof_begin(c, TTS_HIP_K_LN, (double) R * DF * 10, 0));
+        if (!dia_rows_silu_mul_f16(c->stream, (const float *) c->di_gu, DF, R, c->di_h16)) return set_err("silu_mul_f16_kernel launch failed");
+        CHK(prof_end(c));
+        CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_FC2, y.out, c->di_x, DH, R, true));
+    }
+    CHK(dia_rms_f16(c, c->di_dec_norm, R, DH));
+    CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_HEADS, c->di_heads, c->di_logits, c->di_Vpad, R, false));
+    hipLaunchKernelGGL(dia_cfg_kernel, dim3((NO * V + 255) / 256, U), dim3(256), 0, c->stream, (const float *) c->di_logits, c->di_Vpad, NO * V, c->dia.cfg_scale, c->di_guided);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // the decoder step for the U utterances whose input ids / positions / cache rows are in di_ids / di_pos / di_seq; leaves the guided
 // logits in di_guided.  self_keys sizes the self-attention scratch; fixed_split: a captured step is replayed at every position, so the
 // key-split count must not depend on it (the kernels read the true extent from di_pos)
@@ -1492,6 +1605,14 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     hipLaunchKernelGGL(dia_embed_kernel, dim3((DH + 255) / 256, U), dim3(256), 0, c->stream, ea);
     HIPCHK(hipGetLastError());
     c->di_pending = 0;
+    c->di_pending_max = 0;
+    c->di_tiled = 0;
+    if (dia_step_tiled(c, R)) {   // more than 16 rows, fp16 matrices, tune("dia_tile_min_rows") reached: every GEMM on gemm_tile_kernel
+        const uint64_t before = c->tile_launches;
+        CHK(dia_forward_tiled(c, U, self_keys, fixed_split, snap));
+        c->di_tiled = (int) (c->tile_launches - before);
+        return 0;
+    }
     const uint32_t *nul = nullptr;
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->di_dec[(size_t) l];
@@ -1746,11 +1867,16 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
             HIPCHK(hipMemsetAsync(c->d_repc, 0, (size_t) U * NO * 4, c->stream));
         }
         // a slot no encoder pass has filled (SESSION; BATCH refuses it) holds whatever its cross K/V held: the one position its parked rows attend over becomes zero
-        uint64_t clear = 0;
-        for (int u = 0; u < U; u++) if (!c->di_slot_encoded[(size_t) u]) clear |= 1ull << u;
-        if (clear) {
+        // the kernel's mask holds 64 slots: one launch per group of 64, on the caches from that group's first row on (the layer stride stays 2 * DU rows)
+        for (int u0 = 0; u0 < U; u0 += 64) {
+            const int m = std::min(64, U - u0);
+            uint64_t clear = 0;
+            for (int u = 0; u < m; u++) if (!c->di_slot_encoded[(size_t) (u0 + u)]) clear |= 1ull << u;
+            if (!clear) continue;
             CHK(with_kv(c->di_kv_esz, c->di_ck, c->di_cv, [&](auto *ck, auto *cv) -> int {
-                hipLaunchKernelGGL(dia_stream_clear_kernel<kv_of<decltype(ck)>>, dim3((c->di_A + 255) / 256, 2 * U, c->L), dim3(256), 0, c->stream, ck, cv, clear, 2 * DU, (int64_t) S, c->di_A);
+                const size_t first = (size_t) 2 * u0 * S * c->di_A;
+                hipLaunchKernelGGL(dia_stream_clear_kernel<kv_of<decltype(ck)>>, dim3((c->di_A + 255) / 256, 2 * m, c->L), dim3(256), 0, c->stream, ck + first, cv + first, clear, 2 * DU,
+                                   (int64_t) S, c->di_A);
                 HIPCHK(hipGetLastError());
                 return 0;
             }));

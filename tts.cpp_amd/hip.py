@@ -1085,7 +1085,9 @@ class DiaEngine:
     """A Dia context (tts_hip_dia_create): encoder + cross K/V once per sentence, then one decoder step per call."""
 
     def __init__(self, cfg, device=0, flags=0, cfg_scale=0.0, max_utterances=1, kv_type=gguf.F32):
-        """kv_type: gguf.F32 (the reference's caches) or gguf.F16 (tts_hip_dia_desc::kv_type: the self and cross K/V caches in fp16, rounded once as they are stored)"""
+        """kv_type: gguf.F32 (the reference's caches) or gguf.F16 (tts_hip_dia_desc::kv_type: the self and cross K/V caches in fp16, rounded once as they are stored).
+        max_utterances: at most 128 (256 guidance rows per forward); above 64 the steps of more than 16 rows run fp16 matrices on the tiled MFMA GEMM
+        (tune("dia_tile_min_rows"): 17 there, 0 = never on contexts of at most 64 slots)"""
         self.L = load_lib()
         self.cfg = cfg
         d = DiaDesc()
@@ -1128,7 +1130,8 @@ class DiaEngine:
     def debug_read(self, what, max_floats):
         """'di_attn:<layer>:<self|cross>:<q|out|meta>' (set_debug before the step; meta = n_parts, part_stride, ld, rows, then pos / kend / row slot per
         row), 'di_k|di_v:<layer>:<row slot>' [max_gen][kv width], 'di_ck|di_cv:<layer>:<row slot>' [max_ctx][heads * 128] (fp16 caches widened exactly), 'di_kv_elem': the
-        cache element size in bytes (4, or 2 with kv_type=gguf.F16) (test / debugging aid)"""
+        cache element size in bytes (4, or 2 with kv_type=gguf.F16), 'di_tiled': gemm_tile_kernel launches of the last decoder forward (0 on the streaming and
+        16-feature routes), 'di_pending_max': the most K-slice slabs one GEMM of it left for the next rms norm (test / debugging aid)"""
         out = np.empty(max_floats, dtype=np.float32)
         n = self.L.tts_hip_debug_read(self.ctx, what.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), max_floats)
         if n < 0:

@@ -70,7 +70,9 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : stream_session{dia
     d.dec_kv_heads = hp.decoder_attn_heads / hp.decoder_query_heads;   // model.cpp:463: k/v are projected to attn_heads / query_heads groups
     d.head_dim = hp.head_size; d.n_output_heads = hp.n_output_heads; d.output_vocab_size = hp.output_vocab_size;
     d.max_ctx = hp.max_encoder_context_length; d.max_gen = hp.max_generation_size; d.cfg_scale = hp.cfg_scale;
-    max_seqs = tts_load_max_seqs();
+    const uint32_t asked = tts_load_max_seqs();
+    max_seqs = std::min<uint32_t>(asked, 128);   // two guidance rows per utterance, 256 rows per decoder forward (tts_hip_dia_create)
+    if (max_seqs != asked) fprintf(stderr, "dia: max_seqs %u exceeds what one decoder forward carries: loading with %u slots\n", asked, max_seqs);
     d.max_utterances = max_seqs;
     // the fp8 cache is the Orpheus decoder's alone: a silent fp32 cache here would be worse than a failed load
     if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("dia: TTS_HIP_KV_F8 is set, and a Dia decoder has no fp8 K/V caches (TTS_HIP_KV_F16 selects its fp16 ones)\n");

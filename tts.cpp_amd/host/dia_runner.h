@@ -92,7 +92,7 @@ struct dia_runner final : stream_session {
     bool     session_chunks_ready(uint32_t chunk_frames) override;
     uint32_t batch_capacity() const override { return max_seqs; }
     uint32_t kv_element_bytes() const override;   // 4, or 2 when TTS_HIP_KV_F16 was in the environment at load (tts_hip_dia_desc::kv_type)
-    uint32_t max_seqs = 1;
+    uint32_t max_seqs = 1;   // utterance slots of the decoder context (tts_load_options::max_seqs, at most 128: two guidance rows each, 256 rows per forward)
 
     dia_hparams        hp;
     sampler            smp;
