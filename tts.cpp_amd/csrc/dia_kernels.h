@@ -184,7 +184,7 @@ struct DiaAdmitArgs {
     int pen_len;
 };
 
-// blockIdx.y = admitted utterance; thread 0 of block x == 0 resets the slot, all threads move its penalty table and its uniforms
+// blockIdx.y = admitted utterance; thread 0 of block x == 0 resets the slot, then admit_sampler_state (parler_kernels.h): all threads move its penalty table and its uniforms
 static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitArgs a) {
     const int i = blockIdx.y;
     if (i >= a.n) return;
@@ -198,20 +198,8 @@ static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitAr
         a.cend[2 * u] = a.max_ctx; a.cend[2 * u + 1] = a.max_ctx;
         a.delay[u] = -1; a.done[u] = 0; a.call[u] = 1; a.handed[u] = 0;
         a.budget[u] = a.budgets[i]; a.steps[u] = 0;
-        if (a.rec_in) a.rec[u] = a.rec_in[i];
     }
-    bool sampled = a.uni_in != nullptr;
-    if (a.rec_in) {
-        if (a.rec_in[i].pen_table)
-            for (int e = blockIdx.x * 256 + threadIdx.x; e < a.pen_len; e += gridDim.x * 256) a.pen[(int64_t) u * a.pen_len + e] = a.pen_in[(int64_t) i * a.pen_len + e];
-        sampled = sampled && a.rec_in[i].mode == SAMPLE_ROW_SAMPLE;   // a greedy utterance's block of uniforms is ignored
-    }
-    if (!sampled) return;
-    const int64_t total = (int64_t) a.max_gen * a.n_out;
-    for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
-        const int64_t k = e / a.n_out, h = e - k * a.n_out;
-        a.uni[(k * a.n_slots + u) * a.n_out + h] = a.uni_in[(int64_t) i * total + e];
-    }
+    admit_sampler_state(a.rec_in, a.rec, a.pen_in, a.pen, a.pen_len, a.uni_in, a.uni, a.max_gen, a.n_slots, a.n_out, i, u, a.uni_in != nullptr);
 }
 
 // cross K/V [L][rows][S][A] of KV = float or _Float16 elements (tts_hip_dia_desc::kv_type): position 0 of rows 2u, 2u+1 of the flagged slots.

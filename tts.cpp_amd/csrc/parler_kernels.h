@@ -1424,6 +1424,26 @@ static __global__ void feed_kernel(FeedArgs a) {
     }
 }
 
+// What the admit kernels of the sessions (parler_stream_admit_kernel here, dia_stream_admit_kernel) do alike for admitted utterance i = blockIdx.y
+// going into slot u, after their own slot reset: the record rec_in[i] (rec_in NULL: a uniform session, the sampler is the launch's) into rec[u]
+// by thread 0 of block x == 0; by all blocks its penalty table [pen_len] where the record names one, and, if `sampled` and the record (if any)
+// samples, its draws uni_in [n][steps][n_out] into column u of uni [steps][n_total][n_out].  A greedy utterance's block of uni_in is ignored.
+static __device__ __forceinline__ void admit_sampler_state(const SampleRow *rec_in, SampleRow *rec, const double *pen_in, double *pen, int pen_len, const float *uni_in, float *uni,
+                                                           uint32_t steps, int n_total, int n_out, int i, uint32_t u, bool sampled) {
+    if (rec_in) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) rec[u] = rec_in[i];
+        if (rec_in[i].pen_table)
+            for (int e = blockIdx.x * 256 + threadIdx.x; e < pen_len; e += gridDim.x * 256) pen[(int64_t) u * pen_len + e] = pen_in[(int64_t) i * pen_len + e];
+        sampled = sampled && rec_in[i].mode == SAMPLE_ROW_SAMPLE;
+    }
+    if (!sampled) return;
+    const int64_t total = (int64_t) steps * n_out;
+    for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
+        const int64_t k = e / n_out, h = e - k * n_out;
+        uni[(k * n_total + u) * n_out + h] = uni_in[(int64_t) i * total + e];
+    }
+}
+
 // The admission of a mixed continuous session (tts_hip_parler_stream_admit_mixed): ONE launch for all admitted slots.  Everything here is
 // indexed by cache slot, as sample_kernel and feed_kernel read it through orig = the rows' cache slots.
 struct ParlerAdmitArgs {
@@ -1444,8 +1464,7 @@ struct ParlerAdmitArgs {
     int pen_len;
 };
 
-// blockIdx.y = admitted utterance; block x == 0 resets the slot (EOS flags, steps_done, sampler::reset, the record), all blocks move its penalty
-// table and its draws.  A greedy utterance's block of uni_in is ignored.
+// blockIdx.y = admitted utterance; block x == 0 resets the slot (EOS flags, steps_done, sampler::reset), then admit_sampler_state
 static __global__ __launch_bounds__(256) void parler_stream_admit_kernel(ParlerAdmitArgs a) {
     const int i = blockIdx.y;
     if (i >= a.n) return;
@@ -1458,16 +1477,8 @@ static __global__ __launch_bounds__(256) void parler_stream_admit_kernel(ParlerA
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.steps_done[u] = 0;
         a.handed[u] = 0;
-        a.rec[u] = a.rec_in[i];
     }
-    if (a.rec_in[i].pen_table)
-        for (int e = blockIdx.x * 256 + threadIdx.x; e < a.pen_len; e += gridDim.x * 256) a.pen[(int64_t) u * a.pen_len + e] = a.pen_in[(int64_t) i * a.pen_len + e];
-    if (!a.uni_in || a.rec_in[i].mode != SAMPLE_ROW_SAMPLE) return;
-    const int64_t total = (int64_t) a.max_steps * a.n_out;
-    for (int64_t e = (int64_t) blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t) gridDim.x * 256) {
-        const int64_t k = e / a.n_out, h = e - k * a.n_out;
-        a.uni[(k * a.n_total + u) * a.n_out + h] = a.uni_in[(int64_t) i * total + e];
-    }
+    admit_sampler_state(a.rec_in, a.rec, a.pen_in, a.pen, a.pen_len, a.uni_in, a.uni, a.max_steps, a.n_total, a.n_out, i, u, a.uni_in != nullptr);
 }
 
 // The look-in of a session wait that takes rows (tts_hip_parler_stream_wait): the token rows no earlier wait handed out, of every slot the host

@@ -690,11 +690,7 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
         }
         B.dbuf_elems = want_elems; B.cap_codes = want_codes; B.h_pcm_elems = want_pcm;   // capacities are recorded only once every buffer exists
     }
-    if (n > c->d_frames_cap) {
-        free_dev(c->d_frames);
-        HIPCHK(hipMalloc((void **) &c->d_frames, (size_t) n * 4));
-        c->d_frames_cap = n;
-    }
+    CHK(grow_dev(&c->d_frames, &c->d_frames_cap, n));
     HIPCHK(hipMemcpyAsync(c->d_frames, frames, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));
     {   // codes padded to [n][Fmax][n_cb]
         size_t off = 0;
@@ -1753,22 +1749,12 @@ static int snac_decode_pass(tts_hip_ctx *c, const char *what, const uint32_t *co
     if (n_in > c->s_in_cap) {
         HIPCHK(hipStreamSynchronize(c->stream));
         const size_t cap = std::max(n_in, whole_cap ? (size_t) 6 + (size_t) sd.max_frames * (sd.n_codebooks + up_sum) : 0);
-        c->s_in_cap = 0;
-        free_dev(c->s_in); c->s_in = nullptr;
-        if (c->h_in) { (void) hipHostFree(c->h_in); c->h_in = nullptr; }
-        HIPCHK(hipMalloc((void **) &c->s_in, cap * 4));
-        HIPCHK(hipHostMalloc((void **) &c->h_in, cap * 4));
-        c->s_in_cap = cap;
+        CHK(grow_bufs(&c->s_in_cap, cap, nullptr, &c->s_in, pinned(&c->h_in)));
     }
     if (n_keep > c->s_out_cap) {
         HIPCHK(hipStreamSynchronize(c->stream));
         const size_t cap = std::max(n_keep, whole_cap ? (size_t) sd.max_frames * c->s_up : 0);
-        c->s_out_cap = 0;
-        free_dev(c->s_out); c->s_out = nullptr;
-        if (c->h_out) { (void) hipHostFree(c->h_out); c->h_out = nullptr; }
-        HIPCHK(hipMalloc((void **) &c->s_out, cap * 4));
-        HIPCHK(hipHostMalloc((void **) &c->h_out, cap * 4));
-        c->s_out_cap = cap;
+        CHK(grow_bufs(&c->s_out_cap, cap, nullptr, &c->s_out, pinned(&c->h_out)));
     }
     // the input block: [tok | code_base | noise_base | crop src | crop dst | crop len][n], the codes, the noise
     uint32_t *hs = c->h_in;

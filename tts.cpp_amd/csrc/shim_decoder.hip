@@ -1,8 +1,7 @@
 // shim_decoder.hip — launch plumbing, the GEMM / attention launchers, the Parler decoder forward, finalize, the generation loops,
 // the T5 voice-prompt encoder and the introspection entry points.  (tts_hip.hip until round 4; split so that the units build in parallel.)
-#include "shim_internal.h"
+#include "shim_session.h"
 
-#include "parler_kernels.h"
 #include "gemm_tile_kernels.h"
 #include "gemv_stream_kernels.h"
 #include "t5_kernels.h"
@@ -1048,13 +1047,6 @@ static int derive_scale_tables(tts_hip_ctx *c) {
 // ------------------------------------------------------------------------------------------------
 // finalize
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static int dmalloc(T **p, size_t n) {
-    HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
-}
-
 // di_h16, the fp16 rows of Dia's tiled route: allocated once the context can take the route (tune("dia_tile_min_rows") above 0: the default of more than 64
 // slots), by finalize or by the tts_hip_tune call that turns the key on afterwards.  Contexts that keep the key at 0 never hold it.
 int dia_tiled_buffers(tts_hip_ctx *c) {
@@ -1631,14 +1623,9 @@ static int gen_begin(tts_hip_ctx *c, int mode, uint32_t n, const uint32_t *start
         c->h_seq[r] = r;
         c->host_pos[r] = start_pos[r];
     }
-    const size_t need = (size_t) n_steps * n * c->NO;
-    if (need > c->tokens_out_cap) {
-        free_dev(c->d_tokens_out);
-        c->d_tokens_out = nullptr;
-        HIPCHK(hipMalloc((void **) &c->d_tokens_out, need * 4));
-        c->tokens_out_cap = need;
-        drop_gen_graphs(c);  // the captured graphs baked the old pointer in
-    }
+    bool moved = false;
+    CHK(grow_dev(&c->d_tokens_out, &c->tokens_out_cap, (size_t) n_steps * n * c->NO, &moved));
+    if (moved) drop_gen_graphs(c);  // the captured graphs baked the old pointer in
     for (uint32_t r = 0; r < n; r++) c->h_tok[r] = 1;  // current_step of the first audio decode (model.cpp:783-785)
     HIPCHK(hipMemcpyAsync(c->d_ids, c->h_ids, (size_t) n * c->NO * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_pos, c->h_pos, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1768,13 +1755,9 @@ static int check_sampling(const tts_hip_ctx *c, const tts_hip_sampling *sp, cons
 }
 
 int stage_uniforms(tts_hip_ctx *c, const float *uniforms, size_t count) {
-    if (count > c->uniforms_cap) {
-        free_dev(c->d_uniforms);
-        c->d_uniforms = nullptr;
-        HIPCHK(hipMalloc((void **) &c->d_uniforms, count * 4));
-        c->uniforms_cap = count;
-        drop_gen_graphs(c);
-    }
+    bool moved = false;
+    CHK(grow_dev(&c->d_uniforms, &c->uniforms_cap, count, &moved));
+    if (moved) drop_gen_graphs(c);
     HIPCHK(hipMemcpyAsync(c->d_uniforms, uniforms, count * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -1783,15 +1766,11 @@ int stage_uniforms(tts_hip_ctx *c, const float *uniforms, size_t count) {
 // pow(penalty, count) for count = 0..n: evaluated here with the host libm, the arithmetic sampler.cpp:90 performs
 int stage_penalty(tts_hip_ctx *c, float penalty, int n) {
     if (penalty == 1.0f) return 0;
-    if (n + 1 > c->pen_len) {
-        free_dev(c->d_pen);
-        c->d_pen = nullptr;
-        HIPCHK(hipMalloc((void **) &c->d_pen, (size_t) (n + 1) * 8));
-        c->pen_len = n + 1;
-        drop_gen_graphs(c);
-    }
+    bool moved = false;
+    CHK(grow_dev(&c->d_pen, &c->pen_len, (size_t) n + 1, &moved));
+    if (moved) drop_gen_graphs(c);
     std::vector<double> t((size_t) c->pen_len);
-    for (int i = 0; i < c->pen_len; i++) t[(size_t) i] = pow((double) penalty, (double) i);
+    penalty_table(t.data(), penalty, c->pen_len);
     HIPCHK(hipMemcpyAsync(c->d_pen, t.data(), t.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -1898,33 +1877,12 @@ static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uin
         }
         HIPCHK(hipMemsetAsync(c->gs_handed, 0, (size_t) RT * 4, c->stream));
     }
+    bool moved = false;
     if (mixed) {
-        // everything an admission writes into is sized here, once: no admission reallocates what a captured launch holds
-        const size_t count = (size_t) (max_steps + 1) * RT * c->NO;
-        if (count > c->uniforms_cap) {
-            free_dev(c->d_uniforms); c->d_uniforms = nullptr; c->uniforms_cap = 0;
-            HIPCHK(hipMalloc((void **) &c->d_uniforms, count * 4));
-            c->uniforms_cap = count;
-            drop_gen_graphs(c);
-            // once: an admission writes a sampled slot's whole column; the plane after the last is read by a row that spent its budget inside a
-            // chunk, whose id is recorded nowhere
-            HIPCHK(hipMemsetAsync(c->d_uniforms, 0, count * 4, c->stream));
-        }
-        if ((size_t) RT > c->gs_rec_cap) {
-            free_dev(c->gs_rec); free_dev(c->gs_rec_in); free_dev(c->gs_adm);
-            c->gs_rec = c->gs_rec_in = nullptr; c->gs_adm = nullptr; c->gs_rec_cap = 0;
-            HIPCHK(hipMalloc(&c->gs_rec, (size_t) RT * sizeof(SampleRow)));
-            HIPCHK(hipMalloc(&c->gs_rec_in, (size_t) RT * sizeof(SampleRow)));
-            HIPCHK(hipMalloc((void **) &c->gs_adm, (size_t) RT * 4));
-            c->gs_rec_cap = RT;
-            drop_gen_graphs(c);   // the captured MODE_GEN_MIXED launch holds gs_rec
-        }
-        if ((size_t) n_slots * max_steps > c->gs_pen_cap) {   // reached through the records alone: no captured launch holds it
-            free_dev(c->gs_pen);
-            c->gs_pen = nullptr; c->gs_pen_cap = 0;
-            HIPCHK(hipMalloc((void **) &c->gs_pen, (size_t) n_slots * max_steps * 8));
-            c->gs_pen_cap = (size_t) n_slots * max_steps;
-        }
+        // everything an admission writes into is sized here (and the uniforms below), once: no admission reallocates what a captured launch holds
+        CHK(grow_bufs(&c->gs_rec_cap, RT, &moved, (SampleRow **) &c->gs_rec, (SampleRow **) &c->gs_rec_in, &c->gs_adm));
+        if (moved) drop_gen_graphs(c);   // the captured MODE_GEN_MIXED launch holds gs_rec
+        CHK(grow_dev(&c->gs_pen, &c->gs_pen_cap, (size_t) n_slots * max_steps));   // reached through the records alone: no captured launch holds it
         c->gs_pen_len = (int) max_steps;
         HIPCHK(hipMemsetAsync(c->gs_rec, 0, c->gs_rec_cap * sizeof(SampleRow), c->stream));   // SAMPLE_ROW_MAX, no table: the padding slot's for good
         g.mixed = true;
@@ -1936,23 +1894,18 @@ static int parler_stream_begin(tts_hip_ctx *c, const char *what, bool mixed, uin
             (sp->repetition_penalty != 1.0f) != (c->smp.repetition_penalty != 1.0f))
             drop_gen_graphs(c);
         c->smp = *sp;
-        const size_t count = (size_t) (max_steps + 1) * RT * c->NO;   // + 1: a row that spent its budget inside a chunk still reads the plane after its last
-        if (count > c->uniforms_cap) {
-            free_dev(c->d_uniforms); c->d_uniforms = nullptr;
-            HIPCHK(hipMalloc((void **) &c->d_uniforms, count * 4));
-            c->uniforms_cap = count;
-            drop_gen_graphs(c);
-        }
-        HIPCHK(hipMemsetAsync(c->d_uniforms, 0, count * 4, c->stream));
         CHK(stage_penalty(c, sp->repetition_penalty, (int) max_steps));
     }
-    const size_t need = (size_t) max_steps * RT * c->NO;
-    if (need > c->tokens_out_cap) {
-        free_dev(c->d_tokens_out); c->d_tokens_out = nullptr;
-        HIPCHK(hipMalloc((void **) &c->d_tokens_out, need * 4));
-        c->tokens_out_cap = need;
-        drop_gen_graphs(c);
+    if (mixed || sp) {
+        // + 1: a row that spent its budget inside a chunk still reads the plane after its last, whose id is recorded nowhere.  A uniform session
+        // starts from zeros; a mixed one zeroes the block once, since an admission writes a sampled slot's whole column
+        const size_t count = (size_t) (max_steps + 1) * RT * c->NO;
+        CHK(grow_dev(&c->d_uniforms, &c->uniforms_cap, count, &moved));
+        if (moved) drop_gen_graphs(c);
+        if (moved || sp) HIPCHK(hipMemsetAsync(c->d_uniforms, 0, count * 4, c->stream));
     }
+    CHK(grow_dev(&c->d_tokens_out, &c->tokens_out_cap, (size_t) max_steps * RT * c->NO, &moved));
+    if (moved) drop_gen_graphs(c);
     if (c->g_bos != bos || c->g_eos != eos) { drop_gen_graphs(c); c->g_bos = bos; c->g_eos = eos; }
     if (c->gen_total != (int) RT || !c->gs_graphs || c->gs_baked_steps != max_steps) { drop_gen_graphs(c); c->gen_total = (int) RT; c->gs_graphs = true; c->gs_baked_steps = max_steps; }   // feed_kernel's padding slot is baked in too
     HIPCHK(hipMemsetAsync(c->d_eos, 0, (size_t) RT * c->NO, c->stream));
@@ -1991,13 +1944,10 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
     if (!slots || !ids || !lens) return set_err("stream_admit: null argument");
     if (g.sampled && !uniforms) return set_err("stream_admit: a sampled stream needs the utterances' uniforms [n][max_steps][heads]");
     const uint32_t RT = g.n_slots + 1, max_pos = (uint32_t) std::min(c->KVPOS, c->NPOS);
-    bool any_sampled = false, any_rep = false;
+    CHK(check_slot_list("stream_admit", n, slots, g.slot_live, 1u << SlotLedger::FREE, ">=", "is still generating"));   // slot_live's 0 / 1 are FREE / LIVE
     {
         size_t off = 0;
         for (uint32_t i = 0; i < n; i++) {
-            if (slots[i] >= g.n_slots) return set_err("stream_admit: slot %u >= %u", slots[i], g.n_slots);
-            if (g.slot_live[slots[i]]) return set_err("stream_admit: slot %u is still generating", slots[i]);
-            for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("stream_admit: slot %u named twice", slots[i]);
             if (lens[i] == 0 || lens[i] >= max_pos) return set_err("stream_admit: prompt of %u ids leaves no room in %u cached positions", lens[i], max_pos);
             for (uint32_t j = 0; j < lens[i]; j++)
                 if (ids[off + j] >= (uint32_t) c->PV) return set_err("stream_admit: text id %u >= prompt vocab %d", ids[off + j], c->PV);
@@ -2006,25 +1956,19 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
             if (!sp) continue;
             CHK(check_sampling(c, sp, what));
             if (!uniforms) return set_err("%s: utterance %u is sampled: it needs uniforms [n][max_steps][heads]", what, i);
-            any_sampled = true;
-            any_rep = any_rep || sp->repetition_penalty != 1.0f;
         }
     }
+    // a mixed session: per utterance its record and its penalty table, through the staging copies.  Those grow before anything is launched; no
+    // captured launch holds them
     const size_t per = (size_t) g.max_steps * c->NO;
-    if (mixed) {   // the staging copies grow before anything is launched; no captured launch holds them
-        const int len = c->gs_pen_len;
-        if (any_sampled && n * per > c->gs_uni_in_cap) {
-            free_dev(c->gs_uni_in);
-            c->gs_uni_in = nullptr; c->gs_uni_in_cap = 0;
-            HIPCHK(hipMalloc((void **) &c->gs_uni_in, n * per * 4));
-            c->gs_uni_in_cap = n * per;
-        }
-        if (any_rep && (size_t) n * len > c->gs_pen_in_cap) {
-            free_dev(c->gs_pen_in);
-            c->gs_pen_in = nullptr; c->gs_pen_in_cap = 0;
-            HIPCHK(hipMalloc((void **) &c->gs_pen_in, (size_t) n * len * 8));
-            c->gs_pen_in_cap = (size_t) n * len;
-        }
+    const int len = c->gs_pen_len;
+    bool any_sampled = false, any_rep = false;
+    std::vector<SampleRow> recs;
+    std::vector<double> tabs;
+    if (mixed) {
+        build_sample_rows(n, sampling, len, [&](uint32_t i) { return c->gs_pen + (size_t) slots[i] * len; }, recs, tabs, &any_sampled, &any_rep);
+        if (any_sampled) CHK(grow_dev(&c->gs_uni_in, &c->gs_uni_in_cap, n * per));
+        if (any_rep) CHK(grow_dev(&c->gs_pen_in, &c->gs_pen_in_cap, (size_t) n * len));
     }
     {   // The newcomers' prompts as one side batch (prefill_batch's rows), padded with rows of the padding slot to the row counts the decode steps
         // use (multiples of 64): a lone 5-id prompt would otherwise run through the small-batch GEMM kernels (other summation order than the
@@ -2055,24 +1999,7 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
             HIPCHK(hipStreamSynchronize(c->stream));
         }
     }
-    // a mixed session: per utterance its record, and pow(penalty, count) in double as stage_penalty evaluates it, through the staging copies
-    std::vector<SampleRow> recs(mixed ? n : 0);
-    std::vector<double> tabs;
     if (mixed) {
-        const int len = c->gs_pen_len;
-        tabs.resize(any_rep ? (size_t) n * len : 0);
-        for (uint32_t i = 0; i < n; i++) {
-            const tts_hip_sampling *sp = sampling ? sampling[i] : nullptr;
-            SampleRow &r = recs[i];
-            r = SampleRow{};
-            r.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
-            r.top_k = sp ? sp->top_k : 0u; r.top_p = sp ? sp->top_p : 1.0f; r.temperature = sp ? sp->temperature : 1.0f;
-            r.pen_len = len;
-            if (sp && sp->repetition_penalty != 1.0f) {
-                r.pen_table = c->gs_pen + (size_t) slots[i] * len;
-                for (int k = 0; k < len; k++) tabs[(size_t) i * len + k] = pow((double) sp->repetition_penalty, (double) k);
-            }
-        }
         HIPCHK(hipMemcpyAsync(c->gs_adm, slots, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->gs_rec_in, recs.data(), recs.size() * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
         if (any_rep) HIPCHK(hipMemcpyAsync(c->gs_pen_in, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -2091,32 +2018,21 @@ static int parler_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uin
         const uint32_t s = slots[i];
         g.slot_sofar[s] = g.slot_done[s] = g.slot_handed[s] = 0;   // the newcomer's rows start at 0; un-taken rows of the last occupant are gone
         g.slot_pend[s] = 0;
-        if (mixed) {
+        if (mixed) {   // the slot's device state is parler_stream_admit_kernel's
             g.slot_sampled[s] = sampling && sampling[i];
-            g.slot_live[s] = 1;
-            g.row_slot.push_back(s);
-            g.pos.push_back(lens[i]);
-            g.step.push_back(1);
-            for (int h = 0; h < c->NO; h++) g.ids.push_back(g.bos);
-            continue;
-        }
-        HIPCHK(hipMemsetAsync(c->d_eos + (size_t) s * c->NO, 0, (size_t) c->NO, c->stream));
-        HIPCHK(hipMemsetAsync(c->d_steps_done + s, 0, 4, c->stream));
-        HIPCHK(hipMemsetAsync(c->gs_handed + s, 0, 4, c->stream));
-        if (g.sampled) {
-            if (c->smp.repetition_penalty != 1.0f) {   // sampler::reset for this utterance
+        } else {
+            HIPCHK(hipMemsetAsync(c->d_eos + (size_t) s * c->NO, 0, (size_t) c->NO, c->stream));
+            HIPCHK(hipMemsetAsync(c->d_steps_done + s, 0, 4, c->stream));
+            HIPCHK(hipMemsetAsync(c->gs_handed + s, 0, 4, c->stream));
+            if (g.sampled && c->smp.repetition_penalty != 1.0f) {   // sampler::reset for this utterance
                 HIPCHK(hipMemsetAsync(c->d_last + (size_t) s * c->NO, 0xFF, (size_t) c->NO * 4, c->stream));
                 HIPCHK(hipMemsetAsync(c->d_repc + (size_t) s * c->NO, 0, (size_t) c->NO * 4, c->stream));
             }
-            // the utterance's draws [max_steps][heads] into its column of [max_steps][slots + 1][heads]
-            HIPCHK(hipMemcpy2DAsync(c->d_uniforms + (size_t) s * c->NO, (size_t) RT * c->NO * 4, uniforms + (size_t) i * g.max_steps * c->NO, (size_t) c->NO * 4,
-                                    (size_t) c->NO * 4, g.max_steps, hipMemcpyHostToDevice, c->stream));
+            if (g.sampled)   // the utterance's draws [max_steps][heads] into its column of [max_steps][slots + 1][heads]
+                HIPCHK(hipMemcpy2DAsync(c->d_uniforms + (size_t) s * c->NO, (size_t) RT * c->NO * 4, uniforms + (size_t) i * g.max_steps * c->NO, (size_t) c->NO * 4,
+                                        (size_t) c->NO * 4, g.max_steps, hipMemcpyHostToDevice, c->stream));
         }
-        g.slot_live[s] = 1;
-        g.row_slot.push_back(s);
-        g.pos.push_back(lens[i]);
-        g.step.push_back(1);
-        for (int h = 0; h < c->NO; h++) g.ids.push_back(g.bos);
+        g.push_row(s, lens[i], c->NO);   // live once its device state has been enqueued
     }
     HIPCHK(hipStreamSynchronize(c->stream));   // recs and tabs are locals, slots and uniforms the caller's
     return 0;
@@ -2233,24 +2149,18 @@ static int parler_stream_wait(tts_hip_ctx *c, const char *what, uint32_t *tokens
     }
     if (in_flight || n_look) HIPCHK(hipStreamSynchronize(c->stream));
     g.unwaited = false;
-    if (in_flight) {
-        std::vector<uint32_t> slot2, pos2, step2, ids2;
-        for (uint32_t r = 0; r < live; r++) {
-            const uint32_t sl = g.row_slot[r];
-            uint32_t fin = c->h_tok[sl];
-            if (fin) {
-                finished_slots[*n_finished] = sl;
-                finished_steps[*n_finished] = std::min(fin, g.max_steps);
-                (*n_finished)++;
-                g.slot_live[sl] = 0;
-                g.slot_done[sl] = std::min(fin, g.max_steps);
-                g.slot_pend[sl] = 1;
-                continue;
-            }
-            slot2.push_back(sl); pos2.push_back(c->h_pos[r]); step2.push_back(c->h_seq[r]);
-            ids2.insert(ids2.end(), c->h_ids + (size_t) r * NO, c->h_ids + (size_t) (r + 1) * NO);
-        }
-        g.row_slot.swap(slot2); g.pos.swap(pos2); g.step.swap(step2); g.ids.swap(ids2);
+    if (in_flight) {   // the rows that go on, with the state the steps left them in (row_slot still holds the launch's `live` rows)
+        g.keep_rows([&](uint32_t sl) {
+            const uint32_t fin = c->h_tok[sl];
+            if (!fin) return true;
+            finished_slots[*n_finished] = sl;
+            finished_steps[*n_finished] = std::min(fin, g.max_steps);
+            (*n_finished)++;
+            g.slot_live[sl] = 0;
+            g.slot_done[sl] = std::min(fin, g.max_steps);
+            g.slot_pend[sl] = 1;
+            return false;
+        }, c->h_pos, c->h_seq, c->h_ids, NO);
     }
     if (n_look) {
         parler_look_scatter(c, n_look, cap, tokens_out);
@@ -2303,23 +2213,12 @@ extern "C" int tts_hip_parler_stream_drop(tts_hip_ctx *c, uint32_t n, const uint
     if (g.unwaited) return set_err(GS_IN_FLIGHT, who);
     if (n == 0) return 0;
     if (!slots) return set_err("%s: null argument", who);
-    for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= %u", who, slots[i], g.n_slots);
-        if (!g.slot_live[slots[i]]) return set_err("%s: slot %u is not live", who, slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", who, slots[i]);
-    }
+    CHK(check_slot_list(who, n, slots, g.slot_live, 1u << SlotLedger::LIVE, ">=", "is not live"));
     for (uint32_t i = 0; i < n; i++) {
         g.slot_live[slots[i]] = 0;
         g.slot_sofar[slots[i]] = g.slot_done[slots[i]] = 0;
     }
-    const int NO = c->NO;
-    std::vector<uint32_t> slot2, pos2, step2, ids2;
-    for (size_t r = 0; r < g.row_slot.size(); r++) {
-        if (!g.slot_live[g.row_slot[r]]) continue;
-        slot2.push_back(g.row_slot[r]); pos2.push_back(g.pos[r]); step2.push_back(g.step[r]);
-        ids2.insert(ids2.end(), g.ids.begin() + (ptrdiff_t) (r * NO), g.ids.begin() + (ptrdiff_t) ((r + 1) * NO));
-    }
-    g.row_slot.swap(slot2); g.pos.swap(pos2); g.step.swap(step2); g.ids.swap(ids2);
+    g.keep_rows([&](uint32_t sl) { return g.slot_live[sl] != 0; }, g.pos.data(), g.step.data(), g.ids.data(), c->NO);
     return 0;
 }
 
@@ -2405,20 +2304,9 @@ extern "C" int tts_hip_sample_logits_rows_mixed(tts_hip_ctx *c, uint32_t n_rows,
     double *d_tab = nullptr;
     HIPCHK(hipMalloc((void **) &d_rec, (size_t) n_rows * sizeof(SampleRow)));
     if (any_rep && hipMalloc((void **) &d_tab, (size_t) n_rows * len * 8) != hipSuccess) { free_dev(d_rec); return set_err("%s: out of device memory", what); }
-    std::vector<SampleRow> recs(n_rows);
-    std::vector<double> tabs(any_rep ? (size_t) n_rows * len : 0);
-    for (uint32_t r = 0; r < n_rows; r++) {
-        const tts_hip_sampling *sp = sampling[r];
-        SampleRow &rec = recs[r];
-        rec = SampleRow{};
-        rec.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
-        rec.top_k = sp ? sp->top_k : 0u; rec.top_p = sp ? sp->top_p : 1.0f; rec.temperature = sp ? sp->temperature : 1.0f;
-        rec.pen_len = len;
-        if (sp && sp->repetition_penalty != 1.0f) {
-            rec.pen_table = d_tab + (size_t) r * len;
-            for (int k = 0; k < len; k++) tabs[(size_t) r * len + k] = pow((double) sp->repetition_penalty, (double) k);
-        }
-    }
+    std::vector<SampleRow> recs;
+    std::vector<double> tabs;
+    build_sample_rows(n_rows, sampling, len, [&](uint32_t r) { return d_tab + (size_t) r * len; }, recs, tabs, &any_sampled, &any_rep);
     int rc = 0;
     auto run = [&]() -> int {
         if (any_sampled) CHK(stage_uniforms(c, uniforms, (size_t) n_rows * c->NO));

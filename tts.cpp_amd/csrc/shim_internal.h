@@ -21,7 +21,7 @@
 #include <unordered_map>
 #define LLAMA_GREEDY_CHUNK 8
 
-int set_err(const char *fmt, ...);   // shim_core.hip: thread-local message behind tts_hip_last_error()
+#include "session_slots.h"   // set_err (shim_core.hip: thread-local message behind tts_hip_last_error()), SlotLedger, penalty_table
 // TTS_HIP_FLAG_KV_F16 is tts_hip_orpheus_create's alone: every other create call refuses it by name (true: refused, the message is set)
 static inline bool refuse_kv_f16(uint32_t flags, const char *call) {
     if (!(flags & TTS_HIP_FLAG_KV_F16)) return false;
@@ -216,9 +216,8 @@ struct tts_hip_ctx {
     // One loop, two ways in.  BATCH (tts_hip_dia_gen_begin / _launch / _wait, tts_hip_dia_generate): n encoded slots, all live from the first
     // step with the budget max_gen, until the last one has parked.  SESSION (tts_hip_dia_stream_*): n slots that begin parked; admissions
     // make them live, reports and collections free them again.
-    struct DiaLoop {
+    struct DiaLoop : SlotLedger {         // ENDED: seen parked by a look-in, not yet reported
         enum Mode : uint8_t { NONE = 0, BATCH = 1, SESSION = 2 };
-        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: seen parked by a look-in, not yet reported
         Mode mode = NONE;
         bool sampled = false, rep = false;
         bool mixed = false;              // SESSION opened by tts_hip_dia_stream_begin_mixed: every slot carries its own sampler (di_srec)
@@ -226,13 +225,10 @@ struct tts_hip_ctx {
         uint32_t n = 0, max_gen = 0;     // utterances (BATCH) or slots (SESSION)
         tts_hip_dia_codes codes{};
         tts_hip_sampling sp{};
-        std::vector<uint8_t> slot;       // per slot, one of the above
         std::vector<uint32_t> steps;     // per slot at the last look-in: sampler calls made
         std::vector<uint32_t> budget;    // per slot: the occupant's step budget
         std::vector<uint32_t> handed;    // per slot: history rows of the occupant handed out (the host's copy of di_loop's fourth array)
         uint32_t launched = 0;           // steps enqueued so far (BATCH: at most max_gen + 1)
-        uint32_t in_flight = 0;          // ... of which no look-in has waited for yet
-        uint32_t unread = 0;             // steps enqueued since the last look-in that took rows: bounds the rows a look-in can find
     } dl;
     // what the captured step of a mode holds by value: a begin that changes any of it drops that mode's graph (and only that one, so a
     // caller alternating tts_hip_dia_generate, a session and a mixed session keeps all three)
@@ -286,20 +282,16 @@ struct tts_hip_ctx {
     // (tts_hip_orpheus_gen_begin / _launch / _wait at n_utt > 1, tts_hip_orpheus_generate_batch): slots 0 .. n-1, all admitted at begin.  SESSION
     // (tts_hip_orpheus_stream_*): admissions fill the slots, reports and collections free them again.  The device buffers stay on the context from
     // one loop to the next (cap_slots x cap_new) and grow when a begin asks for more ----
-    struct LlamaStream {
+    struct LlamaStream : SlotLedger {               // ENDED: finished, not yet reported (SESSION) / done (BATCH)
         enum Mode : uint8_t { NONE = 0, BATCH = 1, SESSION = 2 };
         Mode mode = NONE;
         bool sampled = false;
         bool mixed = false;                         // begin_mixed: the admissions bring a sampler per utterance; otherwise every admission takes sp (sampled) or sampler::max
         uint32_t n_slots = 0, max_new = 0, stop_id = 0;
         tts_hip_sampling sp{};
-        enum : uint8_t { FREE = 0, LIVE = 1, ENDED = 2, REPORTED = 3 };   // ENDED: finished, not yet reported (SESSION) / done (BATCH)
-        std::vector<uint8_t> slot;                  // per slot, one of the above
         std::vector<uint32_t> count, cur, pos;      // per slot at the last look-in: ids so far, latest id, its position
         std::vector<uint32_t> handed;               // ids of the occupant that a gen_wait (BATCH) or a stream_wait (SESSION, mirrored in d_handed) has handed out
         std::vector<uint32_t> rows;                 // live slots in slot order (= the rows of the next run)
-        uint32_t in_flight = 0;                     // steps enqueued by a launch that no look-in has waited for
-        uint32_t unread = 0;                        // steps enqueued since the last look-in that took ids
         std::vector<uint8_t> slot_sampled, slot_nucleus;   // per slot, what its occupant selects with: sampler::sample / ... with top_p < 1
         size_t cap_slots = 0, cap_new = 0;          // what the buffers below hold
         uint32_t *state = nullptr;                  // device [slots][LLAMA_SLOT_STATE]
@@ -359,6 +351,25 @@ struct tts_hip_ctx {
         std::vector<uint32_t> slot_done;    // [n_slots] the occupant's steps_done once check_stopping() has fired (0: not yet), until the next admission
         std::vector<uint32_t> slot_handed;  // [n_slots] host mirror of gs_handed: rows of the occupant a wait has handed out
         std::vector<uint8_t> slot_pend;     // [n_slots] finished and reported, rows not all handed out yet (until taken, collected over by an admission, or dropped)
+        // a newcomer with a prompt of len ids: live, a row at position len, step 1, bos in every head
+        void push_row(uint32_t s, uint32_t len, int n_out) {
+            slot_live[s] = 1;
+            row_slot.push_back(s); pos.push_back(len); step.push_back(1);
+            ids.insert(ids.end(), (size_t) n_out, bos);
+        }
+        // the rows whose slot keep(slot) accepts stay, in order, and take position, step and ids [row][n_out] from the arrays given (the session's own, or
+        // what the device left); keep is called once per row, in row order
+        template <class Keep>
+        void keep_rows(Keep keep, const uint32_t *pos_src, const uint32_t *step_src, const uint32_t *ids_src, int n_out) {
+            size_t w = 0;
+            for (size_t r = 0; r < row_slot.size(); r++) {
+                if (!keep(row_slot[r])) continue;
+                row_slot[w] = row_slot[r]; pos[w] = pos_src[r]; step[w] = step_src[r];
+                memmove(ids.data() + w * n_out, ids_src + r * n_out, (size_t) n_out * 4);
+                w++;
+            }
+            row_slot.resize(w); pos.resize(w); step.resize(w); ids.resize(w * n_out);
+        }
     } gs;
     // the look-in of a session wait that takes rows (parler_stream_lookin_kernel): the slots to look at {slot, steps so far} go up from h_gs_look_in,
     // one dense block [entries][2 + cap * heads] comes back into h_gs_look; sized by stream_begin for GS_LOOK_ROWS steps, no wait allocates
@@ -530,6 +541,37 @@ static inline bool llama_many_rows(const tts_hip_ctx *c) { return c->has_llama &
 
 // ---- shim_core.hip
 void free_dev(void *p);
+template <typename T>
+static int dmalloc(T **p, size_t n) {   // n zeroed elements
+    HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
+    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
+    return 0;
+}
+// Buffers that grow when a call asks for more than they hold.  The buffers of a group share one capacity, in elements: all are freed and nulled
+// and the capacity zeroed BEFORE `need` elements of each are allocated, and the capacity is recorded only once all exist, so a failed
+// allocation leaves (NULL, 0) and never a stale capacity.  Nothing is synchronised (a caller whose stream may still read the old buffer does
+// that first); *moved says whether the addresses changed, for callers whose captured graphs hold them.  pinned(&p): a host-pinned member.
+template <class T> struct PinnedRef { T **p; };
+template <class T> static PinnedRef<T> pinned(T **p) { return {p}; }
+template <class T> static void buf_release(T **p) { free_dev(*p); *p = nullptr; }
+template <class T> static void buf_release(PinnedRef<T> h) { if (*h.p) (void) hipHostFree(*h.p); *h.p = nullptr; }
+template <class T> static hipError_t buf_alloc(T **p, size_t n) { return hipMalloc((void **) p, n * sizeof(T)); }
+template <class T> static hipError_t buf_alloc(PinnedRef<T> h, size_t n) { return hipHostMalloc((void **) h.p, n * sizeof(T)); }
+template <class Cap, class... B>
+static int grow_bufs(Cap *cap, size_t need, bool *moved, B... bufs) {
+    if (moved) *moved = false;
+    if (need <= (size_t) *cap) return 0;
+    (buf_release(bufs), ...);
+    *cap = 0;
+    if (moved) *moved = true;
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? buf_alloc(bufs, need) : e), ...);
+    if (e != hipSuccess) return set_err("growing a buffer to %zu elements -> %s", need, hipGetErrorString(e));
+    *cap = (Cap) need;
+    return 0;
+}
+template <class T, class Cap> static int grow_dev(T **p, Cap *cap, size_t need, bool *moved = nullptr) { return grow_bufs(cap, need, moved, p); }
+template <class T, class Cap> static int grow_pinned(T **p, Cap *cap, size_t need) { return grow_bufs(cap, need, nullptr, pinned(p)); }
 void arena_own(tts_hip_ctx *c);
 void arena_share(tts_hip_ctx *c);
 int arena_sharers(tts_hip_ctx *c);   // contexts that hold a reference on c's arena (1: c alone)

@@ -1,7 +1,6 @@
 // shim_llama.hip — the Orpheus (Llama-3) decoder step and Dia, on the row-streaming GEMV kernels.
-#include "shim_internal.h"
+#include "shim_session.h"
 
-#include "parler_kernels.h"
 #include "gemv_stream_kernels.h"
 #include "t5_kernels.h"
 #include "llama_kernels.h"
@@ -525,12 +524,7 @@ static int llama_gen_launch_one(tts_hip_ctx *c, const char *what, uint32_t n_ste
     const tts_hip_sampling *sp = g.sampled ? &g.sp : nullptr;
     const uint32_t pos = g.pos;
     const uint32_t steps = std::min<uint32_t>(std::min<uint32_t>(n_steps, g.max_new - (uint32_t) g.toks.size()), c->lm.n_ctx - pos);
-    if (steps > c->h_hist_cap) {
-        if (c->h_hist) { (void) hipHostFree(c->h_hist); c->h_hist = nullptr; c->h_hist_cap = 0; }
-        const size_t cap = std::max<size_t>(steps, 64);
-        HIPCHK(hipHostMalloc((void **) &c->h_hist, cap * 4));
-        c->h_hist_cap = cap;
-    }
+    if (steps > c->h_hist_cap) CHK(grow_pinned(&c->h_hist, &c->h_hist_cap, std::max<size_t>(steps, 64)));
     uint32_t *hist = c->l_tok + 1 + 2 * ARGMAX_PARTS, *hist_idx = hist + LLAMA_GREEDY_CHUNK;
     HIPCHK(hipMemcpyAsync(c->l_ids, &g.cur, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->l_pos, &g.pos, 4, hipMemcpyHostToDevice, c->stream));
@@ -762,23 +756,14 @@ static int llama_stream_ready(tts_hip_ctx *c, const char *what, bool need_sessio
     return 0;
 }
 
-// between a tts_hip_orpheus_stream_launch and its stream_wait the steps may still be running: nothing else touches the session
-static int llama_stream_idle(const tts_hip_ctx *c, const char *what) {
-    return c->ls.in_flight ? set_err("%s: %u steps are in flight (tts_hip_orpheus_stream_wait first)", what, c->ls.in_flight) : 0;
-}
+static const char *const LLAMA_WAIT = "tts_hip_orpheus_stream_wait", *const LLAMA_RUN = "tts_hip_orpheus_stream_run";   // as SlotLedger's texts name them
 
 // one slot's record and table, as the rows kernels read them: sp NULL is sampler::max; the table is stage_penalty's for sp's penalty, len entries
+// (all 0.0 where the penalty is 1)
 static void llama_slot_sampler_host(const tts_hip_sampling *sp, int len, llama_slot_sampler *rec, double *table) {
     *rec = sp ? llama_slot_sampler{LLAMA_SLOT_SAMPLE, sp->top_k, sp->temperature, sp->top_p} : llama_slot_sampler{LLAMA_SLOT_MAX, 0u, 1.0f, 1.0f};
-    const bool rep = sp && sp->repetition_penalty != 1.0f;
-    for (int i = 0; i < len; i++) table[i] = rep ? pow((double) sp->repetition_penalty, (double) i) : 0.0;
-}
-
-template <typename T>
-static int dmalloc(T **p, size_t n) {
-    HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
+    if (sp && sp->repetition_penalty != 1.0f) penalty_table(table, sp->repetition_penalty, len);
+    else std::fill(table, table + len, 0.0);
 }
 
 static void llama_loop_free(tts_hip_ctx *c) {
@@ -1072,7 +1057,7 @@ static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint
     auto &g = c->ls;
     if (mixed != g.mixed)
         return set_err(g.mixed ? "%s: the session carries a sampler per slot (tts_hip_orpheus_stream_admit_mixed)" : "%s: the session has one sampler (tts_hip_orpheus_stream_admit)", what);
-    CHK(llama_stream_idle(c, what));
+    CHK(g.idle(what, LLAMA_WAIT));
     if (n == 0) return 0;
     if (!slots || !prompts || !n_prompt) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_new]", what);
@@ -1084,11 +1069,9 @@ static int llama_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint
             if (!uniforms) return set_err("%s: a sampled utterance needs the uniforms [n][max_new]", what);
         }
     }
+    CHK(g.check_list(what, n, slots, LS::ADMIT));
     size_t off = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
-        if (g.slot[slots[i]] == LS::LIVE || g.slot[slots[i]] == LS::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
         if (n_prompt[i] == 0 || n_prompt[i] >= c->lm.n_ctx) return set_err("%s: utterance %u: a prompt of %u ids does not fit %u cached positions", what, i, n_prompt[i], c->lm.n_ctx);
         for (uint32_t j = 0; j < n_prompt[i]; j++)
             if (prompts[off + j] >= (uint32_t) c->l_V) return set_err("%s: token id %u >= vocabulary %d", what, prompts[off + j], c->l_V);
@@ -1113,26 +1096,14 @@ extern "C" int tts_hip_orpheus_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, co
     return llama_stream_admit(c, "tts_hip_orpheus_stream_admit_mixed", true, n, slots, prompts, n_prompt, sampling, uniforms);
 }
 
-// slots a look-in saw finished and no call has reported yet, in slot order
-static void llama_stream_report(tts_hip_ctx *c, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_counts) {
-    auto &g = c->ls;
-    *n_finished = 0;
-    for (uint32_t s = 0; s < g.n_slots; s++) {
-        if (g.slot[s] != LS::ENDED) continue;
-        finished_slots[*n_finished] = s;
-        finished_counts[*n_finished] = g.count[s];
-        (*n_finished)++;
-        g.slot[s] = LS::REPORTED;
-    }
-}
-
 extern "C" int tts_hip_orpheus_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
     const char *what = "tts_hip_orpheus_stream_launch";
     CHK(llama_stream_ready(c, what));
-    CHK(llama_stream_idle(c, what));
+    CHK(c->ls.idle(what, LLAMA_WAIT));
     return llama_loop_launch(c, what, n_steps);
 }
 
+// a look-in, then the slots it or an earlier one saw finished and no call has reported yet
 extern "C" int tts_hip_orpheus_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uint32_t *n_out, uint8_t *done, uint32_t *n_finished, uint32_t *finished_slots,
                                            uint32_t *finished_counts) {
     const char *what = "tts_hip_orpheus_stream_wait";
@@ -1140,7 +1111,7 @@ extern "C" int tts_hip_orpheus_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out,
     if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
     *n_finished = 0;
     CHK(llama_loop_look(c, tokens_out, n_out, done));
-    llama_stream_report(c, n_finished, finished_slots, finished_counts);
+    c->ls.report(c->ls.count, n_finished, finished_slots, finished_counts);
     return 0;
 }
 
@@ -1150,9 +1121,9 @@ extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint
     CHK(llama_stream_ready(c, what));
     if (!n_finished || !finished_slots || !finished_counts) return set_err("%s: null argument", what);
     *n_finished = 0;
-    CHK(llama_stream_idle(c, what));
+    CHK(c->ls.idle(what, LLAMA_WAIT));
     CHK(llama_loop_run(c, what, n_steps));
-    llama_stream_report(c, n_finished, finished_slots, finished_counts);
+    c->ls.report(c->ls.count, n_finished, finished_slots, finished_counts);
     return 0;
 }
 
@@ -1161,15 +1132,11 @@ extern "C" int tts_hip_orpheus_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint
 extern "C" int tts_hip_orpheus_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
     const char *what = "tts_hip_orpheus_stream_drop";
     CHK(llama_stream_ready(c, what));
-    CHK(llama_stream_idle(c, what));
     auto &g = c->ls;
+    CHK(g.idle(what, LLAMA_WAIT));
     if (n == 0) return 0;
     if (!slots) return set_err("%s: null argument", what);
-    for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n_slots);
-        if (g.slot[slots[i]] != LS::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
-    }
+    CHK(g.check_list(what, n, slots, LS::DROP));
     for (uint32_t i = 0; i < n; i++) g.slot[slots[i]] = LS::FREE;
     llama_loop_live_rows(c);
     return 0;
@@ -1178,11 +1145,9 @@ extern "C" int tts_hip_orpheus_stream_drop(tts_hip_ctx *c, uint32_t n, const uin
 extern "C" int tts_hip_orpheus_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t count, uint32_t *tokens_out) {
     const char *what = "tts_hip_orpheus_stream_collect";
     CHK(llama_stream_ready(c, what));
-    CHK(llama_stream_idle(c, what));
     auto &g = c->ls;
-    if (slot >= g.n_slots) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n_slots);
-    if (g.slot[slot] != LS::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_orpheus_stream_run reports it)", what, slot);
-    if (count > g.count[slot]) return set_err("%s: slot %u produced %u ids, %u asked for", what, slot, g.count[slot], count);
+    CHK(g.idle(what, LLAMA_WAIT));
+    CHK(g.check_collect(what, slot, count, g.count, LLAMA_RUN, "produced", "ids"));
     if (count == 0) return 0;
     if (!tokens_out) return set_err("%s: null argument", what);
     HIPCHK(hipSetDevice(c->device));
@@ -1752,10 +1717,8 @@ static int dia_stream_ready(tts_hip_ctx *c, const char *what, bool need_session 
     return 0;
 }
 
-// a session's launch must be followed by a wait: admit, collect, drop and a second launch find the state they read or write still moving
-static int dia_stream_idle(tts_hip_ctx *c, const char *what) {
-    return c->dl.in_flight ? set_err("%s: %u steps are in flight (tts_hip_dia_stream_wait first)", what, c->dl.in_flight) : 0;
-}
+// a session's launch must be followed by a wait (SlotLedger::idle): admit, collect, drop and a second launch find the state they read or write still moving
+static const char *const DIA_WAIT = "tts_hip_dia_stream_wait", *const DIA_RUN = "tts_hip_dia_stream_run";
 
 static DiaLoopArgs dia_loop_args(tts_hip_ctx *c) {
     const auto &g = c->dl;
@@ -1838,13 +1801,7 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
             HIPCHK(hipMalloc(&c->di_srec, (size_t) DU * sizeof(SampleRow)));
             HIPCHK(hipMalloc(&c->di_srec_in, (size_t) DU * sizeof(SampleRow)));
         }
-        if ((size_t) DU * max_gen > c->di_spen_cap) {   // nothing is in flight (dia_loop_end), and no captured launch holds these
-            free_dev(c->di_spen); free_dev(c->di_spen_in);
-            c->di_spen = c->di_spen_in = nullptr; c->di_spen_cap = 0;
-            HIPCHK(hipMalloc((void **) &c->di_spen, (size_t) DU * max_gen * 8));
-            HIPCHK(hipMalloc((void **) &c->di_spen_in, (size_t) DU * max_gen * 8));
-            c->di_spen_cap = (size_t) DU * max_gen;
-        }
+        CHK(grow_bufs(&c->di_spen_cap, (size_t) DU * max_gen, nullptr, &c->di_spen, &c->di_spen_in));   // nothing is in flight (dia_loop_end), and no captured launch holds these
         c->di_spen_len = (int) max_gen;
         HIPCHK(hipMemsetAsync(c->di_srec, 0, (size_t) DU * sizeof(SampleRow), c->stream));   // SAMPLE_ROW_MAX, no table
     }
@@ -2046,16 +2003,13 @@ static int dia_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32
     if (mixed != g.mixed)
         return set_err(mixed ? "%s: the session was opened by tts_hip_dia_stream_begin (tts_hip_dia_stream_admit)"
                              : "%s: the session was opened by tts_hip_dia_stream_begin_mixed (tts_hip_dia_stream_admit_mixed)", what);
-    CHK(dia_stream_idle(c, what));
+    CHK(g.idle(what, DIA_WAIT));
     if (n == 0) return 0;
     if (!slots || !tokens || !sentence_len) return set_err("%s: null argument", what);
     if (g.sampled && !uniforms) return set_err("%s: a sampled session needs the utterances' uniforms [n][max_gen][n_output_heads]", what);
     const int S = (int) c->dia.max_ctx, NO = c->NO;
-    bool any_sampled = g.sampled, any_rep = false;
+    CHK(g.check_list(what, n, slots, DL::ADMIT));
     for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n);
-        if (g.slot[slots[i]] == DL::LIVE || g.slot[slots[i]] == DL::ENDED) return set_err("%s: slot %u is busy", what, slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
         if (sentence_len[i] == 0 || sentence_len[i] > (uint32_t) S) return set_err("%s: utterance %u: sentence length %u outside 1..%d", what, i, sentence_len[i], S);
         if (budget && (budget[i] <= g.codes.max_delay || budget[i] > g.max_gen))
             return set_err("%s: utterance %u: budget %u outside max_delay %u < budget <= max_gen %u", what, i, budget[i], g.codes.max_delay, g.max_gen);
@@ -2065,17 +2019,18 @@ static int dia_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32
         if (!sp) continue;
         if (!dia_sampling_ok(sp)) return set_err("%s: utterance %u: temperature, top_p, repetition_penalty must be > 0", what, i);
         if (!uniforms) return set_err("%s: utterance %u is sampled: it needs uniforms [n][max_gen][n_output_heads]", what, i);
-        any_sampled = true;
-        any_rep = any_rep || sp->repetition_penalty != 1.0f;
     }
+    // a mixed session: per utterance its record and its penalty table, for the staging copies
+    const int len = c->di_spen_len;
+    bool any_sampled = g.sampled, any_rep = false;
+    std::vector<SampleRow> recs;
+    std::vector<double> tabs;
+    if (mixed) build_sample_rows(n, sampling, len, [&](uint32_t i) { return c->di_spen + (size_t) slots[i] * len; }, recs, tabs, &any_sampled, &any_rep);
     HIPCHK(hipSetDevice(c->device));
     const size_t per = (size_t) g.max_gen * NO;
     if (any_sampled && n * per > c->di_suni_cap) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->di_suni);
-        c->di_suni = nullptr; c->di_suni_cap = 0;
-        HIPCHK(hipMalloc((void **) &c->di_suni, n * per * 4));
-        c->di_suni_cap = n * per;
+        CHK(grow_dev(&c->di_suni, &c->di_suni_cap, n * per));
     }
     // the encoder and the cross K/V of each slot (stream order: the running slots' steps of the last run are behind us), then one launch for all
     for (uint32_t i = 0; i < n; i++) {
@@ -2086,23 +2041,7 @@ static int dia_stream_admit(tts_hip_ctx *c, const char *what, bool mixed, uint32
     for (uint32_t i = 0; i < n; i++) { adm[i] = slots[i]; adm[(size_t) n + i] = budget ? budget[i] : g.max_gen; }
     HIPCHK(hipMemcpyAsync(c->di_sadm, adm.data(), adm.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (any_sampled) HIPCHK(hipMemcpyAsync(c->di_suni, uniforms, n * per * 4, hipMemcpyHostToDevice, c->stream));
-    // a mixed session: per utterance its record, and pow(penalty, count) in double as stage_penalty evaluates it, into the staging copies
-    const int len = c->di_spen_len;
-    std::vector<SampleRow> recs(mixed ? n : 0);
-    std::vector<double> tabs(mixed && any_rep ? (size_t) n * len : 0);
     if (mixed) {
-        for (uint32_t i = 0; i < n; i++) {
-            const tts_hip_sampling *sp = sampling ? sampling[i] : nullptr;
-            SampleRow &r = recs[i];
-            r = SampleRow{};
-            r.mode = sp ? SAMPLE_ROW_SAMPLE : SAMPLE_ROW_MAX;
-            r.top_k = sp ? sp->top_k : 0u; r.top_p = sp ? sp->top_p : 1.0f; r.temperature = sp ? sp->temperature : 1.0f;
-            r.pen_len = len;
-            if (sp && sp->repetition_penalty != 1.0f) {
-                r.pen_table = c->di_spen + (size_t) slots[i] * len;
-                for (int k = 0; k < len; k++) tabs[(size_t) i * len + k] = pow((double) sp->repetition_penalty, (double) k);
-            }
-        }
         HIPCHK(hipMemcpyAsync(c->di_srec_in, recs.data(), recs.size() * sizeof(SampleRow), hipMemcpyHostToDevice, c->stream));
         if (any_rep) HIPCHK(hipMemcpyAsync(c->di_spen_in, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -2141,23 +2080,10 @@ extern "C" int tts_hip_dia_stream_admit_mixed(tts_hip_ctx *c, uint32_t n, const 
     return dia_stream_admit(c, "tts_hip_dia_stream_admit_mixed", true, n, slots, tokens, sentence_len, budget, sampling, uniforms);
 }
 
-// slots a look-in saw parked and no call has reported yet, in slot order
-static void dia_stream_report(tts_hip_ctx *c, uint32_t *n_finished, uint32_t *finished_slots, uint32_t *finished_steps) {
-    auto &g = c->dl;
-    *n_finished = 0;
-    for (uint32_t s = 0; s < g.n; s++) {
-        if (g.slot[s] != DL::ENDED) continue;
-        finished_slots[*n_finished] = s;
-        finished_steps[*n_finished] = g.steps[s];
-        (*n_finished)++;
-        g.slot[s] = DL::REPORTED;
-    }
-}
-
 extern "C" int tts_hip_dia_stream_launch(tts_hip_ctx *c, uint32_t n_steps) {
     const char *what = "tts_hip_dia_stream_launch";
     CHK(dia_stream_ready(c, what));
-    CHK(dia_stream_idle(c, what));
+    CHK(c->dl.idle(what, DIA_WAIT));
     return dia_loop_launch(c, n_steps);
 }
 
@@ -2168,7 +2094,7 @@ extern "C" int tts_hip_dia_stream_wait(tts_hip_ctx *c, uint32_t *tokens_out, uin
     if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
     *n_finished = 0;
     CHK(dia_loop_look(c, tokens_out, steps_done, done));
-    dia_stream_report(c, n_finished, finished_slots, finished_steps);
+    c->dl.report(c->dl.steps, n_finished, finished_slots, finished_steps);
     return 0;
 }
 
@@ -2178,25 +2104,21 @@ extern "C" int tts_hip_dia_stream_run(tts_hip_ctx *c, uint32_t n_steps, uint32_t
     CHK(dia_stream_ready(c, what));
     if (!n_finished || !finished_slots || !finished_steps) return set_err("%s: null argument", what);
     *n_finished = 0;
-    CHK(dia_stream_idle(c, what));
+    CHK(c->dl.idle(what, DIA_WAIT));
     CHK(dia_loop_launch(c, n_steps));
     if (c->dl.in_flight) CHK(dia_loop_look(c, nullptr, nullptr, nullptr));
-    dia_stream_report(c, n_finished, finished_slots, finished_steps);
+    c->dl.report(c->dl.steps, n_finished, finished_slots, finished_steps);
     return 0;
 }
 
 extern "C" int tts_hip_dia_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_t *slots) {
     const char *what = "tts_hip_dia_stream_drop";
     CHK(dia_stream_ready(c, what));
-    CHK(dia_stream_idle(c, what));
+    CHK(c->dl.idle(what, DIA_WAIT));
     auto &g = c->dl;
     if (n == 0) return 0;
     if (!slots) return set_err("%s: null argument", what);
-    for (uint32_t i = 0; i < n; i++) {
-        if (slots[i] >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slots[i], g.n);
-        if (g.slot[slots[i]] != DL::LIVE) return set_err("%s: slot %u is not live", what, slots[i]);
-        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return set_err("%s: slot %u named twice", what, slots[i]);
-    }
+    CHK(g.check_list(what, n, slots, DL::DROP));
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(c->di_sadm, slots, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));   // n <= n_slots <= max_utterances
     DiaDropArgs a{};
@@ -2212,11 +2134,9 @@ extern "C" int tts_hip_dia_stream_drop(tts_hip_ctx *c, uint32_t n, const uint32_
 extern "C" int tts_hip_dia_stream_collect(tts_hip_ctx *c, uint32_t slot, uint32_t steps, uint32_t *tokens_out) {
     const char *what = "tts_hip_dia_stream_collect";
     CHK(dia_stream_ready(c, what));
-    CHK(dia_stream_idle(c, what));
+    CHK(c->dl.idle(what, DIA_WAIT));
     auto &g = c->dl;
-    if (slot >= g.n) return set_err("%s: slot %u >= n_slots %u", what, slot, g.n);
-    if (g.slot[slot] != DL::REPORTED) return set_err("%s: slot %u has not finished (tts_hip_dia_stream_run reports it)", what, slot);
-    if (steps > g.steps[slot]) return set_err("%s: slot %u made %u steps, %u asked for", what, slot, g.steps[slot], steps);
+    CHK(g.check_collect(what, slot, steps, g.steps, DIA_RUN, "made", "steps"));
     if (steps == 0) return 0;
     if (!tokens_out) return set_err("%s: null argument", what);
     HIPCHK(hipSetDevice(c->device));
