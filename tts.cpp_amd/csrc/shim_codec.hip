@@ -2,6 +2,8 @@
 // which runs its convolutions on the codec's MFMA conv launchers.
 #include "shim_internal.h"
 
+#include <type_traits>
+
 #include "dac_kernels.h"
 #include "dac_b3_kernels.h"
 #include "kokoro_kernels.h"
@@ -19,204 +21,74 @@ static int dac_snapshot(tts_hip_ctx *c, int stage, const float *dev, size_t C, s
     return 0;
 }
 
-// ---- MFMA tile selection (shared by the packer and the launchers) ---------------------------------
-// input channels per LDS chunk of the fp32 k=1 kernels: 16 keeps the footprint at 40-45 KB (3-4 workgroups per CU);
-// with 32 the 96- and 64-channel tiles needed 80-90 KB = ONE workgroup per CU, and a k=1 conv has only C/32 chunks to
-// pipeline over, so its residual loads and stores ran with nothing to overlap (0.88 TB/s)
-#define CI32_K1 16
-// k=7: 4 channels per chunk (40 KB, 4 workgroups per CU) measured 3.7 % faster than 8 (75 KB, 2 per CU)
-#ifndef CI32_T
-#define CI32_T 8
-#endif
-#ifndef CI32_K7
-#define CI32_K7 4
-#endif
-static int conv_tile(int cout, int K, int *CO_T, int *CI_T) {
-    if (K != 7 && K != 1) return -1;
-    *CI_T = K == 7 ? CI32_K7 : CI32_K1;
-    if (cout % 128 == 0) { *CO_T = 128; return 0; }
-    if (cout % 96 == 0 && cout % 64 != 0) { *CO_T = 96; return 1; }
-    if (cout % 64 == 0) { *CO_T = 64; return 2; }
-    return -1;
+// ---- the packed images (c->images; what each weight gets is codec_plan's decision, codec_plan.h) -----------------------------------
+static const CodecImage *find_image(const tts_hip_ctx *c, size_t w_off) {
+    auto it = c->images.find(w_off);
+    return it == c->images.end() ? nullptr : &it->second;
 }
-// the k = 1 conv of a residual unit at <= 192 channels goes through conv1x1_direct_kernel (96-channel tiles; fp32 tensors only)
-static bool conv1_direct(const tts_hip_ctx *c, int cout, int cin) {
-    return c->dac_conv1_direct && !c->dac_f16 && cout == cin && (cin == 96 || cin == 192);
-}
-static int convt_tile(int cout, int s, int *CO_T) {
-    if (s == 8 && cout % 64 == 0) { *CO_T = 64; return 0; }
-    if (s == 4 && cout % 64 == 0) { *CO_T = 64; return 1; }
-    if (s == 2 && cout % 96 == 0) { *CO_T = 96; return 2; }
-    if (s == 2 && cout % 64 == 0) { *CO_T = 64; return 3; }
-    return -1;
-}
-
-static int pack_one(tts_hip_ctx *c, size_t w_off, int cout, int cin, int KT, int CO_T, int CI_T, bool transposed) {
-    const int n_chunks = (cin + CI_T - 1) / CI_T;
-    const size_t n = (size_t) ((cout + CO_T - 1) / CO_T) * n_chunks * KT * CI_T * CO_T;
-    float *dst = nullptr;
-    HIPCHK(hipMalloc((void **) &dst, n * 4));
-    hipLaunchKernelGGL(pack_conv_w_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + w_off), dst, cout, cin, KT,
-                       CO_T, CI_T, n_chunks, transposed ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    c->packed[w_off] = dst;
+static bool image_is(const tts_hip_ctx *c, size_t w_off, uint8_t kind) { const CodecImage *im = find_image(c, w_off); return im && im->kind == kind; }
+// one image: allocation, optional clear, the pack launch (launch(dst)), its check, the table entry.  An error leaves nothing behind
+template <class Launch>
+static int pack_image(tts_hip_ctx *c, size_t w_off, CodecImage meta, size_t elems, size_t elem_size, bool zero_first, Launch launch) {
+    void *dst = nullptr;
+    HIPCHK(hipMalloc(&dst, elems * elem_size));
+    hipError_t e = zero_first ? hipMemsetAsync(dst, 0, elems * elem_size, c->stream) : hipSuccess;
+    if (e == hipSuccess) { launch(dst); e = hipGetLastError(); }
+    if (e != hipSuccess) { (void) hipFree(dst); return set_err("packing a codec weight image of %zu bytes -> %s", elems * elem_size, hipGetErrorString(e)); }
+    meta.w = dst;
+    c->images[w_off] = meta;
+    c->plane_images += meta.kind == IMG_PLANES;
+    c->codec_packs++;
     return 0;
 }
-
-// one-time re-layout of the DAC conv weights into MFMA LDS images (after the arena holds the weights,
-// i.e. also after an RCCL broadcast filled it)
-static int pack_one16(tts_hip_ctx *c, size_t w_off, int cout, int cin, int KT, int CO_T, int CI_T, bool transposed) {
-    const int n_chunks = (cin + CI_T - 1) / CI_T;
-    const size_t n = (size_t) ((cout + CO_T - 1) / CO_T) * n_chunks * KT * CI_T * CO_T;
-    _Float16 *dst = nullptr;
-    HIPCHK(hipMalloc((void **) &dst, n * 2));
-    hipLaunchKernelGGL(pack_conv_w16_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + w_off), dst, cout, cin, KT,
-                       CO_T, CI_T, n_chunks, transposed ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    c->packed16[w_off] = dst;
-    return 0;
-}
-// operand split of the plane kernels (dac_kernels.h): 0 = bf16 x 3 / six products, 1 = fp16 hi + lo / three products (F32 tensors), 2 = fp16 / one product (F16 tensors)
-static int dac_scheme(const tts_hip_ctx *c) { return c->dac_f16 ? 2 : (c->dac_split ? 1 : 0); }
-// scheme: 0 = three bf16 planes, 1 = fp16 hi + lo (conv1d_mfma_b3_kernel<.., SplitB3 / SplitH2>)
-static int b3_scheme(const tts_hip_ctx *c) { return c->has_kokoro ? (c->kk_split ? 1 : 0) : (c->dac_split ? 1 : 0); }
-static int pack_one_b3(tts_hip_ctx *c, size_t w_off, int cout, int cin, int CO_T, int KT = 7) {   // 64- or 96-channel tiles, 8 input channels per chunk, tap pairs
-    const int n_chunks = (cin + 7) / 8, scheme = b3_scheme(c);
-    const size_t n = (size_t) ((cout + CO_T - 1) / CO_T) * n_chunks * split_planes(scheme) * (2 * ((KT + 1) / 2)) * CO_T * 8;
-    __bf16 *dst = nullptr;
-    HIPCHK(hipMalloc((void **) &dst, n * 2));
-    hipLaunchKernelGGL(pack_conv_w_b3_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + w_off), dst, cout, cin, CO_T, n_chunks, KT, scheme);
-    HIPCHK(hipGetLastError());
-    c->packed_b3[w_off] = dst;
-    return 0;
-}
-// residual units of 96 / 192 channels as one launch (resunit_b3_kernel): k-steps per stage of the k = 7 / k = 1 part
-static bool resunit_shape(int C, int *KS, int *KS2) {
-    if (C == 96) { *KS = 4; *KS2 = 3; return true; }
-    if (C == 192) { *KS = 2; *KS2 = 4; return true; }
-    return false;
-}
-static int pack_resunit(tts_hip_ctx *c, const DRes &r, int C) {
+// one-time re-layout of a conv weight into the image codec_plan gives it (after the arena holds the weights, i.e. also after an RCCL broadcast
+// filled it); w1_off: the k = 1 weight of a fused unit
+static int plan_and_pack(tts_hip_ctx *c, const CodecKnobs &k, CodecRole role, size_t w_off, int cout, int cin, int K, int stride, size_t w1_off = 0, int dil = 1) {
+    const CodecImage p = codec_plan(role, cout, cin, K, stride, k, dil);
+    if (p.kind == IMG_NONE || c->images.count(w_off)) return 0;
+    const float *src = (const float *) (c->arena + w_off), *src1 = (const float *) (c->arena + w1_off);
+    const dim3 g(1024), b(256);
     int KS = 0, KS2 = 0;
-    if (!resunit_shape(C, &KS, &KS2)) return 0;
-    __bf16 *dst = nullptr;
-    if (c->dac_tap7) {   // resunit_t7_kernel: one tap per k-step, stages of {4, 3} / {2, 2, 2, 1} k-steps per 16-channel chunk
-        const int MI = C / 32, SPC = MI == 3 ? 2 : 4, MAXCNT = MI == 3 ? 4 : 2;
-        const size_t WST = (size_t) split_planes(dac_scheme(c)) * MAXCNT * 2 * C * 8;
-        const size_t n = (size_t) ((C / 16) * SPC + (C / 96) * ((C / 16) / KS2) + 1) * WST;
-        HIPCHK(hipMalloc((void **) &dst, n * 2));
-        HIPCHK(hipMemsetAsync(dst, 0, n * 2, c->stream));
-        hipLaunchKernelGGL(pack_resunit_t7_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + r.in_w), (const float *) (c->arena + r.out_w), dst, C, KS2, dac_scheme(c));
-    } else {
-        const ResUnitGeom g = resunit_geom(C, KS, KS2);
-        const size_t n = (size_t) (g.n7 + g.n1 + 1) * g.WST;   // + 1: the prefetch of the stage after the last one stays inside the buffer
-        HIPCHK(hipMalloc((void **) &dst, n * 2));
-        HIPCHK(hipMemsetAsync(dst, 0, n * 2, c->stream));
-        hipLaunchKernelGGL(pack_resunit_b3_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + r.in_w), (const float *) (c->arena + r.out_w), dst, C, KS, KS2);
+    switch (p.kind) {
+    case IMG_F32_TILE: case IMG_F32_DIRECT:
+        return pack_image(c, w_off, p, p.elems, 4, false, [&](void *d) {
+            hipLaunchKernelGGL(pack_conv_w_kernel, g, b, 0, c->stream, src, (float *) d, cout, cin, p.kt, p.co_t, p.ci_t, (cin + p.ci_t - 1) / p.ci_t, (int) p.transposed); });
+    case IMG_F16_TILE:
+        return pack_image(c, w_off, p, p.elems, 2, false, [&](void *d) {
+            hipLaunchKernelGGL(pack_conv_w16_kernel, g, b, 0, c->stream, src, (_Float16 *) d, cout, cin, p.kt, p.co_t, p.ci_t, (cin + p.ci_t - 1) / p.ci_t, (int) p.transposed); });
+    case IMG_B3:
+        return pack_image(c, w_off, p, p.elems, 2, false, [&](void *d) {
+            hipLaunchKernelGGL(pack_conv_w_b3_kernel, g, b, 0, c->stream, src, (__bf16 *) d, cout, cin, p.co_t, (cin + 7) / 8, p.kt, (int) p.scheme); });
+    case IMG_PLANES:
+        return pack_image(c, w_off, p, p.elems, 2, false, [&](void *d) {
+            hipLaunchKernelGGL(pack_conv_w_b3p_kernel, g, b, 0, c->stream, src, (__bf16 *) d, cout, cin, p.kt, p.co_t, p.ns, cin / p.ci_t, (int) p.scheme); });
+    case IMG_CONVT_PLANES:
+        return pack_image(c, w_off, p, p.elems, 2, false, [&](void *d) {
+            hipLaunchKernelGGL(pack_convt_w_b3_kernel, g, b, 0, c->stream, src, (__bf16 *) d, cout, cin, p.kt / 2, p.co_t, cin / 16, (int) p.scheme); });
+    case IMG_UNIT_TAP:
+        resunit_shape(cout, &KS, &KS2);
+        return pack_image(c, w_off, p, p.elems, 2, true, [&](void *d) {
+            hipLaunchKernelGGL(pack_resunit_t7_kernel, g, b, 0, c->stream, src, src1, (__bf16 *) d, cout, KS2, (int) p.scheme); });
+    case IMG_UNIT_PAIR: {
+        resunit_shape(cout, &KS, &KS2);
+        const ResUnitGeom rg = resunit_geom(cout, KS, KS2);
+        if (p.elems != (size_t) (rg.n7 + rg.n1 + 1) * rg.WST) return set_err("codec_plan: the tap-pair unit at %d channels is planned at %zu elements, resunit_geom has %zu", cout, p.elems, (size_t) (rg.n7 + rg.n1 + 1) * rg.WST);
+        return pack_image(c, w_off, p, p.elems, 2, true, [&](void *d) {
+            hipLaunchKernelGGL(pack_resunit_b3_kernel, g, b, 0, c->stream, src, src1, (__bf16 *) d, cout, KS, KS2); });
     }
-    HIPCHK(hipGetLastError());
-    c->packed_ru[r.in_w] = dst;
+    }
     return 0;
 }
-// transposed convs as bf16 x 3 products (convt_b3_kernel): 32 MI output channels per workgroup
-static int convt_b3_tile(int cout, int cin, int s) {
-    if (cin % 16) return 0;
-    if (s == 8 && cout % 32 == 0) return 32;
-    if (s == 4 && cout % 64 == 0) return 64;
-    if (s == 2 && cout % 96 == 0) return 96;
-    return 0;
-}
-static bool convt_b3_fits(int cout, int cin, int s) {   // the kernel's LDS request (weight stages + input planes + alpha) inside a CU's 160 KB (three planes: the largest scheme)
-    const int t = convt_b3_tile(cout, cin, s);
-    return t && (size_t) 6 * (2 * s * 2 * t * 8) * 2 + 6 * 2 * 257 * 8 * 2 + (size_t) cin * 8 <= 160 * 1024;
-}
-static int pack_convt_b3(tts_hip_ctx *c, const DBlock &b) {
-    const int CO_T = convt_b3_tile(b.cout, b.cin, b.stride);
-    if (!CO_T) return 0;
-    const int n_chunks = b.cin / 16;
-    const size_t n = (size_t) (b.cout / CO_T) * n_chunks * split_planes(dac_scheme(c)) * 2 * b.stride * 2 * CO_T * 8;
-    __bf16 *dst = nullptr;
-    HIPCHK(hipMalloc((void **) &dst, n * 2));
-    hipLaunchKernelGGL(pack_convt_w_b3_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + b.w), dst, b.cout, b.cin, b.stride, CO_T, n_chunks, dac_scheme(c));
-    HIPCHK(hipGetLastError());
-    c->packed_ct[b.w] = dst;
-    return 0;
-}
-// wide classes on split planes (conv_b3p_kernel): k = 7 in 64-channel tiles (four k-steps per 8-channel chunk), k = 1 in 128-channel
-// tiles (one k-step = 16 channels per chunk)
-static bool planes_class(const tts_hip_ctx *c, int ch) {
-    int ks = 0, ks2 = 0;
-    return c->dac_planes && c->dac_b3 && (!c->dac_f16 || c->dac_f16_planes) && ch % 128 == 0 && !(c->dac_fuse && resunit_shape(ch, &ks, &ks2));
-}
-static int pack_planes(tts_hip_ctx *c, size_t w_off, int cout, int cin, int KT) {
-    const bool tapk = KT == 7 && c->dac_tap7 && cin % 16 == 0;
-    const int CO_T = KT == 7 ? 64 : (cout % 256 == 0 ? 256 : 128), NS = KT == 7 ? (tapk ? 7 : 4) : 1;
-    const int n_chunks = KT == 7 && !tapk ? cin / 8 : cin / 16;
-    const size_t n = (size_t) (cout / CO_T) * n_chunks * split_planes(dac_scheme(c)) * NS * 2 * CO_T * 8;
-    __bf16 *dst = nullptr;
-    HIPCHK(hipMalloc((void **) &dst, n * 2));
-    hipLaunchKernelGGL(pack_conv_w_b3p_kernel, dim3(1024), dim3(256), 0, c->stream, (const float *) (c->arena + w_off), dst, cout, cin, KT, CO_T, NS, n_chunks, dac_scheme(c));
-    HIPCHK(hipGetLastError());
-    c->packed_p[w_off] = dst;
-    return 0;
-}
-#define CI16_K7 16
-#define CI16_K1 32
-#define CI16_T  16
 
 static int ensure_packed(tts_hip_ctx *c) {
-    if (c->dac_packed || (c->d.flags & TTS_HIP_FLAG_VALU_GEMM)) return 0;
-    int CO_T = 0, CI_T = 0;
-    // F16 codec tensors (quantize --convert-dac-to-f16): since round 6 on the same plane / fused-unit / transposed kernels as F32 tensors, with one fp16
-    // plane and one product (SplitH1: ggml's fp16 im2col x fp16 kernel — the activations a conv consumes rounded to fp16, exact products, fp32
-    // accumulation); layers those kernels do not cover (other channel counts) keep the fp16 tile kernels of round 2 (packed16)
-    const bool f16p = c->dac_f16 && c->dac_f16_planes && c->dac_b3 && c->dac_tap7;
-    if (c->dac_f16 && !f16p) {
-        if (conv_tile(c->d_c0, 7, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, c->d_initw, c->d_c0, c->d_latent, 7, CO_T, CI16_K7, false));
-        for (auto &b : c->dblocks) {
-            if (convt_tile(b.cout, b.stride, &CO_T) >= 0) CHK(pack_one16(c, b.w, b.cout, b.cin, 2 * b.stride, CO_T, CI16_T, true));
-            for (int r = 0; r < 3; r++) {
-                if (conv_tile(b.cout, 7, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, b.res[r].in_w, b.cout, b.cout, 7, CO_T, CI16_K7, false));
-                if (conv_tile(b.cout, 1, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, b.res[r].out_w, b.cout, b.cout, 1, CO_T, CI16_K1, false));
-            }
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->dac_packed = true;
-        return 0;
-    }
-    // Every weight is packed in the ONE image the kernel that will run it stages (the images are as large as the weights: a second format per
-    // tensor would be dead device memory in every context).
-    if (planes_class(c, c->d_c0) && c->d_latent % 8 == 0) CHK(pack_planes(c, c->d_initw, c->d_c0, c->d_latent, 7));
-    else if (f16p) { if (conv_tile(c->d_c0, 7, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, c->d_initw, c->d_c0, c->d_latent, 7, CO_T, CI16_K7, false)); }
-    else if (c->dac_b3 && c->d_c0 % 64 == 0) CHK(pack_one_b3(c, c->d_initw, c->d_c0, c->d_latent, 64));
-    else if (conv_tile(c->d_c0, 7, &CO_T, &CI_T) >= 0) CHK(pack_one(c, c->d_initw, c->d_c0, c->d_latent, 7, CO_T, CI_T, false));
+    if (c->dac_packed) return 0;
+    const CodecKnobs k = codec_knobs(c);
+    CHK(plan_and_pack(c, k, ROLE_INIT, c->d_initw, c->d_c0, c->d_latent, 7, 1));
     for (auto &b : c->dblocks) {
-        if (c->dac_convt_b3 && convt_b3_fits(b.cout, b.cin, b.stride)) CHK(pack_convt_b3(c, b));
-        else if (f16p) { if (convt_tile(b.cout, b.stride, &CO_T) >= 0) CHK(pack_one16(c, b.w, b.cout, b.cin, 2 * b.stride, CO_T, CI16_T, true)); }
-        else if (convt_tile(b.cout, b.stride, &CO_T) >= 0) CHK(pack_one(c, b.w, b.cout, b.cin, 2 * b.stride, CO_T, CI32_T, true));
-        int ks = 0, ks2 = 0;
+        CHK(plan_and_pack(c, k, ROLE_CONVT, b.w, b.cout, b.cin, 2 * b.stride, b.stride));
         for (int r = 0; r < 3; r++) {
-            if (planes_class(c, b.cout)) {   // split planes: conv_b3p_kernel for both convs of the unit
-                CHK(pack_planes(c, b.res[r].in_w, b.cout, b.cout, 7));
-                CHK(pack_planes(c, b.res[r].out_w, b.cout, b.cout, 1));
-                continue;
-            }
-            if (c->dac_fuse && resunit_shape(b.cout, &ks, &ks2)) {   // one launch per unit (dilations 1 / 3 / 9 all qualify)
-                CHK(pack_resunit(c, b.res[r], b.cout));
-                continue;
-            }
-            if (f16p) {
-                if (conv_tile(b.cout, 7, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, b.res[r].in_w, b.cout, b.cout, 7, CO_T, CI16_K7, false));
-                if (conv_tile(b.cout, 1, &CO_T, &CI_T) >= 0) CHK(pack_one16(c, b.res[r].out_w, b.cout, b.cout, 1, CO_T, CI16_K1, false));
-                continue;
-            }
-            if (c->dac_b3 && b.cout % 64 == 0) CHK(pack_one_b3(c, b.res[r].in_w, b.cout, b.cout, 64));
-            else if (c->dac_b3 >= 2 && b.cout % 96 == 0) CHK(pack_one_b3(c, b.res[r].in_w, b.cout, b.cout, 96));
-            else if (conv_tile(b.cout, 7, &CO_T, &CI_T) >= 0) CHK(pack_one(c, b.res[r].in_w, b.cout, b.cout, 7, CO_T, CI_T, false));
-            if (conv1_direct(c, b.cout, b.cout)) {   // [cin][cout] for conv1x1_direct_kernel
-                CHK(pack_one(c, b.res[r].out_w, b.cout, b.cout, 1, b.cout, CI32_K1, false));
-                c->packed_direct.insert(b.res[r].out_w);
-            } else if (conv_tile(b.cout, 1, &CO_T, &CI_T) >= 0) CHK(pack_one(c, b.res[r].out_w, b.cout, b.cout, 1, CO_T, CI_T, false));
+            CHK(plan_and_pack(c, k, ROLE_UNIT7, b.res[r].in_w, b.cout, b.cout, 7, 1, b.res[r].out_w));
+            CHK(plan_and_pack(c, k, ROLE_UNIT1, b.res[r].out_w, b.cout, b.cout, 1, 1));
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -224,90 +96,71 @@ static int ensure_packed(tts_hip_ctx *c) {
     return 0;
 }
 
+// ---- launch plumbing ---------------------------------------------------------------------------------------------------------------
+// A launch with up to a CU's 160 KB of dynamic LDS: the attribute is set once per device and kernel instantiation
+template <auto Kernel, class Args>
+static int launch_lds(tts_hip_ctx *c, dim3 grid, int threads, size_t lds, const Args &a) {
+    static std::atomic<uint64_t> attr{0};
+    if (attr_needed(attr, c->device)) HIPCHK(hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// f(SplitB3{} / SplitH2{} / SplitH1{}) for the operand split an image was packed for (dac_kernels.h)
+template <class F>
+static int with_split(int scheme, F f) { return scheme == 0 ? f(SplitB3{}) : scheme == 1 ? f(SplitH2{}) : f(SplitH1{}); }
+
 // LDS request of a codec kernel: the tile buffers plus snake's alpha table — unless (keep_residency) the table would cost a resident workgroup.
 // (Leaving LDS free under the codec for another context's decoder workgroups was measured twice and lost: profiles/r02)
-static size_t dac_lds_request(const tts_hip_ctx *c, size_t base, size_t table, int *use_table, bool keep_residency = false) {
-    (void) c;
+static size_t dac_lds_request(size_t base, size_t table, int *use_table, bool keep_residency = false) {
     const size_t CU = 160 * 1024;
     *use_table = table ? 1 : 0;
     if (table && keep_residency && CU / (base + table) < CU / base) { *use_table = 0; return base; }
     return base + table;
 }
+// elements of one staged input buffer of the tile kernels: T = float (conv1d_mfma_kernel, convt1d_mfma_kernel) packs rows of `w` positions,
+// T = _Float16 (the ...16 kernels) pads each position's channels by 8
+template <typename T>
+static size_t x_stage_elems(int ci_t, int w) { return sizeof(T) == 2 ? (size_t) w * (ci_t + 8) : (size_t) ((ci_t * w + 3) & ~3); }
 
-template <int KT, int MI, int NI, int WM, int WN, int CI_T>
+template <typename T, int KT, int MI, int NI, int WM, int WN, int CI_T>
 static int launch_conv_mfma(tts_hip_ctx *c, const ConvArgs &a_in, int nz) {
     constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WCH = KT * CI_T * CO_T;
+    constexpr bool F16 = sizeof(T) == 2;
     const int xw = T_T + (KT - 1) * a_in.dil;
     const int cin_pad = (a_in.cin + CI_T - 1) / CI_T * CI_T;
     ConvArgs a = a_in;
-    const size_t lds = dac_lds_request(c, ((size_t) 2 * WCH + 2 * (size_t) ((CI_T * xw + 3) & ~3)) * 4, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab);
-    if (a.dil > 9) return set_err("conv1d_mfma: dilation %d > 9 unsupported", a.dil);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) conv1d_mfma_kernel<KT, MI, NI, WM, WN, CI_T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    const size_t lds = dac_lds_request(((size_t) 2 * WCH + 2 * x_stage_elems<T>(CI_T, xw)) * sizeof(T), (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab);
+    if (a.dil > 9) return set_err(F16 ? "conv1d_mfma16: dilation %d > 9 unsupported" : "conv1d_mfma: dilation %d > 9 unsupported", a.dil);
     const dim3 grid((a.L + T_T - 1) / T_T, (a.cout + CO_T - 1) / CO_T, nz);
-    hipLaunchKernelGGL((conv1d_mfma_kernel<KT, MI, NI, WM, WN, CI_T>), grid, dim3(64 * WM * WN), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if constexpr (F16) return launch_lds<conv1d_mfma16_kernel<KT, MI, NI, WM, WN, CI_T>>(c, grid, 64 * WM * WN, lds, a);
+    else return launch_lds<conv1d_mfma_kernel<KT, MI, NI, WM, WN, CI_T>>(c, grid, 64 * WM * WN, lds, a);
+}
+// position tiles per channel-tile class as measured best in profiles/r02/dac_variants.log (fp32: the 96-channel k = 7 class on 128-position tiles)
+template <typename T, int K>
+static int launch_conv_tile(tts_hip_ctx *c, const ConvArgs &a, int nz, int co_t) {
+    constexpr int CI = sizeof(T) == 2 ? (K == 7 ? CI16_K7 : CI16_K1) : (K == 7 ? CI32_K7 : CI32_K1), NI96 = K == 7 && sizeof(T) == 4 ? 1 : 2;
+    if (co_t == 128) return launch_conv_mfma<T, K, 2, 2, 2, 2, CI>(c, a, nz);
+    if (co_t == 96) return launch_conv_mfma<T, K, 3, NI96, 1, 4, CI>(c, a, nz);
+    return launch_conv_mfma<T, K, 2, 2, 1, 4, CI>(c, a, nz);
 }
 
 // k = 7 conv as six bf16 MFMAs per product (experiment): 64 channels x 256 positions per workgroup of 4 waves,
 // or 96 channels x 256 positions per workgroup of 8 waves
-template <int MI, int NI, int WM, int WN, int KT, typename SP>
-static int launch_conv_b3_s(tts_hip_ctx *c, const ConvArgs &a_in, int nz) {
-    constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WPL = 2 * ((KT + 1) / 2) * CO_T * 8;
-    const int xw = T_T + (KT - 1) * a_in.dil;
-    const int cin_pad = (a_in.cin + 7) / 8 * 8;
-    ConvArgs a = a_in;
-    const size_t lds = dac_lds_request(c, ((size_t) 2 * SP::NPL * WPL + 2 * SP::NPL * (size_t) xw * 8) * 2, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab, true);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) conv1d_mfma_b3_kernel<MI, NI, WM, WN, KT, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const dim3 grid((a.L + T_T - 1) / T_T, (a.cout + CO_T - 1) / CO_T, nz);
-    if (lds > 160 * 1024) return set_err("conv1d_mfma_b3: k = %d at dilation %d needs %zu bytes of LDS", KT, a.dil, lds);
-    hipLaunchKernelGGL((conv1d_mfma_b3_kernel<MI, NI, WM, WN, KT, SP>), grid, dim3(64 * WM * WN), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 template <int MI, int NI, int WM, int WN, int KT = 7>
-static int launch_conv_b3(tts_hip_ctx *c, const ConvArgs &a, int nz) {
-    return b3_scheme(c) ? launch_conv_b3_s<MI, NI, WM, WN, KT, SplitH2>(c, a, nz) : launch_conv_b3_s<MI, NI, WM, WN, KT, SplitB3>(c, a, nz);
-}
-
-template <int KT, int MI, int NI, int WM, int WN, int CI_T>
-static int launch_conv_mfma16(tts_hip_ctx *c, const ConvArgs &a_in, int nz) {
-    constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WCH = KT * CI_T * CO_T, XS = CI_T + 8;
-    const int xw = T_T + (KT - 1) * a_in.dil;
-    const int cin_pad = (a_in.cin + CI_T - 1) / CI_T * CI_T;
-    ConvArgs a = a_in;
-    const size_t lds = dac_lds_request(c, ((size_t) 2 * WCH + 2 * (size_t) xw * XS) * 2, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab);
-    if (a.dil > 9) return set_err("conv1d_mfma16: dilation %d > 9 unsupported", a.dil);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) conv1d_mfma16_kernel<KT, MI, NI, WM, WN, CI_T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const dim3 grid((a.L + T_T - 1) / T_T, (a.cout + CO_T - 1) / CO_T, nz);
-    hipLaunchKernelGGL((conv1d_mfma16_kernel<KT, MI, NI, WM, WN, CI_T>), grid, dim3(64 * WM * WN), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-template <int S, int MI, int WM, int WN, int CI_T>
-static int launch_convt_mfma16(tts_hip_ctx *c, const ConvTArgs &a_in, int nz) {
-    constexpr int CO_T = 32 * MI * WM, TI_T = 32 * WN, WCH = CI_T * 2 * S * CO_T, XS = CI_T + 8;
-    const int cin_pad = (a_in.cin + CI_T - 1) / CI_T * CI_T;
-    ConvTArgs a = a_in;
-    const size_t lds = dac_lds_request(c, ((size_t) 2 * WCH + 2 * (size_t) (TI_T + 1) * XS) * 2, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab, true);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) convt1d_mfma16_kernel<S, MI, WM, WN, CI_T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const dim3 grid((a.L + 1 + TI_T - 1) / TI_T, (a.cout + CO_T - 1) / CO_T, nz);  // ti runs 0..L inclusive
-    hipLaunchKernelGGL((convt1d_mfma16_kernel<S, MI, WM, WN, CI_T>), grid, dim3(64 * WM * WN), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+static int launch_conv_b3(tts_hip_ctx *c, const ConvArgs &a_in, int nz, int scheme) {
+    const auto go = [&](auto sp) {
+        using SP = decltype(sp);
+        constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WPL = 2 * ((KT + 1) / 2) * CO_T * 8;
+        const int xw = T_T + (KT - 1) * a_in.dil;
+        const int cin_pad = (a_in.cin + 7) / 8 * 8;
+        ConvArgs a = a_in;
+        const size_t lds = dac_lds_request(((size_t) 2 * SP::NPL * WPL + 2 * SP::NPL * (size_t) xw * 8) * 2, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab, true);
+        if (lds > 160 * 1024) return set_err("conv1d_mfma_b3: k = %d at dilation %d needs %zu bytes of LDS", KT, a.dil, lds);
+        return launch_lds<conv1d_mfma_b3_kernel<MI, NI, WM, WN, KT, SP>>(c, dim3((a.L + T_T - 1) / T_T, (a.cout + CO_T - 1) / CO_T, nz), 64 * WM * WN, lds, a);
+    };
+    // no one-plane form of this kernel is built (F16 tensors never get an IMG_B3 image): two schemes, not with_split's three
+    return scheme == 1 ? go(SplitH2{}) : scheme == 0 ? go(SplitB3{}) : set_err("conv1d_mfma_b3: no form for operand split %d", scheme);
 }
 
 // Row stride of a codec activation [C][L]: L is frames x 2^k, so rows packed back to back start a multiple of 2 KB (up to 496 KB) apart and the
@@ -326,6 +179,8 @@ struct DacBatch {
     double tot_frames = 0;      // sum of frames (for flop/byte accounting)
 };
 
+// The kernel follows from the weight's image.  Read at launch, and an image stays valid either way: TTS_HIP_FLAG_VALU_GEMM (fixed at create:
+// no image is ever planned under it) for the one-channel final conv, and dil <= 9 (what the kernels' LDS holds)
 static int launch_conv(tts_hip_ctx *c, const DacBatch &bt, const float *x, int cin, int L, size_t w, size_t b, size_t alpha, bool has_alpha,
                        int cout, int K, int pad, int dil, const float *resid, bool do_tanh, float *y, size_t alpha_out = 0,
                        bool has_alpha_out = false, bool has_bias = true) {
@@ -340,45 +195,27 @@ static int launch_conv(tts_hip_ctx *c, const DacBatch &bt, const float *x, int c
     const double Lv = bt.tot_frames * bt.mult;  // valid positions over the batch
     const double bytes = ((double) cin * Lv + (double) cout * Lv * (resid ? 2 : 1) + (double) cout * cin * K) * 4;
     CHK(prof_begin(c, cout == 1 ? TTS_HIP_K_DAC_FINAL : (K == 7 ? TTS_HIP_K_DAC_CONV7 : TTS_HIP_K_DAC_CONV1), bytes, 2.0 * cout * (double) cin * K * Lv));
-    const bool valu = (c->d.flags & TTS_HIP_FLAG_VALU_GEMM) != 0;
-    int CO_T = 0, CI_T = 0;
-    const int cfg = valu ? -1 : conv_tile(cout, K, &CO_T, &CI_T);
-    auto pk = c->packed.find(w);
-    auto pk16 = c->packed16.find(w);
-    if (!valu && cout == 1 && K == 7) {
+    const CodecImage *im = find_image(c, w);
+    const uint8_t kind = im ? im->kind : (uint8_t) IMG_NONE;
+    if (!(c->d.flags & TTS_HIP_FLAG_VALU_GEMM) && cout == 1 && K == 7) {
         hipLaunchKernelGGL(conv1d_cout1_kernel, dim3((L + C1_T - 1) / C1_T, 1, bt.n), dim3(256), 0, c->stream, a);
         HIPCHK(hipGetLastError());
-    } else if (!valu && K == 7 && c->dac_b3 && !c->dac_f16 && c->packed_b3.count(w) && dil <= 9) {
-        a.w = (const float *) c->packed_b3[w];   // three bf16 planes (experiment)
-        if (cout % 64 == 0) CHK((launch_conv_b3<2, 1, 1, 8>(c, a, bt.n)));   // 64 ch x 256 pos, 8 waves
-        else CHK((launch_conv_b3<3, 1, 1, 8>(c, a, bt.n)));                                                  // 96 ch x 256 pos, 8 waves
-    } else if (cfg >= 0 && c->dac_f16 && pk16 != c->packed16.end()) {
-        a.w = (const float *) pk16->second;  // fp16 LDS images
-        if (K == 7 && cfg == 0) CHK((launch_conv_mfma16<7, 2, 2, 2, 2, CI16_K7>(c, a, bt.n)));
-        else if (K == 7 && cfg == 1) CHK((launch_conv_mfma16<7, 3, 2, 1, 4, CI16_K7>(c, a, bt.n)));
-        else if (K == 7 && cfg == 2) CHK((launch_conv_mfma16<7, 2, 2, 1, 4, CI16_K7>(c, a, bt.n)));
-        else if (K == 1 && cfg == 0) CHK((launch_conv_mfma16<1, 2, 2, 2, 2, CI16_K1>(c, a, bt.n)));
-        else if (K == 1 && cfg == 1) CHK((launch_conv_mfma16<1, 3, 2, 1, 4, CI16_K1>(c, a, bt.n)));
-        else CHK((launch_conv_mfma16<1, 2, 2, 1, 4, CI16_K1>(c, a, bt.n)));
-    } else if (K == 1 && pk != c->packed.end() && c->packed_direct.count(w) && !a.alpha && !a.alpha_out && !do_tanh) {
-        a.w = pk->second;
-        static std::atomic<uint64_t> attr{0};
-        if (attr_needed(attr, c->device)) {
-            HIPCHK(hipFuncSetAttribute((const void *) conv1x1_direct_kernel<3, 2, 96, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHK(hipFuncSetAttribute((const void *) conv1x1_direct_kernel<6, 1, 192, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
-        if (cin == 96) hipLaunchKernelGGL((conv1x1_direct_kernel<3, 2, 96, 96>), dim3((L + 255) / 256, 1, bt.n), dim3(256), (size_t) 96 * 96 * 4, c->stream, a);
-        else hipLaunchKernelGGL((conv1x1_direct_kernel<6, 1, 192, 48>), dim3((L + 127) / 128, 1, bt.n), dim3(256), (size_t) 48 * 192 * 4, c->stream, a);
-        HIPCHK(hipGetLastError());
-    } else if (cfg >= 0 && pk != c->packed.end()) {
-        a.w = pk->second;
-        // position tiles per channel-tile class as measured best in profiles/r02/dac_variants.log (the 96-channel class on 128-position tiles)
-        if (K == 7 && cfg == 0) CHK((launch_conv_mfma<7, 2, 2, 2, 2, CI32_K7>(c, a, bt.n)));
-        else if (K == 7 && cfg == 1) CHK((launch_conv_mfma<7, 3, 1, 1, 4, CI32_K7>(c, a, bt.n)));   // 96 ch x 128 pos
-        else if (K == 7 && cfg == 2) CHK((launch_conv_mfma<7, 2, 2, 1, 4, CI32_K7>(c, a, bt.n)));
-        else if (K == 1 && cfg == 0) CHK((launch_conv_mfma<1, 2, 2, 2, 2, CI32_K1>(c, a, bt.n)));
-        else if (K == 1 && cfg == 1) CHK((launch_conv_mfma<1, 3, 2, 1, 4, CI32_K1>(c, a, bt.n)));
-        else CHK((launch_conv_mfma<1, 2, 2, 1, 4, CI32_K1>(c, a, bt.n)));
+    } else if (kind == IMG_B3 && dil <= 9) {
+        a.w = (const float *) im->w;   // split planes (experiment)
+        if (im->co_t == 64) CHK((launch_conv_b3<2, 1, 1, 8>(c, a, bt.n, im->scheme)));   // 64 ch x 256 pos, 8 waves
+        else CHK((launch_conv_b3<3, 1, 1, 8>(c, a, bt.n, im->scheme)));                  // 96 ch x 256 pos, 8 waves
+    } else if (kind == IMG_F16_TILE) {
+        a.w = (const float *) im->w;  // fp16 LDS images
+        if (K == 7) CHK((launch_conv_tile<_Float16, 7>(c, a, bt.n, im->co_t)));
+        else CHK((launch_conv_tile<_Float16, 1>(c, a, bt.n, im->co_t)));
+    } else if (kind == IMG_F32_DIRECT && !a.alpha && !a.alpha_out && !do_tanh) {
+        a.w = (const float *) im->w;
+        if (cin == 96) CHK((launch_lds<conv1x1_direct_kernel<3, 2, 96, 96>>(c, dim3((L + 255) / 256, 1, bt.n), 256, (size_t) 96 * 96 * 4, a)));
+        else CHK((launch_lds<conv1x1_direct_kernel<6, 1, 192, 48>>(c, dim3((L + 127) / 128, 1, bt.n), 256, (size_t) 48 * 192 * 4, a)));
+    } else if (kind == IMG_F32_TILE) {
+        a.w = (const float *) im->w;
+        if (K == 7) CHK((launch_conv_tile<float, 7>(c, a, bt.n, im->co_t)));
+        else CHK((launch_conv_tile<float, 1>(c, a, bt.n, im->co_t)));
     } else {
         const dim3 grid((L + CV_T - 1) / CV_T, (cout + CV_CO - 1) / CV_CO, bt.n);
         const size_t lds = ((size_t) CV_CI * (CV_T + (K - 1) * dil) + (size_t) CV_CI * K * CV_CO) * 4;
@@ -390,78 +227,55 @@ static int launch_conv(tts_hip_ctx *c, const DacBatch &bt, const float *x, int c
     return prof_end(c);
 }
 
-template <int S, int MI, int WM, int WN, int CI_T>
+template <typename T, int S, int MI, int WM, int WN, int CI_T>
 static int launch_convt_mfma(tts_hip_ctx *c, const ConvTArgs &a_in, int nz) {
     constexpr int CO_T = 32 * MI * WM, TI_T = 32 * WN, WCH = CI_T * 2 * S * CO_T;
     const int cin_pad = (a_in.cin + CI_T - 1) / CI_T * CI_T;
     ConvTArgs a = a_in;
-    const size_t lds = dac_lds_request(c, ((size_t) 2 * WCH + 2 * (size_t) ((CI_T * (TI_T + 1) + 3) & ~3)) * 4, (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab, true);   // two resident workgroups matter more to the transposed convs than the table
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) convt1d_mfma_kernel<S, MI, WM, WN, CI_T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    // two resident workgroups matter more to the transposed convs than the table
+    const size_t lds = dac_lds_request(((size_t) 2 * WCH + 2 * x_stage_elems<T>(CI_T, TI_T + 1)) * sizeof(T), (a.alpha ? 2 * (size_t) cin_pad : 0) * 4, &a.alpha_tab, true);
     const dim3 grid((a.L + 1 + TI_T - 1) / TI_T, (a.cout + CO_T - 1) / CO_T, nz);  // ti runs 0..L inclusive
-    hipLaunchKernelGGL((convt1d_mfma_kernel<S, MI, WM, WN, CI_T>), grid, dim3(64 * WM * WN), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if constexpr (sizeof(T) == 2) return launch_lds<convt1d_mfma16_kernel<S, MI, WM, WN, CI_T>>(c, grid, 64 * WM * WN, lds, a);
+    else return launch_lds<convt1d_mfma_kernel<S, MI, WM, WN, CI_T>>(c, grid, 64 * WM * WN, lds, a);
+}
+template <typename T>
+static int launch_convt_tile(tts_hip_ctx *c, const ConvTArgs &a, int nz, int co_t) {
+    constexpr int CI = sizeof(T) == 2 ? CI16_T : CI32_T;
+    if (a.stride == 8) return launch_convt_mfma<T, 8, 1, 2, 2, CI>(c, a, nz);
+    if (a.stride == 4) return launch_convt_mfma<T, 4, 2, 1, 4, CI>(c, a, nz);
+    if (co_t == 96) return launch_convt_mfma<T, 2, 3, 1, 4, CI>(c, a, nz);
+    return launch_convt_mfma<T, 2, 2, 1, 4, CI>(c, a, nz);
 }
 
-template <int S, int MI, bool PL, typename SP>
-static int launch_convt_b3_t(tts_hip_ctx *c, const ConvTArgs &a, int nz) {
-    constexpr int CO_T = 32 * MI, WPL = 2 * S * 2 * CO_T * 8, xpl = 2 * 257 * 8;
-    const size_t lds = (size_t) 2 * SP::NPL * WPL * 2 + (size_t) 2 * SP::NPL * xpl * 2 + (size_t) a.cin * 8;
-    if (lds > 160 * 1024) return set_err("convt_b3: %d input channels need %zu bytes of LDS", a.cin, lds);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) convt_b3_kernel<S, MI, PL, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    ConvTArgs b = a;
-    b.npos = (a.L + 1 + 255) / 256; b.nz = nz;   // ti runs 0..L inclusive
-    b.nco = xcd_order(a.cout / CO_T, (double) a.cin * a.L * nz * 4, (double) a.cout * a.cin * 2 * S * 6);
-    hipLaunchKernelGGL((convt_b3_kernel<S, MI, PL, SP>), dim3(xcd_grid(b.npos, a.cout / CO_T, b.nz)), dim3(512), lds, c->stream, b);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-template <int S, int MI, typename SP>
-static int launch_convt_b3_s(tts_hip_ctx *c, const ConvTArgs &a, int nz) {
-    return a.xp ? launch_convt_b3_t<S, MI, true, SP>(c, a, nz) : launch_convt_b3_t<S, MI, false, SP>(c, a, nz);
-}
 template <int S, int MI>
-static int launch_convt_b3(tts_hip_ctx *c, const ConvTArgs &a, int nz) {
-    const int sc = dac_scheme(c);
-    return sc == 0 ? launch_convt_b3_s<S, MI, SplitB3>(c, a, nz) : sc == 1 ? launch_convt_b3_s<S, MI, SplitH2>(c, a, nz) : launch_convt_b3_s<S, MI, SplitH1>(c, a, nz);
+static int launch_convt_b3(tts_hip_ctx *c, const ConvTArgs &a, int nz, int scheme) {
+    return with_split(scheme, [&](auto sp) {
+        using SP = decltype(sp);
+        constexpr int CO_T = 32 * MI, WPL = 2 * S * 2 * CO_T * 8, xpl = 2 * 257 * 8;
+        const size_t lds = (size_t) 2 * SP::NPL * WPL * 2 + (size_t) 2 * SP::NPL * xpl * 2 + (size_t) a.cin * 8;
+        if (lds > 160 * 1024) return set_err("convt_b3: %d input channels need %zu bytes of LDS", a.cin, lds);
+        ConvTArgs b = a;
+        b.npos = (a.L + 1 + 255) / 256; b.nz = nz;   // ti runs 0..L inclusive
+        b.nco = xcd_order(a.cout / CO_T, (double) a.cin * a.L * nz * 4, (double) a.cout * a.cin * 2 * S * 6);
+        const dim3 grid(xcd_grid(b.npos, a.cout / CO_T, b.nz));
+        return a.xp ? launch_lds<convt_b3_kernel<S, MI, true, SP>>(c, grid, 512, lds, b) : launch_lds<convt_b3_kernel<S, MI, false, SP>>(c, grid, 512, lds, b);
+    });
 }
 
 static int launch_convt(tts_hip_ctx *c, ConvTArgs ta, size_t w_off, int nz) {
-    const bool valu = (c->d.flags & TTS_HIP_FLAG_VALU_GEMM) != 0;
+    const CodecImage *im = find_image(c, w_off);
+    const uint8_t kind = im ? im->kind : (uint8_t) IMG_NONE;
     const int s = ta.stride;
-    auto pct = c->packed_ct.find(w_off);
-    if (!valu && c->dac_convt_b3 && pct != c->packed_ct.end()) {
-        ta.w = (const float *) pct->second;
+    if (kind != IMG_NONE) ta.w = (const float *) im->w;
+    if (kind == IMG_CONVT_PLANES) {
         ta.x_f16 = 0;
-        if (s == 8) return launch_convt_b3<8, 1>(c, ta, nz);
-        if (s == 4) return launch_convt_b3<4, 2>(c, ta, nz);
-        return launch_convt_b3<2, 3>(c, ta, nz);
+        if (s == 8) return launch_convt_b3<8, 1>(c, ta, nz, im->scheme);
+        if (s == 4) return launch_convt_b3<4, 2>(c, ta, nz, im->scheme);
+        return launch_convt_b3<2, 3>(c, ta, nz, im->scheme);
     }
-    int CO_T = 0;
-    const int cfg = valu ? -1 : convt_tile(ta.cout, s, &CO_T);
     ta.x_f16 = c->dac_f16 ? 1 : 0;
-    auto pk16 = c->packed16.find(w_off);
-    if (cfg >= 0 && c->dac_f16 && pk16 != c->packed16.end()) {
-        ta.w = (const float *) pk16->second;
-        if (cfg == 0) return launch_convt_mfma16<8, 1, 2, 2, CI16_T>(c, ta, nz);
-        if (cfg == 1) return launch_convt_mfma16<4, 2, 1, 4, CI16_T>(c, ta, nz);
-        if (cfg == 2) return launch_convt_mfma16<2, 3, 1, 4, CI16_T>(c, ta, nz);
-        return launch_convt_mfma16<2, 2, 1, 4, CI16_T>(c, ta, nz);
-    }
-    auto pk = c->packed.find(w_off);
-    if (cfg >= 0 && pk != c->packed.end()) {
-        ta.w = pk->second;
-        if (cfg == 0) return launch_convt_mfma<8, 1, 2, 2, CI32_T>(c, ta, nz);
-        if (cfg == 1) return launch_convt_mfma<4, 2, 1, 4, CI32_T>(c, ta, nz);
-        if (cfg == 2) return launch_convt_mfma<2, 3, 1, 4, CI32_T>(c, ta, nz);
-        return launch_convt_mfma<2, 2, 1, 4, CI32_T>(c, ta, nz);
-    }
+    if (kind == IMG_F16_TILE) return launch_convt_tile<_Float16>(c, ta, nz, im->co_t);
+    if (kind == IMG_F32_TILE) return launch_convt_tile<float>(c, ta, nz, im->co_t);
     const dim3 grid((ta.Lout + CV_T - 1) / CV_T, (ta.cout + CV_CO - 1) / CV_CO, nz);
     const size_t lds = ((size_t) CT_CI * ((CV_T + s - 1) / s + 2) + (size_t) CT_CI * 2 * s * CV_CO) * 4;
     hipLaunchKernelGGL(convt1d_kernel, grid, dim3(256), lds, c->stream, ta);
@@ -470,63 +284,51 @@ static int launch_convt(tts_hip_ctx *c, ConvTArgs ta, size_t w_off, int nz) {
 }
 
 // ---- wide classes on split planes --------------------------------------------------------------------------------------------------
-static int launch_split(tts_hip_ctx *c, const DacBatch &bt, const float *x, int C, int LS, size_t alpha, bool has_alpha, __bf16 *yp) {
+// scheme: that of the image of the conv that consumes the planes
+static int launch_split(tts_hip_ctx *c, const DacBatch &bt, const float *x, int C, int LS, size_t alpha, bool has_alpha, __bf16 *yp, int scheme) {
     SplitArgs a{};
     a.x = x; a.alpha = has_alpha ? (const float *) (c->arena + alpha) : nullptr; a.yp = yp; a.C = C; a.L = LS; a.frames = bt.frames; a.mult = bt.mult;
     const double Lv = bt.tot_frames * bt.mult;
     CHK(prof_begin(c, TTS_HIP_K_DAC_CONV1, (double) C * Lv * 10, 0));
-    const int sc = dac_scheme(c);
-    if (sc == 0) hipLaunchKernelGGL(snake_split_kernel<SplitB3>, dim3((LS + 255) / 256, C / 8, bt.n), dim3(256), 0, c->stream, a);
-    else if (sc == 1) hipLaunchKernelGGL(snake_split_kernel<SplitH2>, dim3((LS + 255) / 256, C / 8, bt.n), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(snake_split_kernel<SplitH1>, dim3((LS + 255) / 256, C / 8, bt.n), dim3(256), 0, c->stream, a);
+    CHK(with_split(scheme, [&](auto sp) { hipLaunchKernelGGL(snake_split_kernel<decltype(sp)>, dim3((LS + 255) / 256, C / 8, bt.n), dim3(256), 0, c->stream, a); return 0; }));
     HIPCHK(hipGetLastError());
     return prof_end(c);
 }
-template <int KT, int MI, int NI, int WM, int WN, int NS, int MINW, int NB, typename SP>
-static int launch_conv_b3p_s(tts_hip_ctx *c, const PConvArgs &a, int nz) {
-    constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WPL = NS * 2 * CO_T * 8, NCG = KT == 7 ? (NS == 7 ? 2 : 1) : 2 * NS;
-    const int xw = T_T + (KT - 1) * a.dil;
-    const size_t lds = (size_t) NB * (SP::NPL * WPL * 2 + (size_t) SP::NPL * NCG * xw * 8 * 2);
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) conv_b3p_kernel<KT, MI, NI, WM, WN, NS, MINW, NB, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    PConvArgs b = a;
-    b.npos = (a.L + T_T - 1) / T_T; b.nz = nz;
-    b.nco = xcd_order(a.cout / CO_T, (double) a.cin * a.L * nz * 6, (double) a.cout * a.cin * KT * 6);
-    hipLaunchKernelGGL((conv_b3p_kernel<KT, MI, NI, WM, WN, NS, MINW, NB, SP>), dim3(xcd_grid(b.npos, a.cout / CO_T, b.nz)), dim3(64 * WM * WN), lds, c->stream, b);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 template <int KT, int MI, int NI, int WM, int WN, int NS, int MINW, int NB = 2>
-static int launch_conv_b3p_t(tts_hip_ctx *c, const PConvArgs &a, int nz) {
-    const int sc = dac_scheme(c);
-    if (sc == 0) return launch_conv_b3p_s<KT, MI, NI, WM, WN, NS, MINW, NB, SplitB3>(c, a, nz);
-    if (sc == 1) return launch_conv_b3p_s<KT, MI, NI, WM, WN, NS, MINW, NB, SplitH2>(c, a, nz);
-    return launch_conv_b3p_s<KT, MI, NI, WM, WN, NS, MINW, NB, SplitH1>(c, a, nz);
+static int launch_conv_b3p(tts_hip_ctx *c, const PConvArgs &a, int nz, int scheme) {
+    return with_split(scheme, [&](auto sp) {
+        using SP = decltype(sp);
+        constexpr int CO_T = 32 * MI * WM, T_T = 32 * NI * WN, WPL = NS * 2 * CO_T * 8, NCG = KT == 7 ? (NS == 7 ? 2 : 1) : 2 * NS;
+        const int xw = T_T + (KT - 1) * a.dil;
+        const size_t lds = (size_t) NB * (SP::NPL * WPL * 2 + (size_t) SP::NPL * NCG * xw * 8 * 2);
+        PConvArgs b = a;
+        b.npos = (a.L + T_T - 1) / T_T; b.nz = nz;
+        b.nco = xcd_order(a.cout / CO_T, (double) a.cin * a.L * nz * 6, (double) a.cout * a.cin * KT * 6);
+        return launch_lds<conv_b3p_kernel<KT, MI, NI, WM, WN, NS, MINW, NB, SP>>(c, dim3(xcd_grid(b.npos, a.cout / CO_T, b.nz)), 64 * WM * WN, lds, b);
+    });
 }
 // conv on planes: y (fp32, may be NULL) and / or yp (planes with the consumer's snake, may be NULL)
 static int launch_conv_planes(tts_hip_ctx *c, const DacBatch &bt, const __bf16 *xp, int cin, int LS, size_t w, size_t b, int cout, int K, int dil, const float *resid,
                               float *y, __bf16 *yp, size_t alpha_out, bool has_alpha_out) {
+    const CodecImage &im = c->images.at(w);
     PConvArgs a{};
-    a.xp = xp; a.w = c->packed_p.at(w); a.b = (const float *) (c->arena + b); a.resid = resid; a.y = y; a.yp = yp;
+    a.xp = xp; a.w = (const __bf16 *) im.w; a.b = (const float *) (c->arena + b); a.resid = resid; a.y = y; a.yp = yp;
     a.alpha_out = has_alpha_out ? (const float *) (c->arena + alpha_out) : nullptr;
     a.cin = cin; a.cout = cout; a.L = LS; a.dil = dil; a.pad = K == 7 ? 3 * dil : 0; a.frames = bt.frames; a.mult = bt.mult;
     const double Lv = bt.tot_frames * bt.mult;
     const double bytes = ((double) cin * Lv * 6 + (double) cout * Lv * ((resid ? 4 : 0) + (y ? 4 : 0) + (yp ? 6 : 0)) + (double) cout * cin * K * 6);
     CHK(prof_begin(c, K == 7 ? TTS_HIP_K_DAC_CONV7 : TTS_HIP_K_DAC_CONV1, bytes, 2.0 * cout * (double) cin * K * Lv));
     if (K == 7) {
-        const bool tapk = c->dac_tap7 && cin % 16 == 0;
         // 64 ch x 256 pos, 4 waves.  One tap per k-step: one LDS buffer (73 KB, two workgroups per CU).  Measured and dropped (64-utterance pass,
         // k = 7 family, profiles/r03/tap7_call16.txt): 8 waves 49.9 ms (128 registers, spills), two LDS buffers 53.5 / 48.6 ms against 45.7.
         // Round 6, fp16 hi + lo planes (48.5 KB of LDS: a third workgroup per CU would fit): compiled for three waves per SIMD (<= 168 registers from 198) the
         // kernel spills 120 bytes per lane and the family takes 30.6 ms against 26.1 (profiles/CALLS_r06.md 107).
-        if (tapk) CHK((launch_conv_b3p_t<7, 2, 2, 1, 4, 7, 2, 1>(c, a, bt.n)));
-        else CHK((launch_conv_b3p_t<7, 2, 2, 1, 4, 4, 2>(c, a, bt.n)));                             // tap pairs (dac_tap7 = 0)
-    } else if (cout % 256 == 0) {
-        CHK((launch_conv_b3p_t<1, 4, 2, 2, 4, 1, 2>(c, a, bt.n)));                                  // 256 ch x 256 pos, 8 waves
+        if (im.ns == 7) CHK((launch_conv_b3p<7, 2, 2, 1, 4, 7, 2, 1>(c, a, bt.n, im.scheme)));
+        else CHK((launch_conv_b3p<7, 2, 2, 1, 4, 4, 2>(c, a, bt.n, im.scheme)));                             // tap pairs (dac_tap7 = 0)
+    } else if (im.co_t == 256) {
+        CHK((launch_conv_b3p<1, 4, 2, 2, 4, 1, 2>(c, a, bt.n, im.scheme)));                                  // 256 ch x 256 pos, 8 waves
     } else {
-        CHK((launch_conv_b3p_t<1, 2, 4, 2, 4, 1, 2>(c, a, bt.n)));                                  // 128 ch x 512 pos, 8 waves (128 x 256: 21.9 against 20.4 ms per pass)
+        CHK((launch_conv_b3p<1, 2, 4, 2, 4, 1, 2>(c, a, bt.n, im.scheme)));                                  // 128 ch x 512 pos, 8 waves (128 x 256: 21.9 against 20.4 ms per pass)
     }
     return prof_end(c);
 }
@@ -538,13 +340,7 @@ static int launch_resunit_t(tts_hip_ctx *c, const ResUnitArgs &a, int nz) {
     const ResUnitGeom g = resunit_geom(C, KS, KS2);
     const int xw = 256 + 6 * a.dil;
     const size_t lds = (size_t) 2 * g.WST * 2 + (size_t) 6 * xw * 8 * 2 + (size_t) C * 24;
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) resunit_b3_kernel<MI, KS, KS2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL((resunit_b3_kernel<MI, KS, KS2>), dim3((a.L + 255) / 256, 1, nz), dim3(512), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<resunit_b3_kernel<MI, KS, KS2>>(c, dim3((a.L + 255) / 256, 1, nz), 512, lds, a);
 }
 template <int MI, int KS2, typename SP, bool WDMA, int VAR, int NI = 1>
 static int launch_resunit_t7_s(tts_hip_ctx *c, const ResUnitArgs &a, int nz) {
@@ -552,38 +348,34 @@ static int launch_resunit_t7_s(tts_hip_ctx *c, const ResUnitArgs &a, int nz) {
     const int xw = T_T + 6 * a.dil;
     const size_t WST = (size_t) SP::NPL * ResT7<MI>::MAXCNT * 2 * C * 8;
     const size_t lds = 2 * WST * 2 + (size_t) 2 * SP::NPL * 2 * xw * 8 * 2 + (size_t) C * 24;
-    static std::atomic<uint64_t> attr{0};
-    if (attr_needed(attr, c->device)) {
-        HIPCHK(hipFuncSetAttribute((const void *) resunit_t7_kernel<MI, KS2, SP, WDMA, VAR, NI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL((resunit_t7_kernel<MI, KS2, SP, WDMA, VAR, NI>), dim3((a.L + T_T - 1) / T_T, 1, nz), dim3(512), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<resunit_t7_kernel<MI, KS2, SP, WDMA, VAR, NI>>(c, dim3((a.L + T_T - 1) / T_T, 1, nz), 512, lds, a);
 }
 // round 6 default: weight stages by global_load_lds, the k = 1 conv's B operand made once (dac_wdma = 1, VAR 2), and at 96 channels two position tiles per
-// wave (NI 2: 4.72 -> 4.47 ms per launch; at 192 channels the accumulators of two tiles do not fit); tune("dac_wdma") = 0: the round-5 form
+// wave (NI 2: 4.72 -> 4.47 ms per launch; at 192 channels the accumulators of two tiles do not fit); tune("dac_wdma") = 0: the round-5 form.  The three-plane
+// scheme keeps VAR 0 and one tile.  dac_wdma is read at launch: both forms stage the same image
 template <int MI, int KS2>
-static int launch_resunit_t7(tts_hip_ctx *c, const ResUnitArgs &a, int nz) {
-    const int sc = dac_scheme(c);
-    constexpr int NI = MI == 3 ? 2 : 1;
-    if (c->dac_wdma)
-        return sc == 0 ? launch_resunit_t7_s<MI, KS2, SplitB3, true, 0>(c, a, nz) : sc == 1 ? launch_resunit_t7_s<MI, KS2, SplitH2, true, 2, NI>(c, a, nz) : launch_resunit_t7_s<MI, KS2, SplitH1, true, 2, NI>(c, a, nz);
-    return sc == 0 ? launch_resunit_t7_s<MI, KS2, SplitB3, false, 0>(c, a, nz) : sc == 1 ? launch_resunit_t7_s<MI, KS2, SplitH2, false, 0>(c, a, nz) : launch_resunit_t7_s<MI, KS2, SplitH1, false, 0>(c, a, nz);
+static int launch_resunit_t7(tts_hip_ctx *c, const ResUnitArgs &a, int nz, int scheme) {
+    if (c->dac_wdma) return with_split(scheme, [&](auto sp) {
+        constexpr bool B3 = std::is_same_v<decltype(sp), SplitB3>;
+        return launch_resunit_t7_s<MI, KS2, decltype(sp), true, B3 ? 0 : 2, B3 ? 1 : (MI == 3 ? 2 : 1)>(c, a, nz); });
+    return with_split(scheme, [&](auto sp) { return launch_resunit_t7_s<MI, KS2, decltype(sp), false, 0>(c, a, nz); });
 }
+// dil <= 9 is read at launch (what the unit kernels' LDS holds): beyond it the unit runs as two convs on the kernels that read the GGUF layout
 static bool resunit_fused(const tts_hip_ctx *c, const DRes &r, int dil) {
-    return c->dac_fuse && !(c->d.flags & TTS_HIP_FLAG_VALU_GEMM) && dil <= 9 && c->packed_ru.count(r.in_w);
+    return dil <= 9 && (image_is(c, r.in_w, IMG_UNIT_TAP) || image_is(c, r.in_w, IMG_UNIT_PAIR));
 }
 static int launch_resunit(tts_hip_ctx *c, const DacBatch &bt, const DRes &r, int C, int LS, int dil, const float *x, float *y) {
+    const CodecImage &im = c->images.at(r.in_w);
     ResUnitArgs a{};
-    a.x = x; a.y = y; a.w = c->packed_ru.at(r.in_w);
+    a.x = x; a.y = y; a.w = (const __bf16 *) im.w;
     a.b7 = (const float *) (c->arena + r.in_b); a.b1 = (const float *) (c->arena + r.out_b);
     a.alpha_in = (const float *) (c->arena + r.in_alpha); a.alpha_mid = (const float *) (c->arena + r.out_alpha);
     a.L = LS; a.dil = dil; a.pad = 3 * dil; a.frames = bt.frames; a.mult = bt.mult;
     const double Lv = bt.tot_frames * bt.mult;
     CHK(prof_begin(c, TTS_HIP_K_DAC_RESUNIT, (2.0 * C * Lv + 8.0 * C * C) * 4, 2.0 * C * (double) C * 8 * Lv));
-    if (c->dac_tap7) {
-        if (C == 96) CHK((launch_resunit_t7<3, 3>(c, a, bt.n)));
-        else CHK((launch_resunit_t7<6, 4>(c, a, bt.n)));
+    if (im.kind == IMG_UNIT_TAP) {
+        if (C == 96) CHK((launch_resunit_t7<3, 3>(c, a, bt.n, im.scheme)));
+        else CHK((launch_resunit_t7<6, 4>(c, a, bt.n, im.scheme)));
     } else if (C == 96) CHK((launch_resunit_t<3, 4, 3>(c, a, bt.n)));
     else CHK((launch_resunit_t<6, 2, 4>(c, a, bt.n)));
     return prof_end(c);
@@ -655,12 +447,12 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
         int Lq = (int) Fmax;
         need_elems = (size_t) std::max(c->d_latent, c->d_c0) * dac_row_stride(c, Lq);
         // split planes (6 bytes per element) of the wide classes live in these buffers too
-        if (c->packed_p.count(c->d_initw)) need_elems = std::max(need_elems, ((size_t) c->d_latent * dac_row_stride(c, Lq) * 3 + 1) / 2);
+        if (image_is(c, c->d_initw, IMG_PLANES)) need_elems = std::max(need_elems, ((size_t) c->d_latent * dac_row_stride(c, Lq) * 3 + 1) / 2);
         for (auto &b : c->dblocks) {
             need_elems = std::max(need_elems, (size_t) b.cin * dac_row_stride(c, Lq));
             Lq = (Lq - 1) * b.stride - 2 * b.padding + 2 * b.stride;
             need_elems = std::max(need_elems, (size_t) b.cout * dac_row_stride(c, Lq));
-            if (c->packed_p.count(b.res[0].in_w)) need_elems = std::max(need_elems, ((size_t) b.cout * dac_row_stride(c, Lq) * 3 + 1) / 2);
+            if (image_is(c, b.res[0].in_w, IMG_PLANES)) need_elems = std::max(need_elems, ((size_t) b.cout * dac_row_stride(c, Lq) * 3 + 1) / 2);
         }
         need_elems *= n;
         pcm_elems = (size_t) n * dac_row_stride(c, Lq);
@@ -668,7 +460,7 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
     // the device's codec buffers (the caller holds the device's pass lock)
     DacBuffers &B = g_dac_buffers[(unsigned) c->device % 64];
     if (!c->dac_buf_user) { c->dac_buf_user = true; B.users++; }
-    if (need_frames * c->d_ncb > B.cap_codes || need_elems > B.dbuf_elems || pcm_elems > B.h_pcm_elems || (!c->packed_p.empty() && !B.dplanes)) {
+    if (need_frames * c->d_ncb > B.cap_codes || need_elems > B.dbuf_elems || pcm_elems > B.h_pcm_elems || (c->plane_images && !B.dplanes)) {
         HIPCHK(hipStreamSynchronize(c->stream));
         const size_t want_elems = std::max(need_elems, B.dbuf_elems), want_codes = std::max(need_frames * c->d_ncb, B.cap_codes), want_pcm = std::max(pcm_elems, B.h_pcm_elems);
         auto drop = [&]() {
@@ -681,12 +473,12 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
         drop();
         hipError_t e = hipSuccess;
         for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipMalloc((void **) &B.dbuf[i], want_elems * 4);
-        if (e == hipSuccess && !c->packed_p.empty()) e = hipMalloc((void **) &B.dplanes, want_elems * 4);   // 6 bytes per element of the widest planes class <= a dbuf
+        if (e == hipSuccess && c->plane_images) e = hipMalloc((void **) &B.dplanes, want_elems * 4);   // 6 bytes per element of the widest planes class <= a dbuf
         if (e == hipSuccess) e = hipMalloc((void **) &B.d_codes, want_codes * 4);
         if (e == hipSuccess) e = hipHostMalloc((void **) &B.h_pcm, want_pcm * 4);
         if (e != hipSuccess) {
             drop();
-            return set_err("tts_hip_dac_decode: codec buffers of %zu floats x %d + %zu ids: %s", want_elems, c->packed_p.empty() ? 3 : 4, want_codes, hipGetErrorString(e));
+            return set_err("tts_hip_dac_decode: codec buffers of %zu floats x %d + %zu ids: %s", want_elems, c->plane_images ? 4 : 3, want_codes, hipGetErrorString(e));
         }
         B.dbuf_elems = want_elems; B.cap_codes = want_codes; B.h_pcm_elems = want_pcm;   // capacities are recorded only once every buffer exists
     }
@@ -722,16 +514,13 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
 
     // A transposed conv on the bf16 x 3 kernel takes its input as split planes when the producer is a planes conv: the producer's epilogue applies
     // this layer's snake and the split once per element, where the fp32 form redoes both in every one of the cout / 32 channel-tile workgroups.
-    auto convt_takes_planes = [&](size_t bi) {
-        if (bi >= c->dblocks.size() || !c->dac_convt_planes || (c->d.flags & TTS_HIP_FLAG_VALU_GEMM)) return false;
-        const DBlock &nb = c->dblocks[bi];
-        return c->dac_convt_b3 && c->packed_ct.count(nb.w) != 0 && nb.cin % 16 == 0;
-    };
+    // (dac_convt_planes is read at launch: convt_b3_kernel stages the same image from either input)
+    auto convt_takes_planes = [&](size_t bi) { return bi < c->dblocks.size() && c->dac_convt_planes && image_is(c, c->dblocks[bi].w, IMG_CONVT_PLANES); };
     const __bf16 *convt_in = nullptr;    // planes of the next transposed conv's input, when its producer wrote them
-    if (c->packed_p.count(c->d_initw) && !(c->d.flags & TTS_HIP_FLAG_VALU_GEMM)) {
+    if (const CodecImage *im = find_image(c, c->d_initw); im && im->kind == IMG_PLANES) {
         // quantizer output -> split planes (no snake in front of the first conv) -> k = 7 conv on planes -> the first transposed conv's planes
         // (snaked with ITS alpha), or fp32 for it
-        CHK(launch_split(c, bt, cur, c->d_latent, LS, 0, false, (__bf16 *) t2));
+        CHK(launch_split(c, bt, cur, c->d_latent, LS, 0, false, (__bf16 *) t2, im->scheme));
         const bool pl = convt_takes_planes(0);
         CHK(launch_conv_planes(c, bt, (const __bf16 *) t2, c->d_latent, LS, c->d_initw, c->d_initb, c->d_c0, 7, 1, nullptr, (!pl || (c->debug && n == 1)) ? t1 : nullptr,
                                pl ? (__bf16 *) B.dplanes : nullptr, pl ? c->dblocks[0].alpha : 0, pl));
@@ -760,12 +549,12 @@ static int dac_decode_batch_on(tts_hip_ctx *c, const uint32_t *codes, const uint
         std::swap(cur, t1);
         L = Lout; LS = LSout; C = b.cout;
         bt.mult *= b.stride;
-        if (c->packed_p.count(b.res[0].in_w) && !(c->d.flags & TTS_HIP_FLAG_VALU_GEMM)) {
+        if (const CodecImage *im = find_image(c, b.res[0].in_w); im && im->kind == IMG_PLANES) {
             // a wide class on split planes: the activation a conv consumes is written by its producer already snaked (the consumer's alpha)
             // and split; the fp32 tensor exists only where the residual add and the next transposed conv need it.
             //   X (cur, fp32) --split(snake in_alpha 0)--> PA ;  k7(PA) -> PB = split(snake out_alpha) ;  k1(PB) + X -> X' (fp32) [+ PA for the next unit]
             __bf16 *PA = (__bf16 *) t2, *PB = (__bf16 *) B.dplanes;
-            CHK(launch_split(c, bt, cur, C, LS, b.res[0].in_alpha, true, PA));
+            CHK(launch_split(c, bt, cur, C, LS, b.res[0].in_alpha, true, PA, im->scheme));
             for (int r = 0; r < 3; r++) {
                 int dil = 1;
                 for (int e = 0; e < r; e++) dil *= 3;
@@ -1096,48 +885,55 @@ struct KRun {
     // Everything else (stride 2, nearest-2x input, one output channel, the scaled shortcut) stays on kk_conv1d_kernel.
     // The same convolutions as bf16 x 3 split products on the bf16 matrix pipe (conv1d_mfma_b3_kernel<.., KT>: fp32-level error, 2-3x the rate of the
     // exact-fp32 MFMA at these sizes): k = 3 / 5 / 7 / 11, 64-channel tiles x 256 positions, weights packed once per tensor as three bf16 planes.
-    template <int KT>
-    bool conv_b3(const float *x, int cin, int64_t L, const float *wt, const float *b, int cout, int pad, int dil, float *y, int acc) {
+    // the image of an arena-resident weight, packed at its first use (NULL: none is planned for it, or packing failed and err says so)
+    const CodecImage *image(CodecRole role, const float *wt, int cout, int cin, int K, int stride, int dil) {
         const size_t w_off = (size_t) ((const char *) wt - c->arena);
-        if (c->packed_b3.find(w_off) == c->packed_b3.end() && pack_one_b3(c, w_off, cout, cin, 64, KT) != 0) { err = tts_hip_last_error(); return true; }
+        if (!find_image(c, w_off) && plan_and_pack(c, codec_knobs(c), role, w_off, cout, cin, K, stride, 0, dil) != 0) err = tts_hip_last_error();
+        return find_image(c, w_off);
+    }
+    // KT taps on the kernel the image was packed for: launch(a) is conv1d_mfma_b3_kernel (64 ch x 256 pos) or conv1d_mfma_kernel
+    template <class Launch>
+    void conv_image(const CodecImage &im, int KT, const float *x, int cin, int64_t L, const float *b, int cout, int pad, int dil, float *y, int acc, Launch launch) {
         ConvArgs a{};
-        a.x = x; a.w = (const float *) c->packed_b3[w_off]; a.b = b; a.alpha = nullptr; a.alpha_out = nullptr; a.resid = acc ? y : nullptr; a.y = y;
+        a.x = x; a.w = (const float *) im.w; a.b = b; a.alpha = nullptr; a.alpha_out = nullptr; a.resid = acc ? y : nullptr; a.y = y;
         a.cin = cin; a.cout = cout; a.L = (int) L; a.dil = dil; a.pad = pad; a.do_tanh = 0; a.frames = nullptr; a.mult = 1; a.x_f16 = 0;
-        if (prof_begin(c, TTS_HIP_K_KOKORO_CONV, ((double) cin * L + (double) cout * L * (acc ? 2 : 1) + (double) cout * cin * KT) * 4, 2.0 * cout * (double) cin * KT * L) != 0) { err = tts_hip_last_error(); return true; }
-        const int rc = launch_conv_b3<2, 1, 1, 8, KT>(c, a, 1);
-        if (rc != 0 || prof_end(c) != 0) err = tts_hip_last_error();
-        return true;
+        if (prof_begin(c, TTS_HIP_K_KOKORO_CONV, ((double) cin * L + (double) cout * L * (acc ? 2 : 1) + (double) cout * cin * KT) * 4, 2.0 * cout * (double) cin * KT * L) != 0) { err = tts_hip_last_error(); return; }
+        if (launch(a) != 0 || prof_end(c) != 0) err = tts_hip_last_error();
+    }
+    template <int KT>
+    void conv_b3(const CodecImage &im, const float *x, int cin, int64_t L, const float *b, int cout, int pad, int dil, float *y, int acc) {
+        conv_image(im, KT, x, cin, L, b, cout, pad, dil, y, acc, [&](const ConvArgs &a) { return launch_conv_b3<2, 1, 1, 8, KT>(c, a, 1, im.scheme); });
     }
     template <int KT, int CI_T>
-    bool conv_mfma(const float *x, int cin, int64_t L, const float *wt, const float *b, int cout, int pad, int dil, float *y, int acc) {
-        const size_t w_off = (size_t) ((const char *) wt - c->arena);
-        const int CO_T = cout % 128 == 0 ? 128 : 64;   // other widths (conv_post: 22 channels): 64-channel tiles, zero-padded weights, stores masked
-        if (c->packed.find(w_off) == c->packed.end() && pack_one(c, w_off, cout, cin, KT, CO_T, CI_T, false) != 0) { err = tts_hip_last_error(); return true; }
-        ConvArgs a{};
-        a.x = x; a.w = c->packed[w_off]; a.b = b; a.alpha = nullptr; a.alpha_out = nullptr; a.resid = acc ? y : nullptr; a.y = y;
-        a.cin = cin; a.cout = cout; a.L = (int) L; a.dil = dil; a.pad = pad; a.do_tanh = 0; a.frames = nullptr; a.mult = 1; a.x_f16 = 0;
-        if (prof_begin(c, TTS_HIP_K_KOKORO_CONV, ((double) cin * L + (double) cout * L * (acc ? 2 : 1) + (double) cout * cin * KT) * 4, 2.0 * cout * (double) cin * KT * L) != 0) { err = tts_hip_last_error(); return true; }
-        const int rc = CO_T == 128 ? launch_conv_mfma<KT, 2, 2, 2, 2, CI_T>(c, a, 1) : launch_conv_mfma<KT, 2, 2, 1, 4, CI_T>(c, a, 1);
-        if (rc != 0 || prof_end(c) != 0) err = tts_hip_last_error();
-        return true;
+    void conv_tile(const CodecImage &im, const float *x, int cin, int64_t L, const float *b, int cout, int pad, int dil, float *y, int acc) {
+        conv_image(im, KT, x, cin, L, b, cout, pad, dil, y, acc, [&](const ConvArgs &a) {
+            return im.co_t == 128 ? launch_conv_mfma<float, KT, 2, 2, 2, 2, CI_T>(c, a, 1) : launch_conv_mfma<float, KT, 2, 2, 1, 4, CI_T>(c, a, 1); });
     }
     void conv1d(const float *x, int cin, int64_t L, const float *wt, const float *b, int cout, int K, int stride, int pad, int dil, int in_shift, float *y, int64_t Lout,
                 int acc, float post) {
         if (!x || !wt || !y) return;
         const bool same = stride == 1 && !in_shift && Lout == L && pad * 2 == dil * (K - 1) && post == 1.0f && dil <= 9;
-        if (same && c->kk_mfma && cout >= 16 && cin >= 16 && L < (1 << 30) && (const char *) wt >= c->arena && (const char *) wt < c->arena + c->arena_bytes) {
-            if (K == 1 && (L & 3) == 0 && (((uintptr_t) x | (uintptr_t) y) & 15) == 0 && conv_mfma<1, 16>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;   // k = 1 stages 16-byte pieces
-            if (c->kk_b3 && dil <= 5) {   // bf16 x 3 split products (tune("kokoro_b3", 0): the exact-fp32 MFMA kernels below)
-                if (K == 3 && conv_b3<3>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-                if (K == 5 && conv_b3<5>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-                if (K == 7 && conv_b3<7>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-                if (K == 11 && conv_b3<11>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
+        if (same && L < (1 << 30) && (const char *) wt >= c->arena && (const char *) wt < c->arena + c->arena_bytes) {
+            // k = 1 stages 16-byte pieces (alignment is a property of the launch); k = 3 / 5 / 7 / 11: split products up to dilation 5
+            // (tune("kokoro_b3", 0): the exact-fp32 MFMA kernel), as the image says
+            const bool k1 = K == 1 && (L & 3) == 0 && (((uintptr_t) x | (uintptr_t) y) & 15) == 0;
+            const CodecImage *im = k1 || K == 3 || K == 5 || K == 7 || K == 11 ? image(ROLE_KOKORO_SAME, wt, cout, cin, K, 1, dil) : nullptr;
+            const uint8_t kind = im ? im->kind : (uint8_t) IMG_NONE;
+            if (kind == IMG_F32_TILE && K == 1) return conv_tile<1, 16>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+            if (kind == IMG_B3 && dil <= 5) {
+                if (K == 3) return conv_b3<3>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                if (K == 5) return conv_b3<5>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                if (K == 7) return conv_b3<7>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                return conv_b3<11>(*im, x, cin, L, b, cout, pad, dil, y, acc);
             }
-            if (K == 3 && conv_mfma<3, 8>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-            if (K == 5 && conv_mfma<5, 4>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-            if (K == 7 && conv_mfma<7, 4>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
-            if (K == 11 && conv_mfma<11, 4>(x, cin, L, wt, b, cout, pad, dil, y, acc)) return;
+            if (kind == IMG_F32_TILE) {
+                if (K == 3) return conv_tile<3, 8>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                if (K == 5) return conv_tile<5, 4>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                if (K == 7) return conv_tile<7, 4>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+                return conv_tile<11, 4>(*im, x, cin, L, b, cout, pad, dil, y, acc);
+            }
         }
+        // (kokoro_mfma here picks a kernel that reads the GGUF layout: no image is involved)
         if (c->kk_mfma && K == 1 && stride == 1 && pad == 0 && dil == 1 && cin >= 16 && cout >= 16 && Lout == (in_shift ? 2 * L : L)) {
             // the k = 1 shortcuts (any channel count, nearest-2x input, accumulate + 1/sqrt 2): 64 x 64 tiles on the exact-fp32 matrix pipe
             hipLaunchKernelGGL(kk_conv1x1_mfma_kernel, dim3((unsigned) ((Lout + 63) / 64), (unsigned) ((cout + 63) / 64)), dim3(256), 0, st, x, cin, L, wt, b, cout, in_shift, y, Lout, acc, post);
@@ -1571,17 +1367,16 @@ extern "C" int tts_hip_kokoro_generate(tts_hip_ctx *c, const uint32_t *tokens, u
         const int64_t Lo = (Lg - 1) * kd.up_stride[i] - 2 * (int64_t) kd.up_padding[i] + K;
         float *y = s.f((size_t) Co * Lo);
         const int S_ = (int) kd.up_stride[i];
-        const bool mfma_up = c->kk_mfma && K == 2 * S_ && (S_ == 10 || S_ == 6) && Co % 64 == 0 && 2 * (int) kd.up_padding[i] == K - S_ && Lo == Lg * S_;
-        if (y && mfma_up) {
+        // the geometry the phase-decomposed kernel covers; whether the weight has a tile image is the plan's word (kokoro_mfma, stride 10 / 6, 64-channel tiles)
+        const CodecImage *up_im = y && 2 * (int) kd.up_padding[i] == K - S_ && Lo == Lg * S_ ? k.image(ROLE_KOKORO_CONVT, uw, Co, Cg, K, S_, 1) : nullptr;
+        if (up_im && up_im->kind == IMG_F32_TILE) {
             // the generator's ConvTranspose1d (stride 10 / 6, kernel = 2 x stride: every output touches two taps) on the codec's
             // phase-decomposed MFMA kernel; the one-thread-per-output kernel spent 18 ms per launch here
-            const size_t w_off = (size_t) ((const char *) uw - c->arena);
-            if (c->packed.find(w_off) == c->packed.end()) CHK(pack_one(c, w_off, Co, Cg, K, 64, CI32_T, true));
             ConvTArgs ta{};
-            ta.x = g; ta.w = c->packed[w_off]; ta.b = k.w(gb + "ups." + std::to_string(i) + ".bias"); ta.alpha = nullptr; ta.y = y;
+            ta.x = g; ta.w = (const float *) up_im->w; ta.b = k.w(gb + "ups." + std::to_string(i) + ".bias"); ta.alpha = nullptr; ta.y = y;
             ta.cin = Cg; ta.cout = Co; ta.L = (int) Lg; ta.Lout = (int) Lo; ta.stride = S_; ta.pad = (int) kd.up_padding[i]; ta.frames = nullptr; ta.mult = 1;
-            if (S_ == 10) CHK((launch_convt_mfma<10, 1, 2, 2, CI32_T>(c, ta, 1)));
-            else CHK((launch_convt_mfma<6, 1, 2, 2, CI32_T>(c, ta, 1)));
+            if (S_ == 10) CHK((launch_convt_mfma<float, 10, 1, 2, 2, CI32_T>(c, ta, 1)));
+            else CHK((launch_convt_mfma<float, 6, 1, 2, 2, CI32_T>(c, ta, 1)));
         } else
         if (y) hipLaunchKernelGGL(kk_convt1d_kernel, kgrid((int64_t) Co * Lo), dim3(256), 0, c->stream, (const float *) g, Cg, Lg, uw, k.w(gb + "ups." + std::to_string(i) + ".bias"), Co, K,
                                   (int) kd.up_stride[i], (int) kd.up_padding[i], y, Lo);
@@ -1651,15 +1446,13 @@ extern "C" tts_hip_ctx *tts_hip_snac_create(int device, const tts_hip_snac_desc 
 }
 
 static int ensure_packed_snac(tts_hip_ctx *c) {
-    if (c->snac_packed || (c->d.flags & TTS_HIP_FLAG_VALU_GEMM)) return 0;
-    int CO_T = 0, CI_T = 0;
-    if (conv_tile(c->s_c0, 1, &CO_T, &CI_T) >= 0) CHK(pack_one(c, c->s_upw, c->s_c0, c->s_latent, 1, CO_T, CI_T, false));
+    if (c->snac_packed) return 0;
+    const CodecKnobs k = codec_knobs(c);
+    CHK(plan_and_pack(c, k, ROLE_SNAC_POINTWISE, c->s_upw, c->s_c0, c->s_latent, 1, 1));
     for (auto &b : c->sblocks) {
-        if (convt_tile(b.cout, b.stride, &CO_T) >= 0) CHK(pack_one(c, b.w, b.cout, b.cin, 2 * b.stride, CO_T, CI32_T, true));
-        if (conv_tile(b.cout, 1, &CO_T, &CI_T) >= 0) {
-            CHK(pack_one(c, b.noise_w, b.cout, b.cout, 1, CO_T, CI_T, false));
-            for (int r = 0; r < 3; r++) CHK(pack_one(c, b.res[r].out_w, b.cout, b.cout, 1, CO_T, CI_T, false));
-        }
+        CHK(plan_and_pack(c, k, ROLE_SNAC_CONVT, b.w, b.cout, b.cin, 2 * b.stride, b.stride));
+        CHK(plan_and_pack(c, k, ROLE_SNAC_POINTWISE, b.noise_w, b.cout, b.cout, 1, 1));
+        for (int r = 0; r < 3; r++) CHK(plan_and_pack(c, k, ROLE_SNAC_POINTWISE, b.res[r].out_w, b.cout, b.cout, 1, 1));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->snac_packed = true;

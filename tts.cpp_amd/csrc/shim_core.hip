@@ -156,6 +156,7 @@ extern "C" tts_hip_ctx *tts_hip_create(int device, const tts_hip_desc *desc) {
 extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     if (!c || !key) return set_err("tts_hip_tune: null argument");
     const std::string k(key);
+    const CodecKnobs before = codec_knobs(c);
     if (k == "dac_exact_fp32") {   // the codec as exact-fp32 MFMA kernels throughout (round 2's pipe): the reference arithmetic the bf16 x 3 default is held against
         c->dac_b3 = v ? 0 : 2; c->dac_fuse = c->dac_convt_b3 = c->dac_planes = v ? 0 : 1;
     } else if (k == "dac_fuse") c->dac_fuse = v;                 // 0: residual units at 96 / 192 channels as two launches
@@ -171,10 +172,7 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "kokoro_mfma") c->kk_mfma = v != 0;
     else if (k == "kokoro_b3") c->kk_b3 = v != 0;
     else if (k == "kokoro_attn_lds") c->kk_attn_lds = v != 0;
-    else if (k == "kokoro_split") {   // the packed planes belong to a scheme: drop them, the next convolution packs again
-        if (c->kk_split != (v != 0)) { (void) hipDeviceSynchronize(); for (auto &pw : c->packed_b3) free_dev(pw.second); c->packed_b3.clear(); }
-        c->kk_split = v != 0;
-    }
+    else if (k == "kokoro_split") c->kk_split = v != 0;
     else if (k == "kokoro_lstm_split") c->kk_lstm_split = v != 0;
     else if (k == "kokoro_adain_split") c->kk_adain_split = v != 0;
     else if (k == "ln_fuse_max") c->ln_fuse_max = std::max(0, std::min(32, v));
@@ -217,7 +215,18 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "b1_defer_combine") c->b1_defer_combine = v != 0;
     else if (k == "b1_stamps") c->b1_stamps_want = v != 0;
     else return set_err("tts_hip_tune: unknown key '%s'", key);
+    if (!(before == codec_knobs(c))) drop_codec_images(c);   // a layout key changed: the packed images belong to the old value, the next pass packs again
     return 0;
+}
+
+void drop_codec_images(tts_hip_ctx *c) {
+    c->dac_packed = c->snac_packed = false;
+    if (c->images.empty()) return;
+    (void) hipSetDevice(c->device);
+    (void) hipStreamSynchronize(c->stream);
+    if (c->dac_stream) (void) hipStreamSynchronize(c->dac_stream);
+    for (auto &im : c->images) free_dev(im.second.w);
+    c->images.clear(); c->plane_images = 0;
 }
 
 void free_dev(void *p) { if (p) (void) hipFree(p); }
@@ -302,14 +311,9 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     free_dev(c->d_seq); free_dev(c->d_gather); free_dev(c->d_tok); free_dev(c->d_step); free_dev(c->d_steps_done); free_dev(c->d_tokens_out);
     free_dev(c->d_eos); free_dev(c->d_frames);
     dac_buffers_release(c);
-    for (auto &pw : c->packed) free_dev(pw.second);
-    for (auto &pw : c->packed16) free_dev(pw.second);
-    for (auto &pw : c->packed_b3) free_dev(pw.second);
+    drop_codec_images(c);
     free_dev(c->cond_text_enc); free_dev(c->cond_cross_kv);
     free_dev(c->vb_kv); free_dev(c->vb_enc); free_dev(c->vb_len); free_dev(c->vb_seq);   // the voice bank
-    for (auto &pw : c->packed_ru) free_dev(pw.second);
-    for (auto &pw : c->packed_ct) free_dev(pw.second);
-    for (auto &pw : c->packed_p) free_dev(pw.second);
     if (c->h_ids) (void) hipHostFree(c->h_ids);
     if (c->h_pos) (void) hipHostFree(c->h_pos);
     if (c->h_seq) (void) hipHostFree(c->h_seq);

@@ -2493,6 +2493,11 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
         return (int64_t) n;
     }
+    if (w == "codec_packs") {   // pack launches of codec weight images since create (a layout key that changes value drops the images: the next pass packs again)
+        if (max_floats < 1) { set_err("debug_read(codec_packs): buffer too small"); return -1; }
+        out[0] = (float) c->codec_packs;
+        return 1;
+    }
     if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, 2 under TTS_HIP_FLAG_KV_F16, 1 under TTS_HIP_KV_F8_E4M3
         if (max_floats < 1) { set_err("debug_read(l_kv_elem): buffer too small"); return -1; }
         out[0] = (float) c->l_kv_esz;

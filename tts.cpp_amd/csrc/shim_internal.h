@@ -21,6 +21,7 @@
 #include <unordered_map>
 #define LLAMA_GREEDY_CHUNK 8
 
+#include "codec_plan.h"      // CodecKnobs, CodecImage, codec_plan: which packed image a codec conv weight gets
 #include "session_slots.h"   // set_err (shim_core.hip: thread-local message behind tts_hip_last_error()), SlotLedger, penalty_table
 // TTS_HIP_FLAG_KV_F16 is tts_hip_orpheus_create's alone: every other create call refuses it by name (true: refused, the message is set)
 static inline bool refuse_kv_f16(uint32_t flags, const char *call) {
@@ -423,12 +424,11 @@ struct tts_hip_ctx {
     struct DiaAttnSnap { std::vector<float> q, out, meta; };
     std::map<int, DiaAttnSnap> dia_attn_dbg;
     std::vector<float> win_pcm;    // tts_hip_dac_decode_windows: the windows' whole PCM before the crop
-    std::map<size_t, float *> packed;  // arena offset of a conv weight -> its MFMA-tile-packed copy
-    std::set<size_t> packed_direct;    // ... of those, the k = 1 weights packed as [cin][cout] for conv1x1_direct_kernel
-    std::map<size_t, _Float16 *> packed16;  // same, fp16 images (dac_f16)
-    std::map<size_t, __bf16 *> packed_b3;   // k = 7 conv weights as three bf16 planes (dac_b3, experiment)
-    std::map<size_t, __bf16 *> packed_ru;   // residual unit (keyed by its k = 7 weight) -> stage stream of resunit_b3_kernel
-    std::map<size_t, __bf16 *> packed_p;    // conv weight -> bf16 planes in stage order for conv_b3p_kernel (k = 7: 64-channel tiles, k = 1: 128-channel tiles)
+    // arena offset of a conv weight -> its ONE packed image (codec_plan.h; a fused residual unit under its k = 7 weight).  Made by pack_image
+    // (shim_codec.hip), freed by drop_codec_images alone
+    std::map<size_t, CodecImage> images;
+    int plane_images = 0;       // ... of which IMG_PLANES: the device's codec buffers then carry DacBuffers::dplanes
+    uint64_t codec_packs = 0;   // pack launches since create (debug_read "codec_packs")
     int dac_split = 1;          // tune("dac_split") / TTS_HIP_DAC_SPLIT: operand split of the codec's plane kernels for F32 tensors: 1 (default since round 6) = fp16 hi + lo, three
                                 // products; 0 = bf16 x 3, six products (rounds 3 - 5).  64 x 248-frame pass 132.4 -> 84.6 ms, every DAC bar held (profiles/r06/dac_split_call1.txt)
     int dac_f16_planes = 1;     // tune("dac_f16_planes")=0: F16 codec tensors stay on round 2's fp16 tile kernels (conv1d_mfma16_kernel / convt1d_mfma16_kernel) instead of the plane kernels with one fp16 plane
@@ -436,7 +436,6 @@ struct tts_hip_ctx {
     int dac_wdma = 1;           // tune("dac_wdma")=0: the fused units as in round 5 (weight stages through registers + ds_write_b128, the k = 1 operand rebuilt per pass)
     int dac_planes = 1;         // tune("dac_planes")=0: the wide classes (channels % 128 == 0, no fused unit) keep fp32 activations and stage snake + split per tile
     bool dac_buf_user = false;  // counted in g_dac_buffers[device].users
-    std::map<size_t, __bf16 *> packed_ct;   // transposed conv weight -> bf16 planes of convt_b3_kernel
     int dac_convt_planes = 1;   // tune("dac_convt_planes") = 0: the bf16 x 3 transposed convs always stage fp32 input (snake + split per workgroup) instead of the producer's planes
     int dac_convt_b3 = 1;       // tune("dac_convt_b3")=0: the transposed convs stay on the exact-fp32 MFMA kernel
     int dac_fuse = 1;           // tune("dac_fuse")=0: residual units at 96 / 192 channels stay two launches (k = 7 conv, k = 1 conv + residual)
@@ -541,6 +540,12 @@ static inline bool llama_many_rows(const tts_hip_ctx *c) { return c->has_llama &
 
 // ---- shim_core.hip
 void free_dev(void *p);
+// the layout knobs as codec_plan reads them.  Read where an image is planned and where tts_hip_tune compares before / after, nowhere else
+static inline CodecKnobs codec_knobs(const tts_hip_ctx *c) {
+    return CodecKnobs{(c->d.flags & TTS_HIP_FLAG_VALU_GEMM) ? 1 : 0, c->dac_f16, c->dac_b3, c->dac_fuse, c->dac_planes, c->dac_split, c->dac_f16_planes, c->dac_tap7,
+                      c->dac_convt_b3, c->dac_conv1_direct, c->kk_split, c->kk_b3, c->kk_mfma};
+}
+void drop_codec_images(tts_hip_ctx *c);   // synchronises, frees every packed image; the next pass plans and packs again
 template <typename T>
 static int dmalloc(T **p, size_t n) {   // n zeroed elements
     HIPCHK(hipMalloc((void **) p, n * sizeof(T)));
