@@ -117,6 +117,9 @@ void         *tts_c_runner_device_context(tts_c_runner *r);
  * environment at load, TTS_HIP_FLAG_KV_F16 / tts_hip_dia_desc::kv_type; Orpheus alone: 1 when TTS_HIP_KV_F8 was, the e4m3 cache of
  * tts_hip_orpheus_desc::kv_type - with both variables set the load fails, and a Parler or Dia load fails under TTS_HIP_KV_F8); 0 when the architecture does not report it */
 uint32_t      tts_c_runner_kv_element_bytes(tts_c_runner *r);
+/* bounded cross-attention launches of the decoder's last forward (a Dia runner: 0 unless TTS_HIP_DIA_CROSS_BOUNDED=1 was in the environment at load, which sets
+ * tts_hip_tune("dia_cross_bounded") on the context it opens; include/tts_hip.h); -1 when the architecture does not report it */
+int32_t       tts_c_runner_cross_bounded_launches(tts_c_runner *r);
 /* utterances a continuous session of the runner holds at once (tts_generation_runner::stream_capacity: an Orpheus runner's max_seqs, at most 256;
  * 0: the runner has no session) */
 uint32_t      tts_c_runner_stream_capacity(tts_c_runner *r);

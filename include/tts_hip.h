@@ -880,6 +880,18 @@ int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs
  *                       Like every key it is read when a step is issued: a loop graph captured before the call keeps replaying the route
  *                       it was captured with (set it before the first tts_hip_dia_generate / gen_* / stream_* of the context); the same
  *                       holds for tile_force and tile_ks.  The decoder must be at most 2048 wide for the route
+ *   dia_cross_bounded   1: the cross-attention reads the keys of a row slot's sentence and one fp32 row — the sum of the cache's V rows behind the
+ *                       sentence, written by the slot's encoder pass (tts_hip_dia_encode_slot, tts_hip_dia_stream_admit) — instead of all max_ctx
+ *                       keys: the zero K rows there score exactly 0, so they enter the softmax as P e^(0 - m) and e^(0 - m) sum V.  The same softmax . V
+ *                       in another association; results agree with key 0 to rounding, not bit for bit.  It applies wherever a step takes
+ *                       attn_gqa_wave_kernel's EXT form (step_batch, generate, gen_*, stream_*), which is where the keys are split over workgroups:
+ *                       rows x heads <= 256.  At Dia-1.6B shapes (16 heads) that is steps of at most 8 utterances, on the streaming route; the tiled
+ *                       route and every step of more rows are not reached (the tiled route is only on models of few heads).  A step on the split kernel (a context the eight passes
+ *                       do not cover, or attn_wave 0) or, with more rows, on the unsplit kernel stays on it, unbounded.  Default 0 on every context.  Read when a step
+ *                       is issued, like dia_tile_min_rows: set it before the first loop of the context.  A slot encoded before the key was first set is
+ *                       read unbounded until its next encoder pass.  tts_hip_debug_read: "di_cross_bounded" (bounded launches of the last forward),
+ *                       "di_klive" (keys read per row slot), "di_cvsum:<layer>:<row slot>" (the sums).  The host runner sets it on the contexts it
+ *                       opens when TTS_HIP_DIA_CROSS_BOUNDED=1 is in the environment at load
  *   tile_force, tile_ks tile shape index (0..5, -1 = the cost model's) and K slices of the residual GEMMs (0 = the cost model's) of every
  *                       tiled GEMM: tests and tuning */
 int tts_hip_tune(tts_hip_ctx *ctx, const char *key, int value);

@@ -16,6 +16,10 @@ on to the position, 16 steps of warm-up, then the timed steps; ms per step from 
               every context); 64 live utterances on a 128-slot context; 128 slots
 --far adds the legs at position 2000 (8 and 64 slots, 64 live of 128): 2000 steps to get there, so they run in the first --far-reps repetitions only.
 --profile: one eager 256-row step (128 slots, position 100) under tts_hip_profile, by class.
+--sentence N: the sentences' length in bytes (default 200: 824 of the 1024 text positions are pad; 1024: none).  --cross-bounded: this tree's legs a second
+time with tune("dia_cross_bounded") = 1 (", bounded": the cross-attention reads the sentence's keys and the pad rows' V sum; meant for --out profiles/dia_cross_bounded.json, not yet run),
+and the profile for both values of the key.  Every leg also carries encode_ms: one slot's encoder pass and cross K/V fill (bounded: plus the writer).  --slots:
+only the legs with that many live slots.
 Every figure is the list of its repetitions; the report prints median and max - min."""
 import argparse
 import json
@@ -30,6 +34,7 @@ import numpy as np
 MAX_GEN = 2100
 WARM = 16
 DELAY = [0, 8, 9, 10, 11, 12, 13, 14, 15]
+SENTENCE = 200
 
 
 def _setup():
@@ -44,23 +49,25 @@ def _setup():
     rng = np.random.default_rng(3)
     tensors, _ = sb.dia_tensors(cfg, rng)
     toks = np.zeros(cfg.max_ctx, dtype=np.uint32)
-    toks[:200] = rng.integers(32, 127, 200)
+    toks[:SENTENCE] = rng.integers(32, 127, SENTENCE)
     return gguf, hip, cfg, sb._Model(cfg, tensors), toks
 
 
-def _engine(gguf, hip, cfg, model, toks, ctx, live, kv, key):
+def _engine(gguf, hip, cfg, model, toks, ctx, live, kv, key, bounded=False):
     eng = hip.DiaEngine(cfg, max_utterances=ctx, **({"kv_type": gguf.F16} if kv == "f16" else {}))
     if key is not None:
         eng.tune("dia_tile_min_rows", key)
+    if bounded:
+        eng.tune("dia_cross_bounded", 1)
     eng.load(model)
     for u in range(live):
-        eng.encode_slot(u, toks, 200)
+        eng.encode_slot(u, toks, SENTENCE)
     return eng
 
 
-def one_leg(env, ctx, live, kv, key, positions, steps):
+def one_leg(env, ctx, live, kv, key, positions, steps, bounded=False):
     gguf, hip, cfg, model, toks = env
-    eng = _engine(gguf, hip, cfg, model, toks, ctx, live, kv, key)
+    eng = _engine(gguf, hip, cfg, model, toks, ctx, live, kv, key, bounded)
     eng.gen_begin(live, MAX_GEN, DELAY, cfg.bos, cfg.eos, cfg.pad, 15)
     out, at = {}, 0
     for P in positions:
@@ -78,6 +85,13 @@ def one_leg(env, ctx, live, kv, key, positions, steps):
         out["di_tiled"] = int(eng.debug_read("di_tiled", 1)[0])
     except Exception:      # a tree without the route
         out["di_tiled"] = 0
+    if bounded:
+        out["di_cross_bounded"] = int(eng.debug_read("di_cross_bounded", 1)[0])
+    eng.encode_slot(0, toks, SENTENCE)      # one slot's encoder pass and cross fill (the loop is over: encode_slot drops it; it waits for the stream itself)
+    t = time.perf_counter()
+    for _ in range(3):
+        eng.encode_slot(0, toks, SENTENCE)
+    out["encode_ms"] = round((time.perf_counter() - t) / 3 * 1e3, 4)
     eng.close()
     return out
 
@@ -100,18 +114,21 @@ def run_tree(args):
     positions = [2000] if args.far else [100]
     res = {}
     for name, ctx, live, key in legs_of(args.tree, args.far):
+        if args.slots and live not in args.slots:
+            continue
         for kv in args.kv.split(","):
-            r = one_leg(env, ctx, live, kv, key, positions, args.steps)
-            res["%s, %s cache" % (name, kv)] = r
-            print("#", name, kv, json.dumps(r), file=sys.stderr, flush=True)
+            for bounded in ((False, True) if args.cross_bounded and args.tree == "this" else (False,)):
+                r = one_leg(env, ctx, live, kv, key, positions, args.steps, bounded)
+                res["%s%s, %s cache" % (name, ", bounded" if bounded else "", kv)] = r
+                print("#", name, bounded, kv, json.dumps(r), file=sys.stderr, flush=True)
     print(json.dumps(res))
 
 
 def run_profile(args):
     gguf, hip, cfg, model, toks = env = _setup()
     res = {}
-    for kv in args.kv.split(","):
-        eng = _engine(*env, 128, 128, kv, None)
+    for kv, bounded in [(kv, b) for kv in args.kv.split(",") for b in ((False, True) if args.cross_bounded else (False,))]:
+        eng = _engine(*env, 128, 128, kv, None, bounded)
         ids = np.full((128, cfg.n_out), cfg.bos, dtype=np.uint32)
         pos = np.full(128, 100, dtype=np.uint32)
         eng.step_batch(ids, pos)
@@ -120,6 +137,7 @@ def run_profile(args):
             eng.step_batch(ids, pos)
         st = hip.engine_profile_get(eng)
         hip.engine_profile(eng, 0)
+        kv += ", bounded" if bounded else ""
         res[kv] = {k: {"ms_per_step": round(v["ms_total"] / 3, 4), "launches_per_step": v["launches"] // 3} for k, v in st.items() if v["launches"]}
         res[kv]["di_tiled"] = int(eng.debug_read("di_tiled", 1)[0])
         eng.close()
@@ -129,10 +147,11 @@ def run_profile(args):
 def orchestrate(args):
     me = os.path.abspath(__file__)
     outs = {"this": {}, "parent": {}}
-    meta = {"shapes": "dia-1.6b, fp16 matrices, max_gen %d, 200-byte sentences; ms per step of the device loop" % MAX_GEN, "steps_timed": args.steps}
+    meta = {"shapes": "dia-1.6b, fp16 matrices, max_gen %d, %d-byte sentences; ms per step of the device loop" % (MAX_GEN, SENTENCE), "steps_timed": args.steps}
+    extra = ["--sentence", str(SENTENCE)] + (["--cross-bounded"] if args.cross_bounded else []) + (["--slots"] + [str(s) for s in args.slots] if args.slots else [])
 
     def child(tree, cwd, far):
-        cmd = [sys.executable, me, "--tree", tree, "--kv", args.kv, "--steps", str(args.steps)] + (["--far"] if far else [])
+        cmd = [sys.executable, me, "--tree", tree, "--kv", args.kv, "--steps", str(args.steps)] + (["--far"] if far else []) + extra
         p = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=1100)
         sys.stderr.write(p.stderr[-4000:])
         if p.returncode != 0:
@@ -159,7 +178,7 @@ def orchestrate(args):
                 child("parent", args.parent, True)
             child("this", os.getcwd(), True)
     if args.with_profile:
-        p = subprocess.run([sys.executable, me, "--profile", "--kv", args.kv], capture_output=True, text=True, timeout=600)
+        p = subprocess.run([sys.executable, me, "--profile", "--kv", args.kv] + extra, capture_output=True, text=True, timeout=600)
         sys.stderr.write(p.stderr[-2000:])
         if p.returncode == 0:
             meta["profile_256_rows_eager"] = json.loads(p.stdout.strip().splitlines()[-1])
@@ -172,7 +191,7 @@ def report(files):
         print(fn, "(%s)" % d["shapes"])
         for name, by in d["ms_per_step"].items():
             for k, v in by.items():
-                if k != "di_tiled":
+                if k not in ("di_tiled", "di_cross_bounded"):
                     print("  %-36s position %-5s median %.4f  max - min %.4f  (%d)  tiled launches %s" % (name, k, statistics.median(v), max(v) - min(v), len(v), by.get("di_tiled", ["-"])[0]))
         for kv, classes in d.get("profile_256_rows_eager", {}).items():
             print("  eager 256-row step, %s cache:" % kv, json.dumps(classes))
@@ -189,10 +208,15 @@ def main():
     ap.add_argument("--far", action="store_true", help="also the legs at position 2000, in the first --far-reps repetitions")
     ap.add_argument("--far-reps", type=int, default=2)
     ap.add_argument("--with-profile", action="store_true")
+    ap.add_argument("--sentence", type=int, default=200, help="bytes per sentence, 1 .. 1024")
+    ap.add_argument("--cross-bounded", action="store_true", help="this tree's legs also with tune('dia_cross_bounded') = 1")
+    ap.add_argument("--slots", type=int, nargs="*", help="only the legs with this many live slots")
     ap.add_argument("--tree", help="internal: run the legs of 'this' or 'parent' tree in this process")
     ap.add_argument("--profile", action="store_true", help="internal: the eager 256-row step by class")
     ap.add_argument("--report", nargs="+", metavar="FILE")
     args = ap.parse_args()
+    global SENTENCE
+    SENTENCE = args.sentence
     if args.report:
         return report(args.report)
     if args.profile:

@@ -1056,6 +1056,23 @@ int dia_tiled_buffers(tts_hip_ctx *c) {
     return 0;
 }
 
+// di_cvsum / di_klive, what the bounded cross-attention reads beside the caches: allocated once tune("dia_cross_bounded") is non-zero, by finalize or by the
+// tts_hip_tune call that turns the key on afterwards, and behind every other buffer: a context that leaves the key at 0 allocates what it always allocated, in
+// the same order.  Every length starts at max_ctx — a slot encoded before the buffers existed stays unbounded (no pad keys, its sums are never read) until
+// its next encoder pass.
+int dia_cross_buffers(tts_hip_ctx *c) {
+    if (!c->has_dia || c->di_cvsum || !c->dia_cross_bounded || c->di_U < 1 || !c->di_x) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t RS = (size_t) 2 * c->di_U, nsum = (size_t) c->L * RS * c->di_A;
+    HIPCHK(hipMalloc((void **) &c->di_cvsum, nsum * 4));
+    HIPCHK(hipMalloc((void **) &c->di_klive, RS * 4));
+    HIPCHK(hipMemset(c->di_cvsum, 0, nsum * 4));
+    const std::vector<uint32_t> klive(RS, c->dia.max_ctx);
+    HIPCHK(hipMemcpy(c->di_klive, klive.data(), RS * 4, hipMemcpyHostToDevice));
+    c->di_klive_host.assign((size_t) c->di_U, c->dia.max_ctx);
+    return 0;
+}
+
 extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
     if (!c) return set_err("null ctx");
     if (c->finalized) return set_err("tts_hip_finalize: already finalized");
@@ -1236,6 +1253,7 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         std::vector<uint32_t> cend((size_t) R, (uint32_t) S);
         HIPCHK(hipMemcpy(c->di_cend, cend.data(), (size_t) R * 4, hipMemcpyHostToDevice));
         CHK(dia_tiled_buffers(c));   // after everything else, and only where the tiled route can be taken: a context with the key at 0 allocates what it always allocated
+        CHK(dia_cross_buffers(c));   // the same for tune("dia_cross_bounded")
     }
     if (c->has_t5) {
         const int H = c->H, F = c->F, S = (int) c->t5.max_ctx_length;
@@ -2547,6 +2565,28 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (max_floats < 1) { set_err("debug_read(%s): buffer too small", what); return -1; }
         out[0] = (float) (w == "di_tiled" ? c->di_tiled : c->di_pending_max);
         return 1;
+    }
+    if (c->has_dia && w == "di_cross_bounded") {   // attn_cross_bounded_kernel launches of the last decoder forward issued (a captured step replays what its capture counted); 0 with the key off
+        if (max_floats < 1) { set_err("debug_read(%s): buffer too small", what); return -1; }
+        out[0] = (float) c->di_cross_bounded;
+        return 1;
+    }
+    if (c->has_dia && (w == "di_klive" || starts_with(w, "di_cvsum:"))) {   // "di_klive": [2 * slots] keys the bounded reader reads per row slot; "di_cvsum:<layer>:<row slot>": [A] the sum of the V rows behind them
+        if (!c->di_cvsum) { set_err("debug_read(%s): tune(\"dia_cross_bounded\") has not been set on this context", what); return -1; }
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (w == "di_klive") {
+            const size_t n = std::min(max_floats, (size_t) 2 * c->di_U);
+            std::vector<uint32_t> k(n);
+            if (hipMemcpy(k.data(), c->di_klive, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = (float) k[i];
+            return (int64_t) n;
+        }
+        int layer = 0, row = 0;
+        if (sscanf(w.c_str() + 9, "%d:%d", &layer, &row) != 2 || layer < 0 || layer >= c->L || row < 0 || row >= 2 * c->di_U) { set_err("debug_read(%s): bad layer/row slot", what); return -1; }
+        const size_t n = std::min(max_floats, (size_t) c->di_A);
+        if (hipMemcpy(out, c->di_cvsum + ((size_t) layer * 2 * c->di_U + row) * c->di_A, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        return (int64_t) n;
     }
     if (c->has_dia && w.size() > 5 && w[0] == 'd' && w[1] == 'i' && w[2] == '_') {   // "di_k|di_v:<layer>:<row slot>" [max_gen][kv width], "di_ck|di_cv:<layer>:<row slot>" [max_ctx][A]
         const bool cross = w[3] == 'c';

@@ -213,6 +213,13 @@ struct tts_hip_ctx {
     int dia_tile_min_rows = 0;    // tune("dia_tile_min_rows"): steps of at least this many rows (and more than 16) take the route; 0 = never.  0 up to 64 slots, 17 above
     int di_tiled = 0;             // gemm_tile_kernel launches of the last dia_forward (debug_read "di_tiled")
     int di_pending_max = 0;       // most K-slice slabs one GEMM of the last dia_forward left in di_parts (debug_read "di_pending_max")
+    // the bounded cross-attention (dia_cross_kernels.h): the sum of the V rows behind each row slot's sentence and the sentence lengths, written by the encoder
+    // pass of a slot (dia_encode_into) from the moment they exist.  NULL until the key is first set (dia_cross_buffers)
+    float *di_cvsum = nullptr;    // [L][2 * di_U][A] fp32
+    std::vector<uint32_t> di_klive_host;   // [di_U] the host's copy of the lengths, per slot (tts_hip_profile's byte count of a bounded launch)
+    uint32_t *di_klive = nullptr; // [2 * di_U] keys the bounded reader reads of a row slot; max_ctx for a slot no encoder pass has filled since: unbounded
+    int dia_cross_bounded = 0;    // tune("dia_cross_bounded"): steps whose cross-attention takes attn_gqa_wave_kernel's EXT form take attn_cross_bounded_kernel; 0 on every context
+    int di_cross_bounded = 0;     // attn_cross_bounded_kernel launches of the last dia_forward (debug_read "di_cross_bounded")
     int di_U = 1;                        // utterance slots (rows = 2 per slot)
     // One loop, two ways in.  BATCH (tts_hip_dia_gen_begin / _launch / _wait, tts_hip_dia_generate): n encoded slots, all live from the first
     // step with the budget max_gen, until the last one has parked.  SESSION (tts_hip_dia_stream_*): n slots that begin parked; admissions
@@ -588,6 +595,7 @@ bool attr_needed(std::atomic<uint64_t> &done, int device);
 int prof_begin(tts_hip_ctx *c, int kclass, double bytes, double flops);
 int prof_end(tts_hip_ctx *c);
 int dia_tiled_buffers(tts_hip_ctx *c);   // di_h16 once tune("dia_tile_min_rows") is above 0 (finalize, or the tune call after it)
+int dia_cross_buffers(tts_hip_ctx *c);   // di_cvsum / di_klive once tune("dia_cross_bounded") is non-zero (finalize, or the tune call after it)
 int ready(tts_hip_ctx *c, const char *who);
 int stage_uniforms(tts_hip_ctx *c, const float *uniforms, size_t count);
 int stage_penalty(tts_hip_ctx *c, float penalty, int n);

@@ -8,6 +8,7 @@
 #include "gemv_kernels.h"
 #include "shim_decoder.h"
 #include "shim_dia_rows.h"
+#include "shim_dia_cross.h"
 
 // Orpheus decoder (src/models/orpheus/model.cpp:186-325)
 // ------------------------------------------------------------------------------------------------
@@ -83,10 +84,13 @@ static int attn_gqa_allow_lds(tts_hip_ctx *c, size_t lds) {
 
 // attention of the Llama / Dia steps: one workgroup per (head, row), or — few rows, many keys — the keys split over `nz` workgroups
 // plus a combine launch (attn_gqa_kernel<128, true, KV>).  max_keys bounds the LDS score buffer.  seq_stride counts cache elements.
+// klive / vsum (Dia's cross-attention with tune("dia_cross_bounded") on: the row slots' sentence lengths and the V sums behind them, of this layer): where the
+// choice is the EXT form, its bounded sibling attn_cross_bounded_kernel (shim_dia_cross.hip) runs instead and the combine follows unchanged.  Where the
+// choice is the split kernel (a context the eight passes do not cover, or tune("attn_wave") 0) the step stays on it, over all keys: unbounded.
 template <typename KV>
 static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const KV *kc, const KV *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
-                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0) {
+                           QPre qp = QPre{}, int *deferred = nullptr, int n_ctx_keys = 0, const uint32_t *klive = nullptr, const float *vsum = nullptr) {
     int nz = 1;
     if (deferred) *deferred = 0;
     if (c->attn_split_max > 1 && NHq * rows <= 256) {
@@ -112,7 +116,12 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
             ext = c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8;
             // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through KVRow<KV>::EXT_SLOTS
             // rolling register slots (the parked rows of a loop step, kend[r] = 1, request that one key only)
-            if (ext) {
+            if (ext && vsum && row_seq && NKV == NHq) {
+                if (!dia_cross_bounded(c->stream, (int) sizeof(KV), qkv, ld, kc, vc, NHq, rows, nz, scale, c->attn_part, n_ctx_keys, kend, row_seq, seq_stride, klive, vsum, qp.n_parts,
+                                       qp.part_stride, qp.rope_pos, qp.theta_scale))
+                    return set_err("attn_cross_bounded_kernel launch failed");
+                c->di_cross_bounded++;
+            } else if (ext) {
                 hipLaunchKernelGGL((attn_gqa_wave_kernel<128, KVRow<KV>::EXT_SLOTS, true, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale,
                                    c->attn_part, n_ctx_keys, kend, row_seq, seq_stride, qp);
             }
@@ -1420,6 +1429,15 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
             for (int b = 0; b < 2; b++)
                 HIPCHK(hipMemsetAsync(ck + ((size_t) b * S + sentence_len) * A * esz, 0, (size_t) (S - (int) sentence_len) * A * esz, c->stream));
     }
+    // the bounded cross-attention's side of the fill, from the moment its buffers exist (whatever the key says now: a slot filled while it is off must not
+    // leave a stale length behind): the sum of the slot's V rows behind the sentence in every layer, and the sentence length (dia_cross_padsum_kernel)
+    if (c->di_cvsum) {
+        CHK(prof_begin(c, TTS_HIP_K_GEMM_OTHER, (double) c->L * 2 * (S - (int) sentence_len) * A * (double) c->di_kv_esz, 0));
+        const bool launched = dia_cross_padsum(c->stream, c->di_kv_esz, c->di_cv, c->L, 2 * c->di_U, S, A, (int) slot, (int) sentence_len, c->di_cvsum, c->di_klive);
+        CHK(prof_end(c));
+        if (!launched) return set_err("dia_cross_padsum_kernel launch failed");
+        c->di_klive_host[slot] = sentence_len;
+    }
     if (enc_out) HIPCHK(hipMemcpyAsync(enc_out, c->di_exn, (size_t) n * EH * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->di_slot_encoded[slot] = 1;
@@ -1448,6 +1466,19 @@ static int dia_attn_snapshot(tts_hip_ctx *c, int layer, bool cross, const float 
     s.meta.assign({(float) n_parts, (float) part_stride, (float) ld, (float) R});
     for (uint32_t v : u) s.meta.push_back((float) v);
     return 0;
+}
+
+// layer l's V sums for launch_attn_gqa, or NULL: tune("dia_cross_bounded") is 0 and the cross-attention reads all max_ctx keys as it always did
+static const float *dia_cross_vsum(const tts_hip_ctx *c, int l) {
+    return c->dia_cross_bounded && c->di_cvsum ? c->di_cvsum + (size_t) l * 2 * c->di_U * c->di_A : nullptr;
+}
+
+// what tts_hip_profile counts for a bounded launch: the mean sentence length of the context's slots stands for every row's keys (which slot a row belongs to is
+// device state in the loop); a slot no encoder pass has filled since the buffers exist counts max_ctx, as it is read
+static double dia_cross_mean_keys(const tts_hip_ctx *c) {
+    double sum = 0.0;
+    for (uint32_t n : c->di_klive_host) sum += n;
+    return sum / (double) std::max<size_t>(c->di_klive_host.size(), 1);
 }
 
 // ---- the tiled route: a decoder step of more than 16 rows with every matrix on gemm_tile_kernel -----------------------------------------------
@@ -1531,9 +1562,10 @@ static int dia_forward_tiled(tts_hip_ctx *c, int U, int self_keys, bool fixed_sp
         QPre qp;   // one part; the rope of the cross-attention query happens as the attention workgroups load it
         qp.n_parts = 1; qp.part_stride = 0; qp.rope_pos = c->di_pos; qp.theta_scale = theta_scale;
         CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
-            CHK(prof_begin(c, TTS_HIP_K_ATTN_CROSS, (double) R * S * 2 * A * kvb, 0));
+            CHK(prof_begin(c, TTS_HIP_K_ATTN_CROSS, dia_cross_vsum(c, l) ? (double) R * (dia_cross_mean_keys(c) * 2 * A * kvb + A * 4.0) : (double) R * S * 2 * A * kvb, 0));
             CHK(launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
-                                                    (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp, nullptr, S));
+                                                    (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp, nullptr, S, c->di_klive,
+                                                    dia_cross_vsum(c, l)));
             return prof_end(c);
         }));
         if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, 1, 0, R, A, c->di_cend));
@@ -1572,6 +1604,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     c->di_pending = 0;
     c->di_pending_max = 0;
     c->di_tiled = 0;
+    c->di_cross_bounded = 0;
     if (dia_step_tiled(c, R)) {   // more than 16 rows, fp16 matrices, tune("dia_tile_min_rows") reached: every GEMM on gemm_tile_kernel
         const uint64_t before = c->tile_launches;
         CHK(dia_forward_tiled(c, U, self_keys, fixed_split, snap));
@@ -1613,7 +1646,8 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
             return launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
                                                                        (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
-                                                                       A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S);
+                                                                       A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S, c->di_klive,
+                                                                       dia_cross_vsum(c, l));
         }));
         if (snap) CHK(dia_attn_snapshot(c, l, true, c->di_q, A, qp.n_parts, qp.part_stride, R, A, c->di_cend));
         CHK(dia_gemm_stream(c, y.co, c->di_att, A, c->di_parts, DH, R, DIA_STREAM_SLABS, (int64_t) c->RMAX * DH, &sl, slices ? PRO_ATTN8 : PRO_F32));
@@ -1739,7 +1773,7 @@ static int dia_loop_step(tts_hip_ctx *c, const DiaLoopArgs &la, bool captured) {
     const int U = (int) g.n, NO = c->NO, V = c->di_V;
     hipLaunchKernelGGL(dia_loop_prestep_kernel, dim3((U + 63) / 64), dim3(64), 0, c->stream, la);
     HIPCHK(hipGetLastError());
-    CHK(dia_forward(c, U, (int) c->dia.max_gen, captured));
+    CHK(dia_forward(c, U, (int) c->dia.max_gen, captured, c->debug && !captured));   // debug: an eager step of the loop leaves the snapshots step_batch leaves (parked rows included)
     if (g.mixed) {   // one launch whatever the slots hold: every row reads its slot's record, greedy rows leave after sampler::max
         SampleArgs sa{};
         sa.logits = c->di_guided; sa.V = V; sa.n_out = NO; sa.R = U;

@@ -108,6 +108,8 @@ struct tts_generation_runner : tts_runner {
     // bytes per element of the decoder's K/V cache as its device context reports them (orpheus_runner: 4, 2 when TTS_HIP_KV_F16 or 1 when TTS_HIP_KV_F8 was set at load);
     // 0: the runner does not report it
     virtual uint32_t kv_element_bytes() const { return 0; }
+    // bounded cross-attention launches of the decoder's last forward (dia_runner: 0 unless TTS_HIP_DIA_CROSS_BOUNDED=1 was set at load); -1: the runner does not report it
+    virtual int32_t  cross_bounded_launches() const { return -1; }
 
     // ---- extension: continuous batching — a session that takes utterances in while others are still generating ---------------------
     // The reference's server hands one task at a time to a worker that owns a whole model (examples/server/server.cpp:126-158, 236-271);

@@ -79,6 +79,13 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : stream_session{dia
     if (getenv("TTS_HIP_KV_F16")) d.kv_type = TTS_HIP_F16;   // the switch the Parler and Orpheus runners read: fp16 self and cross K/V caches (extension, include/tts_hip.h)
     lm = tts_hip_dia_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_dia_create failed: %s\n", tts_hip_last_error());
+    // read at load like the cache type: cross-attention over the sentence's keys plus the pad rows' V sum instead of all max_ctx keys (extension, include/tts_hip.h)
+    if (const char * e = getenv("TTS_HIP_DIA_CROSS_BOUNDED"))
+        if (atoi(e) != 0 && tts_hip_tune(lm, "dia_cross_bounded", 1) != 0) {
+            tts_hip_destroy(lm);
+            lm = nullptr;
+            TTS_ABORT("tts_hip_tune(dia_cross_bounded) failed: %s\n", tts_hip_last_error());
+        }
     tts_hip_desc a{};
     a.struct_size = sizeof(a);
     a.dac_n_blocks = hp.dac_n_layers;
@@ -108,6 +115,11 @@ dia_runner::~dia_runner() {
 uint32_t dia_runner::kv_element_bytes() const {
     float v = 0.0f;
     return tts_hip_debug_read(lm, "di_kv_elem", &v, 1) == 1 ? (uint32_t) v : 0;
+}
+
+int32_t dia_runner::cross_bounded_launches() const {
+    float v = 0.0f;
+    return tts_hip_debug_read(lm, "di_cross_bounded", &v, 1) == 1 ? (int32_t) v : -1;
 }
 
 void dia_runner::assign_weight(const char * name, const gguf_tensor_view & t) {

@@ -34,7 +34,8 @@ EXPORTS = ["tts_c_default_config", "tts_c_runner_from_file", "tts_c_generate", "
            "tts_c_kokoro_duration_groups", "tts_c_kokoro_noise_starts",
            "tts_c_generate_chunked", "tts_c_generate_batch_chunked", "tts_c_parler_final_frames", "tts_c_dia_final_frames", "tts_c_chunk_windows",
            "tts_c_generate_stream_chunked", "tts_c_generate_stream_configs", "tts_c_generate_stream_chunked_configs",
-           "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes", "tts_c_runner_stream_capacity"]
+           "tts_c_add_voice", "tts_c_list_voices", "tts_c_pool_add_voice", "tts_c_runner_kv_element_bytes", "tts_c_runner_stream_capacity",
+           "tts_c_runner_cross_bounded_launches"]
 
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t)   # tts_c_chunk_fn
 
@@ -118,6 +119,8 @@ def load_lib():
         L.tts_c_runner_device_context.restype = C.c_void_p
         L.tts_c_runner_kv_element_bytes.argtypes = [C.c_void_p]
         L.tts_c_runner_kv_element_bytes.restype = C.c_uint32
+        L.tts_c_runner_cross_bounded_launches.argtypes = [C.c_void_p]
+        L.tts_c_runner_cross_bounded_launches.restype = C.c_int32
         L.tts_c_runner_stream_capacity.argtypes = [C.c_void_p]
         L.tts_c_runner_stream_capacity.restype = C.c_uint32
         L.tts_c_runner_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]
@@ -283,6 +286,10 @@ class Runner:
         """bytes per element of the decoder's K/V cache (Orpheus: 4, 2 with TTS_HIP_KV_F16 or 1 with TTS_HIP_KV_F8 (the e4m3 cache) in the environment
         at load; both set: the load fails); 0: not reported"""
         return int(self.L.tts_c_runner_kv_element_bytes(self.h))
+
+    def cross_bounded_launches(self):
+        """bounded cross-attention launches of the decoder's last forward (Dia: 0 unless TTS_HIP_DIA_CROSS_BOUNDED=1 was in the environment at load); -1: not reported"""
+        return int(self.L.tts_c_runner_cross_bounded_launches(self.h))
 
     def stream_capacity(self):
         """utterances a continuous session of this runner holds at once (0: no session)"""
