@@ -883,11 +883,11 @@ int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs
  *   dia_cross_bounded   1: the cross-attention reads the keys of a row slot's sentence and one fp32 row — the sum of the cache's V rows behind the
  *                       sentence, written by the slot's encoder pass (tts_hip_dia_encode_slot, tts_hip_dia_stream_admit) — instead of all max_ctx
  *                       keys: the zero K rows there score exactly 0, so they enter the softmax as P e^(0 - m) and e^(0 - m) sum V.  The same softmax . V
- *                       in another association; results agree with key 0 to rounding, not bit for bit.  It applies wherever a step takes
- *                       attn_gqa_wave_kernel's EXT form (step_batch, generate, gen_*, stream_*), which is where the keys are split over workgroups:
- *                       rows x heads <= 256.  At Dia-1.6B shapes (16 heads) that is steps of at most 8 utterances, on the streaming route; the tiled
- *                       route and every step of more rows are not reached (the tiled route is only on models of few heads).  A step on the split kernel (a context the eight passes
- *                       do not cover, or attn_wave 0) or, with more rows, on the unsplit kernel stays on it, unbounded.  Default 0 on every context.  Read when a step
+ *                       in another association; results agree with key 0 to rounding, not bit for bit.  It applies to every step (step_batch, generate,
+ *                       gen_*, stream_*; the streaming and the tiled route alike): where the keys are split over workgroups (rows x heads <= 256: up to 8
+ *                       utterances at Dia-1.6B shapes) in place of attn_gqa_wave_kernel's EXT form (attn_cross_bounded_kernel), with more rows in place of the
+ *                       unsplit kernel (attn_cross_bounded_rows_kernel, which writes the attended rows itself).  Only a step whose key-split choice is the split
+ *                       kernel (a context the eight passes do not cover, or attn_wave 0) stays on it, unbounded.  Default 0 on every context.  Read when a step
  *                       is issued, like dia_tile_min_rows: set it before the first loop of the context.  A slot encoded before the key was first set is
  *                       read unbounded until its next encoder pass.  tts_hip_debug_read: "di_cross_bounded" (bounded launches of the last forward),
  *                       "di_klive" (keys read per row slot), "di_cvsum:<layer>:<row slot>" (the sums).  The host runner sets it on the contexts it

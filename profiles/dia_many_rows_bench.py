@@ -17,7 +17,7 @@ on to the position, 16 steps of warm-up, then the timed steps; ms per step from 
 --far adds the legs at position 2000 (8 and 64 slots, 64 live of 128): 2000 steps to get there, so they run in the first --far-reps repetitions only.
 --profile: one eager 256-row step (128 slots, position 100) under tts_hip_profile, by class.
 --sentence N: the sentences' length in bytes (default 200: 824 of the 1024 text positions are pad; 1024: none).  --cross-bounded: this tree's legs a second
-time with tune("dia_cross_bounded") = 1 (", bounded": the cross-attention reads the sentence's keys and the pad rows' V sum; meant for --out profiles/dia_cross_bounded.json, not yet run),
+time with tune("dia_cross_bounded") = 1 (", bounded": the cross-attention reads the sentence's keys and the pad rows' V sum; the run behind profiles/dia_cross_bounded.json / dia_cross_bounded_parent_before.json),
 and the profile for both values of the key.  Every leg also carries encode_ms: one slot's encoder pass and cross K/V fill (bounded: plus the writer).  --slots:
 only the legs with that many live slots.
 Every figure is the list of its repetitions; the report prints median and max - min."""

@@ -92,10 +92,23 @@ __global__ __launch_bounds__(256) void dia_cross_padsum_kernel(const KV *vcache,
 // klive >= 1 (the encoder pass refuses an empty sentence; the max(1, ..) below only keeps a request in bounds).
 // klive is indexed by row slot, so the limits are two dependent scalar loads (row_seq[r], then klive) ahead of the first row request, one more than the
 // EXT form's.
-template <int U, typename KV>
-__global__ __launch_bounds__(256) void attn_cross_bounded_kernel(const float *qkv, int ld, const KV *kcache, const KV *vcache, int NH, float scale, float *part, int n_ctx,
-                                                                const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive, const float *vsum,
-                                                                QPre qp) {
+//
+// attn_cross_bounded_rows_kernel (ROWS; launch_attn_gqa's launch of more than 256 (head, row) pairs, where no keys are split): the finished-row form.  grid
+// (head, row), one slice (z = 0, nz = 1: key j is group j % 16, pass j / 16), the same requests, consume, wave merge and five-partial workgroup merge; what differs:
+//   * the pass count is ceil(live / 16), a runtime value up to n_ctx / 16, not eight: rounds of U passes, straight-line inside a round so that every slot
+//     index is a compile-time constant (the slots stay registers), around them a loop whose carried state is the U slots, the running max / sum / row and the
+//     round's first pass.  Pass p's slot is requested again for pass p + U the moment p is consumed, clamped to key live - 1 whatever p + U is (a request
+//     behind the sentence re-reads one cached row and is dropped).  The loop runs the whole rounds that have a pass behind them and has one exit; the last
+//     round — every pass of it is in flight by then, nothing more is requested — is a straight-line tail with the slice form's uniform exit after each pass.
+//     (One loop with that exit inside its rounds compiles to exits that join the round's end before they leave, and the waits at the head of a round then
+//     cover every request in flight: vmcnt(0) where 4 (U - 1) may stay outstanding.  As written the waits are vmcnt(4 (U - 1) + 3 ..) throughout.)
+//   * the workgroup divides by the total (live >= 1: never 0) and writes out[r][h 128 + tid], fp32, itself: no partial buffer, no combine launch.
+// Against attn_gqa_kernel<128, false, KV>, the launch it replaces: K and V of a pass are requested together and consumed by an online softmax — no LDS score
+// buffer, no second key pass, three barriers in all — and `live` keys plus one fp32 row are read instead of kend[r].
+template <int U, typename KV, bool ROWS>
+__device__ __forceinline__ void attn_cross_bounded_body(const float *qkv, int ld, const KV *kcache, const KV *vcache, int NH, float scale, float *dst, int n_ctx,
+                                                        const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive, const float *vsum,
+                                                        const QPre &qp) {
     constexpr int HD = 128;
     static_assert(U >= 1 && U <= 8, "eight passes through U register slots");
     typedef KVRow<KV> Row;
@@ -103,7 +116,7 @@ __global__ __launch_bounds__(256) void attn_cross_bounded_kernel(const float *qk
     __shared__ __attribute__((aligned(16))) float s_acc[4][HD];
     __shared__ __attribute__((aligned(16))) float s_q[HD];
     __shared__ float s_pad[HD];
-    const int h = blockIdx.x, r = blockIdx.y, z = blockIdx.z, nz = gridDim.z, tid = threadIdx.x, lane = tid & 63;
+    const int h = blockIdx.x, r = blockIdx.y, z = ROWS ? 0 : blockIdx.z, nz = ROWS ? 1 : gridDim.z, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, sub = lane & 15, gi = wave * 4 + g;
     const int kvH = NH * HD;   // one K/V head per query head
     const int seq = (int) row_seq[r];
@@ -182,14 +195,34 @@ __global__ __launch_bounds__(256) void attn_cross_bounded_kernel(const float *qk
             m = mn;
         }
     };
-    // eight passes (the host checks: at most 16 nz 8 keys), U register slots: a slot is requested again for pass p + U the moment pass p has been consumed
+    if constexpr (ROWS) {
+        // ceil(live / 16) passes in rounds of U: slot u of a round holds pass p0 + u and is requested again for pass p0 + u + U the moment it has been consumed
+        int p0 = 0;
+        for (; 16 * (p0 + U) < live; p0 += U) {   // a whole round with at least one pass behind it
 #pragma unroll
-    for (int p = 0; p < 8; p++) {
-        consume(p % U, p);
-        __builtin_amdgcn_sched_barrier(0);   // the slot's registers are free only now
-        if (p + U < 8) request_one(p % U, p + U);
-        __builtin_amdgcn_sched_barrier(0);
-        if (16 * nz * (p + 1) >= live) break;   // workgroup-uniform: no key of pass p + 1 or later, in any slice, is below `live`
+            for (int u = 0; u < U; u++) {
+                consume(u, p0 + u);
+                __builtin_amdgcn_sched_barrier(0);   // the slot's registers are free only now
+                request_one(u, p0 + u + U);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {   // the last round: its passes are all requested, 16 (p0 + U) >= live
+            consume(u, p0 + u);
+            __builtin_amdgcn_sched_barrier(0);
+            if (16 * (p0 + u + 1) >= live) break;   // workgroup-uniform: no key of the next pass is below `live`
+        }
+    } else {
+        // eight passes (the host checks: at most 16 nz 8 keys), U register slots: a slot is requested again for pass p + U the moment pass p has been consumed
+#pragma unroll
+        for (int p = 0; p < 8; p++) {
+            consume(p % U, p);
+            __builtin_amdgcn_sched_barrier(0);   // the slot's registers are free only now
+            if (p + U < 8) request_one(p % U, p + U);
+            __builtin_amdgcn_sched_barrier(0);
+            if (16 * nz * (p + 1) >= live) break;   // workgroup-uniform: no key of pass p + 1 or later, in any slice, is below `live`
+        }
     }
     // the wave's four groups (lanes sub, 16 + sub, 32 + sub, 48 + sub hold the same dims): common max, rescale, add
     auto x16 = [](float v) { const unsigned w = __builtin_bit_cast(unsigned, v); const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
@@ -227,8 +260,28 @@ __global__ __launch_bounds__(256) void attn_cross_bounded_kernel(const float *qk
             o += f * s_pad[tid];
             L += f * (float) P;
         }
-        float *pz = part + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
-        pz[2 + tid] = o;
-        if (tid == 0) { pz[0] = M; pz[1] = L; }
+        if constexpr (ROWS) {
+            dst[((int64_t) r * NH + h) * HD + tid] = o / L;   // (a parked row: o is its one V row, L is 1)
+        } else {
+            float *pz = dst + (((int64_t) r * NH + h) * nz + z) * ATTN_PART;
+            pz[2 + tid] = o;
+            if (tid == 0) { pz[0] = M; pz[1] = L; }
+        }
     }
+}
+
+// grid (head, row, slice); `part`: the slices' partials for attn_gqa_combine_kernel
+template <int U, typename KV>
+__global__ __launch_bounds__(256) void attn_cross_bounded_kernel(const float *qkv, int ld, const KV *kcache, const KV *vcache, int NH, float scale, float *part, int n_ctx,
+                                                                const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive, const float *vsum,
+                                                                QPre qp) {
+    attn_cross_bounded_body<U, KV, false>(qkv, ld, kcache, vcache, NH, scale, part, n_ctx, kend, row_seq, seq_stride, klive, vsum, qp);
+}
+
+// grid (head, row); `out`: the attended rows [rows][NH 128], fp32
+template <int U, typename KV>
+__global__ __launch_bounds__(256) void attn_cross_bounded_rows_kernel(const float *qkv, int ld, const KV *kcache, const KV *vcache, int NH, float scale, float *out, int n_ctx,
+                                                                     const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive,
+                                                                     const float *vsum, QPre qp) {
+    attn_cross_bounded_body<U, KV, true>(qkv, ld, kcache, vcache, NH, scale, out, n_ctx, kend, row_seq, seq_stride, klive, vsum, qp);
 }

@@ -2566,7 +2566,7 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         out[0] = (float) (w == "di_tiled" ? c->di_tiled : c->di_pending_max);
         return 1;
     }
-    if (c->has_dia && w == "di_cross_bounded") {   // attn_cross_bounded_kernel launches of the last decoder forward issued (a captured step replays what its capture counted); 0 with the key off
+    if (c->has_dia && w == "di_cross_bounded") {   // bounded reader launches (attn_cross_bounded_kernel / _rows_kernel) of the last decoder forward issued (a captured step replays what its capture counted); 0 with the key off
         if (max_floats < 1) { set_err("debug_read(%s): buffer too small", what); return -1; }
         out[0] = (float) c->di_cross_bounded;
         return 1;

@@ -1,4 +1,4 @@
-// shim_dia_cross.h — launchers of shim_dia_cross.hip (the kernels of dia_cross_kernels.h), called by dia_encode_into and launch_attn_gqa.
+// shim_dia_cross.h — launchers of shim_dia_cross.hip (the kernels of dia_cross_kernels.h), called by dia_encode_into and launch_attn_gqa (both of its branches).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,3 +11,8 @@ bool dia_cross_padsum(hipStream_t stream, int kv_esz, const void *cv, int L, int
 bool dia_cross_bounded(hipStream_t stream, int kv_esz, const float *q, int ld, const void *kc, const void *vc, int NH, int rows, int nz, float scale, float *part, int n_ctx,
                        const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive, const float *vsum, int n_parts, int64_t part_stride,
                        const uint32_t *rope_pos, float theta_scale);
+// the finished-row form for a launch that splits no keys (attn_cross_bounded_rows_kernel): grid (NH, rows), the attended rows into out [rows][NH 128] (fp32), any
+// number of keys up to n_ctx, no partials and no combine launch behind it
+bool dia_cross_bounded_rows(hipStream_t stream, int kv_esz, const float *q, int ld, const void *kc, const void *vc, int NH, int rows, float scale, float *out, int n_ctx,
+                            const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, const uint32_t *klive, const float *vsum, int n_parts, int64_t part_stride,
+                            const uint32_t *rope_pos, float theta_scale);

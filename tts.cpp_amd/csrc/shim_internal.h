@@ -218,8 +218,8 @@ struct tts_hip_ctx {
     float *di_cvsum = nullptr;    // [L][2 * di_U][A] fp32
     std::vector<uint32_t> di_klive_host;   // [di_U] the host's copy of the lengths, per slot (tts_hip_profile's byte count of a bounded launch)
     uint32_t *di_klive = nullptr; // [2 * di_U] keys the bounded reader reads of a row slot; max_ctx for a slot no encoder pass has filled since: unbounded
-    int dia_cross_bounded = 0;    // tune("dia_cross_bounded"): steps whose cross-attention takes attn_gqa_wave_kernel's EXT form take attn_cross_bounded_kernel; 0 on every context
-    int di_cross_bounded = 0;     // attn_cross_bounded_kernel launches of the last dia_forward (debug_read "di_cross_bounded")
+    int dia_cross_bounded = 0;    // tune("dia_cross_bounded"): the cross-attention reads the sentence's keys: attn_cross_bounded_kernel where keys are split, attn_cross_bounded_rows_kernel where not; 0 on every context
+    int di_cross_bounded = 0;     // bounded reader launches (either form) of the last dia_forward (debug_read "di_cross_bounded")
     int di_U = 1;                        // utterance slots (rows = 2 per slot)
     // One loop, two ways in.  BATCH (tts_hip_dia_gen_begin / _launch / _wait, tts_hip_dia_generate): n encoded slots, all live from the first
     // step with the budget max_gen, until the last one has parked.  SESSION (tts_hip_dia_stream_*): n slots that begin parked; admissions

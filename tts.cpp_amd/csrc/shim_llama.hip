@@ -86,7 +86,9 @@ static int attn_gqa_allow_lds(tts_hip_ctx *c, size_t lds) {
 // plus a combine launch (attn_gqa_kernel<128, true, KV>).  max_keys bounds the LDS score buffer.  seq_stride counts cache elements.
 // klive / vsum (Dia's cross-attention with tune("dia_cross_bounded") on: the row slots' sentence lengths and the V sums behind them, of this layer): where the
 // choice is the EXT form, its bounded sibling attn_cross_bounded_kernel (shim_dia_cross.hip) runs instead and the combine follows unchanged.  Where the
-// choice is the split kernel (a context the eight passes do not cover, or tune("attn_wave") 0) the step stays on it, over all keys: unbounded.
+// choice is the split kernel (a context the eight passes do not cover, or tune("attn_wave") 0) the step stays on it, over all keys: unbounded.  Where no keys
+// are split (more than 256 (head, row) pairs, or tune("attn_split") 1) attn_cross_bounded_rows_kernel runs instead of attn_gqa_kernel<128, false, KV> and writes
+// `out` itself; without klive / vsum that launch is what it always was.
 template <typename KV>
 static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const KV *kc, const KV *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
@@ -98,7 +100,18 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         nz = fixed_split ? c->attn_split_max : std::min(c->attn_split_max, std::max(1, max_keys / 128));
         while (nz > 1 && (size_t) rows * NHq * nz > c->attn_part_cap) nz--;
     }
+    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * sizeof(KV) < (1ull << 32);   // the wave kernels address a sequence's rows with 32-bit byte offsets
     if (nz <= 1) {
+        if constexpr (KVRow<KV>::EXT_SLOTS > 0) {
+            // Dia's cross-attention with the key on at more than 256 (head, row) pairs: the finished-row form of the bounded reader, any sentence length, `out` written
+            if (vsum && klive && row_seq && kend && !kbeg && !q_out && NKV == NHq && n_ctx_keys > 0 && off32 && qp.n_parts <= 8) {
+                if (!dia_cross_bounded_rows(c->stream, (int) sizeof(KV), qkv, ld, kc, vc, NHq, rows, scale, out, n_ctx_keys, kend, row_seq, seq_stride, klive, vsum, qp.n_parts,
+                                            qp.part_stride, qp.rope_pos, qp.theta_scale))
+                    return set_err("attn_cross_bounded_rows_kernel launch failed");
+                c->di_cross_bounded++;
+                return 0;
+            }
+        }
         hipLaunchKernelGGL((attn_gqa_kernel<128, false, KV>), dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
                            row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
         HIPCHK(hipGetLastError());
@@ -106,7 +119,6 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         return 0;
     }
     const int chunk = (max_keys + nz - 1) / nz;
-    const bool off32 = (uint64_t) std::max(n_ctx_keys, 1) * (uint64_t) NKV * 128 * sizeof(KV) < (1ull << 32);   // attn_gqa_wave_kernel addresses a sequence's rows with 32-bit byte offsets
     if (c->attn_wave && off32 && !kbeg && !kend && !row_seq && qp.n_parts == 1 && !qp.rope_pos && n_ctx_keys > 0) {
         // the captured one-row step (Orpheus): every key row requested at kernel start, online softmax per 16-lane group, one barrier (attn_gqa_wave_kernel)
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4, false, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
