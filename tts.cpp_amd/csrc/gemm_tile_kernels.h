@@ -247,7 +247,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_tile_kernel(GemmArgs a, Til
                         *(float4v *) (a.q + (int64_t) r * a.H + c) = v;
                     } else {
                         void *base = which == 1 ? a.kc : a.vc;
-                        if (a.kv_f16) {
+                        if (a.kv_f16 == KV_E4M3) {
+                            *(uint32_t *) ((uint8_t *) base + rowoff[mi] + c) = kv_f8_pack4(v);
+                        } else if (a.kv_f16) {
                             half4 h;
 #pragma unroll
                             for (int e = 0; e < 4; e++) h[e] = (_Float16) v[e];

@@ -216,18 +216,7 @@ static __global__ __launch_bounds__(256) void rms_fold_rows_q8t_kernel(float *x,
     }
 }
 
-// One-byte cache element: OCP e4m3fn (1 sign, 4 exponent, 3 mantissa bits, bias 7: largest finite 448, subnormals below 2^-6 in steps of 2^-9, no inf).
-// The writers convert with `(KV) y`, as they do for _Float16: clamped to +-448 here (what v_cvt_pk_fp8_f32 does above 448 depends on a mode bit the
-// kernels do not own), then rounded to nearest-even by the hardware conversion.  Readers widen exactly (KVRow<kv_f8>).
-struct kv_f8 {
-    uint8_t b;
-    kv_f8() = default;
-    explicit __device__ __forceinline__ kv_f8(float x) {
-        const float c = fminf(fmaxf(x, -448.0f), 448.0f);
-        b = (uint8_t) __builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false);
-    }
-};
-static_assert(sizeof(kv_f8) == 1, "a cache row of kv_f8 is one byte per element");
+// (the one-byte cache element kv_f8 — OCP e4m3fn, clamped to +-448 and rounded to nearest-even once as it is stored — is in wave_ops.h: Parler's cache shares it)
 
 // qkv [R][(NH + 2 NKV) * HD] (q | k | v).  One wave per (row, q or k head); lane = pair i (and i + 64, ... for HD > 128).
 // theta walks pos, pos*s, (pos*s)*s, ... in fp32 exactly like ggml_rope_cache_init (theta *= theta_scale), theta_scale =

@@ -84,6 +84,8 @@ enum { PRO_F32 = 0, PRO_LN = 1, PRO_F16 = 2, PRO_ATTN = 3,
 #define ATTN_FOLD_NZ 8    // slices a consumer's staging prologue merges (the default split count of the captured steps)
 // key-split partials of one (row, head): [nsplit][ATT_PS] floats = max, sum, pad, pad, acc[64] (acc 16-byte aligned)
 constexpr int ATT_PS = 68, ATT_PO = 4;
+// element codes of the self-attention K/V cache (GemmArgs::kv_f16, AttnArgs::kv_f16): fp32, fp16, or one-byte e4m3 (kv_f8, wave_ops.h; tts_hip_tune "kv_f8")
+enum { KV_F32 = 0, KV_F16 = 1, KV_E4M3 = 2 };
 enum { EPI_STORE = 0, EPI_QKV = 1, EPI_RESID = 2, EPI_GELU = 3,
        EPI_CROSS = 4 };   // gemm_tile_kernel<64, 64, ..> only: the tile is one head's cross-attention query for 64 rows; the attention runs in the epilogue
 
@@ -99,7 +101,7 @@ struct GemmArgs {
     // EPI_QKV: n in [0,H) -> q, [H,2H) -> K cache, [2H,3H) -> V cache
     float *q;           // [R][H]
     void *kc, *vc;      // this layer's cache base [seq][n_ctx][H]
-    int kv_f16;
+    int kv_f16;         // the cache's element code: KV_F32, KV_F16 or KV_E4M3 (0 and 1 are the flag this field was)
     int64_t seq_stride; // elements between sequences in the cache
     const uint32_t *row_seq, *row_pos;
     int H;
@@ -172,7 +174,9 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmArgs &a, int EPI, int r
         } else {
             const int64_t off = (int64_t) a.row_seq[r] * a.seq_stride + (int64_t) a.row_pos[r] * a.H + c;
             void *base = which == 1 ? a.kc : a.vc;
-            if (a.kv_f16) {
+            if (a.kv_f16 == KV_E4M3) {   // rounded once, as it is appended: one packed 4-byte store
+                *(uint32_t *) ((uint8_t *) base + off) = kv_f8_pack4(v);
+            } else if (a.kv_f16) {
                 half4 h;
 #pragma unroll
                 for (int e = 0; e < 4; e++) h[e] = (_Float16) v[e];
@@ -587,7 +591,8 @@ __global__ void gemv_valu_kernel(GemmArgs a, int EPI, int act_f16_src) {
                 else {
                     const int64_t off = (int64_t) a.row_seq[r] * a.seq_stride + (int64_t) a.row_pos[r] * a.H + c;
                     void *base = which == 1 ? a.kc : a.vc;
-                    if (a.kv_f16) ((_Float16 *) base)[off] = (_Float16) acc;
+                    if (a.kv_f16 == KV_E4M3) ((uint8_t *) base)[off] = kv_f8(acc).b;
+                    else if (a.kv_f16) ((_Float16 *) base)[off] = (_Float16) acc;
                     else ((float *) base)[off] = acc;
                 }
             }
@@ -741,7 +746,7 @@ static __global__ __launch_bounds__(256) void ln_rows_kernel(float *x, int H, co
 struct AttnArgs {
     const float *q;        // [R][H]
     const void *kc, *vc;   // [seq][n_ctx][H]  (or [E][H] for cross)
-    int kv_f16;
+    int kv_f16;            // element code of kc / vc: KV_F32, KV_F16 or KV_E4M3 (the cross K / V are always KV_F32)
     int64_t seq_stride;    // 0 for cross attention
     const uint32_t *row_seq, *row_pos;  // NULL for cross attention
     int T_fixed;           // cross: n_encode_length
@@ -770,16 +775,22 @@ __device__ __forceinline__ float4v load_kv4(const void *base, int kv_f16, int64_
     return *(const float4v *) ((const float *) base + off);
 }
 
-template <bool KVF16>
+// KVC = the cache's element code.  KV_E4M3: a lane's piece of a key is one 4-byte load per array, kept packed until its key is consumed (the eight rows
+// of a pass in 8 registers), widened there by two v_cvt_pk_f32_fp8: the fp32 arithmetic on the widened values, in the same order
+template <int KVC>
 __device__ __forceinline__ void attn_key_pass(const AttnArgs &a, int64_t hb, float4v q4, int tbeg, int t1, int step, int NKG, float &m, float &l, float4v &acc) {
     for (int t = tbeg; t < t1; t += step) {
         // the eight rows of a pass requested back to back (a key beyond the slice re-reads the slice's last key and is never used): under
         // `if (t + u * NKG < t1)` each pair of loads was a basic block behind its own s_waitcnt, four dependent round trips per pass
         float4v k4[4], v4[4];
+        uint32_t kp[4], vp[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int64_t off = hb + (int64_t) min(t + u * NKG, t1 - 1) * a.H;
-            if (KVF16) {
+            if (KVC == KV_E4M3) {
+                kp[u] = *(const uint32_t *) ((const uint8_t *) a.kc + off);
+                vp[u] = *(const uint32_t *) ((const uint8_t *) a.vc + off);
+            } else if (KVC == KV_F16) {
                 const half4 hk = *(const half4 *) ((const _Float16 *) a.kc + off), hv = *(const half4 *) ((const _Float16 *) a.vc + off);
                 k4[u] = (float4v){(float) hk[0], (float) hk[1], (float) hk[2], (float) hk[3]};
                 v4[u] = (float4v){(float) hv[0], (float) hv[1], (float) hv[2], (float) hv[3]};
@@ -791,6 +802,7 @@ __device__ __forceinline__ void attn_key_pass(const AttnArgs &a, int64_t hb, flo
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (t + u * NKG < t1) {
+                if (KVC == KV_E4M3) { k4[u] = kv_f8_widen4(kp[u]); v4[u] = kv_f8_widen4(vp[u]); }
                 float d = q4[0] * k4[u][0] + q4[1] * k4[u][1] + q4[2] * k4[u][2] + q4[3] * k4[u][3];
                 d = row16_sum(d);
                 d *= a.scale;  // soft_max_ext(kq, mask, 1/sqrt(d), 0)
@@ -833,8 +845,9 @@ static __global__ __launch_bounds__(1024) void attn_kernel(AttnArgs a) {   // U 
     float4v acc = {0.f, 0.f, 0.f, 0.f};
     // the cache type is a run-time flag of the context: one instance of the key pass per type, chosen once (a `flag ? half load : float load`
     // inside the pass made every load its own basic block behind a wait: 11 dependent load groups in the ISA of the dominant kernel)
-    if (a.kv_f16) attn_key_pass<true>(a, hb, q4, t0 + kg, t1, step, NKG, m, l, acc);
-    else attn_key_pass<false>(a, hb, q4, t0 + kg, t1, step, NKG, m, l, acc);
+    if (a.kv_f16 == KV_E4M3) attn_key_pass<KV_E4M3>(a, hb, q4, t0 + kg, t1, step, NKG, m, l, acc);
+    else if (a.kv_f16) attn_key_pass<KV_F16>(a, hb, q4, t0 + kg, t1, step, NKG, m, l, acc);
+    else attn_key_pass<KV_F32>(a, hb, q4, t0 + kg, t1, step, NKG, m, l, acc);
     if (a.stamps != nullptr) { asm volatile("" :: "v"(acc[0])); B1_STAMP(a.stamps, 1); }
     // merge the key groups
     if (cl == 0) red[NKG * 64 + kg] = m;

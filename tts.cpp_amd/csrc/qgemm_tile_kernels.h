@@ -371,7 +371,9 @@ __global__ __launch_bounds__(WM * WN * KG * 64) __attribute__((amdgpu_waves_per_
                         *(float4v *) (a.q + (int64_t) rr[mi] * a.H + c + 4 * q) = t;
                     } else {
                         void *cb = which == 1 ? a.kc : a.vc;
-                        if (a.kv_f16) {
+                        if (a.kv_f16 == KV_E4M3) {
+                            *(uint32_t *) ((uint8_t *) cb + rowoff[mi] + c + 4 * q) = kv_f8_pack4(t);
+                        } else if (a.kv_f16) {
                             half4 h;
 #pragma unroll
                             for (int e = 0; e < 4; e++) h[e] = (_Float16) t[e];

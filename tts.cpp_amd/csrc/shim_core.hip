@@ -182,6 +182,12 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
         if (v != 2 && v != 4 && v != 8) return set_err("tts_hip_tune: attn_rows_u is 2, 4 or 8 (got %d)", v);
         c->attn_rows_u = v;
     }
+    else if (k == "kv_f8") {   // Parler's self-attention K/V cache as one-byte e4m3 (kv_f8, wave_ops.h); the cache is sized by tts_hip_finalize
+        if (!c->has_parler) return set_err("tts_hip_tune: kv_f8 is the Parler decoder's key: this context has none (Orpheus: tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3; Dia has no fp8 cache)");
+        if (c->finalized) return set_err("tts_hip_tune: kv_f8 after tts_hip_finalize: the K/V cache has its element size already");
+        if (c->d.kv_type == TTS_HIP_F16) return set_err("tts_hip_tune: kv_f8 on a context whose kv_type is TTS_HIP_F16: one cache element type per context");
+        c->kv_f8 = v != 0;
+    }
     else if (k == "attn_fused") c->attn_fused = v != 0;
     else if (k == "attn_split") c->attn_split_max = std::max(1, std::min(16, v));
     else if (k == "orpheus_batch_run") c->l_batch_run = (uint32_t) std::max(1, std::min(1024, v));

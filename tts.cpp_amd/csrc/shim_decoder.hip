@@ -795,7 +795,8 @@ static int run_attn(tts_hip_ctx *c, int kclass, AttnArgs a, int R, int nsplit, d
         HIPCHK(hipGetLastError());
         return prof_end(c);
     }
-    if (nsplit == 1 && a.row_pos && a.row_seq && c->attn_rows_min > 0 && R >= c->attn_rows_min && c->NH * 16 <= 1024 && c->H == c->NH * 64) {
+    // (an e4m3 cache, tune("kv_f8"), has no row-major reader: every row count runs attn_kernel's e4m3 key pass below)
+    if (nsplit == 1 && a.row_pos && a.row_seq && c->attn_rows_min > 0 && R >= c->attn_rows_min && c->NH * 16 <= 1024 && c->H == c->NH * 64 && a.kv_f16 != KV_E4M3) {
         // many rows: one workgroup per row reads whole K / V rows (attn_rows_kernel); below 1024 rows the keys of a row are cut into FOUR slices
         // (about a thousand workgroups again) that attn_combine_kernel folds — a fixed count per row-count class, so that a generation whose rows
         // are compacted from 384 to 256 keeps its summation order
@@ -860,7 +861,7 @@ static int run_attn_voices(tts_hip_ctx *c, AttnArgs a, int R, int layer) {
 static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, bool same_seq) {
     const int H = c->H;
     const int64_t seq_stride = (int64_t) c->KVPOS * H;
-    const size_t kv_esz = c->d.kv_type == TTS_HIP_F16 ? 2 : 4;
+    const size_t kv_esz = c->kv_esz();
     const size_t layer_kv_bytes = (size_t) c->d.max_seqs * seq_stride * kv_esz;
     const bool voices = c->fwd_voices;
 
@@ -901,7 +902,7 @@ static int enqueue_forward(tts_hip_ctx *c, int R, bool audio, bool want_logits, 
         g.q = c->q;
         g.kc = (char *) c->kcache + (size_t) l * layer_kv_bytes;
         g.vc = (char *) c->vcache + (size_t) l * layer_kv_bytes;
-        g.kv_f16 = c->d.kv_type == TTS_HIP_F16;
+        g.kv_f16 = c->kv_f8 ? KV_E4M3 : c->d.kv_type == TTS_HIP_F16 ? KV_F16 : KV_F32;
         g.seq_stride = seq_stride; g.row_seq = c->d_seq; g.row_pos = c->d_pos;
         CHK(run_gemm(c, TTS_HIP_K_GEMM_QKV, y.qkv, g, PRO_LN, EPI_QKV));
 
@@ -1097,10 +1098,13 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         const int H = c->H;
         c->RMAX = std::max(max_rows_for(c), 1);
         if ((int) c->d.max_seqs > c->RMAX) return set_err("max_seqs=%u exceeds the %d rows one forward can carry with these weight types", c->d.max_seqs, c->RMAX);
-        const size_t kv_esz = c->d.kv_type == TTS_HIP_F16 ? 2 : 4;
-        const size_t kvb = (size_t) c->L * c->d.max_seqs * c->KVPOS * H * kv_esz;
-        HIPCHK(hipMalloc(&c->kcache, kvb));
-        HIPCHK(hipMalloc(&c->vcache, kvb));
+        const size_t kv_esz = c->kv_esz();
+        const size_t kvb = (size_t) c->L * c->d.max_seqs * c->KVPOS * H * kv_esz;   // [layer][seq][KVPOS][H] elements: fp32, fp16, or e4m3 bytes under tune("kv_f8")
+        if (hipMalloc(&c->kcache, kvb) != hipSuccess || hipMalloc(&c->vcache, kvb) != hipSuccess) {
+            (void) hipGetLastError();
+            return set_err("tts_hip_finalize: the %s K/V cache of %u slots does not fit: 2 x %zu bytes asked for (fewer slots or kv_positions)",
+                           c->kv_f8 ? "fp8 (e4m3)" : kv_esz == 2 ? "fp16" : "fp32", c->d.max_seqs, kvb);
+        }
         HIPCHK(hipMemset(c->kcache, 0, kvb));  // ggml_backend_buffer_clear(buf, 0), model.cpp:381
         HIPCHK(hipMemset(c->vcache, 0, kvb));
         const int R = c->RMAX;
@@ -2454,6 +2458,13 @@ __global__ void half_to_float_kernel(const _Float16 *in, float *out, size_t n) {
     if (i < n) out[i] = (float) in[i];
 }
 
+// one e4m3fn byte as the fp32 number it is (bias 7, 3 mantissa bits; subnormals m * 2^-9; no inf, one NaN code per sign)
+static float e4m3_to_float(uint8_t b) {
+    const int e = (b >> 3) & 15, m = b & 7;
+    const float mag = e == 15 && m == 7 ? NAN : e ? ldexpf((float) (8 + m), e - 10) : ldexpf((float) m, -9);
+    return (b & 128) ? -mag : mag;
+}
+
 extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *out, size_t max_floats) {
     if (!c || !what || !out || !c->finalized) { set_err("tts_hip_debug_read: bad argument"); return -1; }
     if (hipSetDevice(c->device) != hipSuccess) { set_err("hipSetDevice failed"); return -1; }
@@ -2501,11 +2512,7 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         if (c->l_kv_esz == 1) {   // the e4m3 cache: the bytes decoded on the host (exact: every finite e4m3 number is an fp32 number)
             std::vector<uint8_t> h(n);
             if (hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
-            for (size_t i = 0; i < n; i++) {
-                const int e = (h[i] >> 3) & 15, m = h[i] & 7;
-                const float mag = e == 15 && m == 7 ? NAN : e ? ldexpf((float) (8 + m), e - 10) : ldexpf((float) m, -9);   // bias 7, 3 mantissa bits; subnormals m * 2^-9
-                out[i] = (h[i] & 128) ? -mag : mag;
-            }
+            for (size_t i = 0; i < n; i++) out[i] = e4m3_to_float(h[i]);
             return (int64_t) n;
         }
         if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
@@ -2514,6 +2521,11 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
     if (w == "codec_packs") {   // pack launches of codec weight images since create (a layout key that changes value drops the images: the next pass packs again)
         if (max_floats < 1) { set_err("debug_read(codec_packs): buffer too small"); return -1; }
         out[0] = (float) c->codec_packs;
+        return 1;
+    }
+    if (c->has_parler && w == "kv_elem") {   // Parler's cache element size in bytes: 4, 2 under kv_type = TTS_HIP_F16, 1 under tune("kv_f8")
+        if (max_floats < 1) { set_err("debug_read(kv_elem): buffer too small"); return -1; }
+        out[0] = (float) c->kv_esz();
         return 1;
     }
     if (c->has_llama && w == "l_kv_elem") {   // the cache element size in bytes: 4, 2 under TTS_HIP_FLAG_KV_F16, 1 under TTS_HIP_KV_F8_E4M3
@@ -2647,11 +2659,15 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
             return -1;
         }
         const size_t n = std::min(max_floats / c->H, (size_t) c->KVPOS) * c->H;
-        const size_t kv_esz = c->d.kv_type == TTS_HIP_F16 ? 2 : 4;
+        const size_t kv_esz = c->kv_esz();
         const char *base = (const char *) (w[0] == 'k' ? c->kcache : c->vcache) +
                            ((size_t) layer * c->d.max_seqs + seq) * (size_t) c->KVPOS * c->H * kv_esz;
         if (kv_esz == 4) {
             if (hipMemcpy(out, base, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+        } else if (kv_esz == 1) {   // the e4m3 cache: the bytes decoded on the host (exact)
+            std::vector<uint8_t> h(n);
+            if (hipMemcpy(h.data(), base, n, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = e4m3_to_float(h[i]);
         } else {
             float *tmp = nullptr;
             if (hipMalloc((void **) &tmp, n * 4) != hipSuccess) { set_err("alloc failed"); return -1; }

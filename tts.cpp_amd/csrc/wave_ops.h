@@ -56,6 +56,33 @@ __device__ __forceinline__ float lanes32_max(float v) {
     return row16_max(v);
 }
 
+// One-byte cache element: OCP e4m3fn (1 sign, 4 exponent, 3 mantissa bits, bias 7: largest finite 448, subnormals below 2^-6 in steps of 2^-9, no inf).
+// The writers convert with `(KV) y`, as they do for _Float16: clamped to +-448 here (what v_cvt_pk_fp8_f32 does above 448 depends on a mode bit the
+// kernels do not own), then rounded to nearest-even by the hardware conversion.  Readers widen exactly (KVRow<kv_f8>, kv_f8_widen4).
+// Shared by the Llama decoder's cache (llama_kernels.h) and Parler's (parler_kernels.h: element code KV_E4M3).
+struct kv_f8 {
+    uint8_t b;
+    kv_f8() = default;
+    explicit __device__ __forceinline__ kv_f8(float x) {
+        const float c = fminf(fmaxf(x, -448.0f), 448.0f);
+        b = (uint8_t) __builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false);
+    }
+};
+static_assert(sizeof(kv_f8) == 1, "a cache row of kv_f8 is one byte per element");
+// four consecutive elements of a row as one word (element e in byte e): the same clamp and conversion, two v_cvt_pk_fp8_f32
+__device__ __forceinline__ uint32_t kv_f8_pack4(float4v v) {
+    float c[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) c[e] = fminf(fmaxf(v[e], -448.0f), 448.0f);
+    const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
+    return (uint32_t) __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
+}
+// and back, exactly (every finite e4m3 number is an fp32 number): two v_cvt_pk_f32_fp8, bytes 0-1 and bytes 2-3
+__device__ __forceinline__ float4v kv_f8_widen4(uint32_t w) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int) w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int) w, true);
+    return (float4v){lo[0], lo[1], hi[0], hi[1]};
+}
+
 // ggml_gelu.  mode 1 restates ggml's CPU path, which evaluates GELU through a table indexed by the
 // fp16 bits of x and holding fp16 results (upstream ggml_vec_gelu_f32 / GGML_GELU_FP16): a table is
 // memoisation, so rounding x to fp16, evaluating in fp32 and rounding the result to fp16 is the

@@ -86,6 +86,8 @@ parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok
     }
     // the fp8 cache is the Orpheus decoder's alone: a silent fp32 cache here would be worse than a failed load
     if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("parler: TTS_HIP_KV_F8 is set, and a Parler decoder has no fp8 K/V cache (TTS_HIP_KV_F16 selects its fp16 one)\n");
+    const char * want_f8 = getenv("TTS_HIP_PARLER_KV_F8");
+    if (want_f8 && atoi(want_f8) != 0 && getenv("TTS_HIP_KV_F16")) TTS_ABORT("parler: TTS_HIP_PARLER_KV_F8 and TTS_HIP_KV_F16 are both set: one K/V cache element type per runner\n");
     d.kv_type = getenv("TTS_HIP_KV_F16") ? TTS_HIP_F16 : TTS_HIP_F32;
     d.gelu_mode = 1;
     // one utterance: the reference layout (max_ctx_length positions, model.cpp:368-369); lock-step batches keep only
@@ -94,6 +96,12 @@ parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok
     dac_halo = tts_hip_dac_halo_frames(&d);
     ctx = tts_hip_create(device, &d);
     if (!ctx) TTS_ABORT("tts_hip_create failed: %s\n", tts_hip_last_error());
+    // read at load like the cache type: the self-attention K/V cache as one-byte e4m3 (extension, include/tts_hip.h: tts_hip_tune "kv_f8"), sized by finalize
+    if (want_f8 && atoi(want_f8) != 0 && tts_hip_tune(ctx, "kv_f8", 1) != 0) {
+        tts_hip_destroy(ctx);
+        ctx = nullptr;
+        TTS_ABORT("tts_hip_tune(kv_f8) failed: %s\n", tts_hip_last_error());
+    }
     smp.n_output_heads = hp.n_output_heads;
     smp.vocab_size = hp.output_vocab_size;
     smp.eos_token_id = hp.eos_token_id;
@@ -101,6 +109,11 @@ parler_runner::parler_runner(const parler_hparams & hp_, unigram_tokenizer * tok
 }
 
 parler_runner::~parler_runner() { tts_hip_destroy(ctx); }
+
+uint32_t parler_runner::kv_element_bytes() const {
+    float v = 0.0f;
+    return tts_hip_debug_read(ctx, "kv_elem", &v, 1) == 1 ? (uint32_t) v : 0;
+}
 
 void parler_runner::assign_weight(const char * name, const gguf_tensor_view & t) {
     // model.cpp:500-508 routes "audio_encoder." / "decoder." prefixes; the shim does the same by name

@@ -86,6 +86,7 @@ struct parler_runner final : stream_session {
     // on, not earlier: the chunker's rows are the slots.  on_chunk returning false drops that utterance only (tts_hip_parler_stream_drop),
     // reported with what it got.  last_batch_tokens[ticket] keeps an utterance's tokens for tickets below TOKEN_RECORD_TICKETS.
     void *   device_context() const override { return ctx; }
+    uint32_t kv_element_bytes() const override;   // 4, 2 when TTS_HIP_KV_F16 or 1 when TTS_HIP_PARLER_KV_F8=1 was in the environment at load
     // chunked audio (common.h): codec windows of the frames that became final are decoded while the next steps run
     void generate_chunked(const char * sentence, const generation_configuration & config, uint32_t chunk_frames,
                           const std::function<bool(const float *, size_t)> & on_chunk) override;

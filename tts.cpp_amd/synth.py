@@ -39,6 +39,7 @@ class Config:
     dac_f16: bool = False
     suppress_special: bool = True
     paddings: tuple = field(default=None)
+    kv_gain: float = 1.0      # factor on layer 0's self-attention k_proj / v_proj (1: the tensors as they always were, bit for bit); large values drive K and V past the e4m3 range (+-448)
 
     def __post_init__(self):
         if self.paddings is None:
@@ -298,7 +299,10 @@ class SynthModel:
             p = f"decoder.layers.{l}."
             for blk in ("self_attn", "encoder_attn"):
                 for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
-                    add(p + f"{blk}.{proj}.weight", normal((H, H)))
+                    w = normal((H, H))
+                    if cfg.kv_gain != 1.0 and l == 0 and blk == "self_attn" and proj in ("k_proj", "v_proj"):
+                        w = w * np.float32(cfg.kv_gain)
+                    add(p + f"{blk}.{proj}.weight", w)
                 add(p + f"{blk}_layer_norm.weight", normal((H,), mean=1.0))
                 add(p + f"{blk}_layer_norm.bias", normal((H,)))
             add(p + "fc1.weight", normal((F, H)))
