@@ -892,6 +892,15 @@ int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs
  *                       read unbounded until its next encoder pass.  tts_hip_debug_read: "di_cross_bounded" (bounded launches of the last forward),
  *                       "di_klive" (keys read per row slot), "di_cvsum:<layer>:<row slot>" (the sums).  The host runner sets it on the contexts it
  *                       opens when TTS_HIP_DIA_CROSS_BOUNDED=1 is in the environment at load
+ *   kv_f8               1, before tts_hip_finalize (which sizes the caches): the self and cross K/V caches in one-byte OCP e4m3fn instead of fp32 — a quarter of the
+ *                       bytes held (0.27 GB per slot at Dia-1.6B shapes against 1.06 GB) and read.  K and V are rounded once as they are stored (the encoder
+ *                       pass's cross rows, every step's self rows): clamped to +-448, nearest-even; all arithmetic stays fp32, readers widen exactly.  The
+ *                       cross-attention reads 16 bytes per lane and key (attn_cross_f8_kernel / attn_cross_f8_rows_kernel, with or without
+ *                       dia_cross_bounded) where four passes of 32 keys per slice cover max_ctx, the split / unsplit kernels over e4m3 elsewhere; the
+ *                       self-attention runs those.  Refused after finalize and on kv_type = TTS_HIP_F16 (tts_hip_dia_desc::kv_type itself takes F32 and
+ *                       F16 only).  tts_hip_debug_read("di_kv_elem") then reports 1, "di_k" / "di_v" / "di_ck" / "di_cv" widen exactly.  Results move
+ *                       with the rounding; default 0.  The host runner sets it when TTS_HIP_DIA_KV_F8=1 is in the environment at
+ *                       load (a load with TTS_HIP_KV_F16 as well fails).  The same key on a Parler context selects its e4m3 self-attention cache
  *   tile_force, tile_ks tile shape index (0..5, -1 = the cost model's) and K slices of the residual GEMMs (0 = the cost model's) of every
  *                       tiled GEMM: tests and tuning */
 int tts_hip_tune(tts_hip_ctx *ctx, const char *key, int value);

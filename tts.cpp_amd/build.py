@@ -16,10 +16,11 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-UNITS = ["shim_core", "shim_decoder", "shim_codec", "shim_llama", "shim_qtile", "shim_dia_rows", "shim_dia_cross"]
+UNITS = ["shim_core", "shim_decoder", "shim_codec", "shim_llama", "shim_qtile", "shim_dia_rows", "shim_dia_cross", "shim_dia_f8"]
 # per-unit code-generation switches (the reasons are in the unit's header comment)
 UNIT_FLAGS = {"shim_qtile": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-              "shim_dia_cross": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "shim_dia_cross": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "shim_dia_f8": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _deps(depfile, fallback):

@@ -16,15 +16,18 @@
 
 #define PADSUM_STRETCHES 4   // contiguous stretches of pad positions per workgroup, one per wave; part of the sum's order (tests restate it)
 
-// 16 bytes of a cache row per lane: 4 fp32 or 8 fp16 columns, non-temporal (up to 2 S A L elements per encoder pass, read once)
+// 16 bytes of a cache row per lane: 4 fp32 or 8 fp16 columns (16 e4m3 ones: dia_f8_kernels.h), non-temporal (up to 2 S A L elements per encoder pass, read
+// once); at(v, e): column e widened exactly
 template <typename KV> struct PadVec;
 template <> struct PadVec<float> {
     static constexpr int N = 4;
     typedef float4v vec;
+    static __device__ __forceinline__ float at(const vec &v, int e) { return v[e]; }
 };
 template <> struct PadVec<_Float16> {
     static constexpr int N = 8;
     typedef half8 vec;
+    static __device__ __forceinline__ float at(const vec &v, int e) { return (float) v[e]; }
 };
 
 // Vsum[layer][row][A] (fp32) = sum over j = n .. S - 1 of the cache's V row j widened exactly (an fp16 cache sums its rounded rows), for the two row slots
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(256) void dia_cross_padsum_kernel(const KV *vcache,
         for (int u = 0; u < NB; u++)
             if (j + u < j1) {
 #pragma unroll
-                for (int e = 0; e < N; e++) acc[e] += (float) v[u][e];
+                for (int e = 0; e < N; e++) acc[e] += PadVec<KV>::at(v[u], e);
             }
     }
     if (wave) {

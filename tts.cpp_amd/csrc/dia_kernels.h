@@ -202,7 +202,7 @@ static __global__ __launch_bounds__(256) void dia_stream_admit_kernel(DiaAdmitAr
     admit_sampler_state(a.rec_in, a.rec, a.pen_in, a.pen, a.pen_len, a.uni_in, a.uni, a.max_gen, a.n_slots, a.n_out, i, u, a.uni_in != nullptr);
 }
 
-// cross K/V [L][rows][S][A] of KV = float or _Float16 elements (tts_hip_dia_desc::kv_type): position 0 of rows 2u, 2u+1 of the flagged slots.
+// cross K/V [L][rows][S][A] of KV = float, _Float16 (tts_hip_dia_desc::kv_type) or kv_f8 (tune("kv_f8")) elements: position 0 of rows 2u, 2u+1 of the flagged slots.
 // grid (ceil(A / 256), 2 * n_slots, L)
 template <typename KV>
 __global__ __launch_bounds__(256) void dia_stream_clear_kernel(KV *ck, KV *cv, uint64_t clear, int rows, int64_t S, int A) {

@@ -403,7 +403,7 @@ template <> struct KVRow<_Float16> {
 // is in flight (a quarter of the fp32 form's registers) and widened by two v_cvt_pk_f32_fp8 (bytes 0-1, bytes 2-3; exact) where it is consumed.
 template <> struct KVRow<kv_f8> {
     typedef uint32_t vec4;
-    static constexpr int EXT_SLOTS = 0;   // no EXT form over this type (Dia has no fp8 cache): the host never names one
+    static constexpr int EXT_SLOTS = 0;   // no EXT form over this type: Dia's e4m3 cross-attention has a mapping of its own (dia_f8_kernels.h)
     static __device__ __forceinline__ vec4 load(const void *a) { return *(const uint32_t *) a; }
     static __device__ __forceinline__ vec4 load_nt(const void *a) { return __builtin_nontemporal_load((const uint32_t *) a); }
     static __device__ __forceinline__ float4 widen(vec4 w) {

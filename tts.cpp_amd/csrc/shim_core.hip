@@ -182,11 +182,12 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
         if (v != 2 && v != 4 && v != 8) return set_err("tts_hip_tune: attn_rows_u is 2, 4 or 8 (got %d)", v);
         c->attn_rows_u = v;
     }
-    else if (k == "kv_f8") {   // Parler's self-attention K/V cache as one-byte e4m3 (kv_f8, wave_ops.h); the cache is sized by tts_hip_finalize
-        if (!c->has_parler) return set_err("tts_hip_tune: kv_f8 is the Parler decoder's key: this context has none (Orpheus: tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3; Dia has no fp8 cache)");
+    else if (k == "kv_f8") {   // the K/V caches as one-byte e4m3 (kv_f8, wave_ops.h): Parler's self-attention cache, or a Dia context's self and cross caches; sized by tts_hip_finalize
+        if (!c->has_parler && !c->has_dia) return set_err("tts_hip_tune: kv_f8 is the Parler decoder's key and the Dia decoder's: this context has neither (Orpheus: tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3)");
         if (c->finalized) return set_err("tts_hip_tune: kv_f8 after tts_hip_finalize: the K/V cache has its element size already");
-        if (c->d.kv_type == TTS_HIP_F16) return set_err("tts_hip_tune: kv_f8 on a context whose kv_type is TTS_HIP_F16: one cache element type per context");
-        c->kv_f8 = v != 0;
+        if ((c->has_dia ? c->dia.kv_type : c->d.kv_type) == TTS_HIP_F16) return set_err("tts_hip_tune: kv_f8 on a context whose kv_type is TTS_HIP_F16: one cache element type per context");
+        if (c->has_dia) c->di_kv_esz = v != 0 ? 1 : 4;   // (readers: attn_cross_f8_kernel, dia_f8_kernels.h, and attn_gqa_kernel<128, *, kv_f8>)
+        else c->kv_f8 = v != 0;
     }
     else if (k == "attn_fused") c->attn_fused = v != 0;
     else if (k == "attn_split") c->attn_split_max = std::max(1, std::min(16, v));
@@ -295,7 +296,7 @@ extern "C" void tts_hip_destroy(tts_hip_ctx *c) {
     for (float *p : {c->di_ex, c->di_exn, c->di_eqkv, c->di_eatt, c->di_egu, c->di_eg, c->di_ek, c->di_ev, c->di_ckv, c->di_x,
                      c->di_xn, c->di_qkv, c->di_q, c->di_att, c->di_gu, c->di_g, c->di_parts, c->di_logits, c->di_guided})
         free_dev(p);
-    free_dev(c->di_ck); free_dev(c->di_cv); free_dev(c->di_k); free_dev(c->di_v);   // fp32 or fp16 (di_kv_esz)
+    free_dev(c->di_ck); free_dev(c->di_cv); free_dev(c->di_k); free_dev(c->di_v);   // fp32, fp16 or e4m3 (di_kv_esz)
     free_dev(c->di_h16);
     free_dev(c->di_cvsum); free_dev(c->di_klive);
     for (uint32_t *p : {c->di_tok, c->di_epos, c->di_eseq, c->di_kbeg, c->di_kend, c->di_ids, c->di_pos, c->di_seq, c->di_cend, c->di_stok, c->di_loop, c->di_hist, c->di_look, c->di_sbud, c->di_sadm}) free_dev(p);

@@ -1227,13 +1227,13 @@ extern "C" int tts_hip_finalize(tts_hip_ctx *c, void *external_arena) {
         c->di_slot_encoded.assign((size_t) U, 0);
         c->attn_part_cap = (size_t) R * c->NH * 16;
         CHK(dmalloc(&c->attn_part, c->attn_part_cap * ATTN_PART));
-        const size_t kve = (size_t) c->di_kv_esz;   // bytes per cache element: half of them under tts_hip_dia_desc::kv_type = TTS_HIP_F16
+        const size_t kve = (size_t) c->di_kv_esz;   // bytes per cache element: 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16, 1 (e4m3) under tune("kv_f8")
         const size_t crossb = (size_t) c->L * U * n * A * kve, selfb = (size_t) c->L * R * G * kvH * kve;
         if (dmalloc((char **) &c->di_ck, crossb) || dmalloc((char **) &c->di_cv, crossb) ||   // [L][2U][S][A], zero like the reference's cleared cache (dia/model.cpp:329)
             dmalloc((char **) &c->di_k, selfb) || dmalloc((char **) &c->di_v, selfb)) {       // [L][2U][G][kvH]
             (void) hipGetLastError();
-            return set_err("tts_hip_finalize: the K/V caches of %d utterance slots do not fit: 2 x %zu (cross) + 2 x %zu (self) bytes asked for (%s; fewer slots, or TTS_HIP_KV_F16 halves it)", U,
-                           crossb, selfb, kve == 2 ? "fp16 caches" : "fp32 caches");
+            return set_err("tts_hip_finalize: the K/V caches of %d utterance slots do not fit: 2 x %zu (cross) + 2 x %zu (self) bytes asked for (%s; fewer slots, or a smaller element: TTS_HIP_KV_F16, or tune kv_f8 / TTS_HIP_DIA_KV_F8)", U,
+                           crossb, selfb, kve == 1 ? "fp8 (e4m3) caches" : kve == 2 ? "fp16 caches" : "fp32 caches");
         }
         CHK(dmalloc(&c->di_x, (size_t) R * DH)); CHK(dmalloc(&c->di_xn, (size_t) R * DH));
         // the projections of a step with <= 16 rows may arrive as up to DIA_STREAM_SLABS K-slice slabs of 16 rows (gemv_stream_kernels.h)
@@ -2568,7 +2568,7 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
         memcpy(out, v->data(), v->size() * 4);
         return (int64_t) v->size();
     }
-    if (c->has_dia && w == "di_kv_elem") {   // the element size of the four caches in bytes: 4, or 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16
+    if (c->has_dia && w == "di_kv_elem") {   // the element size of the four caches in bytes: 4, 2 under tts_hip_dia_desc::kv_type = TTS_HIP_F16, or 1 under tune("kv_f8")
         if (max_floats < 1) { set_err("debug_read(di_kv_elem): buffer too small"); return -1; }
         out[0] = (float) c->di_kv_esz;
         return 1;
@@ -2614,6 +2614,12 @@ extern "C" int64_t tts_hip_debug_read(tts_hip_ctx *c, const char *what, float *o
             std::vector<_Float16> h(n);
             if (hipMemcpy(h.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
             for (size_t i = 0; i < n; i++) out[i] = (float) h[i];
+            return (int64_t) n;
+        }
+        if (c->di_kv_esz == 1) {   // the e4m3 caches: the bytes decoded on the host (exact)
+            std::vector<uint8_t> h(n);
+            if (hipMemcpy(h.data(), src, n, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }
+            for (size_t i = 0; i < n; i++) out[i] = e4m3_to_float(h[i]);
             return (int64_t) n;
         }
         if (hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("copy failed"); return -1; }

@@ -9,6 +9,7 @@
 #include "shim_decoder.h"
 #include "shim_dia_rows.h"
 #include "shim_dia_cross.h"
+#include "shim_dia_f8.h"
 
 // Orpheus decoder (src/models/orpheus/model.cpp:186-325)
 // ------------------------------------------------------------------------------------------------
@@ -66,10 +67,10 @@ template <typename F>
 static int with_kv(int kv_esz, void *kc, void *vc, F &&f) {
     return kv_esz == 2 ? f((_Float16 *) kc, (_Float16 *) vc) : f((float *) kc, (float *) vc);
 }
-// The Llama forward's dispatch: the same, plus 1: e4m3 (tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3).  Dia's call sites stay on with_kv: no Dia writer
-// and no EXT reader is built for kv_f8.
+// The decoders' dispatch: the same, plus 1: one-byte e4m3 (kv_f8; Orpheus: tts_hip_orpheus_desc::kv_type = TTS_HIP_KV_F8_E4M3, Dia: tts_hip_tune "kv_f8").  The
+// encoder's own K/V scratch is fp32 and never comes here.
 template <typename F>
-static int with_kv_llama(int kv_esz, void *kc, void *vc, F &&f) {
+static int with_kv_any(int kv_esz, void *kc, void *vc, F &&f) {
     return kv_esz == 1 ? f((kv_f8 *) kc, (kv_f8 *) vc) : with_kv(kv_esz, kc, vc, f);
 }
 
@@ -89,6 +90,10 @@ static int attn_gqa_allow_lds(tts_hip_ctx *c, size_t lds) {
 // choice is the split kernel (a context the eight passes do not cover, or tune("attn_wave") 0) the step stays on it, over all keys: unbounded.  Where no keys
 // are split (more than 256 (head, row) pairs, or tune("attn_split") 1) attn_cross_bounded_rows_kernel runs instead of attn_gqa_kernel<128, false, KV> and writes
 // `out` itself; without klive / vsum that launch is what it always was.
+// A kv_f8 cache (Dia's, tune("kv_f8")) makes the same choices among the instantiations of attn_cross_f8_body (shim_dia_f8.hip; four passes of 32 keys per slice:
+// max_keys <= 32 nz 4): attn_cross_f8_kernel<bounded> where the others take the EXT form or its bounded sibling, attn_cross_f8_rows_kernel<bounded> where no
+// keys are split (the unbounded one in place of attn_gqa_kernel<128, false, kv_f8>, under tune("attn_wave") like the slice form), and attn_gqa_kernel<128, true /
+// false, kv_f8> wherever the others fall back to theirs.  Only Dia's cross launch passes kend and row_seq without kbeg: Orpheus' kv_f8 launches are untouched.
 template <typename KV>
 static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, const float *qkv, int ld, const uint32_t *pos, const KV *kc, const KV *vc, int NKV,
                            float scale, float *out, const uint32_t *kbeg, const uint32_t *kend, const uint32_t *row_seq, int64_t seq_stride, bool fixed_split, bool q_out = false,
@@ -112,6 +117,16 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
                 return 0;
             }
         }
+        if constexpr (std::is_same_v<KV, kv_f8>) {
+            const bool bounded = vsum && klive;
+            if (row_seq && kend && !kbeg && !q_out && NKV == NHq && n_ctx_keys > 0 && off32 && qp.n_parts <= 8 && (bounded || c->attn_wave)) {
+                if (!dia_f8_cross(c->stream, qkv, ld, kc, vc, NHq, rows, 0, scale, out, n_ctx_keys, kend, row_seq, seq_stride, klive, vsum, qp.n_parts, qp.part_stride, qp.rope_pos,
+                                  qp.theta_scale))
+                    return set_err("attn_cross_f8_rows_kernel launch failed");
+                if (bounded) c->di_cross_bounded++;
+                return 0;
+            }
+        }
         hipLaunchKernelGGL((attn_gqa_kernel<128, false, KV>), dim3(NHq, rows), dim3(256), (size_t) (128 + max_keys) * 4, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, out, kbeg, kend,
                            row_seq, seq_stride, qp, q_out ? c->aq : (int8_t *) nullptr, q_out ? c->ad : (float *) nullptr);
         HIPCHK(hipGetLastError());
@@ -124,7 +139,17 @@ static int launch_attn_gqa(tts_hip_ctx *c, int NHq, int rows, int max_keys, cons
         hipLaunchKernelGGL((attn_gqa_wave_kernel<128, 4, false, KV>), dim3(NHq, rows, nz), dim3(256), 0, c->stream, qkv, ld, pos, kc, vc, NHq, NKV, scale, c->attn_part, n_ctx_keys);
     } else {
         bool ext = false;
-        if constexpr (KVRow<KV>::EXT_SLOTS > 0) {   // (kv_f8, the Llama decoder's alone, has no EXT form: nothing of it is built)
+        if constexpr (std::is_same_v<KV, kv_f8>) {   // Dia's cross-attention over e4m3: 16 bytes per lane and key, four passes of 32 keys per slice, all in flight
+            ext = c->attn_wave && off32 && !kbeg && kend && row_seq && NKV == NHq && n_ctx_keys > 0 && max_keys <= 32 * nz * 4 && n_ctx_keys <= 32 * nz * 4 && qp.n_parts <= 8;
+            if (ext) {
+                const bool bounded = vsum && klive;
+                if (!dia_f8_cross(c->stream, qkv, ld, kc, vc, NHq, rows, nz, scale, c->attn_part, n_ctx_keys, kend, row_seq, seq_stride, klive, vsum, qp.n_parts, qp.part_stride,
+                                  qp.rope_pos, qp.theta_scale))
+                    return set_err("attn_cross_f8_kernel launch failed");
+                if (bounded) c->di_cross_bounded++;
+            }
+        }
+        if constexpr (KVRow<KV>::EXT_SLOTS > 0) {   // (kv_f8 has no EXT form of this mapping: nothing of it is built)
             ext = c->attn_wave && off32 && !kbeg && kend && n_ctx_keys > 0 && max_keys <= 16 * nz * 8 && qp.n_parts <= 8;
             // Dia's cross-attention (keys end at kend[r], per-row sequences, the query as slabs to fold and rotate): the same form, 8 passes through KVRow<KV>::EXT_SLOTS
             // rolling register slots (the parked rows of a loop step, kend[r] = 1, request that one key only)
@@ -264,14 +289,14 @@ static int llama_forward(tts_hip_ctx *c, const uint32_t *ids, int n, uint32_t po
     };
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->l_layers[l];
-        // this layer of slot 0: fp32 rows, fp16 rows under TTS_HIP_FLAG_KV_F16 or e4m3 bytes under kv_type = TTS_HIP_KV_F8_E4M3 (with_kv_llama: the cache's writer and
+        // this layer of slot 0: fp32 rows, fp16 rows under TTS_HIP_FLAG_KV_F16 or e4m3 bytes under kv_type = TTS_HIP_KV_F8_E4M3 (with_kv_any: the cache's writer and
         // readers below are launched for that type)
         const size_t layer_off = (size_t) l * NCTX * c->l_kvH * (size_t) c->l_kv_esz;
         const size_t qkv_lds = (size_t) n * H + (size_t) n * (H / 32) * 4;
         const bool qkv_fused = !row_seq && n <= 4 && c->q4_rope && c->q4_lds && y.qkv.q4 && q_for(y.qkv, n, QS_QKV) && HD == 128 && H % 512 == 0 && qkv_lds <= 64 * 1024 && !c->prof;
         // the rms norm inside the consuming projection's staging (stage_rms_q8): no slabs may be pending, the row is held in registers
         const bool rms_fused = c->q4_rms && !c->l_pending && H <= 4096;
-        CHK(with_kv_llama(c->l_kv_esz, (char *) c->l_kc + layer_off, (char *) c->l_vc + layer_off, [&](auto *kc, auto *vc) -> int {
+        CHK(with_kv_any(c->l_kv_esz, (char *) c->l_kc + layer_off, (char *) c->l_vc + layer_off, [&](auto *kc, auto *vc) -> int {
             typedef kv_of<decltype(kc)> KV;
             const RopeEpi<KV> re{(const uint32_t *) c->l_pos, f32(c->l_ropef), theta_scale, NH, NKV, kc, vc};
             if (qkv_fused && rms_fused) {
@@ -1431,7 +1456,7 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
         const size_t esz = (size_t) c->di_kv_esz, slot_off = ((size_t) l * c->di_U + slot) * n * A * esz;   // rows 2*slot, 2*slot+1
         char *ck = (char *) c->di_ck + slot_off, *cv = (char *) c->di_cv + slot_off;
         CHK(dia_gemm_rows(c, y.ckv, c->di_exn, EH, c->di_ckv, 2 * A, n, EPI_STORE));
-        CHK(with_kv(c->di_kv_esz, ck, cv, [&](auto *k, auto *v) -> int {   // an fp16 cache: the same rotation, K and V rounded once as they are stored
+        CHK(with_kv_any(c->di_kv_esz, ck, cv, [&](auto *k, auto *v) -> int {   // an fp16 / e4m3 cache: the same rotation, K and V rounded once as they are stored
             hipLaunchKernelGGL(llama_rope_kv_kernel<kv_of<decltype(k)>>, dim3(n, NH), dim3(64), 0, c->stream, c->di_ckv, (const uint32_t *) c->di_epos,
                                (const float *) nullptr, theta_scale, 0, NH, HD, k, v, (const uint32_t *) c->di_eseq, (int64_t) S * A);
             HIPCHK(hipGetLastError());
@@ -1445,7 +1470,8 @@ static int dia_encode_into(tts_hip_ctx *c, uint32_t slot, const uint32_t *tokens
     // leave a stale length behind): the sum of the slot's V rows behind the sentence in every layer, and the sentence length (dia_cross_padsum_kernel)
     if (c->di_cvsum) {
         CHK(prof_begin(c, TTS_HIP_K_GEMM_OTHER, (double) c->L * 2 * (S - (int) sentence_len) * A * (double) c->di_kv_esz, 0));
-        const bool launched = dia_cross_padsum(c->stream, c->di_kv_esz, c->di_cv, c->L, 2 * c->di_U, S, A, (int) slot, (int) sentence_len, c->di_cvsum, c->di_klive);
+        const bool launched = c->di_kv_esz == 1 ? dia_f8_padsum(c->stream, c->di_cv, c->L, 2 * c->di_U, S, A, (int) slot, (int) sentence_len, c->di_cvsum, c->di_klive)
+                                                : dia_cross_padsum(c->stream, c->di_kv_esz, c->di_cv, c->L, 2 * c->di_U, S, A, (int) slot, (int) sentence_len, c->di_cvsum, c->di_klive);
         CHK(prof_end(c));
         if (!launched) return set_err("dia_cross_padsum_kernel launch failed");
         c->di_klive_host[slot] = sentence_len;
@@ -1554,7 +1580,7 @@ static int dia_forward_tiled(tts_hip_ctx *c, int U, int self_keys, bool fixed_sp
         char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off, *ck = (char *) c->di_ck + cross_off, *cv = (char *) c->di_cv + cross_off;
         CHK(dia_rms_f16(c, y.sa_norm, R, DH));
         CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_QKV, y.sqkv, c->di_qkv, QKV, R, false));
-        CHK(with_kv(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {
+        CHK(with_kv_any(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {
             typedef kv_of<decltype(k)> KV;
             CHK(prof_begin(c, TTS_HIP_K_LN, (double) R * QKV * 8, 0));
             hipLaunchKernelGGL(llama_rope_kv_kernel<KV>, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
@@ -1573,7 +1599,7 @@ static int dia_forward_tiled(tts_hip_ctx *c, int U, int self_keys, bool fixed_sp
         CHK(dia_gemm_tile(c, TTS_HIP_K_GEMM_CROSS_Q, y.cq, c->di_q, A, R, false));
         QPre qp;   // one part; the rope of the cross-attention query happens as the attention workgroups load it
         qp.n_parts = 1; qp.part_stride = 0; qp.rope_pos = c->di_pos; qp.theta_scale = theta_scale;
-        CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
+        CHK(with_kv_any(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
             CHK(prof_begin(c, TTS_HIP_K_ATTN_CROSS, dia_cross_vsum(c, l) ? (double) R * (dia_cross_mean_keys(c) * 2 * A * kvb + A * 4.0) : (double) R * S * 2 * A * kvb, 0));
             CHK(launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
                                                     (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp, nullptr, S, c->di_klive,
@@ -1607,7 +1633,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     auto f32 = [&](size_t off) { return (const float *) (c->arena + off); };
     const float theta_scale = powf(10000.0f, -2.0f / (float) HD);
     const size_t attn_lds = (size_t) (128 + std::max(S, G)) * 4;
-    CHK(kv_esz == 2 ? attn_gqa_allow_lds<_Float16>(c, attn_lds) : attn_gqa_allow_lds<float>(c, attn_lds));
+    CHK(kv_esz == 1 ? attn_gqa_allow_lds<kv_f8>(c, attn_lds) : kv_esz == 2 ? attn_gqa_allow_lds<_Float16>(c, attn_lds) : attn_gqa_allow_lds<float>(c, attn_lds));
     DiaEmbedArgs ea{};
     for (int i = 0; i < NO; i++) ea.table[i] = f32(c->di_embd[i]);
     ea.ids = c->di_ids; ea.n_out = NO; ea.H = DH; ea.x = c->di_x;
@@ -1627,7 +1653,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
     for (int l = 0; l < c->L; l++) {
         const auto &y = c->di_dec[(size_t) l];
         const size_t self_off = (size_t) l * RS * G * kvH * (size_t) kv_esz, cross_off = (size_t) l * RS * S * A * (size_t) kv_esz;
-        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off, *ck = (char *) c->di_ck + cross_off, *cv = (char *) c->di_cv + cross_off;   // fp32 or fp16 rows (with_kv)
+        char *kc = (char *) c->di_k + self_off, *vc = (char *) c->di_v + self_off, *ck = (char *) c->di_ck + cross_off, *cv = (char *) c->di_cv + cross_off;   // fp32, fp16 or e4m3 rows (with_kv_any)
         // every projection: gemv_stream_kernel slabs folded by its consumer when the step has <= 16 rows and fp16 matrices
         // (sl = slabs written, 0 = shape does not qualify -> gemm16_kernel as before)
         int sl = 0;
@@ -1636,7 +1662,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         CHK(dia_gemm_stream(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, DIA_STREAM_SLABS, st16 * QKV, &sl));
         if (!sl) CHK(dia_gemm(c, y.sqkv, c->di_xn, DH, c->di_qkv, QKV, R, EPI_STORE));
         int slices = 0;   // key slices the attention left unmerged for the projection's staging prologue (0: di_att holds the rows)
-        CHK(with_kv(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {   // an fp16 cache: the same slab fold and rotation, K and V rounded once as they are appended
+        CHK(with_kv_any(kv_esz, kc, vc, [&](auto *k, auto *v) -> int {   // an fp16 / e4m3 cache: the same slab fold and rotation, K and V rounded once as they are appended
             typedef kv_of<decltype(k)> KV;
             hipLaunchKernelGGL(llama_rope_kv_kernel<KV>, dim3(R, NH + NKV), dim3(64), 0, c->stream, c->di_qkv, (const uint32_t *) c->di_pos, (const float *) nullptr, theta_scale, NH,
                                NKV, HD, k, v, (const uint32_t *) c->di_seq, (int64_t) G * kvH, std::max(sl, 1), st16 * QKV);
@@ -1655,7 +1681,7 @@ static int dia_forward(tts_hip_ctx *c, int U, int self_keys, bool fixed_split, b
         QPre qp;   // slab fold + rope of the cross-attention query happen as the attention workgroups load it
         qp.n_parts = std::max(sl, 1); qp.part_stride = st16 * A; qp.rope_pos = c->di_pos; qp.theta_scale = theta_scale;
         slices = 0;
-        CHK(with_kv(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
+        CHK(with_kv_any(kv_esz, ck, cv, [&](auto *k, auto *v) -> int {
             return launch_attn_gqa<kv_of<decltype(k)>>(c, NH, R, S, (const float *) c->di_q, A, (const uint32_t *) c->di_pos, k, v, NH, 1.0f, c->di_att, nul,
                                                                        (const uint32_t *) c->di_cend, (const uint32_t *) c->di_seq, (int64_t) S * A, false, false, qp,
                                                                        A % 128 == 0 && stream_fold_ok(c, y.co, R, DIA_STREAM_SLABS) ? &slices : nullptr, S, c->di_klive,
@@ -1876,7 +1902,7 @@ static int dia_loop_begin(tts_hip_ctx *c, DL::Mode mode, uint32_t n, uint32_t ma
             uint64_t clear = 0;
             for (int u = 0; u < m; u++) if (!c->di_slot_encoded[(size_t) (u0 + u)]) clear |= 1ull << u;
             if (!clear) continue;
-            CHK(with_kv(c->di_kv_esz, c->di_ck, c->di_cv, [&](auto *ck, auto *cv) -> int {
+            CHK(with_kv_any(c->di_kv_esz, c->di_ck, c->di_cv, [&](auto *ck, auto *cv) -> int {
                 const size_t first = (size_t) 2 * u0 * S * c->di_A;
                 hipLaunchKernelGGL(dia_stream_clear_kernel<kv_of<decltype(ck)>>, dim3((c->di_A + 255) / 256, 2 * m, c->L), dim3(256), 0, c->stream, ck + first, cv + first, clear, 2 * DU,
                                    (int64_t) S, c->di_A);

@@ -1087,7 +1087,8 @@ class DiaEngine:
     def __init__(self, cfg, device=0, flags=0, cfg_scale=0.0, max_utterances=1, kv_type=gguf.F32, tune=None):
         """tune: {key: value} for tts_hip_tune, set before load ('dia_cross_bounded': 1 = cross-attention over the sentence's keys plus the V sum of the pad
         rows instead of all max_ctx keys, at every step size: attn_cross_bounded_kernel where keys are split over workgroups, attn_cross_bounded_rows_kernel where not;
-        0 on every context by default).
+        0 on every context by default; 'kv_f8': 1 = the self and cross K/V caches in one-byte e4m3, rounded once as they are stored and read 16 bytes per lane
+        by attn_cross_f8_kernel, fp32 kv_type only, before load: the caches are sized there).
         kv_type: gguf.F32 (the reference's caches) or gguf.F16 (tts_hip_dia_desc::kv_type: the self and cross K/V caches in fp16, rounded once as they are stored).
         max_utterances: at most 128 (256 guidance rows per forward); above 64 the steps of more than 16 rows run fp16 matrices on the tiled MFMA GEMM
         (tune("dia_tile_min_rows"): 17 there, 0 = never on contexts of at most 64 slots)"""
@@ -1135,7 +1136,7 @@ class DiaEngine:
     def debug_read(self, what, max_floats):
         """'di_attn:<layer>:<self|cross>:<q|out|meta>' (set_debug before the step; meta = n_parts, part_stride, ld, rows, then pos / kend / row slot per
         row), 'di_k|di_v:<layer>:<row slot>' [max_gen][kv width], 'di_ck|di_cv:<layer>:<row slot>' [max_ctx][heads * 128] (fp16 caches widened exactly), 'di_kv_elem': the
-        cache element size in bytes (4, or 2 with kv_type=gguf.F16), 'di_tiled': gemm_tile_kernel launches of the last decoder forward (0 on the streaming and
+        cache element size in bytes (4, 2 with kv_type=gguf.F16, 1 with tune('kv_f8'); e4m3 rows are widened exactly too), 'di_tiled': gemm_tile_kernel launches of the last decoder forward (0 on the streaming and
         16-feature routes), 'di_pending_max': the most K-slice slabs one GEMM of it left for the next rms norm, 'di_cross_bounded': bounded reader launches of it, either form (0 with
         tune('dia_cross_bounded') off); with that key set once: 'di_klive' [2 * slots] the keys the bounded reader reads per row slot, 'di_cvsum:<layer>:<row slot>'
         [heads * 128] the fp32 sum of the cache's V rows behind them (test / debugging aid)"""

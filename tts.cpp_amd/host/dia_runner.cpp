@@ -74,11 +74,20 @@ dia_runner::dia_runner(const dia_hparams & hp_, int device) : stream_session{dia
     max_seqs = std::min<uint32_t>(asked, 128);   // two guidance rows per utterance, 256 rows per decoder forward (tts_hip_dia_create)
     if (max_seqs != asked) fprintf(stderr, "dia: max_seqs %u exceeds what one decoder forward carries: loading with %u slots\n", asked, max_seqs);
     d.max_utterances = max_seqs;
-    // the fp8 cache is the Orpheus decoder's alone: a silent fp32 cache here would be worse than a failed load
-    if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("dia: TTS_HIP_KV_F8 is set, and a Dia decoder has no fp8 K/V caches (TTS_HIP_KV_F16 selects its fp16 ones)\n");
+    // TTS_HIP_KV_F8 is the Orpheus decoder's switch: a silent fp32 cache here would be worse than a failed load
+    if (getenv("TTS_HIP_KV_F8")) TTS_ABORT("dia: TTS_HIP_KV_F8 is set, and that is the Orpheus decoder's switch (TTS_HIP_DIA_KV_F8=1 selects Dia's e4m3 K/V caches, TTS_HIP_KV_F16 its fp16 ones)\n");
+    const char * want_f8 = getenv("TTS_HIP_DIA_KV_F8");
+    const bool f8 = want_f8 && atoi(want_f8) != 0;
+    if (f8 && getenv("TTS_HIP_KV_F16")) TTS_ABORT("dia: TTS_HIP_DIA_KV_F8 and TTS_HIP_KV_F16 are both set: one K/V cache element type per runner\n");
     if (getenv("TTS_HIP_KV_F16")) d.kv_type = TTS_HIP_F16;   // the switch the Parler and Orpheus runners read: fp16 self and cross K/V caches (extension, include/tts_hip.h)
     lm = tts_hip_dia_create(device, &d);
     if (!lm) TTS_ABORT("tts_hip_dia_create failed: %s\n", tts_hip_last_error());
+    // read at load like the cache type: the self and cross K/V caches as one-byte e4m3 (extension, include/tts_hip.h: tts_hip_tune "kv_f8"), sized by finalize
+    if (f8 && tts_hip_tune(lm, "kv_f8", 1) != 0) {
+        tts_hip_destroy(lm);
+        lm = nullptr;
+        TTS_ABORT("tts_hip_tune(kv_f8) failed: %s\n", tts_hip_last_error());
+    }
     // read at load like the cache type: cross-attention over the sentence's keys plus the pad rows' V sum instead of all max_ctx keys (extension, include/tts_hip.h)
     if (const char * e = getenv("TTS_HIP_DIA_CROSS_BOUNDED"))
         if (atoi(e) != 0 && tts_hip_tune(lm, "dia_cross_bounded", 1) != 0) {

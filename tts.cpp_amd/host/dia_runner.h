@@ -91,7 +91,7 @@ struct dia_runner final : stream_session {
     // itself is stream_session's; this runner's part always says yes: with an unknown halo its chunker hands whole utterances out through the hook.
     bool     session_chunks_ready(uint32_t chunk_frames) override;
     uint32_t batch_capacity() const override { return max_seqs; }
-    uint32_t kv_element_bytes() const override;   // 4, or 2 when TTS_HIP_KV_F16 was in the environment at load (tts_hip_dia_desc::kv_type)
+    uint32_t kv_element_bytes() const override;   // 4, 2 when TTS_HIP_KV_F16 or 1 when TTS_HIP_DIA_KV_F8=1 was in the environment at load
     int32_t  cross_bounded_launches() const override;   // of the last decoder forward; 0 unless TTS_HIP_DIA_CROSS_BOUNDED=1 was in the environment at load (tune("dia_cross_bounded"))
     uint32_t max_seqs = 1;   // utterance slots of the decoder context (tts_load_options::max_seqs, at most 128: two guidance rows each, 256 rows per forward)
 
