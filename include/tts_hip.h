@@ -901,6 +901,10 @@ int tts_hip_parler_seq_voices(tts_hip_ctx *ctx, uint32_t n, const uint32_t *seqs
  *                       F16 only).  tts_hip_debug_read("di_kv_elem") then reports 1, "di_k" / "di_v" / "di_ck" / "di_cv" widen exactly.  Results move
  *                       with the rounding; default 0.  The host runner sets it when TTS_HIP_DIA_KV_F8=1 is in the environment at
  *                       load (a load with TTS_HIP_KV_F16 as well fails).  The same key on a Parler context selects its e4m3 self-attention cache
+ *   attn_rows_f8_min    Parler, e4m3 cache (kv_f8): forwards of at least max(attn_rows_min, this) rows read the cache through the row-major reader
+ *                       attn_rows_f8_kernel (16 channels per lane, one workgroup of 256 threads per row; hidden = 64 heads, at most 1024, hidden / 16 a
+ *                       power of two), fewer rows and other shapes through attn_kernel.  Default 256; 0: attn_kernel at every row count.  Read when a
+ *                       forward is issued: set it before the first captured loop of the context
  *   tile_force, tile_ks tile shape index (0..5, -1 = the cost model's) and K slices of the residual GEMMs (0 = the cost model's) of every
  *                       tiled GEMM: tests and tuning */
 int tts_hip_tune(tts_hip_ctx *ctx, const char *key, int value);

@@ -14,7 +14,11 @@ type the tree has runs in the same process, taking turns repetition by repetitio
   attn_self   PROF further steps of the same sessions under tts_hip_profile (eager, every launch between events): ms per step in the self-attention
               launches and the K/V bytes they are asked to read
 
-There is no sweep over keys in flight: an e4m3 cache is read by attn_kernel at every row count (no row-major reader over e4m3 rows).
+The e4m3 cache runs twice: "e4m3" with the row-major reader attn_rows_f8_kernel (tune "attn_rows_f8_min" at its default, 256 rows) and "e4m3_attn_kernel"
+with attn_rows_f8_min = 0 (attn_kernel at every row count, what the parent of the reader ran); a tree without a key skips the legs that name it.  256 slots
+is the reader's four-slice form, 8 slots never reach it.  --extra NAME=key:value,... adds a context with further tune keys to the turns (the sweep over the
+reader's keys in flight was run that way on a build that held three instantiations); --kinds restricts the turns.  profiles/parler_kv_f8_rows.json
+/ parler_kv_f8_rows_parent_before.json are this file's output at --slots 1023,256,8.
 Every figure is the list of its repetitions with its median and max - min."""
 import argparse
 import json
@@ -26,7 +30,7 @@ import numpy as np
 
 WARM, STEPS, PROF = 8, 16, 4
 LEGS = (("short", 16), ("long", 200))
-SLOTS = (1023, 8)
+SLOTS = (1023, 256, 8)
 
 
 def stat(v):
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--slots", default=",".join(str(s) for s in SLOTS))
+    ap.add_argument("--kinds", default="", help="comma list of the contexts that run (default: all)")
+    ap.add_argument("--extra", action="append", default=[], help="NAME=key:value,key:value: one more context, with these tune keys")
     args = ap.parse_args()
     root = os.getcwd()
     sys.path.insert(0, root)
@@ -49,7 +55,13 @@ def main():
     kvpos = max(p for _, p in LEGS) + total + 8
     cfg = synth.parler_mini(weight_type=gguf.F16, max_gen=kvpos)
     model = synth.build(cfg)
-    how = {"f32": dict(kv_type=gguf.F32), "f16": dict(kv_type=gguf.F16), "e4m3": dict(kv_type=gguf.F32, tune={"kv_f8": 1})}
+    how = {"f32": dict(kv_type=gguf.F32), "f16": dict(kv_type=gguf.F16), "e4m3": dict(kv_type=gguf.F32, tune={"kv_f8": 1}),
+           "e4m3_attn_kernel": dict(kv_type=gguf.F32, tune={"kv_f8": 1, "attn_rows_f8_min": 0})}
+    for x in args.extra:
+        name, keys = x.split("=", 1)
+        how[name] = dict(kv_type=gguf.F32, tune={k: int(v) for k, v in (kv.split(":") for kv in keys.split(","))})
+    if args.kinds:
+        how = {k: how[k] for k in args.kinds.split(",")}
     res = {"shapes": "synthetic Parler-Mini (24 x 1024, 16 heads, ffn 4096, 9 x 1088 logits), fp16 matrices, no codec, %d cached positions" % kvpos,
            "warm_steps": WARM, "timed_steps": STEPS, "profiled_steps": PROF, "reps": reps, "step_ms": {}, "attn_self_ms_per_step": {}, "attn_self_kv_bytes_per_step": {}}
     rng = np.random.default_rng(3)
@@ -59,7 +71,7 @@ def main():
             try:
                 eng = hip.HipEngine(cfg, max_seqs=slots + 1, kv_positions=kvpos, flags=hip.FLAG_NO_DAC, **kw)
             except hip.HipError:      # a tree without the key
-                assert kind == "e4m3"
+                assert "tune" in kw, kind
                 continue
             eng.load(model)
             engs[kind] = eng

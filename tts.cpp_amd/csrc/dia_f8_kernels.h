@@ -27,8 +27,6 @@
 
 #include "dia_cross_kernels.h"   // PadVec, dia_cross_padsum_kernel; llama_kernels.h: QPre, ATTN_PART
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of an e4m3 row: 16 elements, element e in byte e
-
 // the pad-sum's 16 bytes per lane over e4m3: 16 columns in one load, widened exactly; dia_cross_padsum_kernel<kv_f8> keeps the stretches, the request order
 // and the sum order of the other two types (A is a multiple of 128, so of 16)
 template <> struct PadVec<kv_f8> {

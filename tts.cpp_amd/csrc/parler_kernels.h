@@ -962,22 +962,10 @@ __device__ __forceinline__ void attn_row_pass(const AttnArgs &a, int64_t hb, flo
         }
     }
 }
-template <int U>
-__global__ __launch_bounds__(1024) void attn_rows_kernel(AttnArgs a) {
-    const int r = blockIdx.x, z = blockIdx.y, nz = gridDim.y, tid = threadIdx.x;
-    const int h = tid >> 4, cl = tid & 15;
-    const int T = (int) a.row_pos[r] + 1;
-    const int64_t sb = (int64_t) a.row_seq[r] * a.seq_stride;
-    const int chunk = (T + nz - 1) / nz;
-    const int t0 = z * chunk, t1 = min(T, t0 + chunk);
-    const int64_t hb = sb + tid * 4;                        // head h = tid / 16, channels 4 (tid % 16) .. + 3 of it: element tid * 4 of the row
-    const float4v q4 = *(const float4v *) (a.q + (int64_t) r * a.H + tid * 4);
-    float m = -INFINITY, l = 0.0f;
-    float4v acc = {0.f, 0.f, 0.f, 0.f};
-    if (t0 < t1) {
-        if (a.kv_f16) attn_row_pass<true, U>(a, hb, q4, t0, t1, m, l, acc);
-        else attn_row_pass<false, U>(a, hb, q4, t0, t1, m, l, acc);
-    }
+// The tail of a row-major self-attention workgroup (attn_rows_kernel, attn_rows_f8_kernel): thread tid holds channels 4 tid .. + 3 of row r (head tid / 16) as
+// the running max m, sum l and unnormalised output acc over the keys of slice z.  One slice: the row leaves as `out`, `out16` or its Q8_0 blocks; several:
+// the partial attn_combine_kernel reads.  Every thread tid < H / 4 of the workgroup calls it (quant4_q8 pairs eight neighbouring threads).
+__device__ __forceinline__ void attn_rows_store(const AttnArgs &a, int r, int z, int nz, int tid, float m, float l, float4v acc) {
     if (nz == 1) {
         const float inv = 1.0f / l;
         if (a.out16) {
@@ -999,10 +987,115 @@ __global__ __launch_bounds__(1024) void attn_rows_kernel(AttnArgs a) {
             }
         }
     } else {   // read by attn_combine_kernel: max (-inf: an empty slice), sum, unnormalised out[64] of this slice
+        const int h = tid >> 4, cl = tid & 15;
         float *p = a.part + (((int64_t) r * a.n_heads + h) * nz + z) * ATT_PS;
         if (cl == 0) { p[0] = m; p[1] = l; }
         *(float4v *) (p + ATT_PO + cl * 4) = acc;
     }
+}
+template <int U>
+__global__ __launch_bounds__(1024) void attn_rows_kernel(AttnArgs a) {
+    const int r = blockIdx.x, z = blockIdx.y, nz = gridDim.y, tid = threadIdx.x;
+    const int T = (int) a.row_pos[r] + 1;
+    const int64_t sb = (int64_t) a.row_seq[r] * a.seq_stride;
+    const int chunk = (T + nz - 1) / nz;
+    const int t0 = z * chunk, t1 = min(T, t0 + chunk);
+    const int64_t hb = sb + tid * 4;                        // head h = tid / 16, channels 4 (tid % 16) .. + 3 of it: element tid * 4 of the row
+    const float4v q4 = *(const float4v *) (a.q + (int64_t) r * a.H + tid * 4);
+    float m = -INFINITY, l = 0.0f;
+    float4v acc = {0.f, 0.f, 0.f, 0.f};
+    if (t0 < t1) {
+        if (a.kv_f16) attn_row_pass<true, U>(a, hb, q4, t0, t1, m, l, acc);
+        else attn_row_pass<false, U>(a, hb, q4, t0, t1, m, l, acc);
+    }
+    attn_rows_store(a, r, z, nz, tid, m, l, acc);
+}
+
+// The row-major reader over a one-byte e4m3 cache (tts_hip_tune "kv_f8"; run_attn, tune("attn_rows_f8_min")).  attn_row_pass gives a lane four channels, which
+// over e4m3 is a 4-byte load per lane and key; here a lane owns 16 consecutive channels of one head — one 16-byte non-temporal load of K and one of V per key —
+// so four lanes make a head of 64 and LR = H / 16 lanes one whole key row.  One workgroup of 256 threads per row (blockIdx.y: the key slice, as above) holds
+// NKL = 256 / LR key lanes: Parler-Mini (H = 1024) LR = 64, every wave one key lane whose load instruction reads one key's contiguous 1 KB row; H = 256: 16 key
+// lanes, four per wave.  Key lane kl takes keys t0 + kl, t0 + kl + NKL, ... of its slice, U of them requested before the first is folded (a key beyond the
+// slice re-reads the slice's last key and is never used).  The bytes stay packed, 4 + 4 registers per key in flight, and are widened (kv_f8_widen4, exact)
+// where the key is consumed.  Score: 16 FMAs per lane and two quad steps (DPP) over the head's four lanes; every lane keeps its key lane's running max / sum
+// of its head and 16 fp32 accumulators, all arithmetic fp32.  The key lanes merge through LDS once, at the end of the slice: thread t < H / 4 folds channels
+// 4 t .. + 3 over the key lanes in key-lane order (attn_combine_kernel's arithmetic, m = -inf: a key lane that held no key) and then holds what thread t of
+// attn_rows_kernel holds at its tail: attn_rows_store.  LDS: NKL (H + 2 n_heads) floats = 4096 + 128 whatever H is (NKL H = 4096, NKL n_heads = 64).
+// The host checks H = 64 n_heads, H <= 1024 and H / 16 a power of two.
+template <int U>
+__global__ __launch_bounds__(256) void attn_rows_f8_kernel(AttnArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[4096 + 128];   // [NKL][H] acc, [NKL][n_heads] max, [NKL][n_heads] sum
+    float *rm = red + 4096, *rl = rm + 64;
+    const int r = blockIdx.x, z = blockIdx.y, nz = gridDim.y, tid = threadIdx.x;
+    const int lrs = __builtin_ctz(a.H >> 4), NKL = 256 >> lrs;       // LR = 1 << lrs lanes per key row
+    const int kl = tid >> lrs, c16 = (tid & ((1 << lrs) - 1)) * 16;  // key lane; first channel of the lane (head c16 / 64)
+    const int T = (int) a.row_pos[r] + 1;
+    const int64_t sb = (int64_t) a.row_seq[r] * a.seq_stride;
+    const int chunk = (T + nz - 1) / nz;
+    const int t0 = z * chunk, t1 = min(T, t0 + chunk);
+    const uint8_t *kp = (const uint8_t *) a.kc + sb + c16, *vp = (const uint8_t *) a.vc + sb + c16;
+    float4v q[4], acc[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        q[w] = *(const float4v *) (a.q + (int64_t) r * a.H + c16 + 4 * w);
+        acc[w] = (float4v){0.f, 0.f, 0.f, 0.f};
+    }
+    float m = -INFINITY, l = 0.0f;
+    for (int t = t0 + kl; t < t1; t += NKL * U) {
+        u32x4 kr[U], vr[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {   // straight-line, as attn_row_pass
+            const int64_t off = (int64_t) min(t + u * NKL, t1 - 1) * a.H;
+            kr[u] = __builtin_nontemporal_load((const u32x4 *) (kp + off));
+            vr[u] = __builtin_nontemporal_load((const u32x4 *) (vp + off));
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (t + u * NKL < t1) {
+                float d = 0.0f;
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    const float4v k4 = kv_f8_widen4(kr[u][w]);
+                    d += q[w][0] * k4[0] + q[w][1] * k4[1] + q[w][2] * k4[2] + q[w][3] * k4[3];
+                }
+                d += dpp_f<0xB1>(d); d += dpp_f<0x4E>(d);   // the head's four lanes: xor 1, xor 2 (quad_perm); a key lane is whole quads
+                d *= a.scale;  // soft_max_ext(kq, mask, 1/sqrt(d), 0)
+                const float mn = fmaxf(m, d);
+                const float f = expf(m - mn);   // 0 on the first key (m = -inf)
+                const float p = expf(d - mn);
+                l = l * f + p;
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    const float4v v4 = kv_f8_widen4(vr[u][w]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) acc[w][e] = acc[w][e] * f + p * v4[e];
+                }
+                m = mn;
+            }
+        }
+    }
+    // merge the key lanes
+#pragma unroll
+    for (int w = 0; w < 4; w++) *(float4v *) (red + kl * a.H + c16 + 4 * w) = acc[w];
+    if ((tid & 3) == 0) { rm[kl * a.n_heads + (c16 >> 6)] = m; rl[kl * a.n_heads + (c16 >> 6)] = l; }
+    __syncthreads();
+    if (tid >= (a.H >> 2)) return;
+    const int h = tid >> 4;
+    float mx = -INFINITY;
+    for (int i = 0; i < NKL; i++) mx = fmaxf(mx, rm[i * a.n_heads + h]);
+    float4v o = {0.f, 0.f, 0.f, 0.f};
+    float s = 0.0f;
+    for (int i = 0; i < NKL; i++) {
+        const float mi = rm[i * a.n_heads + h];
+        if (mi != -INFINITY) {
+            const float f = expf(mi - mx);
+            const float4v oi = *(const float4v *) (red + i * a.H + tid * 4);
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[e] += f * oi[e];
+            s += f * rl[i * a.n_heads + h];
+        }
+    }
+    attn_rows_store(a, r, z, nz, tid, mx, s, o);
 }
 
 // Cross-attention over a short voice prompt (T_fixed <= 32 encoder positions; Parler-Mini: 8..40): the general kernel

@@ -178,6 +178,7 @@ extern "C" int tts_hip_tune(tts_hip_ctx *c, const char *key, int v) {
     else if (k == "ln_fuse_max") c->ln_fuse_max = std::max(0, std::min(32, v));
     else if (k == "attn_short") c->attn_short = v != 0;
     else if (k == "attn_rows_min") c->attn_rows_min = std::max(0, v);
+    else if (k == "attn_rows_f8_min") c->attn_rows_f8_min = std::max(0, v);   // e4m3 cache: row count from which attn_rows_f8_kernel reads it (and attn_rows_min); 0: never
     else if (k == "attn_rows_u") {   // the instantiations run_attn holds
         if (v != 2 && v != 4 && v != 8) return set_err("tts_hip_tune: attn_rows_u is 2, 4 or 8 (got %d)", v);
         c->attn_rows_u = v;

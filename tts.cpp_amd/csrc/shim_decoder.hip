@@ -795,8 +795,12 @@ static int run_attn(tts_hip_ctx *c, int kclass, AttnArgs a, int R, int nsplit, d
         HIPCHK(hipGetLastError());
         return prof_end(c);
     }
-    // (an e4m3 cache, tune("kv_f8"), has no row-major reader: every row count runs attn_kernel's e4m3 key pass below)
-    if (nsplit == 1 && a.row_pos && a.row_seq && c->attn_rows_min > 0 && R >= c->attn_rows_min && c->NH * 16 <= 1024 && c->H == c->NH * 64 && a.kv_f16 != KV_E4M3) {
+    // an e4m3 cache, tune("kv_f8"), has a row-major reader of its own mapping (attn_rows_f8_kernel: 16 channels per lane, 256 threads per row) behind a
+    // threshold of its own, tune("attn_rows_f8_min"): 0, a row count below either threshold, or a head layout it does not hold keeps attn_kernel's e4m3 key pass
+    const bool rows = nsplit == 1 && a.row_pos && a.row_seq && c->attn_rows_min > 0 && R >= c->attn_rows_min && c->H == c->NH * 64;
+    const int lr = c->H / 16;   // lanes per key row of the e4m3 reader
+    const bool rows_f8 = rows && a.kv_f16 == KV_E4M3 && c->attn_rows_f8_min > 0 && R >= c->attn_rows_f8_min && c->H <= 1024 && (lr & (lr - 1)) == 0;
+    if (rows_f8 || (rows && c->NH * 16 <= 1024 && a.kv_f16 != KV_E4M3)) {
         // many rows: one workgroup per row reads whole K / V rows (attn_rows_kernel); below 1024 rows the keys of a row are cut into FOUR slices
         // (about a thousand workgroups again) that attn_combine_kernel folds — a fixed count per row-count class, so that a generation whose rows
         // are compacted from 384 to 256 keeps its summation order
@@ -809,7 +813,10 @@ static int run_attn(tts_hip_ctx *c, int kclass, AttnArgs a, int R, int nsplit, d
         // off every SIMD that another context's fused residual units occupy; 2 keys = 32 registers fit beside every codec kernel and
         // are also the fastest alone, at short and at long histories (profiles/attn_beside_codec.txt)
         auto *rows_kernel = c->attn_rows_u == 2 ? attn_rows_kernel<2> : c->attn_rows_u == 4 ? attn_rows_kernel<4> : attn_rows_kernel<8>;
-        hipLaunchKernelGGL(rows_kernel, dim3(R, nzr), dim3(c->NH * 16), 0, c->stream, a);
+        // attn_rows_f8_kernel: 2 keys in flight per key lane, 72 registers (2 / 4 / 8 measured: 0.790 / 0.839 / 0.893 ms of attn_self per 1024-row step at
+        // positions 24.., 2.19 / 2.24 / 2.25 at 208.., the same order in every timed stretch; profiles/parler_kv_f8_rows_u_sweep.json)
+        if (rows_f8) hipLaunchKernelGGL(attn_rows_f8_kernel<2>, dim3(R, nzr), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(rows_kernel, dim3(R, nzr), dim3(c->NH * 16), 0, c->stream, a);
         HIPCHK(hipGetLastError());
         if (nzr > 1) {
             hipLaunchKernelGGL(attn_combine_kernel, dim3(c->NH, R), dim3(64), 0, c->stream, (const float *) a.part, nzr, c->H, c->NH, a.out, a.out16, a.out_q, a.out_dT, a.ldr);

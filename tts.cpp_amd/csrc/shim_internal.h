@@ -460,6 +460,7 @@ struct tts_hip_ctx {
     int dac_group = 64;         // TTS_HIP_DAC_GROUP: utterances per codec pass (16: 451, 32: 458, 64: 461, 128: 460, 384: 462 audio-s/s at 3 x 384)
     bool dac_conv1_direct = true;   // tune("dac_conv1_direct")=0: the 96- / 192-channel k=1 convs stay on conv1d_mfma_kernel<1,...>
     int attn_rows_min = 256;    // tune("attn_rows_min") / TTS_HIP_ATTN_ROWS: forwards with at least this many rows run the self-attention one workgroup per ROW (attn_rows_kernel); 0 = never
+    int attn_rows_f8_min = 256; // tune("attn_rows_f8_min"): over an e4m3 cache (kv_f8), forwards with at least max(attn_rows_min, this) rows run attn_rows_f8_kernel (16 channels per lane, 256 threads per row); 0 = attn_kernel's e4m3 key pass at every row count
     int attn_rows_u = 2;        // tune("attn_rows_u") / TTS_HIP_ATTN_ROWS_U: keys in flight per lane of attn_rows_kernel, 2 / 4 / 8 = 32 / 48 / 80 VGPRs; same arithmetic in the same key order.  2: a wave fits beside every codec kernel of another context (measured in profiles/attn_beside_codec.txt)
     bool kv_f8 = false;         // tune("kv_f8")=1, before finalize (the cache is sized there), fp32 kv_type only: Parler's self-attention K/V cache as one-byte e4m3, rounded once as appended
     size_t kv_esz() const { return kv_f8 ? 1 : d.kv_type == TTS_HIP_F16 ? 2 : 4; }   // bytes per element of kcache / vcache

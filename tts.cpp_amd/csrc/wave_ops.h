@@ -69,6 +69,7 @@ struct kv_f8 {
     }
 };
 static_assert(sizeof(kv_f8) == 1, "a cache row of kv_f8 is one byte per element");
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of an e4m3 row: 16 elements, element e in byte e (the 16-byte-lane readers: dia_f8_kernels.h, attn_rows_f8_kernel)
 // four consecutive elements of a row as one word (element e in byte e): the same clamp and conversion, two v_cvt_pk_fp8_f32
 __device__ __forceinline__ uint32_t kv_f8_pack4(float4v v) {
     float c[4];
